@@ -7,7 +7,7 @@ resident in HBM:   16 kHz audio [64, 64000] -> HIP mel front-end -> spec [64,128
                    (spec, text, prior poses, emotion map) -> HIP generator -> pose [64,34,126] (+ the 4 auxiliary returns)
 This is BASELINE.json configs[1] ("Batch=64 synthetic 16 kHz audio -> gesture inference, 1xMI355X").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f32|bf16x3|bf16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f32|bf16x3|bf16] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1: one process per GPU, clips sharded across ranks (weak scaling: 64 clips per GPU), no collective on the data
@@ -174,7 +174,19 @@ def parse_args():
     ap.add_argument("--dp-train-batch", type=int, default=16,
                     help="clips per GPU per step of the data-parallel training leg that the default line carries at --gpus N > 1 (16 x 8 GPUs = global 128)")
     ap.add_argument("--train-batch", type=int, default=16, help="clips per GPU per training step (16 = global 128 on 8 GPUs, SURVEY.md §8d cfg 3)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: parity against the CPU oracle, FGD, the lanes' bitwise check, the sustained / f32 / "
+                         "fold_affine / b256 / one-clip / BEAT-long / diversity legs, the training legs, the roofline and the CPU baseline (the --no-* "
+                         "options above then switch single parts off); without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy (float32; rank 0's clips; "
+                         "a fixed, seeded sample of the clips when all of them would exceed 64 MB)")
+    args = ap.parse_args()
+    if args.train and args.dump_outputs:
+        ap.error("--dump-outputs writes the inference step's outputs; it does not apply to --train")
+    if not args.full:
+        args.no_extra_legs = args.no_roofline = args.no_cpu_baseline = args.no_train_legs = True
+    return args
 
 
 # ---- self-launch: `python bench.py --gpus N` without an outer torchrun ------------------------------------------------------
@@ -588,6 +600,23 @@ def _train_leg_body(dev, B, precision, graph, steps, warmup, rank, world, dist, 
     return out
 
 
+OUTPUT_NAMES = ("pose", "emo", "sem", "emo_pred", "text_embedding")      # the generator's 5-tuple, named as oracle.generator_forward names it
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, outs):
+    """The step's 5-tuple as float32 .npy files; past DUMP_LIMIT_BYTES in all, the same seeded sample of clips (rows of dim 0) from every array."""
+    arrs = [o.detach().float().cpu().numpy() for o in outs]
+    B = arrs[0].shape[0]
+    total = sum(a.nbytes for a in arrs)
+    if total > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(B, max(1, B * DUMP_LIMIT_BYTES // total), replace=False))
+        arrs = [a[keep] for a in arrs]
+    os.makedirs(path, exist_ok=True)
+    for name, a in zip(OUTPUT_NAMES, arrs):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def emit(line):
     """The ONE JSON line, as the LAST line of stdout: RCCL writes its version banner through libc's stdout buffer, which would otherwise be flushed
     behind Python's at exit."""
@@ -760,6 +789,8 @@ def main():
 
     step, pipe = make_runner(gen, lanes)
     elapsed, out = timed(step, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)        # before anything below replays a lane and overwrites its outputs
     total_clips = B * world * args.steps
     value = total_clips / elapsed
 
@@ -767,7 +798,7 @@ def main():
     launch_desc = "eager" if pipe is None else f"hipGraph replay, {lanes} step(s) in flight"
     # every lane ran the same resident batch: their outputs must agree bit for bit (catches any cross-lane interference)
     lanes_equal = None
-    if pipe is not None and lanes > 1:
+    if args.full and pipe is not None and lanes > 1:
         base = pipe.outputs(0)
         lanes_equal = all(torch.equal(a, b) for i in range(1, lanes) for a, b in zip(pipe.outputs(i), base))
         if not lanes_equal:
@@ -792,7 +823,7 @@ def main():
     cpu = None
     f32 = None
     pose_ref = None
-    if rank == 0:
+    if rank == 0 and args.full:
         from emotiongestures_amd.builders import clip_rel_l2
         from oracle import emogest_oracle as O
         with torch.no_grad():
@@ -801,7 +832,7 @@ def main():
             s_ref = O.cvae_sample(sd_v, tn["label"], tn["z"])
             pose_ref = O.generator_forward(sd_g, O.GenCfg(), spec_ref, tn["text"], tn["pre_pose"], s_ref)[0]
         parity = clip_rel_l2(out[0].cpu().numpy(), pose_ref.numpy())          # max over all B clips of the timed batch
-    if rank == 0 and B >= 32:
+    if rank == 0 and args.full and B >= 32:
         # Frechet distance between the FGD auto-encoder latents (model/FGD.py:26-82, HIP path, synthetic weights) of the GPU
         # poses and of the CPU oracle's poses for the same B clips (B x 34 feature rows)
         from emotiongestures_amd.harness import MLP_Reconstruct, calculate_frechet_distance
@@ -992,7 +1023,7 @@ def main():
                        "launch": launch_desc,
                        "branch_streams": timed_concurrent, "fold_affine": bool(getattr(gen, "fold_affine", False)),
                        "algorithmic_gflop_per_clip": round((FLOP_PER_CLIP + MEL_FLOP_PER_CLIP + CVAE_FLOP_PER_CLIP) / 1e9, 3)},
-            "pose_rel_l2_vs_cpu_oracle": parity, "parity_clips_checked": B, "fgd_vs_cpu_oracle": fgd,
+            "pose_rel_l2_vs_cpu_oracle": parity, "parity_clips_checked": None if parity is None else B, "fgd_vs_cpu_oracle": fgd,
             "lanes_bitwise_equal": lanes_equal, "sustained": sustained, "f32": f32, "extra_legs": extra, "train": train, "roofline": roof, "cpu_baseline": cpu,
         }
         if facts is not None:       # N > 1 (or EG_FORCE_COLLECTIVES): what the barrier / max-over-ranks really ran over

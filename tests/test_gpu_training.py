@@ -1738,7 +1738,7 @@ def test_bench_train_two_ranks_share_one_gpu_over_gloo(graph):
 
 
 def test_default_bench_line_at_two_ranks_carries_the_data_parallel_training_leg():
-    """Round-5 verdict item 3: `bench.py --gpus N` (the command the driver's scaling run uses) must measure BASELINE configs[2] too.  Two ranks on this
+    """Round-5 verdict item 3: `bench.py --gpus N --full` must measure BASELINE configs[2] too (a plain run times the headline only).  Two ranks on this
     box's one GPU over gloo: the inference headline (clip-sharded, no data-path collective), then every rank runs the SegmentedStep training leg with
     fp32 and with bf16 gradient payloads; the line carries both, per-rank step-time spread, the exposed all-reduce time and the collectives' facts;
     the process group is gone before rank 0's solo work (roofline), so no rank waits in a collective for it."""
@@ -1747,7 +1747,7 @@ def test_default_bench_line_at_two_ranks_carries_the_data_parallel_training_leg(
     env = dict(os.environ, EG_BENCH_BACKEND="gloo")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "EG_DIST_STORE"):
         env.pop(k, None)
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--batch", "4", "--steps", "4", "--warmup", "1", "--in-flight", "2", "--no-extra-legs",
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "2", "--batch", "4", "--steps", "4", "--warmup", "1", "--in-flight", "2", "--no-extra-legs",
            "--dp-train-batch", "2"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, (r.stderr[:2000], r.stderr[-2000:])

@@ -5,7 +5,7 @@ set -u
 TAG=${1:-r04}
 O=gpurun_out
 cd "$(dirname "$0")/.." && export TMPDIR=/tmp
-INF="python3 bench.py --no-cpu-baseline --no-extra-legs --no-train-legs"
+INF="python3 bench.py --full --no-cpu-baseline --no-extra-legs --no-train-legs"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_ks -- $INF > $O/${TAG}_ks.log 2>&1
 python3 tools/rocprof_summary.py $O/${TAG}_ks $O/${TAG}_kernel_stats_default_cmd.md
 export EG_BENCH_SHARED_CHIP=1       # the eager profiling passes use the GEMM tile policy of the timed 4-lane configuration
