@@ -6,6 +6,7 @@ Layout:
   modules                     host mirror of the reference's nn.Module surface
   Full_model/, CAVE/, model/, skeleton_classifer/   the reference's import paths (thin re-exports of ``modules`` / ``harness``)
   harness                     the eval loop around the generator: FGD features, Frechet/diversity, emotion classifier
+  beat                        beat-alignment score (HIP onset front-end + pose extrema + GAHR), drop-in ``alignment``
   synth                       platform-exact synthetic weights / inputs
   dist                        clip sharding across ranks (one process per GPU)
 """
@@ -14,12 +15,19 @@ from . import synth  # noqa: F401  (pure numpy; safe without the HIP library)
 __version__ = "0.1.0"
 
 
-def install_aliases() -> None:
+def install_aliases(beat_score: bool = False) -> None:
     """Make the reference's own import lines resolve to this package, e.g.
     ``from Full_model.Models_memory import Transformer`` and ``from CAVE.BEAT_CVAE import MLP_Reconstruct_v3``
-    (test_emotion_gesture_diversity_iterative.py:25-26)."""
+    (test_emotion_gesture_diversity_iterative.py:25-26).
+
+    ``beat_score=True`` (opt-in) also points ``model.Beat_score_v2`` at :mod:`emotiongestures_amd.beat`, whose ``alignment`` computes the
+    beat-alignment score (load_audio on the GPU).  Its audio half is restated from librosa 0.10's documented onset routines and is not
+    pinned against librosa itself, so the default keeps the refusing stub."""
     import importlib
     import sys
+
+    if beat_score:
+        sys.modules["model.Beat_score_v2"] = importlib.import_module(f"{__name__}.beat")
 
     for top in ("Full_model", "CAVE", "model", "skeleton_classifer", "data_loader", "utils"):
         pkg = importlib.import_module(f"{__name__}.{top}")

@@ -84,6 +84,9 @@ SIGNATURES = {
     "eg_mel_tables": (C.c_int, [_P, _P, _P, _P]),
     "eg_mel_workspace_bytes": (_L, [_I, _I]),
     "eg_melspectrogram": (C.c_int, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _L, _P]),
+    "eg_beat_tables": (C.c_int, [_P, _P, _P, _P]),
+    "eg_beat_workspace_bytes": (_L, [_I, _I]),
+    "eg_beat_align": (C.c_int, [_P, _I, _I, _P, _I, _I, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P]),
     "eg_conv3x3": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "eg_conv3x3_se": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "eg_se_gate_pre": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

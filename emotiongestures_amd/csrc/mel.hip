@@ -115,11 +115,13 @@ double mel_to_hz(double m) {
 
 }  // namespace
 
-// Host tables: Slaney mel filterbank TRANSPOSED [513][128], periodic Hann [1024], twiddles (cos, -sin) [512][2],
-// per-mel non-zero bin range [128][2] (begin, end).
-extern "C" int eg_mel_tables(float* h_melfb_t, float* h_window, float* h_twiddle, int32_t* h_band) {
-    EG_REQUIRE(h_melfb_t && h_window && h_twiddle && h_band, EG_ERR_BAD_ARG, "eg_mel_tables: null pointer");
-    const int n_mels = 128, n_bins = 513;
+namespace {
+
+// Slaney mel filterbank (librosa.filters.mel, sr 16 kHz, fmin 0, fmax sr/2, slaney norm) TRANSPOSED [n_fft/2+1][128], per-mel non-zero bin
+// range [128][2] (begin, end), periodic Hann [n_fft], twiddles (cos, -sin) [n_fft/2][2].  Shared by the n_fft 1024 spectrogram front-end and
+// the n_fft 2048 onset front-end of the beat score.
+void mel_tables_host(int n_fft, float* h_melfb_t, float* h_window, float* h_twiddle, int32_t* h_band) {
+    const int n_mels = 128, n_bins = n_fft / 2 + 1;
     const double sr = 16000.0;
     double hz[130];
     const double m_lo = hz_to_mel(0.0), m_hi = hz_to_mel(sr / 2);
@@ -141,11 +143,20 @@ extern "C" int eg_mel_tables(float* h_melfb_t, float* h_window, float* h_twiddle
         h_band[2 * m] = lo; h_band[2 * m + 1] = hi;
     }
     const double pi = 3.14159265358979323846;
-    for (int i = 0; i < 1024; ++i) h_window[i] = (float)(0.5 - 0.5 * cos(2.0 * pi * i / 1024.0));
-    for (int t = 0; t < 512; ++t) {
-        h_twiddle[2 * t] = (float)cos(2.0 * pi * t / 1024.0);
-        h_twiddle[2 * t + 1] = (float)(-sin(2.0 * pi * t / 1024.0));
+    for (int i = 0; i < n_fft; ++i) h_window[i] = (float)(0.5 - 0.5 * cos(2.0 * pi * i / n_fft));
+    for (int t = 0; t < n_fft / 2; ++t) {
+        h_twiddle[2 * t] = (float)cos(2.0 * pi * t / n_fft);
+        h_twiddle[2 * t + 1] = (float)(-sin(2.0 * pi * t / n_fft));
     }
+}
+
+}  // namespace
+
+// Host tables: Slaney mel filterbank TRANSPOSED [513][128], periodic Hann [1024], twiddles (cos, -sin) [512][2],
+// per-mel non-zero bin range [128][2] (begin, end).
+extern "C" int eg_mel_tables(float* h_melfb_t, float* h_window, float* h_twiddle, int32_t* h_band) {
+    EG_REQUIRE(h_melfb_t && h_window && h_twiddle && h_band, EG_ERR_BAD_ARG, "eg_mel_tables: null pointer");
+    mel_tables_host(1024, h_melfb_t, h_window, h_twiddle, h_band);
     return EG_OK;
 }
 
@@ -170,4 +181,335 @@ extern "C" int eg_melspectrogram(const float* audio, int32_t batch, int32_t n_sa
     if (rc) return rc;
     hipLaunchKernelGGL(mel_db_kernel, dim3(batch), dim3(1024), 0, st, melpow, spec, n_frames, out_frames);
     return eg_check_launch("mel_db");
+}
+
+// ==== Beat-alignment score (model/Beat_score_v2.py:51-197, alignment(sigma, order)) ===================================================
+// Audio half = alignment.load_audio restated from librosa 0.10's documented routines (librosa itself is not pinned against here):
+//   onset_strength(y, sr=16000): |STFT|^2 (n_fft 2048, hop 512, centred, zero pad, periodic Hann) -> 128 Slaney mels (fmax 8000)
+//     -> power_to_db(ref=1.0, amin 1e-10, top_db 80 below the CLIP max) -> mean over mels of max(0, db[t] - db[t-1]), left-padded by
+//     lag + n_fft/(2 hop) = 3 frames and trimmed to T = 1 + n/512;
+//   onset_detect(onset_envelope=oenv) with librosa's default sr 22050: x = (oenv - min) / (max + tiny), peak_pick(pre_max 1, post_max 1,
+//     pre_avg 4, post_avg 5, wait 1, delta 0.07);
+//   onset_backtrack(events, oenv) and onset_backtrack(events, rms) with rms = feature.rms(S=|X|) (DC and Nyquist bins halved).
+// Pose half = load_pose: velocity L2 norms of 8 joint groups (pose columns 18:42 and 150:174), beats = argrelextrema(np.less, order,
+// mode clip); the four right-side curves are sliced [t_start*fps : t_end*fps], the left ones are not (upstream quirk, kept).
+// Score = calculate_align: GAHR over 3 audio x 8 pose beat sets in fp64, audio beat times frame*512/22050 (librosa's default sr on 16 kHz
+// audio, upstream quirk, kept), pose beat times idx/fps.
+//
+// kernel 1 (beat_stft_kernel): one workgroup per (frame pair, clip); two real frames as one 2048-point complex radix-2 FFT in LDS (as
+//           mel_power_kernel), epilogue: the 128 mel powers as dB (banded Slaney filters) and the frame RMS; the spectrum stays in LDS.
+// kernel 2 (beat_align_kernel): one workgroup per clip: clip dB max, floor, flux -> oenv, normalisation, peak candidates (parallel), the
+//           wait-suppressed scan (one lane), both backtracks, pose velocity norms and extrema straight from [B, F, D], 24 GAHR terms.
+#define EG_BEAT_MAX_EVENTS (EG_BEAT_MAX_FRAMES / 2 + 1)
+
+namespace {
+
+__global__ __launch_bounds__(256) void beat_stft_kernel(const float* __restrict__ audio, int n_samples, const float* __restrict__ melfb_t,
+                                                        const float* __restrict__ window, const float* __restrict__ twiddle,
+                                                        const int* __restrict__ band, float* __restrict__ meldb, float* __restrict__ rms,
+                                                        int n_frames) {
+    __shared__ float re[2048], im[2048], tws[2048];
+    __shared__ float red[2][4];
+    const int f0 = blockIdx.x * 2, f1 = f0 + 1, b = blockIdx.y, tid = threadIdx.x;
+    const float* clip = audio + (size_t)b * n_samples;
+    int live = 0;                          // bit 0 / 1: frame f0 / f1 has a non-zero windowed sample
+    for (int i = tid; i < 2048; i += 256) {
+        const int s0 = f0 * 512 - 1024 + i, s1 = s0 + 512;
+        const float wv = window[i];
+        const int r = (int)(__brev((unsigned)i) >> 21);       // 11-bit reversal
+        const float a = (s0 >= 0 && s0 < n_samples) ? clip[s0] * wv : 0.f;
+        const float c = (f1 < n_frames && s1 >= 0 && s1 < n_samples) ? clip[s1] * wv : 0.f;
+        re[r] = a; im[r] = c;
+        live |= (a != 0.f) | ((c != 0.f) << 1);
+        tws[i] = twiddle[i];
+    }
+    // an all-zero frame keeps an exactly zero spectrum (librosa transforms each frame alone): without this the pairing's fp32 cross-talk
+    // from a loud partner frame gives a silent frame a tiny RMS and moves onset_backtrack's minima on it
+    const bool live0 = __syncthreads_or(live & 1), live1 = __syncthreads_or(live & 2);
+#pragma unroll 1
+    for (int s = 0; s < 11; ++s) {
+        const int half = 1 << s;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j = tid + u * 256;
+            const int pos = j & (half - 1), i0 = ((j >> s) << (s + 1)) + pos, i1 = i0 + half;
+            const int tw = pos << (10 - s);
+            const float c = tws[2 * tw], sn = tws[2 * tw + 1];             // exp(-2*pi*i*tw/2048) = c + i*sn
+            const float xr = re[i1], xi = im[i1];
+            const float tr = xr * c - xi * sn, ti = xr * sn + xi * c;
+            const float ar = re[i0], ai = im[i0];
+            re[i0] = ar + tr; im[i0] = ai + ti;
+            re[i1] = ar - tr; im[i1] = ai - ti;
+        }
+        __syncthreads();
+    }
+    // power spectra of the two frames, bins 0..1024: thread tid takes k = tid + 256 u (and 1024 on thread 0)
+    float pa[5], pb[5];
+    float ra = 0.f, rb = 0.f;             // RMS partial sums, fixed order (k ascending per thread, then a fixed tree)
+#pragma unroll
+    for (int u = 0; u < 5; ++u) {
+        const int k = u < 4 ? tid + u * 256 : 1024, nk = (2048 - k) & 2047;
+        pa[u] = pb[u] = 0.f;
+        if (u < 4 || tid == 0) {
+            const float zr = re[k], zi = im[k], yr = re[nk], yi = im[nk];
+            const float r0 = 0.5f * (zr + yr), i0 = 0.5f * (zi - yi);      // X0[k]
+            const float r1 = 0.5f * (zi + yi), i1 = 0.5f * (yr - zr);      // X1[k]
+            pa[u] = live0 ? r0 * r0 + i0 * i0 : 0.f;
+            pb[u] = live1 ? r1 * r1 + i1 * i1 : 0.f;
+            const float h = (k == 0 || k == 1024) ? 0.5f : 1.f;            // feature.rms(S=...): DC and Nyquist halved
+            ra += h * pa[u];
+            rb += h * pb[u];
+        }
+    }
+    ra = wave_sum(ra);
+    rb = wave_sum(rb);
+    if ((tid & 63) == 0) { red[0][tid >> 6] = ra; red[1][tid >> 6] = rb; }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { re[tid + u * 256] = pa[u]; im[tid + u * 256] = pb[u]; }
+    if (tid == 0) { re[1024] = pa[4]; im[1024] = pb[4]; }
+    if (tid < 2) {
+        const int f = f0 + tid;
+        const float s = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+        if (f < n_frames) rms[(size_t)b * n_frames + f] = sqrtf(2.f * s / 4194304.f);      // 2 sum / n_fft^2
+    }
+    __syncthreads();
+    // mel projection over the banded filters, thread (m = tid & 127, frame = tid >> 7); stored as power_to_db(ref=1.0) before the floor
+    const int m = tid & 127, fr = tid >> 7, f = f0 + fr;
+    const float* pw = fr ? im : re;
+    const int b0 = band[2 * m], b1 = band[2 * m + 1];
+    float s = 0.f;
+    for (int k = b0; k < b1; ++k) s += melfb_t[k * 128 + m] * pw[k];
+    if (f < n_frames) meldb[((size_t)b * 128 + m) * n_frames + f] = 10.f * log10f(fmaxf(1e-10f, s));
+}
+
+// fp64 GAHR (Beat_score_v2.py:159-171) of one (audio set, pose set): mean over audio beats of exp(-d^2 / (2 sigma^2)), d = distance to the
+// nearest pose beat (both lists ascending: the nearest is one of the two pose beats around the audio beat; |p - a| is monotone in p, so this
+// is the same minimum upstream's double loop finds).  An empty pose set gives d = inf -> 0.
+__device__ double gahr(const short* __restrict__ ev, int n_ev, const short* __restrict__ pb, int n_pb, int fps, double sigma) {
+    double acc = 0.0;
+    int j = 0;
+    for (int i = 0; i < n_ev; ++i) {
+        const double a = (double)(ev[i] * 512) / 22050.0;
+        while (j < n_pb && (double)pb[j] / (double)fps < a) ++j;
+        double d = INFINITY;
+        if (j < n_pb) d = fmin(d, fabs((double)pb[j] / (double)fps - a));
+        if (j > 0) d = fmin(d, fabs((double)pb[j - 1] / (double)fps - a));
+        acc += exp(-(d * d) / (2.0 * (sigma * sigma)));
+    }
+    return acc / (double)n_ev;
+}
+
+__global__ __launch_bounds__(256) void beat_align_kernel(const float* __restrict__ meldb, const float* __restrict__ rms_ws, int n_frames,
+                                                         const float* __restrict__ pose, int pose_frames, int pose_dim, int fps, int r_lo,
+                                                         int r_hi, double sigma, int order, double* __restrict__ score,
+                                                         int* __restrict__ n_audio_beats, float* __restrict__ oenv_out,
+                                                         float* __restrict__ rms_out, uint8_t* __restrict__ audio_mask,
+                                                         uint8_t* __restrict__ pose_mask) {
+    __shared__ float oenv[EG_BEAT_MAX_FRAMES], x[EG_BEAT_MAX_FRAMES], rms[EG_BEAT_MAX_FRAMES];
+    __shared__ uint8_t fl[3][EG_BEAT_MAX_FRAMES];          // peak candidates, oenv minima, rms minima; then the three beat counts
+    uint8_t* cand = fl[0];
+    uint8_t* min_o = fl[1];
+    uint8_t* min_r = fl[2];
+    __shared__ short ev[3][EG_BEAT_MAX_EVENTS];
+    __shared__ float vel[8][EG_BEAT_MAX_FRAMES];
+    __shared__ short pbeat[8][EG_BEAT_MAX_EVENTS];
+    __shared__ int n_pb[8];
+    __shared__ float redf[2][4];
+    __shared__ int n_ev_s, any_s;
+    __shared__ double g24[24];
+    const int b = blockIdx.x, tid = threadIdx.x, T = n_frames;
+    const float* db = meldb + (size_t)b * 128 * T;
+
+    // ---- onset envelope: clip dB max -> floor, flux, mean over the 128 bands (fixed order)
+    float mx = -INFINITY;
+    for (int i = tid; i < 128 * T; i += 256) mx = fmaxf(mx, db[i]);
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) redf[0][tid >> 6] = mx;
+    __syncthreads();
+    const float floor_db = fmaxf(fmaxf(redf[0][0], redf[0][1]), fmaxf(redf[0][2], redf[0][3])) - 80.f;
+    for (int t = tid; t < T; t += 256) {
+        float s = 0.f;
+        if (t >= 3)
+#pragma unroll 8
+            for (int m = 0; m < 128; ++m) {
+                const float cur = fmaxf(db[m * T + t - 2], floor_db), prev = fmaxf(db[m * T + t - 3], floor_db);
+                s += fmaxf(0.f, cur - prev);
+            }
+        oenv[t] = s / 128.f;
+        rms[t] = rms_ws[(size_t)b * T + t];
+    }
+    __syncthreads();
+    // ---- onset_detect normalisation: x = (oenv - min) / (max(oenv - min) + tiny(float32))
+    float lo = INFINITY, hi = -INFINITY;
+    for (int t = tid; t < T; t += 256) { lo = fminf(lo, oenv[t]); hi = fmaxf(hi, oenv[t]); }
+    lo = -wave_max(-lo);
+    hi = wave_max(hi);
+    if ((tid & 63) == 0) { redf[0][tid >> 6] = lo; redf[1][tid >> 6] = hi; }
+    if (tid == 0) any_s = 0;
+    __syncthreads();
+    lo = fminf(fminf(redf[0][0], redf[0][1]), fminf(redf[0][2], redf[0][3]));
+    hi = fmaxf(fmaxf(redf[1][0], redf[1][1]), fmaxf(redf[1][2], redf[1][3]));
+    const float den = (hi - lo) + 1.17549435e-38f;
+    int bad = 0, nz = 0;
+    for (int t = tid; t < T; t += 256) {
+        const float v = (oenv[t] - lo) / den;
+        x[t] = v;
+        bad |= !isfinite(v);
+        nz |= v != 0.f;
+    }
+    if (bad) atomicOr(&any_s, 2);           // flags only (order-free): 1 = some x != 0, 2 = a non-finite x
+    if (nz) atomicOr(&any_s, 1);
+    __syncthreads();
+    const bool detect = any_s == 1;
+    // peak candidates: x[n] == max(x[n-1 : n+1]) and x[n] >= mean(x[n-4 : n+5]) + delta (windows clipped to the clip); fp32, fixed order
+    for (int t = tid; t < T; t += 256) {
+        const float v = x[t];
+        const bool is_max = t == 0 || v >= x[t - 1];
+        const int a0 = t - 4 < 0 ? 0 : t - 4, a1 = t + 5 > T ? T : t + 5;
+        float s = 0.f;
+        for (int i = a0; i < a1; ++i) s += x[i];
+        // peak_pick's numba loop: fp32 running sum, mean and threshold in fp64 with delta cast to fp32 (its guvectorize signature)
+        cand[t] = detect && is_max && (double)v >= (double)s / (double)(a1 - a0) + (double)0.07f;
+        // onset_backtrack minima (frame 0 always): e[i] <= e[i-1] and e[i] < e[i+1]
+        min_o[t] = t == 0 || (t < T - 1 && oenv[t] <= oenv[t - 1] && oenv[t] < oenv[t + 1]);
+        min_r[t] = t == 0 || (t < T - 1 && rms[t] <= rms[t - 1] && rms[t] < rms[t + 1]);
+    }
+    __syncthreads();
+    if (tid == 0) {                         // wait = 1: after an accepted peak the next frame is skipped
+        int n = 0, c = 0;
+        while (n < T) {
+            if (cand[n]) { ev[0][c++] = (short)n; n += 2; } else ++n;
+        }
+        n_ev_s = c;
+    }
+    __syncthreads();
+    const int n_ev = n_ev_s;
+    for (int i = tid; i < n_ev; i += 256) {       // backtrack: the largest minimum <= the event
+        int j = ev[0][i];
+        while (!min_o[j]) --j;
+        ev[1][i] = (short)j;
+        j = ev[0][i];
+        while (!min_r[j]) --j;
+        ev[2][i] = (short)j;
+    }
+    if (n_audio_beats && tid == 0) n_audio_beats[b] = n_ev;
+    for (int t = tid; t < T; t += 256) {
+        if (oenv_out) oenv_out[(size_t)b * T + t] = oenv[t];
+        if (rms_out) rms_out[(size_t)b * T + t] = rms[t];
+    }
+    __syncthreads();
+    if (audio_mask) {                       // onset_raw as 0/1; the backtracked sets as multiplicities (two events can share a minimum)
+        for (int t = tid; t < T; t += 256) fl[0][t] = fl[1][t] = fl[2][t] = 0;      // free once the backtracks above are done
+        __syncthreads();
+        if (tid < 3)
+            for (int i = 0; i < n_ev; ++i) {
+                const int f = ev[tid][i];
+                fl[tid][f] = (uint8_t)min(255, fl[tid][f] + 1);
+            }
+        __syncthreads();
+        uint8_t* am = audio_mask + (size_t)b * 3 * T;
+        for (int t = tid; t < T; t += 256) { am[t] = fl[0][t]; am[T + t] = fl[1][t]; am[2 * T + t] = fl[2][t]; }
+    }
+    if (!pose) return;
+
+    // ---- pose half: vel = p[t+1] - p[t] on columns 18:42 ++ 150:174, per-group L2 norm summed in numpy's order (no FMA contraction)
+    const int L = pose_frames - 1;
+    const float* pp = pose + (size_t)b * pose_frames * pose_dim;
+    for (int i = tid; i < 8 * L; i += 256) {
+        const int g = i / L, t = i - g * L;          // g = vel column group 0..7 (right shoulder, arm, fore arm, wrist, left ...)
+        const int c0 = g < 4 ? 18 + 6 * g : 150 + 6 * (g - 4);
+        const float* r0 = pp + (size_t)t * pose_dim + c0;
+        const float* r1 = r0 + pose_dim;
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            const float d = __fsub_rn(r1[c], r0[c]);
+            s = c == 0 ? __fmul_rn(d, d) : __fadd_rn(s, __fmul_rn(d, d));
+        }
+        vel[g][t] = __fsqrt_rn(s);
+    }
+    __syncthreads();
+    // argrelextrema(np.less, order, mode='clip') per returned set q (upstream order: right arm, shoulder, fore arm, wrist, left arm, ...);
+    // lane q compacts its own set, so each list is ascending
+    if (tid < 8) {
+        const int q = tid;
+        const int g = q == 0 ? 1 : q == 1 ? 0 : q == 4 ? 5 : q == 5 ? 4 : q;
+        const int s0 = q < 4 ? min(r_lo, L) : 0, s1 = q < 4 ? min(r_hi, L) : L;
+        const int len = s1 > s0 ? s1 - s0 : 0;
+        const float* c = &vel[g][s0];
+        int cnt = 0;
+        for (int i = 0; i < len; ++i) {
+            bool ok = true;
+            for (int k = 1; k <= order && ok; ++k) {
+                const int ip = i + k < len ? i + k : len - 1, im_ = i - k > 0 ? i - k : 0;
+                ok = c[i] < c[ip] && c[i] < c[im_];
+            }
+            if (ok) pbeat[q][cnt++] = (short)i;
+        }
+        n_pb[q] = cnt;
+        if (pose_mask) {
+            uint8_t* pm = pose_mask + ((size_t)b * 8 + q) * L;
+            for (int i = 0; i < L; ++i) pm[i] = 0;
+            for (int i = 0; i < cnt; ++i) pm[pbeat[q][i]] = 1;
+        }
+    }
+    __syncthreads();
+    // ---- calculate_align: 24 GAHR terms (audio set major), summed in upstream's order, / 24
+    if (tid < 24 && n_ev > 0) g24[tid] = gahr(ev[tid / 8], n_ev, pbeat[tid % 8], n_pb[tid % 8], fps, sigma);
+    __syncthreads();
+    if (tid == 0) {
+        double acc = 0.0;
+        for (int i = 0; i < 24; ++i) acc += g24[i];
+        score[b] = n_ev > 0 ? acc / 24.0 : (double)NAN;
+    }
+}
+
+}  // namespace
+
+// Host tables of the onset front-end: Slaney filterbank TRANSPOSED [1025][128], periodic Hann [2048], twiddles (cos, -sin) [1024][2],
+// per-mel non-zero bin range [128][2].
+extern "C" int eg_beat_tables(float* h_melfb_t, float* h_window, float* h_twiddle, int32_t* h_band) {
+    EG_REQUIRE(h_melfb_t && h_window && h_twiddle && h_band, EG_ERR_BAD_ARG, "eg_beat_tables: null pointer");
+    mel_tables_host(2048, h_melfb_t, h_window, h_twiddle, h_band);
+    return EG_OK;
+}
+
+extern "C" int64_t eg_beat_workspace_bytes(int32_t batch, int32_t n_samples) {
+    const int n_frames = 1 + n_samples / 512;
+    return (int64_t)batch * 129 * n_frames * (int64_t)sizeof(float);      // mel dB [B,128,T] + rms [B,T]
+}
+
+extern "C" int eg_beat_align(const float* audio, int32_t batch, int32_t n_samples, const float* pose, int32_t frames, int32_t pose_dim,
+                             int32_t pose_fps, int32_t t_start, int32_t t_end, double sigma, int32_t order, const float* d_melfb_t,
+                             const float* d_window, const float* d_twiddle, const int32_t* d_band, void* workspace, int64_t workspace_bytes,
+                             double* score, int32_t* n_audio_beats, float* oenv, float* rms, uint8_t* audio_beats, uint8_t* pose_beats,
+                             void* stream) {
+    EG_REQUIRE(audio && d_melfb_t && d_window && d_twiddle && d_band && workspace, EG_ERR_BAD_ARG, "eg_beat_align: null pointer");
+    EG_REQUIRE(batch > 0 && n_samples >= 2048, EG_ERR_BAD_ARG, "eg_beat_align: batch=%d n_samples=%d (needs >= 2048)", batch, n_samples);
+    const int n_frames = 1 + n_samples / 512;
+    EG_REQUIRE(n_frames <= EG_BEAT_MAX_FRAMES, EG_ERR_BAD_ARG, "eg_beat_align: %d onset frames (n_samples=%d) exceed %d", n_frames, n_samples,
+               EG_BEAT_MAX_FRAMES);
+    EG_REQUIRE(workspace_bytes >= eg_beat_workspace_bytes(batch, n_samples), EG_ERR_WORKSPACE, "eg_beat_align: workspace too small");
+    if (pose) {
+        EG_REQUIRE(score, EG_ERR_BAD_ARG, "eg_beat_align: null score");
+        EG_REQUIRE(pose_dim >= 174, EG_ERR_BAD_ARG, "eg_beat_align: pose_dim=%d (the beat joints are columns 18:42 and 150:174)", pose_dim);
+        EG_REQUIRE(frames >= 2 && frames - 1 <= EG_BEAT_MAX_FRAMES, EG_ERR_BAD_ARG, "eg_beat_align: frames=%d (2..%d)", frames,
+                   EG_BEAT_MAX_FRAMES + 1);
+        EG_REQUIRE(pose_fps > 0 && order >= 1 && sigma > 0.0, EG_ERR_BAD_ARG, "eg_beat_align: pose_fps=%d order=%d sigma=%g", pose_fps,
+                   order, sigma);
+        EG_REQUIRE(t_start >= 0 && t_start < t_end && (int64_t)t_end * pose_fps < (1 << 30), EG_ERR_BAD_ARG,
+                   "eg_beat_align: t_start=%d t_end=%d", t_start, t_end);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    float* meldb = reinterpret_cast<float*>(workspace);
+    float* rms_ws = meldb + (size_t)batch * 128 * n_frames;
+    hipLaunchKernelGGL(beat_stft_kernel, dim3((n_frames + 1) / 2, batch), dim3(256), 0, st, audio, n_samples, d_melfb_t, d_window, d_twiddle,
+                       d_band, meldb, rms_ws, n_frames);
+    int rc = eg_check_launch("beat_stft");
+    if (rc) return rc;
+    const int r_lo = pose ? t_start * pose_fps : 0, r_hi = pose ? t_end * pose_fps : 0;
+    hipLaunchKernelGGL(beat_align_kernel, dim3(batch), dim3(256), 0, st, meldb, rms_ws, n_frames, pose, frames, pose_dim, pose_fps, r_lo, r_hi,
+                       sigma, order, score, n_audio_beats, oenv, rms, audio_beats, pose_beats);
+    return eg_check_launch("beat_align");
 }

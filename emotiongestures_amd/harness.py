@@ -4,8 +4,9 @@ Mirrors what the reference's eval loop does around the generator
 (test_emotion_gesture_diversity_iterative.py:191-261): CVAE sample -> generator -> pose, then the FGD auto-encoder
 features of predicted and target poses (model/FGD.py:26-82), their Frechet distance and diversity score
 (model/FHD_score.py:159-217,247-311), MPJRE, pose L2 and the emotion accuracy of a skeleton classifier
-(skeleton_classifer/Models.py:199-283).  The beat-alignment score is left out: it is a per-sample librosa routine
-(model/Beat_score_v2.py) and librosa is neither vendored nor installed.
+(skeleton_classifer/Models.py:199-283).  The beat-alignment score (model/Beat_score_v2.py, :241-248) is opt-in (``evaluate(...,
+beat=True)``): it runs batched on the GPU through :mod:`emotiongestures_amd.beat`, whose audio half is restated from librosa 0.10's
+documented onset routines and is not pinned against librosa itself.
 
 Every network forward runs on the GPU through libemogest_hip.so (the FGD encoder and the classifier are built from the
 same Linear / attention / LayerNorm operators as the generator); the Gaussian statistics and the matrix square root
@@ -407,12 +408,15 @@ def diversity_score(activations: np.ndarray, frames: int = 60):
 
 # ---- the eval loop ---------------------------------------------------------------------------------------------------
 def evaluate(generator, vae, fgd: MLP_Reconstruct, classifier: Optional[SkeletonTransformer], batches: Iterable[dict],
-             n_pre_poses: int, device="cuda", z_list: Optional[list] = None) -> Dict[str, float]:
+             n_pre_poses: int, device="cuda", z_list: Optional[list] = None, beat: bool = False, fps: int = 15) -> Dict[str, float]:
     """One pass of test_model's hot loop (:191-261) over an iterable of batches, each a dict with
     ``spec [B,128,T]``, ``text [B,60]``, ``pose_seq [B,F,D]`` (target; the first n_pre_poses frames are the prior) and
     ``label [B,8]`` one-hot.  ``z_list`` optionally fixes the CVAE latents per batch (default: torch.randn on the CPU
-    generator as upstream).  Returns the metrics of the summary line (:261) except the beat score."""
-    pred_feats, tgt_feats, l2s, rots, accs = [], [], [], [], []
+    generator as upstream).  Returns the metrics of the summary line (:261); the beat score only with ``beat=True``
+    (opt-in, see the module docstring): then every batch also carries ``audio [B, n]`` (16 kHz) and ``"beat"`` is the mean per-clip
+    score of the predicted poses (t_start 0, t_end int(F / fps), sigma 0.3, order 2: BL_score / (len(loader) * batch) for full
+    batches).  A clip without audio onsets raises ValueError (upstream dies there with ZeroDivisionError)."""
+    pred_feats, tgt_feats, l2s, rots, accs, beats = [], [], [], [], [], []
     frames = None
     with torch.no_grad():
         for bi, batch in enumerate(batches):
@@ -431,6 +435,13 @@ def evaluate(generator, vae, fgd: MLP_Reconstruct, classifier: Optional[Skeleton
             pred_feats.append(pf.reshape(-1, 512).cpu().numpy().astype(np.float64))
             tgt_feats.append(tf.reshape(-1, 512).cpu().numpy().astype(np.float64))
             l2s.append(l2_distance_pose(pred_pose.cpu().numpy().astype(np.float32), pose_seq.cpu().numpy().astype(np.float32)))
+            if beat:                                                                                                 # :241-248
+                from .beat import beat_alignment
+                sc = beat_alignment(batch["audio"].to(device), pred_pose, fps=fps, t_start=0, t_end=int(frames / fps)).cpu().numpy()
+                bad = np.flatnonzero(np.isnan(sc))
+                if bad.size:
+                    raise ValueError(f"evaluate: batch {bi} clip {int(bad[0])} has no audio onsets (the beat score divides by their count)")
+                beats.append(sc)
     pred_arr, tgt_arr = np.concatenate(pred_feats), np.concatenate(tgt_feats)
     fid = calculate_frechet_distance(np.mean(pred_arr, axis=0), np.cov(pred_arr, rowvar=False),
                                      np.mean(tgt_arr, axis=0), np.cov(tgt_arr, rowvar=False))                       # :250-255
@@ -439,4 +450,6 @@ def evaluate(generator, vae, fgd: MLP_Reconstruct, classifier: Optional[Skeleton
            "diversity": float(np.ravel(div)[0]), "diversity_lo": float(np.ravel(interval[0])[0]), "diversity_hi": float(np.ravel(interval[1])[0])}
     if accs:
         out["emotion_acc"] = float(np.mean(accs))
+    if beat:
+        out["beat"] = float(np.mean(np.concatenate(beats)))
     return out

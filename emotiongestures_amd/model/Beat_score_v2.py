@@ -1,11 +1,11 @@
 """Import-line mirror of model/Beat_score_v2.py so that `from model.Beat_score_v2 import alignment`
 (test_emotion_gesture_diversity_iterative.py:29) resolves after `install_aliases()`.
 
-The beat-alignment metric itself is OUT of the hot-path scope: upstream computes audio onsets with librosa
-(model/Beat_score_v2.py:58-77) and velocity extrema with scipy on the host; nothing of it runs on the GPU.  `alignment(sigma, order)` constructs
-(the caller builds it before its loop, :185); every method that would compute something raises `BeatScoreUnavailable` with that explanation, as do
-the two other metric classes of that file.  Point `sys.modules["model.Beat_score_v2"]` at the reference's own file to get the metric back
-(it needs librosa and matplotlib)."""
+This default is a refusing stub: `alignment(sigma, order)` constructs (the caller builds it before its loop, :185) and every method that would
+compute something raises `BeatScoreUnavailable`, as do the two other metric classes of that file.  The metric itself lives in
+`emotiongestures_amd.beat` (batched `beat_alignment` on the GPU, and a drop-in `alignment` class); `install_aliases(beat_score=True)` points
+`model.Beat_score_v2` there.  It is opt-in because its audio half is restated from librosa 0.10's documented onset routines and is not
+pinned against librosa itself."""
 
 
 class BeatScoreUnavailable(NotImplementedError):
@@ -13,8 +13,8 @@ class BeatScoreUnavailable(NotImplementedError):
 
 
 def _refuse(what):
-    raise BeatScoreUnavailable(f"model.Beat_score_v2.{what}: librosa-dependent host-side metric, not part of the HIP path "
-                               "(import the reference's model/Beat_score_v2.py for it)")
+    raise BeatScoreUnavailable(f"model.Beat_score_v2.{what}: the librosa-restated beat score is opt-in "
+                               "(install_aliases(beat_score=True), or emotiongestures_amd.beat)")
 
 
 class alignment(object):

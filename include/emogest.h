@@ -229,6 +229,35 @@ int eg_melspectrogram(const float* audio, int32_t batch, int32_t n_samples, cons
                       void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Beat-alignment score = model/Beat_score_v2.py alignment(sigma, order): load_audio + load_pose +
+ * calculate_align for a batch of clips (test_emotion_gesture_diversity_iterative.py:241-248)
+ * ------------------------------------------------------------------------------------------ */
+/* The audio half restates librosa 0.10's onset_strength / onset_detect / onset_backtrack / feature.rms (n_fft 2048, hop 512, centred,
+ * zero pad, 128 Slaney mels, power_to_db(ref=1.0, top_db=80), peak picking with librosa's default sr 22050); it is not pinned against
+ * librosa itself.
+ * audio [B, n_samples] fp32 16 kHz, already starting at t_start (the caller slices); T = 1 + n_samples/512 onset frames,
+ * n_samples >= 2048 and T <= EG_BEAT_MAX_FRAMES (n_samples < 524288: 32 s; a BEAT 10 s clip has T = 313).
+ * pose [B, frames, pose_dim] fp32 (pose_dim >= 174: the beat joints are columns 18:42 and 150:174), frames - 1 <= EG_BEAT_MAX_FRAMES;
+ * the right-side curves are sliced [t_start*pose_fps : t_end*pose_fps] as upstream; sigma > 0, order >= 1, 0 <= t_start < t_end.
+ * pose == NULL: audio half only (score and pose_beats unused).
+ * Outputs, each written only when non-NULL (score required with a pose):
+ *   score [B] fp64 (NaN for a clip without audio onsets), n_audio_beats [B] (onset_raw count), oenv / rms [B, T],
+ *   audio_beats [B, 3, T] uint8 (onset_raw 0/1; onset_bt, onset_bt_rms as multiplicities: two onsets can backtrack to one frame),
+ *   pose_beats [B, 8, frames-1] uint8 in load_pose's return order (right arm, shoulder, fore arm, wrist, left ...; the right-side
+ *   indices are relative to the slice start, as upstream).
+ * d_melfb_t [1025,128], d_window [2048], d_twiddle [1024,2], d_band [128,2]: device copies of eg_beat_tables.
+ * workspace >= eg_beat_workspace_bytes.  Deterministic (fixed summation orders), stream-ordered, no host synchronisation. */
+#define EG_BEAT_MAX_FRAMES 1024
+int eg_beat_tables(float* h_melfb_t /*1025*128, transposed*/, float* h_window /*2048*/, float* h_twiddle /*2*1024*/,
+                   int32_t* h_band /*128*2*/);
+int64_t eg_beat_workspace_bytes(int32_t batch, int32_t n_samples);
+int eg_beat_align(const float* audio, int32_t batch, int32_t n_samples, const float* pose, int32_t frames, int32_t pose_dim,
+                  int32_t pose_fps, int32_t t_start, int32_t t_end, double sigma, int32_t order, const float* d_melfb_t,
+                  const float* d_window, const float* d_twiddle, const int32_t* d_band, void* workspace, int64_t workspace_bytes,
+                  double* score, int32_t* n_audio_beats, float* oenv, float* rms, uint8_t* audio_beats, uint8_t* pose_beats,
+                  void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Block-level operators (the reference's L2 blocks), used by the module-level mirrors and by the
  * per-kernel parity tests.  Weights here are passed as individual device pointers in the PACKED
  * layouts named above.
