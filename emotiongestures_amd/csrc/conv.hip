@@ -1157,6 +1157,12 @@ int conv_channel_split(int wgs, int max_split) {
     return split;
 }
 
+// the channel split a C -> C body convolution takes (1: none; the split kernels exist for bf16x3, stride 1, 64 and 128 channels, NHWC output)
+int body_channel_split(int batch, int tiles, int cin, int cout, int stride, int precision, int nchw_out) {
+    if (!((cin == 64 || cin == 128) && cout == cin && stride == 1 && precision == EG_PREC_BF16X3 && !nchw_out)) return 1;
+    return conv_channel_split(tiles * batch, cin == 128 ? 4 : 2);
+}
+
 template <int CIN, int NT, int S, int TH, int WM, int WN>
 int launch_conv(const ConvArgs& a, int batch, int precision, hipStream_t st) {
     dim3 grid(a.tiles, batch), block(256);
@@ -1256,6 +1262,11 @@ extern "C" int32_t eg_conv3x3_gap_tiles(int32_t h, int32_t wdt, int32_t cin, int
     return eg_cdiv(ho, th) * eg_cdiv(wo, 32);
 }
 
+// The channel split eg_conv3x3 (and every entry point that shares its dispatch: _se, _sq, _sq_in_affine, _res_masked) takes for this launch.
+extern "C" int32_t eg_conv3x3_channel_split(int32_t batch, int32_t h, int32_t wdt, int32_t cin, int32_t cout, int32_t stride, int32_t precision) {
+    return body_channel_split(batch, eg_conv3x3_gap_tiles(h, wdt, cin, cout, stride), cin, cout, stride, precision, 0);
+}
+
 // Packed weight size in floats for one 3x3 conv: fp32 image + (hi, lo) bf16 images.
 extern "C" int64_t eg_conv3x3_packed_floats(int32_t cin, int32_t cout_pad) {
     return (int64_t)9 * cin * cout_pad * 2;     // 9*cin*coutp fp32 + 2 * 9*cin*coutp bf16 (= same bytes again)
@@ -1345,9 +1356,8 @@ int conv3x3_dispatch(const float* x, const float* w, const float* bias, const fl
     if (cin == 32 && coutp == 32 && stride == 1 && th == 4) return launch_conv<32, 2, 1, 4, 4, 1>(a, batch, precision, st);
     if (cin == 32 && coutp == 32 && stride == 1) return launch_conv<32, 2, 1, 8, 4, 1>(a, batch, precision, st);
     if (cin == 32 && coutp == 64 && stride == 2) return launch_conv<32, 4, 2, 2, 2, 2>(a, batch, precision, st);
-    if ((cin == 64 || cin == 128) && cout == cin && stride == 1 && precision == EG_PREC_BF16X3 && !nchw_out) {
+    if (const int split = body_channel_split(batch, a.tiles, cin, cout, stride, precision, nchw_out); split > 1) {
         // few pixel tiles (small batches): spread the output channels over workgroups as well -- bitwise the unsplit kernels below
-        const int split = conv_channel_split(a.tiles * batch, cin == 128 ? 4 : 2);
         const size_t f32_floats = (size_t)9 * cin * cout;
         const bf8* whi = reinterpret_cast<const bf8*>(a.w + f32_floats);
         const bf8* wlo = whi + (size_t)9 * (cin / 8) * cout;

@@ -272,6 +272,9 @@ int eg_conv3x3(const float* x, const float* w, const float* bias, const float* s
                float* y, float* gap_partial, int32_t batch, int32_t h, int32_t wdt, int32_t cin, int32_t cout,
                int32_t stride, int32_t relu, int32_t nchw_out, int32_t precision, void* stream);
 int32_t eg_conv3x3_gap_tiles(int32_t h, int32_t wdt, int32_t cin, int32_t cout, int32_t stride);
+/* The output-channel split (1, 2 or 4 workgroups per pixel tile) the NHWC convolution takes at this shape and precision: the split kernels
+ * serve the bf16x3 stride-1 64 -> 64 and 128 -> 128 bodies while there are few pixel tiles (EG_CONV_SPLIT forces 1, 2 or 4). */
+int32_t eg_conv3x3_channel_split(int32_t batch, int32_t h, int32_t wdt, int32_t cin, int32_t cout, int32_t stride, int32_t precision);
 /* eg_conv3x3 with the SEBasicBlock tail of an identity block fused into the epilogue (ResNetBlocks.py:28-36):
  *   y = relu(BN(conv(x)) * gate[b, co] + residual[pixel, co]),   gate [B, Cout] from eg_se_gate_pre, residual NHWC like y.
  * gate == residual == NULL: plain eg_conv3x3.  gate == NULL with a residual: y = BN(conv(x)) + residual, no ReLU -- the fused fan-in add of
