@@ -71,6 +71,8 @@ SIGNATURES = {
     "eg_generator_forward": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "eg_generator_forward_draws": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _L, _P]),
     "eg_generator_draws_workspace_bytes": (_L, [_P, _I, _I]),
+    "eg_generator_forward_rollout": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "eg_generator_rollout_workspace_bytes": (_L, [_P, _I, _I]),
     "eg_generator_tap": (C.c_int, [_P, _I, _P, C.c_char_p, C.POINTER(_P), C.POINTER(_L)]),
     "eg_cvae_default_config": (C.c_int, [C.POINTER(EgCvaeConfig)]),
     "eg_cvae_create": (C.c_int, [C.POINTER(EgCvaeConfig), C.POINTER(_P)]),
@@ -84,6 +86,7 @@ SIGNATURES = {
     "eg_mel_tables": (C.c_int, [_P, _P, _P, _P]),
     "eg_mel_workspace_bytes": (_L, [_I, _I]),
     "eg_melspectrogram": (C.c_int, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _L, _P]),
+    "eg_window_gather": (C.c_int, [_P, _I, _L, _I, _L, _I, _P, _P]),
     "eg_beat_tables": (C.c_int, [_P, _P, _P, _P]),
     "eg_beat_workspace_bytes": (_L, [_I, _I]),
     "eg_beat_align": (C.c_int, [_P, _I, _I, _P, _I, _I, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P]),

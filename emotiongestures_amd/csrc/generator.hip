@@ -147,6 +147,9 @@ int egi_conv1d(const float* x, const float* w, const float* bias, const float* s
                int cout, int lin, int k, int stride, int pad, int act, hipStream_t st);
 int egi_convt1d(const float* x, const float* w, const float* bias, const float* scale, const float* shift, float* y, int n, int cin,
                 int cout, int lin, hipStream_t st);
+int egi_swap01(const void* in, void* out, int A, int B, size_t inner_words, hipStream_t st);
+int egi_rollout_handoff(const float* pose, const float* prior_in, const float* alpha, float* track, float* windows, float* prior_out, int U,
+                        int W, int w, int F, int P, int D, hipStream_t st);
 int egi_small_linear(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int n, int in, int out,
                      hipStream_t st);
 
@@ -447,6 +450,19 @@ int run_mha(const EgGenerator* g, const float* arena, const MhaW& m, const Act& 
     return egi_layernorm(pr, arena + m.ln_g, arena + m.ln_b, out.f, g->cfg.precision != EG_PREC_F32 ? out.img : nullptr, B * Lq, D, 1e-6f, st);
 }
 
+// Cross attention over K|V that is already projected (kv: [B*Lk, 2*d_model] fp32, K in columns [0, D), V in [D, 2D)): run_mha's
+// cross branch without its K|V product.
+int run_mha_kv(const EgGenerator* g, const float* arena, const MhaW& m, const Act& xq, const float* kv, const Act& out, const GenWs& w,
+               void* ws, int B, int Lq, int Lk, hipStream_t st) {
+    const int D = g->cfg.d_model;
+    float *q = P(ws, w.q), *ao = P(ws, w.ao), *pr = P(ws, w.proj);
+    void* aimg = g->cfg.precision != EG_PREC_F32 ? P(ws, w.im_h) : nullptr;
+    EG_TRY(lin(g, arena, m.q, xq, 0, act(q, D), true, B * Lq, 0, nullptr, 0, st));
+    EG_TRY(egi_attention(q, D, kv, 2 * D, kv + D, 2 * D, ao, D, nullptr, aimg, B, g->cfg.n_head, Lq, Lk, g->cfg.d_k, g->cfg.precision, st));
+    EG_TRY(lin(g, arena, m.o, act(ao, D, aimg, D), 0, act(pr, D), true, B * Lq, 0, xq.f, D, st));
+    return egi_layernorm(pr, arena + m.ln_g, arena + m.ln_b, out.f, g->cfg.precision != EG_PREC_F32 ? out.img : nullptr, B * Lq, D, 1e-6f, st);
+}
+
 // PositionwiseFeedForward.forward (SubLayers.py:74-84); the 2048-wide hidden only exists as images in the bf16 modes
 int run_ffn(const EgGenerator* g, const float* arena, const FfnW& f, const Act& x, const Act& out, const GenWs& w, void* ws, int rows,
             hipStream_t st) {
@@ -555,12 +571,12 @@ int run_prior(const EgGenerator* g, const float* arena, const float* prior, cons
     return lin(g, arena, g->prior_h2, ph, 0, act(P(ws, w.prior_enc), c.d_model, P(ws, w.im_p[1]), c.d_model), true, rows, 0, nullptr, 0, st);
 }
 
-// fusion -> encoder -> decoder -> post_projector for NB sequences (Models_spatial_memory.py:601-614)
-int run_transformer(const EgGenerator* g, const float* arena, const float* fusion_in, const Act& prior_enc, float* pose, const GenWs& w,
-                    void* ws, int NB, hipStream_t st) {
+// fusion_proj -> positional add -> encoder stack for NB sequences (Models_spatial_memory.py:601-606): enc_out = xa (+ images in im_enc)
+int run_encoder(const EgGenerator* g, const float* arena, const float* fusion_in, Act& enc_out, const GenWs& w, void* ws, int NB,
+                hipStream_t st) {
     const EgGeneratorConfig& c = g->cfg;
     const int F = c.frames, D = c.d_model, rows = NB * F;
-    void *im0 = P(ws, w.im_x[0]), *im1 = P(ws, w.im_x[1]), *ime = P(ws, w.im_enc), *imh = P(ws, w.im_h);
+    void *im0 = P(ws, w.im_x[0]), *im1 = P(ws, w.im_x[1]), *ime = P(ws, w.im_enc);
     const Act fh = act(P(ws, w.fus_h), D, im0, D);
     EG_TRY(lin(g, arena, g->fus0, act(const_cast<float*>(fusion_in), D), 0, fh, false, rows, 1, nullptr, 0, st));
     EG_TRY(lin(g, arena, g->fus2, fh, 0, act(P(ws, w.fusion), D), true, rows, 0, nullptr, 0, st));
@@ -574,18 +590,17 @@ int run_transformer(const EgGenerator* g, const float* arena, const float* fusio
         EG_TRY(run_ffn(g, arena, g->enc_ffn[l], mid, nxt, w, ws, rows, st));
         x = nxt;
     }
-    const Act enc_out = x;                               // xa + images in im_enc, alive through the decoder
-    float* da = P(ws, w.fus_h);                          // reuse (fusion hidden is dead)
-    Act dx = prior_enc;
-    for (int l = 0; l < c.n_layers; ++l) {
-        const Act mid = act(xb, D, im0, D);
-        const Act nxt = act(da, D, im1, D);
-        EG_TRY(run_mha(g, arena, g->dec_attn[l], dx, enc_out, mid, w, ws, NB, F, F, st));
-        EG_TRY(run_ffn(g, arena, g->dec_ffn[l], mid, nxt, w, ws, rows, st));
-        dx = nxt;
-    }
+    enc_out = x;                                         // xa + images in im_enc, alive through the decoder
+    return EG_OK;
+}
+
+// post_projector on the decoder output (Models_spatial_memory.py:612-614)
+int run_post(const EgGenerator* g, const float* arena, const Act& dx, float* pose, const GenWs& w, void* ws, int rows, hipStream_t st) {
+    const EgGeneratorConfig& c = g->cfg;
+    const int D = c.d_model;
+    void *im0 = P(ws, w.im_x[0]), *im1 = P(ws, w.im_x[1]), *imh = P(ws, w.im_h);
     if (g->fold) return lin(g, arena, g->f_post, dx, 0, act(pose, c.pose_dim), true, rows, 0, nullptr, 0, st);
-    // post_projector: four affine layers chained through images (fp32 copies only in f32 mode)
+    // four affine layers chained through images (fp32 copies only in f32 mode)
     const Act pa = act(P(ws, w.post_a), D * 4, imh, D * 4), pb = act(P(ws, w.post_b), D, im0, D), pc = act(P(ws, w.post_c), g->Dpad, im1, g->Dpad);
     EG_TRY(lin(g, arena, g->post[0], dx, 0, pa, false, rows, 0, nullptr, 0, st));
     EG_TRY(lin(g, arena, g->post[1], pa, 0, pb, false, rows, 0, nullptr, 0, st));
@@ -593,6 +608,56 @@ int run_transformer(const EgGenerator* g, const float* arena, const float* fusio
     return lin(g, arena, g->post[3], pc, 0, act(pose, c.pose_dim), true, rows, 0, nullptr, 0, st);
 }
 
+// decoder stack -> post_projector for NB sequences (Models_spatial_memory.py:607-614).  The layers' K|V come either from enc_out (projected
+// here, layer by layer) or, in a roll-out step, from kv[l]: [NB*F, 2*d_model] fp32 projected in phase A -- the same launches minus that product.
+int run_decoder(const EgGenerator* g, const float* arena, const Act& prior_enc, const Act& enc_out, float* const* kv, float* pose,
+                const GenWs& w, void* ws, int NB, hipStream_t st) {
+    const EgGeneratorConfig& c = g->cfg;
+    const int F = c.frames, D = c.d_model, rows = NB * F;
+    void *im0 = P(ws, w.im_x[0]), *im1 = P(ws, w.im_x[1]);
+    float *xb = P(ws, w.xb), *da = P(ws, w.fus_h);       // reuse (fusion hidden is dead)
+    Act dx = prior_enc;
+    for (int l = 0; l < c.n_layers; ++l) {
+        const Act mid = act(xb, D, im0, D);
+        const Act nxt = act(da, D, im1, D);
+        if (kv) EG_TRY(run_mha_kv(g, arena, g->dec_attn[l], dx, kv[l], mid, w, ws, NB, F, F, st));
+        else EG_TRY(run_mha(g, arena, g->dec_attn[l], dx, enc_out, mid, w, ws, NB, F, F, st));
+        EG_TRY(run_ffn(g, arena, g->dec_ffn[l], mid, nxt, w, ws, rows, st));
+        dx = nxt;
+    }
+    return run_post(g, arena, dx, pose, w, ws, rows, st);
+}
+
+// fusion -> encoder -> decoder -> post_projector for NB sequences (Models_spatial_memory.py:601-614)
+int run_transformer(const EgGenerator* g, const float* arena, const float* fusion_in, const Act& prior_enc, float* pose, const GenWs& w,
+                    void* ws, int NB, hipStream_t st) {
+    Act enc_out;
+    EG_TRY(run_encoder(g, arena, fusion_in, enc_out, w, ws, NB, st));
+    return run_decoder(g, arena, prior_enc, enc_out, nullptr, pose, w, ws, NB, st);
+}
+
+// emotion_proj / semantic_proj of the audio feature and the emotion classifier header (Models_spatial_memory.py:588-592)
+int run_heads(const EgGenerator* g, const float* arena, float* emo, float* sem, float* pred, const GenWs& w, void* ws, int B, hipStream_t st) {
+    const EgGeneratorConfig& c = g->cfg;
+    const int F = c.frames, D = c.d_model, rows = B * F, prec = c.precision;
+    // emotion_proj.0 | semantic_proj.0 fused: [rows, 2D] = (emotion hidden | semantic hidden)
+    const Act afeat = act(P(ws, w.afeat), D, P(ws, w.im_a[1]), D), es = act(P(ws, w.emo_t), 2 * D, P(ws, w.im_a[2]), 2 * D);
+    if (g->fold) {
+        EG_TRY(lin(g, arena, g->f_emo, afeat, 0, act(emo, D), true, rows, 0, nullptr, 0, st));
+        EG_TRY(lin(g, arena, g->f_sem, afeat, 0, act(sem, D), true, rows, 0, nullptr, 0, st));
+    } else {
+        EG_TRY(lin(g, arena, g->emosem0, afeat, 0, es, false, rows, 0, nullptr, 0, st));
+        EG_TRY(lin(g, arena, g->emo2, es, 0, act(emo, D), true, rows, 0, nullptr, 0, st));
+        EG_TRY(lin(g, arena, g->sem2, es, D, act(sem, D), true, rows, 0, nullptr, 0, st));
+    }
+    // emotion classifier header on emotion_feature.reshape(B, F*D)  (:592)
+    const int K0 = F * D;
+    EG_TRY(eg_linear_splitk(emo, K0, arena + g->cls[0].w, g->cls[0].kpad, arena + g->cls[0].b, P(ws, w.cls_h[0]), D, B, D, K0, 1,
+                            F, P(ws, w.cls_part), prec, st));
+    EG_TRY(run_linear(arena, g->cls[1], P(ws, w.cls_h[0]), D, P(ws, w.cls_h[1]), 256, B, 1, nullptr, 0, prec, st));
+    EG_TRY(run_linear(arena, g->cls[2], P(ws, w.cls_h[1]), 256, P(ws, w.cls_h[2]), 64, B, 1, nullptr, 0, prec, st));
+    return run_linear(arena, g->cls[3], P(ws, w.cls_h[2]), 64, pred, 8, B, 0, nullptr, 0, prec, st);
+}
 
 int validate_cfg(const EgGeneratorConfig& c) {
     EG_REQUIRE(c.frames > c.prior_frames && c.prior_frames >= c.chunk && c.chunk > 0, EG_ERR_BAD_ARG, "config: frames/prior/chunk inconsistent");
@@ -780,7 +845,7 @@ extern "C" int eg_generator_forward(const EgGenerator* g, const float* arena, in
     EG_REQUIRE(eg_aligned16(ws) && eg_aligned16(arena) && eg_aligned16(spec), EG_ERR_ALIGN, "eg_generator_forward: 16-byte alignment");
     hipStream_t st = (hipStream_t)stream;
     const EgGeneratorConfig& c = g->cfg;
-    const int F = c.frames, D = c.d_model, rows = B * F, prec = c.precision;
+    const int F = c.frames, D = c.d_model, rows = B * F;
 
     float* txt = text_embedding ? text_embedding : P(ws, w.t_out);
     hipStream_t s_text = st, s_prior = st;
@@ -798,29 +863,9 @@ extern "C" int eg_generator_forward(const EgGenerator* g, const float* arena, in
         EG_HIP_TRY(hipEventRecord(g->ev_join[1], s_prior), "branch join");
     }
     EG_TRY(run_audio_tower(g, arena, spec, w, ws, B, st));
-    const float* feat = P(ws, w.afeat);
     float* emo = emotion_feature ? emotion_feature : P(ws, w.emo);
     float* sem = semantic_feature ? semantic_feature : P(ws, w.sem);
-    // emotion_proj.0 | semantic_proj.0 fused: [rows, 2D] = (emotion hidden | semantic hidden)
-    const Act afeat = act(P(ws, w.afeat), D, P(ws, w.im_a[1]), D), es = act(P(ws, w.emo_t), 2 * D, P(ws, w.im_a[2]), 2 * D);
-    if (g->fold) {
-        EG_TRY(lin(g, arena, g->f_emo, afeat, 0, act(emo, D), true, rows, 0, nullptr, 0, st));
-        EG_TRY(lin(g, arena, g->f_sem, afeat, 0, act(sem, D), true, rows, 0, nullptr, 0, st));
-    } else {
-        EG_TRY(lin(g, arena, g->emosem0, afeat, 0, es, false, rows, 0, nullptr, 0, st));
-        EG_TRY(lin(g, arena, g->emo2, es, 0, act(emo, D), true, rows, 0, nullptr, 0, st));
-        EG_TRY(lin(g, arena, g->sem2, es, D, act(sem, D), true, rows, 0, nullptr, 0, st));
-    }
-    // emotion classifier header on emotion_feature.reshape(B, F*D)  (:592)
-    {
-        const int K0 = F * D;
-        EG_TRY(eg_linear_splitk(emo, K0, arena + g->cls[0].w, g->cls[0].kpad, arena + g->cls[0].b, P(ws, w.cls_h[0]), D, B, D, K0, 1,
-                                F, P(ws, w.cls_part), prec, st));
-        EG_TRY(run_linear(arena, g->cls[1], P(ws, w.cls_h[0]), D, P(ws, w.cls_h[1]), 256, B, 1, nullptr, 0, prec, st));
-        EG_TRY(run_linear(arena, g->cls[2], P(ws, w.cls_h[1]), 256, P(ws, w.cls_h[2]), 64, B, 1, nullptr, 0, prec, st));
-        float* pred = emotion_prediction ? emotion_prediction : P(ws, w.cls_out);
-        EG_TRY(run_linear(arena, g->cls[3], P(ws, w.cls_h[2]), 64, pred, 8, B, 0, nullptr, 0, prec, st));
-    }
+    EG_TRY(run_heads(g, arena, emo, sem, emotion_prediction ? emotion_prediction : P(ws, w.cls_out), w, ws, B, st));
     EG_TRY(egi_add(sampled ? sampled : emo, sem, P(ws, w.fus_in), (size_t)rows * D, D, 0, st));
     float* pose_out = pose ? pose : P(ws, w.pose);
     if (g->concurrent) {        // join: the decoder needs the prior encoding; the caller's stream must also cover the text branch
@@ -859,6 +904,103 @@ extern "C" int eg_generator_forward_draws(const EgGenerator* g, const float* are
     EG_TRY(egi_add_bcast(sampled, P(ws, w.sem), P(ws, w.fus_in), (size_t)B * R * F, D, F, R, st));
     EG_TRY(egi_add_bcast(nullptr, P(ws, w.prior_enc), P(ws, w.prior_rep), (size_t)B * R * F, D, F, R, st));
     return run_transformer(g, arena, P(ws, w.fus_in), act(P(ws, w.prior_rep), D), pose, w, ws, B * R, st);
+}
+
+// ---- roll-out: W dependent windows of U utterances --------------------------------------------------------------------------------
+namespace {
+struct RollWs { GenWs a; int64_t kv[8], prior[2], spec, text, sampled, total; };
+RollWs carve_rollout(const EgGenerator* g, int U, int W) {
+    const EgGeneratorConfig& c = g->cfg;
+    const int64_t N = (int64_t)U * W;
+    RollWs r;
+    r.a = carve(g, (int)N);             // phase A at batch U*W; the decoder steps reuse its buffers at batch U
+    Carver cv;
+    cv.off = r.a.total;
+    for (int l = 0; l < c.n_layers; ++l) r.kv[l] = cv.take(N * c.frames * 2 * c.d_model);
+    r.prior[0] = cv.take((int64_t)U * c.prior_frames * c.pose_dim);
+    r.prior[1] = cv.take((int64_t)U * c.prior_frames * c.pose_dim);
+    // window-major copies of the utterance-major arguments (unused when U == 1 or W == 1: the two orders coincide)
+    r.spec = cv.take(N * c.n_mels * c.spec_len);
+    r.text = cv.take(N * c.text_len * 2);
+    r.sampled = cv.take(N * c.frames * c.d_model);
+    r.total = cv.off;
+    return r;
+}
+}  // namespace
+
+extern "C" int64_t eg_generator_rollout_workspace_bytes(const EgGenerator* g, int32_t utterances, int32_t windows) {
+    if (!g || utterances <= 0 || windows <= 0 || g->cfg.n_layers > 8 || (int64_t)utterances * windows > (1 << 20)) return 0;
+    return carve_rollout(g, utterances, windows).total;
+}
+
+extern "C" int eg_generator_forward_rollout(const EgGenerator* g, const float* arena, int32_t U, int32_t W, const float* spec,
+                                            const int64_t* text, const float* seed_pose, const float* sampled, const float* alpha,
+                                            float* track, float* windows, float* emotion_prediction, float* emotion_feature,
+                                            float* semantic_feature, float* text_embedding, void* ws, int64_t ws_bytes, void* stream) {
+    EG_REQUIRE(g && arena && spec && seed_pose && track && ws, EG_ERR_BAD_ARG, "eg_generator_forward_rollout: null pointer");
+    EG_REQUIRE(U >= 1, EG_ERR_BAD_ARG, "eg_generator_forward_rollout: utterances=%d (need >= 1)", U);
+    EG_REQUIRE(W >= 1, EG_ERR_BAD_ARG, "eg_generator_forward_rollout: windows=%d (need >= 1)", W);
+    EG_REQUIRE((int64_t)U * W <= (1 << 20), EG_ERR_UNSUPPORTED, "eg_generator_forward_rollout: utterances*windows=%lld", (long long)U * W);
+    EG_REQUIRE(text || !text_embedding, EG_ERR_BAD_ARG, "eg_generator_forward_rollout: text_embedding wanted without text");
+    EG_REQUIRE(g->cfg.n_layers <= 8, EG_ERR_UNSUPPORTED, "eg_generator_forward_rollout: n_layers=%d > 8", g->cfg.n_layers);
+    const RollWs r = carve_rollout(g, U, W);
+    const GenWs& w = r.a;
+    EG_REQUIRE(ws_bytes >= r.total, EG_ERR_WORKSPACE, "eg_generator_forward_rollout: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)r.total);
+    EG_REQUIRE(eg_aligned16(ws) && eg_aligned16(arena) && eg_aligned16(spec), EG_ERR_ALIGN, "eg_generator_forward_rollout: 16-byte alignment");
+    hipStream_t st = (hipStream_t)stream;
+    const EgGeneratorConfig& c = g->cfg;
+    const int F = c.frames, D = c.d_model, N = U * W, P_ = c.prior_frames, PD = c.pose_dim;
+    const bool swap = U > 1 && W > 1;           // clip n = w*U + u in phase A, so that the U clips of a step are contiguous
+
+    // ---- phase A, batch U*W: everything the prior does not reach
+    if (swap) {
+        EG_TRY(egi_swap01(spec, P(ws, r.spec), U, W, (size_t)c.n_mels * c.spec_len, st));
+        spec = P(ws, r.spec);
+        if (text_embedding) {
+            EG_TRY(egi_swap01(text, P(ws, r.text), U, W, (size_t)c.text_len * 2, st));
+            text = reinterpret_cast<const int64_t*>(P(ws, r.text));
+        }
+        if (sampled) {
+            EG_TRY(egi_swap01(sampled, P(ws, r.sampled), U, W, (size_t)F * D, st));
+            sampled = P(ws, r.sampled);
+        }
+    }
+    // outputs in utterance-major order: made in the workspace and swapped back, or written in place when the orders coincide
+    float* txt = swap ? P(ws, w.t_out) : text_embedding;
+    float* emo = swap || !emotion_feature ? P(ws, w.emo) : emotion_feature;
+    float* sem = swap || !semantic_feature ? P(ws, w.sem) : semantic_feature;
+    float* pred = swap || !emotion_prediction ? P(ws, w.cls_out) : emotion_prediction;
+    if (text_embedding) EG_TRY(run_text(g, arena, text, txt, w, ws, N, st));
+    EG_TRY(run_audio_tower(g, arena, spec, w, ws, N, st));
+    EG_TRY(run_heads(g, arena, emo, sem, pred, w, ws, N, st));
+    EG_TRY(egi_add(sampled ? sampled : emo, sem, P(ws, w.fus_in), (size_t)N * F * D, D, 0, st));
+    Act enc_out;
+    EG_TRY(run_encoder(g, arena, P(ws, w.fus_in), enc_out, w, ws, N, st));
+    float* kv[8];
+    for (int l = 0; l < c.n_layers; ++l) {
+        kv[l] = P(ws, r.kv[l]);
+        EG_TRY(lin(g, arena, g->dec_attn[l].kv, enc_out, 0, act(kv[l], 2 * D), true, N * F, 0, nullptr, 0, st));
+    }
+    if (swap) {
+        if (text_embedding) EG_TRY(egi_swap01(txt, text_embedding, W, U, (size_t)c.text_len * 512, st));
+        if (emotion_feature) EG_TRY(egi_swap01(emo, emotion_feature, W, U, (size_t)F * D, st));
+        if (semantic_feature) EG_TRY(egi_swap01(sem, semantic_feature, W, U, (size_t)F * D, st));
+        if (emotion_prediction) EG_TRY(egi_swap01(pred, emotion_prediction, W, U, 8, st));
+    }
+
+    // ---- phase B, W dependent steps of U clips: prior encoder -> decoder over that step's K|V slice -> post_projector -> hand-off
+    const float* prior = seed_pose;
+    const Act prior_enc = act(P(ws, w.prior_enc), D, P(ws, w.im_p[1]), D);
+    for (int s = 0; s < W; ++s) {
+        EG_TRY(run_prior(g, arena, prior, w, ws, U, st));
+        float* step_kv[8];
+        for (int l = 0; l < c.n_layers; ++l) step_kv[l] = kv[l] + (size_t)s * U * F * 2 * D;
+        EG_TRY(run_decoder(g, arena, prior_enc, Act(), step_kv, P(ws, w.pose), w, ws, U, st));
+        float* next = P(ws, r.prior[s & 1]);
+        EG_TRY(egi_rollout_handoff(P(ws, w.pose), prior, alpha, track, windows, next, U, W, s, F, P_, PD, st));
+        prior = next;
+    }
+    return EG_OK;
 }
 
 extern "C" int eg_generator_tap(const EgGenerator* g, int32_t batch, void* ws, const char* name, float** d_ptr, int64_t* numel) {

@@ -422,6 +422,64 @@ __global__ __launch_bounds__(256) void add_bcast_kernel(const f4* __restrict__ a
     }
 }
 
+// out[(b * A + a) * inner + i] = in[(a * B + b) * inner + i]: swap the two leading axes of an [A, B, inner] array of 32-bit words
+// (roll-out: utterance-major [U, W, ...] arguments <-> the window-major order phase A and the decoder steps work in)
+template <typename V>
+__global__ __launch_bounds__(256) void swap01_kernel(const V* __restrict__ in, V* __restrict__ out, int A, int B, size_t inner) {
+    const size_t n = (size_t)A * B * inner;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const size_t row = i / inner, c = i - row * inner;
+        const size_t b = row / A, a = row - b * A;
+        out[i] = in[(a * B + b) * inner + c];
+    }
+}
+
+// Roll-out hand-off after window w (one launch per decoder step).  pose [U, F, D] is the step's raw output; prior_in [U, P, D] is the
+// prior this step was seeded with (for w >= 1 the raw last P frames of window w-1); H = F - P.
+//   track [U, T, D], T = W*H + P:  rows w*H + j = (1 - alpha[j]) * prior_in[j] + alpha[j] * pose[j] for j < P and w >= 1, pose[j] otherwise
+//   windows [U, W, F, D] (optional): the raw pose;  prior_out [U, P, D]: pose[H + j], the next step's prior.
+// alpha == nullptr: alpha[j] = (j + 1) / (P + 1).  prior_in and prior_out are different buffers (the caller ping-pongs), so no thread reads what another one writes.  The blend is
+// two rounded products and one rounded sum (no fused multiply-add): the arithmetic a host restatement in fp32 reproduces bit for bit.
+__global__ __launch_bounds__(256) void rollout_handoff_kernel(const float* __restrict__ pose, const float* __restrict__ prior_in,
+                                                              const float* __restrict__ alpha, float* __restrict__ track,
+                                                              float* __restrict__ windows, float* __restrict__ prior_out, int U, int W,
+                                                              int w, int F, int P, int D) {
+    const int H = F - P;
+    const size_t T = (size_t)W * H + P, n = (size_t)U * F * D;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const int d = (int)(i % D), j = (int)((i / D) % F), u = (int)(i / ((size_t)D * F));
+        const float v = pose[i];
+        float t = v;
+        if (w > 0 && j < P) {
+#pragma clang fp contract(off)      // the products are rounded before the sum: no v_fma here, whatever the translation unit's default
+            const float a = alpha ? alpha[j] : (float)(j + 1) / (float)(P + 1);
+            const float keep = (1.f - a) * prior_in[((size_t)u * P + j) * D + d], take = a * v;
+            t = keep + take;
+        }
+        track[((size_t)u * T + (size_t)w * H + j) * D + d] = t;
+        if (windows) windows[(((size_t)u * W + w) * F + j) * D + d] = v;
+        if (j >= H) prior_out[((size_t)u * P + (j - H)) * D + d] = v;
+    }
+}
+
+// out[(u * W + w), i] = audio[u, w * hop + i]: the overlapping windows of a long recording as a batch of clips.  A window that runs past
+// the end of the track holds L = total - w * hop < n samples and is completed as make_audio_fixed_length does (np.pad mode="symmetric":
+// the samples mirrored about the end, the last one repeated, with period 2L).
+__global__ __launch_bounds__(256) void window_gather_kernel(const float* __restrict__ audio, float* __restrict__ out, int U, int64_t total,
+                                                            int W, int64_t hop, int n) {
+    const size_t cnt = (size_t)U * W * n;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (size_t)gridDim.x * 256) {
+        const size_t clip = i / n;
+        const int64_t start = (int64_t)(clip % W) * hop, L = total - start;     // L >= 1 (checked by the launcher)
+        int64_t k = (int64_t)(i - clip * n);
+        if (k >= L) {
+            k %= 2 * L;
+            if (k >= L) k = 2 * L - 1 - k;
+        }
+        out[i] = audio[(clip / W) * (size_t)total + start + k];
+    }
+}
+
 inline int grid_for(size_t n, int cap = 4096) {
     const size_t g = (n + 255) / 256;
     return (int)(g < (size_t)cap ? (g ? g : 1) : cap);
@@ -476,6 +534,20 @@ extern "C" int eg_add_rows(const float* a, const float* table, float* out, int64
     return eg_check_launch("add_rows");
 }
 
+extern "C" int eg_window_gather(const float* audio, int32_t utterances, int64_t total_samples, int32_t windows, int64_t hop_samples,
+                                int32_t n_samples, float* out, void* stream) {
+    EG_REQUIRE(audio && out, EG_ERR_BAD_ARG, "eg_window_gather: null pointer");
+    EG_REQUIRE(utterances >= 1 && windows >= 1, EG_ERR_BAD_ARG, "eg_window_gather: utterances=%d windows=%d", utterances, windows);
+    EG_REQUIRE(total_samples >= 1 && hop_samples >= 1 && n_samples >= 1, EG_ERR_BAD_ARG, "eg_window_gather: total_samples=%lld hop_samples=%lld n_samples=%d",
+               (long long)total_samples, (long long)hop_samples, n_samples);
+    EG_REQUIRE((int64_t)(windows - 1) * hop_samples < total_samples, EG_ERR_BAD_ARG,
+               "eg_window_gather: windows=%d: the last window starts at sample %lld of %lld", windows, (long long)(windows - 1) * hop_samples,
+               (long long)total_samples);
+    hipLaunchKernelGGL(window_gather_kernel, dim3(grid_for((size_t)utterances * windows * n_samples)), dim3(256), 0, (hipStream_t)stream, audio, out,
+                       utterances, total_samples, windows, hop_samples, n_samples);
+    return eg_check_launch("window_gather");
+}
+
 // ---- internal (C++ linkage) launchers used by generator.hip ------------------------------------------------
 int egi_embedding(const int64_t* idx, const float* table, float* out, int rows, int dim, int ld, int n_words, hipStream_t st) {
     hipLaunchKernelGGL(embedding_kernel, dim3(grid_for((size_t)rows * dim / 4)), dim3(256), 0, st, idx, table, out, rows, dim, ld, n_words);
@@ -500,6 +572,24 @@ int egi_time_linear(const float* x, const float* w, const float* bias, float* y,
 int egi_copy2d(const float* src, int lds_, float* dst, int ldd, int rows, int cols, hipStream_t st) {
     hipLaunchKernelGGL(copy2d_kernel, dim3(grid_for((size_t)rows * cols)), dim3(256), 0, st, src, lds_, dst, ldd, rows, cols);
     return eg_check_launch("copy2d");
+}
+
+int egi_swap01(const void* in, void* out, int A, int B, size_t inner_words, hipStream_t st) {
+    if ((inner_words & 3) == 0 && eg_aligned16(in) && eg_aligned16(out)) {
+        const size_t q = inner_words / 4;
+        hipLaunchKernelGGL((swap01_kernel<u32x4_t>), dim3(grid_for((size_t)A * B * q)), dim3(256), 0, st, reinterpret_cast<const u32x4_t*>(in),
+                           reinterpret_cast<u32x4_t*>(out), A, B, q);
+    } else {
+        hipLaunchKernelGGL((swap01_kernel<unsigned int>), dim3(grid_for((size_t)A * B * inner_words)), dim3(256), 0, st,
+                           reinterpret_cast<const unsigned int*>(in), reinterpret_cast<unsigned int*>(out), A, B, inner_words);
+    }
+    return eg_check_launch("swap01");
+}
+int egi_rollout_handoff(const float* pose, const float* prior_in, const float* alpha, float* track, float* windows, float* prior_out, int U,
+                        int W, int w, int F, int P, int D, hipStream_t st) {
+    hipLaunchKernelGGL(rollout_handoff_kernel, dim3(grid_for((size_t)U * F * D)), dim3(256), 0, st, pose, prior_in, alpha, track, windows,
+                       prior_out, U, W, w, F, P, D);
+    return eg_check_launch("rollout_handoff");
 }
 
 struct EgiPriorW {

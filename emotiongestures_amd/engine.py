@@ -146,6 +146,61 @@ class GeneratorEngine:
                                                      _ptr(pose), _ptr(ws), ws_bytes, _stream(dev)), "eg_generator_forward_draws")
         return pose
 
+    # ---- long-form synthesis ----
+    def _rollout_args(self, spec, text, seed_pose, sampled, alpha):
+        """Shape contract of forward_rollout (checked before anything touches the device); returns (U, W)."""
+        c = self.cfg
+        if spec.dim() != 4 or tuple(spec.shape[2:]) != (c.n_mels, c.spec_len):
+            raise L.EgError(f"spec shape {tuple(spec.shape)} != (U,W,{c.n_mels},{c.spec_len})")
+        U, W = int(spec.shape[0]), int(spec.shape[1])
+        if U < 1:
+            raise L.EgError(f"spec: utterances U={U} (need >= 1)")
+        if W < 1:
+            raise L.EgError(f"spec: windows W={W} (need >= 1)")
+        if tuple(text.shape) != (U, W, c.text_len):
+            raise L.EgError(f"text shape {tuple(text.shape)} != ({U},{W},{c.text_len})")
+        if tuple(seed_pose.shape) != (U, c.prior_frames, c.pose_dim):
+            raise L.EgError(f"seed_pose shape {tuple(seed_pose.shape)} != ({U},{c.prior_frames},{c.pose_dim})")
+        if sampled is not None and tuple(sampled.shape) != (U, W, c.frames, c.d_model):
+            raise L.EgError(f"sampled shape {tuple(sampled.shape)} != ({U},{W},{c.frames},{c.d_model})")
+        if alpha is not None and tuple(alpha.shape) != (c.prior_frames,):
+            raise L.EgError(f"alpha shape {tuple(alpha.shape)} != ({c.prior_frames},)")
+        return U, W
+
+    @_locked
+    def forward_rollout(self, spec, text, seed_pose, sampled=None, alpha=None, want_windows=False, want_aux=False, slot=0):
+        """eg_generator_forward_rollout: W consecutive windows of U utterances, each seeded with the raw last prior_frames poses of the one
+        before it, stitched into one track with a linear cross-fade over the overlap.
+        spec [U,W,n_mels,spec_len], text [U,W,text_len], seed_pose [U,P,D], sampled [U,W,F,d_model] or None, alpha [P] or None
+        (alpha[j] = (j+1)/(P+1)).  Returns a dict: track [U, W*(F-P)+P, D], emotion_prediction [U,W,8], windows [U,W,F,D] with
+        want_windows, emotion_feature / semantic_feature [U,W,F,d_model] and text_embedding [U,W,text_len,512] with want_aux."""
+        U, W = self._rollout_args(spec, text, seed_pose, sampled, alpha)
+        if self.arena is None:
+            raise L.EgError("GeneratorEngine.forward_rollout before load_weights")
+        dev = self.arena.device
+        c = self.cfg
+        spec, text, seed_pose = _need_cuda(spec, "spec"), _need_cuda(text, "text", torch.int64), _need_cuda(seed_pose, "seed_pose")
+        sampled = None if sampled is None else _need_cuda(sampled, "sampled")
+        alpha = None if alpha is None else _need_cuda(alpha, "alpha")
+        ws_bytes = self._lib.eg_generator_rollout_workspace_bytes(self._h, U, W)
+        if ws_bytes <= 0:
+            raise L.EgError(f"eg_generator_rollout_workspace_bytes: unsupported U={U} W={W}")
+        ws = self._workspace(("rollout", U, W) if slot == 0 else ("rollout", U, W, slot), ws_bytes, dev)
+        F, H = c.frames, c.frames - c.prior_frames
+        out = {"track": torch.empty(U, W * H + c.prior_frames, c.pose_dim, device=dev),
+               "emotion_prediction": torch.empty(U, W, 8, device=dev)}
+        if want_windows:
+            out["windows"] = torch.empty(U, W, F, c.pose_dim, device=dev)
+        if want_aux:
+            out["emotion_feature"] = torch.empty(U, W, F, c.d_model, device=dev)
+            out["semantic_feature"] = torch.empty(U, W, F, c.d_model, device=dev)
+            out["text_embedding"] = torch.empty(U, W, c.text_len, 512, device=dev)
+        L.check(self._lib.eg_generator_forward_rollout(
+            self._h, _ptr(self.arena), U, W, _ptr(spec), _ptr(text), _ptr(seed_pose), _ptr(sampled), _ptr(alpha), _ptr(out["track"]),
+            _ptr(out.get("windows")), _ptr(out["emotion_prediction"]), _ptr(out.get("emotion_feature")), _ptr(out.get("semantic_feature")),
+            _ptr(out.get("text_embedding")), _ptr(ws), ws_bytes, _stream(dev)), "eg_generator_forward_rollout")
+        return out
+
     def tap(self, name: str, batch: int) -> torch.Tensor:
         """Copy of an intermediate of the last forward(batch) (parity tests)."""
         ws = self._ws[("fwd", batch)]
@@ -247,3 +302,20 @@ class MelFrontEnd:
         L.check(self._lib.eg_melspectrogram(_ptr(audio), B, n, _ptr(self.fb), _ptr(self.win), _ptr(self.tw), _ptr(self.band), _ptr(spec), out_frames,
                                             _ptr(ws), nbytes, _stream(self.device)), "eg_melspectrogram")
         return spec
+
+    def windows(self, audio: torch.Tensor, windows: int, hop_samples: int, n_samples: int, out_frames: Optional[int] = None,
+                slot: int = 0) -> torch.Tensor:
+        """Long recordings [U, total_samples] -> spec [U, windows, 128, out_frames]: window w is the spectrogram of samples
+        [w*hop_samples, w*hop_samples + n_samples) taken as a clip of its own, gathered on the device; a window that runs past the end is completed by symmetric padding
+        of its own samples, as make_audio_fixed_length does."""
+        audio = _need_cuda(audio, "audio")
+        if audio.dim() != 2:
+            raise L.EgError(f"audio shape {tuple(audio.shape)} != (U, total_samples)")
+        if windows < 1 or hop_samples < 1:
+            raise L.EgError(f"windows={windows} hop_samples={hop_samples} (need >= 1)")
+        U, total = audio.shape
+        clips = torch.empty(U * windows, n_samples, device=self.device)
+        L.check(self._lib.eg_window_gather(_ptr(audio), U, total, windows, hop_samples, n_samples, _ptr(clips), _stream(self.device)),
+                "eg_window_gather")
+        spec = self(clips, out_frames, slot)
+        return spec.view(U, windows, 128, spec.shape[-1])

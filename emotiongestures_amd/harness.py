@@ -453,3 +453,44 @@ def evaluate(generator, vae, fgd: MLP_Reconstruct, classifier: Optional[Skeleton
     if beat:
         out["beat"] = float(np.mean(np.concatenate(beats)))
     return out
+
+
+# ---- long-form synthesis ---------------------------------------------------------------------------------------------
+def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch.Tensor, labels: Optional[torch.Tensor] = None,
+               hop_samples: Optional[int] = None, n_samples: Optional[int] = None, windows: Optional[int] = None,
+               z: Optional[torch.Tensor] = None, alpha: Optional[torch.Tensor] = None, fps: int = 15, sample_rate: int = 16000,
+               want_windows: bool = False, want_aux: bool = False, mel=None) -> Dict[str, torch.Tensor]:
+    """One gesture track per utterance from raw 16 kHz audio: windows -> mel -> optional CVAE sample per window -> roll-out.
+
+    ``models = (generator, vae | None)``, eval mode, on the GPU.  ``audio [U, total_samples]``; ``text [U, W, 60]`` (the words of every
+    window); ``seed_pose [U, prior_frames, pose_dim]``; ``labels`` (with a VAE) ``[U, 8]`` or ``[U, W, 8]`` one-hot, ``z [U, W, 32]``
+    fixes the latents (default torch.randn on the CPU generator, as MLP_Reconstruct_v3.sample draws them).  Window w covers samples
+    ``[w*hop_samples, w*hop_samples + n_samples)``; the defaults tie them to the generator's geometry: ``hop_samples`` is the duration of
+    ``frames - prior_frames`` poses at ``fps``, ``n_samples = (spec_len - 1) * 512`` (the shortest clip whose spectrogram has spec_len
+    columns).  ``windows`` defaults to ``text.shape[1]``.  Returns GeneratorEngine.forward_rollout's dict plus ``"spec"``."""
+    from .engine import MelFrontEnd
+    gen, vae = models
+    _eval_only(gen)
+    eng = gen.engine()
+    c = eng.cfg
+    if audio.dim() != 2:
+        raise L.EgError(f"audio shape {tuple(audio.shape)} != (U, total_samples)")
+    U = audio.shape[0]
+    W = int(text.shape[1]) if windows is None and text.dim() == 3 else windows
+    if W is None or W < 1:
+        raise L.EgError(f"windows={W} (need >= 1): text must be [U, W, {c.text_len}] or `windows` given")
+    hop = int(round((c.frames - c.prior_frames) * sample_rate / fps)) if hop_samples is None else int(hop_samples)
+    n = (c.spec_len - 1) * 512 if n_samples is None else int(n_samples)
+    mel = MelFrontEnd(audio.device) if mel is None else mel
+    with torch.no_grad():
+        spec = mel.windows(audio, W, hop, n, out_frames=c.spec_len)
+        sampled = None
+        if vae is not None:
+            if labels is None:
+                raise L.EgError("labels: needed when a VAE is given ([U, 8] or [U, W, 8] one-hot)")
+            lab = labels.to(audio.device)
+            lab = (lab[:, None, :].expand(U, W, 8) if lab.dim() == 2 else lab).reshape(U * W, 8).contiguous()
+            sampled = vae.sample(lab, z=None if z is None else z.reshape(U * W, 32)).view(U, W, c.frames, c.d_model)
+        out = eng.forward_rollout(spec, text, seed_pose, sampled, alpha=alpha, want_windows=want_windows, want_aux=want_aux)
+    out["spec"] = spec
+    return out

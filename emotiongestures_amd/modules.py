@@ -762,6 +762,16 @@ class Transformer(ReplicaAware, nn.Module):
         _eval_only(self)
         return self.engine().forward_draws(input_spectrum, prior_seq, sampled_emotion_features, slot=slot)
 
+    def synthesize(self, input_spectrum, text, seed_pose, sampled_emotion_features=None, *, alpha=None, want_windows=False,
+                   want_aux=False, slot=0):
+        """Long-form synthesis: input_spectrum [U,W,n_mels,spec_len], text [U,W,text_len], seed_pose [U,prior_frames,pose_dim],
+        sampled_emotion_features [U,W,frames,d_model] or None.  Window w >= 1 is seeded with the raw last prior_frames poses of window
+        w-1; the dict returned holds track [U, W*(frames-prior_frames)+prior_frames, pose_dim] (overlaps cross-faded with `alpha`,
+        default (j+1)/(prior_frames+1)), emotion_prediction [U,W,8] and the optional outputs of GeneratorEngine.forward_rollout."""
+        _eval_only(self)
+        return self.engine().forward_rollout(input_spectrum, text, seed_pose, sampled_emotion_features, alpha=alpha,
+                                             want_windows=want_windows, want_aux=want_aux, slot=slot)
+
 
 class TransformerMemory(Transformer):
     _variant = "memory"

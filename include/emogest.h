@@ -174,6 +174,34 @@ int eg_generator_forward_draws(const EgGenerator* g, const float* arena, int32_t
                                void* workspace, int64_t workspace_bytes, void* stream);
 int64_t eg_generator_draws_workspace_bytes(const EgGenerator* g, int32_t batch, int32_t draws);
 
+/* Long-form synthesis: W consecutive windows of U utterances rolled out on the device.  Window 0 is seeded with seed_pose; window
+ * w >= 1 with the RAW last prior_frames poses of window w-1 (never the blended track).  Every step sees the U windows of index w as
+ * one batch (the memory variant's TM_Memory_Net couples the utterances of a step, never the windows of an utterance).
+ * With F = frames, P = prior_frames, H = F - P, D = pose_dim:
+ *   spec   [U, W, n_mels, spec_len]     text [U, W, text_len] int64 (may be NULL unless text_embedding is wanted)
+ *   seed_pose [U, P, D]                 sampled [U, W, F, d_model] or NULL (the generator's own emotion feature, as in forward)
+ *   alpha  [P] overlap weights on the device, or NULL for alpha[j] = (j + 1) / (P + 1)
+ *   track  [U, W*H + P, D]:  rows [0, F) = pose_0;  for w >= 1 row w*H + j = (1 - alpha[j]) * pose_{w-1}[H + j] + alpha[j] * pose_w[j]
+ *          for j < P (two rounded products, one rounded sum) and pose_w[j] for P <= j < F
+ *   optional (NULL to skip): windows [U, W, F, D] raw per-window poses, emotion_prediction [U, W, 8],
+ *          emotion_feature / semantic_feature [U, W, F, d_model], text_embedding [U, W, text_len, 512]
+ * Two phases on `stream`, no allocation, host round trip or synchronisation (capturable into one hipGraph for fixed U, W):
+ *   A, batch U*W in window-major order: text branch (only when text_embedding is wanted), audio tower, projections, classifier header,
+ *      fusion, encoder, and every decoder layer's K|V projection of the encoder output, kept as fp32 (what the attention kernel reads);
+ *   B, W steps of U clips: prior encoder -> decoder layers over the step's K|V slice -> post_projector -> one hand-off launch that
+ *      writes track, windows[:, w] and the next step's prior.
+ * Requires utterances >= 1, windows >= 1, n_layers <= 8, utterances * windows <= 2^20.  fold_affine generators are supported (the folded
+ * products are used in both phases).  The branch streams of `concurrent` generators are not used: everything is enqueued on `stream`.
+ * Phase B takes the product paths eg_generator_forward takes at batch U (the one-clip split-K of w_2 included); phase A takes those of
+ * batch U*W, so against a loop of eg_generator_forward calls the result is bitwise equal where the products are chunking-invariant
+ * (U >= 2) and equal to rounding at U == 1. */
+int eg_generator_forward_rollout(const EgGenerator* g, const float* arena, int32_t utterances, int32_t windows,
+                                 const float* spec, const int64_t* text, const float* seed_pose, const float* sampled,
+                                 const float* alpha, float* track, float* windows_out, float* emotion_prediction,
+                                 float* emotion_feature, float* semantic_feature, float* text_embedding,
+                                 void* workspace, int64_t workspace_bytes, void* stream);
+int64_t eg_generator_rollout_workspace_bytes(const EgGenerator* g, int32_t utterances, int32_t windows);
+
 /* Intermediate taps of the most recent eg_generator_forward on this workspace (for parity tests):
  * returns the device pointer inside `workspace` and the element count; names: "stem", "layer1", "layer2", "layer3"
  * (NHWC, only when the generator was created with keep_taps), "audio_map", "audio_feat", "prior_enc", "fusion", "enc_out",
@@ -227,6 +255,14 @@ int64_t eg_mel_workspace_bytes(int32_t batch, int32_t n_samples);
 int eg_melspectrogram(const float* audio, int32_t batch, int32_t n_samples, const float* d_melfb_t,
                       const float* d_window, const float* d_twiddle, const int32_t* d_band, float* spec, int32_t out_frames,
                       void* workspace, int64_t workspace_bytes, void* stream);
+/* Overlapping windows of long recordings as a batch of clips, for eg_melspectrogram (each window is its own clip: centre padding and
+ * power_to_db(ref=max) are per clip upstream, so windows cannot share STFT frames):
+ *   audio [utterances, total_samples] -> out [utterances * windows, n_samples], out[u*W + w, i] = audio[u, w*hop_samples + i],
+ * A window that runs past the end of the track is completed from its own L = total_samples - w*hop_samples samples as
+ * make_audio_fixed_length does (utils/train_utils_BEAT.py:220-226, np.pad mode="symmetric": mirrored about the end, period 2L).
+ * Every window must start inside the track: (windows - 1) * hop_samples < total_samples. */
+int eg_window_gather(const float* audio, int32_t utterances, int64_t total_samples, int32_t windows, int64_t hop_samples,
+                     int32_t n_samples, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Beat-alignment score = model/Beat_score_v2.py alignment(sigma, order): load_audio + load_pose +

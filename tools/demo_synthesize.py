@@ -1,0 +1,54 @@
+#!/usr/bin/env python3
+"""Long-form synthesis walk-through on synthetic data, every stage on the HIP path:
+
+  raw 16 kHz recordings [U, total_samples] --eg_window_gather + extract_melspectrogram (GPU)--> one spectrogram per window
+  --MLP_Reconstruct_v3.sample per window--> emotion maps --eg_generator_forward_rollout (everything the prior does not reach once at
+  batch U*W, then W dependent decoder steps, each seeded with the raw last 4 poses of the one before)--> one gesture track per recording.
+
+Weights are synthetic (integer hash), so the poses carry no meaning; the script shows the call sequence and prints the shapes, the seam
+statistics of the track and the time of one call.  usage: demo_synthesize.py [utterances=4] [seconds=60]"""
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+from emotiongestures_amd import harness as H
+from emotiongestures_amd.builders import build_mirror
+from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
+from emotiongestures_amd.synth import load_synth_weights, synth_audio
+
+U = int(sys.argv[1]) if len(sys.argv) > 1 else 4
+seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 60.0
+dev = torch.device("cuda:0")
+FRAMES, POSE_DIM, PRIOR, FPS = 34, 126, 4, 15           # TED timing: 34 poses @ 15 fps, 4 of them the prior
+HOP = FRAMES - PRIOR
+hop_samples = int(round(HOP * 16000 / FPS))              # 30 poses = 2 s = 32 000 samples
+total = int(seconds * 16000)
+W = (total - 1) // hop_samples + 1                       # every window starts inside the recording; the last is completed by mirroring
+
+audio = torch.from_numpy(synth_audio(U, total, seed=90)).to(dev)
+text = torch.zeros(U, W, 60, dtype=torch.int64, device=dev)
+seed_pose = torch.zeros(U, PRIOR, POSE_DIM, device=dev)
+labels = torch.nn.functional.one_hot(torch.arange(U) % 8, 8).float().to(dev)     # one emotion per recording
+
+gen = build_mirror("spatial", FRAMES, POSE_DIM, PRIOR, PRIOR, seed=7, precision="bf16x3").to(dev)
+vae = load_synth_weights(MLP_Reconstruct_v3(frames=FRAMES), 7).eval().to(dev)
+z = torch.randn(U, W, 32)
+out = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, want_windows=True)          # warm-up (packs weights, allocates workspaces)
+torch.cuda.synchronize()
+t0 = time.perf_counter()
+out = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, want_windows=True)
+torch.cuda.synchronize()
+dt = time.perf_counter() - t0
+
+track, windows = out["track"], out["windows"]
+print(f"{U} recordings x {seconds:.0f} s -> {W} windows of {FRAMES} poses (hop {HOP}) -> track {tuple(track.shape)} = {track.shape[1] / FPS:.1f} s at {FPS} fps")
+step = (track[:, 1:] - track[:, :-1]).norm(dim=2)                       # pose change per frame
+seams = torch.tensor([w * HOP + j for w in range(1, W) for j in range(PRIOR + 1)]) - 1
+print(f"mean |pose[t+1] - pose[t]|: {float(step.mean()):.4f} over the track, {float(step[:, seams].mean()):.4f} across the cross-faded seams")
+print(f"window 1 beyond its overlap (rows [{HOP + PRIOR}, {2 * HOP})) appears raw in the track: "
+      f"{bool(torch.equal(track[:, HOP + PRIOR: FRAMES + HOP - PRIOR], windows[:, 1, PRIOR: HOP]))}")
+print(f"one call (mel + CVAE + roll-out, eager): {1e3 * dt:.2f} ms = {1e3 * dt / (U * track.shape[1] / FPS):.4f} ms per second of audio")
