@@ -73,6 +73,11 @@ SIGNATURES = {
     "eg_generator_draws_workspace_bytes": (_L, [_P, _I, _I]),
     "eg_generator_forward_rollout": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "eg_generator_rollout_workspace_bytes": (_L, [_P, _I, _I]),
+    "eg_stream_state_bytes": (_L, [_P, _I, _I, _I]),
+    "eg_stream_reset": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "eg_stream_push": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "eg_generator_stream_step": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "eg_stream_tail": (C.c_int, [_P, _P, _I, _I, _I, _P, _P]),
     "eg_generator_tap": (C.c_int, [_P, _I, _P, C.c_char_p, C.POINTER(_P), C.POINTER(_L)]),
     "eg_cvae_default_config": (C.c_int, [C.POINTER(EgCvaeConfig)]),
     "eg_cvae_create": (C.c_int, [C.POINTER(EgCvaeConfig), C.POINTER(_P)]),

@@ -63,6 +63,16 @@ static inline int64_t eg_round_up(int64_t x, int64_t m) { return (x + m - 1) / m
 static inline int eg_cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // ---- device helpers ------------------------------------------------------------------------
+// The cross-fade of one overlap element, shared by the roll-out's hand-off (misc.hip) and the stream's (stream.hip) so that the two cannot
+// drift: (1 - a) * old + a * fresh with a = alpha[j] (alpha == nullptr: (j + 1) / (P + 1)) as two rounded products and one rounded sum --
+// no v_fma here, whatever the translation unit's default: the arithmetic a host restatement in fp32 reproduces bit for bit.
+__device__ __forceinline__ float handoff_blend(const float* __restrict__ alpha, int j, int P, float old, float fresh) {
+#pragma clang fp contract(off)
+    const float a = alpha ? alpha[j] : (float)(j + 1) / (float)(P + 1);
+    const float keep = (1.f - a) * old, take = a * fresh;
+    return keep + take;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

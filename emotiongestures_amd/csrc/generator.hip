@@ -1003,6 +1003,98 @@ extern "C" int eg_generator_forward_rollout(const EgGenerator* g, const float* a
     return EG_OK;
 }
 
+// ---- streaming: a device-resident session (audio ring, prior, counters) and a step whose launches do not depend on the step index -----
+int egi_stream_reset(float* ring, float* prior, int64_t* ctr, const int32_t* mask, const float* seed, int U, int64_t ring_len, int PD,
+                     hipStream_t st);
+int egi_stream_push(float* ring, int64_t* ctr, const float* chunk, const int32_t* ends, float* clips, int U, int64_t hop, int n, int lag,
+                    hipStream_t st);
+int egi_stream_handoff(const float* pose, float* prior, int64_t* ctr, const float* alpha, float* rows_out, int32_t* valid_out,
+                       float* window_out, int U, int F, int P, int D, hipStream_t st);
+namespace {
+struct StreamState { int64_t ring, prior, ctr, total, ring_len; int lag; };      // byte offsets into the state buffer
+int64_t stream_lag(int hop, int n) { return ((int64_t)n + hop - 1) / hop; }         // 64-bit: n + hop may pass 2^31
+bool stream_geometry_ok(const EgGenerator* g, int U, int hop, int n) {
+    if (!g || U < 1 || U > (1 << 20) || hop < 1 || n < 1) return false;
+    const int64_t per = stream_lag(hop, n) * hop + n;       // the push kernel indexes a row's ring and clip with 32-bit integers
+    return per < ((int64_t)1 << 31) && (int64_t)U * per < ((int64_t)1 << 40);
+}
+StreamState carve_stream(const EgGenerator* g, int U, int hop, int n) {
+    StreamState s;
+    s.lag = (int)stream_lag(hop, n);
+    s.ring_len = (int64_t)s.lag * hop;
+    Carver cv;
+    s.ring = cv.take((int64_t)U * s.ring_len);
+    s.prior = cv.take((int64_t)U * g->cfg.prior_frames * g->cfg.pose_dim);
+    s.ctr = cv.take((int64_t)U * 4 * 2);        // int64 [4, U]
+    s.total = cv.off;
+    return s;
+}
+inline int64_t* stream_ctr(void* state, const StreamState& s) { return reinterpret_cast<int64_t*>(reinterpret_cast<char*>(state) + s.ctr); }
+}  // namespace
+
+extern "C" int64_t eg_stream_state_bytes(const EgGenerator* g, int32_t rows, int32_t hop_samples, int32_t n_samples) {
+    if (!stream_geometry_ok(g, rows, hop_samples, n_samples)) return 0;
+    return carve_stream(g, rows, hop_samples, n_samples).total;
+}
+
+extern "C" int eg_stream_reset(const EgGenerator* g, void* state, int32_t rows, int32_t hop_samples, int32_t n_samples,
+                               const int32_t* row_mask, const float* seed_pose, void* stream) {
+    EG_REQUIRE(g && state && seed_pose, EG_ERR_BAD_ARG, "eg_stream_reset: null pointer");
+    EG_REQUIRE(stream_geometry_ok(g, rows, hop_samples, n_samples), EG_ERR_BAD_ARG, "eg_stream_reset: rows=%d hop_samples=%d n_samples=%d", rows,
+               hop_samples, n_samples);
+    EG_REQUIRE(eg_aligned16(state), EG_ERR_ALIGN, "eg_stream_reset: 16-byte alignment");
+    const StreamState s = carve_stream(g, rows, hop_samples, n_samples);
+    return egi_stream_reset(P(state, s.ring), P(state, s.prior), stream_ctr(state, s), row_mask, seed_pose, rows, s.ring_len,
+                            g->cfg.prior_frames * g->cfg.pose_dim, (hipStream_t)stream);
+}
+
+extern "C" int eg_stream_push(const EgGenerator* g, void* state, int32_t rows, int32_t hop_samples, int32_t n_samples, const float* chunk,
+                              const int32_t* ends, float* clips, void* stream) {
+    EG_REQUIRE(g && state && chunk && clips, EG_ERR_BAD_ARG, "eg_stream_push: null pointer");
+    EG_REQUIRE(stream_geometry_ok(g, rows, hop_samples, n_samples), EG_ERR_BAD_ARG, "eg_stream_push: rows=%d hop_samples=%d n_samples=%d", rows,
+               hop_samples, n_samples);
+    EG_REQUIRE(eg_aligned16(state), EG_ERR_ALIGN, "eg_stream_push: 16-byte alignment");
+    const StreamState s = carve_stream(g, rows, hop_samples, n_samples);
+    return egi_stream_push(P(state, s.ring), stream_ctr(state, s), chunk, ends, clips, rows, hop_samples, n_samples, s.lag, (hipStream_t)stream);
+}
+
+extern "C" int eg_stream_tail(const EgGenerator* g, const void* state, int32_t rows, int32_t hop_samples, int32_t n_samples, float* out,
+                              void* stream) {
+    EG_REQUIRE(g && state && out, EG_ERR_BAD_ARG, "eg_stream_tail: null pointer");
+    EG_REQUIRE(stream_geometry_ok(g, rows, hop_samples, n_samples), EG_ERR_BAD_ARG, "eg_stream_tail: rows=%d hop_samples=%d n_samples=%d", rows,
+               hop_samples, n_samples);
+    const StreamState s = carve_stream(g, rows, hop_samples, n_samples);
+    const int PD = g->cfg.prior_frames * g->cfg.pose_dim;
+    return egi_copy2d(P(const_cast<void*>(state), s.prior), PD, out, PD, rows, PD, (hipStream_t)stream);
+}
+
+extern "C" int eg_generator_stream_step(const EgGenerator* g, const float* arena, void* state, int32_t U, int32_t hop_samples,
+                                        int32_t n_samples, const float* spec, const int64_t* text, const float* sampled, const float* alpha,
+                                        float* rows_out, int32_t* valid_out, float* window_out, float* emotion_prediction, void* ws,
+                                        int64_t ws_bytes, void* stream) {
+    EG_REQUIRE(g && arena && state && spec && rows_out && valid_out && ws, EG_ERR_BAD_ARG, "eg_generator_stream_step: null pointer");
+    EG_REQUIRE(stream_geometry_ok(g, U, hop_samples, n_samples), EG_ERR_BAD_ARG, "eg_generator_stream_step: rows=%d hop_samples=%d n_samples=%d", U,
+               hop_samples, n_samples);
+    const GenWs w = carve(g, U);
+    EG_REQUIRE(ws_bytes >= w.total, EG_ERR_WORKSPACE, "eg_generator_stream_step: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)w.total);
+    EG_REQUIRE(eg_aligned16(ws) && eg_aligned16(arena) && eg_aligned16(spec) && eg_aligned16(state), EG_ERR_ALIGN,
+               "eg_generator_stream_step: 16-byte alignment");
+    const StreamState s = carve_stream(g, U, hop_samples, n_samples);
+    hipStream_t st = (hipStream_t)stream;
+    const EgGeneratorConfig& c = g->cfg;
+    const int F = c.frames, D = c.d_model, rows = U * F;
+    float* prior = P(state, s.prior);
+    // the launches of eg_generator_forward at batch U, all on `stream` (the branch streams of `concurrent` generators are not used)
+    if (text) EG_TRY(run_text(g, arena, text, P(ws, w.t_out), w, ws, U, st));
+    EG_TRY(run_prior(g, arena, prior, w, ws, U, st));
+    EG_TRY(run_audio_tower(g, arena, spec, w, ws, U, st));
+    EG_TRY(run_heads(g, arena, P(ws, w.emo), P(ws, w.sem), emotion_prediction ? emotion_prediction : P(ws, w.cls_out), w, ws, U, st));
+    EG_TRY(egi_add(sampled ? sampled : P(ws, w.emo), P(ws, w.sem), P(ws, w.fus_in), (size_t)rows * D, D, 0, st));
+    EG_TRY(run_transformer(g, arena, P(ws, w.fus_in), act(P(ws, w.prior_enc), D, P(ws, w.im_p[1]), D), P(ws, w.pose), w, ws, U, st));
+    return egi_stream_handoff(P(ws, w.pose), prior, stream_ctr(state, s), alpha, rows_out, valid_out, window_out, U, F, c.prior_frames, c.pose_dim,
+                              st);
+}
+
 extern "C" int eg_generator_tap(const EgGenerator* g, int32_t batch, void* ws, const char* name, float** d_ptr, int64_t* numel) {
     EG_REQUIRE(g && ws && name && d_ptr && numel && batch > 0, EG_ERR_BAD_ARG, "eg_generator_tap: null pointer");
     const GenWs w = carve(g, batch);

@@ -450,12 +450,7 @@ __global__ __launch_bounds__(256) void rollout_handoff_kernel(const float* __res
         const int d = (int)(i % D), j = (int)((i / D) % F), u = (int)(i / ((size_t)D * F));
         const float v = pose[i];
         float t = v;
-        if (w > 0 && j < P) {
-#pragma clang fp contract(off)      // the products are rounded before the sum: no v_fma here, whatever the translation unit's default
-            const float a = alpha ? alpha[j] : (float)(j + 1) / (float)(P + 1);
-            const float keep = (1.f - a) * prior_in[((size_t)u * P + j) * D + d], take = a * v;
-            t = keep + take;
-        }
+        if (w > 0 && j < P) t = handoff_blend(alpha, j, P, prior_in[((size_t)u * P + j) * D + d], v);     // common.h: rounded products, rounded sum
         track[((size_t)u * T + (size_t)w * H + j) * D + d] = t;
         if (windows) windows[(((size_t)u * W + w) * F + j) * D + d] = v;
         if (j >= H) prior_out[((size_t)u * P + (j - H)) * D + d] = v;

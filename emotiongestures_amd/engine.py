@@ -201,6 +201,114 @@ class GeneratorEngine:
             _ptr(out.get("text_embedding")), _ptr(ws), ws_bytes, _stream(dev)), "eg_generator_forward_rollout")
         return out
 
+    # ---- streaming synthesis (a session's state buffer is owned by the caller: emotiongestures_amd.streaming.GestureStream) ----
+    def _stream_geometry(self, rows, hop_samples, n_samples):
+        if int(rows) < 1 or int(hop_samples) < 1 or int(n_samples) < 1:
+            raise L.EgError(f"stream: rows={rows} hop_samples={hop_samples} n_samples={n_samples} (need >= 1)")
+        return int(rows), int(hop_samples), int(n_samples)
+
+    def _stream_state(self, state, geom):
+        nbytes = self.stream_state_bytes(*geom)
+        if not isinstance(state, torch.Tensor) or not state.is_cuda:
+            raise L.EgError("stream state: the HIP path needs a GPU buffer (torch.uint8, stream_state_bytes long); there is no CPU fallback")
+        if state.dtype != torch.uint8 or state.numel() < nbytes or not state.is_contiguous():
+            raise L.EgError(f"stream state: need a contiguous uint8 buffer of {nbytes} bytes (got {state.dtype}, {state.numel()})")
+        return state
+
+    def stream_state_bytes(self, rows, hop_samples, n_samples) -> int:
+        geom = self._stream_geometry(rows, hop_samples, n_samples)
+        nbytes = self._lib.eg_stream_state_bytes(self._h, *geom)
+        if nbytes <= 0:
+            raise L.EgError(f"eg_stream_state_bytes: unsupported rows={geom[0]} hop_samples={geom[1]} n_samples={geom[2]}")
+        return int(nbytes)
+
+    def _stream_step_args(self, U, spec, text, sampled, alpha):
+        """Shape contract of stream_step (checked before anything touches the device)."""
+        c = self.cfg
+        if tuple(spec.shape) != (U, c.n_mels, c.spec_len):
+            raise L.EgError(f"spec shape {tuple(spec.shape)} != ({U},{c.n_mels},{c.spec_len})")
+        if text is not None and tuple(text.shape) != (U, c.text_len):
+            raise L.EgError(f"text shape {tuple(text.shape)} != ({U},{c.text_len})")
+        if sampled is not None and tuple(sampled.shape) != (U, c.frames, c.d_model):
+            raise L.EgError(f"sampled shape {tuple(sampled.shape)} != ({U},{c.frames},{c.d_model})")
+        if alpha is not None and tuple(alpha.shape) != (c.prior_frames,):
+            raise L.EgError(f"alpha shape {tuple(alpha.shape)} != ({c.prior_frames},)")
+
+    @_locked
+    def stream_reset(self, state, rows, hop_samples, n_samples, seed_pose, row_mask=None):
+        """eg_stream_reset: seed_pose [U,P,D]; row_mask int32 [U] on the device (non-zero = reset that row) or None for every row."""
+        geom = self._stream_geometry(rows, hop_samples, n_samples)
+        c = self.cfg
+        if tuple(seed_pose.shape) != (geom[0], c.prior_frames, c.pose_dim):
+            raise L.EgError(f"seed_pose shape {tuple(seed_pose.shape)} != ({geom[0]},{c.prior_frames},{c.pose_dim})")
+        if row_mask is not None and tuple(row_mask.shape) != (geom[0],):
+            raise L.EgError(f"row_mask shape {tuple(row_mask.shape)} != ({geom[0]},)")
+        state = self._stream_state(state, geom)
+        seed_pose = _need_cuda(seed_pose, "seed_pose")
+        row_mask = None if row_mask is None else _need_cuda(row_mask, "row_mask", torch.int32)
+        L.check(self._lib.eg_stream_reset(self._h, _ptr(state), *geom, _ptr(row_mask), _ptr(seed_pose), _stream(state.device)), "eg_stream_reset")
+
+    @_locked
+    def stream_push(self, state, rows, hop_samples, n_samples, chunk, ends=None, clips=None):
+        """eg_stream_push: chunk [U,hop], ends int32 [U] on the device or None -> clips [U,n] (written in place when given)."""
+        geom = self._stream_geometry(rows, hop_samples, n_samples)
+        if tuple(chunk.shape) != geom[:2]:
+            raise L.EgError(f"audio shape {tuple(chunk.shape)} != ({geom[0]},{geom[1]})")
+        if ends is not None and tuple(ends.shape) != (geom[0],):
+            raise L.EgError(f"ends shape {tuple(ends.shape)} != ({geom[0]},)")
+        if clips is not None and (tuple(clips.shape) != (geom[0], geom[2]) or clips.dtype != torch.float32 or not clips.is_contiguous()):
+            raise L.EgError(f"clips: need a contiguous float32 [{geom[0]},{geom[2]}]")
+        state = self._stream_state(state, geom)
+        chunk = _need_cuda(chunk, "audio")
+        ends = None if ends is None else _need_cuda(ends, "ends", torch.int32)
+        if clips is None:
+            clips = torch.empty(geom[0], geom[2], device=state.device)
+        elif not clips.is_cuda:
+            raise L.EgError("clips: the HIP path needs a GPU tensor; there is no CPU fallback")
+        L.check(self._lib.eg_stream_push(self._h, _ptr(state), *geom, _ptr(chunk), _ptr(ends), _ptr(clips), _stream(state.device)), "eg_stream_push")
+        return clips
+
+    @_locked
+    def stream_step(self, state, rows, hop_samples, n_samples, spec, text=None, sampled=None, alpha=None, want_window=False, want_prediction=False,
+                    workspace=None):
+        """eg_generator_stream_step: the generator at batch U seeded from the state's prior, then the stream's hand-off.  Returns a dict:
+        rows [U,H,D], valid int32 [U], and window [U,F,D] / emotion_prediction [U,8] when wanted.  `workspace`: a private uint8 buffer of
+        eg_generator_workspace_bytes(U) (a session that bakes it into a graph owns one); default: this engine's own."""
+        geom = self._stream_geometry(rows, hop_samples, n_samples)
+        U = geom[0]
+        self._stream_step_args(U, spec, text, sampled, alpha)
+        if self.arena is None:
+            raise L.EgError("GeneratorEngine.stream_step before load_weights")
+        state = self._stream_state(state, geom)
+        dev = self.arena.device
+        c = self.cfg
+        spec = _need_cuda(spec, "spec")
+        text = None if text is None else _need_cuda(text, "text", torch.int64)
+        sampled = None if sampled is None else _need_cuda(sampled, "sampled")
+        alpha = None if alpha is None else _need_cuda(alpha, "alpha")
+        ws_bytes = self._lib.eg_generator_workspace_bytes(self._h, U)
+        ws = self._workspace(("stream", U), ws_bytes, dev) if workspace is None else workspace
+        if ws.numel() < ws_bytes or not ws.is_cuda:
+            raise L.EgError(f"stream_step: workspace of {ws.numel()} bytes on {ws.device} (need {ws_bytes} on the GPU)")
+        out = {"rows": torch.empty(U, c.frames - c.prior_frames, c.pose_dim, device=dev), "valid": torch.empty(U, dtype=torch.int32, device=dev)}
+        if want_window:
+            out["window"] = torch.empty(U, c.frames, c.pose_dim, device=dev)
+        if want_prediction:
+            out["emotion_prediction"] = torch.empty(U, 8, device=dev)
+        L.check(self._lib.eg_generator_stream_step(
+            self._h, _ptr(self.arena), _ptr(state), *geom, _ptr(spec), _ptr(text), _ptr(sampled), _ptr(alpha), _ptr(out["rows"]), _ptr(out["valid"]),
+            _ptr(out.get("window")), _ptr(out.get("emotion_prediction")), _ptr(ws), ws_bytes, _stream(dev)), "eg_generator_stream_step")
+        return out
+
+    @_locked
+    def stream_tail(self, state, rows, hop_samples, n_samples):
+        """eg_stream_tail: the priors [U,P,D] = the last P rows of every row's track as it stands."""
+        geom = self._stream_geometry(rows, hop_samples, n_samples)
+        state = self._stream_state(state, geom)
+        out = torch.empty(geom[0], self.cfg.prior_frames, self.cfg.pose_dim, device=state.device)
+        L.check(self._lib.eg_stream_tail(self._h, _ptr(state), *geom, _ptr(out), _stream(state.device)), "eg_stream_tail")
+        return out
+
     def tap(self, name: str, batch: int) -> torch.Tensor:
         """Copy of an intermediate of the last forward(batch) (parity tests)."""
         ws = self._ws[("fwd", batch)]

@@ -494,3 +494,13 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
         out = eng.forward_rollout(spec, text, seed_pose, sampled, alpha=alpha, want_windows=want_windows, want_aux=want_aux)
     out["spec"] = spec
     return out
+
+
+def open_stream(models, rows: int, seed_pose: torch.Tensor, *, mel=None, **kw):
+    """`synthesize` fed hop by hop: a `streaming.GestureStream` for `rows` speakers.  ``models = (generator, vae | None)``, eval mode, on the GPU;
+    ``mel``: a MelFrontEnd to share (default: one of the session's own on seed_pose's device), as for `synthesize`.  A row's emitted rows followed
+    by its tail are `synthesize`'s track for the same audio, text, labels / z, seed pose and alpha.  Sessions on ready spectrograms (push_spec):
+    `streaming.GestureStream((generator, vae, None), ...)`."""
+    from .streaming import AUTO_MEL, GestureStream
+    gen, vae = models
+    return GestureStream((gen, vae, AUTO_MEL if mel is None else mel), rows, seed_pose, **kw)

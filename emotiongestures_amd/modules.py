@@ -773,6 +773,13 @@ class Transformer(ReplicaAware, nn.Module):
                                              want_windows=want_windows, want_aux=want_aux, slot=slot)
 
 
+    def open_stream(self, rows, seed_pose, *, vae=None, mel=None, **kw):
+        """Streaming synthesis: `harness.open_stream((self, vae), rows, seed_pose, mel=mel, **kw)` -- a `streaming.GestureStream` fed raw audio
+        hop by hop (`mel`: a MelFrontEnd to share; default one of the session's own).  Keyword arguments as GestureStream's."""
+        from .streaming import AUTO_MEL, GestureStream
+        return GestureStream((self, vae, AUTO_MEL if mel is None else mel), rows, seed_pose, **kw)
+
+
 class TransformerMemory(Transformer):
     _variant = "memory"
 

@@ -202,6 +202,54 @@ int eg_generator_forward_rollout(const EgGenerator* g, const float* arena, int32
                                  void* workspace, int64_t workspace_bytes, void* stream);
 int64_t eg_generator_rollout_workspace_bytes(const EgGenerator* g, int32_t utterances, int32_t windows);
 
+/* Streaming synthesis: the roll-out fed hop by hop.  A session of `rows` = U rows lives in a caller-owned device buffer `state`
+ * (eg_stream_state_bytes, 16-byte aligned, carved deterministically from (g, rows, hop_samples, n_samples): pass the same four to every
+ * entry): an audio ring [U, lag * hop], lag = ceil(n_samples / hop_samples), the prior [U, P, D] and per row the counters c (pushes since
+ * the row's reset), w (windows done), total (-1 while the row is open, else the number of samples T the row was fed) and the verdict of
+ * the last push.  The counters stay on the device: no entry reads them back, every entry is stream-ordered and makes no allocation,
+ * synchronisation or host round trip, and the launches, grids and pointers of push and step do not depend on the step index, so one
+ * captured hipGraph of push (-> eg_melspectrogram -> eg_cvae_sample) -> step serves a stream for ever.
+ * With F = frames, P = prior_frames, H = F - P, D = pose_dim, hop = hop_samples, n = n_samples:
+ *   open row:   window w = samples [w*hop, w*hop + n) of the row's recording; ready when c >= w + lag (it then starts at the oldest
+ *               sample the ring holds; samples before the start of the recording are zero).
+ *   ended row:  window w is ready while w*hop < total; it holds L = total - w*hop real samples and, if L < n, is completed by symmetric
+ *               padding of its own samples (period 2L, np.pad mode="symmetric": eg_window_gather's rule).
+ * A row's emitted rows, concatenated and followed by its tail, are the track eg_generator_forward_rollout returns for the same recording
+ * [:T] with W = the number of windows taken. */
+int64_t eg_stream_state_bytes(const EgGenerator* g, int32_t rows, int32_t hop_samples, int32_t n_samples);
+/* Rows with row_mask[u] != 0 (device int32 [U]; NULL: every row): c = w = 0, total = -1, ring row zeroed, prior := seed_pose[u]
+ * (seed_pose [U, P, D]; the rows not selected are not read). */
+int eg_stream_reset(const EgGenerator* g, void* state, int32_t rows, int32_t hop_samples, int32_t n_samples,
+                    const int32_t* row_mask, const float* seed_pose, void* stream);
+/* One step of audio for every row: chunk [U, hop] is written into the ring with wrap-around (nothing is moved), c += 1, and a row with
+ * ends[u] = m in [0, hop] (device int32 [U], -1 = the row goes on; NULL: all go on) ends here: only its first m samples are real, total =
+ * (c - 1)*hop + m.  That push and every later one is still a step for an ended row: its audio is ignored and its ring is fed zeros.
+ * clips [U, n]: every row's window w, oldest sample first, by the rules above -- bitwise eg_window_gather's clip on the same recording;
+ * a row without a ready window (waiting for its first `lag` pushes, or ended and out of windows) gets an ALL-ZERO clip, whose
+ * eg_melspectrogram is finite: 0 dB throughout (power_to_db's amin 1e-10 is both the value and the reference), |value| < 1e-6 after
+ * the fp16 rounding.  Two launches.  Call eg_generator_stream_step at most once per push: a second step would emit the window again. */
+int eg_stream_push(const EgGenerator* g, void* state, int32_t rows, int32_t hop_samples, int32_t n_samples, const float* chunk,
+                   const int32_t* ends, float* clips, void* stream);
+/* The launches of eg_generator_forward at batch U on `stream` with the prior read from the state (the product paths eg_generator_forward
+ * takes at batch U, the one-clip split-K included; workspace >= eg_generator_workspace_bytes(g, U); the branch streams of `concurrent`
+ * generators are not used), then ONE hand-off launch that applies, per row, the verdict of the last eg_stream_push:
+ *   ready:      rows_out[u] = track rows [w*H, (w+1)*H): for w >= 1 the first P are (1 - alpha[j]) * prior[u, j] + alpha[j] * pose[u, j]
+ *               (two rounded products, one rounded sum: the roll-out's blend, one device function), the rest the raw pose;
+ *               prior[u] := pose[u, H:F] (raw), w += 1, valid_out[u] = 1, window_out[u] = pose[u]
+ *   not ready:  rows_out[u] = 0, window_out[u] = 0, valid_out[u] = 0; prior and w unchanged.
+ *   spec [U, n_mels, spec_len]   text [U, text_len] int64 or NULL (the text branch does not reach the pose: NULL skips it)
+ *   sampled [U, F, d_model] or NULL   alpha [P] on the device or NULL for (j + 1) / (P + 1)
+ *   rows_out [U, H, D]   valid_out [U] int32   optional (NULL to skip): window_out [U, F, D], emotion_prediction [U, 8]
+ * The prior is read and overwritten in that launch at its fixed address, each element by one thread.  The memory variant's TM_Memory_Net
+ * couples the rows of a step: there every row's result depends on the priors of ALL rows, ready or not. */
+int eg_generator_stream_step(const EgGenerator* g, const float* arena, void* state, int32_t rows, int32_t hop_samples,
+                             int32_t n_samples, const float* spec, const int64_t* text, const float* sampled, const float* alpha,
+                             float* rows_out, int32_t* valid_out, float* window_out, float* emotion_prediction,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+/* out [U, P, D] = the priors: the last P rows of every row's track as it stands. */
+int eg_stream_tail(const EgGenerator* g, const void* state, int32_t rows, int32_t hop_samples, int32_t n_samples, float* out,
+                   void* stream);
+
 /* Intermediate taps of the most recent eg_generator_forward on this workspace (for parity tests):
  * returns the device pointer inside `workspace` and the element count; names: "stem", "layer1", "layer2", "layer3"
  * (NHWC, only when the generator was created with keep_taps), "audio_map", "audio_feat", "prior_enc", "fusion", "enc_out",

@@ -1,0 +1,96 @@
+#!/usr/bin/env python3
+"""Streaming synthesis walk-through on synthetic data: the recordings of tools/demo_synthesize.py fed hop by hop (2 s of audio per push) through
+one GestureStream, one row leaving and rejoining with a second recording while the others go on:
+
+  push(audio [U, 32 000]) --eg_stream_push (ring + window clips)--> extract_melspectrogram --> MLP_Reconstruct_v3.sample -->
+  eg_generator_stream_step (the generator at batch U seeded from the device-resident prior, then the hand-off) --> 30 finished poses per row,
+
+all of it ONE captured hipGraph replayed per push.  Every row's emitted rows followed by its tail are checked to EQUAL the track
+harness.synthesize gives for the same recording.  Weights are synthetic (integer hash), so the poses carry no meaning.
+usage: demo_stream.py [rows=4] [seconds=20]"""
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from emotiongestures_amd import harness as H
+from emotiongestures_amd.builders import build_mirror
+from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
+from emotiongestures_amd.synth import load_synth_weights, synth_audio
+
+U = int(sys.argv[1]) if len(sys.argv) > 1 else 4
+seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 20.0
+dev = torch.device("cuda:0")
+FRAMES, POSE_DIM, PRIOR, FPS = 34, 126, 4, 15
+total = int(seconds * 16000)
+
+gen = build_mirror("spatial", FRAMES, POSE_DIM, PRIOR, PRIOR, seed=7, precision="bf16x3").to(dev)
+vae = load_synth_weights(MLP_Reconstruct_v3(frames=FRAMES), 7).eval().to(dev)
+stream = H.open_stream((gen, vae), U, torch.zeros(U, PRIOR, POSE_DIM, device=dev))
+hop = stream.hop
+W = (total - 1) // hop + 1                               # windows per recording = pushes that carry its audio
+short = total // 2                                       # the leaving row's first recording; its second one has `short` samples too
+W_short = (short - 1) // hop + 1
+leaver = U - 1
+
+audio = torch.from_numpy(synth_audio(U, total, seed=90)).to(dev)
+second = torch.from_numpy(synth_audio(1, short, seed=91)).to(dev)[0]
+labels = torch.nn.functional.one_hot(torch.arange(U) % 8, 8).float().to(dev)
+text = torch.zeros(U, 60, dtype=torch.int64, device=dev)
+steps = W + stream.lag - 1                               # the last window comes out lag - 1 pushes after the last audio
+z = torch.randn(steps, U, 32)
+seed2 = torch.full((U, PRIOR, POSE_DIM), 0.1, device=dev)
+
+# the leaving row: first recording in pushes [1, W_short], reset, second recording from push `rejoin` on
+rejoin = W_short + stream.lag
+feeds = {u: [(1, audio[u], total)] for u in range(U)}
+feeds[leaver] = [(1, audio[leaver, :short], short), (rejoin, second, short)]
+tracks = {u: [[] for _ in feeds[u]] for u in range(U)}
+zs = {u: [[] for _ in feeds[u]] for u in range(U)}
+tails = {}
+t_steps = []
+for k in range(1, steps + 1):
+    if k == rejoin:
+        tails[(leaver, 0)] = stream.tail()[leaver].clone()
+        stream.reset(rows=[leaver], seed_pose=seed2)
+    chunk, ends, which = torch.zeros(U, hop, device=dev), [-1] * U, [0] * U
+    for u in range(U):
+        which[u] = max(i for i, (start, _a, _t) in enumerate(feeds[u]) if start <= k)
+        start, a, T = feeds[u][which[u]]
+        lo = (k - start) * hop
+        if lo < T:
+            part = a[lo: lo + hop]
+            chunk[u, : len(part)] = part
+            if lo + hop >= T:
+                ends[u] = T - lo
+    t0 = time.perf_counter()
+    rows, valid = stream.push(chunk, text, labels, z[k - 1], ends=ends)
+    torch.cuda.synchronize()
+    t_steps.append(time.perf_counter() - t0)
+    for u in range(U):
+        if stream.last_valid[u]:
+            tracks[u][which[u]].append(rows[u])
+            zs[u][which[u]].append(z[k - 1, u])
+    print(f"push {k:2d}: valid {valid.cpu().tolist()}  windows {stream.last_windows}  {1e3 * t_steps[-1]:.2f} ms")
+final = stream.tail()
+
+ok = True
+for u in range(U):
+    for i, (_start, a, T) in enumerate(feeds[u]):
+        n_win = len(tracks[u][i])
+        if n_win == 0:
+            continue
+        tail = tails.get((u, i), final[u])
+        got = torch.cat(tracks[u][i] + [tail], 0)
+        # synthesize on a batch of two recordings of this length (chunk invariance is stated from two clips up): this one and a copy
+        seedp = (seed2 if i == 1 else torch.zeros_like(seed2))[u]
+        zz = torch.stack(zs[u][i])[None].expand(2, n_win, 32).contiguous()
+        want = H.synthesize((gen, vae), torch.stack([a[:T], a[:T]]), text[u][None, None].expand(2, n_win, 60).contiguous(), torch.stack([seedp, seedp]),
+                            labels=labels[u][None].expand(2, 8).contiguous(), z=zz, windows=n_win, mel=stream.mel)["track"][0]
+        same = torch.equal(got, want)
+        ok &= same
+        print(f"row {u} recording {i}: {T / 16000:.1f} s -> {n_win} windows -> track {tuple(got.shape)}; equals harness.synthesize: {same}")
+print(f"steady-state push (one graph replay + copies, synchronised): {1e3 * sorted(t_steps)[len(t_steps) // 2]:.2f} ms for {hop / 16000:.1f} s of audio per row")
+sys.exit(0 if ok else 1)
