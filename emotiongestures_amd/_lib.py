@@ -73,6 +73,11 @@ SIGNATURES = {
     "eg_generator_draws_workspace_bytes": (_L, [_P, _I, _I]),
     "eg_generator_forward_rollout": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "eg_generator_rollout_workspace_bytes": (_L, [_P, _I, _I]),
+    "eg_rows_by_table": (C.c_int, [_P, _P, _P, _I, _L, _I, _P]),
+    "eg_rollout_ragged_plan_ints": (_L, [_I, _L]),
+    "eg_rollout_ragged_plan": (C.c_int, [_P, _I, _P, _P, _P, _P]),
+    "eg_generator_forward_rollout_ragged": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "eg_generator_rollout_ragged_workspace_bytes": (_L, [_P, _I, _L]),
     "eg_stream_state_bytes": (_L, [_P, _I, _I, _I]),
     "eg_stream_reset": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "eg_stream_push": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
@@ -92,6 +97,7 @@ SIGNATURES = {
     "eg_mel_workspace_bytes": (_L, [_I, _I]),
     "eg_melspectrogram": (C.c_int, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _L, _P]),
     "eg_window_gather": (C.c_int, [_P, _I, _L, _I, _L, _I, _P, _P]),
+    "eg_window_gather_ragged": (C.c_int, [_P, _I, _L, _P, _P, _L, _I, _P, _P]),
     "eg_beat_tables": (C.c_int, [_P, _P, _P, _P]),
     "eg_beat_workspace_bytes": (_L, [_I, _I]),
     "eg_beat_align": (C.c_int, [_P, _I, _I, _P, _I, _I, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P]),

@@ -7,6 +7,7 @@
 #include "common.h"
 #include <string>
 #include <vector>
+#include <algorithm>
 #include <string.h>
 #include <map>
 #include <mutex>
@@ -148,6 +149,9 @@ int egi_conv1d(const float* x, const float* w, const float* bias, const float* s
 int egi_convt1d(const float* x, const float* w, const float* bias, const float* scale, const float* shift, float* y, int n, int cin,
                 int cout, int lin, hipStream_t st);
 int egi_swap01(const void* in, void* out, int A, int B, size_t inner_words, hipStream_t st);
+int egi_rows_by_table(const void* in, void* out, const int32_t* table, int rows, size_t inner_words, bool scatter, hipStream_t st);     // ragged.hip
+int egi_rollout_handoff_ragged(const float* pose, const float* prior_in, const float* alpha, float* track, float* windows, float* prior_out,
+                               const int32_t* table, int N, int U, int active, int Wmax, int s, int F, int P, int D, hipStream_t st);
 int egi_rollout_handoff(const float* pose, const float* prior_in, const float* alpha, float* track, float* windows, float* prior_out, int U,
                         int W, int w, int F, int P, int D, hipStream_t st);
 int egi_small_linear(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int n, int in, int out,
@@ -909,9 +913,8 @@ extern "C" int eg_generator_forward_draws(const EgGenerator* g, const float* are
 // ---- roll-out: W dependent windows of U utterances --------------------------------------------------------------------------------
 namespace {
 struct RollWs { GenWs a; int64_t kv[8], prior[2], spec, text, sampled, total; };
-RollWs carve_rollout(const EgGenerator* g, int U, int W) {
+RollWs carve_rollout(const EgGenerator* g, int U, int64_t N) {      // N clips in all: U*W for a rectangle, sum of W_u for a ragged call
     const EgGeneratorConfig& c = g->cfg;
-    const int64_t N = (int64_t)U * W;
     RollWs r;
     r.a = carve(g, (int)N);             // phase A at batch U*W; the decoder steps reuse its buffers at batch U
     Carver cv;
@@ -930,7 +933,7 @@ RollWs carve_rollout(const EgGenerator* g, int U, int W) {
 
 extern "C" int64_t eg_generator_rollout_workspace_bytes(const EgGenerator* g, int32_t utterances, int32_t windows) {
     if (!g || utterances <= 0 || windows <= 0 || g->cfg.n_layers > 8 || (int64_t)utterances * windows > (1 << 20)) return 0;
-    return carve_rollout(g, utterances, windows).total;
+    return carve_rollout(g, utterances, (int64_t)utterances * windows).total;
 }
 
 extern "C" int eg_generator_forward_rollout(const EgGenerator* g, const float* arena, int32_t U, int32_t W, const float* spec,
@@ -943,7 +946,7 @@ extern "C" int eg_generator_forward_rollout(const EgGenerator* g, const float* a
     EG_REQUIRE((int64_t)U * W <= (1 << 20), EG_ERR_UNSUPPORTED, "eg_generator_forward_rollout: utterances*windows=%lld", (long long)U * W);
     EG_REQUIRE(text || !text_embedding, EG_ERR_BAD_ARG, "eg_generator_forward_rollout: text_embedding wanted without text");
     EG_REQUIRE(g->cfg.n_layers <= 8, EG_ERR_UNSUPPORTED, "eg_generator_forward_rollout: n_layers=%d > 8", g->cfg.n_layers);
-    const RollWs r = carve_rollout(g, U, W);
+    const RollWs r = carve_rollout(g, U, (int64_t)U * W);
     const GenWs& w = r.a;
     EG_REQUIRE(ws_bytes >= r.total, EG_ERR_WORKSPACE, "eg_generator_forward_rollout: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)r.total);
     EG_REQUIRE(eg_aligned16(ws) && eg_aligned16(arena) && eg_aligned16(spec), EG_ERR_ALIGN, "eg_generator_forward_rollout: 16-byte alignment");
@@ -999,6 +1002,105 @@ extern "C" int eg_generator_forward_rollout(const EgGenerator* g, const float* a
         float* next = P(ws, r.prior[s & 1]);
         EG_TRY(egi_rollout_handoff(P(ws, w.pose), prior, alpha, track, windows, next, U, W, s, F, P_, PD, st));
         prior = next;
+    }
+    return EG_OK;
+}
+
+// ---- ragged roll-out: U recordings with their own window counts (plan and kernels: ragged.hip) -----------------------------------------
+extern "C" int64_t eg_generator_rollout_ragged_workspace_bytes(const EgGenerator* g, int32_t utterances, int64_t total_windows) {
+    if (!g || utterances <= 0 || total_windows < utterances || g->cfg.n_layers > 8 || total_windows > (1 << 20)) return 0;
+    return carve_rollout(g, utterances, total_windows).total;
+}
+
+extern "C" int eg_generator_forward_rollout_ragged(const EgGenerator* g, const float* arena, int32_t U, const int32_t* windows_per,
+                                                   const int32_t* plan, const float* spec, const int64_t* text, const float* seed_pose,
+                                                   const float* sampled, const float* alpha, float* track, float* windows,
+                                                   float* emotion_prediction, float* emotion_feature, float* semantic_feature,
+                                                   float* text_embedding, void* ws, int64_t ws_bytes, void* stream) {
+    EG_REQUIRE(g && arena && windows_per && plan && spec && seed_pose && track && ws, EG_ERR_BAD_ARG, "eg_generator_forward_rollout_ragged: null pointer");
+    EG_REQUIRE(U >= 1, EG_ERR_BAD_ARG, "eg_generator_forward_rollout_ragged: utterances=%d (need >= 1)", U);
+    int64_t N64 = 0;
+    int Wmax = 0;
+    for (int u = 0; u < U; ++u) {
+        EG_REQUIRE(windows_per[u] >= 1, EG_ERR_BAD_ARG, "eg_generator_forward_rollout_ragged: windows_per[%d]=%d (need >= 1)", u, windows_per[u]);
+        N64 += windows_per[u];
+        Wmax = windows_per[u] > Wmax ? windows_per[u] : Wmax;
+    }
+    EG_REQUIRE(N64 <= (1 << 20), EG_ERR_UNSUPPORTED, "eg_generator_forward_rollout_ragged: total windows=%lld > 2^20", (long long)N64);
+    EG_REQUIRE(text || !text_embedding, EG_ERR_BAD_ARG, "eg_generator_forward_rollout_ragged: text_embedding wanted without text");
+    EG_REQUIRE(g->cfg.n_layers <= 8, EG_ERR_UNSUPPORTED, "eg_generator_forward_rollout_ragged: n_layers=%d > 8", g->cfg.n_layers);
+    const RollWs r = carve_rollout(g, U, N64);
+    const GenWs& w = r.a;
+    EG_REQUIRE(ws_bytes >= r.total, EG_ERR_WORKSPACE, "eg_generator_forward_rollout_ragged: workspace %lld < %lld bytes", (long long)ws_bytes,
+               (long long)r.total);
+    EG_REQUIRE(eg_aligned16(ws) && eg_aligned16(arena) && eg_aligned16(spec) && (reinterpret_cast<uintptr_t>(plan) & 3u) == 0, EG_ERR_ALIGN,
+               "eg_generator_forward_rollout_ragged: 16-byte alignment (plan: 4-byte)");
+    hipStream_t st = (hipStream_t)stream;
+    const EgGeneratorConfig& c = g->cfg;
+    const int F = c.frames, D = c.d_model, N = (int)N64, P_ = c.prior_frames, PD = c.pose_dim;
+    // the working order (longer first, ties by index): the active recordings of every step are its first U_s ranks
+    std::vector<int32_t> order(U);
+    for (int u = 0; u < U; ++u) order[u] = u;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return windows_per[a] > windows_per[b]; });
+    bool sorted = true;
+    for (int u = 0; u < U; ++u) sorted = sorted && order[u] == u;
+    const bool move = U > 1 && Wmax > 1;        // else step-major and packed recording-major order coincide (slot_row is the identity)
+
+    // ---- phase A, batch N in step-major order (slot (s, rank) after the slots of the steps before it): everything the prior does not reach
+    if (move) {
+        EG_TRY(egi_rows_by_table(spec, P(ws, r.spec), plan, N, (size_t)c.n_mels * c.spec_len, false, st));
+        spec = P(ws, r.spec);
+        if (text_embedding) {
+            EG_TRY(egi_rows_by_table(text, P(ws, r.text), plan, N, (size_t)c.text_len * 2, false, st));
+            text = reinterpret_cast<const int64_t*>(P(ws, r.text));
+        }
+        if (sampled) {
+            EG_TRY(egi_rows_by_table(sampled, P(ws, r.sampled), plan, N, (size_t)F * D, false, st));
+            sampled = P(ws, r.sampled);
+        }
+    }
+    float* txt = move ? P(ws, w.t_out) : text_embedding;
+    float* emo = move || !emotion_feature ? P(ws, w.emo) : emotion_feature;
+    float* sem = move || !semantic_feature ? P(ws, w.sem) : semantic_feature;
+    float* pred = move || !emotion_prediction ? P(ws, w.cls_out) : emotion_prediction;
+    if (text_embedding) EG_TRY(run_text(g, arena, text, txt, w, ws, N, st));
+    EG_TRY(run_audio_tower(g, arena, spec, w, ws, N, st));
+    EG_TRY(run_heads(g, arena, emo, sem, pred, w, ws, N, st));
+    EG_TRY(egi_add(sampled ? sampled : emo, sem, P(ws, w.fus_in), (size_t)N * F * D, D, 0, st));
+    Act enc_out;
+    EG_TRY(run_encoder(g, arena, P(ws, w.fus_in), enc_out, w, ws, N, st));
+    float* kv[8];
+    for (int l = 0; l < c.n_layers; ++l) {
+        kv[l] = P(ws, r.kv[l]);
+        EG_TRY(lin(g, arena, g->dec_attn[l].kv, enc_out, 0, act(kv[l], 2 * D), true, N * F, 0, nullptr, 0, st));
+    }
+    if (move) {     // per-window outputs back to the caller's packed recording-major rows
+        if (text_embedding) EG_TRY(egi_rows_by_table(txt, text_embedding, plan, N, (size_t)c.text_len * 512, true, st));
+        if (emotion_feature) EG_TRY(egi_rows_by_table(emo, emotion_feature, plan, N, (size_t)F * D, true, st));
+        if (semantic_feature) EG_TRY(egi_rows_by_table(sem, semantic_feature, plan, N, (size_t)F * D, true, st));
+        if (emotion_prediction) EG_TRY(egi_rows_by_table(pred, emotion_prediction, plan, N, 8, true, st));
+    }
+
+    // ---- phase B, Wmax dependent steps; step s runs the U_s recordings with W_u > s.  Priors ping-pong between two buffers indexed by
+    // rank, so a recording keeps its slot for its whole life; the seed poses are brought into rank order first unless they are in it.
+    const float* prior = seed_pose;
+    if (!sorted) {
+        EG_TRY(egi_rows_by_table(seed_pose, P(ws, r.prior[1]), plan + N, U, (size_t)P_ * PD, false, st));
+        prior = P(ws, r.prior[1]);
+    }
+    const Act prior_enc = act(P(ws, w.prior_enc), D, P(ws, w.im_p[1]), D);
+    int active = U;
+    size_t slot = 0;
+    for (int s = 0; s < Wmax; ++s) {
+        while (active > 0 && windows_per[order[active - 1]] <= s) --active;
+        EG_TRY(run_prior(g, arena, prior, w, ws, active, st));
+        float* step_kv[8];
+        for (int l = 0; l < c.n_layers; ++l) step_kv[l] = kv[l] + slot * F * 2 * D;
+        EG_TRY(run_decoder(g, arena, prior_enc, Act(), step_kv, P(ws, w.pose), w, ws, active, st));
+        float* next = P(ws, r.prior[s & 1]);
+        EG_TRY(egi_rollout_handoff_ragged(P(ws, w.pose), prior, alpha, track, windows, next, plan, N, U, active, Wmax, s, F, P_, PD, st));
+        prior = next;
+        slot += (size_t)active;
     }
     return EG_OK;
 }

@@ -42,6 +42,29 @@ def _locked(fn):
     return wrapper
 
 
+def ragged_plan(windows_per) -> dict:
+    """eg_rollout_ragged_plan on the host (no GPU needed): for window counts W_u the working order "longer first, ties by index" (`order`:
+    rank -> recording, `inverse`: recording -> rank), `step_batch` [Wmax] (recordings active in step s), `offsets` [U] (exclusive prefix
+    sum of W_u: recording u's first packed row), `slot_row` [N] (step-major slot -> packed row) and `table` [N + 2U], what the device reads."""
+    import numpy as np
+    wp = np.ascontiguousarray(np.asarray(windows_per, dtype=np.int32).reshape(-1))
+    lib = L.load()
+    U = int(wp.size)
+    N = int(wp.astype(np.int64).sum()) if U else 0
+    good = U >= 1 and bool((wp >= 1).all())
+    Wmax = int(wp.max()) if good else 1
+    ints = lib.eg_rollout_ragged_plan_ints(U, N) if good else 0
+    order, inverse = np.zeros(max(U, 1), np.int32), np.zeros(max(U, 1), np.int32)
+    step_batch, table = np.zeros(Wmax, np.int32), np.zeros(max(int(ints), 1), np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    L.check(lib.eg_rollout_ragged_plan(p(wp), U, p(order), p(inverse), p(step_batch), p(table) if ints > 0 else None), "eg_rollout_ragged_plan")
+    if ints <= 0:
+        raise L.EgError(f"eg_rollout_ragged_plan_ints: unsupported U={U} N={N}")
+    offsets = np.concatenate([[0], np.cumsum(wp[:-1], dtype=np.int64)]).astype(np.int32)
+    return {"windows_per": wp, "order": order, "inverse": inverse, "step_batch": step_batch, "offsets": offsets, "slot_row": table[:N].copy(),
+            "table": table}
+
+
 class GeneratorEngine:
     """Host handle for eg_generator_* (Transformer.forward, Full_model/Models_spatial_memory.py:566-616)."""
 
@@ -73,6 +96,7 @@ class GeneratorEngine:
         self.arena_floats = lib.eg_generator_arena_floats(h)
         self.arena: Optional[torch.Tensor] = None
         self._ws: Dict[tuple, torch.Tensor] = {}
+        self._plans: Dict[tuple, dict] = {}     # ragged roll-out: plan tables per (W_u) vector and device
         self._lock = threading.RLock()
         self.uploads = 0                 # arena packs + uploads so far (tests: once per device and weight version)
 
@@ -199,6 +223,113 @@ class GeneratorEngine:
             self._h, _ptr(self.arena), U, W, _ptr(spec), _ptr(text), _ptr(seed_pose), _ptr(sampled), _ptr(alpha), _ptr(out["track"]),
             _ptr(out.get("windows")), _ptr(out["emotion_prediction"]), _ptr(out.get("emotion_feature")), _ptr(out.get("semantic_feature")),
             _ptr(out.get("text_embedding")), _ptr(ws), ws_bytes, _stream(dev)), "eg_generator_forward_rollout")
+        return out
+
+    # ---- ragged roll-out: recordings with their own window counts ----
+    def _rollout_ragged_args(self, spec, text, seed_pose, windows_per, sampled, alpha):
+        """Shape contract of forward_rollout_ragged (checked before anything touches the device); returns (U, N, windows_per as a tuple)."""
+        c = self.cfg
+        try:
+            wp = tuple(int(v) for v in (windows_per.tolist() if hasattr(windows_per, "tolist") else windows_per))
+        except TypeError:
+            raise L.EgError(f"windows_per: need a sequence of U window counts (got {type(windows_per).__name__})")
+        U = len(wp)
+        if U < 1:
+            raise L.EgError(f"windows_per: utterances U={U} (need >= 1)")
+        for u, v in enumerate(wp):
+            if v < 1:
+                raise L.EgError(f"windows_per[{u}]={v} (need >= 1)")
+        N = sum(wp)
+        if N > 1 << 20:
+            raise L.EgError(f"windows_per: total windows N={N} > 2^20")
+        if tuple(spec.shape) != (N, c.n_mels, c.spec_len):
+            raise L.EgError(f"spec shape {tuple(spec.shape)} != (N={N},{c.n_mels},{c.spec_len}) packed, N = sum(windows_per)")
+        if tuple(text.shape) != (N, c.text_len):
+            raise L.EgError(f"text shape {tuple(text.shape)} != ({N},{c.text_len})")
+        if tuple(seed_pose.shape) != (U, c.prior_frames, c.pose_dim):
+            raise L.EgError(f"seed_pose shape {tuple(seed_pose.shape)} != ({U},{c.prior_frames},{c.pose_dim})")
+        if sampled is not None and tuple(sampled.shape) != (N, c.frames, c.d_model):
+            raise L.EgError(f"sampled shape {tuple(sampled.shape)} != ({N},{c.frames},{c.d_model})")
+        if alpha is not None and tuple(alpha.shape) != (c.prior_frames,):
+            raise L.EgError(f"alpha shape {tuple(alpha.shape)} != ({c.prior_frames},)")
+        return U, N, wp
+
+    def _ragged_plan(self, wp, device):
+        """The plan of one (W_u) vector: host tables from eg_rollout_ragged_plan, the device copy of its table uploaded once and kept."""
+        key = (wp, str(device))
+        ent = self._plans.get(key)
+        if ent is None:
+            ent = ragged_plan(wp)
+            ent["windows_per_c"] = (C.c_int32 * len(wp))(*wp)
+            ent["table_dev"] = torch.from_numpy(ent["table"]).to(device)
+            if len(self._plans) >= 64:          # a long-running caller with ever-new vectors: drop the oldest, keep the cache bounded
+                self._plans.pop(next(iter(self._plans)))
+            self._plans[key] = ent
+        return ent
+
+    @_locked
+    def pack_ragged(self, x, windows_per, name="argument"):
+        """Padded [U, Wmax, ...] -> packed [N, ...] on the device by eg_rows_by_table (row off[u] + w = x[u, w] for w < W_u; entries past W_u
+        are never read).  float32 or int64."""
+        wp = tuple(int(v) for v in (windows_per.tolist() if hasattr(windows_per, "tolist") else windows_per))
+        U, Wmax = len(wp), max(wp) if len(wp) else 0
+        if x.dim() < 2 or int(x.shape[0]) != U or int(x.shape[1]) != Wmax:
+            raise L.EgError(f"{name} shape {tuple(x.shape)}: a padded argument is (U={U}, Wmax={Wmax}, ...)")
+        if self.arena is None:
+            raise L.EgError("GeneratorEngine.pack_ragged before load_weights")
+        x = _need_cuda(x, name, torch.int64 if x.dtype == torch.int64 else torch.float32)
+        plan = self._ragged_plan(wp, x.device)
+        if "pad_table_dev" not in plan:
+            plan["pad_table_dev"] = torch.tensor([u * Wmax + w for u in range(U) for w in range(wp[u])], dtype=torch.int32).to(x.device)
+        N = sum(wp)
+        out = torch.empty((N,) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device)
+        words = (x[0, 0].numel() * x.element_size()) // 4
+        L.check(self._lib.eg_rows_by_table(_ptr(x), _ptr(out), _ptr(plan["pad_table_dev"]), N, words, 0, _stream(x.device)), "eg_rows_by_table")
+        return out
+
+    @_locked
+    def forward_rollout_ragged(self, spec, text, seed_pose, windows_per, sampled=None, alpha=None, want_windows=False, want_aux=False, slot=0,
+                               track=None):
+        """eg_generator_forward_rollout_ragged: U recordings with their own window counts windows_per[u] = W_u >= 1 in one call; step s runs
+        the recordings with W_u > s only.  Window-indexed arguments are PACKED recording-major (N = sum W_u rows, recording u at rows
+        [off[u], off[u] + W_u)): spec [N,n_mels,spec_len], text [N,text_len], sampled [N,F,d_model] or None; seed_pose [U,P,D]; alpha [P] or
+        None.  Returns a dict: track [U, Wmax*(F-P)+P, D] (rows past track_frames[u] are zero), track_frames [U] = W_u*(F-P)+P and
+        window_offsets [U] = off (int64, on the host), packed emotion_prediction [N,8], windows [N,F,D] with want_windows,
+        emotion_feature / semantic_feature [N,F,d_model] and text_embedding [N,text_len,512] with want_aux.  `track`: a caller-owned
+        contiguous float32 GPU buffer of the track's shape to write into (default: a new one); every element of it is written."""
+        U, N, wp = self._rollout_ragged_args(spec, text, seed_pose, windows_per, sampled, alpha)
+        T = max(wp) * (self.cfg.frames - self.cfg.prior_frames) + self.cfg.prior_frames
+        if track is not None and (tuple(track.shape) != (U, T, self.cfg.pose_dim) or track.dtype != torch.float32 or not track.is_contiguous()
+                                  or not track.is_cuda):
+            raise L.EgError(f"track: need a contiguous float32 GPU tensor [{U},{T},{self.cfg.pose_dim}]")
+        if self.arena is None:
+            raise L.EgError("GeneratorEngine.forward_rollout_ragged before load_weights")
+        dev = self.arena.device
+        c = self.cfg
+        spec, text, seed_pose = _need_cuda(spec, "spec"), _need_cuda(text, "text", torch.int64), _need_cuda(seed_pose, "seed_pose")
+        sampled = None if sampled is None else _need_cuda(sampled, "sampled")
+        alpha = None if alpha is None else _need_cuda(alpha, "alpha")
+        plan = self._ragged_plan(wp, dev)
+        ws_bytes = self._lib.eg_generator_rollout_ragged_workspace_bytes(self._h, U, N)
+        if ws_bytes <= 0:
+            raise L.EgError(f"eg_generator_rollout_ragged_workspace_bytes: unsupported U={U} N={N}")
+        ws = self._workspace(("ragged", U, N) if slot == 0 else ("ragged", U, N, slot), ws_bytes, dev)
+        F, H, Wmax = c.frames, c.frames - c.prior_frames, max(wp)
+        out = {"track": torch.empty(U, T, c.pose_dim, device=dev) if track is None else track,
+               "track_frames": torch.tensor([v * H + c.prior_frames for v in wp], dtype=torch.int64),
+               "window_offsets": torch.from_numpy(plan["offsets"].astype("int64")),
+               "emotion_prediction": torch.empty(N, 8, device=dev)}
+        if want_windows:
+            out["windows"] = torch.empty(N, F, c.pose_dim, device=dev)
+        if want_aux:
+            out["emotion_feature"] = torch.empty(N, F, c.d_model, device=dev)
+            out["semantic_feature"] = torch.empty(N, F, c.d_model, device=dev)
+            out["text_embedding"] = torch.empty(N, c.text_len, 512, device=dev)
+        L.check(self._lib.eg_generator_forward_rollout_ragged(
+            self._h, _ptr(self.arena), U, plan["windows_per_c"], _ptr(plan["table_dev"]), _ptr(spec), _ptr(text), _ptr(seed_pose), _ptr(sampled),
+            _ptr(alpha), _ptr(out["track"]), _ptr(out.get("windows")), _ptr(out["emotion_prediction"]), _ptr(out.get("emotion_feature")),
+            _ptr(out.get("semantic_feature")), _ptr(out.get("text_embedding")), _ptr(ws), ws_bytes, _stream(dev)),
+            "eg_generator_forward_rollout_ragged")
         return out
 
     # ---- streaming synthesis (a session's state buffer is owned by the caller: emotiongestures_amd.streaming.GestureStream) ----
@@ -394,7 +525,7 @@ class MelFrontEnd:
         L.check(lib.eg_mel_tables(fb.ctypes.data_as(C.c_void_p), win.ctypes.data_as(C.c_void_p), tw.ctypes.data_as(C.c_void_p),
                                   band.ctypes.data_as(C.c_void_p)), "eg_mel_tables")
         self.fb, self.win, self.tw, self.band = (torch.from_numpy(a).to(device) for a in (fb, win, tw, band))
-        self._lib, self.device, self._ws = lib, torch.device(device), {}
+        self._lib, self.device, self._ws, self._meta = lib, torch.device(device), {}, {}
 
     def __call__(self, audio: torch.Tensor, out_frames: Optional[int] = None, slot: int = 0) -> torch.Tensor:
         audio = _need_cuda(audio, "audio")
@@ -427,3 +558,32 @@ class MelFrontEnd:
                 "eg_window_gather")
         spec = self(clips, out_frames, slot)
         return spec.view(U, windows, 128, spec.shape[-1])
+
+    def windows_ragged(self, audio: torch.Tensor, lengths, hop_samples: int, n_samples: int, out_frames: Optional[int] = None, slot: int = 0):
+        """Recordings of unequal length, audio [U, stride] with lengths[u] real samples each (what follows them is never read) -> (spec
+        [N, 128, out_frames] packed recording-major, windows_per): recording u has W_u = ceil(lengths[u] / hop_samples) windows, every window
+        that starts inside it; a window that runs past the recording's own end is completed by symmetric padding of its own samples."""
+        if audio.dim() != 2:
+            raise L.EgError(f"audio shape {tuple(audio.shape)} != (U, max_total_samples)")
+        U, stride = int(audio.shape[0]), int(audio.shape[1])
+        lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        if len(lens) != U:
+            raise L.EgError(f"lengths: {len(lens)} entries for {U} recordings")
+        if hop_samples < 1 or n_samples < 1:
+            raise L.EgError(f"hop_samples={hop_samples} n_samples={n_samples} (need >= 1)")
+        for u, v in enumerate(lens):
+            if v < 1 or v > stride:
+                raise L.EgError(f"lengths[{u}]={v} (need 1 .. {stride}, the width of audio)")
+        audio = _need_cuda(audio, "audio")
+        wp = [(v + hop_samples - 1) // hop_samples for v in lens]
+        off = [sum(wp[:u]) for u in range(U)]
+        key = (tuple(lens), int(hop_samples))
+        meta = self._meta.get(key)              # lengths | offsets on the device, uploaded once per vector (bounded: the oldest goes first)
+        if meta is None:
+            if len(self._meta) >= 64:
+                self._meta.pop(next(iter(self._meta)))
+            meta = self._meta[key] = torch.tensor(lens + off, dtype=torch.int64).to(self.device)
+        clips = torch.empty(sum(wp), n_samples, device=self.device)
+        L.check(self._lib.eg_window_gather_ragged(_ptr(audio), U, stride, (C.c_int64 * U)(*lens), _ptr(meta), hop_samples, n_samples, _ptr(clips),
+                                                  _stream(self.device)), "eg_window_gather_ragged")
+        return self(clips, out_frames, slot), wp

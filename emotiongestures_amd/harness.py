@@ -459,7 +459,7 @@ def evaluate(generator, vae, fgd: MLP_Reconstruct, classifier: Optional[Skeleton
 def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch.Tensor, labels: Optional[torch.Tensor] = None,
                hop_samples: Optional[int] = None, n_samples: Optional[int] = None, windows: Optional[int] = None,
                z: Optional[torch.Tensor] = None, alpha: Optional[torch.Tensor] = None, fps: int = 15, sample_rate: int = 16000,
-               want_windows: bool = False, want_aux: bool = False, mel=None) -> Dict[str, torch.Tensor]:
+               want_windows: bool = False, want_aux: bool = False, mel=None, lengths=None) -> Dict[str, torch.Tensor]:
     """One gesture track per utterance from raw 16 kHz audio: windows -> mel -> optional CVAE sample per window -> roll-out.
 
     ``models = (generator, vae | None)``, eval mode, on the GPU.  ``audio [U, total_samples]``; ``text [U, W, 60]`` (the words of every
@@ -467,7 +467,13 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     fixes the latents (default torch.randn on the CPU generator, as MLP_Reconstruct_v3.sample draws them).  Window w covers samples
     ``[w*hop_samples, w*hop_samples + n_samples)``; the defaults tie them to the generator's geometry: ``hop_samples`` is the duration of
     ``frames - prior_frames`` poses at ``fps``, ``n_samples = (spec_len - 1) * 512`` (the shortest clip whose spectrogram has spec_len
-    columns).  ``windows`` defaults to ``text.shape[1]``.  Returns GeneratorEngine.forward_rollout's dict plus ``"spec"``."""
+    columns).  ``windows`` defaults to ``text.shape[1]``.  Returns GeneratorEngine.forward_rollout's dict plus ``"spec"``.
+
+    ``lengths`` (U sample counts): recordings of unequal length, ``audio [U, max_total]`` with ``lengths[u]`` real samples in row u (the rest
+    is never read).  Recording u then has ``W_u = ceil(lengths[u] / hop_samples)`` windows -- every window that starts inside it, the count a
+    stream reaches for a row ended at that length; ``text``, ``labels`` and ``z`` are per recording (labels ``[U, 8]`` only), padded
+    ``[U, max W_u, ...]`` or packed ``[sum W_u, ...]``; ``windows`` is not used.  Returns GeneratorEngine.forward_rollout_ragged's dict plus
+    packed ``"spec"`` and ``"windows_per"``."""
     from .engine import MelFrontEnd
     gen, vae = models
     _eval_only(gen)
@@ -476,6 +482,9 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     if audio.dim() != 2:
         raise L.EgError(f"audio shape {tuple(audio.shape)} != (U, total_samples)")
     U = audio.shape[0]
+    if lengths is not None:
+        return _synthesize_ragged(eng, vae, audio, lengths, text, seed_pose, labels, hop_samples, n_samples, z, alpha, fps, sample_rate,
+                                  want_windows, want_aux, mel)
     W = int(text.shape[1]) if windows is None and text.dim() == 3 else windows
     if W is None or W < 1:
         raise L.EgError(f"windows={W} (need >= 1): text must be [U, W, {c.text_len}] or `windows` given")
@@ -493,6 +502,40 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
             sampled = vae.sample(lab, z=None if z is None else z.reshape(U * W, 32)).view(U, W, c.frames, c.d_model)
         out = eng.forward_rollout(spec, text, seed_pose, sampled, alpha=alpha, want_windows=want_windows, want_aux=want_aux)
     out["spec"] = spec
+    return out
+
+
+def _synthesize_ragged(eng, vae, audio, lengths, text, seed_pose, labels, hop_samples, n_samples, z, alpha, fps, sample_rate, want_windows,
+                       want_aux, mel):
+    from .engine import MelFrontEnd
+    c = eng.cfg
+    U = audio.shape[0]
+    hop = int(round((c.frames - c.prior_frames) * sample_rate / fps)) if hop_samples is None else int(hop_samples)
+    n = (c.spec_len - 1) * 512 if n_samples is None else int(n_samples)
+    mel = MelFrontEnd(audio.device) if mel is None else mel
+    with torch.no_grad():
+        spec, wp = mel.windows_ragged(audio, lengths, hop, n, out_frames=c.spec_len)
+        N = sum(wp)
+        packed = lambda x, packed_dim, name: eng.pack_ragged(x, wp, name) if x.dim() == packed_dim + 1 else x
+        sampled = None
+        if vae is not None:
+            if labels is None:
+                raise L.EgError("labels: needed when a VAE is given ([U, 8], [U, Wmax, 8] or packed [N, 8] one-hot)")
+            lab = labels.to(audio.device).float()
+            if lab.dim() == 2 and lab.shape[0] == U and U != N:         # one label per recording: repeated over its windows
+                lab = lab[:, None, :].expand(U, max(wp), 8).contiguous()
+            lab = packed(lab, 2, "labels")
+            if tuple(lab.shape) != (N, 8):
+                raise L.EgError(f"labels shape {tuple(labels.shape)}: need ({U},8), ({U},{max(wp)},8) or packed ({N},8)")
+            if z is not None:
+                z = packed(z.to(audio.device).float(), 2, "z")
+                if tuple(z.shape) != (N, 32):
+                    raise L.EgError(f"z shape {tuple(z.shape)}: need ({U},{max(wp)},32) or packed ({N},32)")
+            sampled = vae.sample(lab, z=z)
+        out = eng.forward_rollout_ragged(spec, packed(text, 2, "text"), seed_pose, wp, sampled, alpha=alpha, want_windows=want_windows,
+                                         want_aux=want_aux)
+    out["spec"] = spec
+    out["windows_per"] = list(wp)
     return out
 
 

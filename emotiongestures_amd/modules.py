@@ -763,15 +763,25 @@ class Transformer(ReplicaAware, nn.Module):
         return self.engine().forward_draws(input_spectrum, prior_seq, sampled_emotion_features, slot=slot)
 
     def synthesize(self, input_spectrum, text, seed_pose, sampled_emotion_features=None, *, alpha=None, want_windows=False,
-                   want_aux=False, slot=0):
+                   want_aux=False, slot=0, windows_per=None):
         """Long-form synthesis: input_spectrum [U,W,n_mels,spec_len], text [U,W,text_len], seed_pose [U,prior_frames,pose_dim],
         sampled_emotion_features [U,W,frames,d_model] or None.  Window w >= 1 is seeded with the raw last prior_frames poses of window
         w-1; the dict returned holds track [U, W*(frames-prior_frames)+prior_frames, pose_dim] (overlaps cross-faded with `alpha`,
-        default (j+1)/(prior_frames+1)), emotion_prediction [U,W,8] and the optional outputs of GeneratorEngine.forward_rollout."""
-        _eval_only(self)
-        return self.engine().forward_rollout(input_spectrum, text, seed_pose, sampled_emotion_features, alpha=alpha,
-                                             want_windows=want_windows, want_aux=want_aux, slot=slot)
+        default (j+1)/(prior_frames+1)), emotion_prediction [U,W,8] and the optional outputs of GeneratorEngine.forward_rollout.
 
+        ``windows_per`` (a sequence of U counts W_u >= 1): recordings of unequal length in one call -- step s runs the recordings with
+        W_u > s only.  The window-indexed arguments are then packed ``[N, ...]`` (N = sum W_u, recording u at rows [off[u], off[u] + W_u))
+        or padded ``[U, max W_u, ...]`` (packed on the device; entries past W_u are never read); the dict is
+        GeneratorEngine.forward_rollout_ragged's: track [U, max W_u * H + P, pose_dim] zero past track_frames[u], per-window outputs packed."""
+        _eval_only(self)
+        if windows_per is None:
+            return self.engine().forward_rollout(input_spectrum, text, seed_pose, sampled_emotion_features, alpha=alpha,
+                                                 want_windows=want_windows, want_aux=want_aux, slot=slot)
+        eng = self.engine()
+        pack = lambda x, packed_dim, name: eng.pack_ragged(x, windows_per, name) if x is not None and x.dim() == packed_dim + 1 else x
+        return eng.forward_rollout_ragged(pack(input_spectrum, 3, "input_spectrum"), pack(text, 2, "text"), seed_pose, windows_per,
+                                          pack(sampled_emotion_features, 3, "sampled_emotion_features"), alpha=alpha,
+                                          want_windows=want_windows, want_aux=want_aux, slot=slot)
 
     def open_stream(self, rows, seed_pose, *, vae=None, mel=None, **kw):
         """Streaming synthesis: `harness.open_stream((self, vae), rows, seed_pose, mel=mel, **kw)` -- a `streaming.GestureStream` fed raw audio

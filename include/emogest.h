@@ -202,6 +202,60 @@ int eg_generator_forward_rollout(const EgGenerator* g, const float* arena, int32
                                  void* workspace, int64_t workspace_bytes, void* stream);
 int64_t eg_generator_rollout_workspace_bytes(const EgGenerator* g, int32_t utterances, int32_t windows);
 
+/* Ragged roll-out: the roll-out above for U recordings with their OWN window counts W_u >= 1 (N = sum W_u, Wmax = max W_u), in one call.
+ * Step s (0 <= s < Wmax) is the generator on the ACTIVE recordings {u : W_u > s}, taken in the working order "longer first, ties by
+ * index" (stable sort by (-W_u, u)): the active set of every step is a prefix of that order, the batch of step s is U_s = #{u : W_u > s},
+ * and nothing of an inactive recording enters a step (the memory variant's TM_Memory_Net couples exactly the active recordings).
+ * Recording u's window w >= 1 is seeded with the raw last P poses of its own window w-1, window 0 with seed_pose[u]; its track is the
+ * stitch of its own W_u windows.  Arguments and results are in the CALLER's recording order.
+ *
+ * The plan (host only: no HIP call, usable without a GPU).  From windows_per [U] it fills (any output may be NULL):
+ *   order [U]       rank -> recording, the working order          inverse [U]    recording -> rank
+ *   step_batch [Wmax]   U_s, non-increasing, sums to N
+ *   table [N + 2U] (the count eg_rollout_ragged_plan_ints returns), what the device reads:
+ *       [0, N)       slot_row: step-major slot (s, rank) = sum_{s' < s} U_s' + rank  ->  packed row off[order[rank]] + s,
+ *                    off = exclusive prefix sum of W_u in caller order (a permutation of 0 .. N-1)
+ *       [N, N+U)     order           [N+U, N+2U)  W_order[rank]
+ * The caller uploads `table` once per (W_u) vector as int32 and passes the device copy as `plan`, beside the host array windows_per.
+ * Refuses utterances < 1, W_u < 1 and N > 2^20 by name.  eg_rollout_ragged_plan_ints is 0 for counts it would refuse. */
+/* Whole rows moved by an index table on the device (the ragged roll-out's gather / scatter; also packs padded [U, Wmax, ...] arguments):
+ *   scatter == 0: out[i] = in[d_table[i]]      scatter != 0: out[d_table[i]] = in[i]      for i < rows,
+ * rows of row_words 32-bit words, d_table int32 [rows] on the device; 16-byte accesses when row_words % 4 == 0 and both buffers are
+ * 16-byte aligned.  The table entry is read once per row.  The entries are the caller's: they must index rows that exist, and for a scatter be
+ * distinct.  One launch. */
+int eg_rows_by_table(const void* in, void* out, const int32_t* d_table, int32_t rows, int64_t row_words, int32_t scatter, void* stream);
+int64_t eg_rollout_ragged_plan_ints(int32_t utterances, int64_t total_windows);
+int eg_rollout_ragged_plan(const int32_t* windows_per, int32_t utterances, int32_t* order, int32_t* inverse, int32_t* step_batch,
+                           int32_t* table);
+/* With F, P, H, D as above, every window-indexed array PACKED recording-major: recording u owns rows [off[u], off[u] + W_u):
+ *   windows_per [U] on the HOST        plan [N + 2U] int32 on the DEVICE (the plan's table for the same windows_per)
+ *   spec [N, n_mels, spec_len]         text [N, text_len] int64 (may be NULL unless text_embedding is wanted)
+ *   seed_pose [U, P, D]                sampled [N, F, d_model] or NULL      alpha [P] on the device or NULL
+ *   track [U, Wmax*H + P, D]: rows [0, W_u*H + P) of recording u as eg_generator_forward_rollout defines them (the same blend: two
+ *          rounded products, one rounded sum); rows [W_u*H + P, Wmax*H + P) are ZERO, written by this call
+ *   optional (NULL to skip): windows [N, F, D], emotion_prediction [N, 8], emotion_feature / semantic_feature [N, F, d_model],
+ *          text_embedding [N, text_len, 512]
+ * Same contract as eg_generator_forward_rollout: one stream, no allocation on the device, host round trip or synchronisation; for a fixed
+ * (W_u) vector the launches, grids and pointers are fixed, so the call captures into one hipGraph.
+ *   A, batch N in step-major order: the packed inputs are brought into it by one row gather each through slot_row (16-byte accesses where
+ *      the row length allows; skipped when U == 1 or Wmax == 1, where the two orders coincide), then the launches of phase A above; the
+ *      wanted per-window outputs go back to packed rows by one row scatter each.  Step s's K|V is the contiguous slice of its U_s slots.
+ *   B, Wmax steps at batch U_s: prior encoder -> decoder -> post_projector (the product paths eg_generator_forward takes at batch U_s)
+ *      -> one hand-off launch for the active ranks: track rows, windows, and the next prior into ping-pong buffers indexed by RANK (a
+ *      recording keeps its slot for its whole life).  The zero fill of a recording's track tail is folded into that recording's LAST
+ *      hand-off (no launch of its own).  The seed poses are gathered into rank order by one launch unless they already are in it.
+ * With every W_u equal the call makes exactly the launches of eg_generator_forward_rollout on that rectangle and returns its results bit
+ * for bit.  workspace >= eg_generator_rollout_ragged_workspace_bytes at (U, N): a function of U and N only, equal to
+ * eg_generator_rollout_workspace_bytes at (U, W) when N = U*W -- the plan table is the caller's buffer, not workspace.  It is 0 for
+ * utterances < 1, N < utterances, N > 2^20, n_layers > 8.  Refused by name before the first launch: utterances < 1, W_u < 1, N > 2^20, n_layers > 8, a
+ * short workspace, null pointers, misaligned buffers. */
+int eg_generator_forward_rollout_ragged(const EgGenerator* g, const float* arena, int32_t utterances, const int32_t* windows_per,
+                                        const int32_t* plan, const float* spec, const int64_t* text, const float* seed_pose,
+                                        const float* sampled, const float* alpha, float* track, float* windows_out,
+                                        float* emotion_prediction, float* emotion_feature, float* semantic_feature, float* text_embedding,
+                                        void* workspace, int64_t workspace_bytes, void* stream);
+int64_t eg_generator_rollout_ragged_workspace_bytes(const EgGenerator* g, int32_t utterances, int64_t total_windows);
+
 /* Streaming synthesis: the roll-out fed hop by hop.  A session of `rows` = U rows lives in a caller-owned device buffer `state`
  * (eg_stream_state_bytes, 16-byte aligned, carved deterministically from (g, rows, hop_samples, n_samples): pass the same four to every
  * entry): an audio ring [U, lag * hop], lag = ceil(n_samples / hop_samples), the prior [U, P, D] and per row the counters c (pushes since
@@ -311,6 +365,15 @@ int eg_melspectrogram(const float* audio, int32_t batch, int32_t n_samples, cons
  * Every window must start inside the track: (windows - 1) * hop_samples < total_samples. */
 int eg_window_gather(const float* audio, int32_t utterances, int64_t total_samples, int32_t windows, int64_t hop_samples,
                      int32_t n_samples, float* out, void* stream);
+/* The same for recordings of unequal length: audio [utterances, stride], recording u holds lengths[u] real samples (1 .. stride; what
+ * follows them in its row is never read) and has W_u = ceil(lengths[u] / hop_samples) windows -- every window that starts inside the
+ * recording (w * hop_samples < lengths[u]), the rule eg_stream_push states for an ended row, so a stream and the offline path count the
+ * same windows.  out [N, n_samples], N = sum W_u, packed recording-major: row off[u] + w is eg_window_gather's clip for a recording of
+ * lengths[u] samples (a window that runs past the recording's own end is completed by symmetric padding of its own L = lengths[u] -
+ * w*hop_samples samples).  lengths [U] int64 on the HOST (checked here); d_meta [2U] int64 on the DEVICE: lengths [U] | off [U], the
+ * caller's upload of the same numbers.  Refuses utterances < 1, lengths[u] < 1 or > stride, and N > 2^20 by name.  One launch. */
+int eg_window_gather_ragged(const float* audio, int32_t utterances, int64_t stride, const int64_t* lengths, const int64_t* d_meta,
+                            int64_t hop_samples, int32_t n_samples, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Beat-alignment score = model/Beat_score_v2.py alignment(sigma, order): load_audio + load_pose +

@@ -52,3 +52,15 @@ print(f"mean |pose[t+1] - pose[t]|: {float(step.mean()):.4f} over the track, {fl
 print(f"window 1 beyond its overlap (rows [{HOP + PRIOR}, {2 * HOP})) appears raw in the track: "
       f"{bool(torch.equal(track[:, HOP + PRIOR: FRAMES + HOP - PRIOR], windows[:, 1, PRIOR: HOP]))}")
 print(f"one call (mel + CVAE + roll-out, eager): {1e3 * dt:.2f} ms = {1e3 * dt / (U * track.shape[1] / FPS):.4f} ms per second of audio")
+
+# Recordings of unequal length in one call: recording u keeps (u + 1) / U of the audio.  Step s runs only the recordings that still have a
+# window s; the track is padded to the longest recording and zero past each recording's own end.
+if U > 1:
+    lengths = [max(1, total * (u + 1) // U) for u in range(U)]
+    rag = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, lengths=lengths)
+    torch.cuda.synchronize()
+    frames = rag["track_frames"].tolist()
+    print(f"lengths {[round(v / 16000, 1) for v in lengths]} s -> windows {rag['windows_per']} -> track {tuple(rag['track'].shape)}, frames per recording {frames}; "
+          f"rows past a recording's end are zero: {all(not bool(rag['track'][u, frames[u]:].any()) for u in range(U))}; "
+          f"the longest recording against the rectangular call's: rel-L2 {float((rag['track'][U - 1] - track[U - 1]).norm() / track[U - 1].norm()):.1e} "
+          f"(its last steps run alone, at batch 1)")
