@@ -73,6 +73,8 @@ SIGNATURES = {
     "eg_generator_draws_workspace_bytes": (_L, [_P, _I, _I]),
     "eg_generator_forward_rollout": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "eg_generator_rollout_workspace_bytes": (_L, [_P, _I, _I]),
+    "eg_generator_forward_rollout_draws": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "eg_generator_rollout_draws_workspace_bytes": (_L, [_P, _I, _I, _I]),
     "eg_rows_by_table": (C.c_int, [_P, _P, _P, _I, _L, _I, _P]),
     "eg_rollout_ragged_plan_ints": (_L, [_I, _L]),
     "eg_rollout_ragged_plan": (C.c_int, [_P, _I, _P, _P, _P, _P]),

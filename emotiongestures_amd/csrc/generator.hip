@@ -1006,6 +1006,126 @@ extern "C" int eg_generator_forward_rollout(const EgGenerator* g, const float* a
     return EG_OK;
 }
 
+// ---- diverse roll-out: R sampled tracks per recording, the audio tower once (kernels: draws.hip) -------------------------------------
+int egi_draws_fusion(const float* sampled, const float* semantic, float* fus_in, int U, int W, int R, size_t clip_floats, hipStream_t st);
+int egi_draws_seed(const float* seed, float* prior, int U, int R, int PD, hipStream_t st);
+namespace {
+// R >= 2 (R == 1 is carve_rollout's layout: the call is then eg_generator_forward_rollout itself).  Phase A: carve(N, N*R) -- the tower
+// side at N = U*W clips, fusion / encoder / decoder buffers at N*R rows.  Phase B runs the prior encoder at batch U*R, which carve sizes
+// for N: when U*R > N (R > W) its buffers are taken again at U*R.  No copy of `sampled`: the fusion kernel reads the caller's order.
+struct RollDrawsWs { GenWs a; int64_t kv[8], prior[2], spec, text, total; };
+RollDrawsWs carve_rollout_draws(const EgGenerator* g, int U, int64_t N, int R) {
+    const EgGeneratorConfig& c = g->cfg;
+    RollDrawsWs r;
+    r.a = carve(g, (int)N, (int)(N * R));
+    GenWs& w = r.a;
+    Carver cv;
+    cv.off = w.total;
+    const int64_t UR = (int64_t)U * R, D = c.d_model;
+    if (UR > N) {
+        const int64_t BF = UR * c.frames, B64 = eg_round_up(BF, 64);
+        w.prior_cat = cv.take(BF * g->Dpad); w.prior_h = cv.take(BF * D); w.prior_enc = cv.take(BF * D);
+        w.im_p[0] = cv.take(B64 * D); w.im_p[1] = cv.take(B64 * D);
+        w.tm_mem = cv.take(UR * c.pose_dim); w.tm_pe = cv.take(UR * c.chunk + 16);
+    }
+    for (int l = 0; l < c.n_layers; ++l) r.kv[l] = cv.take(N * R * c.frames * 2 * D);
+    r.prior[0] = cv.take(UR * c.prior_frames * c.pose_dim);
+    r.prior[1] = cv.take(UR * c.prior_frames * c.pose_dim);
+    r.spec = cv.take(N * c.n_mels * c.spec_len);
+    r.text = cv.take(N * c.text_len * 2);
+    r.total = cv.off;
+    return r;
+}
+}  // namespace
+
+extern "C" int64_t eg_generator_rollout_draws_workspace_bytes(const EgGenerator* g, int32_t utterances, int32_t windows, int32_t draws) {
+    if (!g || utterances <= 0 || windows <= 0 || draws <= 0 || g->cfg.n_layers > 8) return 0;
+    const int64_t N = (int64_t)utterances * windows;
+    if (N > (1 << 20) || N * draws > (1 << 20)) return 0;
+    if (draws == 1) return carve_rollout(g, utterances, N).total;
+    return carve_rollout_draws(g, utterances, N, draws).total;
+}
+
+// Models_spatial_memory.py:566-616 / Models_memory.py:521-565 per (window, draw), chained as eg_generator_forward_rollout chains them.  The
+// sampled map enters at :601-602 / :551-552 (fusion input) and the prior at :585 / :535 -> decoder target stream (:611 / :560) only, so
+// :583, :588-592 (audio tower, emotion / semantic projections, classifier header) run once per clip, :607-609 and the decoder's K|V once
+// per (clip, draw), and the W dependent steps (:585, :611-614) at batch U*R.  Row u*R + r of every step is recording u*R + r of the replicated eg_generator_forward_rollout call;
+// step 0's prior is seed_pose[u] repeated over the draws by ONE launch of U*R*P*D elements (draws_seed_kernel) into the ping-pong buffer
+// step 0 does not write, so the prior encoder and the hand-off kernel read it as they read every later step's.
+extern "C" int eg_generator_forward_rollout_draws(const EgGenerator* g, const float* arena, int32_t U, int32_t W, int32_t R, const float* spec,
+                                                  const int64_t* text, const float* seed_pose, const float* sampled, const float* alpha,
+                                                  float* track, float* windows, float* emotion_prediction, float* emotion_feature,
+                                                  float* semantic_feature, float* text_embedding, void* ws, int64_t ws_bytes, void* stream) {
+    EG_REQUIRE(g && arena && spec && seed_pose && sampled && track && ws, EG_ERR_BAD_ARG, "eg_generator_forward_rollout_draws: null pointer");
+    EG_REQUIRE(U >= 1, EG_ERR_BAD_ARG, "eg_generator_forward_rollout_draws: utterances=%d (need >= 1)", U);
+    EG_REQUIRE(W >= 1, EG_ERR_BAD_ARG, "eg_generator_forward_rollout_draws: windows=%d (need >= 1)", W);
+    EG_REQUIRE(R >= 1, EG_ERR_BAD_ARG, "eg_generator_forward_rollout_draws: draws=%d (need >= 1)", R);
+    EG_REQUIRE((int64_t)U * W <= (1 << 20) && (int64_t)U * W * R <= (1 << 20), EG_ERR_UNSUPPORTED,
+               "eg_generator_forward_rollout_draws: utterances*windows*draws=%d*%d*%d > 2^20", U, W, R);
+    EG_REQUIRE(text || !text_embedding, EG_ERR_BAD_ARG, "eg_generator_forward_rollout_draws: text_embedding wanted without text");
+    EG_REQUIRE(g->cfg.n_layers <= 8, EG_ERR_UNSUPPORTED, "eg_generator_forward_rollout_draws: n_layers=%d > 8", g->cfg.n_layers);
+    const int64_t need = eg_generator_rollout_draws_workspace_bytes(g, U, W, R);
+    EG_REQUIRE(ws_bytes >= need, EG_ERR_WORKSPACE, "eg_generator_forward_rollout_draws: workspace %lld < %lld bytes", (long long)ws_bytes,
+               (long long)need);
+    EG_REQUIRE(eg_aligned16(ws) && eg_aligned16(arena) && eg_aligned16(spec) && eg_aligned16(sampled), EG_ERR_ALIGN,
+               "eg_generator_forward_rollout_draws: 16-byte alignment");
+    if (R == 1)         // [U, 1, W, ...] is [U, W, ...]: the roll-out itself, launch for launch
+        return eg_generator_forward_rollout(g, arena, U, W, spec, text, seed_pose, sampled, alpha, track, windows, emotion_prediction,
+                                            emotion_feature, semantic_feature, text_embedding, ws, ws_bytes, stream);
+    const RollDrawsWs r = carve_rollout_draws(g, U, (int64_t)U * W, R);
+    const GenWs& w = r.a;
+    hipStream_t st = (hipStream_t)stream;
+    const EgGeneratorConfig& c = g->cfg;
+    const int F = c.frames, D = c.d_model, N = U * W, UR = U * R, P_ = c.prior_frames, PD = c.pose_dim;
+    const bool swap = U > 1 && W > 1;           // clip n = w*U + u in phase A; (clip, draw) row (w*U + u)*R + r from the fusion on
+
+    // ---- phase A: the tower side at batch N, as the roll-out makes it; fusion, encoder and K|V at N*R rows in draw order
+    if (swap) {
+        EG_TRY(egi_swap01(spec, P(ws, r.spec), U, W, (size_t)c.n_mels * c.spec_len, st));
+        spec = P(ws, r.spec);
+        if (text_embedding) {
+            EG_TRY(egi_swap01(text, P(ws, r.text), U, W, (size_t)c.text_len * 2, st));
+            text = reinterpret_cast<const int64_t*>(P(ws, r.text));
+        }
+    }
+    float* txt = swap ? P(ws, w.t_out) : text_embedding;
+    float* emo = swap || !emotion_feature ? P(ws, w.emo) : emotion_feature;
+    float* sem = swap || !semantic_feature ? P(ws, w.sem) : semantic_feature;
+    float* pred = swap || !emotion_prediction ? P(ws, w.cls_out) : emotion_prediction;
+    if (text_embedding) EG_TRY(run_text(g, arena, text, txt, w, ws, N, st));
+    EG_TRY(run_audio_tower(g, arena, spec, w, ws, N, st));
+    EG_TRY(run_heads(g, arena, emo, sem, pred, w, ws, N, st));
+    EG_TRY(egi_draws_fusion(sampled, sem, P(ws, w.fus_in), U, W, R, (size_t)F * D, st));
+    Act enc_out;
+    EG_TRY(run_encoder(g, arena, P(ws, w.fus_in), enc_out, w, ws, N * R, st));
+    float* kv[8];
+    for (int l = 0; l < c.n_layers; ++l) {
+        kv[l] = P(ws, r.kv[l]);
+        EG_TRY(lin(g, arena, g->dec_attn[l].kv, enc_out, 0, act(kv[l], 2 * D), true, N * R * F, 0, nullptr, 0, st));
+    }
+    if (swap) {
+        if (text_embedding) EG_TRY(egi_swap01(txt, text_embedding, W, U, (size_t)c.text_len * 512, st));
+        if (emotion_feature) EG_TRY(egi_swap01(emo, emotion_feature, W, U, (size_t)F * D, st));
+        if (semantic_feature) EG_TRY(egi_swap01(sem, semantic_feature, W, U, (size_t)F * D, st));
+        if (emotion_prediction) EG_TRY(egi_swap01(pred, emotion_prediction, W, U, 8, st));
+    }
+
+    // ---- phase B, W dependent steps of U*R rows: the roll-out's steps on the (recording, draw) rows
+    EG_TRY(egi_draws_seed(seed_pose, P(ws, r.prior[1]), U, R, P_ * PD, st));
+    const float* prior = P(ws, r.prior[1]);
+    const Act prior_enc = act(P(ws, w.prior_enc), D, P(ws, w.im_p[1]), D);
+    for (int s = 0; s < W; ++s) {
+        EG_TRY(run_prior(g, arena, prior, w, ws, UR, st));
+        float* step_kv[8];
+        for (int l = 0; l < c.n_layers; ++l) step_kv[l] = kv[l] + (size_t)s * UR * F * 2 * D;
+        EG_TRY(run_decoder(g, arena, prior_enc, Act(), step_kv, P(ws, w.pose), w, ws, UR, st));
+        float* next = P(ws, r.prior[s & 1]);
+        EG_TRY(egi_rollout_handoff(P(ws, w.pose), prior, alpha, track, windows, next, UR, W, s, F, P_, PD, st));
+        prior = next;
+    }
+    return EG_OK;
+}
+
 // ---- ragged roll-out: U recordings with their own window counts (plan and kernels: ragged.hip) -----------------------------------------
 extern "C" int64_t eg_generator_rollout_ragged_workspace_bytes(const EgGenerator* g, int32_t utterances, int64_t total_windows) {
     if (!g || utterances <= 0 || total_windows < utterances || g->cfg.n_layers > 8 || total_windows > (1 << 20)) return 0;

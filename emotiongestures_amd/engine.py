@@ -225,6 +225,56 @@ class GeneratorEngine:
             _ptr(out.get("text_embedding")), _ptr(ws), ws_bytes, _stream(dev)), "eg_generator_forward_rollout")
         return out
 
+    # ---- diverse roll-out: several sampled tracks per recording ----
+    def _rollout_draws_args(self, spec, text, seed_pose, sampled, alpha):
+        """Shape contract of forward_rollout_draws (checked before anything touches the device); returns (U, W, R)."""
+        c = self.cfg
+        if sampled is None:
+            raise L.EgError(f"sampled: required, shape (U,R,W,F,d_model) = (U,R,W,{c.frames},{c.d_model}) (without it every draw is the same track)")
+        if sampled.dim() != 5:
+            raise L.EgError(f"sampled shape {tuple(sampled.shape)} != (U,R,W,F,d_model) = (U,R,W,{c.frames},{c.d_model})")
+        R = int(sampled.shape[1])
+        if R < 1:
+            raise L.EgError(f"sampled shape {tuple(sampled.shape)}: draws R={R} (need >= 1) in (U,R,W,F,d_model)")
+        U, W = self._rollout_args(spec, text, seed_pose, None, alpha)
+        if tuple(sampled.shape) != (U, R, W, c.frames, c.d_model):
+            raise L.EgError(f"sampled shape {tuple(sampled.shape)} != (U,R,W,F,d_model) = ({U},{R},{W},{c.frames},{c.d_model})")
+        return U, W, R
+
+    @_locked
+    def forward_rollout_draws(self, spec, text, seed_pose, sampled, alpha=None, want_windows=False, want_aux=False, slot=0):
+        """eg_generator_forward_rollout_draws: R sampled tracks for each of U recordings, the audio tower run once per window.  By definition
+        forward_rollout on U*R recordings, recording u*R + r having spec[u], text[u], seed_pose[u] and sampled[u, r].
+        spec [U,W,n_mels,spec_len], text [U,W,text_len], seed_pose [U,P,D], sampled [U,R,W,F,d_model] (required), alpha [P] or None.
+        Returns a dict: track [U, R, W*(F-P)+P, D], emotion_prediction [U,W,8] (independent of the draw), windows [U,R,W,F,D] with
+        want_windows, emotion_feature / semantic_feature [U,W,F,d_model] and text_embedding [U,W,text_len,512] with want_aux."""
+        U, W, R = self._rollout_draws_args(spec, text, seed_pose, sampled, alpha)
+        if self.arena is None:
+            raise L.EgError("GeneratorEngine.forward_rollout_draws before load_weights")
+        dev = self.arena.device
+        c = self.cfg
+        spec, text, seed_pose = _need_cuda(spec, "spec"), _need_cuda(text, "text", torch.int64), _need_cuda(seed_pose, "seed_pose")
+        sampled = _need_cuda(sampled, "sampled")
+        alpha = None if alpha is None else _need_cuda(alpha, "alpha")
+        ws_bytes = self._lib.eg_generator_rollout_draws_workspace_bytes(self._h, U, W, R)
+        if ws_bytes <= 0:
+            raise L.EgError(f"eg_generator_rollout_draws_workspace_bytes: unsupported U={U} W={W} R={R}")
+        ws = self._workspace(("rollout_draws", U, W, R) if slot == 0 else ("rollout_draws", U, W, R, slot), ws_bytes, dev)
+        F, H = c.frames, c.frames - c.prior_frames
+        out = {"track": torch.empty(U, R, W * H + c.prior_frames, c.pose_dim, device=dev),
+               "emotion_prediction": torch.empty(U, W, 8, device=dev)}
+        if want_windows:
+            out["windows"] = torch.empty(U, R, W, F, c.pose_dim, device=dev)
+        if want_aux:
+            out["emotion_feature"] = torch.empty(U, W, F, c.d_model, device=dev)
+            out["semantic_feature"] = torch.empty(U, W, F, c.d_model, device=dev)
+            out["text_embedding"] = torch.empty(U, W, c.text_len, 512, device=dev)
+        L.check(self._lib.eg_generator_forward_rollout_draws(
+            self._h, _ptr(self.arena), U, W, R, _ptr(spec), _ptr(text), _ptr(seed_pose), _ptr(sampled), _ptr(alpha), _ptr(out["track"]),
+            _ptr(out.get("windows")), _ptr(out["emotion_prediction"]), _ptr(out.get("emotion_feature")), _ptr(out.get("semantic_feature")),
+            _ptr(out.get("text_embedding")), _ptr(ws), ws_bytes, _stream(dev)), "eg_generator_forward_rollout_draws")
+        return out
+
     # ---- ragged roll-out: recordings with their own window counts ----
     def _rollout_ragged_args(self, spec, text, seed_pose, windows_per, sampled, alpha):
         """Shape contract of forward_rollout_ragged (checked before anything touches the device); returns (U, N, windows_per as a tuple)."""

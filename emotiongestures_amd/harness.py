@@ -459,7 +459,7 @@ def evaluate(generator, vae, fgd: MLP_Reconstruct, classifier: Optional[Skeleton
 def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch.Tensor, labels: Optional[torch.Tensor] = None,
                hop_samples: Optional[int] = None, n_samples: Optional[int] = None, windows: Optional[int] = None,
                z: Optional[torch.Tensor] = None, alpha: Optional[torch.Tensor] = None, fps: int = 15, sample_rate: int = 16000,
-               want_windows: bool = False, want_aux: bool = False, mel=None, lengths=None) -> Dict[str, torch.Tensor]:
+               want_windows: bool = False, want_aux: bool = False, mel=None, lengths=None, draws: Optional[int] = None) -> Dict[str, torch.Tensor]:
     """One gesture track per utterance from raw 16 kHz audio: windows -> mel -> optional CVAE sample per window -> roll-out.
 
     ``models = (generator, vae | None)``, eval mode, on the GPU.  ``audio [U, total_samples]``; ``text [U, W, 60]`` (the words of every
@@ -473,10 +473,23 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     is never read).  Recording u then has ``W_u = ceil(lengths[u] / hop_samples)`` windows -- every window that starts inside it, the count a
     stream reaches for a row ended at that length; ``text``, ``labels`` and ``z`` are per recording (labels ``[U, 8]`` only), padded
     ``[U, max W_u, ...]`` or packed ``[sum W_u, ...]``; ``windows`` is not used.  Returns GeneratorEngine.forward_rollout_ragged's dict plus
-    packed ``"spec"`` and ``"windows_per"``."""
+    packed ``"spec"`` and ``"windows_per"``.
+
+    ``draws=R`` (a VAE is required): R sampled tracks per recording in one call.  ``z [U, R, W, 32]`` (default torch.randn on the CPU generator
+    in that shape), ``labels`` ``[U, 8]``, ``[U, W, 8]`` or ``[U, R, W, 8]`` (each draw its own emotion); one ``vae.sample`` at batch
+    ``U*R*W``, mel and window gather once per recording.  Returns GeneratorEngine.forward_rollout_draws's dict (track ``[U, R, T, pose_dim]``)
+    plus ``"spec"``.  Rectangular calls only: not with ``lengths``."""
     from .engine import MelFrontEnd
     gen, vae = models
     _eval_only(gen)
+    if draws is not None:
+        if lengths is not None:
+            raise L.EgError("synthesize: draws= with lengths= is not supported (draws in the ragged roll-out); call the rectangular "
+                            "synthesize(..., draws=R) once per group of recordings of equal length")
+        if vae is None:
+            raise L.EgError("synthesize: draws= needs a VAE (without sampled emotion maps every draw is the same track)")
+        if int(draws) < 1:
+            raise L.EgError(f"synthesize: draws={int(draws)} (need >= 1)")
     eng = gen.engine()
     c = eng.cfg
     if audio.dim() != 2:
@@ -493,6 +506,25 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     mel = MelFrontEnd(audio.device) if mel is None else mel
     with torch.no_grad():
         spec = mel.windows(audio, W, hop, n, out_frames=c.spec_len)
+        if draws is not None:
+            R = int(draws)
+            if labels is None:
+                raise L.EgError("labels: needed with draws= ([U, 8], [U, W, 8] or [U, R, W, 8] one-hot)")
+            lab = labels.to(audio.device)
+            if tuple(lab.shape) == (U, 8):
+                lab = lab[:, None, None, :].expand(U, R, W, 8)
+            elif tuple(lab.shape) == (U, W, 8):
+                lab = lab[:, None, :, :].expand(U, R, W, 8)
+            elif tuple(lab.shape) != (U, R, W, 8):
+                raise L.EgError(f"labels shape {tuple(labels.shape)}: need ({U},8), ({U},{W},8) or ({U},{R},{W},8)")
+            if z is None:
+                z = torch.randn(U, R, W, 32)
+            elif tuple(z.shape) != (U, R, W, 32):
+                raise L.EgError(f"z shape {tuple(z.shape)} != ({U},{R},{W},32)")
+            sampled = vae.sample(lab.reshape(U * R * W, 8).contiguous(), z=z.reshape(U * R * W, 32)).view(U, R, W, c.frames, c.d_model)
+            out = eng.forward_rollout_draws(spec, text, seed_pose, sampled, alpha=alpha, want_windows=want_windows, want_aux=want_aux)
+            out["spec"] = spec
+            return out
         sampled = None
         if vae is not None:
             if labels is None:

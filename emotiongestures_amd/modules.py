@@ -763,7 +763,7 @@ class Transformer(ReplicaAware, nn.Module):
         return self.engine().forward_draws(input_spectrum, prior_seq, sampled_emotion_features, slot=slot)
 
     def synthesize(self, input_spectrum, text, seed_pose, sampled_emotion_features=None, *, alpha=None, want_windows=False,
-                   want_aux=False, slot=0, windows_per=None):
+                   want_aux=False, slot=0, windows_per=None, draws=None):
         """Long-form synthesis: input_spectrum [U,W,n_mels,spec_len], text [U,W,text_len], seed_pose [U,prior_frames,pose_dim],
         sampled_emotion_features [U,W,frames,d_model] or None.  Window w >= 1 is seeded with the raw last prior_frames poses of window
         w-1; the dict returned holds track [U, W*(frames-prior_frames)+prior_frames, pose_dim] (overlaps cross-faded with `alpha`,
@@ -772,8 +772,26 @@ class Transformer(ReplicaAware, nn.Module):
         ``windows_per`` (a sequence of U counts W_u >= 1): recordings of unequal length in one call -- step s runs the recordings with
         W_u > s only.  The window-indexed arguments are then packed ``[N, ...]`` (N = sum W_u, recording u at rows [off[u], off[u] + W_u))
         or padded ``[U, max W_u, ...]`` (packed on the device; entries past W_u are never read); the dict is
-        GeneratorEngine.forward_rollout_ragged's: track [U, max W_u * H + P, pose_dim] zero past track_frames[u], per-window outputs packed."""
+        GeneratorEngine.forward_rollout_ragged's: track [U, max W_u * H + P, pose_dim] zero past track_frames[u], per-window outputs packed.
+
+        ``draws=R``: R sampled tracks per recording in one call, the audio tower run once per window -- sampled_emotion_features
+        [U,R,W,frames,d_model] is then required; the result is that of ``synthesize`` on U*R recordings, recording u*R + r having the
+        inputs of u and sampled_emotion_features[u, r]: track [U,R,T,pose_dim], windows [U,R,W,frames,pose_dim], the outputs that do not
+        depend on the draw returned once (GeneratorEngine.forward_rollout_draws).  Rectangular calls only: not with ``windows_per``."""
         _eval_only(self)
+        if draws is not None:
+            if windows_per is not None:
+                raise L.EgError("synthesize: draws= with windows_per= is not supported (draws in the ragged roll-out); call the rectangular "
+                                "synthesize(..., draws=R) once per group of recordings with equal window counts")
+            R = int(draws)
+            s = sampled_emotion_features
+            if R < 1:
+                raise L.EgError(f"synthesize: draws={R} (need >= 1)")
+            if s is None or s.dim() != 5 or s.shape[1] != R:
+                raise L.EgError(f"synthesize(draws={R}): sampled_emotion_features shape {None if s is None else tuple(s.shape)} != "
+                                f"(U,R,W,F,d_model) with R={R}")
+            return self.engine().forward_rollout_draws(input_spectrum, text, seed_pose, s, alpha=alpha, want_windows=want_windows,
+                                                       want_aux=want_aux, slot=slot)
         if windows_per is None:
             return self.engine().forward_rollout(input_spectrum, text, seed_pose, sampled_emotion_features, alpha=alpha,
                                                  want_windows=want_windows, want_aux=want_aux, slot=slot)

@@ -149,7 +149,11 @@ class GestureStream:
     `hop_samples` / `n_samples` default to the generator's geometry as in harness.synthesize; `graph=True` replays one captured hipGraph."""
 
     def __init__(self, models: Tuple, rows: int, seed_pose: torch.Tensor, *, hop_samples: Optional[int] = None, n_samples: Optional[int] = None,
-                 fps: int = 15, sample_rate: int = 16000, alpha: Optional[torch.Tensor] = None, graph: bool = True, want_windows: bool = False):
+                 fps: int = 15, sample_rate: int = 16000, alpha: Optional[torch.Tensor] = None, graph: bool = True, want_windows: bool = False,
+                 draws: Optional[int] = None):
+        if draws is not None:
+            raise L.EgError("GestureStream: draws= is not supported (a stream has one track per row); for several sampled tracks of a whole "
+                            "recording call the rectangular synthesize(..., draws=R), or open the stream with each speaker's row repeated")
         self.gen, self.vae, self.mel = models
         if self.mel is None and (hop_samples is not None or n_samples is not None):
             raise L.EgError("hop_samples / n_samples: the session has no mel front-end (models[2] is None); it takes one ready window per push_spec")

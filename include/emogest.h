@@ -202,6 +202,39 @@ int eg_generator_forward_rollout(const EgGenerator* g, const float* arena, int32
                                  void* workspace, int64_t workspace_bytes, void* stream);
 int64_t eg_generator_rollout_workspace_bytes(const EgGenerator* g, int32_t utterances, int32_t windows);
 
+/* Diverse roll-out: R = draws sampled tracks for each of U recordings in one call.  By definition the result is
+ * eg_generator_forward_rollout on U*R recordings, recording u*R + r having spec[u], text[u], seed_pose[u] and sampled[u, r]:
+ *   spec [U, W, n_mels, spec_len]   text [U, W, text_len] int64 (may be NULL unless text_embedding is wanted)   seed_pose [U, P, D]
+ *   sampled [U, R, W, F, d_model], REQUIRED (without it every draw would be the same track)        alpha [P] or NULL
+ *   track [U, R, W*H + P, D];  optional: windows [U, R, W, F, D], and -- independent of the draw, returned once --
+ *   emotion_prediction [U, W, 8], emotion_feature / semantic_feature [U, W, F, d_model], text_embedding [U, W, text_len, 512]
+ * The sampled map enters the generator at the fusion input (Models_spatial_memory.py:601-602 / Models_memory.py:551-552) and the prior
+ * through the prior encoder -> decoder target stream only (:585, :611 / :535, :560), so the text branch, the audio tower, the projections
+ * and the classifier header (:577-592 / :527-542) see neither the draw nor the prior:
+ *   A: tower side at batch N = U*W in clip order n = w*U + u -- the launches eg_generator_forward_rollout makes at batch N; ONE fusion
+ *      launch (draws.hip) writes fus_in[(w*U + u)*R + r] = sampled[u, r, w] + semantic[w*U + u], reading the caller's order (no
+ *      window-major copy of `sampled`); encoder and every decoder layer's K|V product at N*R sequences;
+ *   B: W steps at batch U*R: prior encoder -> decoder over the step's contiguous K|V slice -> post_projector -> the roll-out's hand-off
+ *      kernel with U*R rows (the same handoff_blend).  Row u*R + r of a step is row u*R + r of track viewed [U*R, T, D]; in the memory
+ *      variant TM_Memory_Net couples the U*R rows of a step, as in the replicated call.  Step 0's prior is seed_pose[u] repeated over
+ *      the R draws by one launch of U*R*P*D elements (not by indexing row / R where the seed is read).
+ * Same contract as eg_generator_forward_rollout: one stream, no allocation, host round trip or synchronisation; launches, grids and
+ * pointers are fixed for fixed (U, W, R): capturable into one hipGraph.  Fusion, encoder, K|V and phase B run at the batch of the
+ * replicated call, and the tower-side products accumulate K in one order from two clips up, so for U*W >= 2 every output equals the
+ * replicated eg_generator_forward_rollout bit for bit (f32 and bf16x3); at U*W == 1 the tower side takes the one-clip paths (split-K of
+ * w_2, the one-clip convolution tiles) where the replicated call has R clips: equal to rounding.  With draws == 1 the call IS
+ * eg_generator_forward_rollout (its launches, its bits).
+ * Refuses by name, before the first launch: a null required pointer (sampled included), utterances / windows / draws < 1,
+ * utterances*windows*draws > 2^20, n_layers > 8, text_embedding without text, a short workspace, buffers not 16-byte aligned.
+ * workspace >= eg_generator_rollout_draws_workspace_bytes, which is 0 for arguments the call would refuse and equals
+ * eg_generator_rollout_workspace_bytes(g, U, W) at draws == 1. */
+int eg_generator_forward_rollout_draws(const EgGenerator* g, const float* arena, int32_t utterances, int32_t windows, int32_t draws,
+                                       const float* spec, const int64_t* text, const float* seed_pose, const float* sampled,
+                                       const float* alpha, float* track, float* windows_out, float* emotion_prediction,
+                                       float* emotion_feature, float* semantic_feature, float* text_embedding,
+                                       void* workspace, int64_t workspace_bytes, void* stream);
+int64_t eg_generator_rollout_draws_workspace_bytes(const EgGenerator* g, int32_t utterances, int32_t windows, int32_t draws);
+
 /* Ragged roll-out: the roll-out above for U recordings with their OWN window counts W_u >= 1 (N = sum W_u, Wmax = max W_u), in one call.
  * Step s (0 <= s < Wmax) is the generator on the ACTIVE recordings {u : W_u > s}, taken in the working order "longer first, ties by
  * index" (stable sort by (-W_u, u)): the active set of every step is a prefix of that order, the batch of step s is U_s = #{u : W_u > s},

@@ -6,7 +6,9 @@
   batch U*W, then W dependent decoder steps, each seeded with the raw last 4 poses of the one before)--> one gesture track per recording.
 
 Weights are synthetic (integer hash), so the poses carry no meaning; the script shows the call sequence and prints the shapes, the seam
-statistics of the track and the time of one call.  usage: demo_synthesize.py [utterances=4] [seconds=60]"""
+statistics of the track and the time of one call.  With --draws R it then makes R tracks per recording in one call (draw r delivers the line
+in emotion (u + r) % 8; the audio tower runs once per window, not R times) and, with --out FILE.npz, writes them: tracks [U, R, T, pose_dim].
+usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--out tracks.npz]"""
 import os
 import sys
 import time
@@ -20,8 +22,17 @@ from emotiongestures_amd.builders import build_mirror
 from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
 from emotiongestures_amd.synth import load_synth_weights, synth_audio
 
-U = int(sys.argv[1]) if len(sys.argv) > 1 else 4
-seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 60.0
+argv, DRAWS, OUT = [], 0, None
+it = iter(sys.argv[1:])
+for a in it:
+    if a == "--draws":
+        DRAWS = int(next(it))
+    elif a == "--out":
+        OUT = next(it)
+    else:
+        argv.append(a)
+U = int(argv[0]) if len(argv) > 0 else 4
+seconds = float(argv[1]) if len(argv) > 1 else 60.0
 dev = torch.device("cuda:0")
 FRAMES, POSE_DIM, PRIOR, FPS = 34, 126, 4, 15           # TED timing: 34 poses @ 15 fps, 4 of them the prior
 HOP = FRAMES - PRIOR
@@ -64,3 +75,23 @@ if U > 1:
           f"rows past a recording's end are zero: {all(not bool(rag['track'][u, frames[u]:].any()) for u in range(U))}; "
           f"the longest recording against the rectangular call's: rel-L2 {float((rag['track'][U - 1] - track[U - 1]).norm() / track[U - 1].norm()):.1e} "
           f"(its last steps run alone, at batch 1)")
+
+# Several candidate performances of every recording in one call: draw r of recording u is sampled with emotion (u + r) % 8 and its own latents.
+if DRAWS > 0:
+    labels_r = torch.nn.functional.one_hot((torch.arange(U)[:, None] + torch.arange(DRAWS)[None, :]) % 8, 8).float()
+    labels_r = labels_r[:, :, None, :].expand(U, DRAWS, W, 8).to(dev)
+    zr = torch.randn(U, DRAWS, W, 32)
+    H.synthesize((gen, vae), audio, text, seed_pose, labels=labels_r, z=zr, draws=DRAWS)                  # warm-up
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    div = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels_r, z=zr, draws=DRAWS)
+    torch.cuda.synchronize()
+    dt_r = time.perf_counter() - t0
+    tracks = div["track"]
+    spread = (tracks - tracks.mean(dim=1, keepdim=True)).norm(dim=3).mean()
+    print(f"--draws {DRAWS}: tracks {tuple(tracks.shape)} in one call, {1e3 * dt_r:.2f} ms = {1e3 * dt_r / (U * DRAWS * tracks.shape[2] / FPS):.4f} ms per "
+          f"second of track (one track per recording: {1e3 * dt / (U * track.shape[1] / FPS):.4f}); mean distance of a draw from its recording's mean "
+          f"track: {float(spread):.4f}")
+    if OUT:
+        np.savez(OUT, tracks=tracks.cpu().numpy(), emotion=((torch.arange(U)[:, None] + torch.arange(DRAWS)[None, :]) % 8).numpy(), fps=FPS)
+        print(f"wrote {OUT}: tracks [U, R, T, pose_dim] = {tuple(tracks.shape)}")
