@@ -1,7 +1,11 @@
 """Beat-alignment score (model/Beat_score_v2.py:51-197, ``alignment(sigma=0.3, order=2)``), the seventh metric of the eval loop's summary
 line (test_emotion_gesture_diversity_iterative.py:241-248,258-261).
 
-Batched GPU path: ``beat_alignment(audio, pose)`` runs load_audio + load_pose + calculate_align for a whole batch in two HIP kernels
+Whole recordings: ``beat_alignment_tracks(audio, track, lengths, frames)`` scores roll-outs of any and unequal length, several draws per
+recording, with the per-frame arrays in a workspace instead of one workgroup's LDS (csrc/beat_tracks.hip); where a recording fits the clip
+call it returns the clip call's bits.
+
+Batched GPU path (clips up to 32 s): ``beat_alignment(audio, pose)`` runs load_audio + load_pose + calculate_align for a whole batch in two HIP kernels
 (csrc/mel.hip: beat_stft_kernel, beat_align_kernel) and returns the fp64 per-clip scores.  Drop-in path: ``alignment`` has the reference's
 constructor and methods; ``load_audio`` runs the kernels' audio-only mode on one clip, ``load_pose`` / ``calculate_align`` are host numpy /
 scipy following the reference line by line (they are also the in-package reference the GPU's fused stages are tested against).
@@ -22,7 +26,7 @@ import torch
 
 from . import _lib as L
 
-__all__ = ["beat_alignment", "alignment", "L1div", "SRGR", "BeatScoreUnavailable", "MAX_FRAMES", "SAMPLE_RATE"]
+__all__ = ["beat_alignment", "beat_alignment_tracks", "alignment", "L1div", "SRGR", "BeatScoreUnavailable", "MAX_FRAMES", "SAMPLE_RATE"]
 
 SAMPLE_RATE = 16000
 HOP = 512
@@ -128,6 +132,138 @@ def beat_alignment(audio: torch.Tensor, pose: torch.Tensor, fps: int = 15, t_sta
         audio = audio[:, t_start * SAMPLE_RATE:]
     score, beats = _run(audio, pose, fps, t_start, t_end, sigma, order, want_beats)
     return (score, beats) if want_beats else score
+
+
+# ---- whole recordings ---------------------------------------------------------------------------------------------------------------
+class _TracksPlan:
+    """Host vectors, the uploaded meta table and the workspace size of one (lengths, frames, t_end, fps, draws, Tmax, device)."""
+    _cache: Dict[tuple, "_TracksPlan"] = {}
+    _CACHE_MAX = 16
+
+    def __init__(self, lib, lengths, frames, t_end, fps, draws, Tmax, device):
+        U = len(lengths)
+        self.U = U
+        self.lengths = np.ascontiguousarray(lengths, np.int32)
+        self.frames = None if frames is None else np.ascontiguousarray(frames, np.int32)
+        self.t_end = None if t_end is None else np.ascontiguousarray(t_end, np.int32)
+        hp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        self.h_lengths, self.h_frames, self.h_t_end = hp(self.lengths), hp(self.frames), hp(self.t_end)
+        meta = np.zeros(max(int(lib.eg_beat_tracks_meta_ints(U)), 1), np.int32)
+        L.check(lib.eg_beat_tracks_meta(self.h_lengths, self.h_frames, self.h_t_end, int(fps), U, meta.ctypes.data_as(C.c_void_p)),
+                "eg_beat_tracks_meta")
+        self.T = 1 + self.lengths // HOP
+        self.offsets = np.concatenate([[0], np.cumsum(self.T)[:-1]]).astype(np.int64)
+        self.sum_T = int(self.T.sum())
+        self.bytes = int(lib.eg_beat_tracks_workspace_bytes(self.h_lengths, self.h_frames, U, int(draws), int(Tmax)))
+        if self.bytes <= 0:
+            raise L.EgError(f"eg_beat_tracks_workspace_bytes: refused ({lib.eg_last_error().decode()})")
+        self.meta = torch.from_numpy(meta).to(device)
+
+    @classmethod
+    def get(cls, lib, lengths, frames, t_end, fps, draws, Tmax, device) -> "_TracksPlan":
+        key = (tuple(lengths), None if frames is None else tuple(frames), None if t_end is None else tuple(t_end), int(fps), int(draws),
+               int(Tmax), str(device))
+        p = cls._cache.get(key)
+        if p is None:
+            if len(cls._cache) >= cls._CACHE_MAX:
+                cls._cache.pop(next(iter(cls._cache)))
+            p = cls._cache[key] = cls(lib, lengths, frames, t_end, fps, draws, Tmax, device)
+        return p
+
+
+def _int_list(v, n, name):
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu().tolist()
+    v = [int(a) for a in (v.tolist() if isinstance(v, np.ndarray) else v)]
+    if len(v) != n:
+        raise ValueError(f"beat_alignment_tracks: {name} has {len(v)} entries for {n} recordings")
+    return v
+
+
+def _run_tracks(audio: torch.Tensor, track: Optional[torch.Tensor], lengths, frames, fps, t_start, t_end, sigma, order, want_beats,
+                workspace: Optional[torch.Tensor] = None, out: Optional[dict] = None):
+    """One eg_beat_align_tracks call.  ``audio`` is already sliced at t_start; ``track [U, R, Tmax, D]`` or None (audio half only).
+    ``workspace`` / ``out``: preallocated buffers of an earlier call with the same shapes (graph capture: no allocation inside)."""
+    dev = audio.device
+    U, stride = audio.shape
+    R = Tmax = D = 0
+    if track is not None:
+        _, R, Tmax, D = track.shape
+    tab = _Tables.get(dev)
+    lib = tab.lib
+    plan = _TracksPlan.get(lib, lengths, frames if track is not None else None, t_end if track is not None else None, fps, max(R, 1), Tmax, dev)
+    ws = workspace if workspace is not None else torch.empty(plan.bytes, dtype=torch.uint8, device=dev)
+    if out is None:
+        out = {"score": torch.empty(U, R, dtype=torch.float64, device=dev) if track is not None else None,
+               "n_audio_beats": torch.empty(U, dtype=torch.int32, device=dev), "oenv": None, "rms": None, "audio_beats": None,
+               "pose_beats": None}
+        if want_beats:
+            out["oenv"] = torch.empty(plan.sum_T, dtype=torch.float32, device=dev)
+            out["rms"] = torch.empty(plan.sum_T, dtype=torch.float32, device=dev)
+            out["audio_beats"] = torch.empty(3, plan.sum_T, dtype=torch.uint8, device=dev)
+            if track is not None:
+                out["pose_beats"] = torch.empty(U, R, 8, Tmax - 1, dtype=torch.uint8, device=dev)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    L.check(lib.eg_beat_align_tracks(_ptr(audio), U, stride, plan.h_lengths, _ptr(plan.meta), _ptr(track), max(R, 1), Tmax, D, plan.h_frames,
+                                     int(fps), int(t_start), plan.h_t_end, float(sigma), int(order), _ptr(tab.fb), _ptr(tab.win), _ptr(tab.tw),
+                                     _ptr(tab.band), _ptr(ws), ws.numel(), _ptr(out["score"]), _ptr(out["n_audio_beats"]), _ptr(out["oenv"]),
+                                     _ptr(out["rms"]), _ptr(out["audio_beats"]), _ptr(out["pose_beats"]), stream), "eg_beat_align_tracks")
+    return out, plan, ws
+
+
+def beat_alignment_tracks(audio: torch.Tensor, track: torch.Tensor, lengths=None, frames=None, fps: int = 15, t_start: int = 0, t_end=None,
+                          sigma: float = 0.3, order: int = 2, want_beats: bool = False):
+    """Beat-alignment scores of whole recordings: ``alignment(sigma, order)`` on ``(audio[u, :lengths[u]], track[u, r, :frames[u]])`` for
+    every recording u and draw r, any length, one call (eg_beat_align_tracks).
+
+    audio [U, stride] fp32 CUDA, 16 kHz, ``lengths[u]`` real samples in row u (default: the whole row; nothing past them is read);
+    track [U, Tmax, D] or [U, R, Tmax, D] fp32 CUDA with D >= 174, ``frames[u]`` real poses (default Tmax).  ``t_start`` is common (audio sliced
+    at t_start * 16000 as load_audio does), ``t_end``: None (int(frames[u] / fps) per recording), an int, or U ints.  The audio half of a
+    recording runs once and serves its R draws.  Returns fp64 scores [U] or [U, R] on the device, NaN for a recording without onsets.
+
+    ``want_beats`` also returns the dict of ``beat_alignment`` with the per-recording arrays zero-padded to the longest recording and the
+    counts beside them: ``n_audio_beats`` [U], ``oenv`` / ``rms`` [U, max T], ``audio_beats`` [U, 3, max T] uint8, ``n_frames`` [U] (the
+    onset frames T_u of each recording), ``pose_beats`` [U, (R,) 8, Tmax-1] uint8, ``pose_frames`` [U].  Where a recording fits
+    ``beat_alignment`` every one of these equals, bit for bit, what ``beat_alignment`` returns for the trimmed rows."""
+    if not (isinstance(audio, torch.Tensor) and audio.is_cuda):
+        raise RuntimeError("beat_alignment_tracks: audio must be a CUDA tensor (there is no CPU fallback)")
+    if not (isinstance(track, torch.Tensor) and track.device == audio.device):
+        raise RuntimeError("beat_alignment_tracks: track must be a CUDA tensor on the audio's device")
+    if audio.dim() != 2:
+        raise ValueError(f"beat_alignment_tracks: audio must be [U, samples], got {tuple(audio.shape)}")
+    U = audio.shape[0]
+    if track.dim() not in (3, 4) or track.shape[0] != U:
+        raise ValueError(f"beat_alignment_tracks: track must be [U, Tmax, D] or [U, R, Tmax, D] with U={U}, got {tuple(track.shape)}")
+    has_draws = track.dim() == 4
+    if track.shape[-1] < POSE_MIN_DIM:
+        raise ValueError(f"beat_alignment_tracks: pose_dim={track.shape[-1]}: the beat joints are columns 18:42 and 150:174 "
+                         f"(needs >= {POSE_MIN_DIM})")
+    trk = track.to(torch.float32).contiguous()
+    trk = trk if has_draws else trk[:, None]
+    Tmax = trk.shape[2]
+    lengths = [audio.shape[1]] * U if lengths is None else _int_list(lengths, U, "lengths")
+    frames = [Tmax] * U if frames is None else _int_list(frames, U, "frames")
+    if t_end is not None:
+        t_end = [int(t_end)] * U if isinstance(t_end, (int, np.integer)) else _int_list(t_end, U, "t_end")
+    audio = audio.to(torch.float32)
+    if t_start:
+        audio = audio[:, int(t_start) * SAMPLE_RATE:]
+        lengths = [n - int(t_start) * SAMPLE_RATE for n in lengths]
+    audio = audio.contiguous()
+    out, plan, _ws = _run_tracks(audio, trk, lengths, frames, fps, t_start, t_end, sigma, order, want_beats)
+    score = out["score"] if has_draws else out["score"][:, 0]
+    if not want_beats:
+        return score
+    maxT = int(plan.T.max())
+    idx = torch.from_numpy((plan.offsets[:, None] + np.minimum(np.arange(maxT)[None, :], plan.T[:, None] - 1)).astype(np.int64)).to(audio.device)
+    live = torch.from_numpy(np.arange(maxT)[None, :] < plan.T[:, None]).to(audio.device)
+    pad = lambda packed: torch.where(live, packed[idx], torch.zeros((), dtype=packed.dtype, device=packed.device))
+    am = torch.stack([pad(out["audio_beats"][a]) for a in range(3)], dim=1)
+    pb = out["pose_beats"] if has_draws else out["pose_beats"][:, 0]
+    beats = {"n_audio_beats": out["n_audio_beats"], "oenv": pad(out["oenv"]), "rms": pad(out["rms"]), "audio_beats": am, "pose_beats": pb,
+             "n_frames": torch.from_numpy(plan.T.astype(np.int32)).to(audio.device),
+             "pose_frames": torch.tensor(frames, dtype=torch.int32, device=audio.device)}
+    return score, beats
 
 
 # ---- drop-in for `from model.Beat_score_v2 import alignment` ----------------------------------------------------------------------

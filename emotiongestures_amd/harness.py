@@ -459,7 +459,8 @@ def evaluate(generator, vae, fgd: MLP_Reconstruct, classifier: Optional[Skeleton
 def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch.Tensor, labels: Optional[torch.Tensor] = None,
                hop_samples: Optional[int] = None, n_samples: Optional[int] = None, windows: Optional[int] = None,
                z: Optional[torch.Tensor] = None, alpha: Optional[torch.Tensor] = None, fps: int = 15, sample_rate: int = 16000,
-               want_windows: bool = False, want_aux: bool = False, mel=None, lengths=None, draws: Optional[int] = None) -> Dict[str, torch.Tensor]:
+               want_windows: bool = False, want_aux: bool = False, mel=None, lengths=None, draws: Optional[int] = None,
+               beat: bool = False) -> Dict[str, torch.Tensor]:
     """One gesture track per utterance from raw 16 kHz audio: windows -> mel -> optional CVAE sample per window -> roll-out.
 
     ``models = (generator, vae | None)``, eval mode, on the GPU.  ``audio [U, total_samples]``; ``text [U, W, 60]`` (the words of every
@@ -478,10 +479,16 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     ``draws=R`` (a VAE is required): R sampled tracks per recording in one call.  ``z [U, R, W, 32]`` (default torch.randn on the CPU generator
     in that shape), ``labels`` ``[U, 8]``, ``[U, W, 8]`` or ``[U, R, W, 8]`` (each draw its own emotion); one ``vae.sample`` at batch
     ``U*R*W``, mel and window gather once per recording.  Returns GeneratorEngine.forward_rollout_draws's dict (track ``[U, R, T, pose_dim]``)
-    plus ``"spec"``.  Rectangular calls only: not with ``lengths``."""
+    plus ``"spec"``.  Rectangular calls only: not with ``lengths``.
+
+    ``beat=True`` (opt-in; BEAT-shaped generators, pose_dim >= 174): adds ``"beat"``, the beat-alignment score of every returned track
+    against the audio it was made from (beat.beat_alignment_tracks: fp64 ``[U]``, or ``[U, R]`` with ``draws``), recording u scored on its
+    own ``lengths[u]`` samples and its own ``W_u * (frames - prior_frames) + prior_frames`` poses."""
     from .engine import MelFrontEnd
     gen, vae = models
     _eval_only(gen)
+    if beat and seed_pose.shape[-1] < 174:
+        raise L.EgError(f"synthesize: beat=True: pose_dim={seed_pose.shape[-1]}: the beat joints are columns 18:42 and 150:174 (needs >= 174)")
     if draws is not None:
         if lengths is not None:
             raise L.EgError("synthesize: draws= with lengths= is not supported (draws in the ragged roll-out); call the rectangular "
@@ -496,8 +503,11 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
         raise L.EgError(f"audio shape {tuple(audio.shape)} != (U, total_samples)")
     U = audio.shape[0]
     if lengths is not None:
-        return _synthesize_ragged(eng, vae, audio, lengths, text, seed_pose, labels, hop_samples, n_samples, z, alpha, fps, sample_rate,
-                                  want_windows, want_aux, mel)
+        out = _synthesize_ragged(eng, vae, audio, lengths, text, seed_pose, labels, hop_samples, n_samples, z, alpha, fps, sample_rate,
+                                 want_windows, want_aux, mel)
+        if beat:
+            _add_beat(out, audio, c, fps, lengths, out["windows_per"])
+        return out
     W = int(text.shape[1]) if windows is None and text.dim() == 3 else windows
     if W is None or W < 1:
         raise L.EgError(f"windows={W} (need >= 1): text must be [U, W, {c.text_len}] or `windows` given")
@@ -524,6 +534,8 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
             sampled = vae.sample(lab.reshape(U * R * W, 8).contiguous(), z=z.reshape(U * R * W, 32)).view(U, R, W, c.frames, c.d_model)
             out = eng.forward_rollout_draws(spec, text, seed_pose, sampled, alpha=alpha, want_windows=want_windows, want_aux=want_aux)
             out["spec"] = spec
+            if beat:
+                _add_beat(out, audio, c, fps, None, [W] * U)
             return out
         sampled = None
         if vae is not None:
@@ -534,7 +546,18 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
             sampled = vae.sample(lab, z=None if z is None else z.reshape(U * W, 32)).view(U, W, c.frames, c.d_model)
         out = eng.forward_rollout(spec, text, seed_pose, sampled, alpha=alpha, want_windows=want_windows, want_aux=want_aux)
     out["spec"] = spec
+    if beat:
+        _add_beat(out, audio, c, fps, None, [W] * U)
     return out
+
+
+def _add_beat(out, audio, c, fps, lengths, windows_per):
+    """``out["beat"]``: the beat-alignment score of the roll-out's tracks against the recordings' own audio."""
+    from .beat import beat_alignment_tracks
+    H = c.frames - c.prior_frames
+    frames = [int(w) * H + c.prior_frames for w in windows_per]
+    with torch.no_grad():
+        out["beat"] = beat_alignment_tracks(audio, out["track"], lengths=lengths, frames=frames, fps=fps)
 
 
 def _synthesize_ragged(eng, vae, audio, lengths, text, seed_pose, labels, hop_samples, n_samples, z, alpha, fps, sample_rate, want_windows,

@@ -437,6 +437,43 @@ int eg_beat_align(const float* audio, int32_t batch, int32_t n_samples, const fl
                   double* score, int32_t* n_audio_beats, float* oenv, float* rms, uint8_t* audio_beats, uint8_t* pose_beats,
                   void* stream);
 
+/* The same score for whole recordings of any and unequal length, R gesture tracks ("draws") per recording: the score of a synthesize()
+ * roll-out.  EG_BEAT_MAX_FRAMES does not apply: the per-frame arrays live in the workspace, packed recording after recording, and every
+ * stage that grows with the recording is a grid over the chip (csrc/beat_tracks.hip).  The audio half of a recording is computed once and
+ * serves all its draws.  A recording that fits eg_beat_align gets, for every output, the bits eg_beat_align gives on its trimmed rows.
+ *
+ * audio [U, stride] fp32 16 kHz, row u holds lengths[u] real samples (already sliced at t_start * 16000); nothing past lengths[u] is read.
+ * pose [U, draws, Tmax, pose_dim] fp32, recording u has frames[u] real poses; pose == NULL: audio half only (draws / Tmax / frames / score /
+ * pose_beats unused).  lengths / frames / t_end: HOST arrays [U]; t_end == NULL: frames[u] / pose_fps per recording.
+ *
+ * d_meta: a device copy of the table eg_beat_tracks_meta writes (eg_beat_tracks_meta_ints(U) int32: a head {U, sum T, max T, max frames}, then
+ * per recording {length, T_u = 1 + length / 512, frames, offset = sum of the earlier T, t_end, 0, 0, 0}); host only, no HIP call.  The caller
+ * uploads it once per (lengths, frames, t_end) and passes the same host vectors to the call, which checks them but does not read d_meta.
+ *
+ * Outputs, each written only when non-NULL (score required with a pose): score [U * draws] fp64 (NaN for a recording without onsets),
+ * n_audio_beats [U], oenv / rms [sum T] packed at the table's offsets, audio_beats [3, sum T] uint8 (as eg_beat_align's, packed),
+ * pose_beats [U * draws, 8, Tmax - 1] uint8 (zero past a recording's own frames).
+ * Refused with the argument's name: null required pointers, U < 1, draws < 1, lengths[u] < 2048 or > stride, frames[u] < 2 or > Tmax,
+ * pose_dim < 174, pose_fps <= 0, order < 1, sigma <= 0, t_start < 0, t_end[u] <= t_start, a workspace below eg_beat_tracks_workspace_bytes
+ * (which is 0 for a refused shape), and sizes beyond the index types: sum T > 2^24, U or U * draws > 65535, U * draws * 8 * (Tmax - 1) >= 2^31.
+ * One hour per recording (T = 112501, 54000 poses) is well inside.  Deterministic, stream-ordered, no allocation, no host synchronisation;
+ * launches, grids and pointers depend on (lengths, frames, draws) only, so the call captures into a hipGraph. */
+int64_t eg_beat_tracks_meta_ints(int32_t recordings);
+int eg_beat_tracks_meta(const int32_t* lengths, const int32_t* frames /*NULL: audio only*/, const int32_t* t_end /*NULL: frames/fps*/,
+                        int32_t pose_fps, int32_t recordings, int32_t* meta);
+int64_t eg_beat_tracks_workspace_bytes(const int32_t* lengths, const int32_t* frames /*NULL: audio only*/, int32_t recordings, int32_t draws,
+                                       int32_t Tmax);
+int eg_beat_align_tracks(const float* audio, int32_t recordings, int64_t stride, const int32_t* lengths, const int32_t* d_meta,
+                         const float* pose, int32_t draws, int32_t Tmax, int32_t pose_dim, const int32_t* frames, int32_t pose_fps,
+                         int32_t t_start, const int32_t* t_end, double sigma, int32_t order, const float* d_melfb_t, const float* d_window,
+                         const float* d_twiddle, const int32_t* d_band, void* workspace, int64_t workspace_bytes, double* score,
+                         int32_t* n_audio_beats, float* oenv, float* rms, uint8_t* audio_beats, uint8_t* pose_beats, void* stream);
+/* Test entry: the wait-suppressed scan of peak_pick as the per-frame rule "accepted iff a candidate at an even offset from the start of its
+ * run of candidates" plus the compaction, on a caller-made d_cand [sum T] uint8 packed as the table places the recordings.  events [sum T]
+ * int32 (recording u's accepted frames ascending from its offset), counts [U]; workspace as for the audio half. */
+int eg_beat_tracks_scan(const uint8_t* d_cand, const int32_t* lengths, int32_t recordings, const int32_t* d_meta, void* workspace,
+                        int64_t workspace_bytes, int32_t* events, int32_t* counts, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Block-level operators (the reference's L2 blocks), used by the module-level mirrors and by the
  * per-kernel parity tests.  Weights here are passed as individual device pointers in the PACKED

@@ -8,7 +8,9 @@
 Weights are synthetic (integer hash), so the poses carry no meaning; the script shows the call sequence and prints the shapes, the seam
 statistics of the track and the time of one call.  With --draws R it then makes R tracks per recording in one call (draw r delivers the line
 in emotion (u + r) % 8; the audio tower runs once per window, not R times) and, with --out FILE.npz, writes them: tracks [U, R, T, pose_dim].
-usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--out tracks.npz]"""
+With --beat the generator is BEAT-shaped (60 poses of 282 columns, 10 of them the prior: the beat joints are columns 18:42 and 150:174) and every
+call also returns the beat-alignment score of each track against its own audio (per recording, and per draw with --draws).
+usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--out tracks.npz]"""
 import os
 import sys
 import time
@@ -22,11 +24,13 @@ from emotiongestures_amd.builders import build_mirror
 from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
 from emotiongestures_amd.synth import load_synth_weights, synth_audio
 
-argv, DRAWS, OUT = [], 0, None
+argv, DRAWS, OUT, BEAT = [], 0, None, False
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--draws":
         DRAWS = int(next(it))
+    elif a == "--beat":
+        BEAT = True
     elif a == "--out":
         OUT = next(it)
     else:
@@ -35,6 +39,8 @@ U = int(argv[0]) if len(argv) > 0 else 4
 seconds = float(argv[1]) if len(argv) > 1 else 60.0
 dev = torch.device("cuda:0")
 FRAMES, POSE_DIM, PRIOR, FPS = 34, 126, 4, 15           # TED timing: 34 poses @ 15 fps, 4 of them the prior
+if BEAT:
+    FRAMES, POSE_DIM, PRIOR = 60, 282, 10               # BEAT: 60 poses of 282 columns, 10 of them the prior
 HOP = FRAMES - PRIOR
 hop_samples = int(round(HOP * 16000 / FPS))              # 30 poses = 2 s = 32 000 samples
 total = int(seconds * 16000)
@@ -51,7 +57,7 @@ z = torch.randn(U, W, 32)
 out = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, want_windows=True)          # warm-up (packs weights, allocates workspaces)
 torch.cuda.synchronize()
 t0 = time.perf_counter()
-out = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, want_windows=True)
+out = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, want_windows=True, beat=BEAT)
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 
@@ -62,14 +68,18 @@ seams = torch.tensor([w * HOP + j for w in range(1, W) for j in range(PRIOR + 1)
 print(f"mean |pose[t+1] - pose[t]|: {float(step.mean()):.4f} over the track, {float(step[:, seams].mean()):.4f} across the cross-faded seams")
 print(f"window 1 beyond its overlap (rows [{HOP + PRIOR}, {2 * HOP})) appears raw in the track: "
       f"{bool(torch.equal(track[:, HOP + PRIOR: FRAMES + HOP - PRIOR], windows[:, 1, PRIOR: HOP]))}")
-print(f"one call (mel + CVAE + roll-out, eager): {1e3 * dt:.2f} ms = {1e3 * dt / (U * track.shape[1] / FPS):.4f} ms per second of audio")
+print(f"one call (mel + CVAE + roll-out{' + beat score' if BEAT else ''}, eager): {1e3 * dt:.2f} ms = {1e3 * dt / (U * track.shape[1] / FPS):.4f} ms per second of audio")
+if BEAT:
+    print(f"--beat: beat-alignment score per recording: {[round(float(v), 4) for v in out['beat'].cpu()]}")
 
 # Recordings of unequal length in one call: recording u keeps (u + 1) / U of the audio.  Step s runs only the recordings that still have a
 # window s; the track is padded to the longest recording and zero past each recording's own end.
 if U > 1:
     lengths = [max(1, total * (u + 1) // U) for u in range(U)]
-    rag = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, lengths=lengths)
+    rag = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, lengths=lengths, beat=BEAT)
     torch.cuda.synchronize()
+    if BEAT:
+        print(f"--beat: recordings of unequal length, each scored on its own samples and poses: {[round(float(v), 4) for v in rag['beat'].cpu()]}")
     frames = rag["track_frames"].tolist()
     print(f"lengths {[round(v / 16000, 1) for v in lengths]} s -> windows {rag['windows_per']} -> track {tuple(rag['track'].shape)}, frames per recording {frames}; "
           f"rows past a recording's end are zero: {all(not bool(rag['track'][u, frames[u]:].any()) for u in range(U))}; "
@@ -84,9 +94,11 @@ if DRAWS > 0:
     H.synthesize((gen, vae), audio, text, seed_pose, labels=labels_r, z=zr, draws=DRAWS)                  # warm-up
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    div = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels_r, z=zr, draws=DRAWS)
+    div = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels_r, z=zr, draws=DRAWS, beat=BEAT)
     torch.cuda.synchronize()
     dt_r = time.perf_counter() - t0
+    if BEAT:
+        print(f"--beat: score per recording and draw [U, R] (the audio half runs once per recording):\n{div['beat'].cpu().numpy().round(4)}")
     tracks = div["track"]
     spread = (tracks - tracks.mean(dim=1, keepdim=True)).norm(dim=3).mean()
     print(f"--draws {DRAWS}: tracks {tuple(tracks.shape)} in one call, {1e3 * dt_r:.2f} ms = {1e3 * dt_r / (U * DRAWS * tracks.shape[2] / FPS):.4f} ms per "
