@@ -109,6 +109,11 @@ SIGNATURES = {
     "eg_beat_align_tracks": (C.c_int, [_P, _I, _L, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P, C.c_double, _I, _P, _P, _P, _P, _P, _L, _P, _P, _P,
                                        _P, _P, _P, _P]),
     "eg_beat_tracks_scan": (C.c_int, [_P, _P, _I, _P, _P, _L, _P, _P, _P]),
+    "eg_take_meta_ints": (_L, [_I]),
+    "eg_take_meta": (C.c_int, [_P, _I, _P]),
+    "eg_track_rows_pack": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "eg_take_distance_workspace_bytes": (_L, [_P, _I, _I]),
+    "eg_take_distance": (C.c_int, [_P, _I, _I, _I, _P, _P, _I, _P, _L, _P, _P, _P]),
     "eg_conv3x3": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "eg_conv3x3_se": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "eg_se_gate_pre": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

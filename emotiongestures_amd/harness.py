@@ -23,9 +23,11 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from .modules import Encoder, Linear, ReplicaAware, _eval_only, _seq, replica_forward
+from .takes import take_distance, take_diversity, track_features  # noqa: F401  (re-exported: the whole-track FGD features / take diversity)
 
 __all__ = ["MLP_Reconstruct", "SkeletonTransformer", "Prior_Encoder", "compute_acc", "l2_distance_pose", "mpjre", "calc_motion",
-           "calculate_frechet_distance", "calculate_diversity", "diversity_score", "evaluate"]
+           "calculate_frechet_distance", "calculate_diversity", "diversity_score", "evaluate", "track_features", "take_distance",
+           "take_diversity"]
 
 
 class _PackCache:
@@ -460,7 +462,7 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
                hop_samples: Optional[int] = None, n_samples: Optional[int] = None, windows: Optional[int] = None,
                z: Optional[torch.Tensor] = None, alpha: Optional[torch.Tensor] = None, fps: int = 15, sample_rate: int = 16000,
                want_windows: bool = False, want_aux: bool = False, mel=None, lengths=None, draws: Optional[int] = None,
-               beat: bool = False) -> Dict[str, torch.Tensor]:
+               beat: bool = False, diversity=None) -> Dict[str, torch.Tensor]:
     """One gesture track per utterance from raw 16 kHz audio: windows -> mel -> optional CVAE sample per window -> roll-out.
 
     ``models = (generator, vae | None)``, eval mode, on the GPU.  ``audio [U, total_samples]``; ``text [U, W, 60]`` (the words of every
@@ -483,7 +485,11 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
 
     ``beat=True`` (opt-in; BEAT-shaped generators, pose_dim >= 174): adds ``"beat"``, the beat-alignment score of every returned track
     against the audio it was made from (beat.beat_alignment_tracks: fp64 ``[U]``, or ``[U, R]`` with ``draws``), recording u scored on its
-    own ``lengths[u]`` samples and its own ``W_u * (frames - prior_frames) + prior_frames`` poses."""
+    own ``lengths[u]`` samples and its own ``W_u * (frames - prior_frames) + prior_frames`` poses.
+
+    ``diversity=fgd`` (an eval-mode ``MLP_Reconstruct``; with ``draws=R``, R >= 2): adds ``"take_distance"`` ``[U, R, R]`` and
+    ``"take_diversity"`` ``[U]`` (fp64), the pairwise distances of the returned takes of every recording in FGD feature space and their mean
+    (takes.take_diversity with ``span = frames``: the unit of the clip metric ``calculate_diversity`` on one generator window)."""
     from .engine import MelFrontEnd
     gen, vae = models
     _eval_only(gen)
@@ -497,6 +503,9 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
             raise L.EgError("synthesize: draws= needs a VAE (without sampled emotion maps every draw is the same track)")
         if int(draws) < 1:
             raise L.EgError(f"synthesize: draws={int(draws)} (need >= 1)")
+    if diversity is not None and (draws is None or int(draws) < 2):
+        raise L.EgError(f"synthesize: diversity= needs draws >= 2 (got draws={draws}): the take diversity is a distance between the takes of "
+                        "one recording")
     eng = gen.engine()
     c = eng.cfg
     if audio.dim() != 2:
@@ -536,6 +545,9 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
             out["spec"] = spec
             if beat:
                 _add_beat(out, audio, c, fps, None, [W] * U)
+            if diversity is not None:
+                td = take_diversity(diversity, out["track"], span=c.frames)
+                out["take_distance"], out["take_diversity"] = td["distance"], td["diversity"]
             return out
         sampled = None
         if vae is not None:

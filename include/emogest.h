@@ -474,6 +474,56 @@ int eg_beat_align_tracks(const float* audio, int32_t recordings, int64_t stride,
 int eg_beat_tracks_scan(const uint8_t* d_cand, const int32_t* lengths, int32_t recordings, const int32_t* d_meta, void* workspace,
                         int64_t workspace_bytes, int32_t* events, int32_t* counts, void* stream);
 
+/* Take diversity of whole tracks: the FGD features of a synthesize() roll-out and the pairwise distances of the R takes ("draws") of one
+ * recording (csrc/takes.hip) -- the whole-track counterpart of eg_beat_align_tracks for the FGD / Div_score half of the eval loop's summary
+ * line (test_emotion_gesture_diversity_iterative.py:250-261).  The FGD encoder itself (model/FGD.py:26-82) is three eg_linear products on
+ * the packed rows; these entries are everything around it.
+ *
+ * Inputs.  track [U, R, Tmax, D] fp32 on the device; frames[u] in 1 .. Tmax on the HOST, the real poses of recording u.  Rows at or beyond
+ * frames[u] are never read: they may hold anything, NaN included.
+ * Packed order: recording-major, then draw, then frame.  With off[u] the exclusive prefix sum of frames, row R*off[u] + r*frames[u] + t
+ * holds pose (u, r, t); the row count is N = R * sum(frames).
+ * Meta table (host only: no HIP call, usable without a GPU): eg_take_meta writes `frames | off`, 2U int32 (the count eg_take_meta_ints
+ * returns; 0 for U < 1 or U > 65535).  The caller uploads it once per frames vector and passes the device copy as d_meta beside the host
+ * vector; the kernels read d_meta, the host checks `frames`.  Refuses by name: null pointers, U outside 1 .. 65535, frames[u] < 1,
+ * sum(frames) >= 2^31.
+ *
+ * eg_track_rows_pack: rows [N, Dpad], Dpad = 4*ceil(D/4): the valid rows of `track` in packed order, the pad columns written as zeros --
+ * the K % 4 == 0 input eg_linear wants, without a concatenation per call.  One launch gridded over the chip; every output element has one
+ * owning thread; 16-byte stores, 16-byte loads where D % 4 == 0 and `track` is 16-byte aligned, scalar loads otherwise (D = 282 and 126).
+ * draws >= 1 here.  Refuses by name: null pointers, rows not 16-byte aligned, U outside 1 .. 65535, draws outside 1 .. EG_TAKE_MAX_DRAWS,
+ * Tmax < 1, D < 1, frames[u] outside 1 .. Tmax, N * Dpad >= 2^40.
+ *
+ * eg_take_distance on packed features feat [N, K] fp32 (K = 512 for the FGD encoder; any multiple of 4):
+ *   S[u, r, r']        = sum_{t < frames[u]} sum_{k < K} (feat[u,r,t,k] - feat[u,r',t,k])^2
+ *   distance[u, r, r'] = sqrt(S * scale_u),  scale_u = 1 when span <= 0 ("None": exactly the pair distance of model/FHD_score.py:270-286 on
+ *                        activations of frames[u] rows), scale_u = span / frames[u] otherwise: the same quantity brought to the scale of
+ *                        a span-frame clip, so takes of a 30 s and of a 60 s recording, and the clip metric at frames == span, read in one unit
+ *   diversity[u]       = 2 / (R (R - 1)) * sum_{r < r'} distance[u, r, r'], summed in lexicographic pair order
+ * Differences, squares and sums are fp64, each fp32 operand widened before the subtraction.  distance [U, R, R] fp64 is symmetric bit for
+ * bit with an exactly zero diagonal; diversity [U] fp64.
+ * Stage 1: the frames of every recording are cut into chunks of EG_TAKE_CHUNK_FRAMES frames (the result may depend on that constant and
+ * on nothing else: not on U, not on the recording's place in the batch, not on the order of the draws); grid over (chunk, base take r).
+ * A workgroup keeps take r's chunk in registers while looping r' > r (the re-reads of the other takes' chunks are served by L2), reduces
+ * lane -> wave -> workgroup in a fixed order and one thread per pair stores the partial to workspace[chunk, pair] -- no floating-point
+ * atomics.  Stage 2 (second launch): per (u, pair) the chunk partials summed in ascending chunk order, scale, sqrt, both triangles and the
+ * diagonal; per u the diversity.
+ * workspace >= eg_take_distance_workspace_bytes(frames, U, R), which is 0 for arguments the call would refuse.
+ * Refuses by name, before the first launch: null pointers, feat / workspace / distance / diversity not 16-byte aligned, U outside
+ * 1 .. 65535, draws outside 2 .. EG_TAKE_MAX_DRAWS, frames[u] < 1, K < 4 or not a multiple of 4, N * K >= 2^40, a short workspace.
+ * Both calls: one stream, no allocation, no host round trip, no synchronisation; launches, grids and pointers are fixed for a fixed
+ * (frames, draws), so they capture into a hipGraph. */
+#define EG_TAKE_CHUNK_FRAMES 16
+#define EG_TAKE_MAX_DRAWS 64
+int64_t eg_take_meta_ints(int32_t recordings);
+int eg_take_meta(const int32_t* frames, int32_t recordings, int32_t* meta);
+int eg_track_rows_pack(const float* track, int32_t recordings, int32_t draws, int32_t Tmax, int32_t pose_dim, const int32_t* frames,
+                       const int32_t* d_meta, float* rows, void* stream);
+int64_t eg_take_distance_workspace_bytes(const int32_t* frames, int32_t recordings, int32_t draws);
+int eg_take_distance(const float* feat, int32_t recordings, int32_t draws, int32_t feat_dim, const int32_t* frames, const int32_t* d_meta,
+                     int32_t span /* <= 0: none */, void* workspace, int64_t workspace_bytes, double* distance, double* diversity,
+                     void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Block-level operators (the reference's L2 blocks), used by the module-level mirrors and by the
  * per-kernel parity tests.  Weights here are passed as individual device pointers in the PACKED

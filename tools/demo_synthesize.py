@@ -10,7 +10,10 @@ statistics of the track and the time of one call.  With --draws R it then makes 
 in emotion (u + r) % 8; the audio tower runs once per window, not R times) and, with --out FILE.npz, writes them: tracks [U, R, T, pose_dim].
 With --beat the generator is BEAT-shaped (60 poses of 282 columns, 10 of them the prior: the beat joints are columns 18:42 and 150:174) and every
 call also returns the beat-alignment score of each track against its own audio (per recording, and per draw with --draws).
-usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--out tracks.npz]"""
+With --diversity (and --draws R, R >= 2) the draws call also returns the take diversity of every recording: the mean pairwise distance of its
+R takes in FGD feature space (takes.take_diversity, fp64 on the GPU, in the unit of one generator window), and the script shows the FGD of
+whole tracks from the same features (takes.track_features -> FrechetAccumulator).
+usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--out tracks.npz]"""
 import os
 import sys
 import time
@@ -24,17 +27,21 @@ from emotiongestures_amd.builders import build_mirror
 from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
 from emotiongestures_amd.synth import load_synth_weights, synth_audio
 
-argv, DRAWS, OUT, BEAT = [], 0, None, False
+argv, DRAWS, OUT, BEAT, DIVERSITY = [], 0, None, False, False
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--draws":
         DRAWS = int(next(it))
     elif a == "--beat":
         BEAT = True
+    elif a == "--diversity":
+        DIVERSITY = True
     elif a == "--out":
         OUT = next(it)
     else:
         argv.append(a)
+if DIVERSITY and DRAWS < 2:
+    sys.exit("--diversity needs --draws R with R >= 2 (the take diversity is a distance between the takes of one recording)")
 U = int(argv[0]) if len(argv) > 0 else 4
 seconds = float(argv[1]) if len(argv) > 1 else 60.0
 dev = torch.device("cuda:0")
@@ -91,15 +98,26 @@ if DRAWS > 0:
     labels_r = torch.nn.functional.one_hot((torch.arange(U)[:, None] + torch.arange(DRAWS)[None, :]) % 8, 8).float()
     labels_r = labels_r[:, :, None, :].expand(U, DRAWS, W, 8).to(dev)
     zr = torch.randn(U, DRAWS, W, 32)
-    H.synthesize((gen, vae), audio, text, seed_pose, labels=labels_r, z=zr, draws=DRAWS)                  # warm-up
+    fgd = load_synth_weights(H.MLP_Reconstruct(pose_dim=POSE_DIM), 7).eval().to(dev) if DIVERSITY else None
+    H.synthesize((gen, vae), audio, text, seed_pose, labels=labels_r, z=zr, draws=DRAWS, diversity=fgd)    # warm-up
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    div = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels_r, z=zr, draws=DRAWS, beat=BEAT)
+    div = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels_r, z=zr, draws=DRAWS, beat=BEAT, diversity=fgd)
     torch.cuda.synchronize()
     dt_r = time.perf_counter() - t0
     if BEAT:
         print(f"--beat: score per recording and draw [U, R] (the audio half runs once per recording):\n{div['beat'].cpu().numpy().round(4)}")
     tracks = div["track"]
+    if DIVERSITY:
+        print(f"--diversity: take diversity per recording (mean FGD-feature distance of its {DRAWS} takes, per {FRAMES}-frame window): "
+              f"{[round(float(v), 4) for v in div['take_diversity'].cpu()]}")
+        # FGD of whole tracks from the same features: draw 0 of every recording against draw 1, valid frames only, moments kept on the GPU
+        from emotiongestures_amd import takes
+        acc_a, acc_b = H.FrechetAccumulator(512, dev), H.FrechetAccumulator(512, dev)
+        acc_a.push(takes.track_features(fgd, tracks[:, 0].contiguous())[0])
+        acc_b.push(takes.track_features(fgd, tracks[:, 1].contiguous())[0])
+        fgd_ab = H.calculate_frechet_distance(*acc_a.stats(), *acc_b.stats())
+        print(f"--diversity: FGD of the draw-0 tracks against the draw-1 tracks ({U * tracks.shape[2]} feature rows each): {float(np.real(fgd_ab)):.4f}")
     spread = (tracks - tracks.mean(dim=1, keepdim=True)).norm(dim=3).mean()
     print(f"--draws {DRAWS}: tracks {tuple(tracks.shape)} in one call, {1e3 * dt_r:.2f} ms = {1e3 * dt_r / (U * DRAWS * tracks.shape[2] / FPS):.4f} ms per "
           f"second of track (one track per recording: {1e3 * dt / (U * track.shape[1] / FPS):.4f}); mean distance of a draw from its recording's mean "
