@@ -15,7 +15,7 @@ EG_PREC_F32, EG_PREC_BF16X3, EG_PREC_BF16 = 0, 1, 2
 PRECISIONS = {"f32": EG_PREC_F32, "fp32": EG_PREC_F32, "bf16x3": EG_PREC_BF16X3, "bf16": EG_PREC_BF16}
 
 (PACK_RAW, PACK_LINEAR, PACK_VEC_PAD, PACK_CONV3X3, PACK_BN_SCALE, PACK_BN_SHIFT, PACK_CONV1X1, PACK_STEM,
- PACK_WN_TAP, PACK_CONV1D, PACK_POS_TABLE, PACK_LINEAR_T, PACK_LINEAR_FOLD, PACK_BIAS_FOLD) = range(14)
+ PACK_WN_TAP, PACK_CONV1D, PACK_POS_TABLE, PACK_LINEAR_T, PACK_LINEAR_FOLD, PACK_BIAS_FOLD, PACK_CONV1X1_BF16) = range(15)
 
 
 class EgError(RuntimeError):
@@ -117,6 +117,7 @@ SIGNATURES = {
     "eg_conv3x3": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "eg_conv3x3_se": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "eg_se_gate_pre": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "eg_se_block_fused": (C.c_int, [_P] * 19 + [_I] * 7 + [_P]),
     "eg_conv3x3_gap_tiles": (_I, [_I, _I, _I, _I, _I]),
     "eg_conv3x3_channel_split": (_I, [_I, _I, _I, _I, _I, _I, _I]),
     "eg_stem_conv": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

@@ -78,6 +78,20 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// Sum over the 16 lanes of a DPP row (lanes with the same lane >> 4); every lane of the row gets the total.  Same values, bit for bit, as the chain
+// s += __shfl_xor(s, 1); ... 2; ... 4; ... 8 it replaces: the quad permutations ARE lane ^ 1 and lane ^ 2, and once the lanes of a quad (then of a
+// half row) hold one value, the half-row mirror (i -> 7 - i) and the row mirror (i -> 15 - i) deliver the same partner value as lane ^ 4 and lane ^ 8.
+// Four VALU moves instead of four trips through the LDS crossbar (ds_bpermute) per value.
+template <int CTRL> __device__ __forceinline__ float dpp_move(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float row16_sum(float s) {
+    s += dpp_move<0xB1>(s);         // quad_perm [1, 0, 3, 2]
+    s += dpp_move<0x4E>(s);         // quad_perm [2, 3, 0, 1]
+    s += dpp_move<0x141>(s);        // row_half_mirror
+    s += dpp_move<0x140>(s);        // row_mirror
+    return s;
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

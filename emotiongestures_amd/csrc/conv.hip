@@ -27,6 +27,7 @@ struct ConvArgs {
     float* y; float* gap;
     float* gap2 = nullptr;              // training forward: per-(clip, tile) channel sums of v*v beside `gap` (BatchNorm's variance without a pass over y)
     int H, W, Ho, Wo, cout, relu, nchw, tiles_x, tiles;
+    int batch = 0;                      // clips of the launch (the persistent walk's tile list is tiles * batch long)
     // fused SE tail (SEBasicBlock.forward, ResNetBlocks.py:28-36, identity shortcut): v = relu(v * gate[b, co] + res[pixel, co])
     // applied after the BatchNorm affine; gate comes from se_gate_pre_kernel (computed BEFORE this convolution runs)
     const float* gate = nullptr; const float* res = nullptr; int relu2 = 0;
@@ -38,6 +39,11 @@ struct ConvArgs {
                                         // se_tail_fwd_kernel writes): v += bit ? res : 0 -- the SE block's identity shortcut gradient dout * (out > 0), never stored
     const float* res_q = nullptr;       // DG2 only: a gradient on the dy grid ([B][H][W][cout]) added to the (even, even) phase -- the stride-2 1x1 shortcut's
     unsigned int* dbg = nullptr;        // diagnostic build only (EG_CONV32_STAMP=1): per-wave phase cycle sums of the persistent 32->32 kernel
+    // conv2 of a block WITH a downsample shortcut (conv3x3_bf16_kernel, SCC > 0): the 1x1 stride-sc_S convolution of the block input sc_x
+    // [B][sc_H][sc_W][SCC * 32] is contracted into the same accumulators before the 3x3 taps (weight images [ci/8][co][8], hi then lo) and the
+    // per-clip vectors of se_gate_pre_kernel fold gate, BN2 and the shortcut's BN into one rescale and one affine: sc_vec = [f | q | h], each [B][cout]
+    const float* sc_x = nullptr; const bf8* sc_whi = nullptr; const bf8* sc_wlo = nullptr; const float* sc_vec = nullptr;
+    int sc_H = 0, sc_W = 0, sc_S = 2, sc_B = 0;             // sc_B: the batch (the stride between f, q and h is sc_B * cout)
 };
 // a quad of the residual, behind its ReLU bit mask when there is one (e = element index of the quad's first float, a multiple of 4)
 __device__ __forceinline__ f4 residual_quad(const float* __restrict__ res, const unsigned* __restrict__ bits, size_t e) {
@@ -199,8 +205,7 @@ __global__ __launch_bounds__(256) void conv3x3_f32_kernel(ConvArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float s = gsum[n][r];
-                s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64);
-                s += __shfl_xor(s, 4, 64); s += __shfl_xor(s, 8, 64);
+                s = row16_sum(s);
                 if (li == 0) sred[wave * COUTP + n * 16 + kq * 4 + r] = s;
             }
         }
@@ -237,10 +242,25 @@ __global__ __launch_bounds__(256) void conv3x3_f32_kernel(ConvArgs a) {
 // (tap, 32-channel chunk) with the same weight ring; it accumulates into the phase the tap belongs to (4 x the accumulators, hence the smaller
 // tiles of the launch table).  The weight images are those of the rotated, transposed filter the stride-1 input gradients use (pack flip):
 // image tap t' is the filter's tap (2 - t'/3, 2 - t'%3), which reads dy at (i + (t'/3 == 2), j + (t'%3 == 2)).
-template <int CIN, int NTT, int S, int TH, int WM, int WN, int TERMS, int RING, bool SPLIT = false, bool DG2 = false>
+//
+// SCC > 0: conv2 of a block whose shortcut is a strided 1x1 convolution of the block input (SCC 32-channel chunks of it; the `_make_layer` entries,
+// ResNetSE34V2.py:43-47) with the WHOLE block tail in this launch: out = relu(gate * BN2(conv2(t1)) + BNd(conv1x1(x))) (ResNetBlocks.py:28-36).
+// Before the 3x3 loop the workgroup stages its tile's shortcut pixels x[sc_S * oy, sc_S * ox] at the halo-tile positions the centre tap reads, one
+// 32-channel chunk at a time, split to (hi, lo) like any halo, and runs one ordinary K step per chunk against the packed 1x1 images (the same
+// [ci/8][co][8] packing with a single tap, in the weight ring's free slots).  The accumulators D are then rescaled in place by
+// f[b][co] = sd[co] / q[b][co], q = gate[b][co] * s2[co], the 3x3 taps accumulate on top, and the epilogue relu(acc * q + h),
+// h = h2 * gate + hd, yields gate * (conv2 * s2 + h2) + (D * sd + hd).  f, q, h come from se_gate_pre_kernel, which keeps |q| >= 1e-30.
+//
+// PERSIST: a 1-D grid of resident workgroups walks the (clip, tile) list with the grid's stride, in the same XCD-aware order, as ONE flat sequence of
+// (tile, chunk) steps: the step counter, the weight ring and the halo register prefetch run across tile boundaries (a tile's last two steps issue the next
+// tile's first two weight copies, its last chunk fetches chunk 0 of the next tile's halo), and the epilogue of tile n is followed directly by the
+// store_tile of tile n + 1.  Per output element the K order is unchanged: outputs and pooling partials are bitwise those of the one-tile-per-workgroup launch.
+template <int CIN, int NTT, int S, int TH, int WM, int WN, int TERMS, int RING, bool SPLIT = false, bool DG2 = false, int SCC = 0, bool PERSIST = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const bf8* __restrict__ whi,
                                                            const bf8* __restrict__ wlo) {
+    static_assert(!PERSIST || (!SPLIT && !DG2 && SCC <= 1), "the persistent walk serves the unsplit forward kernels");
     static_assert(!DG2 || (S == 1 && !SPLIT), "DG2 tiles the dy grid with unit stride");
+    static_assert(SCC == 0 || (S == 1 && !DG2 && SCC <= 2 && CIN >= 64), "the shortcut pre-phase belongs to a stride-1 conv2 and uses ring slots 2 and 1");
     using G = typename std::conditional<DG2, ConvGeomDG2<TH>, ConvGeom<S, TH>>::type;
     constexpr int PH = DG2 ? 4 : 1;                 // output phases (accumulator sets)
     constexpr int COUTP = NTT * 16, IW = G::IW, NPIX = G::NPIX, PL = G::PL;
@@ -261,7 +281,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
     // (whole clips at B >= 8); halo rows / columns shared by neighbouring tiles then hit in that XCD's L2.
     int tile_id = blockIdx.x, b = blockIdx.y;
     const int c0 = SPLIT ? (int)blockIdx.z * COUTP : 0;        // first output channel of this workgroup
-    if (!SPLIT) {
+    // PERSIST: workgroup w (XCD-remapped: the grid is a multiple of 8) takes the logical tiles w, w + G, w + 2G, ... so that at any moment the G resident
+    // workgroups work on G consecutive tiles, each XCD on a contiguous run (the walk of conv3x3_c32_persistent_kernel)
+    const int NWG = PERSIST ? (int)gridDim.x : 1, total_tiles = PERSIST ? a.tiles * a.batch : 1;
+    int L = PERSIST ? (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3)) : 0;
+    if constexpr (PERSIST) {
+        if (L >= total_tiles) return;               // surplus workgroups of the rounded-up grid
+        b = L / a.tiles;
+        tile_id = L - b * a.tiles;
+    } else if (!SPLIT) {
         const int total = gridDim.x * gridDim.y;
         if ((total & 7) == 0) {
             const int lin = blockIdx.y * gridDim.x + blockIdx.x;
@@ -270,9 +298,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
             tile_id = log - b * (int)gridDim.x;
         }
     }
-    const int ty = tile_id / a.tiles_x, tx = tile_id - ty * a.tiles_x;
-    const int oy0 = ty * TH, ox0 = tx * 32;
-    const int iy0 = DG2 ? oy0 : oy0 * S - 1, ix0 = DG2 ? ox0 : ox0 * S - 1;
+    int oy0 = (tile_id / a.tiles_x) * TH, ox0 = (tile_id % a.tiles_x) * 32;
 
     int pbase[MT];
 #pragma unroll
@@ -287,7 +313,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
         for (int t = 0; t < MT; ++t)
 #pragma unroll
             for (int n = 0; n < NT; ++n) acc[ph][t][n] = (f4){0.f, 0.f, 0.f, 0.f};
-    const float* __restrict__ xb = a.x + (size_t)b * a.H * a.W * CIN;
+    const float* xb = a.x + (size_t)b * a.H * a.W * CIN;       // the clip whose halo load_tile fetches (PERSIST: runs one tile ahead at a tile's last chunk)
 
     // one step's weights = NIMG runs of WIMG slots; 64-slot (1 KiB) pieces are dealt round-robin to the 4 waves
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
@@ -297,29 +323,29 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
     constexpr int GTOT = NIMG * PIECES;
     constexpr bool COUNTED = (GTOT % 4 == 0);
     constexpr int GW = GTOT / 4;
-    auto issue_weights = [&](int step, int buf) {
-        const int chunk = step / 9, tap = step - chunk * 9;
+    // one K step's weights: octet rows row0 .. row0 + 3 of the images (hi, lo) -> ring slot buf
+    auto issue_rows = [&](const bf8* __restrict__ ihi, const bf8* __restrict__ ilo, int row0, int buf) {
         if constexpr (SPLIT) {
             // the slice's 4 octet rows of COUTP slots are not contiguous in the image (row length a.wrow): per-lane source addresses, the LDS side
             // stays one contiguous KiB per wave-instruction
             static_assert(COUNTED, "split instantiations deal whole pieces to the four waves");
-            const size_t rbase = ((size_t)tap * (CIN / 8) + chunk * 4) * a.wrow + c0;
+            const size_t rbase = (size_t)row0 * a.wrow + c0;
 #pragma unroll
             for (int p = 0; p < GW; ++p) {
                 const int flat = p * 4 + wave_u;
                 const int img = flat / PIECES, piece = flat - img * PIECES;
                 const int slot = piece * 64 + lane, oct = slot / COUTP, co = slot - oct * COUTP;
-                const bf8* src = (img ? wlo : whi) + rbase + (size_t)oct * a.wrow + co;
+                const bf8* src = (img ? ilo : ihi) + rbase + (size_t)oct * a.wrow + co;
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                                  (__attribute__((address_space(3))) void*)(wring + buf * WBUF + img * WIMG + piece * 64), 16, 0, 0);
             }
             return;
         }
-        const size_t gbase = ((size_t)tap * (CIN / 8) + chunk * 4) * COUTP;
+        const size_t gbase = (size_t)row0 * COUTP;
         if constexpr (PIECES % 4 == 0) {        // every wave copies PIECES / 4 pieces of each image (image known at compile time)
 #pragma unroll
             for (int img = 0; img < NIMG; ++img) {
-                const bf8* src = (img ? wlo : whi) + gbase;
+                const bf8* src = (img ? ilo : ihi) + gbase;
 #pragma unroll
                 for (int p = 0; p < PIECES / 4; ++p) {
                     const int piece = p * 4 + wave_u;
@@ -334,13 +360,17 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
                 const int flat = p * 4 + wave_u;
                 if (COUNTED || flat < GTOT) {
                     const int img = flat / PIECES, piece = flat - img * PIECES;
-                    const bf8* src = (img ? wlo : whi) + gbase;
+                    const bf8* src = (img ? ilo : ihi) + gbase;
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + piece * 64 + lane),
                                                      (__attribute__((address_space(3))) void*)(wring + buf * WBUF + img * WIMG + piece * 64),
                                                      16, 0, 0);
                 }
             }
         }
+    };
+    auto issue_weights = [&](int step, int buf) {
+        const int chunk = step / 9, tap = step - chunk * 9;
+        issue_rows(whi, wlo, tap * (CIN / 8) + chunk * 4, buf);
     };
     // halo tile staging, split in two so the HBM latency of chunk c+1 hides under the 9 taps of chunk c:
     //   load_tile: (IH x IW) pixels x 32 channels -> registers (one lane = one pixel x 8 channels per iteration)
@@ -350,16 +380,20 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
     // per-lane staging roles are chunk independent: compute the global element offset (32-bit; -1 = zero padding / unused)
     // and the LDS slot once, so the per-chunk loops carry no address arithmetic
     int goff[NIT], lslot[NIT];
+    auto set_goff = [&](int toy0, int tox0) {       // the halo of the tile whose first output pixel is (toy0, tox0)
+        const int iy0 = DG2 ? toy0 : toy0 * S - 1, ix0 = DG2 ? tox0 : tox0 * S - 1;
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int idx = tid + it * 256;
-        const int p = (idx >> 5) * 8 + (idx & 7), oc = (idx >> 3) & 3;
-        const int iy = p / IW, ix = p - iy * IW;
-        const int gy = iy0 + iy, gx = ix0 + ix;
-        const bool inside = p < NPIX && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-        goff[it] = inside ? (gy * a.W + gx) * CIN + oc * 8 : -1;
-        lslot[it] = p < NPIX ? oc * PL + p : -1;
-    }
+        for (int it = 0; it < NIT; ++it) {
+            const int idx = tid + it * 256;
+            const int p = (idx >> 5) * 8 + (idx & 7), oc = (idx >> 3) & 3;
+            const int iy = p / IW, ix = p - iy * IW;
+            const int gy = iy0 + iy, gx = ix0 + ix;
+            const bool inside = p < NPIX && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+            goff[it] = inside ? (gy * a.W + gx) * CIN + oc * 8 : -1;
+            lslot[it] = p < NPIX ? oc * PL + p : -1;
+        }
+    };
+    set_goff(oy0, ox0);
     auto load_tile = [&](int chunk) {
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
@@ -374,14 +408,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
     const int oc8s = ((tid >> 3) & 3) * 8;          // this thread's channel octet inside a 32-channel chunk (the same for all its iterations)
     auto store_tile = [&](int chunk) {
         f4 s0 = (f4){1.f, 1.f, 1.f, 1.f}, s1 = s0, h0 = (f4){0.f, 0.f, 0.f, 0.f}, h1 = h0;
-        if (a.in_scale) {
+        const bool in_aff = a.in_scale != nullptr;
+        if (in_aff) {
             s0 = *reinterpret_cast<const f4*>(a.in_scale + chunk * 32 + oc8s); s1 = *reinterpret_cast<const f4*>(a.in_scale + chunk * 32 + oc8s + 4);
             h0 = *reinterpret_cast<const f4*>(a.in_shift + chunk * 32 + oc8s); h1 = *reinterpret_cast<const f4*>(a.in_shift + chunk * 32 + oc8s + 4);
         }
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             if (lslot[it] >= 0) {
-                if (a.in_scale && goff[it] >= 0) {          // inside the image only: the zero padding of the normalised map stays zero
+                if (in_aff && goff[it] >= 0) {          // inside the image only: the zero padding of the normalised map stays zero
                     pv[it][0] = pv[it][0] * s0 + h0;
                     pv[it][1] = pv[it][1] * s1 + h1;
                 }
@@ -399,8 +434,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
     //            ... the MFMAs of step s  ->  vmcnt(0) + barrier (copies of s+1, s+2 landed; slot of s is free)
     // so neither the LDS fragment reads nor the global->LDS weight copies sit on the MFMA critical path.
     struct Frags { bf8 wh[NT], wl[NT], xh[MT], xl[MT]; };
-    auto read_w = [&](Frags& f, int tap) {
-        const bf8* Wh = wring + (tap % 3) * WBUF + kq * COUTP + wn * NT * 16 + li;      // step % 3 == tap % 3 (9 taps per chunk)
+    auto read_w = [&](Frags& f, int slot) {                                              // main steps: slot = step % 3 == tap % 3 (9 taps per chunk)
+        const bf8* Wh = wring + slot * WBUF + kq * COUTP + wn * NT * 16 + li;
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
             f.wh[n] = Wh[n * 16];
@@ -449,145 +484,242 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
             __syncthreads();
         }
     };
-    issue_weights(0, 0);
-    if (NSTEP > 1) issue_weights(1, 1);
-    load_tile(0);
     Frags fr[2];
+    for (bool first = true;; first = false) {       // one pass per tile (a single pass unless PERSIST)
+        const bool has_next = PERSIST && L + NWG < total_tiles;
+        int n_b = 0, n_tile = 0, n_oy0 = 0, n_ox0 = 0;
+        if (has_next) {
+            n_b = (L + NWG) / a.tiles;
+            n_tile = L + NWG - n_b * a.tiles;
+            n_oy0 = (n_tile / a.tiles_x) * TH;
+            n_ox0 = (n_tile % a.tiles_x) * 32;
+        }
+        if constexpr (SCC > 0) {
+            // shortcut pre-phase: chunk c's 1x1 weights wait in ring slot 2 - c (free since the previous tile's last barrier), step 0's 3x3 weights and the
+            // first halo chunk are in flight throughout (a later tile of a persistent walk: issued by the previous tile's last steps)
+#pragma unroll
+            for (int c = 0; c < SCC; ++c) issue_rows(a.sc_whi, a.sc_wlo, c * 4, 2 - c);
+            if (first) {
+                issue_weights(0, 0);
+                if (SCC == 1) issue_weights(1, 1);
+            }
+            // staging roles: output pixel p of the TH x 32 tile, channel octet oc (8 consecutive lanes = 8 consecutive pixels of one octet)
+            constexpr int SNIT = TH * 128 / 256;
+            static_assert(SNIT * 256 == TH * 128, "shortcut staging deals whole iterations");
+            int sgoff[SNIT], sslot[SNIT];
+#pragma unroll
+            for (int it = 0; it < SNIT; ++it) {
+                const int idx = tid + it * 256;
+                const int p = (idx >> 5) * 8 + (idx & 7), oc = (idx >> 3) & 3;
+                const int r = p >> 5, col = p & 31, oy = oy0 + r, ox = ox0 + col;
+                // oy < Ho = (sc_H - 1) / sc_S + 1  =>  sc_S * oy <= sc_H - 1: a valid output pixel's source pixel is inside the block input
+                sgoff[it] = (oy < a.Ho && ox < a.Wo) ? (oy * a.sc_S * a.sc_W + ox * a.sc_S) * (SCC * 32) + oc * 8 : -1;
+                sslot[it] = oc * PL + (r + 1) * IW + col + 1;
+            }
+            const float* __restrict__ sxb = a.sc_x + (size_t)b * a.sc_H * a.sc_W * (SCC * 32);
+            f4 sv[SNIT][2];
+            auto load_sc = [&](int c) {
+#pragma unroll
+                for (int it = 0; it < SNIT; ++it) {
+                    sv[it][0] = sv[it][1] = (f4){0.f, 0.f, 0.f, 0.f};
+                    if (sgoff[it] >= 0) {
+                        const float* src = sxb + sgoff[it] + c * 32;
+                        sv[it][0] = *reinterpret_cast<const f4*>(src);
+                        sv[it][1] = *reinterpret_cast<const f4*>(src + 4);
+                    }
+                }
+            };
+            load_sc(0);
+            if (first) load_tile(0);
+#pragma unroll
+            for (int c = 0; c < SCC; ++c) {
+#pragma unroll
+                for (int it = 0; it < SNIT; ++it) {
+                    bf8 hi, lo;
+                    split_octet<TERMS == 3>(sv[it][0], sv[it][1], hi, lo);
+                    tile[sslot[it]] = hi;
+                    if (TERMS == 3) tile[4 * PL + sslot[it]] = lo;
+                }
+                if (c + 1 < SCC) load_sc(c + 1);
+                __syncthreads();                    // shortcut pixels visible; every copy issued so far has landed
+                read_w(fr[0], 2 - c);
+                read_x(fr[0], 4);                   // the centre tap's positions
+                mfma_half(fr[0], 0, 4);
+                mfma_half(fr[0], 1, 4);
+                __syncthreads();                    // fragment reads done: the tile and the slot may be overwritten
+            }
+            if (SCC == 2) issue_weights(1, 1);
+            // D * f: the epilogue's per-clip scale q turns it back into D * sd (f = sd / q), whatever the gate
+            const float* __restrict__ fv = a.sc_vec + (size_t)b * a.cout;
+#pragma unroll
+            for (int n = 0; n < NT; ++n) {
+                const f4 fq = *reinterpret_cast<const f4*>(fv + c0 + (wn * NT + n) * 16 + kq * 4);
+#pragma unroll
+                for (int t = 0; t < MT; ++t) acc[0][t][n] = acc[0][t][n] * fq;
+            }
+        } else if (first) {
+            issue_weights(0, 0);
+            if (NSTEP > 1) issue_weights(1, 1);
+            load_tile(0);
+        }
 #pragma unroll 1
-    for (int chunk = 0; chunk < CIN / 32; ++chunk) {
-        store_tile(chunk);                      // the tile is free: its last reads completed before the barrier of the previous tap 8
-        if (COUNTED && chunk > 0) {              // W of this chunk's tap 0 landed at that barrier too; only W of tap 1 is in flight
-            wait_vmcnt_imm<GW>();
-            wait_lgkmcnt0();                    // tile writes visible
-            wg_barrier();
-        } else {
-            __syncthreads();                    // tile visible; every weight copy issued so far has landed
-        }
-        if (chunk + 1 < CIN / 32) load_tile(chunk + 1);
-        read_w(fr[0], 0);
-        read_x(fr[0], 0);
+        for (int chunk = 0; chunk < CIN / 32; ++chunk) {
+            store_tile(chunk);                      // the tile is free: its last reads completed before the barrier of the previous tap 8
+            if (COUNTED && chunk > 0) {              // W of this chunk's tap 0 landed at that barrier too; only W of tap 1 is in flight
+                wait_vmcnt_imm<GW>();
+                wait_lgkmcnt0();                    // tile writes visible
+                wg_barrier();
+            } else {
+                __syncthreads();                    // tile visible; every weight copy issued so far has landed
+            }
+            if (chunk + 1 < CIN / 32) {
+                load_tile(chunk + 1);
+            } else if (has_next) {                  // the last chunk's taps hide chunk 0 of the NEXT tile's halo
+                set_goff(n_oy0, n_ox0);
+                xb = a.x + (size_t)n_b * a.H * a.W * CIN;
+                load_tile(0);
+            }
+            read_w(fr[0], 0);
+            read_x(fr[0], 0);
 #pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const int step = chunk * 9 + tap;
-            if (step + 2 < NSTEP) issue_weights(step + 2, (tap + 2) % 3);
-            mfma_half(fr[tap & 1], 0, tap);
-            mid_sync(step + 2 < NSTEP);
-            if (tap < 8) { read_w(fr[(tap + 1) & 1], tap + 1); read_x(fr[(tap + 1) & 1], tap + 1); }
-            mfma_half(fr[tap & 1], 1, tap);
+            for (int tap = 0; tap < 9; ++tap) {
+                const int step = chunk * 9 + tap;
+                const bool more = step + 2 < NSTEP || has_next;     // the ring keeps streaming across a tile boundary: steps 0 and 1 of the next tile
+                if (more) issue_weights(step + 2 < NSTEP ? step + 2 : step + 2 - NSTEP, (tap + 2) % 3);
+                mfma_half(fr[tap & 1], 0, tap);
+                mid_sync(more);
+                if (tap < 8) { read_w(fr[(tap + 1) & 1], (tap + 1) % 3); read_x(fr[(tap + 1) & 1], tap + 1); }
+                mfma_half(fr[tap & 1], 1, tap);
+            }
         }
-    }
 
-    if constexpr (DG2) {
-        // four phases: dx[2 * by + py][2 * bx + px] for the base pixel (by, bx) of the dy grid; the (even, even) phase also takes the gradient that
-        // arrives on the dy grid (the stride-2 1x1 shortcut reads exactly those pixels of x)
-        const size_t ohw = (size_t)a.Ho * a.Wo;
-        float* __restrict__ yb = a.y + (size_t)b * ohw * a.cout;
-        const float* __restrict__ rq = a.res_q ? a.res_q + (size_t)b * a.H * a.W * a.cout : nullptr;
+        if constexpr (DG2) {
+            // four phases: dx[2 * by + py][2 * bx + px] for the base pixel (by, bx) of the dy grid; the (even, even) phase also takes the gradient that
+            // arrives on the dy grid (the stride-2 1x1 shortcut reads exactly those pixels of x)
+            const size_t ohw = (size_t)a.Ho * a.Wo;
+            float* __restrict__ yb = a.y + (size_t)b * ohw * a.cout;
+            const float* __restrict__ rq = a.res_q ? a.res_q + (size_t)b * a.H * a.W * a.cout : nullptr;
 #pragma unroll
-        for (int ph = 0; ph < 4; ++ph) {
-            const int py = ph >> 1, px = ph & 1;
+            for (int ph = 0; ph < 4; ++ph) {
+                const int py = ph >> 1, px = ph & 1;
 #pragma unroll
-            for (int t = 0; t < MT; ++t) {
-                const int id = wm * MT + t;
-                const int by = oy0 + (id >> 1), bx = ox0 + (id & 1) * 16 + li;
-                const int oy = 2 * by + py, ox = 2 * bx + px;
-                if (by < a.H && bx < a.W && oy < a.Ho && ox < a.Wo) {
+                for (int t = 0; t < MT; ++t) {
+                    const int id = wm * MT + t;
+                    const int by = oy0 + (id >> 1), bx = ox0 + (id & 1) * 16 + li;
+                    const int oy = 2 * by + py, ox = 2 * bx + px;
+                    if (by < a.H && bx < a.W && oy < a.Ho && ox < a.Wo) {
 #pragma unroll
-                    for (int n = 0; n < NT; ++n) {
-                        const int co = (wn * NT + n) * 16 + kq * 4;
-                        if (co < a.cout) {
-                            f4 v = acc[ph][t][n];
-                            if (ph == 0 && rq) v += *reinterpret_cast<const f4*>(rq + ((size_t)by * a.W + bx) * a.cout + co);
-                            *reinterpret_cast<f4*>(yb + ((size_t)oy * a.Wo + ox) * a.cout + co) = v;
+                        for (int n = 0; n < NT; ++n) {
+                            const int co = (wn * NT + n) * 16 + kq * 4;
+                            if (co < a.cout) {
+                                f4 v = acc[ph][t][n];
+                                if (ph == 0 && rq) v += *reinterpret_cast<const f4*>(rq + ((size_t)by * a.W + bx) * a.cout + co);
+                                *reinterpret_cast<f4*>(yb + ((size_t)oy * a.Wo + ox) * a.cout + co) = v;
+                            }
                         }
                     }
                 }
             }
+            return;
         }
-        return;
-    }
 
-    // epilogue: v = acc + bias; relu; v*scale + shift.  Pixel offsets are 32-bit and computed once per pixel tile; the
-    // per-image base is a scalar.  NHWC: one 16-byte store per (pixel tile, channel tile); NCHW (final_conv1 only): 4 stores.
-    f4 gsum[NT], gsq[NT];
-    int pixo[MT];
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-        const int id = wm * MT + t;
-        const int oy = oy0 + (id >> 1), ox = ox0 + (id & 1) * 16 + li;
-        pixo[t] = (oy < a.Ho && ox < a.Wo) ? oy * a.Wo + ox : -1;
-    }
-    const int hw = a.Ho * a.Wo;
-    float* __restrict__ yb = a.y + (size_t)b * hw * a.cout;
-#pragma unroll
-    for (int n = 0; n < NT; ++n) {
-        gsum[n] = (f4){0.f, 0.f, 0.f, 0.f};
-        gsq[n] = gsum[n];
-        const int co = c0 + (wn * NT + n) * 16 + kq * 4;
-        const f4 bi = a.bias ? *reinterpret_cast<const f4*>(a.bias + co) : (f4){0.f, 0.f, 0.f, 0.f};
-        const f4 sc = a.scale ? *reinterpret_cast<const f4*>(a.scale + co) : (f4){1.f, 1.f, 1.f, 1.f};
-        const f4 sh = a.shift ? *reinterpret_cast<const f4*>(a.shift + co) : (f4){0.f, 0.f, 0.f, 0.f};
-        const f4 gt = (a.gate && co < a.cout) ? *reinterpret_cast<const f4*>(a.gate + (size_t)b * a.cout + co) : (f4){1.f, 1.f, 1.f, 1.f};
-        const bool rb = a.res != nullptr;
-        const size_t rbase = (size_t)b * hw * a.cout;
+        // epilogue: v = acc + bias; relu; v*scale + shift.  Pixel offsets are 32-bit and computed once per pixel tile; the
+        // per-image base is a scalar.  NHWC: one 16-byte store per (pixel tile, channel tile); NCHW (final_conv1 only): 4 stores.
+        f4 gsum[NT], gsq[NT];
+        int pixo[MT];
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
-            f4 v = acc[0][t][n] + bi;
-            if (a.relu) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-            }
-            v = v * sc + sh;
-            if (a.gate) v = v * gt;
-            if (rb && pixo[t] >= 0 && co < a.cout) v += residual_quad(a.res, a.res_bits, rbase + (size_t)pixo[t] * a.cout + co);
-            if (a.relu2) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-            }
-            if (pixo[t] >= 0) {
-                if (!a.nchw) {
-                    if (co < a.cout) *reinterpret_cast<f4*>(yb + pixo[t] * a.cout + co) = v;
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (co + r < a.cout) yb[(co + r) * hw + pixo[t]] = v[r];
-                }
-                gsum[n] += v;
-                if (a.gap2) gsq[n] += v * v;
-            }
+            const int id = wm * MT + t;
+            const int oy = oy0 + (id >> 1), ox = ox0 + (id & 1) * 16 + li;
+            pixo[t] = (oy < a.Ho && ox < a.Wo) ? oy * a.Wo + ox : -1;
         }
-    }
-    if (a.gap) {            // no LDS reads follow the last step's barrier: the LDS is free for the reduction
-        float* sred = reinterpret_cast<float*>(lds);        // [WM][COUTP] sums, then [WM][COUTP] sums of squares
+        const int hw = a.Ho * a.Wo;
+        float* __restrict__ yb = a.y + (size_t)b * hw * a.cout;
+        int cbase = c0;
+        if constexpr (PERSIST) asm volatile("" : "+s"(cbase));      // opaque per tile: the channel vectors are re-read (L1 hits) each tile instead of being
+                                                                    // hoisted out of the tile loop into 48 registers the taps have no room for
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
+            gsum[n] = (f4){0.f, 0.f, 0.f, 0.f};
+            gsq[n] = gsum[n];
+            const int co = cbase + (wn * NT + n) * 16 + kq * 4;
+            const f4 bi = a.bias ? *reinterpret_cast<const f4*>(a.bias + co) : (f4){0.f, 0.f, 0.f, 0.f};
+            f4 sc = a.scale ? *reinterpret_cast<const f4*>(a.scale + co) : (f4){1.f, 1.f, 1.f, 1.f};
+            f4 sh = a.shift ? *reinterpret_cast<const f4*>(a.shift + co) : (f4){0.f, 0.f, 0.f, 0.f};
+            if constexpr (SCC > 0) {                // per-clip scale q and shift h (the launch passes no gate and no residual map, relu2 = 1)
+                const float* __restrict__ qv = a.sc_vec + ((size_t)a.sc_B + b) * a.cout + co;
+                sc = *reinterpret_cast<const f4*>(qv);
+                sh = *reinterpret_cast<const f4*>(qv + (size_t)a.sc_B * a.cout);
+            }
+            const f4 gt = (a.gate && co < a.cout) ? *reinterpret_cast<const f4*>(a.gate + (size_t)b * a.cout + co) : (f4){1.f, 1.f, 1.f, 1.f};
+            const bool rb = a.res != nullptr;
+            const size_t rbase = (size_t)b * hw * a.cout;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float s = gsum[n][r];
-                s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64);
-                s += __shfl_xor(s, 4, 64); s += __shfl_xor(s, 8, 64);
-                if (li == 0) sred[wm * COUTP + (wn * NT + n) * 16 + kq * 4 + r] = s;
-                if (a.gap2) {
-                    float q = gsq[n][r];
-                    q += __shfl_xor(q, 1, 64); q += __shfl_xor(q, 2, 64);
-                    q += __shfl_xor(q, 4, 64); q += __shfl_xor(q, 8, 64);
-                    if (li == 0) sred[(WM + wm) * COUTP + (wn * NT + n) * 16 + kq * 4 + r] = q;
+            for (int t = 0; t < MT; ++t) {
+                f4 v = acc[0][t][n] + bi;
+                if (a.relu) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+                }
+                v = v * sc + sh;
+                if (a.gate) v = v * gt;
+                if (rb && pixo[t] >= 0 && co < a.cout) v += residual_quad(a.res, a.res_bits, rbase + (size_t)pixo[t] * a.cout + co);
+                if (a.relu2) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+                }
+                if (pixo[t] >= 0) {
+                    if (!a.nchw) {
+                        if (co < a.cout) *reinterpret_cast<f4*>(yb + pixo[t] * a.cout + co) = v;
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (co + r < a.cout) yb[(co + r) * hw + pixo[t]] = v[r];
+                    }
+                    gsum[n] += v;
+                    if (a.gap2) gsq[n] += v * v;
                 }
             }
         }
-        __syncthreads();
-        if (tid < (SPLIT ? COUTP : a.cout)) {
-            float s = 0.f;
+        if (a.gap) {            // no LDS reads follow the last step's barrier: the LDS is free for the reduction (PERSIST: the next tile's weights are landing
+                                // in the ring and its halo is stored right after: the scratch has a region of its own behind the ring)
+            float* sred = reinterpret_cast<float*>(PERSIST ? lds + TILE + RING * WBUF : lds);        // [WM][COUTP] sums, then [WM][COUTP] sums of squares
 #pragma unroll
-            for (int m = 0; m < WM; ++m) s += sred[m * COUTP + tid];
-            a.gap[((size_t)b * a.tiles + tile_id) * a.cout + c0 + tid] = s;
-            if (a.gap2) {
-                float q = 0.f;
+            for (int n = 0; n < NT; ++n) {
 #pragma unroll
-                for (int m = 0; m < WM; ++m) q += sred[(WM + m) * COUTP + tid];
-                a.gap2[((size_t)b * a.tiles + tile_id) * a.cout + c0 + tid] = q;
+                for (int r = 0; r < 4; ++r) {
+                    float s = gsum[n][r];
+                    s = row16_sum(s);
+                    if (li == 0) sred[wm * COUTP + (wn * NT + n) * 16 + kq * 4 + r] = s;
+                    if (a.gap2) {
+                        float q = gsq[n][r];
+                        q = row16_sum(q);
+                        if (li == 0) sred[(WM + wm) * COUTP + (wn * NT + n) * 16 + kq * 4 + r] = q;
+                    }
+                }
+            }
+            // LDS traffic only: wait for the scratch writes, not (as __syncthreads would) for the tile's output stores to be acknowledged by memory
+            wait_lgkmcnt0();
+            wg_barrier();
+            if (tid < (SPLIT ? COUTP : a.cout)) {
+                float s = 0.f;
+#pragma unroll
+                for (int m = 0; m < WM; ++m) s += sred[m * COUTP + tid];
+                a.gap[((size_t)b * a.tiles + tile_id) * a.cout + c0 + tid] = s;
+                if (a.gap2) {
+                    float q = 0.f;
+#pragma unroll
+                    for (int m = 0; m < WM; ++m) q += sred[(WM + m) * COUTP + tid];
+                    a.gap2[((size_t)b * a.tiles + tile_id) * a.cout + c0 + tid] = q;
+                }
             }
         }
+        if (!has_next) break;
+        L += NWG; b = n_b; tile_id = n_tile; oy0 = n_oy0; ox0 = n_ox0;
+#pragma unroll
+        for (int t = 0; t < MT; ++t)
+#pragma unroll
+            for (int n = 0; n < NT; ++n) acc[0][t][n] = (f4){0.f, 0.f, 0.f, 0.f};
     }
 }
 
@@ -858,13 +990,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_persistent_kernel(ConvArgs
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float sm = gsum[n][r];
-                    sm += __shfl_xor(sm, 1, 64); sm += __shfl_xor(sm, 2, 64);
-                    sm += __shfl_xor(sm, 4, 64); sm += __shfl_xor(sm, 8, 64);
+                    sm = row16_sum(sm);
                     if (li == 0) sred[wave * sred_pitch + n * 16 + kq * 4 + r] = sm;
                     if (a.gap2) {               // 4-row tiles only (launch check): the squares' scratch follows the sums'
                         float q = gsq[n][r];
-                        q += __shfl_xor(q, 1, 64); q += __shfl_xor(q, 2, 64);
-                        q += __shfl_xor(q, 4, 64); q += __shfl_xor(q, 8, 64);
+                        q = row16_sum(q);
                         if (li == 0) sred[128 + wave * 32 + n * 16 + kq * 4 + r] = q;
                     }
                 }
@@ -970,7 +1100,8 @@ __global__ __launch_bounds__(GP_T) void se_gate_pre_kernel(const float* __restri
                                                            const float* __restrict__ w2img, const float* __restrict__ scale2,
                                                            const float* __restrict__ shift2, const float* __restrict__ w1, const float* __restrict__ b1,
                                                            const float* __restrict__ wf2, const float* __restrict__ bf2, float* __restrict__ gate,
-                                                           int H, int W, int C) {
+                                                           int H, int W, int C, const float* __restrict__ ds_scale, const float* __restrict__ ds_shift,
+                                                           float* __restrict__ sc_vec) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int b = blockIdx.x, t = threadIdx.x, G = GP_T / C, c = t % C, g = t / C, R = C >> 3;
     float* part = sm;                   // [5][GP_T]: total, first row, last row, first column, last column (per thread)
@@ -1051,7 +1182,21 @@ __global__ __launch_bounds__(GP_T) void se_gate_pre_kernel(const float* __restri
     if (t < C) {
         float s = bf2[t];
         for (int j = 0; j < R; ++j) s += wf2[t * R + j] * hbuf[j];
-        gate[(size_t)b * C + t] = 1.f / (1.f + expf(-s));
+        const float gt = 1.f / (1.f + expf(-s));
+        gate[(size_t)b * C + t] = gt;
+        if (sc_vec) {
+            // a block with a downsample shortcut (conv3x3_bf16_kernel, SCC): conv2 scales its shortcut product D by f = sd / q before the 3x3 taps and its
+            // epilogue computes relu(acc * q + h), q = gate * s2, h = h2 * gate + hd.  |q| is kept >= 1e-30 (sign kept; q = 0 counts as positive) so that
+            // f stays finite: D * sd / 1e-30 is inside fp32 for any |D * sd| < 1e8.  The SAME clamped q multiplies the accumulator again in the epilogue,
+            // so the shortcut comes back as D * sd exactly (to rounding), and what the clamp distorts is the conv2 term alone, by less than
+            // 1e-30 * |conv2|: the output error stays at rounding level, also for bn2.weight == 0 or a gate that underflows.
+            const size_t BC = (size_t)gridDim.x * C;
+            float q = gt * scale2[t];
+            if (!(fabsf(q) >= 1e-30f)) q = copysignf(1e-30f, q);
+            sc_vec[(size_t)b * C + t] = ds_scale[t] / q;
+            sc_vec[BC + (size_t)b * C + t] = q;
+            sc_vec[2 * BC + (size_t)b * C + t] = shift2[t] * gt + ds_shift[t];
+        }
     }
 }
 
@@ -1105,28 +1250,29 @@ __global__ __launch_bounds__(256) void se_tail_downsample_kernel(const float* __
     }
 }
 
-template <int CIN, int NT, int S, int TH, int WM, int WN, int TERMS>
+template <int CIN, int NT, int S, int TH, int WM, int WN, int TERMS, int SCC = 0, bool PERSIST = false>
 int launch_conv_bf16(const ConvArgs& a, const bf8* whi, const bf8* wlo, dim3 grid, hipStream_t st) {
     // weight-ring depth: 3 where the K loop is long (C >= 64, stride 1); 2 for the HBM-bound C=32 layer and the
     // stride-2 entries (smaller LDS footprint => one more workgroup per CU)
     constexpr int RING = 3;
     using G = ConvGeom<S, TH>;
     constexpr int NIMG = (TERMS == 3) ? 2 : 1;
-    constexpr size_t LDS_BYTES = sizeof(bf8) * (size_t)(NIMG * 4 * G::PL + RING * NIMG * 4 * NT * 16);
-    auto kern = conv3x3_bf16_kernel<CIN, NT, S, TH, WM, WN, TERMS, RING>;
+    constexpr size_t LDS_BYTES = sizeof(bf8) * (size_t)(NIMG * 4 * G::PL + RING * NIMG * 4 * NT * 16) +
+                                 (PERSIST ? sizeof(float) * 2 * WM * NT * 16 : 0);         // + the pooling scratch of the persistent walk (sums, squares)
+    auto kern = conv3x3_bf16_kernel<CIN, NT, S, TH, WM, WN, TERMS, RING, false, false, SCC, PERSIST>;
     if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS_BYTES, "conv3x3")) return rc;
     hipLaunchKernelGGL(kern, grid, dim3(256), LDS_BYTES, st, a, whi, wlo);
     return eg_check_launch("conv3x3");
 }
 
 // Channel-split launch of a stride-1 body convolution: NTS * 16 output channels per workgroup, grid.z = cout / (NTS * 16) (conv3x3_bf16_kernel, SPLIT).
-template <int CIN, int NTS, int TH, int WM, int WN, int TERMS>
+template <int CIN, int NTS, int TH, int WM, int WN, int TERMS, int SCC = 0>
 int launch_conv_split_t(ConvArgs a, int batch, const bf8* whi, const bf8* wlo, hipStream_t st) {
     constexpr int RING = 3;
     using G = ConvGeom<1, TH>;
     constexpr int NIMG = (TERMS == 3) ? 2 : 1;
     constexpr size_t LDS_BYTES = sizeof(bf8) * (size_t)(NIMG * 4 * G::PL + RING * NIMG * 4 * NTS * 16);
-    auto kern = conv3x3_bf16_kernel<CIN, NTS, 1, TH, WM, WN, TERMS, RING, true>;
+    auto kern = conv3x3_bf16_kernel<CIN, NTS, 1, TH, WM, WN, TERMS, RING, true, false, SCC>;
     if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS_BYTES, "conv3x3 (channel split)")) return rc;
     a.wrow = a.cout;
     hipLaunchKernelGGL(kern, dim3(a.tiles, batch, a.cout / (NTS * 16)), dim3(256), LDS_BYTES, st, a, whi, wlo);
@@ -1163,10 +1309,40 @@ int body_channel_split(int batch, int tiles, int cin, int cout, int stride, int 
     return conv_channel_split(tiles * batch, cin == 128 ? 4 : 2);
 }
 
-template <int CIN, int NT, int S, int TH, int WM, int WN>
+// Grid of the persistent (tile, chunk) walk for a launch of `total` tiles, 0 = one workgroup per tile.  kind: 1 = the 64 -> 64 body, 2 = the 32 -> 64 entry,
+// 4 = the 64 -> 128 entry, 8 = final_conv1.  Default rule: min(total, 2 workgroups per CU) for the kinds in CONV_PERSIST_DEFAULT_KINDS, and only when
+// there are more tiles than resident workgroups.  Same-box A/B runs at 64 clips kept NONE of the four (the walk's per-tile
+// drain of the output stores and its register pressure cost more than the cold prologue it removes), so the mask is empty and every launch is one
+// workgroup per tile unless asked otherwise.  EG_CONV_GRID (read per call, as EG_GEMM_TILE; a captured graph keeps what it was captured
+// with) overrides: 0 = never, N = N workgroups (rounded up to the multiple of 8 the XCD remap needs) for every kind, whatever the tile count;
+// EG_CONV_PERSIST_KINDS = the bit mask of kinds the default rule serves (A/B).
+constexpr int CONV_PERSIST_DEFAULT_KINDS = 0;
+int conv_persist_grid(int kind, int total) {
+    const int resident = 512;                           // 2 workgroups per CU (as launch_conv32_persistent_t)
+    const char* e = getenv("EG_CONV_GRID");
+    if (e && e[0]) {
+        const int g = atoi(e);
+        if (g <= 0) return 0;
+        const int64_t cap = eg_round_up(total, 8), want = eg_round_up(g, 8);
+        return (int)(total > 0 && cap < want ? cap : want);
+    }
+    if (total <= 0) return 0;                           // (conv_persist_forced: only the override counts)
+    const char* k = getenv("EG_CONV_PERSIST_KINDS");
+    const int kinds = (k && k[0]) ? atoi(k) : CONV_PERSIST_DEFAULT_KINDS;
+    return ((kinds & kind) && total > resident) ? resident : 0;
+}
+
+// EG_CONV_GRID names a workgroup count: the launch is wanted on the persistent walk whatever its size, so the small-batch channel split stands back
+bool conv_persist_forced() { return conv_persist_grid(0, 0) > 0; }
+
+template <int CIN, int NT, int S, int TH, int WM, int WN, int SCC = 0, int KIND = 0>
 int launch_conv(const ConvArgs& a, int batch, int precision, hipStream_t st) {
     dim3 grid(a.tiles, batch), block(256);
     if (precision == EG_PREC_F32) {
+        if constexpr (SCC > 0) {
+            eg_set_error("conv3x3: the fused downsample shortcut exists in the split-bf16 modes only");
+            return EG_ERR_UNSUPPORTED;
+        }
         hipLaunchKernelGGL((conv3x3_f32_kernel<CIN, NT, S, TH>), grid, block, 0, st, a);
         return eg_check_launch("conv3x3");
     }
@@ -1174,8 +1350,16 @@ int launch_conv(const ConvArgs& a, int batch, int precision, hipStream_t st) {
     const size_t f32_floats = (size_t)9 * CIN * NT * 16;
     const bf8* whi = reinterpret_cast<const bf8*>(a.w + f32_floats);
     const bf8* wlo = whi + (size_t)9 * (CIN / 8) * NT * 16;
-    if (precision == EG_PREC_BF16X3) return launch_conv_bf16<CIN, NT, S, TH, WM, WN, 3>(a, whi, wlo, grid, st);
-    return launch_conv_bf16<CIN, NT, S, TH, WM, WN, 1>(a, whi, wlo, grid, st);
+    if constexpr (KIND != 0) {
+        // inference launches only: the training forms (squares, input affine, masked residual, plain fan-in add) keep one workgroup per tile
+        const bool infer = !a.gap2 && !a.in_scale && !a.res_bits && !(a.res && !a.gate);
+        if (const int g = infer ? conv_persist_grid(KIND, a.tiles * batch) : 0) {
+            if (precision == EG_PREC_BF16X3) return launch_conv_bf16<CIN, NT, S, TH, WM, WN, 3, SCC, true>(a, whi, wlo, dim3(g), st);
+            return launch_conv_bf16<CIN, NT, S, TH, WM, WN, 1, SCC, true>(a, whi, wlo, dim3(g), st);
+        }
+    }
+    if (precision == EG_PREC_BF16X3) return launch_conv_bf16<CIN, NT, S, TH, WM, WN, 3, SCC>(a, whi, wlo, grid, st);
+    return launch_conv_bf16<CIN, NT, S, TH, WM, WN, 1, SCC>(a, whi, wlo, grid, st);
 }
 
 bool conv32_persistent_enabled() {
@@ -1279,10 +1463,13 @@ extern "C" int eg_conv3x3(const float* x, const float* w, const float* bias, con
 }
 
 namespace {
+// the downsample shortcut conv2 of a stage-entry block contracts itself (conv3x3_bf16_kernel, SCC): block input x [B][h][w][cin], the packed 1x1 images
+// (EG_PACK_CONV1X1_BF16) and the per-clip vectors [f | q | h] of se_gate_pre_kernel
+struct ShortcutArgs { const float* x; const float* wimg; const float* vec; int h, w, cin, stride; };
 int conv3x3_dispatch(const float* x, const float* w, const float* bias, const float* scale, const float* shift, const float* gate, const float* residual,
                      float* y, float* gap_partial, float* gap_sq, int32_t batch, int32_t h, int32_t wdt, int32_t cin, int32_t cout, int32_t stride,
                      int32_t relu, int32_t nchw_out, int32_t precision, void* stream, const float* in_scale = nullptr, const float* in_shift = nullptr,
-                     const uint32_t* res_bits = nullptr);
+                     const uint32_t* res_bits = nullptr, const ShortcutArgs* sc = nullptr);
 }
 extern "C" int eg_conv3x3_se(const float* x, const float* w, const float* bias, const float* scale, const float* shift, const float* gate,
                              const float* residual, float* y, float* gap_partial, int32_t batch, int32_t h, int32_t wdt, int32_t cin,
@@ -1322,7 +1509,8 @@ extern "C" int eg_conv3x3_sq_in_affine(const float* x, const float* in_scale, co
 namespace {
 int conv3x3_dispatch(const float* x, const float* w, const float* bias, const float* scale, const float* shift, const float* gate, const float* residual,
                      float* y, float* gap_partial, float* gap_sq, int32_t batch, int32_t h, int32_t wdt, int32_t cin, int32_t cout, int32_t stride,
-                     int32_t relu, int32_t nchw_out, int32_t precision, void* stream, const float* in_scale, const float* in_shift, const uint32_t* res_bits) {
+                     int32_t relu, int32_t nchw_out, int32_t precision, void* stream, const float* in_scale, const float* in_shift, const uint32_t* res_bits,
+                     const ShortcutArgs* sc) {
     EG_REQUIRE(x && w && y && batch > 0 && h > 0 && wdt > 0, EG_ERR_BAD_ARG, "eg_conv3x3: null pointer or empty shape");
     EG_REQUIRE(!res_bits || (residual && !gate && ((size_t)batch * h * wdt * cout) % 32 == 0), EG_ERR_BAD_ARG,
                "eg_conv3x3_res_masked: the bit mask needs a residual, no gate and a map of a multiple of 32 elements");
@@ -1343,7 +1531,7 @@ int conv3x3_dispatch(const float* x, const float* w, const float* bias, const fl
     a.res_bits = res_bits;
     a.in_scale = in_scale; a.in_shift = in_shift;
     a.H = h; a.W = wdt; a.Ho = (h + 2 - 3) / stride + 1; a.Wo = (wdt + 2 - 3) / stride + 1;
-    a.cout = cout; a.relu = relu; a.nchw = nchw_out;
+    a.cout = cout; a.relu = relu; a.nchw = nchw_out; a.batch = batch;
     const int th = conv_tile_rows(cin, cout, stride);
     a.tiles_x = eg_cdiv(a.Wo, 32);
     a.tiles = a.tiles_x * eg_cdiv(a.Ho, th);
@@ -1351,12 +1539,33 @@ int conv3x3_dispatch(const float* x, const float* w, const float* bias, const fl
     const int coutp = (int)eg_round_up(cout, 16);
     EgProfScope prof((int64_t)cin * 1000000 + (int64_t)cout * 1000 + stride * 100 + 1,
                      2.0 * 9 * cin * cout * (double)a.Ho * a.Wo * batch, st);
+    if (sc) {
+        EG_REQUIRE(precision != EG_PREC_F32 && stride == 1 && !nchw_out && cout == cin && (cin == 64 || cin == 128) && sc->cin * 2 == cin, EG_ERR_UNSUPPORTED,
+                   "conv3x3: the fused downsample shortcut serves 32 -> 64 and 64 -> 128 block entries in the split-bf16 modes (cin=%d cout=%d shortcut cin=%d)",
+                   cin, cout, sc->cin);
+        EG_REQUIRE(sc->x && sc->wimg && sc->vec && !gate && !residual && !bias && !relu && !gap_sq && !in_scale && sc->stride >= 1 &&
+                   (sc->h - 1) / sc->stride + 1 == h && (sc->w - 1) / sc->stride + 1 == wdt && eg_aligned16(sc->x) && eg_aligned16(sc->wimg) &&
+                   eg_aligned16(sc->vec), EG_ERR_BAD_ARG, "conv3x3: fused downsample shortcut: null / misaligned operand or a block input that does not map onto the output");
+        a.sc_x = sc->x; a.sc_vec = sc->vec; a.sc_H = sc->h; a.sc_W = sc->w; a.sc_S = sc->stride; a.sc_B = batch;
+        a.sc_whi = reinterpret_cast<const bf8*>(sc->wimg);
+        a.sc_wlo = a.sc_whi + (size_t)(sc->cin / 8) * cout;
+        a.scale = a.shift = nullptr;             // the epilogue's scale and shift are the per-clip q and h
+        a.relu2 = 1;
+        const int split = (cin == 64 && conv_persist_forced()) ? 1 : body_channel_split(batch, a.tiles, cin, cout, 1, precision, 0);
+        const bf8* whi = reinterpret_cast<const bf8*>(a.w + (size_t)9 * cin * cout);
+        const bf8* wlo = whi + (size_t)9 * (cin / 8) * cout;
+        if (cin == 64 && split == 2) return launch_conv_split_t<64, 2, 8, 4, 1, 3, 1>(a, batch, whi, wlo, st);
+        if (cin == 64) return launch_conv<64, 4, 1, 8, 4, 1, 1, 1>(a, batch, precision, st);
+        if (split == 2) return launch_conv_split_t<128, 4, 4, 2, 2, 3, 2>(a, batch, whi, wlo, st);
+        if (split == 4) return launch_conv_split_t<128, 2, 4, 2, 2, 3, 2>(a, batch, whi, wlo, st);
+        return launch_conv<128, 8, 1, 4, 2, 2, 2>(a, batch, precision, st);
+    }
     if (cin == 32 && coutp == 32 && cout == 32 && stride == 1 && precision != EG_PREC_F32 && !nchw_out && conv32_persistent_enabled())
         return launch_conv32_persistent(a, batch, precision, th, st);
     if (cin == 32 && coutp == 32 && stride == 1 && th == 4) return launch_conv<32, 2, 1, 4, 4, 1>(a, batch, precision, st);
     if (cin == 32 && coutp == 32 && stride == 1) return launch_conv<32, 2, 1, 8, 4, 1>(a, batch, precision, st);
-    if (cin == 32 && coutp == 64 && stride == 2) return launch_conv<32, 4, 2, 2, 2, 2>(a, batch, precision, st);
-    if (const int split = body_channel_split(batch, a.tiles, cin, cout, stride, precision, nchw_out); split > 1) {
+    if (cin == 32 && coutp == 64 && stride == 2) return launch_conv<32, 4, 2, 2, 2, 2, 0, 2>(a, batch, precision, st);
+    if (const int split = (cin == 64 && conv_persist_forced()) ? 1 : body_channel_split(batch, a.tiles, cin, cout, stride, precision, nchw_out); split > 1) {
         // few pixel tiles (small batches): spread the output channels over workgroups as well -- bitwise the unsplit kernels below
         const size_t f32_floats = (size_t)9 * cin * cout;
         const bf8* whi = reinterpret_cast<const bf8*>(a.w + f32_floats);
@@ -1365,16 +1574,16 @@ int conv3x3_dispatch(const float* x, const float* w, const float* bias, const fl
         if (cin == 128 && split == 2) return launch_conv_split_t<128, 4, 4, 2, 2, 3>(a, batch, whi, wlo, st);
         if (cin == 128 && split == 4) return launch_conv_split_t<128, 2, 4, 2, 2, 3>(a, batch, whi, wlo, st);
     }
-    if (cin == 64 && coutp == 64 && stride == 1) return launch_conv<64, 4, 1, 8, 4, 1>(a, batch, precision, st);
-    if (cin == 64 && coutp == 128 && stride == 2) return launch_conv<64, 8, 2, 2, 2, 2>(a, batch, precision, st);
+    if (cin == 64 && coutp == 64 && stride == 1) return launch_conv<64, 4, 1, 8, 4, 1, 0, 1>(a, batch, precision, st);
+    if (cin == 64 && coutp == 128 && stride == 2) return launch_conv<64, 8, 2, 2, 2, 2, 0, 4>(a, batch, precision, st);
     if (cin == 64 && coutp == 128 && stride == 1) return launch_conv<64, 8, 1, 4, 2, 2>(a, batch, precision, st);      // training: input gradient of final_conv1 (dy padded to 64 channels)
     if (cin == 128 && coutp == 128 && stride == 1) return launch_conv<128, 8, 1, 4, 2, 2>(a, batch, precision, st);
     // 256-channel stage of the audio emotion classifier (model/audio_emotion_classifer.py:20-22): 2-row tiles, waves split the channels
     if (cin == 128 && coutp == 256 && stride == 2) return launch_conv<128, 16, 2, 2, 1, 4>(a, batch, precision, st);
     if (cin == 256 && coutp == 256 && stride == 1) return launch_conv<256, 16, 1, 2, 1, 4>(a, batch, precision, st);
     if (cin == 128 && coutp <= 64 && stride == 1) {       // final_conv1: 128 -> frames (34 -> 48, 60 -> 64)
-        if (coutp <= 48) return launch_conv<128, 3, 1, 4, 4, 1>(a, batch, precision, st);
-        return launch_conv<128, 4, 1, 4, 4, 1>(a, batch, precision, st);
+        if (coutp <= 48) return launch_conv<128, 3, 1, 4, 4, 1, 0, 8>(a, batch, precision, st);
+        return launch_conv<128, 4, 1, 4, 4, 1, 0, 8>(a, batch, precision, st);
     }
     // final_conv1 with 65..128 frames (BEAT-long, 120): the 128-wide body kernel on weights zero-padded to 128 channels
     if (cin == 128 && coutp <= 128 && stride == 1) return launch_conv<128, 8, 1, 4, 2, 2>(a, batch, precision, st);
@@ -1430,16 +1639,50 @@ extern "C" int eg_se_gate(const float* gap_partial, int32_t tiles, const float* 
     return eg_check_launch("se_gate");
 }
 
-extern "C" int eg_se_gate_pre(const float* t1, const float* gap_partial, int32_t tiles, const float* conv2_w, const float* scale2,
-                              const float* shift2, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
-                              int32_t batch, int32_t h, int32_t wdt, int32_t c, void* stream) {
+namespace {
+int se_gate_pre_launch(const float* t1, const float* gap_partial, int32_t tiles, const float* conv2_w, const float* scale2,
+                       const float* shift2, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
+                       int32_t batch, int32_t h, int32_t wdt, int32_t c, void* stream, const float* ds_scale, const float* ds_shift, float* sc_vec) {
     EG_REQUIRE(t1 && gap_partial && conv2_w && scale2 && shift2 && w1 && b1 && w2 && b2 && gate && batch > 0 && h > 1 && wdt > 1, EG_ERR_BAD_ARG,
                "eg_se_gate_pre: null pointer or empty shape");
     EG_REQUIRE(c % 8 == 0 && c <= 256 && 256 % c == 0 && eg_aligned16(conv2_w), EG_ERR_UNSUPPORTED, "eg_se_gate_pre: C=%d", c);
     const size_t smem = sizeof(float) * (5 * GP_T + 9 * (size_t)c + GP_T + c + (c >> 3) + 4);
+    EG_REQUIRE(!sc_vec || (ds_scale && ds_shift), EG_ERR_BAD_ARG, "eg_se_gate_pre: the shortcut vectors need the downsample BatchNorm");
     hipLaunchKernelGGL(se_gate_pre_kernel, dim3(batch), dim3(GP_T), smem, (hipStream_t)stream, t1, gap_partial, tiles, conv2_w, scale2, shift2, w1,
-                       b1, w2, b2, gate, h, wdt, c);
+                       b1, w2, b2, gate, h, wdt, c, ds_scale, ds_shift, sc_vec);
     return eg_check_launch("se_gate_pre");
+}
+}  // namespace
+
+extern "C" int eg_se_gate_pre(const float* t1, const float* gap_partial, int32_t tiles, const float* conv2_w, const float* scale2,
+                              const float* shift2, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
+                              int32_t batch, int32_t h, int32_t wdt, int32_t c, void* stream) {
+    return se_gate_pre_launch(t1, gap_partial, tiles, conv2_w, scale2, shift2, w1, b1, w2, b2, gate, batch, h, wdt, c, stream, nullptr, nullptr, nullptr);
+}
+
+// One SEBasicBlock (ResNetBlocks.py:21-37) in the audio tower's fused data flow, identity and stage-entry blocks alike (run_audio_tower calls this):
+//   conv1 (stride s) -> ReLU -> BN1, with per-tile channel sums        t1, gap
+//   gate from the moments of t1 (se_gate_pre_kernel)                    gate (+ the shortcut vectors f, q, h of a block with a downsample)
+//   conv2 with the tail in its epilogue                                 out = relu(gate * BN2(conv2(t1)) + shortcut)
+// ds_w == NULL: identity shortcut (cin == cout, stride 1), any precision.  ds_w != NULL: the 1x1 stride-s downsample's EG_PACK_CONV1X1_BF16 images, contracted
+// inside conv2 (split-bf16 modes; 32 -> 64 and 64 -> 128).  Neither y nor the shortcut map exists; three launches.
+extern "C" int eg_se_block_fused(const float* x, const float* conv1_w, const float* scale1, const float* shift1, const float* conv2_w, const float* scale2,
+                                 const float* shift2, const float* se_w1, const float* se_b1, const float* se_w2, const float* se_b2, const float* ds_w,
+                                 const float* ds_scale, const float* ds_shift, float* t1, float* out, float* gap_partial, float* gate, float* sc_vec,
+                                 int32_t batch, int32_t h, int32_t wdt, int32_t cin, int32_t cout, int32_t stride, int32_t precision, void* stream) {
+    EG_REQUIRE(x && conv1_w && scale1 && shift1 && conv2_w && scale2 && shift2 && t1 && out && gap_partial && gate, EG_ERR_BAD_ARG, "eg_se_block_fused: null pointer");
+    EG_REQUIRE(ds_w ? (ds_scale && ds_shift && sc_vec) : (cin == cout && stride == 1), EG_ERR_BAD_ARG,
+               "eg_se_block_fused: a downsample needs its BatchNorm and the shortcut vectors; an identity shortcut needs cin == cout and stride 1");
+    EG_REQUIRE(stride == 1 || stride == 2, EG_ERR_UNSUPPORTED, "eg_se_block_fused: stride %d", stride);
+    const int ho = (h + 2 - 3) / stride + 1, wo = (wdt + 2 - 3) / stride + 1;
+    if (int rc = eg_conv3x3(x, conv1_w, nullptr, scale1, shift1, t1, gap_partial, batch, h, wdt, cin, cout, stride, 1, 0, precision, stream)) return rc;
+    const int tiles1 = eg_conv3x3_gap_tiles(h, wdt, cin, cout, stride);
+    if (int rc = se_gate_pre_launch(t1, gap_partial, tiles1, conv2_w, scale2, shift2, se_w1, se_b1, se_w2, se_b2, gate, batch, ho, wo, cout, stream,
+                                    ds_w ? ds_scale : nullptr, ds_w ? ds_shift : nullptr, ds_w ? sc_vec : nullptr)) return rc;
+    if (!ds_w) return eg_conv3x3_se(t1, conv2_w, nullptr, scale2, shift2, gate, x, out, nullptr, batch, ho, wo, cout, cout, 1, 0, 0, precision, stream);
+    const ShortcutArgs sc{x, ds_w, sc_vec, h, wdt, cin, stride};
+    return conv3x3_dispatch(t1, conv2_w, nullptr, nullptr, nullptr, nullptr, nullptr, out, nullptr, nullptr, batch, ho, wo, cout, cout, 1, 0, 0, precision, stream,
+                            nullptr, nullptr, nullptr, &sc);
 }
 
 extern "C" int eg_se_residual_relu(const float* y, const float* gate, const float* x_in, const float* ds_w,

@@ -191,6 +191,7 @@ struct BlockW {
     int64_t se_w1, se_b1, se_w2, se_b2;
     bool ds = false;
     int64_t ds_w = -1, ds_scale = -1, ds_shift = -1;
+    int64_t ds_wb = -1;         // the downsample's bf16 (hi, lo) images: the shortcut inside conv2 (eg_se_block_fused)
     int cin, cout, stride;
 };
 struct MhaW { LinW q, kv, qkv, o; int64_t ln_g, ln_b; };
@@ -285,7 +286,7 @@ struct EgGenerator {
     std::vector<BlockW> blocks;
     ConvW final_conv;
     LinW a_fc1, a_fc2, emosem0, emo2, sem2, fus0, fus2, cls[4], post[4], prior_h0, prior_h2, txt_dec;
-    bool fuse_se = true;        // identity SE blocks: gate from input moments + tail in conv2's epilogue (cfg.reserved[3] = 1 disables)
+    bool fuse_se = true;        // SE blocks: gate from input moments + tail (and, split-bf16 modes, the stage entries' 1x1 shortcut) inside conv2 (cfg.reserved[3] = 1 disables)
     bool fold = false;          // cfg.reserved[2]: the chains below replace their members
     bool shared_chip = false;   // cfg.reserved[4]: several batches in flight (ClipPipeline lanes): products choose their tile for CU time
     LinW f_audio, f_emo, f_sem, f_post, f_prior;
@@ -332,7 +333,7 @@ struct EgGenerator {
 namespace {
 
 struct GenWs {      // byte offsets into the workspace, for a given batch
-    int64_t act[3], gap, gate, amap, afc1, afeat, emo_t, emo, sem_t, sem, cls_part, cls_h[3], cls_out;
+    int64_t act[3], gap, gate, scv, amap, afc1, afeat, emo_t, emo, sem_t, sem, cls_part, cls_h[3], cls_out;
     int64_t fus_in, fus_h, fusion, xa, xb, q, qkv, ao, proj, ffn_h, im_x[2], im_enc, im_h, im_a[3], im_p[2];
     int64_t prior_cat, prior_h, prior_enc, prior_rep, tm_mem, tm_pe, tm_gram, post_a, post_b, post_c, pose;
     int64_t t_emb, t_a, t_b, t_c, t_out;
@@ -355,11 +356,15 @@ GenWs carve(const EgGenerator* g, int B, int NB = 0) {
             const int ho = (h + 2 - 3) / b.stride + 1, wo = (wd + 2 - 3) / b.stride + 1;
             const int64_t need = (int64_t)eg_conv3x3_gap_tiles(ho, wo, b.cout, b.cout, 1) * b.cout;
             gap_per_clip = need > gap_per_clip ? need : gap_per_clip;
+            // the fused flow pools conv1's output instead: the stage entries' stride-2 conv1 has its own (smaller) tiles
+            const int64_t need1 = (int64_t)eg_conv3x3_gap_tiles(h, wd, b.cin, b.cout, b.stride) * b.cout;
+            gap_per_clip = need1 > gap_per_clip ? need1 : gap_per_clip;
             h = ho; wd = wo;
         }
         w.gap = cv.take((int64_t)B * gap_per_clip);
     }
     w.gate = cv.take((int64_t)B * 128);
+    w.scv = cv.take((int64_t)3 * B * 128);       // stage-entry blocks: conv2's shortcut rescale f and its per-clip epilogue scale q and shift h
     w.amap = cv.take(BF * g->HW3);
     w.afc1 = cv.take(BF * D); w.afeat = cv.take(BF * D);
     w.emo_t = cv.take(BF * D * 2); w.emo = cv.take(BF * D); w.sem_t = cv.take(16); w.sem = cv.take(BF * D);
@@ -498,15 +503,14 @@ int run_audio_tower(const EgGenerator* g, const float* arena, const float* spec,
             const BlockW& bw = g->blocks[bi];
             const int t1 = (xi + 1) % 3, t2 = (xi + 2) % 3;
             const int ho = (h + 2 - 3) / bw.stride + 1, wo = (wd + 2 - 3) / bw.stride + 1;
-            if (!bw.ds && g->fuse_se) {
-                // identity block: gate from the moments of conv1's output, then conv2 with relu(y * gate + x) in its epilogue --
-                // y is never materialised and the separate tail pass disappears (conv.hip: se_gate_pre_kernel)
-                EG_TRY(run_conv(arena, bw.c1, bufs[xi], bufs[t1], gap, B, h, wd, 1, 0, prec, st));
-                const int tiles1 = eg_conv3x3_gap_tiles(h, wd, bw.cin, bw.cout, 1);
-                EG_TRY(eg_se_gate_pre(bufs[t1], gap, tiles1, arena + bw.c2.w, arena + bw.c2.scale, arena + bw.c2.shift, arena + bw.se_w1,
-                                      arena + bw.se_b1, arena + bw.se_w2, arena + bw.se_b2, gate, B, ho, wo, bw.cout, st));
-                EG_TRY(eg_conv3x3_se(bufs[t1], arena + bw.c2.w, nullptr, arena + bw.c2.scale, arena + bw.c2.shift, gate, bufs[xi], bufs[t2], nullptr, B,
-                                     ho, wo, bw.cout, bw.cout, 1, 0, 0, prec, st));
+            if (g->fuse_se && (!bw.ds || prec != EG_PREC_F32)) {
+                // gate from the moments of conv1's output, then conv2 with the whole tail in its epilogue: relu(y * gate + x) for an identity block; a stage
+                // entry (split-bf16 modes) also contracts its 1x1 stride-2 shortcut inside conv2 -- y is never materialised and no separate tail pass
+                // runs (conv.hip: eg_se_block_fused, se_gate_pre_kernel)
+                EG_TRY(eg_se_block_fused(bufs[xi], arena + bw.c1.w, arena + bw.c1.scale, arena + bw.c1.shift, arena + bw.c2.w, arena + bw.c2.scale,
+                                         arena + bw.c2.shift, arena + bw.se_w1, arena + bw.se_b1, arena + bw.se_w2, arena + bw.se_b2,
+                                         bw.ds ? arena + bw.ds_wb : nullptr, bw.ds ? arena + bw.ds_scale : nullptr, bw.ds ? arena + bw.ds_shift : nullptr,
+                                         bufs[t1], bufs[t2], gap, gate, P(ws, w.scv), B, h, wd, bw.cin, bw.cout, bw.stride, prec, st));
                 xi = t2; h = ho; wd = wo;
                 continue;
             }
@@ -732,6 +736,7 @@ extern "C" int eg_generator_create(const EgGeneratorConfig* cfg, EgGenerator** o
             b.ds = (b.stride != 1 || inpl != planes);
             if (b.ds) {
                 b.ds_w = L.add(p + ".downsample.0.weight", EG_PACK_CONV1X1, planes, inpl, 0, 0, (int64_t)inpl * planes);
+                b.ds_wb = L.add(p + ".downsample.0.weight", EG_PACK_CONV1X1_BF16, planes, inpl, 0, 0, (int64_t)inpl * planes);
                 add_bn(L, p + ".downsample.1", planes, planes, b.ds_scale, b.ds_shift);
             }
             g->blocks.push_back(b);

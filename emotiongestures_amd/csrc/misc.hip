@@ -5,13 +5,10 @@
 namespace {
 
 // ---- LayerNorm (Full_model/SubLayers.py:55-57,80-82): one wave per row, two-pass in registers ----------
-// SUMP: the row is not read from x but folded from `nparts` partial-sum planes [nparts][rows][D] (x = plane 0) in order, + bias2 + resid: the epilogue
-// the fused FFN slab kernel (ffn.hip) leaves to its LayerNorm when the hidden is split over several workgroups.
-struct LnSum { int nparts = 0; const float* bias2 = nullptr; const float* resid = nullptr; int ldr = 0; };
-template <int NV, bool SUMP = false>   // NV f4 per lane (D <= NV*256)
+template <int NV>   // NV f4 per lane (D <= NV*256)
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                         const float* __restrict__ b, float* __restrict__ y, int rows, int D,
-                                                        float eps, unsigned short* __restrict__ img, LnSum ps = LnSum()) {
+                                                        float eps, unsigned short* __restrict__ img) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
     const f4* xr = reinterpret_cast<const f4*>(x + (size_t)row * D);
@@ -22,10 +19,6 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     for (int i = 0; i < NV; ++i) {
         const int q = lane + i * 64;
         v[i] = q < nq ? xr[q] : (f4){0.f, 0.f, 0.f, 0.f};
-        if (SUMP && q < nq) {
-            for (int p = 1; p < ps.nparts; ++p) v[i] += reinterpret_cast<const f4*>(x + ((size_t)p * rows + row) * D)[q];
-            v[i] = v[i] + reinterpret_cast<const f4*>(ps.bias2)[q] + reinterpret_cast<const f4*>(ps.resid + (size_t)row * ps.ldr)[q];
-        }
         s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
     }
     const float mean = wave_sum(s) / (float)D;

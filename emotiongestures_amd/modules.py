@@ -314,6 +314,18 @@ class SEBasicBlock(nn.Module):
             return ops.se_residual_relu(y, gate, x, self.downsample[0].weight, ds[0], ds[1], stride=self.stride)
         return ops.se_residual_relu(y, gate, x)
 
+    def forward_fused_nhwc(self, x):
+        """The block as the generator's audio tower runs it (eg_se_block_fused): the gate from conv1's output, the tail -- and a stage entry's 1x1
+        shortcut -- inside conv2.  forward_nhwc stays the operator-by-operator path."""
+        _eval_only(self)
+        c1, c2, ds = self._packed(x.device)
+        fc = self.se.fc
+        kw = {}
+        if self.downsample is not None:
+            kw = dict(ds_weight=self.downsample[0].weight, ds_scale=ds[0], ds_shift=ds[1])
+        return ops.se_block_fused(x, c1, c2, fc[0].weight, fc[0].bias, fc[2].weight, fc[2].bias, self.conv2.weight.shape[0], stride=self.stride,
+                                  precision=self.precision, **kw)
+
     def forward(self, x):
         return self.forward_nhwc(x.permute(0, 2, 3, 1).contiguous()).permute(0, 3, 1, 2).contiguous()
 
@@ -695,7 +707,7 @@ class Transformer(ReplicaAware, nn.Module):
         self.fold_affine = False         # fold the Dropout-only Linear chains at pack time (fewer launches / FLOPs; off for parity runs)
         self.train_dropout = False       # train(): activate the reference's Dropout layers (default: p = 0, the gradient-parity configuration)
         self.shared_chip = False         # several batches in flight on this GPU (ClipPipeline sets it): GEMM tiles chosen for CU time, not stand-alone latency
-        self.fuse_se = True              # identity SE blocks: gate from conv1's output moments, tail in conv2's epilogue (same arithmetic order per element)
+        self.fuse_se = True              # SE blocks: gate from conv1's output moments, tail (split-bf16 modes: and a stage entry's 1x1 shortcut) inside conv2
 
     # ---- engine management: repack the arena only when weights / device / mode changed ----
     def _weights_version(self):

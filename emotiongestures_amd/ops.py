@@ -125,6 +125,29 @@ def se_residual_relu(y, gate, x_in, ds_weight=None, ds_scale=None, ds_shift=None
     return out
 
 
+def se_block_fused(x_nhwc, c1, c2, se_w1, se_b1, se_w2, se_b2, cout, stride=1, ds_weight=None, ds_scale=None, ds_shift=None, precision="bf16x3"):
+    """One SEBasicBlock in the audio tower's fused data flow (eg_se_block_fused: conv1 -> gate from t1's moments -> conv2 with the tail, and a stage
+    entry's 1x1 shortcut, inside).  c1 / c2 = conv3x3_pack() of the two convolutions with their folded BatchNorm as scale / shift."""
+    lib = L.load()
+    x = _need_cuda(x_nhwc, "x")
+    dev = x.device
+    B, H, W, Cin = x.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    tiles = lib.eg_conv3x3_gap_tiles(H, W, Cin, cout, stride)
+    t1, out = torch.empty(B, Ho, Wo, cout, device=dev), torch.empty(B, Ho, Wo, cout, device=dev)
+    gap, gate = torch.empty(B, tiles, cout, device=dev), torch.empty(B, cout, device=dev)
+    dsw = scv = None
+    if ds_weight is not None:
+        dsw = torch.from_numpy(packing._pack_conv1x1_bf16(ds_weight.detach().cpu().float())).to(dev)
+        scv = torch.empty(3, B, cout, device=dev)
+        ds_scale, ds_shift = _need_cuda(ds_scale, "ds_scale"), _need_cuda(ds_shift, "ds_shift")
+    L.check(lib.eg_se_block_fused(_ptr(x), _ptr(c1[0]), _ptr(c1[2]), _ptr(c1[3]), _ptr(c2[0]), _ptr(c2[2]), _ptr(c2[3]), _ptr(_need_cuda(se_w1, "w1")),
+                                  _ptr(_need_cuda(se_b1, "b1")), _ptr(_need_cuda(se_w2, "w2")), _ptr(_need_cuda(se_b2, "b2")), _ptr(dsw), _ptr(ds_scale),
+                                  _ptr(ds_shift), _ptr(t1), _ptr(out), _ptr(gap), _ptr(gate), _ptr(scv), B, H, W, Cin, cout, stride,
+                                  L.precision_code(precision), _stream(dev)), "eg_se_block_fused")
+    return out
+
+
 def linear(x, weight, bias=None, res1=None, res2=None, relu=False, a_shift=0, a_seq=0, precision="f32", packed=None):
     """y = epi(x @ weight.T): x [M,K] (row-major, K%4==0), weight nn.Linear [N,K]."""
     lib = L.load()

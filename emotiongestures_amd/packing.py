@@ -60,6 +60,14 @@ def _pack_conv3x3(w: torch.Tensor, opad: int) -> np.ndarray:
     return _with_bf16_images(f32.numpy(), hi, lo)
 
 
+def _pack_conv1x1_bf16(w: torch.Tensor) -> np.ndarray:
+    """Conv2d [O,I,1,1] -> bf16 images [I/8][O][8], hi then lo: one tap of the 3x3 images' packing (the stage-entry shortcut inside conv2)."""
+    o, i = w.shape[:2]
+    oct_ = w.reshape(o, i).t().reshape(i // 8, 8, o).permute(0, 2, 1).contiguous()      # [ci/8][co][8]
+    hi, lo = _bf16_split_bits(oct_)
+    return np.concatenate([hi.reshape(-1), lo.reshape(-1)]).view(np.float32)
+
+
 def _bn_affine(sd, prefix: str):
     scale = _t(sd, prefix + ".weight") / torch.sqrt(_t(sd, prefix + ".running_var") + BN_EPS)
     shift = _t(sd, prefix + ".bias") - _t(sd, prefix + ".running_mean") * scale
@@ -105,6 +113,8 @@ def pack_entry(sd: Mapping[str, torch.Tensor], e: L.EgWeightEntry) -> np.ndarray
     elif kind == L.PACK_CONV1X1:
         w = _t(sd, key)
         out = w.reshape(w.shape[0], w.shape[1]).t().contiguous().reshape(-1).numpy()
+    elif kind == L.PACK_CONV1X1_BF16:
+        out = _pack_conv1x1_bf16(_t(sd, key))
     elif kind == L.PACK_STEM:
         w = _t(sd, key)
         out = w.reshape(w.shape[0], 9).t().contiguous().reshape(-1).numpy()

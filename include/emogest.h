@@ -100,7 +100,9 @@ typedef enum EgPackKind {
     EG_PACK_LINEAR_FOLD = 12,   /* key = chain "last@...@first" of nn.Linear prefixes with only Dropout between them (eval mode: an
                                    affine chain): W = W_last ... W_first folded in float64, packed as EG_PACK_LINEAR (same dims);
                                    several chains joined by '|' are concatenated along N */
-    EG_PACK_BIAS_FOLD = 13      /* the folded chain's bias, zero padded to dims[1] */
+    EG_PACK_BIAS_FOLD = 13,     /* the folded chain's bias, zero padded to dims[1] */
+    EG_PACK_CONV1X1_BF16 = 14   /* Conv2d [O,I,1,1] -> bf16 images [I/8][O][8], hi = bf16(w) then lo = bf16(w - hi): the 3x3 images' packing with a
+                                   single tap (dims = O,I; numel = O*I floats).  I % 32 == 0, O % 16 == 0 */
 } EgPackKind;
 
 typedef struct EgWeightEntry {
@@ -572,6 +574,18 @@ int eg_conv3x3_sq_in_affine(const float* x, const float* in_scale, const float* 
 int eg_se_gate_pre(const float* t1, const float* gap_partial, int32_t tiles, const float* conv2_w_packed, const float* scale2,
                    const float* shift2, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
                    int32_t batch, int32_t h, int32_t wdt, int32_t c, void* stream);
+/* One SEBasicBlock (ResNetBlocks.py:21-37) in the audio tower's fused data flow -- what eg_generator_forward runs per block when the SE fusion is on:
+ *   t1 = BN1(relu(conv1(x)))  (stride 1 or 2, with per-tile channel sums in gap_partial)  ->  eg_se_gate_pre on t1  ->
+ *   out = relu(gate * BN2(conv2(t1)) + shortcut) from conv2's epilogue.  Neither conv2's output y nor a shortcut map is written; three launches.
+ * ds_w == NULL: identity shortcut (cin == cout, stride 1; any precision).  ds_w = the EG_PACK_CONV1X1_BF16 images of `downsample.0.weight`: the strided
+ * 1x1 shortcut is contracted on the matrix pipe inside conv2 (split-bf16 modes only; 32 -> 64 and 64 -> 128), ds_scale / ds_shift its folded BatchNorm.
+ *   x [B,H,W,Cin]; conv1_w, conv2_w EG_PACK_CONV3X3; scale / shift [Cout]; se_* as eg_se_gate
+ *   scratch: t1 [B,Ho,Wo,Cout], gap_partial [B, eg_conv3x3_gap_tiles(H,W,Cin,Cout,stride), Cout], gate [B,Cout], sc_vec [3,B,Cout] (downsample only)
+ *   out [B,Ho,Wo,Cout], distinct from x and t1. */
+int eg_se_block_fused(const float* x, const float* conv1_w, const float* scale1, const float* shift1, const float* conv2_w, const float* scale2,
+                      const float* shift2, const float* se_w1, const float* se_b1, const float* se_w2, const float* se_b2, const float* ds_w,
+                      const float* ds_scale, const float* ds_shift, float* t1, float* out, float* gap_partial, float* gate, float* sc_vec,
+                      int32_t batch, int32_t h, int32_t wdt, int32_t cin, int32_t cout, int32_t stride, int32_t precision, void* stream);
 /* size in floats of one EG_PACK_CONV3X3 image (fp32 image + bf16 hi/lo images) */
 int64_t eg_conv3x3_packed_floats(int32_t cin, int32_t cout_pad);
 
