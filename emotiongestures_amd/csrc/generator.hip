@@ -915,113 +915,32 @@ extern "C" int eg_generator_forward_draws(const EgGenerator* g, const float* are
     return run_transformer(g, arena, P(ws, w.fus_in), act(P(ws, w.prior_rep), D), pose, w, ws, B * R, st);
 }
 
-// ---- roll-out: W dependent windows of U utterances --------------------------------------------------------------------------------
-namespace {
-struct RollWs { GenWs a; int64_t kv[8], prior[2], spec, text, sampled, total; };
-RollWs carve_rollout(const EgGenerator* g, int U, int64_t N) {      // N clips in all: U*W for a rectangle, sum of W_u for a ragged call
-    const EgGeneratorConfig& c = g->cfg;
-    RollWs r;
-    r.a = carve(g, (int)N);             // phase A at batch U*W; the decoder steps reuse its buffers at batch U
-    Carver cv;
-    cv.off = r.a.total;
-    for (int l = 0; l < c.n_layers; ++l) r.kv[l] = cv.take(N * c.frames * 2 * c.d_model);
-    r.prior[0] = cv.take((int64_t)U * c.prior_frames * c.pose_dim);
-    r.prior[1] = cv.take((int64_t)U * c.prior_frames * c.pose_dim);
-    // window-major copies of the utterance-major arguments (unused when U == 1 or W == 1: the two orders coincide)
-    r.spec = cv.take(N * c.n_mels * c.spec_len);
-    r.text = cv.take(N * c.text_len * 2);
-    r.sampled = cv.take(N * c.frames * c.d_model);
-    r.total = cv.off;
-    return r;
-}
-}  // namespace
-
-extern "C" int64_t eg_generator_rollout_workspace_bytes(const EgGenerator* g, int32_t utterances, int32_t windows) {
-    if (!g || utterances <= 0 || windows <= 0 || g->cfg.n_layers > 8 || (int64_t)utterances * windows > (1 << 20)) return 0;
-    return carve_rollout(g, utterances, (int64_t)utterances * windows).total;
-}
-
-extern "C" int eg_generator_forward_rollout(const EgGenerator* g, const float* arena, int32_t U, int32_t W, const float* spec,
-                                            const int64_t* text, const float* seed_pose, const float* sampled, const float* alpha,
-                                            float* track, float* windows, float* emotion_prediction, float* emotion_feature,
-                                            float* semantic_feature, float* text_embedding, void* ws, int64_t ws_bytes, void* stream) {
-    EG_REQUIRE(g && arena && spec && seed_pose && track && ws, EG_ERR_BAD_ARG, "eg_generator_forward_rollout: null pointer");
-    EG_REQUIRE(U >= 1, EG_ERR_BAD_ARG, "eg_generator_forward_rollout: utterances=%d (need >= 1)", U);
-    EG_REQUIRE(W >= 1, EG_ERR_BAD_ARG, "eg_generator_forward_rollout: windows=%d (need >= 1)", W);
-    EG_REQUIRE((int64_t)U * W <= (1 << 20), EG_ERR_UNSUPPORTED, "eg_generator_forward_rollout: utterances*windows=%lld", (long long)U * W);
-    EG_REQUIRE(text || !text_embedding, EG_ERR_BAD_ARG, "eg_generator_forward_rollout: text_embedding wanted without text");
-    EG_REQUIRE(g->cfg.n_layers <= 8, EG_ERR_UNSUPPORTED, "eg_generator_forward_rollout: n_layers=%d > 8", g->cfg.n_layers);
-    const RollWs r = carve_rollout(g, U, (int64_t)U * W);
-    const GenWs& w = r.a;
-    EG_REQUIRE(ws_bytes >= r.total, EG_ERR_WORKSPACE, "eg_generator_forward_rollout: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)r.total);
-    EG_REQUIRE(eg_aligned16(ws) && eg_aligned16(arena) && eg_aligned16(spec), EG_ERR_ALIGN, "eg_generator_forward_rollout: 16-byte alignment");
-    hipStream_t st = (hipStream_t)stream;
-    const EgGeneratorConfig& c = g->cfg;
-    const int F = c.frames, D = c.d_model, N = U * W, P_ = c.prior_frames, PD = c.pose_dim;
-    const bool swap = U > 1 && W > 1;           // clip n = w*U + u in phase A, so that the U clips of a step are contiguous
-
-    // ---- phase A, batch U*W: everything the prior does not reach
-    if (swap) {
-        EG_TRY(egi_swap01(spec, P(ws, r.spec), U, W, (size_t)c.n_mels * c.spec_len, st));
-        spec = P(ws, r.spec);
-        if (text_embedding) {
-            EG_TRY(egi_swap01(text, P(ws, r.text), U, W, (size_t)c.text_len * 2, st));
-            text = reinterpret_cast<const int64_t*>(P(ws, r.text));
-        }
-        if (sampled) {
-            EG_TRY(egi_swap01(sampled, P(ws, r.sampled), U, W, (size_t)F * D, st));
-            sampled = P(ws, r.sampled);
-        }
-    }
-    // outputs in utterance-major order: made in the workspace and swapped back, or written in place when the orders coincide
-    float* txt = swap ? P(ws, w.t_out) : text_embedding;
-    float* emo = swap || !emotion_feature ? P(ws, w.emo) : emotion_feature;
-    float* sem = swap || !semantic_feature ? P(ws, w.sem) : semantic_feature;
-    float* pred = swap || !emotion_prediction ? P(ws, w.cls_out) : emotion_prediction;
-    if (text_embedding) EG_TRY(run_text(g, arena, text, txt, w, ws, N, st));
-    EG_TRY(run_audio_tower(g, arena, spec, w, ws, N, st));
-    EG_TRY(run_heads(g, arena, emo, sem, pred, w, ws, N, st));
-    EG_TRY(egi_add(sampled ? sampled : emo, sem, P(ws, w.fus_in), (size_t)N * F * D, D, 0, st));
-    Act enc_out;
-    EG_TRY(run_encoder(g, arena, P(ws, w.fus_in), enc_out, w, ws, N, st));
-    float* kv[8];
-    for (int l = 0; l < c.n_layers; ++l) {
-        kv[l] = P(ws, r.kv[l]);
-        EG_TRY(lin(g, arena, g->dec_attn[l].kv, enc_out, 0, act(kv[l], 2 * D), true, N * F, 0, nullptr, 0, st));
-    }
-    if (swap) {
-        if (text_embedding) EG_TRY(egi_swap01(txt, text_embedding, W, U, (size_t)c.text_len * 512, st));
-        if (emotion_feature) EG_TRY(egi_swap01(emo, emotion_feature, W, U, (size_t)F * D, st));
-        if (semantic_feature) EG_TRY(egi_swap01(sem, semantic_feature, W, U, (size_t)F * D, st));
-        if (emotion_prediction) EG_TRY(egi_swap01(pred, emotion_prediction, W, U, 8, st));
-    }
-
-    // ---- phase B, W dependent steps of U clips: prior encoder -> decoder over that step's K|V slice -> post_projector -> hand-off
-    const float* prior = seed_pose;
-    const Act prior_enc = act(P(ws, w.prior_enc), D, P(ws, w.im_p[1]), D);
-    for (int s = 0; s < W; ++s) {
-        EG_TRY(run_prior(g, arena, prior, w, ws, U, st));
-        float* step_kv[8];
-        for (int l = 0; l < c.n_layers; ++l) step_kv[l] = kv[l] + (size_t)s * U * F * 2 * D;
-        EG_TRY(run_decoder(g, arena, prior_enc, Act(), step_kv, P(ws, w.pose), w, ws, U, st));
-        float* next = P(ws, r.prior[s & 1]);
-        EG_TRY(egi_rollout_handoff(P(ws, w.pose), prior, alpha, track, windows, next, U, W, s, F, P_, PD, st));
-        prior = next;
-    }
-    return EG_OK;
-}
-
-// ---- diverse roll-out: R sampled tracks per recording, the audio tower once (kernels: draws.hip) -------------------------------------
+// ---- roll-out: dependent windows of U recordings, in three calls on one skeleton -----------------------------------------------------------
+// Phase A runs everything the prior does not reach at the batch of all N clips, in step order (the clips of a step contiguous); phase B
+// runs the dependent steps: prior encoder -> decoder over that step's K|V slice -> post_projector -> hand-off.  The rectangular call
+// (W windows each), the ragged call (W_u windows, kernels: ragged.hip) and the diverse call (R >= 2 sampled tracks per recording, kernels:
+// draws.hip) differ in five places only: the row order in and out, the fusion input, the encoder / K|V rows (N*R), step 0's prior, and the
+// step batch with its hand-off.
 int egi_draws_fusion(const float* sampled, const float* semantic, float* fus_in, int U, int W, int R, size_t clip_floats, hipStream_t st);
 int egi_draws_seed(const float* seed, float* prior, int U, int R, int PD, hipStream_t st);
 namespace {
-// R >= 2 (R == 1 is carve_rollout's layout: the call is then eg_generator_forward_rollout itself).  Phase A: carve(N, N*R) -- the tower
-// side at N = U*W clips, fusion / encoder / decoder buffers at N*R rows.  Phase B runs the prior encoder at batch U*R, which carve sizes
-// for N: when U*R > N (R > W) its buffers are taken again at U*R.  No copy of `sampled`: the fusion kernel reads the caller's order.
-struct RollDrawsWs { GenWs a; int64_t kv[8], prior[2], spec, text, total; };
-RollDrawsWs carve_rollout_draws(const EgGenerator* g, int U, int64_t N, int R) {
+struct RollPlan {
+    int U, R, N, steps;             // recordings, draws per recording, clips in all, dependent steps (W, or the longest recording's W_u)
+    const int32_t* plan;            // ragged: the device table (slot -> packed row [N] | rank -> recording [U] | ...); null: a rectangle
+    const int32_t* windows_per;     // ragged, host: W_u
+    const int32_t* order;           // ragged, host: rank -> recording, longer first, ties by index
+    bool same_order;                // step order and the caller's order of the window-indexed rows coincide: nothing is moved
+    bool seed_in_order;             // the seed poses are in the steps' row order already (ragged: the rank order is the identity)
+};
+
+// The layout after carve(N, N*R) -- the tower side at N clips, fusion / encoder / decoder buffers at N*R rows.  Phase B runs the prior
+// encoder at batch U*R, which carve sizes for N: when U*R > N (R > W) its buffers are taken again at U*R.  spec / text / sampled: copies
+// in step order of the caller's arguments (unused when the orders coincide); R >= 2 has no copy of `sampled`, the fusion kernel reads the
+// caller's order.
+struct RollWs { GenWs a; int64_t kv[8], prior[2], spec, text, sampled, total; };
+RollWs carve_rollout(const EgGenerator* g, int U, int64_t N, int R) {      // N: U*W for a rectangle, sum of W_u for a ragged call
     const EgGeneratorConfig& c = g->cfg;
-    RollDrawsWs r;
+    RollWs r;
     r.a = carve(g, (int)N, (int)(N * R));
     GenWs& w = r.a;
     Carver cv;
@@ -1038,25 +957,139 @@ RollDrawsWs carve_rollout_draws(const EgGenerator* g, int U, int64_t N, int R) {
     r.prior[1] = cv.take(UR * c.prior_frames * c.pose_dim);
     r.spec = cv.take(N * c.n_mels * c.spec_len);
     r.text = cv.take(N * c.text_len * 2);
+    r.sampled = R == 1 ? cv.take(N * c.frames * D) : -1;
     r.total = cv.off;
     return r;
 }
+
+// N rows of `words` 32-bit words from the caller's order into step order, or back
+int roll_rows(const RollPlan& p, const void* in, void* out, size_t words, bool back, hipStream_t st) {
+    if (p.plan) return egi_rows_by_table(in, out, p.plan, p.N, words, back, st);
+    return back ? egi_swap01(in, out, p.steps, p.U, words, st) : egi_swap01(in, out, p.U, p.steps, words, st);
+}
+
+// Phase A, batch N (clip n = w*U + u of a rectangle, slot (s, rank) after the slots of the steps before it in a ragged call); from the
+// fusion on N*R rows, (clip, draw) row n*R + r.  Leaves kv[l] = [N*R*F, 2*d_model], the decoder layers' K|V of every step.
+int rollout_phase_a(const EgGenerator* g, const float* arena, const RollPlan& p, const RollWs& r, void* ws, const float* spec,
+                    const int64_t* text, const float* sampled, float* emotion_prediction, float* emotion_feature, float* semantic_feature,
+                    float* text_embedding, float** kv, hipStream_t st) {
+    const EgGeneratorConfig& c = g->cfg;
+    const GenWs& w = r.a;
+    const int F = c.frames, D = c.d_model, N = p.N, NR = p.N * p.R;
+    const bool move = !p.same_order;
+    if (move) {
+        EG_TRY(roll_rows(p, spec, P(ws, r.spec), (size_t)c.n_mels * c.spec_len, false, st));
+        spec = P(ws, r.spec);
+        if (text_embedding) {
+            EG_TRY(roll_rows(p, text, P(ws, r.text), (size_t)c.text_len * 2, false, st));
+            text = reinterpret_cast<const int64_t*>(P(ws, r.text));
+        }
+        if (sampled && p.R == 1) {
+            EG_TRY(roll_rows(p, sampled, P(ws, r.sampled), (size_t)F * D, false, st));
+            sampled = P(ws, r.sampled);
+        }
+    }
+    // outputs in the caller's order: made in the workspace and moved back, or written in place when the orders coincide
+    float* txt = move ? P(ws, w.t_out) : text_embedding;
+    float* emo = move || !emotion_feature ? P(ws, w.emo) : emotion_feature;
+    float* sem = move || !semantic_feature ? P(ws, w.sem) : semantic_feature;
+    float* pred = move || !emotion_prediction ? P(ws, w.cls_out) : emotion_prediction;
+    if (text_embedding) EG_TRY(run_text(g, arena, text, txt, w, ws, N, st));
+    EG_TRY(run_audio_tower(g, arena, spec, w, ws, N, st));
+    EG_TRY(run_heads(g, arena, emo, sem, pred, w, ws, N, st));
+    if (p.R == 1) EG_TRY(egi_add(sampled ? sampled : emo, sem, P(ws, w.fus_in), (size_t)N * F * D, D, 0, st));
+    else EG_TRY(egi_draws_fusion(sampled, sem, P(ws, w.fus_in), p.U, p.steps, p.R, (size_t)F * D, st));
+    Act enc_out;
+    EG_TRY(run_encoder(g, arena, P(ws, w.fus_in), enc_out, w, ws, NR, st));
+    for (int l = 0; l < c.n_layers; ++l) {
+        kv[l] = P(ws, r.kv[l]);
+        EG_TRY(lin(g, arena, g->dec_attn[l].kv, enc_out, 0, act(kv[l], 2 * D), true, NR * F, 0, nullptr, 0, st));
+    }
+    if (move) {
+        if (text_embedding) EG_TRY(roll_rows(p, txt, text_embedding, (size_t)c.text_len * 512, true, st));
+        if (emotion_feature) EG_TRY(roll_rows(p, emo, emotion_feature, (size_t)F * D, true, st));
+        if (semantic_feature) EG_TRY(roll_rows(p, sem, semantic_feature, (size_t)F * D, true, st));
+        if (emotion_prediction) EG_TRY(roll_rows(p, pred, emotion_prediction, 8, true, st));
+    }
+    return EG_OK;
+}
+
+// Phase B: p.steps dependent steps.  A rectangle runs U*R rows in every step (row u*R + r: draw r of recording u); a ragged call runs the
+// recordings with W_u > s, the first ranks of its order, so a step's K|V slice starts at the running sum of the step batches.  The priors
+// ping-pong between two buffers; step 0 reads seed_pose itself, or a copy in the steps' row order in the buffer step 0 does not write.
+int rollout_phase_b(const EgGenerator* g, const float* arena, const RollPlan& p, const RollWs& r, void* ws, float* const* kv,
+                    const float* seed_pose, const float* alpha, float* track, float* windows, hipStream_t st) {
+    const EgGeneratorConfig& c = g->cfg;
+    const GenWs& w = r.a;
+    const int F = c.frames, D = c.d_model, P_ = c.prior_frames, PD = c.pose_dim;
+    const float* prior = seed_pose;
+    if (p.R > 1) {              // seed_pose[u] repeated over the draws by one launch
+        EG_TRY(egi_draws_seed(seed_pose, P(ws, r.prior[1]), p.U, p.R, P_ * PD, st));
+        prior = P(ws, r.prior[1]);
+    } else if (!p.seed_in_order) {
+        EG_TRY(egi_rows_by_table(seed_pose, P(ws, r.prior[1]), p.plan + p.N, p.U, (size_t)P_ * PD, false, st));
+        prior = P(ws, r.prior[1]);
+    }
+    const Act prior_enc = act(P(ws, w.prior_enc), D, P(ws, w.im_p[1]), D);
+    int batch = p.U * p.R;
+    size_t slot = 0;
+    for (int s = 0; s < p.steps; ++s) {
+        if (p.plan)
+            while (batch > 0 && p.windows_per[p.order[batch - 1]] <= s) --batch;
+        EG_TRY(run_prior(g, arena, prior, w, ws, batch, st));
+        float* step_kv[8];
+        for (int l = 0; l < c.n_layers; ++l) step_kv[l] = kv[l] + slot * F * 2 * D;
+        EG_TRY(run_decoder(g, arena, prior_enc, Act(), step_kv, P(ws, w.pose), w, ws, batch, st));
+        float* next = P(ws, r.prior[s & 1]);
+        if (p.plan)
+            EG_TRY(egi_rollout_handoff_ragged(P(ws, w.pose), prior, alpha, track, windows, next, p.plan, p.N, p.U, batch, p.steps, s, F, P_, PD, st));
+        else
+            EG_TRY(egi_rollout_handoff(P(ws, w.pose), prior, alpha, track, windows, next, batch, p.steps, s, F, P_, PD, st));
+        prior = next;
+        slot += (size_t)batch;
+    }
+    return EG_OK;
+}
 }  // namespace
+
+extern "C" int64_t eg_generator_rollout_workspace_bytes(const EgGenerator* g, int32_t utterances, int32_t windows) {
+    if (!g || utterances <= 0 || windows <= 0 || g->cfg.n_layers > 8 || (int64_t)utterances * windows > (1 << 20)) return 0;
+    return carve_rollout(g, utterances, (int64_t)utterances * windows, 1).total;
+}
+
+extern "C" int eg_generator_forward_rollout(const EgGenerator* g, const float* arena, int32_t U, int32_t W, const float* spec,
+                                            const int64_t* text, const float* seed_pose, const float* sampled, const float* alpha,
+                                            float* track, float* windows, float* emotion_prediction, float* emotion_feature,
+                                            float* semantic_feature, float* text_embedding, void* ws, int64_t ws_bytes, void* stream) {
+    EG_REQUIRE(g && arena && spec && seed_pose && track && ws, EG_ERR_BAD_ARG, "eg_generator_forward_rollout: null pointer");
+    EG_REQUIRE(U >= 1, EG_ERR_BAD_ARG, "eg_generator_forward_rollout: utterances=%d (need >= 1)", U);
+    EG_REQUIRE(W >= 1, EG_ERR_BAD_ARG, "eg_generator_forward_rollout: windows=%d (need >= 1)", W);
+    EG_REQUIRE((int64_t)U * W <= (1 << 20), EG_ERR_UNSUPPORTED, "eg_generator_forward_rollout: utterances*windows=%lld", (long long)U * W);
+    EG_REQUIRE(text || !text_embedding, EG_ERR_BAD_ARG, "eg_generator_forward_rollout: text_embedding wanted without text");
+    EG_REQUIRE(g->cfg.n_layers <= 8, EG_ERR_UNSUPPORTED, "eg_generator_forward_rollout: n_layers=%d > 8", g->cfg.n_layers);
+    const RollWs r = carve_rollout(g, U, (int64_t)U * W, 1);
+    EG_REQUIRE(ws_bytes >= r.total, EG_ERR_WORKSPACE, "eg_generator_forward_rollout: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)r.total);
+    EG_REQUIRE(eg_aligned16(ws) && eg_aligned16(arena) && eg_aligned16(spec), EG_ERR_ALIGN, "eg_generator_forward_rollout: 16-byte alignment");
+    const bool same = U == 1 || W == 1;         // else clip n = w*U + u in phase A, so that the U clips of a step are contiguous
+    const RollPlan p = {U, 1, U * W, W, nullptr, nullptr, nullptr, same, true};
+    hipStream_t st = (hipStream_t)stream;
+    float* kv[8];
+    EG_TRY(rollout_phase_a(g, arena, p, r, ws, spec, text, sampled, emotion_prediction, emotion_feature, semantic_feature, text_embedding, kv, st));
+    return rollout_phase_b(g, arena, p, r, ws, kv, seed_pose, alpha, track, windows, st);
+}
 
 extern "C" int64_t eg_generator_rollout_draws_workspace_bytes(const EgGenerator* g, int32_t utterances, int32_t windows, int32_t draws) {
     if (!g || utterances <= 0 || windows <= 0 || draws <= 0 || g->cfg.n_layers > 8) return 0;
     const int64_t N = (int64_t)utterances * windows;
     if (N > (1 << 20) || N * draws > (1 << 20)) return 0;
-    if (draws == 1) return carve_rollout(g, utterances, N).total;
-    return carve_rollout_draws(g, utterances, N, draws).total;
+    return carve_rollout(g, utterances, N, draws).total;
 }
 
 // Models_spatial_memory.py:566-616 / Models_memory.py:521-565 per (window, draw), chained as eg_generator_forward_rollout chains them.  The
 // sampled map enters at :601-602 / :551-552 (fusion input) and the prior at :585 / :535 -> decoder target stream (:611 / :560) only, so
 // :583, :588-592 (audio tower, emotion / semantic projections, classifier header) run once per clip, :607-609 and the decoder's K|V once
-// per (clip, draw), and the W dependent steps (:585, :611-614) at batch U*R.  Row u*R + r of every step is recording u*R + r of the replicated eg_generator_forward_rollout call;
-// step 0's prior is seed_pose[u] repeated over the draws by ONE launch of U*R*P*D elements (draws_seed_kernel) into the ping-pong buffer
-// step 0 does not write, so the prior encoder and the hand-off kernel read it as they read every later step's.
+// per (clip, draw), and the W dependent steps (:585, :611-614) at batch U*R.  Row u*R + r of every step is recording u*R + r of the
+// replicated eg_generator_forward_rollout call.
 extern "C" int eg_generator_forward_rollout_draws(const EgGenerator* g, const float* arena, int32_t U, int32_t W, int32_t R, const float* spec,
                                                   const int64_t* text, const float* seed_pose, const float* sampled, const float* alpha,
                                                   float* track, float* windows, float* emotion_prediction, float* emotion_feature,
@@ -1069,72 +1102,24 @@ extern "C" int eg_generator_forward_rollout_draws(const EgGenerator* g, const fl
                "eg_generator_forward_rollout_draws: utterances*windows*draws=%d*%d*%d > 2^20", U, W, R);
     EG_REQUIRE(text || !text_embedding, EG_ERR_BAD_ARG, "eg_generator_forward_rollout_draws: text_embedding wanted without text");
     EG_REQUIRE(g->cfg.n_layers <= 8, EG_ERR_UNSUPPORTED, "eg_generator_forward_rollout_draws: n_layers=%d > 8", g->cfg.n_layers);
-    const int64_t need = eg_generator_rollout_draws_workspace_bytes(g, U, W, R);
-    EG_REQUIRE(ws_bytes >= need, EG_ERR_WORKSPACE, "eg_generator_forward_rollout_draws: workspace %lld < %lld bytes", (long long)ws_bytes,
-               (long long)need);
+    const RollWs r = carve_rollout(g, U, (int64_t)U * W, R);
+    EG_REQUIRE(ws_bytes >= r.total, EG_ERR_WORKSPACE, "eg_generator_forward_rollout_draws: workspace %lld < %lld bytes", (long long)ws_bytes,
+               (long long)r.total);
     EG_REQUIRE(eg_aligned16(ws) && eg_aligned16(arena) && eg_aligned16(spec) && eg_aligned16(sampled), EG_ERR_ALIGN,
                "eg_generator_forward_rollout_draws: 16-byte alignment");
     if (R == 1)         // [U, 1, W, ...] is [U, W, ...]: the roll-out itself, launch for launch
         return eg_generator_forward_rollout(g, arena, U, W, spec, text, seed_pose, sampled, alpha, track, windows, emotion_prediction,
                                             emotion_feature, semantic_feature, text_embedding, ws, ws_bytes, stream);
-    const RollDrawsWs r = carve_rollout_draws(g, U, (int64_t)U * W, R);
-    const GenWs& w = r.a;
+    const RollPlan p = {U, R, U * W, W, nullptr, nullptr, nullptr, U == 1 || W == 1, true};
     hipStream_t st = (hipStream_t)stream;
-    const EgGeneratorConfig& c = g->cfg;
-    const int F = c.frames, D = c.d_model, N = U * W, UR = U * R, P_ = c.prior_frames, PD = c.pose_dim;
-    const bool swap = U > 1 && W > 1;           // clip n = w*U + u in phase A; (clip, draw) row (w*U + u)*R + r from the fusion on
-
-    // ---- phase A: the tower side at batch N, as the roll-out makes it; fusion, encoder and K|V at N*R rows in draw order
-    if (swap) {
-        EG_TRY(egi_swap01(spec, P(ws, r.spec), U, W, (size_t)c.n_mels * c.spec_len, st));
-        spec = P(ws, r.spec);
-        if (text_embedding) {
-            EG_TRY(egi_swap01(text, P(ws, r.text), U, W, (size_t)c.text_len * 2, st));
-            text = reinterpret_cast<const int64_t*>(P(ws, r.text));
-        }
-    }
-    float* txt = swap ? P(ws, w.t_out) : text_embedding;
-    float* emo = swap || !emotion_feature ? P(ws, w.emo) : emotion_feature;
-    float* sem = swap || !semantic_feature ? P(ws, w.sem) : semantic_feature;
-    float* pred = swap || !emotion_prediction ? P(ws, w.cls_out) : emotion_prediction;
-    if (text_embedding) EG_TRY(run_text(g, arena, text, txt, w, ws, N, st));
-    EG_TRY(run_audio_tower(g, arena, spec, w, ws, N, st));
-    EG_TRY(run_heads(g, arena, emo, sem, pred, w, ws, N, st));
-    EG_TRY(egi_draws_fusion(sampled, sem, P(ws, w.fus_in), U, W, R, (size_t)F * D, st));
-    Act enc_out;
-    EG_TRY(run_encoder(g, arena, P(ws, w.fus_in), enc_out, w, ws, N * R, st));
     float* kv[8];
-    for (int l = 0; l < c.n_layers; ++l) {
-        kv[l] = P(ws, r.kv[l]);
-        EG_TRY(lin(g, arena, g->dec_attn[l].kv, enc_out, 0, act(kv[l], 2 * D), true, N * R * F, 0, nullptr, 0, st));
-    }
-    if (swap) {
-        if (text_embedding) EG_TRY(egi_swap01(txt, text_embedding, W, U, (size_t)c.text_len * 512, st));
-        if (emotion_feature) EG_TRY(egi_swap01(emo, emotion_feature, W, U, (size_t)F * D, st));
-        if (semantic_feature) EG_TRY(egi_swap01(sem, semantic_feature, W, U, (size_t)F * D, st));
-        if (emotion_prediction) EG_TRY(egi_swap01(pred, emotion_prediction, W, U, 8, st));
-    }
-
-    // ---- phase B, W dependent steps of U*R rows: the roll-out's steps on the (recording, draw) rows
-    EG_TRY(egi_draws_seed(seed_pose, P(ws, r.prior[1]), U, R, P_ * PD, st));
-    const float* prior = P(ws, r.prior[1]);
-    const Act prior_enc = act(P(ws, w.prior_enc), D, P(ws, w.im_p[1]), D);
-    for (int s = 0; s < W; ++s) {
-        EG_TRY(run_prior(g, arena, prior, w, ws, UR, st));
-        float* step_kv[8];
-        for (int l = 0; l < c.n_layers; ++l) step_kv[l] = kv[l] + (size_t)s * UR * F * 2 * D;
-        EG_TRY(run_decoder(g, arena, prior_enc, Act(), step_kv, P(ws, w.pose), w, ws, UR, st));
-        float* next = P(ws, r.prior[s & 1]);
-        EG_TRY(egi_rollout_handoff(P(ws, w.pose), prior, alpha, track, windows, next, UR, W, s, F, P_, PD, st));
-        prior = next;
-    }
-    return EG_OK;
+    EG_TRY(rollout_phase_a(g, arena, p, r, ws, spec, text, sampled, emotion_prediction, emotion_feature, semantic_feature, text_embedding, kv, st));
+    return rollout_phase_b(g, arena, p, r, ws, kv, seed_pose, alpha, track, windows, st);
 }
 
-// ---- ragged roll-out: U recordings with their own window counts (plan and kernels: ragged.hip) -----------------------------------------
 extern "C" int64_t eg_generator_rollout_ragged_workspace_bytes(const EgGenerator* g, int32_t utterances, int64_t total_windows) {
     if (!g || utterances <= 0 || total_windows < utterances || g->cfg.n_layers > 8 || total_windows > (1 << 20)) return 0;
-    return carve_rollout(g, utterances, total_windows).total;
+    return carve_rollout(g, utterances, total_windows, 1).total;
 }
 
 extern "C" int eg_generator_forward_rollout_ragged(const EgGenerator* g, const float* arena, int32_t U, const int32_t* windows_per,
@@ -1154,80 +1139,24 @@ extern "C" int eg_generator_forward_rollout_ragged(const EgGenerator* g, const f
     EG_REQUIRE(N64 <= (1 << 20), EG_ERR_UNSUPPORTED, "eg_generator_forward_rollout_ragged: total windows=%lld > 2^20", (long long)N64);
     EG_REQUIRE(text || !text_embedding, EG_ERR_BAD_ARG, "eg_generator_forward_rollout_ragged: text_embedding wanted without text");
     EG_REQUIRE(g->cfg.n_layers <= 8, EG_ERR_UNSUPPORTED, "eg_generator_forward_rollout_ragged: n_layers=%d > 8", g->cfg.n_layers);
-    const RollWs r = carve_rollout(g, U, N64);
-    const GenWs& w = r.a;
+    const RollWs r = carve_rollout(g, U, N64, 1);
     EG_REQUIRE(ws_bytes >= r.total, EG_ERR_WORKSPACE, "eg_generator_forward_rollout_ragged: workspace %lld < %lld bytes", (long long)ws_bytes,
                (long long)r.total);
     EG_REQUIRE(eg_aligned16(ws) && eg_aligned16(arena) && eg_aligned16(spec) && (reinterpret_cast<uintptr_t>(plan) & 3u) == 0, EG_ERR_ALIGN,
                "eg_generator_forward_rollout_ragged: 16-byte alignment (plan: 4-byte)");
-    hipStream_t st = (hipStream_t)stream;
-    const EgGeneratorConfig& c = g->cfg;
-    const int F = c.frames, D = c.d_model, N = (int)N64, P_ = c.prior_frames, PD = c.pose_dim;
-    // the working order (longer first, ties by index): the active recordings of every step are its first U_s ranks
+    // the working order (longer first, ties by index): the active recordings of every step are its first U_s ranks, and a recording keeps
+    // its rank, the row of its prior, for its whole life
     std::vector<int32_t> order(U);
     for (int u = 0; u < U; ++u) order[u] = u;
     std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return windows_per[a] > windows_per[b]; });
     bool sorted = true;
     for (int u = 0; u < U; ++u) sorted = sorted && order[u] == u;
-    const bool move = U > 1 && Wmax > 1;        // else step-major and packed recording-major order coincide (slot_row is the identity)
-
-    // ---- phase A, batch N in step-major order (slot (s, rank) after the slots of the steps before it): everything the prior does not reach
-    if (move) {
-        EG_TRY(egi_rows_by_table(spec, P(ws, r.spec), plan, N, (size_t)c.n_mels * c.spec_len, false, st));
-        spec = P(ws, r.spec);
-        if (text_embedding) {
-            EG_TRY(egi_rows_by_table(text, P(ws, r.text), plan, N, (size_t)c.text_len * 2, false, st));
-            text = reinterpret_cast<const int64_t*>(P(ws, r.text));
-        }
-        if (sampled) {
-            EG_TRY(egi_rows_by_table(sampled, P(ws, r.sampled), plan, N, (size_t)F * D, false, st));
-            sampled = P(ws, r.sampled);
-        }
-    }
-    float* txt = move ? P(ws, w.t_out) : text_embedding;
-    float* emo = move || !emotion_feature ? P(ws, w.emo) : emotion_feature;
-    float* sem = move || !semantic_feature ? P(ws, w.sem) : semantic_feature;
-    float* pred = move || !emotion_prediction ? P(ws, w.cls_out) : emotion_prediction;
-    if (text_embedding) EG_TRY(run_text(g, arena, text, txt, w, ws, N, st));
-    EG_TRY(run_audio_tower(g, arena, spec, w, ws, N, st));
-    EG_TRY(run_heads(g, arena, emo, sem, pred, w, ws, N, st));
-    EG_TRY(egi_add(sampled ? sampled : emo, sem, P(ws, w.fus_in), (size_t)N * F * D, D, 0, st));
-    Act enc_out;
-    EG_TRY(run_encoder(g, arena, P(ws, w.fus_in), enc_out, w, ws, N, st));
+    // U == 1 or Wmax == 1: step-major and packed recording-major order coincide (slot_row is the identity)
+    const RollPlan p = {U, 1, (int)N64, Wmax, plan, windows_per, order.data(), U == 1 || Wmax == 1, sorted};
+    hipStream_t st = (hipStream_t)stream;
     float* kv[8];
-    for (int l = 0; l < c.n_layers; ++l) {
-        kv[l] = P(ws, r.kv[l]);
-        EG_TRY(lin(g, arena, g->dec_attn[l].kv, enc_out, 0, act(kv[l], 2 * D), true, N * F, 0, nullptr, 0, st));
-    }
-    if (move) {     // per-window outputs back to the caller's packed recording-major rows
-        if (text_embedding) EG_TRY(egi_rows_by_table(txt, text_embedding, plan, N, (size_t)c.text_len * 512, true, st));
-        if (emotion_feature) EG_TRY(egi_rows_by_table(emo, emotion_feature, plan, N, (size_t)F * D, true, st));
-        if (semantic_feature) EG_TRY(egi_rows_by_table(sem, semantic_feature, plan, N, (size_t)F * D, true, st));
-        if (emotion_prediction) EG_TRY(egi_rows_by_table(pred, emotion_prediction, plan, N, 8, true, st));
-    }
-
-    // ---- phase B, Wmax dependent steps; step s runs the U_s recordings with W_u > s.  Priors ping-pong between two buffers indexed by
-    // rank, so a recording keeps its slot for its whole life; the seed poses are brought into rank order first unless they are in it.
-    const float* prior = seed_pose;
-    if (!sorted) {
-        EG_TRY(egi_rows_by_table(seed_pose, P(ws, r.prior[1]), plan + N, U, (size_t)P_ * PD, false, st));
-        prior = P(ws, r.prior[1]);
-    }
-    const Act prior_enc = act(P(ws, w.prior_enc), D, P(ws, w.im_p[1]), D);
-    int active = U;
-    size_t slot = 0;
-    for (int s = 0; s < Wmax; ++s) {
-        while (active > 0 && windows_per[order[active - 1]] <= s) --active;
-        EG_TRY(run_prior(g, arena, prior, w, ws, active, st));
-        float* step_kv[8];
-        for (int l = 0; l < c.n_layers; ++l) step_kv[l] = kv[l] + slot * F * 2 * D;
-        EG_TRY(run_decoder(g, arena, prior_enc, Act(), step_kv, P(ws, w.pose), w, ws, active, st));
-        float* next = P(ws, r.prior[s & 1]);
-        EG_TRY(egi_rollout_handoff_ragged(P(ws, w.pose), prior, alpha, track, windows, next, plan, N, U, active, Wmax, s, F, P_, PD, st));
-        prior = next;
-        slot += (size_t)active;
-    }
-    return EG_OK;
+    EG_TRY(rollout_phase_a(g, arena, p, r, ws, spec, text, sampled, emotion_prediction, emotion_feature, semantic_feature, text_embedding, kv, st));
+    return rollout_phase_b(g, arena, p, r, ws, kv, seed_pose, alpha, track, windows, st);
 }
 
 // ---- streaming: a device-resident session (audio ring, prior, counters) and a step whose launches do not depend on the step index -----

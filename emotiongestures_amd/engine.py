@@ -170,7 +170,48 @@ class GeneratorEngine:
                                                      _ptr(pose), _ptr(ws), ws_bytes, _stream(dev)), "eg_generator_forward_draws")
         return pose
 
-    # ---- long-form synthesis ----
+    # ---- long-form synthesis: what the three roll-out calls share ----
+    def _loaded(self, method: str):
+        """The weights' device; `method` names the caller in the error."""
+        if self.arena is None:
+            raise L.EgError(f"GeneratorEngine.{method} before load_weights")
+        return self.arena.device
+
+    @staticmethod
+    def _rollout_tensors(spec, text, seed_pose, sampled, alpha):
+        return (_need_cuda(spec, "spec"), _need_cuda(text, "text", torch.int64), _need_cuda(seed_pose, "seed_pose"),
+                None if sampled is None else _need_cuda(sampled, "sampled"), None if alpha is None else _need_cuda(alpha, "alpha"))
+
+    def _rollout_workspace(self, kind: str, fn: str, sizes: dict, slot, dev):
+        """(workspace, bytes) of one roll-out call: `fn` is the C query, `sizes` its named arguments, (kind, *sizes[, slot]) the slot key."""
+        ws_bytes = getattr(self._lib, fn)(self._h, *sizes.values())
+        if ws_bytes <= 0:
+            raise L.EgError(f"{fn}: unsupported " + " ".join(f"{k}={v}" for k, v in sizes.items()))
+        key = (kind, *sizes.values())
+        return self._workspace(key if slot == 0 else key + (slot,), ws_bytes, dev), ws_bytes
+
+    def _rollout_outputs(self, dev, track_lead, steps, windows_lead, clip_lead, want_windows, want_aux, track=None):
+        """The output dictionary: track [*track_lead, steps*(F-P)+P, D], windows [*windows_lead, F, D], per-window outputs [*clip_lead, ...]."""
+        c = self.cfg
+        T = steps * (c.frames - c.prior_frames) + c.prior_frames
+        out = {"track": torch.empty(*track_lead, T, c.pose_dim, device=dev) if track is None else track,
+               "emotion_prediction": torch.empty(*clip_lead, 8, device=dev)}
+        if want_windows:
+            out["windows"] = torch.empty(*windows_lead, c.frames, c.pose_dim, device=dev)
+        if want_aux:
+            out["emotion_feature"] = torch.empty(*clip_lead, c.frames, c.d_model, device=dev)
+            out["semantic_feature"] = torch.empty(*clip_lead, c.frames, c.d_model, device=dev)
+            out["text_embedding"] = torch.empty(*clip_lead, c.text_len, 512, device=dev)
+        return out
+
+    def _rollout_call(self, fn: str, sizes, tensors, out, ws, ws_bytes, dev):
+        """The C call: handle, arena, the call's own size / plan arguments, then what every roll-out entry takes in the same order."""
+        L.check(getattr(self._lib, fn)(
+            self._h, _ptr(self.arena), *sizes, *(_ptr(t) for t in tensors), _ptr(out["track"]), _ptr(out.get("windows")),
+            _ptr(out["emotion_prediction"]), _ptr(out.get("emotion_feature")), _ptr(out.get("semantic_feature")), _ptr(out.get("text_embedding")),
+            _ptr(ws), ws_bytes, _stream(dev)), fn)
+        return out
+
     def _rollout_args(self, spec, text, seed_pose, sampled, alpha):
         """Shape contract of forward_rollout (checked before anything touches the device); returns (U, W)."""
         c = self.cfg
@@ -199,31 +240,11 @@ class GeneratorEngine:
         (alpha[j] = (j+1)/(P+1)).  Returns a dict: track [U, W*(F-P)+P, D], emotion_prediction [U,W,8], windows [U,W,F,D] with
         want_windows, emotion_feature / semantic_feature [U,W,F,d_model] and text_embedding [U,W,text_len,512] with want_aux."""
         U, W = self._rollout_args(spec, text, seed_pose, sampled, alpha)
-        if self.arena is None:
-            raise L.EgError("GeneratorEngine.forward_rollout before load_weights")
-        dev = self.arena.device
-        c = self.cfg
-        spec, text, seed_pose = _need_cuda(spec, "spec"), _need_cuda(text, "text", torch.int64), _need_cuda(seed_pose, "seed_pose")
-        sampled = None if sampled is None else _need_cuda(sampled, "sampled")
-        alpha = None if alpha is None else _need_cuda(alpha, "alpha")
-        ws_bytes = self._lib.eg_generator_rollout_workspace_bytes(self._h, U, W)
-        if ws_bytes <= 0:
-            raise L.EgError(f"eg_generator_rollout_workspace_bytes: unsupported U={U} W={W}")
-        ws = self._workspace(("rollout", U, W) if slot == 0 else ("rollout", U, W, slot), ws_bytes, dev)
-        F, H = c.frames, c.frames - c.prior_frames
-        out = {"track": torch.empty(U, W * H + c.prior_frames, c.pose_dim, device=dev),
-               "emotion_prediction": torch.empty(U, W, 8, device=dev)}
-        if want_windows:
-            out["windows"] = torch.empty(U, W, F, c.pose_dim, device=dev)
-        if want_aux:
-            out["emotion_feature"] = torch.empty(U, W, F, c.d_model, device=dev)
-            out["semantic_feature"] = torch.empty(U, W, F, c.d_model, device=dev)
-            out["text_embedding"] = torch.empty(U, W, c.text_len, 512, device=dev)
-        L.check(self._lib.eg_generator_forward_rollout(
-            self._h, _ptr(self.arena), U, W, _ptr(spec), _ptr(text), _ptr(seed_pose), _ptr(sampled), _ptr(alpha), _ptr(out["track"]),
-            _ptr(out.get("windows")), _ptr(out["emotion_prediction"]), _ptr(out.get("emotion_feature")), _ptr(out.get("semantic_feature")),
-            _ptr(out.get("text_embedding")), _ptr(ws), ws_bytes, _stream(dev)), "eg_generator_forward_rollout")
-        return out
+        dev = self._loaded("forward_rollout")
+        tensors = self._rollout_tensors(spec, text, seed_pose, sampled, alpha)
+        ws, ws_bytes = self._rollout_workspace("rollout", "eg_generator_rollout_workspace_bytes", {"U": U, "W": W}, slot, dev)
+        out = self._rollout_outputs(dev, (U,), W, (U, W), (U, W), want_windows, want_aux)
+        return self._rollout_call("eg_generator_forward_rollout", (U, W), tensors, out, ws, ws_bytes, dev)
 
     # ---- diverse roll-out: several sampled tracks per recording ----
     def _rollout_draws_args(self, spec, text, seed_pose, sampled, alpha):
@@ -249,31 +270,11 @@ class GeneratorEngine:
         Returns a dict: track [U, R, W*(F-P)+P, D], emotion_prediction [U,W,8] (independent of the draw), windows [U,R,W,F,D] with
         want_windows, emotion_feature / semantic_feature [U,W,F,d_model] and text_embedding [U,W,text_len,512] with want_aux."""
         U, W, R = self._rollout_draws_args(spec, text, seed_pose, sampled, alpha)
-        if self.arena is None:
-            raise L.EgError("GeneratorEngine.forward_rollout_draws before load_weights")
-        dev = self.arena.device
-        c = self.cfg
-        spec, text, seed_pose = _need_cuda(spec, "spec"), _need_cuda(text, "text", torch.int64), _need_cuda(seed_pose, "seed_pose")
-        sampled = _need_cuda(sampled, "sampled")
-        alpha = None if alpha is None else _need_cuda(alpha, "alpha")
-        ws_bytes = self._lib.eg_generator_rollout_draws_workspace_bytes(self._h, U, W, R)
-        if ws_bytes <= 0:
-            raise L.EgError(f"eg_generator_rollout_draws_workspace_bytes: unsupported U={U} W={W} R={R}")
-        ws = self._workspace(("rollout_draws", U, W, R) if slot == 0 else ("rollout_draws", U, W, R, slot), ws_bytes, dev)
-        F, H = c.frames, c.frames - c.prior_frames
-        out = {"track": torch.empty(U, R, W * H + c.prior_frames, c.pose_dim, device=dev),
-               "emotion_prediction": torch.empty(U, W, 8, device=dev)}
-        if want_windows:
-            out["windows"] = torch.empty(U, R, W, F, c.pose_dim, device=dev)
-        if want_aux:
-            out["emotion_feature"] = torch.empty(U, W, F, c.d_model, device=dev)
-            out["semantic_feature"] = torch.empty(U, W, F, c.d_model, device=dev)
-            out["text_embedding"] = torch.empty(U, W, c.text_len, 512, device=dev)
-        L.check(self._lib.eg_generator_forward_rollout_draws(
-            self._h, _ptr(self.arena), U, W, R, _ptr(spec), _ptr(text), _ptr(seed_pose), _ptr(sampled), _ptr(alpha), _ptr(out["track"]),
-            _ptr(out.get("windows")), _ptr(out["emotion_prediction"]), _ptr(out.get("emotion_feature")), _ptr(out.get("semantic_feature")),
-            _ptr(out.get("text_embedding")), _ptr(ws), ws_bytes, _stream(dev)), "eg_generator_forward_rollout_draws")
-        return out
+        dev = self._loaded("forward_rollout_draws")
+        tensors = self._rollout_tensors(spec, text, seed_pose, sampled, alpha)
+        ws, ws_bytes = self._rollout_workspace("rollout_draws", "eg_generator_rollout_draws_workspace_bytes", {"U": U, "W": W, "R": R}, slot, dev)
+        out = self._rollout_outputs(dev, (U, R), W, (U, R, W), (U, W), want_windows, want_aux)
+        return self._rollout_call("eg_generator_forward_rollout_draws", (U, W, R), tensors, out, ws, ws_bytes, dev)
 
     # ---- ragged roll-out: recordings with their own window counts ----
     def _rollout_ragged_args(self, spec, text, seed_pose, windows_per, sampled, alpha):
@@ -352,35 +353,16 @@ class GeneratorEngine:
         if track is not None and (tuple(track.shape) != (U, T, self.cfg.pose_dim) or track.dtype != torch.float32 or not track.is_contiguous()
                                   or not track.is_cuda):
             raise L.EgError(f"track: need a contiguous float32 GPU tensor [{U},{T},{self.cfg.pose_dim}]")
-        if self.arena is None:
-            raise L.EgError("GeneratorEngine.forward_rollout_ragged before load_weights")
-        dev = self.arena.device
+        dev = self._loaded("forward_rollout_ragged")
         c = self.cfg
-        spec, text, seed_pose = _need_cuda(spec, "spec"), _need_cuda(text, "text", torch.int64), _need_cuda(seed_pose, "seed_pose")
-        sampled = None if sampled is None else _need_cuda(sampled, "sampled")
-        alpha = None if alpha is None else _need_cuda(alpha, "alpha")
+        tensors = self._rollout_tensors(spec, text, seed_pose, sampled, alpha)
         plan = self._ragged_plan(wp, dev)
-        ws_bytes = self._lib.eg_generator_rollout_ragged_workspace_bytes(self._h, U, N)
-        if ws_bytes <= 0:
-            raise L.EgError(f"eg_generator_rollout_ragged_workspace_bytes: unsupported U={U} N={N}")
-        ws = self._workspace(("ragged", U, N) if slot == 0 else ("ragged", U, N, slot), ws_bytes, dev)
-        F, H, Wmax = c.frames, c.frames - c.prior_frames, max(wp)
-        out = {"track": torch.empty(U, T, c.pose_dim, device=dev) if track is None else track,
-               "track_frames": torch.tensor([v * H + c.prior_frames for v in wp], dtype=torch.int64),
-               "window_offsets": torch.from_numpy(plan["offsets"].astype("int64")),
-               "emotion_prediction": torch.empty(N, 8, device=dev)}
-        if want_windows:
-            out["windows"] = torch.empty(N, F, c.pose_dim, device=dev)
-        if want_aux:
-            out["emotion_feature"] = torch.empty(N, F, c.d_model, device=dev)
-            out["semantic_feature"] = torch.empty(N, F, c.d_model, device=dev)
-            out["text_embedding"] = torch.empty(N, c.text_len, 512, device=dev)
-        L.check(self._lib.eg_generator_forward_rollout_ragged(
-            self._h, _ptr(self.arena), U, plan["windows_per_c"], _ptr(plan["table_dev"]), _ptr(spec), _ptr(text), _ptr(seed_pose), _ptr(sampled),
-            _ptr(alpha), _ptr(out["track"]), _ptr(out.get("windows")), _ptr(out["emotion_prediction"]), _ptr(out.get("emotion_feature")),
-            _ptr(out.get("semantic_feature")), _ptr(out.get("text_embedding")), _ptr(ws), ws_bytes, _stream(dev)),
-            "eg_generator_forward_rollout_ragged")
-        return out
+        ws, ws_bytes = self._rollout_workspace("ragged", "eg_generator_rollout_ragged_workspace_bytes", {"U": U, "N": N}, slot, dev)
+        out = self._rollout_outputs(dev, (U,), max(wp), (N,), (N,), want_windows, want_aux, track)
+        out["track_frames"] = torch.tensor([v * (c.frames - c.prior_frames) + c.prior_frames for v in wp], dtype=torch.int64)
+        out["window_offsets"] = torch.from_numpy(plan["offsets"].astype("int64"))
+        return self._rollout_call("eg_generator_forward_rollout_ragged", (U, plan["windows_per_c"], _ptr(plan["table_dev"])), tensors, out, ws,
+                                  ws_bytes, dev)
 
     # ---- streaming synthesis (a session's state buffer is owned by the caller: emotiongestures_amd.streaming.GestureStream) ----
     def _stream_geometry(self, rows, hop_samples, n_samples):

@@ -490,7 +490,6 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     ``diversity=fgd`` (an eval-mode ``MLP_Reconstruct``; with ``draws=R``, R >= 2): adds ``"take_distance"`` ``[U, R, R]`` and
     ``"take_diversity"`` ``[U]`` (fp64), the pairwise distances of the returned takes of every recording in FGD feature space and their mean
     (takes.take_diversity with ``span = frames``: the unit of the clip metric ``calculate_diversity`` on one generator window)."""
-    from .engine import MelFrontEnd
     gen, vae = models
     _eval_only(gen)
     if beat and seed_pose.shape[-1] < 174:
@@ -512,17 +511,40 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
         raise L.EgError(f"audio shape {tuple(audio.shape)} != (U, total_samples)")
     U = audio.shape[0]
     if lengths is not None:
-        out = _synthesize_ragged(eng, vae, audio, lengths, text, seed_pose, labels, hop_samples, n_samples, z, alpha, fps, sample_rate,
-                                 want_windows, want_aux, mel)
-        if beat:
-            _add_beat(out, audio, c, fps, lengths, out["windows_per"])
-        return out
-    W = int(text.shape[1]) if windows is None and text.dim() == 3 else windows
-    if W is None or W < 1:
-        raise L.EgError(f"windows={W} (need >= 1): text must be [U, W, {c.text_len}] or `windows` given")
+        out, spec, wp = _synthesize_ragged(eng, vae, audio, lengths, text, seed_pose, labels, z, alpha, want_windows, want_aux,
+                                           *_front_end(c, audio, hop_samples, n_samples, fps, sample_rate, mel))
+        out["windows_per"] = wp
+    else:
+        W = int(text.shape[1]) if windows is None and text.dim() == 3 else windows
+        if W is None or W < 1:
+            raise L.EgError(f"windows={W} (need >= 1): text must be [U, W, {c.text_len}] or `windows` given")
+        out, spec = _synthesize_rect(eng, vae, audio, W, text, seed_pose, labels, z, alpha, want_windows, want_aux, draws,
+                                     *_front_end(c, audio, hop_samples, n_samples, fps, sample_rate, mel))
+        wp = [W] * U
+    out["spec"] = spec
+    if beat:
+        from .beat import beat_alignment_tracks
+        H = c.frames - c.prior_frames
+        with torch.no_grad():
+            out["beat"] = beat_alignment_tracks(audio, out["track"], lengths=lengths, frames=[int(w) * H + c.prior_frames for w in wp], fps=fps)
+    if diversity is not None:
+        with torch.no_grad():
+            td = take_diversity(diversity, out["track"], span=c.frames)
+        out["take_distance"], out["take_diversity"] = td["distance"], td["diversity"]
+    return out
+
+
+def _front_end(c, audio, hop_samples, n_samples, fps, sample_rate, mel):
+    """(hop, n, mel): the windows' hop and length in samples (defaults from the generator's geometry) and the mel front-end."""
+    from .engine import MelFrontEnd
     hop = int(round((c.frames - c.prior_frames) * sample_rate / fps)) if hop_samples is None else int(hop_samples)
     n = (c.spec_len - 1) * 512 if n_samples is None else int(n_samples)
-    mel = MelFrontEnd(audio.device) if mel is None else mel
+    return hop, n, MelFrontEnd(audio.device) if mel is None else mel
+
+
+def _synthesize_rect(eng, vae, audio, W, text, seed_pose, labels, z, alpha, want_windows, want_aux, draws, hop, n, mel):
+    c = eng.cfg
+    U = audio.shape[0]
     with torch.no_grad():
         spec = mel.windows(audio, W, hop, n, out_frames=c.spec_len)
         if draws is not None:
@@ -541,14 +563,7 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
             elif tuple(z.shape) != (U, R, W, 32):
                 raise L.EgError(f"z shape {tuple(z.shape)} != ({U},{R},{W},32)")
             sampled = vae.sample(lab.reshape(U * R * W, 8).contiguous(), z=z.reshape(U * R * W, 32)).view(U, R, W, c.frames, c.d_model)
-            out = eng.forward_rollout_draws(spec, text, seed_pose, sampled, alpha=alpha, want_windows=want_windows, want_aux=want_aux)
-            out["spec"] = spec
-            if beat:
-                _add_beat(out, audio, c, fps, None, [W] * U)
-            if diversity is not None:
-                td = take_diversity(diversity, out["track"], span=c.frames)
-                out["take_distance"], out["take_diversity"] = td["distance"], td["diversity"]
-            return out
+            return eng.forward_rollout_draws(spec, text, seed_pose, sampled, alpha=alpha, want_windows=want_windows, want_aux=want_aux), spec
         sampled = None
         if vae is not None:
             if labels is None:
@@ -556,30 +571,12 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
             lab = labels.to(audio.device)
             lab = (lab[:, None, :].expand(U, W, 8) if lab.dim() == 2 else lab).reshape(U * W, 8).contiguous()
             sampled = vae.sample(lab, z=None if z is None else z.reshape(U * W, 32)).view(U, W, c.frames, c.d_model)
-        out = eng.forward_rollout(spec, text, seed_pose, sampled, alpha=alpha, want_windows=want_windows, want_aux=want_aux)
-    out["spec"] = spec
-    if beat:
-        _add_beat(out, audio, c, fps, None, [W] * U)
-    return out
+        return eng.forward_rollout(spec, text, seed_pose, sampled, alpha=alpha, want_windows=want_windows, want_aux=want_aux), spec
 
 
-def _add_beat(out, audio, c, fps, lengths, windows_per):
-    """``out["beat"]``: the beat-alignment score of the roll-out's tracks against the recordings' own audio."""
-    from .beat import beat_alignment_tracks
-    H = c.frames - c.prior_frames
-    frames = [int(w) * H + c.prior_frames for w in windows_per]
-    with torch.no_grad():
-        out["beat"] = beat_alignment_tracks(audio, out["track"], lengths=lengths, frames=frames, fps=fps)
-
-
-def _synthesize_ragged(eng, vae, audio, lengths, text, seed_pose, labels, hop_samples, n_samples, z, alpha, fps, sample_rate, want_windows,
-                       want_aux, mel):
-    from .engine import MelFrontEnd
+def _synthesize_ragged(eng, vae, audio, lengths, text, seed_pose, labels, z, alpha, want_windows, want_aux, hop, n, mel):
     c = eng.cfg
     U = audio.shape[0]
-    hop = int(round((c.frames - c.prior_frames) * sample_rate / fps)) if hop_samples is None else int(hop_samples)
-    n = (c.spec_len - 1) * 512 if n_samples is None else int(n_samples)
-    mel = MelFrontEnd(audio.device) if mel is None else mel
     with torch.no_grad():
         spec, wp = mel.windows_ragged(audio, lengths, hop, n, out_frames=c.spec_len)
         N = sum(wp)
@@ -601,9 +598,7 @@ def _synthesize_ragged(eng, vae, audio, lengths, text, seed_pose, labels, hop_sa
             sampled = vae.sample(lab, z=z)
         out = eng.forward_rollout_ragged(spec, packed(text, 2, "text"), seed_pose, wp, sampled, alpha=alpha, want_windows=want_windows,
                                          want_aux=want_aux)
-    out["spec"] = spec
-    out["windows_per"] = list(wp)
-    return out
+    return out, spec, list(wp)
 
 
 def open_stream(models, rows: int, seed_pose: torch.Tensor, *, mel=None, **kw):

@@ -82,8 +82,9 @@ def main():
             for g in (gr, ga, gb):
                 g.replay()
         torch.cuda.synchronize()
-        legs.append((name, wp, groups, (gr, o_r, lr), (ga, o_a, la), (gb, o_b, lb)))
-    for name, wp, groups, (gr, o_r, lr), (ga, o_a, la), (gb, o_b, lb) in legs:
+        # the graphs read the inputs where they lie: keep them alive (the next case's capture empties the allocator's cache)
+        legs.append((name, wp, groups, (gr, o_r, lr), (ga, o_a, la), (gb, o_b, lb), (pad, packed, seed_pose, grouped)))
+    for name, wp, groups, (gr, o_r, lr), (ga, o_a, la), (gb, o_b, lb), _inputs in legs:
         tr, ta, tb = [], [], []
         for _ in range(a.rounds):
             tr.append(window_ms(gr, a.iters))
