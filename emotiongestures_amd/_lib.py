@@ -15,7 +15,7 @@ EG_PREC_F32, EG_PREC_BF16X3, EG_PREC_BF16 = 0, 1, 2
 PRECISIONS = {"f32": EG_PREC_F32, "fp32": EG_PREC_F32, "bf16x3": EG_PREC_BF16X3, "bf16": EG_PREC_BF16}
 
 (PACK_RAW, PACK_LINEAR, PACK_VEC_PAD, PACK_CONV3X3, PACK_BN_SCALE, PACK_BN_SHIFT, PACK_CONV1X1, PACK_STEM,
- PACK_WN_TAP, PACK_CONV1D, PACK_POS_TABLE, PACK_LINEAR_T, PACK_LINEAR_FOLD, PACK_BIAS_FOLD, PACK_CONV1X1_BF16) = range(15)
+ PACK_WN_TAP, PACK_CONV1D, PACK_POS_TABLE, PACK_LINEAR_T, PACK_LINEAR_FOLD, PACK_BIAS_FOLD, PACK_CONV1X1_BF16, PACK_WN_TAPS) = range(16)
 
 
 class EgError(RuntimeError):
@@ -126,6 +126,7 @@ SIGNATURES = {
     "eg_linear": (C.c_int, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "eg_split_tiles": (C.c_int, [_P, _I, _I, _I, _P, _P]),
     "eg_linear_presplit": (C.c_int, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "eg_linear_presplit_causal": (C.c_int, [_P, _I, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "eg_linear_splitk": (C.c_int, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "eg_layernorm": (C.c_int, [_P, _P, _P, _P, _I, _I, C.c_float, _P]),
     "eg_attention": (C.c_int, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
@@ -136,6 +137,7 @@ SIGNATURES = {
     "eg_positionwise_ffn": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P]),
     "eg_tcn_forward": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P]),
     "eg_add_rows": (C.c_int, [_P, _P, _P, _L, _I, _I, _P]),
+    "eg_add_rows_split": (C.c_int, [_P, _P, _P, _P, _L, _I, _I, _P]),
     "eg_conv3x3_packed_floats": (_L, [_I, _I]),
     "eg_profile_enable": (C.c_int, [_I]),
     "eg_profile_disable": (C.c_int, []),

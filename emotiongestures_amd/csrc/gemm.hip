@@ -22,6 +22,11 @@ struct GemmArgs {
     unsigned short* yimg = nullptr;
     int yKO = 0, yoct0 = 0;
     int xoct0 = 0;              // pre-split X: first octet of this product's K range inside the X images
+    // pre-split X, causal two-tap product (one K chain over [tap 0 on rows r - xs_shift | tap 1 on rows r]): the first xs_steps 32-deep K steps read
+    // image row r - xs_shift of octets xoct0.., zero where (r mod xs_period) < xs_shift; the steps after them read row r of the same octets.
+    // xzero: a cleared line of xs_steps * 4 * 64 bf8 slots owned by the caller (the kernels keep none).
+    int xs_steps = 0, xs_shift = 0, xs_period = 1;
+    const bf8* xzero = nullptr;
     // training epilogue (eg_linear_ex): ReLU-backward gate and nn.Dropout on the product, both before the residual add
     const float* gate = nullptr; int ldg = 0;       // v = gate[m][n] > 0 ? v : 0
     EgDropout drop;                                 // thr = 0: off; counter = offset + m * N + n (the flat index eg_dropout uses on a [M, N] tensor)
@@ -476,7 +481,9 @@ int launch_glds(const GemmArgs& a, int splits, hipStream_t st) {
 // 4 -> 128 x 64 (two 64-row X image tiles; the wave grid stays 2 x 2, a wave owns 64 x 32).  The 64 x 64 tile streams 16 KB of operands
 // from L2 into LDS per 48 MFMAs; the 128 x 64 tile 24 KB per 96 (3/4 of the operand stream per MFMA, 6 instead of 4 LDS-DMA pieces and
 // 12 instead of 8 ds_read_b128 per wave for twice the MFMAs), at half the workgroups.
-template <int TERMS, int BK, int RING, int WM = 2, bool TRAIN = false>
+// SHIFT: the causal two-tap product (GemmArgs::xs_*): the copy addresses of X are per lane already (lane = image row), so a lane of a shifted step
+// points at row r - xs_shift -- often in the previous 64-row image tile -- or at the caller's zero line; computed once, a K step adds a constant.
+template <int TERMS, int BK, int RING, int WM = 2, bool TRAIN = false, bool SHIFT = false>
 __global__ __launch_bounds__(256, (WM == 2 || RING <= 3) ? 2 : 1) void gemm_presplit_kernel(GemmArgs a, const bf8* __restrict__ xhi, const bf8* __restrict__ xlo, int xKO) {
     constexpr int NIMG = (TERMS == 3) ? 2 : 1;
     constexpr int KG = BK / 32;                                           // MFMA k-groups per step
@@ -501,6 +508,15 @@ __global__ __launch_bounds__(256, (WM == 2 || RING <= 3) ? 2 : 1) void gemm_pres
     const int mt_last = ((a.M + 63) >> 6) - 1;
     // X image tile t of this workgroup (a 128-row workgroup past an odd tile count re-reads the last tile: those rows are never stored)
     const int xt0 = bx * TM, xt1 = min(bx * TM + TM - 1, mt_last);
+    static_assert(!SHIFT || (BK == 32 && WM == 2), "shifted X: 64 x 64 tile, 32-deep steps");
+    const bf8 *sxh = nullptr, *sxl = nullptr;                             // SHIFT: this lane's source of octet `wave` of the shifted segment
+    if constexpr (SHIFT) {
+        const int m = xt0 * 64 + lane, ms = m - a.xs_shift;
+        const bool ok = (m % a.xs_period) >= a.xs_shift;                  // then ms >= 0
+        const size_t gs = ((size_t)(ms >> 6) * xKO + a.xoct0 + wave) * 64 + (ms & 63);
+        sxh = ok ? xhi + gs : a.xzero + wave * 64 + lane;
+        sxl = ok ? xlo + gs : a.xzero + wave * 64 + lane;
+    }
     auto issue = [&](int step, int slot) {
         const int ko = (kbeg + step * BK) >> 3;
         bf8* S = lds + slot * SLOT;
@@ -509,11 +525,15 @@ __global__ __launch_bounds__(256, (WM == 2 || RING <= 3) ? 2 : 1) void gemm_pres
             const int d = (p * 4 + wave) * 64;
 #pragma unroll
             for (int t = 0; t < TM; ++t) {
-                const size_t gx = ((size_t)(t ? xt1 : xt0) * xKO + a.xoct0 + ko + p * 4 + wave) * 64 + lane;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xhi + gx),
+                const int xo = (SHIFT && step >= a.xs_steps) ? ko - a.xs_steps * 4 : ko;       // second segment: the same X octets again
+                const size_t gx = ((size_t)(t ? xt1 : xt0) * xKO + a.xoct0 + xo + p * 4 + wave) * 64 + lane;
+                const bf8* ph = xhi + gx;
+                const bf8* pl = xlo + gx;
+                if (SHIFT && step < a.xs_steps) { ph = sxh + (size_t)step * 256; pl = sxl + (size_t)step * 256; }
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)ph,
                                                  (__attribute__((address_space(3))) void*)(S + t * NIMG * IMG + d), 16, 0, 0);
                 if (TERMS == 3)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xlo + gx),
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pl,
                                                      (__attribute__((address_space(3))) void*)(S + t * NIMG * IMG + IMG + d), 16, 0, 0);
             }
             const size_t gw = ((size_t)by * KO + ko + p * 4 + wave) * 64 + lane;
@@ -593,7 +613,7 @@ __global__ __launch_bounds__(256, (WM == 2 || RING <= 3) ? 2 : 1) void gemm_pres
         wg_barrier();
     };
     int s0 = 0;
-    if constexpr (BK == 32) {
+    if constexpr (BK == 32 && !SHIFT) {
         // Steady state, RING steps per iteration: every step issues a copy (group s+RING-1), so there are no conditionals, the
         // ring slots are compile-time constants and the source addresses are running pointers (one 64-bit add each per
         // step).  A copy has RING-2 steps to land.
@@ -644,11 +664,11 @@ __global__ __launch_bounds__(256, (WM == 2 || RING <= 3) ? 2 : 1) void gemm_pres
     gemm_epilogue<WM, 2, TRAIN>(a, acc, m0 + ((TM == 1) ? wm : wmt * 64) + li, n0 + wn + kq * 4);
 }
 
-template <int TERMS, int BK, int RING, int WM = 2, bool TRAIN = false>
+template <int TERMS, int BK, int RING, int WM = 2, bool TRAIN = false, bool SHIFT = false>
 int launch_presplit(const GemmArgs& a, const bf8* xhi, const bf8* xlo, int xko, dim3 grid, hipStream_t st) {
     constexpr int NIMG = (TERMS == 3) ? 2 : 1;
     constexpr size_t LDS_BYTES = (size_t)RING * (WM / 2 + 1) * NIMG * (BK / 32) * 4 * 64 * 16;
-    auto kern = gemm_presplit_kernel<TERMS, BK, RING, WM, TRAIN>;
+    auto kern = gemm_presplit_kernel<TERMS, BK, RING, WM, TRAIN, SHIFT>;
     if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS_BYTES, "gemm_presplit")) return rc;
     if (WM == 4) grid.x = (grid.x + 1) / 2;          // grid.x arrives as the number of 64-row tiles
     hipLaunchKernelGGL(kern, grid, dim3(256), LDS_BYTES, st, a, xhi, xlo, xko);
@@ -662,7 +682,7 @@ int launch_presplit(const GemmArgs& a, const bf8* xhi, const bf8* xlo, int xko, 
 // workgroup tile 128 x 128 = two 64-row image tiles of X and of W, 32 KB per 32-deep step, 3-slot ring (96 KB: one workgroup
 // = two waves per SIMD).  Schedule as in the convolution: one barrier per step between the two MFMA halves, counted vmcnt
 // (the copy of step s+2 stays in flight), fragments of step s+1 read after the barrier under the second half.
-template <int TERMS, int RING = 3, bool TRAIN = false>
+template <int TERMS, int RING = 3, bool TRAIN = false, bool SHIFT = false>
 __global__ __launch_bounds__(512, 1) void gemm_presplit128_kernel(GemmArgs a, const bf8* __restrict__ xhi, const bf8* __restrict__ xlo, int xKO,
                                                                   int m_tiles, int n_tiles) {
     constexpr int NIMG = (TERMS == 3) ? 2 : 1;
@@ -681,16 +701,31 @@ __global__ __launch_bounds__(512, 1) void gemm_presplit128_kernel(GemmArgs a, co
     // copy role: wave w moves piece w of each image: tile = w>>2, octet = w&3.  A 128-row workgroup whose second 64-row
     // tile does not exist (odd tile counts) re-reads the last tile; those rows / columns are never stored.
     const int pt = wave >> 2, po = wave & 3;
-    const size_t gx = ((size_t)min(bx * 2 + pt, m_tiles - 1) * xKO + a.xoct0 + po) * 64 + lane;
+    const int xtile = min(bx * 2 + pt, m_tiles - 1);
+    const size_t gx = ((size_t)xtile * xKO + a.xoct0 + po) * 64 + lane;
+    const bf8 *sxh = nullptr, *sxl = nullptr;           // SHIFT (see gemm_presplit_kernel): this lane's source in the shifted segment
+    if constexpr (SHIFT) {
+        const int m = xtile * 64 + lane, ms = m - a.xs_shift;
+        const bool ok = (m % a.xs_period) >= a.xs_shift;
+        const size_t gs = ((size_t)(ms >> 6) * xKO + a.xoct0 + po) * 64 + (ms & 63);
+        sxh = ok ? xhi + gs : a.xzero + po * 64 + lane;
+        sxl = ok ? xlo + gs : a.xzero + po * 64 + lane;
+    }
     const size_t gw = ((size_t)min(by * 2 + pt, n_tiles - 1) * KO + po) * 64 + lane;
     const bf8* whi = reinterpret_cast<const bf8*>(a.whi);
     const bf8* wlo = reinterpret_cast<const bf8*>(a.wlo);
     auto issue = [&](int step, int slot) {
         bf8* S = lds + slot * SLOT + wave * 64;
         const size_t o = (size_t)step * 4 * 64;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xhi + gx + o), (__attribute__((address_space(3))) void*)S, 16, 0, 0);
+        const bf8* ph = xhi + gx + o;
+        const bf8* pl = xlo + gx + o;
+        if constexpr (SHIFT) {
+            if (step < a.xs_steps) { ph = sxh + o; pl = sxl + o; }
+            else { ph -= (size_t)a.xs_steps * 256; pl -= (size_t)a.xs_steps * 256; }       // second segment: the same X octets again, plain rows
+        }
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)ph, (__attribute__((address_space(3))) void*)S, 16, 0, 0);
         if (TERMS == 3)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xlo + gx + o), (__attribute__((address_space(3))) void*)(S + OPI), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pl, (__attribute__((address_space(3))) void*)(S + OPI), 16, 0, 0);
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(whi + gw + o), (__attribute__((address_space(3))) void*)(S + OP), 16, 0, 0);
         if (TERMS == 3)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wlo + gw + o), (__attribute__((address_space(3))) void*)(S + OP + OPI), 16, 0, 0);
@@ -757,22 +792,126 @@ __global__ __launch_bounds__(512, 1) void gemm_presplit128_kernel(GemmArgs a, co
     gemm_epilogue<4, 2, TRAIN>(a, acc, m0 + wm * 64 + li, n0 + wn * 32 + kq * 4);
 }
 
-template <int TERMS, int RING = 3, bool TRAIN = false>
+template <int TERMS, int RING = 3, bool TRAIN = false, bool SHIFT = false>
 int launch_presplit128(const GemmArgs& a, const bf8* xhi, const bf8* xlo, int xko, int m_tiles, int n_tiles, hipStream_t st) {
     constexpr int NIMG = (TERMS == 3) ? 2 : 1;
     constexpr size_t LDS_BYTES = (size_t)RING * 2 * NIMG * 8 * 64 * 16;
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-    auto kern = gemm_presplit128_kernel<TERMS, RING, TRAIN>;
+    auto kern = gemm_presplit128_kernel<TERMS, RING, TRAIN, SHIFT>;
     if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS_BYTES, "gemm_presplit128")) return rc;
     dim3 grid(eg_cdiv(m_tiles, 2), eg_cdiv(n_tiles, 2), 1);
     hipLaunchKernelGGL(kern, grid, dim3(512), LDS_BYTES, st, a, xhi, xlo, xko, m_tiles, n_tiles);
     return eg_check_launch("gemm_presplit128");
 }
 
+// ---- 128 x 128 tile with 64-deep steps (EG_GEMM_TILE=128k64) ---------------------------------------------------------------
+// The kernel above spends one barrier, one counted wait and one round of fragment reads per 24 MFMAs of a wave; its K = 512 launches run 16 such
+// steps.  Here a step is 64 deep: 64 KB of operands per slot, a two-slot ring (128 KB, one workgroup per CU as before), 48 MFMAs per wave between
+// two barriers, half the barriers.  The copy of step s+1 is issued at the top of step s and has the whole MFMA phase to land; the wait before
+// the barrier is vmcnt(0) because that copy is the only one in flight.  Per output element the K order and the three split terms are those of
+// the 32-deep kernel: bitwise-equal results.  A K that ends on an odd 32 skips the second half of the last step (its copies re-read the last
+// valid octets).  Inference epilogue, no row shift.
+template <int TERMS>
+__global__ __launch_bounds__(512, 1) void gemm_presplit128_k64_kernel(GemmArgs a, const bf8* __restrict__ xhi, const bf8* __restrict__ xlo, int xKO,
+                                                                      int m_tiles, int n_tiles) {
+    constexpr int NIMG = (TERMS == 3) ? 2 : 1;
+    constexpr int OPI = 2 * 8 * 64;                     // bf8 slots of one image of one operand: [tile(2)][octet(8)][64 rows]
+    constexpr int OP = NIMG * OPI, SLOT = 2 * OP;
+    extern __shared__ __attribute__((aligned(16))) bf8 lds[];
+    const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, kq = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int bx, by;
+    xcd_tile(bx, by);
+    const int m0 = bx * 128, n0 = by * 128;
+    const int wm = wave >> 2, wn = wave & 3;            // wave tile: rows [wm*64, +64), columns [wn*32, +32)
+    const int nsteps = (a.K + 63) / 64, kov = a.K >> 3; // kov: valid octets (K % 32 == 0)
+    const int KO = a.ldw >> 3;
+    const int pt = wave >> 2, po = wave & 3;            // copy role: tile pt, octets po and po + 4 of each image
+    const bf8* px = xhi + ((size_t)min(bx * 2 + pt, m_tiles - 1) * xKO + a.xoct0) * 64 + lane;
+    const bf8* pxl = xlo + ((size_t)min(bx * 2 + pt, m_tiles - 1) * xKO + a.xoct0) * 64 + lane;
+    const bf8* pw = reinterpret_cast<const bf8*>(a.whi) + (size_t)min(by * 2 + pt, n_tiles - 1) * KO * 64 + lane;
+    const bf8* pwl = reinterpret_cast<const bf8*>(a.wlo) + (size_t)min(by * 2 + pt, n_tiles - 1) * KO * 64 + lane;
+    auto issue = [&](int step, int slot) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            bf8* S = lds + slot * SLOT + (pt * 8 + h * 4 + po) * 64;
+            const size_t o = (size_t)min(step * 8 + h * 4 + po, kov - 1) * 64;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(px + o), (__attribute__((address_space(3))) void*)S, 16, 0, 0);
+            if (TERMS == 3)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pxl + o), (__attribute__((address_space(3))) void*)(S + OPI), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pw + o), (__attribute__((address_space(3))) void*)(S + OP), 16, 0, 0);
+            if (TERMS == 3)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pwl + o), (__attribute__((address_space(3))) void*)(S + OP + OPI), 16, 0, 0);
+        }
+    };
+    struct Frags { bf8 xh[4], xl[4], wh[2], wl[2]; };
+    auto read_frags = [&](Frags& f, int slot, int g) {
+        const bf8* X = lds + slot * SLOT + (wm * 8 + g * 4 + kq) * 64 + li;
+        const bf8* W = lds + slot * SLOT + OP + ((wn >> 1) * 8 + g * 4 + kq) * 64 + (wn & 1) * 32 + li;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            f.xh[t] = X[t * 16];
+            if (TERMS == 3) f.xl[t] = X[OPI + t * 16];
+        }
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            f.wh[n] = W[n * 16];
+            if (TERMS == 3) f.wl[n] = W[OPI + n * 16];
+        }
+    };
+    f4 acc[4][2];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int n = 0; n < 2; ++n) acc[t][n] = (f4){0.f, 0.f, 0.f, 0.f};
+    auto mfma_group = [&](const Frags& f) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+                if (TERMS == 3) {
+                    acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wl[n], f.xh[t], acc[t][n], 0, 0, 0);
+                    acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wh[n], f.xl[t], acc[t][n], 0, 0, 0);
+                }
+                acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wh[n], f.xh[t], acc[t][n], 0, 0, 0);
+            }
+    };
+    issue(0, 0);
+    wait_vmcnt_imm<0>();
+    wg_barrier();
+#pragma unroll 1
+    for (int s = 0; s < nsteps; ++s) {
+        const int cur = s & 1;
+        if (s + 1 < nsteps) issue(s + 1, cur ^ 1);      // the other slot: every wave finished reading it before the barrier that ended step s - 1
+        Frags f0, f1;
+        read_frags(f0, cur, 0);
+        read_frags(f1, cur, 1);
+        mfma_group(f0);
+        if (s * 8 + 4 < kov) mfma_group(f1);
+        wait_vmcnt_imm<0>();                            // step s + 1 landed (the only copy in flight)
+        wait_lgkmcnt0();
+        wg_barrier();
+    }
+    gemm_epilogue<4, 2, false>(a, acc, m0 + wm * 64 + li, n0 + wn * 32 + kq * 4);
+}
+
+template <int TERMS>
+int launch_presplit128_k64(const GemmArgs& a, const bf8* xhi, const bf8* xlo, int xko, int m_tiles, int n_tiles, hipStream_t st) {
+    constexpr int NIMG = (TERMS == 3) ? 2 : 1;
+    constexpr size_t LDS_BYTES = (size_t)2 * 2 * NIMG * 16 * 64 * 16;
+    static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+    auto kern = gemm_presplit128_k64_kernel<TERMS>;
+    if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS_BYTES, "gemm_presplit128_k64")) return rc;
+    dim3 grid(eg_cdiv(m_tiles, 2), eg_cdiv(n_tiles, 2), 1);
+    hipLaunchKernelGGL(kern, grid, dim3(512), LDS_BYTES, st, a, xhi, xlo, xko, m_tiles, n_tiles);
+    return eg_check_launch("gemm_presplit128_k64");
+}
+
 // Tile choice of the pre-split product.  Default policy (measured on the 4-lane headline and on tools/bench_ops.py):
 //   the policy of `presplit_tile_default` below (stand-alone: 64 x 64 up to 1024 workgroups; with the caller's shared-chip hint: 128 x 128 from 64).
-// EG_GEMM_TILE overrides it for A/B runs: "64" | "128x64" (4-slot ring, one workgroup per CU) | "128x64r3" (3-slot ring, two per CU) | "128".
-enum PresplitTile { TILE_64 = 0, TILE_128x64 = 1, TILE_128x64_R3 = 2, TILE_128 = 3, TILE_64_R8 = 4, TILE_128x64_R6 = 5, TILE_128_R4 = 6, TILE_AUTO = -1 };
+// EG_GEMM_TILE overrides it for A/B runs: "64" | "128x64" (4-slot ring, one workgroup per CU) | "128x64r3" (3-slot ring, two per CU) | "128" |
+// "128k64" (128 x 128 with 64-deep steps, two slots).
+enum PresplitTile { TILE_64 = 0, TILE_128x64 = 1, TILE_128x64_R3 = 2, TILE_128 = 3, TILE_64_R8 = 4, TILE_128x64_R6 = 5, TILE_128_R4 = 6, TILE_128_K64 = 7, TILE_AUTO = -1 };
 int presplit_tile_override() {          // read per call (a tool / test switches it between launches; a captured graph keeps what it was captured with)
     const char* e = getenv("EG_GEMM_TILE");
     if (!e || !e[0]) return TILE_AUTO;
@@ -783,6 +922,7 @@ int presplit_tile_override() {          // read per call (a tool / test switches
     if (!strcmp(e, "64r8")) return TILE_64_R8;            // deeper rings: more operand bytes in flight per CU (one workgroup per CU)
     if (!strcmp(e, "128x64r6")) return TILE_128x64_R6;
     if (!strcmp(e, "128r4")) return TILE_128_R4;
+    if (!strcmp(e, "128k64")) return TILE_128_K64;
     return TILE_AUTO;
 }
 int presplit_tile_default(int m, int n, int shared_chip) {
@@ -800,20 +940,28 @@ int dispatch_presplit(const GemmArgs& a, const bf8* xhi, const bf8* xlo, int xko
     const int mt = eg_cdiv(a.M, 64), nt = eg_cdiv(a.N, 64);
     int tile = presplit_tile_override();
     if (tile == TILE_AUTO) tile = presplit_tile_default(a.M, a.N, shared_chip);
+    if (a.xs_steps) tile = (tile == TILE_128 || tile == TILE_128_R4 || tile == TILE_128_K64) ? TILE_128 : TILE_64;      // causal two-tap product: the two default tiles
     if (prof) {
-        const int tm = (tile == TILE_64 || tile == TILE_64_R8) ? 1 : 2, tn = (tile == TILE_128 || tile == TILE_128_R4) ? 2 : 1;
+        const int tm = (tile == TILE_64 || tile == TILE_64_R8) ? 1 : 2, tn = (tile == TILE_128 || tile == TILE_128_R4 || tile == TILE_128_K64) ? 2 : 1;
         prof->workgroups(eg_cdiv(mt, tm) * eg_cdiv(nt, tn));
     }
     const bool x3 = precision == EG_PREC_BF16X3;
     dim3 grid(mt, nt, 1);
+    if (a.xs_steps) {
+        if (a.gate || a.drop.thr) { eg_set_error("shifted pre-split product: no training epilogue"); return EG_ERR_UNSUPPORTED; }
+        if (tile == TILE_128)
+            return x3 ? launch_presplit128<3, 3, false, true>(a, xhi, xlo, xko, mt, nt, st) : launch_presplit128<1, 3, false, true>(a, xhi, xlo, xko, mt, nt, st);
+        return x3 ? launch_presplit<3, 32, 4, 2, false, true>(a, xhi, xlo, xko, grid, st) : launch_presplit<1, 32, 4, 2, false, true>(a, xhi, xlo, xko, grid, st);
+    }
     if (a.gate || a.drop.thr) {             // the training epilogue (ReLU-backward gate / Dropout): split-bf16 only, the two default tiles
         if (!x3) { eg_set_error("pre-split product with a training epilogue: bf16x3 only"); return EG_ERR_UNSUPPORTED; }
-        if (tile == TILE_128) return launch_presplit128<3, 3, true>(a, xhi, xlo, xko, mt, nt, st);
+        if (tile == TILE_128 || tile == TILE_128_K64) return launch_presplit128<3, 3, true>(a, xhi, xlo, xko, mt, nt, st);
         return launch_presplit<3, 32, 4, 2, true>(a, xhi, xlo, xko, grid, st);
     }
     switch (tile) {
         case TILE_128: return x3 ? launch_presplit128<3>(a, xhi, xlo, xko, mt, nt, st) : launch_presplit128<1>(a, xhi, xlo, xko, mt, nt, st);
         case TILE_128x64: return x3 ? launch_presplit<3, 32, 4, 4>(a, xhi, xlo, xko, grid, st) : launch_presplit<1, 32, 4, 4>(a, xhi, xlo, xko, grid, st);
+        case TILE_128_K64: return x3 ? launch_presplit128_k64<3>(a, xhi, xlo, xko, mt, nt, st) : launch_presplit128_k64<1>(a, xhi, xlo, xko, mt, nt, st);
         case TILE_128_R4: return x3 ? launch_presplit128<3, 4>(a, xhi, xlo, xko, mt, nt, st) : launch_presplit128<1, 4>(a, xhi, xlo, xko, mt, nt, st);
         case TILE_64_R8: return x3 ? launch_presplit<3, 32, 8>(a, xhi, xlo, xko, grid, st) : launch_presplit<1, 32, 8>(a, xhi, xlo, xko, grid, st);
         case TILE_128x64_R6: return x3 ? launch_presplit<3, 32, 6, 4>(a, xhi, xlo, xko, grid, st) : launch_presplit<1, 32, 6, 4>(a, xhi, xlo, xko, grid, st);
@@ -1041,6 +1189,11 @@ int egi_linear(const EgiLinear& p, hipStream_t st) {
         const bf8* xhi = reinterpret_cast<const bf8*>(p.ximg);
         const bf8* xlo = xhi + (size_t)mt * xko * 64;
         a.xoct0 = p.xk0 >> 3;
+        if (p.xs_shift > 0) {                   // [tap 0 on rows r - shift | tap 1 on rows r] in one K chain: k = 2 * (width of one tap), W = [N][k]
+            EG_REQUIRE((p.k & 63) == 0 && p.xs_period > 0 && p.xzero && p.splits <= 1, EG_ERR_BAD_ARG, "egi_linear: shifted product needs k %% 64 == 0, a period and a zero line");
+            a.xs_steps = p.k >> 6; a.xs_shift = p.xs_shift; a.xs_period = p.xs_period; a.xzero = reinterpret_cast<const bf8*>(p.xzero);
+            return dispatch_presplit(a, xhi, xlo, xko, p.precision, st, &prof, p.shared_chip);
+        }
         if (skinny_ok(a, p.precision)) {        // one clip: 16 columns per workgroup, K over the waves, no LDS staging (replaces the split-K request too)
             prof.workgroups(eg_cdiv(a.N, 16) * eg_cdiv(a.M, 64));
             return launch_skinny<false>(a, xhi, xlo, xko, st);
@@ -1172,4 +1325,20 @@ extern "C" int eg_linear_presplit(const void* x_images, int32_t k_x, const float
     const bf8* xlo = xhi + (size_t)mt * xko * 64;
     EgProfScope prof(3, 2.0 * m * (double)n * k, (hipStream_t)stream);
     return dispatch_presplit(a, xhi, xlo, xko, precision, (hipStream_t)stream, &prof);
+}
+
+// Causal two-tap convolution over rows as ONE pre-split product (see include/emogest.h).
+extern "C" int eg_linear_presplit_causal(const void* x_images, int32_t k_x, const void* zero_line, const float* w, int32_t ldw, const float* bias,
+                                         const float* res2, int32_t ldr, float* y, int32_t ldc, void* y_images, int32_t y_k, int32_t m, int32_t n,
+                                         int32_t k_tap, int32_t relu, int32_t shift, int32_t period, int32_t precision, void* stream) {
+    EG_REQUIRE(x_images && zero_line && w && (y || y_images) && m > 0 && n > 0 && k_tap > 0, EG_ERR_BAD_ARG, "eg_linear_presplit_causal: null pointer or empty shape");
+    EG_REQUIRE(precision == EG_PREC_BF16X3 || precision == EG_PREC_BF16, EG_ERR_BAD_ARG, "eg_linear_presplit_causal: bf16 modes only");
+    EG_REQUIRE((k_tap & 31) == 0 && ldw == 2 * k_tap && (ldw & 63) == 0 && (k_x & 63) == 0 && k_x >= k_tap, EG_ERR_ALIGN,
+               "eg_linear_presplit_causal: k_tap %% 32, ldw == 2 * k_tap, k_x %% 64");
+    EG_REQUIRE(shift > 0 && period > 0, EG_ERR_BAD_ARG, "eg_linear_presplit_causal: shift=%d period=%d", shift, period);
+    EgiLinear p;
+    p.ximg = x_images; p.xK = k_x; p.xk0 = 0; p.w = w; p.ldw = ldw; p.bias = bias; p.res2 = res2; p.ldr = ldr; p.y = y; p.ldc = ldc;
+    p.yimg = y_images; p.yK = y_k; p.m = m; p.n = n; p.k = 2 * k_tap; p.relu = relu; p.precision = precision;
+    p.xs_shift = shift; p.xs_period = period; p.xzero = zero_line;
+    return egi_linear(p, (hipStream_t)stream);
 }

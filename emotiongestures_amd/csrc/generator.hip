@@ -134,7 +134,9 @@ struct EgiPriorW {
     const float *sp_w0, *sp_b0, *sp_w1, *sp_b1, *tc_w0, *tc_b0, *tc_w1, *tc_b1, *tm_w0, *tm_b0, *tm_w1, *tm_b1;
 };
 int egi_embedding(const int64_t* idx, const float* table, float* out, int rows, int dim, int ld, int n_words, hipStream_t st);
+int egi_embedding_img(const int64_t* idx, const float* table, float* out, void* img, void* zero_line, int rows, int dim, int ld, int n_words, hipStream_t st);
 int egi_add(const float* a, const float* b, float* out, size_t n, int row_len, int period, hipStream_t st);
+int egi_add_img(const float* a, const float* b, float* out, void* img, size_t n, int row_len, int period, hipStream_t st);
 int egi_time_linear(const float* x, const float* w, const float* bias, float* y, int batch, int L, int C, int ld, hipStream_t st);
 int egi_copy2d(const float* src, int lds_, float* dst, int ldd, int rows, int cols, hipStream_t st);
 int egi_linear(const EgiLinear& p, hipStream_t st);
@@ -298,7 +300,7 @@ struct EgGenerator {
     int64_t sp_w0, sp_b0, sp_w1, sp_b1, tc_w0, tc_b0, tc_w1, tc_b1, tm_w0, tm_b0, tm_w1, tm_b1;
     // text
     int64_t emb;
-    struct TcnConv { LinW tap0, tap1; int64_t bias; };
+    struct TcnConv { LinW tap0, tap1, taps; int64_t bias; };        // taps: [tap 0 | tap 1] along K (EG_PACK_WN_TAPS), the one-launch causal product
     std::vector<TcnConv> tcn;
     int64_t txt_fc1_w, txt_fc1_b;
     int Cpad;   // padded TCN channel stride
@@ -336,7 +338,7 @@ struct GenWs {      // byte offsets into the workspace, for a given batch
     int64_t act[3], gap, gate, scv, amap, afc1, afeat, emo_t, emo, sem_t, sem, cls_part, cls_h[3], cls_out;
     int64_t fus_in, fus_h, fusion, xa, xb, q, qkv, ao, proj, ffn_h, im_x[2], im_enc, im_h, im_a[3], im_p[2];
     int64_t prior_cat, prior_h, prior_enc, prior_rep, tm_mem, tm_pe, tm_gram, post_a, post_b, post_c, pose;
-    int64_t t_emb, t_a, t_b, t_c, t_out;
+    int64_t t_emb, t_a, t_b, t_c, t_out, im_t[3], t_zero;
     int64_t tap_stem, tap_l[3];
     int64_t total;
 };
@@ -388,6 +390,9 @@ GenWs carve(const EgGenerator* g, int B, int NB = 0) {
     const int64_t BT = (int64_t)B * c.text_len;
     w.t_emb = cv.take(BT * g->Cpad); w.t_a = cv.take(BT * g->Cpad); w.t_b = cv.take(BT * g->Cpad); w.t_c = cv.take(BT * g->Cpad);
     w.t_out = cv.take(BT * 512);
+    // text branch on images: three rotating (hi, lo) image sets of the TCN activations and the cleared line the causal products read for t < dilation
+    for (int i = 0; i < 3; ++i) w.im_t[i] = cv.take(eg_round_up(BT, 64) * g->Cpad);
+    w.t_zero = cv.take((int64_t)g->Cpad * 32);
     w.tap_stem = w.tap_l[0] = w.tap_l[1] = w.tap_l[2] = -1;
     if (g->keep_taps) {
         w.tap_stem = cv.take(act);
@@ -534,11 +539,47 @@ int run_audio_tower(const EgGenerator* g, const float* arena, const float* spec,
     return lin(g, arena, g->a_fc2, h1, 0, act(P(ws, w.afeat), D, P(ws, w.im_a[1]), D), true, B * F, 0, nullptr, 0, st);
 }
 
+// One causal convolution of the TCN as one pre-split product: [tap 0 on rows t - d | tap 1 on rows t] in one K chain, bias, ReLU, then relu(. + res2).
+// All Cpad columns are computed (the padded weight rows and bias are zero), so the output images need no clearing.
+int causal_conv(const EgGenerator* g, const float* arena, const EgGenerator::TcnConv& cv, void* ximg, const void* zero, float* y, void* yimg,
+                const float* res2, int rows, int d, int L, hipStream_t st) {
+    EgiLinear p;
+    p.ximg = ximg; p.xK = g->Cpad; p.w = arena + cv.taps.w; p.ldw = cv.taps.kpad; p.bias = arena + cv.bias; p.res2 = res2; p.ldr = g->Cpad;
+    p.y = y; p.ldc = g->Cpad; p.yimg = yimg; p.yK = g->Cpad; p.m = rows; p.n = g->Cpad; p.k = cv.taps.kpad; p.relu = 1;
+    p.precision = g->cfg.precision; p.shared_chip = g->shared_chip ? 1 : 0;
+    p.xs_shift = d; p.xs_period = L; p.xzero = zero;
+    return egi_linear(p, st);
+}
+
+// EG_TEXT_TAPS = "2" (read per call, like EG_GEMM_TILE) keeps the bf16 modes on the two-launch convolutions below (A/B runs, tests)
+bool text_one_launch(const EgGenerator* g) {
+    if (g->cfg.precision == EG_PREC_F32 || g->cfg.embed_dim != g->cfg.tcn_hidden || g->Cpad != (int)eg_round_up(g->cfg.tcn_hidden, 64)) return false;
+    const char* e = getenv("EG_TEXT_TAPS");
+    return !(e && e[0] == '2');
+}
+
 // text branch: TextEncoderTCN.forward (Models_spatial_memory.py:171-179) channels-last
 int run_text(const EgGenerator* g, const float* arena, const int64_t* text, float* out, const GenWs& w, void* ws, int B, hipStream_t st) {
     const EgGeneratorConfig& c = g->cfg;
     const int L = c.text_len, C = c.tcn_hidden, ld = g->Cpad, rows = B * L, prec = c.precision;
     float *x = P(ws, w.t_emb), *h1 = P(ws, w.t_a), *h2 = P(ws, w.t_b), *y = P(ws, w.t_c);
+    if (text_one_launch(g)) {
+        // bf16 modes: every activation travels as (hi, lo) images (split once by its producer), fp32 rows only where a residual or fc1 reads them;
+        // 2 products per level + the decoder instead of 4 + 1, and tap 0's partial result never goes through memory
+        void *xi = P(ws, w.im_t[0]), *hi = P(ws, w.im_t[1]), *yi = P(ws, w.im_t[2]), *zero = P(ws, w.t_zero);
+        // the embedding launch also clears the zero line (ld * 128 bytes): no separate fill node in a captured step
+        EG_TRY(egi_embedding_img(text, arena + g->emb, x, xi, zero, rows, c.embed_dim, ld, c.n_words, st));
+        for (int i = 0; i < c.tcn_layers; ++i) {
+            const bool last = i + 1 == c.tcn_layers;
+            EG_TRY(causal_conv(g, arena, g->tcn[2 * i], xi, zero, nullptr, hi, nullptr, rows, 1 << i, L, st));
+            EG_TRY(causal_conv(g, arena, g->tcn[2 * i + 1], hi, zero, y, last ? nullptr : yi, x, rows, 1 << i, L, st));
+            float* t = x; x = y; y = t;
+            void* ti = xi; xi = yi; yi = ti;
+        }
+        EG_TRY(egi_time_linear(x, arena + g->txt_fc1_w, arena + g->txt_fc1_b, h1, B, L, C, ld, st));
+        return eg_linear(h1, ld, arena + g->txt_dec.w, g->txt_dec.kpad, arena + g->txt_dec.b, nullptr, nullptr, 0, out, 512, rows, 512, C, 0,
+                         0, 0, prec, st);
+    }
     EG_TRY(egi_embedding(text, arena + g->emb, x, rows, c.embed_dim, ld, c.n_words, st));
     for (int i = 0; i < c.tcn_layers; ++i) {
         const int d = 1 << i;
@@ -579,18 +620,32 @@ int run_prior(const EgGenerator* g, const float* arena, const float* prior, cons
     return lin(g, arena, g->prior_h2, ph, 0, act(P(ws, w.prior_enc), c.d_model, P(ws, w.im_p[1]), c.d_model), true, rows, 0, nullptr, 0, st);
 }
 
+// the fusion input where one plain add builds it: fp32 rows and (bf16 modes) images in im_x[1], free until the first encoder layer's end
+// EG_ADD_IMAGES = "0" (read per call) keeps the two adds fp32-only and their consumers on the fp32-input product (A/B runs)
+bool add_images(const EgGenerator* g) {
+    if (g->cfg.precision == EG_PREC_F32) return false;
+    const char* e = getenv("EG_ADD_IMAGES");
+    return !(e && e[0] == '0');
+}
+Act fusion_act(const EgGenerator* g, const GenWs& w, void* ws) {
+    const int D = g->cfg.d_model;
+    return act(P(ws, w.fus_in), D, add_images(g) ? P(ws, w.im_x[1]) : nullptr, D);
+}
+
 // fusion_proj -> positional add -> encoder stack for NB sequences (Models_spatial_memory.py:601-606): enc_out = xa (+ images in im_enc)
-int run_encoder(const EgGenerator* g, const float* arena, const float* fusion_in, Act& enc_out, const GenWs& w, void* ws, int NB,
+// fusion_in may carry images (the plain emotion + semantic add writes them into im_x[1]); the positional sum xa gets its own from the add
+int run_encoder(const EgGenerator* g, const float* arena, const Act& fusion_in, Act& enc_out, const GenWs& w, void* ws, int NB,
                 hipStream_t st) {
     const EgGeneratorConfig& c = g->cfg;
     const int F = c.frames, D = c.d_model, rows = NB * F;
     void *im0 = P(ws, w.im_x[0]), *im1 = P(ws, w.im_x[1]), *ime = P(ws, w.im_enc);
     const Act fh = act(P(ws, w.fus_h), D, im0, D);
-    EG_TRY(lin(g, arena, g->fus0, act(const_cast<float*>(fusion_in), D), 0, fh, false, rows, 1, nullptr, 0, st));
+    EG_TRY(lin(g, arena, g->fus0, fusion_in, 0, fh, false, rows, 1, nullptr, 0, st));
     EG_TRY(lin(g, arena, g->fus2, fh, 0, act(P(ws, w.fusion), D), true, rows, 0, nullptr, 0, st));
     float *xa = P(ws, w.xa), *xb = P(ws, w.xb);
-    EG_TRY(egi_add(P(ws, w.fusion), arena + g->pos_table, xa, (size_t)rows * D, D, F, st));
-    Act x = act(xa, D);                                  // first layer input has no images (comes from the positional add)
+    void* xa_img = add_images(g) ? im1 : nullptr;          // im1: fusion_in's images are consumed, the first layer writes it only at its end
+    EG_TRY(egi_add_img(P(ws, w.fusion), arena + g->pos_table, xa, xa_img, (size_t)rows * D, D, F, st));
+    Act x = act(xa, D, xa_img, D);
     for (int l = 0; l < c.n_layers; ++l) {
         const Act mid = act(xb, D, im0, D);
         const Act nxt = act(xa, D, l + 1 < c.n_layers ? im1 : ime, D);
@@ -637,7 +692,7 @@ int run_decoder(const EgGenerator* g, const float* arena, const Act& prior_enc, 
 }
 
 // fusion -> encoder -> decoder -> post_projector for NB sequences (Models_spatial_memory.py:601-614)
-int run_transformer(const EgGenerator* g, const float* arena, const float* fusion_in, const Act& prior_enc, float* pose, const GenWs& w,
+int run_transformer(const EgGenerator* g, const float* arena, const Act& fusion_in, const Act& prior_enc, float* pose, const GenWs& w,
                     void* ws, int NB, hipStream_t st) {
     Act enc_out;
     EG_TRY(run_encoder(g, arena, fusion_in, enc_out, w, ws, NB, st));
@@ -819,6 +874,8 @@ extern "C" int eg_generator_create(const EgGeneratorConfig* cfg, EgGenerator** o
                 w.w = L.add(p, EG_PACK_WN_TAP, C, C, tap, g->Cpad, (int64_t)npad * g->Cpad * 2);
                 (tap == 0 ? tc.tap0 : tc.tap1) = w;
             }
+            tc.taps.n = C; tc.taps.k = 2 * g->Cpad; tc.taps.npad = npad; tc.taps.kpad = 2 * g->Cpad;
+            tc.taps.w = L.add(p + ".weight_g|" + p + ".weight_v", EG_PACK_WN_TAPS, C, C, npad, g->Cpad, (int64_t)npad * g->Cpad * 4);
             tc.bias = L.vec(p + ".bias", C, npad);
             g->tcn.push_back(tc);
         }
@@ -875,13 +932,14 @@ extern "C" int eg_generator_forward(const EgGenerator* g, const float* arena, in
     float* emo = emotion_feature ? emotion_feature : P(ws, w.emo);
     float* sem = semantic_feature ? semantic_feature : P(ws, w.sem);
     EG_TRY(run_heads(g, arena, emo, sem, emotion_prediction ? emotion_prediction : P(ws, w.cls_out), w, ws, B, st));
-    EG_TRY(egi_add(sampled ? sampled : emo, sem, P(ws, w.fus_in), (size_t)rows * D, D, 0, st));
+    const Act fus_in = fusion_act(g, w, ws);
+    EG_TRY(egi_add_img(sampled ? sampled : emo, sem, fus_in.f, fus_in.img, (size_t)rows * D, D, 0, st));
     float* pose_out = pose ? pose : P(ws, w.pose);
     if (g->concurrent) {        // join: the decoder needs the prior encoding; the caller's stream must also cover the text branch
         EG_HIP_TRY(hipStreamWaitEvent(st, g->ev_join[1], 0), "branch join");
         EG_HIP_TRY(hipStreamWaitEvent(st, g->ev_join[0], 0), "branch join");
     }
-    return run_transformer(g, arena, P(ws, w.fus_in), act(P(ws, w.prior_enc), D, P(ws, w.im_p[1]), D), pose_out, w, ws, B, st);
+    return run_transformer(g, arena, fus_in, act(P(ws, w.prior_enc), D, P(ws, w.im_p[1]), D), pose_out, w, ws, B, st);
 }
 
 extern "C" int64_t eg_generator_draws_workspace_bytes(const EgGenerator* g, int32_t batch, int32_t draws) {
@@ -912,7 +970,7 @@ extern "C" int eg_generator_forward_draws(const EgGenerator* g, const float* are
     // fusion_in[(b,r,f)] = sampled[(b,r,f)] + semantic[(b,f)];  decoder target stream = prior_enc[b] for every draw
     EG_TRY(egi_add_bcast(sampled, P(ws, w.sem), P(ws, w.fus_in), (size_t)B * R * F, D, F, R, st));
     EG_TRY(egi_add_bcast(nullptr, P(ws, w.prior_enc), P(ws, w.prior_rep), (size_t)B * R * F, D, F, R, st));
-    return run_transformer(g, arena, P(ws, w.fus_in), act(P(ws, w.prior_rep), D), pose, w, ws, B * R, st);
+    return run_transformer(g, arena, act(P(ws, w.fus_in), D), act(P(ws, w.prior_rep), D), pose, w, ws, B * R, st);
 }
 
 // ---- roll-out: dependent windows of U recordings, in three calls on one skeleton -----------------------------------------------------------
@@ -997,10 +1055,13 @@ int rollout_phase_a(const EgGenerator* g, const float* arena, const RollPlan& p,
     if (text_embedding) EG_TRY(run_text(g, arena, text, txt, w, ws, N, st));
     EG_TRY(run_audio_tower(g, arena, spec, w, ws, N, st));
     EG_TRY(run_heads(g, arena, emo, sem, pred, w, ws, N, st));
-    if (p.R == 1) EG_TRY(egi_add(sampled ? sampled : emo, sem, P(ws, w.fus_in), (size_t)N * F * D, D, 0, st));
-    else EG_TRY(egi_draws_fusion(sampled, sem, P(ws, w.fus_in), p.U, p.steps, p.R, (size_t)F * D, st));
+    Act fus_in = act(P(ws, w.fus_in), D);
+    if (p.R == 1) {
+        fus_in = fusion_act(g, w, ws);
+        EG_TRY(egi_add_img(sampled ? sampled : emo, sem, fus_in.f, fus_in.img, (size_t)N * F * D, D, 0, st));
+    } else EG_TRY(egi_draws_fusion(sampled, sem, fus_in.f, p.U, p.steps, p.R, (size_t)F * D, st));
     Act enc_out;
-    EG_TRY(run_encoder(g, arena, P(ws, w.fus_in), enc_out, w, ws, NR, st));
+    EG_TRY(run_encoder(g, arena, fus_in, enc_out, w, ws, NR, st));
     for (int l = 0; l < c.n_layers; ++l) {
         kv[l] = P(ws, r.kv[l]);
         EG_TRY(lin(g, arena, g->dec_attn[l].kv, enc_out, 0, act(kv[l], 2 * D), true, NR * F, 0, nullptr, 0, st));
@@ -1245,8 +1306,9 @@ extern "C" int eg_generator_stream_step(const EgGenerator* g, const float* arena
     EG_TRY(run_prior(g, arena, prior, w, ws, U, st));
     EG_TRY(run_audio_tower(g, arena, spec, w, ws, U, st));
     EG_TRY(run_heads(g, arena, P(ws, w.emo), P(ws, w.sem), emotion_prediction ? emotion_prediction : P(ws, w.cls_out), w, ws, U, st));
-    EG_TRY(egi_add(sampled ? sampled : P(ws, w.emo), P(ws, w.sem), P(ws, w.fus_in), (size_t)rows * D, D, 0, st));
-    EG_TRY(run_transformer(g, arena, P(ws, w.fus_in), act(P(ws, w.prior_enc), D, P(ws, w.im_p[1]), D), P(ws, w.pose), w, ws, U, st));
+    const Act fus_in = fusion_act(g, w, ws);
+    EG_TRY(egi_add_img(sampled ? sampled : P(ws, w.emo), P(ws, w.sem), fus_in.f, fus_in.img, (size_t)rows * D, D, 0, st));
+    EG_TRY(run_transformer(g, arena, fus_in, act(P(ws, w.prior_enc), D, P(ws, w.im_p[1]), D), P(ws, w.pose), w, ws, U, st));
     return egi_stream_handoff(P(ws, w.pose), prior, stream_ctr(state, s), alpha, rows_out, valid_out, window_out, U, F, c.prior_frames, c.pose_dim,
                               st);
 }

@@ -91,6 +91,33 @@ __global__ __launch_bounds__(256) void embedding_kernel(const int64_t* __restric
     }
 }
 
+// The same rows with their bf16 (hi, lo) tile-planar images [ceil(rows/64)][ld/8][64][8] for a pre-split product (ld = dim rounded up to 64): one
+// thread per (row, octet); the columns dim .. ld-1 are written as zeros in the fp32 rows and in the images.  zero (optional): a line of 64 * ld / 8
+// slots this launch clears -- the row source of the causal products that follow on the stream (t < dilation).
+__global__ __launch_bounds__(256) void embedding_img_kernel(const int64_t* __restrict__ idx, const float* __restrict__ table, float* __restrict__ out,
+                                                            bf8* __restrict__ hi, bf8* __restrict__ lo, bf8* __restrict__ zero, int rows, int dim, int ld,
+                                                            int n_words) {
+    const int KO = ld >> 3;
+    const size_t total = (size_t)((rows + 63) >> 6) * 64 * KO;            // consecutive threads = consecutive rows of one octet: 1-KiB image stores
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        if (zero && i < (size_t)64 * KO) zero[i] = (bf8){0, 0, 0, 0, 0, 0, 0, 0};
+        const int t = (int)(i / (64 * KO)), rem = (int)(i - (size_t)t * 64 * KO), o = rem >> 6, r = t * 64 + (rem & 63), k = o * 8;
+        if (r >= rows) continue;
+        int64_t w = idx[r];
+        w = w < 0 ? 0 : (w >= n_words ? n_words - 1 : w);
+        f4 v0 = (f4){0.f, 0.f, 0.f, 0.f}, v1 = v0;
+        if (k < dim) v0 = *reinterpret_cast<const f4*>(table + (size_t)w * dim + k);
+        if (k + 4 < dim) v1 = *reinterpret_cast<const f4*>(table + (size_t)w * dim + k + 4);
+        *reinterpret_cast<f4*>(out + (size_t)r * ld + k) = v0;
+        *reinterpret_cast<f4*>(out + (size_t)r * ld + k + 4) = v1;
+        bf8 h, l;
+        split_octet<true>(v0, v1, h, l);
+        const size_t slot = ((size_t)(r >> 6) * KO + o) * 64 + (r & 63);
+        hi[slot] = h;
+        lo[slot] = l;
+    }
+}
+
 // out = a + b ;  b optionally row-periodic (row % period) -- positional table add (Models_spatial_memory.py:46-48)
 __global__ __launch_bounds__(256) void add_kernel(const f4* __restrict__ a, const f4* __restrict__ b, f4* __restrict__ out,
                                                   size_t n4, int row_q, int period) {
@@ -101,6 +128,29 @@ __global__ __launch_bounds__(256) void add_kernel(const f4* __restrict__ a, cons
             j = (row % period) * row_q + (i - row * row_q);
         }
         out[i] = a[i] + b[j];
+    }
+}
+
+// add_kernel with a second output: the sum split to bf16 (hi, lo) tile-planar images [ceil(rows/64)][row_len/8][64][8] for a pre-split product.
+// One thread per (row, octet), consecutive threads = consecutive rows of one octet (1-KiB image stores); row_o = row_len / 8.
+__global__ __launch_bounds__(256) void add_img_kernel(const f4* __restrict__ a, const f4* __restrict__ b, f4* __restrict__ out, bf8* __restrict__ hi,
+                                                      bf8* __restrict__ lo, size_t rows, int row_o, int period) {
+    const size_t total = ((rows + 63) >> 6) * 64 * row_o;
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        const size_t tile = t / (64 * (size_t)row_o);
+        const int rem = (int)(t - tile * 64 * row_o), o = rem >> 6;
+        const size_t row = tile * 64 + (rem & 63);
+        if (row >= rows) continue;
+        const size_t i = row * row_o + o;
+        const size_t j = period ? (row % period) * row_o + o : i;
+        const f4 v0 = a[2 * i] + b[2 * j], v1 = a[2 * i + 1] + b[2 * j + 1];
+        out[2 * i] = v0;
+        out[2 * i + 1] = v1;
+        bf8 h, l;
+        split_octet<true>(v0, v1, h, l);
+        const size_t slot = ((row >> 6) * row_o + o) * 64 + (row & 63);
+        hi[slot] = h;
+        lo[slot] = l;
     }
 }
 
@@ -522,6 +572,13 @@ extern "C" int eg_add_rows(const float* a, const float* table, float* out, int64
     return eg_check_launch("add_rows");
 }
 
+int egi_add_img(const float* a, const float* b, float* out, void* img, size_t n, int row_len, int period, hipStream_t st);
+// eg_add_rows with a second output: the sum as bf16 (hi, lo) tile-planar images (eg_split_tiles layout of width d) for a pre-split product
+extern "C" int eg_add_rows_split(const float* a, const float* table, float* out, void* images, int64_t rows, int32_t d, int32_t period, void* stream) {
+    EG_REQUIRE(a && table && out && images && rows > 0 && d > 0 && (d & 63) == 0, EG_ERR_BAD_ARG, "eg_add_rows_split: null pointer, empty shape or d %% 64 != 0");
+    return egi_add_img(a, table, out, images, (size_t)rows * d, d, period, (hipStream_t)stream);
+}
+
 extern "C" int eg_window_gather(const float* audio, int32_t utterances, int64_t total_samples, int32_t windows, int64_t hop_samples,
                                 int32_t n_samples, float* out, void* stream) {
     EG_REQUIRE(audio && out, EG_ERR_BAD_ARG, "eg_window_gather: null pointer");
@@ -540,6 +597,26 @@ extern "C" int eg_window_gather(const float* audio, int32_t utterances, int64_t 
 int egi_embedding(const int64_t* idx, const float* table, float* out, int rows, int dim, int ld, int n_words, hipStream_t st) {
     hipLaunchKernelGGL(embedding_kernel, dim3(grid_for((size_t)rows * dim / 4)), dim3(256), 0, st, idx, table, out, rows, dim, ld, n_words);
     return eg_check_launch("embedding");
+}
+int egi_add(const float* a, const float* b, float* out, size_t n, int row_len, int period, hipStream_t st);
+int egi_embedding_img(const int64_t* idx, const float* table, float* out, void* img, void* zero_line, int rows, int dim, int ld, int n_words, hipStream_t st) {
+    EG_REQUIRE((dim & 3) == 0 && (ld & 63) == 0 && ld >= dim, EG_ERR_ALIGN, "embedding: dim %% 4, ld %% 64");
+    bf8* hi = reinterpret_cast<bf8*>(img);
+    bf8* lo = hi + (size_t)eg_cdiv(rows, 64) * (ld >> 3) * 64;
+    hipLaunchKernelGGL(embedding_img_kernel, dim3(grid_for((size_t)eg_cdiv(rows, 64) * 64 * (ld >> 3))), dim3(256), 0, st, idx, table, out, hi, lo,
+                       reinterpret_cast<bf8*>(zero_line), rows, dim, ld, n_words);
+    return eg_check_launch("embedding");
+}
+// img != nullptr: also the sum's bf16 (hi, lo) images of width row_len (row_len % 64 == 0), hi then lo image
+int egi_add_img(const float* a, const float* b, float* out, void* img, size_t n, int row_len, int period, hipStream_t st) {
+    if (!img) return egi_add(a, b, out, n, row_len, period, st);
+    EG_REQUIRE((row_len & 63) == 0, EG_ERR_ALIGN, "add: image output needs row_len %% 64 == 0");
+    const size_t rows = n / row_len;
+    bf8* hi = reinterpret_cast<bf8*>(img);
+    bf8* lo = hi + ((rows + 63) >> 6) * (size_t)(row_len >> 3) * 64;
+    hipLaunchKernelGGL(add_img_kernel, dim3(grid_for(n / 8)), dim3(256), 0, st, reinterpret_cast<const f4*>(a), reinterpret_cast<const f4*>(b),
+                       reinterpret_cast<f4*>(out), hi, lo, rows, row_len / 8, period);
+    return eg_check_launch("add");
 }
 int egi_add(const float* a, const float* b, float* out, size_t n, int row_len, int period, hipStream_t st) {
     hipLaunchKernelGGL(add_kernel, dim3(grid_for(n / 4)), dim3(256), 0, st, reinterpret_cast<const f4*>(a),

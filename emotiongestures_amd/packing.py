@@ -123,6 +123,14 @@ def pack_entry(sd: Mapping[str, torch.Tensor], e: L.EgWeightEntry) -> np.ndarray
         w = v * (g / v.flatten(1).norm(dim=1).view(-1, 1, 1))          # torch weight_norm, dim=0 (tcn.py:19)
         npad = (d[0] + 63) // 64 * 64
         out = _pack_linear(w[:, :, d[2]].contiguous(), npad, d[3])
+    elif kind == L.PACK_WN_TAPS:
+        kg, kv = key.split("|")
+        g, v = _t(sd, kg), _t(sd, kv)
+        w = v * (g / v.flatten(1).norm(dim=1).view(-1, 1, 1))
+        cat = torch.zeros(d[0], 2 * d[3], dtype=torch.float32)          # [tap 0 | tap 1], each padded to Ipad
+        cat[:, : d[1]] = w[:, :, 0]
+        cat[:, d[3]: d[3] + d[1]] = w[:, :, 1]
+        out = _pack_linear(cat, d[2], 2 * d[3])
     elif kind == L.PACK_POS_TABLE:
         out = _t(sd, key)[0, : d[0], :].contiguous().reshape(-1).numpy()
     elif kind == L.PACK_LINEAR_T:

@@ -101,8 +101,11 @@ typedef enum EgPackKind {
                                    affine chain): W = W_last ... W_first folded in float64, packed as EG_PACK_LINEAR (same dims);
                                    several chains joined by '|' are concatenated along N */
     EG_PACK_BIAS_FOLD = 13,     /* the folded chain's bias, zero padded to dims[1] */
-    EG_PACK_CONV1X1_BF16 = 14   /* Conv2d [O,I,1,1] -> bf16 images [I/8][O][8], hi = bf16(w) then lo = bf16(w - hi): the 3x3 images' packing with a
+    EG_PACK_CONV1X1_BF16 = 14,  /* Conv2d [O,I,1,1] -> bf16 images [I/8][O][8], hi = bf16(w) then lo = bf16(w - hi): the 3x3 images' packing with a
                                    single tap (dims = O,I; numel = O*I floats).  I % 32 == 0, O % 16 == 0 */
+    EG_PACK_WN_TAPS = 15        /* key = "<prefix>.weight_g|<prefix>.weight_v" of a weight-norm conv, kernel size 2: both taps of g*v/||v|| side by side along K, [O][tap 0 | tap 1] with
+                                   each tap zero padded to Ipad, packed as EG_PACK_LINEAR with K = 2*Ipad (dims = O,I,Opad,Ipad;
+                                   numel = 4*Opad*Ipad floats): the weight of eg_linear_presplit_causal */
 } EgPackKind;
 
 typedef struct EgWeightEntry {
@@ -622,6 +625,14 @@ int eg_split_tiles(const float* x, int32_t lda, int32_t m, int32_t k, void* imag
 int eg_linear_presplit(const void* x_images, int32_t k_x, const float* w, int32_t ldw, const float* bias,
                        const float* res1, const float* res2, int32_t ldr, float* y, int32_t ldc,
                        int32_t m, int32_t n, int32_t k, int32_t relu, int32_t precision, void* stream);
+/* A causal two-tap convolution over rows (tcn.py:18-24: pad d, chomp d) as ONE pre-split product:
+ *   y[r] = epi(b + W0 x[r - shift] + W1 x[r]),  x[r - shift] = 0 where (r mod period) < shift,  epi = relu, then relu(. + res2) when res2 is given.
+ * x_images: X [M, k_tap] as eg_split_tiles images of width k_x; w: the EG_PACK_LINEAR image of [W0 | W1] ([N][2*k_tap], each tap zero padded to
+ * k_tap; ldw = 2*k_tap); zero_line: k_tap * 128 cleared bytes of device memory (the source of the rows that see zero).  The accumulator runs
+ * through one K chain, tap 0 first.  y (fp32, may be NULL) and / or y_images (images of width y_k, may be NULL) receive the result.  bf16 modes. */
+int eg_linear_presplit_causal(const void* x_images, int32_t k_x, const void* zero_line, const float* w, int32_t ldw, const float* bias,
+                              const float* res2, int32_t ldr, float* y, int32_t ldc, void* y_images, int32_t y_k, int32_t m, int32_t n,
+                              int32_t k_tap, int32_t relu, int32_t shift, int32_t period, int32_t precision, void* stream);
 
 /* Split-K variant for tall-K, short-M products (emotion_classifer_header.0: K = frames*d_model,
  * Models_spatial_memory.py:500).  partial >= splits*M*N floats. */
@@ -704,6 +715,9 @@ int eg_positionwise_ffn(const float* x, const float* w1, const float* b1, const 
 int eg_tcn_forward(const float* x, const float* w, float* y, int32_t batch, int32_t len, int32_t c,
                    int32_t levels, int32_t precision, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* eg_add_rows (below) that also writes the sum as eg_split_tiles images of width d (d % 64 == 0; 4*ceil(rows/64)*64*d bytes, rows past the last
+ * one are left untouched): the producer-side split for the product that consumes the sum. */
+int eg_add_rows_split(const float* a, const float* table, float* out, void* images, int64_t rows, int32_t d, int32_t period, void* stream);
 /* out[r,:] = a[r,:] + table[r % period,:]  (PositionalEncoding.forward, Full_model/Models_spatial_memory.py:46-48);
  * period == 0: plain elementwise add of two [rows, d] tensors (fusion add, :601-605).  d % 4 == 0. */
 int eg_add_rows(const float* a, const float* table, float* out, int64_t rows, int32_t d, int32_t period, void* stream);
