@@ -52,6 +52,13 @@ class EgLinearArgs(C.Structure):
                [("drop_seed", C.c_uint32), ("drop_p", C.c_float)]
 
 
+class EgResamplePlan(C.Structure):
+    """include/emogest.h: eg_resample_plan's result."""
+    _fields_ = [(n, C.c_int32) for n in ("L", "M", "half", "K", "D", "Hs", "pitch", "bank_floats")]
+
+
+EG_RESAMPLE_TILE, EG_RESAMPLE_MAX_FACTOR = 1024, 640
+
 # name -> (restype, argtypes).  Must list every symbol include/emogest.h declares
 # (tests/test_abi.py cross-checks this table against the header).
 SIGNATURES = {
@@ -100,6 +107,13 @@ SIGNATURES = {
     "eg_melspectrogram": (C.c_int, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _L, _P]),
     "eg_window_gather": (C.c_int, [_P, _I, _L, _I, _L, _I, _P, _P]),
     "eg_window_gather_ragged": (C.c_int, [_P, _I, _L, _P, _P, _L, _I, _P, _P]),
+    "eg_resample_plan": (C.c_int, [_I, _I, C.POINTER(EgResamplePlan)]),
+    "eg_resample_out_length": (_L, [_L, _I, _I]),
+    "eg_resample_filter": (C.c_int, [_I, _I, _P, _P]),
+    "eg_resample": (C.c_int, [_P, _I, _L, _P, _P, _I, _I, _P, _L, _P, _L, _P]),
+    "eg_resample_stream_state_bytes": (_L, [_I, _I, _I]),
+    "eg_resample_stream_reset": (C.c_int, [_P, _I, _I, _I, _P, _P]),
+    "eg_resample_stream_push": (C.c_int, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
     "eg_beat_tables": (C.c_int, [_P, _P, _P, _P]),
     "eg_beat_workspace_bytes": (_L, [_I, _I]),
     "eg_beat_align": (C.c_int, [_P, _I, _I, _P, _I, _I, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P]),

@@ -367,10 +367,19 @@ def audio_classifier_collate_fn(data):
     return default_collate(audio), default_collate(spectrogram), default_collate(poses_seq), default_collate(eid_label), aux
 
 
-def clips_from_raw_audio(eid: str, audio_raw: np.ndarray, skeletons: np.ndarray, words, fps_in: float, device="cuda:0") -> dict:
+def clips_from_raw_audio(eid: str, audio_raw: np.ndarray, skeletons: np.ndarray, words, fps_in: float, device="cuda:0",
+                         audio_rate: Optional[int] = None) -> dict:
     """Build one upstream-shaped video dict from raw 16 kHz audio: the whole-clip mel is computed on the GPU, so that
-    raw audio -> DataPreprocessor -> SpeechMotionDataset -> generator starts from samples, as the north star asks."""
+    raw audio -> DataPreprocessor -> SpeechMotionDataset -> generator starts from samples, as the north star asks.
+    ``audio_rate`` (Hz): the samples are at that rate; they are resampled to 16 kHz on the GPU (resample.resample_audio), the 16 kHz samples
+    are what ``audio_raw`` stores and the mel is made from, and the duration comes from the input length and rate."""
     duration = len(audio_raw) / SAMPLE_RATE
+    if audio_rate is not None and int(audio_rate) != SAMPLE_RATE:
+        import torch
+        from .resample import resample_audio
+        duration = len(audio_raw) / int(audio_rate)
+        x = torch.from_numpy(np.ascontiguousarray(audio_raw, np.float32)).to(device)
+        audio_raw = resample_audio(x, int(audio_rate), SAMPLE_RATE).cpu().numpy()
     return {"eid": eid, "clips": [{
         "skeletons": np.asarray(skeletons), "audio_feat": extract_melspectrogram(audio_raw, device=device),
         "audio_raw": np.asarray(audio_raw), "words": [list(w) for w in words],

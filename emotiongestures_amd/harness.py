@@ -462,7 +462,7 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
                hop_samples: Optional[int] = None, n_samples: Optional[int] = None, windows: Optional[int] = None,
                z: Optional[torch.Tensor] = None, alpha: Optional[torch.Tensor] = None, fps: int = 15, sample_rate: int = 16000,
                want_windows: bool = False, want_aux: bool = False, mel=None, lengths=None, draws: Optional[int] = None,
-               beat: bool = False, diversity=None) -> Dict[str, torch.Tensor]:
+               beat: bool = False, diversity=None, audio_rate: Optional[int] = None) -> Dict[str, torch.Tensor]:
     """One gesture track per utterance from raw 16 kHz audio: windows -> mel -> optional CVAE sample per window -> roll-out.
 
     ``models = (generator, vae | None)``, eval mode, on the GPU.  ``audio [U, total_samples]``; ``text [U, W, 60]`` (the words of every
@@ -489,7 +489,13 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
 
     ``diversity=fgd`` (an eval-mode ``MLP_Reconstruct``; with ``draws=R``, R >= 2): adds ``"take_distance"`` ``[U, R, R]`` and
     ``"take_diversity"`` ``[U]`` (fp64), the pairwise distances of the returned takes of every recording in FGD feature space and their mean
-    (takes.take_diversity with ``span = frames``: the unit of the clip metric ``calculate_diversity`` on one generator window)."""
+    (takes.take_diversity with ``span = frames``: the unit of the clip metric ``calculate_diversity`` on one generator window).
+
+    ``audio_rate`` (Hz; e.g. 48000, 44100, 24000): ``audio``, and ``lengths`` when given, are at that rate.  The audio is resampled to
+    ``sample_rate`` once on the device (resample.resample_audio: scipy's ``resample_poly`` design, ``max(L, M) <= 640``), then the path above
+    runs unchanged on the result -- with ``lengths``, ``draws``, ``beat`` (scored against the resampled audio and its lengths) and
+    ``diversity``; ``hop_samples`` / ``n_samples`` stay in model-rate samples.  The dict gains ``"audio"`` (the resampled signal) and, with
+    ``lengths``, ``"lengths"`` (its sample counts).  ``None`` or equal to ``sample_rate``: no launch and no extra keys."""
     gen, vae = models
     _eval_only(gen)
     if beat and seed_pose.shape[-1] < 174:
@@ -510,6 +516,15 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     if audio.dim() != 2:
         raise L.EgError(f"audio shape {tuple(audio.shape)} != (U, total_samples)")
     U = audio.shape[0]
+    resampled = audio_rate is not None and int(audio_rate) != int(sample_rate)
+    if resampled:
+        from . import resample as RS
+        if lengths is not None:
+            lengths = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        with torch.no_grad():
+            audio = RS.resample_audio(audio, int(audio_rate), int(sample_rate), lengths=lengths)
+        if lengths is not None:
+            lengths = [RS.out_length(v, int(audio_rate), int(sample_rate)) for v in lengths]
     if lengths is not None:
         out, spec, wp = _synthesize_ragged(eng, vae, audio, lengths, text, seed_pose, labels, z, alpha, want_windows, want_aux,
                                            *_front_end(c, audio, hop_samples, n_samples, fps, sample_rate, mel))
@@ -522,6 +537,10 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
                                      *_front_end(c, audio, hop_samples, n_samples, fps, sample_rate, mel))
         wp = [W] * U
     out["spec"] = spec
+    if resampled:
+        out["audio"] = audio
+        if lengths is not None:
+            out["lengths"] = list(lengths)
     if beat:
         from .beat import beat_alignment_tracks
         H = c.frames - c.prior_frames

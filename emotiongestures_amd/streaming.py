@@ -150,7 +150,7 @@ class GestureStream:
 
     def __init__(self, models: Tuple, rows: int, seed_pose: torch.Tensor, *, hop_samples: Optional[int] = None, n_samples: Optional[int] = None,
                  fps: int = 15, sample_rate: int = 16000, alpha: Optional[torch.Tensor] = None, graph: bool = True, want_windows: bool = False,
-                 draws: Optional[int] = None):
+                 draws: Optional[int] = None, audio_rate: Optional[int] = None):
         if draws is not None:
             raise L.EgError("GestureStream: draws= is not supported (a stream has one track per row); for several sampled tracks of a whole "
                             "recording call the rectangular synthesize(..., draws=R), or open the stream with each speaker's row repeated")
@@ -170,6 +170,18 @@ class GestureStream:
             self.n = (self.spec_len - 1) * 512 if n_samples is None else int(n_samples)
         else:                   # ready spectrograms: one window per push; the ring degenerates to one sample per row
             self.hop = self.n = 1
+        # audio at another rate: a StreamResampler in front of the ring (its two launches come first in every step, inside the captured graph)
+        self.audio_rate = None if audio_rate is None or int(audio_rate) == int(sample_rate) else int(audio_rate)
+        self.hop_in, self._rs, self._ratio = self.hop, None, (1, 1)
+        if self.audio_rate is not None:
+            from . import resample as RS
+            if self.mel is None:
+                raise L.EgError("GestureStream: audio_rate= with a session that has no mel front-end (models[2] is None): push_spec takes ready "
+                                "spectrograms, there is no audio to resample")
+            self._ratio = RS.ratio(self.audio_rate, sample_rate)                # refuses an unsupported ratio by name
+            if self.hop * self._ratio[1] % self._ratio[0]:
+                raise L.EgError(RS.hop_message("GestureStream", self.hop, self.audio_rate, sample_rate))
+            self.hop_in = self.hop * self._ratio[1] // self._ratio[0]
         self.plan = SessionPlan(self.U, self.hop, self.n, coupled=c["variant"] == "memory")
         self.lag = lag_of(self.hop, self.n)
         if tuple(seed_pose.shape) != (self.U, self.P, self.D):
@@ -192,6 +204,10 @@ class GestureStream:
         z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=dev)
         self._in: Dict[str, torch.Tensor] = {"audio": z(self.U, self.hop), "ends": torch.full((self.U,), -1, dtype=torch.int32, device=dev),
                                              "text": z(self.U, self.text_len, dtype=torch.int64)}
+        if self.audio_rate is not None:
+            from .resample import StreamResampler
+            self._rs = StreamResampler(self.U, self.audio_rate, self.hop, sample_rate, device=dev)
+            self._in["audio"] = self._rs.out                         # the ring is fed the resampler's static output
         self._clips = z(self.U, self.n)
         if self.mel is None:
             self._in["spec"] = z(self.U, self.n_mels, self.spec_len)
@@ -247,7 +263,7 @@ class GestureStream:
         g = self._in
         with torch.no_grad():
             eng = self._engine()
-            clips = eng.stream_push(self._state, *self._geom, g["audio"], g["ends"], self._clips)
+            clips = self._push_only()
             spec = self.mel(clips, out_frames=self.spec_len, slot=self._slot) if self.mel is not None else g["spec"]
             if self.vae is not None:
                 sampled = self.vae.sample(g["label"], z=g["z"], slot=self._slot)
@@ -256,11 +272,18 @@ class GestureStream:
             return eng.stream_step(self._state, *self._geom, spec, g["text"], sampled, self.alpha, want_window=self.want_windows,
                                    workspace=self._ws)
 
+    def _push_only(self):
+        """The resampler's launches (with audio_rate), then the ring's: the part of a step that runs even when no row has a window."""
+        if self._rs is not None:
+            self._rs.run()
+        return self._engine().stream_push(self._state, *self._geom, self._in["audio"], self._in["ends"], self._clips)
+
     def _capture(self, use_sampled: bool) -> dict:
         """Two eager warm-up runs on a side stream (workspaces, kernel attributes: outside the capture), then the capture; the session's state is
         snapshotted before and restored after, so neither advances it."""
         dev = self.device
         snap = self._state.clone()
+        rs_snap = self._rs.snapshot() if self._rs is not None else None      # the resampler's history advances with every run, too
         cap = torch.cuda.Stream(dev)
         cap.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(cap):
@@ -272,6 +295,8 @@ class GestureStream:
         with torch.cuda.graph(graph, capture_error_mode=CAPTURE_MODE):
             out = self._run_step(use_sampled)
         self._state.copy_(snap)
+        if self._rs is not None:
+            self._rs.restore(rs_snap)
         torch.cuda.synchronize(dev)
         # the graph replays raw pointers into the engines' arenas and workspaces: keep them alive as long as the graph (ClipPipeline._capture)
         st = self._engine_state()
@@ -340,9 +365,15 @@ class GestureStream:
             raise L.EgError(f"text shape {tuple(text.shape)} != ({self.U},{self.text_len})")
         use_sampled = self._conditioning(labels, z, sampled)
         _need_cuda(text, "text", torch.int64)
+        ends_in = None
+        if self._rs is not None:
+            ends, ends_in = self._ends_at_model_rate(ends)
         rows, infos, ends_host = self.plan.preview(ends)            # refuses before anything touches the device
         self._check_fresh()
-        if audio is not None:
+        if audio is not None and self._rs is not None:
+            self._rs.chunk.copy_(audio, non_blocking=True)
+            self._rs.ends.copy_(torch.tensor(ends_in, dtype=torch.int32), non_blocking=False)
+        elif audio is not None:
             self._in["audio"].copy_(audio, non_blocking=True)
         if spec is not None:
             self._in["spec"].copy_(spec, non_blocking=True)
@@ -358,7 +389,8 @@ class GestureStream:
             out = self._launch(use_sampled)
         else:
             out = None
-            self._engine().stream_push(self._state, *self._geom, self._in["audio"], self._in["ends"], self._clips)
+            with torch.no_grad():
+                self._push_only()
         # the host mirror follows the device: committed once the push has been enqueued (a launch or capture that raises leaves both where they were)
         self.plan.rows, self.last_valid, self.last_windows = rows, valid, [i["w"] for i in infos]
         self.last_window = out["window"].clone() if out is not None and self.want_windows else None
@@ -366,11 +398,22 @@ class GestureStream:
             return None, torch.zeros(self.U, dtype=torch.int32, device=self.device)
         return out["rows"].clone(), out["valid"].clone()
 
+    def _ends_at_model_rate(self, ends):
+        """With audio_rate: `ends` counts input samples, [0, hop_in].  -> (the same ends in model-rate samples for the session's plan and ring,
+        the resampler's vector: a row that ended in an earlier push carries nothing, 0 real samples)."""
+        e_in = self._rs.host_ends(ends)
+        Lf, M = self._ratio
+        e_out = [-1 if m < 0 else -(-m * Lf // M) for m in e_in]
+        e_rs = [0 if row[2] >= 0 else m for row, m in zip(self.plan.rows, e_in)]
+        return e_out, e_rs
+
     def push(self, audio, text, labels=None, z=None, sampled=None, ends=None):
         if self.mel is None:
             raise L.EgError("push: the session has no mel front-end (models[2] is None); feed ready spectrograms with push_spec")
-        if tuple(audio.shape) != (self.U, self.hop):
-            raise L.EgError(f"audio shape {tuple(audio.shape)} != ({self.U},{self.hop})")
+        if tuple(audio.shape) != (self.U, self.hop_in):
+            raise L.EgError(f"audio shape {tuple(audio.shape)} != ({self.U},{self.hop_in})" +
+                            (f" ({self.hop} samples per push at the model's rate are {self.hop_in} at audio_rate={self.audio_rate})"
+                             if self._rs is not None else ""))
         _need_cuda(audio, "audio")
         return self._step(audio, None, text, labels, z, sampled, ends)
 
@@ -398,6 +441,8 @@ class GestureStream:
             m[sel] = 1
             mask = m.to(self.device)
         self._engine().stream_reset(self._state, *self._geom, seed, mask)
+        if self._rs is not None:
+            self._rs.reset(None if len(sel) == self.U else sel)
 
     def tail(self) -> torch.Tensor:
         """[U, P, D]: every row's current prior = the last P rows of its track."""
@@ -417,16 +462,16 @@ class GestureStream:
         if last_chunk is None:
             if ends is not None:
                 raise L.EgError("finish: ends without last_chunk")
-            ends, chunk = 0, torch.zeros(self.U, self.hop, device=self.device)
+            ends, chunk = 0, torch.zeros(self.U, self.hop_in, device=self.device)
         else:
-            ends, chunk = self.hop if ends is None else ends, last_chunk
-        left = max(self.plan.remaining(ends))
+            ends, chunk = self.hop_in if ends is None else ends, last_chunk
+        left = max(self.plan.remaining(self._ends_at_model_rate(ends)[0] if self._rs is not None else ends))
         if R > left:
             raise L.EgError(f"finish: R={R} steps asked, {left} windows remain")
         lab = lambda r: None if labels is None else (labels[:, r] if labels.dim() == 3 else labels)
         out = []
         for r in range(R):
-            rows, _valid = self.push(chunk if r == 0 else torch.zeros_like(self._in["audio"]), text[:, r], lab(r), None if z is None else z[:, r],
+            rows, _valid = self.push(chunk if r == 0 else torch.zeros_like(chunk), text[:, r], lab(r), None if z is None else z[:, r],
                                      None if sampled is None else sampled[:, r], ends=ends if r == 0 else None)
             out.append(torch.zeros(self.U, self.H, self.D, device=self.device) if rows is None else rows)
         self.plan.finished = True

@@ -414,6 +414,56 @@ int eg_window_gather_ragged(const float* audio, int32_t utterances, int64_t stri
                             int64_t hop_samples, int32_t n_samples, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Polyphase resampler: audio at rate_in -> the model's rate_out (16000) on the device (csrc/resample.hip)
+ * ------------------------------------------------------------------------------------------ */
+/* g = gcd(rate_in, rate_out), L = rate_out / g, M = rate_in / g; supported: max(L, M) <= EG_RESAMPLE_MAX_FACTOR (8000, 11025, 12000, 22050,
+ * 24000, 32000, 44100, 48000, 88200, 96000, 176400, 192000 -> 16000 among them); anything else is refused with its L and M.
+ * Filter: half = 10 * max(L, M), 2*half + 1 taps, fc = 1 / max(L, M), h[k] = fc * sinc(fc * (k - half)) * kaiser(beta 5)[k], normalised to
+ * sum 1, times L: scipy.signal.firwin(2*half + 1, fc, window=("kaiser", 5.0)) * L, the filter of scipy.signal.resample_poly's defaults,
+ * designed in float64 on the host and rounded to fp32.
+ * Output: n_out = ceil(n_in * L / M), y[n] = sum_i x[i] * h[half + (n - delay)*M - i*L] over 0 <= i < n_in with the tap index inside
+ * [0, 2*half]; delay = 0 is resample_poly(x, L, M).  x outside [0, n_in) is zero and is never read.
+ * K = ceil((2*half + 1) / L) taps per output; the device table is the polyphase bank [L][pitch], pitch = K | 1 (odd: consecutive phases start
+ * in different LDS banks), bank[phase][j] = h[phase + j*L], zero past the last tap and in the pad column.
+ * Streaming: output n needs half / L future inputs, so a stream's signal is the offline one delayed by D = ceil(half / M) output samples,
+ * y_d[n] = y[n - D], cut to ceil(n_in * L / M) samples; the history a push needs is the last Hs = ceil((D*M + half) / L) input samples.
+ * eg_resample_plan, eg_resample_out_length (-1 for refused arguments) and eg_resample_filter are host only: no HIP call, usable without a
+ * GPU.  eg_resample_filter fills h_taps [2*half + 1] and / or h_bank [bank_floats] (either may be NULL, not both). */
+#define EG_RESAMPLE_MAX_FACTOR 640
+#define EG_RESAMPLE_TILE 1024       /* output samples of one workgroup of the offline kernel */
+typedef struct EgResamplePlan {
+    int32_t L, M, half, K, D, Hs;
+    int32_t pitch;              /* floats per phase row of the bank */
+    int32_t bank_floats;        /* L * pitch */
+} EgResamplePlan;
+int eg_resample_plan(int32_t rate_in, int32_t rate_out, EgResamplePlan* plan);
+int64_t eg_resample_out_length(int64_t n_in, int32_t rate_in, int32_t rate_out);
+int eg_resample_filter(int32_t rate_in, int32_t rate_out, float* h_taps, float* h_bank);
+/* Offline: x [U, in_stride], row u holds lengths[u] real samples (1 .. in_stride; what follows them may be anything, NaN included) ->
+ * y [U, out_stride]: row u's ceil(lengths[u] * L / M) samples of the signal delayed by `delay` >= 0 output samples, then zeros up to
+ * out_stride (>= the longest row's output).  lengths [U] int64 on the HOST (checked here), d_lengths [U] int64 on the DEVICE: the caller's
+ * upload of the same numbers; d_bank: device copy of eg_resample_filter's bank.  One launch, grid (output tile of EG_RESAMPLE_TILE, row),
+ * one owning thread per output element, no atomics; the input span of a tile is staged in LDS (16-byte loads where x is 16-byte aligned
+ * and in_stride % 4 == 0).  A row's result does not depend on U, on its place in the batch or on the strides.  Launch, grid and pointers
+ * depend on (U, strides, rates) only: the call captures into a hipGraph.  Refuses by name before the launch: null pointers, y / d_bank not
+ * 16-byte aligned, rates, U outside 1 .. 65535, lengths[u] outside 1 .. in_stride, a short out_stride, delay < 0. */
+int eg_resample(const float* x, int32_t rows, int64_t in_stride, const int64_t* lengths, const int64_t* d_lengths, int32_t rate_in,
+                int32_t rate_out, const float* d_bank, int64_t delay, float* y, int64_t out_stride, void* stream);
+/* Stream: state = the history [rows, Hs] fp32 in a caller-owned device buffer of eg_resample_stream_state_bytes (0 for refused arguments).
+ * eg_resample_stream_reset zeroes the history of the rows with row_mask[u] != 0 (device int32 [rows]; NULL: every row).
+ * eg_resample_stream_push: chunk_in [rows, hop_in] + ends_in (device int32 [rows]; -1: the row goes on, else the number of real samples in
+ * this chunk -- what follows them is never read; NULL: all go on) -> out [rows, hop_out]: the next hop_out samples of the delayed signal;
+ * a row that ends with m real samples has ceil(m * L / M) real output samples in this push and zeros after them.  hop_in must be
+ * hop_out * M / L exactly (then every push is the same computation on [history | chunk] in local indices: no device counter, nothing
+ * depends on the step index) and >= Hs.  Two launches: the outputs, then the new history (the last Hs samples of the chunk, zero from the
+ * row's end on) in a launch of its own, so no launch reads and overwrites the history.  The outputs come from the device function the
+ * offline kernel uses: the pushes of a recording, concatenated, are eg_resample(delay = D) on it bit for bit. */
+int64_t eg_resample_stream_state_bytes(int32_t rows, int32_t rate_in, int32_t rate_out);
+int eg_resample_stream_reset(void* state, int32_t rows, int32_t rate_in, int32_t rate_out, const int32_t* row_mask, void* stream);
+int eg_resample_stream_push(void* state, int32_t rows, int32_t rate_in, int32_t rate_out, const float* d_bank, const float* chunk_in,
+                            int32_t hop_in, const int32_t* ends_in, float* out, int32_t hop_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Beat-alignment score = model/Beat_score_v2.py alignment(sigma, order): load_audio + load_pose +
  * calculate_align for a batch of clips (test_emotion_gesture_diversity_iterative.py:241-248)
  * ------------------------------------------------------------------------------------------ */

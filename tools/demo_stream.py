@@ -7,7 +7,9 @@ one GestureStream, one row leaving and rejoining with a second recording while t
 
 all of it ONE captured hipGraph replayed per push.  Every row's emitted rows followed by its tail are checked to EQUAL the track
 harness.synthesize gives for the same recording.  Weights are synthetic (integer hash), so the poses carry no meaning.
-usage: demo_stream.py [rows=4] [seconds=20]"""
+With --audio-rate HZ the recordings are made at that rate and the stream is opened with audio_rate=HZ: every push carries hop * M / L samples,
+a StreamResampler runs first inside the same graph, and the rows equal synthesize on resample_audio(recording, HZ, delay=stream_delay(HZ)).
+usage: demo_stream.py [rows=4] [seconds=20] [--audio-rate HZ]"""
 import os
 import sys
 import time
@@ -20,19 +22,28 @@ from emotiongestures_amd.builders import build_mirror
 from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
 from emotiongestures_amd.synth import load_synth_weights, synth_audio
 
+from emotiongestures_amd import resample as R_
+
+RATE = 16000
+if "--audio-rate" in sys.argv:
+    i = sys.argv.index("--audio-rate")
+    RATE = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
+AR = {"audio_rate": RATE} if RATE != 16000 else {}
 U = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 20.0
 dev = torch.device("cuda:0")
 FRAMES, POSE_DIM, PRIOR, FPS = 34, 126, 4, 15
-total = int(seconds * 16000)
+total = int(seconds * RATE)                              # samples per recording at the caller's rate
+to16 = lambda n: R_.out_length(n, RATE) if AR else n
 
 gen = build_mirror("spatial", FRAMES, POSE_DIM, PRIOR, PRIOR, seed=7, precision="bf16x3").to(dev)
 vae = load_synth_weights(MLP_Reconstruct_v3(frames=FRAMES), 7).eval().to(dev)
-stream = H.open_stream((gen, vae), U, torch.zeros(U, PRIOR, POSE_DIM, device=dev))
-hop = stream.hop
-W = (total - 1) // hop + 1                               # windows per recording = pushes that carry its audio
+stream = H.open_stream((gen, vae), U, torch.zeros(U, PRIOR, POSE_DIM, device=dev), **AR)
+hop, hop16 = stream.hop_in, stream.hop                    # samples per push at the caller's rate and at 16 kHz
+W = (to16(total) - 1) // hop16 + 1                               # windows per recording = pushes that carry its audio
 short = total // 2                                       # the leaving row's first recording; its second one has `short` samples too
-W_short = (short - 1) // hop + 1
+W_short = (to16(short) - 1) // hop16 + 1
 leaver = U - 1
 
 audio = torch.from_numpy(synth_audio(U, total, seed=90)).to(dev)
@@ -87,10 +98,11 @@ for u in range(U):
         # synthesize on a batch of two recordings of this length (chunk invariance is stated from two clips up): this one and a copy
         seedp = (seed2 if i == 1 else torch.zeros_like(seed2))[u]
         zz = torch.stack(zs[u][i])[None].expand(2, n_win, 32).contiguous()
-        want = H.synthesize((gen, vae), torch.stack([a[:T], a[:T]]), text[u][None, None].expand(2, n_win, 60).contiguous(), torch.stack([seedp, seedp]),
+        a16 = R_.resample_audio(a[:T].contiguous(), RATE, delay=R_.stream_delay(RATE)) if AR else a[:T]
+        want = H.synthesize((gen, vae), torch.stack([a16, a16]), text[u][None, None].expand(2, n_win, 60).contiguous(), torch.stack([seedp, seedp]),
                             labels=labels[u][None].expand(2, 8).contiguous(), z=zz, windows=n_win, mel=stream.mel)["track"][0]
         same = torch.equal(got, want)
         ok &= same
-        print(f"row {u} recording {i}: {T / 16000:.1f} s -> {n_win} windows -> track {tuple(got.shape)}; equals harness.synthesize: {same}")
-print(f"steady-state push (one graph replay + copies, synchronised): {1e3 * sorted(t_steps)[len(t_steps) // 2]:.2f} ms for {hop / 16000:.1f} s of audio per row")
+        print(f"row {u} recording {i}: {T / RATE:.1f} s -> {n_win} windows -> track {tuple(got.shape)}; equals harness.synthesize: {same}")
+print(f"steady-state push (one graph replay + copies, synchronised): {1e3 * sorted(t_steps)[len(t_steps) // 2]:.2f} ms for {hop / RATE:.1f} s of audio per row")
 sys.exit(0 if ok else 1)

@@ -13,7 +13,9 @@ call also returns the beat-alignment score of each track against its own audio (
 With --diversity (and --draws R, R >= 2) the draws call also returns the take diversity of every recording: the mean pairwise distance of its
 R takes in FGD feature space (takes.take_diversity, fp64 on the GPU, in the unit of one generator window), and the script shows the FGD of
 whole tracks from the same features (takes.track_features -> FrechetAccumulator).
-usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--out tracks.npz]"""
+With --audio-rate HZ (48000, 44100, 24000, ...) the test signal is made at that rate and every call gets audio_rate=HZ: the recordings are
+resampled to 16 kHz on the GPU (resample.resample_audio) before anything else runs; lengths are then counted in samples at HZ.
+usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--out tracks.npz]"""
 import os
 import sys
 import time
@@ -23,11 +25,12 @@ import numpy as np
 import torch
 
 from emotiongestures_amd import harness as H
+from emotiongestures_amd import resample as R_
 from emotiongestures_amd.builders import build_mirror
 from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
 from emotiongestures_amd.synth import load_synth_weights, synth_audio
 
-argv, DRAWS, OUT, BEAT, DIVERSITY = [], 0, None, False, False
+argv, DRAWS, OUT, BEAT, DIVERSITY, RATE = [], 0, None, False, False, 16000
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--draws":
@@ -36,6 +39,8 @@ for a in it:
         BEAT = True
     elif a == "--diversity":
         DIVERSITY = True
+    elif a == "--audio-rate":
+        RATE = int(next(it))
     elif a == "--out":
         OUT = next(it)
     else:
@@ -50,10 +55,12 @@ if BEAT:
     FRAMES, POSE_DIM, PRIOR = 60, 282, 10               # BEAT: 60 poses of 282 columns, 10 of them the prior
 HOP = FRAMES - PRIOR
 hop_samples = int(round(HOP * 16000 / FPS))              # 30 poses = 2 s = 32 000 samples
-total = int(seconds * 16000)
+total_in = int(seconds * RATE)                            # samples per recording as the caller has them
+AR = {"audio_rate": RATE} if RATE != 16000 else {}
+total = R_.out_length(total_in, RATE) if AR else total_in    # ... and at the model's 16 kHz
 W = (total - 1) // hop_samples + 1                       # every window starts inside the recording; the last is completed by mirroring
 
-audio = torch.from_numpy(synth_audio(U, total, seed=90)).to(dev)
+audio = torch.from_numpy(synth_audio(U, total_in, seed=90)).to(dev)
 text = torch.zeros(U, W, 60, dtype=torch.int64, device=dev)
 seed_pose = torch.zeros(U, PRIOR, POSE_DIM, device=dev)
 labels = torch.nn.functional.one_hot(torch.arange(U) % 8, 8).float().to(dev)     # one emotion per recording
@@ -61,14 +68,16 @@ labels = torch.nn.functional.one_hot(torch.arange(U) % 8, 8).float().to(dev)    
 gen = build_mirror("spatial", FRAMES, POSE_DIM, PRIOR, PRIOR, seed=7, precision="bf16x3").to(dev)
 vae = load_synth_weights(MLP_Reconstruct_v3(frames=FRAMES), 7).eval().to(dev)
 z = torch.randn(U, W, 32)
-out = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, want_windows=True)          # warm-up (packs weights, allocates workspaces)
+out = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, want_windows=True, **AR)          # warm-up (packs weights, allocates workspaces)
 torch.cuda.synchronize()
 t0 = time.perf_counter()
-out = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, want_windows=True, beat=BEAT)
+out = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, want_windows=True, beat=BEAT, **AR)
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 
 track, windows = out["track"], out["windows"]
+if AR:
+    print(f"--audio-rate {RATE}: L / M = {R_.ratio(RATE)}, {total_in} samples -> {tuple(out['audio'].shape)} at 16 kHz on the device")
 print(f"{U} recordings x {seconds:.0f} s -> {W} windows of {FRAMES} poses (hop {HOP}) -> track {tuple(track.shape)} = {track.shape[1] / FPS:.1f} s at {FPS} fps")
 step = (track[:, 1:] - track[:, :-1]).norm(dim=2)                       # pose change per frame
 seams = torch.tensor([w * HOP + j for w in range(1, W) for j in range(PRIOR + 1)]) - 1
@@ -82,13 +91,13 @@ if BEAT:
 # Recordings of unequal length in one call: recording u keeps (u + 1) / U of the audio.  Step s runs only the recordings that still have a
 # window s; the track is padded to the longest recording and zero past each recording's own end.
 if U > 1:
-    lengths = [max(1, total * (u + 1) // U) for u in range(U)]
-    rag = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, lengths=lengths, beat=BEAT)
+    lengths = [max(1, total_in * (u + 1) // U) for u in range(U)]
+    rag = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, lengths=lengths, beat=BEAT, **AR)
     torch.cuda.synchronize()
     if BEAT:
         print(f"--beat: recordings of unequal length, each scored on its own samples and poses: {[round(float(v), 4) for v in rag['beat'].cpu()]}")
     frames = rag["track_frames"].tolist()
-    print(f"lengths {[round(v / 16000, 1) for v in lengths]} s -> windows {rag['windows_per']} -> track {tuple(rag['track'].shape)}, frames per recording {frames}; "
+    print(f"lengths {[round(v / RATE, 1) for v in lengths]} s -> windows {rag['windows_per']} -> track {tuple(rag['track'].shape)}, frames per recording {frames}; "
           f"rows past a recording's end are zero: {all(not bool(rag['track'][u, frames[u]:].any()) for u in range(U))}; "
           f"the longest recording against the rectangular call's: rel-L2 {float((rag['track'][U - 1] - track[U - 1]).norm() / track[U - 1].norm()):.1e} "
           f"(its last steps run alone, at batch 1)")
@@ -99,10 +108,10 @@ if DRAWS > 0:
     labels_r = labels_r[:, :, None, :].expand(U, DRAWS, W, 8).to(dev)
     zr = torch.randn(U, DRAWS, W, 32)
     fgd = load_synth_weights(H.MLP_Reconstruct(pose_dim=POSE_DIM), 7).eval().to(dev) if DIVERSITY else None
-    H.synthesize((gen, vae), audio, text, seed_pose, labels=labels_r, z=zr, draws=DRAWS, diversity=fgd)    # warm-up
+    H.synthesize((gen, vae), audio, text, seed_pose, labels=labels_r, z=zr, draws=DRAWS, diversity=fgd, **AR)    # warm-up
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    div = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels_r, z=zr, draws=DRAWS, beat=BEAT, diversity=fgd)
+    div = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels_r, z=zr, draws=DRAWS, beat=BEAT, diversity=fgd, **AR)
     torch.cuda.synchronize()
     dt_r = time.perf_counter() - t0
     if BEAT:
