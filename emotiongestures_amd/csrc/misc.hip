@@ -4,7 +4,7 @@
 
 namespace {
 
-// ---- LayerNorm (Full_model/SubLayers.py:55-57,80-82): one wave per row, two-pass in registers ----------
+// ---- LayerNorm (Full_model/SubLayers.py:55-57,80-82): one wave per row, two-pass (corrected mean, then variance) in registers ----------
 template <int NV>   // NV f4 per lane (D <= NV*256)
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                         const float* __restrict__ b, float* __restrict__ y, int rows, int D,
@@ -21,7 +21,19 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
         v[i] = q < nq ? xr[q] : (f4){0.f, 0.f, 0.f, 0.f};
         s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
     }
-    const float mean = wave_sum(s) / (float)D;
+    // The mean in two steps: the fp32 sum of D values carries an error of a few ulp of the mean, which 1 / sqrt(var + eps) multiplies (a constant
+    // row: by 1e3, where the output should be beta).  The residuals x - m0 are small, so their sum corrects m0 to the rounding of the exact mean.
+    const float m0 = wave_sum(s) / (float)D;
+    float c = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int q = lane + i * 64;
+        if (q < nq) {
+            const f4 d = v[i] - m0;
+            c += (d[0] + d[1]) + (d[2] + d[3]);
+        }
+    }
+    const float mean = m0 + wave_sum(c) / (float)D;
     float ss = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -63,7 +75,10 @@ __global__ __launch_bounds__(256) void layernorm_any_kernel(const float* __restr
     const float* xr = x + (size_t)row * D;
     float s = 0.f;
     for (int i = lane; i < D; i += 64) s += xr[i];
-    const float mean = wave_sum(s) / (float)D;
+    const float m0 = wave_sum(s) / (float)D;
+    float c = 0.f;
+    for (int i = lane; i < D; i += 64) c += xr[i] - m0;
+    const float mean = m0 + wave_sum(c) / (float)D;            // two-step mean, as in layernorm_kernel
     float ss = 0.f;
     for (int i = lane; i < D; i += 64) { const float d = xr[i] - mean; ss += d * d; }
     const float rstd = 1.0f / sqrtf(wave_sum(ss) / (float)D + eps);
@@ -342,7 +357,7 @@ __global__ __launch_bounds__(64) void tm_apply_kernel(const float* __restrict__ 
 }
 
 // ---- CVAE 1-D convolutions (CAVE/BEAT_CVAE.py:318-332,355-369), layout [n][C][L] ----------------------------
-// y[n,co,l] = post( bias[co] + sum_{ci,k} w[co,ci,k] x[n,ci,l*stride + k - pad] );  post = LeakyReLU(0.2) then BN affine
+// y[n,co,l] = post( bias[co] + sum_{ci,k} w[co,ci,k] x[n,ci,l*stride + k - pad] );  post = LeakyReLU(0.2) (act) then BN affine (scale != NULL)
 // One workgroup = (sample, 64 output positions, 4*COG output channels): the input tile lives in LDS, each wave owns
 // COG output channels (wave-uniform => the weight reads are scalar loads) accumulated in registers, so every LDS read of
 // x is reused COG times.
@@ -393,10 +408,8 @@ __global__ __launch_bounds__(256) void conv1d_kernel(const float* __restrict__ x
             const int co = co0 + j * 4 + r;
             if (co < Cout) {
                 float s = acc[j][r];
-                if (act) {
-                    s = s > 0.f ? s : 0.2f * s;
-                    if (scale) s = s * scale[co] + shift[co];
-                }
+                if (act) s = s > 0.f ? s : 0.2f * s;
+                if (scale) s = s * scale[co] + shift[co];      // the affine does not depend on act
                 y[((size_t)n * Cout + co) * Lout + l] = s;
             }
         }

@@ -322,7 +322,8 @@ def add_rows(a, table, period=0):
 
 
 def conv1d(x, weight, bias, stride=1, padding=0, leaky=False, scale=None, shift=None):
-    """nn.Conv1d on [n, cin, l] (contiguous) with an optional LeakyReLU(0.2) [+ per-channel affine] epilogue (eg_conv1d)."""
+    """nn.Conv1d on [n, cin, l] (contiguous) with an optional LeakyReLU(0.2) (leaky) and an optional per-channel affine y*scale + shift
+    (scale and shift together) as the epilogue, in that order and each on its own: leaky=False with a scale is conv -> affine (eg_conv1d)."""
     lib = L.load()
     x = _need_cuda(x, "x").contiguous()
     dev = x.device

@@ -717,7 +717,8 @@ typedef struct EgLinearArgs {
 } EgLinearArgs;
 int eg_linear_ex(const EgLinearArgs* args, void* stream);
 
-/* nn.LayerNorm(D, eps) over the last axis (Full_model/SubLayers.py:55-57,80-82).  rows x D, D%4==0, D<=2048. */
+/* nn.LayerNorm(D, eps) over the last axis (Full_model/SubLayers.py:55-57,80-82).  rows x D, 1 <= D <= 2048 (else
+ * EG_ERR_UNSUPPORTED); D % 4 == 0 takes the 16-byte kernel, any other D (the 282-wide discriminator) a scalar one with the same two-pass order. */
 int eg_layernorm(const float* x, const float* gamma, const float* beta, float* y, int32_t rows, int32_t d,
                  float eps, void* stream);
 /* The same with a second output: y as bf16 (hi, lo) tile-planar images [ceil(rows/64)][d/8][64][8] (eg_split_tiles layout, d % 64 == 0) for the
@@ -776,8 +777,10 @@ int eg_add_rows(const float* a, const float* table, float* out, int64_t rows, in
 int eg_reparameterize(const float* mu, const float* logvar, const float* eps, float* z, int64_t n, void* stream);
 
 /* nn.Conv1d over [n, cin, lin] -> [n, cout, lout], lout = (lin + 2*pad - k)/stride + 1, weight [cout, cin, k] (PyTorch layout):
- * y = bias + conv(x); act != 0: LeakyReLU(0.2), then (scale != NULL) y*scale[co] + shift[co]  -- the CVAE's conv -> LeakyReLU -> BN
- * order (CAVE/BEAT_CVAE.py:318-332); MotionAE's conv -> BN -> LeakyReLU (model/motion_ae.py:8-31) folds its BN into w / bias.
+ * y = bias + conv(x);  if act != 0: y = LeakyReLU(0.2)(y);  if scale != NULL: y = y*scale[co] + shift[co].  The two steps are independent:
+ * act == 0 with a scale applies the affine to the plain convolution (scale and shift come together, else EG_ERR_BAD_ARG).  act + scale is the
+ * CVAE's conv -> LeakyReLU -> BN order (CAVE/BEAT_CVAE.py:318-332); MotionAE's conv -> BN -> LeakyReLU (model/motion_ae.py:8-31) folds its BN
+ * into w / bias.
  * The input tile and the weights of one workgroup must fit 160 KB of LDS (else EG_ERR_UNSUPPORTED). */
 int eg_conv1d(const float* x, const float* w, const float* bias, const float* scale, const float* shift, float* y, int32_t n,
               int32_t cin, int32_t cout, int32_t lin, int32_t k, int32_t stride, int32_t pad, int32_t act, void* stream);
