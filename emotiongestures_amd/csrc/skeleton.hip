@@ -1,0 +1,318 @@
+// Skeleton output (include/emogest.h: eg_skeleton_check, eg_skeleton_out_frames, eg_skeleton_tile_frames, eg_skeleton_joints,
+// eg_skeleton_dir_vec): whole gesture tracks in the model's coordinates (K bone direction vectors per frame) -> joint positions, and back.
+//   forward   x_k = track[b, t, 3k .. 3k+2] (+ mean_k) (unit: / max(|x_k|, 1e-12));  p[0] = 0,  p[child_k] = p[parent_k] + len_k * x_k in table order;
+//             output frame k' of a row with n valid frames: lo = min(floor(k' M / L), n - 2), f = (k' M - lo L) / L, joints = p(lo) + (p(lo+1) - p(lo)) f
+//             (linear interpolation, extrapolated past the last frame; L / M = 1: joints = p(k') and nothing is blended); zeros from ceil(n L / M) on.
+//   inverse   d = p[child_k] - p[parent_k], d / max(|d|, 1e-12) (- mean_k); zeros from frame n on.
+// Both are memory-bound streams: a workgroup stages the source frames of a tile of TF output frames through LDS with 16-byte loads (the span
+// starts up to 3 floats early, as in resample.hip: 3K and 3J are no multiples of 4), walks the tree with one thread per (source frame,
+// coordinate) column of a transposed LDS tile p[joint][column] -- a thread's parent reads are its own earlier writes, so the chain needs no
+// barrier, and the rows of the tile are conflict-free -- and writes the outputs coalesced, 16 bytes per lane where a quad lies inside the tile.
+// The bone table is an argument, read once per workgroup; nothing about a particular body is built in.  Every output element has one owning
+// thread; plain vector stores, no atomics, nothing device-scope; the grid depends on the shapes only.
+#include "common.h"
+#include <math.h>
+
+namespace {
+
+constexpr int TF = EG_SKELETON_TILE_FRAMES;             // output frames of one workgroup
+constexpr int SLOTS = TF + 2;                           // source frames of one pass: TF output frames at L >= M touch at most TF + 1
+constexpr int NC = 3 * SLOTS;                           // columns of the joint tile: (source frame, coordinate)
+constexpr int THREADS = 128;
+constexpr int MAX_K = EG_SKELETON_MAX_BONES;
+constexpr int MAX_LM = EG_SKELETON_MAX_FACTOR;
+constexpr int TAB = 64;                                 // LDS words per table column
+constexpr int HEAD = 3 * TAB + 3 * TAB;                 // parent | child | length | mean [3 * 64]
+static_assert(NC <= THREADS, "one thread per column of the joint tile");
+static_assert(MAX_K < TAB, "table columns hold K <= 63 bones");
+
+__host__ __device__ inline int round4(int v) { return (v + 3) & ~3; }
+__host__ __device__ inline long long out_frames(long long n, int L, int M) { return (n * L + M - 1) / M; }
+
+struct Args {
+    const float* src;                                   // track [B, T, 3K] (forward) / joints [B, T, J, 3] (inverse)
+    const int* table;                                   // device words: parent [K] | child [K] | length (fp32 bits) [K]
+    const int* frames;                                  // device [B / draws] or null
+    const float* mean;                                  // device [3K] or null
+    float* dst;
+    int B, T, K, draws, frame_unit, L, M, tiles;
+    long long T_out;
+};
+
+// Floats [g0, g1) of base (16-byte aligned; `total` floats in all) -> lds[g - (g0 & ~3)].  Whole quads: the floats before g0 and after g1 that
+// share a quad with the span are copied too (never used); nothing past `total` is read.
+__device__ __forceinline__ void stage_span(const float* __restrict__ base, long long g0, long long g1, long long total, float* lds) {
+    const long long lo4 = g0 & ~3ll;
+    for (long long q = lo4 + 4ll * threadIdx.x; q < g1; q += 4ll * THREADS) {
+        f4 v;
+        if (q + 3 < total) {
+            v = *reinterpret_cast<const f4*>(base + q);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = q + e < total ? base[q + e] : 0.f;
+        }
+        *reinterpret_cast<f4*>(lds + (q - lo4)) = v;
+    }
+}
+
+// base[g] = f(fr, r) for g in [g0, g1), where g - origin = fr * row + r: 16-byte stores for the quads inside the range, single floats at its two
+// ends.  One division per quad; (fr, r) then step with the element.
+template <class F>
+__device__ __forceinline__ void store_range(float* __restrict__ base, long long origin, int row, long long g0, long long g1, F f) {
+    for (long long q = (g0 & ~3ll) + 4ll * threadIdx.x; q < g1; q += 4ll * THREADS) {
+        const int rel = (int)(q - origin);                                      // >= -3: g0 >= origin
+        int fr = rel >= 0 ? rel / row : -1;
+        int r = rel >= 0 ? rel - fr * row : rel + row;
+        const bool whole = q >= g0 && q + 4 <= g1;
+        f4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const bool in = whole || (q + e >= g0 && q + e < g1);
+            v[e] = in ? f(fr, r) : 0.f;
+            if (!whole && in) base[q + e] = v[e];
+            if (++r == row) { r = 0; ++fr; }
+        }
+        if (whole) *reinterpret_cast<f4*>(base + q) = v;
+    }
+}
+
+__device__ __forceinline__ int valid_frames(const Args& a, int b) {
+    if (!a.frames) return a.T;
+    const long long v = (long long)a.frames[b / a.draws] * a.frame_unit;
+    return (int)(v < 0 ? 0 : (v > a.T ? a.T : v));
+}
+
+// The host table is checked; the device copy is the caller's.  Its joint numbers index LDS, so they are clamped to 0..K here: with a stale
+// upload the result is unspecified, but every access stays inside the tile.
+__device__ __forceinline__ void load_table(const Args& a, int* ta, int* tb, float* tl, float* mn) {
+    for (int k = threadIdx.x; k < a.K; k += THREADS) {
+        ta[k] = min(max(a.table[k], 0), a.K);
+        tb[k] = min(max(a.table[a.K + k], 0), a.K);
+        tl[k] = __int_as_float(a.table[2 * a.K + k]);
+    }
+    if (a.mean)
+        for (int r = threadIdx.x; r < 3 * a.K; r += THREADS) mn[r] = a.mean[r];
+}
+
+// grid: (tile of TF output frames) x row, flattened.  NATIVE: L / M = 1.
+template <bool UNIT, bool NATIVE>
+__global__ __launch_bounds__(THREADS) void skeleton_joints_kernel(const Args a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int K = a.K, D = 3 * K, J3 = 3 * (K + 1), tid = threadIdx.x;
+    int* ta = reinterpret_cast<int*>(lds);
+    int* tb = ta + TAB;
+    float* tl = lds + 2 * TAB;
+    float* mn = lds + 3 * TAB;
+    float* xin = lds + HEAD;
+    float* pj = xin + round4(SLOTS * D + 8);
+    const int b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
+    const long long k0 = (long long)tile * TF;
+    const int cnt = (int)(a.T_out - k0 < TF ? a.T_out - k0 : TF);
+    const int n = valid_frames(a, b);
+    const long long n_out = NATIVE ? n : out_frames(n, a.L, a.M);
+    const int live = (int)(n_out - k0 < 0 ? 0 : (n_out - k0 < cnt ? n_out - k0 : cnt));
+    const long long out0 = ((long long)b * a.T_out + k0) * J3;
+    if (live < cnt) store_range(a.dst, out0, J3, out0 + (long long)live * J3, out0 + (long long)cnt * J3, [](int, int) { return 0.f; });
+    if (live == 0) return;
+    load_table(a, ta, tb, tl, mn);
+    for (int c = tid; c < NC; c += THREADS) pj[c] = 0.f;                        // the root joint, every column
+    const bool has_mean = a.mean != nullptr;
+    const long long total = (long long)a.B * a.T * D;
+    const int L = a.L, M = a.M;
+    auto seg = [&](long long kk) -> long long {                                 // first source frame of output frame kk
+        if (NATIVE) return kk;
+        if (n < 2) return 0;
+        const long long lo = kk * M / L;
+        return lo < n - 2 ? lo : n - 2;
+    };
+    for (int i = 0; i < live;) {
+        // outputs [i, i1) of the tile from the source frames [s_base, s_base + nslots): as many outputs as SLOTS source frames reach
+        const long long s_base = seg(k0 + i);
+        int i1 = live;
+        if (!NATIVE && M > L) {
+            const long long jmax = ((s_base + SLOTS - 1) * L - 1) / M - k0;     // last output whose segment starts at or before s_base + SLOTS - 2
+            i1 = jmax + 1 < live ? (int)(jmax + 1) : live;
+            i1 = i1 > i ? i1 : i + 1;
+        }
+        const int nslots = (int)(seg(k0 + i1 - 1) - s_base) + ((NATIVE || n < 2) ? 1 : 2);
+        // no barrier before a later pass: the one after the previous chain ended its reads of xin, the one below precedes every write of pj
+        const long long g0 = ((long long)b * a.T + s_base) * D;
+        stage_span(a.src, g0, g0 + (long long)nslots * D, total, xin);
+        __syncthreads();
+        float* x = xin + (int)(g0 & 3);
+        if (UNIT) {                                                             // one thread per (source frame, bone), in place
+            for (int w = tid; w < nslots * K; w += THREADS) {
+                const int s = w / K, k = w - s * K;
+                float* v = x + s * D + 3 * k;
+                float v0 = v[0], v1 = v[1], v2 = v[2];
+                if (has_mean) { v0 += mn[3 * k]; v1 += mn[3 * k + 1]; v2 += mn[3 * k + 2]; }
+                const float d = fmaxf(sqrtf(v0 * v0 + v1 * v1 + v2 * v2), 1e-12f);
+                v[0] = v0 / d; v[1] = v1 / d; v[2] = v2 / d;
+            }
+            __syncthreads();
+        }
+        if (tid < 3 * nslots) {                                                 // the chain: this thread's column of every joint
+            const int s = tid / 3, c = tid - 3 * s;
+            const float* xs = x + s * D + c;
+            float* pc = pj + tid;
+            float xv = xs[0];
+            for (int k = 0; k < K; ++k) {
+                const float xn = k + 1 < K ? xs[3 * (k + 1)] : 0.f;             // the next bone's vector is in flight while this one is added
+                float v = xv;
+                if (!UNIT && has_mean) v += mn[3 * k + c];
+                pc[tb[k] * NC] = fmaf(tl[k], v, pc[ta[k] * NC]);
+                xv = xn;
+            }
+        }
+        __syncthreads();
+        store_range(a.dst, out0, J3, out0 + (long long)i * J3, out0 + (long long)i1 * J3, [&](int fr, int r) {
+            const int jt = r / 3, c = r - 3 * jt;
+            const float* row = pj + jt * NC + c;
+            if (NATIVE) return row[3 * (fr - i)];
+            if (n < 2) return row[0];
+            const long long kk = k0 + fr, lo = seg(kk);
+            const float f = (float)(kk * M - lo * L) / (float)L;
+            const float p0 = row[3 * (int)(lo - s_base)], p1 = row[3 * (int)(lo - s_base) + 3];
+            return fmaf(p1 - p0, f, p0);
+        });
+        i = i1;
+    }
+}
+
+// grid: (tile of TF frames) x row, flattened.
+__global__ __launch_bounds__(THREADS) void skeleton_dir_vec_kernel(const Args a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int K = a.K, D = 3 * K, J3 = 3 * (K + 1);
+    int* ta = reinterpret_cast<int*>(lds);
+    int* tb = ta + TAB;
+    float* tl = lds + 2 * TAB;
+    float* mn = lds + 3 * TAB;
+    float* pin = lds + HEAD;
+    const int b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
+    const long long t0 = (long long)tile * TF;
+    const int cnt = (int)(a.T - t0 < TF ? a.T - t0 : TF);
+    const int n = valid_frames(a, b);
+    const int live = (int)(n - t0 < 0 ? 0 : (n - t0 < cnt ? n - t0 : cnt));
+    const long long out0 = ((long long)b * a.T + t0) * D;
+    if (live < cnt) store_range(a.dst, out0, D, out0 + (long long)live * D, out0 + (long long)cnt * D, [](int, int) { return 0.f; });
+    if (live == 0) return;
+    load_table(a, ta, tb, tl, mn);
+    const bool has_mean = a.mean != nullptr;
+    const long long g0 = ((long long)b * a.T + t0) * J3;
+    stage_span(a.src, g0, g0 + (long long)live * J3, (long long)a.B * a.T * J3, pin);
+    __syncthreads();
+    const float* p = pin + (int)(g0 & 3);
+    store_range(a.dst, out0, D, out0, out0 + (long long)live * D, [&](int fr, int r) {
+        const int k = r / 3, c = r - 3 * k;
+        const float* pa = p + fr * J3 + 3 * ta[k];
+        const float* pb = p + fr * J3 + 3 * tb[k];
+        const float d0 = pb[0] - pa[0], d1 = pb[1] - pa[1], d2 = pb[2] - pa[2];
+        const float d = fmaxf(sqrtf(d0 * d0 + d1 * d1 + d2 * d2), 1e-12f);
+        const float v = (c == 0 ? d0 : (c == 1 ? d1 : d2)) / d;
+        return has_mean ? v - mn[r] : v;
+    });
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------------------
+int check_table(const char* who, const int32_t* parents, const int32_t* children, const float* lengths, int K) {
+    EG_REQUIRE(parents && children && lengths, EG_ERR_BAD_ARG, "%s: null parents / children / lengths", who);
+    EG_REQUIRE(K >= 1 && K <= MAX_K, EG_ERR_UNSUPPORTED, "%s: bones=%d (1..%d)", who, K, MAX_K);
+    bool made[MAX_K + 1] = {};
+    made[0] = true;                                                             // the root
+    for (int k = 0; k < K; ++k) {
+        const int a = parents[k], b = children[k];
+        EG_REQUIRE(b != 0, EG_ERR_BAD_ARG, "%s: bone %d: child is joint 0, the root", who, k);
+        EG_REQUIRE(b >= 1 && b <= K, EG_ERR_BAD_ARG, "%s: bone %d: child=%d outside the joints 1..%d", who, k, b, K);
+        EG_REQUIRE(!made[b], EG_ERR_BAD_ARG, "%s: bone %d: child=%d is the child of an earlier bone (used twice)", who, k, b);
+        EG_REQUIRE(a >= 0 && a <= K && made[a], EG_ERR_BAD_ARG,
+                   "%s: bone %d: parent=%d is neither the root nor the child of an earlier bone (the table must be in topological order)", who, k, a);
+        EG_REQUIRE(isfinite(lengths[k]) && lengths[k] > 0.f, EG_ERR_BAD_ARG, "%s: bone %d: length=%g (need finite and > 0)", who, k, (double)lengths[k]);
+        made[b] = true;
+    }
+    return EG_OK;
+}
+
+int gcd_int(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
+
+int reduce_rate(const char* who, int& L, int& M) {
+    EG_REQUIRE(L >= 1 && M >= 1, EG_ERR_BAD_ARG, "%s: rate L=%d / M=%d (need >= 1)", who, L, M);
+    const int g = gcd_int(L, M);
+    L /= g; M /= g;
+    EG_REQUIRE(L <= MAX_LM && M <= MAX_LM, EG_ERR_UNSUPPORTED, "%s: the frame-rate ratio L=%d / M=%d: supported up to max(L, M) <= %d", who, L, M, MAX_LM);
+    return EG_OK;
+}
+
+int common_checks(const char* who, const void* src, const void* dst, int B, int T, const int32_t* parents, const int32_t* children,
+                  const float* lengths, int K, const void* d_table, int draws, int frame_unit, const void* d_mean) {
+    EG_REQUIRE(src, EG_ERR_BAD_ARG, "%s: null input", who);
+    EG_REQUIRE(dst, EG_ERR_BAD_ARG, "%s: null output", who);
+    EG_REQUIRE(d_table, EG_ERR_BAD_ARG, "%s: null d_table", who);
+    int rc = check_table(who, parents, children, lengths, K);
+    if (rc != EG_OK) return rc;
+    EG_REQUIRE(eg_aligned16(src) && eg_aligned16(dst), EG_ERR_ALIGN, "%s: input / output not 16-byte aligned", who);
+    EG_REQUIRE((reinterpret_cast<uintptr_t>(d_table) & 3u) == 0 && (reinterpret_cast<uintptr_t>(d_mean) & 3u) == 0, EG_ERR_ALIGN,
+               "%s: d_table / d_mean not 4-byte aligned", who);
+    EG_REQUIRE(B >= 1 && T >= 1, EG_ERR_BAD_ARG, "%s: rows=%d frames=%d (need >= 1)", who, B, T);
+    EG_REQUIRE(draws >= 1 && B % draws == 0, EG_ERR_BAD_ARG, "%s: rows=%d is not a multiple of draws=%d", who, B, draws);
+    EG_REQUIRE(frame_unit >= 1, EG_ERR_BAD_ARG, "%s: frame_unit=%d (need >= 1)", who, frame_unit);
+    return EG_OK;
+}
+
+}  // namespace
+
+extern "C" int eg_skeleton_check(const int32_t* parents, const int32_t* children, const float* lengths, int32_t bones) {
+    return check_table("eg_skeleton_check", parents, children, lengths, bones);
+}
+
+extern "C" int64_t eg_skeleton_out_frames(int64_t n, int32_t L, int32_t M) {
+    int l = L, m = M;
+    if (n < 0 || n >= (1ll << 40) || reduce_rate("eg_skeleton_out_frames", l, m) != EG_OK) return -1;
+    return out_frames(n, l, m);
+}
+
+extern "C" int32_t eg_skeleton_tile_frames(void) { return TF; }
+
+extern "C" int eg_skeleton_joints(const float* track, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children, const float* lengths,
+                                  int32_t bones, const void* d_table, const int32_t* d_frames, int32_t draws, int32_t frame_unit,
+                                  const float* d_mean, int32_t unit, int32_t L, int32_t M, float* joints, int64_t out_stride, void* stream) {
+    const char* who = "eg_skeleton_joints";
+    int rc = common_checks(who, track, joints, rows, T, parents, children, lengths, bones, d_table, draws, frame_unit, d_mean);
+    if (rc != EG_OK) return rc;
+    int l = L, m = M;
+    rc = reduce_rate(who, l, m);
+    if (rc != EG_OK) return rc;
+    const long long t_out = out_frames(T, l, m);
+    EG_REQUIRE(out_stride >= t_out, EG_ERR_BAD_ARG, "%s: out_stride=%lld < %lld output frames of %d input frames at L=%d / M=%d", who,
+               (long long)out_stride, t_out, T, l, m);
+    const long long tiles = (out_stride + TF - 1) / TF;
+    EG_REQUIRE(tiles * rows <= 0x7fffffffll && (long long)rows * out_stride * 3 * (bones + 1) < (1ll << 40), EG_ERR_UNSUPPORTED,
+               "%s: rows=%d x out_stride=%lld: grid / index range", who, rows, (long long)out_stride);
+    Args a = {track, static_cast<const int*>(d_table), d_frames, d_mean, joints, rows, T, bones, draws, frame_unit, l, m, (int)tiles, out_stride};
+    const size_t lds = (size_t)(HEAD + round4(SLOTS * 3 * bones + 8) + (bones + 1) * NC) * sizeof(float);
+    const dim3 grid((unsigned)(tiles * rows)), block(THREADS);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool native = l == 1 && m == 1;
+    if (unit) {
+        if (native) hipLaunchKernelGGL((skeleton_joints_kernel<true, true>), grid, block, lds, st, a);
+        else hipLaunchKernelGGL((skeleton_joints_kernel<true, false>), grid, block, lds, st, a);
+    } else {
+        if (native) hipLaunchKernelGGL((skeleton_joints_kernel<false, true>), grid, block, lds, st, a);
+        else hipLaunchKernelGGL((skeleton_joints_kernel<false, false>), grid, block, lds, st, a);
+    }
+    return eg_check_launch("skeleton_joints");
+}
+
+extern "C" int eg_skeleton_dir_vec(const float* joints, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children, const float* lengths,
+                                   int32_t bones, const void* d_table, const int32_t* d_frames, int32_t draws, int32_t frame_unit,
+                                   const float* d_mean, float* dir_vec, void* stream) {
+    const char* who = "eg_skeleton_dir_vec";
+    int rc = common_checks(who, joints, dir_vec, rows, T, parents, children, lengths, bones, d_table, draws, frame_unit, d_mean);
+    if (rc != EG_OK) return rc;
+    const long long tiles = ((long long)T + TF - 1) / TF;
+    EG_REQUIRE(tiles * rows <= 0x7fffffffll && (long long)rows * T * 3 * (bones + 1) < (1ll << 40), EG_ERR_UNSUPPORTED,
+               "%s: rows=%d x frames=%d: grid / index range", who, rows, T);
+    Args a = {joints, static_cast<const int*>(d_table), d_frames, d_mean, dir_vec, rows, T, bones, draws, frame_unit, 1, 1, (int)tiles, T};
+    const size_t lds = (size_t)(HEAD + round4(TF * 3 * (bones + 1) + 8)) * sizeof(float);
+    hipLaunchKernelGGL(skeleton_dir_vec_kernel, dim3((unsigned)(tiles * rows)), dim3(THREADS), lds, static_cast<hipStream_t>(stream), a);
+    return eg_check_launch("skeleton_dir_vec");
+}

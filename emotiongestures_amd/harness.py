@@ -462,7 +462,8 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
                hop_samples: Optional[int] = None, n_samples: Optional[int] = None, windows: Optional[int] = None,
                z: Optional[torch.Tensor] = None, alpha: Optional[torch.Tensor] = None, fps: int = 15, sample_rate: int = 16000,
                want_windows: bool = False, want_aux: bool = False, mel=None, lengths=None, draws: Optional[int] = None,
-               beat: bool = False, diversity=None, audio_rate: Optional[int] = None) -> Dict[str, torch.Tensor]:
+               beat: bool = False, diversity=None, audio_rate: Optional[int] = None, joints=None, joints_mean=None,
+               joints_unit: bool = False, joints_fps=None) -> Dict[str, torch.Tensor]:
     """One gesture track per utterance from raw 16 kHz audio: windows -> mel -> optional CVAE sample per window -> roll-out.
 
     ``models = (generator, vae | None)``, eval mode, on the GPU.  ``audio [U, total_samples]``; ``text [U, W, 60]`` (the words of every
@@ -495,8 +496,26 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     ``sample_rate`` once on the device (resample.resample_audio: scipy's ``resample_poly`` design, ``max(L, M) <= 640``), then the path above
     runs unchanged on the result -- with ``lengths``, ``draws``, ``beat`` (scored against the resampled audio and its lengths) and
     ``diversity``; ``hop_samples`` / ``n_samples`` stay in model-rate samples.  The dict gains ``"audio"`` (the resampled signal) and, with
-    ``lengths``, ``"lengths"`` (its sample counts).  ``None`` or equal to ``sample_rate``: no launch and no extra keys."""
+    ``lengths``, ``"lengths"`` (its sample counts).  ``None`` or equal to ``sample_rate``: no launch and no extra keys.
+
+    ``joints=skeleton`` (a ``skeleton.Skeleton`` with ``3K == pose_dim``, e.g. ``skeleton.ted_expressive()``): adds ``"joints"``, the joint
+    positions of every returned track in metres -- ``[U, T', J, 3]``, or ``[U, R, T', J, 3]`` with ``draws`` -- and ``"joint_frames"`` (U ints):
+    ``skeleton.joints_from_tracks(out["track"], skeleton, frames, joints_mean, joints_unit, joints_fps)`` with recording u's own
+    ``W_u * (frames - prior_frames) + prior_frames`` valid poses, one launch.  ``joints_mean [pose_dim]``: the data set's mean direction vectors,
+    added first; ``joints_unit``: bones re-normalised to unit length; ``joints_fps=(src, dst)``: resampled linearly to the renderer's rate
+    (``T' = ceil(T * dst / src)``).  Works with ``lengths``, ``draws``, ``beat``, ``diversity`` and ``audio_rate``; without ``joints`` nothing
+    changes."""
     gen, vae = models
+    if joints is not None:
+        from . import skeleton as SK
+        if not isinstance(joints, SK.Skeleton):
+            raise L.EgError(f"synthesize: joints= takes a skeleton.Skeleton, got {type(joints).__name__}")
+        if joints.pose_dim != seed_pose.shape[-1]:
+            raise L.EgError(f"synthesize: joints=: the skeleton has K={joints.K} bones, 3K={joints.pose_dim} != pose_dim={seed_pose.shape[-1]} "
+                            "(the BEAT generators' 282 columns hold rotations, not bone direction vectors)")
+        SK.rate_ratio(joints_fps, "synthesize: joints_fps")                        # refuses an unsupported ratio before anything runs
+    elif joints_mean is not None or joints_unit or joints_fps is not None:
+        raise L.EgError("synthesize: joints_mean / joints_unit / joints_fps without joints=skeleton")
     _eval_only(gen)
     if beat and seed_pose.shape[-1] < 174:
         raise L.EgError(f"synthesize: beat=True: pose_dim={seed_pose.shape[-1]}: the beat joints are columns 18:42 and 150:174 (needs >= 174)")
@@ -550,6 +569,11 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
         with torch.no_grad():
             td = take_diversity(diversity, out["track"], span=c.frames)
         out["take_distance"], out["take_diversity"] = td["distance"], td["diversity"]
+    if joints is not None:
+        H = c.frames - c.prior_frames
+        with torch.no_grad():
+            out["joints"], out["joint_frames"] = SK.joints_from_tracks(out["track"], joints, frames=[int(w) * H + c.prior_frames for w in wp],
+                                                                       mean=joints_mean, unit=joints_unit, fps=joints_fps)
     return out
 
 

@@ -146,11 +146,19 @@ class GestureStream:
     `lag - 1` pushes, or ended and out of windows) is not valid in that step: zero rows, prior unchanged.  While no row is valid only the
     push kernels run and `rows` is None.  `ends[u] = m in [0, hop]` (host values: int, list or CPU tensor) ends row u in this push: only
     its first m samples are real.  `mel=None`: `push_spec(spec [U, n_mels, spec_len], text, ...)`, one ready window per call.
-    `hop_samples` / `n_samples` default to the generator's geometry as in harness.synthesize; `graph=True` replays one captured hipGraph."""
+    `hop_samples` / `n_samples` default to the generator's geometry as in harness.synthesize; `graph=True` replays one captured hipGraph.
+    `joints=skeleton` (a skeleton.Skeleton with 3K == pose_dim; `joints_mean [pose_dim]`, `joints_unit` as in skeleton.joints_from_tracks): every
+    step ends with one more launch (inside the graph) that leaves the joint positions of the rows just emitted in `last_joints [U, H, J, 3]`
+    -- zeros for a row that was not valid, None while `rows` is None; `push` returns what it returned.  `tail_joints()`: the joints of `tail()`.
+    `joints_fps` is refused: a frame-rate change needs the frame after the last one emitted."""
 
     def __init__(self, models: Tuple, rows: int, seed_pose: torch.Tensor, *, hop_samples: Optional[int] = None, n_samples: Optional[int] = None,
                  fps: int = 15, sample_rate: int = 16000, alpha: Optional[torch.Tensor] = None, graph: bool = True, want_windows: bool = False,
-                 draws: Optional[int] = None, audio_rate: Optional[int] = None):
+                 draws: Optional[int] = None, audio_rate: Optional[int] = None, joints=None, joints_mean=None, joints_unit: bool = False,
+                 joints_fps=None):
+        if joints_fps is not None:
+            raise L.EgError("GestureStream: joints_fps= is not supported (a frame-rate change needs the frame after the last one emitted, which a "
+                            "stream does not have yet); resample the joints of the finished track with skeleton.joints_from_tracks(..., fps=)")
         if draws is not None:
             raise L.EgError("GestureStream: draws= is not supported (a stream has one track per row); for several sampled tracks of a whole "
                             "recording call the rectangular synthesize(..., draws=R), or open the stream with each speaker's row repeated")
@@ -165,6 +173,15 @@ class GestureStream:
         self.H = self.F - self.P
         self.text_len, self.n_mels, self.spec_len = c["text_len"], c["n_mels"], c["spec_len"]
         self.U = int(rows)
+        self._sk, self._sk_mean, self._sk_unit = joints, None, bool(joints_unit)
+        if joints is not None:
+            from . import skeleton as SK
+            if not isinstance(joints, SK.Skeleton):
+                raise L.EgError(f"GestureStream: joints= takes a skeleton.Skeleton, got {type(joints).__name__}")
+            if joints.pose_dim != self.D:
+                raise L.EgError(f"GestureStream: joints=: the skeleton has K={joints.K} bones, 3K={joints.pose_dim} != pose_dim={self.D}")
+        elif joints_mean is not None or joints_unit:
+            raise L.EgError("GestureStream: joints_mean / joints_unit without joints=skeleton")
         if self.mel is not None:
             self.hop = int(round(self.H * sample_rate / fps)) if hop_samples is None else int(hop_samples)
             self.n = (self.spec_len - 1) * 512 if n_samples is None else int(n_samples)
@@ -191,6 +208,9 @@ class GestureStream:
         self.seed_pose = _need_cuda(seed_pose, "seed_pose").clone()
         self.alpha = None if alpha is None else _need_cuda(alpha, "alpha").clone()
         self.device = self.seed_pose.device
+        if self._sk is not None and joints_mean is not None:
+            from .skeleton import _mean_dev
+            self._sk_mean = _mean_dev(joints_mean, self._sk.K, self.device, "GestureStream: joints_mean")
         if self.mel is AUTO_MEL:
             from .engine import MelFrontEnd
             self.mel = MelFrontEnd(self.device)
@@ -217,6 +237,7 @@ class GestureStream:
         self.last_valid: List[bool] = [False] * self.U           # the host's verdict for the last step, and the window index per valid row
         self.last_windows: List[Optional[int]] = [None] * self.U
         self.last_window: Optional[torch.Tensor] = None          # with want_windows: the raw poses [U, F, D] of the last step
+        self.last_joints: Optional[torch.Tensor] = None          # with joints=: the joints [U, H, J, 3] of the rows just emitted (zeros for a row that was not valid)
         eng.stream_reset(self._state, *self._geom, self.seed_pose)
 
     # ---- engines, staleness ----
@@ -269,8 +290,12 @@ class GestureStream:
                 sampled = self.vae.sample(g["label"], z=g["z"], slot=self._slot)
             else:
                 sampled = g["sampled"] if use_sampled else None
-            return eng.stream_step(self._state, *self._geom, spec, g["text"], sampled, self.alpha, want_window=self.want_windows,
-                                   workspace=self._ws)
+            out = eng.stream_step(self._state, *self._geom, spec, g["text"], sampled, self.alpha, want_window=self.want_windows,
+                                  workspace=self._ws)
+            if self._sk is not None:                # one more launch after the hand-off: row u has valid[u] * H frames
+                from .skeleton import launch_joints
+                out["joints"] = launch_joints(out["rows"], self._sk, out["valid"], 1, self.H, self._sk_mean, self._sk_unit)
+            return out
 
     def _push_only(self):
         """The resampler's launches (with audio_rate), then the ring's: the part of a step that runs even when no row has a window."""
@@ -394,6 +419,7 @@ class GestureStream:
         # the host mirror follows the device: committed once the push has been enqueued (a launch or capture that raises leaves both where they were)
         self.plan.rows, self.last_valid, self.last_windows = rows, valid, [i["w"] for i in infos]
         self.last_window = out["window"].clone() if out is not None and self.want_windows else None
+        self.last_joints = out["joints"].clone() if out is not None and self._sk is not None else None
         if out is None:
             return None, torch.zeros(self.U, dtype=torch.int32, device=self.device)
         return out["rows"].clone(), out["valid"].clone()
@@ -447,6 +473,14 @@ class GestureStream:
     def tail(self) -> torch.Tensor:
         """[U, P, D]: every row's current prior = the last P rows of its track."""
         return self._engine().stream_tail(self._state, *self._geom)
+
+    def tail_joints(self) -> torch.Tensor:
+        """[U, P, J, 3]: the joints of `tail()` (a session opened with joints=)."""
+        if self._sk is None:
+            raise L.EgError("tail_joints: the session was opened without joints=skeleton")
+        from .skeleton import launch_joints
+        with torch.no_grad():
+            return launch_joints(self.tail(), self._sk, None, 1, 1, self._sk_mean, self._sk_unit)
 
     def finish(self, text, labels=None, z=None, sampled=None, last_chunk=None, ends=None) -> torch.Tensor:
         """End every row together and run R = text.shape[1] steps in all: `text [U, R, text_len]`, `labels [U, 8]` or `[U, R, 8]`, `z [U, R, 32]`

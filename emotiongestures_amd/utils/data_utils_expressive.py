@@ -1,3 +1,63 @@
-"""Mirror of the audio / pose helpers (utils/train_utils_BEAT.py:186-226, duplicated upstream in utils/data_utils_expressive.py:85-126)."""
+"""Mirror of the audio / pose helpers (utils/train_utils_BEAT.py:186-226, duplicated upstream in utils/data_utils_expressive.py:85-126) and of
+the skeleton conversions (utils/data_utils_expressive.py:12-67,153-201) on emotiongestures_amd.skeleton."""
+import numpy as np
+import torch
+
 from ..datapath import (calc_spectrogram_length_from_motion_length, extract_melspectrogram, make_audio_fixed_length,  # noqa: F401
                         resample_pose_seq)
+from ..skeleton import dir_vec_from_joints, joints_from_tracks, ted_expressive
+
+_ted = None
+
+
+def _body():
+    """The TED-Expressive skeleton, built on first use: the table is checked by the shared library, which importing this module (for the audio
+    helpers alone, say) must not need."""
+    global _ted
+    if _ted is None:
+        _ted = ted_expressive()
+    return _ted
+
+
+def __getattr__(name):
+    if name == "dir_vec_pairs":             # (parent joint, child joint, length in metres) per bone
+        return _body().dir_vec_pairs
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def _rows(x, tail, what, ranks):
+    """Split the trailing (42, 3) / (43, 3) axes off when present; -> (flat [..., 3n], leading shape)."""
+    n = tail // 3
+    if x.shape[-1] != 3:
+        if x.shape[-1] != tail:
+            raise ValueError(f"{what}: last axis {x.shape[-1]} is neither 3 nor {tail}")
+        lead = tuple(x.shape[:-1])
+    else:
+        if x.ndim < 2 or x.shape[-2] != n:
+            raise ValueError(f"{what}: shape {tuple(x.shape)} is not (..., {n}, 3)")
+        lead = tuple(x.shape[:-2])
+    if len(lead) + 2 not in ranks:
+        raise ValueError(f"{what}: shape {tuple(x.shape)}: {' / '.join(str(r) for r in ranks)}-D input as (..., {n}, 3)")
+    return x.reshape(lead + (tail,)), lead
+
+
+def convert_dir_vec_to_pose(vec):
+    """Direction vectors -> joint positions: ``(42, 3)``, ``(N, 42, 3)`` or ``(B, N, 42, 3)``, or the same with the last two axes flat (126)
+    -> ``(..., 43, 3)``.  numpy (or anything ``np.array`` takes) in: float64 numpy out, as upstream.  A CUDA tensor in: an fp32 CUDA tensor out,
+    through the kernel."""
+    cuda = isinstance(vec, torch.Tensor) and vec.is_cuda
+    x = vec if cuda else np.array(vec)
+    flat, lead = _rows(x, 126, "convert_dir_vec_to_pose", (2, 3, 4))
+    out = joints_from_tracks(flat.reshape((1, -1, 126)), _body())
+    return out.reshape(lead + (43, 3))
+
+
+def convert_pose_seq_to_dir_vec(pose):
+    """Joint positions ``(N, 43, 3)`` or ``(B, N, 43, 3)`` (or flat, 129) -> unit direction vectors ``(..., 42, 3)`` as a torch tensor (fp32, as
+    upstream; on the GPU for a CUDA tensor)."""
+    cuda = isinstance(pose, torch.Tensor) and pose.is_cuda
+    x = pose if cuda else np.asarray(pose.detach().numpy() if isinstance(pose, torch.Tensor) else pose)
+    flat, lead = _rows(x, 129, "convert_pose_seq_to_dir_vec", (3, 4))
+    out = dir_vec_from_joints(flat.reshape((1, -1, 43, 3)), _body())
+    out = out if cuda else torch.from_numpy(out).float()
+    return out.reshape(lead + (42, 3))

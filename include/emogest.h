@@ -464,6 +464,45 @@ int eg_resample_stream_push(void* state, int32_t rows, int32_t rate_in, int32_t 
                             int32_t hop_in, const int32_t* ends_in, float* out, int32_t hop_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Skeleton output: tracks of bone direction vectors <-> joint positions on the device (csrc/skeleton.hip)
+ * ------------------------------------------------------------------------------------------ */
+/* A skeleton is a table of K bones in topological order, 1 <= K <= EG_SKELETON_MAX_BONES, over J = K + 1 joints: bone k = (parents[k],
+ * children[k], lengths[k]); joint 0 is the root at the origin.  eg_skeleton_check (host only, no HIP call) refuses by name: K out of range,
+ * a child that is joint 0 or outside 1..K, a child used twice, a parent that is neither the root nor the child of an earlier bone, a
+ * length that is not finite and > 0.  The device copy d_table is 3K 32-bit words: parents [K] | children [K] | lengths [K] (fp32).
+ * eg_skeleton_out_frames: ceil(n * L / M) for the reduced ratio L / M (-1 for refused arguments: n < 0, L or M < 1, max(L, M) after
+ * reduction > EG_SKELETON_MAX_FACTOR).  eg_skeleton_tile_frames: EG_SKELETON_TILE_FRAMES. */
+#define EG_SKELETON_MAX_BONES 63
+#define EG_SKELETON_MAX_FACTOR 64
+#define EG_SKELETON_TILE_FRAMES 32  /* output frames of one workgroup */
+int eg_skeleton_check(const int32_t* parents, const int32_t* children, const float* lengths, int32_t bones);
+int64_t eg_skeleton_out_frames(int64_t n, int32_t L, int32_t M);
+int32_t eg_skeleton_tile_frames(void);
+/* Forward: track [rows, T, 3K] fp32 -> joints [rows, out_stride, J, 3] fp32, out_stride >= ceil(T * L / M); L / M = output rate / input
+ * rate (reduced here).  For a source frame t: x_k = track[b, t, 3k .. 3k+2] + d_mean[3k ..] (d_mean NULL: no mean term); unit != 0:
+ * x_k /= max(|x_k|, 1e-12); p[0] = 0, p[children[k]] = p[parents[k]] + lengths[k] * x_k in table order.  Row b has
+ * n = clamp(d_frames[b / draws] * frame_unit, 0, T) valid frames (d_frames NULL: T; device int32 [rows / draws]: one count per recording,
+ * shared by its `draws` consecutive rows; frame_unit: what one count stands for, 1 for frame counts, H for a stream's 0 / 1 valid flags)
+ * and n_out = ceil(n * L / M) output frames: frame k' is p(lo) + (p(lo + 1) - p(lo)) * f with lo = min(floor(k' M / L), n - 2),
+ * f = (k' M - lo L) / L in exact integers (linear interpolation, extrapolated past the last frame; n = 1: p(0)); at L / M = 1 nothing is
+ * blended and frame k' is p(k').  Frames k' >= n_out are written as zeros; source frames t >= n are never used and may hold NaN.
+ * Inverse: joints [rows, T, J, 3] -> dir_vec [rows, T, 3K]: d = p[children[k]] - p[parents[k]], d / max(|d|, 1e-12) (a zero-length bone
+ * gives the zero vector), minus d_mean when given; zeros from frame n on.
+ * parents / children / lengths are on the HOST (checked here as eg_skeleton_check does), d_table is the caller's upload of the same numbers.
+ * Nothing ties the upload to the host table: with a d_table that differs from it the result is unspecified (the kernels clamp its joint
+ * numbers to 0..K, so the accesses stay in range).
+ * All pointers are caller-owned; no allocation, no synchronisation, one launch on `stream`; the grid depends on (rows, T, out_stride) only, so
+ * the call captures into a hipGraph; one owning thread per output element, no atomics.  A row's result does not depend on rows, on its place
+ * in the batch or on out_stride.  Refuses by name before the launch: null pointers, a bad table, track / joints / dir_vec not 16-byte
+ * aligned, rows or T < 1, rows not a multiple of draws, frame_unit < 1, an unsupported ratio, a short out_stride, index range. */
+int eg_skeleton_joints(const float* track, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children, const float* lengths,
+                       int32_t bones, const void* d_table, const int32_t* d_frames, int32_t draws, int32_t frame_unit, const float* d_mean,
+                       int32_t unit, int32_t L, int32_t M, float* joints, int64_t out_stride, void* stream);
+int eg_skeleton_dir_vec(const float* joints, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children, const float* lengths,
+                        int32_t bones, const void* d_table, const int32_t* d_frames, int32_t draws, int32_t frame_unit, const float* d_mean,
+                        float* dir_vec, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Beat-alignment score = model/Beat_score_v2.py alignment(sigma, order): load_audio + load_pose +
  * calculate_align for a batch of clips (test_emotion_gesture_diversity_iterative.py:241-248)
  * ------------------------------------------------------------------------------------------ */

@@ -9,7 +9,9 @@ all of it ONE captured hipGraph replayed per push.  Every row's emitted rows fol
 harness.synthesize gives for the same recording.  Weights are synthetic (integer hash), so the poses carry no meaning.
 With --audio-rate HZ the recordings are made at that rate and the stream is opened with audio_rate=HZ: every push carries hop * M / L samples,
 a StreamResampler runs first inside the same graph, and the rows equal synthesize on resample_audio(recording, HZ, delay=stream_delay(HZ)).
-usage: demo_stream.py [rows=4] [seconds=20] [--audio-rate HZ]"""
+With --joints the stream is opened with joints=skeleton.ted_expressive(): one more launch inside the graph leaves the joint positions of the
+rows just emitted in stream.last_joints [U, 30, 43, 3]; the script prints their shape and the wrist extent in metres per push.
+usage: demo_stream.py [rows=4] [seconds=20] [--audio-rate HZ] [--joints]"""
 import os
 import sys
 import time
@@ -30,6 +32,11 @@ if "--audio-rate" in sys.argv:
     RATE = int(sys.argv[i + 1])
     del sys.argv[i:i + 2]
 AR = {"audio_rate": RATE} if RATE != 16000 else {}
+JOINTS, JK = "--joints" in sys.argv, {}
+if JOINTS:
+    from emotiongestures_amd.skeleton import ted_expressive
+    sys.argv.remove("--joints")
+    JK = dict(joints=ted_expressive(), joints_unit=True)
 U = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 20.0
 dev = torch.device("cuda:0")
@@ -39,7 +46,7 @@ to16 = lambda n: R_.out_length(n, RATE) if AR else n
 
 gen = build_mirror("spatial", FRAMES, POSE_DIM, PRIOR, PRIOR, seed=7, precision="bf16x3").to(dev)
 vae = load_synth_weights(MLP_Reconstruct_v3(frames=FRAMES), 7).eval().to(dev)
-stream = H.open_stream((gen, vae), U, torch.zeros(U, PRIOR, POSE_DIM, device=dev), **AR)
+stream = H.open_stream((gen, vae), U, torch.zeros(U, PRIOR, POSE_DIM, device=dev), **AR, **JK)
 hop, hop16 = stream.hop_in, stream.hop                    # samples per push at the caller's rate and at 16 kHz
 W = (to16(total) - 1) // hop16 + 1                               # windows per recording = pushes that carry its audio
 short = total // 2                                       # the leaving row's first recording; its second one has `short` samples too
@@ -85,6 +92,10 @@ for k in range(1, steps + 1):
             tracks[u][which[u]].append(rows[u])
             zs[u][which[u]].append(z[k - 1, u])
     print(f"push {k:2d}: valid {valid.cpu().tolist()}  windows {stream.last_windows}  {1e3 * t_steps[-1]:.2f} ms")
+    if JOINTS and stream.last_joints is not None:
+        j = stream.last_joints
+        ext = [float((j[:, :, w].amax(1) - j[:, :, w].amin(1)).norm(dim=1).max()) for w in (6, 7)]
+        print(f"         last_joints {tuple(j.shape)}: wrist extent left {ext[0]:.3f} m, right {ext[1]:.3f} m")
 final = stream.tail()
 
 ok = True

@@ -15,7 +15,10 @@ R takes in FGD feature space (takes.take_diversity, fp64 on the GPU, in the unit
 whole tracks from the same features (takes.track_features -> FrechetAccumulator).
 With --audio-rate HZ (48000, 44100, 24000, ...) the test signal is made at that rate and every call gets audio_rate=HZ: the recordings are
 resampled to 16 kHz on the GPU (resample.resample_audio) before anything else runs; lengths are then counted in samples at HZ.
-usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--out tracks.npz]"""
+With --joints (TED shape only) the rectangular call also returns the joint positions of every track in metres (skeleton.ted_expressive(): 43
+joints; the mean is zero here, the bones are re-normalised to unit length), with --joints-fps N resampled from 15 to N frames per second, and the
+script prints their shape and how far the two wrists travel.
+usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--joints-fps N]] [--out tracks.npz]"""
 import os
 import sys
 import time
@@ -30,7 +33,7 @@ from emotiongestures_amd.builders import build_mirror
 from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
 from emotiongestures_amd.synth import load_synth_weights, synth_audio
 
-argv, DRAWS, OUT, BEAT, DIVERSITY, RATE = [], 0, None, False, False, 16000
+argv, DRAWS, OUT, BEAT, DIVERSITY, RATE, JOINTS, JOINTS_FPS = [], 0, None, False, False, 16000, False, None
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--draws":
@@ -43,10 +46,18 @@ for a in it:
         RATE = int(next(it))
     elif a == "--out":
         OUT = next(it)
+    elif a == "--joints":
+        JOINTS = True
+    elif a == "--joints-fps":
+        JOINTS_FPS = int(next(it))
     else:
         argv.append(a)
 if DIVERSITY and DRAWS < 2:
     sys.exit("--diversity needs --draws R with R >= 2 (the take diversity is a distance between the takes of one recording)")
+if JOINTS and BEAT:
+    sys.exit("--joints is for the TED shape: the BEAT generators' 282 columns are rotations, not bone direction vectors")
+if JOINTS_FPS and not JOINTS:
+    sys.exit("--joints-fps needs --joints")
 U = int(argv[0]) if len(argv) > 0 else 4
 seconds = float(argv[1]) if len(argv) > 1 else 60.0
 dev = torch.device("cuda:0")
@@ -87,6 +98,20 @@ print(f"window 1 beyond its overlap (rows [{HOP + PRIOR}, {2 * HOP})) appears ra
 print(f"one call (mel + CVAE + roll-out{' + beat score' if BEAT else ''}, eager): {1e3 * dt:.2f} ms = {1e3 * dt / (U * track.shape[1] / FPS):.4f} ms per second of audio")
 if BEAT:
     print(f"--beat: beat-alignment score per recording: {[round(float(v), 4) for v in out['beat'].cpu()]}")
+if JOINTS:
+    from emotiongestures_amd.skeleton import ted_expressive
+    jk = dict(joints=ted_expressive(), joints_unit=True, joints_fps=(FPS, JOINTS_FPS) if JOINTS_FPS else None)
+    H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, **jk, **AR)          # warm-up (uploads the bone table)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    jo = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, **jk, **AR)
+    torch.cuda.synchronize()
+    dt_j = time.perf_counter() - t0
+    joints = jo["joints"]
+    extent = lambda j: (joints[:, :, j].amax(1) - joints[:, :, j].amin(1)).norm(dim=1).mean()      # diagonal of the joint's bounding box
+    print(f"--joints: joints {tuple(joints.shape)} (frames per recording {jo['joint_frames']}" +
+          (f", {FPS} -> {JOINTS_FPS} fps" if JOINTS_FPS else "") + f"), one more launch in the call ({1e3 * dt_j:.2f} ms against {1e3 * dt:.2f} ms); "
+          f"wrist extent: left {float(extent(6)):.3f} m, right {float(extent(7)):.3f} m")
 
 # Recordings of unequal length in one call: recording u keeps (u + 1) / U of the audio.  Step s runs only the recordings that still have a
 # window s; the track is padded to the longest recording and zero past each recording's own end.
