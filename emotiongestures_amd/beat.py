@@ -17,14 +17,14 @@ right-side pose curves are sliced to [t_start*fps : t_end*fps].  There is no CPU
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
-from typing import Dict, Optional
+from typing import Optional
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from ._host import BoundedCache, host_ptr, int_list, ptr as _ptr, stream as _stream
 
 __all__ = ["beat_alignment", "beat_alignment_tracks", "alignment", "L1div", "SRGR", "BeatScoreUnavailable", "MAX_FRAMES", "SAMPLE_RATE"]
 
@@ -44,30 +44,23 @@ def _refuse(what):
                                "(plotting, load_data, and the other metric classes of that file)")
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 class _Tables:
     """Device copies of eg_beat_tables (filterbank [1025,128] transposed, Hann [2048], twiddles [1024,2], bands [128,2]), per device."""
-    _cache: Dict[str, "_Tables"] = {}
 
     def __init__(self, device: torch.device):
         lib = L.load()
         fb, win, tw = np.zeros(1025 * 128, np.float32), np.zeros(2048, np.float32), np.zeros(2048, np.float32)
         band = np.zeros(256, np.int32)
-        L.check(lib.eg_beat_tables(fb.ctypes.data_as(C.c_void_p), win.ctypes.data_as(C.c_void_p), tw.ctypes.data_as(C.c_void_p),
-                                   band.ctypes.data_as(C.c_void_p)), "eg_beat_tables")
+        L.check(lib.eg_beat_tables(host_ptr(fb), host_ptr(win), host_ptr(tw), host_ptr(band)), "eg_beat_tables")
         self.fb, self.win, self.tw, self.band = (torch.from_numpy(a).to(device) for a in (fb, win, tw, band))
         self.lib = lib
 
-    @classmethod
-    def get(cls, device: torch.device) -> "_Tables":
-        key = str(device)
-        t = cls._cache.get(key)
-        if t is None:
-            t = cls._cache[key] = cls(device)
-        return t
+
+_TABLES = BoundedCache()
+
+
+def _tables(device: torch.device) -> _Tables:
+    return _TABLES.get(str(device), lambda: _Tables(device))
 
 
 def _run(audio: torch.Tensor, pose: Optional[torch.Tensor], fps: int, t_start: int, t_end: int, sigma: float, order: int,
@@ -96,7 +89,7 @@ def _run(audio: torch.Tensor, pose: Optional[torch.Tensor], fps: int, t_start: i
             raise ValueError(f"beat_alignment: {F} pose frames (2..{MAX_FRAMES + 1})")
         if not (0 <= t_start < t_end) or order < 1 or fps <= 0 or not sigma > 0:
             raise ValueError(f"beat_alignment: t_start={t_start} t_end={t_end} order={order} fps={fps} sigma={sigma}")
-    tab = _Tables.get(dev)
+    tab = _tables(dev)
     lib = tab.lib
     nbytes = lib.eg_beat_workspace_bytes(B, n)
     ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
@@ -109,10 +102,9 @@ def _run(audio: torch.Tensor, pose: Optional[torch.Tensor], fps: int, t_start: i
         am = torch.empty(B, 3, T, dtype=torch.uint8, device=dev)
         if pose is not None:
             pm = torch.empty(B, 8, F - 1, dtype=torch.uint8, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     L.check(lib.eg_beat_align(_ptr(audio), B, n, _ptr(pose), F, 0 if pose is None else pose.shape[2], int(fps), int(t_start), int(t_end),
                               float(sigma), int(order), _ptr(tab.fb), _ptr(tab.win), _ptr(tab.tw), _ptr(tab.band), _ptr(ws), nbytes,
-                              _ptr(score), _ptr(nab), _ptr(oenv), _ptr(rms), _ptr(am), _ptr(pm), stream), "eg_beat_align")
+                              _ptr(score), _ptr(nab), _ptr(oenv), _ptr(rms), _ptr(am), _ptr(pm), _stream(dev)), "eg_beat_align")
     return score, {"n_audio_beats": nab, "oenv": oenv, "rms": rms, "audio_beats": am, "pose_beats": pm}
 
 
@@ -137,8 +129,6 @@ def beat_alignment(audio: torch.Tensor, pose: torch.Tensor, fps: int = 15, t_sta
 # ---- whole recordings ---------------------------------------------------------------------------------------------------------------
 class _TracksPlan:
     """Host vectors, the uploaded meta table and the workspace size of one (lengths, frames, t_end, fps, draws, Tmax, device)."""
-    _cache: Dict[tuple, "_TracksPlan"] = {}
-    _CACHE_MAX = 16
 
     def __init__(self, lib, lengths, frames, t_end, fps, draws, Tmax, device):
         U = len(lengths)
@@ -146,11 +136,9 @@ class _TracksPlan:
         self.lengths = np.ascontiguousarray(lengths, np.int32)
         self.frames = None if frames is None else np.ascontiguousarray(frames, np.int32)
         self.t_end = None if t_end is None else np.ascontiguousarray(t_end, np.int32)
-        hp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        self.h_lengths, self.h_frames, self.h_t_end = hp(self.lengths), hp(self.frames), hp(self.t_end)
+        self.h_lengths, self.h_frames, self.h_t_end = host_ptr(self.lengths), host_ptr(self.frames), host_ptr(self.t_end)
         meta = np.zeros(max(int(lib.eg_beat_tracks_meta_ints(U)), 1), np.int32)
-        L.check(lib.eg_beat_tracks_meta(self.h_lengths, self.h_frames, self.h_t_end, int(fps), U, meta.ctypes.data_as(C.c_void_p)),
-                "eg_beat_tracks_meta")
+        L.check(lib.eg_beat_tracks_meta(self.h_lengths, self.h_frames, self.h_t_end, int(fps), U, host_ptr(meta)), "eg_beat_tracks_meta")
         self.T = 1 + self.lengths // HOP
         self.offsets = np.concatenate([[0], np.cumsum(self.T)[:-1]]).astype(np.int64)
         self.sum_T = int(self.T.sum())
@@ -159,22 +147,18 @@ class _TracksPlan:
             raise L.EgError(f"eg_beat_tracks_workspace_bytes: refused ({lib.eg_last_error().decode()})")
         self.meta = torch.from_numpy(meta).to(device)
 
-    @classmethod
-    def get(cls, lib, lengths, frames, t_end, fps, draws, Tmax, device) -> "_TracksPlan":
-        key = (tuple(lengths), None if frames is None else tuple(frames), None if t_end is None else tuple(t_end), int(fps), int(draws),
-               int(Tmax), str(device))
-        p = cls._cache.get(key)
-        if p is None:
-            if len(cls._cache) >= cls._CACHE_MAX:
-                cls._cache.pop(next(iter(cls._cache)))
-            p = cls._cache[key] = cls(lib, lengths, frames, t_end, fps, draws, Tmax, device)
-        return p
+
+_PLANS = BoundedCache(16)
+
+
+def _tracks_plan(lib, lengths, frames, t_end, fps, draws, Tmax, device) -> _TracksPlan:
+    key = (tuple(lengths), None if frames is None else tuple(frames), None if t_end is None else tuple(t_end), int(fps), int(draws),
+           int(Tmax), str(device))
+    return _PLANS.get(key, lambda: _TracksPlan(lib, lengths, frames, t_end, fps, draws, Tmax, device))
 
 
 def _int_list(v, n, name):
-    if isinstance(v, torch.Tensor):
-        v = v.detach().cpu().tolist()
-    v = [int(a) for a in (v.tolist() if isinstance(v, np.ndarray) else v)]
+    v = int_list(v)
     if len(v) != n:
         raise ValueError(f"beat_alignment_tracks: {name} has {len(v)} entries for {n} recordings")
     return v
@@ -183,15 +167,16 @@ def _int_list(v, n, name):
 def _run_tracks(audio: torch.Tensor, track: Optional[torch.Tensor], lengths, frames, fps, t_start, t_end, sigma, order, want_beats,
                 workspace: Optional[torch.Tensor] = None, out: Optional[dict] = None):
     """One eg_beat_align_tracks call.  ``audio`` is already sliced at t_start; ``track [U, R, Tmax, D]`` or None (audio half only).
-    ``workspace`` / ``out``: preallocated buffers of an earlier call with the same shapes (graph capture: no allocation inside)."""
+    ``workspace`` / ``out``: preallocated buffers of an earlier call with the same shapes (graph capture: no allocation inside).  The launch
+    also reads the returned plan's ``meta`` table: whoever captures this call into a graph must keep that plan, the cache of 16 may drop it."""
     dev = audio.device
     U, stride = audio.shape
     R = Tmax = D = 0
     if track is not None:
         _, R, Tmax, D = track.shape
-    tab = _Tables.get(dev)
+    tab = _tables(dev)
     lib = tab.lib
-    plan = _TracksPlan.get(lib, lengths, frames if track is not None else None, t_end if track is not None else None, fps, max(R, 1), Tmax, dev)
+    plan = _tracks_plan(lib, lengths, frames if track is not None else None, t_end if track is not None else None, fps, max(R, 1), Tmax, dev)
     ws = workspace if workspace is not None else torch.empty(plan.bytes, dtype=torch.uint8, device=dev)
     if out is None:
         out = {"score": torch.empty(U, R, dtype=torch.float64, device=dev) if track is not None else None,
@@ -203,11 +188,10 @@ def _run_tracks(audio: torch.Tensor, track: Optional[torch.Tensor], lengths, fra
             out["audio_beats"] = torch.empty(3, plan.sum_T, dtype=torch.uint8, device=dev)
             if track is not None:
                 out["pose_beats"] = torch.empty(U, R, 8, Tmax - 1, dtype=torch.uint8, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     L.check(lib.eg_beat_align_tracks(_ptr(audio), U, stride, plan.h_lengths, _ptr(plan.meta), _ptr(track), max(R, 1), Tmax, D, plan.h_frames,
                                      int(fps), int(t_start), plan.h_t_end, float(sigma), int(order), _ptr(tab.fb), _ptr(tab.win), _ptr(tab.tw),
                                      _ptr(tab.band), _ptr(ws), ws.numel(), _ptr(out["score"]), _ptr(out["n_audio_beats"]), _ptr(out["oenv"]),
-                                     _ptr(out["rms"]), _ptr(out["audio_beats"]), _ptr(out["pose_beats"]), stream), "eg_beat_align_tracks")
+                                     _ptr(out["rms"]), _ptr(out["audio_beats"]), _ptr(out["pose_beats"]), _stream(dev)), "eg_beat_align_tracks")
     return out, plan, ws
 
 

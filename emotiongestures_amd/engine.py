@@ -14,22 +14,8 @@ import torch
 
 from . import _lib as L
 from . import packing
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _need_cuda(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
-    if not t.is_cuda:
-        raise L.EgError(f"{name}: the HIP path needs a GPU tensor (got {t.device}); there is no CPU fallback")
-    if t.dtype != dtype:
-        t = t.to(dtype)
-    return t.contiguous()
+from ._host import BoundedCache, host_ptr, int_list
+from ._host import need_cuda as _need_cuda, ptr as _ptr, stream as _stream      # these names stay importable from here (tests, tools)
 
 
 def _locked(fn):
@@ -56,7 +42,7 @@ def ragged_plan(windows_per) -> dict:
     ints = lib.eg_rollout_ragged_plan_ints(U, N) if good else 0
     order, inverse = np.zeros(max(U, 1), np.int32), np.zeros(max(U, 1), np.int32)
     step_batch, table = np.zeros(Wmax, np.int32), np.zeros(max(int(ints), 1), np.int32)
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    p = host_ptr
     L.check(lib.eg_rollout_ragged_plan(p(wp), U, p(order), p(inverse), p(step_batch), p(table) if ints > 0 else None), "eg_rollout_ragged_plan")
     if ints <= 0:
         raise L.EgError(f"eg_rollout_ragged_plan_ints: unsupported U={U} N={N}")
@@ -96,7 +82,8 @@ class GeneratorEngine:
         self.arena_floats = lib.eg_generator_arena_floats(h)
         self.arena: Optional[torch.Tensor] = None
         self._ws: Dict[tuple, torch.Tensor] = {}
-        self._plans: Dict[tuple, dict] = {}     # ragged roll-out: plan tables per (W_u) vector and device
+        self._plans = BoundedCache(64)          # ragged roll-out: plan tables per (W_u) vector and device; a long-running caller with ever-new
+        #                                         vectors drops the oldest
         self._lock = threading.RLock()
         self.uploads = 0                 # arena packs + uploads so far (tests: once per device and weight version)
 
@@ -281,7 +268,7 @@ class GeneratorEngine:
         """Shape contract of forward_rollout_ragged (checked before anything touches the device); returns (U, N, windows_per as a tuple)."""
         c = self.cfg
         try:
-            wp = tuple(int(v) for v in (windows_per.tolist() if hasattr(windows_per, "tolist") else windows_per))
+            wp = tuple(int_list(windows_per))
         except TypeError:
             raise L.EgError(f"windows_per: need a sequence of U window counts (got {type(windows_per).__name__})")
         U = len(wp)
@@ -307,22 +294,18 @@ class GeneratorEngine:
 
     def _ragged_plan(self, wp, device):
         """The plan of one (W_u) vector: host tables from eg_rollout_ragged_plan, the device copy of its table uploaded once and kept."""
-        key = (wp, str(device))
-        ent = self._plans.get(key)
-        if ent is None:
+        def build():
             ent = ragged_plan(wp)
             ent["windows_per_c"] = (C.c_int32 * len(wp))(*wp)
             ent["table_dev"] = torch.from_numpy(ent["table"]).to(device)
-            if len(self._plans) >= 64:          # a long-running caller with ever-new vectors: drop the oldest, keep the cache bounded
-                self._plans.pop(next(iter(self._plans)))
-            self._plans[key] = ent
-        return ent
+            return ent
+        return self._plans.get((wp, str(device)), build)
 
     @_locked
     def pack_ragged(self, x, windows_per, name="argument"):
         """Padded [U, Wmax, ...] -> packed [N, ...] on the device by eg_rows_by_table (row off[u] + w = x[u, w] for w < W_u; entries past W_u
         are never read).  float32 or int64."""
-        wp = tuple(int(v) for v in (windows_per.tolist() if hasattr(windows_per, "tolist") else windows_per))
+        wp = tuple(int_list(windows_per))
         U, Wmax = len(wp), max(wp) if len(wp) else 0
         if x.dim() < 2 or int(x.shape[0]) != U or int(x.shape[1]) != Wmax:
             raise L.EgError(f"{name} shape {tuple(x.shape)}: a padded argument is (U={U}, Wmax={Wmax}, ...)")
@@ -554,10 +537,9 @@ class MelFrontEnd:
         lib = L.load()
         fb, win, tw = np.zeros(513 * 128, np.float32), np.zeros(1024, np.float32), np.zeros(1024, np.float32)
         band = np.zeros(256, np.int32)
-        L.check(lib.eg_mel_tables(fb.ctypes.data_as(C.c_void_p), win.ctypes.data_as(C.c_void_p), tw.ctypes.data_as(C.c_void_p),
-                                  band.ctypes.data_as(C.c_void_p)), "eg_mel_tables")
+        L.check(lib.eg_mel_tables(host_ptr(fb), host_ptr(win), host_ptr(tw), host_ptr(band)), "eg_mel_tables")
         self.fb, self.win, self.tw, self.band = (torch.from_numpy(a).to(device) for a in (fb, win, tw, band))
-        self._lib, self.device, self._ws, self._meta = lib, torch.device(device), {}, {}
+        self._lib, self.device, self._ws, self._meta = lib, torch.device(device), {}, BoundedCache(64)
 
     def __call__(self, audio: torch.Tensor, out_frames: Optional[int] = None, slot: int = 0) -> torch.Tensor:
         audio = _need_cuda(audio, "audio")
@@ -598,7 +580,7 @@ class MelFrontEnd:
         if audio.dim() != 2:
             raise L.EgError(f"audio shape {tuple(audio.shape)} != (U, max_total_samples)")
         U, stride = int(audio.shape[0]), int(audio.shape[1])
-        lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        lens = int_list(lengths)
         if len(lens) != U:
             raise L.EgError(f"lengths: {len(lens)} entries for {U} recordings")
         if hop_samples < 1 or n_samples < 1:
@@ -609,12 +591,8 @@ class MelFrontEnd:
         audio = _need_cuda(audio, "audio")
         wp = [(v + hop_samples - 1) // hop_samples for v in lens]
         off = [sum(wp[:u]) for u in range(U)]
-        key = (tuple(lens), int(hop_samples))
-        meta = self._meta.get(key)              # lengths | offsets on the device, uploaded once per vector (bounded: the oldest goes first)
-        if meta is None:
-            if len(self._meta) >= 64:
-                self._meta.pop(next(iter(self._meta)))
-            meta = self._meta[key] = torch.tensor(lens + off, dtype=torch.int64).to(self.device)
+        meta = self._meta.get((tuple(lens), int(hop_samples)),   # lengths | offsets on the device, uploaded once per vector (the oldest goes first)
+                              lambda: torch.tensor(lens + off, dtype=torch.int64).to(self.device))
         clips = torch.empty(sum(wp), n_samples, device=self.device)
         L.check(self._lib.eg_window_gather_ragged(_ptr(audio), U, stride, (C.c_int64 * U)(*lens), _ptr(meta), hop_samples, n_samples, _ptr(clips),
                                                   _stream(self.device)), "eg_window_gather_ragged")

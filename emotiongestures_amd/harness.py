@@ -22,6 +22,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from ._host import int_list, stream
 from .modules import Encoder, Linear, ReplicaAware, _eval_only, _seq, replica_forward
 from .takes import take_distance, take_diversity, track_features  # noqa: F401  (re-exported: the whole-track FGD features / take diversity)
 
@@ -234,7 +235,7 @@ class SoftmaxContrastiveLoss(nn.Module):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         p = lambda t: None if t is None else t.data_ptr()
         L.check(lib.eg_contrastive_loss(p(f), p(a), n, d, p(cross), res[0:1].data_ptr(), res[1:2].data_ptr(), p(ws), nbytes,
-                                        torch.cuda.current_stream(dev).cuda_stream), "eg_contrastive_loss")
+                                        stream(dev)), "eg_contrastive_loss")
         return res[0], res[1], cross
 
     @torch.no_grad()
@@ -539,7 +540,7 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     if resampled:
         from . import resample as RS
         if lengths is not None:
-            lengths = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+            lengths = int_list(lengths)
         with torch.no_grad():
             audio = RS.resample_audio(audio, int(audio_rate), int(sample_rate), lengths=lengths)
         if lengths is not None:

@@ -14,7 +14,7 @@ import torch
 
 from . import _lib as L
 from . import packing
-from .engine import _need_cuda, _ptr, _stream
+from ._host import need_cuda as _need_cuda, ptr as _ptr, stream as _stream
 
 
 def _dev(t):

@@ -24,15 +24,12 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._host import BoundedCache, host_ptr, int_list, ptr as _ptr, stream as _stream
 
 __all__ = ["ratio", "plan", "out_length", "stream_delay", "resample_audio", "StreamResampler", "TILE", "MAX_FACTOR"]
 
 TILE = L.EG_RESAMPLE_TILE                   # output samples of one workgroup of the offline kernel
 MAX_FACTOR = L.EG_RESAMPLE_MAX_FACTOR
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _rate(v, who: str) -> int:
@@ -72,48 +69,34 @@ def filter_taps(rate_in: int, rate_out: int = 16000) -> np.ndarray:
     """The library's fp32 taps ``[2*half + 1]`` (eg_resample_filter; host only)."""
     p = plan(rate_in, rate_out)
     h = np.zeros(2 * p["half"] + 1, np.float32)
-    L.check(L.load().eg_resample_filter(int(rate_in), int(rate_out), h.ctypes.data_as(C.c_void_p), None), "eg_resample_filter")
+    L.check(L.load().eg_resample_filter(int(rate_in), int(rate_out), host_ptr(h), None), "eg_resample_filter")
     return h
 
 
 class _Bank:
     """The plan and the uploaded polyphase bank of one (rate_in, rate_out, device)."""
-    _cache: Dict[tuple, "_Bank"] = {}
 
     def __init__(self, rate_in, rate_out, device):
         self.plan = plan(rate_in, rate_out)
         h = np.zeros(self.plan["bank_floats"], np.float32)
-        L.check(L.load().eg_resample_filter(rate_in, rate_out, None, h.ctypes.data_as(C.c_void_p)), "eg_resample_filter")
+        L.check(L.load().eg_resample_filter(rate_in, rate_out, None, host_ptr(h)), "eg_resample_filter")
         self.bank = torch.from_numpy(h).to(device)
 
     @classmethod
     def get(cls, rate_in, rate_out, device) -> "_Bank":
-        key = (int(rate_in), int(rate_out), str(device))
-        b = cls._cache.get(key)
-        if b is None:
-            b = cls._cache[key] = cls(int(rate_in), int(rate_out), device)
-        return b
+        return _BANKS.get((int(rate_in), int(rate_out), str(device)), lambda: cls(int(rate_in), int(rate_out), device))
 
 
 class _Lengths:
     """Host int64 lengths and their upload for one (lengths, device)."""
-    _cache: Dict[tuple, "_Lengths"] = {}
-    _CACHE_MAX = 16
 
     def __init__(self, lengths, device):
         self.host = np.ascontiguousarray(lengths, np.int64)
-        self.h_ptr = self.host.ctypes.data_as(C.c_void_p)
+        self.h_ptr = host_ptr(self.host)
         self.dev = torch.from_numpy(self.host).to(device)
 
-    @classmethod
-    def get(cls, lengths, device) -> "_Lengths":
-        key = (tuple(lengths), str(device))
-        p = cls._cache.get(key)
-        if p is None:
-            if len(cls._cache) >= cls._CACHE_MAX:
-                cls._cache.pop(next(iter(cls._cache)))
-            p = cls._cache[key] = cls(lengths, device)
-        return p
+
+_BANKS, _LENGTHS = BoundedCache(), BoundedCache(16)
 
 
 def _cuda_f32(t, who):
@@ -143,14 +126,14 @@ def resample_audio(audio: torch.Tensor, rate_in: int, rate_out: int = 16000, len
     if lengths is None:
         lens = [T] * U
     else:
-        lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        lens = int_list(lengths)
         if len(lens) != U:
             raise L.EgError(f"resample_audio: lengths has {len(lens)} entries for {U} rows")
         if any(v < 1 or v > T for v in lens):
             raise L.EgError(f"resample_audio: lengths {lens}: every value must be in [1, {T}]")
     dev = x2.device
     bank = _Bank.get(rate_in, rate_out, dev)
-    lt = _Lengths.get(lens, dev)
+    lt = _LENGTHS.get((tuple(lens), str(dev)), lambda: _Lengths(lens, dev))
     n_out = -(-max(lens) * b_plan["L"] // b_plan["M"])
     if out is None:
         y = torch.empty(U, n_out, dtype=torch.float32, device=dev)
@@ -159,7 +142,7 @@ def resample_audio(audio: torch.Tensor, rate_in: int, rate_out: int = 16000, len
         if not (y.is_cuda and y.dtype == torch.float32 and y.is_contiguous() and y.dim() == 2 and y.shape[0] == U and y.shape[1] >= n_out):
             raise L.EgError(f"resample_audio: out must be a contiguous fp32 CUDA tensor [{U}, >= {n_out}]")
     L.check(L.load().eg_resample(_ptr(x2), U, T, lt.h_ptr, _ptr(lt.dev), rate_in, rate_out, _ptr(bank.bank), int(delay), _ptr(y), y.shape[1],
-                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "eg_resample")
+                                 _stream(dev)), "eg_resample")
     return y if x.dim() == 2 or out is not None else y[0]
 
 
@@ -206,7 +189,7 @@ class StreamResampler:
         """The two launches on the current stream, reading ``chunk`` / ``ends``, writing ``out`` and the history."""
         L.check(self._lib.eg_resample_stream_push(_ptr(self.state), self.U, self.rate_in, self.rate_out, _ptr(self._bank.bank), _ptr(self.chunk),
                                                   self.hop_in, _ptr(self.ends), _ptr(self.out), self.hop_out,
-                                                  C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "eg_resample_stream_push")
+                                                  _stream(self.device)), "eg_resample_stream_push")
         return self.out
 
     def host_ends(self, ends_in) -> list:
@@ -214,7 +197,7 @@ class StreamResampler:
             return [-1] * self.U
         if isinstance(ends_in, int):
             ends_in = [ends_in] * self.U
-        e = [int(v) for v in (ends_in.tolist() if hasattr(ends_in, "tolist") else ends_in)]
+        e = int_list(ends_in)
         if len(e) != self.U or any(v < -1 or v > self.hop_in for v in e):
             raise L.EgError(f"ends_in: {self.U} values, each -1 (the row goes on) or in [0, {self.hop_in}] (got {e})")
         return e
@@ -241,7 +224,7 @@ class StreamResampler:
             m[sel] = 1
             mask = m.to(self.device)
         L.check(self._lib.eg_resample_stream_reset(_ptr(self.state), self.U, self.rate_in, self.rate_out, _ptr(mask),
-                                                   C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "eg_resample_stream_reset")
+                                                   _stream(self.device)), "eg_resample_stream_reset")
 
     def snapshot(self) -> torch.Tensor:
         return self.state.clone()

@@ -23,14 +23,14 @@ a GPU.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from ._host import BoundedCache, host_ptr, int_list, ptr as _ptr, stream as _stream
 
 __all__ = ["Skeleton", "ted_expressive", "joints_from_tracks", "dir_vec_from_joints", "out_frames", "rate_ratio", "TILE_FRAMES", "MAX_BONES",
            "MAX_FACTOR"]
@@ -38,14 +38,6 @@ __all__ = ["Skeleton", "ted_expressive", "joints_from_tracks", "dir_vec_from_joi
 TILE_FRAMES = L.EG_SKELETON_TILE_FRAMES      # output frames of one workgroup
 MAX_BONES = L.EG_SKELETON_MAX_BONES
 MAX_FACTOR = L.EG_SKELETON_MAX_FACTOR
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 class Skeleton:
@@ -62,10 +54,10 @@ class Skeleton:
         self.K = int(len(self.parents))
         self.J = self.K + 1
         L.check(L.load().eg_skeleton_check(*self.host_ptrs(), self.K), "eg_skeleton_check")
-        self._tables: Dict[str, torch.Tensor] = {}
+        self._tables = BoundedCache()
 
     def host_ptrs(self):
-        return (self.parents.ctypes.data_as(C.c_void_p), self.children.ctypes.data_as(C.c_void_p), self.lengths32.ctypes.data_as(C.c_void_p))
+        return host_ptr(self.parents), host_ptr(self.children), host_ptr(self.lengths32)
 
     @property
     def pose_dim(self) -> int:
@@ -86,12 +78,8 @@ class Skeleton:
 
     def table(self, device) -> torch.Tensor:
         """int32 ``[3K]`` on ``device``: parents | children | lengths (fp32 bits)."""
-        key = str(device)
-        t = self._tables.get(key)
-        if t is None:
-            words = np.concatenate([self.parents, self.children, self.lengths32.view(np.int32)])
-            t = self._tables[key] = torch.from_numpy(words).to(device)
-        return t
+        return self._tables.get(str(device), lambda: torch.from_numpy(
+            np.concatenate([self.parents, self.children, self.lengths32.view(np.int32)])).to(device))
 
     def __eq__(self, other):
         return (isinstance(other, Skeleton) and np.array_equal(self.parents, other.parents) and np.array_equal(self.children, other.children)
@@ -166,9 +154,7 @@ def out_frames(n: int, fps=None) -> int:
 def _frames_list(frames, U: int, T: int, who: str) -> Optional[List[int]]:
     if frames is None:
         return None
-    if isinstance(frames, torch.Tensor):
-        frames = frames.detach().cpu().tolist()
-    fr = [int(v) for v in (frames.tolist() if isinstance(frames, np.ndarray) else ([frames] if isinstance(frames, int) else frames))]
+    fr = int_list([frames] if isinstance(frames, int) else frames)          # a bare int means one recording
     if len(fr) != U:
         raise L.EgError(f"{who}: frames has {len(fr)} entries for {U} recordings")
     if any(v < 0 or v > T for v in fr):

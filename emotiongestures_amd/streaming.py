@@ -22,7 +22,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib as L
-from .engine import _need_cuda
+from ._host import int_list, need_cuda as _need_cuda
 from .modules import _eval_only
 from .pipeline import CAPTURE_MODE
 
@@ -85,7 +85,7 @@ class SessionPlan:
             return [-1] * self.U
         if isinstance(ends, int):
             ends = [ends] * self.U
-        ends = [int(e) for e in (ends.tolist() if hasattr(ends, "tolist") else ends)]
+        ends = int_list(ends)
         if len(ends) != self.U:
             raise L.EgError(f"ends: {len(ends)} values for {self.U} rows")
         if any(e < -1 or e > self.hop for e in ends):

@@ -19,7 +19,6 @@ per frame times S), so takes of a 30 s and of a 60 s recording, and the clip met
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional
 
 import numpy as np
@@ -27,6 +26,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from ._host import BoundedCache, host_ptr, int_list, ptr as _ptr, stream as _stream
 
 __all__ = ["track_features", "take_distance", "take_diversity", "pack_rows", "workspace_bytes", "FEATURE_DIM", "MAX_DRAWS"]
 
@@ -34,22 +34,16 @@ FEATURE_DIM = 512
 MAX_DRAWS = 64                      # EG_TAKE_MAX_DRAWS
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 class _TakesPlan:
     """Host frames vector, the uploaded ``frames | off`` table and (for draws >= 2) the workspace size of one (frames, draws, device)."""
-    _cache: Dict[tuple, "_TakesPlan"] = {}
-    _CACHE_MAX = 16
 
     def __init__(self, lib, frames, draws, device):
         U = len(frames)
         self.U = U
         self.frames = np.ascontiguousarray(frames, np.int32)
-        self.h_frames = self.frames.ctypes.data_as(C.c_void_p)
+        self.h_frames = host_ptr(self.frames)
         meta = np.zeros(max(int(lib.eg_take_meta_ints(U)), 1), np.int32)
-        L.check(lib.eg_take_meta(self.h_frames, U, meta.ctypes.data_as(C.c_void_p)), "eg_take_meta")
+        L.check(lib.eg_take_meta(self.h_frames, U, host_ptr(meta)), "eg_take_meta")
         self.off = meta[U:2 * U].copy()
         self.sum_frames = int(self.frames.astype(np.int64).sum())
         self.bytes = 0
@@ -61,19 +55,14 @@ class _TakesPlan:
 
     @classmethod
     def get(cls, lib, frames, draws, device) -> "_TakesPlan":
-        key = (tuple(frames), int(draws), str(device))
-        p = cls._cache.get(key)
-        if p is None:
-            if len(cls._cache) >= cls._CACHE_MAX:
-                cls._cache.pop(next(iter(cls._cache)))
-            p = cls._cache[key] = cls(lib, frames, draws, device)
-        return p
+        return _PLANS.get((tuple(frames), int(draws), str(device)), lambda: cls(lib, frames, draws, device))
+
+
+_PLANS = BoundedCache(16)
 
 
 def _int_list(v, n, who):
-    if isinstance(v, torch.Tensor):
-        v = v.detach().cpu().tolist()
-    v = [int(a) for a in (v.tolist() if isinstance(v, np.ndarray) else v)]
+    v = int_list(v)
     if len(v) != n:
         raise ValueError(f"{who}: frames has {len(v)} entries for {n} recordings")
     return v
@@ -98,7 +87,7 @@ def pack_rows(track: torch.Tensor, frames=None):
     plan = _TakesPlan.get(lib, frames, R, trk.device)
     rows = torch.empty(R * plan.sum_frames, (D + 3) // 4 * 4, dtype=torch.float32, device=trk.device)
     L.check(lib.eg_track_rows_pack(_ptr(trk), U, R, Tmax, D, plan.h_frames, _ptr(plan.meta), _ptr(rows),
-                                   C.c_void_p(torch.cuda.current_stream(trk.device).cuda_stream)), "eg_track_rows_pack")
+                                   _stream(trk.device)), "eg_track_rows_pack")
     return rows, frames, plan.off.tolist()
 
 
@@ -134,7 +123,8 @@ def take_distance(feat: torch.Tensor, frames, draws: int, span: Optional[int] = 
     Returns ``{"distance": [U, R, R] fp64, "diversity": [U] fp64}`` on the device: ``distance`` symmetric with an exactly zero diagonal,
     ``diversity[u]`` its mean over the pairs r < r'.  ``span``: see the module docstring (None: the raw pair distance).
     ``workspace`` (uint8, at least the plan's size) / ``out`` (the dict of an earlier call with the same shapes): preallocated buffers, so that
-    the call allocates nothing (graph capture)."""
+    the call allocates nothing (graph capture).  The launches also read the plan's uploaded ``frames | off`` table, which the returned dict does
+    not carry: whoever captures this call into a graph must keep ``_TakesPlan.get(lib, frames, draws, device)``, the cache of 16 may drop it."""
     R = int(draws)
     if R < 2:
         raise L.EgError(f"take_distance: draws={R}: a distance between takes needs draws >= 2")
@@ -159,15 +149,14 @@ def take_distance(feat: torch.Tensor, frames, draws: int, span: Optional[int] = 
     if out is None:
         out = {"distance": torch.empty(U, R, R, dtype=torch.float64, device=dev), "diversity": torch.empty(U, dtype=torch.float64, device=dev)}
     L.check(lib.eg_take_distance(_ptr(feat), U, R, K, plan.h_frames, _ptr(plan.meta), 0 if span is None else int(span), _ptr(ws), ws.numel(),
-                                 _ptr(out["distance"]), _ptr(out["diversity"]), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-            "eg_take_distance")
+                                 _ptr(out["distance"]), _ptr(out["diversity"]), _stream(dev)), "eg_take_distance")
     return out
 
 
 def workspace_bytes(frames, draws: int) -> int:
     """Bytes of ``take_distance``'s workspace for (frames, draws) (eg_take_distance_workspace_bytes; host only)."""
     fr = np.ascontiguousarray(frames, np.int32)
-    n = int(L.load().eg_take_distance_workspace_bytes(fr.ctypes.data_as(C.c_void_p), len(fr), int(draws)))
+    n = int(L.load().eg_take_distance_workspace_bytes(host_ptr(fr), len(fr), int(draws)))
     if n <= 0:
         raise L.EgError(f"eg_take_distance_workspace_bytes: refused ({L.load().eg_last_error().decode()})")
     return n

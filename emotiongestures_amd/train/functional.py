@@ -14,7 +14,7 @@ from typing import Optional
 import torch
 
 from .. import _lib as L
-from ..engine import _ptr, _stream
+from .._host import ptr as _ptr, stream as _stream
 
 F32 = L.EG_PREC_F32
 _WS = {}

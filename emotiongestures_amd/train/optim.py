@@ -19,7 +19,7 @@ from typing import List, Optional
 import torch
 
 from .. import _lib as L
-from ..engine import _ptr, _stream
+from .._host import ptr as _ptr, stream as _stream
 
 
 class FlatParams:

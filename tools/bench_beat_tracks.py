@@ -23,6 +23,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools._timing import alternate, graph_of, summary, write_line  # noqa: E402
 SR, FPS = 16000, 15
 
 
@@ -37,42 +38,6 @@ def make(lengths, R, seed):
     frames = [n * FPS // SR for n in lengths]
     track = np.cumsum(rng.standard_normal((U, R, max(frames), 282)).astype(np.float32) * np.float32(0.05), axis=2, dtype=np.float32)
     return audio, track, frames
-
-
-def graph_of(fn, warmup=3):
-    for _ in range(warmup):
-        out = fn()
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        out = fn()
-    g.replay()
-    torch.cuda.synchronize()
-    return g, out
-
-
-def window_ms(g, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        g.replay()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
-def alternate(graphs, rounds, window_s):
-    """{name: graph} -> {name: per-round ms}; every round times each graph once, in turn."""
-    reps = {k: max(20, int(window_s * 1000.0 / max(window_ms(g, 10), 1e-3)) + 1) for k, g in graphs.items()}
-    res = {k: [] for k in graphs}
-    for _ in range(rounds):
-        for k, g in graphs.items():
-            res[k].append(window_ms(g, reps[k]))
-    return res, reps
-
-
-def summary(v):
-    return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
 
 
 def main():
@@ -113,7 +78,7 @@ def main():
         g_old, s_old = graph_of(lambda: beat_alignment(au_rep, po_rep))
         g_old2, _ = graph_of(lambda: beat_alignment(au_rep, po_rep))                       # the baseline again: its own spread
         same = bool(torch.equal(s_new.reshape(-1).view(torch.int64), s_old.view(torch.int64)))
-        t, reps = alternate({"tracks": g_new, "clip": g_old, "clip_again": g_old2}, a.rounds, a.window_s)
+        t, reps = alternate({"tracks": g_new, "clip": g_old, "clip_again": g_old2}, a.rounds, a.window_s, min_reps=20, probe=10)
         base = t["clip"] + t["clip_again"]
         res[f"u8_30s_r{R}"] = {"tracks": summary(t["tracks"]), f"clip_batch{8 * R}": summary(base),
                                "clip_spread_pct": round(100 * (max(base) - min(base)) / statistics.median(base), 2),
@@ -126,17 +91,13 @@ def main():
         audio, track, frames = make(lengths, R, 20 + len(lengths))
         au, tr = up(audio), up(track)
         g_new, s = graph_of(lambda: beat_alignment_tracks(au, tr, lengths=lengths, frames=frames))
-        t, reps = alternate({"tracks": g_new}, a.rounds, a.window_s)
+        t, reps = alternate({"tracks": g_new}, a.rounds, a.window_s, min_reps=20, probe=10)
         res[name] = {"recordings": len(lengths), "draws": R, "seconds": [round(min(lengths) / SR, 1), round(max(lengths) / SR, 1)],
                      "onset_frames": int(sum(1 + n // 512 for n in lengths)), **summary(t["tracks"]),
                      "us_per_track": round(1000 * statistics.median(t["tracks"]) / (len(lengths) * R), 3),
                      "finite": int(torch.isfinite(s).sum()), "replays_per_window": reps["tracks"]}
     res["device"] = torch.cuda.get_device_name(dev)
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    write_line(res, a.out)
 
 
 if __name__ == "__main__":

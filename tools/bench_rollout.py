@@ -10,7 +10,6 @@ while the graph is captured); the torch ops of (b) are not in them.  Prints one 
     python tools/bench_rollout.py [--shapes 1x30,8x30,64x8] [--iters 10] [--rounds 5] [--out profiles/rollout_bench_line.json]
 """
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -20,6 +19,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools._timing import capture, window_ms, write_line  # noqa: E402
 
 F_, D_, P_, FPS = 34, 126, 4, 15
 H_ = F_ - P_
@@ -46,31 +46,6 @@ def loop(model, g, alpha):
             track[:, w * H_ + P_: w * H_ + F_] = pose[:, P_:]
         prior = pose[:, H_:].contiguous()
     return track
-
-
-def capture(fn, lib):
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side), torch.no_grad():
-        for _ in range(2):
-            fn()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    n0 = lib.eg_launch_count()
-    with torch.cuda.graph(graph), torch.no_grad():
-        out = fn()
-    return graph, out, lib.eg_launch_count() - n0
-
-
-def window_ms(graph, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        graph.replay()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
 
 
 def main():
@@ -119,11 +94,7 @@ def main():
             "loop_ms_per_audio_second": round(mb / seconds, 4), "loop_library_launches_per_window": round(lb / W, 1),
             "speedup": round(mb / ma, 3), "track_rel_l2_rollout_vs_loop": diff, "track_bitwise": bool(torch.equal(oa, ob))})
     res["device"] = torch.cuda.get_device_name(dev)
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    write_line(res, a.out)
 
 
 if __name__ == "__main__":

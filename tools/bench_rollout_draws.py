@@ -10,7 +10,6 @@ the library's own (eg_launch_count while the graph is captured).  Prints one JSO
     python tools/bench_rollout_draws.py [--shapes 1x30x8,8x8x8,8x30x4,1x30x32] [--iters 5] [--rounds 5] [--out profiles/rollout_draws_bench_line.json]
 """
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -19,6 +18,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools._timing import capture, window_ms, write_line  # noqa: E402
 
 F_, D_, P_, FPS = 34, 126, 4, 15
 H_ = F_ - P_
@@ -37,31 +37,6 @@ def replicate(g):
     rep = lambda x: x[:, None].expand((U, R) + tuple(x.shape[1:])).reshape((U * R,) + tuple(x.shape[1:])).contiguous()
     return {"spec": rep(g["spec"]), "text": rep(g["text"]), "seed_pose": rep(g["seed_pose"]),
             "sampled": g["sampled"].reshape((U * R,) + tuple(g["sampled"].shape[2:]))}
-
-
-def capture(fn, lib):
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side), torch.no_grad():
-        for _ in range(2):
-            fn()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    n0 = lib.eg_launch_count()
-    with torch.cuda.graph(graph), torch.no_grad():
-        out = fn()
-    return graph, out, lib.eg_launch_count() - n0
-
-
-def window_ms(graph, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        graph.replay()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
 
 
 def main():
@@ -114,11 +89,7 @@ def main():
             "speedup": round(mb / ma, 3), "flop_estimate_ratio": round((7.75 + 1.5 * R) / (9.25 * R), 3),
             "track_bitwise": bool(torch.equal(oa, ob))})
     res["device"] = torch.cuda.get_device_name(dev)
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    write_line(res, a.out)
 
 
 if __name__ == "__main__":

@@ -13,7 +13,6 @@ step).  Launch counts are the library's own (eg_launch_count over one eager step
     python tools/bench_stream.py [--shapes 1,8,64] [--iters 100] [--rounds 5] [--added-us 13,14,30] [--out profiles/stream_bench_line.json]
 """
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -23,20 +22,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools._timing import window_ms, write_line  # noqa: E402
 
 F_, D_, P_, FPS = 34, 126, 4, 15
 H_ = F_ - P_
 HOP, N = 32000, (124 - 1) * 512
-
-
-def window_ms(replay, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        replay()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
 
 
 def launches(lib, fn):
@@ -128,11 +118,7 @@ def main():
             "eager_loop_ms": round(mc, 4), "eager_loop_ms_min_max": [round(min(tc), 4), round(max(tc), 4)], "eager_loop_library_launches_per_step": ll,
             "speedup_over_eager_loop": round(mc / ma, 3)})
     res["device"] = torch.cuda.get_device_name(dev)
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    write_line(res, a.out)
 
 
 if __name__ == "__main__":

@@ -29,6 +29,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools._timing import alternate, graph_of, summary, write_line  # noqa: E402
 SR, FPS, D, K = 16000, 15, 282, 512
 
 
@@ -55,18 +56,6 @@ def composition(fgd, track, live, span_scale):
     return dist, div
 
 
-def graph_of(fn, warmup=3):
-    for _ in range(warmup):
-        out = fn()
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        out = fn()
-    g.replay()
-    torch.cuda.synchronize()
-    return g, out
-
-
 class Eager:
     """The call itself with a graph's replay(): timed from the host side of the stream, launch overhead included."""
     def __init__(self, fn):
@@ -74,30 +63,6 @@ class Eager:
 
     def replay(self):
         self.fn()
-
-
-def window_ms(g, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        g.replay()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
-def alternate(graphs, rounds, window_s):
-    """{name: graph} -> {name: per-round ms}; every round times each graph once, in turn."""
-    reps = {k: max(5, int(window_s * 1000.0 / max(window_ms(g, 3), 1e-3)) + 1) for k, g in graphs.items()}
-    res = {k: [] for k in graphs}
-    for _ in range(rounds):
-        for k, g in graphs.items():
-            res[k].append(window_ms(g, reps[k]))
-    return res, reps
-
-
-def summary(v):
-    return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
 
 
 def bind_other(path):
@@ -212,11 +177,7 @@ def main():
             res[name] = entry
             del track, rows, feat, g_new, g_pack, g_feat, g_dist, graphs
             torch.cuda.empty_cache()
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    write_line(res, a.out)
 
 
 if __name__ == "__main__":
