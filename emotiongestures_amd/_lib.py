@@ -59,6 +59,7 @@ class EgResamplePlan(C.Structure):
 
 EG_RESAMPLE_TILE, EG_RESAMPLE_MAX_FACTOR = 1024, 640
 EG_SKELETON_MAX_BONES, EG_SKELETON_MAX_FACTOR, EG_SKELETON_TILE_FRAMES = 63, 64, 32
+EG_SKELETON_SPACE_LOCAL, EG_SKELETON_SPACE_GLOBAL = 0, 1
 
 # name -> (restype, argtypes).  Must list every symbol include/emogest.h declares
 # (tests/test_abi.py cross-checks this table against the header).
@@ -120,6 +121,9 @@ SIGNATURES = {
     "eg_skeleton_tile_frames": (_I, []),
     "eg_skeleton_joints": (C.c_int, [_P, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _P, _I, _I, _I, _P, _L, _P]),
     "eg_skeleton_dir_vec": (C.c_int, [_P, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P]),
+    "eg_skeleton_rest_check": (C.c_int, [_P, _I]),
+    "eg_skeleton_levels": (C.c_int, [_P, _P, _P, _I, _P, _P]),
+    "eg_skeleton_rotations": (C.c_int, [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _I, _I, _I, _P, _L, _P]),
     "eg_beat_tables": (C.c_int, [_P, _P, _P, _P]),
     "eg_beat_workspace_bytes": (_L, [_I, _I]),
     "eg_beat_align": (C.c_int, [_P, _I, _I, _P, _I, _I, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P]),

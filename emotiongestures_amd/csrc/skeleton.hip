@@ -10,6 +10,11 @@
 // barrier, and the rows of the tile are conflict-free -- and writes the outputs coalesced, 16 bytes per lane where a quad lies inside the tile.
 // The bone table is an argument, read once per workgroup; nothing about a particular body is built in.  Every output element has one owning
 // thread; plain vector stores, no atomics, nothing device-scope; the grid depends on the shapes only.
+//   rotations (eg_skeleton_rest_check, eg_skeleton_levels, eg_skeleton_rotations): one local rotation per bone relative to a rest pose.  Same grid,
+//             same staging and the same frame handling, but the vectors are blended, not the results, and the chain is a dependent run of
+//             quaternion products, so it is walked level by level: the host orders the bones by depth, one thread owns one (output frame, bone of
+//             the level), one barrier per level.  The global rotations live in an LDS tile g[bone][component][frame] (lanes of consecutive frames
+//             on consecutive banks); x is blended and normalised in registers as it is read; every (frame, bone) leaves as one aligned 16-byte store.
 #include "common.h"
 #include <math.h>
 
@@ -213,6 +218,142 @@ __global__ __launch_bounds__(THREADS) void skeleton_dir_vec_kernel(const Args a)
     });
 }
 
+
+// ---- rotations ------------------------------------------------------------------------------------------------------------------------------
+constexpr int LV_OFFS = 68;                             // LDS words: level offsets [nlev + 1 <= 64] (+ pad)
+constexpr int RHEAD = LV_OFFS + 2 * TAB + 3 * TAB + 3 * TAB;    // offsets | order | bone parents | rest [3 * 64] | mean [3 * 64]
+static_assert(RHEAD % 4 == 0, "the staged frames start on a quad");
+
+struct Quat { float w, x, y, z; };
+
+__device__ __forceinline__ Quat qmul(const Quat& p, const Quat& q) {             // Hamilton product
+    return {p.w * q.w - p.x * q.x - p.y * q.y - p.z * q.z, p.w * q.x + p.x * q.w + p.y * q.z - p.z * q.y,
+            p.w * q.y - p.x * q.z + p.y * q.w + p.z * q.x, p.w * q.z + p.x * q.y - p.y * q.x + p.z * q.w};
+}
+
+// conj(q) o v: v + 2 w (u x v) + 2 u x (u x v) with u = -q.xyz
+__device__ __forceinline__ void rotate_back(const Quat& q, float& v0, float& v1, float& v2) {
+    const float u0 = -q.x, u1 = -q.y, u2 = -q.z;
+    const float t0 = 2.f * (u1 * v2 - u2 * v1), t1 = 2.f * (u2 * v0 - u0 * v2), t2 = 2.f * (u0 * v1 - u1 * v0);
+    v0 += q.w * t0 + (u1 * t2 - u2 * t1);
+    v1 += q.w * t1 + (u2 * t0 - u0 * t2);
+    v2 += q.w * t2 + (u0 * t1 - u1 * t0);
+}
+
+// The shortest arc from the unit vector a to the unit (or zero) vector b; the half turn about a fixed axis perpendicular to a where they oppose.
+__device__ __forceinline__ Quat arc(float a0, float a1, float a2, float b0, float b1, float b2) {
+    const float c = a0 * b0 + a1 * b1 + a2 * b2;
+    if (c >= -1.f + 1e-6f) {
+        const float w = 1.f + c, x = a1 * b2 - a2 * b1, y = a2 * b0 - a0 * b2, z = a0 * b1 - a1 * b0;
+        const float d = sqrtf(w * w + x * x + y * y + z * z);
+        return {w / d, x / d, y / d, z / d};
+    }
+    const float m0 = fabsf(a0), m1 = fabsf(a1), m2 = fabsf(a2);
+    float x, y, z;                                                              // a x e_m, m the first axis on which |a| is smallest
+    if (m0 <= m1 && m0 <= m2) { x = 0.f; y = a2; z = -a1; }
+    else if (m1 <= m2) { x = -a2; y = 0.f; z = a0; }
+    else { x = a1; y = -a0; z = 0.f; }
+    const float d = sqrtf(x * x + y * y + z * z);
+    return {0.f, x / d, y / d, z / d};
+}
+
+// grid: (tile of TF output frames) x row, flattened.  NATIVE: L / M = 1.  GLOBAL: the output holds G_k, else L_k.
+// a.table is the level table of eg_skeleton_levels; as in load_table its numbers index LDS and the output, so they are clamped.
+template <bool NATIVE, bool GLOBAL>
+__global__ __launch_bounds__(THREADS) void skeleton_rotations_kernel(const Args a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int K = a.K, D = 3 * K, Q = 4 * K, tid = threadIdx.x;
+    int* lv = reinterpret_cast<int*>(lds);
+    int* ord = lv + LV_OFFS;
+    int* pbt = ord + TAB;
+    float* rs = lds + LV_OFFS + 2 * TAB;
+    float* mn = rs + 3 * TAB;
+    float* xin = lds + RHEAD;
+    float* gt = xin + round4(SLOTS * D + 8);                                    // g[bone][component][frame of the tile]
+    const int b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
+    const long long k0 = (long long)tile * TF;
+    const int cnt = (int)(a.T_out - k0 < TF ? a.T_out - k0 : TF);
+    const int n = valid_frames(a, b);
+    const long long n_out = NATIVE ? n : out_frames(n, a.L, a.M);
+    const int live = (int)(n_out - k0 < 0 ? 0 : (n_out - k0 < cnt ? n_out - k0 : cnt));
+    float* out = a.dst + ((long long)b * a.T_out + k0) * Q;                      // 16-byte aligned: Q is a multiple of 4
+    for (int q = live * K + tid; q < cnt * K; q += THREADS) *reinterpret_cast<f4*>(out + 4ll * q) = f4{0.f, 0.f, 0.f, 0.f};
+    if (live == 0) return;
+    const int nlev = min(max(a.table[0], 1), K);
+    for (int l = tid; l <= nlev; l += THREADS) lv[l] = min(max(a.table[1 + l], 0), K);
+    for (int k = tid; k < K; k += THREADS) {
+        ord[k] = min(max(a.table[65 + k], 0), K - 1);
+        pbt[k] = min(max(a.table[65 + K + k], -1), K - 1);
+    }
+    for (int r = tid; r < D; r += THREADS) rs[r] = __int_as_float(a.table[65 + 2 * K + r]);
+    const bool has_mean = a.mean != nullptr;
+    if (has_mean)
+        for (int r = tid; r < D; r += THREADS) mn[r] = a.mean[r];
+    const long long total = (long long)a.B * a.T * D;
+    const int L = a.L, M = a.M;
+    auto seg = [&](long long kk) -> long long {                                 // first source frame of output frame kk
+        if (NATIVE) return kk;
+        if (n < 2) return 0;
+        const long long lo = kk * M / L;
+        return lo < n - 2 ? lo : n - 2;
+    };
+    for (int i = 0; i < live;) {
+        // outputs [i, i1) of the tile from the source frames [s_base, s_base + nslots), as in skeleton_joints_kernel
+        const long long s_base = seg(k0 + i);
+        int i1 = live;
+        if (!NATIVE && M > L) {
+            const long long jmax = ((s_base + SLOTS - 1) * L - 1) / M - k0;
+            i1 = jmax + 1 < live ? (int)(jmax + 1) : live;
+            i1 = i1 > i ? i1 : i + 1;
+        }
+        const int nslots = (int)(seg(k0 + i1 - 1) - s_base) + ((NATIVE || n < 2) ? 1 : 2);
+        const long long g0 = ((long long)b * a.T + s_base) * D;
+        stage_span(a.src, g0, g0 + (long long)nslots * D, total, xin);
+        __syncthreads();                                                        // also: the tables, and the last level of the pass before
+        const float* x = xin + (int)(g0 & 3);
+        const int nf = i1 - i;
+        for (int l = 0; l < nlev; ++l) {
+            const int b0 = lv[l], nb = max(lv[l + 1] - b0, 0);
+            for (int w = tid; w < nf * nb; w += THREADS) {                       // one thread per (output frame, bone of the level)
+                const int j = w / nf, fr = i + (w - j * nf);
+                const int k = ord[min(b0 + j, K - 1)], p = pbt[k];
+                float x0, x1, x2;
+                if (NATIVE || n < 2) {
+                    const float* xs = x + (NATIVE ? fr - i : 0) * D + 3 * k;
+                    x0 = xs[0]; x1 = xs[1]; x2 = xs[2];
+                    if (has_mean) { x0 += mn[3 * k]; x1 += mn[3 * k + 1]; x2 += mn[3 * k + 2]; }
+                } else {                                                        // the vectors are blended, after the mean
+                    const long long kk = k0 + fr, lo = seg(kk);
+                    const float f = (float)(kk * M - lo * L) / (float)L;
+                    const float* xs = x + (int)(lo - s_base) * D + 3 * k;
+                    float y0 = xs[0], y1 = xs[1], y2 = xs[2], z0 = xs[D], z1 = xs[D + 1], z2 = xs[D + 2];
+                    if (has_mean) {
+                        y0 += mn[3 * k]; y1 += mn[3 * k + 1]; y2 += mn[3 * k + 2];
+                        z0 += mn[3 * k]; z1 += mn[3 * k + 1]; z2 += mn[3 * k + 2];
+                    }
+                    x0 = fmaf(z0 - y0, f, y0); x1 = fmaf(z1 - y1, f, y1); x2 = fmaf(z2 - y2, f, y2);
+                }
+                const float d = fmaxf(sqrtf(x0 * x0 + x1 * x1 + x2 * x2), 1e-12f);
+                x0 /= d; x1 /= d; x2 /= d;
+                Quat P = {1.f, 0.f, 0.f, 0.f};
+                if (p >= 0) {
+                    const float* gp = gt + p * 4 * TF + fr;
+                    P = {gp[0], gp[TF], gp[2 * TF], gp[3 * TF]};
+                    rotate_back(P, x0, x1, x2);                                 // the bone's direction seen from its parent's frame
+                }
+                const Quat Lq = arc(rs[3 * k], rs[3 * k + 1], rs[3 * k + 2], x0, x1, x2);
+                const Quat G = p >= 0 ? qmul(P, Lq) : Lq;
+                float* gk = gt + k * 4 * TF + fr;
+                gk[0] = G.w; gk[TF] = G.x; gk[2 * TF] = G.y; gk[3 * TF] = G.z;
+                const Quat& o = GLOBAL ? G : Lq;
+                *reinterpret_cast<f4*>(out + ((long long)fr * K + k) * 4) = f4{o.w, o.x, o.y, o.z};
+            }
+            __syncthreads();                                                    // a level reads what the level before wrote
+        }
+        i = i1;
+    }
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
 int check_table(const char* who, const int32_t* parents, const int32_t* children, const float* lengths, int K) {
     EG_REQUIRE(parents && children && lengths, EG_ERR_BAD_ARG, "%s: null parents / children / lengths", who);
@@ -255,6 +396,18 @@ int common_checks(const char* who, const void* src, const void* dst, int B, int 
     EG_REQUIRE(B >= 1 && T >= 1, EG_ERR_BAD_ARG, "%s: rows=%d frames=%d (need >= 1)", who, B, T);
     EG_REQUIRE(draws >= 1 && B % draws == 0, EG_ERR_BAD_ARG, "%s: rows=%d is not a multiple of draws=%d", who, B, draws);
     EG_REQUIRE(frame_unit >= 1, EG_ERR_BAD_ARG, "%s: frame_unit=%d (need >= 1)", who, frame_unit);
+    return EG_OK;
+}
+
+int check_rest(const char* who, const double* rest, int K) {
+    EG_REQUIRE(rest, EG_ERR_BAD_ARG, "%s: null rest", who);
+    for (int k = 0; k < K; ++k) {
+        const double* r = rest + 3 * k;
+        EG_REQUIRE(isfinite(r[0]) && isfinite(r[1]) && isfinite(r[2]), EG_ERR_BAD_ARG, "%s: rest row %d: (%g, %g, %g) is not finite", who, k, r[0],
+                   r[1], r[2]);
+        const double nrm = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+        EG_REQUIRE(nrm >= 1e-6, EG_ERR_BAD_ARG, "%s: rest row %d: norm=%g (need >= 1e-6: a rest direction)", who, k, nrm);
+    }
     return EG_OK;
 }
 
@@ -315,4 +468,84 @@ extern "C" int eg_skeleton_dir_vec(const float* joints, int32_t rows, int32_t T,
     const size_t lds = (size_t)(HEAD + round4(TF * 3 * (bones + 1) + 8)) * sizeof(float);
     hipLaunchKernelGGL(skeleton_dir_vec_kernel, dim3((unsigned)(tiles * rows)), dim3(THREADS), lds, static_cast<hipStream_t>(stream), a);
     return eg_check_launch("skeleton_dir_vec");
+}
+
+extern "C" int eg_skeleton_rest_check(const double* rest, int32_t bones) {
+    const char* who = "eg_skeleton_rest_check";
+    EG_REQUIRE(bones >= 1 && bones <= MAX_K, EG_ERR_UNSUPPORTED, "%s: bones=%d (1..%d)", who, bones, MAX_K);
+    return check_rest(who, rest, bones);
+}
+
+extern "C" int eg_skeleton_levels(const int32_t* parents, const int32_t* children, const float* lengths, int32_t bones, const double* rest,
+                                  int32_t* words) {
+#pragma clang fp contract(off)                          // the rows are x / sqrt(x.x) in plain float64, every operation rounded once
+    const char* who = "eg_skeleton_levels";
+    int rc = check_table(who, parents, children, lengths, bones);
+    if (rc != EG_OK) return rc;
+    rc = check_rest(who, rest, bones);
+    if (rc != EG_OK) return rc;
+    EG_REQUIRE(words, EG_ERR_BAD_ARG, "%s: null words", who);
+    const int K = bones;
+    int owner[MAX_K + 1], depth[MAX_K], count[MAX_K + 1] = {};
+    for (int j = 0; j <= K; ++j) owner[j] = -1;
+    int nlev = 0;
+    int32_t* pb = words + 65 + K;
+    for (int k = 0; k < K; ++k) {                       // topological order: the parent joint's bone, if any, came earlier
+        pb[k] = owner[parents[k]];
+        depth[k] = pb[k] < 0 ? 0 : depth[pb[k]] + 1;
+        owner[children[k]] = k;
+        ++count[depth[k]];
+        nlev = depth[k] + 1 > nlev ? depth[k] + 1 : nlev;
+    }
+    words[0] = nlev;
+    int at[MAX_K + 1];
+    for (int l = 0, s = 0; l < 64; ++l) {
+        words[1 + l] = s;
+        at[l] = s;
+        if (l < nlev) s += count[l];
+    }
+    for (int k = 0; k < K; ++k) words[65 + at[depth[k]]++] = k;                 // by depth, table order inside a level
+    for (int k = 0; k < K; ++k) {
+        const double* r = rest + 3 * k;
+        const double nrm = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+        for (int c = 0; c < 3; ++c) {
+            const float v = (float)(r[c] / nrm);
+            words[65 + 2 * K + 3 * k + c] = *reinterpret_cast<const int32_t*>(&v);
+        }
+    }
+    return EG_OK;
+}
+
+extern "C" int eg_skeleton_rotations(const float* track, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children,
+                                     const float* lengths, int32_t bones, const double* rest, const void* d_levels, const int32_t* d_frames,
+                                     int32_t draws, int32_t frame_unit, const float* d_mean, int32_t space, int32_t L, int32_t M,
+                                     float* rotations, int64_t out_stride, void* stream) {
+    const char* who = "eg_skeleton_rotations";
+    int rc = common_checks(who, track, rotations, rows, T, parents, children, lengths, bones, d_levels, draws, frame_unit, d_mean);
+    if (rc != EG_OK) return rc;
+    rc = check_rest(who, rest, bones);
+    if (rc != EG_OK) return rc;
+    EG_REQUIRE(space == EG_SKELETON_SPACE_LOCAL || space == EG_SKELETON_SPACE_GLOBAL, EG_ERR_BAD_ARG, "%s: space=%d (0: local, 1: global)", who, space);
+    int l = L, m = M;
+    rc = reduce_rate(who, l, m);
+    if (rc != EG_OK) return rc;
+    const long long t_out = out_frames(T, l, m);
+    EG_REQUIRE(out_stride >= t_out, EG_ERR_BAD_ARG, "%s: out_stride=%lld < %lld output frames of %d input frames at L=%d / M=%d", who,
+               (long long)out_stride, t_out, T, l, m);
+    const long long tiles = (out_stride + TF - 1) / TF;
+    EG_REQUIRE(tiles * rows <= 0x7fffffffll && (long long)rows * out_stride * 4 * bones < (1ll << 40), EG_ERR_UNSUPPORTED,
+               "%s: rows=%d x out_stride=%lld: grid / index range", who, rows, (long long)out_stride);
+    Args a = {track, static_cast<const int*>(d_levels), d_frames, d_mean, rotations, rows, T, bones, draws, frame_unit, l, m, (int)tiles, out_stride};
+    const size_t lds = (size_t)(RHEAD + round4(SLOTS * 3 * bones + 8) + bones * 4 * TF) * sizeof(float);
+    const dim3 grid((unsigned)(tiles * rows)), block(THREADS);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool native = l == 1 && m == 1;
+    if (space == EG_SKELETON_SPACE_GLOBAL) {
+        if (native) hipLaunchKernelGGL((skeleton_rotations_kernel<true, true>), grid, block, lds, st, a);
+        else hipLaunchKernelGGL((skeleton_rotations_kernel<false, true>), grid, block, lds, st, a);
+    } else {
+        if (native) hipLaunchKernelGGL((skeleton_rotations_kernel<true, false>), grid, block, lds, st, a);
+        else hipLaunchKernelGGL((skeleton_rotations_kernel<false, false>), grid, block, lds, st, a);
+    }
+    return eg_check_launch("skeleton_rotations");
 }

@@ -464,7 +464,7 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
                z: Optional[torch.Tensor] = None, alpha: Optional[torch.Tensor] = None, fps: int = 15, sample_rate: int = 16000,
                want_windows: bool = False, want_aux: bool = False, mel=None, lengths=None, draws: Optional[int] = None,
                beat: bool = False, diversity=None, audio_rate: Optional[int] = None, joints=None, joints_mean=None,
-               joints_unit: bool = False, joints_fps=None) -> Dict[str, torch.Tensor]:
+               joints_unit: bool = False, joints_fps=None, rotations=None, rotations_space: str = "local") -> Dict[str, torch.Tensor]:
     """One gesture track per utterance from raw 16 kHz audio: windows -> mel -> optional CVAE sample per window -> roll-out.
 
     ``models = (generator, vae | None)``, eval mode, on the GPU.  ``audio [U, total_samples]``; ``text [U, W, 60]`` (the words of every
@@ -505,8 +505,18 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     ``W_u * (frames - prior_frames) + prior_frames`` valid poses, one launch.  ``joints_mean [pose_dim]``: the data set's mean direction vectors,
     added first; ``joints_unit``: bones re-normalised to unit length; ``joints_fps=(src, dst)``: resampled linearly to the renderer's rate
     (``T' = ceil(T * dst / src)``).  Works with ``lengths``, ``draws``, ``beat``, ``diversity`` and ``audio_rate``; without ``joints`` nothing
-    changes."""
+    changes.
+
+    ``rotations=rest`` (with ``joints=skeleton``; ``rest [K, 3]``, the direction of every bone in the avatar's bind pose): adds ``"rotations"``,
+    one unit quaternion ``(w, x, y, z)`` per bone and output frame -- ``[U, T', K, 4]``, or ``[U, R, T', K, 4]`` with ``draws`` -- relative to
+    the parent bone (``rotations_space="local"``, what a rig takes) or to the root (``"global"``):
+    ``skeleton.rotations_from_tracks(out["track"], skeleton, rest, frames, joints_mean, joints_fps, rotations_space)``, one more launch, on the
+    frames ``"joint_frames"`` counts."""
     gen, vae = models
+    if rotations is not None and joints is None:
+        raise L.EgError("synthesize: rotations= without joints=skeleton (the rest pose belongs to a skeleton's bones)")
+    if rotations is None and rotations_space != "local":
+        raise L.EgError("synthesize: rotations_space without rotations=rest")
     if joints is not None:
         from . import skeleton as SK
         if not isinstance(joints, SK.Skeleton):
@@ -515,6 +525,9 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
             raise L.EgError(f"synthesize: joints=: the skeleton has K={joints.K} bones, 3K={joints.pose_dim} != pose_dim={seed_pose.shape[-1]} "
                             "(the BEAT generators' 282 columns hold rotations, not bone direction vectors)")
         SK.rate_ratio(joints_fps, "synthesize: joints_fps")                        # refuses an unsupported ratio before anything runs
+        if rotations is not None:                                                  # and a bad rest pose or space
+            SK._space(rotations_space, "synthesize: rotations_space")
+            rotations = joints.rest_pose(rotations)
     elif joints_mean is not None or joints_unit or joints_fps is not None:
         raise L.EgError("synthesize: joints_mean / joints_unit / joints_fps without joints=skeleton")
     _eval_only(gen)
@@ -575,6 +588,9 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
         with torch.no_grad():
             out["joints"], out["joint_frames"] = SK.joints_from_tracks(out["track"], joints, frames=[int(w) * H + c.prior_frames for w in wp],
                                                                        mean=joints_mean, unit=joints_unit, fps=joints_fps)
+            if rotations is not None:
+                out["rotations"], _n = SK.rotations_from_tracks(out["track"], joints, rotations, frames=[int(w) * H + c.prior_frames for w in wp],
+                                                                mean=joints_mean, fps=joints_fps, space=rotations_space)
     return out
 
 

@@ -9,6 +9,8 @@ A renderer, an avatar or a metric in metres needs joints.  The reference bridges
 ``joints_from_tracks(track, skeleton, ...)``  ``[..., T, 3K]`` -> ``[..., T_out, J, 3]``: add the mean, optionally re-normalise the bones, walk the
                                               tree; with ``fps=(src, dst)`` also resample linearly to the renderer's frame rate
 ``dir_vec_from_joints(joints, skeleton)``     the inverse: joints -> unit bone vectors (minus the mean): the ``seed_pose`` a generator takes
+``rotations_from_tracks(track, skeleton, rest, ...)``  ``[..., T, 3K]`` -> ``[..., T_out, K, 4]``: one local (or global) unit quaternion
+                                              ``(w, x, y, z)`` per bone relative to the rest pose ``rest [K, 3]``: what a rigged avatar consumes
 
 Definition (include/emogest.h).  For a source frame t: ``x_k = track[t, 3k:3k+3] + mean_k``; with ``unit``: ``x_k /= max(|x_k|, 1e-12)``;
 ``p[0] = 0`` and ``p[child_k] = p[parent_k] + length_k * x_k`` in table order.  With ``L / M = dst / src`` reduced, a row of n valid frames has
@@ -16,6 +18,12 @@ Definition (include/emogest.h).  For a source frame t: ``x_k = track[t, 3k:3k+3]
 ``f = (k' M - lo L) / L`` in exact integers: ``datapath.resample_pose_seq``'s linear interpolation with its extrapolation past the last frame
 (n = 1: every frame is ``p(0)``).  At the native rate nothing is blended.  Output frames from ``n_out`` on are zeros; source frames from n on
 are never used and may hold NaN.
+
+Rotations (include/emogest.h: eg_skeleton_rotations).  ``rest`` rows are normalised in float64 and rounded to fp32.  ``pb(k)`` is the bone whose
+child is ``parents[k]`` (-1 at the root); ``x^_k = x_k / max(|x_k|, 1e-12)``; in table order ``P_k = G_pb(k)`` (the identity at the root),
+``v_k = conj(P_k) o x^_k``, ``L_k = arc(rest_k, v_k)``, ``G_k = P_k (x) L_k`` -- ``arc(a, b)`` the shortest arc ``(1 + c, a x b)`` normalised,
+``c = a . b``, or for ``c < -1 + 1e-6`` the half turn about ``a x e_m`` (``e_m`` the first axis on which ``|a|`` is smallest).  On an interpolated
+frame the vectors are blended (after the mean), then the chain runs on the blended frame.
 
 CUDA tensors go through the kernels (fp32; there is no eager-PyTorch fallback for them).  numpy arrays and CPU tensors take the definition in
 float64 numpy -- what the reference's functions compute -- so data preparation and the drop-ins of ``utils.data_utils_expressive`` run without
@@ -32,8 +40,8 @@ import torch
 from . import _lib as L
 from ._host import BoundedCache, host_ptr, int_list, ptr as _ptr, stream as _stream
 
-__all__ = ["Skeleton", "ted_expressive", "joints_from_tracks", "dir_vec_from_joints", "out_frames", "rate_ratio", "TILE_FRAMES", "MAX_BONES",
-           "MAX_FACTOR"]
+__all__ = ["Skeleton", "RestPose", "ted_expressive", "joints_from_tracks", "dir_vec_from_joints", "rotations_from_tracks", "out_frames",
+           "rate_ratio", "TILE_FRAMES", "MAX_BONES", "MAX_FACTOR"]
 
 TILE_FRAMES = L.EG_SKELETON_TILE_FRAMES      # output frames of one workgroup
 MAX_BONES = L.EG_SKELETON_MAX_BONES
@@ -55,6 +63,7 @@ class Skeleton:
         self.J = self.K + 1
         L.check(L.load().eg_skeleton_check(*self.host_ptrs(), self.K), "eg_skeleton_check")
         self._tables = BoundedCache()
+        self._rests = BoundedCache(limit=16)
 
     def host_ptrs(self):
         return host_ptr(self.parents), host_ptr(self.children), host_ptr(self.lengths32)
@@ -76,6 +85,25 @@ class Skeleton:
             d[b] = d[a] + 1
         return d
 
+    @property
+    def bone_parents(self) -> np.ndarray:
+        """``pb [K]``: the bone whose child is ``parents[k]``, -1 where that is the root.  ``pb[k] < k``."""
+        owner = {int(b): k for k, b in enumerate(self.children)}
+        return np.array([owner.get(int(a), -1) for a in self.parents], np.int64)
+
+    def rest_pose(self, rest) -> "RestPose":
+        """The checked, normalised rest pose ``rest [K, 3]`` with its level table; built once per distinct pose (the last 16 are kept)."""
+        if isinstance(rest, RestPose):
+            if rest.sk is not self and rest.sk != self:
+                raise L.EgError(f"rest pose of {rest.sk!r} used with {self!r}")
+            return rest
+        if isinstance(rest, torch.Tensor):
+            rest = rest.detach().cpu().numpy()
+        raw = np.ascontiguousarray(rest, np.float64)
+        if raw.shape != (self.K, 3):
+            raise L.EgError(f"rest pose shape {raw.shape}: a skeleton of K={self.K} bones takes one direction per bone, [{self.K}, 3]")
+        return self._rests.get(raw.tobytes(), lambda: RestPose(self, raw))
+
     def table(self, device) -> torch.Tensor:
         """int32 ``[3K]`` on ``device``: parents | children | lengths (fp32 bits)."""
         return self._tables.get(str(device), lambda: torch.from_numpy(
@@ -89,6 +117,27 @@ class Skeleton:
 
     def __repr__(self):
         return f"Skeleton(bones={self.K}, joints={self.J})"
+
+
+class RestPose:
+    """The bind pose of an avatar for one skeleton: ``raw [K, 3]`` float64 as given (eg_skeleton_rest_check refuses a non-finite or
+    near-zero row by name), ``unit32 [K, 3]``: every row normalised in float64 and rounded to fp32 -- the unit vectors both the device and the
+    float64 path use -- and ``words``, eg_skeleton_levels' table (levels by depth, bone parents, the same fp32 rows), uploaded once per device."""
+
+    def __init__(self, sk: Skeleton, raw: np.ndarray):
+        self.sk, self.raw = sk, raw
+        L.check(L.load().eg_skeleton_rest_check(host_ptr(raw), sk.K), "eg_skeleton_rest_check")
+        self.unit32 = (raw / np.sqrt(raw[:, 0] * raw[:, 0] + raw[:, 1] * raw[:, 1] + raw[:, 2] * raw[:, 2])[:, None]).astype(np.float32)
+        self.words = np.zeros(65 + 5 * sk.K, np.int32)
+        L.check(L.load().eg_skeleton_levels(*sk.host_ptrs(), sk.K, host_ptr(raw), host_ptr(self.words)), "eg_skeleton_levels")
+        self._tables = BoundedCache()
+
+    def table(self, device) -> torch.Tensor:
+        """int32 ``[65 + 5K]`` on ``device``."""
+        return self._tables.get(str(device), lambda: torch.from_numpy(self.words).to(device))
+
+    def __repr__(self):
+        return f"RestPose(bones={self.sk.K}, levels={int(self.words[0])})"
 
 
 def ted_expressive() -> Skeleton:
@@ -260,6 +309,75 @@ def _dir_vec64(p: np.ndarray, sk: Skeleton, frames: List[int], mean) -> np.ndarr
     return out
 
 
+# quaternions (w, x, y, z) on the last axis, float64
+def _qmul(p: np.ndarray, q: np.ndarray) -> np.ndarray:
+    pw, px, py, pz = np.moveaxis(p, -1, 0)
+    qw, qx, qy, qz = np.moveaxis(q, -1, 0)
+    return np.stack([pw * qw - px * qx - py * qy - pz * qz, pw * qx + px * qw + py * qz - pz * qy,
+                     pw * qy - px * qz + py * qw + pz * qx, pw * qz + px * qy - py * qx + pz * qw], -1)
+
+
+def _qrot(q: np.ndarray, v: np.ndarray) -> np.ndarray:
+    """q o v."""
+    u, w = q[..., 1:], q[..., :1]
+    t = 2.0 * np.cross(u, v)
+    return v + w * t + np.cross(u, t)
+
+
+def _qconj(q: np.ndarray) -> np.ndarray:
+    return q * np.array([1.0, -1.0, -1.0, -1.0])
+
+
+def _arc64(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """a [3] unit, b [n, 3] unit or zero -> [n, 4]."""
+    c = b[:, 0] * a[0] + b[:, 1] * a[1] + b[:, 2] * a[2]
+    q = np.concatenate([(1.0 + c)[:, None], np.cross(a[None, :], b)], -1)
+    q = q / np.maximum(np.sqrt((q * q).sum(-1, keepdims=True)), 1e-300)
+    half = c < -1.0 + 1e-6
+    if half.any():
+        e = np.zeros(3)
+        e[int(np.argmin(np.abs(a)))] = 1.0                      # argmin: the first axis on ties
+        nrm = np.cross(a, e)
+        q[half] = np.concatenate([[0.0], nrm / np.sqrt((nrm * nrm).sum())])
+    return q
+
+
+def _rotations64(v: np.ndarray, sk: Skeleton, rest: np.ndarray, frames: List[int], mean, glob: bool, Lf: int, M: int) -> np.ndarray:
+    """v [B, T, 3K] float64, rest [K, 3] (unit), frames [B] -> [B, ceil(T L / M), K, 4]."""
+    B, T, _D = v.shape
+    out = np.zeros((B, -(-T * Lf // M), sk.K, 4))
+    pb = sk.bone_parents
+    for b in range(B):
+        n = frames[b]
+        if n < 1:
+            continue
+        x = v[b, :n].reshape(n, sk.K, 3)
+        if mean is not None:
+            x = x + mean.reshape(sk.K, 3)
+        n_out = -(-n * Lf // M)
+        if Lf == M:
+            pass
+        elif n == 1:
+            x = np.repeat(x[:1], n_out, 0)
+        else:                                                   # the vectors are blended, then the chain runs on the blended frame
+            k = np.arange(n_out, dtype=np.int64)
+            lo = np.minimum(k * M // Lf, n - 2)
+            f = ((k * M - lo * Lf) / Lf)[:, None, None]
+            x = (x[lo + 1] - x[lo]) * f + x[lo]
+        x = x / np.maximum(np.sqrt((x * x).sum(-1, keepdims=True)), 1e-12)
+        G = np.zeros((n_out, sk.K, 4))
+        loc = np.zeros((n_out, sk.K, 4))
+        for k in range(sk.K):
+            if pb[k] < 0:
+                loc[:, k] = G[:, k] = _arc64(rest[k], x[:, k])
+            else:
+                P = G[:, pb[k]]
+                loc[:, k] = _arc64(rest[k], _qrot(_qconj(P), x[:, k]))
+                G[:, k] = _qmul(P, loc[:, k])
+        out[b, :n_out] = G if glob else loc
+    return out
+
+
 # ---- the device path ---------------------------------------------------------------------------------------------------------------------
 def launch_joints(track: torch.Tensor, sk: Skeleton, d_frames: Optional[torch.Tensor] = None, draws: int = 1, frame_unit: int = 1,
                   mean: Optional[torch.Tensor] = None, unit: bool = False, ratio: Tuple[int, int] = (1, 1),
@@ -288,6 +406,31 @@ def launch_dir_vec(joints: torch.Tensor, sk: Skeleton, d_frames: Optional[torch.
         out = torch.empty(B, T, sk.pose_dim, dtype=torch.float32, device=joints.device)
     L.check(L.load().eg_skeleton_dir_vec(_ptr(joints), B, T, *sk.host_ptrs(), sk.K, _ptr(sk.table(joints.device)), _ptr(d_frames), int(draws),
                                          int(frame_unit), _ptr(mean), _ptr(out), _stream(joints.device)), "eg_skeleton_dir_vec")
+    return out
+
+
+def _space(space, who: str) -> int:
+    if space not in ("local", "global"):
+        raise L.EgError(f"{who}: space={space!r}: 'local' (every bone relative to its parent) or 'global'")
+    return L.EG_SKELETON_SPACE_GLOBAL if space == "global" else L.EG_SKELETON_SPACE_LOCAL
+
+
+def launch_rotations(track: torch.Tensor, sk: Skeleton, rest: RestPose, d_frames: Optional[torch.Tensor] = None, draws: int = 1,
+                     frame_unit: int = 1, mean: Optional[torch.Tensor] = None, space: str = "local", ratio: Tuple[int, int] = (1, 1),
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """eg_skeleton_rotations on ``track [B, T, 3K]`` (contiguous fp32 CUDA, 16-byte aligned) -> ``[B, T_out, K, 4]``: one launch on the current
+    stream, nothing else (the level table is uploaded on first use per device: warm up before a capture).  ``rest``: ``sk.rest_pose(...)``;
+    the other arguments as in ``launch_joints``."""
+    B, T, D = track.shape
+    if D != sk.pose_dim:
+        raise L.EgError(f"skeleton of {sk.K} bones takes tracks of {sk.pose_dim} columns, got {D}")
+    Lf, M = ratio
+    t_out = -(-T * Lf // M)
+    if out is None:
+        out = torch.empty(B, t_out, sk.K, 4, dtype=torch.float32, device=track.device)
+    L.check(L.load().eg_skeleton_rotations(_ptr(track), B, T, *sk.host_ptrs(), sk.K, host_ptr(rest.raw), _ptr(rest.table(track.device)),
+                                           _ptr(d_frames), int(draws), int(frame_unit), _ptr(mean), _space(space, "launch_rotations"), Lf, M,
+                                           _ptr(out), out.shape[1], _stream(track.device)), "eg_skeleton_rotations")
     return out
 
 
@@ -354,3 +497,46 @@ def dir_vec_from_joints(joints, skeleton: Skeleton, frames=None, mean=None):
     per_row = [n for n in (fr if fr is not None else [T] * U) for _ in range(R)]
     d = _dir_vec64(p, sk, per_row, _mean_host(mean, sk.K, who)).reshape(lead + (T, sk.pose_dim))
     return torch.from_numpy(d) if isinstance(joints, torch.Tensor) else d
+
+
+def rotations_from_tracks(track, skeleton: Skeleton, rest, frames=None, mean=None, fps=None, space: str = "local"):
+    """``track [..., T, 3K]`` with up to two leading axes -> ``rotations [..., T_out, K, 4]``: per bone and output frame the unit quaternion
+    ``(w, x, y, z)`` that turns the rest pose's bone into the track's -- ``space="local"``: relative to the parent bone (a pure swing, ``w >= 0``:
+    what a glTF / VRM node, an engine rig or a BVH channel takes); ``"global"``: relative to the root, ``G_k o rest_k = x^_k``.
+
+    ``rest [K, 3]``: the direction of every bone in the avatar's bind pose (any length; a row that is not finite or shorter than 1e-6 is
+    refused by name), or ``skeleton.rest_pose(rest)``.  ``frames``, ``mean`` and ``fps`` as in ``joints_from_tracks``; on a resampled frame
+    the bone vectors are blended and the rotations follow from the blended frame.  Forward kinematics with the offsets
+    ``lengths[k] * rest_k`` and the local rotations gives ``joints_from_tracks(..., unit=True)``.
+
+    A CUDA tensor: one kernel launch, fp32 CUDA result.  numpy or a CPU tensor: the definition in float64.  With ``frames`` or ``fps`` the
+    result is ``(rotations, rotation_frames)`` under the rule of ``joints_from_tracks``."""
+    who = "rotations_from_tracks"
+    if not isinstance(skeleton, Skeleton):
+        raise L.EgError(f"{who}: skeleton must be a Skeleton, got {type(skeleton).__name__}")
+    sk = skeleton
+    shape = tuple(track.shape)
+    if len(shape) < 2 or shape[-2] < 1:
+        raise L.EgError(f"{who}: track shape {shape}: need [..., T >= 1, {sk.pose_dim}]")
+    if shape[-1] != sk.pose_dim:
+        raise L.EgError(f"{who}: track shape {shape}: a skeleton of K={sk.K} bones takes 3K={sk.pose_dim} columns per frame, not {shape[-1]}")
+    sp = _space(space, who)
+    pose = sk.rest_pose(rest)
+    lead, U, R = _lead(shape, 2, who)
+    T = shape[-2]
+    Lf, M = rate_ratio(fps, f"{who}: fps")
+    fr = _frames_list(frames, U, T, who)
+    t_out = -(-T * Lf // M)
+    if _is_cuda(track):
+        x = _dev32(track).reshape(U * R, T, sk.pose_dim)
+        q = launch_rotations(x, sk, pose, _frames_dev(fr, x.device), R, 1, _mean_dev(mean, sk.K, x.device, who), space, (Lf, M))
+        rot = q.reshape(lead + (t_out, sk.K, 4))
+    else:
+        v = _host64(track, who).reshape(U * R, T, sk.pose_dim)
+        per_row = [n for n in (fr if fr is not None else [T] * U) for _ in range(R)]
+        q = _rotations64(v, sk, pose.unit32.astype(np.float64), per_row, _mean_host(mean, sk.K, who), sp == L.EG_SKELETON_SPACE_GLOBAL, Lf, M)
+        q = q.reshape(lead + (t_out, sk.K, 4))
+        rot = torch.from_numpy(q) if isinstance(track, torch.Tensor) else q
+    if frames is None and fps is None:
+        return rot
+    return rot, [-(-n * Lf // M) for n in (fr if fr is not None else [T] * U)]

@@ -150,15 +150,20 @@ class GestureStream:
     `joints=skeleton` (a skeleton.Skeleton with 3K == pose_dim; `joints_mean [pose_dim]`, `joints_unit` as in skeleton.joints_from_tracks): every
     step ends with one more launch (inside the graph) that leaves the joint positions of the rows just emitted in `last_joints [U, H, J, 3]`
     -- zeros for a row that was not valid, None while `rows` is None; `push` returns what it returned.  `tail_joints()`: the joints of `tail()`.
-    `joints_fps` is refused: a frame-rate change needs the frame after the last one emitted."""
+    `joints_fps` is refused: a frame-rate change needs the frame after the last one emitted.
+    `rotations=rest` (with `joints=`; `rest [K, 3]` the avatar's bind pose, `rotations_space` as in skeleton.rotations_from_tracks): one more
+    launch inside the graph leaves the bone rotations of the rows just emitted in `last_rotations [U, H, K, 4]` under the same rules;
+    `tail_rotations()`: the rotations of `tail()`."""
 
     def __init__(self, models: Tuple, rows: int, seed_pose: torch.Tensor, *, hop_samples: Optional[int] = None, n_samples: Optional[int] = None,
                  fps: int = 15, sample_rate: int = 16000, alpha: Optional[torch.Tensor] = None, graph: bool = True, want_windows: bool = False,
                  draws: Optional[int] = None, audio_rate: Optional[int] = None, joints=None, joints_mean=None, joints_unit: bool = False,
-                 joints_fps=None):
+                 joints_fps=None, rotations=None, rotations_space: str = "local"):
         if joints_fps is not None:
             raise L.EgError("GestureStream: joints_fps= is not supported (a frame-rate change needs the frame after the last one emitted, which a "
                             "stream does not have yet); resample the joints of the finished track with skeleton.joints_from_tracks(..., fps=)")
+        if rotations is not None and joints is None:
+            raise L.EgError("GestureStream: rotations= without joints=skeleton (the rest pose belongs to a skeleton's bones)")
         if draws is not None:
             raise L.EgError("GestureStream: draws= is not supported (a stream has one track per row); for several sampled tracks of a whole "
                             "recording call the rectangular synthesize(..., draws=R), or open the stream with each speaker's row repeated")
@@ -182,6 +187,12 @@ class GestureStream:
                 raise L.EgError(f"GestureStream: joints=: the skeleton has K={joints.K} bones, 3K={joints.pose_dim} != pose_dim={self.D}")
         elif joints_mean is not None or joints_unit:
             raise L.EgError("GestureStream: joints_mean / joints_unit without joints=skeleton")
+        self._rest, self._rot_space = None, rotations_space
+        if rotations is not None:
+            SK._space(rotations_space, "GestureStream: rotations_space")
+            self._rest = joints.rest_pose(rotations)          # held here: the captured graph replays the address of its device table
+        elif rotations_space != "local":
+            raise L.EgError("GestureStream: rotations_space without rotations=rest")
         if self.mel is not None:
             self.hop = int(round(self.H * sample_rate / fps)) if hop_samples is None else int(hop_samples)
             self.n = (self.spec_len - 1) * 512 if n_samples is None else int(n_samples)
@@ -238,6 +249,7 @@ class GestureStream:
         self.last_windows: List[Optional[int]] = [None] * self.U
         self.last_window: Optional[torch.Tensor] = None          # with want_windows: the raw poses [U, F, D] of the last step
         self.last_joints: Optional[torch.Tensor] = None          # with joints=: the joints [U, H, J, 3] of the rows just emitted (zeros for a row that was not valid)
+        self.last_rotations: Optional[torch.Tensor] = None       # with rotations=: their bone rotations [U, H, K, 4], under the same rules
         eng.stream_reset(self._state, *self._geom, self.seed_pose)
 
     # ---- engines, staleness ----
@@ -295,6 +307,9 @@ class GestureStream:
             if self._sk is not None:                # one more launch after the hand-off: row u has valid[u] * H frames
                 from .skeleton import launch_joints
                 out["joints"] = launch_joints(out["rows"], self._sk, out["valid"], 1, self.H, self._sk_mean, self._sk_unit)
+            if self._rest is not None:
+                from .skeleton import launch_rotations
+                out["rotations"] = launch_rotations(out["rows"], self._sk, self._rest, out["valid"], 1, self.H, self._sk_mean, self._rot_space)
             return out
 
     def _push_only(self):
@@ -420,6 +435,7 @@ class GestureStream:
         self.plan.rows, self.last_valid, self.last_windows = rows, valid, [i["w"] for i in infos]
         self.last_window = out["window"].clone() if out is not None and self.want_windows else None
         self.last_joints = out["joints"].clone() if out is not None and self._sk is not None else None
+        self.last_rotations = out["rotations"].clone() if out is not None and self._rest is not None else None
         if out is None:
             return None, torch.zeros(self.U, dtype=torch.int32, device=self.device)
         return out["rows"].clone(), out["valid"].clone()
@@ -481,6 +497,14 @@ class GestureStream:
         from .skeleton import launch_joints
         with torch.no_grad():
             return launch_joints(self.tail(), self._sk, None, 1, 1, self._sk_mean, self._sk_unit)
+
+    def tail_rotations(self) -> torch.Tensor:
+        """[U, P, K, 4]: the bone rotations of `tail()` (a session opened with rotations=)."""
+        if self._rest is None:
+            raise L.EgError("tail_rotations: the session was opened without rotations=rest")
+        from .skeleton import launch_rotations
+        with torch.no_grad():
+            return launch_rotations(self.tail(), self._sk, self._rest, None, 1, 1, self._sk_mean, self._rot_space)
 
     def finish(self, text, labels=None, z=None, sampled=None, last_chunk=None, ends=None) -> torch.Tensor:
         """End every row together and run R = text.shape[1] steps in all: `text [U, R, text_len]`, `labels [U, 8]` or `[U, R, 8]`, `z [U, R, 32]`

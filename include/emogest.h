@@ -502,6 +502,47 @@ int eg_skeleton_dir_vec(const float* joints, int32_t rows, int32_t T, const int3
                         int32_t bones, const void* d_table, const int32_t* d_frames, int32_t draws, int32_t frame_unit, const float* d_mean,
                         float* dir_vec, void* stream);
 
+/* Rotations: track [rows, T, 3K] fp32 -> one unit quaternion (w, x, y, z) per bone and output frame, relative to a rest pose: what a rigged
+ * avatar (glTF / VRM, a game-engine rig, BVH) consumes.  rotations [rows, out_stride, K, 4] fp32.
+ * Inputs.  The bone table as above.  rest [K, 3] float64 on the HOST: the direction of every bone in the avatar's bind pose.  Each row is
+ * normalised in float64 (r / sqrt(r . r)) and rounded to fp32; from then on the rows are treated as unit vectors.  A row that is not finite
+ * or whose norm is below 1e-6 is refused by name (eg_skeleton_rest_check: host only, no HIP call).
+ * Helpers.  pb(k): the bone whose child is parents[k], -1 when parents[k] is the root -- unique (a joint is the child of at most one bone),
+ * and pb(k) < k (topological order).  x_k = track[3k .. 3k+2] (+ d_mean) of a source frame; x^_k = x_k / max(|x_k|, 1e-12).
+ * arc(a, b) for unit a, b with c = a . b:  c >= -1 + 1e-6: q = (1 + c, a x b) / |(1 + c, a x b)|, the shortest arc, w >= 0;
+ * otherwise the half turn q = (0, n), n = (a x e_m) / |a x e_m| with e_m the coordinate axis on which |a| is smallest (the first such axis
+ * on ties).  A zero b gives the identity (the formula yields it).
+ * Chain, in table order; quaternions are Hamilton products, q o v rotates v by q:
+ *     P_k = G_pb(k)                 (the identity when pb(k) = -1)
+ *     v_k = conj(P_k) o x^_k        (the bone's direction seen from its parent's frame)
+ *     L_k = arc(rest_k, v_k)        (local rotation: a pure swing relative to the parent, w >= 0)
+ *     G_k = P_k (x) L_k             (global rotation; its sign is the product's, never flipped)
+ * so G_k o rest_k = x^_k for every bone, and forward kinematics with the offsets lengths[k] * rest_k and the locals L_k reproduces
+ * eg_skeleton_joints(unit = 1).
+ * Frames.  rows, d_frames, draws, frame_unit, the reduced ratio L / M, n_out = ceil(n L / M), lo and f exactly as in eg_skeleton_joints.  On
+ * an interpolated frame the VECTORS are blended before anything else: x_k = fmaf(x_k(lo + 1) - x_k(lo), f, x_k(lo)), taken after the mean;
+ * the chain then runs on the blended frame.  n = 1: frame 0.  At L / M = 1 nothing is blended.
+ * Output.  L_k for space = EG_SKELETON_SPACE_LOCAL, G_k for EG_SKELETON_SPACE_GLOBAL.  Frames k' >= n_out are written as zeros; source
+ * frames t >= n are never read and may hold NaN.
+ * eg_skeleton_levels (host only) writes the device table of the call, EG_SKELETON_LEVEL_WORDS(K) 32-bit words, which the caller uploads as
+ * d_levels: [0] the number of depth levels; [1 .. 64] the first position of every level in `order` (the count K from the last level on);
+ * order [K]: the bones sorted by depth, table order inside a level; pb [K]; the normalised rest [K, 3] (fp32 bits).  One thread owns one
+ * (output frame, bone) and a workgroup walks the levels with one barrier each.  As with d_table nothing ties the upload to the host
+ * arguments: with a d_levels that differs the result is unspecified (its numbers are clamped, the accesses stay in range).
+ * Guarantees as for eg_skeleton_joints: caller-owned memory, no allocation, no synchronisation, one launch, capturable; one owning thread
+ * per output element (each bone's quaternion is one aligned 16-byte store), no atomics; a row's result does not depend on rows, on its
+ * place in the batch, on out_stride or on the tile a frame falls in.  Refuses by name before the launch what eg_skeleton_joints refuses,
+ * a bad rest row and an unknown space. */
+#define EG_SKELETON_SPACE_LOCAL 0
+#define EG_SKELETON_SPACE_GLOBAL 1
+#define EG_SKELETON_LEVEL_WORDS(K) (65 + 5 * (K))
+int eg_skeleton_rest_check(const double* rest, int32_t bones);
+int eg_skeleton_levels(const int32_t* parents, const int32_t* children, const float* lengths, int32_t bones, const double* rest,
+                       int32_t* words);
+int eg_skeleton_rotations(const float* track, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children, const float* lengths,
+                          int32_t bones, const double* rest, const void* d_levels, const int32_t* d_frames, int32_t draws, int32_t frame_unit,
+                          const float* d_mean, int32_t space, int32_t L, int32_t M, float* rotations, int64_t out_stride, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Beat-alignment score = model/Beat_score_v2.py alignment(sigma, order): load_audio + load_pose +
  * calculate_align for a batch of clips (test_emotion_gesture_diversity_iterative.py:241-248)

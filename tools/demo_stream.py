@@ -11,7 +11,10 @@ With --audio-rate HZ the recordings are made at that rate and the stream is open
 a StreamResampler runs first inside the same graph, and the rows equal synthesize on resample_audio(recording, HZ, delay=stream_delay(HZ)).
 With --joints the stream is opened with joints=skeleton.ted_expressive(): one more launch inside the graph leaves the joint positions of the
 rows just emitted in stream.last_joints [U, 30, 43, 3]; the script prints their shape and the wrist extent in metres per push.
-usage: demo_stream.py [rows=4] [seconds=20] [--audio-rate HZ] [--joints]"""
+With --rotations (and --joints) the stream also gets rotations=rest, the rest pose taken from the normalised first generated frame of row 0 (one
+window of synthesize beforehand): another launch inside the graph leaves the local bone rotations of the rows just emitted in
+stream.last_rotations [U, 30, 42, 4]; the script prints the largest elbow swing in degrees per push.
+usage: demo_stream.py [rows=4] [seconds=20] [--audio-rate HZ] [--joints [--rotations]]"""
 import os
 import sys
 import time
@@ -37,6 +40,11 @@ if JOINTS:
     from emotiongestures_amd.skeleton import ted_expressive
     sys.argv.remove("--joints")
     JK = dict(joints=ted_expressive(), joints_unit=True)
+ROTATIONS = "--rotations" in sys.argv
+if ROTATIONS:
+    sys.argv.remove("--rotations")
+    if not JOINTS:
+        sys.exit("--rotations needs --joints (the rest pose belongs to the skeleton's bones)")
 U = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 20.0
 dev = torch.device("cuda:0")
@@ -46,6 +54,11 @@ to16 = lambda n: R_.out_length(n, RATE) if AR else n
 
 gen = build_mirror("spatial", FRAMES, POSE_DIM, PRIOR, PRIOR, seed=7, precision="bf16x3").to(dev)
 vae = load_synth_weights(MLP_Reconstruct_v3(frames=FRAMES), 7).eval().to(dev)
+audio = torch.from_numpy(synth_audio(U, total, seed=90)).to(dev)
+if ROTATIONS:                                            # the rest pose: the first generated frame of row 0's first window
+    first = H.synthesize((gen, vae), audio[:1], torch.zeros(1, 1, 60, dtype=torch.int64, device=dev), torch.zeros(1, PRIOR, POSE_DIM, device=dev),
+                         labels=torch.nn.functional.one_hot(torch.zeros(1, dtype=torch.int64), 8).float().to(dev), z=torch.zeros(1, 1, 32), **AR)
+    JK["rotations"] = first["track"][0, PRIOR].reshape(-1, 3).cpu()
 stream = H.open_stream((gen, vae), U, torch.zeros(U, PRIOR, POSE_DIM, device=dev), **AR, **JK)
 hop, hop16 = stream.hop_in, stream.hop                    # samples per push at the caller's rate and at 16 kHz
 W = (to16(total) - 1) // hop16 + 1                               # windows per recording = pushes that carry its audio
@@ -53,7 +66,6 @@ short = total // 2                                       # the leaving row's fir
 W_short = (to16(short) - 1) // hop16 + 1
 leaver = U - 1
 
-audio = torch.from_numpy(synth_audio(U, total, seed=90)).to(dev)
 second = torch.from_numpy(synth_audio(1, short, seed=91)).to(dev)[0]
 labels = torch.nn.functional.one_hot(torch.arange(U) % 8, 8).float().to(dev)
 text = torch.zeros(U, 60, dtype=torch.int64, device=dev)
@@ -96,6 +108,10 @@ for k in range(1, steps + 1):
         j = stream.last_joints
         ext = [float((j[:, :, w].amax(1) - j[:, :, w].amin(1)).norm(dim=1).max()) for w in (6, 7)]
         print(f"         last_joints {tuple(j.shape)}: wrist extent left {ext[0]:.3f} m, right {ext[1]:.3f} m")
+    if ROTATIONS and stream.last_rotations is not None:
+        q = stream.last_rotations[valid.bool()]             # a row that was not valid holds zeros, not rotations
+        deg = [float(torch.rad2deg(2 * torch.acos(q[:, :, b, 0].clamp(max=1.0))).max()) for b in (4, 21)]      # the forearm bones
+        print(f"         last_rotations {tuple(q.shape)}: largest elbow swing left {deg[0]:.1f} degrees, right {deg[1]:.1f} degrees")
 final = stream.tail()
 
 ok = True

@@ -18,7 +18,10 @@ resampled to 16 kHz on the GPU (resample.resample_audio) before anything else ru
 With --joints (TED shape only) the rectangular call also returns the joint positions of every track in metres (skeleton.ted_expressive(): 43
 joints; the mean is zero here, the bones are re-normalised to unit length), with --joints-fps N resampled from 15 to N frames per second, and the
 script prints their shape and how far the two wrists travel.
-usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--joints-fps N]] [--out tracks.npz]"""
+With --rotations (and --joints) the call also returns one local rotation per bone and frame (unit quaternions w, x, y, z relative to the parent
+bone: what a rigged avatar takes) against a rest pose taken from the normalised first generated frame of recording 0, and the script prints
+their shape and the largest elbow swing in degrees.
+usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--joints-fps N] [--rotations]] [--out tracks.npz]"""
 import os
 import sys
 import time
@@ -33,7 +36,7 @@ from emotiongestures_amd.builders import build_mirror
 from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
 from emotiongestures_amd.synth import load_synth_weights, synth_audio
 
-argv, DRAWS, OUT, BEAT, DIVERSITY, RATE, JOINTS, JOINTS_FPS = [], 0, None, False, False, 16000, False, None
+argv, DRAWS, OUT, BEAT, DIVERSITY, RATE, JOINTS, JOINTS_FPS, ROTATIONS = [], 0, None, False, False, 16000, False, None, False
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--draws":
@@ -50,6 +53,8 @@ for a in it:
         JOINTS = True
     elif a == "--joints-fps":
         JOINTS_FPS = int(next(it))
+    elif a == "--rotations":
+        ROTATIONS = True
     else:
         argv.append(a)
 if DIVERSITY and DRAWS < 2:
@@ -58,6 +63,8 @@ if JOINTS and BEAT:
     sys.exit("--joints is for the TED shape: the BEAT generators' 282 columns are rotations, not bone direction vectors")
 if JOINTS_FPS and not JOINTS:
     sys.exit("--joints-fps needs --joints")
+if ROTATIONS and not JOINTS:
+    sys.exit("--rotations needs --joints (the rest pose belongs to the skeleton's bones)")
 U = int(argv[0]) if len(argv) > 0 else 4
 seconds = float(argv[1]) if len(argv) > 1 else 60.0
 dev = torch.device("cuda:0")
@@ -101,6 +108,8 @@ if BEAT:
 if JOINTS:
     from emotiongestures_amd.skeleton import ted_expressive
     jk = dict(joints=ted_expressive(), joints_unit=True, joints_fps=(FPS, JOINTS_FPS) if JOINTS_FPS else None)
+    if ROTATIONS:                                        # the rest pose: the first generated frame of recording 0 (normalised by the call)
+        jk["rotations"] = track[0, PRIOR].reshape(-1, 3).cpu()
     H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, **jk, **AR)          # warm-up (uploads the bone table)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -112,6 +121,11 @@ if JOINTS:
     print(f"--joints: joints {tuple(joints.shape)} (frames per recording {jo['joint_frames']}" +
           (f", {FPS} -> {JOINTS_FPS} fps" if JOINTS_FPS else "") + f"), one more launch in the call ({1e3 * dt_j:.2f} ms against {1e3 * dt:.2f} ms); "
           f"wrist extent: left {float(extent(6)):.3f} m, right {float(extent(7)):.3f} m")
+    if ROTATIONS:
+        rot = jo["rotations"]
+        swing = lambda k: float(torch.rad2deg(2 * torch.acos(rot[:, :, k, 0].clamp(max=1.0))).max())    # bone 4 / 21: left / right forearm
+        print(f"--rotations: rotations {tuple(rot.shape)}, one more launch; largest elbow swing against the first generated frame: "
+              f"left {swing(4):.1f} degrees, right {swing(21):.1f} degrees")
 
 # Recordings of unequal length in one call: recording u keeps (u + 1) / U of the audio.  Step s runs only the recordings that still have a
 # window s; the track is padded to the longest recording and zero past each recording's own end.
