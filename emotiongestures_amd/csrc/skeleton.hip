@@ -10,8 +10,9 @@
 // barrier, and the rows of the tile are conflict-free -- and writes the outputs coalesced, 16 bytes per lane where a quad lies inside the tile.
 // The bone table is an argument, read once per workgroup; nothing about a particular body is built in.  Every output element has one owning
 // thread; plain vector stores, no atomics, nothing device-scope; the grid depends on the shapes only.
-//   rotations (eg_skeleton_rest_check, eg_skeleton_levels, eg_skeleton_rotations): one local rotation per bone relative to a rest pose.  Same grid,
-//             same staging and the same frame handling, but the vectors are blended, not the results, and the chain is a dependent run of
+//   rotations (eg_skeleton_rest_check, eg_skeleton_levels, eg_skeleton_rotations): one local rotation per bone relative to a rest pose.  The grid,
+//             the staging and the frame handling are the forward kernel's (tile_of, Walk, stage_pass), but the vectors are blended, not the results,
+//             and the chain is a dependent run of
 //             quaternion products, so it is walked level by level: the host orders the bones by depth, one thread owns one (output frame, bone of
 //             the level), one barrier per level.  The global rotations live in an LDS tile g[bone][component][frame] (lanes of consecutive frames
 //             on consecutive banks); x is blended and normalised in registers as it is read; every (frame, bone) leaves as one aligned 16-byte store.
@@ -31,7 +32,7 @@ constexpr int HEAD = 3 * TAB + 3 * TAB;                 // parent | child | leng
 static_assert(NC <= THREADS, "one thread per column of the joint tile");
 static_assert(MAX_K < TAB, "table columns hold K <= 63 bones");
 
-__host__ __device__ inline int round4(int v) { return (v + 3) & ~3; }
+__host__ __device__ constexpr int round4(int v) { return (v + 3) & ~3; }
 __host__ __device__ inline long long out_frames(long long n, int L, int M) { return (n * L + M - 1) / M; }
 
 struct Args {
@@ -87,51 +88,63 @@ __device__ __forceinline__ int valid_frames(const Args& a, int b) {
     return (int)(v < 0 ? 0 : (v > a.T ? a.T : v));
 }
 
-// The host table is checked; the device copy is the caller's.  Its joint numbers index LDS, so they are clamped to 0..K here: with a stale
-// upload the result is unspecified, but every access stays inside the tile.
-__device__ __forceinline__ void load_table(const Args& a, int* ta, int* tb, float* tl, float* mn) {
-    for (int k = threadIdx.x; k < a.K; k += THREADS) {
-        ta[k] = min(max(a.table[k], 0), a.K);
-        tb[k] = min(max(a.table[a.K + k], 0), a.K);
-        tl[k] = __int_as_float(a.table[2 * a.K + k]);
-    }
+__device__ __forceinline__ void load_mean(const Args& a, float* mn) {
     if (a.mean)
         for (int r = threadIdx.x; r < 3 * a.K; r += THREADS) mn[r] = a.mean[r];
 }
 
-// grid: (tile of TF output frames) x row, flattened.  NATIVE: L / M = 1.
-template <bool UNIT, bool NATIVE>
-__global__ __launch_bounds__(THREADS) void skeleton_joints_kernel(const Args a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int K = a.K, D = 3 * K, J3 = 3 * (K + 1), tid = threadIdx.x;
-    int* ta = reinterpret_cast<int*>(lds);
-    int* tb = ta + TAB;
-    float* tl = lds + 2 * TAB;
-    float* mn = lds + 3 * TAB;
-    float* xin = lds + HEAD;
-    float* pj = xin + round4(SLOTS * D + 8);
+// The first HEAD words of LDS, filled by the workgroup.  The host table is checked; the device copy is the caller's.  Its joint numbers index
+// LDS, so they are clamped to 0..K here: with a stale upload the result is unspecified, but every access stays inside the tile.
+struct Head { int *ta, *tb; float *tl, *mn; };
+__device__ __forceinline__ Head load_head(const Args& a, float* lds) {
+    const Head h = {reinterpret_cast<int*>(lds), reinterpret_cast<int*>(lds) + TAB, lds + 2 * TAB, lds + 3 * TAB};
+    for (int k = threadIdx.x; k < a.K; k += THREADS) {
+        h.ta[k] = min(max(a.table[k], 0), a.K);
+        h.tb[k] = min(max(a.table[a.K + k], 0), a.K);
+        h.tl[k] = __int_as_float(a.table[2 * a.K + k]);
+    }
+    load_mean(a, h.mn);
+    return h;
+}
+
+// What a workgroup owns.  grid: (tile of TF frames) x row, flattened: frames [k0, k0 + cnt) of the T_out frames of row b, the first `live` of
+// them inside the row's own output (n valid source frames); the rest of the tile is the zero tail behind a ragged row.  NATIVE: L / M = 1.
+// live64 is live before it is cut to 32 bits, and zero_tail's offset is made from it: do not fold the two.  With `live` alone the compiler narrows
+// the selects, the joints prologue loses three scalar instructions, all code behind it moves by 12 bytes and the native kernel measures 1-2 % slower.
+struct Tile { int b; long long k0; int cnt, n; long long live64; int live; };
+
+template <bool NATIVE>
+__device__ __forceinline__ Tile tile_of(const Args& a, long long T_out) {
     const int b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
     const long long k0 = (long long)tile * TF;
-    const int cnt = (int)(a.T_out - k0 < TF ? a.T_out - k0 : TF);
+    const int cnt = (int)(T_out - k0 < TF ? T_out - k0 : TF);
     const int n = valid_frames(a, b);
     const long long n_out = NATIVE ? n : out_frames(n, a.L, a.M);
-    const int live = (int)(n_out - k0 < 0 ? 0 : (n_out - k0 < cnt ? n_out - k0 : cnt));
-    const long long out0 = ((long long)b * a.T_out + k0) * J3;
-    if (live < cnt) store_range(a.dst, out0, J3, out0 + (long long)live * J3, out0 + (long long)cnt * J3, [](int, int) { return 0.f; });
-    if (live == 0) return;
-    load_table(a, ta, tb, tl, mn);
-    for (int c = tid; c < NC; c += THREADS) pj[c] = 0.f;                        // the root joint, every column
-    const bool has_mean = a.mean != nullptr;
-    const long long total = (long long)a.B * a.T * D;
-    const int L = a.L, M = a.M;
-    auto seg = [&](long long kk) -> long long {                                 // first source frame of output frame kk
+    const long long live = n_out - k0 < 0 ? 0 : (n_out - k0 < cnt ? n_out - k0 : cnt);
+    return {b, k0, cnt, n, live, (int)live};
+}
+
+// Zeros in the frames [live, cnt) of a tile whose frames have `row` floats and start at float out0.
+__device__ __forceinline__ void zero_tail(float* __restrict__ dst, long long out0, int row, const Tile& t) {
+    if (t.live < t.cnt) store_range(dst, out0, row, out0 + t.live64 * row, out0 + (long long)t.cnt * row, [](int, int) { return 0.f; });
+}
+
+// The source frames of a tile of the forward kernels.  A pass makes the outputs [i, i1) of the tile from the source frames
+// [s_base, s_base + nslots): as many outputs as SLOTS source frames reach (all of them unless the rate drops, M > L).
+struct Pass { long long s_base; int i1, nslots; };
+struct Blend { int slot; float f; };                    // output = frame(slot) + (frame(slot + 1) - frame(slot)) * f, slots counted from s_base
+
+template <bool NATIVE>
+struct Walk {
+    long long k0;
+    int n, L, M;
+    __device__ __forceinline__ long long seg(long long kk) const {             // first source frame of output frame kk
         if (NATIVE) return kk;
         if (n < 2) return 0;
         const long long lo = kk * M / L;
         return lo < n - 2 ? lo : n - 2;
-    };
-    for (int i = 0; i < live;) {
-        // outputs [i, i1) of the tile from the source frames [s_base, s_base + nslots): as many outputs as SLOTS source frames reach
+    }
+    __device__ __forceinline__ Pass pass(int i, int live) const {
         const long long s_base = seg(k0 + i);
         int i1 = live;
         if (!NATIVE && M > L) {
@@ -139,24 +152,57 @@ __global__ __launch_bounds__(THREADS) void skeleton_joints_kernel(const Args a) 
             i1 = jmax + 1 < live ? (int)(jmax + 1) : live;
             i1 = i1 > i ? i1 : i + 1;
         }
-        const int nslots = (int)(seg(k0 + i1 - 1) - s_base) + ((NATIVE || n < 2) ? 1 : 2);
-        // no barrier before a later pass: the one after the previous chain ended its reads of xin, the one below precedes every write of pj
-        const long long g0 = ((long long)b * a.T + s_base) * D;
-        stage_span(a.src, g0, g0 + (long long)nslots * D, total, xin);
-        __syncthreads();
-        float* x = xin + (int)(g0 & 3);
+        return {s_base, i1, (int)(seg(k0 + i1 - 1) - s_base) + ((NATIVE || n < 2) ? 1 : 2)};
+    }
+    __device__ __forceinline__ Blend blend(const Pass& p, int fr) const {      // output frame fr of the tile; not NATIVE, n >= 2
+        const long long kk = k0 + fr, lo = seg(kk);
+        return {(int)(lo - p.s_base), (float)(kk * M - lo * L) / (float)L};
+    }
+};
+
+// The pass that starts at output i of the tile (for (i = 0; i < live; i = p.i1)): its source frames staged into xin, one barrier behind the
+// loads; returns where they start.  No barrier before the staging of a later pass: the last barrier of the caller's pass ended the reads of
+// xin (joints: the one behind the chain; rotations: the one behind the last level), and the one here precedes every write of the caller's tile.
+template <bool NATIVE>
+__device__ __forceinline__ float* stage_pass(const Args& a, const Tile& t, const Walk<NATIVE>& w, int i, float* xin, Pass& p) {
+    const int D = 3 * a.K;
+    p = w.pass(i, t.live);
+    const long long g0 = ((long long)t.b * a.T + p.s_base) * D;
+    stage_span(a.src, g0, g0 + (long long)p.nslots * D, (long long)a.B * a.T * D, xin);
+    __syncthreads();
+    return xin + (int)(g0 & 3);
+}
+
+// NATIVE: L / M = 1.
+template <bool UNIT, bool NATIVE>
+__global__ __launch_bounds__(THREADS) void skeleton_joints_kernel(const Args a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int K = a.K, D = 3 * K, J3 = 3 * (K + 1), tid = threadIdx.x;
+    float* xin = lds + HEAD;
+    float* pj = xin + round4(SLOTS * D + 8);
+    const Tile t = tile_of<NATIVE>(a, a.T_out);
+    const long long out0 = ((long long)t.b * a.T_out + t.k0) * J3;
+    zero_tail(a.dst, out0, J3, t);
+    if (t.live == 0) return;
+    const Head h = load_head(a, lds);
+    for (int c = tid; c < NC; c += THREADS) pj[c] = 0.f;                        // the root joint, every column
+    const bool has_mean = a.mean != nullptr;
+    const Walk<NATIVE> w = {t.k0, t.n, a.L, a.M};
+    Pass ps;
+    for (int i = 0; i < t.live; i = ps.i1) {
+        float* x = stage_pass(a, t, w, i, xin, ps);
         if (UNIT) {                                                             // one thread per (source frame, bone), in place
-            for (int w = tid; w < nslots * K; w += THREADS) {
-                const int s = w / K, k = w - s * K;
+            for (int q = tid; q < ps.nslots * K; q += THREADS) {
+                const int s = q / K, k = q - s * K;
                 float* v = x + s * D + 3 * k;
                 float v0 = v[0], v1 = v[1], v2 = v[2];
-                if (has_mean) { v0 += mn[3 * k]; v1 += mn[3 * k + 1]; v2 += mn[3 * k + 2]; }
+                if (has_mean) { v0 += h.mn[3 * k]; v1 += h.mn[3 * k + 1]; v2 += h.mn[3 * k + 2]; }
                 const float d = fmaxf(sqrtf(v0 * v0 + v1 * v1 + v2 * v2), 1e-12f);
                 v[0] = v0 / d; v[1] = v1 / d; v[2] = v2 / d;
             }
             __syncthreads();
         }
-        if (tid < 3 * nslots) {                                                 // the chain: this thread's column of every joint
+        if (tid < 3 * ps.nslots) {                                              // the chain: this thread's column of every joint
             const int s = tid / 3, c = tid - 3 * s;
             const float* xs = x + s * D + c;
             float* pc = pj + tid;
@@ -164,63 +210,58 @@ __global__ __launch_bounds__(THREADS) void skeleton_joints_kernel(const Args a) 
             for (int k = 0; k < K; ++k) {
                 const float xn = k + 1 < K ? xs[3 * (k + 1)] : 0.f;             // the next bone's vector is in flight while this one is added
                 float v = xv;
-                if (!UNIT && has_mean) v += mn[3 * k + c];
-                pc[tb[k] * NC] = fmaf(tl[k], v, pc[ta[k] * NC]);
+                if (!UNIT && has_mean) v += h.mn[3 * k + c];
+                pc[h.tb[k] * NC] = fmaf(h.tl[k], v, pc[h.ta[k] * NC]);
                 xv = xn;
             }
         }
         __syncthreads();
-        store_range(a.dst, out0, J3, out0 + (long long)i * J3, out0 + (long long)i1 * J3, [&](int fr, int r) {
+        store_range(a.dst, out0, J3, out0 + (long long)i * J3, out0 + (long long)ps.i1 * J3, [&](int fr, int r) {
             const int jt = r / 3, c = r - 3 * jt;
             const float* row = pj + jt * NC + c;
             if (NATIVE) return row[3 * (fr - i)];
-            if (n < 2) return row[0];
-            const long long kk = k0 + fr, lo = seg(kk);
-            const float f = (float)(kk * M - lo * L) / (float)L;
-            const float p0 = row[3 * (int)(lo - s_base)], p1 = row[3 * (int)(lo - s_base) + 3];
-            return fmaf(p1 - p0, f, p0);
+            if (t.n < 2) return row[0];
+            const Blend bl = w.blend(ps, fr);
+            const float p0 = row[3 * bl.slot], p1 = row[3 * bl.slot + 3];
+            return fmaf(p1 - p0, bl.f, p0);
         });
-        i = i1;
     }
 }
 
-// grid: (tile of TF frames) x row, flattened.
 __global__ __launch_bounds__(THREADS) void skeleton_dir_vec_kernel(const Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int K = a.K, D = 3 * K, J3 = 3 * (K + 1);
-    int* ta = reinterpret_cast<int*>(lds);
-    int* tb = ta + TAB;
-    float* tl = lds + 2 * TAB;
-    float* mn = lds + 3 * TAB;
     float* pin = lds + HEAD;
-    const int b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
-    const long long t0 = (long long)tile * TF;
-    const int cnt = (int)(a.T - t0 < TF ? a.T - t0 : TF);
-    const int n = valid_frames(a, b);
-    const int live = (int)(n - t0 < 0 ? 0 : (n - t0 < cnt ? n - t0 : cnt));
-    const long long out0 = ((long long)b * a.T + t0) * D;
-    if (live < cnt) store_range(a.dst, out0, D, out0 + (long long)live * D, out0 + (long long)cnt * D, [](int, int) { return 0.f; });
-    if (live == 0) return;
-    load_table(a, ta, tb, tl, mn);
+    const Tile t = tile_of<true>(a, a.T);
+    const long long out0 = ((long long)t.b * a.T + t.k0) * D;
+    zero_tail(a.dst, out0, D, t);
+    if (t.live == 0) return;
+    const Head h = load_head(a, lds);
     const bool has_mean = a.mean != nullptr;
-    const long long g0 = ((long long)b * a.T + t0) * J3;
-    stage_span(a.src, g0, g0 + (long long)live * J3, (long long)a.B * a.T * J3, pin);
+    const long long g0 = ((long long)t.b * a.T + t.k0) * J3;
+    stage_span(a.src, g0, g0 + (long long)t.live * J3, (long long)a.B * a.T * J3, pin);
     __syncthreads();
     const float* p = pin + (int)(g0 & 3);
-    store_range(a.dst, out0, D, out0, out0 + (long long)live * D, [&](int fr, int r) {
+    store_range(a.dst, out0, D, out0, out0 + (long long)t.live * D, [&](int fr, int r) {
         const int k = r / 3, c = r - 3 * k;
-        const float* pa = p + fr * J3 + 3 * ta[k];
-        const float* pb = p + fr * J3 + 3 * tb[k];
+        const float* pa = p + fr * J3 + 3 * h.ta[k];
+        const float* pb = p + fr * J3 + 3 * h.tb[k];
         const float d0 = pb[0] - pa[0], d1 = pb[1] - pa[1], d2 = pb[2] - pa[2];
         const float d = fmaxf(sqrtf(d0 * d0 + d1 * d1 + d2 * d2), 1e-12f);
         const float v = (c == 0 ? d0 : (c == 1 ? d1 : d2)) / d;
-        return has_mean ? v - mn[r] : v;
+        return has_mean ? v - h.mn[r] : v;
     });
 }
 
-
 // ---- rotations ------------------------------------------------------------------------------------------------------------------------------
-constexpr int LV_OFFS = 68;                             // LDS words: level offsets [nlev + 1 <= 64] (+ pad)
+// The level table of eg_skeleton_levels (include/emogest.h): the level count | LEVEL_SLOTS level offsets | order [K] | bone parents [K] | rest [3K].
+constexpr int LEVEL_SLOTS = 64;
+constexpr int LV_FIRST = 1, LV_ORDER = LV_FIRST + LEVEL_SLOTS;
+__host__ __device__ constexpr int lv_parents(int K) { return LV_ORDER + K; }
+__host__ __device__ constexpr int lv_rest(int K) { return LV_ORDER + 2 * K; }
+static_assert(lv_rest(1) + 3 == EG_SKELETON_LEVEL_WORDS(1) && lv_rest(MAX_K) + 3 * MAX_K == EG_SKELETON_LEVEL_WORDS(MAX_K), "the header's table size");
+static_assert(MAX_K <= LEVEL_SLOTS, "a level per bone at most, and the offset behind the last one");
+constexpr int LV_OFFS = round4(LV_ORDER);               // LDS words: level offsets [nlev + 1 <= LEVEL_SLOTS] (+ pad)
 constexpr int RHEAD = LV_OFFS + 2 * TAB + 3 * TAB + 3 * TAB;    // offsets | order | bone parents | rest [3 * 64] | mean [3 * 64]
 static_assert(RHEAD % 4 == 0, "the staged frames start on a quad");
 
@@ -257,8 +298,8 @@ __device__ __forceinline__ Quat arc(float a0, float a1, float a2, float b0, floa
     return {0.f, x / d, y / d, z / d};
 }
 
-// grid: (tile of TF output frames) x row, flattened.  NATIVE: L / M = 1.  GLOBAL: the output holds G_k, else L_k.
-// a.table is the level table of eg_skeleton_levels; as in load_table its numbers index LDS and the output, so they are clamped.
+// NATIVE: L / M = 1.  GLOBAL: the output holds G_k, else L_k.
+// a.table is the level table of eg_skeleton_levels; as in load_head its numbers index LDS and the output, so they are clamped.
 template <bool NATIVE, bool GLOBAL>
 __global__ __launch_bounds__(THREADS) void skeleton_rotations_kernel(const Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -270,62 +311,39 @@ __global__ __launch_bounds__(THREADS) void skeleton_rotations_kernel(const Args 
     float* mn = rs + 3 * TAB;
     float* xin = lds + RHEAD;
     float* gt = xin + round4(SLOTS * D + 8);                                    // g[bone][component][frame of the tile]
-    const int b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
-    const long long k0 = (long long)tile * TF;
-    const int cnt = (int)(a.T_out - k0 < TF ? a.T_out - k0 : TF);
-    const int n = valid_frames(a, b);
-    const long long n_out = NATIVE ? n : out_frames(n, a.L, a.M);
-    const int live = (int)(n_out - k0 < 0 ? 0 : (n_out - k0 < cnt ? n_out - k0 : cnt));
-    float* out = a.dst + ((long long)b * a.T_out + k0) * Q;                      // 16-byte aligned: Q is a multiple of 4
-    for (int q = live * K + tid; q < cnt * K; q += THREADS) *reinterpret_cast<f4*>(out + 4ll * q) = f4{0.f, 0.f, 0.f, 0.f};
-    if (live == 0) return;
+    const Tile t = tile_of<NATIVE>(a, a.T_out);
+    float* out = a.dst + ((long long)t.b * a.T_out + t.k0) * Q;                  // 16-byte aligned: Q is a multiple of 4
+    for (int q = t.live * K + tid; q < t.cnt * K; q += THREADS) *reinterpret_cast<f4*>(out + 4ll * q) = f4{0.f, 0.f, 0.f, 0.f};
+    if (t.live == 0) return;
     const int nlev = min(max(a.table[0], 1), K);
-    for (int l = tid; l <= nlev; l += THREADS) lv[l] = min(max(a.table[1 + l], 0), K);
+    for (int l = tid; l <= nlev; l += THREADS) lv[l] = min(max(a.table[LV_FIRST + l], 0), K);
     for (int k = tid; k < K; k += THREADS) {
-        ord[k] = min(max(a.table[65 + k], 0), K - 1);
-        pbt[k] = min(max(a.table[65 + K + k], -1), K - 1);
+        ord[k] = min(max(a.table[LV_ORDER + k], 0), K - 1);
+        pbt[k] = min(max(a.table[lv_parents(K) + k], -1), K - 1);
     }
-    for (int r = tid; r < D; r += THREADS) rs[r] = __int_as_float(a.table[65 + 2 * K + r]);
+    for (int r = tid; r < D; r += THREADS) rs[r] = __int_as_float(a.table[lv_rest(K) + r]);
     const bool has_mean = a.mean != nullptr;
-    if (has_mean)
-        for (int r = tid; r < D; r += THREADS) mn[r] = a.mean[r];
-    const long long total = (long long)a.B * a.T * D;
-    const int L = a.L, M = a.M;
-    auto seg = [&](long long kk) -> long long {                                 // first source frame of output frame kk
-        if (NATIVE) return kk;
-        if (n < 2) return 0;
-        const long long lo = kk * M / L;
-        return lo < n - 2 ? lo : n - 2;
-    };
-    for (int i = 0; i < live;) {
-        // outputs [i, i1) of the tile from the source frames [s_base, s_base + nslots), as in skeleton_joints_kernel
-        const long long s_base = seg(k0 + i);
-        int i1 = live;
-        if (!NATIVE && M > L) {
-            const long long jmax = ((s_base + SLOTS - 1) * L - 1) / M - k0;
-            i1 = jmax + 1 < live ? (int)(jmax + 1) : live;
-            i1 = i1 > i ? i1 : i + 1;
-        }
-        const int nslots = (int)(seg(k0 + i1 - 1) - s_base) + ((NATIVE || n < 2) ? 1 : 2);
-        const long long g0 = ((long long)b * a.T + s_base) * D;
-        stage_span(a.src, g0, g0 + (long long)nslots * D, total, xin);
-        __syncthreads();                                                        // also: the tables, and the last level of the pass before
-        const float* x = xin + (int)(g0 & 3);
-        const int nf = i1 - i;
+    load_mean(a, mn);
+    // stage_pass' barrier also covers the tables, and the last level of the pass before
+    const Walk<NATIVE> w = {t.k0, t.n, a.L, a.M};
+    Pass ps;
+    for (int i = 0; i < t.live; i = ps.i1) {
+        const float* x = stage_pass(a, t, w, i, xin, ps);
+        const int nf = ps.i1 - i;
         for (int l = 0; l < nlev; ++l) {
             const int b0 = lv[l], nb = max(lv[l + 1] - b0, 0);
-            for (int w = tid; w < nf * nb; w += THREADS) {                       // one thread per (output frame, bone of the level)
-                const int j = w / nf, fr = i + (w - j * nf);
+            for (int q = tid; q < nf * nb; q += THREADS) {                       // one thread per (output frame, bone of the level)
+                const int j = q / nf, fr = i + (q - j * nf);
                 const int k = ord[min(b0 + j, K - 1)], p = pbt[k];
                 float x0, x1, x2;
-                if (NATIVE || n < 2) {
+                if (NATIVE || t.n < 2) {
                     const float* xs = x + (NATIVE ? fr - i : 0) * D + 3 * k;
                     x0 = xs[0]; x1 = xs[1]; x2 = xs[2];
                     if (has_mean) { x0 += mn[3 * k]; x1 += mn[3 * k + 1]; x2 += mn[3 * k + 2]; }
                 } else {                                                        // the vectors are blended, after the mean
-                    const long long kk = k0 + fr, lo = seg(kk);
-                    const float f = (float)(kk * M - lo * L) / (float)L;
-                    const float* xs = x + (int)(lo - s_base) * D + 3 * k;
+                    const Blend bl = w.blend(ps, fr);
+                    const float f = bl.f;
+                    const float* xs = x + bl.slot * D + 3 * k;
                     float y0 = xs[0], y1 = xs[1], y2 = xs[2], z0 = xs[D], z1 = xs[D + 1], z2 = xs[D + 2];
                     if (has_mean) {
                         y0 += mn[3 * k]; y1 += mn[3 * k + 1]; y2 += mn[3 * k + 2];
@@ -350,7 +368,6 @@ __global__ __launch_bounds__(THREADS) void skeleton_rotations_kernel(const Args 
             }
             __syncthreads();                                                    // a level reads what the level before wrote
         }
-        i = i1;
     }
 }
 
@@ -399,6 +416,27 @@ int common_checks(const char* who, const void* src, const void* dst, int B, int 
     return EG_OK;
 }
 
+// What eg_skeleton_joints and eg_skeleton_rotations check behind their own arguments, in the header's order -- the rate, out_stride, the grid
+// and the index range of an output of `per_frame` floats per frame -- and the rest of the kernel's arguments: a.L, a.M, a.tiles, a.T_out.
+int forward_args(const char* who, Args& a, int L, int M, long long out_stride, int per_frame) {
+    int rc = reduce_rate(who, L, M);
+    if (rc != EG_OK) return rc;
+    const long long t_out = out_frames(a.T, L, M);
+    EG_REQUIRE(out_stride >= t_out, EG_ERR_BAD_ARG, "%s: out_stride=%lld < %lld output frames of %d input frames at L=%d / M=%d", who, out_stride,
+               t_out, a.T, L, M);
+    const long long tiles = (out_stride + TF - 1) / TF;
+    EG_REQUIRE(tiles * a.B <= 0x7fffffffll && (long long)a.B * out_stride * per_frame < (1ll << 40), EG_ERR_UNSUPPORTED,
+               "%s: rows=%d x out_stride=%lld: grid / index range", who, a.B, out_stride);
+    a.L = L; a.M = M; a.tiles = (int)tiles; a.T_out = out_stride;
+    return EG_OK;
+}
+
+// One workgroup per tile of every row.
+int launch(void (*kernel)(Args), const Args& a, size_t lds_floats, void* stream, const char* what) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((long long)a.tiles * a.B)), dim3(THREADS), lds_floats * sizeof(float), static_cast<hipStream_t>(stream), a);
+    return eg_check_launch(what);
+}
+
 int check_rest(const char* who, const double* rest, int K) {
     EG_REQUIRE(rest, EG_ERR_BAD_ARG, "%s: null rest", who);
     for (int k = 0; k < K; ++k) {
@@ -431,28 +469,13 @@ extern "C" int eg_skeleton_joints(const float* track, int32_t rows, int32_t T, c
     const char* who = "eg_skeleton_joints";
     int rc = common_checks(who, track, joints, rows, T, parents, children, lengths, bones, d_table, draws, frame_unit, d_mean);
     if (rc != EG_OK) return rc;
-    int l = L, m = M;
-    rc = reduce_rate(who, l, m);
+    Args a = {track, static_cast<const int*>(d_table), d_frames, d_mean, joints, rows, T, bones, draws, frame_unit};
+    rc = forward_args(who, a, L, M, out_stride, 3 * (bones + 1));
     if (rc != EG_OK) return rc;
-    const long long t_out = out_frames(T, l, m);
-    EG_REQUIRE(out_stride >= t_out, EG_ERR_BAD_ARG, "%s: out_stride=%lld < %lld output frames of %d input frames at L=%d / M=%d", who,
-               (long long)out_stride, t_out, T, l, m);
-    const long long tiles = (out_stride + TF - 1) / TF;
-    EG_REQUIRE(tiles * rows <= 0x7fffffffll && (long long)rows * out_stride * 3 * (bones + 1) < (1ll << 40), EG_ERR_UNSUPPORTED,
-               "%s: rows=%d x out_stride=%lld: grid / index range", who, rows, (long long)out_stride);
-    Args a = {track, static_cast<const int*>(d_table), d_frames, d_mean, joints, rows, T, bones, draws, frame_unit, l, m, (int)tiles, out_stride};
-    const size_t lds = (size_t)(HEAD + round4(SLOTS * 3 * bones + 8) + (bones + 1) * NC) * sizeof(float);
-    const dim3 grid((unsigned)(tiles * rows)), block(THREADS);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool native = l == 1 && m == 1;
-    if (unit) {
-        if (native) hipLaunchKernelGGL((skeleton_joints_kernel<true, true>), grid, block, lds, st, a);
-        else hipLaunchKernelGGL((skeleton_joints_kernel<true, false>), grid, block, lds, st, a);
-    } else {
-        if (native) hipLaunchKernelGGL((skeleton_joints_kernel<false, true>), grid, block, lds, st, a);
-        else hipLaunchKernelGGL((skeleton_joints_kernel<false, false>), grid, block, lds, st, a);
-    }
-    return eg_check_launch("skeleton_joints");
+    const bool native = a.L == 1 && a.M == 1;
+    return launch(unit ? (native ? skeleton_joints_kernel<true, true> : skeleton_joints_kernel<true, false>)
+                       : (native ? skeleton_joints_kernel<false, true> : skeleton_joints_kernel<false, false>),
+                  a, HEAD + round4(SLOTS * 3 * bones + 8) + (bones + 1) * NC, stream, "skeleton_joints");
 }
 
 extern "C" int eg_skeleton_dir_vec(const float* joints, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children, const float* lengths,
@@ -465,9 +488,7 @@ extern "C" int eg_skeleton_dir_vec(const float* joints, int32_t rows, int32_t T,
     EG_REQUIRE(tiles * rows <= 0x7fffffffll && (long long)rows * T * 3 * (bones + 1) < (1ll << 40), EG_ERR_UNSUPPORTED,
                "%s: rows=%d x frames=%d: grid / index range", who, rows, T);
     Args a = {joints, static_cast<const int*>(d_table), d_frames, d_mean, dir_vec, rows, T, bones, draws, frame_unit, 1, 1, (int)tiles, T};
-    const size_t lds = (size_t)(HEAD + round4(TF * 3 * (bones + 1) + 8)) * sizeof(float);
-    hipLaunchKernelGGL(skeleton_dir_vec_kernel, dim3((unsigned)(tiles * rows)), dim3(THREADS), lds, static_cast<hipStream_t>(stream), a);
-    return eg_check_launch("skeleton_dir_vec");
+    return launch(skeleton_dir_vec_kernel, a, HEAD + round4(TF * 3 * (bones + 1) + 8), stream, "skeleton_dir_vec");
 }
 
 extern "C" int eg_skeleton_rest_check(const double* rest, int32_t bones) {
@@ -489,7 +510,7 @@ extern "C" int eg_skeleton_levels(const int32_t* parents, const int32_t* childre
     int owner[MAX_K + 1], depth[MAX_K], count[MAX_K + 1] = {};
     for (int j = 0; j <= K; ++j) owner[j] = -1;
     int nlev = 0;
-    int32_t* pb = words + 65 + K;
+    int32_t* pb = words + lv_parents(K);
     for (int k = 0; k < K; ++k) {                       // topological order: the parent joint's bone, if any, came earlier
         pb[k] = owner[parents[k]];
         depth[k] = pb[k] < 0 ? 0 : depth[pb[k]] + 1;
@@ -498,19 +519,19 @@ extern "C" int eg_skeleton_levels(const int32_t* parents, const int32_t* childre
         nlev = depth[k] + 1 > nlev ? depth[k] + 1 : nlev;
     }
     words[0] = nlev;
-    int at[MAX_K + 1];
-    for (int l = 0, s = 0; l < 64; ++l) {
-        words[1 + l] = s;
+    int at[LEVEL_SLOTS];
+    for (int l = 0, s = 0; l < LEVEL_SLOTS; ++l) {
+        words[LV_FIRST + l] = s;
         at[l] = s;
         if (l < nlev) s += count[l];
     }
-    for (int k = 0; k < K; ++k) words[65 + at[depth[k]]++] = k;                 // by depth, table order inside a level
+    for (int k = 0; k < K; ++k) words[LV_ORDER + at[depth[k]]++] = k;                 // by depth, table order inside a level
     for (int k = 0; k < K; ++k) {
         const double* r = rest + 3 * k;
         const double nrm = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
         for (int c = 0; c < 3; ++c) {
             const float v = (float)(r[c] / nrm);
-            words[65 + 2 * K + 3 * k + c] = *reinterpret_cast<const int32_t*>(&v);
+            words[lv_rest(K) + 3 * k + c] = *reinterpret_cast<const int32_t*>(&v);
         }
     }
     return EG_OK;
@@ -526,26 +547,11 @@ extern "C" int eg_skeleton_rotations(const float* track, int32_t rows, int32_t T
     rc = check_rest(who, rest, bones);
     if (rc != EG_OK) return rc;
     EG_REQUIRE(space == EG_SKELETON_SPACE_LOCAL || space == EG_SKELETON_SPACE_GLOBAL, EG_ERR_BAD_ARG, "%s: space=%d (0: local, 1: global)", who, space);
-    int l = L, m = M;
-    rc = reduce_rate(who, l, m);
+    Args a = {track, static_cast<const int*>(d_levels), d_frames, d_mean, rotations, rows, T, bones, draws, frame_unit};
+    rc = forward_args(who, a, L, M, out_stride, 4 * bones);
     if (rc != EG_OK) return rc;
-    const long long t_out = out_frames(T, l, m);
-    EG_REQUIRE(out_stride >= t_out, EG_ERR_BAD_ARG, "%s: out_stride=%lld < %lld output frames of %d input frames at L=%d / M=%d", who,
-               (long long)out_stride, t_out, T, l, m);
-    const long long tiles = (out_stride + TF - 1) / TF;
-    EG_REQUIRE(tiles * rows <= 0x7fffffffll && (long long)rows * out_stride * 4 * bones < (1ll << 40), EG_ERR_UNSUPPORTED,
-               "%s: rows=%d x out_stride=%lld: grid / index range", who, rows, (long long)out_stride);
-    Args a = {track, static_cast<const int*>(d_levels), d_frames, d_mean, rotations, rows, T, bones, draws, frame_unit, l, m, (int)tiles, out_stride};
-    const size_t lds = (size_t)(RHEAD + round4(SLOTS * 3 * bones + 8) + bones * 4 * TF) * sizeof(float);
-    const dim3 grid((unsigned)(tiles * rows)), block(THREADS);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool native = l == 1 && m == 1;
-    if (space == EG_SKELETON_SPACE_GLOBAL) {
-        if (native) hipLaunchKernelGGL((skeleton_rotations_kernel<true, true>), grid, block, lds, st, a);
-        else hipLaunchKernelGGL((skeleton_rotations_kernel<false, true>), grid, block, lds, st, a);
-    } else {
-        if (native) hipLaunchKernelGGL((skeleton_rotations_kernel<true, false>), grid, block, lds, st, a);
-        else hipLaunchKernelGGL((skeleton_rotations_kernel<false, false>), grid, block, lds, st, a);
-    }
-    return eg_check_launch("skeleton_rotations");
+    const bool native = a.L == 1 && a.M == 1;
+    return launch(space == EG_SKELETON_SPACE_GLOBAL ? (native ? skeleton_rotations_kernel<true, true> : skeleton_rotations_kernel<false, true>)
+                                                    : (native ? skeleton_rotations_kernel<true, false> : skeleton_rotations_kernel<false, false>),
+                  a, RHEAD + round4(SLOTS * 3 * bones + 8) + bones * 4 * TF, stream, "skeleton_rotations");
 }

@@ -513,23 +513,9 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     ``skeleton.rotations_from_tracks(out["track"], skeleton, rest, frames, joints_mean, joints_fps, rotations_space)``, one more launch, on the
     frames ``"joint_frames"`` counts."""
     gen, vae = models
-    if rotations is not None and joints is None:
-        raise L.EgError("synthesize: rotations= without joints=skeleton (the rest pose belongs to a skeleton's bones)")
-    if rotations is None and rotations_space != "local":
-        raise L.EgError("synthesize: rotations_space without rotations=rest")
-    if joints is not None:
-        from . import skeleton as SK
-        if not isinstance(joints, SK.Skeleton):
-            raise L.EgError(f"synthesize: joints= takes a skeleton.Skeleton, got {type(joints).__name__}")
-        if joints.pose_dim != seed_pose.shape[-1]:
-            raise L.EgError(f"synthesize: joints=: the skeleton has K={joints.K} bones, 3K={joints.pose_dim} != pose_dim={seed_pose.shape[-1]} "
-                            "(the BEAT generators' 282 columns hold rotations, not bone direction vectors)")
-        SK.rate_ratio(joints_fps, "synthesize: joints_fps")                        # refuses an unsupported ratio before anything runs
-        if rotations is not None:                                                  # and a bad rest pose or space
-            SK._space(rotations_space, "synthesize: rotations_space")
-            rotations = joints.rest_pose(rotations)
-    elif joints_mean is not None or joints_unit or joints_fps is not None:
-        raise L.EgError("synthesize: joints_mean / joints_unit / joints_fps without joints=skeleton")
+    from . import skeleton as SK
+    rotations = SK.output_args("synthesize", seed_pose.shape[-1], joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space,
+                               hint=" (the BEAT generators' 282 columns hold rotations, not bone direction vectors)")
     _eval_only(gen)
     if beat and seed_pose.shape[-1] < 174:
         raise L.EgError(f"synthesize: beat=True: pose_dim={seed_pose.shape[-1]}: the beat joints are columns 18:42 and 150:174 (needs >= 174)")
@@ -584,13 +570,11 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
             td = take_diversity(diversity, out["track"], span=c.frames)
         out["take_distance"], out["take_diversity"] = td["distance"], td["diversity"]
     if joints is not None:
-        H = c.frames - c.prior_frames
+        kw = dict(frames=[int(w) * (c.frames - c.prior_frames) + c.prior_frames for w in wp], mean=joints_mean, fps=joints_fps)
         with torch.no_grad():
-            out["joints"], out["joint_frames"] = SK.joints_from_tracks(out["track"], joints, frames=[int(w) * H + c.prior_frames for w in wp],
-                                                                       mean=joints_mean, unit=joints_unit, fps=joints_fps)
+            out["joints"], out["joint_frames"] = SK.joints_from_tracks(out["track"], joints, unit=joints_unit, **kw)
             if rotations is not None:
-                out["rotations"], _n = SK.rotations_from_tracks(out["track"], joints, rotations, frames=[int(w) * H + c.prior_frames for w in wp],
-                                                                mean=joints_mean, fps=joints_fps, space=rotations_space)
+                out["rotations"], _n = SK.rotations_from_tracks(out["track"], joints, rotations, space=rotations_space, **kw)
     return out
 
 

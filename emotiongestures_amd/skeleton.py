@@ -32,6 +32,7 @@ a GPU.
 from __future__ import annotations
 
 import math
+from types import SimpleNamespace
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -46,6 +47,11 @@ __all__ = ["Skeleton", "RestPose", "ted_expressive", "joints_from_tracks", "dir_
 TILE_FRAMES = L.EG_SKELETON_TILE_FRAMES      # output frames of one workgroup
 MAX_BONES = L.EG_SKELETON_MAX_BONES
 MAX_FACTOR = L.EG_SKELETON_MAX_FACTOR
+
+
+def level_words(K: int) -> int:
+    """EG_SKELETON_LEVEL_WORDS(K): the level count | 64 level offsets | order [K] | bone parents [K] | rest [K, 3]."""
+    return 1 + 64 + 5 * K
 
 
 class Skeleton:
@@ -128,12 +134,12 @@ class RestPose:
         self.sk, self.raw = sk, raw
         L.check(L.load().eg_skeleton_rest_check(host_ptr(raw), sk.K), "eg_skeleton_rest_check")
         self.unit32 = (raw / np.sqrt(raw[:, 0] * raw[:, 0] + raw[:, 1] * raw[:, 1] + raw[:, 2] * raw[:, 2])[:, None]).astype(np.float32)
-        self.words = np.zeros(65 + 5 * sk.K, np.int32)
+        self.words = np.zeros(level_words(sk.K), np.int32)
         L.check(L.load().eg_skeleton_levels(*sk.host_ptrs(), sk.K, host_ptr(raw), host_ptr(self.words)), "eg_skeleton_levels")
         self._tables = BoundedCache()
 
     def table(self, device) -> torch.Tensor:
-        """int32 ``[65 + 5K]`` on ``device``."""
+        """int32 ``[level_words(K)]`` on ``device``."""
         return self._tables.get(str(device), lambda: torch.from_numpy(self.words).to(device))
 
     def __repr__(self):
@@ -240,22 +246,18 @@ def _dev32(x: torch.Tensor) -> torch.Tensor:
     return x.clone() if x.data_ptr() % 16 else x                # a slice of a larger tensor may start anywhere
 
 
-def _mean_dev(mean, K: int, device, who: str) -> Optional[torch.Tensor]:
-    if mean is None:
-        return None
-    m = torch.as_tensor(mean).detach().to(device=device, dtype=torch.float32).reshape(-1).contiguous()
-    if m.numel() != 3 * K:
-        raise L.EgError(f"{who}: mean has {m.numel()} values, the skeleton's tracks have {3 * K}")
+def _mean_checked(m, K: int, who: str):                        # m: the flat mean, a tensor or an array
+    if len(m) != 3 * K:
+        raise L.EgError(f"{who}: mean has {len(m)} values, the skeleton's tracks have {3 * K}")
     return m
+
+
+def _mean_dev(mean, K: int, device, who: str) -> Optional[torch.Tensor]:
+    return None if mean is None else _mean_checked(torch.as_tensor(mean).detach().to(device=device, dtype=torch.float32).reshape(-1).contiguous(), K, who)
 
 
 def _mean_host(mean, K: int, who: str) -> Optional[np.ndarray]:
-    if mean is None:
-        return None
-    m = _host64(mean, who).reshape(-1)
-    if m.size != 3 * K:
-        raise L.EgError(f"{who}: mean has {m.size} values, the skeleton's tracks have {3 * K}")
-    return m
+    return None if mean is None else _mean_checked(_host64(mean, who).reshape(-1), K, who)
 
 
 # ---- the float64 path: the definition ------------------------------------------------------------------------------------------------------
@@ -265,6 +267,17 @@ def _chain64(sk: Skeleton, x: np.ndarray) -> np.ndarray:
     for k in range(sk.K):
         p[..., sk.children[k], :] = p[..., sk.parents[k], :] + sk.lengths[k] * x[..., k, :]
     return p
+
+
+def _resample64(y: np.ndarray, n_out: int, Lf: int, M: int) -> np.ndarray:
+    """y [n, ., 3] at the source rate -> [n_out, ., 3]: frame k' blends the source frames lo and lo + 1 with the weight f (n = 1: frame 0)."""
+    n = len(y)
+    if Lf == M or n == 1:
+        return y if Lf == M else np.repeat(y, n_out, 0)
+    k = np.arange(n_out, dtype=np.int64)
+    lo = np.minimum(k * M // Lf, n - 2)
+    f = ((k * M - lo * Lf) / Lf)[:, None, None]
+    return y[lo] + (y[lo + 1] - y[lo]) * f
 
 
 def _joints64(v: np.ndarray, sk: Skeleton, frames: List[int], mean, unit: bool, Lf: int, M: int) -> np.ndarray:
@@ -280,17 +293,8 @@ def _joints64(v: np.ndarray, sk: Skeleton, frames: List[int], mean, unit: bool, 
             x = x + mean.reshape(sk.K, 3)
         if unit:
             x = x / np.maximum(np.sqrt((x * x).sum(-1, keepdims=True)), 1e-12)
-        p = _chain64(sk, x)
         n_out = -(-n * Lf // M)
-        if Lf == M:
-            out[b, :n] = p
-        elif n == 1:
-            out[b, :n_out] = p[0]
-        else:
-            k = np.arange(n_out, dtype=np.int64)
-            lo = np.minimum(k * M // Lf, n - 2)
-            f = ((k * M - lo * Lf) / Lf)[:, None, None]
-            out[b, :n_out] = p[lo] + (p[lo + 1] - p[lo]) * f
+        out[b, :n_out] = _resample64(_chain64(sk, x), n_out, Lf, M)
     return out
 
 
@@ -355,15 +359,7 @@ def _rotations64(v: np.ndarray, sk: Skeleton, rest: np.ndarray, frames: List[int
         if mean is not None:
             x = x + mean.reshape(sk.K, 3)
         n_out = -(-n * Lf // M)
-        if Lf == M:
-            pass
-        elif n == 1:
-            x = np.repeat(x[:1], n_out, 0)
-        else:                                                   # the vectors are blended, then the chain runs on the blended frame
-            k = np.arange(n_out, dtype=np.int64)
-            lo = np.minimum(k * M // Lf, n - 2)
-            f = ((k * M - lo * Lf) / Lf)[:, None, None]
-            x = (x[lo + 1] - x[lo]) * f + x[lo]
+        x = _resample64(x, n_out, Lf, M)                        # the vectors are blended, then the chain runs on the blended frame
         x = x / np.maximum(np.sqrt((x * x).sum(-1, keepdims=True)), 1e-12)
         G = np.zeros((n_out, sk.K, 4))
         loc = np.zeros((n_out, sk.K, 4))
@@ -379,19 +375,24 @@ def _rotations64(v: np.ndarray, sk: Skeleton, rest: np.ndarray, frames: List[int
 
 
 # ---- the device path ---------------------------------------------------------------------------------------------------------------------
+def _forward_out(track: torch.Tensor, sk: Skeleton, ratio: Tuple[int, int], out: Optional[torch.Tensor], tail: Tuple[int, int]):
+    """What launch_joints and launch_rotations do before the call: ``(B, T, L, M, out)``, ``out [B, T_out, *tail]`` made here unless given."""
+    B, T, D = track.shape
+    if D != sk.pose_dim:
+        raise L.EgError(f"skeleton of {sk.K} bones takes tracks of {sk.pose_dim} columns, got {D}")
+    Lf, M = ratio
+    if out is None:
+        out = torch.empty((B, -(-T * Lf // M)) + tail, dtype=torch.float32, device=track.device)
+    return B, T, Lf, M, out
+
+
 def launch_joints(track: torch.Tensor, sk: Skeleton, d_frames: Optional[torch.Tensor] = None, draws: int = 1, frame_unit: int = 1,
                   mean: Optional[torch.Tensor] = None, unit: bool = False, ratio: Tuple[int, int] = (1, 1),
                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """eg_skeleton_joints on ``track [B, T, 3K]`` (contiguous fp32 CUDA, 16-byte aligned) -> ``[B, T_out, J, 3]``: one launch on the current
     stream, nothing else -- static inputs and ``out`` make it capturable.  ``d_frames``: device int32 ``[B / draws]``, row b has
     ``d_frames[b // draws] * frame_unit`` valid frames."""
-    B, T, D = track.shape
-    if D != sk.pose_dim:
-        raise L.EgError(f"skeleton of {sk.K} bones takes tracks of {sk.pose_dim} columns, got {D}")
-    Lf, M = ratio
-    t_out = -(-T * Lf // M)
-    if out is None:
-        out = torch.empty(B, t_out, sk.J, 3, dtype=torch.float32, device=track.device)
+    B, T, Lf, M, out = _forward_out(track, sk, ratio, out, (sk.J, 3))
     L.check(L.load().eg_skeleton_joints(_ptr(track), B, T, *sk.host_ptrs(), sk.K, _ptr(sk.table(track.device)), _ptr(d_frames), int(draws),
                                         int(frame_unit), _ptr(mean), int(bool(unit)), Lf, M, _ptr(out), out.shape[1], _stream(track.device)),
             "eg_skeleton_joints")
@@ -421,13 +422,7 @@ def launch_rotations(track: torch.Tensor, sk: Skeleton, rest: RestPose, d_frames
     """eg_skeleton_rotations on ``track [B, T, 3K]`` (contiguous fp32 CUDA, 16-byte aligned) -> ``[B, T_out, K, 4]``: one launch on the current
     stream, nothing else (the level table is uploaded on first use per device: warm up before a capture).  ``rest``: ``sk.rest_pose(...)``;
     the other arguments as in ``launch_joints``."""
-    B, T, D = track.shape
-    if D != sk.pose_dim:
-        raise L.EgError(f"skeleton of {sk.K} bones takes tracks of {sk.pose_dim} columns, got {D}")
-    Lf, M = ratio
-    t_out = -(-T * Lf // M)
-    if out is None:
-        out = torch.empty(B, t_out, sk.K, 4, dtype=torch.float32, device=track.device)
+    B, T, Lf, M, out = _forward_out(track, sk, ratio, out, (sk.K, 4))
     L.check(L.load().eg_skeleton_rotations(_ptr(track), B, T, *sk.host_ptrs(), sk.K, host_ptr(rest.raw), _ptr(rest.table(track.device)),
                                            _ptr(d_frames), int(draws), int(frame_unit), _ptr(mean), _space(space, "launch_rotations"), Lf, M,
                                            _ptr(out), out.shape[1], _stream(track.device)), "eg_skeleton_rotations")
@@ -435,6 +430,42 @@ def launch_rotations(track: torch.Tensor, sk: Skeleton, rest: RestPose, d_frames
 
 
 # ---- the public functions --------------------------------------------------------------------------------------------------------------------
+def _per_row(fr: Optional[List[int]], U: int, R: int, T: int) -> List[int]:
+    return [n for n in (fr if fr is not None else [T] * U) for _ in range(R)]
+
+
+def _shape_checked(track, sk, who: str) -> Skeleton:
+    """The first half of the front end of both forward functions: the skeleton's type and the track's shape; returns the skeleton."""
+    if not isinstance(sk, Skeleton):
+        raise L.EgError(f"{who}: skeleton must be a Skeleton, got {type(sk).__name__}")
+    shape = tuple(track.shape)
+    if len(shape) < 2 or shape[-2] < 1:
+        raise L.EgError(f"{who}: track shape {shape}: need [..., T >= 1, {sk.pose_dim}]")
+    if shape[-1] != sk.pose_dim:
+        raise L.EgError(f"{who}: track shape {shape}: a skeleton of K={sk.K} bones takes 3K={sk.pose_dim} columns per frame, not {shape[-1]}")
+    return sk
+
+
+def _front(track, sk: Skeleton, frames, fps, who: str) -> SimpleNamespace:
+    """The second half, behind a caller's own checks: the leading axes ``lead`` of the track (``()``, ``(U,)`` or ``(U, R)``), ``U``, ``R``,
+    ``T``, the reduced ``ratio = (L, M)``, ``fr`` (``frames`` as a checked list, or None), ``t_out``, the valid source frames
+    ``per_row [U * R]`` and the valid output frames ``n_out [U]``."""
+    lead, U, R = _lead(track.shape, 2, who)
+    T = track.shape[-2]
+    Lf, M = rate_ratio(fps, f"{who}: fps")
+    fr = _frames_list(frames, U, T, who)
+    return SimpleNamespace(lead=lead, U=U, R=R, T=T, ratio=(Lf, M), fr=fr, t_out=-(-T * Lf // M), per_row=_per_row(fr, U, R, T),
+                           n_out=[-(-n * Lf // M) for n in (fr if fr is not None else [T] * U)])
+
+
+def _finish(res, track, fe, tail: Tuple[int, int], frames, fps):
+    """``res [U * R, T_out, *tail]`` under the leading axes of ``track``; tensor in: tensor out; with ``frames`` or ``fps``: ``(res, n_out)``."""
+    res = res.reshape(fe.lead + (fe.t_out,) + tail)
+    if isinstance(track, torch.Tensor) and not isinstance(res, torch.Tensor):
+        res = torch.from_numpy(res)
+    return res if frames is None and fps is None else (res, fe.n_out)
+
+
 def joints_from_tracks(track, skeleton: Skeleton, frames=None, mean=None, unit: bool = False, fps=None):
     """``track [..., T, 3K]`` with up to two leading axes (``[T, D]``, ``[U, T, D]``, ``[U, R, T, D]``) -> ``joints [..., T_out, J, 3]``,
     ``T_out = ceil(T * L / M)``.
@@ -448,31 +479,15 @@ def joints_from_tracks(track, skeleton: Skeleton, frames=None, mean=None, unit: 
     float64 tensor out).  With ``frames`` or ``fps`` the result is ``(joints, joint_frames)``, ``joint_frames`` the valid output frames per
     recording (a list of U ints)."""
     who = "joints_from_tracks"
-    if not isinstance(skeleton, Skeleton):
-        raise L.EgError(f"{who}: skeleton must be a Skeleton, got {type(skeleton).__name__}")
-    sk = skeleton
-    shape = tuple(track.shape)
-    if len(shape) < 2 or shape[-2] < 1:
-        raise L.EgError(f"{who}: track shape {shape}: need [..., T >= 1, {sk.pose_dim}]")
-    if shape[-1] != sk.pose_dim:
-        raise L.EgError(f"{who}: track shape {shape}: a skeleton of K={sk.K} bones takes 3K={sk.pose_dim} columns per frame, not {shape[-1]}")
-    lead, U, R = _lead(shape, 2, who)
-    T = shape[-2]
-    Lf, M = rate_ratio(fps, f"{who}: fps")
-    fr = _frames_list(frames, U, T, who)
-    t_out = -(-T * Lf // M)
+    sk = _shape_checked(track, skeleton, who)
+    fe = _front(track, sk, frames, fps, who)
     if _is_cuda(track):
-        x = _dev32(track).reshape(U * R, T, sk.pose_dim)
-        j = launch_joints(x, sk, _frames_dev(fr, x.device), R, 1, _mean_dev(mean, sk.K, x.device, who), unit, (Lf, M))
-        joints = j.reshape(lead + (t_out, sk.J, 3))
+        x = _dev32(track).reshape(fe.U * fe.R, fe.T, sk.pose_dim)
+        j = launch_joints(x, sk, _frames_dev(fe.fr, x.device), fe.R, 1, _mean_dev(mean, sk.K, x.device, who), unit, fe.ratio)
     else:
-        v = _host64(track, who).reshape(U * R, T, sk.pose_dim)
-        per_row = [n for n in (fr if fr is not None else [T] * U) for _ in range(R)]
-        j = _joints64(v, sk, per_row, _mean_host(mean, sk.K, who), bool(unit), Lf, M).reshape(lead + (t_out, sk.J, 3))
-        joints = torch.from_numpy(j) if isinstance(track, torch.Tensor) else j
-    if frames is None and fps is None:
-        return joints
-    return joints, [-(-n * Lf // M) for n in (fr if fr is not None else [T] * U)]
+        v = _host64(track, who).reshape(fe.U * fe.R, fe.T, sk.pose_dim)
+        j = _joints64(v, sk, fe.per_row, _mean_host(mean, sk.K, who), bool(unit), *fe.ratio)
+    return _finish(j, track, fe, (sk.J, 3), frames, fps)
 
 
 def dir_vec_from_joints(joints, skeleton: Skeleton, frames=None, mean=None):
@@ -494,8 +509,7 @@ def dir_vec_from_joints(joints, skeleton: Skeleton, frames=None, mean=None):
         p = _dev32(joints).reshape(U * R, T, sk.J, 3)
         return launch_dir_vec(p, sk, _frames_dev(fr, p.device), R, 1, _mean_dev(mean, sk.K, p.device, who)).reshape(lead + (T, sk.pose_dim))
     p = _host64(joints, who).reshape(U * R, T, sk.J, 3)
-    per_row = [n for n in (fr if fr is not None else [T] * U) for _ in range(R)]
-    d = _dir_vec64(p, sk, per_row, _mean_host(mean, sk.K, who)).reshape(lead + (T, sk.pose_dim))
+    d = _dir_vec64(p, sk, _per_row(fr, U, R, T), _mean_host(mean, sk.K, who)).reshape(lead + (T, sk.pose_dim))
     return torch.from_numpy(d) if isinstance(joints, torch.Tensor) else d
 
 
@@ -512,31 +526,45 @@ def rotations_from_tracks(track, skeleton: Skeleton, rest, frames=None, mean=Non
     A CUDA tensor: one kernel launch, fp32 CUDA result.  numpy or a CPU tensor: the definition in float64.  With ``frames`` or ``fps`` the
     result is ``(rotations, rotation_frames)`` under the rule of ``joints_from_tracks``."""
     who = "rotations_from_tracks"
-    if not isinstance(skeleton, Skeleton):
-        raise L.EgError(f"{who}: skeleton must be a Skeleton, got {type(skeleton).__name__}")
-    sk = skeleton
-    shape = tuple(track.shape)
-    if len(shape) < 2 or shape[-2] < 1:
-        raise L.EgError(f"{who}: track shape {shape}: need [..., T >= 1, {sk.pose_dim}]")
-    if shape[-1] != sk.pose_dim:
-        raise L.EgError(f"{who}: track shape {shape}: a skeleton of K={sk.K} bones takes 3K={sk.pose_dim} columns per frame, not {shape[-1]}")
-    sp = _space(space, who)
-    pose = sk.rest_pose(rest)
-    lead, U, R = _lead(shape, 2, who)
-    T = shape[-2]
-    Lf, M = rate_ratio(fps, f"{who}: fps")
-    fr = _frames_list(frames, U, T, who)
-    t_out = -(-T * Lf // M)
+    sk = _shape_checked(track, skeleton, who)
+    sp, pose = _space(space, who), sk.rest_pose(rest)
+    fe = _front(track, sk, frames, fps, who)
     if _is_cuda(track):
-        x = _dev32(track).reshape(U * R, T, sk.pose_dim)
-        q = launch_rotations(x, sk, pose, _frames_dev(fr, x.device), R, 1, _mean_dev(mean, sk.K, x.device, who), space, (Lf, M))
-        rot = q.reshape(lead + (t_out, sk.K, 4))
+        x = _dev32(track).reshape(fe.U * fe.R, fe.T, sk.pose_dim)
+        q = launch_rotations(x, sk, pose, _frames_dev(fe.fr, x.device), fe.R, 1, _mean_dev(mean, sk.K, x.device, who), space, fe.ratio)
     else:
-        v = _host64(track, who).reshape(U * R, T, sk.pose_dim)
-        per_row = [n for n in (fr if fr is not None else [T] * U) for _ in range(R)]
-        q = _rotations64(v, sk, pose.unit32.astype(np.float64), per_row, _mean_host(mean, sk.K, who), sp == L.EG_SKELETON_SPACE_GLOBAL, Lf, M)
-        q = q.reshape(lead + (t_out, sk.K, 4))
-        rot = torch.from_numpy(q) if isinstance(track, torch.Tensor) else q
-    if frames is None and fps is None:
-        return rot
-    return rot, [-(-n * Lf // M) for n in (fr if fr is not None else [T] * U)]
+        v = _host64(track, who).reshape(fe.U * fe.R, fe.T, sk.pose_dim)
+        q = _rotations64(v, sk, pose.unit32.astype(np.float64), fe.per_row, _mean_host(mean, sk.K, who), sp == L.EG_SKELETON_SPACE_GLOBAL, *fe.ratio)
+    return _finish(q, track, fe, (sk.K, 4), frames, fps)
+
+
+def _output_args_early(who: str, joints, joints_fps, rotations, fps_allowed: bool = True) -> None:
+    """The part of ``output_args`` that needs no model: what a caller refuses before it looks at anything else."""
+    if not fps_allowed and joints_fps is not None:
+        raise L.EgError(f"{who}: joints_fps= is not supported (a frame-rate change needs the frame after the last one emitted, which a "
+                        "stream does not have yet); resample the joints of the finished track with skeleton.joints_from_tracks(..., fps=)")
+    if rotations is not None and joints is None:
+        raise L.EgError(f"{who}: rotations= without joints=skeleton (the rest pose belongs to a skeleton's bones)")
+
+
+def output_args(who: str, pose_dim: int, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, fps_allowed: bool = True,
+                hint: str = "") -> Optional[RestPose]:
+    """The skeleton-output arguments of a caller (``synthesize``, ``GestureStream``: ``who``, the prefix of every message), checked before
+    anything runs; returns the rest pose of ``rotations=`` on ``joints``' skeleton, or None.  ``pose_dim``: the model's; ``fps_allowed``: the
+    caller can change the frame rate; ``hint`` ends the message about a skeleton that does not fit ``pose_dim``."""
+    _output_args_early(who, joints, joints_fps, rotations, fps_allowed)
+    if rotations is None and rotations_space != "local":
+        raise L.EgError(f"{who}: rotations_space without rotations=rest")
+    if joints is None:
+        if joints_mean is not None or joints_unit or joints_fps is not None:
+            raise L.EgError(f"{who}: joints_mean / joints_unit{' / joints_fps' if fps_allowed else ''} without joints=skeleton")
+        return None
+    if not isinstance(joints, Skeleton):
+        raise L.EgError(f"{who}: joints= takes a skeleton.Skeleton, got {type(joints).__name__}")
+    if joints.pose_dim != pose_dim:
+        raise L.EgError(f"{who}: joints=: the skeleton has K={joints.K} bones, 3K={joints.pose_dim} != pose_dim={pose_dim}{hint}")
+    rate_ratio(joints_fps, f"{who}: joints_fps")                                   # refuses an unsupported ratio
+    if rotations is None:
+        return None
+    _space(rotations_space, f"{who}: rotations_space")                             # and a bad space or rest pose
+    return joints.rest_pose(rotations)

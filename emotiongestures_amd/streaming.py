@@ -22,6 +22,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib as L
+from . import skeleton as SK
 from ._host import int_list, need_cuda as _need_cuda
 from .modules import _eval_only
 from .pipeline import CAPTURE_MODE
@@ -159,11 +160,7 @@ class GestureStream:
                  fps: int = 15, sample_rate: int = 16000, alpha: Optional[torch.Tensor] = None, graph: bool = True, want_windows: bool = False,
                  draws: Optional[int] = None, audio_rate: Optional[int] = None, joints=None, joints_mean=None, joints_unit: bool = False,
                  joints_fps=None, rotations=None, rotations_space: str = "local"):
-        if joints_fps is not None:
-            raise L.EgError("GestureStream: joints_fps= is not supported (a frame-rate change needs the frame after the last one emitted, which a "
-                            "stream does not have yet); resample the joints of the finished track with skeleton.joints_from_tracks(..., fps=)")
-        if rotations is not None and joints is None:
-            raise L.EgError("GestureStream: rotations= without joints=skeleton (the rest pose belongs to a skeleton's bones)")
+        SK._output_args_early("GestureStream", joints, joints_fps, rotations, fps_allowed=False)
         if draws is not None:
             raise L.EgError("GestureStream: draws= is not supported (a stream has one track per row); for several sampled tracks of a whole "
                             "recording call the rectangular synthesize(..., draws=R), or open the stream with each speaker's row repeated")
@@ -179,20 +176,9 @@ class GestureStream:
         self.text_len, self.n_mels, self.spec_len = c["text_len"], c["n_mels"], c["spec_len"]
         self.U = int(rows)
         self._sk, self._sk_mean, self._sk_unit = joints, None, bool(joints_unit)
-        if joints is not None:
-            from . import skeleton as SK
-            if not isinstance(joints, SK.Skeleton):
-                raise L.EgError(f"GestureStream: joints= takes a skeleton.Skeleton, got {type(joints).__name__}")
-            if joints.pose_dim != self.D:
-                raise L.EgError(f"GestureStream: joints=: the skeleton has K={joints.K} bones, 3K={joints.pose_dim} != pose_dim={self.D}")
-        elif joints_mean is not None or joints_unit:
-            raise L.EgError("GestureStream: joints_mean / joints_unit without joints=skeleton")
-        self._rest, self._rot_space = None, rotations_space
-        if rotations is not None:
-            SK._space(rotations_space, "GestureStream: rotations_space")
-            self._rest = joints.rest_pose(rotations)          # held here: the captured graph replays the address of its device table
-        elif rotations_space != "local":
-            raise L.EgError("GestureStream: rotations_space without rotations=rest")
+        # the rest pose is held here: the captured graph replays the address of its device table
+        self._rest, self._rot_space = SK.output_args("GestureStream", self.D, joints, joints_mean, joints_unit, joints_fps, rotations,
+                                                     rotations_space, fps_allowed=False), rotations_space
         if self.mel is not None:
             self.hop = int(round(self.H * sample_rate / fps)) if hop_samples is None else int(hop_samples)
             self.n = (self.spec_len - 1) * 512 if n_samples is None else int(n_samples)
@@ -219,9 +205,8 @@ class GestureStream:
         self.seed_pose = _need_cuda(seed_pose, "seed_pose").clone()
         self.alpha = None if alpha is None else _need_cuda(alpha, "alpha").clone()
         self.device = self.seed_pose.device
-        if self._sk is not None and joints_mean is not None:
-            from .skeleton import _mean_dev
-            self._sk_mean = _mean_dev(joints_mean, self._sk.K, self.device, "GestureStream: joints_mean")
+        if self._sk is not None:
+            self._sk_mean = SK._mean_dev(joints_mean, self._sk.K, self.device, "GestureStream: joints_mean")
         if self.mel is AUTO_MEL:
             from .engine import MelFrontEnd
             self.mel = MelFrontEnd(self.device)
@@ -305,11 +290,9 @@ class GestureStream:
             out = eng.stream_step(self._state, *self._geom, spec, g["text"], sampled, self.alpha, want_window=self.want_windows,
                                   workspace=self._ws)
             if self._sk is not None:                # one more launch after the hand-off: row u has valid[u] * H frames
-                from .skeleton import launch_joints
-                out["joints"] = launch_joints(out["rows"], self._sk, out["valid"], 1, self.H, self._sk_mean, self._sk_unit)
+                out["joints"] = SK.launch_joints(out["rows"], self._sk, out["valid"], 1, self.H, self._sk_mean, self._sk_unit)
             if self._rest is not None:
-                from .skeleton import launch_rotations
-                out["rotations"] = launch_rotations(out["rows"], self._sk, self._rest, out["valid"], 1, self.H, self._sk_mean, self._rot_space)
+                out["rotations"] = SK.launch_rotations(out["rows"], self._sk, self._rest, out["valid"], 1, self.H, self._sk_mean, self._rot_space)
             return out
 
     def _push_only(self):
@@ -494,17 +477,15 @@ class GestureStream:
         """[U, P, J, 3]: the joints of `tail()` (a session opened with joints=)."""
         if self._sk is None:
             raise L.EgError("tail_joints: the session was opened without joints=skeleton")
-        from .skeleton import launch_joints
         with torch.no_grad():
-            return launch_joints(self.tail(), self._sk, None, 1, 1, self._sk_mean, self._sk_unit)
+            return SK.launch_joints(self.tail(), self._sk, None, 1, 1, self._sk_mean, self._sk_unit)
 
     def tail_rotations(self) -> torch.Tensor:
         """[U, P, K, 4]: the bone rotations of `tail()` (a session opened with rotations=)."""
         if self._rest is None:
             raise L.EgError("tail_rotations: the session was opened without rotations=rest")
-        from .skeleton import launch_rotations
         with torch.no_grad():
-            return launch_rotations(self.tail(), self._sk, self._rest, None, 1, 1, self._sk_mean, self._rot_space)
+            return SK.launch_rotations(self.tail(), self._sk, self._rest, None, 1, 1, self._sk_mean, self._rot_space)
 
     def finish(self, text, labels=None, z=None, sampled=None, last_chunk=None, ends=None) -> torch.Tensor:
         """End every row together and run R = text.shape[1] steps in all: `text [U, R, text_len]`, `labels [U, 8]` or `[U, R, 8]`, `z [U, R, 32]`

@@ -10,43 +10,14 @@ import numpy as np
 import pytest
 import torch
 
-import rollout_np as RO
 import rotations_np as RN
 import skeleton_np as SN
-from conftest import build_mirror
 from emotiongestures_amd import harness as Hs
 from emotiongestures_amd import skeleton as SK
-from emotiongestures_amd.synth import load_synth_weights, synth_audio
+from emotiongestures_amd.synth import synth_audio
+from skeleton_gpu_common import FPS, H_, HOP, LENGTHS, N, NAMES, P_, RAGGED, RATES, TF, dev, inputs, mean_of, skeleton, table_of, ted_models
 
 pytestmark = pytest.mark.gpu
-
-TF = SK.TILE_FRAMES
-RATES = [(1, 1), (2, 1), (5, 3), (2, 3)]                 # L / M
-FPS = {(1, 1): None, (2, 1): (15, 30), (5, 3): (15, 25), (2, 3): (15, 10)}
-LENGTHS = [1, 2, TF - 1, TF, TF + 1, 2 * TF + 3]
-RAGGED = [1, TF + 1, 2 * TF + 3]
-NAMES = ["ted", "chain", "star", "random63"]
-_SK = {}
-
-
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def skeleton(name):
-    if name not in _SK:
-        _SK[name] = {"ted": SK.ted_expressive, "chain": lambda: SK.Skeleton(*SN.chain_table()), "star": lambda: SK.Skeleton(*SN.star_table()),
-                     "random63": lambda: SK.Skeleton(*SN.random_table())}[name]()
-    return _SK[name]
-
-
-def table_of(sk):
-    return sk.parents.tolist(), sk.children.tolist(), sk.lengths.tolist()
-
-
-def mean_of(K, seed):
-    return (np.random.default_rng(seed).standard_normal(3 * K) * 0.2).astype(np.float32)
 
 
 def up_to_sign(a, b):
@@ -234,25 +205,6 @@ def test_graph_replay_equals_the_eager_call():
 
 
 # ---- the callers ---------------------------------------------------------------------------------------------------------------------------
-F_, D_, P_ = 34, 126, 4
-H_ = F_ - P_
-HOP, N = 32000, (124 - 1) * 512
-_MODELS = {}
-
-
-def ted_models():
-    from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
-    if "ted" not in _MODELS:
-        _MODELS["ted"] = (build_mirror("spatial", F_, D_, P_, 4, seed=7, precision="bf16x3").to(dev()),
-                          load_synth_weights(MLP_Reconstruct_v3(frames=F_), 7).eval().to(dev()))
-    return _MODELS["ted"]
-
-
-def inputs(U, W, seed):
-    inp = RO.rollout_inputs(U, W, F_, D_, P_, seed=seed)
-    return {k: torch.from_numpy(inp[k]).to(dev()) for k in ("text", "seed_pose", "label", "z")}
-
-
 def test_synthesize_rotations_equal_the_function_on_its_track():
     model, vae = ted_models()
     sk = skeleton("ted")

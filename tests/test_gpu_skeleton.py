@@ -8,45 +8,17 @@ import numpy as np
 import pytest
 import torch
 
-import rollout_np as RO
 import skeleton_np as SN
-from conftest import build_mirror
 from emotiongestures_amd import harness as Hs
 from emotiongestures_amd import skeleton as SK
-from emotiongestures_amd.synth import load_synth_weights, synth_audio
+from emotiongestures_amd.synth import synth_audio
+from skeleton_gpu_common import FPS, H_, HOP, LENGTHS, N, P_, RAGGED, RATES, TF, dev, inputs, mean_of, skeleton, table_of, ted_models
 
 pytestmark = pytest.mark.gpu
-
-TF = SK.TILE_FRAMES
-RATES = [(1, 1), (2, 1), (5, 3), (2, 3)]                 # L / M
-FPS = {(1, 1): None, (2, 1): (15, 30), (5, 3): (15, 25), (2, 3): (15, 10)}
-LENGTHS = [1, 2, TF - 1, TF, TF + 1, 2 * TF + 3]
-RAGGED = [1, TF + 1, 2 * TF + 3]
-_SK = {}
-
-
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def skeleton(name):
-    if name not in _SK:
-        _SK[name] = {"ted": SK.ted_expressive, "chain": lambda: SK.Skeleton(*SN.chain_table()), "star": lambda: SK.Skeleton(*SN.star_table()),
-                     "random63": lambda: SK.Skeleton(*SN.random_table())}[name]()
-    return _SK[name]
-
-
-def table_of(sk):
-    return sk.parents.tolist(), sk.children.tolist(), sk.lengths.tolist()
 
 
 def tracks(B, T, K, seed, scale=1.0):
     return (np.random.default_rng(seed).standard_normal((B, T, 3 * K)) * scale).astype(np.float32)
-
-
-def mean_of(K, seed):
-    return (np.random.default_rng(seed).standard_normal(3 * K) * 0.2).astype(np.float32)
 
 
 def check_forward(sk, v, frames, mean, unit, rate, what):
@@ -121,6 +93,26 @@ def test_draws_axis_equals_the_flattened_call():
         want = SN.joints(v.reshape(U * R, T, -1), table_of(sk), [T, T, 5, 5], mean.numpy().astype(np.float64), False, Lf, M)
         bound = SN.joints_bound(v.reshape(U * R, T, -1), table_of(sk), [T, T, 5, 5], mean.numpy().astype(np.float64), False, Lf, M)
         assert (np.abs(flat.cpu().numpy() - want) <= bound).all()
+
+
+@pytest.mark.parametrize("rate", [(1, 1), (5, 3), (2, 3)])
+@pytest.mark.parametrize("unit", [False, True])
+def test_out_stride_batch_and_tile_do_not_change_the_bits(unit, rate):
+    """(2, 3) needs more than TF + 2 source frames for a tile and so takes more than one pass."""
+    sk = skeleton("ted")
+    T = 2 * TF + 3
+    x = torch.from_numpy(tracks(3, T, sk.K, 23)).to(dev())
+    base = SK.launch_joints(x, sk, unit=unit, ratio=rate)
+    t_out = base.shape[1]
+    wide = torch.full((3, t_out + TF + 5, sk.J, 3), float("nan"), device=dev())
+    SK.launch_joints(x, sk, unit=unit, ratio=rate, out=wide)
+    assert torch.equal(wide[:, :t_out], base) and not wide[:, t_out:].any()
+    for b in range(3):                                           # another batch, another place in it
+        assert torch.equal(SK.launch_joints(x[b:b + 1].clone(), sk, unit=unit, ratio=rate), base[b:b + 1])
+    assert torch.equal(SK.launch_joints(x.flip(0).contiguous(), sk, unit=unit, ratio=rate), base.flip(0))
+    if rate == (1, 1):                                           # the same frames in another tile, at another place of it
+        for s in (1, TF - 1, TF + 7):
+            assert torch.equal(SK.launch_joints(x[:, s:].contiguous(), sk, unit=unit), base[:, s:])
 
 
 @pytest.mark.parametrize("name", ["ted", "chain", "star", "random63"])
@@ -205,25 +197,6 @@ def test_drop_in_on_a_cuda_tensor_within_the_forward_bound_of_the_golden():
 
 
 # ---- the callers ---------------------------------------------------------------------------------------------------------------------------
-F_, D_, P_ = 34, 126, 4
-H_ = F_ - P_
-HOP, N = 32000, (124 - 1) * 512
-_MODELS = {}
-
-
-def ted_models():
-    from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
-    if "ted" not in _MODELS:
-        _MODELS["ted"] = (build_mirror("spatial", F_, D_, P_, 4, seed=7, precision="bf16x3").to(dev()),
-                          load_synth_weights(MLP_Reconstruct_v3(frames=F_), 7).eval().to(dev()))
-    return _MODELS["ted"]
-
-
-def inputs(U, W, seed):
-    inp = RO.rollout_inputs(U, W, F_, D_, P_, seed=seed)
-    return {k: torch.from_numpy(inp[k]).to(dev()) for k in ("text", "seed_pose", "label", "z")}
-
-
 def test_synthesize_joints_equal_the_function_on_its_track():
     model, vae = ted_models()
     sk = skeleton("ted")

@@ -72,6 +72,18 @@ def test_level_table_and_rest_rows_of_the_host_call(name):
 
 
 @pytest.mark.parametrize("name", list(TABLES))
+def test_the_host_call_fills_level_words_and_no_more(name):
+    """skeleton.level_words(K) is the table eg_skeleton_levels writes: every word of it, and nothing behind it."""
+    sk = SK.Skeleton(*table(name))
+    n, mark = SK.level_words(sk.K), 0x7F7F7F7F                           # no offset, bone number or component of a unit vector
+    words = np.full(n + 8, mark, np.int32)
+    raw = rest_of(name).astype(np.float64)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    assert L.load().eg_skeleton_levels(*sk.host_ptrs(), sk.K, ptr(raw), ptr(words)) == 0
+    assert (words[:n] != mark).all() and (words[n:] == mark).all()
+
+
+@pytest.mark.parametrize("name", list(TABLES))
 def test_globals_turn_the_rest_pose_into_the_track(name):
     t, rest = table(name), rest_of(name)
     K = len(rest)
