@@ -186,6 +186,16 @@ struct EgProfScope {
     ~EgProfScope();
 };
 
+// ---- internal (C++ linkage) operands of the fused CVAE sample (misc.hip: cvae_sample_fused_kernel), filled by generator.hip ------------
+struct EgiCvaeFused {
+    const float *y = nullptr, *z = nullptr;                          // [n][8] labels, [n][32] latent draws
+    const float *lin_w[4] = {}, *lin_b[4] = {};                      // Posterior_Y_embedding.0 / .2, fusion_z_posterior.0 / .2
+    const float *t_w[2] = {}, *t_b[2] = {}, *t_s[2] = {}, *t_t[2] = {};      // ConvTranspose 4->8, 8->16: weight, bias, BN scale, BN shift
+    const float *c_w[3] = {}, *c_b[3] = {}, *c_s[2] = {}, *c_t[2] = {};      // Conv 16->32, 32->F, F->F (the last one plain)
+    float* out = nullptr;                                           // [n][F][L]
+    int F = 0, L = 0, T = 0;                                        // frames, d_model, tile of the L axis (set by the launch function)
+};
+
 // ---- internal (C++ linkage) product descriptor shared by gemm.hip and generator.hip --------------------------------
 struct EgiLinear {
     const float* x = nullptr; int lda = 0;                          // fp32 input, or ...

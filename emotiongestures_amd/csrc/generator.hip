@@ -158,6 +158,7 @@ int egi_rollout_handoff(const float* pose, const float* prior_in, const float* a
                         int W, int w, int F, int P, int D, hipStream_t st);
 int egi_small_linear(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int n, int in, int out,
                      hipStream_t st);
+int egi_cvae_sample_fused(EgiCvaeFused a, int n, hipStream_t st, int* taken);
 
 #define EG_TRY(expr)              \
     do {                          \
@@ -1392,6 +1393,11 @@ int cvae_decode(const EgCvae* c, const float* A, const CvaeWs& w, void* ws, int 
     EG_TRY(egi_conv1d(P(ws, w.d3), A + dc[1].w, A + dc[1].b, A + dc[1].s, A + dc[1].t, P(ws, w.d4), n, 32, F, D, 3, 1, 1, 1, st));
     return egi_conv1d(P(ws, w.d4), A + dc[2].w, A + dc[2].b, nullptr, nullptr, out, n, F, F, D, 3, 1, 1, 0, st);
 }
+// EG_CVAE_FUSED = "0" (read per call, like EG_TEXT_TAPS) keeps eg_cvae_sample on the launch chain (A/B runs, tests)
+bool cvae_fused_on() {
+    const char* e = getenv("EG_CVAE_FUSED");
+    return !(e && e[0] == '0');
+}
 }  // namespace
 
 extern "C" int eg_cvae_default_config(EgCvaeConfig* c) {
@@ -1448,6 +1454,18 @@ extern "C" int eg_cvae_sample(const EgCvae* c, const float* A, int32_t n, const 
     const CvaeWs w = cvae_carve(c, n);
     EG_REQUIRE(ws_bytes >= w.total, EG_ERR_WORKSPACE, "eg_cvae_sample: workspace too small");
     hipStream_t st = (hipStream_t)stream;
+    if (cvae_fused_on()) {
+        EgiCvaeFused f;
+        f.y = y; f.z = z; f.out = out; f.F = c->cfg.frames; f.L = c->cfg.d_model;
+        const EgCvae::Lin* lin[4] = {&c->py0, &c->py2, &c->fz0, &c->fz2};
+        for (int i = 0; i < 4; ++i) { f.lin_w[i] = A + lin[i]->w; f.lin_b[i] = A + lin[i]->b; }
+        for (int i = 0; i < 2; ++i) { f.t_w[i] = A + c->dec_t[i].w; f.t_b[i] = A + c->dec_t[i].b; f.t_s[i] = A + c->dec_t[i].s; f.t_t[i] = A + c->dec_t[i].t; }
+        for (int i = 0; i < 3; ++i) { f.c_w[i] = A + c->dec_conv[i].w; f.c_b[i] = A + c->dec_conv[i].b; }
+        for (int i = 0; i < 2; ++i) { f.c_s[i] = A + c->dec_conv[i].s; f.c_t[i] = A + c->dec_conv[i].t; }
+        int taken = 0;
+        EG_TRY(egi_cvae_sample_fused(f, n, st, &taken));
+        if (taken) return EG_OK;
+    }
     // post_y = Posterior_Y_embedding(y); zy = cat(z, post_y)  (BEAT_CVAE.py:440-443)
     EG_TRY(egi_small_linear(y, 8, A + c->py0.w, A + c->py0.b, P(ws, w.py_h), 16, n, 8, 16, st));
     EG_TRY(egi_small_linear(P(ws, w.py_h), 16, A + c->py2.w, A + c->py2.b, P(ws, w.zy) + 32, 64, n, 16, 32, st));

@@ -417,6 +417,8 @@ __global__ __launch_bounds__(256) void conv1d_kernel(const float* __restrict__ x
 
 // ConvTranspose1d(k=3, stride=2, padding=1, output_padding=1): Lout = 2*Lin; weight [Cin][Cout][3]
 // y[co, lo] = bias + sum_ci sum_k [ (lo + 1 - k) even, li = (lo+1-k)/2 in range ] x[ci, li] w[ci, co, k]
+// Left as the serial per-term walk it was: eg_cvae_sample no longer comes here (cvae_sample_fused_kernel below), only the training-mode forward
+// and the frames = 120 fall-back do, and its term order is the one the fused kernel reproduces.
 __global__ __launch_bounds__(128) void convt1d_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                       const float* __restrict__ bias, const float* __restrict__ scale,
                                                       const float* __restrict__ shift, float* __restrict__ y, int Cin, int Cout,
@@ -465,6 +467,242 @@ __global__ __launch_bounds__(256) void copy2d_kernel(const float* __restrict__ s
         const int r = (int)(i / cols), c = (int)(i % cols);
         dst[(size_t)r * ldd + c] = src[(size_t)r * lds_ + c];
     }
+}
+
+// ---- CVAE sample, fused: Posterior_Y_embedding -> fusion_z_posterior -> Decoder (BEAT_CVAE.py:355-369,440-446) in one launch ----------
+// One workgroup = (sample n, tile [l0, l0 + T) of the L = d_model axis).  It recomputes the MLP head, then walks the five decoder stages for
+// its tile with every intermediate in LDS; each stage also produces the halo the next one reads:
+//   out [l0, l0+T)  <-  d4 [l0-1, l0+T+1)  <-  d3 [l0-2, l0+T+2)  <-  d2 [l0-4, l0+T+4)  <-  d1 [l0/2-2, l0/2+T/2+4)  <-  z0 [l0/4-1, l0/4+T/4+3)
+// (d2 / d1 start on an even position so that a transposed stage is a walk over input positions li: output 2*li takes the tap k = 1 of x[li],
+// output 2*li + 1 the taps k = 0 of x[li + 1] and k = 2 of x[li] -- no per-term parity branch; T % 4 == 0 keeps l0/2 - 2 even).  A position
+// outside [0, L_stage) is the next stage's zero padding and is stored as 0, never computed from the bias; that zero is also what drops the
+// tap li + 1 == Lin of the last odd output (the chain skips that term, here it is + 0 * w: the same value unless the accumulator is exactly -0
+// or the weight is not finite).  Every output element is summed in the order of the launch chain it replaces (small_linear_kernel,
+// convt1d_kernel, conv1d_kernel: bias first, ci outer, k inner, LeakyReLU, then the BatchNorm affine), so the result is the chain's bit for bit.
+constexpr int CVAE_WAVES = 8;       // two waves per SIMD: one wave's LDS reads run under the other's FMAs
+struct CvaeFusedLds {       // float offsets into the dynamic LDS; d4 overlays the buffers that are dead once d3 is complete
+    int n0, n1, n2, n3, n4, cbF, d3, w6, w7, head, z0, d1, d2, w5, d4, total;
+};
+__host__ __device__ inline CvaeFusedLds cvae_fused_lds(int F, int T) {
+    CvaeFusedLds s;
+    s.n0 = T / 4 + 4; s.n1 = T / 2 + 6; s.n2 = T + 8; s.n3 = T + 4; s.n4 = T + 2;
+    s.cbF = (F + 7) & ~7;                            // output channels in groups of 8: the row length of the staged F-wide weights
+    int o = 0;
+    s.d3 = o; o += (32 * s.n3 + 3) & ~3;
+    s.w6 = o; o += 32 * 3 * s.cbF;
+    s.w7 = o; o += F * 3 * s.cbF;
+    s.d4 = o;
+    s.head = o; o += 16 + 64 + 128;                  // py_h | zy = [z | post_y] | fz_h
+    s.z0 = o; o += 4 * s.n0;
+    s.d1 = o; o += (8 * s.n1 + 3) & ~3;
+    s.d2 = o; o += 16 * s.n2;
+    s.w5 = o; o += 16 * 3 * 32;
+    const int d4_end = s.d4 + ((F * s.n4 + 3) & ~3);
+    s.total = o > d4_end ? o : d4_end;
+    return s;
+}
+
+// conv weights [Cout][CK] -> LDS [CK][CB] (zero beyond Cout), the layout conv1d_kernel stages
+__device__ __forceinline__ void cvae_stage_w(float* __restrict__ dst, const float* __restrict__ w, int Cout, int CK, int CB, int tid) {
+    for (int i = tid; i < CK * CB; i += 64 * CVAE_WAVES) {
+        const int ck = i / CB, c = i - ck * CB;
+        dst[i] = c < Cout ? w[(size_t)c * CK + ck] : 0.f;
+    }
+}
+
+// y[o] = bias[o] + sum_i w[o][i] x[i], one wave per output exactly as small_linear_kernel sums it; R outputs of a wave in flight at a time
+template <int R>
+__device__ __forceinline__ void cvae_linear(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                            float* __restrict__ y, int In, int Out, int wave, int lane) {
+    for (int o0 = wave * R; o0 < Out; o0 += CVAE_WAVES * R) {
+        float t[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int o = o0 + r;
+            float s = 0.f;
+            if (o < Out)
+                for (int i = lane; i < In; i += 64) s += w[(size_t)o * In + i] * x[i];
+            t[r] = s;
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) t[r] = wave_sum(t[r]);
+        if (lane == 0) {
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                if (o0 + r < Out) y[o0 + r] = t[r] + bias[o0 + r];
+        }
+    }
+}
+
+// ConvTranspose1d(k 3, stride 2, pad 1, output pad 1) + LeakyReLU + affine, LDS -> LDS.  xin [Cin][nin] and yout [Cout][nout] start at
+// positions p and 2p (pos0 = 2p); a lane owns the input position j and its two outputs, a wave COG output channels (wave-uniform weights).
+template <int COG>
+__device__ __forceinline__ void cvae_convt_stage(const float* __restrict__ xin, int nin, const float* __restrict__ w,
+                                                 const float* __restrict__ bias, const float* __restrict__ scale,
+                                                 const float* __restrict__ shift, float* __restrict__ yout, int nout, int Cin, int Cout,
+                                                 int pos0, int Lout, int wave, int lane) {
+    const int npairs = nout >> 1, ng = Cout / COG, nitems = ng * ((npairs + 63) >> 6);
+    for (int item = wave; item < nitems; item += CVAE_WAVES) {
+        const int g = item % ng, j = (item / ng) * 64 + lane;
+        if (j >= npairs) continue;
+        float e[COG], o[COG];
+#pragma unroll
+        for (int r = 0; r < COG; ++r) e[r] = o[r] = bias[g * COG + r];
+        for (int ci = 0; ci < Cin; ++ci) {
+            const float x0 = xin[ci * nin + j], x1 = xin[ci * nin + j + 1];
+#pragma unroll
+            for (int r = 0; r < COG; ++r) {
+                const float* wr = w + ((size_t)ci * Cout + g * COG + r) * 3;
+                o[r] += x1 * wr[0];
+                e[r] += x0 * wr[1];
+                o[r] += x0 * wr[2];
+            }
+        }
+        const int pe = pos0 + 2 * j;
+        const bool in_e = pe >= 0 && pe < Lout, in_o = pe + 1 >= 0 && pe + 1 < Lout;
+#pragma unroll
+        for (int r = 0; r < COG; ++r) {
+            const int co = g * COG + r;
+            float se = e[r], so = o[r];
+            se = se > 0.f ? se : 0.2f * se;
+            so = so > 0.f ? so : 0.2f * so;
+            se = se * scale[co] + shift[co];
+            so = so * scale[co] + shift[co];
+            yout[co * nout + 2 * j] = in_e ? se : 0.f;
+            yout[co * nout + 2 * j + 1] = in_o ? so : 0.f;
+        }
+    }
+}
+
+// Conv1d(k 3, pad 1) with conv1d_kernel's inner loop: a wave owns 8 output channels (f4 broadcast reads of the staged weights), a lane a position,
+// every LDS read of x feeds 8 FMAs.  xin [Cin][nin]: output index p reads xin[xoff + p + k].  FINAL: plain, to out[co][pos0 + p] in global
+// memory where pos0 + p < L; otherwise LeakyReLU + affine to yout [Cout][nout] in LDS, zero outside [0, L).
+template <bool FINAL>
+__device__ __forceinline__ void cvae_conv_stage(const float* __restrict__ xin, int nin, int xoff, const float* __restrict__ wl, int CB,
+                                                const float* __restrict__ bias, const float* __restrict__ scale,
+                                                const float* __restrict__ shift, float* __restrict__ yout, int nout, int Cin, int Cout,
+                                                int pos0, int L, int wave, int lane) {
+    const int ng = CB >> 3, nitems = ng * ((nout + 63) >> 6);
+    for (int item = wave; item < nitems; item += CVAE_WAVES) {
+        const int g = item % ng, p = (item / ng) * 64 + lane;
+        const int co0 = g * 8;
+        f4 acc[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[j][r] = (co0 + j * 4 + r < Cout) ? bias[co0 + j * 4 + r] : 0.f;
+        const float* xp = xin + xoff + (p < nout ? p : nout - 1);        // lanes past the stage's span read its last position and store nothing
+        const float* wg = wl + co0;
+#pragma unroll 4
+        for (int ci = 0; ci < Cin; ++ci) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float xv = xp[ci * nin + k];
+                const f4* wp = reinterpret_cast<const f4*>(wg + (ci * 3 + k) * CB);
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[j] += wp[j] * xv;
+            }
+        }
+        if (p >= nout) continue;
+        const int pos = pos0 + p;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int co = co0 + j * 4 + r;
+                if (co < Cout) {
+                    float s = acc[j][r];
+                    if (FINAL) {
+                        if (pos < L) yout[(size_t)co * L + pos] = s;
+                    } else {
+                        s = s > 0.f ? s : 0.2f * s;
+                        s = s * scale[co] + shift[co];
+                        yout[co * nout + p] = (pos >= 0 && pos < L) ? s : 0.f;
+                    }
+                }
+            }
+    }
+}
+
+__global__ __launch_bounds__(64 * CVAE_WAVES) void cvae_sample_fused_kernel(const EgiCvaeFused a) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int F = a.F, L = a.L, T = a.T, l0 = blockIdx.x * T;
+    const CvaeFusedLds s = cvae_fused_lds(F, T);
+    // The head's two wide layers (fz0: 128 x 64, the tile's rows of fz2: up to 144 x 128) are one global-memory latency each if fetched when
+    // their input is ready; the rows a wave sums depend on l0 alone, so their weights and biases are fetched here, before anything else.
+    constexpr int FR = 128 / CVAE_WAVES, ZR = 18;               // outputs per wave; 4 * n0 <= CVAE_WAVES * ZR while T <= 128
+    const int Q = L >> 2, q0 = (l0 >> 2) - 1;
+    float wf[FR], bf[FR], wz[ZR][2], bz[ZR];
+    int zrow[ZR];
+#pragma unroll
+    for (int r = 0; r < FR; ++r) {
+        const int o = wave * FR + r;
+        wf[r] = a.lin_w[2][o * 64 + lane];
+        bf[r] = a.lin_b[2][o];
+    }
+#pragma unroll
+    for (int r = 0; r < ZR; ++r) {
+        const int idx = wave * ZR + r, c = idx / s.n0, q = q0 + idx - c * s.n0;
+        zrow[r] = (idx < 4 * s.n0 && q >= 0 && q < Q) ? c * Q + q : -1;
+        const size_t row = zrow[r] >= 0 ? zrow[r] : 0;
+        wz[r][0] = a.lin_w[3][row * 128 + lane];
+        wz[r][1] = a.lin_w[3][row * 128 + lane + 64];
+        bz[r] = a.lin_b[3][row];
+    }
+    cvae_stage_w(sm + s.w5, a.c_w[0], 32, 16 * 3, 32, tid);
+    cvae_stage_w(sm + s.w6, a.c_w[1], F, 32 * 3, s.cbF, tid);
+    cvae_stage_w(sm + s.w7, a.c_w[2], F, F * 3, s.cbF, tid);
+    // post_y = py2(py0(y)); zy = [z | post_y]; fz_h = fz0(zy)
+    float* py_h = sm + s.head;
+    float* zy = py_h + 16;
+    float* fz_h = zy + 64;
+    if (tid < 32) zy[tid] = a.z[(size_t)n * 32 + tid];
+    cvae_linear<2>(a.y + (size_t)n * 8, a.lin_w[0], a.lin_b[0], py_h, 8, 16, wave, lane);
+    __syncthreads();
+    cvae_linear<4>(py_h, a.lin_w[1], a.lin_b[1], zy + 32, 16, 32, wave, lane);
+    __syncthreads();
+    {   // fz_h = fz0(zy): In = 64, one product per lane, as small_linear_kernel sums it
+        float t[FR];
+#pragma unroll
+        for (int r = 0; r < FR; ++r) {
+            float v = 0.f;
+            v += wf[r] * zy[lane];
+            t[r] = wave_sum(v);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int r = 0; r < FR; ++r) fz_h[wave * FR + r] = t[r] + bf[r];
+        }
+    }
+    __syncthreads();
+    {   // the slice of z0 = fz2(fz_h), viewed [4][L/4], that the tile reads: positions [l0/4 - 1, l0/4 - 1 + n0); zero outside [0, L/4)
+        float* z0 = sm + s.z0;
+        float t[ZR];
+#pragma unroll
+        for (int r = 0; r < ZR; ++r) {
+            float v = 0.f;
+            v += wz[r][0] * fz_h[lane];
+            v += wz[r][1] * fz_h[lane + 64];
+            t[r] = wave_sum(v);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int r = 0; r < ZR; ++r)
+                if (wave * ZR + r < 4 * s.n0) z0[wave * ZR + r] = zrow[r] >= 0 ? t[r] + bz[r] : 0.f;
+        }
+    }
+    __syncthreads();
+    cvae_convt_stage<2>(sm + s.z0, s.n0, a.t_w[0], a.t_b[0], a.t_s[0], a.t_t[0], sm + s.d1, s.n1, 4, 8, (l0 >> 1) - 2, L >> 1, wave, lane);
+    __syncthreads();
+    cvae_convt_stage<4>(sm + s.d1, s.n1, a.t_w[1], a.t_b[1], a.t_s[1], a.t_t[1], sm + s.d2, s.n2, 8, 16, l0 - 4, L, wave, lane);
+    __syncthreads();
+    cvae_conv_stage<false>(sm + s.d2, s.n2, 1, sm + s.w5, 32, a.c_b[0], a.c_s[0], a.c_t[0], sm + s.d3, s.n3, 16, 32, l0 - 2, L, wave, lane);
+    __syncthreads();            // d2 and everything before it is dead: d4 overlays it
+    cvae_conv_stage<false>(sm + s.d3, s.n3, 0, sm + s.w6, s.cbF, a.c_b[1], a.c_s[1], a.c_t[1], sm + s.d4, s.n4, 32, F, l0 - 1, L, wave, lane);
+    __syncthreads();
+    cvae_conv_stage<true>(sm + s.d4, s.n4, 0, sm + s.w7, s.cbF, a.c_b[2], nullptr, nullptr, a.out + (size_t)n * F * L, T, F, F, l0, L, wave, lane);
 }
 
 // out[row] = (a ? a[row] : 0) + b[(row / (rep*period)) * period + row % period]   (per-clip rows broadcast over `rep` draws)
@@ -740,6 +978,21 @@ int egi_small_linear(const float* x, int ldx, const float* w, const float* bias,
     hipLaunchKernelGGL(small_linear_kernel, dim3(eg_cdiv(out, 4) < 64 ? eg_cdiv(out, 4) : 64, n), dim3(256), 0, st, x, ldx, w, bias, y,
                        ldy, in, out);
     return eg_check_launch("small_linear");
+}
+// The whole of eg_cvae_sample in one launch.  *taken = 0 (and nothing launched) where the staged weights and the tile do not fit the LDS
+// (frames = 120: the last stage's weights alone are 172 KB): the caller then runs the launch chain.  The tile of the d_model axis is
+// 128 positions (64 and 256 were measured slower), the whole axis where that is shorter.
+int egi_cvae_sample_fused(EgiCvaeFused a, int n, hipStream_t st, int* taken) {
+    *taken = 0;
+    const int T = a.L < 128 ? a.L : 128;
+    if (a.L % 4 != 0 || n > 65535) return EG_OK;
+    const size_t smem = sizeof(float) * (size_t)cvae_fused_lds(a.F, T).total;
+    if (smem > 160 * 1024) return EG_OK;
+    if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(cvae_sample_fused_kernel), smem, "cvae sample")) return rc;
+    a.T = T;
+    hipLaunchKernelGGL(cvae_sample_fused_kernel, dim3(eg_cdiv(a.L, T), n), dim3(64 * CVAE_WAVES), smem, st, a);
+    *taken = 1;
+    return eg_check_launch("cvae_sample_fused");
 }
 
 
