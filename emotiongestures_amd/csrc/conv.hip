@@ -27,7 +27,6 @@ struct ConvArgs {
     float* y; float* gap;
     float* gap2 = nullptr;              // training forward: per-(clip, tile) channel sums of v*v beside `gap` (BatchNorm's variance without a pass over y)
     int H, W, Ho, Wo, cout, relu, nchw, tiles_x, tiles;
-    int batch = 0;                      // clips of the launch (the persistent walk's tile list is tiles * batch long)
     // fused SE tail (SEBasicBlock.forward, ResNetBlocks.py:28-36, identity shortcut): v = relu(v * gate[b, co] + res[pixel, co])
     // applied after the BatchNorm affine; gate comes from se_gate_pre_kernel (computed BEFORE this convolution runs)
     const float* gate = nullptr; const float* res = nullptr; int relu2 = 0;
@@ -251,14 +250,11 @@ __global__ __launch_bounds__(256) void conv3x3_f32_kernel(ConvArgs a) {
 // f[b][co] = sd[co] / q[b][co], q = gate[b][co] * s2[co], the 3x3 taps accumulate on top, and the epilogue relu(acc * q + h),
 // h = h2 * gate + hd, yields gate * (conv2 * s2 + h2) + (D * sd + hd).  f, q, h come from se_gate_pre_kernel, which keeps |q| >= 1e-30.
 //
-// PERSIST: a 1-D grid of resident workgroups walks the (clip, tile) list with the grid's stride, in the same XCD-aware order, as ONE flat sequence of
-// (tile, chunk) steps: the step counter, the weight ring and the halo register prefetch run across tile boundaries (a tile's last two steps issue the next
-// tile's first two weight copies, its last chunk fetches chunk 0 of the next tile's halo), and the epilogue of tile n is followed directly by the
-// store_tile of tile n + 1.  Per output element the K order is unchanged: outputs and pooling partials are bitwise those of the one-tile-per-workgroup launch.
-template <int CIN, int NTT, int S, int TH, int WM, int WN, int TERMS, int RING, bool SPLIT = false, bool DG2 = false, int SCC = 0, bool PERSIST = false>
+// One workgroup computes one tile in one straight pass: prologue (first two weight copies, first halo chunk, the shortcut pre-phase when SCC > 0), the
+// chunk x tap loop, the epilogue.
+template <int CIN, int NTT, int S, int TH, int WM, int WN, int TERMS, int RING, bool SPLIT = false, bool DG2 = false, int SCC = 0>
 __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const bf8* __restrict__ whi,
                                                            const bf8* __restrict__ wlo) {
-    static_assert(!PERSIST || (!SPLIT && !DG2 && SCC <= 1), "the persistent walk serves the unsplit forward kernels");
     static_assert(!DG2 || (S == 1 && !SPLIT), "DG2 tiles the dy grid with unit stride");
     static_assert(SCC == 0 || (S == 1 && !DG2 && SCC <= 2 && CIN >= 64), "the shortcut pre-phase belongs to a stride-1 conv2 and uses ring slots 2 and 1");
     using G = typename std::conditional<DG2, ConvGeomDG2<TH>, ConvGeom<S, TH>>::type;
@@ -281,15 +277,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
     // (whole clips at B >= 8); halo rows / columns shared by neighbouring tiles then hit in that XCD's L2.
     int tile_id = blockIdx.x, b = blockIdx.y;
     const int c0 = SPLIT ? (int)blockIdx.z * COUTP : 0;        // first output channel of this workgroup
-    // PERSIST: workgroup w (XCD-remapped: the grid is a multiple of 8) takes the logical tiles w, w + G, w + 2G, ... so that at any moment the G resident
-    // workgroups work on G consecutive tiles, each XCD on a contiguous run (the walk of conv3x3_c32_persistent_kernel)
-    const int NWG = PERSIST ? (int)gridDim.x : 1, total_tiles = PERSIST ? a.tiles * a.batch : 1;
-    int L = PERSIST ? (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3)) : 0;
-    if constexpr (PERSIST) {
-        if (L >= total_tiles) return;               // surplus workgroups of the rounded-up grid
-        b = L / a.tiles;
-        tile_id = L - b * a.tiles;
-    } else if (!SPLIT) {
+    if (!SPLIT) {
         const int total = gridDim.x * gridDim.y;
         if ((total & 7) == 0) {
             const int lin = blockIdx.y * gridDim.x + blockIdx.x;
@@ -298,7 +286,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
             tile_id = log - b * (int)gridDim.x;
         }
     }
-    int oy0 = (tile_id / a.tiles_x) * TH, ox0 = (tile_id % a.tiles_x) * 32;
+    const int oy0 = (tile_id / a.tiles_x) * TH, ox0 = (tile_id % a.tiles_x) * 32;
 
     int pbase[MT];
 #pragma unroll
@@ -313,7 +301,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
         for (int t = 0; t < MT; ++t)
 #pragma unroll
             for (int n = 0; n < NT; ++n) acc[ph][t][n] = (f4){0.f, 0.f, 0.f, 0.f};
-    const float* xb = a.x + (size_t)b * a.H * a.W * CIN;       // the clip whose halo load_tile fetches (PERSIST: runs one tile ahead at a tile's last chunk)
+    const float* xb = a.x + (size_t)b * a.H * a.W * CIN;       // the clip whose halo load_tile fetches
 
     // one step's weights = NIMG runs of WIMG slots; 64-slot (1 KiB) pieces are dealt round-robin to the 4 waves
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
@@ -485,241 +473,212 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
         }
     };
     Frags fr[2];
-    for (bool first = true;; first = false) {       // one pass per tile (a single pass unless PERSIST)
-        const bool has_next = PERSIST && L + NWG < total_tiles;
-        int n_b = 0, n_tile = 0, n_oy0 = 0, n_ox0 = 0;
-        if (has_next) {
-            n_b = (L + NWG) / a.tiles;
-            n_tile = L + NWG - n_b * a.tiles;
-            n_oy0 = (n_tile / a.tiles_x) * TH;
-            n_ox0 = (n_tile % a.tiles_x) * 32;
-        }
-        if constexpr (SCC > 0) {
-            // shortcut pre-phase: chunk c's 1x1 weights wait in ring slot 2 - c (free since the previous tile's last barrier), step 0's 3x3 weights and the
-            // first halo chunk are in flight throughout (a later tile of a persistent walk: issued by the previous tile's last steps)
+    if constexpr (SCC > 0) {
+        // shortcut pre-phase: chunk c's 1x1 weights wait in ring slot 2 - c, step 0's 3x3 weights and the first halo chunk are in flight throughout
 #pragma unroll
-            for (int c = 0; c < SCC; ++c) issue_rows(a.sc_whi, a.sc_wlo, c * 4, 2 - c);
-            if (first) {
-                issue_weights(0, 0);
-                if (SCC == 1) issue_weights(1, 1);
-            }
-            // staging roles: output pixel p of the TH x 32 tile, channel octet oc (8 consecutive lanes = 8 consecutive pixels of one octet)
-            constexpr int SNIT = TH * 128 / 256;
-            static_assert(SNIT * 256 == TH * 128, "shortcut staging deals whole iterations");
-            int sgoff[SNIT], sslot[SNIT];
+        for (int c = 0; c < SCC; ++c) issue_rows(a.sc_whi, a.sc_wlo, c * 4, 2 - c);
+        issue_weights(0, 0);
+        if (SCC == 1) issue_weights(1, 1);
+        // staging roles: output pixel p of the TH x 32 tile, channel octet oc (8 consecutive lanes = 8 consecutive pixels of one octet)
+        constexpr int SNIT = TH * 128 / 256;
+        static_assert(SNIT * 256 == TH * 128, "shortcut staging deals whole iterations");
+        int sgoff[SNIT], sslot[SNIT];
+#pragma unroll
+        for (int it = 0; it < SNIT; ++it) {
+            const int idx = tid + it * 256;
+            const int p = (idx >> 5) * 8 + (idx & 7), oc = (idx >> 3) & 3;
+            const int r = p >> 5, col = p & 31, oy = oy0 + r, ox = ox0 + col;
+            // oy < Ho = (sc_H - 1) / sc_S + 1  =>  sc_S * oy <= sc_H - 1: a valid output pixel's source pixel is inside the block input
+            sgoff[it] = (oy < a.Ho && ox < a.Wo) ? (oy * a.sc_S * a.sc_W + ox * a.sc_S) * (SCC * 32) + oc * 8 : -1;
+            sslot[it] = oc * PL + (r + 1) * IW + col + 1;
+        }
+        const float* __restrict__ sxb = a.sc_x + (size_t)b * a.sc_H * a.sc_W * (SCC * 32);
+        f4 sv[SNIT][2];
+        auto load_sc = [&](int c) {
 #pragma unroll
             for (int it = 0; it < SNIT; ++it) {
-                const int idx = tid + it * 256;
-                const int p = (idx >> 5) * 8 + (idx & 7), oc = (idx >> 3) & 3;
-                const int r = p >> 5, col = p & 31, oy = oy0 + r, ox = ox0 + col;
-                // oy < Ho = (sc_H - 1) / sc_S + 1  =>  sc_S * oy <= sc_H - 1: a valid output pixel's source pixel is inside the block input
-                sgoff[it] = (oy < a.Ho && ox < a.Wo) ? (oy * a.sc_S * a.sc_W + ox * a.sc_S) * (SCC * 32) + oc * 8 : -1;
-                sslot[it] = oc * PL + (r + 1) * IW + col + 1;
-            }
-            const float* __restrict__ sxb = a.sc_x + (size_t)b * a.sc_H * a.sc_W * (SCC * 32);
-            f4 sv[SNIT][2];
-            auto load_sc = [&](int c) {
-#pragma unroll
-                for (int it = 0; it < SNIT; ++it) {
-                    sv[it][0] = sv[it][1] = (f4){0.f, 0.f, 0.f, 0.f};
-                    if (sgoff[it] >= 0) {
-                        const float* src = sxb + sgoff[it] + c * 32;
-                        sv[it][0] = *reinterpret_cast<const f4*>(src);
-                        sv[it][1] = *reinterpret_cast<const f4*>(src + 4);
-                    }
+                sv[it][0] = sv[it][1] = (f4){0.f, 0.f, 0.f, 0.f};
+                if (sgoff[it] >= 0) {
+                    const float* src = sxb + sgoff[it] + c * 32;
+                    sv[it][0] = *reinterpret_cast<const f4*>(src);
+                    sv[it][1] = *reinterpret_cast<const f4*>(src + 4);
                 }
-            };
-            load_sc(0);
-            if (first) load_tile(0);
-#pragma unroll
-            for (int c = 0; c < SCC; ++c) {
-#pragma unroll
-                for (int it = 0; it < SNIT; ++it) {
-                    bf8 hi, lo;
-                    split_octet<TERMS == 3>(sv[it][0], sv[it][1], hi, lo);
-                    tile[sslot[it]] = hi;
-                    if (TERMS == 3) tile[4 * PL + sslot[it]] = lo;
-                }
-                if (c + 1 < SCC) load_sc(c + 1);
-                __syncthreads();                    // shortcut pixels visible; every copy issued so far has landed
-                read_w(fr[0], 2 - c);
-                read_x(fr[0], 4);                   // the centre tap's positions
-                mfma_half(fr[0], 0, 4);
-                mfma_half(fr[0], 1, 4);
-                __syncthreads();                    // fragment reads done: the tile and the slot may be overwritten
             }
-            if (SCC == 2) issue_weights(1, 1);
-            // D * f: the epilogue's per-clip scale q turns it back into D * sd (f = sd / q), whatever the gate
-            const float* __restrict__ fv = a.sc_vec + (size_t)b * a.cout;
+        };
+        load_sc(0);
+        load_tile(0);
 #pragma unroll
-            for (int n = 0; n < NT; ++n) {
-                const f4 fq = *reinterpret_cast<const f4*>(fv + c0 + (wn * NT + n) * 16 + kq * 4);
+        for (int c = 0; c < SCC; ++c) {
 #pragma unroll
-                for (int t = 0; t < MT; ++t) acc[0][t][n] = acc[0][t][n] * fq;
+            for (int it = 0; it < SNIT; ++it) {
+                bf8 hi, lo;
+                split_octet<TERMS == 3>(sv[it][0], sv[it][1], hi, lo);
+                tile[sslot[it]] = hi;
+                if (TERMS == 3) tile[4 * PL + sslot[it]] = lo;
             }
-        } else if (first) {
-            issue_weights(0, 0);
-            if (NSTEP > 1) issue_weights(1, 1);
-            load_tile(0);
+            if (c + 1 < SCC) load_sc(c + 1);
+            __syncthreads();                    // shortcut pixels visible; every copy issued so far has landed
+            read_w(fr[0], 2 - c);
+            read_x(fr[0], 4);                   // the centre tap's positions
+            mfma_half(fr[0], 0, 4);
+            mfma_half(fr[0], 1, 4);
+            __syncthreads();                    // fragment reads done: the tile and the slot may be overwritten
         }
+        if (SCC == 2) issue_weights(1, 1);
+        // D * f: the epilogue's per-clip scale q turns it back into D * sd (f = sd / q), whatever the gate
+        const float* __restrict__ fv = a.sc_vec + (size_t)b * a.cout;
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+            const f4 fq = *reinterpret_cast<const f4*>(fv + c0 + (wn * NT + n) * 16 + kq * 4);
+#pragma unroll
+            for (int t = 0; t < MT; ++t) acc[0][t][n] = acc[0][t][n] * fq;
+        }
+    } else {
+        issue_weights(0, 0);
+        if (NSTEP > 1) issue_weights(1, 1);
+        load_tile(0);
+    }
 #pragma unroll 1
-        for (int chunk = 0; chunk < CIN / 32; ++chunk) {
-            store_tile(chunk);                      // the tile is free: its last reads completed before the barrier of the previous tap 8
-            if (COUNTED && chunk > 0) {              // W of this chunk's tap 0 landed at that barrier too; only W of tap 1 is in flight
-                wait_vmcnt_imm<GW>();
-                wait_lgkmcnt0();                    // tile writes visible
-                wg_barrier();
-            } else {
-                __syncthreads();                    // tile visible; every weight copy issued so far has landed
-            }
-            if (chunk + 1 < CIN / 32) {
-                load_tile(chunk + 1);
-            } else if (has_next) {                  // the last chunk's taps hide chunk 0 of the NEXT tile's halo
-                set_goff(n_oy0, n_ox0);
-                xb = a.x + (size_t)n_b * a.H * a.W * CIN;
-                load_tile(0);
-            }
-            read_w(fr[0], 0);
-            read_x(fr[0], 0);
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                const int step = chunk * 9 + tap;
-                const bool more = step + 2 < NSTEP || has_next;     // the ring keeps streaming across a tile boundary: steps 0 and 1 of the next tile
-                if (more) issue_weights(step + 2 < NSTEP ? step + 2 : step + 2 - NSTEP, (tap + 2) % 3);
-                mfma_half(fr[tap & 1], 0, tap);
-                mid_sync(more);
-                if (tap < 8) { read_w(fr[(tap + 1) & 1], (tap + 1) % 3); read_x(fr[(tap + 1) & 1], tap + 1); }
-                mfma_half(fr[tap & 1], 1, tap);
-            }
+    for (int chunk = 0; chunk < CIN / 32; ++chunk) {
+        store_tile(chunk);                      // the tile is free: its last reads completed before the barrier of the previous tap 8
+        if (COUNTED && chunk > 0) {              // W of this chunk's tap 0 landed at that barrier too; only W of tap 1 is in flight
+            wait_vmcnt_imm<GW>();
+            wait_lgkmcnt0();                    // tile writes visible
+            wg_barrier();
+        } else {
+            __syncthreads();                    // tile visible; every weight copy issued so far has landed
         }
+        if (chunk + 1 < CIN / 32) load_tile(chunk + 1);
+        read_w(fr[0], 0);
+        read_x(fr[0], 0);
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int step = chunk * 9 + tap;
+            const bool more = step + 2 < NSTEP;
+            if (more) issue_weights(step + 2, (tap + 2) % 3);
+            mfma_half(fr[tap & 1], 0, tap);
+            mid_sync(more);
+            if (tap < 8) { read_w(fr[(tap + 1) & 1], (tap + 1) % 3); read_x(fr[(tap + 1) & 1], tap + 1); }
+            mfma_half(fr[tap & 1], 1, tap);
+        }
+    }
 
-        if constexpr (DG2) {
-            // four phases: dx[2 * by + py][2 * bx + px] for the base pixel (by, bx) of the dy grid; the (even, even) phase also takes the gradient that
-            // arrives on the dy grid (the stride-2 1x1 shortcut reads exactly those pixels of x)
-            const size_t ohw = (size_t)a.Ho * a.Wo;
-            float* __restrict__ yb = a.y + (size_t)b * ohw * a.cout;
-            const float* __restrict__ rq = a.res_q ? a.res_q + (size_t)b * a.H * a.W * a.cout : nullptr;
+    if constexpr (DG2) {
+        // four phases: dx[2 * by + py][2 * bx + px] for the base pixel (by, bx) of the dy grid; the (even, even) phase also takes the gradient that
+        // arrives on the dy grid (the stride-2 1x1 shortcut reads exactly those pixels of x)
+        const size_t ohw = (size_t)a.Ho * a.Wo;
+        float* __restrict__ yb = a.y + (size_t)b * ohw * a.cout;
+        const float* __restrict__ rq = a.res_q ? a.res_q + (size_t)b * a.H * a.W * a.cout : nullptr;
 #pragma unroll
-            for (int ph = 0; ph < 4; ++ph) {
-                const int py = ph >> 1, px = ph & 1;
+        for (int ph = 0; ph < 4; ++ph) {
+            const int py = ph >> 1, px = ph & 1;
 #pragma unroll
-                for (int t = 0; t < MT; ++t) {
-                    const int id = wm * MT + t;
-                    const int by = oy0 + (id >> 1), bx = ox0 + (id & 1) * 16 + li;
-                    const int oy = 2 * by + py, ox = 2 * bx + px;
-                    if (by < a.H && bx < a.W && oy < a.Ho && ox < a.Wo) {
+            for (int t = 0; t < MT; ++t) {
+                const int id = wm * MT + t;
+                const int by = oy0 + (id >> 1), bx = ox0 + (id & 1) * 16 + li;
+                const int oy = 2 * by + py, ox = 2 * bx + px;
+                if (by < a.H && bx < a.W && oy < a.Ho && ox < a.Wo) {
 #pragma unroll
-                        for (int n = 0; n < NT; ++n) {
-                            const int co = (wn * NT + n) * 16 + kq * 4;
-                            if (co < a.cout) {
-                                f4 v = acc[ph][t][n];
-                                if (ph == 0 && rq) v += *reinterpret_cast<const f4*>(rq + ((size_t)by * a.W + bx) * a.cout + co);
-                                *reinterpret_cast<f4*>(yb + ((size_t)oy * a.Wo + ox) * a.cout + co) = v;
-                            }
+                    for (int n = 0; n < NT; ++n) {
+                        const int co = (wn * NT + n) * 16 + kq * 4;
+                        if (co < a.cout) {
+                            f4 v = acc[ph][t][n];
+                            if (ph == 0 && rq) v += *reinterpret_cast<const f4*>(rq + ((size_t)by * a.W + bx) * a.cout + co);
+                            *reinterpret_cast<f4*>(yb + ((size_t)oy * a.Wo + ox) * a.cout + co) = v;
                         }
                     }
                 }
             }
-            return;
         }
+        return;
+    }
 
-        // epilogue: v = acc + bias; relu; v*scale + shift.  Pixel offsets are 32-bit and computed once per pixel tile; the
-        // per-image base is a scalar.  NHWC: one 16-byte store per (pixel tile, channel tile); NCHW (final_conv1 only): 4 stores.
-        f4 gsum[NT], gsq[NT];
-        int pixo[MT];
+    // epilogue: v = acc + bias; relu; v*scale + shift.  Pixel offsets are 32-bit and computed once per pixel tile; the
+    // per-image base is a scalar.  NHWC: one 16-byte store per (pixel tile, channel tile); NCHW (final_conv1 only): 4 stores.
+    f4 gsum[NT], gsq[NT];
+    int pixo[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+        const int id = wm * MT + t;
+        const int oy = oy0 + (id >> 1), ox = ox0 + (id & 1) * 16 + li;
+        pixo[t] = (oy < a.Ho && ox < a.Wo) ? oy * a.Wo + ox : -1;
+    }
+    const int hw = a.Ho * a.Wo;
+    float* __restrict__ yb = a.y + (size_t)b * hw * a.cout;
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+        gsum[n] = (f4){0.f, 0.f, 0.f, 0.f};
+        gsq[n] = gsum[n];
+        const int co = c0 + (wn * NT + n) * 16 + kq * 4;
+        const f4 bi = a.bias ? *reinterpret_cast<const f4*>(a.bias + co) : (f4){0.f, 0.f, 0.f, 0.f};
+        f4 sc = a.scale ? *reinterpret_cast<const f4*>(a.scale + co) : (f4){1.f, 1.f, 1.f, 1.f};
+        f4 sh = a.shift ? *reinterpret_cast<const f4*>(a.shift + co) : (f4){0.f, 0.f, 0.f, 0.f};
+        if constexpr (SCC > 0) {                // per-clip scale q and shift h (the launch passes no gate and no residual map, relu2 = 1)
+            const float* __restrict__ qv = a.sc_vec + ((size_t)a.sc_B + b) * a.cout + co;
+            sc = *reinterpret_cast<const f4*>(qv);
+            sh = *reinterpret_cast<const f4*>(qv + (size_t)a.sc_B * a.cout);
+        }
+        const f4 gt = (a.gate && co < a.cout) ? *reinterpret_cast<const f4*>(a.gate + (size_t)b * a.cout + co) : (f4){1.f, 1.f, 1.f, 1.f};
+        const bool rb = a.res != nullptr;
+        const size_t rbase = (size_t)b * hw * a.cout;
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
-            const int id = wm * MT + t;
-            const int oy = oy0 + (id >> 1), ox = ox0 + (id & 1) * 16 + li;
-            pixo[t] = (oy < a.Ho && ox < a.Wo) ? oy * a.Wo + ox : -1;
+            f4 v = acc[0][t][n] + bi;
+            if (a.relu) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+            }
+            v = v * sc + sh;
+            if (a.gate) v = v * gt;
+            if (rb && pixo[t] >= 0 && co < a.cout) v += residual_quad(a.res, a.res_bits, rbase + (size_t)pixo[t] * a.cout + co);
+            if (a.relu2) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+            }
+            if (pixo[t] >= 0) {
+                if (!a.nchw) {
+                    if (co < a.cout) *reinterpret_cast<f4*>(yb + pixo[t] * a.cout + co) = v;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (co + r < a.cout) yb[(co + r) * hw + pixo[t]] = v[r];
+                }
+                gsum[n] += v;
+                if (a.gap2) gsq[n] += v * v;
+            }
         }
-        const int hw = a.Ho * a.Wo;
-        float* __restrict__ yb = a.y + (size_t)b * hw * a.cout;
-        int cbase = c0;
-        if constexpr (PERSIST) asm volatile("" : "+s"(cbase));      // opaque per tile: the channel vectors are re-read (L1 hits) each tile instead of being
-                                                                    // hoisted out of the tile loop into 48 registers the taps have no room for
+    }
+    if (a.gap) {            // no LDS reads follow the last step's barrier: the LDS is free for the reduction
+        float* sred = reinterpret_cast<float*>(lds);        // [WM][COUTP] sums, then [WM][COUTP] sums of squares
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
-            gsum[n] = (f4){0.f, 0.f, 0.f, 0.f};
-            gsq[n] = gsum[n];
-            const int co = cbase + (wn * NT + n) * 16 + kq * 4;
-            const f4 bi = a.bias ? *reinterpret_cast<const f4*>(a.bias + co) : (f4){0.f, 0.f, 0.f, 0.f};
-            f4 sc = a.scale ? *reinterpret_cast<const f4*>(a.scale + co) : (f4){1.f, 1.f, 1.f, 1.f};
-            f4 sh = a.shift ? *reinterpret_cast<const f4*>(a.shift + co) : (f4){0.f, 0.f, 0.f, 0.f};
-            if constexpr (SCC > 0) {                // per-clip scale q and shift h (the launch passes no gate and no residual map, relu2 = 1)
-                const float* __restrict__ qv = a.sc_vec + ((size_t)a.sc_B + b) * a.cout + co;
-                sc = *reinterpret_cast<const f4*>(qv);
-                sh = *reinterpret_cast<const f4*>(qv + (size_t)a.sc_B * a.cout);
-            }
-            const f4 gt = (a.gate && co < a.cout) ? *reinterpret_cast<const f4*>(a.gate + (size_t)b * a.cout + co) : (f4){1.f, 1.f, 1.f, 1.f};
-            const bool rb = a.res != nullptr;
-            const size_t rbase = (size_t)b * hw * a.cout;
 #pragma unroll
-            for (int t = 0; t < MT; ++t) {
-                f4 v = acc[0][t][n] + bi;
-                if (a.relu) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-                }
-                v = v * sc + sh;
-                if (a.gate) v = v * gt;
-                if (rb && pixo[t] >= 0 && co < a.cout) v += residual_quad(a.res, a.res_bits, rbase + (size_t)pixo[t] * a.cout + co);
-                if (a.relu2) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-                }
-                if (pixo[t] >= 0) {
-                    if (!a.nchw) {
-                        if (co < a.cout) *reinterpret_cast<f4*>(yb + pixo[t] * a.cout + co) = v;
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            if (co + r < a.cout) yb[(co + r) * hw + pixo[t]] = v[r];
-                    }
-                    gsum[n] += v;
-                    if (a.gap2) gsq[n] += v * v;
-                }
-            }
-        }
-        if (a.gap) {            // no LDS reads follow the last step's barrier: the LDS is free for the reduction (PERSIST: the next tile's weights are landing
-                                // in the ring and its halo is stored right after: the scratch has a region of its own behind the ring)
-            float* sred = reinterpret_cast<float*>(PERSIST ? lds + TILE + RING * WBUF : lds);        // [WM][COUTP] sums, then [WM][COUTP] sums of squares
-#pragma unroll
-            for (int n = 0; n < NT; ++n) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float s = gsum[n][r];
-                    s = row16_sum(s);
-                    if (li == 0) sred[wm * COUTP + (wn * NT + n) * 16 + kq * 4 + r] = s;
-                    if (a.gap2) {
-                        float q = gsq[n][r];
-                        q = row16_sum(q);
-                        if (li == 0) sred[(WM + wm) * COUTP + (wn * NT + n) * 16 + kq * 4 + r] = q;
-                    }
-                }
-            }
-            // LDS traffic only: wait for the scratch writes, not (as __syncthreads would) for the tile's output stores to be acknowledged by memory
-            wait_lgkmcnt0();
-            wg_barrier();
-            if (tid < (SPLIT ? COUTP : a.cout)) {
-                float s = 0.f;
-#pragma unroll
-                for (int m = 0; m < WM; ++m) s += sred[m * COUTP + tid];
-                a.gap[((size_t)b * a.tiles + tile_id) * a.cout + c0 + tid] = s;
+            for (int r = 0; r < 4; ++r) {
+                float s = gsum[n][r];
+                s = row16_sum(s);
+                if (li == 0) sred[wm * COUTP + (wn * NT + n) * 16 + kq * 4 + r] = s;
                 if (a.gap2) {
-                    float q = 0.f;
-#pragma unroll
-                    for (int m = 0; m < WM; ++m) q += sred[(WM + m) * COUTP + tid];
-                    a.gap2[((size_t)b * a.tiles + tile_id) * a.cout + c0 + tid] = q;
+                    float q = gsq[n][r];
+                    q = row16_sum(q);
+                    if (li == 0) sred[(WM + wm) * COUTP + (wn * NT + n) * 16 + kq * 4 + r] = q;
                 }
             }
         }
-        if (!has_next) break;
-        L += NWG; b = n_b; tile_id = n_tile; oy0 = n_oy0; ox0 = n_ox0;
+        // LDS traffic only: wait for the scratch writes, not (as __syncthreads would) for the tile's output stores to be acknowledged by memory
+        wait_lgkmcnt0();
+        wg_barrier();
+        if (tid < (SPLIT ? COUTP : a.cout)) {
+            float s = 0.f;
 #pragma unroll
-        for (int t = 0; t < MT; ++t)
+            for (int m = 0; m < WM; ++m) s += sred[m * COUTP + tid];
+            a.gap[((size_t)b * a.tiles + tile_id) * a.cout + c0 + tid] = s;
+            if (a.gap2) {
+                float q = 0.f;
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[0][t][n] = (f4){0.f, 0.f, 0.f, 0.f};
+                for (int m = 0; m < WM; ++m) q += sred[(WM + m) * COUTP + tid];
+                a.gap2[((size_t)b * a.tiles + tile_id) * a.cout + c0 + tid] = q;
+            }
+        }
     }
 }
 
@@ -1250,16 +1209,15 @@ __global__ __launch_bounds__(256) void se_tail_downsample_kernel(const float* __
     }
 }
 
-template <int CIN, int NT, int S, int TH, int WM, int WN, int TERMS, int SCC = 0, bool PERSIST = false>
+template <int CIN, int NT, int S, int TH, int WM, int WN, int TERMS, int SCC = 0>
 int launch_conv_bf16(const ConvArgs& a, const bf8* whi, const bf8* wlo, dim3 grid, hipStream_t st) {
     // weight-ring depth: 3 where the K loop is long (C >= 64, stride 1); 2 for the HBM-bound C=32 layer and the
     // stride-2 entries (smaller LDS footprint => one more workgroup per CU)
     constexpr int RING = 3;
     using G = ConvGeom<S, TH>;
     constexpr int NIMG = (TERMS == 3) ? 2 : 1;
-    constexpr size_t LDS_BYTES = sizeof(bf8) * (size_t)(NIMG * 4 * G::PL + RING * NIMG * 4 * NT * 16) +
-                                 (PERSIST ? sizeof(float) * 2 * WM * NT * 16 : 0);         // + the pooling scratch of the persistent walk (sums, squares)
-    auto kern = conv3x3_bf16_kernel<CIN, NT, S, TH, WM, WN, TERMS, RING, false, false, SCC, PERSIST>;
+    constexpr size_t LDS_BYTES = sizeof(bf8) * (size_t)(NIMG * 4 * G::PL + RING * NIMG * 4 * NT * 16);
+    auto kern = conv3x3_bf16_kernel<CIN, NT, S, TH, WM, WN, TERMS, RING, false, false, SCC>;
     if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS_BYTES, "conv3x3")) return rc;
     hipLaunchKernelGGL(kern, grid, dim3(256), LDS_BYTES, st, a, whi, wlo);
     return eg_check_launch("conv3x3");
@@ -1309,33 +1267,7 @@ int body_channel_split(int batch, int tiles, int cin, int cout, int stride, int 
     return conv_channel_split(tiles * batch, cin == 128 ? 4 : 2);
 }
 
-// Grid of the persistent (tile, chunk) walk for a launch of `total` tiles, 0 = one workgroup per tile.  kind: 1 = the 64 -> 64 body, 2 = the 32 -> 64 entry,
-// 4 = the 64 -> 128 entry, 8 = final_conv1.  Default rule: min(total, 2 workgroups per CU) for the kinds in CONV_PERSIST_DEFAULT_KINDS, and only when
-// there are more tiles than resident workgroups.  Same-box A/B runs at 64 clips kept NONE of the four (the walk's per-tile
-// drain of the output stores and its register pressure cost more than the cold prologue it removes), so the mask is empty and every launch is one
-// workgroup per tile unless asked otherwise.  EG_CONV_GRID (read per call, as EG_GEMM_TILE; a captured graph keeps what it was captured
-// with) overrides: 0 = never, N = N workgroups (rounded up to the multiple of 8 the XCD remap needs) for every kind, whatever the tile count;
-// EG_CONV_PERSIST_KINDS = the bit mask of kinds the default rule serves (A/B).
-constexpr int CONV_PERSIST_DEFAULT_KINDS = 0;
-int conv_persist_grid(int kind, int total) {
-    const int resident = 512;                           // 2 workgroups per CU (as launch_conv32_persistent_t)
-    const char* e = getenv("EG_CONV_GRID");
-    if (e && e[0]) {
-        const int g = atoi(e);
-        if (g <= 0) return 0;
-        const int64_t cap = eg_round_up(total, 8), want = eg_round_up(g, 8);
-        return (int)(total > 0 && cap < want ? cap : want);
-    }
-    if (total <= 0) return 0;                           // (conv_persist_forced: only the override counts)
-    const char* k = getenv("EG_CONV_PERSIST_KINDS");
-    const int kinds = (k && k[0]) ? atoi(k) : CONV_PERSIST_DEFAULT_KINDS;
-    return ((kinds & kind) && total > resident) ? resident : 0;
-}
-
-// EG_CONV_GRID names a workgroup count: the launch is wanted on the persistent walk whatever its size, so the small-batch channel split stands back
-bool conv_persist_forced() { return conv_persist_grid(0, 0) > 0; }
-
-template <int CIN, int NT, int S, int TH, int WM, int WN, int SCC = 0, int KIND = 0>
+template <int CIN, int NT, int S, int TH, int WM, int WN, int SCC = 0>
 int launch_conv(const ConvArgs& a, int batch, int precision, hipStream_t st) {
     dim3 grid(a.tiles, batch), block(256);
     if (precision == EG_PREC_F32) {
@@ -1350,14 +1282,6 @@ int launch_conv(const ConvArgs& a, int batch, int precision, hipStream_t st) {
     const size_t f32_floats = (size_t)9 * CIN * NT * 16;
     const bf8* whi = reinterpret_cast<const bf8*>(a.w + f32_floats);
     const bf8* wlo = whi + (size_t)9 * (CIN / 8) * NT * 16;
-    if constexpr (KIND != 0) {
-        // inference launches only: the training forms (squares, input affine, masked residual, plain fan-in add) keep one workgroup per tile
-        const bool infer = !a.gap2 && !a.in_scale && !a.res_bits && !(a.res && !a.gate);
-        if (const int g = infer ? conv_persist_grid(KIND, a.tiles * batch) : 0) {
-            if (precision == EG_PREC_BF16X3) return launch_conv_bf16<CIN, NT, S, TH, WM, WN, 3, SCC, true>(a, whi, wlo, dim3(g), st);
-            return launch_conv_bf16<CIN, NT, S, TH, WM, WN, 1, SCC, true>(a, whi, wlo, dim3(g), st);
-        }
-    }
     if (precision == EG_PREC_BF16X3) return launch_conv_bf16<CIN, NT, S, TH, WM, WN, 3, SCC>(a, whi, wlo, grid, st);
     return launch_conv_bf16<CIN, NT, S, TH, WM, WN, 1, SCC>(a, whi, wlo, grid, st);
 }
@@ -1531,7 +1455,7 @@ int conv3x3_dispatch(const float* x, const float* w, const float* bias, const fl
     a.res_bits = res_bits;
     a.in_scale = in_scale; a.in_shift = in_shift;
     a.H = h; a.W = wdt; a.Ho = (h + 2 - 3) / stride + 1; a.Wo = (wdt + 2 - 3) / stride + 1;
-    a.cout = cout; a.relu = relu; a.nchw = nchw_out; a.batch = batch;
+    a.cout = cout; a.relu = relu; a.nchw = nchw_out;
     const int th = conv_tile_rows(cin, cout, stride);
     a.tiles_x = eg_cdiv(a.Wo, 32);
     a.tiles = a.tiles_x * eg_cdiv(a.Ho, th);
@@ -1551,11 +1475,11 @@ int conv3x3_dispatch(const float* x, const float* w, const float* bias, const fl
         a.sc_wlo = a.sc_whi + (size_t)(sc->cin / 8) * cout;
         a.scale = a.shift = nullptr;             // the epilogue's scale and shift are the per-clip q and h
         a.relu2 = 1;
-        const int split = (cin == 64 && conv_persist_forced()) ? 1 : body_channel_split(batch, a.tiles, cin, cout, 1, precision, 0);
+        const int split = body_channel_split(batch, a.tiles, cin, cout, 1, precision, 0);
         const bf8* whi = reinterpret_cast<const bf8*>(a.w + (size_t)9 * cin * cout);
         const bf8* wlo = whi + (size_t)9 * (cin / 8) * cout;
         if (cin == 64 && split == 2) return launch_conv_split_t<64, 2, 8, 4, 1, 3, 1>(a, batch, whi, wlo, st);
-        if (cin == 64) return launch_conv<64, 4, 1, 8, 4, 1, 1, 1>(a, batch, precision, st);
+        if (cin == 64) return launch_conv<64, 4, 1, 8, 4, 1, 1>(a, batch, precision, st);
         if (split == 2) return launch_conv_split_t<128, 4, 4, 2, 2, 3, 2>(a, batch, whi, wlo, st);
         if (split == 4) return launch_conv_split_t<128, 2, 4, 2, 2, 3, 2>(a, batch, whi, wlo, st);
         return launch_conv<128, 8, 1, 4, 2, 2, 2>(a, batch, precision, st);
@@ -1564,8 +1488,8 @@ int conv3x3_dispatch(const float* x, const float* w, const float* bias, const fl
         return launch_conv32_persistent(a, batch, precision, th, st);
     if (cin == 32 && coutp == 32 && stride == 1 && th == 4) return launch_conv<32, 2, 1, 4, 4, 1>(a, batch, precision, st);
     if (cin == 32 && coutp == 32 && stride == 1) return launch_conv<32, 2, 1, 8, 4, 1>(a, batch, precision, st);
-    if (cin == 32 && coutp == 64 && stride == 2) return launch_conv<32, 4, 2, 2, 2, 2, 0, 2>(a, batch, precision, st);
-    if (const int split = (cin == 64 && conv_persist_forced()) ? 1 : body_channel_split(batch, a.tiles, cin, cout, stride, precision, nchw_out); split > 1) {
+    if (cin == 32 && coutp == 64 && stride == 2) return launch_conv<32, 4, 2, 2, 2, 2>(a, batch, precision, st);
+    if (const int split = body_channel_split(batch, a.tiles, cin, cout, stride, precision, nchw_out); split > 1) {
         // few pixel tiles (small batches): spread the output channels over workgroups as well -- bitwise the unsplit kernels below
         const size_t f32_floats = (size_t)9 * cin * cout;
         const bf8* whi = reinterpret_cast<const bf8*>(a.w + f32_floats);
@@ -1574,16 +1498,16 @@ int conv3x3_dispatch(const float* x, const float* w, const float* bias, const fl
         if (cin == 128 && split == 2) return launch_conv_split_t<128, 4, 4, 2, 2, 3>(a, batch, whi, wlo, st);
         if (cin == 128 && split == 4) return launch_conv_split_t<128, 2, 4, 2, 2, 3>(a, batch, whi, wlo, st);
     }
-    if (cin == 64 && coutp == 64 && stride == 1) return launch_conv<64, 4, 1, 8, 4, 1, 0, 1>(a, batch, precision, st);
-    if (cin == 64 && coutp == 128 && stride == 2) return launch_conv<64, 8, 2, 2, 2, 2, 0, 4>(a, batch, precision, st);
+    if (cin == 64 && coutp == 64 && stride == 1) return launch_conv<64, 4, 1, 8, 4, 1>(a, batch, precision, st);
+    if (cin == 64 && coutp == 128 && stride == 2) return launch_conv<64, 8, 2, 2, 2, 2>(a, batch, precision, st);
     if (cin == 64 && coutp == 128 && stride == 1) return launch_conv<64, 8, 1, 4, 2, 2>(a, batch, precision, st);      // training: input gradient of final_conv1 (dy padded to 64 channels)
     if (cin == 128 && coutp == 128 && stride == 1) return launch_conv<128, 8, 1, 4, 2, 2>(a, batch, precision, st);
     // 256-channel stage of the audio emotion classifier (model/audio_emotion_classifer.py:20-22): 2-row tiles, waves split the channels
     if (cin == 128 && coutp == 256 && stride == 2) return launch_conv<128, 16, 2, 2, 1, 4>(a, batch, precision, st);
     if (cin == 256 && coutp == 256 && stride == 1) return launch_conv<256, 16, 1, 2, 1, 4>(a, batch, precision, st);
     if (cin == 128 && coutp <= 64 && stride == 1) {       // final_conv1: 128 -> frames (34 -> 48, 60 -> 64)
-        if (coutp <= 48) return launch_conv<128, 3, 1, 4, 4, 1, 0, 8>(a, batch, precision, st);
-        return launch_conv<128, 4, 1, 4, 4, 1, 0, 8>(a, batch, precision, st);
+        if (coutp <= 48) return launch_conv<128, 3, 1, 4, 4, 1>(a, batch, precision, st);
+        return launch_conv<128, 4, 1, 4, 4, 1>(a, batch, precision, st);
     }
     // final_conv1 with 65..128 frames (BEAT-long, 120): the 128-wide body kernel on weights zero-padded to 128 channels
     if (cin == 128 && coutp <= 128 && stride == 1) return launch_conv<128, 8, 1, 4, 2, 2>(a, batch, precision, st);

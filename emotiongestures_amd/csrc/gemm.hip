@@ -477,100 +477,74 @@ int launch_glds(const GemmArgs& a, int splits, hipStream_t st) {
 // ahead, fragments of step s+1 read from LDS while the MFMAs of step s run (register double buffer), one counted vmcnt and
 // one raw barrier per 32-deep step.
 
-// BK = K elements per barrier interval, RING = LDS slots, WM = MFMA tiles of a wave along M: 2 -> 64 (M) x 64 (N) workgroup tile,
-// 4 -> 128 x 64 (two 64-row X image tiles; the wave grid stays 2 x 2, a wave owns 64 x 32).  The 64 x 64 tile streams 16 KB of operands
-// from L2 into LDS per 48 MFMAs; the 128 x 64 tile 24 KB per 96 (3/4 of the operand stream per MFMA, 6 instead of 4 LDS-DMA pieces and
-// 12 instead of 8 ds_read_b128 per wave for twice the MFMAs), at half the workgroups.
+// 64 (M) x 64 (N) workgroup tile, wave grid 2 x 2 (a wave owns 32 x 32), 32-deep steps, 4-slot ring (64 KB in bf16x3: two workgroups per CU): the
+// tile streams 16 KB of operands from L2 into LDS per 48 MFMAs.
 // SHIFT: the causal two-tap product (GemmArgs::xs_*): the copy addresses of X are per lane already (lane = image row), so a lane of a shifted step
 // points at row r - xs_shift -- often in the previous 64-row image tile -- or at the caller's zero line; computed once, a K step adds a constant.
-template <int TERMS, int BK, int RING, int WM = 2, bool TRAIN = false, bool SHIFT = false>
-__global__ __launch_bounds__(256, (WM == 2 || RING <= 3) ? 2 : 1) void gemm_presplit_kernel(GemmArgs a, const bf8* __restrict__ xhi, const bf8* __restrict__ xlo, int xKO) {
+template <int TERMS, bool TRAIN = false, bool SHIFT = false>
+__global__ __launch_bounds__(256, 2) void gemm_presplit_kernel(GemmArgs a, const bf8* __restrict__ xhi, const bf8* __restrict__ xlo, int xKO) {
+    constexpr int BK = 32;                                                // K elements per barrier interval
+    constexpr int RING = 4;                                               // LDS slots
+    constexpr int WM = 2;                                                 // MFMA tiles of a wave along M (and along N)
     constexpr int NIMG = (TERMS == 3) ? 2 : 1;
-    constexpr int KG = BK / 32;                                           // MFMA k-groups per step
-    constexpr int TM = WM / 2;                                            // 64-row X image tiles per workgroup
-    constexpr int IMG = KG * 256;                                         // bf8 slots of one (tile, image): KG*4 octets x 64 rows
-    constexpr int XO = TM * NIMG * IMG, SLOT = XO + NIMG * IMG;           // slot: X [tile][hi|lo] then W [hi|lo]
-    constexpr int G = (TM + 1) * NIMG * KG;                               // LDS-DMA instructions per wave per step
-    static_assert(WM == 2 || (WM == 4 && BK == 32), "wave tile: 32 x 32 or 64 x 32");
+    constexpr int IMG = 256;                                              // bf8 slots of one image of a step: 4 octets x 64 rows
+    constexpr int XO = NIMG * IMG, SLOT = XO + NIMG * IMG;                // slot: X [hi|lo] then W [hi|lo]
+    constexpr int G = 2 * NIMG;                                           // LDS-DMA instructions per wave per step
     extern __shared__ __attribute__((aligned(16))) bf8 lds[];             // RING * SLOT
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, kq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int bx, by;
     xcd_tile(bx, by);
-    const int m0 = bx * 64 * TM, n0 = by * 64;
-    const int wmt = wave >> 1;                                            // WM == 2: 32-row half of the tile; WM == 4: which 64-row tile
-    const int wm = (TM == 1) ? wmt * 32 : 0, wn = (wave & 1) * 32;
-    const int xfrag0 = (TM == 1) ? 0 : wmt * NIMG * IMG;                  // this wave's X fragments start here inside a slot
+    const int m0 = bx * 64, n0 = by * 64;
+    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
     const int kbeg = blockIdx.z * a.k_per_split;
     const int kend = min(a.K, kbeg + a.k_per_split);
     const int nsteps = (kend - kbeg + BK - 1) / BK;
     const int KO = a.ldw >> 3;
-    const int mt_last = ((a.M + 63) >> 6) - 1;
-    // X image tile t of this workgroup (a 128-row workgroup past an odd tile count re-reads the last tile: those rows are never stored)
-    const int xt0 = bx * TM, xt1 = min(bx * TM + TM - 1, mt_last);
-    static_assert(!SHIFT || (BK == 32 && WM == 2), "shifted X: 64 x 64 tile, 32-deep steps");
     const bf8 *sxh = nullptr, *sxl = nullptr;                             // SHIFT: this lane's source of octet `wave` of the shifted segment
     if constexpr (SHIFT) {
-        const int m = xt0 * 64 + lane, ms = m - a.xs_shift;
+        const int m = bx * 64 + lane, ms = m - a.xs_shift;
         const bool ok = (m % a.xs_period) >= a.xs_shift;                  // then ms >= 0
         const size_t gs = ((size_t)(ms >> 6) * xKO + a.xoct0 + wave) * 64 + (ms & 63);
         sxh = ok ? xhi + gs : a.xzero + wave * 64 + lane;
         sxl = ok ? xlo + gs : a.xzero + wave * 64 + lane;
     }
-    auto issue = [&](int step, int slot) {
+    auto issue = [&](int step, int slot) {          // this wave's piece = octet `wave` of the step
         const int ko = (kbeg + step * BK) >> 3;
         bf8* S = lds + slot * SLOT;
-#pragma unroll
-        for (int p = 0; p < KG; ++p) {                                    // piece = octet (p*4 + wave) of this step
-            const int d = (p * 4 + wave) * 64;
-#pragma unroll
-            for (int t = 0; t < TM; ++t) {
-                const int xo = (SHIFT && step >= a.xs_steps) ? ko - a.xs_steps * 4 : ko;       // second segment: the same X octets again
-                const size_t gx = ((size_t)(t ? xt1 : xt0) * xKO + a.xoct0 + xo + p * 4 + wave) * 64 + lane;
-                const bf8* ph = xhi + gx;
-                const bf8* pl = xlo + gx;
-                if (SHIFT && step < a.xs_steps) { ph = sxh + (size_t)step * 256; pl = sxl + (size_t)step * 256; }
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)ph,
-                                                 (__attribute__((address_space(3))) void*)(S + t * NIMG * IMG + d), 16, 0, 0);
-                if (TERMS == 3)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pl,
-                                                     (__attribute__((address_space(3))) void*)(S + t * NIMG * IMG + IMG + d), 16, 0, 0);
-            }
-            const size_t gw = ((size_t)by * KO + ko + p * 4 + wave) * 64 + lane;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const bf8*>(a.whi) + gw),
-                                             (__attribute__((address_space(3))) void*)(S + XO + d), 16, 0, 0);
-            if (TERMS == 3)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const bf8*>(a.wlo) + gw),
-                                                 (__attribute__((address_space(3))) void*)(S + XO + IMG + d), 16, 0, 0);
-        }
+        const int d = wave * 64;
+        const int xo = (SHIFT && step >= a.xs_steps) ? ko - a.xs_steps * 4 : ko;       // second segment: the same X octets again
+        const size_t gx = ((size_t)bx * xKO + a.xoct0 + xo + wave) * 64 + lane;
+        const bf8* ph = xhi + gx;
+        const bf8* pl = xlo + gx;
+        if (SHIFT && step < a.xs_steps) { ph = sxh + (size_t)step * 256; pl = sxl + (size_t)step * 256; }
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)ph, (__attribute__((address_space(3))) void*)(S + d), 16, 0, 0);
+        if (TERMS == 3)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pl, (__attribute__((address_space(3))) void*)(S + IMG + d), 16, 0, 0);
+        const size_t gw = ((size_t)by * KO + ko + wave) * 64 + lane;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const bf8*>(a.whi) + gw),
+                                         (__attribute__((address_space(3))) void*)(S + XO + d), 16, 0, 0);
+        if (TERMS == 3)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const bf8*>(a.wlo) + gw),
+                                             (__attribute__((address_space(3))) void*)(S + XO + IMG + d), 16, 0, 0);
     };
-    auto wait_groups = [&](int n) {                 // all but the youngest n step groups of this wave have landed
-        switch (n) {
-            case 0: wait_vmcnt_imm<0>(); break;
-            case 1: wait_vmcnt_imm<G>(); break;
-            case 2: wait_vmcnt_imm<2 * G>(); break;
-            case 3: wait_vmcnt_imm<3 * G>(); break;
-            case 4: wait_vmcnt_imm<4 * G>(); break;
-            default: wait_vmcnt_imm<5 * G>(); break;
-        }
+    static_assert(RING == 4, "a step group must land within two steps: at most one younger group stays in flight across a barrier");
+    auto wait_groups = [&](int n) {                 // all but the youngest n (0 or 1) step groups of this wave have landed
+        if (n == 0) wait_vmcnt_imm<0>(); else wait_vmcnt_imm<G>();
     };
-    static_assert(RING <= 8 && (RING - 3) * G <= 63, "wait_groups covers RING - 3 groups in flight");
-    struct Frags { bf8 xh[KG][WM], xl[KG][WM], wh[KG][2], wl[KG][2]; };
+    struct Frags { bf8 xh[WM], xl[WM], wh[2], wl[2]; };
     auto read_frags = [&](Frags& f, int slot) {
         const bf8* S = lds + slot * SLOT + li;
+        const int o = kq * 64;
 #pragma unroll
-        for (int g = 0; g < KG; ++g) {
-            const int o = (g * 4 + kq) * 64;
+        for (int t = 0; t < WM; ++t) {
+            f.xh[t] = S[o + wm + t * 16];
+            if (TERMS == 3) f.xl[t] = S[IMG + o + wm + t * 16];
+        }
 #pragma unroll
-            for (int t = 0; t < WM; ++t) {
-                f.xh[g][t] = S[xfrag0 + o + wm + t * 16];
-                if (TERMS == 3) f.xl[g][t] = S[xfrag0 + IMG + o + wm + t * 16];
-            }
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                f.wh[g][n] = S[XO + o + wn + n * 16];
-                if (TERMS == 3) f.wl[g][n] = S[XO + IMG + o + wn + n * 16];
-            }
+        for (int n = 0; n < 2; ++n) {
+            f.wh[n] = S[XO + o + wn + n * 16];
+            if (TERMS == 3) f.wl[n] = S[XO + IMG + o + wn + n * 16];
         }
     };
     f4 acc[WM][2];
@@ -580,17 +554,15 @@ __global__ __launch_bounds__(256, (WM == 2 || RING <= 3) ? 2 : 1) void gemm_pres
         for (int n = 0; n < 2; ++n) acc[t][n] = (f4){0.f, 0.f, 0.f, 0.f};
     auto mfma_step = [&](const Frags& f) {
 #pragma unroll
-        for (int g = 0; g < KG; ++g)
+        for (int t = 0; t < WM; ++t)
 #pragma unroll
-            for (int t = 0; t < WM; ++t)
-#pragma unroll
-                for (int n = 0; n < 2; ++n) {
-                    if (TERMS == 3) {
-                        acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wl[g][n], f.xh[g][t], acc[t][n], 0, 0, 0);
-                        acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wh[g][n], f.xl[g][t], acc[t][n], 0, 0, 0);
-                    }
-                    acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wh[g][n], f.xh[g][t], acc[t][n], 0, 0, 0);
+            for (int n = 0; n < 2; ++n) {
+                if (TERMS == 3) {
+                    acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wl[n], f.xh[t], acc[t][n], 0, 0, 0);
+                    acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wh[n], f.xl[t], acc[t][n], 0, 0, 0);
                 }
+                acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wh[n], f.xh[t], acc[t][n], 0, 0, 0);
+            }
     };
 
     // prologue: groups 0..RING-2 in flight; groups 0 and 1 landed before the loop
@@ -606,23 +578,21 @@ __global__ __launch_bounds__(256, (WM == 2 || RING <= 3) ? 2 : 1) void gemm_pres
         if (s + RING - 1 < nsteps) issue(s + RING - 1, (s + RING - 1) % RING);
         if (s + 1 < nsteps) read_frags(nxt, (s + 1) % RING);
         mfma_step(cur);
-        // at the next step's start, group s+2 must be landed (its fragments are read then); younger ones may stay in flight
+        // at the next step's start, group s+2 must be landed (its fragments are read then); the one younger group may stay in flight
         const int newest = min(s + RING - 1, nsteps - 1);
         wait_groups(max(0, min(RING - 3, newest - (s + 2))));
         __builtin_amdgcn_s_waitcnt(0xC07F);       // lgkmcnt(0) as a real instruction, so the compiler's own wait insertion sees it
         wg_barrier();
     };
     int s0 = 0;
-    if constexpr (BK == 32 && !SHIFT) {
+    if constexpr (!SHIFT) {
         // Steady state, RING steps per iteration: every step issues a copy (group s+RING-1), so there are no conditionals, the
         // ring slots are compile-time constants and the source addresses are running pointers (one 64-bit add each per
         // step).  A copy has RING-2 steps to land.
         constexpr int AHEAD = (RING - 1) * 4;                           // octets between this step and the group it issues
         const size_t xoff = (size_t)(a.xoct0 + (kbeg >> 3) + AHEAD + wave) * 64 + lane;
-        const bf8* px = xhi + (size_t)xt0 * xKO * 64 + xoff;
-        const bf8* pxl = xlo + (size_t)xt0 * xKO * 64 + xoff;
-        const bf8* px1 = xhi + (size_t)xt1 * xKO * 64 + xoff;          // second X tile (WM == 4 only)
-        const bf8* pxl1 = xlo + (size_t)xt1 * xKO * 64 + xoff;
+        const bf8* px = xhi + (size_t)bx * xKO * 64 + xoff;
+        const bf8* pxl = xlo + (size_t)bx * xKO * 64 + xoff;
         const bf8* pw = reinterpret_cast<const bf8*>(a.whi) + ((size_t)by * KO + (kbeg >> 3) + AHEAD + wave) * 64 + lane;
         const bf8* pwl = reinterpret_cast<const bf8*>(a.wlo) + ((size_t)by * KO + (kbeg >> 3) + AHEAD + wave) * 64 + lane;
         auto fast = [&](const int j, Frags& cur, Frags& nxt) {     // j = step index mod RING (static)
@@ -630,29 +600,22 @@ __global__ __launch_bounds__(256, (WM == 2 || RING <= 3) ? 2 : 1) void gemm_pres
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)px, (__attribute__((address_space(3))) void*)S, 16, 0, 0);
             if (TERMS == 3)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pxl, (__attribute__((address_space(3))) void*)(S + IMG), 16, 0, 0);
-            if (TM == 2) {
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)px1, (__attribute__((address_space(3))) void*)(S + NIMG * IMG), 16, 0, 0);
-                if (TERMS == 3)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pxl1, (__attribute__((address_space(3))) void*)(S + NIMG * IMG + IMG), 16, 0, 0);
-                px1 += 256; pxl1 += 256;
-            }
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pw, (__attribute__((address_space(3))) void*)(S + XO), 16, 0, 0);
             if (TERMS == 3)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pwl, (__attribute__((address_space(3))) void*)(S + XO + IMG), 16, 0, 0);
             px += 256; pxl += 256; pw += 256; pwl += 256;
             read_frags(nxt, (j + 1) % RING);
             mfma_step(cur);
-            wait_vmcnt_imm<(RING - 3) * G>();       // group s+2 landed; the RING-3 younger copies stay in flight
+            wait_vmcnt_imm<(RING - 3) * G>();       // group s+2 landed; the one younger copy stays in flight
             wait_lgkmcnt0();
             wg_barrier();
         };
-        constexpr int UNR = (RING % 2) ? 2 * RING : RING;               // whole ring turns and an even number of steps (fa / fb)
 #pragma unroll 1
-        for (; s0 + UNR + RING - 1 <= nsteps; s0 += UNR) {
+        for (; s0 + 2 * RING - 1 <= nsteps; s0 += RING) {              // a whole ring turn: an even number of steps (fa / fb)
 #pragma unroll
-            for (int j = 0; j < UNR; j += 2) {
-                fast(j % RING, fa, fb);
-                fast((j + 1) % RING, fb, fa);
+            for (int j = 0; j < RING; j += 2) {
+                fast(j, fa, fb);
+                fast(j + 1, fb, fa);
             }
         }
     }
@@ -661,16 +624,15 @@ __global__ __launch_bounds__(256, (WM == 2 || RING <= 3) ? 2 : 1) void gemm_pres
         step(s, fa, fb);
         if (s + 1 < nsteps) step(s + 1, fb, fa);
     }
-    gemm_epilogue<WM, 2, TRAIN>(a, acc, m0 + ((TM == 1) ? wm : wmt * 64) + li, n0 + wn + kq * 4);
+    gemm_epilogue<WM, 2, TRAIN>(a, acc, m0 + wm + li, n0 + wn + kq * 4);
 }
 
-template <int TERMS, int BK, int RING, int WM = 2, bool TRAIN = false, bool SHIFT = false>
+template <int TERMS, bool TRAIN = false, bool SHIFT = false>
 int launch_presplit(const GemmArgs& a, const bf8* xhi, const bf8* xlo, int xko, dim3 grid, hipStream_t st) {
     constexpr int NIMG = (TERMS == 3) ? 2 : 1;
-    constexpr size_t LDS_BYTES = (size_t)RING * (WM / 2 + 1) * NIMG * (BK / 32) * 4 * 64 * 16;
-    auto kern = gemm_presplit_kernel<TERMS, BK, RING, WM, TRAIN, SHIFT>;
+    constexpr size_t LDS_BYTES = (size_t)4 * 2 * NIMG * 4 * 64 * 16;      // 4 slots of (X, W) x NIMG images x 4 octets x 64 rows
+    auto kern = gemm_presplit_kernel<TERMS, TRAIN, SHIFT>;
     if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS_BYTES, "gemm_presplit")) return rc;
-    if (WM == 4) grid.x = (grid.x + 1) / 2;          // grid.x arrives as the number of 64-row tiles
     hipLaunchKernelGGL(kern, grid, dim3(256), LDS_BYTES, st, a, xhi, xlo, xko);
     return eg_check_launch("gemm_presplit");
 }
@@ -682,9 +644,10 @@ int launch_presplit(const GemmArgs& a, const bf8* xhi, const bf8* xlo, int xko, 
 // workgroup tile 128 x 128 = two 64-row image tiles of X and of W, 32 KB per 32-deep step, 3-slot ring (96 KB: one workgroup
 // = two waves per SIMD).  Schedule as in the convolution: one barrier per step between the two MFMA halves, counted vmcnt
 // (the copy of step s+2 stays in flight), fragments of step s+1 read after the barrier under the second half.
-template <int TERMS, int RING = 3, bool TRAIN = false, bool SHIFT = false>
+template <int TERMS, bool TRAIN = false, bool SHIFT = false>
 __global__ __launch_bounds__(512, 1) void gemm_presplit128_kernel(GemmArgs a, const bf8* __restrict__ xhi, const bf8* __restrict__ xlo, int xKO,
                                                                   int m_tiles, int n_tiles) {
+    constexpr int RING = 3;                             // LDS slots
     constexpr int NIMG = (TERMS == 3) ? 2 : 1;
     constexpr int OPI = 8 * 64;                         // bf8 slots of one image of one operand: [tile(2)][octet(4)][64 rows]
     constexpr int OP = NIMG * OPI, SLOT = 2 * OP;
@@ -762,7 +725,6 @@ __global__ __launch_bounds__(512, 1) void gemm_presplit128_kernel(GemmArgs a, co
                 acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wh[n], f.xh[t], acc[t][n], 0, 0, 0);
             }
     };
-    static_assert(RING == 3 || RING == 4, "ring depth");
     auto wait_younger = [&](int n) {                // all but the youngest n groups of this wave have landed
         if (n <= 0) wait_vmcnt_imm<0>();
         else if (n == 1) wait_vmcnt_imm<G>();
@@ -792,138 +754,29 @@ __global__ __launch_bounds__(512, 1) void gemm_presplit128_kernel(GemmArgs a, co
     gemm_epilogue<4, 2, TRAIN>(a, acc, m0 + wm * 64 + li, n0 + wn * 32 + kq * 4);
 }
 
-template <int TERMS, int RING = 3, bool TRAIN = false, bool SHIFT = false>
+template <int TERMS, bool TRAIN = false, bool SHIFT = false>
 int launch_presplit128(const GemmArgs& a, const bf8* xhi, const bf8* xlo, int xko, int m_tiles, int n_tiles, hipStream_t st) {
     constexpr int NIMG = (TERMS == 3) ? 2 : 1;
-    constexpr size_t LDS_BYTES = (size_t)RING * 2 * NIMG * 8 * 64 * 16;
+    constexpr size_t LDS_BYTES = (size_t)3 * 2 * NIMG * 8 * 64 * 16;       // 3 slots of (X, W) x NIMG images x 2 tiles x 4 octets x 64 rows
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-    auto kern = gemm_presplit128_kernel<TERMS, RING, TRAIN, SHIFT>;
+    auto kern = gemm_presplit128_kernel<TERMS, TRAIN, SHIFT>;
     if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS_BYTES, "gemm_presplit128")) return rc;
     dim3 grid(eg_cdiv(m_tiles, 2), eg_cdiv(n_tiles, 2), 1);
     hipLaunchKernelGGL(kern, grid, dim3(512), LDS_BYTES, st, a, xhi, xlo, xko, m_tiles, n_tiles);
     return eg_check_launch("gemm_presplit128");
 }
 
-// ---- 128 x 128 tile with 64-deep steps (EG_GEMM_TILE=128k64) ---------------------------------------------------------------
-// The kernel above spends one barrier, one counted wait and one round of fragment reads per 24 MFMAs of a wave; its K = 512 launches run 16 such
-// steps.  Here a step is 64 deep: 64 KB of operands per slot, a two-slot ring (128 KB, one workgroup per CU as before), 48 MFMAs per wave between
-// two barriers, half the barriers.  The copy of step s+1 is issued at the top of step s and has the whole MFMA phase to land; the wait before
-// the barrier is vmcnt(0) because that copy is the only one in flight.  Per output element the K order and the three split terms are those of
-// the 32-deep kernel: bitwise-equal results.  A K that ends on an odd 32 skips the second half of the last step (its copies re-read the last
-// valid octets).  Inference epilogue, no row shift.
-template <int TERMS>
-__global__ __launch_bounds__(512, 1) void gemm_presplit128_k64_kernel(GemmArgs a, const bf8* __restrict__ xhi, const bf8* __restrict__ xlo, int xKO,
-                                                                      int m_tiles, int n_tiles) {
-    constexpr int NIMG = (TERMS == 3) ? 2 : 1;
-    constexpr int OPI = 2 * 8 * 64;                     // bf8 slots of one image of one operand: [tile(2)][octet(8)][64 rows]
-    constexpr int OP = NIMG * OPI, SLOT = 2 * OP;
-    extern __shared__ __attribute__((aligned(16))) bf8 lds[];
-    const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, kq = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int bx, by;
-    xcd_tile(bx, by);
-    const int m0 = bx * 128, n0 = by * 128;
-    const int wm = wave >> 2, wn = wave & 3;            // wave tile: rows [wm*64, +64), columns [wn*32, +32)
-    const int nsteps = (a.K + 63) / 64, kov = a.K >> 3; // kov: valid octets (K % 32 == 0)
-    const int KO = a.ldw >> 3;
-    const int pt = wave >> 2, po = wave & 3;            // copy role: tile pt, octets po and po + 4 of each image
-    const bf8* px = xhi + ((size_t)min(bx * 2 + pt, m_tiles - 1) * xKO + a.xoct0) * 64 + lane;
-    const bf8* pxl = xlo + ((size_t)min(bx * 2 + pt, m_tiles - 1) * xKO + a.xoct0) * 64 + lane;
-    const bf8* pw = reinterpret_cast<const bf8*>(a.whi) + (size_t)min(by * 2 + pt, n_tiles - 1) * KO * 64 + lane;
-    const bf8* pwl = reinterpret_cast<const bf8*>(a.wlo) + (size_t)min(by * 2 + pt, n_tiles - 1) * KO * 64 + lane;
-    auto issue = [&](int step, int slot) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            bf8* S = lds + slot * SLOT + (pt * 8 + h * 4 + po) * 64;
-            const size_t o = (size_t)min(step * 8 + h * 4 + po, kov - 1) * 64;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(px + o), (__attribute__((address_space(3))) void*)S, 16, 0, 0);
-            if (TERMS == 3)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pxl + o), (__attribute__((address_space(3))) void*)(S + OPI), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pw + o), (__attribute__((address_space(3))) void*)(S + OP), 16, 0, 0);
-            if (TERMS == 3)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pwl + o), (__attribute__((address_space(3))) void*)(S + OP + OPI), 16, 0, 0);
-        }
-    };
-    struct Frags { bf8 xh[4], xl[4], wh[2], wl[2]; };
-    auto read_frags = [&](Frags& f, int slot, int g) {
-        const bf8* X = lds + slot * SLOT + (wm * 8 + g * 4 + kq) * 64 + li;
-        const bf8* W = lds + slot * SLOT + OP + ((wn >> 1) * 8 + g * 4 + kq) * 64 + (wn & 1) * 32 + li;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            f.xh[t] = X[t * 16];
-            if (TERMS == 3) f.xl[t] = X[OPI + t * 16];
-        }
-#pragma unroll
-        for (int n = 0; n < 2; ++n) {
-            f.wh[n] = W[n * 16];
-            if (TERMS == 3) f.wl[n] = W[OPI + n * 16];
-        }
-    };
-    f4 acc[4][2];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) acc[t][n] = (f4){0.f, 0.f, 0.f, 0.f};
-    auto mfma_group = [&](const Frags& f) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                if (TERMS == 3) {
-                    acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wl[n], f.xh[t], acc[t][n], 0, 0, 0);
-                    acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wh[n], f.xl[t], acc[t][n], 0, 0, 0);
-                }
-                acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wh[n], f.xh[t], acc[t][n], 0, 0, 0);
-            }
-    };
-    issue(0, 0);
-    wait_vmcnt_imm<0>();
-    wg_barrier();
-#pragma unroll 1
-    for (int s = 0; s < nsteps; ++s) {
-        const int cur = s & 1;
-        if (s + 1 < nsteps) issue(s + 1, cur ^ 1);      // the other slot: every wave finished reading it before the barrier that ended step s - 1
-        Frags f0, f1;
-        read_frags(f0, cur, 0);
-        read_frags(f1, cur, 1);
-        mfma_group(f0);
-        if (s * 8 + 4 < kov) mfma_group(f1);
-        wait_vmcnt_imm<0>();                            // step s + 1 landed (the only copy in flight)
-        wait_lgkmcnt0();
-        wg_barrier();
-    }
-    gemm_epilogue<4, 2, false>(a, acc, m0 + wm * 64 + li, n0 + wn * 32 + kq * 4);
-}
-
-template <int TERMS>
-int launch_presplit128_k64(const GemmArgs& a, const bf8* xhi, const bf8* xlo, int xko, int m_tiles, int n_tiles, hipStream_t st) {
-    constexpr int NIMG = (TERMS == 3) ? 2 : 1;
-    constexpr size_t LDS_BYTES = (size_t)2 * 2 * NIMG * 16 * 64 * 16;
-    static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-    auto kern = gemm_presplit128_k64_kernel<TERMS>;
-    if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS_BYTES, "gemm_presplit128_k64")) return rc;
-    dim3 grid(eg_cdiv(m_tiles, 2), eg_cdiv(n_tiles, 2), 1);
-    hipLaunchKernelGGL(kern, grid, dim3(512), LDS_BYTES, st, a, xhi, xlo, xko, m_tiles, n_tiles);
-    return eg_check_launch("gemm_presplit128_k64");
-}
-
 // Tile choice of the pre-split product.  Default policy (measured on the 4-lane headline and on tools/bench_ops.py):
 //   the policy of `presplit_tile_default` below (stand-alone: 64 x 64 up to 1024 workgroups; with the caller's shared-chip hint: 128 x 128 from 64).
-// EG_GEMM_TILE overrides it for A/B runs: "64" | "128x64" (4-slot ring, one workgroup per CU) | "128x64r3" (3-slot ring, two per CU) | "128" |
-// "128k64" (128 x 128 with 64-deep steps, two slots).
-enum PresplitTile { TILE_64 = 0, TILE_128x64 = 1, TILE_128x64_R3 = 2, TILE_128 = 3, TILE_64_R8 = 4, TILE_128x64_R6 = 5, TILE_128_R4 = 6, TILE_128_K64 = 7, TILE_AUTO = -1 };
+// EG_GEMM_TILE overrides it for A/B runs: "64" | "128".  Any other value is refused (TILE_BAD): the variants measured and rejected in earlier rounds
+// live in tools/experiments/, and a stale name must not silently measure the default.
+enum PresplitTile { TILE_64 = 0, TILE_128 = 1, TILE_AUTO = -1, TILE_BAD = -2 };
 int presplit_tile_override() {          // read per call (a tool / test switches it between launches; a captured graph keeps what it was captured with)
     const char* e = getenv("EG_GEMM_TILE");
     if (!e || !e[0]) return TILE_AUTO;
     if (!strcmp(e, "64")) return TILE_64;
-    if (!strcmp(e, "128x64")) return TILE_128x64;
-    if (!strcmp(e, "128x64r3")) return TILE_128x64_R3;
     if (!strcmp(e, "128")) return TILE_128;
-    if (!strcmp(e, "64r8")) return TILE_64_R8;            // deeper rings: more operand bytes in flight per CU (one workgroup per CU)
-    if (!strcmp(e, "128x64r6")) return TILE_128x64_R6;
-    if (!strcmp(e, "128r4")) return TILE_128_R4;
-    if (!strcmp(e, "128k64")) return TILE_128_K64;
-    return TILE_AUTO;
+    return TILE_BAD;
 }
 int presplit_tile_default(int m, int n, int shared_chip) {
     // Stand-alone (one stream, nothing else resident) the 64 x 64 tile is the faster one below ~1000 workgroups: at the headline's 2176-row products
@@ -939,39 +792,31 @@ int presplit_tile_default(int m, int n, int shared_chip) {
 int dispatch_presplit(const GemmArgs& a, const bf8* xhi, const bf8* xlo, int xko, int precision, hipStream_t st, EgProfScope* prof = nullptr, int shared_chip = 0) {
     const int mt = eg_cdiv(a.M, 64), nt = eg_cdiv(a.N, 64);
     int tile = presplit_tile_override();
-    if (tile == TILE_AUTO) tile = presplit_tile_default(a.M, a.N, shared_chip);
-    if (a.xs_steps) tile = (tile == TILE_128 || tile == TILE_128_R4 || tile == TILE_128_K64) ? TILE_128 : TILE_64;      // causal two-tap product: the two default tiles
-    if (prof) {
-        const int tm = (tile == TILE_64 || tile == TILE_64_R8) ? 1 : 2, tn = (tile == TILE_128 || tile == TILE_128_R4 || tile == TILE_128_K64) ? 2 : 1;
-        prof->workgroups(eg_cdiv(mt, tm) * eg_cdiv(nt, tn));
+    if (tile == TILE_BAD) {
+        eg_set_error("EG_GEMM_TILE=\"%s\": accepted values are \"64\" and \"128\" (unset or empty: automatic); the retired tile variants are in tools/experiments/README.md",
+                     getenv("EG_GEMM_TILE"));
+        return EG_ERR_BAD_ARG;
     }
+    if (tile == TILE_AUTO) tile = presplit_tile_default(a.M, a.N, shared_chip);
+    if (prof) prof->workgroups(tile == TILE_128 ? eg_cdiv(mt, 2) * eg_cdiv(nt, 2) : mt * nt);
     const bool x3 = precision == EG_PREC_BF16X3;
     dim3 grid(mt, nt, 1);
-    if (a.xs_steps) {
+    if (a.xs_steps) {                       // causal two-tap product
         if (a.gate || a.drop.thr) { eg_set_error("shifted pre-split product: no training epilogue"); return EG_ERR_UNSUPPORTED; }
         if (tile == TILE_128)
-            return x3 ? launch_presplit128<3, 3, false, true>(a, xhi, xlo, xko, mt, nt, st) : launch_presplit128<1, 3, false, true>(a, xhi, xlo, xko, mt, nt, st);
-        return x3 ? launch_presplit<3, 32, 4, 2, false, true>(a, xhi, xlo, xko, grid, st) : launch_presplit<1, 32, 4, 2, false, true>(a, xhi, xlo, xko, grid, st);
+            return x3 ? launch_presplit128<3, false, true>(a, xhi, xlo, xko, mt, nt, st) : launch_presplit128<1, false, true>(a, xhi, xlo, xko, mt, nt, st);
+        return x3 ? launch_presplit<3, false, true>(a, xhi, xlo, xko, grid, st) : launch_presplit<1, false, true>(a, xhi, xlo, xko, grid, st);
     }
-    if (a.gate || a.drop.thr) {             // the training epilogue (ReLU-backward gate / Dropout): split-bf16 only, the two default tiles
+    if (a.gate || a.drop.thr) {             // the training epilogue (ReLU-backward gate / Dropout): split-bf16 only
         if (!x3) { eg_set_error("pre-split product with a training epilogue: bf16x3 only"); return EG_ERR_UNSUPPORTED; }
-        if (tile == TILE_128 || tile == TILE_128_K64) return launch_presplit128<3, 3, true>(a, xhi, xlo, xko, mt, nt, st);
-        return launch_presplit<3, 32, 4, 2, true>(a, xhi, xlo, xko, grid, st);
+        if (tile == TILE_128) return launch_presplit128<3, true>(a, xhi, xlo, xko, mt, nt, st);
+        return launch_presplit<3, true>(a, xhi, xlo, xko, grid, st);
     }
-    switch (tile) {
-        case TILE_128: return x3 ? launch_presplit128<3>(a, xhi, xlo, xko, mt, nt, st) : launch_presplit128<1>(a, xhi, xlo, xko, mt, nt, st);
-        case TILE_128x64: return x3 ? launch_presplit<3, 32, 4, 4>(a, xhi, xlo, xko, grid, st) : launch_presplit<1, 32, 4, 4>(a, xhi, xlo, xko, grid, st);
-        case TILE_128_K64: return x3 ? launch_presplit128_k64<3>(a, xhi, xlo, xko, mt, nt, st) : launch_presplit128_k64<1>(a, xhi, xlo, xko, mt, nt, st);
-        case TILE_128_R4: return x3 ? launch_presplit128<3, 4>(a, xhi, xlo, xko, mt, nt, st) : launch_presplit128<1, 4>(a, xhi, xlo, xko, mt, nt, st);
-        case TILE_64_R8: return x3 ? launch_presplit<3, 32, 8>(a, xhi, xlo, xko, grid, st) : launch_presplit<1, 32, 8>(a, xhi, xlo, xko, grid, st);
-        case TILE_128x64_R6: return x3 ? launch_presplit<3, 32, 6, 4>(a, xhi, xlo, xko, grid, st) : launch_presplit<1, 32, 6, 4>(a, xhi, xlo, xko, grid, st);
-        case TILE_128x64_R3: return x3 ? launch_presplit<3, 32, 3, 4>(a, xhi, xlo, xko, grid, st) : launch_presplit<1, 32, 3, 4>(a, xhi, xlo, xko, grid, st);
-        default: break;
-    }
+    if (tile == TILE_128) return x3 ? launch_presplit128<3>(a, xhi, xlo, xko, mt, nt, st) : launch_presplit128<1>(a, xhi, xlo, xko, mt, nt, st);
     // 64 x 64: 32-deep steps, 4 slots (64 KB: two workgroups per CU).  Measured and dropped in round 1 (2176-row products, bf16x3):
     // 64-deep steps with 4 slots (16 % slower), 5 slots (no change), 8 slots (one workgroup per CU: the 272-tile grids
     // then need two passes, 50 % slower), register-staged copies instead of LDS-DMA (30 % slower).
-    return x3 ? launch_presplit<3, 32, 4>(a, xhi, xlo, xko, grid, st) : launch_presplit<1, 32, 4>(a, xhi, xlo, xko, grid, st);
+    return x3 ? launch_presplit<3>(a, xhi, xlo, xko, grid, st) : launch_presplit<1>(a, xhi, xlo, xko, grid, st);
 }
 
 // ---- products of few rows (one clip: M <= 64 by default) ------------------------------------------------------------------
@@ -1207,7 +1052,7 @@ int egi_linear(const EgiLinear& p, hipStream_t st) {
             const int nsplit = eg_cdiv(a.K, a.k_per_split);
             prof.workgroups(mt * eg_cdiv(a.N, 64) * nsplit);
             dim3 grid(mt, eg_cdiv(a.N, 64), nsplit);
-            const int rc = (p.precision == EG_PREC_BF16X3) ? launch_presplit<3, 32, 4>(a, xhi, xlo, xko, grid, st) : launch_presplit<1, 32, 4>(a, xhi, xlo, xko, grid, st);
+            const int rc = (p.precision == EG_PREC_BF16X3) ? launch_presplit<3>(a, xhi, xlo, xko, grid, st) : launch_presplit<1>(a, xhi, xlo, xko, grid, st);
             if (rc) return rc;
             hipLaunchKernelGGL(splitk_reduce_kernel, dim3(eg_cdiv(a.M * a.N, 256)), dim3(256), 0, st, a, nsplit);
             return eg_check_launch("splitk_reduce");

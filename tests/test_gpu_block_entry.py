@@ -108,63 +108,3 @@ def test_generator_fuse_se_on_matches_off(prec):
     e = clip_rel_l2(poses[True], poses[False])
     print(f"generator {prec}: fuse_se on vs off, per-clip rel_l2 {e:.3e} (bound {POSE_TOL[prec]:.1e})")
     assert e < POSE_TOL[prec]
-
-
-class _grid:
-    """EG_CONV_GRID for the calls inside the block (the library reads it per call): '0' = one workgroup per tile, N = N persistent workgroups."""
-
-    def __init__(self, value):
-        self.value = value
-
-    def __enter__(self):
-        import os
-        self.old = os.environ.pop("EG_CONV_GRID", None)
-        if self.value is not None:
-            os.environ["EG_CONV_GRID"] = str(self.value)
-
-    def __exit__(self, *exc):
-        import os
-        os.environ.pop("EG_CONV_GRID", None)
-        if self.old is not None:
-            os.environ["EG_CONV_GRID"] = self.old
-
-
-# 64 -> 64 at 20 x 37: 3 x 2 tiles per clip, 18 in all: 8 workgroups walk 3 or 2 tiles each, 24 leave six without a tile; the stride-2 entries at
-# 37 x 69 -> 19 x 35: 10 x 2 tiles per clip (2-row tiles); final_conv1 128 -> 34 with the NCHW epilogue at 20 x 31: 5 tiles per clip
-PERSIST_CASES = [(64, 64, 1, 20, 37, False), (32, 64, 2, 37, 69, False), (64, 128, 2, 37, 69, False), (128, 34, 1, 20, 31, True)]
-
-
-@pytest.mark.parametrize("prec", ["bf16x3", "bf16"])
-@pytest.mark.parametrize("cin,cout,stride,H,W,nchw", PERSIST_CASES)
-def test_persistent_walk_is_bitwise_the_tile_per_workgroup_launch(cin, cout, stride, H, W, nchw, prec):
-    from emotiongestures_amd import ops
-    B = 3
-    x = T(f"px{cin}", (B, H, W, cin), -1, 1).to(dev())
-    w = T(f"pw{cin}{cout}", (cout, cin, 3, 3), -0.1, 0.1)
-    bias, scale, shift = T("b", (cout,), -0.2, 0.2), T("s", (cout,), 0.5, 1.5), T("t", (cout,), -0.3, 0.3)
-    packed = ops.conv3x3_pack(w, bias, scale, shift, dev())
-
-    def run(grid):
-        with _grid(grid):
-            y, gap = ops.conv3x3(x, w, stride=stride, relu=True, nchw_out=nchw, want_gap=True, precision=prec, packed=packed)
-        torch.cuda.synchronize()
-        return y, gap
-
-    y0, g0 = run(0)
-    assert torch.isfinite(y0).all() and float(y0.abs().max()) > 0
-    for grid in (8, 24, None):
-        y, g = run(grid)
-        assert torch.equal(y, y0), grid
-        assert torch.equal(g, g0), grid
-
-
-@pytest.mark.parametrize("prec", ["bf16x3", "bf16"])
-def test_persistent_walk_carries_the_shortcut_pre_phase(prec):
-    """layer2.0 in the fused flow (conv2 = the 64 -> 64 kernel with the shortcut steps first in every tile's sequence): 3 clips, 19 x 35 output."""
-    blk, x, _ref = _case("layer2", 37, 69, True)
-    outs = []
-    for grid in (0, 8, 24, None):
-        with _grid(grid):
-            outs.append(_fused(blk, x, prec))
-    for o in outs[1:]:
-        assert torch.equal(o, outs[0])

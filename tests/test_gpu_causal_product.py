@@ -153,33 +153,3 @@ def test_add_rows_split_images_and_products():
         e = rel_l2(y_img.cpu().numpy(), y_f32.cpu().numpy())
         print(f"N={N}: images vs fp32 input rel-L2 {e:.3e}")
         assert e < 3e-5             # tests/test_gpu_kernels.py TOL["bf16x3"]
-
-
-@pytest.mark.parametrize("prec", ["bf16x3", "bf16"])
-@pytest.mark.parametrize("M,N,K", [(136, 512, 512), (2176, 128, 2048), (200, 192, 96)])
-def test_presplit128_64_deep_steps_bitwise_equal(prec, M, N, K, monkeypatch):
-    """EG_GEMM_TILE=128k64 (128 x 128 tile, 64-deep steps, two-slot ring) keeps the K order of every output element: bitwise the 32-deep
-    128 x 128 kernel, with bias + residual + ReLU; K = 96 ends on an odd 32 (half a last step), 200 x 192 has odd tile counts on both axes."""
-    from emotiongestures_amd import _lib as L
-    from emotiongestures_amd import ops
-    from emotiongestures_amd.engine import _ptr, _stream
-    lib = L.load()
-    x, w = T("kx", (M, K)), T("kw", (N, K), -0.1, 0.1)
-    bias, res = T("kb", (N,)), T("kr", (M, N))
-    xd, rd = x.to(dev()), res.to(dev())
-    wp, npad, kpad = ops.pack_linear_weight(w, dev())
-    bp = torch.zeros(npad, device=dev())
-    bp[:N] = bias.to(dev())
-    img = split_images(xd, M, K)
-    outs = {}
-    for tile in ("128", "128k64"):
-        monkeypatch.setenv("EG_GEMM_TILE", tile)
-        y = torch.full((M, N), float("nan"), device=dev())
-        L.check(lib.eg_linear_presplit(_ptr(img), K, _ptr(wp), kpad, _ptr(bp), _ptr(rd), None, N, _ptr(y), N, M, N, K, 1,
-                                       L.precision_code(prec), _stream(dev())), "eg_linear_presplit " + tile)
-        torch.cuda.synchronize()
-        outs[tile] = y
-    monkeypatch.delenv("EG_GEMM_TILE")
-    ref = torch.relu(x.double() @ w.double().T + bias.double() + res.double())
-    assert rel_l2(outs["128"].cpu().numpy(), ref.numpy()) < {"bf16x3": 3e-5, "bf16": 2e-2}[prec]
-    assert torch.equal(outs["128k64"], outs["128"])

@@ -249,9 +249,9 @@ def test_linear_presplit_matches_fp64(prec, M, N, K):
 @pytest.mark.parametrize("M,N,K", [(2176, 512, 512), (2176, 2048, 512), (2176, 512, 2048),     # the headline's transformer products
                                    (200, 192, 96), (8390, 320, 1024), (64, 64, 32)])          # odd tile counts, a short K, a single tile
 def test_linear_presplit_tile_variants_are_bitwise_equal(prec, M, N, K, monkeypatch):
-    """The workgroup tile of the pre-split product is a scheduling choice: every variant (64 x 64, 128 x 64 with a 4- or 3-slot ring,
-    128 x 128; forced through EG_GEMM_TILE, which the library reads per call) accumulates each output element over K in the same order with
-    the same three split terms, so the results are bitwise identical -- to each other and to eg_linear's in-kernel split."""
+    """The workgroup tile of the pre-split product is a scheduling choice: both tiles (64 x 64 and 128 x 128; forced through EG_GEMM_TILE,
+    which the library reads per call) accumulate each output element over K in the same order with the same three split terms, so the
+    results are bitwise identical."""
     from emotiongestures_amd import _lib as L
     from emotiongestures_amd import ops
     from emotiongestures_amd.engine import _ptr, _stream
@@ -265,7 +265,7 @@ def test_linear_presplit_tile_variants_are_bitwise_equal(prec, M, N, K, monkeypa
     img = torch.empty(2 * mt * 64 * kp, dtype=torch.int16, device=dev())
     L.check(lib.eg_split_tiles(_ptr(xd), K, M, K, _ptr(img), _stream(dev())), "eg_split_tiles")
     outs = {}
-    for tile in ("64", "64r8", "128x64", "128x64r3", "128x64r6", "128", "128r4"):
+    for tile in ("64", "128"):
         monkeypatch.setenv("EG_GEMM_TILE", tile)
         y = torch.full((M, N), float("nan"), device=dev())
         L.check(lib.eg_linear_presplit(_ptr(img), K, _ptr(wp), kpad, _ptr(bp), _ptr(rd), None, N, _ptr(y), N, M, N, K, 1,
@@ -275,8 +275,41 @@ def test_linear_presplit_tile_variants_are_bitwise_equal(prec, M, N, K, monkeypa
     monkeypatch.delenv("EG_GEMM_TILE")
     ref = torch.relu(x.double() @ w.double().T + bias.double() + res.double())
     assert rel_l2(outs["64"].cpu().numpy(), ref.numpy()) < TOL[prec]
-    for tile in ("64r8", "128x64", "128x64r3", "128x64r6", "128", "128r4"):
-        assert torch.equal(outs[tile], outs["64"]), tile
+    assert torch.equal(outs["128"], outs["64"])
+
+
+def test_linear_presplit_refuses_a_retired_tile_name(monkeypatch):
+    """EG_GEMM_TILE accepts "64" and "128" (unset or empty: the automatic policy).  The name of a tile variant that was measured, rejected and
+    moved to tools/experiments/ must not silently run the default: eg_linear_presplit returns an error that names the accepted values before it
+    launches anything (the NaN-filled output of the single-tile product stays NaN), and the same call succeeds once the variable is gone."""
+    from emotiongestures_amd import _lib as L
+    from emotiongestures_amd import ops
+    from emotiongestures_amd.engine import _ptr, _stream
+    lib = L.load()
+    M, N, K = 64, 64, 32
+    x, w = T("rx", (M, K)), T("rw", (N, K), -0.1, 0.1)
+    xd = x.to(dev())
+    wp, npad, kpad = ops.pack_linear_weight(w, dev())
+    bp = torch.zeros(npad, device=dev())
+    img = torch.empty(2 * 64 * 64, dtype=torch.int16, device=dev())
+    L.check(lib.eg_split_tiles(_ptr(xd), K, M, K, _ptr(img), _stream(dev())), "eg_split_tiles")
+    y = torch.full((M, N), float("nan"), device=dev())
+
+    def run():
+        rc = lib.eg_linear_presplit(_ptr(img), K, _ptr(wp), kpad, _ptr(bp), None, None, N, _ptr(y), N, M, N, K, 0,
+                                    L.precision_code("bf16x3"), _stream(dev()))
+        torch.cuda.synchronize()
+        return rc
+
+    for tile in ("128x64", "128k64"):
+        monkeypatch.setenv("EG_GEMM_TILE", tile)
+        assert run() != 0, tile
+        msg = lib.eg_last_error().decode()
+        assert '"64"' in msg and '"128"' in msg and tile in msg and "tools/experiments/README.md" in msg, msg
+        assert torch.isnan(y).all(), tile
+    monkeypatch.delenv("EG_GEMM_TILE")
+    assert run() == 0
+    assert rel_l2(y.cpu().numpy(), (x.double() @ w.double().T).numpy()) < TOL["bf16x3"]
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "bf16"])

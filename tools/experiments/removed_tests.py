@@ -1,5 +1,5 @@
-"""Tests of the experiments in this directory as they stood when the kernels were in the product library (round 5).  Not collected by pytest
-(not under tests/); they need the kernels pasted back as the README says."""
+"""Tests of the experiments in this directory as they stood when the kernels were in the product library (rounds 5 to 8).  Not collected by pytest
+(not under tests/); they need the kernels pasted or patched back as the README says."""
 
 def test_conv32_teams_kernel_is_bitwise_the_persistent_kernel(monkeypatch):
     """csrc/conv.hip conv3x3_c32_teams_kernel (EG_CONV32_TEAMS = 2 | 3: teams of 4 waves per workgroup sharing ONE LDS copy of the 9 taps' weights,
@@ -59,3 +59,99 @@ def test_fused_ffn_slab_kernel_matches_the_two_launch_path(monkeypatch):
     assert torch.equal(one, ref)
     assert torch.equal(four, four_again) and not torch.equal(four, ref)
     assert clip_rel_l2(four.cpu().numpy(), ref.cpu().numpy()) < 2e-5          # another summation order over the hidden chunks, six FFNs deep (measured 8e-6)
+
+
+# ---- round 10: the convolution's (tile, chunk) walk (conv_tile_walk.patch); from tests/test_gpu_block_entry.py, whose T, dev, _case and _fused they use ----
+
+class _grid:
+    """EG_CONV_GRID for the calls inside the block (the library reads it per call): '0' = one workgroup per tile, N = N persistent workgroups."""
+
+    def __init__(self, value):
+        self.value = value
+
+    def __enter__(self):
+        import os
+        self.old = os.environ.pop("EG_CONV_GRID", None)
+        if self.value is not None:
+            os.environ["EG_CONV_GRID"] = str(self.value)
+
+    def __exit__(self, *exc):
+        import os
+        os.environ.pop("EG_CONV_GRID", None)
+        if self.old is not None:
+            os.environ["EG_CONV_GRID"] = self.old
+
+
+# 64 -> 64 at 20 x 37: 3 x 2 tiles per clip, 18 in all: 8 workgroups walk 3 or 2 tiles each, 24 leave six without a tile; the stride-2 entries at
+# 37 x 69 -> 19 x 35: 10 x 2 tiles per clip (2-row tiles); final_conv1 128 -> 34 with the NCHW epilogue at 20 x 31: 5 tiles per clip
+PERSIST_CASES = [(64, 64, 1, 20, 37, False), (32, 64, 2, 37, 69, False), (64, 128, 2, 37, 69, False), (128, 34, 1, 20, 31, True)]
+
+
+@pytest.mark.parametrize("prec", ["bf16x3", "bf16"])
+@pytest.mark.parametrize("cin,cout,stride,H,W,nchw", PERSIST_CASES)
+def test_persistent_walk_is_bitwise_the_tile_per_workgroup_launch(cin, cout, stride, H, W, nchw, prec):
+    from emotiongestures_amd import ops
+    B = 3
+    x = T(f"px{cin}", (B, H, W, cin), -1, 1).to(dev())
+    w = T(f"pw{cin}{cout}", (cout, cin, 3, 3), -0.1, 0.1)
+    bias, scale, shift = T("b", (cout,), -0.2, 0.2), T("s", (cout,), 0.5, 1.5), T("t", (cout,), -0.3, 0.3)
+    packed = ops.conv3x3_pack(w, bias, scale, shift, dev())
+
+    def run(grid):
+        with _grid(grid):
+            y, gap = ops.conv3x3(x, w, stride=stride, relu=True, nchw_out=nchw, want_gap=True, precision=prec, packed=packed)
+        torch.cuda.synchronize()
+        return y, gap
+
+    y0, g0 = run(0)
+    assert torch.isfinite(y0).all() and float(y0.abs().max()) > 0
+    for grid in (8, 24, None):
+        y, g = run(grid)
+        assert torch.equal(y, y0), grid
+        assert torch.equal(g, g0), grid
+
+
+@pytest.mark.parametrize("prec", ["bf16x3", "bf16"])
+def test_persistent_walk_carries_the_shortcut_pre_phase(prec):
+    """layer2.0 in the fused flow (conv2 = the 64 -> 64 kernel with the shortcut steps first in every tile's sequence): 3 clips, 19 x 35 output."""
+    blk, x, _ref = _case("layer2", 37, 69, True)
+    outs = []
+    for grid in (0, 8, 24, None):
+        with _grid(grid):
+            outs.append(_fused(blk, x, prec))
+    for o in outs[1:]:
+        assert torch.equal(o, outs[0])
+
+
+# ---- round 10: the 128 x 128 tile with 64-deep steps (gemm_presplit_tiles.patch); from tests/test_gpu_causal_product.py, whose T, dev and
+# split_images it uses.  The same patch brings back the "64r8", "128x64", "128x64r3", "128x64r6" and "128r4" entries of the tile list of
+# tests/test_gpu_kernels.py::test_linear_presplit_tile_variants_are_bitwise_equal ----
+
+@pytest.mark.parametrize("prec", ["bf16x3", "bf16"])
+@pytest.mark.parametrize("M,N,K", [(136, 512, 512), (2176, 128, 2048), (200, 192, 96)])
+def test_presplit128_64_deep_steps_bitwise_equal(prec, M, N, K, monkeypatch):
+    """EG_GEMM_TILE=128k64 (128 x 128 tile, 64-deep steps, two-slot ring) keeps the K order of every output element: bitwise the 32-deep
+    128 x 128 kernel, with bias + residual + ReLU; K = 96 ends on an odd 32 (half a last step), 200 x 192 has odd tile counts on both axes."""
+    from emotiongestures_amd import _lib as L
+    from emotiongestures_amd import ops
+    from emotiongestures_amd.engine import _ptr, _stream
+    lib = L.load()
+    x, w = T("kx", (M, K)), T("kw", (N, K), -0.1, 0.1)
+    bias, res = T("kb", (N,)), T("kr", (M, N))
+    xd, rd = x.to(dev()), res.to(dev())
+    wp, npad, kpad = ops.pack_linear_weight(w, dev())
+    bp = torch.zeros(npad, device=dev())
+    bp[:N] = bias.to(dev())
+    img = split_images(xd, M, K)
+    outs = {}
+    for tile in ("128", "128k64"):
+        monkeypatch.setenv("EG_GEMM_TILE", tile)
+        y = torch.full((M, N), float("nan"), device=dev())
+        L.check(lib.eg_linear_presplit(_ptr(img), K, _ptr(wp), kpad, _ptr(bp), _ptr(rd), None, N, _ptr(y), N, M, N, K, 1,
+                                       L.precision_code(prec), _stream(dev())), "eg_linear_presplit " + tile)
+        torch.cuda.synchronize()
+        outs[tile] = y
+    monkeypatch.delenv("EG_GEMM_TILE")
+    ref = torch.relu(x.double() @ w.double().T + bias.double() + res.double())
+    assert rel_l2(outs["128"].cpu().numpy(), ref.numpy()) < {"bf16x3": 3e-5, "bf16": 2e-2}[prec]
+    assert torch.equal(outs["128k64"], outs["128"])
