@@ -180,7 +180,6 @@ SIGNATURES = {
     "eg_conv3x3_wgrad": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
     "eg_im2col3x3": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "eg_subsample": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "eg_im2col1d": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "eg_conv1d_cl_forward": (C.c_int, [_P, _P, _P, _P] + [_I] * 9 + [_P]),
     "eg_conv1d_cl_backward_input": (C.c_int, [_P, _P, _P, _P] + [_I] * 9 + [_P]),
     "eg_conv1d_cl_backward_weight_workspace_floats": (_L, [_I] * 7),
@@ -220,7 +219,6 @@ SIGNATURES = {
     "eg_seg_dot": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P]),
     "eg_se_scale": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "eg_layernorm_backward": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, C.c_float, _P]),
-    "eg_attention_backward": (C.c_int, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "eg_attention_train": (C.c_int, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, C.c_float, C.c_uint32, C.c_uint64, _P, _P]),
     "eg_attention_backward_train": (C.c_int, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_float, C.c_uint32,
                                               C.c_uint64, _P, _P]),

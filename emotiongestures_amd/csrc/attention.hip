@@ -457,11 +457,11 @@ int launch_att_bwd(const float* q, int ldq, const float* k, int ldk, const float
     const dim3 grid(heads, batch);
     if (dr.thr) {
         auto kern = attention_bwd_mfma_kernel<KT, QC, true>;
-        if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, "eg_attention_backward")) return rc;
+        if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, "eg_attention_backward_train")) return rc;
         hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, q, ldq, k, ldk, v, ldv, p, dout, ldo, dq, lddq, dk, lddk, dv, lddv, heads, lq, lk, inv_temp, dr);
     } else {
         auto kern = attention_bwd_mfma_kernel<KT, QC, false>;
-        if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, "eg_attention_backward")) return rc;
+        if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, "eg_attention_backward_train")) return rc;
         hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, q, ldq, k, ldk, v, ldv, p, dout, ldo, dq, lddq, dk, lddk, dv, lddv, heads, lq, lk, inv_temp, dr);
     }
     return eg_check_launch("attention_backward");

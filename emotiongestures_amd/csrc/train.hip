@@ -278,38 +278,6 @@ __global__ __launch_bounds__(256) void subsample_kernel(const float* __restrict_
         }
     }
 }
-// 1-D channels-last: x [B, L, C] -> col [B*Lout, k*C], position l*stride + j*dil - pad_left
-__global__ __launch_bounds__(256) void im2col1d_kernel(const float* __restrict__ x, float* __restrict__ col, int B, int L, int C, int Lout,
-                                                       int k, int stride, int pad_left, int dil) {
-    const size_t total = (size_t)B * Lout * k * C;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C);
-        size_t r = i / C;
-        const int j = (int)(r % k);
-        r /= k;
-        const int lo = (int)(r % Lout), b = (int)(r / Lout);
-        const int l = lo * stride + j * dil - pad_left;
-        col[i] = (l >= 0 && l < L) ? x[((size_t)b * L + l) * C + c] : 0.f;
-    }
-}
-__global__ __launch_bounds__(256) void col2im1d_kernel(const float* __restrict__ col, float* __restrict__ dx, int B, int L, int C, int Lout,
-                                                       int k, int stride, int pad_left, int dil) {
-    const size_t total = (size_t)B * L * C;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C);
-        size_t r = i / C;
-        const int l = (int)(r % L), b = (int)(r / L);
-        float s = 0.f;
-        for (int j = 0; j < k; ++j) {
-            const int t = l + pad_left - j * dil;
-            if (t < 0 || t % stride) continue;
-            const int lo = t / stride;
-            if (lo >= Lout) continue;
-            s += col[(((size_t)b * Lout + lo) * k + j) * C + c];
-        }
-        dx[i] = s;
-    }
-}
 
 // ---- column reductions over rows: two deterministic levels ---------------------------------------------------------------
 // level 1: block (bx, by) sums rows [by*rows_per, ...) of 64 columns -> part[by][2][C]
@@ -1140,71 +1108,6 @@ __global__ __launch_bounds__(256) void ln_bwd_ex_kernel(const float* __restrict_
     }
 }
 
-// ---- attention backward (Full_model/Modules.py:13-23), one workgroup per (head, clip), Lq, Lk <= 64 -------------------------
-// given P (the forward's probabilities) and dO:  dV = P^T dO;  dP = dO V^T;  dS = P * (dP - rowsum(dP * P));
-// dQ = dS K / temp;  dK = dS^T Q / temp
-__global__ __launch_bounds__(256) void attention_bwd_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k, int ldk,
-                                                            const float* __restrict__ v, int ldv, const float* __restrict__ p,
-                                                            const float* __restrict__ dout, int ldo, float* __restrict__ dq, int lddq,
-                                                            float* __restrict__ dk, int lddk, float* __restrict__ dv, int lddv, int H, int Lq,
-                                                            int Lk, float inv_temp) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    float* Qs = sm;                     // [Lq][65]
-    float* Ks = Qs + Lq * 65;           // [Lk][65]
-    float* Vs = Ks + Lk * 65;           // [Lk][65]
-    float* Ds = Vs + Lk * 65;           // dO [Lq][65]
-    float* Ps = Ds + Lq * 65;           // P  [Lq][Lk+1]
-    float* Ss = Ps + Lq * (Lk + 1);     // dS [Lq][Lk+1]
-    for (int i = tid; i < Lq * 64; i += 256) {
-        const int r = i >> 6, c = i & 63;
-        Qs[r * 65 + c] = q[((size_t)b * Lq + r) * ldq + h * 64 + c];
-        Ds[r * 65 + c] = dout[((size_t)b * Lq + r) * ldo + h * 64 + c];
-    }
-    for (int i = tid; i < Lk * 64; i += 256) {
-        const int r = i >> 6, c = i & 63;
-        Ks[r * 65 + c] = k[((size_t)b * Lk + r) * ldk + h * 64 + c];
-        Vs[r * 65 + c] = v[((size_t)b * Lk + r) * ldv + h * 64 + c];
-    }
-    for (int i = tid; i < Lq * Lk; i += 256) {
-        const int r = i / Lk, c = i - r * Lk;
-        Ps[r * (Lk + 1) + c] = p[(((size_t)b * H + h) * Lq + r) * Lk + c];
-    }
-    __syncthreads();
-    // dP
-    for (int i = tid; i < Lq * Lk; i += 256) {
-        const int r = i / Lk, c = i - r * Lk;
-        float s = 0.f;
-        for (int d = 0; d < 64; ++d) s += Ds[r * 65 + d] * Vs[c * 65 + d];
-        Ss[r * (Lk + 1) + c] = s;
-    }
-    __syncthreads();
-    // dS = P * (dP - sum_k dP*P), one wave per row
-    const int wave = tid >> 6, lane = tid & 63;
-    for (int r = wave; r < Lq; r += 4) {
-        float s = 0.f;
-        for (int c = lane; c < Lk; c += 64) s += Ss[r * (Lk + 1) + c] * Ps[r * (Lk + 1) + c];
-        s = wave_sum(s);
-        for (int c = lane; c < Lk; c += 64) Ss[r * (Lk + 1) + c] = Ps[r * (Lk + 1) + c] * (Ss[r * (Lk + 1) + c] - s);
-    }
-    __syncthreads();
-    for (int i = tid; i < Lq * 64; i += 256) {           // dQ
-        const int r = i >> 6, d = i & 63;
-        float s = 0.f;
-        for (int c = 0; c < Lk; ++c) s += Ss[r * (Lk + 1) + c] * Ks[c * 65 + d];
-        dq[((size_t)b * Lq + r) * lddq + h * 64 + d] = s * inv_temp;
-    }
-    for (int i = tid; i < Lk * 64; i += 256) {           // dK, dV
-        const int c = i >> 6, d = i & 63;
-        float s = 0.f, t = 0.f;
-        for (int r = 0; r < Lq; ++r) {
-            s += Ss[r * (Lk + 1) + c] * Qs[r * 65 + d];
-            t += Ps[r * (Lk + 1) + c] * Ds[r * 65 + d];
-        }
-        dk[((size_t)b * Lk + c) * lddk + h * 64 + d] = s * inv_temp;
-        dv[((size_t)b * Lk + c) * lddv + h * 64 + d] = t;
-    }
-}
 
 // ---- losses (one workgroup; sums in fixed order) -----------------------------------------------------------------------------
 // smooth-L1 (nn.SmoothL1Loss / F.smooth_l1_loss, mean reduction, beta): loss = mean(|d|<beta ? 0.5 d^2/beta : |d| - 0.5 beta)
@@ -1568,17 +1471,6 @@ extern "C" int eg_subsample(const float* x, float* y, int32_t batch, int32_t h, 
     else
         hipLaunchKernelGGL(subsample_kernel, grid1(total, 65536), dim3(256), 0, ST, x, y, batch, h, w, c, ho, wo, stride, backward);
     return eg_check_launch("subsample");
-}
-extern "C" int eg_im2col1d(const float* x, float* col, int32_t batch, int32_t len, int32_t c, int32_t k, int32_t stride, int32_t pad_left,
-                           int32_t dilation, int32_t lout, int32_t backward, void* stream) {
-    EG_REQUIRE(x && col && batch > 0 && len > 0 && c > 0 && k > 0 && stride > 0 && dilation > 0 && lout > 0, EG_ERR_BAD_ARG, "eg_im2col1d: bad argument");
-    if (!backward)
-        hipLaunchKernelGGL(im2col1d_kernel, grid1((size_t)batch * lout * k * c, 65536), dim3(256), 0, ST, x, col, batch, len, c, lout, k, stride,
-                           pad_left, dilation);
-    else
-        hipLaunchKernelGGL(col2im1d_kernel, grid1((size_t)batch * len * c, 65536), dim3(256), 0, ST, x, col, batch, len, c, lout, k, stride, pad_left,
-                           dilation);
-    return eg_check_launch("im2col1d");
 }
 
 namespace {
@@ -1959,19 +1851,6 @@ extern "C" int eg_layernorm_backward_ex(const float* x, const float* dy, const f
     return eg_check_launch("layernorm_backward_ex_fold");
 }
 
-extern "C" int eg_attention_backward(const float* q, int32_t ldq, const float* k, int32_t ldk, const float* v, int32_t ldv, const float* attn,
-                                     const float* dout, int32_t ldo, float* dq, int32_t lddq, float* dk, int32_t lddk, float* dv, int32_t lddv,
-                                     int32_t batch, int32_t heads, int32_t lq, int32_t lk, int32_t dk_dim, void* stream) {
-    EG_REQUIRE(q && k && v && attn && dout && dq && dk && dv && batch > 0 && heads > 0 && lq > 0 && lk > 0, EG_ERR_BAD_ARG,
-               "eg_attention_backward: bad argument");
-    EG_REQUIRE(dk_dim == 64, EG_ERR_UNSUPPORTED, "eg_attention_backward: d_k=%d", dk_dim);
-    const size_t smem = sizeof(float) * ((size_t)2 * lq * 65 + (size_t)2 * lk * 65 + (size_t)2 * lq * (lk + 1));
-    EG_REQUIRE(smem <= 160 * 1024, EG_ERR_UNSUPPORTED, "eg_attention_backward: Lq=%d Lk=%d needs %zu B of LDS", lq, lk, smem);
-    if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(attention_bwd_kernel), smem, "eg_attention_backward")) return rc;
-    hipLaunchKernelGGL(attention_bwd_kernel, dim3(heads, batch), dim3(256), smem, ST, q, ldq, k, ldk, v, ldv, attn, dout, ldo, dq, lddq, dk, lddk, dv,
-                       lddv, heads, lq, lk, 1.0f / sqrtf((float)dk_dim));
-    return eg_check_launch("attention_backward");
-}
 
 // loss[0] = scale * mean smooth_l1(pred, target; beta);  dpred (optional) = d loss / d pred.  workspace >= 1024 floats.
 extern "C" int eg_smooth_l1(const float* pred, const float* target, float* loss, float* dpred, int64_t n, float beta, float scale, float* workspace,

@@ -9,7 +9,7 @@ Everything is fp32 (EG_PREC_F32: v_mfma_f32_16x16x4_f32) -- gradient parity with
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -552,94 +552,323 @@ S2_DGRAD = __import__("os").environ.get("EG_S2_DGRAD", "1") != "0"      # False:
 S2_WGRAD = __import__("os").environ.get("EG_S2_WGRAD", "1") != "0"      # False: stride-2 weight gradients on the fp32 implicit GEMM (A/B switch)
 
 
+class ConvRoute(NamedTuple):
+    """The kernels one conv3x3 call runs, decided once at forward time by `conv3x3_route` (the table: DESIGN.md section 8)."""
+    forward: str            # sq_in_affine | sq | nhwc | channel_major | stem | im2col
+    wgrad: str              # mfma_in_affine | mfma | mfma_padded | gather_mfma | implicit_gemm | im2col
+    dgrad: str              # rotated | rotated_padded | s2 | col2im | none (no input gradient wanted)
+    gap_planes: int         # pooling partials the forward emits: 0, 1 (sums: [B, tiles, C]) or 2 (sums and squares: [2, B, tiles, C])
+    adds_full: bool         # the input-gradient epilogue adds the passthrough alias's full-grid gradient
+    adds_quarter: bool      # ... the strided shortcut's quarter-grid gradient (passthrough="sub")
+    masks_bits: bool        # ... can mask a second gradient from the block tail's ReLU bits (res_link)
+
+
+def conv3x3_route(cin, cout, stride, precision_code, has_bias, relu, in_affine, want_gap, need_dx, passthrough) -> ConvRoute:
+    """Pure: shapes, flags, the precision code and the switches PAD_WGRAD / S2_WGRAD / S2_DGRAD in, route out.  No tensors, no library.
+    Within each cascade the first match wins."""
+    split = precision_code != F32
+    if in_affine:
+        # x is the PRE-normalisation map of a deferred BatchNorm (batch_norm(defer_apply=True)): its per-channel affine is applied while the
+        # convolution (and later its weight-gradient kernel) stages the operand -- the normalised map never exists in memory
+        if not (split and stride == 1 and cin % 32 == 0 and cout % 32 == 0 and not has_bias and not relu):
+            raise L.EgError("conv3x3: a deferred BatchNorm in front needs a split-bf16, stride-1, bias-free convolution with channels % 32 == 0")
+        if want_gap and 256 % cout:
+            raise L.EgError("conv3x3: a deferred BatchNorm in front needs Cout to divide 256 for the pooling partials")
+        fwd, planes = "sq_in_affine", 2 if want_gap else 0
+    elif cin % 32 == 0 and cout % 4 == 0:
+        # split-bf16 modes: the epilogue also emits the per-tile sums of squares -- gap is then [2, B, tiles, Co] (plane 0 = the sums every
+        # consumer reads through the base pointer, plane 1 = the squares): train-mode BatchNorm needs no pass over y for its variance
+        fwd, planes = ("sq", 2) if (want_gap and split and 256 % cout == 0) else ("nhwc", 1 if want_gap else 0)
+    elif cin % 32 == 0:         # ragged channel count (final_conv1: 128 -> frames): channel-major epilogue, then back to NHWC
+        fwd, planes = "channel_major", 0
+    elif cin == 1 and stride == 1 and relu and has_bias and cout % 4 == 0 and cout <= 128 and 256 % (cout // 4) == 0:
+        fwd, planes = "stem", 0
+    else:                       # other thin inputs: im2col rows through the GEMM
+        fwd, planes = "im2col", 0
+    if want_gap and not planes:
+        raise ValueError("conv3x3(want_gap=True): only the NHWC tower convolutions (Cin % 32 == 0, Cout % 4 == 0) emit pooling partials")
+    if in_affine:
+        wgrad = "mfma_in_affine"
+    elif split and stride == 1 and cin % 32 == 0 and cout % 32 == 0:
+        wgrad = "mfma"
+    elif split and stride == 1 and cin % 32 == 0 and PAD_WGRAD:
+        wgrad = "mfma_padded"
+    elif precision_code == L.EG_PREC_BF16X3 and stride == 2 and cin % 4 == 0 and S2_WGRAD:
+        wgrad = "gather_mfma"
+    elif cin % 4 == 0:
+        wgrad = "implicit_gemm"
+    else:                       # the stem (1 input channel)
+        wgrad = "im2col"
+    if not need_dx:
+        dgrad = "none"
+    elif stride == 1 and cin == cout and cin % 32 == 0:
+        dgrad = "rotated"
+    elif split and stride == 1 and cin == 128 and cout <= 64 and PAD_WGRAD:
+        dgrad = "rotated_padded"
+    elif stride == 2 and precision_code == L.EG_PREC_BF16X3 and S2_DGRAD and (cin, cout) in ((32, 64), (64, 128), (128, 256)):
+        dgrad = "s2"
+    else:
+        dgrad = "col2im"
+    return ConvRoute(fwd, wgrad, dgrad, planes, adds_full=dgrad in ("rotated", "rotated_padded") and bool(passthrough),
+                     adds_quarter=dgrad == "s2" and passthrough == "sub", masks_bits=dgrad == "rotated" and passthrough is True)
+
+
+def gap_planes(gap) -> int:
+    """How many planes of pooling partials `gap` (the second output of conv3x3(want_gap=True), or None) holds: what its convolution's route stated."""
+    return 0 if gap is None else gap._eg_planes
+
+
+# ---- conv3x3 forward, one helper per ConvRoute.forward: (xd, wd, b, stride, relu, planes, prec, aff) -> (y, gap) -------------------------------
+def _conv_operands(wd, b):
+    """The packed filter image and the bias padded to the image's 16-channel granule."""
+    Co = wd.shape[0]
+    wp, bp = _pack_conv(wd), None
+    if b is not None:
+        bp = torch.zeros((Co + 15) // 16 * 16, dtype=torch.float32, device=wd.device)
+        bp[:Co].copy_(_chk(b))
+    return wp, bp
+
+
+def _conv_out(xd, Co, stride, planes):
+    """y [B, Ho, Wo, Co] and the per-(clip, tile) pooling partials of `planes` planes (None for 0)."""
+    B, H, W, Ci = xd.shape
+    y = torch.empty(B, (H - 1) // stride + 1, (W - 1) // stride + 1, Co, dtype=torch.float32, device=xd.device)
+    if not planes:
+        return y, None
+    tiles = int(_lib().eg_conv3x3_gap_tiles(H, W, Ci, Co, stride))
+    return y, torch.empty((2, B, tiles, Co) if planes == 2 else (B, tiles, Co), dtype=torch.float32, device=xd.device)
+
+
+def _conv_fwd_sq_in_affine(xd, wd, b, stride, relu, planes, prec, aff):
+    B, H, W, Ci = xd.shape
+    Co = wd.shape[0]
+    wp, _ = _conv_operands(wd, None)
+    y, gap = _conv_out(xd, Co, 1, planes)
+    L.check(_lib().eg_conv3x3_sq_in_affine(_ptr(xd), _ptr(aff[0]), _ptr(aff[1]), _ptr(wp), None, _ptr(y), _ptr(gap), _ptr(gap[1]) if gap is not None else None,
+                                           B, H, W, Ci, Co, 1, 0, prec, _stream(xd.device)), "eg_conv3x3_sq_in_affine")
+    return y, gap
+
+
+def _conv_fwd_sq(xd, wd, b, stride, relu, planes, prec, aff):
+    B, H, W, Ci = xd.shape
+    Co = wd.shape[0]
+    wp, bp = _conv_operands(wd, b)
+    y, gap = _conv_out(xd, Co, stride, 2)
+    L.check(_lib().eg_conv3x3_sq(_ptr(xd), _ptr(wp), _ptr(bp), _ptr(y), _ptr(gap), _ptr(gap[1]), B, H, W, Ci, Co, stride, int(relu), prec, _stream(xd.device)),
+            "eg_conv3x3_sq")
+    return y, gap
+
+
+def _conv_fwd_nhwc(xd, wd, b, stride, relu, planes, prec, aff):
+    B, H, W, Ci = xd.shape
+    Co = wd.shape[0]
+    wp, bp = _conv_operands(wd, b)
+    y, gap = _conv_out(xd, Co, stride, planes)      # per-(clip, tile) channel sums of y from the conv epilogue: BatchNorm's mean / the SE pooling for free
+    L.check(_lib().eg_conv3x3(_ptr(xd), _ptr(wp), _ptr(bp), None, None, _ptr(y), _ptr(gap), B, H, W, Ci, Co, stride, int(relu), 0, prec, _stream(xd.device)),
+            "eg_conv3x3")
+    return y, gap
+
+
+def _conv_fwd_channel_major(xd, wd, b, stride, relu, planes, prec, aff):
+    B, H, W, Ci = xd.shape
+    Co = wd.shape[0]
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    wp, bp = _conv_operands(wd, b)
+    yc = torch.empty(B, Co, Ho * Wo, dtype=torch.float32, device=xd.device)
+    L.check(_lib().eg_conv3x3(_ptr(xd), _ptr(wp), _ptr(bp), None, None, _ptr(yc), None, B, H, W, Ci, Co, stride, int(relu), 1, prec, _stream(xd.device)),
+            "eg_conv3x3")
+    return yc.view(B, Co, Ho, Wo).permute(0, 2, 3, 1).contiguous(), None
+
+
+def _conv_fwd_stem(xd, wd, b, stride, relu, planes, prec, aff):
+    # the stem (ResNetSE34V2.py:64-66: conv -> ReLU, BatchNorm follows as its own operator): the inference stem kernel with an identity affine
+    B, H, W, _ = xd.shape
+    Co, dev = wd.shape[0], xd.device
+    w9 = raw_transpose(wd.view(Co, 9))                                  # [9][Co] tap-major
+    one, zero = _const_vec(dev, Co, 1.0), _const_vec(dev, Co, 0.0)
+    y, _ = _conv_out(xd, Co, 1, 0)
+    L.check(_lib().eg_stem_conv(_ptr(xd), _ptr(w9), _ptr(_chk(b)), _ptr(one), _ptr(zero), _ptr(y), B, H, W, Co, _stream(dev)), "eg_stem_conv")
+    return y, None
+
+
+def _conv_fwd_im2col(xd, wd, b, stride, relu, planes, prec, aff):
+    B, H, W, Ci = xd.shape
+    Co = wd.shape[0]
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    col = torch.empty(B * Ho * Wo, 9 * Ci, dtype=torch.float32, device=xd.device)
+    L.check(_lib().eg_im2col3x3(_ptr(xd), _ptr(col), B, H, W, Ci, stride, 0, _stream(xd.device)), "eg_im2col3x3")
+    wm = wd.permute(0, 2, 3, 1).reshape(Co, 9 * Ci).contiguous()
+    return raw_linear(col, wm, _chk(b) if b is not None else None, relu).view(B, Ho, Wo, Co), None
+
+
+_CONV_FWD = {"sq_in_affine": _conv_fwd_sq_in_affine, "sq": _conv_fwd_sq, "nhwc": _conv_fwd_nhwc, "channel_major": _conv_fwd_channel_major,
+             "stem": _conv_fwd_stem, "im2col": _conv_fwd_im2col}
+
+
+# ---- conv3x3 weight gradient, one helper per ConvRoute.wgrad: (x, dy2 [pixels, Co], dw OIHW, stride, aff) writes dw -----------------------------
+def _store_dw(dw, dwm):
+    Co, Ci = dw.shape[:2]
+    dw.copy_(dwm.view(Co, 3, 3, Ci).permute(0, 3, 1, 2))           # (kh, kw, ci) -> OIHW, straight into the flat gradient slice
+
+
+def _wgrad_mfma(x, dy2, dw, stride, aff):
+    # split-bf16 MFMA weight gradient, written OIHW straight into the flat gradient slice; aff: the deferred BatchNorm's affine re-applied while
+    # x is staged
+    lib = _lib()
+    B, H, W, Ci = x.shape
+    Co = dy2.shape[1]
+    ws = _scratch(x.device, lib.eg_conv3x3_wgrad_mfma_workspace_floats(B, H, W, Ci, Co), "wgrad")
+    if aff is not None:
+        L.check(lib.eg_conv3x3_wgrad_mfma_oihw_in_affine(_ptr(x), _ptr(aff[0]), _ptr(aff[1]), _ptr(dy2), _ptr(dw), B, H, W, Ci, Co, _ptr(ws), ws.numel(),
+                                                         _stream(x.device)), "eg_conv3x3_wgrad_mfma (in-affine)")
+    else:
+        L.check(lib.eg_conv3x3_wgrad_mfma_oihw(_ptr(x), _ptr(dy2), _ptr(dw), B, H, W, Ci, Co, _ptr(ws), ws.numel(), _stream(x.device)), "eg_conv3x3_wgrad_mfma")
+
+
+def _wgrad_mfma_padded(x, dy2, dw, stride, aff):
+    # a ragged output width (final_conv1: 128 -> frames = 34 / 60 / 120): the same MFMA kernel on dy zero-padded to a multiple of 32 channels --
+    # the padded rows of dW come out zero and are dropped (one pad pass over dy and a small copy instead of the fp32 implicit GEMM:
+    # 274 -> ~60 us at 128 clips)
+    Co, Ci = dw.shape[:2]
+    dyp = _pad_cols(dy2, 32)
+    dwp = torch.empty(dyp.shape[1], Ci, 3, 3, dtype=torch.float32, device=x.device)
+    _wgrad_mfma(x, dyp, dwp, stride, None)
+    dw.copy_(dwp[:Co])                                              # data movement into the flat gradient slice
+
+
+def _wgrad_gather_mfma(x, dy2, dw, stride, aff):
+    # stride-2 entry convolution: dW = dY^T im2col(x) on the split-bf16 Linear weight-gradient kernel, the window gathered while x is staged
+    # (was the fp32 implicit GEMM below: 263 us per layer at 128 clips)
+    lib = _lib()
+    B, H, W, Ci = x.shape
+    P, Co = dy2.shape
+    dwm = torch.empty(Co, 9 * Ci, dtype=torch.float32, device=x.device)
+    need = int(lib.eg_linear_wgrad_mfma_workspace_floats(P, Co, 9 * Ci))
+    ws = _scratch(x.device, need, "lingrad") if need else None
+    L.check(lib.eg_conv3x3_wgrad_gather_mfma(_ptr(x), _ptr(dy2), _ptr(dwm), B, H, W, Ci, Co, stride, _ptr(ws), ws.numel() if ws is not None else 0,
+                                             _stream(x.device)), "eg_conv3x3_wgrad_gather_mfma")
+    _store_dw(dw, dwm)
+
+
+def _wgrad_implicit_gemm(x, dy2, dw, stride, aff):
+    # implicit GEMM over the output pixels (no im2col buffer)
+    lib = _lib()
+    B, H, W, Ci = x.shape
+    P, Co = dy2.shape
+    dwm = torch.empty(Co, 9 * Ci, dtype=torch.float32, device=x.device)
+    need = lib.eg_gemm_tn_workspace_floats(Co, 9 * Ci, P)
+    ws = _scratch(x.device, need, "tn") if need else None
+    L.check(lib.eg_conv3x3_wgrad(_ptr(x), _ptr(dy2), _ptr(dwm), B, H, W, Ci, Co, stride, _ptr(ws), ws.numel() if ws is not None else 0, _stream(x.device)),
+            "eg_conv3x3_wgrad")
+    _store_dw(dw, dwm)
+
+
+def _wgrad_im2col(x, dy2, dw, stride, aff):
+    B, H, W, Ci = x.shape
+    col = torch.empty(dy2.shape[0], 9 * Ci, dtype=torch.float32, device=x.device)
+    L.check(_lib().eg_im2col3x3(_ptr(x), _ptr(col), B, H, W, Ci, stride, 0, _stream(x.device)), "eg_im2col3x3")
+    _store_dw(dw, raw_gemm_tn(dy2, col))                            # [Co, (kh,kw,ci)]
+
+
+_CONV_WGRAD = {"mfma_in_affine": _wgrad_mfma, "mfma": _wgrad_mfma, "mfma_padded": _wgrad_mfma_padded, "gather_mfma": _wgrad_gather_mfma,
+               "implicit_gemm": _wgrad_implicit_gemm, "im2col": _wgrad_im2col}
+
+
+# ---- conv3x3 input gradient, one helper per ConvRoute.dgrad: (x, w, dyd NHWC, res, lazy, prec, stride) -> dx -------------------------------------
+# res: the second gradient the epilogue adds (on the grid the route's facts name) or None; lazy: (dout, ReLU bits) it masks instead (rotated only)
+def _dgrad_rotated(x, w, dyd, res, lazy, prec, stride):
+    # input gradient of a square stride-1 conv = the forward kernel on the 180-degree rotated, transposed filter
+    # (F.conv2d's dgrad); no 9x im2col intermediate
+    lib = _lib()
+    B, H, W, Ci = x.shape
+    Co = w.shape[0]
+    wp = _pack_conv(w, flip=True)                                       # w'[ci][co][kh][kw] = w[co][ci][2-kh][2-kw]
+    dx = torch.empty_like(x)
+    if lazy is not None:                                                # the other consumer's gradient masked in the epilogue from (dout, ReLU bits)
+        L.check(lib.eg_conv3x3_res_masked(_ptr(dyd), _ptr(wp), _ptr(lazy[0]), _ptr(lazy[1]), _ptr(dx), B, H, W, Co, Ci, prec, _stream(x.device)),
+                "eg_conv3x3_res_masked (dgrad)")
+    else:                                                               # ... added there as a map
+        L.check(lib.eg_conv3x3_se(_ptr(dyd), _ptr(wp), None, None, None, None, _ptr(res), _ptr(dx), None, B, H, W, Co, Ci, 1, 0, 0, prec, _stream(x.device)),
+                "eg_conv3x3 (dgrad)")
+    return dx
+
+
+def _dgrad_rotated_padded(x, w, dyd, res, lazy, prec, stride):
+    # final_conv1 (128 -> frames): the same rotated-filter convolution on dy and the filter zero-padded to 64 output channels, instead of
+    # the [pixels, 9 * 128] column product + col2im (585 MB written and re-read per 128-clip step)
+    B, H, W, Ci = x.shape
+    Co = w.shape[0]
+    dyp = _pad_cols(dyd.view(-1, Co), 64).view(B, H, W, 64)
+    wpad = torch.zeros(64, Ci, 3, 3, dtype=torch.float32, device=x.device)
+    wpad[:Co].copy_(w)
+    wp = _pack_conv(wpad, flip=True)
+    dx = torch.empty_like(x)
+    L.check(_lib().eg_conv3x3_se(_ptr(dyp), _ptr(wp), None, None, None, None, _ptr(res), _ptr(dx), None, B, H, W, 64, Ci, 1, 0, 0, prec, _stream(x.device)),
+            "eg_conv3x3 (dgrad, padded)")
+    return dx
+
+
+def _dgrad_s2(x, w, dyd, res, lazy, prec, stride):
+    # stride-2 entry convolution of a stage: the phase-decomposed MFMA input gradient (9 tap products per four dx pixels), the shortcut's
+    # quarter-grid gradient added in its epilogue -- instead of the [pixels, 9 Ci] column product + col2im (+ the zero-filled scatter)
+    B, H, W, Ci = x.shape
+    wp = _pack_conv(w, flip=True)
+    dx = torch.empty_like(x)
+    L.check(_lib().eg_conv3x3_dgrad_s2(_ptr(dyd), _ptr(wp), _ptr(res), _ptr(dx), B, H, W, Ci, w.shape[0], prec, _stream(x.device)), "eg_conv3x3_dgrad_s2")
+    return dx
+
+
+def _dgrad_col2im(x, w, dyd, res, lazy, prec, stride):
+    B, H, W, Ci = x.shape
+    Co = w.shape[0]
+    wmat_t = w.permute(2, 3, 1, 0).reshape(9 * Ci, Co).contiguous()   # [(kh,kw,ci), co] = Wmat^T
+    dcol = raw_linear(dyd.view(-1, Co), wmat_t)                       # [P, 9 Ci]
+    dx = torch.empty_like(x)
+    L.check(_lib().eg_im2col3x3(_ptr(dcol), _ptr(dx), B, H, W, Ci, stride, 1, _stream(x.device)), "eg_col2im3x3")
+    return dx
+
+
+_CONV_DGRAD = {"rotated": _dgrad_rotated, "rotated_padded": _dgrad_rotated_padded, "s2": _dgrad_s2, "col2im": _dgrad_col2im}
+
+
+def _scatter_quarter(dres, x, stride):
+    """The strided shortcut's quarter-grid gradient as a zero-filled map on x's grid."""
+    B, H, W, Ci = x.shape
+    full = torch.empty_like(x)
+    L.check(_lib().eg_subsample(_ptr(_chk(dres)), _ptr(full), B, H, W, Ci, stride, 1, _stream(x.device)), "eg_subsample")
+    return full
+
+
 class _Conv3x3(torch.autograd.Function):
-    """nn.Conv2d(k=3, pad=1, stride s) on NHWC activations; weight OIHW as in the reference's state_dict."""
+    """nn.Conv2d(k=3, pad=1, stride s) on NHWC activations; weight OIHW as in the reference's state_dict.  `route` and `prec` are what conv3x3()
+    decided (conv3x3_route, the precision code of that moment): forward and backward only execute them."""
 
     @staticmethod
-    def forward(ctx, x, w, b, stride, relu, want_gap=False, defer_mask=False, passthrough=False, in_scale=None, in_shift=None, res_link=None):
-        lib = _lib()
+    def forward(ctx, x, w, b, stride, relu, defer_mask, passthrough, in_scale, in_shift, res_link, route, prec):
         ctx.set_materialize_grads(False)            # no zero-filled "gradients" for the non-differentiable pooling partials / an unused alias
         xd, wd = _chk(x, "x"), _chk(w, "weight")
-        ctx.in_affine = None
-        if in_scale is not None:
-            # x is the PRE-normalisation map of a deferred BatchNorm (batch_norm(defer_apply=True)): its per-channel affine is applied while the
-            # convolution (and later its weight-gradient kernel) stages the operand -- the normalised map never exists in memory
-            if not (_PREC["conv"] != F32 and stride == 1 and xd.shape[-1] % 32 == 0 and wd.shape[0] % 32 == 0 and b is None and not relu):
-                raise L.EgError("conv3x3: a deferred BatchNorm in front needs a split-bf16, stride-1, bias-free convolution with channels % 32 == 0")
-            ctx.in_affine = (in_scale, in_shift)
-        gap = None
-        B, H, W, Ci = xd.shape
-        Co = wd.shape[0]
-        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-        dev = xd.device
-        if Ci % 32 == 0:
-            coutp = (Co + 15) // 16 * 16
-            wp = _pack_conv(wd)
-            prec = _PREC["conv"]
-            bp = None
-            if b is not None:
-                bp = torch.zeros(coutp, dtype=torch.float32, device=dev)
-                bp[:Co].copy_(_chk(b))
-            if Co % 4 == 0:
-                y = torch.empty(B, Ho, Wo, Co, dtype=torch.float32, device=dev)
-                tiles = int(lib.eg_conv3x3_gap_tiles(H, W, Ci, Co, stride)) if want_gap else 0
-                if ctx.in_affine is not None:
-                    if want_gap:
-                        if 256 % Co:
-                            raise L.EgError("conv3x3: a deferred BatchNorm in front needs Cout to divide 256 for the pooling partials")
-                        gap = torch.empty(2, B, tiles, Co, dtype=torch.float32, device=dev)
-                    L.check(lib.eg_conv3x3_sq_in_affine(_ptr(xd), _ptr(in_scale), _ptr(in_shift), _ptr(wp), None, _ptr(y), _ptr(gap),
-                                                        _ptr(gap[1]) if gap is not None else None, B, H, W, Ci, Co, 1, 0, prec, _stream(dev)),
-                            "eg_conv3x3_sq_in_affine")
-                elif want_gap and prec != F32 and 256 % Co == 0:
-                    # split-bf16 modes: the epilogue also emits the per-tile sums of squares -- gap is then [2, B, tiles, Co] (plane 0 = the sums every
-                    # consumer reads through the base pointer, plane 1 = the squares): train-mode BatchNorm needs no pass over y for its variance
-                    gap = torch.empty(2, B, tiles, Co, dtype=torch.float32, device=dev)
-                    L.check(lib.eg_conv3x3_sq(_ptr(xd), _ptr(wp), _ptr(bp), _ptr(y), _ptr(gap), _ptr(gap[1]), B, H, W, Ci, Co, stride, int(relu), prec,
-                                              _stream(dev)), "eg_conv3x3_sq")
-                else:
-                    if want_gap:        # per-(clip, tile) channel sums of y from the conv epilogue: BatchNorm's mean / the SE pooling for free
-                        gap = torch.empty(B, tiles, Co, dtype=torch.float32, device=dev)
-                    L.check(lib.eg_conv3x3(_ptr(xd), _ptr(wp), _ptr(bp), None, None, _ptr(y), _ptr(gap), B, H, W, Ci, Co, stride, int(relu), 0, prec,
-                                           _stream(dev)), "eg_conv3x3")
-            else:           # ragged channel count (final_conv1: 128 -> frames): channel-major epilogue, then back to NHWC
-                yc = torch.empty(B, Co, Ho * Wo, dtype=torch.float32, device=dev)
-                L.check(lib.eg_conv3x3(_ptr(xd), _ptr(wp), _ptr(bp), None, None, _ptr(yc), None, B, H, W, Ci, Co, stride, int(relu), 1, prec,
-                                       _stream(dev)), "eg_conv3x3")
-                y = yc.view(B, Co, Ho, Wo).permute(0, 2, 3, 1).contiguous()
-        elif Ci == 1 and stride == 1 and relu and b is not None and Co % 4 == 0 and Co <= 128 and 256 % (Co // 4) == 0:
-            # the stem (ResNetSE34V2.py:64-66: conv -> ReLU, BatchNorm follows as its own operator): the inference stem kernel with an identity affine
-            w9 = raw_transpose(wd.view(Co, 9))                                  # [9][Co] tap-major
-            one, zero = _const_vec(dev, Co, 1.0), _const_vec(dev, Co, 0.0)
-            y = torch.empty(B, Ho, Wo, Co, dtype=torch.float32, device=dev)
-            L.check(lib.eg_stem_conv(_ptr(xd), _ptr(w9), _ptr(_chk(b)), _ptr(one), _ptr(zero), _ptr(y), B, H, W, Co, _stream(dev)), "eg_stem_conv")
-        else:               # other thin inputs: im2col rows through the GEMM
-            col = torch.empty(B * Ho * Wo, 9 * Ci, dtype=torch.float32, device=dev)
-            L.check(lib.eg_im2col3x3(_ptr(xd), _ptr(col), B, H, W, Ci, stride, 0, _stream(dev)), "eg_im2col3x3")
-            wm = wd.permute(0, 2, 3, 1).reshape(Co, 9 * Ci).contiguous()
-            y = raw_linear(col, wm, _chk(b) if b is not None else None, relu).view(B, Ho, Wo, Co)
-        if want_gap and gap is None:
-            raise ValueError("conv3x3(want_gap=True): only the NHWC tower convolutions (Cin % 32 == 0, Cout % 4 == 0) emit pooling partials")
+        ctx.route, ctx.prec = route, prec
+        ctx.in_affine = (in_scale, in_shift) if in_scale is not None else None
+        y, gap = _CONV_FWD[route.forward](xd, wd, b, stride, relu, route.gap_planes, prec, ctx.in_affine)
         ctx.save_for_backward(xd, wd, y if (relu and not defer_mask) else None)      # defer_mask: the consumer (batch_norm(relu_input=True)) applies it
-        ctx.stride, ctx.has_b, ctx.need_dx = stride, b is not None, x.requires_grad
+        ctx.stride, ctx.has_b = stride, b is not None
         ctx.params = (w, b)
         ctx.passthrough = bool(passthrough)
         ctx.pass_sub = passthrough == "sub"
         # res_link (a dict shared with the block's se_block_tail): the tail's backward leaves (dout, ReLU bits) there instead of writing the identity
         # shortcut's gradient dout * [out > 0] as a map; this backward masks dout in the input-gradient epilogue (eg_conv3x3_res_masked)
-        ctx.res_link = res_link if (passthrough is True and stride == 1 and Ci == Co and Ci % 32 == 0) else None
-        if res_link is not None and ctx.res_link is None:
-            raise L.EgError("conv3x3(res_link=...): only with passthrough=True on a square stride-1 convolution with channels % 32 == 0")
+        ctx.res_link = res_link
         outs = (y,)
-        if want_gap:
+        if gap is not None:
             ctx.mark_non_differentiable(gap)
             outs += (gap,)
         if ctx.pass_sub:
             # the second consumer is the stride-2 1x1 shortcut (ResNetSE34V2.py:43-47), which reads x[:, ::s, ::s] only: hand it that quarter map; its
             # gradient comes back on the quarter grid and the stride-2 input-gradient kernel adds it to the pixels it belongs to -- no zero-filled
             # full-resolution map is written and re-read
-            xs = torch.empty(B, Ho, Wo, Ci, dtype=torch.float32, device=dev)
-            L.check(lib.eg_subsample(_ptr(xd), _ptr(xs), B, H, W, Ci, stride, 0, _stream(dev)), "eg_subsample")
+            B, H, W, Ci = xd.shape
+            xs = torch.empty(B, y.shape[1], y.shape[2], Ci, dtype=torch.float32, device=xd.device)
+            L.check(_lib().eg_subsample(_ptr(xd), _ptr(xs), B, H, W, Ci, stride, 0, _stream(xd.device)), "eg_subsample")
             outs += (xs,)
         elif passthrough:       # a second use of x (the block's residual branch): its gradient comes back into THIS backward and is added in the
             outs += (x.view_as(x),)                 # dgrad launch's epilogue instead of a separate map-sized add (fork)
@@ -647,132 +876,53 @@ class _Conv3x3(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, *rest):
-        lib = _lib()
+        route = ctx.route
         dres = rest[-1] if ctx.passthrough else None
         x, w, y = ctx.saved_tensors
-        B, H, W, Ci = x.shape
-        Co = w.shape[0]
+        Co, Ci = w.shape[:2]
         lazy = ctx.res_link.pop("masked", None) if ctx.res_link is not None else None        # (dout, bits) left by the block's tail
         if lazy is not None and (dres is not None or dy is None):
             raise L.EgError("conv3x3: the masked shortcut gradient cannot be combined with another gradient of the alias / a missing dy")
         if dy is None:              # only the alias was used downstream
             if dres is not None and ctx.pass_sub:
-                full = torch.empty_like(x)
-                L.check(lib.eg_subsample(_ptr(_chk(dres)), _ptr(full), B, H, W, Ci, ctx.stride, 1, _stream(x.device)), "eg_subsample")
-                dres = full
-            return (_chk(dres) if dres is not None else None), None, None, None, None, None, None, None, None, None, None
+                dres = _scatter_quarter(dres, x, ctx.stride)
+            return (_chk(dres) if dres is not None else None), None, None, None, None, None, None, None, None, None, None, None
         dyd = _chk(dy)
         if y is not None:
             dyd = raw_ew(EW_RELU_BWD, dyd, y)
-        Ho, Wo = dyd.shape[1], dyd.shape[2]
-        dev = x.device
-        dy2 = dyd.view(B * Ho * Wo, Co)
+        dy2 = dyd.view(-1, Co)
         dw = grad_out(ctx.params[0], (Co, Ci, 3, 3))
-        dwm = None
-        if ctx.in_affine is not None:   # the deferred BatchNorm's affine re-applied while x is staged (forward checked the shape constraints)
-            need = lib.eg_conv3x3_wgrad_mfma_workspace_floats(B, H, W, Ci, Co)
-            ws = _scratch(dev, need, "wgrad")
-            L.check(lib.eg_conv3x3_wgrad_mfma_oihw_in_affine(_ptr(x), _ptr(ctx.in_affine[0]), _ptr(ctx.in_affine[1]), _ptr(dy2), _ptr(dw), B, H, W, Ci, Co,
-                                                             _ptr(ws), ws.numel(), _stream(dev)), "eg_conv3x3_wgrad_mfma (in-affine)")
-        elif _PREC["conv"] != F32 and ctx.stride == 1 and Ci % 32 == 0 and Co % 32 == 0:       # split-bf16 MFMA weight gradient, written OIHW
-            need = lib.eg_conv3x3_wgrad_mfma_workspace_floats(B, H, W, Ci, Co)                # straight into the flat gradient slice
-            ws = _scratch(dev, need, "wgrad")
-            L.check(lib.eg_conv3x3_wgrad_mfma_oihw(_ptr(x), _ptr(dy2), _ptr(dw), B, H, W, Ci, Co, _ptr(ws), ws.numel(), _stream(dev)),
-                    "eg_conv3x3_wgrad_mfma")
-        elif _PREC["conv"] != F32 and ctx.stride == 1 and Ci % 32 == 0 and PAD_WGRAD:
-            # a ragged output width (final_conv1: 128 -> frames = 34 / 60 / 120): the same MFMA kernel on dy zero-padded to a multiple of 32 channels --
-            # the padded rows of dW come out zero and are dropped (one pad pass over dy and a small copy instead of the fp32 implicit GEMM:
-            # 274 -> ~60 us at 128 clips)
-            Cop = (Co + 31) // 32 * 32
-            dyp = _pad_cols(dy2, 32)
-            dwp = torch.empty(Cop, Ci, 3, 3, dtype=torch.float32, device=dev)
-            need = lib.eg_conv3x3_wgrad_mfma_workspace_floats(B, H, W, Ci, Cop)
-            ws = _scratch(dev, need, "wgrad")
-            L.check(lib.eg_conv3x3_wgrad_mfma_oihw(_ptr(x), _ptr(dyp), _ptr(dwp), B, H, W, Ci, Cop, _ptr(ws), ws.numel(), _stream(dev)),
-                    "eg_conv3x3_wgrad_mfma")
-            dw.copy_(dwp[:Co])                                              # data movement into the flat gradient slice
-        elif _PREC["conv"] == L.EG_PREC_BF16X3 and ctx.stride == 2 and Ci % 4 == 0 and S2_WGRAD:
-            # stride-2 entry convolution: dW = dY^T im2col(x) on the split-bf16 Linear weight-gradient kernel, the window gathered while x is staged
-            # (was the fp32 implicit GEMM below: 263 us per layer at 128 clips)
-            dwm = torch.empty(Co, 9 * Ci, dtype=torch.float32, device=dev)
-            need = int(lib.eg_linear_wgrad_mfma_workspace_floats(B * Ho * Wo, Co, 9 * Ci))
-            ws = _scratch(dev, need, "lingrad") if need else None
-            L.check(lib.eg_conv3x3_wgrad_gather_mfma(_ptr(x), _ptr(dy2), _ptr(dwm), B, H, W, Ci, Co, ctx.stride, _ptr(ws), ws.numel() if ws is not None else 0,
-                                                     _stream(dev)), "eg_conv3x3_wgrad_gather_mfma")
-        elif Ci % 4 == 0:           # implicit GEMM over the output pixels (no im2col buffer)
-            dwm = torch.empty(Co, 9 * Ci, dtype=torch.float32, device=dev)
-            need = lib.eg_gemm_tn_workspace_floats(Co, 9 * Ci, B * Ho * Wo)
-            ws = _scratch(dev, need, "tn") if need else None
-            L.check(lib.eg_conv3x3_wgrad(_ptr(x), _ptr(dy2), _ptr(dwm), B, H, W, Ci, Co, ctx.stride, _ptr(ws), ws.numel() if ws is not None else 0,
-                                         _stream(dev)), "eg_conv3x3_wgrad")
-        else:                       # the stem (1 input channel)
-            col = torch.empty(B * Ho * Wo, 9 * Ci, dtype=torch.float32, device=dev)
-            L.check(lib.eg_im2col3x3(_ptr(x), _ptr(col), B, H, W, Ci, ctx.stride, 0, _stream(dev)), "eg_im2col3x3")
-            dwm = raw_gemm_tn(dy2, col)                                     # [Co, (kh,kw,ci)]
-        if dwm is not None:
-            dw.copy_(dwm.view(Co, 3, 3, Ci).permute(0, 3, 1, 2))           # (kh, kw, ci) -> OIHW, straight into the flat gradient slice
+        _CONV_WGRAD[route.wgrad](x, dy2, dw, ctx.stride, ctx.in_affine)
         db = raw_colsum(dy2, out0=grad_out(ctx.params[1]))[0] if ctx.has_b else None
         dx = None
-        if ctx.need_dx and ctx.stride == 1 and Ci == Co and Ci % 32 == 0:
-            # input gradient of a square stride-1 conv = the forward kernel on the 180-degree rotated, transposed filter
-            # (F.conv2d's dgrad); no 9x im2col intermediate
-            wp = _pack_conv(w, flip=True)                                       # w'[ci][co][kh][kw] = w[co][ci][2-kh][2-kw]
-            dx = torch.empty_like(x)
-            res = _chk(dres) if dres is not None else None                      # the other consumer's gradient: added in the epilogue
-            if lazy is not None:                                                # ... masked there from (dout, ReLU bits): never a map of its own
-                L.check(lib.eg_conv3x3_res_masked(_ptr(dyd), _ptr(wp), _ptr(lazy[0]), _ptr(lazy[1]), _ptr(dx), B, H, W, Co, Ci, _PREC["conv"], _stream(dev)),
-                        "eg_conv3x3_res_masked (dgrad)")
-                lazy = None
-            else:
-                L.check(lib.eg_conv3x3_se(_ptr(dyd), _ptr(wp), None, None, None, None, _ptr(res), _ptr(dx), None, B, H, W, Co, Ci, 1, 0, 0, _PREC["conv"],
-                                          _stream(dev)), "eg_conv3x3 (dgrad)")
-            dres = None
-        elif ctx.need_dx and _PREC["conv"] != F32 and ctx.stride == 1 and Ci == 128 and Co <= 64 and PAD_WGRAD:
-            # final_conv1 (128 -> frames): the same rotated-filter convolution on dy and the filter zero-padded to 64 output channels, instead of
-            # the [pixels, 9 * 128] column product + col2im (585 MB written and re-read per 128-clip step)
-            dyp = _pad_cols(dy2, 64).view(B, Ho, Wo, 64)
-            wpad = torch.zeros(64, Ci, 3, 3, dtype=torch.float32, device=dev)
-            wpad[:Co].copy_(w)
-            wp = _pack_conv(wpad, flip=True)
-            dx = torch.empty_like(x)
-            res = _chk(dres) if dres is not None else None
-            L.check(lib.eg_conv3x3_se(_ptr(dyp), _ptr(wp), None, None, None, None, _ptr(res), _ptr(dx), None, B, H, W, 64, Ci, 1, 0, 0, _PREC["conv"],
-                                      _stream(dev)), "eg_conv3x3 (dgrad, padded)")
-            dres = None
-        elif ctx.need_dx and ctx.stride == 2 and _PREC["conv"] == L.EG_PREC_BF16X3 and S2_DGRAD and (Ci, Co) in ((32, 64), (64, 128), (128, 256)):
-            # stride-2 entry convolution of a stage: the phase-decomposed MFMA input gradient (9 tap products per four dx pixels), the shortcut's
-            # quarter-grid gradient added in its epilogue -- instead of the [pixels, 9 Ci] column product + col2im (+ the zero-filled scatter)
-            wp = _pack_conv(w, flip=True)
-            dx = torch.empty_like(x)
-            rq = _chk(dres) if (dres is not None and ctx.pass_sub) else None
-            L.check(lib.eg_conv3x3_dgrad_s2(_ptr(dyd), _ptr(wp), _ptr(rq), _ptr(dx), B, H, W, Ci, Co, _PREC["conv"], _stream(dev)), "eg_conv3x3_dgrad_s2")
-            if rq is not None:
+        if route.dgrad != "none":
+            fused = dres is not None and (route.adds_full or route.adds_quarter)       # the other consumer's gradient: added in the epilogue
+            assert lazy is None or route.masks_bits, "conv3x3: the masked shortcut gradient was left for an input-gradient path without the fused epilogue"
+            dx = _CONV_DGRAD[route.dgrad](x, w, dyd, _chk(dres) if fused else None, lazy, ctx.prec, ctx.stride)
+            if fused:
                 dres = None
-        elif ctx.need_dx:
-            wmat_t = w.permute(2, 3, 1, 0).reshape(9 * Ci, Co).contiguous()   # [(kh,kw,ci), co] = Wmat^T
-            dcol = raw_linear(dy2, wmat_t)                                    # [P, 9 Ci]
-            dx = torch.empty_like(x)
-            L.check(lib.eg_im2col3x3(_ptr(dcol), _ptr(dx), B, H, W, Ci, ctx.stride, 1, _stream(dev)), "eg_col2im3x3")
-        if lazy is not None and ctx.need_dx:
-            raise L.EgError("conv3x3: the masked shortcut gradient was left for an input-gradient path without the fused epilogue")
-        if dres is not None and ctx.pass_sub:       # the shortcut's quarter-grid gradient on a path without the fused epilogue: scatter, then add
-            full = torch.empty_like(x)
-            L.check(lib.eg_subsample(_ptr(_chk(dres)), _ptr(full), B, H, W, Ci, ctx.stride, 1, _stream(dev)), "eg_subsample")
-            dres = full
-        if dres is not None:        # passthrough on a path without the fused epilogue (or no dx wanted): the plain add
-            dx = raw_ew(EW_ADD, dx, _chk(dres)) if dx is not None else _chk(dres)
-        return dx, dw, db, None, None, None, None, None, None, None, None
+        if dres is not None:        # a second gradient on a path without the fused epilogue (or no dx wanted): scatter the quarter grid, then the plain add
+            dres = _scatter_quarter(dres, x, ctx.stride) if ctx.pass_sub else _chk(dres)
+            dx = raw_ew(EW_ADD, dx, dres) if dx is not None else dres
+        return dx, dw, db, None, None, None, None, None, None, None, None, None
 
 
 def conv3x3(x_nhwc, w_oihw, b=None, stride=1, relu=False, want_gap=False, defer_mask=False, passthrough=False, res_link=None):
     """want_gap: also return the per-(clip, tile) channel sums of the output; defer_mask: the ReLU's backward is applied by the consumer;
     passthrough: also return an alias of the input for its second consumer (the residual branch) -- the two gradients are then summed in the
     input-gradient launch's epilogue instead of by a `fork`; passthrough="sub" (stride > 1): that consumer is the strided 1x1 shortcut, the extra
-    output is x[:, ::stride, ::stride] and its gradient comes back on that grid."""
-    aff = getattr(x_nhwc, "_eg_in_affine", None)        # a deferred BatchNorm produced x: (scale, shift) to apply while staging
-    if aff is not None:
-        return _Conv3x3.apply(x_nhwc, w_oihw, b, stride, relu, want_gap, defer_mask, passthrough, aff[0], aff[1], res_link)
-    return _Conv3x3.apply(x_nhwc, w_oihw, b, stride, relu, want_gap, defer_mask, passthrough, None, None, res_link)
+    output is x[:, ::stride, ::stride] and its gradient comes back on that grid.  res_link: see _Conv3x3.forward; refused here when the route's
+    input gradient cannot mask from bits.  The route and the precision are fixed HERE: the backward runs what the forward decided, whatever the
+    precision or the switches say by then."""
+    aff = getattr(x_nhwc, "_eg_in_affine", None) or (None, None)        # a deferred BatchNorm produced x: (scale, shift) to apply while staging
+    prec = _PREC["conv"]
+    route = conv3x3_route(x_nhwc.shape[-1], w_oihw.shape[0], stride, prec, b is not None, relu, aff[0] is not None, want_gap, x_nhwc.requires_grad, passthrough)
+    if res_link is not None and not route.masks_bits:
+        raise L.EgError("conv3x3(res_link=...): only with passthrough=True on a square stride-1 convolution with channels % 32 == 0")
+    out = _Conv3x3.apply(x_nhwc, w_oihw, b, stride, relu, defer_mask, passthrough, aff[0], aff[1], res_link, route, prec)
+    if want_gap:
+        out[1]._eg_planes = route.gap_planes
+    return out
 
 
 class _Subsample(torch.autograd.Function):
@@ -829,7 +979,7 @@ class _BatchNorm(torch.autograd.Function):
     """nn.BatchNorm{1,2}d in train() mode over the last (channel) axis; updates the running buffers in place."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, run_mean, run_var, momentum, eps, gap=None, relu_input=False, defer=False):
+    def forward(ctx, x, gamma, beta, run_mean, run_var, momentum, eps, gap=None, relu_input=False, route="two_pass"):
         lib = _lib()
         xd, g, b = _chk(x), _chk(gamma), _chk(beta)
         Cc = xd.shape[-1]
@@ -837,7 +987,7 @@ class _BatchNorm(torch.autograd.Function):
         dev = xd.device
         mean, rstd = torch.empty(Cc, device=dev), torch.empty(Cc, device=dev)
         ws = _scratch(dev, lib.eg_colreduce_workspace_floats(Cc), "col")
-        if defer:
+        if route == "deferred":
             # statistics only; the apply is handed to the consuming convolution as one affine per channel (conv3x3 reads `_eg_in_affine` off the
             # returned alias): the normalised map is neither written nor read -- one write + one read of the map less per block, forward
             aff = torch.empty(2, Cc, device=dev)
@@ -850,11 +1000,11 @@ class _BatchNorm(torch.autograd.Function):
             ctx.mark_non_differentiable(aff)
             return x.view_as(x), aff
         y = torch.empty_like(xd)
-        if gap is not None and gap.dim() == 4:     # sums and sums of squares from the producing convolution: statistics without touching the map
+        if route == "from_squares":     # sums and sums of squares from the producing convolution: statistics without touching the map
             L.check(lib.eg_bn_train_forward_sq(_ptr(xd), _ptr(gap), _ptr(gap[1]), gap.shape[2], gap.shape[1], _ptr(g), _ptr(b), _ptr(y), _ptr(mean),
                                                _ptr(rstd), None, _ptr(run_mean), _ptr(run_var), rows, Cc, float(momentum), float(eps), _ptr(ws),
                                                _stream(dev)), "eg_bn_train_forward_sq")
-        elif gap is not None:       # mean from the producing convolution's pooling partials: one pass (centred squares) instead of two
+        elif route == "from_sums":      # mean from the producing convolution's pooling partials: one pass (centred squares) instead of two
             L.check(lib.eg_bn_train_forward_gap(_ptr(xd), _ptr(gap), gap.shape[1], gap.shape[0], _ptr(g), _ptr(b), _ptr(y), _ptr(mean), _ptr(rstd), None,
                                                 _ptr(run_mean), _ptr(run_var), rows, Cc, float(momentum), float(eps), _ptr(ws), _stream(dev)),
                     "eg_bn_train_forward_gap")
@@ -887,20 +1037,26 @@ DEFER_BN_APPLY = __import__("os").environ.get("EG_DEFER_BN", "1") != "0"       #
 DEFER_BN_MIN_NUMEL = int(__import__("os").environ.get("EG_DEFER_BN_MIN_NUMEL", str(12 << 20)))
 
 
+def batch_norm_route(defer_apply, precision_code, planes, channels, ndim, numel) -> str:
+    """Pure: where train-mode BatchNorm takes its statistics from, given the pooling-partial planes its producer's route stated --
+    "deferred" (from sums and squares, the apply left to the consuming convolution), "from_squares", "from_sums" or "two_pass"."""
+    if (defer_apply and DEFER_BN_APPLY and precision_code != F32 and planes == 2 and channels % 32 == 0 and 256 % channels == 0 and ndim == 4
+            and numel >= DEFER_BN_MIN_NUMEL):
+        return "deferred"
+    return ("two_pass", "from_sums", "from_squares")[planes]
+
+
 def batch_norm(x_channels_last, bn, momentum=0.1, eps=1e-5, gap=None, relu_input=False, defer_apply=False):
     """`bn` = a BatchNorm parameter holder (weight, bias, running_mean, running_var, num_batches_tracked).  gap: pooling partials of the
     convolution that produced x (conv3x3(want_gap=True)); relu_input: x = relu(.) whose mask this backward applies (conv3x3(defer_mask=True)).
     defer_apply: the ONLY consumer is a stride-1, bias-free conv3x3 (a block's conv2): in the split-bf16 modes the normalisation is then not
     applied here but handed to that convolution as a per-channel affine (returned tensor = an alias of x carrying `_eg_in_affine`; conv3x3 and its
     weight-gradient kernel apply it while staging): nobody else may read the returned tensor's values."""
-    Cc = x_channels_last.shape[-1]
-    if (defer_apply and DEFER_BN_APPLY and _PREC["conv"] != F32 and gap is not None and gap.dim() == 4 and Cc % 32 == 0 and 256 % Cc == 0
-            and x_channels_last.dim() == 4 and x_channels_last.numel() >= DEFER_BN_MIN_NUMEL):
-        y, aff = _BatchNorm.apply(x_channels_last, bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum, eps, gap, relu_input, True)
+    route = batch_norm_route(defer_apply, _PREC["conv"], gap_planes(gap), x_channels_last.shape[-1], x_channels_last.dim(), x_channels_last.numel())
+    y = _BatchNorm.apply(x_channels_last, bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum, eps, gap, relu_input, route)
+    if route == "deferred":
+        y, aff = y
         y._eg_in_affine = (aff[0], aff[1])
-        _running_stats_written(bn)
-        return y
-    y = _BatchNorm.apply(x_channels_last, bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum, eps, gap, relu_input)
     _running_stats_written(bn)
     return y
 
@@ -909,12 +1065,22 @@ SE_TAIL_RELU_BITS = __import__("os").environ.get("EG_SE_TAIL_BITS", "1") != "0" 
 LAZY_SHORTCUT_GRAD = __import__("os").environ.get("EG_LAZY_SHORTCUT", "1") != "0"     # False: the tail writes the identity shortcut's gradient as a map (A/B)
 
 
+class SeTailRoute(NamedTuple):
+    stats: str              # bn2's statistics and the SE pooling: from_squares (no pass over c2) | from_sums (one centred pass)
+    keeps_bits: bool        # the ReLU mask is kept as bits: the backward never reads `out`, and an identity shortcut's gradient can stay unwritten (res_link)
+
+
+def se_tail_route(planes, numel) -> SeTailRoute:
+    """Pure: `planes` = the pooling-partial planes conv2's route stated (1 or 2), `numel` = elements of the block's map."""
+    return SeTailRoute(("from_sums", "from_squares")[planes - 1], SE_TAIL_RELU_BITS and numel % 32 == 0)
+
+
 class _SEBlockTail(torch.autograd.Function):
     """relu(se(bn2(c2)) + res) of SEBasicBlock.forward (ResNetBlocks.py:28-36) as one operator: bn2's statistics from conv2's pooling
     partials + one centred pass, the SE gate per clip, one fused output pass; bn2's output is never stored (the backward recomputes it)."""
 
     @staticmethod
-    def forward(ctx, c2, gap, res, gamma, beta, run_mean, run_var, w1, b1, w2, b2, momentum, eps, res_link=None):
+    def forward(ctx, c2, gap, res, gamma, beta, run_mean, run_var, w1, b1, w2, b2, momentum, eps, res_link, route):
         lib = _lib()
         x, r = _chk(c2), _chk(res)
         B, H, W, Cc = x.shape
@@ -923,7 +1089,7 @@ class _SEBlockTail(torch.autograd.Function):
         mean, rstd, clip = torch.empty(Cc, device=dev), torch.empty(Cc, device=dev), torch.empty(B, Cc, device=dev)
         ws = _scratch(dev, lib.eg_colreduce_workspace_floats(Cc), "col")
         st = _stream(dev)
-        if gap.dim() == 4:          # conv2 emitted sums and sums of squares: bn2's statistics and the SE pooling without a pass over c2
+        if route.stats == "from_squares":          # conv2 emitted sums and sums of squares: bn2's statistics and the SE pooling without a pass over c2
             L.check(lib.eg_bn_train_forward_sq(None, _ptr(gap), _ptr(gap[1]), gap.shape[2], B, None, None, None, _ptr(mean), _ptr(rstd), _ptr(clip),
                                                _ptr(run_mean), _ptr(run_var), B * hw, Cc, float(momentum), float(eps), _ptr(ws), st), "eg_bn_train_forward_sq")
         else:
@@ -934,13 +1100,13 @@ class _SEBlockTail(torch.autograd.Function):
                                              _ptr(h), _ptr(gate), B, hw, Cc, st), "eg_se_gate_train_forward")
         out = torch.empty_like(x)
         # the tail's ReLU mask as bits (one nibble per float4): the two backward passes read it instead of the whole `out` map
-        bits = torch.empty(x.numel() // 32, dtype=torch.int32, device=dev) if (SE_TAIL_RELU_BITS and x.numel() % 32 == 0) else None
+        bits = torch.empty(x.numel() // 32, dtype=torch.int32, device=dev) if route.keeps_bits else None
         L.check(lib.eg_se_tail_forward(_ptr(x), _ptr(r), _ptr(mean), _ptr(rstd), _ptr(g), _ptr(bt), _ptr(gate), _ptr(out), _ptr(bits), B, hw, Cc, st), "eg_se_tail_forward")
         ctx.save_for_backward(x, out if bits is None else bits, mean, rstd, clip, pooled, h, gate, g, bt, w1d, w2d)
         ctx.has_bits = bits is not None
         # res_link: `res` is the block input's alias out of conv1 (an identity shortcut); with the bit mask its gradient is not written as a map --
         # (dout, bits) go into the link and conv1's input-gradient epilogue masks dout itself (1.4 GB less written per 128-clip step)
-        ctx.res_link = res_link if bits is not None else None
+        ctx.res_link = res_link
         ctx.params = (gamma, beta, w1, b1, w2, b2)
         return out
 
@@ -973,13 +1139,17 @@ class _SEBlockTail(torch.autograd.Function):
             ctx.res_link["masked"] = (d, bits)
         L.check(lib.eg_se_tail_backward_apply(_ptr(d), _ptr(out), _ptr(bits), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(g), _ptr(gate), _ptr(dgap), _ptr(m1), _ptr(m2),
                                               _ptr(dc2), _ptr(dres), B, hw, Cc, st), "eg_se_tail_backward_apply")
-        return dc2, None, dres, dg, db, None, None, dw1, db1, dw2, db2, None, None, None
+        return dc2, None, dres, dg, db, None, None, dw1, db1, dw2, db2, None, None, None, None
 
 
 def se_block_tail(c2, gap, res, bn, fc0, fc2, momentum=0.1, eps=1e-5, res_link=None):
-    """res_link: the dict also given to the conv3x3(passthrough=True, res_link=...) whose alias output `res` is (see _Conv3x3.forward)."""
+    """res_link: the dict also given to the conv3x3(passthrough=True, res_link=...) whose alias output `res` is (see _Conv3x3.forward); needs a tail
+    that keeps its ReLU mask as bits (se_tail_route)."""
+    route = se_tail_route(gap_planes(gap), c2.numel())
+    if res_link is not None and not route.keeps_bits:
+        raise L.EgError("se_block_tail(res_link=...): only with the ReLU mask kept as bits (SE_TAIL_RELU_BITS, elements % 32 == 0)")
     out = _SEBlockTail.apply(c2, gap, res, bn.weight, bn.bias, bn.running_mean, bn.running_var, fc0.weight, fc0.bias, fc2.weight, fc2.bias, momentum, eps,
-                             res_link)
+                             res_link, route)
     _running_stats_written(bn)
     return out
 

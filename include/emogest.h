@@ -901,9 +901,6 @@ int eg_conv3x3_wgrad(const float* x, const float* dy, float* dw_mat, int32_t bat
 int eg_im2col3x3(const float* x, float* col, int32_t batch, int32_t h, int32_t w, int32_t c, int32_t stride, int32_t backward, void* stream);
 /* pixel subsample of a 1x1 stride-s conv (ResNetSE34V2.py:43-47) and its transpose */
 int eg_subsample(const float* x, float* y, int32_t batch, int32_t h, int32_t w, int32_t c, int32_t stride, int32_t backward, void* stream);
-/* 1-D channels-last im2col: x [B,L,C] -> col [B*Lout, k*C] at l*stride + j*dilation - pad_left; backward = transpose */
-int eg_im2col1d(const float* x, float* col, int32_t batch, int32_t len, int32_t c, int32_t k, int32_t stride, int32_t pad_left,
-                int32_t dilation, int32_t lout, int32_t backward, void* stream);
 /* The small 1-D convolutions of the training step (emotion CVAE Conv1d / ConvTranspose1d stacks, CAVE/BEAT_CVAE.py:318-332,355-369; the prior
  * encoder's pred_conv, Full_model/Models_spatial_memory.py:224-231) on channels-last activations, one fp32 launch per product, fixed-order sums:
  *   forward          y[b, lo, co]  = bias[co] + sum_{ci, j} x[b, lo*stride - pad + j*dilation, ci] * w[co][ci][j]     (w: nn.Conv1d's [cout][cin][k])
@@ -1053,10 +1050,6 @@ int eg_layernorm_backward_ex(const float* x, const float* dy, const float* gamma
                              int32_t rows, int32_t d, float eps, float drop_p, uint32_t drop_seed, uint64_t drop_offset, const int32_t* epoch_dev,
                              float* workspace, void* branch_images, void* stream);      /* branch_images (may be NULL): the gradient that enters the
                              Dropout'ed branch (dx_dropped, or dx when drop_p == 0) also as bf16 (hi, lo) images for a pre-split input-gradient product */
-/* ScaledDotProductAttention backward (Modules.py:13-23) from the forward's probabilities; Lq, Lk <= 64-ish (LDS-resident) */
-int eg_attention_backward(const float* q, int32_t ldq, const float* k, int32_t ldk, const float* v, int32_t ldv, const float* attn,
-                          const float* dout, int32_t ldo, float* dq, int32_t lddq, float* dk, int32_t lddk, float* dv, int32_t lddv,
-                          int32_t batch, int32_t heads, int32_t lq, int32_t lk, int32_t dk_dim, void* stream);
 /* Training pair on the fp32 matrix pipe (v_mfma_f32_16x16x4_f32) with nn.Dropout(p) on the probabilities (Modules.py:21) from the counter-based
  * mask of eg_dropout (counter = offset + linear index of (clip, head, query, key); epoch_dev as in eg_dropout_dev, may be NULL).  The forward stores
  * the UNMASKED probabilities in `attn` [batch, heads, lq, lk]; the backward recomputes the mask from the same (p, seed, offset, epoch).  The backward

@@ -270,8 +270,9 @@ def test_conv_epilogue_squares_give_batchnorm_statistics(B, H, W, Ci, Co, s):
 def test_se_tail_relu_bit_mask_is_bitwise_the_map_mask(li, B, H, W):
     """The fused SE-block tail (`se_block_tail`, ResNetBlocks.py:28-36) keeps its ReLU mask [out > 0] as one nibble per float4 (eg_se_tail_forward's
     relu_bits) and the two backward passes read those bits instead of the whole `out` map: against functional.SE_TAIL_RELU_BITS = False (the map
-    itself as the mask) every gradient of the block -- input, residual, bn2, the SE layers, conv weights -- is bitwise the same, on shapes whose
-    float4 count is a multiple of 8 (bits) and on one where it is not (falls back to the map)."""
+    itself as the mask) every gradient of the block -- input, residual, bn2, the SE layers, conv weights -- is bitwise the same.  Every shape
+    here keeps the bits: with C % 32 == 0 the float4 count of the map is a multiple of 8 whatever B, H and W are (odd H * W included), so none falls
+    back to the map."""
     from emotiongestures_amd.model.audio_emotion_classifer import EmotionNet
     from emotiongestures_amd.train import functional as F, nets
     net = load_synth_weights(EmotionNet(precision="f32"), 5).to(DEV).train()
@@ -749,12 +750,14 @@ def test_tower_shapes_backward_matches_float64(site, B, deferred, split, precisi
     H, W, C = STAGE_MAP[stage]
     u = hash_unit(f"tower_shapes.x.{site}", B * H * W * C, B)
     x = torch.from_numpy((2.0 * u - 1.0 if stage == 0 else np.maximum(2.0 * u - 0.8, 0.0)).astype(np.float32).reshape(B, H, W, C))    # NHWC; a block's input is post-ReLU
-    calls = {"bn_deferred": [], "conv": []}
+    calls = {"bn_deferred": [], "conv": [], "route": []}
     conv0, bn0 = F.conv3x3, F.batch_norm
 
     def conv_rec(xx, w, *a, **k):
         calls["conv"].append((tuple(xx.shape), tuple(w.shape), k.get("res_link") is not None))
-        return conv0(xx, w, *a, **k)
+        out = conv0(xx, w, *a, **k)
+        calls["route"].append((out[0] if isinstance(out, tuple) else out).grad_fn.route)
+        return out
 
     def bn_rec(xx, bn, *a, **k):
         y = bn0(xx, bn, *a, **k)
@@ -799,12 +802,202 @@ def test_tower_shapes_backward_matches_float64(site, B, deferred, split, precisi
         assert int(lib.eg_conv3x3_channel_split(B, Ho, Wo, Co, Co, 1, L.PRECISIONS[precision])) == (split if (bf and split) else 1), (site, B, precision)
     else:
         assert not any(calls["bn_deferred"])
+    # ... and by the route names the convolutions kept (the table above, spelled in conv3x3_route's names)
+    names = [(r.forward, r.wgrad, r.dgrad) for r in calls["route"]]
+    if site == "stem":
+        assert names == [("stem", "im2col", "none")]
+    elif site == "final":
+        assert names == [("channel_major", "mfma_padded", "rotated_padded") if bf else ("channel_major", "implicit_gemm", "col2im")]
+    else:
+        conv2 = (("sq_in_affine", "mfma_in_affine", "rotated") if deferred else ("sq", "mfma", "rotated")) if bf else ("nhwc", "implicit_gemm", "rotated")
+        if blk.downsample is None:
+            conv1 = ("sq", "mfma", "rotated") if bf else ("nhwc", "implicit_gemm", "rotated")
+        else:
+            conv1 = ("sq", "gather_mfma", "s2") if bf else ("nhwc", "implicit_gemm", "col2im")
+        assert names == [conv1, conv2], (site, B, precision, names)
+        r1 = calls["route"][0]
+        assert (r1.masks_bits, r1.adds_full, r1.adds_quarter) == ((True, True, False) if blk.downsample is None else (False, False, bf)), (site, r1)
     if site == "final":
         assert float(ae.final_conv1.bias.grad.norm()) < 1e-4 * float(ae.final_conv1.weight.grad.norm())
     line, _ = _tower_vs_float64(site, sd0, x.permute(0, 3, 1, 2), g.permute(0, 3, 1, 2), stride, y.detach(), xh.grad if site != "stem" else None, params,
                                 bns, taps, precision, 1e-5)
     path = ("deferred BatchNorm, " if (deferred and bf) else "") + (f"split {split if bf else 1}, " if split else "")
     print(f"B={B} {path}" + line)
+
+
+# ---- route name -> entry points launched ----------------------------------------------------------------------------------------------
+# One forward + backward per case with functional._lib replaced by a forwarding proxy that records the eg_* entry points called (launches and
+# packers; the size queries *_floats / *_tiles are left out).  The lists were recorded ONCE by this same recorder on commit f396f39, the last one whose
+# operators chose their kernels in shape / precision / switch cascades spread over forward and backward; they are not output of the route functions.
+class _LaunchRecorder:
+    def __init__(self, lib):
+        self._lib, self.names = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith("eg_") or name.endswith(("_floats", "_tiles")):
+            return fn
+
+        def call(*a):
+            self.names.append(name[3:])
+            return fn(*a)
+        return call
+
+
+def _route_conv_case(shape, cout, bias, relu, need_dx, bn):
+    """conv3x3 (-> batch_norm) as resnetse_forward's stem / audio_encoder_forward's final_conv1 call them, or a bare thin-input convolution."""
+    def run(F, nets):
+        from types import SimpleNamespace as NS
+        x = torch.randn(shape, device=DEV).requires_grad_(need_dx)
+        w = (0.1 * torch.randn(cout, shape[-1], 3, 3, device=DEV)).requires_grad_(True)
+        b = torch.zeros(cout, device=DEV, requires_grad=True) if bias else None
+        y = F.conv3x3(x, w, b, 1, relu=relu, defer_mask=relu and bn)
+        if bn:
+            holder = NS(weight=torch.ones(cout, device=DEV, requires_grad=True), bias=torch.zeros(cout, device=DEV, requires_grad=True),
+                        running_mean=torch.zeros(cout, device=DEV), running_var=torch.ones(cout, device=DEV),
+                        num_batches_tracked=torch.zeros((), dtype=torch.long, device=DEV))
+            y = F.batch_norm(y, holder, relu_input=relu)
+        y.backward(torch.randn_like(y))
+    return run
+
+
+def _route_block_case(shape, cout, stride):
+    def run(F, nets):
+        from emotiongestures_amd.modules import ResNetSE, SEBasicBlock
+        cin = shape[-1]
+        blk = (ResNetSE(SEBasicBlock, [1, 1, 1], [cin, cout, 2 * cout]).layer2[0] if stride == 2 else SEBasicBlock(cin, cout)).to(DEV)
+        x = torch.randn(shape, device=DEV).requires_grad_(True)
+        y = nets.se_basic_block(blk, x)
+        y.backward(torch.randn_like(y))
+    return run
+
+
+# id: (switches, runner, the (forward, wgrad, dgrad) of every conv3x3 call in f32, in bf16x3)
+_S1 = [("nhwc", "implicit_gemm", "rotated")] * 2
+_S2 = [("sq", "mfma", "rotated")] * 2
+ROUTE_CASES = {
+    "stem": ({}, _route_conv_case((2, 16, 12, 1), 32, True, True, False, True), [("stem", "im2col", "none")], [("stem", "im2col", "none")]),
+    "thin4": ({}, _route_conv_case((2, 9, 7, 4), 8, True, False, True, False), [("im2col", "implicit_gemm", "col2im")], [("im2col", "implicit_gemm", "col2im")]),
+    "thin3": ({}, _route_conv_case((2, 9, 7, 3), 8, True, False, True, False), [("im2col", "im2col", "col2im")], [("im2col", "im2col", "col2im")]),
+    "block32": ({}, _route_block_case((2, 12, 20, 32), 32, 1), _S1, _S2),
+    "block64": ({}, _route_block_case((3, 32, 30, 64), 64, 1), _S1, _S2),
+    # the shape of test_stride2_block_backward_uses_the_fused_input_gradient_and_equals_the_column_path
+    "entry-s2-on": ({"S2_DGRAD": True, "S2_WGRAD": True}, _route_block_case((3, 40, 36, 32), 64, 2),
+                    [("nhwc", "implicit_gemm", "col2im"), ("nhwc", "implicit_gemm", "rotated")], [("sq", "gather_mfma", "s2"), ("sq", "mfma", "rotated")]),
+    "entry-s2-off": ({"S2_DGRAD": False, "S2_WGRAD": False}, _route_block_case((3, 40, 36, 32), 64, 2),
+                     [("nhwc", "implicit_gemm", "col2im"), ("nhwc", "implicit_gemm", "rotated")], [("sq", "implicit_gemm", "col2im"), ("sq", "mfma", "rotated")]),
+    "final-pad-on": ({"PAD_WGRAD": True}, _route_conv_case((2, 8, 9, 128), 34, True, False, True, True),
+                     [("channel_major", "implicit_gemm", "col2im")], [("channel_major", "mfma_padded", "rotated_padded")]),
+    "final-pad-off": ({"PAD_WGRAD": False}, _route_conv_case((2, 8, 9, 128), 34, True, False, True, True),
+                      [("channel_major", "implicit_gemm", "col2im")], [("channel_major", "implicit_gemm", "col2im")]),
+    "block32-deferred": ({"DEFER_BN_MIN_NUMEL": 0}, _route_block_case((2, 12, 20, 32), 32, 1), _S1,
+                         [("sq", "mfma", "rotated"), ("sq_in_affine", "mfma_in_affine", "rotated")]),
+}
+ROUTE_LAUNCHES = {
+    ("stem", "f32"): """
+        transpose stem_conv bn_train_forward bn_train_backward im2col3x3 gemm_tn colsum""",
+    ("stem", "bf16x3"): """
+        transpose stem_conv bn_train_forward bn_train_backward im2col3x3 gemm_tn colsum""",
+    ("thin4", "f32"): """
+        im2col3x3 linear_ex conv3x3_wgrad colsum linear_ex im2col3x3""",
+    ("thin4", "bf16x3"): """
+        im2col3x3 pack_linear_device linear_ex conv3x3_wgrad colsum pack_linear_device linear_ex im2col3x3""",
+    ("thin3", "f32"): """
+        im2col3x3 pad_cols pad_cols linear_ex im2col3x3 gemm_tn colsum linear_ex im2col3x3""",
+    ("thin3", "bf16x3"): """
+        im2col3x3 pad_cols pack_linear_device linear_ex im2col3x3 gemm_tn colsum pack_linear_device linear_ex im2col3x3""",
+    ("block32", "f32"): """
+        pack_conv3x3_device conv3x3 bn_train_forward_gap pack_conv3x3_device conv3x3 bn_train_forward_gap se_gate_train_forward se_tail_forward
+        se_tail_backward_reduce se_gate_train_backward se_tail_backward_finish se_tail_backward_apply conv3x3_wgrad pack_conv3x3_device conv3x3_se
+        bn_train_backward conv3x3_wgrad pack_conv3x3_device conv3x3_res_masked""",
+    ("block32", "bf16x3"): """
+        pack_conv3x3_device conv3x3_sq bn_train_forward_sq pack_conv3x3_device conv3x3_sq bn_train_forward_sq se_gate_train_forward se_tail_forward
+        se_tail_backward_reduce se_gate_train_backward se_tail_backward_finish se_tail_backward_apply conv3x3_wgrad_mfma_oihw pack_conv3x3_device
+        conv3x3_se bn_train_backward conv3x3_wgrad_mfma_oihw pack_conv3x3_device conv3x3_res_masked""",
+    ("block64", "f32"): """
+        pack_conv3x3_device conv3x3 bn_train_forward_gap pack_conv3x3_device conv3x3 bn_train_forward_gap se_gate_train_forward se_tail_forward
+        se_tail_backward_reduce se_gate_train_backward se_tail_backward_finish se_tail_backward_apply conv3x3_wgrad pack_conv3x3_device conv3x3_se
+        bn_train_backward conv3x3_wgrad pack_conv3x3_device conv3x3_res_masked""",
+    ("block64", "bf16x3"): """
+        pack_conv3x3_device conv3x3_sq bn_train_forward_sq pack_conv3x3_device conv3x3_sq bn_train_forward_sq se_gate_train_forward se_tail_forward
+        se_tail_backward_reduce se_gate_train_backward se_tail_backward_finish se_tail_backward_apply conv3x3_wgrad_mfma_oihw pack_conv3x3_device
+        conv3x3_se bn_train_backward conv3x3_wgrad_mfma_oihw pack_conv3x3_device conv3x3_res_masked""",
+    ("entry-s2-on", "f32"): """
+        pack_conv3x3_device conv3x3 subsample bn_train_forward_gap pack_conv3x3_device conv3x3 linear_ex bn_train_forward bn_train_forward_gap
+        se_gate_train_forward se_tail_forward se_tail_backward_reduce se_gate_train_backward se_tail_backward_finish se_tail_backward_apply
+        bn_train_backward gemm_tn transpose linear_ex conv3x3_wgrad pack_conv3x3_device conv3x3_se bn_train_backward conv3x3_wgrad linear_ex im2col3x3
+        subsample elementwise""",
+    ("entry-s2-on", "bf16x3"): """
+        pack_conv3x3_device conv3x3_sq subsample bn_train_forward_sq pack_conv3x3_device conv3x3_sq pack_linear_device linear_ex bn_train_forward
+        bn_train_forward_sq se_gate_train_forward se_tail_forward se_tail_backward_reduce se_gate_train_backward se_tail_backward_finish
+        se_tail_backward_apply bn_train_backward linear_wgrad_mfma pack_linear_device linear_ex conv3x3_wgrad_mfma_oihw pack_conv3x3_device conv3x3_se
+        bn_train_backward conv3x3_wgrad_gather_mfma pack_conv3x3_device conv3x3_dgrad_s2""",
+    ("entry-s2-off", "f32"): """
+        pack_conv3x3_device conv3x3 subsample bn_train_forward_gap pack_conv3x3_device conv3x3 linear_ex bn_train_forward bn_train_forward_gap
+        se_gate_train_forward se_tail_forward se_tail_backward_reduce se_gate_train_backward se_tail_backward_finish se_tail_backward_apply
+        bn_train_backward gemm_tn transpose linear_ex conv3x3_wgrad pack_conv3x3_device conv3x3_se bn_train_backward conv3x3_wgrad linear_ex im2col3x3
+        subsample elementwise""",
+    ("entry-s2-off", "bf16x3"): """
+        pack_conv3x3_device conv3x3_sq subsample bn_train_forward_sq pack_conv3x3_device conv3x3_sq pack_linear_device linear_ex bn_train_forward
+        bn_train_forward_sq se_gate_train_forward se_tail_forward se_tail_backward_reduce se_gate_train_backward se_tail_backward_finish
+        se_tail_backward_apply bn_train_backward linear_wgrad_mfma pack_linear_device linear_ex conv3x3_wgrad_mfma_oihw pack_conv3x3_device conv3x3_se
+        bn_train_backward conv3x3_wgrad pack_linear_device linear_ex im2col3x3 subsample elementwise""",
+    ("final-pad-on", "f32"): """
+        pack_conv3x3_device conv3x3 bn_train_forward bn_train_backward conv3x3_wgrad colsum pad_cols pad_cols linear_ex im2col3x3""",
+    ("final-pad-on", "bf16x3"): """
+        pack_conv3x3_device conv3x3 bn_train_forward bn_train_backward pad_cols conv3x3_wgrad_mfma_oihw colsum pad_cols pack_conv3x3_device conv3x3_se""",
+    ("final-pad-off", "f32"): """
+        pack_conv3x3_device conv3x3 bn_train_forward bn_train_backward conv3x3_wgrad colsum pad_cols pad_cols linear_ex im2col3x3""",
+    ("final-pad-off", "bf16x3"): """
+        pack_conv3x3_device conv3x3 bn_train_forward bn_train_backward conv3x3_wgrad colsum pad_cols pack_linear_device linear_ex im2col3x3""",
+    ("block32-deferred", "f32"): """
+        pack_conv3x3_device conv3x3 bn_train_forward_gap pack_conv3x3_device conv3x3 bn_train_forward_gap se_gate_train_forward se_tail_forward
+        se_tail_backward_reduce se_gate_train_backward se_tail_backward_finish se_tail_backward_apply conv3x3_wgrad pack_conv3x3_device conv3x3_se
+        bn_train_backward conv3x3_wgrad pack_conv3x3_device conv3x3_res_masked""",
+    ("block32-deferred", "bf16x3"): """
+        pack_conv3x3_device conv3x3_sq bn_train_stats_sq pack_conv3x3_device conv3x3_sq_in_affine bn_train_forward_sq se_gate_train_forward
+        se_tail_forward se_tail_backward_reduce se_gate_train_backward se_tail_backward_finish se_tail_backward_apply
+        conv3x3_wgrad_mfma_oihw_in_affine pack_conv3x3_device conv3x3_se bn_train_backward conv3x3_wgrad_mfma_oihw pack_conv3x3_device
+        conv3x3_res_masked""",
+}
+
+
+@pytest.mark.parametrize("precision", ["f32", "bf16x3"])
+@pytest.mark.parametrize("case", list(ROUTE_CASES))
+def test_route_names_pin_the_entry_points_launched(case, precision, monkeypatch):
+    """The route a convolution keeps for its backward is the one conv3x3_route gives for its arguments, it carries the names the case is here for, and
+    forward + backward launch exactly the entry points that commit f396f39 launched for the same call (ROUTE_LAUNCHES), in the same order."""
+    import inspect
+    from emotiongestures_amd import _lib as L
+    from emotiongestures_amd.train import functional as F, nets
+    switches, run, names_f32, names_bf = ROUTE_CASES[case]
+    rec = _LaunchRecorder(L.load())
+    conv0, seen = F.conv3x3, []
+
+    def conv_rec(*a, **k):
+        out = conv0(*a, **k)
+        p = inspect.signature(conv0).bind(*a, **k)
+        p.apply_defaults()
+        p = p.arguments
+        fn = (out[0] if isinstance(out, tuple) else out).grad_fn
+        pure = F.conv3x3_route(p["x_nhwc"].shape[-1], p["w_oihw"].shape[0], p["stride"], L.PRECISIONS[precision], p["b"] is not None, p["relu"],
+                               hasattr(p["x_nhwc"], "_eg_in_affine"), p["want_gap"], p["x_nhwc"].requires_grad, p["passthrough"])
+        assert fn.route == pure and fn.prec == L.PRECISIONS[precision], (case, precision, fn.route, pure)
+        seen.append((fn.route.forward, fn.route.wgrad, fn.route.dgrad))
+        return out
+    monkeypatch.setattr(F, "_lib", lambda: rec)
+    monkeypatch.setattr(F, "conv3x3", conv_rec)
+    for k, v in switches.items():
+        monkeypatch.setattr(F, k, v)
+    torch.manual_seed(5)
+    try:
+        with F.precision(precision):
+            run(F, nets)
+        torch.cuda.synchronize()
+    finally:
+        F.flush_batch_counters()
+    assert seen == (names_f32 if precision == "f32" else names_bf), (case, precision, seen)
+    assert rec.names == ROUTE_LAUNCHES[case, precision].split(), (case, precision, rec.names)
 
 
 # ---- network level -----------------------------------------------------------------------------------------------------------
