@@ -988,7 +988,13 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
     const float* dr = dy + (size_t)row * D;
     float s = 0.f;
     for (int i = lane; i < D; i += 64) s += xr[i];
-    const float mean = wave_sum(s) / (float)D;
+    // The mean in two steps, as the forward kernels take it (misc.hip layernorm_kernel): the fp32 sum of D values is off by a few ulp of the mean, which
+    // rstd multiplies -- at a constant row by 1 / sqrt(eps), where xhat must be 0 and the row must add nothing to dgamma.  The residuals x - m0 are
+    // small, so their sum corrects m0 to the rounding of the exact mean.
+    const float m0 = wave_sum(s) / (float)D;
+    float c = 0.f;
+    for (int i = lane; i < D; i += 64) c += xr[i] - m0;
+    const float mean = m0 + wave_sum(c) / (float)D;
     float ss = 0.f;
     for (int i = lane; i < D; i += 64) { const float d = xr[i] - mean; ss += d * d; }
     const float rstd = 1.0f / sqrtf(wave_sum(ss) / (float)D + eps);
@@ -1042,7 +1048,15 @@ __global__ __launch_bounds__(256) void ln_bwd_ex_kernel(const float* __restrict_
             dv[i] = ok ? dr_[lane + i * 64] : z4;
             s += (xv[i][0] + xv[i][1]) + (xv[i][2] + xv[i][3]);
         }
-        const float mean = wave_sum(s) * invD;
+        const float m0 = wave_sum(s) * invD;         // two-step mean (see ln_bwd_kernel): a constant row must give xhat = 0 exactly
+        float c = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+            if (lane + i * 64 < nq) {
+                const f4 d = xv[i] - m0;
+                c += (d[0] + d[1]) + (d[2] + d[3]);
+            }
+        const float mean = m0 + wave_sum(c) * invD;
         float ss = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i)
