@@ -3,15 +3,17 @@
 // (data_loader/lmdb_loader_BEAT_full.py:229).  librosa defaults: centred frames with zero padding, periodic Hann,
 // Slaney mel basis (fmin 0, fmax sr/2, slaney norm), amin 1e-10, top_db 80.
 //
-// kernel 1: one workgroup per (frame, clip): the 1024-sample window is staged in LDS straight from the clip
-//           (coalesced 4-byte loads, hop 512 => each sample is read by two frames, L2 absorbs it), radix-2 FFT in LDS
-//           (10 stages x 512 butterflies, 2 per thread), |X|^2, then the 128x513 mel projection against the transposed
-//           filter table [513][128] (coalesced over the mel index).
+// kernel 1: one workgroup per (frame pair, clip): the two windowed frames go from the clip straight into registers (coalesced 4-byte loads,
+//           hop 512 => each sample is read by two pairs, L2 absorbs it), one 1024-point complex radix-4 Stockham FFT with four points per
+//           thread in registers (5 passes, 8-byte LDS exchanges, twiddles from an LDS copy of the table), |X|^2, then the banded 128x513 mel
+//           projection against the transposed filter table [513][128].  EG_MEL_FFT=2 keeps the earlier all-in-LDS radix-2 kernel for A/B runs.
 // kernel 2: one workgroup per clip: max reduction, dB, floor, fp16 rounding, slice.
 #include "common.h"
 #include "beat_shared.h"
 #include <hip/hip_fp16.h>
 #include <math.h>
+#include <stdlib.h>
+#include <string.h>
 
 namespace {
 
@@ -19,9 +21,10 @@ namespace {
 // as X0[k] = (Z[k] + conj Z[N-k]) / 2, X1[k] = (Z[k] - conj Z[N-k]) / 2i.  Halves the butterflies per frame (the first version transformed one
 // real frame with a zero imaginary part).  The cross-talk between the two frames is bounded by fp32 round-off of the louder one (power floor
 // ~4e-15 of its power: 60 dB below the 80 dB clamp of power_to_db).
-__global__ __launch_bounds__(256) void mel_power_kernel(const float* __restrict__ audio, int n_samples, const float* __restrict__ melfb_t,
-                                                        const float* __restrict__ window, const float* __restrict__ twiddle,
-                                                        const int* __restrict__ band, float* __restrict__ melpow, int n_frames) {
+// Radix-2 form (EG_MEL_FFT=2, this round's A/B reference): everything in LDS, bit-reversed staging, 10 stages of 512 butterflies.
+__global__ __launch_bounds__(256) void mel_power_radix2_kernel(const float* __restrict__ audio, int n_samples, const float* __restrict__ melfb_t,
+                                                               const float* __restrict__ window, const float* __restrict__ twiddle,
+                                                               const int* __restrict__ band, float* __restrict__ melpow, int n_frames) {
     __shared__ float re[1024], im[1024];
     const int f0 = blockIdx.x * 2, f1 = f0 + 1, b = blockIdx.y, tid = threadIdx.x;
     const float* clip = audio + (size_t)b * n_samples;
@@ -76,6 +79,149 @@ __global__ __launch_bounds__(256) void mel_power_kernel(const float* __restrict_
     const int b0 = band[2 * m], b1 = band[2 * m + 1];
     float s = 0.f;
     for (int k = b0; k < b1; ++k) s += melfb_t[k * 128 + m] * pw[k];
+    if (f < n_frames) melpow[((size_t)b * 128 + m) * n_frames + f] = s;
+}
+
+// ---- radix-4 Stockham transform, four points per thread in registers -------------------------------------------------------------------
+// Pass p (NS = 4^p, p = 0..4), thread j = 0..255:  v[r] = in[j + 256 r] * exp(-2 pi i r k / (4 NS)),  k = j mod NS;  4-point DFT of v;
+// out[4 (j - k) + k + r NS] = y[r].  After the fifth pass `out` is the spectrum in natural order (autosort: no digit reversal anywhere).
+// Pass 0 has k = 0 (no twiddle) and its inputs j + 256 r are the coalesced global loads themselves, so nothing is staged.
+//
+// Exchange layout: complex element i lives in float2 slot i ^ (5 * ((i >> 4) & 3)) -- bits 4..5 of i are XORed into bits 0..1 and 2..3.
+// Bank arithmetic (8-byte accesses; a write is served in groups of 16 consecutive lanes over 32 four-byte banks, so a group is conflict-free
+// when its 16 slots differ mod 16; a read in groups of 32 lanes over 64 banks, conflict-free when its 32 slots differ mod 32):
+//   reads  i = j + 256 r: a group's 32 lanes cover one aligned run of 32 elements; the swizzle permutes each aligned 16 within itself -> distinct.
+//   writes NS = 1:  i = 4 j + r; lanes l = 0..15 of a group have i mod 16 = 4 (l & 3) + r, four lanes per residue (4-way) unswizzled;
+//                   bits 4..5 of i are l >> 2, so the slot mod 16 is 4 ((l & 3) ^ (l >> 2)) + (r ^ (l >> 2)) -> distinct.
+//   writes NS = 4:  i = 16 (j >> 2) + (j & 3) + 4 r; i mod 16 = (l & 3) + 4 r (4-way unswizzled), bits 4..5 = l >> 2, slot mod 16 =
+//                   ((l & 3) ^ (l >> 2)) + 4 (r ^ (l >> 2)) -> distinct.
+//   writes NS >= 16: a group's 16 lanes write one aligned run of 16 elements -> distinct.
+__device__ __forceinline__ int fft_slot(int i) { return i ^ (5 * ((i >> 4) & 3)); }
+
+__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+
+// the three twiddles of pass NS for thread j: exp(-2 pi i r t / 1024), t = k * 256 / NS, r = 1..3.  The table holds t < 512; 3 t can reach 765,
+// and exp(-2 pi i (t + 512) / 1024) = -exp(-2 pi i t / 1024) exactly.
+// `tw` is the workgroup's LDS copy of the table, entry t in slot t + (t >> 4): one pad per 16 entries takes the strides 16, 32 and 48 of pass 16
+// (16-way on one bank unpadded) apart; what is left is 4-way in pass 64 and 3-way in pass 256 on 12 reads per thread in all, counted by
+// tools/mel_fft_walk.py (twiddle_read_conflicts).
+__device__ __forceinline__ int tw_slot(int t) { return t + (t >> 4); }
+template <int NS>
+__device__ __forceinline__ void fft_twiddles(const float2* tw, int j, float2 (&w)[3]) {
+    const int t = (j & (NS - 1)) * (256 / NS), t3 = 3 * t;
+    w[0] = tw[tw_slot(t)];
+    w[1] = tw[tw_slot(2 * t)];
+    const float2 x = tw[tw_slot(t3 & 511)];
+    w[2] = t3 < 512 ? x : make_float2(-x.x, -x.y);
+}
+
+template <int NS>
+__device__ __forceinline__ void fft_pass(float2 (&v)[4], const float2 (&w)[3], float2* __restrict__ out, int j) {
+    if (NS > 1) {
+#pragma unroll
+        for (int r = 1; r < 4; ++r) v[r] = cmul(v[r], w[r - 1]);
+    }
+    const float2 a0 = make_float2(v[0].x + v[2].x, v[0].y + v[2].y), a1 = make_float2(v[0].x - v[2].x, v[0].y - v[2].y);
+    const float2 a2 = make_float2(v[1].x + v[3].x, v[1].y + v[3].y), a3 = make_float2(v[1].y - v[3].y, v[3].x - v[1].x);      // -i (v1 - v3)
+    const int k = j & (NS - 1), base = ((j - k) << 2) + k;
+    out[fft_slot(base)] = make_float2(a0.x + a2.x, a0.y + a2.y);
+    out[fft_slot(base + NS)] = make_float2(a1.x + a3.x, a1.y + a3.y);
+    out[fft_slot(base + 2 * NS)] = make_float2(a0.x - a2.x, a0.y - a2.y);
+    out[fft_slot(base + 3 * NS)] = make_float2(a1.x - a3.x, a1.y - a3.y);
+}
+
+__device__ __forceinline__ void fft_gather(float2 (&v)[4], const float2* __restrict__ in, int j) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = in[fft_slot(j + 256 * r)];
+}
+
+__global__ __launch_bounds__(256) void mel_power_kernel(const float* __restrict__ audio, int n_samples, const float* __restrict__ melfb_t,
+                                                        const float* __restrict__ window, const float* __restrict__ twiddle,
+                                                        const int* __restrict__ band, float* __restrict__ melpow, int n_frames) {
+    __shared__ float2 za[1024], zb[1024];          // ping-pong: one barrier per exchange
+    const int f0 = blockIdx.x * 2, f1 = f0 + 1, b = blockIdx.y, tid = threadIdx.x;
+    const float* clip = audio + (size_t)b * n_samples;
+    // sample i = tid + 256 q of frame f0 is clip[s0 + 256 q]; of frame f1 it is clip[s0 + 512 + 256 q]: six distinct loads for the eight points
+    float raw[6];
+    const int s0 = f0 * 512 - 512 + tid;
+#pragma unroll
+    for (int u = 0; u < 6; ++u) {
+        const int s = s0 + 256 * u;
+        raw[u] = (s >= 0 && s < n_samples) ? clip[s] : 0.f;
+    }
+    float2 v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float wv = window[tid + 256 * q];
+        v[q] = make_float2(raw[q] * wv, f1 < n_frames ? raw[q + 2] * wv : 0.f);
+    }
+    // the twiddle table goes to LDS once per workgroup (two coalesced 8-byte loads per thread; zb is free until the second pass writes it)
+    {
+        const float2* tw = reinterpret_cast<const float2*>(twiddle);
+        const float2 ta = tw[tid], tb = tw[tid + 256];
+        zb[tw_slot(tid)] = ta;
+        zb[tw_slot(tid + 256)] = tb;
+    }
+    // projection: thread (m = tid >> 1, frame = tid & 1) -- the two frames of a mel in neighbouring lanes read the same filter value, so a wave's
+    // filter loads ask for 32 different table lines, not 64; the band limits are requested here, ahead of the transform
+    const int m = tid >> 1, fr = tid & 1, f = f0 + fr;
+    const int b0 = band[2 * m], b1 = band[2 * m + 1];
+    __syncthreads();
+    // every pass's twiddles depend on tid alone: read once into registers; the barrier after the first pass orders these reads before the
+    // second pass's writes to zb
+    float2 w1[3], w2[3], w3[3], w4[3];
+    fft_twiddles<4>(zb, tid, w1);
+    fft_twiddles<16>(zb, tid, w2);
+    fft_twiddles<64>(zb, tid, w3);
+    fft_twiddles<256>(zb, tid, w4);
+    float2 none[3];
+    fft_pass<1>(v, none, za, tid);
+    __syncthreads();
+    fft_gather(v, za, tid);
+    fft_pass<4>(v, w1, zb, tid);
+    __syncthreads();
+    fft_gather(v, zb, tid);
+    fft_pass<16>(v, w2, za, tid);
+    __syncthreads();
+    fft_gather(v, za, tid);
+    fft_pass<64>(v, w3, zb, tid);
+    __syncthreads();
+    fft_gather(v, zb, tid);
+    fft_pass<256>(v, w4, za, tid);
+    __syncthreads();
+    // power spectra of the two frames, bins 0..512: thread tid takes k = tid, tid + 256 (and 512 on thread 0)
+    float pa[3], pb[3];
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+        const int k = u < 2 ? tid + u * 256 : 512, nk = (1024 - k) & 1023;
+        pa[u] = pb[u] = 0.f;
+        if (u < 2 || tid == 0) {
+            const float2 z = za[fft_slot(k)], y = za[fft_slot(nk)];
+            const float r0 = 0.5f * (z.x + y.x), i0 = 0.5f * (z.y - y.y);      // X0[k]
+            const float r1 = 0.5f * (z.y + y.y), i1 = 0.5f * (y.x - z.x);      // X1[k]
+            pa[u] = r0 * r0 + i0 * i0;
+            pb[u] = r1 * r1 + i1 * i1;
+        }
+    }
+    // zb is free: its last readers passed the barrier above.  Powers in bin order, frame f0 then frame f1.
+    float* re = reinterpret_cast<float*>(zb);
+    float* im = re + 1024;
+    re[tid] = pa[0]; re[tid + 256] = pa[1];
+    im[tid] = pb[0]; im[tid + 256] = pb[1];
+    if (tid == 0) { re[512] = pa[2]; im[512] = pb[2]; }
+    __syncthreads();
+    // mel projection, each sum in bin order as in the radix-2 form.  Eight filter loads are in flight at a time (the widest band has 24 bins:
+    // three round trips to the table instead of one per bin)
+    const float* pw = fr ? im : re;
+    float s = 0.f;
+    for (int k0 = b0; k0 < b1; k0 += 8) {
+        float wv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) wv[u] = k0 + u < b1 ? melfb_t[(k0 + u) * 128 + m] : 0.f;
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (k0 + u < b1) s += wv[u] * pw[k0 + u];
+    }
     if (f < n_frames) melpow[((size_t)b * 128 + m) * n_frames + f] = s;
 }
 
@@ -174,10 +320,19 @@ extern "C" int eg_melspectrogram(const float* audio, int32_t batch, int32_t n_sa
     const int n_frames = 1 + n_samples / 512;
     EG_REQUIRE(out_frames > 0 && out_frames <= n_frames, EG_ERR_BAD_ARG, "eg_melspectrogram: out_frames=%d of %d", out_frames, n_frames);
     EG_REQUIRE(workspace_bytes >= eg_mel_workspace_bytes(batch, n_samples), EG_ERR_WORKSPACE, "eg_melspectrogram: workspace too small");
+    // EG_MEL_FFT (read per call, like EG_GEMM_TILE): unset, empty or "4" = the register radix-4 transform; "2" = the radix-2 LDS transform
+    // (A/B runs and the accuracy comparison of tests/test_gpu_mel_fft.py, this round only).  Anything else is refused before any launch.
+    const char* fft = getenv("EG_MEL_FFT");
+    const bool radix2 = fft && !strcmp(fft, "2");
+    EG_REQUIRE(!fft || !fft[0] || radix2 || !strcmp(fft, "4"), EG_ERR_BAD_ARG, "EG_MEL_FFT=\"%s\": accepted values are \"4\" and \"2\" (unset or empty: 4)", fft);
     hipStream_t st = (hipStream_t)stream;
     float* melpow = reinterpret_cast<float*>(workspace);
-    hipLaunchKernelGGL(mel_power_kernel, dim3((n_frames + 1) / 2, batch), dim3(256), 0, st, audio, n_samples, d_melfb_t, d_window, d_twiddle,
-                       d_band, melpow, n_frames);
+    if (radix2)
+        hipLaunchKernelGGL(mel_power_radix2_kernel, dim3((n_frames + 1) / 2, batch), dim3(256), 0, st, audio, n_samples, d_melfb_t, d_window,
+                           d_twiddle, d_band, melpow, n_frames);
+    else
+        hipLaunchKernelGGL(mel_power_kernel, dim3((n_frames + 1) / 2, batch), dim3(256), 0, st, audio, n_samples, d_melfb_t, d_window, d_twiddle,
+                           d_band, melpow, n_frames);
     int rc = eg_check_launch("mel_power");
     if (rc) return rc;
     hipLaunchKernelGGL(mel_db_kernel, dim3(batch), dim3(1024), 0, st, melpow, spec, n_frames, out_frames);

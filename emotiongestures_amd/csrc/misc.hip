@@ -1,6 +1,8 @@
 // Small kernels of the generator: LayerNorm, embedding gather, row-periodic add,
 // TCN time-axis Linear, prior/memory encoder, CVAE conv1d / convT1d, reparameterise.
 #include "common.h"
+#include <stdlib.h>
+#include <string.h>
 
 namespace {
 
@@ -171,7 +173,9 @@ __global__ __launch_bounds__(256) void add_img_kernel(const f4* __restrict__ a, 
 
 // ---- TextEncoderTCN.fc1: Linear over the time axis (Models_spatial_memory.py:164-166,176) -----------------
 // x, y [B, L, C] channels-last:  y[b,t',c] = bias[t'] + sum_t W[t',t] x[b,t,c]
-__global__ __launch_bounds__(256) void time_linear_kernel(const float* __restrict__ x, const float* __restrict__ w,
+// Reference form (EG_TIME_LINEAR=ref, this round's A/B and bit-equality reference): W and x in LDS, one output row at a time, two LDS reads
+// per multiply-add.
+__global__ __launch_bounds__(256) void time_linear_ref_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                           const float* __restrict__ bias, float* __restrict__ y, int L, int C, int ld) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* Ws = sm;             // [L][L]
@@ -190,6 +194,86 @@ __global__ __launch_bounds__(256) void time_linear_kernel(const float* __restric
         for (int t = 0; t < L; ++t) s += Ws[tp * L + t] * Xs[t * 64 + c];
         y[((size_t)b * L + tp) * ld + c0 + c] = s;
     }
+}
+
+// R output rows tp0, tp0 + 4, ... of one wave, accumulated together: per four values of t a thread reads four x values (one LDS read each,
+// serving R multiply-adds apiece) and R weight quads, each ONE 16-byte LDS read whose address is the same in every lane (tp0 is wave-uniform: a
+// broadcast, 4 LDS cycles for 4 R multiply-adds).  Per output element the sum is the reference kernel's: bias first, then t ascending, one
+// multiply-add per term -- bit-equal.  Ws rows are Lp = round_up(L, 4) floats apart, so every quad is 16-byte aligned.
+template <int R>
+__device__ __forceinline__ void time_linear_rows(const float* Ws, const float* Xs, const float* __restrict__ bias, float* __restrict__ yc, int tp0,
+                                                 int L, int Lp, int ld, int c) {
+    float acc[R];
+#pragma unroll
+    for (int k = 0; k < R; ++k) acc[k] = bias[tp0 + 4 * k];
+    const float* wr = Ws + tp0 * Lp;
+    const int L4 = L & ~3;
+    int t = 0;
+#pragma unroll 2
+    for (; t < L4; t += 4) {
+        float xv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) xv[u] = Xs[(t + u) * 64 + c];
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            const f4 wv = *reinterpret_cast<const f4*>(wr + 4 * k * Lp + t);
+            acc[k] += wv.x * xv[0];
+            acc[k] += wv.y * xv[1];
+            acc[k] += wv.z * xv[2];
+            acc[k] += wv.w * xv[3];
+        }
+    }
+    for (; t < L; ++t) {
+        const float xv = Xs[t * 64 + c];
+#pragma unroll
+        for (int k = 0; k < R; ++k) acc[k] += wr[4 * k * Lp + t] * xv;
+    }
+#pragma unroll
+    for (int k = 0; k < R; ++k) yc[(size_t)(tp0 + 4 * k) * ld] = acc[k];
+}
+
+// Same grid and row ownership as the reference form (64 channels x clip per workgroup; wave v owns rows v, v + 4, ...).  A thread keeps its rows'
+// sums in registers, fifteen at a time (L = 60: all of a wave's rows in one walk over t), then five, then one, so any L works.  W and x are staged
+// with up to 32 loads in flight per thread (the reference form's one-at-a-time copy loop pays a memory latency per element).
+__global__ __launch_bounds__(256) void time_linear_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                          const float* __restrict__ bias, float* __restrict__ y, int L, int C, int ld) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int Lp = (L + 3) & ~3;
+    float* Ws = sm;             // [L][Lp]
+    float* Xs = sm + L * Lp;    // [L][64]
+    const int b = blockIdx.y, c0 = blockIdx.x * 64, tid = threadIdx.x, c = tid & 63;
+    const bool live = c0 + c < C;
+    const float* xc = x + (size_t)b * L * ld + c0 + c;
+    for (int i0 = tid; i0 < L * max(L, 64); i0 += 16 * 256) {
+        float vx[16], vw[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int i = i0 + u * 256;
+            vx[u] = (live && i < L * 64) ? xc[(size_t)(i >> 6) * ld] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int i = i0 + u * 256;
+            vw[u] = i < L * L ? w[i] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int i = i0 + u * 256;
+            if (i < L * 64) Xs[i] = vx[u];
+        }
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int i = i0 + u * 256, r = i / L;
+            if (i < L * L) Ws[r * Lp + (i - r * L)] = vw[u];
+        }
+    }
+    __syncthreads();
+    int tp = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (!live) return;
+    float* yc = y + (size_t)b * L * ld + c0 + c;
+    for (; tp + 56 < L; tp += 60) time_linear_rows<15>(Ws, Xs, bias, yc, tp, L, Lp, ld, c);
+    for (; tp + 16 < L; tp += 20) time_linear_rows<5>(Ws, Xs, bias, yc, tp, L, Lp, ld, c);
+    for (; tp < L; tp += 4) time_linear_rows<1>(Ws, Xs, bias, yc, tp, L, Lp, ld, c);
 }
 
 // ---- Prior_MemoryEncoder front half (Models_spatial_memory.py:366-390; Models_memory.py:233-251,282-287) ---
@@ -880,10 +964,26 @@ int egi_add_bcast(const float* a, const float* b, float* out, size_t rows, int r
                        reinterpret_cast<const f4*>(b), reinterpret_cast<f4*>(out), n4, row_len / 4, period, rep);
     return eg_check_launch("add_bcast");
 }
+// EG_TIME_LINEAR (read per call, like EG_GEMM_TILE): unset or empty = the register-blocked kernel; "ref" = the reference form (A/B runs and the
+// bit-equality check of tests/test_gpu_time_linear_blocked.py, this round only).  Anything else is refused before any launch.
 int egi_time_linear(const float* x, const float* w, const float* bias, float* y, int batch, int L, int C, int ld, hipStream_t st) {
-    const size_t smem = sizeof(float) * ((size_t)L * L + (size_t)L * 64);
-    hipLaunchKernelGGL(time_linear_kernel, dim3(eg_cdiv(C, 64), batch), dim3(256), smem, st, x, w, bias, y, L, C, ld);
+    const char* e = getenv("EG_TIME_LINEAR");
+    const bool ref = e && !strcmp(e, "ref");
+    EG_REQUIRE(!e || !e[0] || ref, EG_ERR_BAD_ARG, "EG_TIME_LINEAR=\"%s\": the only accepted value is \"ref\" (unset or empty: register-blocked)", e);
+    const size_t smem = sizeof(float) * ((size_t)L * (ref ? L : (L + 3) & ~3) + (size_t)L * 64);
+    EG_REQUIRE(smem <= 65536, EG_ERR_UNSUPPORTED, "time_linear: L=%d needs %zu bytes of LDS", L, smem);
+    if (ref)
+        hipLaunchKernelGGL(time_linear_ref_kernel, dim3(eg_cdiv(C, 64), batch), dim3(256), smem, st, x, w, bias, y, L, C, ld);
+    else
+        hipLaunchKernelGGL(time_linear_kernel, dim3(eg_cdiv(C, 64), batch), dim3(256), smem, st, x, w, bias, y, L, C, ld);
     return eg_check_launch("time_linear");
+}
+// TextEncoderTCN.fc1 on its own (the generator calls egi_time_linear directly)
+extern "C" int eg_time_linear(const float* x, const float* w, const float* bias, float* y, int32_t batch, int32_t len, int32_t c, int32_t ld,
+                              void* stream) {
+    EG_REQUIRE(x && w && bias && y, EG_ERR_BAD_ARG, "eg_time_linear: null pointer");
+    EG_REQUIRE(batch > 0 && len > 0 && c > 0 && ld >= c, EG_ERR_BAD_ARG, "eg_time_linear: batch=%d len=%d c=%d ld=%d", batch, len, c, ld);
+    return egi_time_linear(x, w, bias, y, batch, len, c, ld, (hipStream_t)stream);
 }
 int egi_copy2d(const float* src, int lds_, float* dst, int ldd, int rows, int cols, hipStream_t st) {
     hipLaunchKernelGGL(copy2d_kernel, dim3(grid_for((size_t)rows * cols)), dim3(256), 0, st, src, lds_, dst, ldd, rows, cols);

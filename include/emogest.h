@@ -388,7 +388,9 @@ int eg_cvae_forward(const EgCvae* c, const float* arena, int32_t n, const float*
  * n_fft 1024, hop 512, centred (zero pad), periodic Hann, 128 Slaney mels, power_to_db(ref=max, top_db=80).
  * d_melfb_t [513,128] (transposed filterbank), d_window [1024], d_twiddle [512,2], d_band [128,2] are caller-provided
  * device copies of the tables eg_mel_tables fills on the host.
- * workspace >= eg_mel_workspace_bytes. */
+ * workspace >= eg_mel_workspace_bytes.
+ * EG_MEL_FFT (read per call): unset, empty or "4" = the register radix-4 transform; "2" = the radix-2 LDS transform it replaces (A/B runs);
+ * any other value is EG_ERR_BAD_ARG before any launch. */
 int eg_mel_tables(float* h_melfb_t /*513*128, transposed*/, float* h_window /*1024*/, float* h_twiddle /*2*512*/,
                   int32_t* h_band /*128*2: non-zero bin range of each mel filter*/);
 int64_t eg_mel_workspace_bytes(int32_t batch, int32_t n_samples);
@@ -852,6 +854,13 @@ int eg_add_rows_split(const float* a, const float* table, float* out, void* imag
 /* out[r,:] = a[r,:] + table[r % period,:]  (PositionalEncoding.forward, Full_model/Models_spatial_memory.py:46-48);
  * period == 0: plain elementwise add of two [rows, d] tensors (fusion add, :601-605).  d % 4 == 0. */
 int eg_add_rows(const float* a, const float* table, float* out, int64_t rows, int32_t d, int32_t period, void* stream);
+
+/* TextEncoderTCN.fc1, a Linear over the time axis of channels-last rows (Full_model/Models_spatial_memory.py:164-166,176):
+ * y[b,t',ch] = bias[t'] + sum_t w[t',t] x[b,t,ch];  x, y [batch, len, ld] with c <= ld used channels, w [len, len], bias [len].  Each output
+ * element is summed bias first, then t ascending, one multiply-add per term.  len * (round_up(len, 4) + 64) floats of LDS must fit 64 KB
+ * (len <= 99), else EG_ERR_UNSUPPORTED.
+ * EG_TIME_LINEAR=ref (read per call) selects the one-row-at-a-time reference kernel; any other non-empty value is EG_ERR_BAD_ARG. */
+int eg_time_linear(const float* x, const float* w, const float* bias, float* y, int32_t batch, int32_t len, int32_t c, int32_t ld, void* stream);
 
 /* VAE reparameterisation (CAVE/BEAT_CVAE.py:397-399): z = eps*exp(0.5*logvar) + mu, n elements. */
 int eg_reparameterize(const float* mu, const float* logvar, const float* eps, float* z, int64_t n, void* stream);
