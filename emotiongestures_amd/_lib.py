@@ -89,6 +89,10 @@ SIGNATURES = {
     "eg_rollout_ragged_plan": (C.c_int, [_P, _I, _P, _P, _P, _P]),
     "eg_generator_forward_rollout_ragged": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "eg_generator_rollout_ragged_workspace_bytes": (_L, [_P, _I, _L]),
+    "eg_rollout_takes_plan_ints": (_L, [_I, _L]),
+    "eg_rollout_takes_plan": (C.c_int, [_P, _I, _P, _P, _P, _P]),
+    "eg_generator_forward_rollout_takes": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "eg_generator_rollout_takes_workspace_bytes": (_L, [_P, _I, _L, _I]),
     "eg_stream_state_bytes": (_L, [_P, _I, _I, _I]),
     "eg_stream_reset": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "eg_stream_push": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),

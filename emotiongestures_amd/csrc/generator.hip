@@ -979,13 +979,21 @@ extern "C" int eg_generator_forward_draws(const EgGenerator* g, const float* are
 // runs the dependent steps: prior encoder -> decoder over that step's K|V slice -> post_projector -> hand-off.  The rectangular call
 // (W windows each), the ragged call (W_u windows, kernels: ragged.hip) and the diverse call (R >= 2 sampled tracks per recording, kernels:
 // draws.hip) differ in five places only: the row order in and out, the fusion input, the encoder / K|V rows (N*R), step 0's prior, and the
-// step batch with its hand-off.
+// step batch with its hand-off.  The takes call (R >= 2 draws of recordings with W_u windows: a RollPlan with a table AND R > 1) is the
+// product of the last two and a sixth variant of the same five places: the ragged row order, and the fusion input, step 0's prior and the
+// hand-off by table and by draw (kernels: draws.hip); its step batch is active*R rows, row rank*R + r.
 int egi_draws_fusion(const float* sampled, const float* semantic, float* fus_in, int U, int W, int R, size_t clip_floats, hipStream_t st);
 int egi_draws_seed(const float* seed, float* prior, int U, int R, int PD, hipStream_t st);
+int egi_takes_fusion(const float* sampled, const float* semantic, float* fus_in, const int32_t* table, int N, int U, int R, size_t clip_floats,
+                     hipStream_t st);
+int egi_takes_seed(const float* seed, float* prior, const int32_t* order, int U, int R, int PD, hipStream_t st);
+int egi_takes_handoff(const float* pose, const float* prior_in, const float* alpha, float* track, float* windows, float* prior_out,
+                      const int32_t* table, int N, int U, int R, int active, int Wmax, int s, int F, int P, int D, hipStream_t st);
 namespace {
 struct RollPlan {
     int U, R, N, steps;             // recordings, draws per recording, clips in all, dependent steps (W, or the longest recording's W_u)
-    const int32_t* plan;            // ragged: the device table (slot -> packed row [N] | rank -> recording [U] | ...); null: a rectangle
+    const int32_t* plan;            // ragged: the device table (slot -> packed row [N] | rank -> recording [U] | ...; with R > 1 the takes
+                                    // plan, which adds slot -> rank [N]); null: a rectangle
     const int32_t* windows_per;     // ragged, host: W_u
     const int32_t* order;           // ragged, host: rank -> recording, longer first, ties by index
     bool same_order;                // step order and the caller's order of the window-indexed rows coincide: nothing is moved
@@ -1028,7 +1036,7 @@ int roll_rows(const RollPlan& p, const void* in, void* out, size_t words, bool b
 }
 
 // Phase A, batch N (clip n = w*U + u of a rectangle, slot (s, rank) after the slots of the steps before it in a ragged call); from the
-// fusion on N*R rows, (clip, draw) row n*R + r.  Leaves kv[l] = [N*R*F, 2*d_model], the decoder layers' K|V of every step.
+// fusion on N*R rows, (clip, draw) row n*R + r (takes: slot*R + r).  Leaves kv[l] = [N*R*F, 2*d_model], the decoder layers' K|V of every step.
 int rollout_phase_a(const EgGenerator* g, const float* arena, const RollPlan& p, const RollWs& r, void* ws, const float* spec,
                     const int64_t* text, const float* sampled, float* emotion_prediction, float* emotion_feature, float* semantic_feature,
                     float* text_embedding, float** kv, hipStream_t st) {
@@ -1060,7 +1068,8 @@ int rollout_phase_a(const EgGenerator* g, const float* arena, const RollPlan& p,
     if (p.R == 1) {
         fus_in = fusion_act(g, w, ws);
         EG_TRY(egi_add_img(sampled ? sampled : emo, sem, fus_in.f, fus_in.img, (size_t)N * F * D, D, 0, st));
-    } else EG_TRY(egi_draws_fusion(sampled, sem, fus_in.f, p.U, p.steps, p.R, (size_t)F * D, st));
+    } else if (p.plan) EG_TRY(egi_takes_fusion(sampled, sem, fus_in.f, p.plan, N, p.U, p.R, (size_t)F * D, st));
+    else EG_TRY(egi_draws_fusion(sampled, sem, fus_in.f, p.U, p.steps, p.R, (size_t)F * D, st));
     Act enc_out;
     EG_TRY(run_encoder(g, arena, fus_in, enc_out, w, ws, NR, st));
     for (int l = 0; l < c.n_layers; ++l) {
@@ -1077,7 +1086,8 @@ int rollout_phase_a(const EgGenerator* g, const float* arena, const RollPlan& p,
 }
 
 // Phase B: p.steps dependent steps.  A rectangle runs U*R rows in every step (row u*R + r: draw r of recording u); a ragged call runs the
-// recordings with W_u > s, the first ranks of its order, so a step's K|V slice starts at the running sum of the step batches.  The priors
+// recordings with W_u > s, the first ranks of its order (times R draws, row rank*R + r, in a takes call), so a step's K|V slice starts at
+// the running sum of the step batches.  The priors
 // ping-pong between two buffers; step 0 reads seed_pose itself, or a copy in the steps' row order in the buffer step 0 does not write.
 int rollout_phase_b(const EgGenerator* g, const float* arena, const RollPlan& p, const RollWs& r, void* ws, float* const* kv,
                     const float* seed_pose, const float* alpha, float* track, float* windows, hipStream_t st) {
@@ -1085,25 +1095,29 @@ int rollout_phase_b(const EgGenerator* g, const float* arena, const RollPlan& p,
     const GenWs& w = r.a;
     const int F = c.frames, D = c.d_model, P_ = c.prior_frames, PD = c.pose_dim;
     const float* prior = seed_pose;
-    if (p.R > 1) {              // seed_pose[u] repeated over the draws by one launch
-        EG_TRY(egi_draws_seed(seed_pose, P(ws, r.prior[1]), p.U, p.R, P_ * PD, st));
+    if (p.R > 1) {              // seed_pose[u] repeated over the draws by one launch (takes: gathered into rank order by the same launch)
+        if (p.plan) EG_TRY(egi_takes_seed(seed_pose, P(ws, r.prior[1]), p.plan + p.N, p.U, p.R, P_ * PD, st));
+        else EG_TRY(egi_draws_seed(seed_pose, P(ws, r.prior[1]), p.U, p.R, P_ * PD, st));
         prior = P(ws, r.prior[1]);
     } else if (!p.seed_in_order) {
         EG_TRY(egi_rows_by_table(seed_pose, P(ws, r.prior[1]), p.plan + p.N, p.U, (size_t)P_ * PD, false, st));
         prior = P(ws, r.prior[1]);
     }
     const Act prior_enc = act(P(ws, w.prior_enc), D, P(ws, w.im_p[1]), D);
-    int batch = p.U * p.R;
+    int active = p.U;           // recordings in the step
     size_t slot = 0;
     for (int s = 0; s < p.steps; ++s) {
         if (p.plan)
-            while (batch > 0 && p.windows_per[p.order[batch - 1]] <= s) --batch;
+            while (active > 0 && p.windows_per[p.order[active - 1]] <= s) --active;
+        const int batch = active * p.R;
         EG_TRY(run_prior(g, arena, prior, w, ws, batch, st));
         float* step_kv[8];
         for (int l = 0; l < c.n_layers; ++l) step_kv[l] = kv[l] + slot * F * 2 * D;
         EG_TRY(run_decoder(g, arena, prior_enc, Act(), step_kv, P(ws, w.pose), w, ws, batch, st));
         float* next = P(ws, r.prior[s & 1]);
-        if (p.plan)
+        if (p.plan && p.R > 1)
+            EG_TRY(egi_takes_handoff(P(ws, w.pose), prior, alpha, track, windows, next, p.plan, p.N, p.U, p.R, active, p.steps, s, F, P_, PD, st));
+        else if (p.plan)
             EG_TRY(egi_rollout_handoff_ragged(P(ws, w.pose), prior, alpha, track, windows, next, p.plan, p.N, p.U, batch, p.steps, s, F, P_, PD, st));
         else
             EG_TRY(egi_rollout_handoff(P(ws, w.pose), prior, alpha, track, windows, next, batch, p.steps, s, F, P_, PD, st));
@@ -1111,6 +1125,15 @@ int rollout_phase_b(const EgGenerator* g, const float* arena, const RollPlan& p,
         slot += (size_t)batch;
     }
     return EG_OK;
+}
+
+// The working order of a ragged or takes call (longer first, ties by index): the active recordings of every step are its first U_s ranks,
+// and a recording keeps its rank, the row of its prior, for its whole life
+std::vector<int32_t> working_order(const int32_t* windows_per, int U) {
+    std::vector<int32_t> order(U);
+    for (int u = 0; u < U; ++u) order[u] = u;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return windows_per[a] > windows_per[b]; });
+    return order;
 }
 }  // namespace
 
@@ -1206,15 +1229,59 @@ extern "C" int eg_generator_forward_rollout_ragged(const EgGenerator* g, const f
                (long long)r.total);
     EG_REQUIRE(eg_aligned16(ws) && eg_aligned16(arena) && eg_aligned16(spec) && (reinterpret_cast<uintptr_t>(plan) & 3u) == 0, EG_ERR_ALIGN,
                "eg_generator_forward_rollout_ragged: 16-byte alignment (plan: 4-byte)");
-    // the working order (longer first, ties by index): the active recordings of every step are its first U_s ranks, and a recording keeps
-    // its rank, the row of its prior, for its whole life
-    std::vector<int32_t> order(U);
-    for (int u = 0; u < U; ++u) order[u] = u;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return windows_per[a] > windows_per[b]; });
+    const std::vector<int32_t> order = working_order(windows_per, U);
     bool sorted = true;
     for (int u = 0; u < U; ++u) sorted = sorted && order[u] == u;
     // U == 1 or Wmax == 1: step-major and packed recording-major order coincide (slot_row is the identity)
     const RollPlan p = {U, 1, (int)N64, Wmax, plan, windows_per, order.data(), U == 1 || Wmax == 1, sorted};
+    hipStream_t st = (hipStream_t)stream;
+    float* kv[8];
+    EG_TRY(rollout_phase_a(g, arena, p, r, ws, spec, text, sampled, emotion_prediction, emotion_feature, semantic_feature, text_embedding, kv, st));
+    return rollout_phase_b(g, arena, p, r, ws, kv, seed_pose, alpha, track, windows, st);
+}
+
+extern "C" int64_t eg_generator_rollout_takes_workspace_bytes(const EgGenerator* g, int32_t utterances, int64_t total_windows, int32_t draws) {
+    if (!g || utterances <= 0 || total_windows < utterances || draws <= 0 || g->cfg.n_layers > 8) return 0;
+    if (total_windows > (1 << 20) || total_windows * draws > (1 << 20)) return 0;
+    return carve_rollout(g, utterances, total_windows, draws).total;
+}
+
+// The ragged roll-out on the U*R replicated recordings, recording u*R + r having the inputs and W_u of u and its own sampled maps, with
+// the tower side run once per window as in eg_generator_forward_rollout_draws.  The replicated call's working order is rank*R + r (the R
+// copies of a recording tie and keep their index order), so slot (s, rank, r) is its slot*R + r: row slot*R + r of the fusion, the encoder
+// and the K|V slices, and row rank*R + r of every step, are the replicated call's rows.
+extern "C" int eg_generator_forward_rollout_takes(const EgGenerator* g, const float* arena, int32_t U, int32_t R, const int32_t* windows_per,
+                                                  const int32_t* plan, const float* spec, const int64_t* text, const float* seed_pose,
+                                                  const float* sampled, const float* alpha, float* track, float* windows,
+                                                  float* emotion_prediction, float* emotion_feature, float* semantic_feature,
+                                                  float* text_embedding, void* ws, int64_t ws_bytes, void* stream) {
+    EG_REQUIRE(g && arena && windows_per && plan && spec && seed_pose && sampled && track && ws, EG_ERR_BAD_ARG,
+               "eg_generator_forward_rollout_takes: null pointer");
+    EG_REQUIRE(U >= 1, EG_ERR_BAD_ARG, "eg_generator_forward_rollout_takes: utterances=%d (need >= 1)", U);
+    EG_REQUIRE(R >= 1, EG_ERR_BAD_ARG, "eg_generator_forward_rollout_takes: draws=%d (need >= 1)", R);
+    int64_t N64 = 0;
+    int Wmax = 0;
+    for (int u = 0; u < U; ++u) {
+        EG_REQUIRE(windows_per[u] >= 1, EG_ERR_BAD_ARG, "eg_generator_forward_rollout_takes: windows_per[%d]=%d (need >= 1)", u, windows_per[u]);
+        N64 += windows_per[u];
+        Wmax = windows_per[u] > Wmax ? windows_per[u] : Wmax;
+    }
+    EG_REQUIRE(N64 <= (1 << 20) && N64 * R <= (1 << 20), EG_ERR_UNSUPPORTED,
+               "eg_generator_forward_rollout_takes: total windows*draws=%lld*%d > 2^20", (long long)N64, R);
+    EG_REQUIRE(text || !text_embedding, EG_ERR_BAD_ARG, "eg_generator_forward_rollout_takes: text_embedding wanted without text");
+    EG_REQUIRE(g->cfg.n_layers <= 8, EG_ERR_UNSUPPORTED, "eg_generator_forward_rollout_takes: n_layers=%d > 8", g->cfg.n_layers);
+    const RollWs r = carve_rollout(g, U, N64, R);
+    EG_REQUIRE(ws_bytes >= r.total, EG_ERR_WORKSPACE, "eg_generator_forward_rollout_takes: workspace %lld < %lld bytes", (long long)ws_bytes,
+               (long long)r.total);
+    EG_REQUIRE(eg_aligned16(ws) && eg_aligned16(arena) && eg_aligned16(spec) && eg_aligned16(sampled) &&
+                   (reinterpret_cast<uintptr_t>(plan) & 3u) == 0, EG_ERR_ALIGN,
+               "eg_generator_forward_rollout_takes: 16-byte alignment (plan: 4-byte)");
+    if (R == 1)         // the takes plan begins with the ragged plan's table: the ragged roll-out itself, launch for launch
+        return eg_generator_forward_rollout_ragged(g, arena, U, windows_per, plan, spec, text, seed_pose, sampled, alpha, track, windows,
+                                                   emotion_prediction, emotion_feature, semantic_feature, text_embedding, ws, ws_bytes, stream);
+    const std::vector<int32_t> order = working_order(windows_per, U);
+    // seed_in_order is not read with R > 1: the seed launch gathers by rank whatever the order
+    const RollPlan p = {U, R, (int)N64, Wmax, plan, windows_per, order.data(), U == 1 || Wmax == 1, false};
     hipStream_t st = (hipStream_t)stream;
     float* kv[8];
     EG_TRY(rollout_phase_a(g, arena, p, r, ws, spec, text, sampled, emotion_prediction, emotion_feature, semantic_feature, text_embedding, kv, st));

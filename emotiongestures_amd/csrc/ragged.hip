@@ -125,6 +125,38 @@ extern "C" int eg_rollout_ragged_plan(const int32_t* windows_per, int32_t U, int
     return EG_OK;
 }
 
+// The takes plan (eg_generator_forward_rollout_takes): the ragged plan's table followed by slot_rank [N], the rank of every step-major slot
+// (the fusion kernel of draws.hip finds a slot's recording, offset and step through it).
+extern "C" int64_t eg_rollout_takes_plan_ints(int32_t utterances, int64_t total_windows) {
+    const int64_t ragged = eg_rollout_ragged_plan_ints(utterances, total_windows);
+    return ragged > 0 ? ragged + total_windows : 0;
+}
+
+extern "C" int eg_rollout_takes_plan(const int32_t* windows_per, int32_t U, int32_t* order, int32_t* inverse, int32_t* step_batch,
+                                     int32_t* table) {
+    EG_REQUIRE(U >= 1, EG_ERR_BAD_ARG, "eg_rollout_takes_plan: utterances=%d (need >= 1)", U);
+    EG_REQUIRE(windows_per, EG_ERR_BAD_ARG, "eg_rollout_takes_plan: null pointer");
+    int64_t N = 0;
+    int Wmax = 0;
+    for (int u = 0; u < U; ++u) {
+        EG_REQUIRE(windows_per[u] >= 1, EG_ERR_BAD_ARG, "eg_rollout_takes_plan: windows_per[%d]=%d (need >= 1)", u, windows_per[u]);
+        N += windows_per[u];
+        Wmax = std::max(Wmax, (int)windows_per[u]);
+    }
+    EG_REQUIRE(N <= (1 << 20), EG_ERR_UNSUPPORTED, "eg_rollout_takes_plan: total windows=%lld > 2^20", (long long)N);
+    std::vector<int32_t> batch(Wmax);
+    const int rc = eg_rollout_ragged_plan(windows_per, U, order, inverse, batch.data(), table);
+    if (rc) return rc;
+    int32_t* slot_rank = table ? table + N + 2 * (int64_t)U : nullptr;
+    for (int s = 0, slot = 0; s < Wmax; ++s) {
+        if (step_batch) step_batch[s] = batch[s];
+        if (slot_rank)
+            for (int r = 0; r < batch[s]; ++r) slot_rank[slot + r] = r;
+        slot += batch[s];
+    }
+    return EG_OK;
+}
+
 // ---- internal (C++ linkage) launchers used by generator.hip ---------------------------------------------------------------------
 int egi_rows_by_table(const void* in, void* out, const int32_t* table, int rows, size_t inner_words, bool scatter, hipStream_t st) {
     const bool wide = (inner_words & 3) == 0 && eg_aligned16(in) && eg_aligned16(out);

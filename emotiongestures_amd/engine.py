@@ -347,6 +347,64 @@ class GeneratorEngine:
         return self._rollout_call("eg_generator_forward_rollout_ragged", (U, plan["windows_per_c"], _ptr(plan["table_dev"])), tensors, out, ws,
                                   ws_bytes, dev)
 
+    # ---- takes: several sampled tracks per recording, recordings with their own window counts ----
+    def _rollout_takes_args(self, spec, text, seed_pose, windows_per, sampled, alpha):
+        """Shape contract of forward_rollout_takes (checked before anything touches the device); returns (U, N, R, windows_per as a tuple)."""
+        c = self.cfg
+        U, N, wp = self._rollout_ragged_args(spec, text, seed_pose, windows_per, None, alpha)
+        if sampled is None:
+            raise L.EgError(f"sampled: required, shape (N*R,F,d_model) = ({N}*R,{c.frames},{c.d_model}) (without it every draw is the same track)")
+        if sampled.dim() != 3 or tuple(sampled.shape[1:]) != (c.frames, c.d_model) or int(sampled.shape[0]) < N or int(sampled.shape[0]) % N:
+            raise L.EgError(f"sampled shape {tuple(sampled.shape)} != (N*R,F,d_model) = ({N}*R,{c.frames},{c.d_model}) packed, R >= 1 draws")
+        R = int(sampled.shape[0]) // N
+        if N * R > 1 << 20:
+            raise L.EgError(f"sampled: windows*draws N*R={N}*{R} > 2^20")
+        return U, N, R, wp
+
+    def _takes_plan(self, wp, device):
+        """The takes plan of one (W_u) vector (eg_rollout_takes_plan: the ragged table, then slot_rank), uploaded once and kept like _ragged_plan's."""
+        def build():
+            import numpy as np
+            U, N = len(wp), sum(wp)
+            w = np.asarray(wp, np.int32)
+            table = np.zeros(int(self._lib.eg_rollout_takes_plan_ints(U, N)), np.int32)
+            L.check(self._lib.eg_rollout_takes_plan(host_ptr(w), U, None, None, None, host_ptr(table)), "eg_rollout_takes_plan")
+            off = np.concatenate([[0], np.cumsum(w[:-1], dtype=np.int64)]).astype(np.int64)
+            return {"table": table, "offsets": off, "windows_per_c": (C.c_int32 * U)(*wp), "table_dev": torch.from_numpy(table).to(device)}
+        return self._plans.get(("takes", wp, str(device)), build)
+
+    @_locked
+    def forward_rollout_takes(self, spec, text, seed_pose, windows_per, sampled, alpha=None, want_windows=False, want_aux=False, slot=0,
+                              track=None):
+        """eg_generator_forward_rollout_takes: R sampled tracks for each of U recordings with their own window counts windows_per[u] = W_u,
+        the audio tower run once per window.  By definition forward_rollout_ragged on U*R recordings, recording u*R + r having the windows,
+        text, seed pose and W_u of u and its own sampled maps.  spec [N,n_mels,spec_len], text [N,text_len] packed recording-major (N = sum
+        W_u, off its exclusive prefix sum), seed_pose [U,P,D], sampled [N*R,F,d_model] (required; R is read from it) in the packed order of
+        the replicated call -- window w of draw r of recording u is row R*off[u] + r*W_u + w --, alpha [P] or None.  Returns a dict: track
+        [U, R, Wmax*(F-P)+P, D] (rows past track_frames[u] are zero), track_frames [U], window_offsets [U] = off and take_window_offsets
+        [U, R] = R*off[u] + r*W_u (int64, on the host), packed emotion_prediction [N,8] (independent of the draw), windows [N*R,F,D] in the
+        order of `sampled` with want_windows, emotion_feature / semantic_feature [N,F,d_model] and text_embedding [N,text_len,512] with
+        want_aux.  `track`: a caller-owned contiguous float32 GPU buffer of the track's shape (default: a new one); every element is written."""
+        U, N, R, wp = self._rollout_takes_args(spec, text, seed_pose, windows_per, sampled, alpha)
+        c = self.cfg
+        H = c.frames - c.prior_frames
+        T = max(wp) * H + c.prior_frames
+        if track is not None and (tuple(track.shape) != (U, R, T, c.pose_dim) or track.dtype != torch.float32 or not track.is_contiguous()
+                                  or not track.is_cuda):
+            raise L.EgError(f"track: need a contiguous float32 GPU tensor [{U},{R},{T},{c.pose_dim}]")
+        dev = self._loaded("forward_rollout_takes")
+        tensors = self._rollout_tensors(spec, text, seed_pose, sampled, alpha)
+        plan = self._takes_plan(wp, dev)
+        ws, ws_bytes = self._rollout_workspace("takes", "eg_generator_rollout_takes_workspace_bytes", {"U": U, "N": N, "R": R}, slot, dev)
+        out = self._rollout_outputs(dev, (U, R), max(wp), (N * R,), (N,), want_windows, want_aux, track)
+        off = torch.from_numpy(plan["offsets"])
+        w = torch.tensor(wp, dtype=torch.int64)
+        out["track_frames"] = w * H + c.prior_frames
+        out["window_offsets"] = off.clone()
+        out["take_window_offsets"] = R * off[:, None] + torch.arange(R, dtype=torch.int64)[None, :] * w[:, None]
+        return self._rollout_call("eg_generator_forward_rollout_takes", (U, R, plan["windows_per_c"], _ptr(plan["table_dev"])), tensors, out, ws,
+                                  ws_bytes, dev)
+
     # ---- streaming synthesis (a session's state buffer is owned by the caller: emotiongestures_amd.streaming.GestureStream) ----
     def _stream_geometry(self, rows, hop_samples, n_samples):
         if int(rows) < 1 or int(hop_samples) < 1 or int(n_samples) < 1:

@@ -28,7 +28,7 @@ from .takes import take_distance, take_diversity, track_features  # noqa: F401  
 
 __all__ = ["MLP_Reconstruct", "SkeletonTransformer", "Prior_Encoder", "compute_acc", "l2_distance_pose", "mpjre", "calc_motion",
            "calculate_frechet_distance", "calculate_diversity", "diversity_score", "evaluate", "track_features", "take_distance",
-           "take_diversity"]
+           "take_diversity", "synthesize_takes"]
 
 
 class _PackCache:
@@ -483,7 +483,7 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     ``draws=R`` (a VAE is required): R sampled tracks per recording in one call.  ``z [U, R, W, 32]`` (default torch.randn on the CPU generator
     in that shape), ``labels`` ``[U, 8]``, ``[U, W, 8]`` or ``[U, R, W, 8]`` (each draw its own emotion); one ``vae.sample`` at batch
     ``U*R*W``, mel and window gather once per recording.  Returns GeneratorEngine.forward_rollout_draws's dict (track ``[U, R, T, pose_dim]``)
-    plus ``"spec"``.  Rectangular calls only: not with ``lengths``.
+    plus ``"spec"``.  Rectangular calls only: not with ``lengths`` -- recordings of unequal length with draws are ``synthesize_takes``.
 
     ``beat=True`` (opt-in; BEAT-shaped generators, pose_dim >= 174): adds ``"beat"``, the beat-alignment score of every returned track
     against the audio it was made from (beat.beat_alignment_tracks: fp64 ``[U]``, or ``[U, R]`` with ``draws``), recording u scored on its
@@ -512,29 +512,62 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     the parent bone (``rotations_space="local"``, what a rig takes) or to the root (``"global"``):
     ``skeleton.rotations_from_tracks(out["track"], skeleton, rest, frames, joints_mean, joints_fps, rotations_space)``, one more launch, on the
     frames ``"joint_frames"`` counts."""
+    return _synthesize("synthesize", models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate,
+                       want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, joints, joints_mean, joints_unit, joints_fps,
+                       rotations, rotations_space, takes=False)
+
+
+def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch.Tensor, labels: Optional[torch.Tensor] = None, *,
+                     lengths=None, draws: int, z: Optional[torch.Tensor] = None, alpha: Optional[torch.Tensor] = None,
+                     hop_samples: Optional[int] = None, n_samples: Optional[int] = None, fps: int = 15, sample_rate: int = 16000,
+                     want_windows: bool = False, want_aux: bool = False, mel=None, beat: bool = False, diversity=None,
+                     audio_rate: Optional[int] = None, joints=None, joints_mean=None, joints_unit: bool = False, joints_fps=None,
+                     rotations=None, rotations_space: str = "local") -> Dict[str, torch.Tensor]:
+    """``draws`` = R sampled takes for each of U recordings of any and unequal length, from raw audio, in one call: ``synthesize(lengths=)`` and
+    ``synthesize(draws=)`` combined (a VAE is required).  ``audio [U, max_total]`` with ``lengths[u]`` real samples in row u (``None``: every
+    row at full length); recording u has ``W_u = ceil(lengths[u] / hop_samples)`` windows, N = sum W_u.  ``text`` padded ``[U, Wmax, 60]`` or
+    packed ``[N, 60]``; ``labels`` ``[U, 8]``, ``[U, Wmax, 8]``, ``[U, R, Wmax, 8]`` (each draw its own emotion) or packed ``[N*R, 8]``;
+    ``z [U, R, Wmax, 32]`` or packed ``[N*R, 32]`` (default ``torch.randn(N*R, 32)`` on the CPU generator).  Packed per-take rows are in the
+    order of GeneratorEngine.forward_rollout_takes: window w of draw r of recording u at row ``R*off[u] + r*W_u + w``.  Mel and the window
+    gather run once per recording, one ``vae.sample`` at batch ``N*R``.  Returns forward_rollout_takes's dict (track ``[U, R, T, pose_dim]``
+    zero past ``track_frames[u]``) plus packed ``"spec"`` and ``"windows_per"``.  Every other option is ``synthesize``'s, applied per take with
+    recording u's own samples and poses: ``beat`` -> ``"beat"`` ``[U, R]``; ``diversity`` (R >= 2) -> ``"take_distance"`` ``[U, R, R]`` and
+    ``"take_diversity"`` ``[U]``; ``joints`` -> ``[U, R, T', J, 3]``; ``rotations`` -> ``[U, R, T', K, 4]``; ``audio_rate``."""
+    return _synthesize("synthesize_takes", models, audio, text, seed_pose, labels, hop_samples, n_samples, None, z, alpha, fps, sample_rate,
+                       want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, joints, joints_mean, joints_unit, joints_fps,
+                       rotations, rotations_space, takes=True)
+
+
+def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate, want_windows, want_aux,
+                mel, lengths, draws, beat, diversity, audio_rate, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, takes):
+    """The body of `synthesize` and `synthesize_takes` (`who` names the caller in errors): argument checks, resampling, the roll-out of the
+    call's kind, then the per-track extras."""
     gen, vae = models
     from . import skeleton as SK
-    rotations = SK.output_args("synthesize", seed_pose.shape[-1], joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space,
+    rotations = SK.output_args(who, seed_pose.shape[-1], joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space,
                                hint=" (the BEAT generators' 282 columns hold rotations, not bone direction vectors)")
     _eval_only(gen)
     if beat and seed_pose.shape[-1] < 174:
-        raise L.EgError(f"synthesize: beat=True: pose_dim={seed_pose.shape[-1]}: the beat joints are columns 18:42 and 150:174 (needs >= 174)")
+        raise L.EgError(f"{who}: beat=True: pose_dim={seed_pose.shape[-1]}: the beat joints are columns 18:42 and 150:174 (needs >= 174)")
     if draws is not None:
-        if lengths is not None:
-            raise L.EgError("synthesize: draws= with lengths= is not supported (draws in the ragged roll-out); call the rectangular "
-                            "synthesize(..., draws=R) once per group of recordings of equal length")
+        if lengths is not None and not takes:
+            raise L.EgError("synthesize: draws= with lengths= is not supported (draws in the ragged roll-out are synthesize_takes); call "
+                            "synthesize_takes(..., lengths=, draws=R), or the rectangular synthesize(..., draws=R) once per group of "
+                            "recordings of equal length")
         if vae is None:
-            raise L.EgError("synthesize: draws= needs a VAE (without sampled emotion maps every draw is the same track)")
+            raise L.EgError(f"{who}: draws= needs a VAE (without sampled emotion maps every draw is the same track)")
         if int(draws) < 1:
-            raise L.EgError(f"synthesize: draws={int(draws)} (need >= 1)")
+            raise L.EgError(f"{who}: draws={int(draws)} (need >= 1)")
     if diversity is not None and (draws is None or int(draws) < 2):
-        raise L.EgError(f"synthesize: diversity= needs draws >= 2 (got draws={draws}): the take diversity is a distance between the takes of "
+        raise L.EgError(f"{who}: diversity= needs draws >= 2 (got draws={draws}): the take diversity is a distance between the takes of "
                         "one recording")
     eng = gen.engine()
     c = eng.cfg
     if audio.dim() != 2:
         raise L.EgError(f"audio shape {tuple(audio.shape)} != (U, total_samples)")
     U = audio.shape[0]
+    if takes and lengths is None:
+        lengths = [int(audio.shape[1])] * U
     resampled = audio_rate is not None and int(audio_rate) != int(sample_rate)
     if resampled:
         from . import resample as RS
@@ -544,7 +577,11 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
             audio = RS.resample_audio(audio, int(audio_rate), int(sample_rate), lengths=lengths)
         if lengths is not None:
             lengths = [RS.out_length(v, int(audio_rate), int(sample_rate)) for v in lengths]
-    if lengths is not None:
+    if takes:
+        out, spec, wp = _synthesize_takes(eng, vae, audio, lengths, text, seed_pose, labels, z, alpha, want_windows, want_aux, int(draws),
+                                          *_front_end(c, audio, hop_samples, n_samples, fps, sample_rate, mel))
+        out["windows_per"] = wp
+    elif lengths is not None:
         out, spec, wp = _synthesize_ragged(eng, vae, audio, lengths, text, seed_pose, labels, z, alpha, want_windows, want_aux,
                                            *_front_end(c, audio, hop_samples, n_samples, fps, sample_rate, mel))
         out["windows_per"] = wp
@@ -560,17 +597,17 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
         out["audio"] = audio
         if lengths is not None:
             out["lengths"] = list(lengths)
+    frames = [int(w) * (c.frames - c.prior_frames) + c.prior_frames for w in wp]         # recording u's own valid poses
     if beat:
         from .beat import beat_alignment_tracks
-        H = c.frames - c.prior_frames
         with torch.no_grad():
-            out["beat"] = beat_alignment_tracks(audio, out["track"], lengths=lengths, frames=[int(w) * H + c.prior_frames for w in wp], fps=fps)
+            out["beat"] = beat_alignment_tracks(audio, out["track"], lengths=lengths, frames=frames, fps=fps)
     if diversity is not None:
         with torch.no_grad():
-            td = take_diversity(diversity, out["track"], span=c.frames)
+            td = take_diversity(diversity, out["track"], frames=frames if takes else None, span=c.frames)
         out["take_distance"], out["take_diversity"] = td["distance"], td["diversity"]
     if joints is not None:
-        kw = dict(frames=[int(w) * (c.frames - c.prior_frames) + c.prior_frames for w in wp], mean=joints_mean, fps=joints_fps)
+        kw = dict(frames=frames, mean=joints_mean, fps=joints_fps)
         with torch.no_grad():
             out["joints"], out["joint_frames"] = SK.joints_from_tracks(out["track"], joints, unit=joints_unit, **kw)
             if rotations is not None:
@@ -642,6 +679,38 @@ def _synthesize_ragged(eng, vae, audio, lengths, text, seed_pose, labels, z, alp
             sampled = vae.sample(lab, z=z)
         out = eng.forward_rollout_ragged(spec, packed(text, 2, "text"), seed_pose, wp, sampled, alpha=alpha, want_windows=want_windows,
                                          want_aux=want_aux)
+    return out, spec, list(wp)
+
+
+def _synthesize_takes(eng, vae, audio, lengths, text, seed_pose, labels, z, alpha, want_windows, want_aux, R, hop, n, mel):
+    c = eng.cfg
+    U = audio.shape[0]
+    with torch.no_grad():
+        spec, wp = mel.windows_ragged(audio, lengths, hop, n, out_frames=c.spec_len)
+        wp = tuple(wp)
+        N, Wmax = sum(wp), max(wp)
+        per_take = tuple(w for w in wp for _ in range(R))           # [U, R, Wmax, ...] viewed as U*R padded recordings: the packed take order
+        pack_takes = lambda x, name: eng.pack_ragged(x.reshape((U * R, Wmax) + tuple(x.shape[3:])).contiguous(), per_take, name)
+        if labels is None:
+            raise L.EgError("labels: needed with draws= ([U, 8], [U, Wmax, 8], [U, R, Wmax, 8] or packed [N*R, 8] one-hot)")
+        lab = labels.to(audio.device).float()
+        if tuple(lab.shape) != (N * R, 8):
+            if tuple(lab.shape) == (U, 8):
+                lab = lab[:, None, None, :].expand(U, R, Wmax, 8)
+            elif tuple(lab.shape) == (U, Wmax, 8):
+                lab = lab[:, None, :, :].expand(U, R, Wmax, 8)
+            elif tuple(lab.shape) != (U, R, Wmax, 8):
+                raise L.EgError(f"labels shape {tuple(labels.shape)}: need ({U},8), ({U},{Wmax},8), ({U},{R},{Wmax},8) or packed ({N * R},8)")
+            lab = pack_takes(lab, "labels")
+        if z is None:
+            z = torch.randn(N * R, 32)
+        elif tuple(z.shape) == (U, R, Wmax, 32):
+            z = pack_takes(z.to(audio.device).float(), "z")
+        elif tuple(z.shape) != (N * R, 32):
+            raise L.EgError(f"z shape {tuple(z.shape)}: need ({U},{R},{Wmax},32) or packed ({N * R},32)")
+        sampled = vae.sample(lab.contiguous(), z=z)
+        out = eng.forward_rollout_takes(spec, eng.pack_ragged(text, wp, "text") if text.dim() == 3 else text, seed_pose, wp, sampled,
+                                        alpha=alpha, want_windows=want_windows, want_aux=want_aux)
     return out, spec, list(wp)
 
 

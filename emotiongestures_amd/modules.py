@@ -24,6 +24,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from ._host import int_list
 from .engine import CvaeEngine, GeneratorEngine
 
 __all__ = [
@@ -793,8 +794,9 @@ class Transformer(ReplicaAware, nn.Module):
         _eval_only(self)
         if draws is not None:
             if windows_per is not None:
-                raise L.EgError("synthesize: draws= with windows_per= is not supported (draws in the ragged roll-out); call the rectangular "
-                                "synthesize(..., draws=R) once per group of recordings with equal window counts")
+                raise L.EgError("synthesize: draws= with windows_per= is not supported (draws in the ragged roll-out are synthesize_takes); "
+                                "call synthesize_takes(..., windows_per=, draws=R), or the rectangular synthesize(..., draws=R) once per "
+                                "group of recordings with equal window counts")
             R = int(draws)
             s = sampled_emotion_features
             if R < 1:
@@ -812,6 +814,42 @@ class Transformer(ReplicaAware, nn.Module):
         return eng.forward_rollout_ragged(pack(input_spectrum, 3, "input_spectrum"), pack(text, 2, "text"), seed_pose, windows_per,
                                           pack(sampled_emotion_features, 3, "sampled_emotion_features"), alpha=alpha,
                                           want_windows=want_windows, want_aux=want_aux, slot=slot)
+
+    def synthesize_takes(self, input_spectrum, text, seed_pose, sampled_emotion_features, *, windows_per, draws, alpha=None, want_windows=False,
+                         want_aux=False, slot=0):
+        """``draws`` = R sampled tracks for each of U recordings with their own window counts ``windows_per`` in one call, the audio tower run
+        once per window: the general long-form call, of which ``synthesize(windows_per=)`` (R = 1) and ``synthesize(draws=)`` (equal counts)
+        are special cases.  The result is that of ``synthesize(windows_per=)`` on U*R recordings, recording u*R + r having the inputs and W_u
+        of u and its own sampled maps.  input_spectrum / text: packed ``[N, ...]`` (N = sum W_u) or padded ``[U, max W_u, ...]``;
+        seed_pose [U,prior_frames,pose_dim]; sampled_emotion_features (required): padded ``[U, R, max W_u, frames, d_model]`` or packed
+        ``[N*R, frames, d_model]``, window w of draw r of recording u at row ``R*off[u] + r*W_u + w``.  Padded arguments are packed on the
+        device; entries past W_u are never read.  Returns GeneratorEngine.forward_rollout_takes's dict: track [U, R, max W_u * H + P,
+        pose_dim] zero past track_frames[u], windows ``[N*R, ...]`` in the order of the packed sampled maps (take_window_offsets [U, R]),
+        the outputs that do not depend on the draw packed ``[N, ...]`` and returned once."""
+        _eval_only(self)
+        R = int(draws)
+        if R < 1:
+            raise L.EgError(f"synthesize_takes: draws={R} (need >= 1)")
+        try:
+            wp = tuple(int_list(windows_per))
+        except TypeError:
+            raise L.EgError(f"synthesize_takes: windows_per: need a sequence of U window counts (got {type(windows_per).__name__})")
+        s = sampled_emotion_features
+        if s is None or s.dim() not in (3, 5):
+            raise L.EgError(f"synthesize_takes(draws={R}): sampled_emotion_features shape {None if s is None else tuple(s.shape)}: need padded "
+                            f"(U,R,Wmax,F,d_model) or packed (N*R,F,d_model) with R={R}")
+        if s.dim() == 5 and (int(s.shape[0]) != len(wp) or int(s.shape[1]) != R):
+            raise L.EgError(f"synthesize_takes(draws={R}): sampled_emotion_features shape {tuple(s.shape)} != (U,R,Wmax,F,d_model) with "
+                            f"U={len(wp)}, R={R}")
+        if s.dim() == 3 and int(s.shape[0]) != sum(wp) * R:
+            raise L.EgError(f"synthesize_takes(draws={R}): sampled_emotion_features shape {tuple(s.shape)} != (N*R,F,d_model) with "
+                            f"N*R={sum(wp)}*{R}")
+        eng = self.engine()
+        pack = lambda x, packed_dim, name: eng.pack_ragged(x, wp, name) if x is not None and x.dim() == packed_dim + 1 else x
+        if s.dim() == 5:        # [U, R, Wmax, ...] viewed as U*R padded recordings, recording u*R + r with W_u windows: the packed order
+            s = eng.pack_ragged(s.reshape((len(wp) * R,) + tuple(s.shape[2:])), tuple(w for w in wp for _ in range(R)), "sampled_emotion_features")
+        return eng.forward_rollout_takes(pack(input_spectrum, 3, "input_spectrum"), pack(text, 2, "text"), seed_pose, wp, s, alpha=alpha,
+                                         want_windows=want_windows, want_aux=want_aux, slot=slot)
 
     def open_stream(self, rows, seed_pose, *, vae=None, mel=None, **kw):
         """Streaming synthesis: `harness.open_stream((self, vae), rows, seed_pose, mel=mel, **kw)` -- a `streaming.GestureStream` fed raw audio

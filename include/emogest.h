@@ -294,6 +294,49 @@ int eg_generator_forward_rollout_ragged(const EgGenerator* g, const float* arena
                                         void* workspace, int64_t workspace_bytes, void* stream);
 int64_t eg_generator_rollout_ragged_workspace_bytes(const EgGenerator* g, int32_t utterances, int64_t total_windows);
 
+/* Takes: R sampled tracks for each of U recordings with their OWN window counts W_u -- the general roll-out, of which the ragged call
+ * (R == 1) and the diverse call (every W_u equal) are special cases.  By definition eg_generator_forward_rollout_ragged on U*R recordings,
+ * recording u*R + r having recording u's spec windows, text, seed pose and W_u, and its own sampled maps: the replication rule
+ * eg_generator_forward_rollout_draws has against eg_generator_forward_rollout.  With N = sum W_u, off the exclusive prefix sum of W_u:
+ *   windows_per [U] on the HOST        plan [2N + 2U] int32 on the DEVICE (eg_rollout_takes_plan's table for the same windows_per)
+ *   spec [N, n_mels, spec_len], text [N, text_len] int64 (may be NULL unless text_embedding is wanted): packed recording-major, as for
+ *          eg_generator_forward_rollout_ragged         seed_pose [U, P, D]: one per recording        alpha [P] on the device or NULL
+ *   sampled [N*R, F, d_model] (required): the packed order of the replicated ragged call -- recording u owns rows
+ *          [R*off[u], R*off[u] + R*W_u), window w of draw r is row R*off[u] + r*W_u + w
+ *   track [U, R, Wmax*H + P, D]: rows [0, W_u*H + P) of track[u, r] as the ragged call defines them, the rest ZERO, every element written
+ *   optional (NULL to skip): windows [N*R, F, D] in the order of `sampled`; independent of the draw and returned once, packed:
+ *          emotion_prediction [N, 8], emotion_feature / semantic_feature [N, F, d_model], text_embedding [N, text_len, 512]
+ * The takes plan (host only, like eg_rollout_ragged_plan and with its arguments): table [2N + 2U] (eg_rollout_takes_plan_ints; 0 for
+ * counts the plan refuses) = eg_rollout_ragged_plan's table [N + 2U], then slot_rank [N]: the rank of step-major slot (s, rank).
+ * The R copies of a recording tie in the replicated call's working order and keep their index order, so its rank is rank*R + r and its
+ * slot is slot*R + r:
+ *   A: the ragged call's phase A at batch N (tower side, text, heads: once per window); ONE fusion launch (draws.hip) writes
+ *      fus_in[slot*R + r] = sampled[R*off + r*W_u + s] + semantic[slot], looking rank, off, W_u and s up in the table; encoder and every
+ *      decoder layer's K|V product at N*R sequences;
+ *   B: Wmax steps at batch U_s*R, row rank*R + r: prior encoder -> decoder over the step's contiguous K|V slice (U_s*R slots) ->
+ *      post_projector -> one hand-off launch (draws.hip: track[u, r] rows, windows, the next prior by row, and in a recording's LAST step
+ *      the zero fill of its R track tails).  Step 0's prior is seed_pose[order[rank]] repeated over the R draws by one launch.
+ * Same contract as the calls above: one stream, no allocation, host round trip or synchronisation; launches, grids and pointers are fixed
+ * for a fixed (W_u) vector and R: capturable into one hipGraph.  Fusion, encoder, K|V and phase B run at the batch and row order of the
+ * replicated call and the tower-side products accumulate K in one order from two clips up, so for N >= 2 every output equals the replicated
+ * ragged call bit for bit; at N == 1 the tower side takes the one-clip paths where the replicated call has R clips: equal to rounding.
+ * With draws == 1 the call IS eg_generator_forward_rollout_ragged (its launches, its bits); with every W_u equal it returns
+ * eg_generator_forward_rollout_draws's track bit for bit.
+ * Refuses by name, before the first launch: a null required pointer (sampled included), utterances / draws / W_u < 1, N > 2^20 or
+ * N*draws > 2^20, n_layers > 8, text_embedding without text, a short workspace, buffers not 16-byte aligned (plan: 4-byte).
+ * workspace >= eg_generator_rollout_takes_workspace_bytes at (U, N, R): 0 for what the call refuses, equal to
+ * eg_generator_rollout_draws_workspace_bytes(g, U, W, R) when N = U*W and to eg_generator_rollout_ragged_workspace_bytes(g, U, N) at
+ * draws == 1 (the tower side is carved once per window: below the replicated call's eg_generator_rollout_ragged_workspace_bytes(g, U*R, N*R)). */
+int64_t eg_rollout_takes_plan_ints(int32_t utterances, int64_t total_windows);
+int eg_rollout_takes_plan(const int32_t* windows_per, int32_t utterances, int32_t* order, int32_t* inverse, int32_t* step_batch,
+                          int32_t* table);
+int eg_generator_forward_rollout_takes(const EgGenerator* g, const float* arena, int32_t utterances, int32_t draws,
+                                       const int32_t* windows_per, const int32_t* plan, const float* spec, const int64_t* text,
+                                       const float* seed_pose, const float* sampled, const float* alpha, float* track, float* windows_out,
+                                       float* emotion_prediction, float* emotion_feature, float* semantic_feature, float* text_embedding,
+                                       void* workspace, int64_t workspace_bytes, void* stream);
+int64_t eg_generator_rollout_takes_workspace_bytes(const EgGenerator* g, int32_t utterances, int64_t total_windows, int32_t draws);
+
 /* Streaming synthesis: the roll-out fed hop by hop.  A session of `rows` = U rows lives in a caller-owned device buffer `state`
  * (eg_stream_state_bytes, 16-byte aligned, carved deterministically from (g, rows, hop_samples, n_samples): pass the same four to every
  * entry): an audio ring [U, lag * hop], lag = ceil(n_samples / hop_samples), the prior [U, P, D] and per row the counters c (pushes since

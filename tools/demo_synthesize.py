@@ -8,6 +8,8 @@
 Weights are synthetic (integer hash), so the poses carry no meaning; the script shows the call sequence and prints the shapes, the seam
 statistics of the track and the time of one call.  With --draws R it then makes R tracks per recording in one call (draw r delivers the line
 in emotion (u + r) % 8; the audio tower runs once per window, not R times) and, with --out FILE.npz, writes them: tracks [U, R, T, pose_dim].
+With --draws R and more than one recording it also makes the R takes of the recordings of unequal length in one call (harness.synthesize_takes:
+recording u keeps (u + 1) / U of the audio; --beat and --diversity then score every take on its recording's own samples and poses).
 With --beat the generator is BEAT-shaped (60 poses of 282 columns, 10 of them the prior: the beat joints are columns 18:42 and 150:174) and every
 call also returns the beat-alignment score of each track against its own audio (per recording, and per draw with --draws).
 With --diversity (and --draws R, R >= 2) the draws call also returns the take diversity of every recording: the mean pairwise distance of its
@@ -170,6 +172,22 @@ if DRAWS > 0:
     print(f"--draws {DRAWS}: tracks {tuple(tracks.shape)} in one call, {1e3 * dt_r:.2f} ms = {1e3 * dt_r / (U * DRAWS * tracks.shape[2] / FPS):.4f} ms per "
           f"second of track (one track per recording: {1e3 * dt / (U * track.shape[1] / FPS):.4f}); mean distance of a draw from its recording's mean "
           f"track: {float(spread):.4f}")
+    if U > 1:       # the two combined: R takes of recordings of unequal length, one call (the tower once per window, step s at batch U_s * R)
+        H.synthesize_takes((gen, vae), audio, text, seed_pose, labels_r, lengths=lengths, draws=DRAWS, z=zr, **AR)          # warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        tk = H.synthesize_takes((gen, vae), audio, text, seed_pose, labels_r, lengths=lengths, draws=DRAWS, z=zr, beat=BEAT, diversity=fgd, **AR)
+        torch.cuda.synchronize()
+        dt_t = time.perf_counter() - t0
+        frames = tk["track_frames"].tolist()
+        print(f"--draws {DRAWS} with lengths {[round(v / RATE, 1) for v in lengths]} s (synthesize_takes): windows {tk['windows_per']} -> tracks "
+              f"{tuple(tk['track'].shape)}, frames per recording {frames}, {1e3 * dt_t:.2f} ms = "
+              f"{1e3 * dt_t / (DRAWS * sum(frames) / FPS):.4f} ms per second of track; rows past a recording's end are zero in every take: "
+              f"{all(not bool(tk['track'][u, :, frames[u]:].any()) for u in range(U))}")
+        if BEAT:
+            print(f"--beat: score per recording and take [U, R], each on its own samples and poses:\n{tk['beat'].cpu().numpy().round(4)}")
+        if DIVERSITY:
+            print(f"--diversity: take diversity per recording over its own frames: {[round(float(v), 4) for v in tk['take_diversity'].cpu()]}")
     if OUT:
         np.savez(OUT, tracks=tracks.cpu().numpy(), emotion=((torch.arange(U)[:, None] + torch.arange(DRAWS)[None, :]) % 8).numpy(), fps=FPS)
         print(f"wrote {OUT}: tracks [U, R, T, pose_dim] = {tuple(tracks.shape)}")
