@@ -464,7 +464,7 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
                z: Optional[torch.Tensor] = None, alpha: Optional[torch.Tensor] = None, fps: int = 15, sample_rate: int = 16000,
                want_windows: bool = False, want_aux: bool = False, mel=None, lengths=None, draws: Optional[int] = None,
                beat: bool = False, diversity=None, audio_rate: Optional[int] = None, joints=None, joints_mean=None,
-               joints_unit: bool = False, joints_fps=None, rotations=None, rotations_space: str = "local") -> Dict[str, torch.Tensor]:
+               joints_unit: bool = False, joints_fps=None, rotations=None, rotations_space: str = "local", smooth=None) -> Dict[str, torch.Tensor]:
     """One gesture track per utterance from raw 16 kHz audio: windows -> mel -> optional CVAE sample per window -> roll-out.
 
     ``models = (generator, vae | None)``, eval mode, on the GPU.  ``audio [U, total_samples]``; ``text [U, W, 60]`` (the words of every
@@ -511,10 +511,16 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     one unit quaternion ``(w, x, y, z)`` per bone and output frame -- ``[U, T', K, 4]``, or ``[U, R, T', K, 4]`` with ``draws`` -- relative to
     the parent bone (``rotations_space="local"``, what a rig takes) or to the root (``"global"``):
     ``skeleton.rotations_from_tracks(out["track"], skeleton, rest, frames, joints_mean, joints_fps, rotations_space)``, one more launch, on the
-    frames ``"joint_frames"`` counts."""
+    frames ``"joint_frames"`` counts.
+
+    ``smooth=Smoother | (window, polyorder)`` (``smooth.Smoother``; a pair is a filter at ``fps``): adds ``"track_smooth"``, the shape of
+    ``"track"``: ``smooth.smooth_tracks(out["track"], smooth, frames)``, a Savitzky-Golay filter (``scipy.signal.savgol_filter``,
+    ``mode="interp"``) over recording u's own valid poses, zeros behind them, one launch.  ``"track"`` stays raw and ``beat`` / ``diversity`` keep
+    scoring it (they measure the model); ``"joints"`` and ``"rotations"`` are then made from ``"track_smooth"`` (they are what a renderer
+    takes).  ``deriv != 0`` is refused by name: a velocity track is not a pose track -- call ``smooth_tracks`` for derivatives."""
     return _synthesize("synthesize", models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate,
                        want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, joints, joints_mean, joints_unit, joints_fps,
-                       rotations, rotations_space, takes=False)
+                       rotations, rotations_space, smooth, takes=False)
 
 
 def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch.Tensor, labels: Optional[torch.Tensor] = None, *,
@@ -522,7 +528,7 @@ def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose:
                      hop_samples: Optional[int] = None, n_samples: Optional[int] = None, fps: int = 15, sample_rate: int = 16000,
                      want_windows: bool = False, want_aux: bool = False, mel=None, beat: bool = False, diversity=None,
                      audio_rate: Optional[int] = None, joints=None, joints_mean=None, joints_unit: bool = False, joints_fps=None,
-                     rotations=None, rotations_space: str = "local") -> Dict[str, torch.Tensor]:
+                     rotations=None, rotations_space: str = "local", smooth=None) -> Dict[str, torch.Tensor]:
     """``draws`` = R sampled takes for each of U recordings of any and unequal length, from raw audio, in one call: ``synthesize(lengths=)`` and
     ``synthesize(draws=)`` combined (a VAE is required).  ``audio [U, max_total]`` with ``lengths[u]`` real samples in row u (``None``: every
     row at full length); recording u has ``W_u = ceil(lengths[u] / hop_samples)`` windows, N = sum W_u.  ``text`` padded ``[U, Wmax, 60]`` or
@@ -532,20 +538,28 @@ def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose:
     gather run once per recording, one ``vae.sample`` at batch ``N*R``.  Returns forward_rollout_takes's dict (track ``[U, R, T, pose_dim]``
     zero past ``track_frames[u]``) plus packed ``"spec"`` and ``"windows_per"``.  Every other option is ``synthesize``'s, applied per take with
     recording u's own samples and poses: ``beat`` -> ``"beat"`` ``[U, R]``; ``diversity`` (R >= 2) -> ``"take_distance"`` ``[U, R, R]`` and
-    ``"take_diversity"`` ``[U]``; ``joints`` -> ``[U, R, T', J, 3]``; ``rotations`` -> ``[U, R, T', K, 4]``; ``audio_rate``."""
+    ``"take_diversity"`` ``[U]``; ``joints`` -> ``[U, R, T', J, 3]``; ``rotations`` -> ``[U, R, T', K, 4]``; ``audio_rate``; ``smooth`` ->
+    ``"track_smooth"`` ``[U, R, T, pose_dim]``."""
     return _synthesize("synthesize_takes", models, audio, text, seed_pose, labels, hop_samples, n_samples, None, z, alpha, fps, sample_rate,
                        want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, joints, joints_mean, joints_unit, joints_fps,
-                       rotations, rotations_space, takes=True)
+                       rotations, rotations_space, smooth, takes=True)
 
 
 def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate, want_windows, want_aux,
-                mel, lengths, draws, beat, diversity, audio_rate, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, takes):
+                mel, lengths, draws, beat, diversity, audio_rate, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, smooth,
+                takes):
     """The body of `synthesize` and `synthesize_takes` (`who` names the caller in errors): argument checks, resampling, the roll-out of the
     call's kind, then the per-track extras."""
     gen, vae = models
     from . import skeleton as SK
     rotations = SK.output_args(who, seed_pose.shape[-1], joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space,
                                hint=" (the BEAT generators' 282 columns hold rotations, not bone direction vectors)")
+    if smooth is not None:
+        from . import smooth as SM
+        smooth = SM.Smoother.of(smooth, f"{who}: smooth", fps)
+        if smooth.deriv != 0:
+            raise L.EgError(f"{who}: smooth=: deriv={smooth.deriv}: a velocity track is not a pose track; call smooth.smooth_tracks on "
+                            "out[\"track\"] for derivatives")
     _eval_only(gen)
     if beat and seed_pose.shape[-1] < 174:
         raise L.EgError(f"{who}: beat=True: pose_dim={seed_pose.shape[-1]}: the beat joints are columns 18:42 and 150:174 (needs >= 174)")
@@ -606,12 +620,16 @@ def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samp
         with torch.no_grad():
             td = take_diversity(diversity, out["track"], frames=frames if takes else None, span=c.frames)
         out["take_distance"], out["take_diversity"] = td["distance"], td["diversity"]
+    poses = out["track"]
+    if smooth is not None:                                                                # beat and diversity above score the raw track
+        with torch.no_grad():
+            poses = out["track_smooth"] = SM.smooth_tracks(out["track"], smooth, frames=frames)
     if joints is not None:
         kw = dict(frames=frames, mean=joints_mean, fps=joints_fps)
         with torch.no_grad():
-            out["joints"], out["joint_frames"] = SK.joints_from_tracks(out["track"], joints, unit=joints_unit, **kw)
+            out["joints"], out["joint_frames"] = SK.joints_from_tracks(poses, joints, unit=joints_unit, **kw)
             if rotations is not None:
-                out["rotations"], _n = SK.rotations_from_tracks(out["track"], joints, rotations, space=rotations_space, **kw)
+                out["rotations"], _n = SK.rotations_from_tracks(poses, joints, rotations, space=rotations_space, **kw)
     return out
 
 

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib as L
 from . import skeleton as SK
+from . import smooth as SM
 from ._host import int_list, need_cuda as _need_cuda
 from .modules import _eval_only
 from .pipeline import CAPTURE_MODE
@@ -154,13 +155,26 @@ class GestureStream:
     `joints_fps` is refused: a frame-rate change needs the frame after the last one emitted.
     `rotations=rest` (with `joints=`; `rest [K, 3]` the avatar's bind pose, `rotations_space` as in skeleton.rotations_from_tracks): one more
     launch inside the graph leaves the bone rotations of the rows just emitted in `last_rotations [U, H, K, 4]` under the same rules;
-    `tail_rotations()`: the rotations of `tail()`."""
+    `tail_rotations()`: the rotations of `tail()`.
+    `smooth=Smoother | (window, polyorder)` (smooth.Smoother, deriv 0, window <= H): every step ends with the two launches of a
+    smooth.StreamSmoother (inside the graph) that leave in `last_smooth [U, H, D]` the smoothed frames `[sH - half, (s + 1)H - half)` of a row in
+    its s-th valid step -- `smooth_delay = half` frames behind the rows just emitted, the first `half` entries of step 0 zeros; zeros for a row
+    that was not valid, None while `rows` is None.  `tail_smooth()`: the last `[U, P + half, D]` smoothed frames.  A row's `last_smooth`,
+    concatenated after dropping step 0's leading `half` entries, followed by `tail_smooth()`, is smooth.smooth_tracks on its finished track bit
+    for bit.  `reset(rows=)` resets the smoothing state of those rows.  Not together with `joints=`: the first `half` entries of step 0 are not
+    poses."""
 
     def __init__(self, models: Tuple, rows: int, seed_pose: torch.Tensor, *, hop_samples: Optional[int] = None, n_samples: Optional[int] = None,
                  fps: int = 15, sample_rate: int = 16000, alpha: Optional[torch.Tensor] = None, graph: bool = True, want_windows: bool = False,
                  draws: Optional[int] = None, audio_rate: Optional[int] = None, joints=None, joints_mean=None, joints_unit: bool = False,
-                 joints_fps=None, rotations=None, rotations_space: str = "local"):
+                 joints_fps=None, rotations=None, rotations_space: str = "local", smooth=None):
         SK._output_args_early("GestureStream", joints, joints_fps, rotations, fps_allowed=False)
+        if smooth is not None:
+            if joints is not None:
+                raise L.EgError("GestureStream: smooth= together with joints= is not supported (the smoothed rows run half a window behind and "
+                                "the first `half` entries of step 0 are not poses); take joints from the raw rows, or smooth the finished "
+                                "track with harness.synthesize(..., smooth=, joints=)")
+            smooth = SM.Smoother.of(smooth, "GestureStream: smooth", fps)
         if draws is not None:
             raise L.EgError("GestureStream: draws= is not supported (a stream has one track per row); for several sampled tracks of a whole "
                             "recording call the rectangular synthesize(..., draws=R), or open the stream with each speaker's row repeated")
@@ -229,12 +243,16 @@ class GestureStream:
             self._in["spec"] = z(self.U, self.n_mels, self.spec_len)
         if self.vae is not None:
             self._in["label"], self._in["z"] = z(self.U, 8), z(self.U, 32)
+        # the smoother's state, table and output are held here: the captured graph replays their addresses
+        self._sm = None if smooth is None else SM.StreamSmoother(self.U, self.H, self.D, smooth, device=dev)
+        self.smooth_delay: Optional[int] = None if self._sm is None else self._sm.delay
         self._graphs: Dict[bool, dict] = {}
         self.last_valid: List[bool] = [False] * self.U           # the host's verdict for the last step, and the window index per valid row
         self.last_windows: List[Optional[int]] = [None] * self.U
         self.last_window: Optional[torch.Tensor] = None          # with want_windows: the raw poses [U, F, D] of the last step
         self.last_joints: Optional[torch.Tensor] = None          # with joints=: the joints [U, H, J, 3] of the rows just emitted (zeros for a row that was not valid)
         self.last_rotations: Optional[torch.Tensor] = None       # with rotations=: their bone rotations [U, H, K, 4], under the same rules
+        self.last_smooth: Optional[torch.Tensor] = None          # with smooth=: the smoothed frames [U, H, D], smooth_delay frames behind the rows
         eng.stream_reset(self._state, *self._geom, self.seed_pose)
 
     # ---- engines, staleness ----
@@ -293,6 +311,8 @@ class GestureStream:
                 out["joints"] = SK.launch_joints(out["rows"], self._sk, out["valid"], 1, self.H, self._sk_mean, self._sk_unit)
             if self._rest is not None:
                 out["rotations"] = SK.launch_rotations(out["rows"], self._sk, self._rest, out["valid"], 1, self.H, self._sk_mean, self._rot_space)
+            if self._sm is not None:                # the outputs, then the new history in a launch of its own
+                out["smooth"] = self._sm.run(out["rows"], out["valid"])
             return out
 
     def _push_only(self):
@@ -307,6 +327,7 @@ class GestureStream:
         dev = self.device
         snap = self._state.clone()
         rs_snap = self._rs.snapshot() if self._rs is not None else None      # the resampler's history advances with every run, too
+        sm_snap = self._sm.snapshot() if self._sm is not None else None      # and the smoother's
         cap = torch.cuda.Stream(dev)
         cap.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(cap):
@@ -320,6 +341,8 @@ class GestureStream:
         self._state.copy_(snap)
         if self._rs is not None:
             self._rs.restore(rs_snap)
+        if self._sm is not None:
+            self._sm.restore(sm_snap)
         torch.cuda.synchronize(dev)
         # the graph replays raw pointers into the engines' arenas and workspaces: keep them alive as long as the graph (ClipPipeline._capture)
         st = self._engine_state()
@@ -419,6 +442,7 @@ class GestureStream:
         self.last_window = out["window"].clone() if out is not None and self.want_windows else None
         self.last_joints = out["joints"].clone() if out is not None and self._sk is not None else None
         self.last_rotations = out["rotations"].clone() if out is not None and self._rest is not None else None
+        self.last_smooth = out["smooth"].clone() if out is not None and self._sm is not None else None
         if out is None:
             return None, torch.zeros(self.U, dtype=torch.int32, device=self.device)
         return out["rows"].clone(), out["valid"].clone()
@@ -468,6 +492,8 @@ class GestureStream:
         self._engine().stream_reset(self._state, *self._geom, seed, mask)
         if self._rs is not None:
             self._rs.reset(None if len(sel) == self.U else sel)
+        if self._sm is not None:
+            self._sm.reset(None if len(sel) == self.U else sel)
 
     def tail(self) -> torch.Tensor:
         """[U, P, D]: every row's current prior = the last P rows of its track."""
@@ -486,6 +512,14 @@ class GestureStream:
             raise L.EgError("tail_rotations: the session was opened without rotations=rest")
         with torch.no_grad():
             return SK.launch_rotations(self.tail(), self._sk, self._rest, None, 1, 1, self._sk_mean, self._rot_space)
+
+    def tail_smooth(self) -> torch.Tensor:
+        """[U, P + smooth_delay, D]: the last smoothed frames of every row's track (a session opened with smooth=); zeros for a row that has
+        emitted nothing."""
+        if self._sm is None:
+            raise L.EgError("tail_smooth: the session was opened without smooth=")
+        with torch.no_grad():
+            return self._sm.tail(self.tail())
 
     def finish(self, text, labels=None, z=None, sampled=None, last_chunk=None, ends=None) -> torch.Tensor:
         """End every row together and run R = text.shape[1] steps in all: `text [U, R, text_len]`, `labels [U, 8]` or `[U, R, 8]`, `z [U, R, 32]`

@@ -589,6 +589,60 @@ int eg_skeleton_rotations(const float* track, int32_t rows, int32_t T, const int
                           const float* d_mean, int32_t space, int32_t L, int32_t M, float* rotations, int64_t out_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Smoothed output: a Savitzky-Golay filter along the time axis of whole tracks on the device (csrc/smooth.hip)
+ * ------------------------------------------------------------------------------------------ */
+/* A filter is (window K, polyorder p, deriv d, delta): K odd, 3 <= K <= EG_SMOOTH_MAX_WINDOW; 1 <= p <= min(5, K - 1); 0 <= d <= min(2, p);
+ * delta = 1 / fps > 0 (it matters for d > 0 only); half = K / 2.
+ * eg_smooth_design (host only, no HIP call, usable without a GPU; refuses a bad K, p, d or delta by name) writes the table C[K][K]: row i
+ * holds the weights that give the d-th derivative at window position i of the least-squares polynomial of degree p through K equally spaced
+ * samples.  Designed in float64 with the abscissae centred on the window (t = j - half) and a QR factorisation; table32 is table64 rounded
+ * once to fp32 and is what the device reads (either pointer may be NULL, not both).
+ * Definition.  For a row with n >= K valid frames and every column:
+ *     head      i < half:             y[i] = sum_j C[i][j] x[j]
+ *     interior  half <= i < n - half: y[i] = sum_j C[half][j] x[i - half + j]
+ *     tail      i >= n - half:        y[i] = sum_j C[K - (n - i)][j] x[n - K + j]
+ * which is scipy.signal.savgol_filter(x, K, p, deriv=d, delta=delta, axis=0, mode="interp").  Frames i >= n of the output are zeros; source
+ * frames t >= n are never read and may hold NaN; no sample outside [0, n) enters any output (no padding at the ends).  On the device every
+ * output element is acc = 0, then acc = fmaf(C[.][j], x[.], acc) for j = 0 .. K - 1 in that order, in fp32.
+ * eg_smooth_tracks: track [rows, T, D] fp32 -> out [rows, T, D] fp32.  Row b has n = clamp(d_frames[b / draws] * frame_unit, 0, T) valid
+ * frames, exactly as in eg_skeleton_joints (d_frames NULL: T).  A row with n < K is refused by name -- there is no shrinking window -- and a
+ * device count cannot be checked before the launch, so the call also takes `frames`, the HOST copy of the counts (int32 [rows / draws];
+ * NULL exactly when d_frames is NULL), and checks that.  Nothing ties the two together: with a d_frames that differs from `frames` a row
+ * whose device count is below K comes out as zeros, and every access stays in range.  d_table: device copy of table32.
+ * All pointers are caller-owned; no allocation, no synchronisation, one launch on `stream`; the grid -- (tile of EG_SMOOTH_TILE_FRAMES
+ * frames) x (tile of EG_SMOOTH_TILE_COLS columns) x row -- depends on (rows, T, D) only, so the call captures into a hipGraph; one owning
+ * thread per output element, plain vector stores, no atomics.  A row's result does not depend on rows, on its place in the batch or on T.
+ * Refuses by name before the launch: null pointers, track / out / d_table not 16-byte aligned, out overlapping track, rows, T or D < 1, rows
+ * not a multiple of draws, frame_unit < 1, K out of range or even, a count below K, grid / index range.
+ * eg_smooth_tile_frames / eg_smooth_tile_cols: the two tile sizes. */
+#define EG_SMOOTH_MAX_WINDOW 31
+#define EG_SMOOTH_TILE_FRAMES 64
+#define EG_SMOOTH_TILE_COLS 64
+int eg_smooth_design(int32_t K, int32_t p, int32_t d, double delta, double* table64, float* table32);
+int32_t eg_smooth_tile_frames(void);
+int32_t eg_smooth_tile_cols(void);
+int eg_smooth_tracks(const float* track, int32_t rows, int32_t T, int32_t D, int32_t K, const float* d_table, const int32_t* frames,
+                     const int32_t* d_frames, int32_t draws, int32_t frame_unit, float* out, void* stream);
+/* Stream: the same filter on a track that arrives H frames per step.  state = the last K - 1 raw frames [rows, K - 1, D] fp32 followed by
+ * an int32 count of valid steps per row, in a caller-owned device buffer of eg_smooth_stream_state_bytes (0 for refused arguments).
+ * eg_smooth_stream_reset zeroes history and count of the rows with row_mask[u] != 0 (device int32 [rows]; NULL: every row).
+ * eg_smooth_stream_push: chunk [rows, H, D], the raw rows the step just emitted, and d_valid (device int32 [rows], the step's valid flags;
+ * NULL: every row) -> out [rows, H, D].  A valid row in its s-th valid step gets the smoothed frames [sH - half, (s + 1)H - half) of its
+ * track -- the output runs `half` frames behind the input; entries with a negative frame index, the first `half` of step 0, are zeros.  A
+ * row that is not valid gets zeros and its state stays as it is.  K <= H is required (the head frames need x[0 .. K) inside the first
+ * chunk).  Two launches: the outputs, then the new history and count in a launch of their own, so no launch reads and overwrites the state.
+ * eg_smooth_stream_tail: tail_rows [rows, P, D], the last P raw frames of every track (eg_stream_tail's; P >= 1) -> out [rows, P + half, D],
+ * the last P + half smoothed frames (zeros for a row without a valid step); the state is read only.
+ * Every element comes from the device function the offline kernel uses: the pushes of a row, concatenated after dropping step 0's `half`
+ * leading zeros, followed by the tail, are eg_smooth_tracks on the finished track bit for bit. */
+int64_t eg_smooth_stream_state_bytes(int32_t rows, int32_t D, int32_t K);
+int eg_smooth_stream_reset(void* state, int32_t rows, int32_t D, int32_t K, const int32_t* row_mask, void* stream);
+int eg_smooth_stream_push(void* state, int32_t rows, int32_t H, int32_t D, int32_t K, const float* d_table, const float* chunk,
+                          const int32_t* d_valid, float* out, void* stream);
+int eg_smooth_stream_tail(const void* state, int32_t rows, int32_t P, int32_t D, int32_t K, const float* d_table, const float* tail_rows,
+                          float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Beat-alignment score = model/Beat_score_v2.py alignment(sigma, order): load_audio + load_pose +
  * calculate_align for a batch of clips (test_emotion_gesture_diversity_iterative.py:241-248)
  * ------------------------------------------------------------------------------------------ */

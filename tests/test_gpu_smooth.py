@@ -1,0 +1,245 @@
+"""The smoothing filter on the GPU (eg_smooth_tracks / eg_smooth_stream_* through smooth.smooth_tracks, harness.synthesize(smooth=),
+synthesize_takes(smooth=) and GestureStream(smooth=)) against the float64 restatement tests/smooth_np.py, element by element within the
+a-priori bound stated there, and against itself bit for bit: a row alone against the row in a batch, graph replay against eager, the stream
+against the offline call on the finished track, the callers against the function."""
+import numpy as np
+import pytest
+import torch
+
+import smooth_np as SN
+from emotiongestures_amd import _lib as L
+from emotiongestures_amd import harness as Hs
+from emotiongestures_amd import skeleton as SK
+from emotiongestures_amd import smooth as SM
+from emotiongestures_amd.synth import load_synth_weights, synth_audio
+from skeleton_gpu_common import D_, H_, HOP, N, P_, dev, inputs, ted_models
+
+pytestmark = pytest.mark.gpu
+
+TF, TC = SM.TILE_FRAMES, SM.TILE_COLS
+FILTERS = [(3, 1, 0), (9, 3, 0), (9, 3, 1), (15, 3, 2), (31, 5, 0)]
+_SM = {}
+
+
+def smoother(K, p, d=0):
+    if (K, p, d) not in _SM:
+        _SM[(K, p, d)] = SM.Smoother(K, p, d, fps=15)
+    return _SM[(K, p, d)]
+
+
+def check(sm, v, frames, what):
+    """One call on the device against the restatement: every element inside the bound, zeros behind every recording's end."""
+    K = sm.window
+    lead = v.shape[:-2]
+    R = lead[1] if len(lead) == 2 else 1
+    got = SM.smooth_tracks(torch.from_numpy(v).to(dev()), sm, frames=frames)
+    assert got.is_cuda and got.dtype == torch.float32 and tuple(got.shape) == v.shape, what
+    per_row = None if frames is None else [n for n in frames for _ in range(R)]
+    flat = v.reshape((-1,) + v.shape[-2:])
+    want, mag = SN.smooth(flat, sm.table, per_row)
+    g = got.cpu().numpy().astype(np.float64).reshape(flat.shape)
+    assert np.isfinite(g).all(), what
+    err, bound = np.abs(g - want), SN.bound(mag, K)
+    ratio = float((err[bound > 0] / bound[bound > 0]).max())
+    print(f"{what}: worst error / bound {ratio:.3f}")
+    assert (err <= bound).all(), (what, ratio)
+    for b, n in enumerate(per_row or []):
+        assert not g[b, n:].any(), (what, b)
+    return got
+
+
+@pytest.mark.parametrize("K,p,d", FILTERS)
+def test_every_element_within_the_bound_of_the_float64_definition(K, p, d):
+    """D = 5 (less than a column tile), 126 and 282 (two and five column tiles, the last one partial, rows 16-byte aligned every other frame);
+    T = one frame tile + 1 and two tiles + half; frames = K exactly (head, centre and tail rows meet), K + 1, one below a tile boundary, T;
+    NaN behind every recording's end."""
+    sm = smoother(K, p, d)
+    half = K // 2
+    for D in (5, 126, 282):
+        for T in (TF + 1, 2 * TF + half):
+            rng = np.random.default_rng(1000 * K + 10 * D + T)
+            scale = [0.01, 1.0, 30.0][(D + T) % 3]
+            check(sm, (rng.standard_normal((T, D)) * scale).astype(np.float32), None, f"K={K} p={p} d={d} [T={T}, D={D}]")
+            for shape, frames in (((3, T, D), [K, TF - 1, T]), ((2, 3, T, D), [K + 1, min(T, 2 * TF - 1)])):
+                v = (rng.standard_normal(shape) * scale).astype(np.float32)
+                for u, n in enumerate(frames):
+                    v[u, ..., n:, :] = np.nan
+                check(sm, v, frames, f"K={K} p={p} d={d} {list(shape)} frames={frames}")
+
+
+@pytest.mark.parametrize("K,p", [(9, 3), (31, 5)])
+def test_a_row_does_not_depend_on_the_batch_or_on_T(K, p):
+    sm = smoother(K, p)
+    n, D = TF + 3, 126
+    rng = np.random.default_rng(K)
+    row = rng.standard_normal((n, D)).astype(np.float32)
+    alone = SM.smooth_tracks(torch.from_numpy(row).to(dev()), sm)
+    for place in (0, 2):
+        T = 2 * TF + 5
+        v = rng.standard_normal((3, T, D)).astype(np.float32)
+        frames = [T, K, T - 1]
+        frames[place] = n
+        v[place, :n] = row
+        v[place, n:] = np.nan
+        got = SM.smooth_tracks(torch.from_numpy(v).to(dev()), sm, frames=frames)
+        assert torch.equal(got[place, :n], alone) and not got[place, n:].any(), place
+    assert torch.equal(SM.smooth_tracks(torch.from_numpy(row[None]).to(dev()), sm, frames=[n])[0], alone)
+
+
+def test_graph_replay_equals_the_eager_call():
+    from emotiongestures_amd.pipeline import CAPTURE_MODE
+    sm = smoother(9, 3)
+    T, D, frames = 2 * TF + 4, 126, [2 * TF + 4, TF - 1, 9, 40, 2 * TF, 12]
+    rng = np.random.default_rng(77)
+    x = torch.from_numpy(rng.standard_normal((6, T, D)).astype(np.float32)).to(dev())
+    d_frames = torch.tensor(frames, dtype=torch.int32, device=dev())
+    SM.launch_smooth(x, sm, frames, d_frames)                               # the warm-up: the table is uploaded here
+    out = torch.full_like(x, float("nan"))
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, capture_error_mode=CAPTURE_MODE):
+        SM.launch_smooth(x, sm, frames, d_frames, out=out)
+    for k in range(2):
+        x.copy_(torch.from_numpy(rng.standard_normal((6, T, D)).astype(np.float32)))
+        out.fill_(float("nan"))
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out, SM.launch_smooth(x, sm, frames, d_frames)), k
+    # the draws axis: one count per recording, shared by its rows
+    d2 = torch.tensor(frames[:3], dtype=torch.int32, device=dev())
+    pairs = SM.launch_smooth(x, sm, frames[:3], d2, draws=2)
+    each = SM.launch_smooth(x, sm, [n for n in frames[:3] for _ in range(2)], torch.tensor([n for n in frames[:3] for _ in range(2)], dtype=torch.int32,
+                                                                                          device=dev()))
+    assert torch.equal(pairs, each)
+
+
+# ---- the callers ---------------------------------------------------------------------------------------------------------------------------
+def test_stream_pushes_and_tail_are_the_offline_call_on_the_finished_track():
+    """U = 3, K = 9, six pushes (a window spans two): row 0 runs through; row 1 ends inside push 3 (three windows, then not valid); row 2 is
+    reset after push 3 and rejoins with a second recording, so it is not valid in push 4 beside rows that are.  Every finished track: the
+    concatenated last_smooth without step 0's leading `half` entries, then tail_smooth(), against smooth_tracks on the raw rows + tail()."""
+    model, vae = ted_models()
+    U, K = 3, 9
+    sm = smoother(K, 3)
+    half = K // 2
+    g = inputs(U, 6, 90)
+    audio = torch.from_numpy(synth_audio(U, 6 * HOP, seed=91)).to(dev())
+    s = Hs.open_stream((model, vae), U, g["seed_pose"], hop_samples=HOP, smooth=(K, 3))
+    assert s.smooth_delay == half and s.last_smooth is None
+    raw, smo = [[] for _ in range(U)], [[] for _ in range(U)]
+    seen = []
+
+    def finished(u):
+        track = torch.cat(raw[u] + [s.tail()[u]], 0)
+        got = torch.cat([torch.cat(smo[u], 0)[half:], s.tail_smooth()[u]], 0)
+        want = SM.smooth_tracks(track, sm)
+        assert tuple(s.tail_smooth().shape) == (U, P_ + half, D_) and got.shape == want.shape == track.shape
+        assert torch.equal(got, want), u
+        assert not torch.cat(smo[u], 0)[:half].any()
+        return track.shape[0]
+
+    for k in range(6):
+        rows, valid = s.push(audio[:, k * HOP:(k + 1) * HOP].contiguous(), g["text"][:, k], g["label"][:, k], g["z"][:, k],
+                             ends=[-1, 100, -1] if k == 2 else None)
+        v = valid.cpu().tolist()
+        seen.append(v)
+        assert (rows is None) == (s.last_smooth is None) == (k == 0)
+        for u in range(U):
+            if v[u]:
+                raw[u].append(rows[u])
+                smo[u].append(s.last_smooth[u])
+            elif rows is not None:
+                assert not s.last_smooth[u].any()           # a row that is not valid: zeros, and (below) a state that did not move
+        if k == 2:                                          # row 2's first recording ends here: two windows
+            assert finished(2) == 2 * H_ + P_
+            raw[2], smo[2] = [], []
+            s.reset(rows=[2])
+    assert seen == [[0, 0, 0], [1, 1, 1], [1, 1, 1], [1, 1, 0], [1, 0, 1], [1, 0, 1]]
+    assert [finished(u) for u in range(U)] == [5 * H_ + P_, 3 * H_ + P_, 2 * H_ + P_]
+    # eager session, same inputs: the same bits as the graph's
+    e = Hs.open_stream((model, vae), U, g["seed_pose"], hop_samples=HOP, smooth=sm, graph=False)
+    for k in range(2):
+        e.push(audio[:, k * HOP:(k + 1) * HOP].contiguous(), g["text"][:, k], g["label"][:, k], g["z"][:, k])
+    assert torch.equal(e.last_smooth[0], smo[0][0])
+
+
+def test_stream_refusals_by_name():
+    model, vae = ted_models()
+    g = inputs(2, 1, 92)
+    with pytest.raises(L.EgError, match="window=31 > H=30"):
+        Hs.open_stream((model, vae), 2, g["seed_pose"], hop_samples=HOP, smooth=(31, 3))
+    with pytest.raises(L.EgError, match="smooth= together with joints="):
+        Hs.open_stream((model, vae), 2, g["seed_pose"], hop_samples=HOP, smooth=(9, 3), joints=SK.ted_expressive())
+    with pytest.raises(L.EgError, match="deriv=1"):
+        Hs.open_stream((model, vae), 2, g["seed_pose"], hop_samples=HOP, smooth=SM.Smoother(9, 3, deriv=1))
+    s = Hs.open_stream((model, vae), 2, g["seed_pose"], hop_samples=HOP)
+    with pytest.raises(L.EgError, match="opened without smooth="):
+        s.tail_smooth()
+
+
+def same_but(got, plain, extra):
+    assert set(got) == set(plain) | extra
+    for k, v in plain.items():
+        assert torch.equal(got[k], v) if isinstance(v, torch.Tensor) else got[k] == v, k
+
+
+def test_synthesize_smooth_on_ragged_recordings_with_beat():
+    """A BEAT-shaped generator (282 columns), lengths=: 3 and 2 windows; the beat score keeps scoring the raw track."""
+    from conftest import build_mirror
+    from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
+    import rollout_np as R
+    Fb, Db, Pb = 60, 282, 10
+    model = build_mirror("spatial", Fb, Db, Pb, 10, seed=31).to(dev())
+    vae = load_synth_weights(MLP_Reconstruct_v3(), 31).eval().to(dev())
+    U, hop = 2, 53333
+    lengths = [3 * hop - 100, hop + 700]
+    rng = np.random.default_rng(5)
+    a = 0.05 * rng.standard_normal((U, max(lengths))).astype(np.float32)
+    for k in range(0, max(lengths), 7000):                                      # bursts: onsets for the beat score
+        a[:, k:k + 800] += rng.standard_normal((U, min(800, max(lengths) - k))).astype(np.float32)
+    audio = torch.from_numpy(a).to(dev())
+    inp = R.rollout_inputs(U, 3, Fb, Db, Pb, seed=120)
+    text, seed_pose = torch.from_numpy(inp["text"]).to(dev()), torch.from_numpy(inp["seed_pose"]).to(dev())
+    kw = dict(labels=torch.from_numpy(inp["label"]).to(dev())[:, 0].contiguous(), z=torch.from_numpy(inp["z"]), lengths=lengths, hop_samples=hop,
+              beat=True)
+    plain = Hs.synthesize((model, vae), audio, text, seed_pose, **kw)
+    got = Hs.synthesize((model, vae), audio, text, seed_pose, smooth=(9, 3), **kw)
+    same_but(got, plain, {"track_smooth"})
+    frames = [w * (Fb - Pb) + Pb for w in got["windows_per"]]
+    assert got["windows_per"] == [3, 2] and got["track_smooth"].shape == got["track"].shape
+    assert torch.equal(got["track_smooth"], SM.smooth_tracks(got["track"], (9, 3), frames=frames))
+    assert not got["track_smooth"][1, frames[1]:].any() and got["track_smooth"][1, :frames[1]].any()
+
+
+def test_synthesize_draws_and_takes_smooth_feeds_joints_and_leaves_the_raw_scores():
+    model, vae = ted_models()
+    sk = SK.ted_expressive()
+    sm = smoother(9, 3)
+    U, W, Rd = 2, 2, 2
+    g = inputs(U, W, 80)
+    zz = torch.from_numpy(np.random.default_rng(83).standard_normal((U, Rd, W, 32)).astype(np.float32))
+    # draws=2, rectangular, joints from the smoothed track
+    audio = torch.from_numpy(synth_audio(U, HOP + N, seed=82)).to(dev())
+    kw = dict(labels=g["label"], hop_samples=HOP, z=zz, draws=Rd, joints=sk)
+    plain = Hs.synthesize((model, vae), audio, g["text"], g["seed_pose"], **kw)
+    got = Hs.synthesize((model, vae), audio, g["text"], g["seed_pose"], smooth=sm, **kw)
+    assert set(got) == set(plain) | {"track_smooth"} and torch.equal(got["track"], plain["track"])
+    assert tuple(got["track_smooth"].shape) == (U, Rd, W * H_ + P_, D_)
+    assert torch.equal(got["track_smooth"], SM.smooth_tracks(got["track"], sm, frames=[W * H_ + P_] * U))
+    want, _n = SK.joints_from_tracks(got["track_smooth"], sk, frames=[W * H_ + P_] * U)
+    assert torch.equal(got["joints"], want) and not torch.equal(got["joints"], plain["joints"])
+    # takes: recordings of unequal length, draws=2, the take distances of the raw tracks
+    fgd = load_synth_weights(Hs.MLP_Reconstruct(pose_dim=D_), 5).eval().to(dev())
+    lens = [2 * HOP - 7, HOP - 5]
+    audio = torch.from_numpy(synth_audio(U, max(lens), seed=80)).to(dev())
+    kw = dict(lengths=lens, draws=Rd, z=zz, hop_samples=HOP, diversity=fgd, joints=sk)
+    plain = Hs.synthesize_takes((model, vae), audio, g["text"], g["seed_pose"], g["label"][:, 0].contiguous(), **kw)
+    got = Hs.synthesize_takes((model, vae), audio, g["text"], g["seed_pose"], g["label"][:, 0].contiguous(), smooth=(9, 3), **kw)
+    assert set(got) == set(plain) | {"track_smooth"}
+    for k in ("track", "take_distance", "take_diversity"):
+        assert torch.equal(got[k], plain[k]), k
+    frames = [w * H_ + P_ for w in got["windows_per"]]
+    assert got["windows_per"] == [2, 1]
+    assert torch.equal(got["track_smooth"], SM.smooth_tracks(got["track"], sm, frames=frames))
+    want, _n = SK.joints_from_tracks(got["track_smooth"], sk, frames=frames)
+    assert torch.equal(got["joints"], want) and not got["track_smooth"][1, :, frames[1]:].any()

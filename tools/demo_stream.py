@@ -14,7 +14,11 @@ rows just emitted in stream.last_joints [U, 30, 43, 3]; the script prints their 
 With --rotations (and --joints) the stream also gets rotations=rest, the rest pose taken from the normalised first generated frame of row 0 (one
 window of synthesize beforehand): another launch inside the graph leaves the local bone rotations of the rows just emitted in
 stream.last_rotations [U, 30, 42, 4]; the script prints the largest elbow swing in degrees per push.
-usage: demo_stream.py [rows=4] [seconds=20] [--audio-rate HZ] [--joints [--rotations]]"""
+With --smooth K P (not with --joints) the stream is opened with smooth=(K, P): two more launches inside the graph leave in stream.last_smooth
+[U, 30, 126] the Savitzky-Golay-smoothed frames of every row, K // 2 frames behind the rows just emitted; the script prints the frame-to-frame
+step of the raw and the smoothed rows per push, and every row's smoothed rows followed by tail_smooth() are checked to EQUAL
+smooth.smooth_tracks on its finished track.
+usage: demo_stream.py [rows=4] [seconds=20] [--audio-rate HZ] [--joints [--rotations]] [--smooth K P]"""
 import os
 import sys
 import time
@@ -45,6 +49,15 @@ if ROTATIONS:
     sys.argv.remove("--rotations")
     if not JOINTS:
         sys.exit("--rotations needs --joints (the rest pose belongs to the skeleton's bones)")
+SMOOTH = None
+if "--smooth" in sys.argv:
+    i = sys.argv.index("--smooth")
+    SMOOTH = (int(sys.argv[i + 1]), int(sys.argv[i + 2]))
+    del sys.argv[i:i + 3]
+    if JOINTS:
+        sys.exit("--smooth is not combined with --joints in a stream (the smoothed rows run half a window behind; smooth the finished track with "
+                 "demo_synthesize.py --smooth K P --joints)")
+    JK["smooth"] = SMOOTH
 U = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 20.0
 dev = torch.device("cuda:0")
@@ -79,11 +92,14 @@ feeds = {u: [(1, audio[u], total)] for u in range(U)}
 feeds[leaver] = [(1, audio[leaver, :short], short), (rejoin, second, short)]
 tracks = {u: [[] for _ in feeds[u]] for u in range(U)}
 zs = {u: [[] for _ in feeds[u]] for u in range(U)}
-tails = {}
+smooths = {u: [[] for _ in feeds[u]] for u in range(U)}
+tails, tails_smooth = {}, {}
 t_steps = []
 for k in range(1, steps + 1):
     if k == rejoin:
         tails[(leaver, 0)] = stream.tail()[leaver].clone()
+        if SMOOTH:
+            tails_smooth[(leaver, 0)] = stream.tail_smooth()[leaver].clone()
         stream.reset(rows=[leaver], seed_pose=seed2)
     chunk, ends, which = torch.zeros(U, hop, device=dev), [-1] * U, [0] * U
     for u in range(U):
@@ -103,6 +119,8 @@ for k in range(1, steps + 1):
         if stream.last_valid[u]:
             tracks[u][which[u]].append(rows[u])
             zs[u][which[u]].append(z[k - 1, u])
+            if SMOOTH:
+                smooths[u][which[u]].append(stream.last_smooth[u])
     print(f"push {k:2d}: valid {valid.cpu().tolist()}  windows {stream.last_windows}  {1e3 * t_steps[-1]:.2f} ms")
     if JOINTS and stream.last_joints is not None:
         j = stream.last_joints
@@ -112,7 +130,14 @@ for k in range(1, steps + 1):
         q = stream.last_rotations[valid.bool()]             # a row that was not valid holds zeros, not rotations
         deg = [float(torch.rad2deg(2 * torch.acos(q[:, :, b, 0].clamp(max=1.0))).max()) for b in (4, 21)]      # the forearm bones
         print(f"         last_rotations {tuple(q.shape)}: largest elbow swing left {deg[0]:.1f} degrees, right {deg[1]:.1f} degrees")
+    if SMOOTH and stream.last_smooth is not None:
+        live = valid.bool() & torch.tensor([len(smooths[u][which[u]]) > 1 for u in range(U)], device=dev)     # past step 0's leading zeros
+        if bool(live.any()):
+            d = lambda t: float((t[live][:, 1:] - t[live][:, :-1]).norm(dim=2).mean())
+            print(f"         last_smooth {tuple(stream.last_smooth.shape)}, {stream.smooth_delay} frames behind: mean |pose[t+1] - pose[t]| "
+                  f"{d(rows):.4f} raw, {d(stream.last_smooth):.4f} smoothed")
 final = stream.tail()
+final_smooth = stream.tail_smooth() if SMOOTH else None
 
 ok = True
 for u in range(U):
@@ -131,5 +156,11 @@ for u in range(U):
         same = torch.equal(got, want)
         ok &= same
         print(f"row {u} recording {i}: {T / RATE:.1f} s -> {n_win} windows -> track {tuple(got.shape)}; equals harness.synthesize: {same}")
+        if SMOOTH:
+            from emotiongestures_amd.smooth import smooth_tracks
+            sm_got = torch.cat([torch.cat(smooths[u][i], 0)[stream.smooth_delay:], tails_smooth.get((u, i), final_smooth[u])], 0)
+            same = torch.equal(sm_got, smooth_tracks(got, SMOOTH))
+            ok &= same
+            print(f"         smoothed rows + tail_smooth {tuple(sm_got.shape)}; equal smooth_tracks on the finished track: {same}")
 print(f"steady-state push (one graph replay + copies, synchronised): {1e3 * sorted(t_steps)[len(t_steps) // 2]:.2f} ms for {hop / RATE:.1f} s of audio per row")
 sys.exit(0 if ok else 1)

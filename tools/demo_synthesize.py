@@ -23,7 +23,10 @@ script prints their shape and how far the two wrists travel.
 With --rotations (and --joints) the call also returns one local rotation per bone and frame (unit quaternions w, x, y, z relative to the parent
 bone: what a rigged avatar takes) against a rest pose taken from the normalised first generated frame of recording 0, and the script prints
 their shape and the largest elbow swing in degrees.
-usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--joints-fps N] [--rotations]] [--out tracks.npz]"""
+With --smooth K P the call also returns the smoothed track (smooth.smooth_tracks: a Savitzky-Golay filter of window K and polyorder P along
+time, scipy.signal.savgol_filter(mode="interp"), one more launch); with --joints the joints (and rotations) are made from it, and the script
+prints the mean frame-to-frame step of the left wrist before and after -- without --joints, of the pose vector.
+usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--joints-fps N] [--rotations]] [--smooth K P] [--out tracks.npz]"""
 import os
 import sys
 import time
@@ -38,7 +41,7 @@ from emotiongestures_amd.builders import build_mirror
 from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
 from emotiongestures_amd.synth import load_synth_weights, synth_audio
 
-argv, DRAWS, OUT, BEAT, DIVERSITY, RATE, JOINTS, JOINTS_FPS, ROTATIONS = [], 0, None, False, False, 16000, False, None, False
+argv, DRAWS, OUT, BEAT, DIVERSITY, RATE, JOINTS, JOINTS_FPS, ROTATIONS, SMOOTH = [], 0, None, False, False, 16000, False, None, False, None
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--draws":
@@ -57,6 +60,8 @@ for a in it:
         JOINTS_FPS = int(next(it))
     elif a == "--rotations":
         ROTATIONS = True
+    elif a == "--smooth":
+        SMOOTH = (int(next(it)), int(next(it)))
     else:
         argv.append(a)
 if DIVERSITY and DRAWS < 2:
@@ -109,7 +114,7 @@ if BEAT:
     print(f"--beat: beat-alignment score per recording: {[round(float(v), 4) for v in out['beat'].cpu()]}")
 if JOINTS:
     from emotiongestures_amd.skeleton import ted_expressive
-    jk = dict(joints=ted_expressive(), joints_unit=True, joints_fps=(FPS, JOINTS_FPS) if JOINTS_FPS else None)
+    jk = dict(joints=ted_expressive(), joints_unit=True, joints_fps=(FPS, JOINTS_FPS) if JOINTS_FPS else None, smooth=SMOOTH)
     if ROTATIONS:                                        # the rest pose: the first generated frame of recording 0 (normalised by the call)
         jk["rotations"] = track[0, PRIOR].reshape(-1, 3).cpu()
     H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, **jk, **AR)          # warm-up (uploads the bone table)
@@ -123,11 +128,22 @@ if JOINTS:
     print(f"--joints: joints {tuple(joints.shape)} (frames per recording {jo['joint_frames']}" +
           (f", {FPS} -> {JOINTS_FPS} fps" if JOINTS_FPS else "") + f"), one more launch in the call ({1e3 * dt_j:.2f} ms against {1e3 * dt:.2f} ms); "
           f"wrist extent: left {float(extent(6)):.3f} m, right {float(extent(7)):.3f} m")
+    if SMOOTH:                                           # the joints above come from out["track_smooth"]; the raw track's for comparison
+        from emotiongestures_amd.skeleton import joints_from_tracks
+        raw = joints_from_tracks(jo["track"], jk["joints"], unit=True, fps=jk["joints_fps"])
+        raw = raw[0] if isinstance(raw, tuple) else raw
+        wrist_step = lambda j: float((j[:, 1:, 6] - j[:, :-1, 6]).norm(dim=2).mean())
+        print(f"--smooth {SMOOTH[0]} {SMOOTH[1]}: track_smooth {tuple(jo['track_smooth'].shape)}, one more launch; mean frame-to-frame step of the left "
+              f"wrist: {1e3 * wrist_step(raw):.2f} mm raw, {1e3 * wrist_step(joints):.2f} mm smoothed")
     if ROTATIONS:
         rot = jo["rotations"]
         swing = lambda k: float(torch.rad2deg(2 * torch.acos(rot[:, :, k, 0].clamp(max=1.0))).max())    # bone 4 / 21: left / right forearm
         print(f"--rotations: rotations {tuple(rot.shape)}, one more launch; largest elbow swing against the first generated frame: "
               f"left {swing(4):.1f} degrees, right {swing(21):.1f} degrees")
+if SMOOTH and not JOINTS:
+    ts = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, smooth=SMOOTH, **AR)["track_smooth"]
+    print(f"--smooth {SMOOTH[0]} {SMOOTH[1]}: track_smooth {tuple(ts.shape)}, one more launch; mean |pose[t+1] - pose[t]|: {float(step.mean()):.4f} raw, "
+          f"{float((ts[:, 1:] - ts[:, :-1]).norm(dim=2).mean()):.4f} smoothed")
 
 # Recordings of unequal length in one call: recording u keeps (u + 1) / U of the audio.  Step s runs only the recordings that still have a
 # window s; the track is padded to the longest recording and zero past each recording's own end.
