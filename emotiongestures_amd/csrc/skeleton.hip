@@ -16,6 +16,9 @@
 //             quaternion products, so it is walked level by level: the host orders the bones by depth, one thread owns one (output frame, bone of
 //             the level), one barrier per level.  The global rotations live in an LDS tile g[bone][component][frame] (lanes of consecutive frames
 //             on consecutive banks); x is blended and normalised in registers as it is read; every (frame, bone) leaves as one aligned 16-byte store.
+//   articulated bodies (eg_articulate_check, eg_articulate_levels, eg_articulate_forward, eg_articulate_rot6d): tracks of 6-D joint rotations
+//             (pose_dim = 6J) -> joint positions and joint rotations in one launch, on the same tile walk with a tile height of its own, and the
+//             elementwise inverse; see the section further down.
 #include "common.h"
 #include <math.h>
 
@@ -113,11 +116,11 @@ __device__ __forceinline__ Head load_head(const Args& a, float* lds) {
 // the selects, the joints prologue loses three scalar instructions, all code behind it moves by 12 bytes and the native kernel measures 1-2 % slower.
 struct Tile { int b; long long k0; int cnt, n; long long live64; int live; };
 
-template <bool NATIVE>
+template <bool NATIVE, int TILE = TF>
 __device__ __forceinline__ Tile tile_of(const Args& a, long long T_out) {
     const int b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
-    const long long k0 = (long long)tile * TF;
-    const int cnt = (int)(T_out - k0 < TF ? T_out - k0 : TF);
+    const long long k0 = (long long)tile * TILE;
+    const int cnt = (int)(T_out - k0 < TILE ? T_out - k0 : TILE);
     const int n = valid_frames(a, b);
     const long long n_out = NATIVE ? n : out_frames(n, a.L, a.M);
     const long long live = n_out - k0 < 0 ? 0 : (n_out - k0 < cnt ? n_out - k0 : cnt);
@@ -130,11 +133,11 @@ __device__ __forceinline__ void zero_tail(float* __restrict__ dst, long long out
 }
 
 // The source frames of a tile of the forward kernels.  A pass makes the outputs [i, i1) of the tile from the source frames
-// [s_base, s_base + nslots): as many outputs as SLOTS source frames reach (all of them unless the rate drops, M > L).
+// [s_base, s_base + nslots): as many outputs as SL source frames reach (all of them unless the rate drops, M > L).  SL: the tile height + 2.
 struct Pass { long long s_base; int i1, nslots; };
 struct Blend { int slot; float f; };                    // output = frame(slot) + (frame(slot + 1) - frame(slot)) * f, slots counted from s_base
 
-template <bool NATIVE>
+template <bool NATIVE, int SL = SLOTS>
 struct Walk {
     long long k0;
     int n, L, M;
@@ -148,7 +151,7 @@ struct Walk {
         const long long s_base = seg(k0 + i);
         int i1 = live;
         if (!NATIVE && M > L) {
-            const long long jmax = ((s_base + SLOTS - 1) * L - 1) / M - k0;     // last output whose segment starts at or before s_base + SLOTS - 2
+            const long long jmax = ((s_base + SL - 1) * L - 1) / M - k0;        // last output whose segment starts at or before s_base + SL - 2
             i1 = jmax + 1 < live ? (int)(jmax + 1) : live;
             i1 = i1 > i ? i1 : i + 1;
         }
@@ -163,8 +166,8 @@ struct Walk {
 // The pass that starts at output i of the tile (for (i = 0; i < live; i = p.i1)): its source frames staged into xin, one barrier behind the
 // loads; returns where they start.  No barrier before the staging of a later pass: the last barrier of the caller's pass ended the reads of
 // xin (joints: the one behind the chain; rotations: the one behind the last level), and the one here precedes every write of the caller's tile.
-template <bool NATIVE>
-__device__ __forceinline__ float* stage_pass(const Args& a, const Tile& t, const Walk<NATIVE>& w, int i, float* xin, Pass& p) {
+template <bool NATIVE, int SL = SLOTS>
+__device__ __forceinline__ float* stage_pass(const Args& a, const Tile& t, const Walk<NATIVE, SL>& w, int i, float* xin, Pass& p) {
     const int D = 3 * a.K;
     p = w.pass(i, t.live);
     const long long g0 = ((long long)t.b * a.T + p.s_base) * D;
@@ -371,6 +374,189 @@ __global__ __launch_bounds__(THREADS) void skeleton_rotations_kernel(const Args 
     }
 }
 
+// ---- articulated bodies: 6-D joint rotations -> joints and rotations (eg_articulate_*) ---------------------------------------------------------
+// The rotations kernel's grid, staging and level walk on a tile of TFA output frames; the state of a joint is its global rotation as a matrix
+// and its position, 12 floats in an LDS tile st[joint][component][frame] (the chain is then the definition's own sequence of products, and a
+// degenerate group stays what the definition says).  A pass has two phases: R_j of every (frame, joint) at once -- Gram-Schmidt with its
+// square roots and divisions has no parent -- then the level walk, which only multiplies (skipped when nothing asks for G or p).  A joint's plane has AST = 13 rows of TFA floats: the spare row keeps the joints of a level
+// off each other's banks.  The six numbers of a joint are read straight from the staged quads -- no second copy -- so the staged frames
+// ((TFA + 2) x 6J floats) and the state (J x AST) share the workgroup's LDS about evenly: 45 KiB at J = 64, 34 KiB at J = 47.
+// The level table of eg_articulate_levels: the level count | ALEVELS level offsets | order [J] | parents [J] | offsets [3J].
+constexpr int TFA = EG_ARTICULATE_TILE_FRAMES;
+constexpr int SLA = TFA + 2;
+constexpr int MAX_J = EG_ARTICULATE_MAX_JOINTS;
+constexpr int ALEVELS = MAX_J + 1;                      // a level per joint at most, and the offset behind the last one
+constexpr int AL_FIRST = 1, AL_ORDER = AL_FIRST + ALEVELS;
+__host__ __device__ constexpr int al_parents(int J) { return AL_ORDER + J; }
+__host__ __device__ constexpr int al_offsets(int J) { return AL_ORDER + 2 * J; }
+static_assert(al_offsets(1) + 3 == EG_ARTICULATE_LEVEL_WORDS(1) && al_offsets(MAX_J) + 3 * MAX_J == EG_ARTICULATE_LEVEL_WORDS(MAX_J), "the header's table size");
+constexpr int AL_OFFS = round4(ALEVELS);                // LDS words: level offsets [nlev + 1 <= ALEVELS] (+ pad)
+constexpr int AHEAD = AL_OFFS + 2 * MAX_J + 3 * MAX_J + 6 * MAX_J;      // offsets | order | parents | offsets [3 * 64] | mean [6 * 64]
+constexpr int AST = 13 * TFA;
+static_assert(AHEAD % 4 == 0, "the staged frames start on a quad");
+static_assert((AHEAD + round4(SLA * 6 * MAX_J + 8) + MAX_J * AST) * sizeof(float) <= 64 * 1024, "a workgroup's LDS at J = 64");
+constexpr int TFI = 16;                                 // frames of one workgroup of the inverse
+
+// Args::K counts the 3-vectors of a source frame, 2J: stage_pass and load_mean then see rows of 3K = 6J floats.
+struct ArtArgs { Args a; float* rot; int J, columns; };
+
+// quat(m) of the header: the branch of the first largest of (trace, m00, m11, m22), normalised, w >= 0.
+__device__ __forceinline__ f4 quat_of(const float* m) {
+    const float tr = m[0] + m[4] + m[8];
+    float w, x, y, z;
+    if (tr >= m[0] && tr >= m[4] && tr >= m[8]) { w = 1.f + tr; x = m[7] - m[5]; y = m[2] - m[6]; z = m[3] - m[1]; }
+    else if (m[0] >= m[4] && m[0] >= m[8]) { w = m[7] - m[5]; x = 1.f + m[0] - m[4] - m[8]; y = m[1] + m[3]; z = m[2] + m[6]; }
+    else if (m[4] >= m[8]) { w = m[2] - m[6]; x = m[1] + m[3]; y = 1.f - m[0] + m[4] - m[8]; z = m[5] + m[7]; }
+    else { w = m[3] - m[1]; x = m[2] + m[6]; y = m[5] + m[7]; z = 1.f - m[0] - m[4] + m[8]; }
+    float d = fmaxf(sqrtf(w * w + x * x + y * y + z * z), 1e-12f);
+    if (w < 0.f) d = -d;
+    return f4{w / d, x / d, y / d, z / d};
+}
+
+// NATIVE: L / M = 1.  GLOBAL: the rotations hold G_j, else R_j.  a.dst: the joints or null; k.rot: the rotations or null.
+template <bool NATIVE, bool GLOBAL>
+__global__ __launch_bounds__(THREADS) void articulate_kernel(const ArtArgs k) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const Args& a = k.a;
+    const int J = k.J, D = 6 * J, J3 = 3 * J, tid = threadIdx.x;
+    int* lv = reinterpret_cast<int*>(lds);
+    int* ord = lv + AL_OFFS;
+    int* par = ord + MAX_J;
+    float* off = lds + AL_OFFS + 2 * MAX_J;
+    float* mn = off + 3 * MAX_J;
+    float* xin = lds + AHEAD;
+    float* st = xin + round4(SLA * D + 8);                                      // st[joint][component][frame of the tile]
+    const Tile t = tile_of<NATIVE, TFA>(a, a.T_out);
+    const long long f0 = (long long)t.b * a.T_out + t.k0;                       // the tile's first output frame
+    if (a.dst) zero_tail(a.dst, f0 * J3, J3, t);
+    float* rot = k.rot ? k.rot + f0 * 4 * J : nullptr;                          // 16-byte aligned: every joint is a quad
+    if (rot)
+        for (int q = t.live * J + tid; q < t.cnt * J; q += THREADS) *reinterpret_cast<f4*>(rot + 4ll * q) = f4{0.f, 0.f, 0.f, 0.f};
+    if (t.live == 0) return;
+    const int nlev = min(max(a.table[0], 1), J);
+    for (int l = tid; l <= nlev; l += THREADS) lv[l] = min(max(a.table[AL_FIRST + l], 0), J);
+    for (int j = tid; j < J; j += THREADS) {
+        ord[j] = min(max(a.table[AL_ORDER + j], 0), J - 1);
+        par[j] = min(max(a.table[al_parents(J) + j], -1), J - 1);
+    }
+    for (int r = tid; r < J3; r += THREADS) off[r] = __int_as_float(a.table[al_offsets(J) + r]);
+    const bool has_mean = a.mean != nullptr;
+    load_mean(a, mn);
+    // stage_pass' barrier also covers the tables, and the last level of the pass before
+    const Walk<NATIVE, SLA> w = {t.k0, t.n, a.L, a.M};
+    Pass ps;
+    for (int i = 0; i < t.live; i = ps.i1) {
+        const float* x = stage_pass(a, t, w, i, xin, ps);
+        const int nf = ps.i1 - i;
+        // Phase 1, every (output frame, joint) at once: R_j by Gram-Schmidt into the joint's own plane of the state tile; the local rotations leave here.
+        for (int q = tid; q < nf * J; q += THREADS) {
+            const int j = q / nf, fr = i + (q - j * nf);
+            float d[6];
+            if (NATIVE || t.n < 2) {
+                const float* xs = x + (NATIVE ? fr - i : 0) * D + 6 * j;
+#pragma unroll
+                for (int e = 0; e < 6; ++e) d[e] = has_mean ? xs[e] + mn[6 * j + e] : xs[e];
+            } else {                                                            // the 6-D vectors are blended, after the mean
+                const Blend bl = w.blend(ps, fr);
+                const float* xs = x + bl.slot * D + 6 * j;
+#pragma unroll
+                for (int e = 0; e < 6; ++e) {
+                    float y = xs[e], z = xs[D + e];
+                    if (has_mean) { y += mn[6 * j + e]; z += mn[6 * j + e]; }
+                    d[e] = fmaf(z - y, bl.f, y);
+                }
+            }
+            const float n1 = fmaxf(sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]), 1e-12f);
+            const float b10 = d[0] / n1, b11 = d[1] / n1, b12 = d[2] / n1;
+            const float dot = b10 * d[3] + b11 * d[4] + b12 * d[5];
+            const float u0 = d[3] - dot * b10, u1 = d[4] - dot * b11, u2 = d[5] - dot * b12;
+            const float n2 = fmaxf(sqrtf(u0 * u0 + u1 * u1 + u2 * u2), 1e-12f);
+            const float b20 = u0 / n2, b21 = u1 / n2, b22 = u2 / n2;
+            const float b30 = b11 * b22 - b12 * b21, b31 = b12 * b20 - b10 * b22, b32 = b10 * b21 - b11 * b20;
+            float R[9];
+            if (k.columns) { R[0] = b10; R[1] = b20; R[2] = b30; R[3] = b11; R[4] = b21; R[5] = b31; R[6] = b12; R[7] = b22; R[8] = b32; }
+            else { R[0] = b10; R[1] = b11; R[2] = b12; R[3] = b20; R[4] = b21; R[5] = b22; R[6] = b30; R[7] = b31; R[8] = b32; }
+            float* sj = st + j * AST + fr;
+#pragma unroll
+            for (int e = 0; e < 9; ++e) sj[e * TFA] = R[e];
+            if (!GLOBAL && rot) *reinterpret_cast<f4*>(rot + ((long long)fr * J + j) * 4) = quat_of(R);
+        }
+        __syncthreads();                                                        // xin is free from here on; the chain reads R from the tile
+        // Phase 2, the chain, only where something needs it: G_j replaces R_j in the joint's plane (its owner reads R_j and writes G_j; nobody
+        // else touches the plane before the barrier), the position goes beside it.  The dependent path is 36 multiply-adds per level.
+        const int walk = (a.dst || (GLOBAL && rot)) ? nlev : 0;
+        for (int l = 0; l < walk; ++l) {
+            const int b0 = lv[l], nb = max(lv[l + 1] - b0, 0);
+            for (int q = tid; q < nf * nb; q += THREADS) {                       // one thread per (output frame, joint of the level)
+                const int jl = q / nf, fr = i + (q - jl * nf);
+                const int j = ord[min(b0 + jl, J - 1)], p = par[j];
+                float* sj = st + j * AST + fr;
+                float R[9], G[9], pos[3];
+#pragma unroll
+                for (int e = 0; e < 9; ++e) R[e] = sj[e * TFA];
+                const float o0 = off[3 * j], o1 = off[3 * j + 1], o2 = off[3 * j + 2];
+                if (p >= 0) {
+                    const float* sp = st + p * AST + fr;
+                    float P[9];
+#pragma unroll
+                    for (int e = 0; e < 9; ++e) P[e] = sp[e * TFA];
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) G[3 * r + c] = P[3 * r] * R[c] + P[3 * r + 1] * R[3 + c] + P[3 * r + 2] * R[6 + c];
+                        pos[r] = sp[(9 + r) * TFA] + (P[3 * r] * o0 + P[3 * r + 1] * o1 + P[3 * r + 2] * o2);
+                    }
+#pragma unroll
+                    for (int e = 0; e < 9; ++e) sj[e * TFA] = G[e];
+                } else {                                                        // the root: G = R is in place already
+#pragma unroll
+                    for (int e = 0; e < 9; ++e) G[e] = R[e];
+                    pos[0] = o0; pos[1] = o1; pos[2] = o2;
+                }
+#pragma unroll
+                for (int e = 0; e < 3; ++e) sj[(9 + e) * TFA] = pos[e];
+                if (GLOBAL && rot) *reinterpret_cast<f4*>(rot + ((long long)fr * J + j) * 4) = quat_of(G);
+            }
+            __syncthreads();                                                    // a level reads what the level before wrote
+        }
+        if (a.dst)                                                              // the positions of the pass, from the state tile
+            store_range(a.dst, f0 * J3, J3, (f0 + i) * J3, (f0 + ps.i1) * J3, [&](int fr, int r) {
+                const int jt = r / 3;
+                return st[jt * AST + (9 + r - 3 * jt) * TFA + fr];
+            });
+    }
+}
+
+// quat [B, T, J, 4] -> rot6d [B, T, 6J]: one 16-byte load per (frame, joint), six floats into an LDS tile, coalesced stores from there.
+__global__ __launch_bounds__(THREADS) void articulate_rot6d_kernel(const ArtArgs k) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const Args& a = k.a;
+    const int J = k.J, D = 6 * J, tid = threadIdx.x;
+    float* mn = lds;
+    float* buf = lds + 6 * MAX_J;
+    const Tile t = tile_of<true, TFI>(a, a.T);
+    const long long f0 = (long long)t.b * a.T + t.k0;
+    zero_tail(a.dst, f0 * D, D, t);
+    if (t.live == 0) return;
+    const bool has_mean = a.mean != nullptr;
+    load_mean(a, mn);
+    for (int q = tid; q < t.live * J; q += THREADS) {
+        const f4 v = *reinterpret_cast<const f4*>(a.src + (f0 * J + q) * 4);
+        const float d = fmaxf(sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]), 1e-12f);
+        const float w = v[0] / d, x = v[1] / d, y = v[2] / d, z = v[3] / d;
+        const float m00 = 1.f - 2.f * (y * y + z * z), m01 = 2.f * (x * y - w * z), m02 = 2.f * (x * z + w * y);
+        const float m10 = 2.f * (x * y + w * z), m11 = 1.f - 2.f * (x * x + z * z), m12 = 2.f * (y * z - w * x);
+        float* o = buf + 6 * q;                                                 // q = frame * J + joint: the tile's rows are contiguous
+        if (k.columns) { o[0] = m00; o[1] = m10; o[2] = 2.f * (x * z - w * y); o[3] = m01; o[4] = m11; o[5] = 2.f * (y * z + w * x); }
+        else { o[0] = m00; o[1] = m01; o[2] = m02; o[3] = m10; o[4] = m11; o[5] = m12; }
+    }
+    __syncthreads();
+    store_range(a.dst, f0 * D, D, f0 * D, (f0 + t.live) * D, [&](int fr, int r) {
+        const float v = buf[fr * D + r];
+        return has_mean ? v - mn[r] : v;
+    });
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
 int check_table(const char* who, const int32_t* parents, const int32_t* children, const float* lengths, int K) {
     EG_REQUIRE(parents && children && lengths, EG_ERR_BAD_ARG, "%s: null parents / children / lengths", who);
@@ -418,24 +604,27 @@ int common_checks(const char* who, const void* src, const void* dst, int B, int 
 
 // What eg_skeleton_joints and eg_skeleton_rotations check behind their own arguments, in the header's order -- the rate, out_stride, the grid
 // and the index range of an output of `per_frame` floats per frame -- and the rest of the kernel's arguments: a.L, a.M, a.tiles, a.T_out.
-int forward_args(const char* who, Args& a, int L, int M, long long out_stride, int per_frame) {
+// `tile`: the output frames of one workgroup.
+int forward_args(const char* who, Args& a, int L, int M, long long out_stride, int per_frame, int tile = TF) {
     int rc = reduce_rate(who, L, M);
     if (rc != EG_OK) return rc;
     const long long t_out = out_frames(a.T, L, M);
     EG_REQUIRE(out_stride >= t_out, EG_ERR_BAD_ARG, "%s: out_stride=%lld < %lld output frames of %d input frames at L=%d / M=%d", who, out_stride,
                t_out, a.T, L, M);
-    const long long tiles = (out_stride + TF - 1) / TF;
+    const long long tiles = (out_stride + tile - 1) / tile;
     EG_REQUIRE(tiles * a.B <= 0x7fffffffll && (long long)a.B * out_stride * per_frame < (1ll << 40), EG_ERR_UNSUPPORTED,
                "%s: rows=%d x out_stride=%lld: grid / index range", who, a.B, out_stride);
     a.L = L; a.M = M; a.tiles = (int)tiles; a.T_out = out_stride;
     return EG_OK;
 }
 
-// One workgroup per tile of every row.
-int launch(void (*kernel)(Args), const Args& a, size_t lds_floats, void* stream, const char* what) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((long long)a.tiles * a.B)), dim3(THREADS), lds_floats * sizeof(float), static_cast<hipStream_t>(stream), a);
+// One workgroup per tile of every row.  `a` holds the grid; `k`: what the kernel takes (Args itself, or a block that begins with it).
+template <class A>
+int launch(void (*kernel)(A), const Args& a, const A& k, size_t lds_floats, void* stream, const char* what) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((long long)a.tiles * a.B)), dim3(THREADS), lds_floats * sizeof(float), static_cast<hipStream_t>(stream), k);
     return eg_check_launch(what);
 }
+int launch(void (*kernel)(Args), const Args& a, size_t lds_floats, void* stream, const char* what) { return launch(kernel, a, a, lds_floats, stream, what); }
 
 int check_rest(const char* who, const double* rest, int K) {
     EG_REQUIRE(rest, EG_ERR_BAD_ARG, "%s: null rest", who);
@@ -554,4 +743,108 @@ extern "C" int eg_skeleton_rotations(const float* track, int32_t rows, int32_t T
     return launch(space == EG_SKELETON_SPACE_GLOBAL ? (native ? skeleton_rotations_kernel<true, true> : skeleton_rotations_kernel<false, true>)
                                                     : (native ? skeleton_rotations_kernel<true, false> : skeleton_rotations_kernel<false, false>),
                   a, RHEAD + round4(SLOTS * 3 * bones + 8) + bones * 4 * TF, stream, "skeleton_rotations");
+}
+
+// ---- articulated bodies: host ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+int check_body(const char* who, const int32_t* parents, const float* offsets, int J) {
+    EG_REQUIRE(parents && offsets, EG_ERR_BAD_ARG, "%s: null parents / offsets", who);
+    EG_REQUIRE(J >= 1 && J <= MAX_J, EG_ERR_UNSUPPORTED, "%s: joints=%d (1..%d)", who, J, MAX_J);
+    EG_REQUIRE(parents[0] == -1, EG_ERR_BAD_ARG, "%s: joint 0: parent=%d (joint 0 is the root, its parent is -1)", who, parents[0]);
+    for (int j = 0; j < J; ++j) {
+        EG_REQUIRE(j == 0 || (parents[j] >= 0 && parents[j] < j), EG_ERR_BAD_ARG,
+                   "%s: joint %d: parent=%d is not an earlier joint (the table must be in topological order)", who, j, parents[j]);
+        const float* o = offsets + 3 * j;
+        EG_REQUIRE(isfinite(o[0]) && isfinite(o[1]) && isfinite(o[2]), EG_ERR_BAD_ARG, "%s: joint %d: offset (%g, %g, %g) is not finite", who, j,
+                   (double)o[0], (double)o[1], (double)o[2]);
+    }
+    return EG_OK;
+}
+
+// What both calls check about their rows: the counterpart of common_checks without a bone table.
+int rows_checks(const char* who, const void* src, int B, int T, int draws, int frame_unit, const void* d_mean, int basis) {
+    EG_REQUIRE(src, EG_ERR_BAD_ARG, "%s: null input", who);
+    EG_REQUIRE(eg_aligned16(src), EG_ERR_ALIGN, "%s: input not 16-byte aligned", who);
+    EG_REQUIRE((reinterpret_cast<uintptr_t>(d_mean) & 3u) == 0, EG_ERR_ALIGN, "%s: d_mean not 4-byte aligned", who);
+    EG_REQUIRE(B >= 1 && T >= 1, EG_ERR_BAD_ARG, "%s: rows=%d frames=%d (need >= 1)", who, B, T);
+    EG_REQUIRE(draws >= 1 && B % draws == 0, EG_ERR_BAD_ARG, "%s: rows=%d is not a multiple of draws=%d", who, B, draws);
+    EG_REQUIRE(frame_unit >= 1, EG_ERR_BAD_ARG, "%s: frame_unit=%d (need >= 1)", who, frame_unit);
+    EG_REQUIRE(basis == EG_ARTICULATE_BASIS_ROWS || basis == EG_ARTICULATE_BASIS_COLUMNS, EG_ERR_BAD_ARG, "%s: basis=%d (0: rows, 1: columns)", who,
+               basis);
+    return EG_OK;
+}
+
+}  // namespace
+
+extern "C" int eg_articulate_check(const int32_t* parents, const float* offsets, int32_t joints) {
+    return check_body("eg_articulate_check", parents, offsets, joints);
+}
+
+extern "C" int32_t eg_articulate_tile_frames(void) { return TFA; }
+
+extern "C" int eg_articulate_levels(const int32_t* parents, const float* offsets, int32_t joints, int32_t* words) {
+    const char* who = "eg_articulate_levels";
+    int rc = check_body(who, parents, offsets, joints);
+    if (rc != EG_OK) return rc;
+    EG_REQUIRE(words, EG_ERR_BAD_ARG, "%s: null words", who);
+    const int J = joints;
+    int depth[MAX_J], count[ALEVELS] = {}, at[ALEVELS];
+    int nlev = 0;
+    for (int j = 0; j < J; ++j) {                       // topological order: the parent came earlier
+        depth[j] = j == 0 ? 0 : depth[parents[j]] + 1;
+        ++count[depth[j]];
+        nlev = depth[j] + 1 > nlev ? depth[j] + 1 : nlev;
+    }
+    words[0] = nlev;
+    for (int l = 0, s = 0; l < ALEVELS; ++l) {
+        words[AL_FIRST + l] = s;
+        at[l] = s;
+        if (l < nlev) s += count[l];
+    }
+    for (int j = 0; j < J; ++j) words[AL_ORDER + at[depth[j]]++] = j;                  // by depth, table order inside a level
+    for (int j = 0; j < J; ++j) words[al_parents(J) + j] = parents[j];
+    for (int r = 0; r < 3 * J; ++r) words[al_offsets(J) + r] = *reinterpret_cast<const int32_t*>(offsets + r);
+    return EG_OK;
+}
+
+extern "C" int eg_articulate_forward(const float* track, int32_t rows, int32_t T, const int32_t* parents, const float* offsets, int32_t joints,
+                                     const void* d_table, const int32_t* d_frames, int32_t draws, int32_t frame_unit, const float* d_mean,
+                                     int32_t basis, int32_t space, int32_t L, int32_t M, float* out_joints, float* out_rotations, int64_t out_stride,
+                                     void* stream) {
+    const char* who = "eg_articulate_forward";
+    EG_REQUIRE(out_joints || out_rotations, EG_ERR_BAD_ARG, "%s: null out_joints and out_rotations (need one of them)", who);
+    EG_REQUIRE(d_table, EG_ERR_BAD_ARG, "%s: null d_table", who);
+    int rc = check_body(who, parents, offsets, joints);
+    if (rc != EG_OK) return rc;
+    rc = rows_checks(who, track, rows, T, draws, frame_unit, d_mean, basis);
+    if (rc != EG_OK) return rc;
+    EG_REQUIRE(eg_aligned16(out_joints) && eg_aligned16(out_rotations), EG_ERR_ALIGN, "%s: out_joints / out_rotations not 16-byte aligned", who);
+    EG_REQUIRE((reinterpret_cast<uintptr_t>(d_table) & 3u) == 0, EG_ERR_ALIGN, "%s: d_table not 4-byte aligned", who);
+    EG_REQUIRE(space == EG_SKELETON_SPACE_LOCAL || space == EG_SKELETON_SPACE_GLOBAL, EG_ERR_BAD_ARG, "%s: space=%d (0: local, 1: global)", who, space);
+    EG_REQUIRE((long long)rows * T * 6 * joints < (1ll << 40), EG_ERR_UNSUPPORTED, "%s: rows=%d x frames=%d: index range", who, rows, T);
+    ArtArgs k = {{track, static_cast<const int*>(d_table), d_frames, d_mean, out_joints, rows, T, 2 * joints, draws, frame_unit}, out_rotations, joints,
+                 basis == EG_ARTICULATE_BASIS_COLUMNS};
+    rc = forward_args(who, k.a, L, M, out_stride, 4 * joints, TFA);
+    if (rc != EG_OK) return rc;
+    const bool native = k.a.L == 1 && k.a.M == 1;
+    return launch(space == EG_SKELETON_SPACE_GLOBAL ? (native ? articulate_kernel<true, true> : articulate_kernel<false, true>)
+                                                    : (native ? articulate_kernel<true, false> : articulate_kernel<false, false>),
+                  k.a, k, AHEAD + round4(SLA * 6 * joints + 8) + joints * AST, stream, "articulate_forward");
+}
+
+extern "C" int eg_articulate_rot6d(const float* quat, int32_t rows, int32_t T, int32_t joints, const int32_t* d_frames, int32_t draws,
+                                   int32_t frame_unit, const float* d_mean, int32_t basis, float* rot6d, void* stream) {
+    const char* who = "eg_articulate_rot6d";
+    EG_REQUIRE(rot6d, EG_ERR_BAD_ARG, "%s: null output", who);
+    EG_REQUIRE(joints >= 1 && joints <= MAX_J, EG_ERR_UNSUPPORTED, "%s: joints=%d (1..%d)", who, joints, MAX_J);
+    int rc = rows_checks(who, quat, rows, T, draws, frame_unit, d_mean, basis);
+    if (rc != EG_OK) return rc;
+    EG_REQUIRE(eg_aligned16(rot6d), EG_ERR_ALIGN, "%s: output not 16-byte aligned", who);
+    const long long tiles = ((long long)T + TFI - 1) / TFI;
+    EG_REQUIRE(tiles * rows <= 0x7fffffffll && (long long)rows * T * 6 * joints < (1ll << 40), EG_ERR_UNSUPPORTED,
+               "%s: rows=%d x frames=%d: grid / index range", who, rows, T);
+    const ArtArgs k = {{quat, nullptr, d_frames, d_mean, rot6d, rows, T, 2 * joints, draws, frame_unit, 1, 1, (int)tiles, T}, nullptr, joints,
+                       basis == EG_ARTICULATE_BASIS_COLUMNS};
+    return launch(articulate_rot6d_kernel, k.a, k, 6 * MAX_J + TFI * 6 * joints, stream, "articulate_rot6d");
 }

@@ -513,6 +513,13 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     ``skeleton.rotations_from_tracks(out["track"], skeleton, rest, frames, joints_mean, joints_fps, rotations_space)``, one more launch, on the
     frames ``"joint_frames"`` counts.
 
+    ``joints=tree`` (a ``skeleton.JointTree`` with ``6J == pose_dim``: the BEAT generators, whose columns are 6-D joint rotations):
+    ``"joints"`` ``[U, (R,) T', J, 3]`` and ``"joint_frames"`` as above, and with ``rotations=True`` ``"rotations"`` ``[U, (R,) T', J, 4]`` in
+    ``rotations_space`` -- ``skeleton.joints_from_rot6d`` / ``rotations_from_rot6d`` of the track, both from ONE launch
+    (``skeleton.launch_articulate``).  ``joints_mean [6J]`` and ``joints_fps`` as above; ``joints_unit`` and a rest pose are refused by name
+    (the tree's offsets are the bind pose).  With ``smooth=`` the filtered 6-D rows are re-orthonormalised by Gram-Schmidt on the way to the
+    matrices: this is the sanctioned way to smooth rotations (there is no filter over quaternions).
+
     ``smooth=Smoother | (window, polyorder)`` (``smooth.Smoother``; a pair is a filter at ``fps``): adds ``"track_smooth"``, the shape of
     ``"track"``: ``smooth.smooth_tracks(out["track"], smooth, frames)``, a Savitzky-Golay filter (``scipy.signal.savgol_filter``,
     ``mode="interp"``) over recording u's own valid poses, zeros behind them, one launch.  ``"track"`` stays raw and ``beat`` / ``diversity`` keep
@@ -553,7 +560,8 @@ def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samp
     gen, vae = models
     from . import skeleton as SK
     rotations = SK.output_args(who, seed_pose.shape[-1], joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space,
-                               hint=" (the BEAT generators' 282 columns hold rotations, not bone direction vectors)")
+                               hint=" (the BEAT generators' 282 columns hold rotations, not bone direction vectors): their body is a "
+                                    "skeleton.JointTree of 47 joints")
     if smooth is not None:
         from . import smooth as SM
         smooth = SM.Smoother.of(smooth, f"{who}: smooth", fps)
@@ -627,9 +635,27 @@ def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samp
     if joints is not None:
         kw = dict(frames=frames, mean=joints_mean, fps=joints_fps)
         with torch.no_grad():
-            out["joints"], out["joint_frames"] = SK.joints_from_tracks(poses, joints, unit=joints_unit, **kw)
-            if rotations is not None:
-                out["rotations"], _n = SK.rotations_from_tracks(poses, joints, rotations, space=rotations_space, **kw)
+            if isinstance(joints, SK.JointTree):                                           # 6-D rotations: both outputs from one launch
+                out.update(_articulated(poses, joints, rotations is not None, rotations_space, **kw))
+            else:
+                out["joints"], out["joint_frames"] = SK.joints_from_tracks(poses, joints, unit=joints_unit, **kw)
+                if rotations is not None:
+                    out["rotations"], _n = SK.rotations_from_tracks(poses, joints, rotations, space=rotations_space, **kw)
+    return out
+
+
+def _articulated(poses: torch.Tensor, tree, want_rotations: bool, space: str, frames, mean, fps) -> Dict[str, torch.Tensor]:
+    """``joints`` / ``joint_frames`` (/ ``rotations``) of ``poses [U, (R,) T, 6J]`` on a ``skeleton.JointTree``: what
+    ``skeleton.joints_from_rot6d`` and ``rotations_from_rot6d`` return, from one ``launch_articulate``."""
+    from . import skeleton as SK
+    who = "synthesize: joints"
+    fe = SK._front(poses, tree, frames, fps, who)
+    x = SK._dev32(poses).reshape(fe.U * fe.R, fe.T, tree.pose_dim)
+    j, q = SK.launch_articulate(x, tree, SK._frames_dev(fe.fr, x.device), fe.R, 1, SK._mean_dev(mean, tree.pose_dim, x.device, who), space,
+                                fe.ratio, rotations=want_rotations)
+    out = {"joints": j.reshape(fe.lead + (fe.t_out, tree.J, 3)), "joint_frames": fe.n_out}
+    if want_rotations:
+        out["rotations"] = q.reshape(fe.lead + (fe.t_out, tree.J, 4))
     return out
 
 

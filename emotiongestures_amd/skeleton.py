@@ -25,6 +25,24 @@ child is ``parents[k]`` (-1 at the root); ``x^_k = x_k / max(|x_k|, 1e-12)``; in
 ``c = a . b``, or for ``c < -1 + 1e-6`` the half turn about ``a x e_m`` (``e_m`` the first axis on which ``|a|`` is smallest).  On an interpolated
 frame the vectors are blended (after the mean), then the chain runs on the blended frame.
 
+Articulated bodies (include/emogest.h: eg_articulate_forward / eg_articulate_rot6d).  The BEAT generators' tracks hold one 6-D rotation per
+joint, ``pose_dim = 6J``; their body is ``JointTree(parents, offsets, basis="rows", names=None)``: ``1 <= J <= 64`` joints in topological order
+(``parents[0] == -1``, ``0 <= parents[j] < j``), ``offsets [J, 3]`` in metres the joint's position in its parent's frame at the bind pose
+(finite; zero allowed); ``basis`` states how the data set wrote the six numbers and belongs to the tree.
+``JointTree.from_bvh(text, joints=None, unit=0.01)`` reads the ``HIERARCHY`` block of a BVH file.  For a source frame
+``d_j = track[t, 6j:6j+6] (+ mean_j)``, ``a1 = d_j[0:3]``, ``a2 = d_j[3:6]``; ``b1 = a1 / max(|a1|, 1e-12)``, ``u2 = a2 - (b1 . a2) b1``,
+``b2 = u2 / max(|u2|, 1e-12)``, ``b3 = b1 x b2``; ``R_j`` has the rows ``b1, b2, b3`` (``basis="rows"``: pytorch3d's ``rotation_6d_to_matrix``)
+or has them as columns (``"columns"``: Zhou et al. 2019).  A degenerate group (zero, or ``a1`` parallel to ``a2``) gives a finite matrix that is
+not a rotation; every output stays finite.  Chain, in table order: ``G_0 = R_0``, ``p_0 = offsets[0]``, ``G_j = G_parent R_j``,
+``p_j = p_parent + G_parent offsets[j]``.  ``joints_from_rot6d`` returns ``p [..., T_out, J, 3]``; ``rotations_from_rot6d`` the unit quaternion
+``(w, x, y, z)`` of ``R_j`` (``space="local"``) or ``G_j`` (``"global"``) ``[..., T_out, J, 4]``: from the matrix by the branch of the largest
+of (trace, m00, m11, m22), normalised, ``w >= 0``.  ``fps=(src, dst)``: the same ``L / M``, ``lo`` and ``f`` as above; the 6-D vectors of the
+source frames ``lo`` and ``lo + 1`` are blended, after the mean, and the whole chain runs on the blended frame, so the joints and rotations of
+one call describe the same pose (n = 1: every frame is frame 0).  Source frames from ``frames[u]`` on are never read; output frames from
+``n_out`` on are zeros.  ``rot6d_from_rotations(quat [..., T, J, 4], tree)`` is the inverse: the quaternion normalised
+(``/ max(|q|, 1e-12)``), the first two rows (or columns) of its matrix as ``a1 | a2``, minus the mean; zeros from ``frames[u]`` on: the
+``seed_pose`` a BEAT generator takes from motion capture.
+
 CUDA tensors go through the kernels (fp32; there is no eager-PyTorch fallback for them).  numpy arrays and CPU tensors take the definition in
 float64 numpy -- what the reference's functions compute -- so data preparation and the drop-ins of ``utils.data_utils_expressive`` run without
 a GPU.
@@ -42,7 +60,8 @@ from . import _lib as L
 from ._host import BoundedCache, host_ptr, int_list, ptr as _ptr, stream as _stream
 
 __all__ = ["Skeleton", "RestPose", "ted_expressive", "joints_from_tracks", "dir_vec_from_joints", "rotations_from_tracks", "out_frames",
-           "rate_ratio", "TILE_FRAMES", "MAX_BONES", "MAX_FACTOR"]
+           "rate_ratio", "TILE_FRAMES", "MAX_BONES", "MAX_FACTOR", "JointTree", "joints_from_rot6d", "rotations_from_rot6d",
+           "rot6d_from_rotations", "ARTICULATE_TILE_FRAMES", "MAX_JOINTS"]
 
 TILE_FRAMES = L.EG_SKELETON_TILE_FRAMES      # output frames of one workgroup
 MAX_BONES = L.EG_SKELETON_MAX_BONES
@@ -246,18 +265,18 @@ def _dev32(x: torch.Tensor) -> torch.Tensor:
     return x.clone() if x.data_ptr() % 16 else x                # a slice of a larger tensor may start anywhere
 
 
-def _mean_checked(m, K: int, who: str):                        # m: the flat mean, a tensor or an array
-    if len(m) != 3 * K:
-        raise L.EgError(f"{who}: mean has {len(m)} values, the skeleton's tracks have {3 * K}")
+def _mean_checked(m, D: int, who: str):                        # m: the flat mean, a tensor or an array; D: the body's pose_dim
+    if len(m) != D:
+        raise L.EgError(f"{who}: mean has {len(m)} values, the skeleton's tracks have {D}")
     return m
 
 
-def _mean_dev(mean, K: int, device, who: str) -> Optional[torch.Tensor]:
-    return None if mean is None else _mean_checked(torch.as_tensor(mean).detach().to(device=device, dtype=torch.float32).reshape(-1).contiguous(), K, who)
+def _mean_dev(mean, D: int, device, who: str) -> Optional[torch.Tensor]:
+    return None if mean is None else _mean_checked(torch.as_tensor(mean).detach().to(device=device, dtype=torch.float32).reshape(-1).contiguous(), D, who)
 
 
-def _mean_host(mean, K: int, who: str) -> Optional[np.ndarray]:
-    return None if mean is None else _mean_checked(_host64(mean, who).reshape(-1), K, who)
+def _mean_host(mean, D: int, who: str) -> Optional[np.ndarray]:
+    return None if mean is None else _mean_checked(_host64(mean, who).reshape(-1), D, who)
 
 
 # ---- the float64 path: the definition ------------------------------------------------------------------------------------------------------
@@ -483,10 +502,10 @@ def joints_from_tracks(track, skeleton: Skeleton, frames=None, mean=None, unit: 
     fe = _front(track, sk, frames, fps, who)
     if _is_cuda(track):
         x = _dev32(track).reshape(fe.U * fe.R, fe.T, sk.pose_dim)
-        j = launch_joints(x, sk, _frames_dev(fe.fr, x.device), fe.R, 1, _mean_dev(mean, sk.K, x.device, who), unit, fe.ratio)
+        j = launch_joints(x, sk, _frames_dev(fe.fr, x.device), fe.R, 1, _mean_dev(mean, sk.pose_dim, x.device, who), unit, fe.ratio)
     else:
         v = _host64(track, who).reshape(fe.U * fe.R, fe.T, sk.pose_dim)
-        j = _joints64(v, sk, fe.per_row, _mean_host(mean, sk.K, who), bool(unit), *fe.ratio)
+        j = _joints64(v, sk, fe.per_row, _mean_host(mean, sk.pose_dim, who), bool(unit), *fe.ratio)
     return _finish(j, track, fe, (sk.J, 3), frames, fps)
 
 
@@ -507,9 +526,9 @@ def dir_vec_from_joints(joints, skeleton: Skeleton, frames=None, mean=None):
     fr = _frames_list(frames, U, T, who)
     if _is_cuda(joints):
         p = _dev32(joints).reshape(U * R, T, sk.J, 3)
-        return launch_dir_vec(p, sk, _frames_dev(fr, p.device), R, 1, _mean_dev(mean, sk.K, p.device, who)).reshape(lead + (T, sk.pose_dim))
+        return launch_dir_vec(p, sk, _frames_dev(fr, p.device), R, 1, _mean_dev(mean, sk.pose_dim, p.device, who)).reshape(lead + (T, sk.pose_dim))
     p = _host64(joints, who).reshape(U * R, T, sk.J, 3)
-    d = _dir_vec64(p, sk, _per_row(fr, U, R, T), _mean_host(mean, sk.K, who)).reshape(lead + (T, sk.pose_dim))
+    d = _dir_vec64(p, sk, _per_row(fr, U, R, T), _mean_host(mean, sk.pose_dim, who)).reshape(lead + (T, sk.pose_dim))
     return torch.from_numpy(d) if isinstance(joints, torch.Tensor) else d
 
 
@@ -531,11 +550,338 @@ def rotations_from_tracks(track, skeleton: Skeleton, rest, frames=None, mean=Non
     fe = _front(track, sk, frames, fps, who)
     if _is_cuda(track):
         x = _dev32(track).reshape(fe.U * fe.R, fe.T, sk.pose_dim)
-        q = launch_rotations(x, sk, pose, _frames_dev(fe.fr, x.device), fe.R, 1, _mean_dev(mean, sk.K, x.device, who), space, fe.ratio)
+        q = launch_rotations(x, sk, pose, _frames_dev(fe.fr, x.device), fe.R, 1, _mean_dev(mean, sk.pose_dim, x.device, who), space, fe.ratio)
     else:
         v = _host64(track, who).reshape(fe.U * fe.R, fe.T, sk.pose_dim)
-        q = _rotations64(v, sk, pose.unit32.astype(np.float64), fe.per_row, _mean_host(mean, sk.K, who), sp == L.EG_SKELETON_SPACE_GLOBAL, *fe.ratio)
+        q = _rotations64(v, sk, pose.unit32.astype(np.float64), fe.per_row, _mean_host(mean, sk.pose_dim, who), sp == L.EG_SKELETON_SPACE_GLOBAL, *fe.ratio)
     return _finish(q, track, fe, (sk.K, 4), frames, fps)
+
+
+# ---- articulated bodies: 6-D joint rotations (the BEAT generators) -----------------------------------------------------------------------------
+ARTICULATE_TILE_FRAMES = L.EG_ARTICULATE_TILE_FRAMES
+MAX_JOINTS = L.EG_ARTICULATE_MAX_JOINTS
+_BASES = {"rows": L.EG_ARTICULATE_BASIS_ROWS, "columns": L.EG_ARTICULATE_BASIS_COLUMNS}
+
+
+def articulate_level_words(J: int) -> int:
+    """EG_ARTICULATE_LEVEL_WORDS(J): the level count | 65 level offsets | order [J] | parents [J] | offsets [J, 3]."""
+    return 1 + 65 + 5 * J
+
+
+class JointTree:
+    """A body for tracks of 6-D joint rotations: J joints in topological order (``parents[0] == -1``, ``0 <= parents[j] < j``),
+    ``offsets [J, 3]`` in metres -- the joint's position in its parent's frame at the bind pose -- and ``basis``: how the data set wrote the six
+    numbers of a joint, ``"rows"`` (the first two rows of the matrix: pytorch3d's ``rotation_6d_to_matrix``) or ``"columns"`` (Zhou et al.
+    2019).  ``pose_dim = 6J``.  eg_articulate_check refuses a bad table by name.  The level table (the joints by depth, the parents and the
+    fp32 offsets: what the kernel reads) is built once and uploaded once per device."""
+
+    def __init__(self, parents: Sequence[int], offsets, basis: str = "rows", names: Optional[Sequence[str]] = None):
+        if basis not in _BASES:
+            raise L.EgError(f"JointTree: basis={basis!r}: 'rows' (pytorch3d's rotation_6d_to_matrix) or 'columns' (Zhou et al. 2019)")
+        self.parents = np.ascontiguousarray(parents, np.int32).reshape(-1)
+        if isinstance(offsets, torch.Tensor):
+            offsets = offsets.detach().cpu().numpy()
+        self.offsets = np.ascontiguousarray(offsets, np.float64)          # as given: the float64 path's offsets
+        self.J = int(len(self.parents))
+        if self.offsets.shape != (self.J, 3):
+            raise L.EgError(f"JointTree: offsets shape {self.offsets.shape}: {self.J} parents take one offset per joint, [{self.J}, 3]")
+        self.offsets32 = self.offsets.astype(np.float32)                  # the device's
+        self.basis = basis
+        self.names = None if names is None else [str(n) for n in names]
+        if self.names is not None and (len(self.names) != self.J or len(set(self.names)) != self.J):
+            raise L.EgError(f"JointTree: names: need {self.J} distinct names, got {len(self.names)} ({len(set(self.names))} distinct)")
+        L.check(L.load().eg_articulate_check(*self.host_ptrs(), self.J), "eg_articulate_check")
+        self.words = np.zeros(articulate_level_words(self.J), np.int32)
+        L.check(L.load().eg_articulate_levels(*self.host_ptrs(), self.J, host_ptr(self.words)), "eg_articulate_levels")
+        self._tables = BoundedCache()
+
+    def host_ptrs(self):
+        return host_ptr(self.parents), host_ptr(self.offsets32)
+
+    @property
+    def pose_dim(self) -> int:
+        return 6 * self.J
+
+    @property
+    def basis_code(self) -> int:
+        return _BASES[self.basis]
+
+    @property
+    def depth(self) -> np.ndarray:
+        """Joints between the root and every joint, ``[J]`` (0 at the root)."""
+        d = np.zeros(self.J, np.int64)
+        for j in range(1, self.J):
+            d[j] = d[self.parents[j]] + 1
+        return d
+
+    @property
+    def levels(self) -> int:
+        return int(self.words[0])
+
+    def table(self, device) -> torch.Tensor:
+        """int32 ``[articulate_level_words(J)]`` on ``device``: eg_articulate_levels' table."""
+        return self._tables.get(str(device), lambda: torch.from_numpy(self.words).to(device))
+
+    @classmethod
+    def from_bvh(cls, text: str, joints: Optional[Sequence[str]] = None, unit: float = 0.01, basis: str = "rows") -> "JointTree":
+        """The body of a BVH file's ``HIERARCHY`` block (``ROOT`` / ``JOINT`` / ``End Site`` / ``OFFSET``; ``CHANNELS`` and everything from
+        ``MOTION`` on are ignored).  ``joints``: the names to keep, returned in file order (None: every joint, no end sites).  A kept joint's
+        parent is its nearest kept ancestor and its offset the sum of the offsets along the skipped joints between them -- exact while the
+        skipped joints stay at the identity rotation, which is what a data set that does not animate them means.  The first kept joint is
+        the root and keeps its own offset only.  Offsets are scaled by ``unit`` (0.01: a file in centimetres).  Refuses by name: an unknown
+        joint name, a duplicate, and a kept joint that does not descend from the first kept joint."""
+        nodes: List[Tuple[str, int, List[float]]] = []                    # (name, parent node or -1, offset); end sites have the name None
+        stack: List[int] = []
+        pending: Optional[int] = None
+        tokens = text.split()
+        i = 0
+        while i < len(tokens):
+            tok = tokens[i]
+            if tok == "MOTION":
+                break
+            if tok in ("ROOT", "JOINT") or (tok == "End" and i + 1 < len(tokens) and tokens[i + 1] == "Site"):
+                if i + 1 >= len(tokens):
+                    raise L.EgError(f"JointTree.from_bvh: {tok} without a name at the end of the text")
+                nodes.append((None if tok == "End" else tokens[i + 1], stack[-1] if stack else -1, [0.0, 0.0, 0.0]))
+                pending = len(nodes) - 1
+                i += 2
+                continue
+            if tok == "{":
+                if pending is None:
+                    raise L.EgError("JointTree.from_bvh: '{' without ROOT / JOINT / End Site before it")
+                stack.append(pending)
+                pending = None
+            elif tok == "}":
+                if not stack:
+                    raise L.EgError("JointTree.from_bvh: '}' without an open joint")
+                stack.pop()
+            elif tok == "OFFSET":
+                if not stack or i + 3 >= len(tokens):
+                    raise L.EgError("JointTree.from_bvh: OFFSET outside a joint, or without three numbers")
+                try:
+                    nodes[stack[-1]][2][:] = [float(v) for v in tokens[i + 1:i + 4]]
+                except ValueError:
+                    raise L.EgError(f"JointTree.from_bvh: OFFSET {' '.join(tokens[i + 1:i + 4])}: not three numbers")
+                i += 3
+            i += 1
+        named = [k for k, nd in enumerate(nodes) if nd[0] is not None]
+        if not named:
+            raise L.EgError("JointTree.from_bvh: no ROOT / JOINT in the text (need the HIERARCHY block of a BVH file)")
+        all_names = [nodes[k][0] for k in named]
+        if joints is None:
+            keep = list(all_names)
+        else:
+            keep = [str(n) for n in joints]
+            for n in keep:
+                if n not in all_names:
+                    raise L.EgError(f"JointTree.from_bvh: joints: unknown joint name {n!r} (the file has {len(all_names)} joints)")
+                if keep.count(n) > 1:
+                    raise L.EgError(f"JointTree.from_bvh: joints: duplicate joint name {n!r}")
+        if len(set(all_names)) != len(all_names):
+            dup = next(n for n in all_names if all_names.count(n) > 1)
+            raise L.EgError(f"JointTree.from_bvh: duplicate joint name {dup!r} in the file")
+        kept = [k for k in named if nodes[k][0] in set(keep)]             # file order
+        index = {k: j for j, k in enumerate(kept)}
+        parents, offsets = [], []
+        for j, k in enumerate(kept):
+            off = np.array(nodes[k][2], np.float64)
+            a = nodes[k][1]
+            while j > 0 and a >= 0 and a not in index:                     # the skipped joints between a kept joint and its kept ancestor
+                off = off + np.array(nodes[a][2], np.float64)
+                a = nodes[a][1]
+            if j > 0 and a < 0:
+                raise L.EgError(f"JointTree.from_bvh: joints: {nodes[k][0]!r} does not descend from {nodes[kept[0]][0]!r}, the first kept "
+                                "joint (the root of the body)")
+            parents.append(-1 if j == 0 else index[a])
+            offsets.append(off * float(unit))
+        return cls(parents, np.array(offsets), basis=basis, names=[nodes[k][0] for k in kept])
+
+    def __eq__(self, other):
+        return (isinstance(other, JointTree) and self.basis == other.basis and np.array_equal(self.parents, other.parents)
+                and np.array_equal(self.offsets, other.offsets))
+
+    __hash__ = None
+
+    def __repr__(self):
+        return f"JointTree(joints={self.J}, levels={self.levels}, basis={self.basis!r})"
+
+
+def _quat64(m: np.ndarray) -> np.ndarray:
+    """m [..., 3, 3] -> the unit quaternion [..., 4], ``w >= 0``: the branch of the first largest of (trace, m00, m11, m22)."""
+    m00, m01, m02, m10, m11, m12, m20, m21, m22 = (m[..., r, c] for r in range(3) for c in range(3))
+    tr = m00 + m11 + m22
+    one = np.ones_like(tr)
+    cand = np.stack([np.stack([one + tr, m21 - m12, m02 - m20, m10 - m01], -1),
+                     np.stack([m21 - m12, one + m00 - m11 - m22, m01 + m10, m02 + m20], -1),
+                     np.stack([m02 - m20, m01 + m10, one - m00 + m11 - m22, m12 + m21], -1),
+                     np.stack([m10 - m01, m02 + m20, m12 + m21, one - m00 - m11 + m22], -1)], -2)
+    pick = np.argmax(np.stack([tr, m00, m11, m22], -1), -1)              # argmax: the first on ties
+    q = np.take_along_axis(cand, pick[..., None, None], -2)[..., 0, :]
+    q = q / np.maximum(np.sqrt((q * q).sum(-1, keepdims=True)), 1e-12)
+    return np.where(q[..., :1] < 0, -q, q)
+
+
+def _rot6d_matrices64(d: np.ndarray, columns: bool) -> np.ndarray:
+    """d [..., 6] -> R [..., 3, 3] by Gram-Schmidt."""
+    a1, a2 = d[..., :3], d[..., 3:]
+    b1 = a1 / np.maximum(np.sqrt((a1 * a1).sum(-1, keepdims=True)), 1e-12)
+    u2 = a2 - (b1 * a2).sum(-1, keepdims=True) * b1
+    b2 = u2 / np.maximum(np.sqrt((u2 * u2).sum(-1, keepdims=True)), 1e-12)
+    R = np.stack([b1, b2, np.cross(b1, b2)], -2)
+    return np.swapaxes(R, -1, -2) if columns else R
+
+
+def _articulate64(v: np.ndarray, tree: JointTree, frames: List[int], mean, glob: bool, Lf: int, M: int):
+    """v [B, T, 6J] float64, frames [B] -> (joints [B, T_out, J, 3], rotations [B, T_out, J, 4])."""
+    B, T, _D = v.shape
+    J = tree.J
+    t_out = -(-T * Lf // M)
+    joints, rot = np.zeros((B, t_out, J, 3)), np.zeros((B, t_out, J, 4))
+    for b in range(B):
+        n = frames[b]
+        if n < 1:
+            continue
+        x = v[b, :n].reshape(n, J, 6)
+        if mean is not None:
+            x = x + mean.reshape(J, 6)
+        n_out = -(-n * Lf // M)
+        x = _resample64(x, n_out, Lf, M)                        # the 6-D vectors are blended, then the chain runs on the blended frame
+        R = _rot6d_matrices64(x, tree.basis == "columns")
+        G, p = np.zeros_like(R), np.zeros((n_out, J, 3))
+        for j in range(J):
+            a = int(tree.parents[j])
+            if a < 0:
+                G[:, j], p[:, j] = R[:, j], tree.offsets[j]
+            else:
+                G[:, j] = G[:, a] @ R[:, j]
+                p[:, j] = p[:, a] + G[:, a] @ tree.offsets[j]
+        joints[b, :n_out], rot[b, :n_out] = p, _quat64(G if glob else R)
+    return joints, rot
+
+
+def _rot6d64(q: np.ndarray, tree: JointTree, frames: List[int], mean) -> np.ndarray:
+    """q [B, T, J, 4] float64 -> [B, T, 6J]."""
+    B, T = q.shape[:2]
+    out = np.zeros((B, T, 6 * tree.J))
+    for b in range(B):
+        n = frames[b]
+        if n < 1:
+            continue
+        u = q[b, :n] / np.maximum(np.sqrt((q[b, :n] * q[b, :n]).sum(-1, keepdims=True)), 1e-12)
+        w, x, y, z = (u[..., i] for i in range(4))
+        m = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                      2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                      2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], -1).reshape(n, tree.J, 3, 3)
+        if tree.basis == "columns":
+            m = np.swapaxes(m, -1, -2)
+        d = m[..., :2, :].reshape(n, 6 * tree.J)
+        out[b, :n] = d if mean is None else d - mean
+    return out
+
+
+def launch_articulate(track: torch.Tensor, tree: JointTree, d_frames: Optional[torch.Tensor] = None, draws: int = 1, frame_unit: int = 1,
+                      mean: Optional[torch.Tensor] = None, space: str = "local", ratio: Tuple[int, int] = (1, 1),
+                      out_joints: Optional[torch.Tensor] = None, out_rotations: Optional[torch.Tensor] = None, joints: bool = True,
+                      rotations: bool = True) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """eg_articulate_forward on ``track [B, T, 6J]`` (contiguous fp32 CUDA, 16-byte aligned) -> ``(joints [B, T_out, J, 3] or None,
+    rotations [B, T_out, J, 4] or None)``: one launch on the current stream, nothing else (the level table is uploaded on first use per
+    device: warm up before a capture).  ``joints`` / ``rotations``: which outputs to make (an output that is given is made; not neither).
+    The other arguments as in ``launch_joints``."""
+    B, T, D = track.shape
+    if D != tree.pose_dim:
+        raise L.EgError(f"launch_articulate: a tree of {tree.J} joints takes tracks of {tree.pose_dim} columns, got {D}")
+    Lf, M = ratio
+    t_out = -(-T * Lf // M)
+    if out_joints is None and joints:
+        out_joints = torch.empty((B, t_out, tree.J, 3), dtype=torch.float32, device=track.device)
+    if out_rotations is None and rotations:
+        out_rotations = torch.empty((B, t_out, tree.J, 4), dtype=torch.float32, device=track.device)
+    if out_joints is None and out_rotations is None:
+        raise L.EgError("launch_articulate: neither joints nor rotations asked for")
+    if out_joints is not None and out_rotations is not None and out_joints.shape[1] != out_rotations.shape[1]:
+        raise L.EgError(f"launch_articulate: out_joints has {out_joints.shape[1]} frames per row, out_rotations {out_rotations.shape[1]}")
+    stride = (out_joints if out_joints is not None else out_rotations).shape[1]
+    L.check(L.load().eg_articulate_forward(_ptr(track), B, T, *tree.host_ptrs(), tree.J, _ptr(tree.table(track.device)), _ptr(d_frames),
+                                           int(draws), int(frame_unit), _ptr(mean), tree.basis_code, _space(space, "launch_articulate"), Lf, M,
+                                           _ptr(out_joints), _ptr(out_rotations), stride, _stream(track.device)), "eg_articulate_forward")
+    return out_joints, out_rotations
+
+
+def launch_rot6d(quat: torch.Tensor, tree: JointTree, d_frames: Optional[torch.Tensor] = None, draws: int = 1, frame_unit: int = 1,
+                 mean: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """eg_articulate_rot6d on ``quat [B, T, J, 4]`` -> ``[B, T, 6J]``: one launch on the current stream."""
+    B, T = quat.shape[:2]
+    if out is None:
+        out = torch.empty(B, T, tree.pose_dim, dtype=torch.float32, device=quat.device)
+    L.check(L.load().eg_articulate_rot6d(_ptr(quat), B, T, tree.J, _ptr(d_frames), int(draws), int(frame_unit), _ptr(mean), tree.basis_code,
+                                         _ptr(out), _stream(quat.device)), "eg_articulate_rot6d")
+    return out
+
+
+def _tree_checked(track, tree, who: str) -> JointTree:
+    if not isinstance(tree, JointTree):
+        raise L.EgError(f"{who}: tree must be a JointTree, got {type(tree).__name__}")
+    shape = tuple(track.shape)
+    if len(shape) < 2 or shape[-2] < 1:
+        raise L.EgError(f"{who}: track shape {shape}: need [..., T >= 1, {tree.pose_dim}]")
+    if shape[-1] != tree.pose_dim:
+        raise L.EgError(f"{who}: track shape {shape}: a tree of J={tree.J} joints takes 6J={tree.pose_dim} columns per frame, not {shape[-1]}")
+    return tree
+
+
+def _articulate(track, tree, frames, mean, fps, space: str, want_joints: bool, who: str):
+    """Both forward functions: the joints or the rotations of ``track`` under its leading axes."""
+    tree = _tree_checked(track, tree, who)
+    sp = _space(space, who)
+    fe = _front(track, tree, frames, fps, who)
+    if _is_cuda(track):
+        x = _dev32(track).reshape(fe.U * fe.R, fe.T, tree.pose_dim)
+        res = launch_articulate(x, tree, _frames_dev(fe.fr, x.device), fe.R, 1, _mean_dev(mean, tree.pose_dim, x.device, who), space, fe.ratio,
+                                joints=want_joints, rotations=not want_joints)[0 if want_joints else 1]
+    else:
+        v = _host64(track, who).reshape(fe.U * fe.R, fe.T, tree.pose_dim)
+        res = _articulate64(v, tree, fe.per_row, _mean_host(mean, tree.pose_dim, who), sp == L.EG_SKELETON_SPACE_GLOBAL,
+                            *fe.ratio)[0 if want_joints else 1]
+    return _finish(res, track, fe, (tree.J, 3 if want_joints else 4), frames, fps)
+
+
+def joints_from_rot6d(track, tree: JointTree, frames=None, mean=None, fps=None):
+    """``track [..., T, 6J]`` with up to two leading axes -> ``joints [..., T_out, J, 3]`` in metres: every joint's 6-D rotation made a matrix
+    by Gram-Schmidt (``tree.basis``), then forward kinematics over the tree's offsets: ``G_j = G_parent R_j``,
+    ``p_j = p_parent + G_parent offsets[j]``, ``p_0 = offsets[0]``.  ``frames``, ``mean [6J]`` and ``fps`` as in ``joints_from_tracks``; on a
+    resampled frame the 6-D vectors are blended (after the mean) and the chain runs on the blended frame.  A CUDA tensor: one kernel
+    launch, fp32; numpy or a CPU tensor: the definition in float64.  With ``frames`` or ``fps`` the result is ``(joints, joint_frames)``."""
+    return _articulate(track, tree, frames, mean, fps, "local", True, "joints_from_rot6d")
+
+
+def rotations_from_rot6d(track, tree: JointTree, frames=None, mean=None, fps=None, space: str = "local"):
+    """``track [..., T, 6J]`` -> ``rotations [..., T_out, J, 4]``: the unit quaternion ``(w, x, y, z)``, ``w >= 0``, of every joint's rotation
+    ``R_j`` relative to its parent (``space="local"``: what a rig or a BVH channel takes) or of ``G_j`` relative to the root (``"global"``).
+    A degenerate group (zero, or ``a1`` parallel to ``a2``) gives a finite value that is not a rotation.  The other arguments and the
+    return as in ``joints_from_rot6d``; the rotations and joints of the same arguments describe the same pose."""
+    return _articulate(track, tree, frames, mean, fps, space, False, "rotations_from_rot6d")
+
+
+def rot6d_from_rotations(quat, tree: JointTree, frames=None, mean=None):
+    """``quat [..., T, J, 4]`` (up to two leading axes) -> ``rot6d [..., T, 6J]``: every quaternion normalised (``q / max(|q|, 1e-12)``), the
+    first two rows (``basis="rows"``) or columns of its matrix as ``a1 | a2``, minus ``mean [6J]`` when given: the ``seed_pose`` a BEAT
+    generator takes from motion capture, the counterpart of ``dir_vec_from_joints``.  Zeros from ``frames[u]`` on.  CUDA in: the kernel,
+    fp32; numpy / CPU in: float64."""
+    who = "rot6d_from_rotations"
+    if not isinstance(tree, JointTree):
+        raise L.EgError(f"{who}: tree must be a JointTree, got {type(tree).__name__}")
+    shape = tuple(quat.shape)
+    if len(shape) < 3 or shape[-2:] != (tree.J, 4) or shape[-3] < 1:
+        raise L.EgError(f"{who}: quat shape {shape}: need [..., T >= 1, {tree.J}, 4] for a tree of {tree.J} joints")
+    lead, U, R = _lead(shape, 3, who)
+    T = shape[-3]
+    fr = _frames_list(frames, U, T, who)
+    if _is_cuda(quat):
+        q = _dev32(quat).reshape(U * R, T, tree.J, 4)
+        return launch_rot6d(q, tree, _frames_dev(fr, q.device), R, 1, _mean_dev(mean, tree.pose_dim, q.device, who)).reshape(lead + (T, tree.pose_dim))
+    q = _host64(quat, who).reshape(U * R, T, tree.J, 4)
+    d = _rot6d64(q, tree, _per_row(fr, U, R, T), _mean_host(mean, tree.pose_dim, who)).reshape(lead + (T, tree.pose_dim))
+    return torch.from_numpy(d) if isinstance(quat, torch.Tensor) else d
 
 
 def _output_args_early(who: str, joints, joints_fps, rotations, fps_allowed: bool = True) -> None:
@@ -548,9 +894,10 @@ def _output_args_early(who: str, joints, joints_fps, rotations, fps_allowed: boo
 
 
 def output_args(who: str, pose_dim: int, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, fps_allowed: bool = True,
-                hint: str = "") -> Optional[RestPose]:
+                hint: str = ""):
     """The skeleton-output arguments of a caller (``synthesize``, ``GestureStream``: ``who``, the prefix of every message), checked before
-    anything runs; returns the rest pose of ``rotations=`` on ``joints``' skeleton, or None.  ``pose_dim``: the model's; ``fps_allowed``: the
+    anything runs; returns the rest pose of ``rotations=`` on ``joints``' skeleton, or None.  With ``joints=JointTree`` (``6J == pose_dim``;
+    ``rotations=True`` is the only other value, ``joints_unit`` is refused) it returns True where rotations are asked for.  ``pose_dim``: the model's; ``fps_allowed``: the
     caller can change the frame rate; ``hint`` ends the message about a skeleton that does not fit ``pose_dim``."""
     _output_args_early(who, joints, joints_fps, rotations, fps_allowed)
     if rotations is None and rotations_space != "local":
@@ -559,6 +906,20 @@ def output_args(who: str, pose_dim: int, joints, joints_mean, joints_unit, joint
         if joints_mean is not None or joints_unit or joints_fps is not None:
             raise L.EgError(f"{who}: joints_mean / joints_unit{' / joints_fps' if fps_allowed else ''} without joints=skeleton")
         return None
+    if isinstance(joints, JointTree):                                              # the second body type: 6-D joint rotations
+        if joints.pose_dim != pose_dim:
+            raise L.EgError(f"{who}: joints=: the joint tree has J={joints.J} joints, 6J={joints.pose_dim} != pose_dim={pose_dim}")
+        if joints_unit:
+            raise L.EgError(f"{who}: joints_unit=True with joints=JointTree (Gram-Schmidt already normalises the 6-D rotations; joints_unit "
+                            "re-normalises a Skeleton's bone vectors)")
+        if rotations is not None and rotations is not True:
+            raise L.EgError(f"{who}: rotations= with joints=JointTree takes True, got {type(rotations).__name__} (the tree's offsets are the "
+                            "bind pose: there is no rest)")
+        rate_ratio(joints_fps, f"{who}: joints_fps")
+        if rotations is None:
+            return None
+        _space(rotations_space, f"{who}: rotations_space")
+        return True
     if not isinstance(joints, Skeleton):
         raise L.EgError(f"{who}: joints= takes a skeleton.Skeleton, got {type(joints).__name__}")
     if joints.pose_dim != pose_dim:

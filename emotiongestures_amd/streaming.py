@@ -156,6 +156,9 @@ class GestureStream:
     `rotations=rest` (with `joints=`; `rest [K, 3]` the avatar's bind pose, `rotations_space` as in skeleton.rotations_from_tracks): one more
     launch inside the graph leaves the bone rotations of the rows just emitted in `last_rotations [U, H, K, 4]` under the same rules;
     `tail_rotations()`: the rotations of `tail()`.
+    `joints=tree` (a skeleton.JointTree with 6J == pose_dim: the BEAT generators' 6-D joint rotations; `rotations=True` for the rotations too):
+    ONE more launch inside the graph fills `last_joints [U, H, J, 3]` and `last_rotations [U, H, J, 4]` under the same rules, and
+    `tail_joints()` / `tail_rotations()` work likewise; `joints_unit` and a rest pose are refused by name.
     `smooth=Smoother | (window, polyorder)` (smooth.Smoother, deriv 0, window <= H): every step ends with the two launches of a
     smooth.StreamSmoother (inside the graph) that leave in `last_smooth [U, H, D]` the smoothed frames `[sH - half, (s + 1)H - half)` of a row in
     its s-th valid step -- `smooth_delay = half` frames behind the rows just emitted, the first `half` entries of step 0 zeros; zeros for a row
@@ -190,6 +193,7 @@ class GestureStream:
         self.text_len, self.n_mels, self.spec_len = c["text_len"], c["n_mels"], c["spec_len"]
         self.U = int(rows)
         self._sk, self._sk_mean, self._sk_unit = joints, None, bool(joints_unit)
+        self._tree = isinstance(joints, SK.JointTree)            # 6-D joint rotations (6J == pose_dim): rotations=True, no rest pose
         # the rest pose is held here: the captured graph replays the address of its device table
         self._rest, self._rot_space = SK.output_args("GestureStream", self.D, joints, joints_mean, joints_unit, joints_fps, rotations,
                                                      rotations_space, fps_allowed=False), rotations_space
@@ -220,7 +224,7 @@ class GestureStream:
         self.alpha = None if alpha is None else _need_cuda(alpha, "alpha").clone()
         self.device = self.seed_pose.device
         if self._sk is not None:
-            self._sk_mean = SK._mean_dev(joints_mean, self._sk.K, self.device, "GestureStream: joints_mean")
+            self._sk_mean = SK._mean_dev(joints_mean, self._sk.pose_dim, self.device, "GestureStream: joints_mean")
         if self.mel is AUTO_MEL:
             from .engine import MelFrontEnd
             self.mel = MelFrontEnd(self.device)
@@ -307,13 +311,18 @@ class GestureStream:
                 sampled = g["sampled"] if use_sampled else None
             out = eng.stream_step(self._state, *self._geom, spec, g["text"], sampled, self.alpha, want_window=self.want_windows,
                                   workspace=self._ws)
-            if self._sk is not None:                # one more launch after the hand-off: row u has valid[u] * H frames
+            if self._tree:                          # a JointTree: joints and rotations of the rows just emitted from one launch
+                out["joints"], out["rotations"] = self._articulate(out["rows"], out["valid"], self.H)
+            elif self._sk is not None:              # one more launch after the hand-off: row u has valid[u] * H frames
                 out["joints"] = SK.launch_joints(out["rows"], self._sk, out["valid"], 1, self.H, self._sk_mean, self._sk_unit)
-            if self._rest is not None:
+            if self._rest is not None and not self._tree:
                 out["rotations"] = SK.launch_rotations(out["rows"], self._sk, self._rest, out["valid"], 1, self.H, self._sk_mean, self._rot_space)
             if self._sm is not None:                # the outputs, then the new history in a launch of its own
                 out["smooth"] = self._sm.run(out["rows"], out["valid"])
             return out
+
+    def _articulate(self, rows: torch.Tensor, valid: Optional[torch.Tensor], frame_unit: int):
+        return SK.launch_articulate(rows, self._sk, valid, 1, frame_unit, self._sk_mean, self._rot_space, rotations=self._rest is not None)
 
     def _push_only(self):
         """The resampler's launches (with audio_rate), then the ring's: the part of a step that runs even when no row has a window."""
@@ -504,6 +513,8 @@ class GestureStream:
         if self._sk is None:
             raise L.EgError("tail_joints: the session was opened without joints=skeleton")
         with torch.no_grad():
+            if self._tree:
+                return SK.launch_articulate(self.tail(), self._sk, None, 1, 1, self._sk_mean, rotations=False)[0]
             return SK.launch_joints(self.tail(), self._sk, None, 1, 1, self._sk_mean, self._sk_unit)
 
     def tail_rotations(self) -> torch.Tensor:
@@ -511,6 +522,8 @@ class GestureStream:
         if self._rest is None:
             raise L.EgError("tail_rotations: the session was opened without rotations=rest")
         with torch.no_grad():
+            if self._tree:
+                return SK.launch_articulate(self.tail(), self._sk, None, 1, 1, self._sk_mean, self._rot_space, joints=False)[1]
             return SK.launch_rotations(self.tail(), self._sk, self._rest, None, 1, 1, self._sk_mean, self._rot_space)
 
     def tail_smooth(self) -> torch.Tensor:

@@ -588,6 +588,52 @@ int eg_skeleton_rotations(const float* track, int32_t rows, int32_t T, const int
                           int32_t bones, const double* rest, const void* d_levels, const int32_t* d_frames, int32_t draws, int32_t frame_unit,
                           const float* d_mean, int32_t space, int32_t L, int32_t M, float* rotations, int64_t out_stride, void* stream);
 
+/* Articulated bodies: tracks of 6-D joint rotations (the BEAT generators: pose_dim = 6J) -> joint positions and joint rotations, and back.
+ * Body.  J joints in topological order, 1 <= J <= EG_ARTICULATE_MAX_JOINTS: parents[0] = -1, 0 <= parents[j] < j; offsets [J, 3] fp32 in
+ * metres, the joint's position in its parent's frame at the bind pose (finite; zero allowed).  eg_articulate_check (host only, no HIP call)
+ * refuses by name: J out of range, parents[0] != -1, a parent that is not an earlier joint, an offset that is not finite.
+ * 6-D to matrix.  d_j = track[b, t, 6j .. 6j+5] (+ d_mean[6j ..]); a1 = d_j[0..2], a2 = d_j[3..5];
+ *     b1 = a1 / max(|a1|, 1e-12);  u2 = a2 - (b1 . a2) b1;  b2 = u2 / max(|u2|, 1e-12);  b3 = b1 x b2.
+ * basis = EG_ARTICULATE_BASIS_ROWS: R_j has the rows b1, b2, b3 (pytorch3d's rotation_6d_to_matrix); EG_ARTICULATE_BASIS_COLUMNS: the
+ * columns (Zhou et al. 2019).  A degenerate group (zero, or a1 parallel to a2) gives a finite matrix that is not a rotation; every output
+ * stays finite.
+ * Chain, in table order:  G_0 = R_0, p_0 = offsets[0];  G_j = G_parent R_j,  p_j = p_parent + G_parent offsets[j].
+ * Outputs.  joints [rows, out_stride, J, 3] = p.  rotations [rows, out_stride, J, 4]: the unit quaternion (w, x, y, z) of R_j
+ * (space = EG_SKELETON_SPACE_LOCAL) or of G_j (EG_SKELETON_SPACE_GLOBAL).  quat(m), with tr = m00 + m11 + m22 and the first largest of
+ * (tr, m00, m11, m22):
+ *     tr:  (1 + tr, m21 - m12, m02 - m20, m10 - m01)          m00: (m21 - m12, 1 + m00 - m11 - m22, m01 + m10, m02 + m20)
+ *     m11: (m02 - m20, m01 + m10, 1 - m00 + m11 - m22, m12 + m21)   m22: (m10 - m01, m02 + m20, m12 + m21, 1 - m00 - m11 + m22)
+ * divided by max(|q|, 1e-12) and negated where w < 0, so w >= 0.  Either output pointer may be NULL, not both; one launch writes both.
+ * Frames.  rows, d_frames, draws, frame_unit, the reduced ratio L / M, n_out = ceil(n L / M), lo and f exactly as in eg_skeleton_joints.  On
+ * an interpolated frame the 6-D VECTORS of the source frames lo and lo + 1 are blended, after the mean: d = fmaf(d(lo + 1) - d(lo), f,
+ * d(lo)); the whole chain then runs on the blended frame, so the joints and rotations of one call describe the same pose.  n = 1: frame 0.
+ * Frames k' >= n_out are written as zeros; source frames t >= n are never read and may hold NaN.
+ * eg_articulate_levels (host only) writes the device table of the call, EG_ARTICULATE_LEVEL_WORDS(J) 32-bit words, uploaded by the caller
+ * as d_table: [0] the number of depth levels; [1 .. 65] the first position of every level in `order` (J from the last level on);
+ * order [J]: the joints sorted by depth, table order inside a level; parents [J]; offsets [J, 3] (fp32 bits).  One thread owns one (output
+ * frame, joint of a level) and a workgroup of EG_ARTICULATE_TILE_FRAMES output frames (eg_articulate_tile_frames) walks the levels with one
+ * barrier each.  Nothing ties the upload to the host arguments: with a d_table that differs the result is unspecified (its numbers are
+ * clamped, the accesses stay in range).
+ * Inverse.  eg_articulate_rot6d: quat [rows, T, J, 4] -> rot6d [rows, T, 6J]: q / max(|q|, 1e-12), its matrix, the first two rows (basis
+ * rows) or columns (basis columns) as a1 | a2, minus d_mean when given; zeros from frame n on.
+ * Guarantees as for eg_skeleton_joints: caller-owned memory, no allocation, no synchronisation, one launch, capturable; one owning thread
+ * per output element, no atomics; a row's result does not depend on rows, on its place in the batch or on out_stride.  Refuses by name
+ * before the launch: null pointers, a bad body, pointers not 16-byte aligned (d_table / d_mean: 4-byte), rows or T < 1, rows not a
+ * multiple of draws, frame_unit < 1, an unknown basis or space, an unsupported ratio, a short out_stride, index range. */
+#define EG_ARTICULATE_MAX_JOINTS 64
+#define EG_ARTICULATE_TILE_FRAMES 8  /* output frames of one workgroup */
+#define EG_ARTICULATE_BASIS_ROWS 0
+#define EG_ARTICULATE_BASIS_COLUMNS 1
+#define EG_ARTICULATE_LEVEL_WORDS(J) (66 + 5 * (J))
+int eg_articulate_check(const int32_t* parents, const float* offsets, int32_t joints);
+int eg_articulate_levels(const int32_t* parents, const float* offsets, int32_t joints, int32_t* words);
+int32_t eg_articulate_tile_frames(void);
+int eg_articulate_forward(const float* track, int32_t rows, int32_t T, const int32_t* parents, const float* offsets, int32_t joints,
+                          const void* d_table, const int32_t* d_frames, int32_t draws, int32_t frame_unit, const float* d_mean, int32_t basis,
+                          int32_t space, int32_t L, int32_t M, float* out_joints, float* out_rotations, int64_t out_stride, void* stream);
+int eg_articulate_rot6d(const float* quat, int32_t rows, int32_t T, int32_t joints, const int32_t* d_frames, int32_t draws,
+                        int32_t frame_unit, const float* d_mean, int32_t basis, float* rot6d, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Smoothed output: a Savitzky-Golay filter along the time axis of whole tracks on the device (csrc/smooth.hip)
  * ------------------------------------------------------------------------------------------ */

@@ -18,7 +18,12 @@ With --smooth K P (not with --joints) the stream is opened with smooth=(K, P): t
 [U, 30, 126] the Savitzky-Golay-smoothed frames of every row, K // 2 frames behind the rows just emitted; the script prints the frame-to-frame
 step of the raw and the smoothed rows per push, and every row's smoothed rows followed by tail_smooth() are checked to EQUAL
 smooth.smooth_tracks on its finished track.
-usage: demo_stream.py [rows=4] [seconds=20] [--audio-rate HZ] [--joints [--rotations]] [--smooth K P]"""
+With --beat the generator is BEAT-shaped (60 poses of 282 columns, 10 of them the prior; 50 poses per push).  With --beat --joints the body is a
+skeleton.JointTree -- the BEAT columns are one 6-D rotation per joint -- read from the HIERARCHY block of --bvh FILE (47 joints), or a
+synthetic 47-joint upper body without --bvh: ONE more launch inside the graph leaves stream.last_joints [U, 50, 47, 3] and, with --rotations,
+stream.last_rotations [U, 50, 47, 4] (local joint rotations; there is no rest pose); the script prints how far the deepest joint travels and the
+largest rotation angle per push.
+usage: demo_stream.py [rows=4] [seconds=20] [--beat] [--audio-rate HZ] [--joints [--bvh FILE] [--rotations]] [--smooth K P]"""
 import os
 import sys
 import time
@@ -39,8 +44,24 @@ if "--audio-rate" in sys.argv:
     RATE = int(sys.argv[i + 1])
     del sys.argv[i:i + 2]
 AR = {"audio_rate": RATE} if RATE != 16000 else {}
-JOINTS, JK = "--joints" in sys.argv, {}
-if JOINTS:
+BEAT = "--beat" in sys.argv
+if BEAT:
+    sys.argv.remove("--beat")
+BVH = None
+if "--bvh" in sys.argv:
+    i = sys.argv.index("--bvh")
+    BVH = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
+JOINTS, JK, TREE = "--joints" in sys.argv, {}, None
+if BVH and not (BEAT and JOINTS):
+    sys.exit("--bvh needs --beat --joints (a BVH hierarchy is the body of the BEAT generators' 6-D joint rotations)")
+if JOINTS and BEAT:
+    import emotiongestures_amd.skeleton as SK_
+    from tools.bench_articulate import synthetic_tree
+    sys.argv.remove("--joints")
+    TREE = SK_.JointTree.from_bvh(open(BVH).read()) if BVH else synthetic_tree(SK_)
+    JK = dict(joints=TREE)
+elif JOINTS:
     from emotiongestures_amd.skeleton import ted_expressive
     sys.argv.remove("--joints")
     JK = dict(joints=ted_expressive(), joints_unit=True)
@@ -61,14 +82,16 @@ if "--smooth" in sys.argv:
 U = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 20.0
 dev = torch.device("cuda:0")
-FRAMES, POSE_DIM, PRIOR, FPS = 34, 126, 4, 15
+FRAMES, POSE_DIM, PRIOR, FPS = (60, 282, 10, 15) if BEAT else (34, 126, 4, 15)
 total = int(seconds * RATE)                              # samples per recording at the caller's rate
 to16 = lambda n: R_.out_length(n, RATE) if AR else n
 
 gen = build_mirror("spatial", FRAMES, POSE_DIM, PRIOR, PRIOR, seed=7, precision="bf16x3").to(dev)
 vae = load_synth_weights(MLP_Reconstruct_v3(frames=FRAMES), 7).eval().to(dev)
 audio = torch.from_numpy(synth_audio(U, total, seed=90)).to(dev)
-if ROTATIONS:                                            # the rest pose: the first generated frame of row 0's first window
+if ROTATIONS and TREE is not None:                       # a joint tree has no rest pose: its offsets are the bind pose
+    JK["rotations"] = True
+elif ROTATIONS:                                          # the rest pose: the first generated frame of row 0's first window
     first = H.synthesize((gen, vae), audio[:1], torch.zeros(1, 1, 60, dtype=torch.int64, device=dev), torch.zeros(1, PRIOR, POSE_DIM, device=dev),
                          labels=torch.nn.functional.one_hot(torch.zeros(1, dtype=torch.int64), 8).float().to(dev), z=torch.zeros(1, 1, 32), **AR)
     JK["rotations"] = first["track"][0, PRIOR].reshape(-1, 3).cpu()
@@ -122,11 +145,19 @@ for k in range(1, steps + 1):
             if SMOOTH:
                 smooths[u][which[u]].append(stream.last_smooth[u])
     print(f"push {k:2d}: valid {valid.cpu().tolist()}  windows {stream.last_windows}  {1e3 * t_steps[-1]:.2f} ms")
-    if JOINTS and stream.last_joints is not None:
+    if TREE is not None and stream.last_joints is not None:
+        j, deep = stream.last_joints, int(TREE.depth.argmax())
+        print(f"         last_joints {tuple(j.shape)}: extent of joint {deep} ({int(TREE.depth[deep])} joints from the root) "
+              f"{float((j[:, :, deep].amax(1) - j[:, :, deep].amin(1)).norm(dim=1).max()):.3f} m")
+        if ROTATIONS:
+            q = stream.last_rotations[valid.bool()]             # a row that was not valid holds zeros, not rotations
+            print(f"         last_rotations {tuple(q.shape)}: largest local rotation "
+                  f"{float(torch.rad2deg(2 * torch.acos(q[..., 0].clamp(max=1.0))).max()):.1f} degrees")
+    elif JOINTS and stream.last_joints is not None:
         j = stream.last_joints
         ext = [float((j[:, :, w].amax(1) - j[:, :, w].amin(1)).norm(dim=1).max()) for w in (6, 7)]
         print(f"         last_joints {tuple(j.shape)}: wrist extent left {ext[0]:.3f} m, right {ext[1]:.3f} m")
-    if ROTATIONS and stream.last_rotations is not None:
+    if ROTATIONS and TREE is None and stream.last_rotations is not None:
         q = stream.last_rotations[valid.bool()]             # a row that was not valid holds zeros, not rotations
         deg = [float(torch.rad2deg(2 * torch.acos(q[:, :, b, 0].clamp(max=1.0))).max()) for b in (4, 21)]      # the forearm bones
         print(f"         last_rotations {tuple(q.shape)}: largest elbow swing left {deg[0]:.1f} degrees, right {deg[1]:.1f} degrees")

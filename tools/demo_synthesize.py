@@ -26,7 +26,11 @@ their shape and the largest elbow swing in degrees.
 With --smooth K P the call also returns the smoothed track (smooth.smooth_tracks: a Savitzky-Golay filter of window K and polyorder P along
 time, scipy.signal.savgol_filter(mode="interp"), one more launch); with --joints the joints (and rotations) are made from it, and the script
 prints the mean frame-to-frame step of the left wrist before and after -- without --joints, of the pose vector.
-usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--joints-fps N] [--rotations]] [--smooth K P] [--out tracks.npz]"""
+With --beat --joints the body is a skeleton.JointTree -- the BEAT columns are one 6-D rotation per joint -- read from the HIERARCHY block of
+--bvh FILE (which must have 47 joints, or name them with --bvh-joints A,B,...), or a synthetic 47-joint upper body without --bvh: joint
+positions and, with --rotations, one local rotation per joint come from ONE more launch (skeleton.launch_articulate), and the script prints their
+shapes, how far the deepest joint travels and the largest rotation angle.
+usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--bvh FILE [--bvh-joints A,B,...]] [--joints-fps N] [--rotations]] [--smooth K P] [--out tracks.npz]"""
 import os
 import sys
 import time
@@ -42,6 +46,7 @@ from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
 from emotiongestures_amd.synth import load_synth_weights, synth_audio
 
 argv, DRAWS, OUT, BEAT, DIVERSITY, RATE, JOINTS, JOINTS_FPS, ROTATIONS, SMOOTH = [], 0, None, False, False, 16000, False, None, False, None
+BVH, BVH_JOINTS = None, None
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--draws":
@@ -60,14 +65,18 @@ for a in it:
         JOINTS_FPS = int(next(it))
     elif a == "--rotations":
         ROTATIONS = True
+    elif a == "--bvh":
+        BVH = next(it)
+    elif a == "--bvh-joints":
+        BVH_JOINTS = next(it).split(",")
     elif a == "--smooth":
         SMOOTH = (int(next(it)), int(next(it)))
     else:
         argv.append(a)
 if DIVERSITY and DRAWS < 2:
     sys.exit("--diversity needs --draws R with R >= 2 (the take diversity is a distance between the takes of one recording)")
-if JOINTS and BEAT:
-    sys.exit("--joints is for the TED shape: the BEAT generators' 282 columns are rotations, not bone direction vectors")
+if BVH and not (JOINTS and BEAT):
+    sys.exit("--bvh needs --beat --joints (a BVH hierarchy is the body of the BEAT generators' 6-D joint rotations)")
 if JOINTS_FPS and not JOINTS:
     sys.exit("--joints-fps needs --joints")
 if ROTATIONS and not JOINTS:
@@ -112,7 +121,32 @@ print(f"window 1 beyond its overlap (rows [{HOP + PRIOR}, {2 * HOP})) appears ra
 print(f"one call (mel + CVAE + roll-out{' + beat score' if BEAT else ''}, eager): {1e3 * dt:.2f} ms = {1e3 * dt / (U * track.shape[1] / FPS):.4f} ms per second of audio")
 if BEAT:
     print(f"--beat: beat-alignment score per recording: {[round(float(v), 4) for v in out['beat'].cpu()]}")
-if JOINTS:
+if JOINTS and BEAT:
+    from emotiongestures_amd.skeleton import JointTree
+    from tools.bench_articulate import synthetic_tree
+    import emotiongestures_amd.skeleton as SK_
+    tree = JointTree.from_bvh(open(BVH).read(), joints=BVH_JOINTS) if BVH else synthetic_tree(SK_)
+    jk = dict(joints=tree, joints_fps=(FPS, JOINTS_FPS) if JOINTS_FPS else None, smooth=SMOOTH, rotations=True if ROTATIONS else None)
+    H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, **jk, **AR)          # warm-up (uploads the level table)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    jo = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, **jk, **AR)
+    torch.cuda.synchronize()
+    dt_j = time.perf_counter() - t0
+    joints = jo["joints"]
+    deep = int(tree.depth.argmax())
+    extent = (joints[:, :, deep].amax(1) - joints[:, :, deep].amin(1)).norm(dim=1).mean()
+    print(f"--joints: {tree!r}{' from ' + BVH if BVH else ' (synthetic)'}: joints {tuple(joints.shape)} (frames per recording {jo['joint_frames']}" +
+          (f", {FPS} -> {JOINTS_FPS} fps" if JOINTS_FPS else "") + f"), one more launch in the call ({1e3 * dt_j:.2f} ms against {1e3 * dt:.2f} ms); "
+          f"extent of joint {deep}{' ' + tree.names[deep] if tree.names else ''} ({int(tree.depth[deep])} joints from the root): {float(extent):.3f} m")
+    if SMOOTH:
+        print(f"--smooth {SMOOTH[0]} {SMOOTH[1]}: the joints come from track_smooth {tuple(jo['track_smooth'].shape)}: Gram-Schmidt re-orthonormalises "
+              "the filtered 6-D rows")
+    if ROTATIONS:
+        rot = jo["rotations"]
+        print(f"--rotations: rotations {tuple(rot.shape)} from the same launch; largest local rotation: "
+              f"{float(torch.rad2deg(2 * torch.acos(rot[..., 0].clamp(max=1.0))).max()):.1f} degrees")
+elif JOINTS:
     from emotiongestures_amd.skeleton import ted_expressive
     jk = dict(joints=ted_expressive(), joints_unit=True, joints_fps=(FPS, JOINTS_FPS) if JOINTS_FPS else None, smooth=SMOOTH)
     if ROTATIONS:                                        # the rest pose: the first generated frame of recording 0 (normalised by the call)
