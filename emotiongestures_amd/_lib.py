@@ -62,6 +62,7 @@ EG_SKELETON_MAX_BONES, EG_SKELETON_MAX_FACTOR, EG_SKELETON_TILE_FRAMES = 63, 64,
 EG_SKELETON_SPACE_LOCAL, EG_SKELETON_SPACE_GLOBAL = 0, 1
 EG_ARTICULATE_MAX_JOINTS, EG_ARTICULATE_TILE_FRAMES = 64, 8
 EG_ARTICULATE_BASIS_ROWS, EG_ARTICULATE_BASIS_COLUMNS = 0, 1
+EG_UNWRAP_TILE_FRAMES = 64
 EG_SMOOTH_MAX_WINDOW, EG_SMOOTH_TILE_FRAMES, EG_SMOOTH_TILE_COLS = 31, 64, 64
 
 # name -> (restype, argtypes).  Must list every symbol include/emogest.h declares
@@ -136,6 +137,10 @@ SIGNATURES = {
     "eg_articulate_tile_frames": (_I, []),
     "eg_articulate_forward": (C.c_int, [_P, _I, _I, _P, _P, _I, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _L, _P]),
     "eg_articulate_rot6d": (C.c_int, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P]),
+    "eg_articulate_euler": (C.c_int, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P, _L, _P]),
+    "eg_articulate_rot6d_euler": (C.c_int, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P, _P]),
+    "eg_angle_unwrap_workspace_bytes": (_L, [_I, _I, _I]),
+    "eg_angle_unwrap": (C.c_int, [_P, _I, _I, _I, _P, _I, _I, C.c_double, _P, _L, _P]),
     "eg_smooth_design": (C.c_int, [_I, _I, _I, C.c_double, _P, _P]),
     "eg_smooth_tile_frames": (_I, []),
     "eg_smooth_tile_cols": (_I, []),

@@ -19,6 +19,9 @@
 //   articulated bodies (eg_articulate_check, eg_articulate_levels, eg_articulate_forward, eg_articulate_rot6d): tracks of 6-D joint rotations
 //             (pose_dim = 6J) -> joint positions and joint rotations in one launch, on the same tile walk with a tile height of its own, and the
 //             elementwise inverse; see the section further down.
+//   Euler channels (eg_articulate_euler, eg_articulate_rot6d_euler): the same tracks -> the angles of every joint's BVH rotation channels, on the
+//             articulate kernel's tile walk without the level walk, and the elementwise inverse; see the section further down.  The Euler
+//             filter over the angles is csrc/euler.hip.
 #include "common.h"
 #include <math.h>
 
@@ -557,6 +560,147 @@ __global__ __launch_bounds__(THREADS) void articulate_rot6d_kernel(const ArtArgs
     });
 }
 
+// ---- Euler channels (eg_articulate_euler, eg_articulate_rot6d_euler) ------------------------------------------------------------------------
+// No tree walk: R_j of every (output frame, joint) by the articulate kernel's own Gram-Schmidt, three angles from it, 12 bytes into an LDS tile
+// eo[frame][joint][3] that leaves through store_range as whole rows.  An order code is 2 i + (descending): XYZ XZY YXZ YZX ZXY ZYX = 0..5;
+// the seven (inverse: six) entries a thread needs are picked from its nine registers by selects, so joints of different orders in one wave
+// run the same instructions.  The device table of codes indexes nothing but the selects; it is clamped to 0..5 all the same.
+constexpr int EHEAD = MAX_J + 6 * MAX_J;                // order codes | mean [6 * 64]
+static_assert(EHEAD % 4 == 0, "the staged frames start on a quad");
+
+struct EulArgs { Args a; const int* orders; int J, columns; float scale; };     // scale: forward rad -> output unit; inverse: input unit -> rad
+
+__device__ __forceinline__ float pick9(const float* m, int idx) {
+    float v = m[0];
+#pragma unroll
+    for (int e = 1; e < 9; ++e) v = idx == e ? m[e] : v;
+    return v;
+}
+
+struct Axes { int i, j, k; float eps; };
+__device__ __forceinline__ Axes order_axes(int code) {
+    const int i = code >> 1, lo = i == 0 ? 1 : 0, hi = i == 2 ? 1 : 2;
+    const int j = (code & 1) ? hi : lo, k = (code & 1) ? lo : hi;
+    return {i, j, k, j == (i == 2 ? 0 : i + 1) ? 1.f : -1.f};
+}
+
+template <bool NATIVE>
+__global__ __launch_bounds__(THREADS) void articulate_euler_kernel(const EulArgs k) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const Args& a = k.a;
+    const int J = k.J, D = 6 * J, J3 = 3 * J, tid = threadIdx.x;
+    int* ord = reinterpret_cast<int*>(lds);
+    float* mn = lds + MAX_J;
+    float* xin = lds + EHEAD;
+    float* eo = xin + round4(SLA * D + 8);                                      // eo[frame of the tile][joint][3]
+    const Tile t = tile_of<NATIVE, TFA>(a, a.T_out);
+    const long long f0 = (long long)t.b * a.T_out + t.k0;
+    zero_tail(a.dst, f0 * J3, J3, t);
+    if (t.live == 0) return;
+    for (int j = tid; j < J; j += THREADS) ord[j] = min(max(k.orders[j], 0), 5);
+    const bool has_mean = a.mean != nullptr;
+    load_mean(a, mn);
+    // stage_pass' barrier also covers the tables; the barrier behind the angles ended the reads of xin, and a later pass writes other frames of eo
+    const Walk<NATIVE, SLA> w = {t.k0, t.n, a.L, a.M};
+    Pass ps;
+    for (int i = 0; i < t.live; i = ps.i1) {
+        const float* x = stage_pass(a, t, w, i, xin, ps);
+        const int nf = ps.i1 - i;
+        for (int q = tid; q < nf * J; q += THREADS) {                            // one thread per (output frame, joint)
+            const int fl = q / J, j = q - fl * J, fr = i + fl;
+            float d[6];
+            if (NATIVE || t.n < 2) {
+                const float* xs = x + (NATIVE ? fl : 0) * D + 6 * j;
+#pragma unroll
+                for (int e = 0; e < 6; ++e) d[e] = has_mean ? xs[e] + mn[6 * j + e] : xs[e];
+            } else {                                                            // the 6-D vectors are blended, after the mean
+                const Blend bl = w.blend(ps, fr);
+                const float* xs = x + bl.slot * D + 6 * j;
+#pragma unroll
+                for (int e = 0; e < 6; ++e) {
+                    float y = xs[e], z = xs[D + e];
+                    if (has_mean) { y += mn[6 * j + e]; z += mn[6 * j + e]; }
+                    d[e] = fmaf(z - y, bl.f, y);
+                }
+            }
+            const float n1 = fmaxf(sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]), 1e-12f);
+            const float b10 = d[0] / n1, b11 = d[1] / n1, b12 = d[2] / n1;
+            const float dot = b10 * d[3] + b11 * d[4] + b12 * d[5];
+            const float u0 = d[3] - dot * b10, u1 = d[4] - dot * b11, u2 = d[5] - dot * b12;
+            const float n2 = fmaxf(sqrtf(u0 * u0 + u1 * u1 + u2 * u2), 1e-12f);
+            const float b20 = u0 / n2, b21 = u1 / n2, b22 = u2 / n2;
+            const float b30 = b11 * b22 - b12 * b21, b31 = b12 * b20 - b10 * b22, b32 = b10 * b21 - b11 * b20;
+            float R[9];
+            if (k.columns) { R[0] = b10; R[1] = b20; R[2] = b30; R[3] = b11; R[4] = b21; R[5] = b31; R[6] = b12; R[7] = b22; R[8] = b32; }
+            else { R[0] = b10; R[1] = b11; R[2] = b12; R[3] = b20; R[4] = b21; R[5] = b22; R[6] = b30; R[7] = b31; R[8] = b32; }
+            const Axes o = order_axes(ord[j]);
+            const float rii = pick9(R, 4 * o.i), rij = pick9(R, 3 * o.i + o.j), s = o.eps * pick9(R, 3 * o.i + o.k);
+            const float eb = atan2f(s, sqrtf(rii * rii + rij * rij));
+            float ea, ec;
+            if (1.f - fabsf(s) >= 0x1p-20f) {
+                ea = atan2f(-o.eps * pick9(R, 3 * o.j + o.k), pick9(R, 4 * o.k));
+                ec = atan2f(-o.eps * rij, rii);
+            } else {                                                            // the lock: a and c turn about one axis, c = 0
+                ea = atan2f(o.eps * pick9(R, 3 * o.k + o.j), pick9(R, 4 * o.j));
+                ec = 0.f;
+            }
+            float* e3 = eo + (fr * J + j) * 3;
+            e3[0] = ea * k.scale; e3[1] = eb * k.scale; e3[2] = ec * k.scale;
+        }
+        __syncthreads();
+        store_range(a.dst, f0 * J3, J3, (f0 + i) * J3, (f0 + ps.i1) * J3, [&](int fr, int r) { return eo[fr * J3 + r]; });
+    }
+}
+
+// euler [B, T, J, 3] -> rot6d [B, T, 6J]: R = R_i(a) R_j(b) R_k(c) in closed form.  With (sa, sb, sc) the sines times eps and p(.) the
+// place of an axis in the order, R[r][c] = m[p(r)][p(c)] of
+//     m = | cb cc             -cb sc              sb    |
+//         | sa sb cc + ca sc   ca cc - sa sb sc  -sa cb |
+//         | sa sc - ca sb cc   sa cc + ca sb sc   ca cb |
+__global__ __launch_bounds__(THREADS) void articulate_rot6d_euler_kernel(const EulArgs k) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const Args& a = k.a;
+    const int J = k.J, D = 6 * J, tid = threadIdx.x;
+    int* ord = reinterpret_cast<int*>(lds);
+    float* mn = lds + MAX_J;
+    float* buf = lds + EHEAD;
+    const Tile t = tile_of<true, TFI>(a, a.T);
+    const long long f0 = (long long)t.b * a.T + t.k0;
+    zero_tail(a.dst, f0 * D, D, t);
+    if (t.live == 0) return;
+    for (int j = tid; j < J; j += THREADS) ord[j] = min(max(k.orders[j], 0), 5);
+    const bool has_mean = a.mean != nullptr;
+    load_mean(a, mn);
+    __syncthreads();
+    for (int q = tid; q < t.live * J; q += THREADS) {
+        const float* src = a.src + (f0 * J + q) * 3;
+        const Axes o = order_axes(ord[q % J]);
+        float sa, ca, sb, cb, sc, cc;
+        sincosf(src[0] * k.scale, &sa, &ca);
+        sincosf(src[1] * k.scale, &sb, &cb);
+        sincosf(src[2] * k.scale, &sc, &cc);
+        sa *= o.eps; sb *= o.eps; sc *= o.eps;
+        const float m[9] = {cb * cc, -(cb * sc), sb,
+                            sa * sb * cc + ca * sc, ca * cc - sa * sb * sc, -(sa * cb),
+                            sa * sc - ca * sb * cc, sa * cc + ca * sb * sc, ca * cb};
+        const int p0 = o.i == 0 ? 0 : (o.j == 0 ? 1 : 2), p1 = o.i == 1 ? 0 : (o.j == 1 ? 1 : 2), p2 = o.i == 2 ? 0 : (o.j == 2 ? 1 : 2);
+        float* out = buf + 6 * q;                                               // q = frame * J + joint: the tile's rows are contiguous
+        out[0] = pick9(m, 4 * p0);
+        if (k.columns) {
+            out[1] = pick9(m, 3 * p1 + p0); out[2] = pick9(m, 3 * p2 + p0);
+            out[3] = pick9(m, 3 * p0 + p1); out[4] = pick9(m, 4 * p1); out[5] = pick9(m, 3 * p2 + p1);
+        } else {
+            out[1] = pick9(m, 3 * p0 + p1); out[2] = pick9(m, 3 * p0 + p2);
+            out[3] = pick9(m, 3 * p1 + p0); out[4] = pick9(m, 4 * p1); out[5] = pick9(m, 3 * p1 + p2);
+        }
+    }
+    __syncthreads();
+    store_range(a.dst, f0 * D, D, f0 * D, (f0 + t.live) * D, [&](int fr, int r) {
+        const float v = buf[fr * D + r];
+        return has_mean ? v - mn[r] : v;
+    });
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
 int check_table(const char* who, const int32_t* parents, const int32_t* children, const float* lengths, int K) {
     EG_REQUIRE(parents && children && lengths, EG_ERR_BAD_ARG, "%s: null parents / children / lengths", who);
@@ -847,4 +991,56 @@ extern "C" int eg_articulate_rot6d(const float* quat, int32_t rows, int32_t T, i
     const ArtArgs k = {{quat, nullptr, d_frames, d_mean, rot6d, rows, T, 2 * joints, draws, frame_unit, 1, 1, (int)tiles, T}, nullptr, joints,
                        basis == EG_ARTICULATE_BASIS_COLUMNS};
     return launch(articulate_rot6d_kernel, k.a, k, 6 * MAX_J + TFI * 6 * joints, stream, "articulate_rot6d");
+}
+
+// ---- Euler channels: host -------------------------------------------------------------------------------------------------------------------
+namespace {
+
+int check_orders(const char* who, const int32_t* orders, const void* d_orders, int J) {
+    EG_REQUIRE(J >= 1 && J <= MAX_J, EG_ERR_UNSUPPORTED, "%s: joints=%d (1..%d)", who, J, MAX_J);
+    EG_REQUIRE(orders && d_orders, EG_ERR_BAD_ARG, "%s: null orders / d_orders", who);
+    EG_REQUIRE((reinterpret_cast<uintptr_t>(d_orders) & 3u) == 0, EG_ERR_ALIGN, "%s: d_orders not 4-byte aligned", who);
+    for (int j = 0; j < J; ++j)
+        EG_REQUIRE(orders[j] >= 0 && orders[j] <= 5, EG_ERR_BAD_ARG, "%s: joint %d: order code %d (0..5: XYZ XZY YXZ YZX ZXY ZYX)", who, j, orders[j]);
+    return EG_OK;
+}
+
+}  // namespace
+
+extern "C" int eg_articulate_euler(const float* track, int32_t rows, int32_t T, int32_t joints, const int32_t* orders, const void* d_orders,
+                                   const int32_t* d_frames, int32_t draws, int32_t frame_unit, const float* d_mean, int32_t basis,
+                                   int32_t degrees, int32_t L, int32_t M, float* euler, int64_t out_stride, void* stream) {
+    const char* who = "eg_articulate_euler";
+    EG_REQUIRE(euler, EG_ERR_BAD_ARG, "%s: null output", who);
+    int rc = check_orders(who, orders, d_orders, joints);
+    if (rc != EG_OK) return rc;
+    rc = rows_checks(who, track, rows, T, draws, frame_unit, d_mean, basis);
+    if (rc != EG_OK) return rc;
+    EG_REQUIRE(eg_aligned16(euler), EG_ERR_ALIGN, "%s: output not 16-byte aligned", who);
+    EG_REQUIRE((long long)rows * T * 6 * joints < (1ll << 40), EG_ERR_UNSUPPORTED, "%s: rows=%d x frames=%d: index range", who, rows, T);
+    EulArgs k = {{track, nullptr, d_frames, d_mean, euler, rows, T, 2 * joints, draws, frame_unit}, static_cast<const int*>(d_orders), joints,
+                 basis == EG_ARTICULATE_BASIS_COLUMNS, degrees ? (float)(180.0 / M_PI) : 1.f};
+    rc = forward_args(who, k.a, L, M, out_stride, 3 * joints, TFA);
+    if (rc != EG_OK) return rc;
+    const bool native = k.a.L == 1 && k.a.M == 1;
+    return launch(native ? articulate_euler_kernel<true> : articulate_euler_kernel<false>, k.a, k,
+                  EHEAD + round4(SLA * 6 * joints + 8) + TFA * 3 * joints, stream, "articulate_euler");
+}
+
+extern "C" int eg_articulate_rot6d_euler(const float* euler, int32_t rows, int32_t T, int32_t joints, const int32_t* orders, const void* d_orders,
+                                         const int32_t* d_frames, int32_t draws, int32_t frame_unit, const float* d_mean, int32_t basis,
+                                         int32_t degrees, float* rot6d, void* stream) {
+    const char* who = "eg_articulate_rot6d_euler";
+    EG_REQUIRE(rot6d, EG_ERR_BAD_ARG, "%s: null output", who);
+    int rc = check_orders(who, orders, d_orders, joints);
+    if (rc != EG_OK) return rc;
+    rc = rows_checks(who, euler, rows, T, draws, frame_unit, d_mean, basis);
+    if (rc != EG_OK) return rc;
+    EG_REQUIRE(eg_aligned16(rot6d), EG_ERR_ALIGN, "%s: output not 16-byte aligned", who);
+    const long long tiles = ((long long)T + TFI - 1) / TFI;
+    EG_REQUIRE(tiles * rows <= 0x7fffffffll && (long long)rows * T * 6 * joints < (1ll << 40), EG_ERR_UNSUPPORTED,
+               "%s: rows=%d x frames=%d: grid / index range", who, rows, T);
+    const EulArgs k = {{euler, nullptr, d_frames, d_mean, rot6d, rows, T, 2 * joints, draws, frame_unit, 1, 1, (int)tiles, T},
+                       static_cast<const int*>(d_orders), joints, basis == EG_ARTICULATE_BASIS_COLUMNS, degrees ? (float)(M_PI / 180.0) : 1.f};
+    return launch(articulate_rot6d_euler_kernel, k.a, k, EHEAD + TFI * 6 * joints, stream, "articulate_rot6d_euler");
 }

@@ -464,7 +464,8 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
                z: Optional[torch.Tensor] = None, alpha: Optional[torch.Tensor] = None, fps: int = 15, sample_rate: int = 16000,
                want_windows: bool = False, want_aux: bool = False, mel=None, lengths=None, draws: Optional[int] = None,
                beat: bool = False, diversity=None, audio_rate: Optional[int] = None, joints=None, joints_mean=None,
-               joints_unit: bool = False, joints_fps=None, rotations=None, rotations_space: str = "local", smooth=None) -> Dict[str, torch.Tensor]:
+               joints_unit: bool = False, joints_fps=None, rotations=None, rotations_space: str = "local", smooth=None, euler=None,
+               euler_unwrap: bool = False) -> Dict[str, torch.Tensor]:
     """One gesture track per utterance from raw 16 kHz audio: windows -> mel -> optional CVAE sample per window -> roll-out.
 
     ``models = (generator, vae | None)``, eval mode, on the GPU.  ``audio [U, total_samples]``; ``text [U, W, 60]`` (the words of every
@@ -520,6 +521,13 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     (the tree's offsets are the bind pose).  With ``smooth=`` the filtered 6-D rows are re-orthonormalised by Gram-Schmidt on the way to the
     matrices: this is the sanctioned way to smooth rotations (there is no filter over quaternions).
 
+    ``euler=order | BvhFile`` (with ``joints=tree``): adds ``"euler"`` ``[U, (R,) T', J, 3]``, the BVH rotation channels of every joint in
+    degrees on the frames ``"joint_frames"`` counts: ``skeleton.euler_from_rot6d(track, tree, order, frames, joints_mean, joints_fps,
+    unwrap=euler_unwrap)``, one more launch (three more with ``euler_unwrap=True``, the Euler filter).  ``order``: one of XYZ .. ZYX for all
+    joints, or J of them; a ``bvh.BvhFile`` gives the orders of the tree's joints by name, and its ``format`` / ``write`` then turn one take
+    of ``out["euler"]`` into a ``.bvh`` text.  Made from ``"track_smooth"`` with ``smooth=``.  Refused by name: ``euler=`` without
+    ``joints=``, and with a ``Skeleton`` (direction-vector bodies have no joint rotations).
+
     ``smooth=Smoother | (window, polyorder)`` (``smooth.Smoother``; a pair is a filter at ``fps``): adds ``"track_smooth"``, the shape of
     ``"track"``: ``smooth.smooth_tracks(out["track"], smooth, frames)``, a Savitzky-Golay filter (``scipy.signal.savgol_filter``,
     ``mode="interp"``) over recording u's own valid poses, zeros behind them, one launch.  ``"track"`` stays raw and ``beat`` / ``diversity`` keep
@@ -527,7 +535,7 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     takes).  ``deriv != 0`` is refused by name: a velocity track is not a pose track -- call ``smooth_tracks`` for derivatives."""
     return _synthesize("synthesize", models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate,
                        want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, joints, joints_mean, joints_unit, joints_fps,
-                       rotations, rotations_space, smooth, takes=False)
+                       rotations, rotations_space, smooth, takes=False, euler=euler, euler_unwrap=euler_unwrap)
 
 
 def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch.Tensor, labels: Optional[torch.Tensor] = None, *,
@@ -535,7 +543,8 @@ def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose:
                      hop_samples: Optional[int] = None, n_samples: Optional[int] = None, fps: int = 15, sample_rate: int = 16000,
                      want_windows: bool = False, want_aux: bool = False, mel=None, beat: bool = False, diversity=None,
                      audio_rate: Optional[int] = None, joints=None, joints_mean=None, joints_unit: bool = False, joints_fps=None,
-                     rotations=None, rotations_space: str = "local", smooth=None) -> Dict[str, torch.Tensor]:
+                     rotations=None, rotations_space: str = "local", smooth=None, euler=None,
+                     euler_unwrap: bool = False) -> Dict[str, torch.Tensor]:
     """``draws`` = R sampled takes for each of U recordings of any and unequal length, from raw audio, in one call: ``synthesize(lengths=)`` and
     ``synthesize(draws=)`` combined (a VAE is required).  ``audio [U, max_total]`` with ``lengths[u]`` real samples in row u (``None``: every
     row at full length); recording u has ``W_u = ceil(lengths[u] / hop_samples)`` windows, N = sum W_u.  ``text`` padded ``[U, Wmax, 60]`` or
@@ -549,12 +558,12 @@ def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose:
     ``"track_smooth"`` ``[U, R, T, pose_dim]``."""
     return _synthesize("synthesize_takes", models, audio, text, seed_pose, labels, hop_samples, n_samples, None, z, alpha, fps, sample_rate,
                        want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, joints, joints_mean, joints_unit, joints_fps,
-                       rotations, rotations_space, smooth, takes=True)
+                       rotations, rotations_space, smooth, takes=True, euler=euler, euler_unwrap=euler_unwrap)
 
 
 def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate, want_windows, want_aux,
                 mel, lengths, draws, beat, diversity, audio_rate, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, smooth,
-                takes):
+                takes, euler=None, euler_unwrap=False):
     """The body of `synthesize` and `synthesize_takes` (`who` names the caller in errors): argument checks, resampling, the roll-out of the
     call's kind, then the per-track extras."""
     gen, vae = models
@@ -562,6 +571,7 @@ def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samp
     rotations = SK.output_args(who, seed_pose.shape[-1], joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space,
                                hint=" (the BEAT generators' 282 columns hold rotations, not bone direction vectors): their body is a "
                                     "skeleton.JointTree of 47 joints")
+    euler = SK.euler_args(who, joints, euler, euler_unwrap)
     if smooth is not None:
         from . import smooth as SM
         smooth = SM.Smoother.of(smooth, f"{who}: smooth", fps)
@@ -641,6 +651,8 @@ def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samp
                 out["joints"], out["joint_frames"] = SK.joints_from_tracks(poses, joints, unit=joints_unit, **kw)
                 if rotations is not None:
                     out["rotations"], _n = SK.rotations_from_tracks(poses, joints, rotations, space=rotations_space, **kw)
+            if euler is not None:                                                          # one more launch (and the unwrap's)
+                out["euler"], _n = SK.euler_from_rot6d(poses, joints, euler, unwrap=euler_unwrap, **kw)
     return out
 
 

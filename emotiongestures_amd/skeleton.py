@@ -43,6 +43,11 @@ one call describe the same pose (n = 1: every frame is frame 0).  Source frames 
 (``/ max(|q|, 1e-12)``), the first two rows (or columns) of its matrix as ``a1 | a2``, minus the mean; zeros from ``frames[u]`` on: the
 ``seed_pose`` a BEAT generator takes from motion capture.
 
+Euler channels (include/emogest.h: eg_articulate_euler / eg_articulate_rot6d_euler / eg_angle_unwrap).  ``euler_from_rot6d(track, tree, order)``
+gives the same ``R_j`` as the angles of a BVH file's rotation channels, ``[..., T_out, J, 3]``; ``rot6d_from_euler`` is the inverse and
+``unwrap_angles`` the Euler filter (whole turns only); their docstrings hold the definitions.  ``emotiongestures_amd.bvh`` reads and writes
+the files.
+
 CUDA tensors go through the kernels (fp32; there is no eager-PyTorch fallback for them).  numpy arrays and CPU tensors take the definition in
 float64 numpy -- what the reference's functions compute -- so data preparation and the drop-ins of ``utils.data_utils_expressive`` run without
 a GPU.
@@ -61,7 +66,8 @@ from ._host import BoundedCache, host_ptr, int_list, ptr as _ptr, stream as _str
 
 __all__ = ["Skeleton", "RestPose", "ted_expressive", "joints_from_tracks", "dir_vec_from_joints", "rotations_from_tracks", "out_frames",
            "rate_ratio", "TILE_FRAMES", "MAX_BONES", "MAX_FACTOR", "JointTree", "joints_from_rot6d", "rotations_from_rot6d",
-           "rot6d_from_rotations", "ARTICULATE_TILE_FRAMES", "MAX_JOINTS"]
+           "rot6d_from_rotations", "ARTICULATE_TILE_FRAMES", "MAX_JOINTS", "euler_from_rot6d", "rot6d_from_euler", "unwrap_angles", "launch_euler",
+           "launch_rot6d_euler", "launch_unwrap", "unwrap_workspace", "order_codes", "euler_args", "ORDERS", "UNWRAP_TILE_FRAMES"]
 
 TILE_FRAMES = L.EG_SKELETON_TILE_FRAMES      # output frames of one workgroup
 MAX_BONES = L.EG_SKELETON_MAX_BONES
@@ -882,6 +888,278 @@ def rot6d_from_rotations(quat, tree: JointTree, frames=None, mean=None):
     q = _host64(quat, who).reshape(U * R, T, tree.J, 4)
     d = _rot6d64(q, tree, _per_row(fr, U, R, T), _mean_host(mean, tree.pose_dim, who)).reshape(lead + (T, tree.pose_dim))
     return torch.from_numpy(d) if isinstance(quat, torch.Tensor) else d
+
+
+# ---- Euler channels of 6-D rotation tracks, their inverse, and the Euler filter ------------------------------------------------------------------
+ORDERS = ("XYZ", "XZY", "YXZ", "YZX", "ZXY", "ZYX")               # the order codes of include/emogest.h: i = code // 2, the others up / down
+UNWRAP_TILE_FRAMES = L.EG_UNWRAP_TILE_FRAMES
+
+
+def order_codes(order, J: int, who: str = "order") -> np.ndarray:
+    """One order string for all joints, or J strings -> int32 ``[J]`` codes.  Refuses by name an order that is no permutation of XYZ (one that
+    repeats an axis, like ``ZXZ``, is a proper Euler order, not a Tait-Bryan one: BVH rotation channels never have it)."""
+    names = [order] * J if isinstance(order, str) else list(order)
+    if len(names) != J:
+        raise L.EgError(f"{who}: {len(names)} orders for {J} joints (one string for all joints, or one per joint)")
+    codes = []
+    for j, o in enumerate(names):
+        o = str(o).upper()
+        if len(o) == 3 and set(o) <= set("XYZ") and len(set(o)) < 3:
+            raise L.EgError(f"{who}: joint {j}: order {o!r} repeats an axis; the six Tait-Bryan orders are {', '.join(ORDERS)}")
+        if o not in ORDERS:
+            raise L.EgError(f"{who}: joint {j}: order {o!r}: need one of {', '.join(ORDERS)}")
+        codes.append(ORDERS.index(o))
+    return np.array(codes, np.int32)
+
+
+def _axes(code: int) -> Tuple[int, int, int, float]:
+    i, j, k = ("XYZ".index(ch) for ch in ORDERS[int(code)])
+    return i, j, k, (1.0 if j == (i + 1) % 3 else -1.0)
+
+
+def _euler_of_matrices64(R: np.ndarray, codes: np.ndarray) -> np.ndarray:
+    """R [..., J, 3, 3] -> (a, b, c) [..., J, 3] in radians: the definition of include/emogest.h in float64."""
+    out = np.zeros(R.shape[:-2] + (3,))
+    for jt, code in enumerate(codes):
+        i, j, k, eps = _axes(code)
+        m = R[..., jt, :, :]
+        s = eps * m[..., i, k]
+        lock = 1.0 - np.abs(s) < 2.0 ** -20
+        out[..., jt, 1] = np.arctan2(s, np.sqrt(m[..., i, i] ** 2 + m[..., i, j] ** 2))
+        out[..., jt, 0] = np.where(lock, np.arctan2(eps * m[..., k, j], m[..., j, j]), np.arctan2(-eps * m[..., j, k], m[..., k, k]))
+        out[..., jt, 2] = np.where(lock, 0.0, np.arctan2(-eps * m[..., i, j], m[..., i, i]))
+    return out
+
+
+def _axis_rotation64(axis: int, th: np.ndarray) -> np.ndarray:
+    c, s = np.cos(th), np.sin(th)
+    m = np.zeros(th.shape + (3, 3))
+    u, v = (axis + 1) % 3, (axis + 2) % 3
+    m[..., axis, axis] = 1.0
+    m[..., u, u], m[..., u, v], m[..., v, u], m[..., v, v] = c, -s, s, c
+    return m
+
+
+def _matrices_of_euler64(e: np.ndarray, codes: np.ndarray) -> np.ndarray:
+    """(a, b, c) [..., J, 3] in radians -> R = R_i(a) R_j(b) R_k(c) [..., J, 3, 3]."""
+    R = np.zeros(e.shape[:-1] + (3, 3))
+    for jt, code in enumerate(codes):
+        i, j, k, _eps = _axes(code)
+        R[..., jt, :, :] = _axis_rotation64(i, e[..., jt, 0]) @ _axis_rotation64(j, e[..., jt, 1]) @ _axis_rotation64(k, e[..., jt, 2])
+    return R
+
+
+def _unwrap64(p: np.ndarray, frames: List[int], period: float) -> np.ndarray:
+    """p [B, T, C] float64 -> the definition in float64: ``out_t = p_t - c_t P``; frames from ``frames[b]`` on stay as they are."""
+    out = np.array(p, np.float64)
+    for b, n in enumerate(frames):
+        if n > 1:
+            k = np.rint(np.diff(out[b, :n], axis=0) / period)
+            out[b, 1:n] -= np.cumsum(k, axis=0) * period
+    return out
+
+
+def _euler64(v: np.ndarray, tree: JointTree, codes: np.ndarray, frames: List[int], mean, Lf: int, M: int, degrees: bool) -> np.ndarray:
+    """v [B, T, 6J] float64 -> [B, T_out, J, 3]."""
+    B, T, _D = v.shape
+    J = tree.J
+    out = np.zeros((B, -(-T * Lf // M), J, 3))
+    for b in range(B):
+        n = frames[b]
+        if n < 1:
+            continue
+        x = v[b, :n].reshape(n, J, 6)
+        if mean is not None:
+            x = x + mean.reshape(J, 6)
+        n_out = -(-n * Lf // M)
+        e = _euler_of_matrices64(_rot6d_matrices64(_resample64(x, n_out, Lf, M), tree.basis == "columns"), codes)
+        out[b, :n_out] = np.degrees(e) if degrees else e
+    return out
+
+
+class _Orders:
+    """The order codes of a call on the host and, once per device, on the device."""
+    _cache = BoundedCache(64)
+
+    @classmethod
+    def get(cls, order, J: int, who: str):
+        codes = order_codes(order, J, who)
+        return cls._cache.get(codes.tobytes(), lambda: SimpleNamespace(codes=codes, dev=BoundedCache()))
+
+    @staticmethod
+    def table(entry, device) -> torch.Tensor:
+        return entry.dev.get(str(device), lambda: torch.from_numpy(entry.codes).to(device))
+
+
+def launch_euler(track: torch.Tensor, tree: JointTree, order, d_frames: Optional[torch.Tensor] = None, draws: int = 1, frame_unit: int = 1,
+                 mean: Optional[torch.Tensor] = None, ratio: Tuple[int, int] = (1, 1), degrees: bool = True,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """eg_articulate_euler on ``track [B, T, 6J]`` (contiguous fp32 CUDA, 16-byte aligned) -> ``[B, T_out, J, 3]``: one launch on the current
+    stream, nothing else (the order codes are uploaded on first use per device: warm up before a capture).  The other arguments as in
+    ``launch_articulate``."""
+    B, T, D = track.shape
+    if D != tree.pose_dim:
+        raise L.EgError(f"launch_euler: a tree of {tree.J} joints takes tracks of {tree.pose_dim} columns, got {D}")
+    Lf, M = ratio
+    if out is None:
+        out = torch.empty((B, -(-T * Lf // M), tree.J, 3), dtype=torch.float32, device=track.device)
+    o = _Orders.get(order, tree.J, "launch_euler: order")
+    L.check(L.load().eg_articulate_euler(_ptr(track), B, T, tree.J, host_ptr(o.codes), _ptr(_Orders.table(o, track.device)), _ptr(d_frames),
+                                         int(draws), int(frame_unit), _ptr(mean), tree.basis_code, int(bool(degrees)), Lf, M, _ptr(out),
+                                         out.shape[1], _stream(track.device)), "eg_articulate_euler")
+    return out
+
+
+def launch_rot6d_euler(euler: torch.Tensor, tree: JointTree, order, d_frames: Optional[torch.Tensor] = None, draws: int = 1,
+                       frame_unit: int = 1, mean: Optional[torch.Tensor] = None, degrees: bool = True,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """eg_articulate_rot6d_euler on ``euler [B, T, J, 3]`` -> ``[B, T, 6J]``: one launch on the current stream."""
+    B, T = euler.shape[:2]
+    if out is None:
+        out = torch.empty(B, T, tree.pose_dim, dtype=torch.float32, device=euler.device)
+    o = _Orders.get(order, tree.J, "launch_rot6d_euler: order")
+    L.check(L.load().eg_articulate_rot6d_euler(_ptr(euler), B, T, tree.J, host_ptr(o.codes), _ptr(_Orders.table(o, euler.device)),
+                                               _ptr(d_frames), int(draws), int(frame_unit), _ptr(mean), tree.basis_code, int(bool(degrees)),
+                                               _ptr(out), _stream(euler.device)), "eg_articulate_rot6d_euler")
+    return out
+
+
+def unwrap_workspace(rows: int, T: int, C: int, device) -> Optional[torch.Tensor]:
+    """The workspace ``launch_unwrap`` takes for ``[rows, T, C]``; None where the track fits one tile and none is needed."""
+    if T <= UNWRAP_TILE_FRAMES:
+        return None
+    need = int(L.load().eg_angle_unwrap_workspace_bytes(int(rows), int(T), int(C)))
+    if need <= 0:
+        L.check(1, "eg_angle_unwrap_workspace_bytes")
+    return torch.empty(need // 4, dtype=torch.int32, device=device)
+
+
+def launch_unwrap(angles: torch.Tensor, d_frames: Optional[torch.Tensor] = None, draws: int = 1, frame_unit: int = 1, period: float = 360.0,
+                  workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """eg_angle_unwrap on ``angles [B, T, C]`` (contiguous fp32 CUDA), in place: up to three launches on the current stream, nothing else
+    when ``workspace`` (``unwrap_workspace``) is given; without it one is allocated here."""
+    B, T, Cc = angles.shape
+    if workspace is None:
+        workspace = unwrap_workspace(B, T, Cc, angles.device)
+    L.check(L.load().eg_angle_unwrap(_ptr(angles), B, T, Cc, _ptr(d_frames), int(draws), int(frame_unit), float(period), _ptr(workspace),
+                                     0 if workspace is None else workspace.numel() * 4, _stream(angles.device)), "eg_angle_unwrap")
+    return angles
+
+
+def _period_checked(period, who: str) -> float:
+    p = float(period)
+    if not (math.isfinite(p) and p > 0.0 and math.isfinite(float(np.float32(p))) and float(np.float32(p)) > 0.0):
+        raise L.EgError(f"{who}: period={period!r} (need finite and > 0)")
+    return p
+
+
+def euler_from_rot6d(track, tree: JointTree, order, frames=None, mean=None, fps=None, degrees: bool = True, unwrap: bool = False):
+    """``track [..., T, 6J]`` with up to two leading axes -> ``euler [..., T_out, J, 3]``: the angles ``(a, b, c)`` of every joint's rotation
+    ``R_j = R_i(a) R_j(b) R_k(c)`` relative to its parent, in the order of the joint's BVH rotation channels, in degrees (``degrees=False``:
+    radians).  ``order``: one of XYZ, XZY, YXZ, YZX, ZXY, ZYX for all joints, or J of them; ``CHANNELS 3 Zrotation Xrotation Yrotation`` is
+    ``"ZXY"``.  With ``eps = +1`` for XYZ, YZX, ZXY and ``-1`` for the others: ``s = eps R[i][k]``, ``b = atan2(s, sqrt(R[i][i]^2 +
+    R[i][j]^2))`` in ``[-90, 90]``; ``a = atan2(-eps R[j][k], R[k][k])``, ``c = atan2(-eps R[i][j], R[i][i])`` while ``1 - |s| >= 2^-20``;
+    at the lock ``a = atan2(eps R[k][j], R[j][j])``, ``c = 0``.  ``R_j`` is ``joints_from_rot6d``'s (mean, blend of the 6-D vectors with
+    ``fps``, Gram-Schmidt, ``tree.basis``), so the angles, the quaternions and the joints of the same arguments describe one pose.
+    ``unwrap=True`` then runs ``unwrap_angles`` over the result: whole turns are taken out along time.  Only whole turns: the middle angle
+    stays in ``[-90, 90]`` by definition, so the other Euler triple of a rotation is never chosen and ``a`` / ``c`` still jump by 180 degrees
+    where a joint passes through the lock.  A CUDA tensor: one launch (plus the unwrap launches), fp32; numpy or a CPU tensor: float64.
+    With ``frames`` or ``fps`` the result is ``(euler, joint_frames)``; zeros from ``joint_frames[u]`` on."""
+    who = "euler_from_rot6d"
+    tree = _tree_checked(track, tree, who)
+    o = _Orders.get(order, tree.J, f"{who}: order")
+    fe = _front(track, tree, frames, fps, who)
+    period = 360.0 if degrees else 2.0 * math.pi
+    if _is_cuda(track):
+        x = _dev32(track).reshape(fe.U * fe.R, fe.T, tree.pose_dim)
+        res = launch_euler(x, tree, order, _frames_dev(fe.fr, x.device), fe.R, 1, _mean_dev(mean, tree.pose_dim, x.device, who), fe.ratio, degrees)
+        if unwrap:
+            launch_unwrap(res.view(fe.U * fe.R, fe.t_out, 3 * tree.J), _frames_dev(fe.n_out if fe.fr is not None else None, x.device), fe.R, 1, period)
+    else:
+        v = _host64(track, who).reshape(fe.U * fe.R, fe.T, tree.pose_dim)
+        res = _euler64(v, tree, o.codes, fe.per_row, _mean_host(mean, tree.pose_dim, who), *fe.ratio, degrees)
+        if unwrap:
+            n_rows = [n for n in fe.n_out for _ in range(fe.R)]
+            res = _unwrap64(res.reshape(fe.U * fe.R, fe.t_out, 3 * tree.J), n_rows, period)
+    return _finish(res, track, fe, (tree.J, 3), frames, fps)
+
+
+def rot6d_from_euler(euler, tree: JointTree, order, frames=None, mean=None, degrees: bool = True):
+    """``euler [..., T, J, 3]`` (up to two leading axes; degrees unless ``degrees=False``) -> ``rot6d [..., T, 6J]``: ``R = R_i(a) R_j(b)
+    R_k(c)`` for the joint's ``order``, its first two rows (``basis="rows"``) or columns as ``a1 | a2``, minus ``mean [6J]`` when given:
+    the ``seed_pose`` or the target track of a BEAT generator from a BVH file's channels.  Zeros from ``frames[u]`` on.  CUDA in: the
+    kernel, fp32; numpy / CPU in: float64."""
+    who = "rot6d_from_euler"
+    if not isinstance(tree, JointTree):
+        raise L.EgError(f"{who}: tree must be a JointTree, got {type(tree).__name__}")
+    shape = tuple(euler.shape)
+    if len(shape) < 3 or shape[-2:] != (tree.J, 3) or shape[-3] < 1:
+        raise L.EgError(f"{who}: euler shape {shape}: need [..., T >= 1, {tree.J}, 3] for a tree of {tree.J} joints")
+    o = _Orders.get(order, tree.J, f"{who}: order")
+    lead, U, R = _lead(shape, 3, who)
+    T = shape[-3]
+    fr = _frames_list(frames, U, T, who)
+    if _is_cuda(euler):
+        e = _dev32(euler).reshape(U * R, T, tree.J, 3)
+        return launch_rot6d_euler(e, tree, order, _frames_dev(fr, e.device), R, 1, _mean_dev(mean, tree.pose_dim, e.device, who),
+                                  degrees).reshape(lead + (T, tree.pose_dim))
+    e = _host64(euler, who).reshape(U * R, T, tree.J, 3)
+    mh = _mean_host(mean, tree.pose_dim, who)
+    d = np.zeros((U * R, T, tree.pose_dim))
+    for b, n in enumerate(_per_row(fr, U, R, T)):
+        if n < 1:
+            continue
+        m = _matrices_of_euler64(np.radians(e[b, :n]) if degrees else e[b, :n], o.codes)
+        if tree.basis == "columns":
+            m = np.swapaxes(m, -1, -2)
+        d[b, :n] = m[..., :2, :].reshape(n, tree.pose_dim) - (0.0 if mh is None else mh)
+    d = d.reshape(lead + (T, tree.pose_dim))
+    return torch.from_numpy(d) if isinstance(euler, torch.Tensor) else d
+
+
+def unwrap_angles(angles, frames=None, period: float = 360.0):
+    """The Euler filter on ``angles [..., T, C]`` (up to two leading axes; flatten ``[T, J, 3]`` to ``[T, 3J]`` first): every (row, column)
+    series loses its whole-period jumps: ``k_t = nearbyint((p_t - p_(t-1)) / period)``, ``out_t = p_t - period (k_1 + .. + k_t)``:
+    ``np.unwrap`` on tie-free input.  ``frames``: valid frames per recording; the rest stays as it is.  Returns a new tensor or array.
+    CUDA in: fp32 on the device (the differences in fp32, the quotient in float64, ``fmaf(-c_t, period, p_t)``; up to three launches);
+    numpy / CPU in: float64.  Only whole periods are removed: see ``euler_from_rot6d``."""
+    who = "unwrap_angles"
+    period = _period_checked(period, who)
+    shape = tuple(angles.shape)
+    if len(shape) < 2 or shape[-2] < 1 or shape[-1] < 1:
+        raise L.EgError(f"{who}: angles shape {shape}: need [..., T >= 1, C >= 1]")
+    lead, U, R = _lead(shape, 2, who)
+    T, Cc = shape[-2], shape[-1]
+    fr = _frames_list(frames, U, T, who)
+    if _is_cuda(angles):
+        a = angles.detach().to(torch.float32).reshape(U * R, T, Cc).clone()
+        return launch_unwrap(a, _frames_dev(fr, a.device), R, 1, period).reshape(shape)
+    out = _unwrap64(_host64(angles, who).reshape(U * R, T, Cc), _per_row(fr, U, R, T), period).reshape(shape)
+    return torch.from_numpy(out) if isinstance(angles, torch.Tensor) else out
+
+
+def euler_args(who: str, joints, euler, euler_unwrap: bool = False, unwrap_allowed: bool = True):
+    """The ``euler=`` / ``euler_unwrap=`` arguments of a caller, checked before anything runs: the J order strings, or None.  ``euler``: an
+    order for all joints, J orders, or a ``bvh.BvhFile`` (the orders of the tree's joints, by name)."""
+    if euler is None:
+        if euler_unwrap:
+            raise L.EgError(f"{who}: euler_unwrap=True without euler=order")
+        return None
+    if not unwrap_allowed and euler_unwrap:
+        raise L.EgError(f"{who}: euler_unwrap=True is not supported (a stream emits principal values: a whole turn is only known against the "
+                        "frames before it); unwrap the finished track with skeleton.unwrap_angles")
+    if joints is None:
+        raise L.EgError(f"{who}: euler= without joints=tree (the angles belong to a JointTree's joints)")
+    if isinstance(joints, Skeleton):
+        raise L.EgError(f"{who}: euler= with joints=Skeleton: direction-vector bodies have no joint rotations (Euler channels need a "
+                        "skeleton.JointTree and a generator of 6-D rotations)")
+    if not isinstance(joints, JointTree):
+        raise L.EgError(f"{who}: euler= needs joints=JointTree, got {type(joints).__name__}")
+    if callable(getattr(euler, "orders", None)):                                   # a bvh.BvhFile
+        if joints.names is None:
+            raise L.EgError(f"{who}: euler=BvhFile needs a tree with joint names (BvhFile.tree(...))")
+        euler = euler.orders(joints.names)
+    return [ORDERS[c] for c in order_codes(euler, joints.J, f"{who}: euler")]
 
 
 def _output_args_early(who: str, joints, joints_fps, rotations, fps_allowed: bool = True) -> None:

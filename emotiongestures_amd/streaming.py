@@ -159,6 +159,10 @@ class GestureStream:
     `joints=tree` (a skeleton.JointTree with 6J == pose_dim: the BEAT generators' 6-D joint rotations; `rotations=True` for the rotations too):
     ONE more launch inside the graph fills `last_joints [U, H, J, 3]` and `last_rotations [U, H, J, 4]` under the same rules, and
     `tail_joints()` / `tail_rotations()` work likewise; `joints_unit` and a rest pose are refused by name.
+    `euler=order | BvhFile` (with `joints=tree`; as in harness.synthesize): one more launch inside the graph leaves the BVH rotation channels of
+    the rows just emitted in `last_euler [U, H, J, 3]` (degrees, principal values) under the same rules; `tail_euler()`: those of `tail()`.  A
+    row's `last_euler` followed by its `tail_euler()` are skeleton.euler_from_rot6d on its finished track bit for bit.  `euler_unwrap=True` is
+    refused by name: unwrap the finished track (skeleton.unwrap_angles).
     `smooth=Smoother | (window, polyorder)` (smooth.Smoother, deriv 0, window <= H): every step ends with the two launches of a
     smooth.StreamSmoother (inside the graph) that leave in `last_smooth [U, H, D]` the smoothed frames `[sH - half, (s + 1)H - half)` of a row in
     its s-th valid step -- `smooth_delay = half` frames behind the rows just emitted, the first `half` entries of step 0 zeros; zeros for a row
@@ -170,8 +174,11 @@ class GestureStream:
     def __init__(self, models: Tuple, rows: int, seed_pose: torch.Tensor, *, hop_samples: Optional[int] = None, n_samples: Optional[int] = None,
                  fps: int = 15, sample_rate: int = 16000, alpha: Optional[torch.Tensor] = None, graph: bool = True, want_windows: bool = False,
                  draws: Optional[int] = None, audio_rate: Optional[int] = None, joints=None, joints_mean=None, joints_unit: bool = False,
-                 joints_fps=None, rotations=None, rotations_space: str = "local", smooth=None):
+                 joints_fps=None, rotations=None, rotations_space: str = "local", smooth=None, euler=None, euler_unwrap: bool = False):
         SK._output_args_early("GestureStream", joints, joints_fps, rotations, fps_allowed=False)
+        # the order table is held here: the captured graph replays the address of its device copy
+        self._euler = SK.euler_args("GestureStream", joints, euler, euler_unwrap, unwrap_allowed=False)
+        self._euler_hold = None if self._euler is None else SK._Orders.get(self._euler, joints.J, "GestureStream: euler")
         if smooth is not None:
             if joints is not None:
                 raise L.EgError("GestureStream: smooth= together with joints= is not supported (the smoothed rows run half a window behind and "
@@ -256,6 +263,7 @@ class GestureStream:
         self.last_window: Optional[torch.Tensor] = None          # with want_windows: the raw poses [U, F, D] of the last step
         self.last_joints: Optional[torch.Tensor] = None          # with joints=: the joints [U, H, J, 3] of the rows just emitted (zeros for a row that was not valid)
         self.last_rotations: Optional[torch.Tensor] = None       # with rotations=: their bone rotations [U, H, K, 4], under the same rules
+        self.last_euler: Optional[torch.Tensor] = None           # with euler=: their Euler channels [U, H, J, 3] in degrees (principal values), likewise
         self.last_smooth: Optional[torch.Tensor] = None          # with smooth=: the smoothed frames [U, H, D], smooth_delay frames behind the rows
         eng.stream_reset(self._state, *self._geom, self.seed_pose)
 
@@ -317,6 +325,8 @@ class GestureStream:
                 out["joints"] = SK.launch_joints(out["rows"], self._sk, out["valid"], 1, self.H, self._sk_mean, self._sk_unit)
             if self._rest is not None and not self._tree:
                 out["rotations"] = SK.launch_rotations(out["rows"], self._sk, self._rest, out["valid"], 1, self.H, self._sk_mean, self._rot_space)
+            if self._euler is not None:             # one more launch: the Euler channels of the rows just emitted
+                out["euler"] = SK.launch_euler(out["rows"], self._sk, self._euler, out["valid"], 1, self.H, self._sk_mean)
             if self._sm is not None:                # the outputs, then the new history in a launch of its own
                 out["smooth"] = self._sm.run(out["rows"], out["valid"])
             return out
@@ -451,6 +461,7 @@ class GestureStream:
         self.last_window = out["window"].clone() if out is not None and self.want_windows else None
         self.last_joints = out["joints"].clone() if out is not None and self._sk is not None else None
         self.last_rotations = out["rotations"].clone() if out is not None and self._rest is not None else None
+        self.last_euler = out["euler"].clone() if out is not None and self._euler is not None else None
         self.last_smooth = out["smooth"].clone() if out is not None and self._sm is not None else None
         if out is None:
             return None, torch.zeros(self.U, dtype=torch.int32, device=self.device)
@@ -525,6 +536,13 @@ class GestureStream:
             if self._tree:
                 return SK.launch_articulate(self.tail(), self._sk, None, 1, 1, self._sk_mean, self._rot_space, joints=False)[1]
             return SK.launch_rotations(self.tail(), self._sk, self._rest, None, 1, 1, self._sk_mean, self._rot_space)
+
+    def tail_euler(self) -> torch.Tensor:
+        """[U, P, J, 3]: the Euler channels of `tail()` in degrees (a session opened with euler=)."""
+        if self._euler is None:
+            raise L.EgError("tail_euler: the session was opened without euler=order")
+        with torch.no_grad():
+            return SK.launch_euler(self.tail(), self._sk, self._euler, None, 1, 1, self._sk_mean)
 
     def tail_smooth(self) -> torch.Tensor:
         """[U, P + smooth_delay, D]: the last smoothed frames of every row's track (a session opened with smooth=); zeros for a row that has

@@ -634,6 +634,49 @@ int eg_articulate_forward(const float* track, int32_t rows, int32_t T, const int
 int eg_articulate_rot6d(const float* quat, int32_t rows, int32_t T, int32_t joints, const int32_t* d_frames, int32_t draws,
                         int32_t frame_unit, const float* d_mean, int32_t basis, float* rot6d, void* stream);
 
+/* Euler channels of 6-D rotation tracks (BVH's rotation channels), their inverse, and the Euler filter (csrc/skeleton.hip, csrc/euler.hip).
+ * Order.  A joint's channel order is a permutation (i, j, k) of the axes X, Y, Z, as a code: XYZ 0, XZY 1, YXZ 2, YZX 3, ZXY 4, ZYX 5
+ * (i = code / 2; the other two ascending for an even code, descending for an odd one).  `Zrotation Xrotation Yrotation` is ZXY and means
+ * R = Rz(a) Rx(b) Ry(c) with v_parent = R v_local: the R_j of eg_articulate_forward.  eps = +1 for XYZ, YZX, ZXY and -1 for XZY, YXZ, ZYX.
+ * eg_articulate_euler: track [rows, T, 6J] -> euler [rows, out_stride, J, 3].  R_j from the six numbers exactly as in eg_articulate_forward
+ * (d_mean, the blend of the 6-D vectors at L / M != 1, Gram-Schmidt, basis), then in fp32 with the library's sqrtf / atan2f:
+ *     s = eps R[i][k];   h = sqrt(R[i][i]^2 + R[i][j]^2);   b = atan2(s, h)                       (b in [-pi/2, pi/2])
+ *     1 - |s| >= 2^-20:  a = atan2(-eps R[j][k], R[k][k]);  c = atan2(-eps R[i][j], R[i][i])
+ *     otherwise (lock):  a = atan2( eps R[k][j], R[j][j]);  c = 0
+ * The output holds (a, b, c), the order of the joint's rotation channels, in radians, or with degrees != 0 each times (float)(180 / pi).
+ * No tree is involved: one thread per (output frame, joint), no level barriers, a tile of EG_ARTICULATE_TILE_FRAMES output frames per
+ * workgroup.  rows, d_frames, draws, frame_unit, L / M, out_stride: as in eg_articulate_forward; frames k' >= n_out are zeros; source
+ * frames t >= n are never read and may hold NaN; a degenerate group gives finite angles.  orders: the J codes on the host (checked);
+ * d_orders: the same on the device (clamped to 0..5 where they differ).
+ * eg_articulate_rot6d_euler: euler [rows, T, J, 3] -> rot6d [rows, T, 6J]: the angles (times (float)(pi / 180) with degrees != 0), the
+ * library's sincosf, R = R_i(a) R_j(b) R_k(c) in closed form -- with (sa, sb, sc) the sines times eps and p(.) the place of an axis in the
+ * order, R[r][c] = m[p(r)][p(c)] of
+ *     m = | cb cc, -cb sc, sb |  | sa sb cc + ca sc, ca cc - sa sb sc, -sa cb |  | sa sc - ca sb cc, sa cc + ca sb sc, ca cb |
+ * -- its first two rows (basis rows) or columns as a1 | a2, minus d_mean when given; zeros from frame n on.
+ * Both: caller-owned memory, no allocation, no synchronisation, one launch, capturable; one owning thread per output element, no atomics.
+ * Refuse by name before the launch: null pointers, joints outside 1 .. EG_ARTICULATE_MAX_JOINTS, an order code outside 0..5, pointers not
+ * 16-byte aligned (d_orders / d_mean: 4-byte), rows or T < 1, rows not a multiple of draws, frame_unit < 1, an unknown basis, an
+ * unsupported ratio, a short out_stride, grid / index range.
+ * eg_angle_unwrap: angles [rows, T, C] fp32, in place; row b has n valid frames as above; every (row, column) is a series p_0 .. p_(n-1):
+ *     d_t = p_t - p_(t-1) in fp32;   k_t = nearbyint((double)d_t / period) (ties to even), k_0 = 0;   c_t = k_0 + .. + k_t, a 32-bit integer;
+ *     out_t = fmaf(-(float)c_t, (float)period, p_t).
+ * Frames t >= n are neither read nor written.  The input is finite and its jumps sum to less than 2^31 periods.  Integer counts make the
+ * result independent of the tiling: a tile is EG_UNWRAP_TILE_FRAMES frames; per-tile totals, their scan per row and column, then the
+ * pass that writes -- three launches, one when T fits a tile; no atomics.  workspace: eg_angle_unwrap_workspace_bytes bytes
+ * of device memory (0 for refused arguments), 4-byte aligned, not read or written when T fits a tile (then it may be NULL).  Capturable.
+ * Refuses by name: null angles, rows / T / C < 1, rows not a multiple of draws, frame_unit < 1, a period that is not finite and > 0 in
+ * fp32, a missing or short workspace, grid / index range. */
+#define EG_UNWRAP_TILE_FRAMES 64
+int eg_articulate_euler(const float* track, int32_t rows, int32_t T, int32_t joints, const int32_t* orders, const void* d_orders,
+                        const int32_t* d_frames, int32_t draws, int32_t frame_unit, const float* d_mean, int32_t basis, int32_t degrees,
+                        int32_t L, int32_t M, float* euler, int64_t out_stride, void* stream);
+int eg_articulate_rot6d_euler(const float* euler, int32_t rows, int32_t T, int32_t joints, const int32_t* orders, const void* d_orders,
+                              const int32_t* d_frames, int32_t draws, int32_t frame_unit, const float* d_mean, int32_t basis,
+                              int32_t degrees, float* rot6d, void* stream);
+int64_t eg_angle_unwrap_workspace_bytes(int32_t rows, int32_t T, int32_t C);
+int eg_angle_unwrap(float* angles, int32_t rows, int32_t T, int32_t C, const int32_t* d_frames, int32_t draws, int32_t frame_unit,
+                    double period, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Smoothed output: a Savitzky-Golay filter along the time axis of whole tracks on the device (csrc/smooth.hip)
  * ------------------------------------------------------------------------------------------ */

@@ -23,7 +23,10 @@ skeleton.JointTree -- the BEAT columns are one 6-D rotation per joint -- read fr
 synthetic 47-joint upper body without --bvh: ONE more launch inside the graph leaves stream.last_joints [U, 50, 47, 3] and, with --rotations,
 stream.last_rotations [U, 50, 47, 4] (local joint rotations; there is no rest pose); the script prints how far the deepest joint travels and the
 largest rotation angle per push.
-usage: demo_stream.py [rows=4] [seconds=20] [--beat] [--audio-rate HZ] [--joints [--bvh FILE] [--rotations]] [--smooth K P]"""
+With --euler (and --beat --joints) the stream also gets euler= -- the channel orders of --bvh FILE, or ZXY for every joint -- and one more launch
+inside the graph leaves the BVH rotation channels of the rows just emitted in stream.last_euler [U, 50, 47, 3] (degrees, principal values: the
+Euler filter runs on a finished track, skeleton.unwrap_angles); the script prints the largest angle per push.
+usage: demo_stream.py [rows=4] [seconds=20] [--beat] [--audio-rate HZ] [--joints [--bvh FILE] [--rotations] [--euler]] [--smooth K P]"""
 import os
 import sys
 import time
@@ -61,10 +64,16 @@ if JOINTS and BEAT:
     sys.argv.remove("--joints")
     TREE = SK_.JointTree.from_bvh(open(BVH).read()) if BVH else synthetic_tree(SK_)
     JK = dict(joints=TREE)
+    if "--euler" in sys.argv:
+        from emotiongestures_amd import bvh as BVH_
+        sys.argv.remove("--euler")
+        JK["euler"] = BVH_.read(BVH) if BVH else "ZXY"
 elif JOINTS:
     from emotiongestures_amd.skeleton import ted_expressive
     sys.argv.remove("--joints")
     JK = dict(joints=ted_expressive(), joints_unit=True)
+if "--euler" in sys.argv:
+    sys.exit("--euler needs --beat --joints (Euler channels are the rotations of a JointTree's joints)")
 ROTATIONS = "--rotations" in sys.argv
 if ROTATIONS:
     sys.argv.remove("--rotations")
@@ -153,6 +162,10 @@ for k in range(1, steps + 1):
             q = stream.last_rotations[valid.bool()]             # a row that was not valid holds zeros, not rotations
             print(f"         last_rotations {tuple(q.shape)}: largest local rotation "
                   f"{float(torch.rad2deg(2 * torch.acos(q[..., 0].clamp(max=1.0))).max()):.1f} degrees")
+        if stream.last_euler is not None:
+            e = stream.last_euler
+            print(f"         last_euler {tuple(e.shape)}: largest channel {float(e.abs().max()):.1f} degrees, middle angles within "
+                  f"{float(e[..., 1].abs().max()):.1f}")
     elif JOINTS and stream.last_joints is not None:
         j = stream.last_joints
         ext = [float((j[:, :, w].amax(1) - j[:, :, w].amin(1)).norm(dim=1).max()) for w in (6, 7)]

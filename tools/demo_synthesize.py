@@ -30,7 +30,10 @@ With --beat --joints the body is a skeleton.JointTree -- the BEAT columns are on
 --bvh FILE (which must have 47 joints, or name them with --bvh-joints A,B,...), or a synthetic 47-joint upper body without --bvh: joint
 positions and, with --rotations, one local rotation per joint come from ONE more launch (skeleton.launch_articulate), and the script prints their
 shapes, how far the deepest joint travels and the largest rotation angle.
-usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--bvh FILE [--bvh-joints A,B,...]] [--joints-fps N] [--rotations]] [--smooth K P] [--out tracks.npz]"""
+With --bvh FILE --bvh-out DIR the call also returns the Euler channels of every joint in the file's own channel orders (euler=BvhFile,
+euler_unwrap=True: one more launch and the Euler filter's three) and the script writes DIR/recording_U[_take_R].bvh -- the file's HIERARCHY,
+then the generated MOTION at the joints' frame rate -- one file per recording and take, formatted on the host (bvh.BvhFile.write).
+usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--bvh FILE [--bvh-joints A,B,...] [--bvh-out DIR]] [--joints-fps N] [--rotations]] [--smooth K P] [--out tracks.npz]"""
 import os
 import sys
 import time
@@ -46,7 +49,7 @@ from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
 from emotiongestures_amd.synth import load_synth_weights, synth_audio
 
 argv, DRAWS, OUT, BEAT, DIVERSITY, RATE, JOINTS, JOINTS_FPS, ROTATIONS, SMOOTH = [], 0, None, False, False, 16000, False, None, False, None
-BVH, BVH_JOINTS = None, None
+BVH, BVH_JOINTS, BVH_OUT = None, None, None
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--draws":
@@ -69,6 +72,8 @@ for a in it:
         BVH = next(it)
     elif a == "--bvh-joints":
         BVH_JOINTS = next(it).split(",")
+    elif a == "--bvh-out":
+        BVH_OUT = next(it)
     elif a == "--smooth":
         SMOOTH = (int(next(it)), int(next(it)))
     else:
@@ -77,6 +82,8 @@ if DIVERSITY and DRAWS < 2:
     sys.exit("--diversity needs --draws R with R >= 2 (the take diversity is a distance between the takes of one recording)")
 if BVH and not (JOINTS and BEAT):
     sys.exit("--bvh needs --beat --joints (a BVH hierarchy is the body of the BEAT generators' 6-D joint rotations)")
+if BVH_OUT and not BVH:
+    sys.exit("--bvh-out needs --bvh FILE (the written files repeat that file's HIERARCHY)")
 if JOINTS_FPS and not JOINTS:
     sys.exit("--joints-fps needs --joints")
 if ROTATIONS and not JOINTS:
@@ -127,6 +134,10 @@ if JOINTS and BEAT:
     import emotiongestures_amd.skeleton as SK_
     tree = JointTree.from_bvh(open(BVH).read(), joints=BVH_JOINTS) if BVH else synthetic_tree(SK_)
     jk = dict(joints=tree, joints_fps=(FPS, JOINTS_FPS) if JOINTS_FPS else None, smooth=SMOOTH, rotations=True if ROTATIONS else None)
+    if BVH_OUT:
+        from emotiongestures_amd import bvh as BVH_
+        bvh_file = BVH_.read(BVH)
+        jk.update(euler=bvh_file, euler_unwrap=True)
     H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, **jk, **AR)          # warm-up (uploads the level table)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -146,6 +157,18 @@ if JOINTS and BEAT:
         rot = jo["rotations"]
         print(f"--rotations: rotations {tuple(rot.shape)} from the same launch; largest local rotation: "
               f"{float(torch.rad2deg(2 * torch.acos(rot[..., 0].clamp(max=1.0))).max()):.1f} degrees")
+    if BVH_OUT:
+        os.makedirs(BVH_OUT, exist_ok=True)
+        eul = jo["euler"]
+        takes = eul if eul.dim() == 5 else eul[:, None]                  # [U, R, T', J, 3]
+        t0 = time.perf_counter()
+        for u in range(takes.shape[0]):
+            for r in range(takes.shape[1]):
+                name = f"recording_{u}" + (f"_take_{r}" if eul.dim() == 5 else "") + ".bvh"
+                bvh_file.write(os.path.join(BVH_OUT, name), takes[u, r, :jo["joint_frames"][u]], joints=tree.names,
+                               frame_time=1.0 / (JOINTS_FPS or FPS))
+        print(f"--bvh-out: euler {tuple(eul.shape)} in the orders of {BVH} (unwrapped), {takes.shape[0] * takes.shape[1]} files in {BVH_OUT} "
+              f"formatted on the host in {time.perf_counter() - t0:.2f} s")
 elif JOINTS:
     from emotiongestures_amd.skeleton import ted_expressive
     jk = dict(joints=ted_expressive(), joints_unit=True, joints_fps=(FPS, JOINTS_FPS) if JOINTS_FPS else None, smooth=SMOOTH)
