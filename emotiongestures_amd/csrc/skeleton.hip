@@ -416,6 +416,38 @@ __device__ __forceinline__ f4 quat_of(const float* m) {
     return f4{w / d, x / d, y / d, z / d};
 }
 
+// R_j of output frame fr of the tile (frame fl of the pass ps, staged at x in rows of D floats): the six numbers of joint j (+ mean), blended
+// where the rate changes, then Gram-Schmidt.  The one definition behind the joints, the quaternions and the Euler angles of a pose.
+template <bool NATIVE, int SL>
+__device__ __forceinline__ void rot6d_matrix(const float* x, const Walk<NATIVE, SL>& w, const Pass& ps, int fl, int fr, int j, int D, const float* mn,
+                                             bool has_mean, int columns, float (&R)[9]) {
+    const float* mj = mn + 6 * j;                                              // once: written as mn[6 * j + e] the address is remade per element
+    float d[6];
+    if (NATIVE || w.n < 2) {
+        const float* xs = x + (NATIVE ? fl : 0) * D + 6 * j;
+#pragma unroll
+        for (int e = 0; e < 6; ++e) d[e] = has_mean ? xs[e] + mj[e] : xs[e];
+    } else {                                                                    // the 6-D vectors are blended, after the mean
+        const Blend bl = w.blend(ps, fr);
+        const float* xs = x + bl.slot * D + 6 * j;
+#pragma unroll
+        for (int e = 0; e < 6; ++e) {
+            float y = xs[e], z = xs[D + e];
+            if (has_mean) { y += mj[e]; z += mj[e]; }
+            d[e] = fmaf(z - y, bl.f, y);
+        }
+    }
+    const float n1 = fmaxf(sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]), 1e-12f);
+    const float b10 = d[0] / n1, b11 = d[1] / n1, b12 = d[2] / n1;
+    const float dot = b10 * d[3] + b11 * d[4] + b12 * d[5];
+    const float u0 = d[3] - dot * b10, u1 = d[4] - dot * b11, u2 = d[5] - dot * b12;
+    const float n2 = fmaxf(sqrtf(u0 * u0 + u1 * u1 + u2 * u2), 1e-12f);
+    const float b20 = u0 / n2, b21 = u1 / n2, b22 = u2 / n2;
+    const float b30 = b11 * b22 - b12 * b21, b31 = b12 * b20 - b10 * b22, b32 = b10 * b21 - b11 * b20;
+    if (columns) { R[0] = b10; R[1] = b20; R[2] = b30; R[3] = b11; R[4] = b21; R[5] = b31; R[6] = b12; R[7] = b22; R[8] = b32; }
+    else { R[0] = b10; R[1] = b11; R[2] = b12; R[3] = b20; R[4] = b21; R[5] = b22; R[6] = b30; R[7] = b31; R[8] = b32; }
+}
+
 // NATIVE: L / M = 1.  GLOBAL: the rotations hold G_j, else R_j.  a.dst: the joints or null; k.rot: the rotations or null.
 template <bool NATIVE, bool GLOBAL>
 __global__ __launch_bounds__(THREADS) void articulate_kernel(const ArtArgs k) {
@@ -454,31 +486,8 @@ __global__ __launch_bounds__(THREADS) void articulate_kernel(const ArtArgs k) {
         // Phase 1, every (output frame, joint) at once: R_j by Gram-Schmidt into the joint's own plane of the state tile; the local rotations leave here.
         for (int q = tid; q < nf * J; q += THREADS) {
             const int j = q / nf, fr = i + (q - j * nf);
-            float d[6];
-            if (NATIVE || t.n < 2) {
-                const float* xs = x + (NATIVE ? fr - i : 0) * D + 6 * j;
-#pragma unroll
-                for (int e = 0; e < 6; ++e) d[e] = has_mean ? xs[e] + mn[6 * j + e] : xs[e];
-            } else {                                                            // the 6-D vectors are blended, after the mean
-                const Blend bl = w.blend(ps, fr);
-                const float* xs = x + bl.slot * D + 6 * j;
-#pragma unroll
-                for (int e = 0; e < 6; ++e) {
-                    float y = xs[e], z = xs[D + e];
-                    if (has_mean) { y += mn[6 * j + e]; z += mn[6 * j + e]; }
-                    d[e] = fmaf(z - y, bl.f, y);
-                }
-            }
-            const float n1 = fmaxf(sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]), 1e-12f);
-            const float b10 = d[0] / n1, b11 = d[1] / n1, b12 = d[2] / n1;
-            const float dot = b10 * d[3] + b11 * d[4] + b12 * d[5];
-            const float u0 = d[3] - dot * b10, u1 = d[4] - dot * b11, u2 = d[5] - dot * b12;
-            const float n2 = fmaxf(sqrtf(u0 * u0 + u1 * u1 + u2 * u2), 1e-12f);
-            const float b20 = u0 / n2, b21 = u1 / n2, b22 = u2 / n2;
-            const float b30 = b11 * b22 - b12 * b21, b31 = b12 * b20 - b10 * b22, b32 = b10 * b21 - b11 * b20;
             float R[9];
-            if (k.columns) { R[0] = b10; R[1] = b20; R[2] = b30; R[3] = b11; R[4] = b21; R[5] = b31; R[6] = b12; R[7] = b22; R[8] = b32; }
-            else { R[0] = b10; R[1] = b11; R[2] = b12; R[3] = b20; R[4] = b21; R[5] = b22; R[6] = b30; R[7] = b31; R[8] = b32; }
+            rot6d_matrix(x, w, ps, fr - i, fr, j, D, mn, has_mean, k.columns, R);
             float* sj = st + j * AST + fr;
 #pragma unroll
             for (int e = 0; e < 9; ++e) sj[e * TFA] = R[e];
@@ -530,33 +539,42 @@ __global__ __launch_bounds__(THREADS) void articulate_kernel(const ArtArgs k) {
     }
 }
 
-// quat [B, T, J, 4] -> rot6d [B, T, 6J]: one 16-byte load per (frame, joint), six floats into an LDS tile, coalesced stores from there.
-__global__ __launch_bounds__(THREADS) void articulate_rot6d_kernel(const ArtArgs k) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const Args& a = k.a;
-    const int J = k.J, D = 6 * J, tid = threadIdx.x;
-    float* mn = lds;
-    float* buf = lds + 6 * MAX_J;
+// The frame of both inverse kernels, anything [B, T, J, .] -> rot6d [B, T, 6J] on tiles of TFI frames: the zero tail, the mean, then
+// fill(n, q0) leaves the six floats of the tile's n (frame, joint) pairs in buf[6 q] -- pair q is pair q0 + q of the whole input, the tile's
+// rows are contiguous -- and they leave through store_range minus the mean, coalesced.
+template <class F>
+__device__ __forceinline__ void rot6d_tile(const Args& a, int J, float* mn, const float* buf, F fill) {
+    const int D = 6 * J;
     const Tile t = tile_of<true, TFI>(a, a.T);
     const long long f0 = (long long)t.b * a.T + t.k0;
     zero_tail(a.dst, f0 * D, D, t);
     if (t.live == 0) return;
     const bool has_mean = a.mean != nullptr;
     load_mean(a, mn);
-    for (int q = tid; q < t.live * J; q += THREADS) {
-        const f4 v = *reinterpret_cast<const f4*>(a.src + (f0 * J + q) * 4);
-        const float d = fmaxf(sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]), 1e-12f);
-        const float w = v[0] / d, x = v[1] / d, y = v[2] / d, z = v[3] / d;
-        const float m00 = 1.f - 2.f * (y * y + z * z), m01 = 2.f * (x * y - w * z), m02 = 2.f * (x * z + w * y);
-        const float m10 = 2.f * (x * y + w * z), m11 = 1.f - 2.f * (x * x + z * z), m12 = 2.f * (y * z - w * x);
-        float* o = buf + 6 * q;                                                 // q = frame * J + joint: the tile's rows are contiguous
-        if (k.columns) { o[0] = m00; o[1] = m10; o[2] = 2.f * (x * z - w * y); o[3] = m01; o[4] = m11; o[5] = 2.f * (y * z + w * x); }
-        else { o[0] = m00; o[1] = m01; o[2] = m02; o[3] = m10; o[4] = m11; o[5] = m12; }
-    }
+    fill(t.live * J, f0 * J);
     __syncthreads();
     store_range(a.dst, f0 * D, D, f0 * D, (f0 + t.live) * D, [&](int fr, int r) {
         const float v = buf[fr * D + r];
         return has_mean ? v - mn[r] : v;
+    });
+}
+
+// quat [B, T, J, 4] -> rot6d [B, T, 6J]: one 16-byte load per (frame, joint).
+__global__ __launch_bounds__(THREADS) void articulate_rot6d_kernel(const ArtArgs k) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const Args& a = k.a;
+    float* buf = lds + 6 * MAX_J;
+    rot6d_tile(a, k.J, lds, buf, [&](int n, long long q0) {
+        for (int q = threadIdx.x; q < n; q += THREADS) {
+            const f4 v = *reinterpret_cast<const f4*>(a.src + (q0 + q) * 4);
+            const float d = fmaxf(sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]), 1e-12f);
+            const float w = v[0] / d, x = v[1] / d, y = v[2] / d, z = v[3] / d;
+            const float m00 = 1.f - 2.f * (y * y + z * z), m01 = 2.f * (x * y - w * z), m02 = 2.f * (x * z + w * y);
+            const float m10 = 2.f * (x * y + w * z), m11 = 1.f - 2.f * (x * x + z * z), m12 = 2.f * (y * z - w * x);
+            float* o = buf + 6 * q;
+            if (k.columns) { o[0] = m00; o[1] = m10; o[2] = 2.f * (x * z - w * y); o[3] = m01; o[4] = m11; o[5] = 2.f * (y * z + w * x); }
+            else { o[0] = m00; o[1] = m01; o[2] = m02; o[3] = m10; o[4] = m11; o[5] = m12; }
+        }
     });
 }
 
@@ -608,31 +626,8 @@ __global__ __launch_bounds__(THREADS) void articulate_euler_kernel(const EulArgs
         const int nf = ps.i1 - i;
         for (int q = tid; q < nf * J; q += THREADS) {                            // one thread per (output frame, joint)
             const int fl = q / J, j = q - fl * J, fr = i + fl;
-            float d[6];
-            if (NATIVE || t.n < 2) {
-                const float* xs = x + (NATIVE ? fl : 0) * D + 6 * j;
-#pragma unroll
-                for (int e = 0; e < 6; ++e) d[e] = has_mean ? xs[e] + mn[6 * j + e] : xs[e];
-            } else {                                                            // the 6-D vectors are blended, after the mean
-                const Blend bl = w.blend(ps, fr);
-                const float* xs = x + bl.slot * D + 6 * j;
-#pragma unroll
-                for (int e = 0; e < 6; ++e) {
-                    float y = xs[e], z = xs[D + e];
-                    if (has_mean) { y += mn[6 * j + e]; z += mn[6 * j + e]; }
-                    d[e] = fmaf(z - y, bl.f, y);
-                }
-            }
-            const float n1 = fmaxf(sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]), 1e-12f);
-            const float b10 = d[0] / n1, b11 = d[1] / n1, b12 = d[2] / n1;
-            const float dot = b10 * d[3] + b11 * d[4] + b12 * d[5];
-            const float u0 = d[3] - dot * b10, u1 = d[4] - dot * b11, u2 = d[5] - dot * b12;
-            const float n2 = fmaxf(sqrtf(u0 * u0 + u1 * u1 + u2 * u2), 1e-12f);
-            const float b20 = u0 / n2, b21 = u1 / n2, b22 = u2 / n2;
-            const float b30 = b11 * b22 - b12 * b21, b31 = b12 * b20 - b10 * b22, b32 = b10 * b21 - b11 * b20;
             float R[9];
-            if (k.columns) { R[0] = b10; R[1] = b20; R[2] = b30; R[3] = b11; R[4] = b21; R[5] = b31; R[6] = b12; R[7] = b22; R[8] = b32; }
-            else { R[0] = b10; R[1] = b11; R[2] = b12; R[3] = b20; R[4] = b21; R[5] = b22; R[6] = b30; R[7] = b31; R[8] = b32; }
+            rot6d_matrix(x, w, ps, fl, fr, j, D, mn, has_mean, k.columns, R);
             const Axes o = order_axes(ord[j]);
             const float rii = pick9(R, 4 * o.i), rij = pick9(R, 3 * o.i + o.j), s = o.eps * pick9(R, 3 * o.i + o.k);
             const float eb = atan2f(s, sqrtf(rii * rii + rij * rij));
@@ -660,44 +655,34 @@ __global__ __launch_bounds__(THREADS) void articulate_euler_kernel(const EulArgs
 __global__ __launch_bounds__(THREADS) void articulate_rot6d_euler_kernel(const EulArgs k) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const Args& a = k.a;
-    const int J = k.J, D = 6 * J, tid = threadIdx.x;
+    const int J = k.J, tid = threadIdx.x;
     int* ord = reinterpret_cast<int*>(lds);
-    float* mn = lds + MAX_J;
     float* buf = lds + EHEAD;
-    const Tile t = tile_of<true, TFI>(a, a.T);
-    const long long f0 = (long long)t.b * a.T + t.k0;
-    zero_tail(a.dst, f0 * D, D, t);
-    if (t.live == 0) return;
-    for (int j = tid; j < J; j += THREADS) ord[j] = min(max(k.orders[j], 0), 5);
-    const bool has_mean = a.mean != nullptr;
-    load_mean(a, mn);
-    __syncthreads();
-    for (int q = tid; q < t.live * J; q += THREADS) {
-        const float* src = a.src + (f0 * J + q) * 3;
-        const Axes o = order_axes(ord[q % J]);
-        float sa, ca, sb, cb, sc, cc;
-        sincosf(src[0] * k.scale, &sa, &ca);
-        sincosf(src[1] * k.scale, &sb, &cb);
-        sincosf(src[2] * k.scale, &sc, &cc);
-        sa *= o.eps; sb *= o.eps; sc *= o.eps;
-        const float m[9] = {cb * cc, -(cb * sc), sb,
-                            sa * sb * cc + ca * sc, ca * cc - sa * sb * sc, -(sa * cb),
-                            sa * sc - ca * sb * cc, sa * cc + ca * sb * sc, ca * cb};
-        const int p0 = o.i == 0 ? 0 : (o.j == 0 ? 1 : 2), p1 = o.i == 1 ? 0 : (o.j == 1 ? 1 : 2), p2 = o.i == 2 ? 0 : (o.j == 2 ? 1 : 2);
-        float* out = buf + 6 * q;                                               // q = frame * J + joint: the tile's rows are contiguous
-        out[0] = pick9(m, 4 * p0);
-        if (k.columns) {
-            out[1] = pick9(m, 3 * p1 + p0); out[2] = pick9(m, 3 * p2 + p0);
-            out[3] = pick9(m, 3 * p0 + p1); out[4] = pick9(m, 4 * p1); out[5] = pick9(m, 3 * p2 + p1);
-        } else {
-            out[1] = pick9(m, 3 * p0 + p1); out[2] = pick9(m, 3 * p0 + p2);
-            out[3] = pick9(m, 3 * p1 + p0); out[4] = pick9(m, 4 * p1); out[5] = pick9(m, 3 * p1 + p2);
+    rot6d_tile(a, J, lds + MAX_J, buf, [&](int n, long long q0) {
+        for (int j = tid; j < J; j += THREADS) ord[j] = min(max(k.orders[j], 0), 5);
+        __syncthreads();
+        for (int q = tid; q < n; q += THREADS) {
+            const float* src = a.src + (q0 + q) * 3;
+            const Axes o = order_axes(ord[q % J]);
+            float sa, ca, sb, cb, sc, cc;
+            sincosf(src[0] * k.scale, &sa, &ca);
+            sincosf(src[1] * k.scale, &sb, &cb);
+            sincosf(src[2] * k.scale, &sc, &cc);
+            sa *= o.eps; sb *= o.eps; sc *= o.eps;
+            const float m[9] = {cb * cc, -(cb * sc), sb,
+                                sa * sb * cc + ca * sc, ca * cc - sa * sb * sc, -(sa * cb),
+                                sa * sc - ca * sb * cc, sa * cc + ca * sb * sc, ca * cb};
+            const int p0 = o.i == 0 ? 0 : (o.j == 0 ? 1 : 2), p1 = o.i == 1 ? 0 : (o.j == 1 ? 1 : 2), p2 = o.i == 2 ? 0 : (o.j == 2 ? 1 : 2);
+            float* out = buf + 6 * q;
+            out[0] = pick9(m, 4 * p0);
+            if (k.columns) {
+                out[1] = pick9(m, 3 * p1 + p0); out[2] = pick9(m, 3 * p2 + p0);
+                out[3] = pick9(m, 3 * p0 + p1); out[4] = pick9(m, 4 * p1); out[5] = pick9(m, 3 * p2 + p1);
+            } else {
+                out[1] = pick9(m, 3 * p0 + p1); out[2] = pick9(m, 3 * p0 + p2);
+                out[3] = pick9(m, 3 * p1 + p0); out[4] = pick9(m, 4 * p1); out[5] = pick9(m, 3 * p1 + p2);
+            }
         }
-    }
-    __syncthreads();
-    store_range(a.dst, f0 * D, D, f0 * D, (f0 + t.live) * D, [&](int fr, int r) {
-        const float v = buf[fr * D + r];
-        return has_mean ? v - mn[r] : v;
     });
 }
 
@@ -762,6 +747,15 @@ int forward_args(const char* who, Args& a, int L, int M, long long out_stride, i
     return EG_OK;
 }
 
+// The inverse side's counterpart: the calls at the native rate, whose output has T frames of `per_frame` floats per row.
+int inverse_args(const char* who, Args& a, int per_frame, int tile) {
+    const long long tiles = ((long long)a.T + tile - 1) / tile;
+    EG_REQUIRE(tiles * a.B <= 0x7fffffffll && (long long)a.B * a.T * per_frame < (1ll << 40), EG_ERR_UNSUPPORTED,
+               "%s: rows=%d x frames=%d: grid / index range", who, a.B, a.T);
+    a.L = 1; a.M = 1; a.tiles = (int)tiles; a.T_out = a.T;
+    return EG_OK;
+}
+
 // One workgroup per tile of every row.  `a` holds the grid; `k`: what the kernel takes (Args itself, or a block that begins with it).
 template <class A>
 int launch(void (*kernel)(A), const Args& a, const A& k, size_t lds_floats, void* stream, const char* what) {
@@ -817,10 +811,9 @@ extern "C" int eg_skeleton_dir_vec(const float* joints, int32_t rows, int32_t T,
     const char* who = "eg_skeleton_dir_vec";
     int rc = common_checks(who, joints, dir_vec, rows, T, parents, children, lengths, bones, d_table, draws, frame_unit, d_mean);
     if (rc != EG_OK) return rc;
-    const long long tiles = ((long long)T + TF - 1) / TF;
-    EG_REQUIRE(tiles * rows <= 0x7fffffffll && (long long)rows * T * 3 * (bones + 1) < (1ll << 40), EG_ERR_UNSUPPORTED,
-               "%s: rows=%d x frames=%d: grid / index range", who, rows, T);
-    Args a = {joints, static_cast<const int*>(d_table), d_frames, d_mean, dir_vec, rows, T, bones, draws, frame_unit, 1, 1, (int)tiles, T};
+    Args a = {joints, static_cast<const int*>(d_table), d_frames, d_mean, dir_vec, rows, T, bones, draws, frame_unit};
+    rc = inverse_args(who, a, 3 * (bones + 1), TF);
+    if (rc != EG_OK) return rc;
     return launch(skeleton_dir_vec_kernel, a, HEAD + round4(TF * 3 * (bones + 1) + 8), stream, "skeleton_dir_vec");
 }
 
@@ -985,11 +978,9 @@ extern "C" int eg_articulate_rot6d(const float* quat, int32_t rows, int32_t T, i
     int rc = rows_checks(who, quat, rows, T, draws, frame_unit, d_mean, basis);
     if (rc != EG_OK) return rc;
     EG_REQUIRE(eg_aligned16(rot6d), EG_ERR_ALIGN, "%s: output not 16-byte aligned", who);
-    const long long tiles = ((long long)T + TFI - 1) / TFI;
-    EG_REQUIRE(tiles * rows <= 0x7fffffffll && (long long)rows * T * 6 * joints < (1ll << 40), EG_ERR_UNSUPPORTED,
-               "%s: rows=%d x frames=%d: grid / index range", who, rows, T);
-    const ArtArgs k = {{quat, nullptr, d_frames, d_mean, rot6d, rows, T, 2 * joints, draws, frame_unit, 1, 1, (int)tiles, T}, nullptr, joints,
-                       basis == EG_ARTICULATE_BASIS_COLUMNS};
+    ArtArgs k = {{quat, nullptr, d_frames, d_mean, rot6d, rows, T, 2 * joints, draws, frame_unit}, nullptr, joints, basis == EG_ARTICULATE_BASIS_COLUMNS};
+    rc = inverse_args(who, k.a, 6 * joints, TFI);
+    if (rc != EG_OK) return rc;
     return launch(articulate_rot6d_kernel, k.a, k, 6 * MAX_J + TFI * 6 * joints, stream, "articulate_rot6d");
 }
 
@@ -1037,10 +1028,9 @@ extern "C" int eg_articulate_rot6d_euler(const float* euler, int32_t rows, int32
     rc = rows_checks(who, euler, rows, T, draws, frame_unit, d_mean, basis);
     if (rc != EG_OK) return rc;
     EG_REQUIRE(eg_aligned16(rot6d), EG_ERR_ALIGN, "%s: output not 16-byte aligned", who);
-    const long long tiles = ((long long)T + TFI - 1) / TFI;
-    EG_REQUIRE(tiles * rows <= 0x7fffffffll && (long long)rows * T * 6 * joints < (1ll << 40), EG_ERR_UNSUPPORTED,
-               "%s: rows=%d x frames=%d: grid / index range", who, rows, T);
-    const EulArgs k = {{euler, nullptr, d_frames, d_mean, rot6d, rows, T, 2 * joints, draws, frame_unit, 1, 1, (int)tiles, T},
-                       static_cast<const int*>(d_orders), joints, basis == EG_ARTICULATE_BASIS_COLUMNS, degrees ? (float)(M_PI / 180.0) : 1.f};
+    EulArgs k = {{euler, nullptr, d_frames, d_mean, rot6d, rows, T, 2 * joints, draws, frame_unit}, static_cast<const int*>(d_orders), joints,
+                 basis == EG_ARTICULATE_BASIS_COLUMNS, degrees ? (float)(M_PI / 180.0) : 1.f};
+    rc = inverse_args(who, k.a, 6 * joints, TFI);
+    if (rc != EG_OK) return rc;
     return launch(articulate_rot6d_euler_kernel, k.a, k, EHEAD + TFI * 6 * joints, stream, "articulate_rot6d_euler");
 }

@@ -533,9 +533,9 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     ``mode="interp"``) over recording u's own valid poses, zeros behind them, one launch.  ``"track"`` stays raw and ``beat`` / ``diversity`` keep
     scoring it (they measure the model); ``"joints"`` and ``"rotations"`` are then made from ``"track_smooth"`` (they are what a renderer
     takes).  ``deriv != 0`` is refused by name: a velocity track is not a pose track -- call ``smooth_tracks`` for derivatives."""
+    outputs = _track_outputs("synthesize", seed_pose, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, euler, euler_unwrap)
     return _synthesize("synthesize", models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate,
-                       want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, joints, joints_mean, joints_unit, joints_fps,
-                       rotations, rotations_space, smooth, takes=False, euler=euler, euler_unwrap=euler_unwrap)
+                       want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=False)
 
 
 def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch.Tensor, labels: Optional[torch.Tensor] = None, *,
@@ -556,22 +556,24 @@ def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose:
     recording u's own samples and poses: ``beat`` -> ``"beat"`` ``[U, R]``; ``diversity`` (R >= 2) -> ``"take_distance"`` ``[U, R, R]`` and
     ``"take_diversity"`` ``[U]``; ``joints`` -> ``[U, R, T', J, 3]``; ``rotations`` -> ``[U, R, T', K, 4]``; ``audio_rate``; ``smooth`` ->
     ``"track_smooth"`` ``[U, R, T, pose_dim]``."""
+    outputs = _track_outputs("synthesize_takes", seed_pose, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, euler, euler_unwrap)
     return _synthesize("synthesize_takes", models, audio, text, seed_pose, labels, hop_samples, n_samples, None, z, alpha, fps, sample_rate,
-                       want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, joints, joints_mean, joints_unit, joints_fps,
-                       rotations, rotations_space, smooth, takes=True, euler=euler, euler_unwrap=euler_unwrap)
+                       want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=True)
+
+
+def _track_outputs(who, seed_pose, *args):
+    """The output stage of `synthesize` / `synthesize_takes` (skeleton.TrackOutputs, or None): their arguments, checked before anything else."""
+    from . import skeleton as SK
+    outs = SK.TrackOutputs(who, *args, pose_dim=seed_pose.shape[-1], hint=" (the BEAT generators' 282 columns hold rotations, not bone direction "
+                           "vectors): their body is a skeleton.JointTree of 47 joints")
+    return None if outs.body is None else outs
 
 
 def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate, want_windows, want_aux,
-                mel, lengths, draws, beat, diversity, audio_rate, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, smooth,
-                takes, euler=None, euler_unwrap=False):
+                mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes):
     """The body of `synthesize` and `synthesize_takes` (`who` names the caller in errors): argument checks, resampling, the roll-out of the
-    call's kind, then the per-track extras."""
+    call's kind, then the per-track extras.  `outputs`: the caller's checked output stage (`_track_outputs`)."""
     gen, vae = models
-    from . import skeleton as SK
-    rotations = SK.output_args(who, seed_pose.shape[-1], joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space,
-                               hint=" (the BEAT generators' 282 columns hold rotations, not bone direction vectors): their body is a "
-                                    "skeleton.JointTree of 47 joints")
-    euler = SK.euler_args(who, joints, euler, euler_unwrap)
     if smooth is not None:
         from . import smooth as SM
         smooth = SM.Smoother.of(smooth, f"{who}: smooth", fps)
@@ -642,32 +644,9 @@ def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samp
     if smooth is not None:                                                                # beat and diversity above score the raw track
         with torch.no_grad():
             poses = out["track_smooth"] = SM.smooth_tracks(out["track"], smooth, frames=frames)
-    if joints is not None:
-        kw = dict(frames=frames, mean=joints_mean, fps=joints_fps)
+    if outputs is not None:                                                               # joints, rotations, Euler channels: skeleton.TrackOutputs
         with torch.no_grad():
-            if isinstance(joints, SK.JointTree):                                           # 6-D rotations: both outputs from one launch
-                out.update(_articulated(poses, joints, rotations is not None, rotations_space, **kw))
-            else:
-                out["joints"], out["joint_frames"] = SK.joints_from_tracks(poses, joints, unit=joints_unit, **kw)
-                if rotations is not None:
-                    out["rotations"], _n = SK.rotations_from_tracks(poses, joints, rotations, space=rotations_space, **kw)
-            if euler is not None:                                                          # one more launch (and the unwrap's)
-                out["euler"], _n = SK.euler_from_rot6d(poses, joints, euler, unwrap=euler_unwrap, **kw)
-    return out
-
-
-def _articulated(poses: torch.Tensor, tree, want_rotations: bool, space: str, frames, mean, fps) -> Dict[str, torch.Tensor]:
-    """``joints`` / ``joint_frames`` (/ ``rotations``) of ``poses [U, (R,) T, 6J]`` on a ``skeleton.JointTree``: what
-    ``skeleton.joints_from_rot6d`` and ``rotations_from_rot6d`` return, from one ``launch_articulate``."""
-    from . import skeleton as SK
-    who = "synthesize: joints"
-    fe = SK._front(poses, tree, frames, fps, who)
-    x = SK._dev32(poses).reshape(fe.U * fe.R, fe.T, tree.pose_dim)
-    j, q = SK.launch_articulate(x, tree, SK._frames_dev(fe.fr, x.device), fe.R, 1, SK._mean_dev(mean, tree.pose_dim, x.device, who), space,
-                                fe.ratio, rotations=want_rotations)
-    out = {"joints": j.reshape(fe.lead + (fe.t_out, tree.J, 3)), "joint_frames": fe.n_out}
-    if want_rotations:
-        out["rotations"] = q.reshape(fe.lead + (fe.t_out, tree.J, 4))
+            out.update(outputs.tracks(poses, frames))
     return out
 
 

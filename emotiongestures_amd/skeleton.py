@@ -67,7 +67,7 @@ from ._host import BoundedCache, host_ptr, int_list, ptr as _ptr, stream as _str
 __all__ = ["Skeleton", "RestPose", "ted_expressive", "joints_from_tracks", "dir_vec_from_joints", "rotations_from_tracks", "out_frames",
            "rate_ratio", "TILE_FRAMES", "MAX_BONES", "MAX_FACTOR", "JointTree", "joints_from_rot6d", "rotations_from_rot6d",
            "rot6d_from_rotations", "ARTICULATE_TILE_FRAMES", "MAX_JOINTS", "euler_from_rot6d", "rot6d_from_euler", "unwrap_angles", "launch_euler",
-           "launch_rot6d_euler", "launch_unwrap", "unwrap_workspace", "order_codes", "euler_args", "ORDERS", "UNWRAP_TILE_FRAMES"]
+           "launch_rot6d_euler", "launch_unwrap", "unwrap_workspace", "order_codes", "order_axes", "euler_args", "TrackOutputs", "ORDERS", "UNWRAP_TILE_FRAMES"]
 
 TILE_FRAMES = L.EG_SKELETON_TILE_FRAMES      # output frames of one workgroup
 MAX_BONES = L.EG_SKELETON_MAX_BONES
@@ -82,6 +82,7 @@ def level_words(K: int) -> int:
 class Skeleton:
     """K bones ``(parents[k], children[k], lengths[k])`` in topological order (eg_skeleton_check refuses anything else by name).  The device
     table is uploaded once per device."""
+    noun, sym, parts, factor = "skeleton", "K", "bones", 3        # how the checks speak of this body: pose_dim = factor * count
 
     def __init__(self, parents: Sequence[int], children: Sequence[int], lengths: Sequence[float]):
         if not (len(parents) == len(children) == len(lengths)):
@@ -90,7 +91,7 @@ class Skeleton:
         self.children = np.ascontiguousarray(children, np.int32)
         self.lengths = np.ascontiguousarray(lengths, np.float64)          # as given: the float64 path's lengths
         self.lengths32 = self.lengths.astype(np.float32)                  # the device's
-        self.K = int(len(self.parents))
+        self.K = self.count = int(len(self.parents))
         self.J = self.K + 1
         L.check(L.load().eg_skeleton_check(*self.host_ptrs(), self.K), "eg_skeleton_check")
         self._tables = BoundedCache()
@@ -305,37 +306,37 @@ def _resample64(y: np.ndarray, n_out: int, Lf: int, M: int) -> np.ndarray:
     return y[lo] + (y[lo + 1] - y[lo]) * f
 
 
+def _valid_rows64(v: np.ndarray, frames: List[int], tail: Tuple[int, ...], fn, Lf: int = 1, M: int = 1) -> np.ndarray:
+    """The valid rows of every recording, zeros elsewhere: ``out [B, ceil(T L / M), *tail]`` with ``out[b, :n_out] = fn(v[b, :n], n, n_out)`` for
+    the ``n = frames[b] >= 1`` valid source frames of row b of ``v [B, T, ...]`` and their ``n_out = ceil(n L / M)`` output frames."""
+    out = np.zeros((len(v), -(-v.shape[1] * Lf // M)) + tail)
+    for b, n in enumerate(frames):
+        if n >= 1:
+            n_out = -(-n * Lf // M)
+            out[b, :n_out] = fn(v[b, :n], n, n_out)
+    return out
+
+
 def _joints64(v: np.ndarray, sk: Skeleton, frames: List[int], mean, unit: bool, Lf: int, M: int) -> np.ndarray:
     """v [B, T, 3K] float64, frames [B] -> [B, ceil(T L / M), J, 3]."""
-    B, T, _D = v.shape
-    out = np.zeros((B, -(-T * Lf // M), sk.J, 3))
-    for b in range(B):
-        n = frames[b]
-        if n < 1:
-            continue
-        x = v[b, :n].reshape(n, sk.K, 3)
+    def row(x, n, n_out):
+        x = x.reshape(n, sk.K, 3)
         if mean is not None:
             x = x + mean.reshape(sk.K, 3)
         if unit:
             x = x / np.maximum(np.sqrt((x * x).sum(-1, keepdims=True)), 1e-12)
-        n_out = -(-n * Lf // M)
-        out[b, :n_out] = _resample64(_chain64(sk, x), n_out, Lf, M)
-    return out
+        return _resample64(_chain64(sk, x), n_out, Lf, M)
+    return _valid_rows64(v, frames, (sk.J, 3), row, Lf, M)
 
 
 def _dir_vec64(p: np.ndarray, sk: Skeleton, frames: List[int], mean) -> np.ndarray:
     """p [B, T, J, 3] float64 -> [B, T, 3K]."""
-    B, T = p.shape[:2]
-    out = np.zeros((B, T, 3 * sk.K))
-    for b in range(B):
-        n = frames[b]
-        if n < 1:
-            continue
-        d = p[b, :n][:, sk.children] - p[b, :n][:, sk.parents]
+    def row(pn, n, _n_out):
+        d = pn[:, sk.children] - pn[:, sk.parents]
         d = d / np.maximum(np.sqrt((d * d).sum(-1, keepdims=True)), 1e-12)
         d = d.reshape(n, 3 * sk.K)
-        out[b, :n] = d if mean is None else d - mean
-    return out
+        return d if mean is None else d - mean
+    return _valid_rows64(p, frames, (3 * sk.K,), row)
 
 
 # quaternions (w, x, y, z) on the last axis, float64
@@ -373,17 +374,12 @@ def _arc64(a: np.ndarray, b: np.ndarray) -> np.ndarray:
 
 def _rotations64(v: np.ndarray, sk: Skeleton, rest: np.ndarray, frames: List[int], mean, glob: bool, Lf: int, M: int) -> np.ndarray:
     """v [B, T, 3K] float64, rest [K, 3] (unit), frames [B] -> [B, ceil(T L / M), K, 4]."""
-    B, T, _D = v.shape
-    out = np.zeros((B, -(-T * Lf // M), sk.K, 4))
     pb = sk.bone_parents
-    for b in range(B):
-        n = frames[b]
-        if n < 1:
-            continue
-        x = v[b, :n].reshape(n, sk.K, 3)
+
+    def row(x, n, n_out):
+        x = x.reshape(n, sk.K, 3)
         if mean is not None:
             x = x + mean.reshape(sk.K, 3)
-        n_out = -(-n * Lf // M)
         x = _resample64(x, n_out, Lf, M)                        # the vectors are blended, then the chain runs on the blended frame
         x = x / np.maximum(np.sqrt((x * x).sum(-1, keepdims=True)), 1e-12)
         G = np.zeros((n_out, sk.K, 4))
@@ -395,8 +391,8 @@ def _rotations64(v: np.ndarray, sk: Skeleton, rest: np.ndarray, frames: List[int
                 P = G[:, pb[k]]
                 loc[:, k] = _arc64(rest[k], _qrot(_qconj(P), x[:, k]))
                 G[:, k] = _qmul(P, loc[:, k])
-        out[b, :n_out] = G if glob else loc
-    return out
+        return G if glob else loc
+    return _valid_rows64(v, frames, (sk.K, 4), row, Lf, M)
 
 
 # ---- the device path ---------------------------------------------------------------------------------------------------------------------
@@ -459,16 +455,23 @@ def _per_row(fr: Optional[List[int]], U: int, R: int, T: int) -> List[int]:
     return [n for n in (fr if fr is not None else [T] * U) for _ in range(R)]
 
 
-def _shape_checked(track, sk, who: str) -> Skeleton:
-    """The first half of the front end of both forward functions: the skeleton's type and the track's shape; returns the skeleton."""
-    if not isinstance(sk, Skeleton):
-        raise L.EgError(f"{who}: skeleton must be a Skeleton, got {type(sk).__name__}")
+def _body_checked(body, kind, who: str):
+    if not isinstance(body, kind):
+        raise L.EgError(f"{who}: {kind.noun} must be a {kind.__name__}, got {type(body).__name__}")
+    return body
+
+
+def _track_checked(track, body, kind, who: str):
+    """The first half of the front end of every forward function: the body's type (``kind``: Skeleton or JointTree) and the track's shape, in
+    the body's own words; returns the body."""
+    b = _body_checked(body, kind, who)
     shape = tuple(track.shape)
     if len(shape) < 2 or shape[-2] < 1:
-        raise L.EgError(f"{who}: track shape {shape}: need [..., T >= 1, {sk.pose_dim}]")
-    if shape[-1] != sk.pose_dim:
-        raise L.EgError(f"{who}: track shape {shape}: a skeleton of K={sk.K} bones takes 3K={sk.pose_dim} columns per frame, not {shape[-1]}")
-    return sk
+        raise L.EgError(f"{who}: track shape {shape}: need [..., T >= 1, {b.pose_dim}]")
+    if shape[-1] != b.pose_dim:
+        raise L.EgError(f"{who}: track shape {shape}: a {b.noun} of {b.sym}={b.count} {b.parts} takes {b.factor}{b.sym}={b.pose_dim} columns "
+                        f"per frame, not {shape[-1]}")
+    return b
 
 
 def _front(track, sk: Skeleton, frames, fps, who: str) -> SimpleNamespace:
@@ -491,6 +494,44 @@ def _finish(res, track, fe, tail: Tuple[int, int], frames, fps):
     return res if frames is None and fps is None else (res, fe.n_out)
 
 
+def _forward(track, body, frames, mean, fps, who: str, tail: Tuple[int, int], on_device, on_host):
+    """Behind the checks of a forward function: ``_front``, then ``on_device(x [U * R, T, D] fp32, fe, d_frames, d_mean)`` for a CUDA tensor
+    or ``on_host(v [U * R, T, D] float64, fe, mean64)`` for anything else, then ``_finish``."""
+    fe = _front(track, body, frames, fps, who)
+    D = body.pose_dim
+    if _is_cuda(track):
+        x = _dev32(track).reshape(fe.U * fe.R, fe.T, D)
+        res = on_device(x, fe, _frames_dev(fe.fr, x.device), _mean_dev(mean, D, x.device, who))
+    else:
+        res = on_host(_host64(track, who).reshape(fe.U * fe.R, fe.T, D), fe, _mean_host(mean, D, who))
+    return _finish(res, track, fe, tail, frames, fps)
+
+
+def _inverse(x, body, kind, name: str, width: int, who: str):
+    """The check of an inverse function: the body's type and the shape of ``x [..., T, J, width]``; returns the body."""
+    b = _body_checked(body, kind, who)
+    shape = tuple(x.shape)
+    if len(shape) < 3 or shape[-2:] != (b.J, width) or shape[-3] < 1:
+        raise L.EgError(f"{who}: {name} shape {shape}: need [..., T >= 1, {b.J}, {width}] for a {b.noun} of {b.count} {b.parts}")
+    return b
+
+
+def _per_frame(x, n_tail: int, frames, who: str, tail: Tuple[int, ...], on_device, on_host):
+    """The front end and the finish of the inverse and in-place functions, whose output has the input's frames: ``x [..., T, *]`` with
+    ``n_tail`` axes from T on and up to two leading ones -> ``[..., T, *tail]`` from ``on_device(x [U * R, T, *] fp32, d_frames, R)`` for a
+    CUDA tensor or ``on_host(x [U * R, T, *] float64, per_row)`` for anything else (tensor in: tensor out)."""
+    shape = tuple(x.shape)
+    lead, U, R = _lead(shape, n_tail, who)
+    T = shape[-n_tail]
+    fr = _frames_list(frames, U, T, who)
+    rows = (U * R,) + shape[-n_tail:]
+    if _is_cuda(x):
+        xd = _dev32(x).reshape(rows)
+        return on_device(xd, _frames_dev(fr, xd.device), R).reshape(lead + (T,) + tail)
+    res = on_host(_host64(x, who).reshape(rows), _per_row(fr, U, R, T)).reshape(lead + (T,) + tail)
+    return torch.from_numpy(res) if isinstance(x, torch.Tensor) else res
+
+
 def joints_from_tracks(track, skeleton: Skeleton, frames=None, mean=None, unit: bool = False, fps=None):
     """``track [..., T, 3K]`` with up to two leading axes (``[T, D]``, ``[U, T, D]``, ``[U, R, T, D]``) -> ``joints [..., T_out, J, 3]``,
     ``T_out = ceil(T * L / M)``.
@@ -504,15 +545,10 @@ def joints_from_tracks(track, skeleton: Skeleton, frames=None, mean=None, unit: 
     float64 tensor out).  With ``frames`` or ``fps`` the result is ``(joints, joint_frames)``, ``joint_frames`` the valid output frames per
     recording (a list of U ints)."""
     who = "joints_from_tracks"
-    sk = _shape_checked(track, skeleton, who)
-    fe = _front(track, sk, frames, fps, who)
-    if _is_cuda(track):
-        x = _dev32(track).reshape(fe.U * fe.R, fe.T, sk.pose_dim)
-        j = launch_joints(x, sk, _frames_dev(fe.fr, x.device), fe.R, 1, _mean_dev(mean, sk.pose_dim, x.device, who), unit, fe.ratio)
-    else:
-        v = _host64(track, who).reshape(fe.U * fe.R, fe.T, sk.pose_dim)
-        j = _joints64(v, sk, fe.per_row, _mean_host(mean, sk.pose_dim, who), bool(unit), *fe.ratio)
-    return _finish(j, track, fe, (sk.J, 3), frames, fps)
+    sk = _track_checked(track, skeleton, Skeleton, who)
+    return _forward(track, sk, frames, mean, fps, who, (sk.J, 3),
+                    lambda x, fe, d_frames, d_mean: launch_joints(x, sk, d_frames, fe.R, 1, d_mean, unit, fe.ratio),
+                    lambda v, fe, mean64: _joints64(v, sk, fe.per_row, mean64, bool(unit), *fe.ratio))
 
 
 def dir_vec_from_joints(joints, skeleton: Skeleton, frames=None, mean=None):
@@ -521,21 +557,10 @@ def dir_vec_from_joints(joints, skeleton: Skeleton, frames=None, mean=None):
     motion-capture joints.  ``frames`` as in ``joints_from_tracks``: zeros from ``frames[u]`` on.  CUDA in: the kernel, fp32; numpy / CPU in:
     float64."""
     who = "dir_vec_from_joints"
-    if not isinstance(skeleton, Skeleton):
-        raise L.EgError(f"{who}: skeleton must be a Skeleton, got {type(skeleton).__name__}")
-    sk = skeleton
-    shape = tuple(joints.shape)
-    if len(shape) < 3 or shape[-2:] != (sk.J, 3) or shape[-3] < 1:
-        raise L.EgError(f"{who}: joints shape {shape}: need [..., T >= 1, {sk.J}, 3] for a skeleton of {sk.K} bones")
-    lead, U, R = _lead(shape, 3, who)
-    T = shape[-3]
-    fr = _frames_list(frames, U, T, who)
-    if _is_cuda(joints):
-        p = _dev32(joints).reshape(U * R, T, sk.J, 3)
-        return launch_dir_vec(p, sk, _frames_dev(fr, p.device), R, 1, _mean_dev(mean, sk.pose_dim, p.device, who)).reshape(lead + (T, sk.pose_dim))
-    p = _host64(joints, who).reshape(U * R, T, sk.J, 3)
-    d = _dir_vec64(p, sk, _per_row(fr, U, R, T), _mean_host(mean, sk.pose_dim, who)).reshape(lead + (T, sk.pose_dim))
-    return torch.from_numpy(d) if isinstance(joints, torch.Tensor) else d
+    sk = _inverse(joints, skeleton, Skeleton, "joints", 3, who)
+    return _per_frame(joints, 3, frames, who, (sk.pose_dim,),
+                      lambda p, d_frames, R: launch_dir_vec(p, sk, d_frames, R, 1, _mean_dev(mean, sk.pose_dim, p.device, who)),
+                      lambda p, per_row: _dir_vec64(p, sk, per_row, _mean_host(mean, sk.pose_dim, who)))
 
 
 def rotations_from_tracks(track, skeleton: Skeleton, rest, frames=None, mean=None, fps=None, space: str = "local"):
@@ -551,16 +576,12 @@ def rotations_from_tracks(track, skeleton: Skeleton, rest, frames=None, mean=Non
     A CUDA tensor: one kernel launch, fp32 CUDA result.  numpy or a CPU tensor: the definition in float64.  With ``frames`` or ``fps`` the
     result is ``(rotations, rotation_frames)`` under the rule of ``joints_from_tracks``."""
     who = "rotations_from_tracks"
-    sk = _shape_checked(track, skeleton, who)
+    sk = _track_checked(track, skeleton, Skeleton, who)
     sp, pose = _space(space, who), sk.rest_pose(rest)
-    fe = _front(track, sk, frames, fps, who)
-    if _is_cuda(track):
-        x = _dev32(track).reshape(fe.U * fe.R, fe.T, sk.pose_dim)
-        q = launch_rotations(x, sk, pose, _frames_dev(fe.fr, x.device), fe.R, 1, _mean_dev(mean, sk.pose_dim, x.device, who), space, fe.ratio)
-    else:
-        v = _host64(track, who).reshape(fe.U * fe.R, fe.T, sk.pose_dim)
-        q = _rotations64(v, sk, pose.unit32.astype(np.float64), fe.per_row, _mean_host(mean, sk.pose_dim, who), sp == L.EG_SKELETON_SPACE_GLOBAL, *fe.ratio)
-    return _finish(q, track, fe, (sk.K, 4), frames, fps)
+    return _forward(track, sk, frames, mean, fps, who, (sk.K, 4),
+                    lambda x, fe, d_frames, d_mean: launch_rotations(x, sk, pose, d_frames, fe.R, 1, d_mean, space, fe.ratio),
+                    lambda v, fe, mean64: _rotations64(v, sk, pose.unit32.astype(np.float64), fe.per_row, mean64,
+                                                       sp == L.EG_SKELETON_SPACE_GLOBAL, *fe.ratio))
 
 
 # ---- articulated bodies: 6-D joint rotations (the BEAT generators) -----------------------------------------------------------------------------
@@ -580,6 +601,7 @@ class JointTree:
     numbers of a joint, ``"rows"`` (the first two rows of the matrix: pytorch3d's ``rotation_6d_to_matrix``) or ``"columns"`` (Zhou et al.
     2019).  ``pose_dim = 6J``.  eg_articulate_check refuses a bad table by name.  The level table (the joints by depth, the parents and the
     fp32 offsets: what the kernel reads) is built once and uploaded once per device."""
+    noun, sym, parts, factor = "tree", "J", "joints", 6
 
     def __init__(self, parents: Sequence[int], offsets, basis: str = "rows", names: Optional[Sequence[str]] = None):
         if basis not in _BASES:
@@ -588,7 +610,7 @@ class JointTree:
         if isinstance(offsets, torch.Tensor):
             offsets = offsets.detach().cpu().numpy()
         self.offsets = np.ascontiguousarray(offsets, np.float64)          # as given: the float64 path's offsets
-        self.J = int(len(self.parents))
+        self.J = self.count = int(len(self.parents))
         if self.offsets.shape != (self.J, 3):
             raise L.EgError(f"JointTree: offsets shape {self.offsets.shape}: {self.J} parents take one offset per joint, [{self.J}, 3]")
         self.offsets32 = self.offsets.astype(np.float32)                  # the device's
@@ -737,21 +759,20 @@ def _rot6d_matrices64(d: np.ndarray, columns: bool) -> np.ndarray:
     return np.swapaxes(R, -1, -2) if columns else R
 
 
+def _rot6d_rows64(x: np.ndarray, J: int, mean, n_out: int, Lf: int, M: int) -> np.ndarray:
+    """x [n, 6J] -> the 6-D vectors [n_out, J, 6] of the output frames: plus the mean, then blended; the chain runs on the blended frame."""
+    x = x.reshape(len(x), J, 6)
+    if mean is not None:
+        x = x + mean.reshape(J, 6)
+    return _resample64(x, n_out, Lf, M)
+
+
 def _articulate64(v: np.ndarray, tree: JointTree, frames: List[int], mean, glob: bool, Lf: int, M: int):
     """v [B, T, 6J] float64, frames [B] -> (joints [B, T_out, J, 3], rotations [B, T_out, J, 4])."""
-    B, T, _D = v.shape
     J = tree.J
-    t_out = -(-T * Lf // M)
-    joints, rot = np.zeros((B, t_out, J, 3)), np.zeros((B, t_out, J, 4))
-    for b in range(B):
-        n = frames[b]
-        if n < 1:
-            continue
-        x = v[b, :n].reshape(n, J, 6)
-        if mean is not None:
-            x = x + mean.reshape(J, 6)
-        n_out = -(-n * Lf // M)
-        x = _resample64(x, n_out, Lf, M)                        # the 6-D vectors are blended, then the chain runs on the blended frame
+
+    def row(x, n, n_out):                                       # position | quaternion, seven numbers per joint
+        x = _rot6d_rows64(x, J, mean, n_out, Lf, M)
         R = _rot6d_matrices64(x, tree.basis == "columns")
         G, p = np.zeros_like(R), np.zeros((n_out, J, 3))
         for j in range(J):
@@ -761,28 +782,29 @@ def _articulate64(v: np.ndarray, tree: JointTree, frames: List[int], mean, glob:
             else:
                 G[:, j] = G[:, a] @ R[:, j]
                 p[:, j] = p[:, a] + G[:, a] @ tree.offsets[j]
-        joints[b, :n_out], rot[b, :n_out] = p, _quat64(G if glob else R)
-    return joints, rot
+        return np.concatenate([p, _quat64(G if glob else R)], -1)
+    out = _valid_rows64(v, frames, (J, 7), row, Lf, M)
+    return out[..., :3], out[..., 3:]
+
+
+def _first_two64(m: np.ndarray, tree: JointTree, mean) -> np.ndarray:
+    """m [n, J, 3, 3] -> [n, 6J]: the first two rows (``basis="rows"``) or columns of every matrix as ``a1 | a2``, minus the mean."""
+    if tree.basis == "columns":
+        m = np.swapaxes(m, -1, -2)
+    d = m[..., :2, :].reshape(len(m), 6 * tree.J)
+    return d if mean is None else d - mean
 
 
 def _rot6d64(q: np.ndarray, tree: JointTree, frames: List[int], mean) -> np.ndarray:
     """q [B, T, J, 4] float64 -> [B, T, 6J]."""
-    B, T = q.shape[:2]
-    out = np.zeros((B, T, 6 * tree.J))
-    for b in range(B):
-        n = frames[b]
-        if n < 1:
-            continue
-        u = q[b, :n] / np.maximum(np.sqrt((q[b, :n] * q[b, :n]).sum(-1, keepdims=True)), 1e-12)
+    def row(qn, n, _n_out):
+        u = qn / np.maximum(np.sqrt((qn * qn).sum(-1, keepdims=True)), 1e-12)
         w, x, y, z = (u[..., i] for i in range(4))
         m = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
                       2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
                       2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], -1).reshape(n, tree.J, 3, 3)
-        if tree.basis == "columns":
-            m = np.swapaxes(m, -1, -2)
-        d = m[..., :2, :].reshape(n, 6 * tree.J)
-        out[b, :n] = d if mean is None else d - mean
-    return out
+        return _first_two64(m, tree, mean)
+    return _valid_rows64(q, frames, (6 * tree.J,), row)
 
 
 def launch_articulate(track: torch.Tensor, tree: JointTree, d_frames: Optional[torch.Tensor] = None, draws: int = 1, frame_unit: int = 1,
@@ -824,31 +846,14 @@ def launch_rot6d(quat: torch.Tensor, tree: JointTree, d_frames: Optional[torch.T
     return out
 
 
-def _tree_checked(track, tree, who: str) -> JointTree:
-    if not isinstance(tree, JointTree):
-        raise L.EgError(f"{who}: tree must be a JointTree, got {type(tree).__name__}")
-    shape = tuple(track.shape)
-    if len(shape) < 2 or shape[-2] < 1:
-        raise L.EgError(f"{who}: track shape {shape}: need [..., T >= 1, {tree.pose_dim}]")
-    if shape[-1] != tree.pose_dim:
-        raise L.EgError(f"{who}: track shape {shape}: a tree of J={tree.J} joints takes 6J={tree.pose_dim} columns per frame, not {shape[-1]}")
-    return tree
-
-
 def _articulate(track, tree, frames, mean, fps, space: str, want_joints: bool, who: str):
     """Both forward functions: the joints or the rotations of ``track`` under its leading axes."""
-    tree = _tree_checked(track, tree, who)
-    sp = _space(space, who)
-    fe = _front(track, tree, frames, fps, who)
-    if _is_cuda(track):
-        x = _dev32(track).reshape(fe.U * fe.R, fe.T, tree.pose_dim)
-        res = launch_articulate(x, tree, _frames_dev(fe.fr, x.device), fe.R, 1, _mean_dev(mean, tree.pose_dim, x.device, who), space, fe.ratio,
-                                joints=want_joints, rotations=not want_joints)[0 if want_joints else 1]
-    else:
-        v = _host64(track, who).reshape(fe.U * fe.R, fe.T, tree.pose_dim)
-        res = _articulate64(v, tree, fe.per_row, _mean_host(mean, tree.pose_dim, who), sp == L.EG_SKELETON_SPACE_GLOBAL,
-                            *fe.ratio)[0 if want_joints else 1]
-    return _finish(res, track, fe, (tree.J, 3 if want_joints else 4), frames, fps)
+    tree = _track_checked(track, tree, JointTree, who)
+    sp, pick = _space(space, who), 0 if want_joints else 1
+    return _forward(track, tree, frames, mean, fps, who, (tree.J, 3 if want_joints else 4),
+                    lambda x, fe, d_frames, d_mean: launch_articulate(x, tree, d_frames, fe.R, 1, d_mean, space, fe.ratio, joints=want_joints,
+                                                                      rotations=not want_joints)[pick],
+                    lambda v, fe, mean64: _articulate64(v, tree, fe.per_row, mean64, sp == L.EG_SKELETON_SPACE_GLOBAL, *fe.ratio)[pick])
 
 
 def joints_from_rot6d(track, tree: JointTree, frames=None, mean=None, fps=None):
@@ -874,20 +879,10 @@ def rot6d_from_rotations(quat, tree: JointTree, frames=None, mean=None):
     generator takes from motion capture, the counterpart of ``dir_vec_from_joints``.  Zeros from ``frames[u]`` on.  CUDA in: the kernel,
     fp32; numpy / CPU in: float64."""
     who = "rot6d_from_rotations"
-    if not isinstance(tree, JointTree):
-        raise L.EgError(f"{who}: tree must be a JointTree, got {type(tree).__name__}")
-    shape = tuple(quat.shape)
-    if len(shape) < 3 or shape[-2:] != (tree.J, 4) or shape[-3] < 1:
-        raise L.EgError(f"{who}: quat shape {shape}: need [..., T >= 1, {tree.J}, 4] for a tree of {tree.J} joints")
-    lead, U, R = _lead(shape, 3, who)
-    T = shape[-3]
-    fr = _frames_list(frames, U, T, who)
-    if _is_cuda(quat):
-        q = _dev32(quat).reshape(U * R, T, tree.J, 4)
-        return launch_rot6d(q, tree, _frames_dev(fr, q.device), R, 1, _mean_dev(mean, tree.pose_dim, q.device, who)).reshape(lead + (T, tree.pose_dim))
-    q = _host64(quat, who).reshape(U * R, T, tree.J, 4)
-    d = _rot6d64(q, tree, _per_row(fr, U, R, T), _mean_host(mean, tree.pose_dim, who)).reshape(lead + (T, tree.pose_dim))
-    return torch.from_numpy(d) if isinstance(quat, torch.Tensor) else d
+    tree = _inverse(quat, tree, JointTree, "quat", 4, who)
+    return _per_frame(quat, 3, frames, who, (tree.pose_dim,),
+                      lambda q, d_frames, R: launch_rot6d(q, tree, d_frames, R, 1, _mean_dev(mean, tree.pose_dim, q.device, who)),
+                      lambda q, per_row: _rot6d64(q, tree, per_row, _mean_host(mean, tree.pose_dim, who)))
 
 
 # ---- Euler channels of 6-D rotation tracks, their inverse, and the Euler filter ------------------------------------------------------------------
@@ -912,7 +907,8 @@ def order_codes(order, J: int, who: str = "order") -> np.ndarray:
     return np.array(codes, np.int32)
 
 
-def _axes(code: int) -> Tuple[int, int, int, float]:
+def order_axes(code: int) -> Tuple[int, int, int, float]:
+    """An order code -> its axes ``(i, j, k)`` and ``eps``: +1 for XYZ, YZX, ZXY (``j`` follows ``i`` cyclically), -1 for the others."""
     i, j, k = ("XYZ".index(ch) for ch in ORDERS[int(code)])
     return i, j, k, (1.0 if j == (i + 1) % 3 else -1.0)
 
@@ -921,7 +917,7 @@ def _euler_of_matrices64(R: np.ndarray, codes: np.ndarray) -> np.ndarray:
     """R [..., J, 3, 3] -> (a, b, c) [..., J, 3] in radians: the definition of include/emogest.h in float64."""
     out = np.zeros(R.shape[:-2] + (3,))
     for jt, code in enumerate(codes):
-        i, j, k, eps = _axes(code)
+        i, j, k, eps = order_axes(code)
         m = R[..., jt, :, :]
         s = eps * m[..., i, k]
         lock = 1.0 - np.abs(s) < 2.0 ** -20
@@ -944,7 +940,7 @@ def _matrices_of_euler64(e: np.ndarray, codes: np.ndarray) -> np.ndarray:
     """(a, b, c) [..., J, 3] in radians -> R = R_i(a) R_j(b) R_k(c) [..., J, 3, 3]."""
     R = np.zeros(e.shape[:-1] + (3, 3))
     for jt, code in enumerate(codes):
-        i, j, k, _eps = _axes(code)
+        i, j, k, _eps = order_axes(code)
         R[..., jt, :, :] = _axis_rotation64(i, e[..., jt, 0]) @ _axis_rotation64(j, e[..., jt, 1]) @ _axis_rotation64(k, e[..., jt, 2])
     return R
 
@@ -961,20 +957,10 @@ def _unwrap64(p: np.ndarray, frames: List[int], period: float) -> np.ndarray:
 
 def _euler64(v: np.ndarray, tree: JointTree, codes: np.ndarray, frames: List[int], mean, Lf: int, M: int, degrees: bool) -> np.ndarray:
     """v [B, T, 6J] float64 -> [B, T_out, J, 3]."""
-    B, T, _D = v.shape
-    J = tree.J
-    out = np.zeros((B, -(-T * Lf // M), J, 3))
-    for b in range(B):
-        n = frames[b]
-        if n < 1:
-            continue
-        x = v[b, :n].reshape(n, J, 6)
-        if mean is not None:
-            x = x + mean.reshape(J, 6)
-        n_out = -(-n * Lf // M)
-        e = _euler_of_matrices64(_rot6d_matrices64(_resample64(x, n_out, Lf, M), tree.basis == "columns"), codes)
-        out[b, :n_out] = np.degrees(e) if degrees else e
-    return out
+    def row(x, _n, n_out):
+        e = _euler_of_matrices64(_rot6d_matrices64(_rot6d_rows64(x, tree.J, mean, n_out, Lf, M), tree.basis == "columns"), codes)
+        return np.degrees(e) if degrees else e
+    return _valid_rows64(v, frames, (tree.J, 3), row, Lf, M)
 
 
 class _Orders:
@@ -1066,22 +1052,27 @@ def euler_from_rot6d(track, tree: JointTree, order, frames=None, mean=None, fps=
     where a joint passes through the lock.  A CUDA tensor: one launch (plus the unwrap launches), fp32; numpy or a CPU tensor: float64.
     With ``frames`` or ``fps`` the result is ``(euler, joint_frames)``; zeros from ``joint_frames[u]`` on."""
     who = "euler_from_rot6d"
-    tree = _tree_checked(track, tree, who)
+    tree = _track_checked(track, tree, JointTree, who)
     o = _Orders.get(order, tree.J, f"{who}: order")
-    fe = _front(track, tree, frames, fps, who)
     period = 360.0 if degrees else 2.0 * math.pi
-    if _is_cuda(track):
-        x = _dev32(track).reshape(fe.U * fe.R, fe.T, tree.pose_dim)
-        res = launch_euler(x, tree, order, _frames_dev(fe.fr, x.device), fe.R, 1, _mean_dev(mean, tree.pose_dim, x.device, who), fe.ratio, degrees)
-        if unwrap:
-            launch_unwrap(res.view(fe.U * fe.R, fe.t_out, 3 * tree.J), _frames_dev(fe.n_out if fe.fr is not None else None, x.device), fe.R, 1, period)
-    else:
-        v = _host64(track, who).reshape(fe.U * fe.R, fe.T, tree.pose_dim)
-        res = _euler64(v, tree, o.codes, fe.per_row, _mean_host(mean, tree.pose_dim, who), *fe.ratio, degrees)
+
+    def on_device(x, fe, d_frames, d_mean):
+        res = launch_euler(x, tree, order, d_frames, fe.R, 1, d_mean, fe.ratio, degrees)
+        return _unwrapped(res, fe, period) if unwrap else res
+
+    def on_host(v, fe, mean64):
+        res = _euler64(v, tree, o.codes, fe.per_row, mean64, *fe.ratio, degrees)
         if unwrap:
             n_rows = [n for n in fe.n_out for _ in range(fe.R)]
             res = _unwrap64(res.reshape(fe.U * fe.R, fe.t_out, 3 * tree.J), n_rows, period)
-    return _finish(res, track, fe, (tree.J, 3), frames, fps)
+        return res
+    return _forward(track, tree, frames, mean, fps, who, (tree.J, 3), on_device, on_host)
+
+
+def _unwrapped(euler: torch.Tensor, fe: SimpleNamespace, period: float) -> torch.Tensor:
+    """The Euler filter over ``euler [U * R, T_out, J, 3]`` on the device, in place, on the valid output frames of the front end ``fe``."""
+    launch_unwrap(euler.view(fe.U * fe.R, fe.t_out, -1), _frames_dev(fe.n_out if fe.fr is not None else None, euler.device), fe.R, 1, period)
+    return euler
 
 
 def rot6d_from_euler(euler, tree: JointTree, order, frames=None, mean=None, degrees: bool = True):
@@ -1090,31 +1081,16 @@ def rot6d_from_euler(euler, tree: JointTree, order, frames=None, mean=None, degr
     the ``seed_pose`` or the target track of a BEAT generator from a BVH file's channels.  Zeros from ``frames[u]`` on.  CUDA in: the
     kernel, fp32; numpy / CPU in: float64."""
     who = "rot6d_from_euler"
-    if not isinstance(tree, JointTree):
-        raise L.EgError(f"{who}: tree must be a JointTree, got {type(tree).__name__}")
-    shape = tuple(euler.shape)
-    if len(shape) < 3 or shape[-2:] != (tree.J, 3) or shape[-3] < 1:
-        raise L.EgError(f"{who}: euler shape {shape}: need [..., T >= 1, {tree.J}, 3] for a tree of {tree.J} joints")
+    tree = _inverse(euler, tree, JointTree, "euler", 3, who)
     o = _Orders.get(order, tree.J, f"{who}: order")
-    lead, U, R = _lead(shape, 3, who)
-    T = shape[-3]
-    fr = _frames_list(frames, U, T, who)
-    if _is_cuda(euler):
-        e = _dev32(euler).reshape(U * R, T, tree.J, 3)
-        return launch_rot6d_euler(e, tree, order, _frames_dev(fr, e.device), R, 1, _mean_dev(mean, tree.pose_dim, e.device, who),
-                                  degrees).reshape(lead + (T, tree.pose_dim))
-    e = _host64(euler, who).reshape(U * R, T, tree.J, 3)
-    mh = _mean_host(mean, tree.pose_dim, who)
-    d = np.zeros((U * R, T, tree.pose_dim))
-    for b, n in enumerate(_per_row(fr, U, R, T)):
-        if n < 1:
-            continue
-        m = _matrices_of_euler64(np.radians(e[b, :n]) if degrees else e[b, :n], o.codes)
-        if tree.basis == "columns":
-            m = np.swapaxes(m, -1, -2)
-        d[b, :n] = m[..., :2, :].reshape(n, tree.pose_dim) - (0.0 if mh is None else mh)
-    d = d.reshape(lead + (T, tree.pose_dim))
-    return torch.from_numpy(d) if isinstance(euler, torch.Tensor) else d
+
+    def on_host(e, per_row):
+        mh = _mean_host(mean, tree.pose_dim, who)
+        return _valid_rows64(e, per_row, (tree.pose_dim,),
+                             lambda en, _n, _n_out: _first_two64(_matrices_of_euler64(np.radians(en) if degrees else en, o.codes), tree, mh))
+    return _per_frame(euler, 3, frames, who, (tree.pose_dim,),
+                      lambda e, d_frames, R: launch_rot6d_euler(e, tree, order, d_frames, R, 1, _mean_dev(mean, tree.pose_dim, e.device, who), degrees),
+                      on_host)
 
 
 def unwrap_angles(angles, frames=None, period: float = 360.0):
@@ -1128,14 +1104,8 @@ def unwrap_angles(angles, frames=None, period: float = 360.0):
     shape = tuple(angles.shape)
     if len(shape) < 2 or shape[-2] < 1 or shape[-1] < 1:
         raise L.EgError(f"{who}: angles shape {shape}: need [..., T >= 1, C >= 1]")
-    lead, U, R = _lead(shape, 2, who)
-    T, Cc = shape[-2], shape[-1]
-    fr = _frames_list(frames, U, T, who)
-    if _is_cuda(angles):
-        a = angles.detach().to(torch.float32).reshape(U * R, T, Cc).clone()
-        return launch_unwrap(a, _frames_dev(fr, a.device), R, 1, period).reshape(shape)
-    out = _unwrap64(_host64(angles, who).reshape(U * R, T, Cc), _per_row(fr, U, R, T), period).reshape(shape)
-    return torch.from_numpy(out) if isinstance(angles, torch.Tensor) else out
+    return _per_frame(angles, 2, frames, who, shape[-1:], lambda a, d_frames, R: launch_unwrap(a.clone(), d_frames, R, 1, period),
+                      lambda a, per_row: _unwrap64(a, per_row, period))
 
 
 def euler_args(who: str, joints, euler, euler_unwrap: bool = False, unwrap_allowed: bool = True):
@@ -1162,48 +1132,104 @@ def euler_args(who: str, joints, euler, euler_unwrap: bool = False, unwrap_allow
     return [ORDERS[c] for c in order_codes(euler, joints.J, f"{who}: euler")]
 
 
-def _output_args_early(who: str, joints, joints_fps, rotations, fps_allowed: bool = True) -> None:
-    """The part of ``output_args`` that needs no model: what a caller refuses before it looks at anything else."""
-    if not fps_allowed and joints_fps is not None:
-        raise L.EgError(f"{who}: joints_fps= is not supported (a frame-rate change needs the frame after the last one emitted, which a "
-                        "stream does not have yet); resample the joints of the finished track with skeleton.joints_from_tracks(..., fps=)")
-    if rotations is not None and joints is None:
-        raise L.EgError(f"{who}: rotations= without joints=skeleton (the rest pose belongs to a skeleton's bones)")
 
 
-def output_args(who: str, pose_dim: int, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, fps_allowed: bool = True,
-                hint: str = ""):
-    """The skeleton-output arguments of a caller (``synthesize``, ``GestureStream``: ``who``, the prefix of every message), checked before
-    anything runs; returns the rest pose of ``rotations=`` on ``joints``' skeleton, or None.  With ``joints=JointTree`` (``6J == pose_dim``;
-    ``rotations=True`` is the only other value, ``joints_unit`` is refused) it returns True where rotations are asked for.  ``pose_dim``: the model's; ``fps_allowed``: the
-    caller can change the frame rate; ``hint`` ends the message about a skeleton that does not fit ``pose_dim``."""
-    _output_args_early(who, joints, joints_fps, rotations, fps_allowed)
-    if rotations is None and rotations_space != "local":
-        raise L.EgError(f"{who}: rotations_space without rotations=rest")
-    if joints is None:
-        if joints_mean is not None or joints_unit or joints_fps is not None:
-            raise L.EgError(f"{who}: joints_mean / joints_unit{' / joints_fps' if fps_allowed else ''} without joints=skeleton")
-        return None
-    if isinstance(joints, JointTree):                                              # the second body type: 6-D joint rotations
-        if joints.pose_dim != pose_dim:
-            raise L.EgError(f"{who}: joints=: the joint tree has J={joints.J} joints, 6J={joints.pose_dim} != pose_dim={pose_dim}")
-        if joints_unit:
-            raise L.EgError(f"{who}: joints_unit=True with joints=JointTree (Gram-Schmidt already normalises the 6-D rotations; joints_unit "
-                            "re-normalises a Skeleton's bone vectors)")
-        if rotations is not None and rotations is not True:
-            raise L.EgError(f"{who}: rotations= with joints=JointTree takes True, got {type(rotations).__name__} (the tree's offsets are the "
-                            "bind pose: there is no rest)")
-        rate_ratio(joints_fps, f"{who}: joints_fps")
-        if rotations is None:
+# ---- the output stage of the callers -------------------------------------------------------------------------------------------------------
+class TrackOutputs:
+    """The output stage of a caller (``synthesize``, ``GestureStream``: ``who``, the prefix of every message): the one place that knows which
+    launches turn pose rows into the joints, rotations and Euler channels the caller asked for.  Construction checks the caller's arguments
+    before anything runs, in two steps: here what needs no model (``streaming``: the caller is a stream, which refuses ``joints_fps`` and
+    ``euler_unwrap``), in ``fit`` the rest against the model's ``pose_dim`` -- at once where ``pose_dim`` is given; ``hint`` ends the message
+    about a skeleton that does not fit it.  Plain fields: ``body`` (the Skeleton or JointTree), ``tree`` (it is a JointTree), ``unit``,
+    ``ratio`` (the reduced ``(L, M)`` of ``joints_fps``), ``rest`` (a RestPose; None without rotations, and with a tree, whose offsets are
+    the bind pose), ``want_rotations``, ``space``, ``euler`` (the J order strings, or None), ``unwrap``, and ``made``: the outputs' names in
+    launch order.  ``to(device)`` makes the device copies of the mean, the tables and the order codes and holds them: their addresses are
+    what a captured graph replays."""
+
+    def __init__(self, who: str, joints, joints_mean=None, joints_unit: bool = False, joints_fps=None, rotations=None,
+                 rotations_space: str = "local", euler=None, euler_unwrap: bool = False, pose_dim: Optional[int] = None,
+                 streaming: bool = False, hint: str = ""):
+        self.who, self.streaming, self.hint = who, bool(streaming), hint
+        self.body, self.tree = joints, isinstance(joints, JointTree)
+        self.unit, self.fps, self.space, self.unwrap = bool(joints_unit), joints_fps, rotations_space, bool(euler_unwrap)
+        self._mean, self._rotations, self._device = joints_mean, rotations, None
+        if streaming and joints_fps is not None:
+            raise L.EgError(f"{who}: joints_fps= is not supported (a frame-rate change needs the frame after the last one emitted, which a "
+                            "stream does not have yet); resample the joints of the finished track with skeleton.joints_from_tracks(..., fps=)")
+        if rotations is not None and joints is None:
+            raise L.EgError(f"{who}: rotations= without joints=skeleton (the rest pose belongs to a skeleton's bones)")
+        if pose_dim is not None:
+            self.fit(pose_dim)
+        self.euler = euler_args(who, joints, euler, euler_unwrap, unwrap_allowed=not streaming)
+        self.orders = None if self.euler is None else _Orders.get(self.euler, joints.J, f"{who}: euler")
+
+    def fit(self, pose_dim: int) -> Optional["TrackOutputs"]:
+        """The second step: the arguments against each other and against the model's ``pose_dim``; returns the stage, or None when no output
+        was asked for."""
+        who, body, rotations = self.who, self.body, self._rotations
+        if rotations is None and self.space != "local":
+            raise L.EgError(f"{who}: rotations_space without rotations=rest")
+        if body is None:
+            if self._mean is not None or self.unit or self.fps is not None:
+                raise L.EgError(f"{who}: joints_mean / joints_unit{'' if self.streaming else ' / joints_fps'} without joints=skeleton")
             return None
-        _space(rotations_space, f"{who}: rotations_space")
-        return True
-    if not isinstance(joints, Skeleton):
-        raise L.EgError(f"{who}: joints= takes a skeleton.Skeleton, got {type(joints).__name__}")
-    if joints.pose_dim != pose_dim:
-        raise L.EgError(f"{who}: joints=: the skeleton has K={joints.K} bones, 3K={joints.pose_dim} != pose_dim={pose_dim}{hint}")
-    rate_ratio(joints_fps, f"{who}: joints_fps")                                   # refuses an unsupported ratio
-    if rotations is None:
-        return None
-    _space(rotations_space, f"{who}: rotations_space")                             # and a bad space or rest pose
-    return joints.rest_pose(rotations)
+        if self.tree:                                                                  # the second body type: 6-D joint rotations
+            if body.pose_dim != pose_dim:
+                raise L.EgError(f"{who}: joints=: the joint tree has J={body.J} joints, 6J={body.pose_dim} != pose_dim={pose_dim}")
+            if self.unit:
+                raise L.EgError(f"{who}: joints_unit=True with joints=JointTree (Gram-Schmidt already normalises the 6-D rotations; joints_unit "
+                                "re-normalises a Skeleton's bone vectors)")
+            if rotations is not None and rotations is not True:
+                raise L.EgError(f"{who}: rotations= with joints=JointTree takes True, got {type(rotations).__name__} (the tree's offsets are the "
+                                "bind pose: there is no rest)")
+        elif not isinstance(body, Skeleton):
+            raise L.EgError(f"{who}: joints= takes a skeleton.Skeleton, got {type(body).__name__}")
+        elif body.pose_dim != pose_dim:
+            raise L.EgError(f"{who}: joints=: the skeleton has K={body.K} bones, 3K={body.pose_dim} != pose_dim={pose_dim}{self.hint}")
+        self.ratio = rate_ratio(self.fps, f"{who}: joints_fps")                        # refuses an unsupported ratio
+        self.want_rotations, self.rest = rotations is not None, None
+        if self.want_rotations:
+            _space(self.space, f"{who}: rotations_space")                              # and a bad space or rest pose
+            self.rest = None if self.tree else body.rest_pose(rotations)
+        return self
+
+    @property
+    def made(self) -> Tuple[str, ...]:
+        return ("joints",) + ("rotations",) * self.want_rotations + ("euler",) * (self.euler is not None)
+
+    def to(self, device) -> "TrackOutputs":
+        """The device copies, made once per device: ``mean`` here, the tables and the order codes where they are cached, held here."""
+        if self._device != str(device):
+            self.mean = _mean_dev(self._mean, self.body.pose_dim, device, f"{self.who}: joints_mean")
+            self._held = (self.body.table(device), self.rest and self.rest.table(device), self.orders and _Orders.table(self.orders, device))
+            self._device = str(device)
+        return self
+
+    def launch(self, rows: torch.Tensor, d_frames: Optional[torch.Tensor] = None, draws: int = 1, frame_unit: int = 1,
+               want: Sequence[str] = ("joints", "rotations", "euler")) -> dict:
+        """Those of the outputs ``want`` names that the caller asked for, of ``rows [B, T, pose_dim]`` (contiguous fp32 on the device of
+        ``to``, 16-byte aligned; ``d_frames``, ``draws``, ``frame_unit`` as in ``launch_joints``) -> ``{name: [B, T_out, ., .]}``.  Nothing
+        but the launches, so it can be captured: a tree's joints and rotations from one ``launch_articulate`` and its Euler channels from
+        one ``launch_euler``; a skeleton's from ``launch_joints`` and ``launch_rotations``."""
+        j, q, e = (n in want and n in self.made for n in ("joints", "rotations", "euler"))
+        args, out = (d_frames, draws, frame_unit, self.mean), {}
+        if self.tree and (j or q):
+            out["joints"], out["rotations"] = launch_articulate(rows, self.body, *args, self.space if q else "local", self.ratio, joints=j, rotations=q)
+        if not self.tree and j:
+            out["joints"] = launch_joints(rows, self.body, *args, self.unit, self.ratio)
+        if not self.tree and q:
+            out["rotations"] = launch_rotations(rows, self.body, self.rest, *args, self.space, self.ratio)
+        if e:
+            out["euler"] = launch_euler(rows, self.body, self.euler, *args, self.ratio)
+        return {n: v for n, v in out.items() if v is not None}
+
+    def tracks(self, poses: torch.Tensor, frames) -> dict:
+        """Whole tracks ``poses [U, (R,) T, pose_dim]`` with ``frames [U]`` valid poses per recording -> every output under the leading axes
+        of ``poses``, ``[U, (R,) T_out, ., .]``, and ``"joint_frames"``, the valid output frames per recording; the Euler channels
+        unwrapped where the caller asked for it."""
+        fe = _front(poses, self.body, frames, self.fps, f"{self.who}: joints")
+        x = _dev32(poses).reshape(fe.U * fe.R, fe.T, self.body.pose_dim)
+        out = self.to(x.device).launch(x, _frames_dev(fe.fr, x.device), fe.R)
+        if self.unwrap:
+            _unwrapped(out["euler"], fe, 360.0)
+        return dict({n: v.reshape(fe.lead + tuple(v.shape[1:])) for n, v in out.items()}, joint_frames=fe.n_out)

@@ -175,10 +175,9 @@ class GestureStream:
                  fps: int = 15, sample_rate: int = 16000, alpha: Optional[torch.Tensor] = None, graph: bool = True, want_windows: bool = False,
                  draws: Optional[int] = None, audio_rate: Optional[int] = None, joints=None, joints_mean=None, joints_unit: bool = False,
                  joints_fps=None, rotations=None, rotations_space: str = "local", smooth=None, euler=None, euler_unwrap: bool = False):
-        SK._output_args_early("GestureStream", joints, joints_fps, rotations, fps_allowed=False)
-        # the order table is held here: the captured graph replays the address of its device copy
-        self._euler = SK.euler_args("GestureStream", joints, euler, euler_unwrap, unwrap_allowed=False)
-        self._euler_hold = None if self._euler is None else SK._Orders.get(self._euler, joints.J, "GestureStream: euler")
+        # the output stage: what needs no model is checked here, the rest once pose_dim is known
+        outputs = SK.TrackOutputs("GestureStream", joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, euler, euler_unwrap,
+                                  streaming=True)
         if smooth is not None:
             if joints is not None:
                 raise L.EgError("GestureStream: smooth= together with joints= is not supported (the smoothed rows run half a window behind and "
@@ -199,11 +198,8 @@ class GestureStream:
         self.H = self.F - self.P
         self.text_len, self.n_mels, self.spec_len = c["text_len"], c["n_mels"], c["spec_len"]
         self.U = int(rows)
-        self._sk, self._sk_mean, self._sk_unit = joints, None, bool(joints_unit)
-        self._tree = isinstance(joints, SK.JointTree)            # 6-D joint rotations (6J == pose_dim): rotations=True, no rest pose
-        # the rest pose is held here: the captured graph replays the address of its device table
-        self._rest, self._rot_space = SK.output_args("GestureStream", self.D, joints, joints_mean, joints_unit, joints_fps, rotations,
-                                                     rotations_space, fps_allowed=False), rotations_space
+        # it holds the mean, the tables and the order codes on the device: the captured graph replays their addresses
+        self._outs: Optional[SK.TrackOutputs] = outputs.fit(self.D)
         if self.mel is not None:
             self.hop = int(round(self.H * sample_rate / fps)) if hop_samples is None else int(hop_samples)
             self.n = (self.spec_len - 1) * 512 if n_samples is None else int(n_samples)
@@ -230,8 +226,8 @@ class GestureStream:
         self.seed_pose = _need_cuda(seed_pose, "seed_pose").clone()
         self.alpha = None if alpha is None else _need_cuda(alpha, "alpha").clone()
         self.device = self.seed_pose.device
-        if self._sk is not None:
-            self._sk_mean = SK._mean_dev(joints_mean, self._sk.pose_dim, self.device, "GestureStream: joints_mean")
+        if self._outs is not None:
+            self._outs.to(self.device)
         if self.mel is AUTO_MEL:
             from .engine import MelFrontEnd
             self.mel = MelFrontEnd(self.device)
@@ -319,20 +315,11 @@ class GestureStream:
                 sampled = g["sampled"] if use_sampled else None
             out = eng.stream_step(self._state, *self._geom, spec, g["text"], sampled, self.alpha, want_window=self.want_windows,
                                   workspace=self._ws)
-            if self._tree:                          # a JointTree: joints and rotations of the rows just emitted from one launch
-                out["joints"], out["rotations"] = self._articulate(out["rows"], out["valid"], self.H)
-            elif self._sk is not None:              # one more launch after the hand-off: row u has valid[u] * H frames
-                out["joints"] = SK.launch_joints(out["rows"], self._sk, out["valid"], 1, self.H, self._sk_mean, self._sk_unit)
-            if self._rest is not None and not self._tree:
-                out["rotations"] = SK.launch_rotations(out["rows"], self._sk, self._rest, out["valid"], 1, self.H, self._sk_mean, self._rot_space)
-            if self._euler is not None:             # one more launch: the Euler channels of the rows just emitted
-                out["euler"] = SK.launch_euler(out["rows"], self._sk, self._euler, out["valid"], 1, self.H, self._sk_mean)
+            if self._outs is not None:              # the outputs of the rows just emitted, after the hand-off: row u has valid[u] * H frames
+                out.update(self._outs.launch(out["rows"], out["valid"], 1, self.H))
             if self._sm is not None:                # the outputs, then the new history in a launch of its own
                 out["smooth"] = self._sm.run(out["rows"], out["valid"])
             return out
-
-    def _articulate(self, rows: torch.Tensor, valid: Optional[torch.Tensor], frame_unit: int):
-        return SK.launch_articulate(rows, self._sk, valid, 1, frame_unit, self._sk_mean, self._rot_space, rotations=self._rest is not None)
 
     def _push_only(self):
         """The resampler's launches (with audio_rate), then the ring's: the part of a step that runs even when no row has a window."""
@@ -459,9 +446,8 @@ class GestureStream:
         # the host mirror follows the device: committed once the push has been enqueued (a launch or capture that raises leaves both where they were)
         self.plan.rows, self.last_valid, self.last_windows = rows, valid, [i["w"] for i in infos]
         self.last_window = out["window"].clone() if out is not None and self.want_windows else None
-        self.last_joints = out["joints"].clone() if out is not None and self._sk is not None else None
-        self.last_rotations = out["rotations"].clone() if out is not None and self._rest is not None else None
-        self.last_euler = out["euler"].clone() if out is not None and self._euler is not None else None
+        self.last_joints, self.last_rotations, self.last_euler = (out[name].clone() if out is not None and name in out else None
+                                                                  for name in ("joints", "rotations", "euler"))
         self.last_smooth = out["smooth"].clone() if out is not None and self._sm is not None else None
         if out is None:
             return None, torch.zeros(self.U, dtype=torch.int32, device=self.device)
@@ -521,28 +507,21 @@ class GestureStream:
 
     def tail_joints(self) -> torch.Tensor:
         """[U, P, J, 3]: the joints of `tail()` (a session opened with joints=)."""
-        if self._sk is None:
-            raise L.EgError("tail_joints: the session was opened without joints=skeleton")
-        with torch.no_grad():
-            if self._tree:
-                return SK.launch_articulate(self.tail(), self._sk, None, 1, 1, self._sk_mean, rotations=False)[0]
-            return SK.launch_joints(self.tail(), self._sk, None, 1, 1, self._sk_mean, self._sk_unit)
+        return self._tail_output("joints", "joints=skeleton")
 
     def tail_rotations(self) -> torch.Tensor:
         """[U, P, K, 4]: the bone rotations of `tail()` (a session opened with rotations=)."""
-        if self._rest is None:
-            raise L.EgError("tail_rotations: the session was opened without rotations=rest")
-        with torch.no_grad():
-            if self._tree:
-                return SK.launch_articulate(self.tail(), self._sk, None, 1, 1, self._sk_mean, self._rot_space, joints=False)[1]
-            return SK.launch_rotations(self.tail(), self._sk, self._rest, None, 1, 1, self._sk_mean, self._rot_space)
+        return self._tail_output("rotations", "rotations=rest")
 
     def tail_euler(self) -> torch.Tensor:
         """[U, P, J, 3]: the Euler channels of `tail()` in degrees (a session opened with euler=)."""
-        if self._euler is None:
-            raise L.EgError("tail_euler: the session was opened without euler=order")
+        return self._tail_output("euler", "euler=order")
+
+    def _tail_output(self, name: str, opened_with: str) -> torch.Tensor:
+        if self._outs is None or name not in self._outs.made:
+            raise L.EgError(f"tail_{name}: the session was opened without {opened_with}")
         with torch.no_grad():
-            return SK.launch_euler(self.tail(), self._sk, self._euler, None, 1, 1, self._sk_mean)
+            return self._outs.launch(self.tail(), want=(name,))[name]
 
     def tail_smooth(self) -> torch.Tensor:
         """[U, P + smooth_delay, D]: the last smoothed frames of every row's track (a session opened with smooth=); zeros for a row that has

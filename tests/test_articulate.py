@@ -368,9 +368,9 @@ def test_callers_check_the_joint_tree():
         ST.GestureStream((None, None, None), 1, beat_seed, joints=tree, joints_fps=(15, 30))
     with pytest.raises(L.EgError, match="GestureStream: smooth= together with joints= is not supported"):
         ST.GestureStream((None, None, None), 1, beat_seed, joints=tree, smooth=(9, 3))
-    assert SK.output_args("x", 282, tree, None, False, None, None, "local") is None
-    assert SK.output_args("x", 282, tree, None, False, (15, 30), True, "global") is True
+    assert SK.TrackOutputs("x", tree, None, False, None, None, "local", pose_dim=282).want_rotations is False
+    assert SK.TrackOutputs("x", tree, None, False, (15, 30), True, "global", pose_dim=282).want_rotations is True
     with pytest.raises(L.EgError, match="x: joints=: the joint tree has J=47 joints, 6J=282 != pose_dim=126"):
-        SK.output_args("x", 126, tree, None, False, None, True, "local", fps_allowed=False)
+        SK.TrackOutputs("x", tree, None, False, None, True, "local", pose_dim=126, streaming=True)
     with pytest.raises(L.EgError, match="x: joints_unit=True with joints=JointTree"):
-        SK.output_args("x", 282, tree, None, True, None, None, "local", fps_allowed=False)
+        SK.TrackOutputs("x", tree, None, True, None, None, "local", pose_dim=282, streaming=True)

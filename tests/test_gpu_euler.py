@@ -426,8 +426,11 @@ def test_graph_replay_equals_the_eager_call():
 
 
 # ---- callers -------------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", ["alone", "draws", "takes", "fps", "smooth"])
+@pytest.mark.parametrize("case", ["alone", "draws", "takes", "fps", "smooth", "all"])
 def test_synthesize_with_euler_equals_the_function_on_its_track(case):
+    """"all": joints, rotations and Euler channels of one call, recordings of unequal length at another frame rate, each bit for bit the
+    public function on out["track"].  The body is the 47-joint tree: a call refuses a tree whose 6J is not the generator's pose_dim (282 for
+    the one BEAT-shaped generator the suite builds), so the five-joint chain cannot go through synthesize."""
     model, vae = beat_models()
     tree = tree_of("upper47")
     orders = names_of(EN.orders_cyclic(tree.J))
@@ -450,8 +453,8 @@ def test_synthesize_with_euler_equals_the_function_on_its_track(case):
         fn = Hs.synthesize_takes
         kw.update(labels=g["label"][:, 0].contiguous(), z=zz, draws=2, lengths=lengths, euler_unwrap=True, rotations=True)
         unwrap = True
-    elif case == "fps":
-        kw.update(labels=g["label"][:, 0].contiguous(), z=g["z"], lengths=lengths, joints_fps=(15, 30))
+    elif case in ("fps", "all"):
+        kw.update(labels=g["label"][:, 0].contiguous(), z=g["z"], lengths=lengths, joints_fps=(15, 30), **(dict(rotations=True) if case == "all" else {}))
         fps = (15, 30)
     else:
         kw.update(labels=g["label"][:, 0].contiguous(), z=g["z"], lengths=lengths, smooth=(9, 3))
@@ -464,7 +467,11 @@ def test_synthesize_with_euler_equals_the_function_on_its_track(case):
     assert out["joint_frames"] == n_out == [SK.out_frames(n, fps) for n in frames]
     assert tuple(out["euler"].shape) == lead + (SK.out_frames(poses.shape[-2], fps), 47, 3) == tuple(out["joints"].shape)
     assert torch.equal(out["euler"], we) and torch.isfinite(we).all() and we[0].any()
-    assert ("rotations" in out) == (case == "takes")
+    assert ("rotations" in out) == (case in ("takes", "all"))
+    if case == "all":
+        wj, nj = SK.joints_from_rot6d(poses, tree, frames=frames, mean=mean, fps=fps)
+        wq, nq = SK.rotations_from_rot6d(poses, tree, frames=frames, mean=mean, fps=fps)
+        assert nj == nq == n_out and torch.equal(out["joints"], wj) and torch.equal(out["rotations"], wq) and wq[0].any()
     if case != "draws":
         assert wp == [3, 2] and not out["euler"][1, ..., n_out[1]:, :, :].any()
     if case == "alone":                                                                             # without euler=: the same, no "euler"
@@ -576,7 +583,7 @@ def _hist_child():
             s = Hs.open_stream((model, vae), U, g["seed_pose"], hop_samples=HOP, graph=graph, **kw)
             tree.table(dev())                                     # the tables' uploads are no launches of the library, but keep them out of the step
             if "euler" in kw:
-                SK._Orders.table(s._euler_hold, dev())
+                s._outs.to(dev())
             torch.cuda.synchronize()
             histogram(True)
             emitted = []

@@ -92,10 +92,10 @@ def main():
     codes = SK.order_codes(orders, J)
     rows7 = []
     for code in codes:
-        i, j, k, _e = SK._axes(code)
+        i, j, k, _e = SK.order_axes(code)
         rows7.append([3 * i + i, 3 * i + j, 3 * i + k, 3 * j + k, 3 * k + k, 3 * k + j, 3 * j + j])
     idx = torch.tensor(rows7, device=dev)
-    eps = torch.tensor([SK._axes(c)[3] for c in codes], device=dev)
+    eps = torch.tensor([SK.order_axes(c)[3] for c in codes], device=dev)
     rng = np.random.default_rng(64)
     ragged = [frames_of(s) for s in rng.uniform(12, 89, 64)]
     cases = {"u8_30s_x8": ([frames_of(30)] * 8, 8, (1, 1), False), "ten_min_x32": ([frames_of(600)], 32, (1, 1), False),
