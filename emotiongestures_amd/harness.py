@@ -465,7 +465,7 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
                want_windows: bool = False, want_aux: bool = False, mel=None, lengths=None, draws: Optional[int] = None,
                beat: bool = False, diversity=None, audio_rate: Optional[int] = None, joints=None, joints_mean=None,
                joints_unit: bool = False, joints_fps=None, rotations=None, rotations_space: str = "local", smooth=None, euler=None,
-               euler_unwrap: bool = False) -> Dict[str, torch.Tensor]:
+               euler_unwrap: bool = False, kinematics=None) -> Dict[str, torch.Tensor]:
     """One gesture track per utterance from raw 16 kHz audio: windows -> mel -> optional CVAE sample per window -> roll-out.
 
     ``models = (generator, vae | None)``, eval mode, on the GPU.  ``audio [U, total_samples]``; ``text [U, W, 60]`` (the words of every
@@ -532,10 +532,20 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     ``"track"``: ``smooth.smooth_tracks(out["track"], smooth, frames)``, a Savitzky-Golay filter (``scipy.signal.savgol_filter``,
     ``mode="interp"``) over recording u's own valid poses, zeros behind them, one launch.  ``"track"`` stays raw and ``beat`` / ``diversity`` keep
     scoring it (they measure the model); ``"joints"`` and ``"rotations"`` are then made from ``"track_smooth"`` (they are what a renderer
-    takes).  ``deriv != 0`` is refused by name: a velocity track is not a pose track -- call ``smooth_tracks`` for derivatives."""
+    takes).  ``deriv != 0`` is refused by name: a velocity track is not a pose track -- call ``smooth_tracks`` for derivatives.
+
+    ``kinematics=True | edges | SpeedBins`` (with ``joints=``; without it, refused by name): adds ``"kinematics"``, the motion statistics of
+    ``out["joints"]`` over the frames ``"joint_frames"`` counts -- ``kinematics.kinematics_of_joints(out["joints"], rate, out["joint_frames"],
+    edges)``: ``"speed"``, ``"accel"``, ``"jerk"`` ``[U, (R,) J]`` float64 (the means per joint in m/s, m/s^2, m/s^3), ``"speed_hist"``
+    ``[U, (R,) J, B]`` and ``"speed_over"`` ``[U, (R,) J]`` int32 and ``"edges"`` (m/s; ``True``: 0, 0.05 .. 2.0), one read of the joints on the
+    device.  ``rate`` is the output rate: ``joints_fps[1]`` when given, else ``fps``.  With ``smooth=`` the figures describe the smoothed
+    joints, because that is what ``out["joints"]`` holds; the raw figure is
+    ``kinematics_of_joints(skeleton.joints_from_tracks(out["track"], skeleton, frames, joints_mean, joints_unit, joints_fps)[0], rate,
+    out["joint_frames"])``.  Works with ``lengths`` and ``draws``; without ``kinematics`` no key and no launch changes."""
     outputs = _track_outputs("synthesize", seed_pose, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, euler, euler_unwrap)
+    kinematics = _kinematics_arg("synthesize", kinematics, outputs, joints_fps, fps)
     return _synthesize("synthesize", models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate,
-                       want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=False)
+                       want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=False, kinematics=kinematics)
 
 
 def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch.Tensor, labels: Optional[torch.Tensor] = None, *,
@@ -544,7 +554,7 @@ def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose:
                      want_windows: bool = False, want_aux: bool = False, mel=None, beat: bool = False, diversity=None,
                      audio_rate: Optional[int] = None, joints=None, joints_mean=None, joints_unit: bool = False, joints_fps=None,
                      rotations=None, rotations_space: str = "local", smooth=None, euler=None,
-                     euler_unwrap: bool = False) -> Dict[str, torch.Tensor]:
+                     euler_unwrap: bool = False, kinematics=None) -> Dict[str, torch.Tensor]:
     """``draws`` = R sampled takes for each of U recordings of any and unequal length, from raw audio, in one call: ``synthesize(lengths=)`` and
     ``synthesize(draws=)`` combined (a VAE is required).  ``audio [U, max_total]`` with ``lengths[u]`` real samples in row u (``None``: every
     row at full length); recording u has ``W_u = ceil(lengths[u] / hop_samples)`` windows, N = sum W_u.  ``text`` padded ``[U, Wmax, 60]`` or
@@ -555,10 +565,21 @@ def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose:
     zero past ``track_frames[u]``) plus packed ``"spec"`` and ``"windows_per"``.  Every other option is ``synthesize``'s, applied per take with
     recording u's own samples and poses: ``beat`` -> ``"beat"`` ``[U, R]``; ``diversity`` (R >= 2) -> ``"take_distance"`` ``[U, R, R]`` and
     ``"take_diversity"`` ``[U]``; ``joints`` -> ``[U, R, T', J, 3]``; ``rotations`` -> ``[U, R, T', K, 4]``; ``audio_rate``; ``smooth`` ->
-    ``"track_smooth"`` ``[U, R, T, pose_dim]``."""
+    ``"track_smooth"`` ``[U, R, T, pose_dim]``; ``kinematics`` (with ``joints``) -> ``"kinematics"``, the figures ``[U, R, J]`` per take."""
     outputs = _track_outputs("synthesize_takes", seed_pose, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, euler, euler_unwrap)
+    kinematics = _kinematics_arg("synthesize_takes", kinematics, outputs, joints_fps, fps)
     return _synthesize("synthesize_takes", models, audio, text, seed_pose, labels, hop_samples, n_samples, None, z, alpha, fps, sample_rate,
-                       want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=True)
+                       want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=True, kinematics=kinematics)
+
+
+def _kinematics_arg(who, kinematics, outputs, joints_fps, fps):
+    """The ``kinematics=`` argument of `synthesize` / `synthesize_takes`, checked before anything runs: the SpeedBins at the output rate, or None."""
+    if kinematics is None:
+        return None
+    if outputs is None:
+        raise L.EgError(f"{who}: kinematics= without joints= (the statistics are those of out[\"joints\"], in metres)")
+    from . import kinematics as KN
+    return KN.SpeedBins.of(kinematics, f"{who}: kinematics", fps if joints_fps is None else joints_fps[1])
 
 
 def _track_outputs(who, seed_pose, *args):
@@ -570,7 +591,7 @@ def _track_outputs(who, seed_pose, *args):
 
 
 def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate, want_windows, want_aux,
-                mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes):
+                mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes, kinematics=None):
     """The body of `synthesize` and `synthesize_takes` (`who` names the caller in errors): argument checks, resampling, the roll-out of the
     call's kind, then the per-track extras.  `outputs`: the caller's checked output stage (`_track_outputs`)."""
     gen, vae = models
@@ -647,6 +668,10 @@ def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samp
     if outputs is not None:                                                               # joints, rotations, Euler channels: skeleton.TrackOutputs
         with torch.no_grad():
             out.update(outputs.tracks(poses, frames))
+    if kinematics is not None:                                                            # of out["joints"]: the smoothed ones with smooth=
+        from . import kinematics as KN
+        with torch.no_grad():
+            out["kinematics"] = KN.kinematics_of_joints(out["joints"], kinematics.fps, frames=out["joint_frames"], edges=kinematics)
     return out
 
 

@@ -732,6 +732,45 @@ int eg_smooth_stream_tail(const void* state, int32_t rows, int32_t P, int32_t D,
                           float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Motion statistics of whole tracks: mean speed, acceleration and jerk per joint and a histogram of the joint speeds (csrc/kinematics.hip)
+ * ------------------------------------------------------------------------------------------ */
+/* Input: joint positions p [rows, T, J, 3] in fp32 metres (what eg_skeleton_joints / eg_articulate_forward write).  Row b has
+ * n = clamp(d_frames[b / draws] * frame_unit, 0, T) valid frames, exactly as in eg_smooth_tracks (d_frames NULL: T); frames t >= n may hold
+ * NaN and no sample at or beyond n enters any output.
+ * Differences, in fp32, one IEEE subtraction each, by successive differencing:
+ *     d1[t] = p[t+1] - p[t] for t < n - 1;   d2[t] = d1[t+1] - d1[t] for t < n - 2;   d3[t] = d2[t+1] - d2[t] for t < n - 3
+ * (no product in these steps, so contraction cannot change them and numpy in float32 reproduces them bit for bit).
+ * Squared magnitudes: s2_k[t, j] = (x*x + y*y) + z*z in fp64 of the three fp32 components of d_k[t, j], widened first: every square is exact
+ * (24-bit operands), so the value is the same with or without fused multiply-add.
+ * Means: mean[b, k - 1, j] = (sum_t sqrt(s2_k[t, j])) * fps^k / (n - k) for k = 1, 2, 3 -- m/s, m/s^2, m/s^3 --, the sum in fp64 in a fixed
+ * order that depends on the row's own n and on EG_KIN_TILE_FRAMES only; fps, fps^2 and fps^3 are formed on the host in fp64.
+ * Speed histogram: `edges` are E = bins + 1 ascending fp64 values in m/s with edges[0] == 0.  eg_kin_edges2 (host only, no HIP call, usable
+ * without a GPU) writes edges2[e] = q * q with q = edges[e] / fps, two fp64 operations; it refuses by name fewer than 2 or more than
+ * EG_KIN_MAX_BINS + 1 edges, edges[0] != 0, edges that are not strictly ascending, non-finite values and an fps that is not finite and > 0.
+ * Speed sample (t, j) falls into bin e when edges2[e] <= s2_1 < edges2[e + 1] and into the overflow column `bins` when s2_1 >= edges2[bins]
+ * (a value exactly on an edge belongs to the upper bin; no square root and no division for binning).  hist [rows, J, bins + 1] int32, the
+ * last column the overflow; hist[b, j] sums to n - 1.
+ * eg_kin_stats: three launches on `stream` -- hist = 0, the tiles, the means --; no allocation, no synchronisation, no floating-point
+ * atomics (integer atomics for the bins: order-free), plain vector stores; the grids depend on (rows, T, J, bins) only, so the call captures
+ * into a hipGraph.  A row's result does not depend on rows, on its place in the batch or on T.  workspace: eg_kin_workspace_bytes (0 for
+ * refused arguments), the [rows, tiles, 3, J] fp64 tile sums.  d_edges2: device copy of eg_kin_edges2's table.
+ * A row with n < 4 is refused by name from `frames`, the HOST copy of the counts (int32 [rows / draws]; NULL exactly when d_frames is NULL),
+ * the mechanism of eg_smooth_tracks; with a device count below 4 although the host count is not, that row's outputs are zeros and every
+ * access stays in range.
+ * Refuses by name before the first launch: null pointers, joints / workspace / mean / hist not 16-byte aligned, rows < 1, T < 4, J outside
+ * 1..EG_KIN_MAX_JOINTS, bins outside 1..EG_KIN_MAX_BINS, rows not a multiple of draws, frame_unit < 1, fps not finite or not positive, a host
+ * count below 4, a short workspace, grid / index range. */
+#define EG_KIN_MAX_JOINTS 64
+#define EG_KIN_MAX_BINS 256
+#define EG_KIN_TILE_FRAMES 64
+int32_t eg_kin_tile_frames(void);
+int eg_kin_edges2(const double* edges, int32_t n_edges, double fps, double* edges2);
+int64_t eg_kin_workspace_bytes(int32_t rows, int32_t T, int32_t J, int32_t bins);
+int eg_kin_stats(const float* joints, int32_t rows, int32_t T, int32_t J, const int32_t* frames, const int32_t* d_frames, int32_t draws,
+                 int32_t frame_unit, double fps, const double* d_edges2, int32_t bins, void* workspace, int64_t workspace_bytes, double* mean,
+                 int32_t* hist, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Beat-alignment score = model/Beat_score_v2.py alignment(sigma, order): load_audio + load_pose +
  * calculate_align for a batch of clips (test_emotion_gesture_diversity_iterative.py:241-248)
  * ------------------------------------------------------------------------------------------ */

@@ -26,6 +26,10 @@ their shape and the largest elbow swing in degrees.
 With --smooth K P the call also returns the smoothed track (smooth.smooth_tracks: a Savitzky-Golay filter of window K and polyorder P along
 time, scipy.signal.savgol_filter(mode="interp"), one more launch); with --joints the joints (and rotations) are made from it, and the script
 prints the mean frame-to-frame step of the left wrist before and after -- without --joints, of the pose vector.
+With --kinematics (and --joints, TED shape) the call also returns the motion statistics of the joints (kinematics.kinematics_of_joints: mean
+speed, acceleration and jerk per joint and a histogram of the joint speeds, one read of the joints on the device), and the script prints the
+mean speed and jerk of the two wrists -- with --smooth also those of the raw joints and the Hellinger distance between the raw and the smoothed
+speed histograms.
 With --beat --joints the body is a skeleton.JointTree -- the BEAT columns are one 6-D rotation per joint -- read from the HIERARCHY block of
 --bvh FILE (which must have 47 joints, or name them with --bvh-joints A,B,...), or a synthetic 47-joint upper body without --bvh: joint
 positions and, with --rotations, one local rotation per joint come from ONE more launch (skeleton.launch_articulate), and the script prints their
@@ -33,7 +37,7 @@ shapes, how far the deepest joint travels and the largest rotation angle.
 With --bvh FILE --bvh-out DIR the call also returns the Euler channels of every joint in the file's own channel orders (euler=BvhFile,
 euler_unwrap=True: one more launch and the Euler filter's three) and the script writes DIR/recording_U[_take_R].bvh -- the file's HIERARCHY,
 then the generated MOTION at the joints' frame rate -- one file per recording and take, formatted on the host (bvh.BvhFile.write).
-usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--bvh FILE [--bvh-joints A,B,...] [--bvh-out DIR]] [--joints-fps N] [--rotations]] [--smooth K P] [--out tracks.npz]"""
+usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--bvh FILE [--bvh-joints A,B,...] [--bvh-out DIR]] [--joints-fps N] [--rotations]] [--smooth K P] [--kinematics] [--out tracks.npz]"""
 import os
 import sys
 import time
@@ -49,7 +53,7 @@ from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
 from emotiongestures_amd.synth import load_synth_weights, synth_audio
 
 argv, DRAWS, OUT, BEAT, DIVERSITY, RATE, JOINTS, JOINTS_FPS, ROTATIONS, SMOOTH = [], 0, None, False, False, 16000, False, None, False, None
-BVH, BVH_JOINTS, BVH_OUT = None, None, None
+BVH, BVH_JOINTS, BVH_OUT, KINEMATICS = None, None, None, False
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--draws":
@@ -76,6 +80,8 @@ for a in it:
         BVH_OUT = next(it)
     elif a == "--smooth":
         SMOOTH = (int(next(it)), int(next(it)))
+    elif a == "--kinematics":
+        KINEMATICS = True
     else:
         argv.append(a)
 if DIVERSITY and DRAWS < 2:
@@ -88,6 +94,8 @@ if JOINTS_FPS and not JOINTS:
     sys.exit("--joints-fps needs --joints")
 if ROTATIONS and not JOINTS:
     sys.exit("--rotations needs --joints (the rest pose belongs to the skeleton's bones)")
+if KINEMATICS and (not JOINTS or BEAT):
+    sys.exit("--kinematics needs --joints without --beat (the statistics are those of the joints, in metres; the script names the TED wrists)")
 U = int(argv[0]) if len(argv) > 0 else 4
 seconds = float(argv[1]) if len(argv) > 1 else 60.0
 dev = torch.device("cuda:0")
@@ -171,7 +179,8 @@ if JOINTS and BEAT:
               f"formatted on the host in {time.perf_counter() - t0:.2f} s")
 elif JOINTS:
     from emotiongestures_amd.skeleton import ted_expressive
-    jk = dict(joints=ted_expressive(), joints_unit=True, joints_fps=(FPS, JOINTS_FPS) if JOINTS_FPS else None, smooth=SMOOTH)
+    jk = dict(joints=ted_expressive(), joints_unit=True, joints_fps=(FPS, JOINTS_FPS) if JOINTS_FPS else None, smooth=SMOOTH,
+              kinematics=True if KINEMATICS else None)
     if ROTATIONS:                                        # the rest pose: the first generated frame of recording 0 (normalised by the call)
         jk["rotations"] = track[0, PRIOR].reshape(-1, 3).cpu()
     H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, **jk, **AR)          # warm-up (uploads the bone table)
@@ -192,6 +201,20 @@ elif JOINTS:
         wrist_step = lambda j: float((j[:, 1:, 6] - j[:, :-1, 6]).norm(dim=2).mean())
         print(f"--smooth {SMOOTH[0]} {SMOOTH[1]}: track_smooth {tuple(jo['track_smooth'].shape)}, one more launch; mean frame-to-frame step of the left "
               f"wrist: {1e3 * wrist_step(raw):.2f} mm raw, {1e3 * wrist_step(joints):.2f} mm smoothed")
+    if KINEMATICS:                                       # of jo["joints"]: the smoothed ones with --smooth
+        from emotiongestures_amd import kinematics as KM
+        kin = jo["kinematics"]
+        wrists = lambda k, name: [round(float(k[name][:, j].mean()), 3) for j in (6, 7)]
+        print(f"--kinematics: one read of the joints ({kin['speed_hist'].shape[-1]} bins up to {kin['edges'][-1]:g} m/s); mean wrist speed (left, right) "
+              f"{wrists(kin, 'speed')} m/s, mean wrist jerk {wrists(kin, 'jerk')} m/s^3")
+        if SMOOTH:
+            from emotiongestures_amd.skeleton import joints_from_tracks
+            raw_j = joints_from_tracks(jo["track"], jk["joints"], unit=True, fps=jk["joints_fps"])
+            raw_k = KM.kinematics_of_joints(raw_j[0] if isinstance(raw_j, tuple) else raw_j, JOINTS_FPS or FPS, frames=jo["joint_frames"])
+            full = lambda k: torch.cat([k["speed_hist"], k["speed_over"][..., None]], -1)
+            print(f"--kinematics --smooth: the raw joints: mean wrist speed {wrists(raw_k, 'speed')} m/s, mean wrist jerk {wrists(raw_k, 'jerk')} m/s^3; "
+                  f"Hellinger distance between the raw and the smoothed speed histograms, all joints pooled, per recording: "
+                  f"{[round(float(v), 4) for v in KM.hellinger(full(raw_k), full(kin), pool=True).cpu()]}")
     if ROTATIONS:
         rot = jo["rotations"]
         swing = lambda k: float(torch.rad2deg(2 * torch.acos(rot[:, :, k, 0].clamp(max=1.0))).max())    # bone 4 / 21: left / right forearm
