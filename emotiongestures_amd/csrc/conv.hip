@@ -13,6 +13,7 @@
 //                          channel-quad planar image [ci/4][pixel][4]: a ds_read_b128 per lane, bank-conflict
 //                          free for 16 consecutive pixels (plane stride = 0 mod 16 slots, stride 1; odd, stride 2),
 //   D: each lane owns 4 consecutive output channels of one pixel -> one 16-byte NHWC store per tile.
+#include <string.h>
 #include <type_traits>
 #include "common.h"
 
@@ -73,6 +74,12 @@ template <int TH> struct ConvGeomDG2 {
     static constexpr int NPIX = IH * IW;
     static constexpr int PL = (NPIX + 15) / 16 * 16;
 };
+
+// Tap order of the STRIDE-2 split-bf16 convolutions: by the (row, column) parity of the input pixel a tap reads, which is the order the parity-plane
+// walk of the stage entries needs (conv3x3_s2_planes_kernel).  The interleaved form (conv3x3_bf16_kernel, S = 2) accumulates in the same order, so that
+// the two forms -- chosen by the size of the launch -- give every output element bit for bit the same value.
+constexpr int s2p_tap(int k) { constexpr int T[9] = {4, 3, 5, 1, 7, 0, 2, 6, 8}; return T[k]; }        // tap of the chunk's k-th step
+constexpr int s2p_plane(int k) { constexpr int P[9] = {0, 1, 1, 2, 2, 3, 3, 3, 3}; return P[k]; }      // its plane = (row parity) * 2 + (column parity)
 
 // ---- fp32 MFMA path -------------------------------------------------------------------------
 template <int CIN, int NT, int S, int TH>
@@ -356,8 +363,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
             }
         }
     };
+    // the chunk's k-th step: taps 0 .. 8 in order, in plane order (s2p_tap) at stride 2
+    auto tap_of = [](int k) { return (S == 2 && !DG2) ? s2p_tap(k) : k; };
     auto issue_weights = [&](int step, int buf) {
-        const int chunk = step / 9, tap = step - chunk * 9;
+        const int chunk = step / 9, tap = tap_of(step - chunk * 9);
         issue_rows(whi, wlo, tap * (CIN / 8) + chunk * 4, buf);
     };
     // halo tile staging, split in two so the HBM latency of chunk c+1 hides under the 9 taps of chunk c:
@@ -550,7 +559,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
         }
         if (chunk + 1 < CIN / 32) load_tile(chunk + 1);
         read_w(fr[0], 0);
-        read_x(fr[0], 0);
+        read_x(fr[0], tap_of(0));
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int step = chunk * 9 + tap;
@@ -558,7 +567,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
             if (more) issue_weights(step + 2, (tap + 2) % 3);
             mfma_half(fr[tap & 1], 0, tap);
             mid_sync(more);
-            if (tap < 8) { read_w(fr[(tap + 1) & 1], (tap + 1) % 3); read_x(fr[(tap + 1) & 1], tap + 1); }
+            if (tap < 8) { read_w(fr[(tap + 1) & 1], (tap + 1) % 3); read_x(fr[(tap + 1) & 1], tap_of(tap + 1)); }
             mfma_half(fr[tap & 1], 1, tap);
         }
     }
@@ -677,6 +686,295 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
 #pragma unroll
                 for (int m = 0; m < WM; ++m) q += sred[(WM + m) * COUTP + tid];
                 a.gap2[((size_t)b * a.tiles + tile_id) * a.cout + c0 + tid] = q;
+            }
+        }
+    }
+}
+
+// ---- stride-2 stage entries (32 -> 64, 64 -> 128) on parity planes ----------------------------------------------------------------
+// Tap (kh, kw) of output pixel (oy, ox) reads input (2 oy + kh - 1, 2 ox + kw - 1).  By (row, column) parity the input splits into four planes and
+// every tap reads exactly one of them at UNIT stride:
+//   plane 0 (even, even): TH x 32 pixels, tap 4           plane 1 (even, odd): TH x 33, taps 3, 5
+//   plane 2 (odd, even): (TH + 1) x 32, taps 1, 7         plane 3 (odd, odd): (TH + 1) x 33, taps 0, 2, 6, 8
+// Plane pixel (pr, pc) of the tile at (oy0, ox0) is input (2 (oy0 + pr) - rp, 2 (ox0 + pc) - cp), rp / cp = 1 for the odd planes; inside its plane a
+// tap reads (row + (kh == 2), col + (kw == 2)).  The interleaved form (conv3x3_bf16_kernel, S = 2) stages a (2 TH + 1) x 65 halo per 32-channel chunk,
+// which caps it at 2-row tiles (41.6 KB); here the LDS tile holds ONE plane of one chunk at a time (TH = 8: 38 KB), so that the tiles can be 4 or 8 rows
+// and a step has the body kernels' 48 MFMAs per wave.  The workgroup walks (chunk, plane) sub-chunks; the next plane's pixels are in flight in
+// registers while the current plane's 1, 2 or 4 taps run; the weight ring streams the taps in plane order (s2p_tap) from the unchanged packed images
+// with the schedule of conv3x3_bf16_kernel, plus one barrier per plane swap.  The four-tap plane comes last in a chunk: it covers the load of the next
+// chunk's first plane.
+// Pooling partials keep the interleaved form's layout (eg_conv3x3_gap_tiles: one per 2 x 32 output block): a wave's four pixel tiles ARE one such
+// block for its channel range, so every wave writes its own sums and no cross-wave fold is needed.
+// The launch function picks the form by the size of the launch (conv_s2_form), so the two forms must agree bit for bit (a clip's result may not
+// depend on the batch it is computed in): the interleaved form accumulates its taps in the same order, and the partial is folded here as there,
+// row sums first, then the two rows.
+template <int TH> struct ConvGeomS2P {
+    static constexpr int PW = 33;                       // row length of every plane's LDS image (the odd-column planes hold 33 columns)
+    static constexpr int NPIX = (TH + 1) * PW;          // the largest plane, (odd, odd)
+    static constexpr int PL = (NPIX + 15) / 16 * 16;
+};
+
+template <int CIN, int NTT, int TH, int WM, int WN, int TERMS, bool AFF>
+__global__ __launch_bounds__(256, 2) void conv3x3_s2_planes_kernel(ConvArgs a, const bf8* __restrict__ whi, const bf8* __restrict__ wlo) {
+    using G = ConvGeomS2P<TH>;
+    constexpr int COUTP = NTT * 16, PW = G::PW, NPIX = G::NPIX, PL = G::PL;
+    constexpr int MT = TH * 2 / WM, NT = NTT / WN;
+    constexpr int NIMG = (TERMS == 3) ? 2 : 1;
+    constexpr int TILE = NIMG * 4 * PL;             // bf8 slots of the plane tile
+    constexpr int WIMG = 4 * COUTP;                 // bf8 slots of one weight image of one step
+    constexpr int WBUF = NIMG * WIMG;
+    constexpr int NSTEP = (CIN / 32) * 9;
+    static_assert(WM * WN == 4 && MT == 4 && NT * WN == NTT, "a wave owns one 2 x 32 output block (four pixel tiles) of its channel range");
+    extern __shared__ __attribute__((aligned(16))) bf8 lds[];      // TILE + 3 * WBUF slots
+    bf8* tile = lds;
+    bf8* wring = lds + TILE;
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, kq = lane >> 4;
+    const int wm = wave / WN, wn = wave % WN;
+    int tile_id = blockIdx.x, b = blockIdx.y;       // XCD-aware tile order, as conv3x3_bf16_kernel
+    {
+        const int total = gridDim.x * gridDim.y;
+        if ((total & 7) == 0) {
+            const int lin = blockIdx.y * gridDim.x + blockIdx.x;
+            const int log = (lin & 7) * (total >> 3) + (lin >> 3);
+            b = log / (int)gridDim.x;
+            tile_id = log - b * (int)gridDim.x;
+        }
+    }
+    const int ty = tile_id / a.tiles_x, tx = tile_id - ty * a.tiles_x;
+    const int oy0 = ty * TH, ox0 = tx * 32;
+
+    int pbase[MT];                                  // pixel tile t of the wave: output row 2 wm + (t >> 1), columns (t & 1) * 16 ..
+#pragma unroll
+    for (int t = 0; t < MT; ++t) pbase[t] = (2 * wm + (t >> 1)) * PW + (t & 1) * 16 + li;
+    f4 acc[MT][NT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t)
+#pragma unroll
+        for (int n = 0; n < NT; ++n) acc[t][n] = (f4){0.f, 0.f, 0.f, 0.f};
+    const float* xb = a.x + (size_t)b * a.H * a.W * CIN;
+
+    // one step's weights = NIMG runs of WIMG slots; 64-slot (1 KiB) pieces dealt round-robin to the 4 waves, the same count for every wave
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    constexpr int PIECES = WIMG / 64;
+    static_assert(PIECES % 4 == 0, "every wave copies PIECES / 4 pieces of each image (the per-step wait is a counted vmcnt)");
+    constexpr int GW = NIMG * PIECES / 4;
+    const unsigned lane_b = lane * (unsigned)sizeof(bf8);
+    auto issue_weights = [&](int step, int buf) {   // chunk-major steps, the chunk's taps in plane order
+        const int chunk = step / 9, tap = s2p_tap(step - chunk * 9);
+        const size_t gbase = (size_t)(tap * (CIN / 8) + chunk * 4) * COUTP;
+#pragma unroll
+        for (int img = 0; img < NIMG; ++img) {
+            const bf8* src = (img ? wlo : whi) + gbase;
+#pragma unroll
+            for (int p = 0; p < PIECES / 4; ++p) {
+                const int piece = p * 4 + wave_u;
+                // a uniform base and a 32-bit lane offset: one address register for every copy of the kernel
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const char*>(src + piece * 64) + lane_b),
+                                                 (__attribute__((address_space(3))) void*)(wring + buf * WBUF + img * WIMG + piece * 64), 16, 0, 0);
+            }
+        }
+    };
+    // plane staging: one lane = one plane pixel x 8 channels per iteration.  The roles are the same for every plane and chunk: the element offset of
+    // the (even, even) pixel of the lane's position (plane (rp, cp) reads rp rows and cp columns before it), the LDS slot, and one bit per plane:
+    // the position belongs to the plane and lies inside the image.  Loads and stores are unconditional (no divergent branches, and a fixed number
+    // of loads per plane for the counted waits of the schedule): a position outside the plane or the image reads the clip's first pixel and is
+    // stored as zero (the padding); positions past the largest plane share the image's last slot, which no tap reads.
+    constexpr int NIT = (((NPIX + 7) / 8) * 32 + 255) / 256;
+    constexpr int LV = 2 * NIT;                     // global loads of one plane per lane
+    static_assert(PL > NPIX, "the spare slot");
+    f4 pv[NIT][2];
+    int goff[NIT], pmask = 0;                       // bit it * 4 + pl
+    static_assert(NIT * 4 <= 32, "one mask word");
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int idx = tid + it * 256;
+        const int p = (idx >> 5) * 8 + (idx & 7), oc = (idx >> 3) & 3;
+        const int pr = p / PW, pc = p - pr * PW;
+        const int gy0 = 2 * (oy0 + pr), gx0 = 2 * (ox0 + pc);
+        goff[it] = (gy0 * a.W + gx0) * CIN + oc * 8;
+#pragma unroll
+        for (int pl = 0; pl < 4; ++pl) {
+            const int rp = pl >> 1, cp = pl & 1, gy = gy0 - rp, gx = gx0 - cp;
+            if (p < NPIX && pr < TH + rp && pc < 32 + cp && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) pmask |= 1 << (it * 4 + pl);
+        }
+    }
+    auto load_plane = [&](int chunk, int pl) {
+        const int poff = ((pl >> 1) * a.W + (pl & 1)) * CIN - chunk * 32;
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const float* src = xb + (((pmask >> (it * 4 + pl)) & 1) ? goff[it] - poff : 0);
+            pv[it][0] = *reinterpret_cast<const f4*>(src);
+            pv[it][1] = *reinterpret_cast<const f4*>(src + 4);
+        }
+    };
+    const int ocs = (tid >> 3) & 3, oc8s = ocs * 8, p0 = (tid >> 5) * 8 + (tid & 7);        // this lane's channel octet and first position
+    auto store_plane = [&](int chunk, int pl) {
+        // AFF: the input affine of the training path, x' = x * in_scale[ci] + in_shift[ci] inside the image (these loads are the youngest memory
+        // operations when they are used: the wait for them lands every copy in flight, which the counted waits tolerate -- they only assume that
+        // no FEWER operations were issued)
+        f4 s0, s1, h0, h1;
+        if constexpr (AFF) {
+            s0 = *reinterpret_cast<const f4*>(a.in_scale + chunk * 32 + oc8s); s1 = *reinterpret_cast<const f4*>(a.in_scale + chunk * 32 + oc8s + 4);
+            h0 = *reinterpret_cast<const f4*>(a.in_shift + chunk * 32 + oc8s); h1 = *reinterpret_cast<const f4*>(a.in_shift + chunk * 32 + oc8s + 4);
+        }
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            // zeroed by a bit mask, not a select: a select becomes a divergent branch around the multiply-adds, and the memory waits behind a
+            // branch are no longer counted
+            const u32x4_t m = (u32x4_t)(0u - (unsigned)((pmask >> (it * 4 + pl)) & 1));
+            f4 x0 = pv[it][0], x1 = pv[it][1];
+            if constexpr (AFF) { x0 = x0 * s0 + h0; x1 = x1 * s1 + h1; }
+            const f4 v0 = __builtin_bit_cast(f4, __builtin_bit_cast(u32x4_t, x0) & m), v1 = __builtin_bit_cast(f4, __builtin_bit_cast(u32x4_t, x1) & m);
+            bf8 hi, lo;
+            split_octet<TERMS == 3>(v0, v1, hi, lo);
+            const int p = p0 + it * 64, slot = ocs * PL + (p < PL - 1 ? p : PL - 1);
+            tile[slot] = hi;
+            if (TERMS == 3) tile[4 * PL + slot] = lo;
+        }
+    };
+
+    struct Frags { bf8 wh[NT], wl[NT], xh[MT], xl[MT]; };
+    auto read_w = [&](Frags& f, int slot) {
+        const bf8* Wh = wring + slot * WBUF + kq * COUTP + wn * NT * 16 + li;
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+            f.wh[n] = Wh[n * 16];
+            if (TERMS == 3) f.wl[n] = Wh[WIMG + n * 16];
+        }
+    };
+    auto read_x = [&](Frags& f, int tap) {          // unit stride inside the tap's plane
+        const int toff = (tap / 3 == 2 ? PW : 0) + (tap % 3 == 2 ? 1 : 0);
+#pragma unroll
+        for (int t = 0; t < MT; ++t) {
+            f.xh[t] = tile[kq * PL + pbase[t] + toff];
+            if (TERMS == 3) f.xl[t] = tile[(4 + kq) * PL + pbase[t] + toff];
+        }
+    };
+    auto mfma_half = [&](const Frags& f, int half) {
+#pragma unroll
+        for (int t = half * (MT / 2); t < (half + 1) * (MT / 2); ++t)
+#pragma unroll
+            for (int n = 0; n < NT; ++n) {
+                if (TERMS == 3) {
+                    acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wl[n], f.xh[t], acc[t][n], 0, 0, 0);
+                    acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wh[n], f.xl[t], acc[t][n], 0, 0, 0);
+                }
+                acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wh[n], f.xh[t], acc[t][n], 0, 0, 0);
+            }
+    };
+    // Schedule.  Step s = (chunk, k) runs tap s2p_tap(k); W(s) = its weights, in ring slot k % 3.  As in conv3x3_bf16_kernel a step is
+    //   [issue W(s+2)]  MFMAs first half  wait: W(s+1) landed; barrier  read the fragments of s+1  MFMAs second half
+    // and a step that ends its plane (k = 0, 2, 4, and 8 when a chunk follows) SWAPS after that barrier instead:
+    //   store the next plane (its pixels are in registers)  MFMAs second half  barrier  issue W(s+3)  load the plane after the next  fragments of s+1
+    // The memory counter retires in order, and the mid-step wait is "all but the youngest N operations": a plane's LV loads are issued BEHIND
+    // W(s+3), which the step after the swap would otherwise issue, so they stay in flight through the waits of the next two steps (N = GW + LV:
+    // the loads and one weight copy) and are forced to land only by the third -- or by the next swap's store.  The waits per k (L = the plane
+    // load issued at the last swap, none after k = 4 of the last chunk):
+    //   k = 0, 1, 3, 5 (after a swap; W(s+2) was issued there): younger than W(s+1) are W(s+2), L      -> GW + LV
+    //   k = 2, 4, 6    (second step; issues W(s+2)):            younger than W(s+1) are L, W(s+2)      -> GW + LV
+    //   k = 7, 8       (issue W(s+2) while a chunk follows):    younger than W(s+1) is W(s+2)          -> GW, or 0 in the last chunk
+    auto mid_sync = [&](int k, bool nxt) {
+        __builtin_amdgcn_sched_barrier(0);          // keep the first-half MFMAs in front of the wait (the scheduler would sink them)
+        if (k <= 4) wait_vmcnt_imm<GW + LV>();
+        else if (k <= 6) { if (nxt) wait_vmcnt_imm<GW + LV>(); else wait_vmcnt_imm<GW>(); }
+        else { if (nxt) wait_vmcnt_imm<GW>(); else wait_vmcnt_imm<0>(); }
+        wait_lgkmcnt0();
+        wg_barrier();
+    };
+    Frags fr[2];
+    issue_weights(0, 0);
+    issue_weights(1, 1);
+    load_plane(0, 0);
+    store_plane(0, 0);
+    wait_vmcnt_imm<0>();
+    wait_lgkmcnt0();
+    wg_barrier();
+    issue_weights(2, 2);
+    __builtin_amdgcn_sched_barrier(0);
+    load_plane(0, 1);
+    read_w(fr[0], 0);
+    read_x(fr[0], s2p_tap(0));
+#pragma unroll 1
+    for (int chunk = 0; chunk < CIN / 32; ++chunk) {
+        // opaque to the optimiser per chunk: hoisted out of the loop, the masks (one vector per plane and iteration) and the copies' per-chunk
+        // addresses cost more registers than the kernel has
+        int chunk_u = chunk;
+        asm volatile("" : "+s"(chunk_u), "+v"(pmask));
+        const bool nxt = chunk_u + 1 < CIN / 32;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const int step = chunk_u * 9 + k;
+            const bool after_swap = k == 0 || k == 1 || k == 3 || k == 5;
+            const bool swap = k == 0 || k == 2 || k == 4 || (k == 8 && nxt);
+            const int kn = (k + 1) % 9, fn = k < 8 ? (k + 1) & 1 : 0;           // the next step's k and fragment set (a chunk starts on set 0)
+            if (!after_swap && step + 2 < NSTEP) issue_weights(step + 2, (k + 2) % 3);
+            mfma_half(fr[k & 1], 0);
+            mid_sync(k, nxt);
+            if (swap) {
+                // every wave holds this step's fragments: the tile takes the next plane, under the second half of the MFMAs
+                store_plane(k < 8 ? chunk_u : chunk_u + 1, s2p_plane(kn));
+                mfma_half(fr[k & 1], 1);
+                wait_lgkmcnt0();
+                wg_barrier();
+                issue_weights(step + 3, k % 3);     // slot (k + 3) % 3: W(s) was last read before this step's first barrier
+                __builtin_amdgcn_sched_barrier(0);  // the loads stay behind the weight copy
+                if (k == 0) load_plane(chunk_u, 2);
+                else if (k == 2) load_plane(chunk_u, 3);
+                else if (k == 8) load_plane(chunk_u + 1, 1);
+                else if (nxt) load_plane(chunk_u + 1, 0);
+                read_w(fr[fn], kn % 3);
+                read_x(fr[fn], s2p_tap(kn));
+            } else {
+                if (k < 8) { read_w(fr[fn], kn % 3); read_x(fr[fn], s2p_tap(kn)); }
+                mfma_half(fr[k & 1], 1);
+            }
+        }
+    }
+
+    // epilogue: v = acc + bias; relu; v * scale + shift; one 16-byte NHWC store per (pixel tile, channel tile)
+    int pixo[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+        const int oy = oy0 + 2 * wm + (t >> 1), ox = ox0 + (t & 1) * 16 + li;
+        pixo[t] = (oy < a.Ho && ox < a.Wo) ? oy * a.Wo + ox : -1;
+    }
+    const int hw = a.Ho * a.Wo;
+    float* __restrict__ yb = a.y + (size_t)b * hw * COUTP;
+    // the wave's 2 x 32 block in the numbering of eg_conv3x3_gap_tiles (2-row tiles); a block below the map's last row does not exist
+    const bool blk_ok = oy0 + 2 * wm < a.Ho;
+    const size_t gbase = ((size_t)b * a.tiles + (size_t)(ty * (TH / 2) + wm) * a.tiles_x + tx) * COUTP;
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+        f4 gsum[2], gsq[2];                         // per output row of the block: the interleaved form's summation order (a wave per row, then the two rows)
+        gsum[0] = gsum[1] = gsq[0] = gsq[1] = (f4){0.f, 0.f, 0.f, 0.f};
+        const int co = (wn * NT + n) * 16 + kq * 4;
+        const f4 bi = a.bias ? *reinterpret_cast<const f4*>(a.bias + co) : (f4){0.f, 0.f, 0.f, 0.f};
+        const f4 sc = a.scale ? *reinterpret_cast<const f4*>(a.scale + co) : (f4){1.f, 1.f, 1.f, 1.f};
+        const f4 sh = a.shift ? *reinterpret_cast<const f4*>(a.shift + co) : (f4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int t = 0; t < MT; ++t) {
+            f4 v = acc[t][n] + bi;
+            if (a.relu) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+            }
+            v = v * sc + sh;
+            if (pixo[t] >= 0) {
+                *reinterpret_cast<f4*>(yb + pixo[t] * COUTP + co) = v;
+                gsum[t >> 1] += v;
+                if (a.gap2) gsq[t >> 1] += v * v;
+            }
+        }
+        if (a.gap) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                gsum[0][r] = (0.f + row16_sum(gsum[0][r])) + row16_sum(gsum[1][r]);
+                if (a.gap2) gsq[0][r] = (0.f + row16_sum(gsq[0][r])) + row16_sum(gsq[1][r]);
+            }
+            if (li == 0 && blk_ok) {
+                *reinterpret_cast<f4*>(a.gap + gbase + co) = gsum[0];
+                if (a.gap2) *reinterpret_cast<f4*>(a.gap2 + gbase + co) = gsq[0];
             }
         }
     }
@@ -1286,6 +1584,46 @@ int launch_conv(const ConvArgs& a, int batch, int precision, hipStream_t st) {
     return launch_conv_bf16<CIN, NT, S, TH, WM, WN, 1, SCC>(a, whi, wlo, grid, st);
 }
 
+// The two stage-entry convolutions (32 -> 64, 64 -> 128, stride 2) on parity planes (conv3x3_s2_planes_kernel): TH x 32 output tiles.
+template <int CIN, int NTT, int TH, int WM, int WN>
+int launch_conv_s2_planes(const ConvArgs& a, int batch, int precision, hipStream_t st) {
+    using G = ConvGeomS2P<TH>;
+    const bf8* whi = reinterpret_cast<const bf8*>(a.w + (size_t)9 * CIN * NTT * 16);
+    const bf8* wlo = whi + (size_t)9 * (CIN / 8) * NTT * 16;
+    const dim3 grid(a.tiles_x * eg_cdiv(a.Ho, TH), batch);
+    auto go = [&](auto kern, size_t lds_bytes) {
+        if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds_bytes, "conv3x3 (stride 2, planes)")) return rc;
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, st, a, whi, wlo);
+        return eg_check_launch("conv3x3 (stride 2, planes)");
+    };
+    constexpr size_t LDS3 = sizeof(bf8) * (size_t)(2 * 4 * G::PL + 3 * 2 * 4 * NTT * 16), LDS1 = sizeof(bf8) * (size_t)(4 * G::PL + 3 * 4 * NTT * 16);
+    if (a.in_scale) {           // the training path's input affine: instantiations of their own, so that the inference kernels carry none of it
+        if (precision == EG_PREC_BF16X3) return go(conv3x3_s2_planes_kernel<CIN, NTT, TH, WM, WN, 3, true>, LDS3);
+        return go(conv3x3_s2_planes_kernel<CIN, NTT, TH, WM, WN, 1, true>, LDS1);
+    }
+    if (precision == EG_PREC_BF16X3) return go(conv3x3_s2_planes_kernel<CIN, NTT, TH, WM, WN, 3, false>, LDS3);
+    return go(conv3x3_s2_planes_kernel<CIN, NTT, TH, WM, WN, 1, false>, LDS1);
+}
+// Which form a stage-entry convolution takes: 0 = interleaved halo (conv3x3_bf16_kernel, S = 2, 2-row tiles), else the tile height of the plane walk.
+// EG_CONV_S2 is an A/B switch read per call (a captured graph keeps what it was captured with): "interleaved"; "planes" (the plane walk at every
+// size); "planes4" / "planes8" (the same with the 32 -> 64 entry's tile height forced; the 64 -> 128 entry has 4-row tiles only); unset = by size.
+// Measured alone (TED shapes, bf16x3, us per launch at 1 / 8 / 16 / 32 / 64 clips; profiles/r13_stride2_planes_ab.txt):
+//   32 -> 64:  interleaved 7.1 / 11.5 / 19.7 / 38.1 / 73.3   4-row planes 9.8 / 12.4 / 14.9 / 31.5 / 55.0   8-row planes 15.1 / 17.0 / 18.9 / 25.2 / 55.4
+//   64 -> 128: interleaved 13.2 / 14.9 / 16.4 / 29.5 / 59.1  4-row planes 19.1 / 21.1 / 21.8 / 23.4 / 34.9
+// A plane-walk workgroup lives longer than an interleaved one (four plane swaps per chunk), which pays once the launch fills the chip: the
+// interleaved form stays below 256 workgroups of the plane walk (8-row tiles counted for 32 -> 64), 8-row tiles start at 512.
+int conv_s2_form(int cin, int batch, int ho, int wo) {
+    const char* e = getenv("EG_CONV_S2");
+    if (e && !strcmp(e, "interleaved")) return 0;
+    const bool forced = e && !strncmp(e, "planes", 6);
+    const int wgs = eg_cdiv(wo, 32) * eg_cdiv(ho, cin == 64 ? 4 : 8) * batch;
+    if (!forced && wgs < 256) return 0;
+    if (cin == 64) return 4;
+    if (e && !strcmp(e, "planes4")) return 4;
+    if (e && !strcmp(e, "planes8")) return 8;
+    return wgs >= 512 ? 8 : 4;
+}
+
 bool conv32_persistent_enabled() {
     static const bool on = [] { const char* e = getenv("EG_CONV32_PERSISTENT"); return !(e && e[0] == '0'); }();
     return on;
@@ -1488,6 +1826,11 @@ int conv3x3_dispatch(const float* x, const float* w, const float* bias, const fl
         return launch_conv32_persistent(a, batch, precision, th, st);
     if (cin == 32 && coutp == 32 && stride == 1 && th == 4) return launch_conv<32, 2, 1, 4, 4, 1>(a, batch, precision, st);
     if (cin == 32 && coutp == 32 && stride == 1) return launch_conv<32, 2, 1, 8, 4, 1>(a, batch, precision, st);
+    // the stage entries walk parity planes (conv_s2_form); the interleaved form serves fp32, NCHW output, padded channels and the A/B switch
+    const int s2p = (stride == 2 && cout == coutp && precision != EG_PREC_F32 && !nchw_out && (!gap_partial || eg_aligned16(gap_partial)) &&
+                     (!gap_sq || eg_aligned16(gap_sq))) ? conv_s2_form(cin, batch, a.Ho, a.Wo) : 0;
+    if (cin == 32 && coutp == 64 && stride == 2 && s2p == 8) return launch_conv_s2_planes<32, 4, 8, 4, 1>(a, batch, precision, st);
+    if (cin == 32 && coutp == 64 && stride == 2 && s2p == 4) return launch_conv_s2_planes<32, 4, 4, 2, 2>(a, batch, precision, st);
     if (cin == 32 && coutp == 64 && stride == 2) return launch_conv<32, 4, 2, 2, 2, 2>(a, batch, precision, st);
     if (const int split = body_channel_split(batch, a.tiles, cin, cout, stride, precision, nchw_out); split > 1) {
         // few pixel tiles (small batches): spread the output channels over workgroups as well -- bitwise the unsplit kernels below
@@ -1499,6 +1842,7 @@ int conv3x3_dispatch(const float* x, const float* w, const float* bias, const fl
         if (cin == 128 && split == 4) return launch_conv_split_t<128, 2, 4, 2, 2, 3>(a, batch, whi, wlo, st);
     }
     if (cin == 64 && coutp == 64 && stride == 1) return launch_conv<64, 4, 1, 8, 4, 1>(a, batch, precision, st);
+    if (cin == 64 && coutp == 128 && stride == 2 && s2p == 4) return launch_conv_s2_planes<64, 8, 4, 2, 2>(a, batch, precision, st);
     if (cin == 64 && coutp == 128 && stride == 2) return launch_conv<64, 8, 2, 2, 2, 2>(a, batch, precision, st);
     if (cin == 64 && coutp == 128 && stride == 1) return launch_conv<64, 8, 1, 4, 2, 2>(a, batch, precision, st);      // training: input gradient of final_conv1 (dy padded to 64 channels)
     if (cin == 128 && coutp == 128 && stride == 1) return launch_conv<128, 8, 1, 4, 2, 2>(a, batch, precision, st);

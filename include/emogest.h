@@ -896,7 +896,9 @@ int eg_take_distance(const float* feat, int32_t recordings, int32_t draws, int32
  * fused epilogue  v = acc + bias[c]; if relu: v = max(v,0); v = v*scale[c] + shift[c].
  *   x [B,H,W,Cin]   w EG_PACK_CONV3X3   bias/scale/shift [Cout_pad] (NULL = 0/1/0)
  *   y NHWC [B,Ho,Wo,Cout] or, if nchw_out, [B,Cout,Ho*Wo]
- *   gap_partial (optional) [B, eg_conv3x3_gap_tiles(...), Cout]: per-tile channel sums of y (for SE). */
+ *   gap_partial (optional) [B, eg_conv3x3_gap_tiles(...), Cout]: per-tile channel sums of y (for SE).
+ * The stride-2 stage entries (32 -> 64, 64 -> 128, split-bf16 modes, NHWC) run on parity planes with 4- or 8-row tiles once the launch fills the
+ * chip (EG_CONV_S2 = interleaved | planes | planes4 | planes8 forces a form); their partials stay one per 2 x 32 output block in either form. */
 int eg_conv3x3(const float* x, const float* w, const float* bias, const float* scale, const float* shift,
                float* y, float* gap_partial, int32_t batch, int32_t h, int32_t wdt, int32_t cin, int32_t cout,
                int32_t stride, int32_t relu, int32_t nchw_out, int32_t precision, void* stream);
