@@ -38,7 +38,6 @@ struct ConvArgs {
     const unsigned* res_bits = nullptr; // residual behind a ReLU mask: one bit per element of `res` (bit e & 31 of word e >> 5 = the nibble-per-float4 layout
                                         // se_tail_fwd_kernel writes): v += bit ? res : 0 -- the SE block's identity shortcut gradient dout * (out > 0), never stored
     const float* res_q = nullptr;       // DG2 only: a gradient on the dy grid ([B][H][W][cout]) added to the (even, even) phase -- the stride-2 1x1 shortcut's
-    unsigned int* dbg = nullptr;        // diagnostic build only (EG_CONV32_STAMP=1): per-wave phase cycle sums of the persistent 32->32 kernel
     // conv2 of a block WITH a downsample shortcut (conv3x3_bf16_kernel, SCC > 0): the 1x1 stride-sc_S convolution of the block input sc_x
     // [B][sc_H][sc_W][SCC * 32] is contracted into the same accumulators before the 3x3 taps (weight images [ci/8][co][8], hi then lo) and the
     // per-clip vectors of se_gate_pre_kernel fold gate, BN2 and the shortcut's BN into one rescale and one affine: sc_vec = [f | q | h], each [B][cout]
@@ -75,11 +74,53 @@ template <int TH> struct ConvGeomDG2 {
     static constexpr int PL = (NPIX + 15) / 16 * 16;
 };
 
+constexpr int WRING = 3;        // slots of the split-bf16 kernels' weight ring: step s runs, step s + 1's fragments are read, the copy of step s + 2 is in flight
+// LDS of a kernel with a weight ring, in bf8 slots: [tile: NIMG images x 4 octet planes x PL pixels][WRING x WBUF: the NIMG weight images of a K step, 4 octet rows x COUTP]
+template <int PL, int COUTP, int TERMS> struct RingLds {
+    static constexpr int NIMG = (TERMS == 3) ? 2 : 1;
+    static constexpr int TILE = NIMG * 4 * PL, WIMG = 4 * COUTP, WBUF = NIMG * WIMG;
+    static constexpr size_t BYTES = sizeof(bf8) * (size_t)(TILE + WRING * WBUF);
+};
+template <int S, int TH, bool DG2> using ConvBf16Geom = typename std::conditional<DG2, ConvGeomDG2<TH>, ConvGeom<S, TH>>::type;     // conv3x3_bf16_kernel's halo tile
+
 // Tap order of the STRIDE-2 split-bf16 convolutions: by the (row, column) parity of the input pixel a tap reads, which is the order the parity-plane
 // walk of the stage entries needs (conv3x3_s2_planes_kernel).  The interleaved form (conv3x3_bf16_kernel, S = 2) accumulates in the same order, so that
 // the two forms -- chosen by the size of the launch -- give every output element bit for bit the same value.
 constexpr int s2p_tap(int k) { constexpr int T[9] = {4, 3, 5, 1, 7, 0, 2, 6, 8}; return T[k]; }        // tap of the chunk's k-th step
 constexpr int s2p_plane(int k) { constexpr int P[9] = {0, 1, 1, 2, 2, 3, 3, 3, 3}; return P[k]; }      // its plane = (row parity) * 2 + (column parity)
+
+// the three-term split-bf16 product of a fragment pair, small terms first: acc += wl * xh + wh * xl + wh * xh (TERMS == 1: the last term alone)
+template <int TERMS> __device__ __forceinline__ f4 mfma_split(bf8 wh, bf8 wl, bf8 xh, bf8 xl, f4 acc) {
+    if (TERMS == 3) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, xh, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xl, acc, 0, 0, 0);
+    }
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xh, acc, 0, 0, 0);
+}
+__device__ __forceinline__ f4 relu4(f4 v) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+    return v;
+}
+// 8 staged fp32 channels of one pixel -> the tile's hi image (and, for the three-term product, its lo image 4 planes behind)
+template <int TERMS, int PL> __device__ __forceinline__ void store_split(bf8* tile, int slot, const f4& v0, const f4& v1) {
+    bf8 hi, lo;
+    split_octet<TERMS == 3>(v0, v1, hi, lo);
+    tile[slot] = hi;
+    if (TERMS == 3) tile[4 * PL + slot] = lo;
+}
+// staging roles of the split-bf16 kernels by thread index: 8 consecutive lanes stage 8 consecutive pixels of one channel octet (conflict-free ds_write_b128)
+__device__ __forceinline__ int stage_pixel(int idx) { return (idx >> 5) * 8 + (idx & 7); }
+__device__ __forceinline__ int stage_octet(int idx) { return (idx >> 3) & 3; }
+// a wave's fragments of one K step, and the read of their weight half: Wh = the lane's first slot in the step's hi image, the lo image lies WIMG slots behind
+template <int NT, int MT> struct ConvFrags { bf8 wh[NT], wl[NT], xh[MT], xl[MT]; };
+template <int TERMS, int WIMG, int NT, int MT> __device__ __forceinline__ void read_w_frags(ConvFrags<NT, MT>& f, const bf8* Wh) {
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+        f.wh[n] = Wh[n * 16];
+        if (TERMS == 3) f.wl[n] = Wh[WIMG + n * 16];
+    }
+}
 
 // ---- fp32 MFMA path -------------------------------------------------------------------------
 template <int CIN, int NT, int S, int TH>
@@ -259,22 +300,20 @@ __global__ __launch_bounds__(256) void conv3x3_f32_kernel(ConvArgs a) {
 //
 // One workgroup computes one tile in one straight pass: prologue (first two weight copies, first halo chunk, the shortcut pre-phase when SCC > 0), the
 // chunk x tap loop, the epilogue.
-template <int CIN, int NTT, int S, int TH, int WM, int WN, int TERMS, int RING, bool SPLIT = false, bool DG2 = false, int SCC = 0>
+template <int CIN, int NTT, int S, int TH, int WM, int WN, int TERMS, bool SPLIT = false, bool DG2 = false, int SCC = 0>
 __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const bf8* __restrict__ whi,
                                                            const bf8* __restrict__ wlo) {
     static_assert(!DG2 || (S == 1 && !SPLIT), "DG2 tiles the dy grid with unit stride");
     static_assert(SCC == 0 || (S == 1 && !DG2 && SCC <= 2 && CIN >= 64), "the shortcut pre-phase belongs to a stride-1 conv2 and uses ring slots 2 and 1");
-    using G = typename std::conditional<DG2, ConvGeomDG2<TH>, ConvGeom<S, TH>>::type;
+    using G = ConvBf16Geom<S, TH, DG2>;
     constexpr int PH = DG2 ? 4 : 1;                 // output phases (accumulator sets)
     constexpr int COUTP = NTT * 16, IW = G::IW, NPIX = G::NPIX, PL = G::PL;
     constexpr int MT = TH * 2 / WM, NT = NTT / WN;
-    constexpr int NIMG = (TERMS == 3) ? 2 : 1;
-    constexpr int TILE = NIMG * 4 * PL;             // bf8 slots of the halo tile
-    constexpr int WIMG = 4 * COUTP;                 // bf8 slots of one weight image of one step
-    constexpr int WBUF = NIMG * WIMG;
+    using L = RingLds<PL, COUTP, TERMS>;
+    constexpr int NIMG = L::NIMG, TILE = L::TILE, WIMG = L::WIMG, WBUF = L::WBUF;
     constexpr int NSTEP = (CIN / 32) * 9;
     static_assert(WM * WN == 4 && MT * WM == TH * 2 && NT * WN == NTT, "wave tiling");
-    extern __shared__ __attribute__((aligned(16))) bf8 lds[];      // TILE + RING * WBUF slots (dynamic: can exceed 64 KB)
+    extern __shared__ __attribute__((aligned(16))) bf8 lds[];      // RingLds: TILE + WRING * WBUF slots (dynamic: can exceed 64 KB)
     bf8* tile = lds;
     bf8* wring = lds + TILE;
 
@@ -382,7 +421,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int idx = tid + it * 256;
-            const int p = (idx >> 5) * 8 + (idx & 7), oc = (idx >> 3) & 3;
+            const int p = stage_pixel(idx), oc = stage_octet(idx);
             const int iy = p / IW, ix = p - iy * IW;
             const int gy = iy0 + iy, gx = ix0 + ix;
             const bool inside = p < NPIX && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
@@ -417,10 +456,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
                     pv[it][0] = pv[it][0] * s0 + h0;
                     pv[it][1] = pv[it][1] * s1 + h1;
                 }
-                bf8 hi, lo;
-                split_octet<TERMS == 3>(pv[it][0], pv[it][1], hi, lo);
-                tile[lslot[it]] = hi;
-                if (TERMS == 3) tile[4 * PL + lslot[it]] = lo;
+                store_split<TERMS, PL>(tile, lslot[it], pv[it][0], pv[it][1]);
             }
         }
     };
@@ -430,14 +466,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
     //   step s:  issue the weight copy of step s+2  ->  read step s+1's fragments from LDS (in flight during ...)
     //            ... the MFMAs of step s  ->  vmcnt(0) + barrier (copies of s+1, s+2 landed; slot of s is free)
     // so neither the LDS fragment reads nor the global->LDS weight copies sit on the MFMA critical path.
-    struct Frags { bf8 wh[NT], wl[NT], xh[MT], xl[MT]; };
+    using Frags = ConvFrags<NT, MT>;
     auto read_w = [&](Frags& f, int slot) {                                              // main steps: slot = step % 3 == tap % 3 (9 taps per chunk)
-        const bf8* Wh = wring + slot * WBUF + kq * COUTP + wn * NT * 16 + li;
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-            f.wh[n] = Wh[n * 16];
-            if (TERMS == 3) f.wl[n] = Wh[WIMG + n * 16];
-        }
+        read_w_frags<TERMS, WIMG>(f, wring + slot * WBUF + kq * COUTP + wn * NT * 16 + li);
     };
     auto read_x = [&](Frags& f, int tap) {
         const int kh = tap / 3, kw = tap - kh * 3;
@@ -454,15 +485,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
 #pragma unroll
         for (int t = half * (MT / 2); t < (half + 1) * (MT / 2); ++t)
 #pragma unroll
-            for (int n = 0; n < NT; ++n) {
-                if (TERMS == 3) {
-                    acc[ph][t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wl[n], f.xh[t], acc[ph][t][n], 0, 0, 0);
-                    acc[ph][t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wh[n], f.xl[t], acc[ph][t][n], 0, 0, 0);
-                }
-                acc[ph][t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wh[n], f.xh[t], acc[ph][t][n], 0, 0, 0);
-            }
+            for (int n = 0; n < NT; ++n) acc[ph][t][n] = mfma_split<TERMS>(f.wh[n], f.wl[n], f.xh[t], f.xl[t], acc[ph][t][n]);
     };
-    static_assert(RING == 3, "schedule below assumes a 3-slot ring");
+    static_assert(WRING == 3, "schedule below assumes a 3-slot ring");
     // Schedule of step s (one tap of one 32-channel chunk), one barrier per step, placed between the two MFMA halves:
     //   issue copy W(s+2) -> slot (s+2)%3        (its previous content, W(s-1), was last read before the barrier of step s-1)
     //   read the pixel fragments of step s+1     (hidden under ...)
@@ -495,7 +520,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
 #pragma unroll
         for (int it = 0; it < SNIT; ++it) {
             const int idx = tid + it * 256;
-            const int p = (idx >> 5) * 8 + (idx & 7), oc = (idx >> 3) & 3;
+            const int p = stage_pixel(idx), oc = stage_octet(idx);
             const int r = p >> 5, col = p & 31, oy = oy0 + r, ox = ox0 + col;
             // oy < Ho = (sc_H - 1) / sc_S + 1  =>  sc_S * oy <= sc_H - 1: a valid output pixel's source pixel is inside the block input
             sgoff[it] = (oy < a.Ho && ox < a.Wo) ? (oy * a.sc_S * a.sc_W + ox * a.sc_S) * (SCC * 32) + oc * 8 : -1;
@@ -520,10 +545,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
         for (int c = 0; c < SCC; ++c) {
 #pragma unroll
             for (int it = 0; it < SNIT; ++it) {
-                bf8 hi, lo;
-                split_octet<TERMS == 3>(sv[it][0], sv[it][1], hi, lo);
-                tile[sslot[it]] = hi;
-                if (TERMS == 3) tile[4 * PL + sslot[it]] = lo;
+                store_split<TERMS, PL>(tile, sslot[it], sv[it][0], sv[it][1]);
             }
             if (c + 1 < SCC) load_sc(c + 1);
             __syncthreads();                    // shortcut pixels visible; every copy issued so far has landed
@@ -633,17 +655,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(ConvArgs a, const 
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
             f4 v = acc[0][t][n] + bi;
-            if (a.relu) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-            }
+            if (a.relu) v = relu4(v);
             v = v * sc + sh;
             if (a.gate) v = v * gt;
             if (rb && pixo[t] >= 0 && co < a.cout) v += residual_quad(a.res, a.res_bits, rbase + (size_t)pixo[t] * a.cout + co);
-            if (a.relu2) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-            }
+            if (a.relu2) v = relu4(v);
             if (pixo[t] >= 0) {
                 if (!a.nchw) {
                     if (co < a.cout) *reinterpret_cast<f4*>(yb + pixo[t] * a.cout + co) = v;
@@ -719,13 +735,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_s2_planes_kernel(ConvArgs a, c
     using G = ConvGeomS2P<TH>;
     constexpr int COUTP = NTT * 16, PW = G::PW, NPIX = G::NPIX, PL = G::PL;
     constexpr int MT = TH * 2 / WM, NT = NTT / WN;
-    constexpr int NIMG = (TERMS == 3) ? 2 : 1;
-    constexpr int TILE = NIMG * 4 * PL;             // bf8 slots of the plane tile
-    constexpr int WIMG = 4 * COUTP;                 // bf8 slots of one weight image of one step
-    constexpr int WBUF = NIMG * WIMG;
+    using L = RingLds<PL, COUTP, TERMS>;
+    constexpr int NIMG = L::NIMG, TILE = L::TILE, WIMG = L::WIMG, WBUF = L::WBUF;
     constexpr int NSTEP = (CIN / 32) * 9;
     static_assert(WM * WN == 4 && MT == 4 && NT * WN == NTT, "a wave owns one 2 x 32 output block (four pixel tiles) of its channel range");
-    extern __shared__ __attribute__((aligned(16))) bf8 lds[];      // TILE + 3 * WBUF slots
+    extern __shared__ __attribute__((aligned(16))) bf8 lds[];      // RingLds: TILE + WRING * WBUF slots
     bf8* tile = lds;
     bf8* wring = lds + TILE;
 
@@ -789,7 +803,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_s2_planes_kernel(ConvArgs a, c
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int idx = tid + it * 256;
-        const int p = (idx >> 5) * 8 + (idx & 7), oc = (idx >> 3) & 3;
+        const int p = stage_pixel(idx), oc = stage_octet(idx);
         const int pr = p / PW, pc = p - pr * PW;
         const int gy0 = 2 * (oy0 + pr), gx0 = 2 * (ox0 + pc);
         goff[it] = (gy0 * a.W + gx0) * CIN + oc * 8;
@@ -834,15 +848,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_s2_planes_kernel(ConvArgs a, c
         }
     };
 
-    struct Frags { bf8 wh[NT], wl[NT], xh[MT], xl[MT]; };
-    auto read_w = [&](Frags& f, int slot) {
-        const bf8* Wh = wring + slot * WBUF + kq * COUTP + wn * NT * 16 + li;
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-            f.wh[n] = Wh[n * 16];
-            if (TERMS == 3) f.wl[n] = Wh[WIMG + n * 16];
-        }
-    };
+    using Frags = ConvFrags<NT, MT>;
+    auto read_w = [&](Frags& f, int slot) { read_w_frags<TERMS, WIMG>(f, wring + slot * WBUF + kq * COUTP + wn * NT * 16 + li); };
     auto read_x = [&](Frags& f, int tap) {          // unit stride inside the tap's plane
         const int toff = (tap / 3 == 2 ? PW : 0) + (tap % 3 == 2 ? 1 : 0);
 #pragma unroll
@@ -855,13 +862,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_s2_planes_kernel(ConvArgs a, c
 #pragma unroll
         for (int t = half * (MT / 2); t < (half + 1) * (MT / 2); ++t)
 #pragma unroll
-            for (int n = 0; n < NT; ++n) {
-                if (TERMS == 3) {
-                    acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wl[n], f.xh[t], acc[t][n], 0, 0, 0);
-                    acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wh[n], f.xl[t], acc[t][n], 0, 0, 0);
-                }
-                acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wh[n], f.xh[t], acc[t][n], 0, 0, 0);
-            }
+            for (int n = 0; n < NT; ++n) acc[t][n] = mfma_split<TERMS>(f.wh[n], f.wl[n], f.xh[t], f.xl[t], acc[t][n]);
     };
     // Schedule.  Step s = (chunk, k) runs tap s2p_tap(k); W(s) = its weights, in ring slot k % 3.  As in conv3x3_bf16_kernel a step is
     //   [issue W(s+2)]  MFMAs first half  wait: W(s+1) landed; barrier  read the fragments of s+1  MFMAs second half
@@ -986,23 +987,25 @@ __global__ __launch_bounds__(256, 2) void conv3x3_s2_planes_kernel(ConvArgs a, c
 // 4 x 32-pixel tiles: all 9 taps' weights (36 KB of hi/lo images) are copied to LDS once, the NEXT tile's halo pixels (and this tile's
 // residual, for the fused SE tail) are in flight in registers while the 9 taps of the current tile run, and the taps need no barrier
 // (weights and tile are static): two barriers per tile instead of ten.  Same arithmetic and summation order as the tiled kernel.
-// STAMP: s_memtime stamps around the six phases of a tile (a separate diagnostic instantiation; the production kernel executes none)
-template <int TERMS, int TH = 4, bool STAMP = false>
+constexpr int C32_ROWS = 4;     // tile height of the walk (8-row tiles were measured and retired: tools/experiments/README.md)
+// its LDS, in bf8 slots: [tile][hi image: 9 taps x 4 octet rows x 32 channels][lo image], then the pooling scratch in floats
+template <int TERMS> struct C32Lds {
+    static constexpr int NIMG = (TERMS == 3) ? 2 : 1;
+    static constexpr int TILE = NIMG * 4 * ConvGeom<1, C32_ROWS>::PL, WTAP = 4 * 32, WIMG = 9 * WTAP;
+    static constexpr size_t BYTES = sizeof(bf8) * (size_t)(TILE + NIMG * WIMG) + 2 * 4 * 32 * sizeof(float);        // + [4 waves][32] sums, then the squares
+};
+template <int TERMS>
 __global__ __launch_bounds__(256, 2) void conv3x3_c32_persistent_kernel(ConvArgs a, const bf8* __restrict__ whi, const bf8* __restrict__ wlo,
-                                                                     int total_tiles, int tiles_per_wg) {
+                                                                     int total_tiles) {
+    constexpr int TH = C32_ROWS;
     using G = ConvGeom<1, TH>;
+    using L = C32Lds<TERMS>;
     constexpr int CIN = 32, IW = G::IW, NPIX = G::NPIX, PL = G::PL, MT = TH / 2, NT = 2;
-    constexpr int NIMG = (TERMS == 3) ? 2 : 1;
-    constexpr int TILE = NIMG * 4 * PL, WTAP = 4 * 32, WIMG = 9 * WTAP;
-    static_assert(PL - NPIX >= 8 || TH == 4, "the gap scratch of the 8-row variant lives in the planes' padding slots");
+    constexpr int NIMG = L::NIMG, TILE = L::TILE, WTAP = L::WTAP, WIMG = L::WIMG;
     extern __shared__ __attribute__((aligned(16))) bf8 lds[];      // tile | weights (hi [tap][octet][co], lo) | gap scratch
     bf8* tile = lds;
     bf8* wl = lds + TILE;
-    // gap scratch [4 waves][32 floats] (+ the same again for the sums of squares): behind the weights (4-row tiles), or -- 8-row tiles: tile + weights fill exactly half a CU's LDS -- in the
-    // padding slots NPIX .. PL-1 of the first four channel-octet planes, which no staging write and no fragment read touches
-    float* sred_base = reinterpret_cast<float*>(lds + TILE + NIMG * WIMG);
-    const int sred_pitch = (TH == 4) ? 32 : PL * 4;               // floats between two waves' scratch rows
-    float* sred = (TH == 4) ? sred_base : reinterpret_cast<float*>(tile + NPIX);
+    float* sred = reinterpret_cast<float*>(lds + TILE + NIMG * WIMG);      // gap scratch [4 waves][32 floats], then the same again for the sums of squares
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, kq = lane >> 4;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
@@ -1015,7 +1018,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_persistent_kernel(ConvArgs
     // launch at the memory-side counters against 196 MB for the tiled kernel.)
     const int NWG = gridDim.x;
     const int t_begin = wg, t_end = total_tiles;
-    (void)tiles_per_wg;
     if (t_begin >= t_end) return;
 
     // all weights -> LDS, once: NIMG x 18 pieces of 64 slots, dealt round-robin to the 4 waves
@@ -1037,7 +1039,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_persistent_kernel(ConvArgs
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int idx = tid + it * 256;
-        const int p = (idx >> 5) * 8 + (idx & 7), oc = (idx >> 3) & 3;
+        const int p = stage_pixel(idx), oc = stage_octet(idx);
         piy[it] = p / IW;
         pix[it] = p - piy[it] * IW;
         lslot[it] = p < NPIX ? oc * PL + p : -1;
@@ -1084,10 +1086,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_persistent_kernel(ConvArgs
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             if (lslot[it] >= 0) {
-                bf8 hi, lo;
-                split_octet<TERMS == 3>(pv[it][0], pv[it][1], hi, lo);
-                tile[lslot[it]] = hi;
-                if (TERMS == 3) tile[4 * PL + lslot[it]] = lo;
+                store_split<TERMS, PL>(tile, lslot[it], pv[it][0], pv[it][1]);
             }
         }
     };
@@ -1099,15 +1098,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_persistent_kernel(ConvArgs
     }
     // (Keeping the hi weight fragments of all 9 taps in registers -- 72 VGPRs, a quarter less LDS fragment traffic -- measured no faster
     //  in the step and 7 % slower alone: the fragment reads are not what bounds this kernel.)
-    struct Frags { bf8 wh[NT], wlf[NT], xh[MT], xl[MT]; };
+    using Frags = ConvFrags<NT, MT>;
     auto read_frags = [&](Frags& f, int tap) {
-        const bf8* Wh = wl + tap * WTAP + kq * 32 + li;
         const int kh = tap / 3, kw = tap - kh * 3, toff = kh * IW + kw;
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-            f.wh[n] = Wh[n * 16];
-            if (TERMS == 3) f.wlf[n] = Wh[WIMG + n * 16];
-        }
+        read_w_frags<TERMS, WIMG>(f, wl + tap * WTAP + kq * 32 + li);
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
             f.xh[t] = tile[kq * PL + pbase[t] + toff];
@@ -1148,24 +1142,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_persistent_kernel(ConvArgs
     load_tile(cur);
     load_res(cur);
     wait_vmcnt_imm<0>();                       // the weight copies have landed (this wave's); the barrier below publishes all of them
-    unsigned int ph[6] = {0, 0, 0, 0, 0, 0};
-    unsigned long long tk = 0;
-    auto stamp = [&](int i) {
-        if constexpr (STAMP) {
-            const unsigned long long now = __builtin_amdgcn_s_memtime();
-            if (i >= 0) ph[i] += (unsigned int)(now - tk);
-            tk = now;
-        }
-    };
     for (int L = t_begin; L < t_end; L += NWG, cur = nxt) {
         const int b = cur.b, tile_id = cur.ty * a.tiles_x + cur.tx;
         const int oy0 = cur.ty * TH, ox0 = cur.tx * 32;
         advance(nxt);
-        stamp(-1);
         store_tile();
-        stamp(0);
         __syncthreads();                        // tile (and, first time, weights) visible
-        stamp(1);
         // halo AND residual of the NEXT tile: in flight during this tile's 9 taps and epilogue
         int pixo[MT];
         f4 rs[MT][NT];
@@ -1180,7 +1162,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_persistent_kernel(ConvArgs
         const bool has_res = a.res != nullptr;
         if (L + NWG < t_end) load_res(nxt);
         if (L + NWG < t_end) load_tile(nxt);
-        stamp(2);
 
         f4 acc[MT][NT];
 #pragma unroll
@@ -1196,22 +1177,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_persistent_kernel(ConvArgs
 #pragma unroll
             for (int t = 0; t < MT; ++t)
 #pragma unroll
-                for (int n = 0; n < NT; ++n) {
-                    if (TERMS == 3) {
-                        acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wlf[n], f.xh[t], acc[t][n], 0, 0, 0);
-                        acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wh[n], f.xl[t], acc[t][n], 0, 0, 0);
-                    }
-                    acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.wh[n], f.xh[t], acc[t][n], 0, 0, 0);
-                }
+                for (int n = 0; n < NT; ++n) acc[t][n] = mfma_split<TERMS>(f.wh[n], f.wl[n], f.xh[t], f.xl[t], acc[t][n]);
         }
 
-        if constexpr (STAMP) {
-#pragma unroll
-            for (int t = 0; t < MT; ++t)
-#pragma unroll
-                for (int n = 0; n < NT; ++n) asm volatile("" : "+v"(acc[t][n]));        // the stamp must not move above the last MFMA's result
-        }
-        stamp(3);
         float* __restrict__ yb = a.y + (size_t)b * hw * 32;
         f4 gsum[NT], gsq[NT];
 #pragma unroll
@@ -1223,17 +1191,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_persistent_kernel(ConvArgs
 #pragma unroll
             for (int t = 0; t < MT; ++t) {
                 f4 v = acc[t][n] + bi[n];
-                if (a.relu) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-                }
+                if (a.relu) v = relu4(v);
                 v = v * sc[n] + sh[n];
                 if (a.gate) v = v * gt;
                 if (has_res && pixo[t] >= 0) v += rs[t][n];
-                if (a.relu2) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-                }
+                if (a.relu2) v = relu4(v);
                 if (pixo[t] >= 0) {
                     *reinterpret_cast<f4*>(yb + pixo[t] * 32 + co) = v;
                     gsum[n] += v;
@@ -1248,29 +1210,22 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_persistent_kernel(ConvArgs
                 for (int r = 0; r < 4; ++r) {
                     float sm = gsum[n][r];
                     sm = row16_sum(sm);
-                    if (li == 0) sred[wave * sred_pitch + n * 16 + kq * 4 + r] = sm;
-                    if (a.gap2) {               // 4-row tiles only (launch check): the squares' scratch follows the sums'
+                    if (li == 0) sred[wave * 32 + n * 16 + kq * 4 + r] = sm;
+                    if (a.gap2) {               // the squares' scratch follows the sums'
                         float q = gsq[n][r];
                         q = row16_sum(q);
                         if (li == 0) sred[128 + wave * 32 + n * 16 + kq * 4 + r] = q;
                     }
                 }
         }
-        stamp(4);
         __syncthreads();                        // every wave is done with the tile image (and the gap scratch is complete)
-        stamp(5);
         if (a.gap && tid < 32) {
             float sm = 0.f;
 #pragma unroll
-            for (int m = 0; m < 4; ++m) sm += sred[m * sred_pitch + tid];
+            for (int m = 0; m < 4; ++m) sm += sred[m * 32 + tid];
             a.gap[((size_t)b * a.tiles + tile_id) * 32 + tid] = sm;
             if (a.gap2) a.gap2[((size_t)b * a.tiles + tile_id) * 32 + tid] = (sred[128 + tid] + sred[160 + tid]) + (sred[192 + tid] + sred[224 + tid]);
         }
-    }
-    if constexpr (STAMP) {
-        if (lane == 0 && a.dbg)
-#pragma unroll
-            for (int i = 0; i < 6; ++i) a.dbg[((size_t)blockIdx.x * 4 + wave) * 8 + i] = ph[i];
     }
 }
 
@@ -1507,45 +1462,107 @@ __global__ __launch_bounds__(256) void se_tail_downsample_kernel(const float* __
     }
 }
 
-template <int CIN, int NT, int S, int TH, int WM, int WN, int TERMS, int SCC = 0>
-int launch_conv_bf16(const ConvArgs& a, const bf8* whi, const bf8* wlo, dim3 grid, hipStream_t st) {
-    // weight-ring depth: 3 where the K loop is long (C >= 64, stride 1); 2 for the HBM-bound C=32 layer and the
-    // stride-2 entries (smaller LDS footprint => one more workgroup per CU)
-    constexpr int RING = 3;
-    using G = ConvGeom<S, TH>;
-    constexpr int NIMG = (TERMS == 3) ? 2 : 1;
-    constexpr size_t LDS_BYTES = sizeof(bf8) * (size_t)(NIMG * 4 * G::PL + RING * NIMG * 4 * NT * 16);
-    auto kern = conv3x3_bf16_kernel<CIN, NT, S, TH, WM, WN, TERMS, RING, false, false, SCC>;
-    if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS_BYTES, "conv3x3")) return rc;
-    hipLaunchKernelGGL(kern, grid, dim3(256), LDS_BYTES, st, a, whi, wlo);
-    return eg_check_launch("conv3x3");
+// ---- launch functions ---------------------------------------------------------------------------------------------------------------
+// A launch with dynamic LDS: opt the kernel in past 64 KB (once per kernel and device), launch 256 threads per workgroup, check.
+template <typename K, typename... Args>
+int launch_dyn(K kernel, dim3 grid, size_t lds_bytes, const char* what, hipStream_t st, const Args&... args) {
+    if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds_bytes, what)) return rc;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds_bytes, st, args...);
+    return eg_check_launch(what);
 }
 
-// Channel-split launch of a stride-1 body convolution: NTS * 16 output channels per workgroup, grid.z = cout / (NTS * 16) (conv3x3_bf16_kernel, SPLIT).
-template <int CIN, int NTS, int TH, int WM, int WN, int TERMS, int SCC = 0>
-int launch_conv_split_t(ConvArgs a, int batch, const bf8* whi, const bf8* wlo, hipStream_t st) {
-    constexpr int RING = 3;
-    using G = ConvGeom<1, TH>;
-    constexpr int NIMG = (TERMS == 3) ? 2 : 1;
-    constexpr size_t LDS_BYTES = sizeof(bf8) * (size_t)(NIMG * 4 * G::PL + RING * NIMG * 4 * NTS * 16);
-    auto kern = conv3x3_bf16_kernel<CIN, NTS, 1, TH, WM, WN, TERMS, RING, true, false, SCC>;
-    if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS_BYTES, "conv3x3 (channel split)")) return rc;
+// The split-bf16 images of a packed 3x3 weight (eg_conv3x3_packed_floats): [fp32 image: 9 * cin * coutp floats][hi: 9 * cin / 8 * coutp octets][lo: the same].
+// The only place that knows the arena layout behind the fp32 image.
+struct PackedImages { const bf8* whi; const bf8* wlo; };
+PackedImages packed_images(const float* w, int cin, int coutp) {
+    const bf8* whi = reinterpret_cast<const bf8*>(w + (size_t)9 * cin * coutp);
+    return {whi, whi + (size_t)9 * (cin / 8) * coutp};
+}
+
+// ---- routes ---------------------------------------------------------------------------------------------------------------------------
+// One entry per supported (input channels, stride, output channels).  `rows` is the tile height that sizes the grid AND the layout of the pooling partials
+// (eg_conv3x3_gap_tiles: callers size their buffers from it), wm x wn the wave grid (pixels x channels) of the tiled kernels, `split` the largest channel
+// split.  The launch functions below take their template arguments from here, so a launch and its buffers cannot disagree.
+struct ConvRoute {
+    int cin, stride, cout_lo, cout_hi, rows, wm, wn, split = 1;
+    constexpr int nt() const { return (cout_hi + 15) / 16; }        // 16-channel tiles of the padded output channels (the row length of the packed images)
+};
+enum { R_32, R_32_NARROW, R_32_64, R_64, R_64_128, R_64_128_S1, R_128, R_128_64, R_128_48, R_128_256, R_256, NROUTES };
+constexpr ConvRoute ROUTES[NROUTES] = {
+    {.cin = 32, .stride = 1, .cout_lo = 32, .cout_hi = 32, .rows = 4, .wm = 4, .wn = 1},        // HBM-bound first stage: smaller LDS footprint, more workgroups in flight
+    {.cin = 32, .stride = 1, .cout_lo = 17, .cout_hi = 31, .rows = 8, .wm = 4, .wn = 1},
+    {.cin = 32, .stride = 2, .cout_lo = 49, .cout_hi = 64, .rows = 2, .wm = 2, .wn = 2},        // stage entry
+    {.cin = 64, .stride = 1, .cout_lo = 49, .cout_hi = 64, .rows = 8, .wm = 4, .wn = 1, .split = 2},
+    {.cin = 64, .stride = 2, .cout_lo = 113, .cout_hi = 128, .rows = 2, .wm = 2, .wn = 2},      // stage entry
+    {.cin = 64, .stride = 1, .cout_lo = 128, .cout_hi = 128, .rows = 4, .wm = 2, .wn = 2},      // training: input gradient of final_conv1 (dy padded to 64 channels)
+    {.cin = 128, .stride = 1, .cout_lo = 65, .cout_hi = 128, .rows = 4, .wm = 2, .wn = 2, .split = 4},      // body; final_conv1 with 65 .. 128 frames on zero-padded weights
+    {.cin = 128, .stride = 1, .cout_lo = 49, .cout_hi = 64, .rows = 4, .wm = 4, .wn = 1},       // final_conv1: 128 -> frames (60 -> 64)
+    {.cin = 128, .stride = 1, .cout_lo = 1, .cout_hi = 48, .rows = 4, .wm = 4, .wn = 1},        // final_conv1 (34 -> 48)
+    // 256-channel stage of the audio emotion classifier (model/audio_emotion_classifer.py:20-22): 2-row tiles, waves split the channels
+    {.cin = 128, .stride = 2, .cout_lo = 241, .cout_hi = 256, .rows = 2, .wm = 1, .wn = 4},
+    {.cin = 256, .stride = 1, .cout_lo = 256, .cout_hi = 256, .rows = 2, .wm = 1, .wn = 4},
+};
+constexpr int route_index(int cin, int cout, int stride) {      // NROUTES: no kernel serves the shape
+    int i = 0;
+    while (i < NROUTES && !(ROUTES[i].cin == cin && ROUTES[i].stride == stride && cout >= ROUTES[i].cout_lo && cout <= ROUTES[i].cout_hi)) ++i;
+    return i;
+}
+// eg_conv3x3_gap_tiles answers for every shape (callers size buffers first): a route's `rows`, else this rule, which on the routes gives `rows` too (checked below)
+constexpr int unserved_tile_rows(int cin, int cout, int stride) {
+    if (stride == 2 || cout >= 256) return 2;
+    if (cin == 32 && cout == 32) return 4;
+    return (cout >= 128 || cin >= 128) ? 4 : 8;
+}
+constexpr int conv_tile_rows(int cin, int cout, int stride) {
+    const int i = route_index(cin, cout, stride);
+    return i < NROUTES ? ROUTES[i].rows : unserved_tile_rows(cin, cout, stride);
+}
+constexpr bool routes_keep_the_tile_rows() {
+    for (const ConvRoute& r : ROUTES)
+        for (int cout = r.cout_lo; cout <= r.cout_hi; ++cout)
+            if (r.rows != unserved_tile_rows(r.cin, cout, r.stride)) return false;
+    return true;
+}
+static_assert(routes_keep_the_tile_rows(), "a route's tile height differs from what eg_conv3x3_gap_tiles has always answered for its shapes");
+static_assert(ROUTES[R_32].rows == C32_ROWS, "the persistent walk writes the route's partial layout");
+
+// Route I's tiled kernel, one workgroup per rows x 32 tile and all output channels (conv3x3_f32_kernel, or conv3x3_bf16_kernel on the route's wave grid).
+// SCC > 0: conv2 of a stage-entry block, which contracts SCC 32-channel chunks of the block input through the 1x1 downsample shortcut itself.
+template <int I, int SCC = 0>
+int launch_conv(const ConvArgs& a, int batch, int precision, hipStream_t st) {
+    constexpr ConvRoute R = ROUTES[I];
+    const dim3 grid(a.tiles, batch);
+    if (precision == EG_PREC_F32) {
+        if constexpr (SCC > 0) {
+            eg_set_error("conv3x3: the fused downsample shortcut exists in the split-bf16 modes only");
+            return EG_ERR_UNSUPPORTED;
+        }
+        hipLaunchKernelGGL((conv3x3_f32_kernel<R.cin, R.nt(), R.stride, R.rows>), grid, dim3(256), 0, st, a);
+        return eg_check_launch("conv3x3");
+    }
+    const PackedImages p = packed_images(a.w, R.cin, R.nt() * 16);
+    constexpr int PL = ConvBf16Geom<R.stride, R.rows, false>::PL;
+    if (precision == EG_PREC_BF16X3)
+        return launch_dyn(conv3x3_bf16_kernel<R.cin, R.nt(), R.stride, R.rows, R.wm, R.wn, 3, false, false, SCC>, grid, RingLds<PL, R.nt() * 16, 3>::BYTES, "conv3x3", st, a, p.whi, p.wlo);
+    return launch_dyn(conv3x3_bf16_kernel<R.cin, R.nt(), R.stride, R.rows, R.wm, R.wn, 1, false, false, SCC>, grid, RingLds<PL, R.nt() * 16, 1>::BYTES, "conv3x3", st, a, p.whi, p.wlo);
+}
+// Channel-split launch of a stride-1 C -> C body convolution (bf16x3): 1 / SPLIT of the output channels per workgroup, grid.z = SPLIT; bitwise the unsplit kernel
+template <int I, int SPLIT, int SCC = 0>
+int launch_conv_split(ConvArgs a, int batch, hipStream_t st) {
+    constexpr ConvRoute R = ROUTES[I];
+    constexpr int NTS = R.nt() / SPLIT;
+    const PackedImages p = packed_images(a.w, R.cin, a.cout);
     a.wrow = a.cout;
-    hipLaunchKernelGGL(kern, dim3(a.tiles, batch, a.cout / (NTS * 16)), dim3(256), LDS_BYTES, st, a, whi, wlo);
-    return eg_check_launch("conv3x3 (channel split)");
+    return launch_dyn(conv3x3_bf16_kernel<R.cin, NTS, 1, R.rows, R.wm, R.wn, 3, true, false, SCC>, dim3(a.tiles, batch, SPLIT),
+                      RingLds<ConvBf16Geom<1, R.rows, false>::PL, NTS * 16, 3>::BYTES, "conv3x3 (channel split)", st, a, p.whi, p.wlo);
 }
 // Input gradient of a stride-2 convolution (conv3x3_bf16_kernel, DG2): KCH = the convolution's output channels (the contraction), NTN * 16 = its input
 // channels; grid over TH x 32 tiles of the dy grid.
 template <int KCH, int NTN, int TH, int WM, int WN>
-int launch_dgrad_s2_t(const ConvArgs& a, int batch, const bf8* whi, const bf8* wlo, hipStream_t st) {
-    constexpr int RING = 3;
-    using G = ConvGeomDG2<TH>;
-    constexpr size_t LDS_BYTES = sizeof(bf8) * (size_t)(2 * 4 * G::PL + RING * 2 * 4 * NTN * 16);
-    auto kern = conv3x3_bf16_kernel<KCH, NTN, 1, TH, WM, WN, 3, RING, false, true>;
-    if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS_BYTES, "conv3x3 (stride-2 input gradient)")) return rc;
-    dim3 grid(eg_cdiv(a.W, 32) * eg_cdiv(a.H, TH), batch);
-    hipLaunchKernelGGL(kern, grid, dim3(256), LDS_BYTES, st, a, whi, wlo);
-    return eg_check_launch("conv3x3 (stride-2 input gradient)");
+int launch_dgrad_s2(const ConvArgs& a, int batch, hipStream_t st) {
+    const PackedImages p = packed_images(a.w, KCH, NTN * 16);        // the flipped image: KCH "input" channels -> NTN * 16 "output" channels
+    return launch_dyn(conv3x3_bf16_kernel<KCH, NTN, 1, TH, WM, WN, 3, false, true>, dim3(eg_cdiv(a.W, 32) * eg_cdiv(a.H, TH), batch),
+                      RingLds<ConvBf16Geom<1, TH, true>::PL, NTN * 16, 3>::BYTES, "conv3x3 (stride-2 input gradient)", st, a, p.whi, p.wlo);
 }
 // how many ways to split the channels of a C -> C body convolution with `wgs` pixel-tile workgroups: keep the launch near one workgroup per CU
 int conv_channel_split(int wgs, int max_split) {
@@ -1558,53 +1575,31 @@ int conv_channel_split(int wgs, int max_split) {
     while (split < max_split && wgs * split * 2 <= 512) split *= 2;
     return split;
 }
-
-// the channel split a C -> C body convolution takes (1: none; the split kernels exist for bf16x3, stride 1, 64 and 128 channels, NHWC output)
+// the channel split a C -> C body convolution takes (1: none; the split kernels exist for bf16x3 and NHWC output)
 int body_channel_split(int batch, int tiles, int cin, int cout, int stride, int precision, int nchw_out) {
-    if (!((cin == 64 || cin == 128) && cout == cin && stride == 1 && precision == EG_PREC_BF16X3 && !nchw_out)) return 1;
-    return conv_channel_split(tiles * batch, cin == 128 ? 4 : 2);
+    const int i = route_index(cin, cout, stride);
+    if (i == NROUTES || cout != cin || precision != EG_PREC_BF16X3 || nchw_out) return 1;
+    return conv_channel_split(tiles * batch, ROUTES[i].split);
 }
 
-template <int CIN, int NT, int S, int TH, int WM, int WN, int SCC = 0>
-int launch_conv(const ConvArgs& a, int batch, int precision, hipStream_t st) {
-    dim3 grid(a.tiles, batch), block(256);
-    if (precision == EG_PREC_F32) {
-        if constexpr (SCC > 0) {
-            eg_set_error("conv3x3: the fused downsample shortcut exists in the split-bf16 modes only");
-            return EG_ERR_UNSUPPORTED;
-        }
-        hipLaunchKernelGGL((conv3x3_f32_kernel<CIN, NT, S, TH>), grid, block, 0, st, a);
-        return eg_check_launch("conv3x3");
-    }
-    // packed bf16 weights follow the fp32 image in the arena: [hi image][lo image], each 9*CIN*COUTP bf16
-    const size_t f32_floats = (size_t)9 * CIN * NT * 16;
-    const bf8* whi = reinterpret_cast<const bf8*>(a.w + f32_floats);
-    const bf8* wlo = whi + (size_t)9 * (CIN / 8) * NT * 16;
-    if (precision == EG_PREC_BF16X3) return launch_conv_bf16<CIN, NT, S, TH, WM, WN, 3, SCC>(a, whi, wlo, grid, st);
-    return launch_conv_bf16<CIN, NT, S, TH, WM, WN, 1, SCC>(a, whi, wlo, grid, st);
-}
-
-// The two stage-entry convolutions (32 -> 64, 64 -> 128, stride 2) on parity planes (conv3x3_s2_planes_kernel): TH x 32 output tiles.
-template <int CIN, int NTT, int TH, int WM, int WN>
+// A stage-entry route (32 -> 64, 64 -> 128, stride 2) on parity planes (conv3x3_s2_planes_kernel): TH x 32 output tiles, a wave per 2 x 32 output block of
+// its channel range (wave grid TH / 2 x 8 / TH).
+template <int I, int TH>
 int launch_conv_s2_planes(const ConvArgs& a, int batch, int precision, hipStream_t st) {
-    using G = ConvGeomS2P<TH>;
-    const bf8* whi = reinterpret_cast<const bf8*>(a.w + (size_t)9 * CIN * NTT * 16);
-    const bf8* wlo = whi + (size_t)9 * (CIN / 8) * NTT * 16;
+    constexpr int CIN = ROUTES[I].cin, NTT = ROUTES[I].nt(), WM = TH / 2, WN = 4 / WM, PL = ConvGeomS2P<TH>::PL;
+    static_assert(ROUTES[I].rows == 2, "the plane walk writes the partials of 2 x 32 blocks (conv_s2_form)");
+    const PackedImages p = packed_images(a.w, CIN, NTT * 16);
     const dim3 grid(a.tiles_x * eg_cdiv(a.Ho, TH), batch);
-    auto go = [&](auto kern, size_t lds_bytes) {
-        if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds_bytes, "conv3x3 (stride 2, planes)")) return rc;
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, st, a, whi, wlo);
-        return eg_check_launch("conv3x3 (stride 2, planes)");
-    };
-    constexpr size_t LDS3 = sizeof(bf8) * (size_t)(2 * 4 * G::PL + 3 * 2 * 4 * NTT * 16), LDS1 = sizeof(bf8) * (size_t)(4 * G::PL + 3 * 4 * NTT * 16);
-    if (a.in_scale) {           // the training path's input affine: instantiations of their own, so that the inference kernels carry none of it
-        if (precision == EG_PREC_BF16X3) return go(conv3x3_s2_planes_kernel<CIN, NTT, TH, WM, WN, 3, true>, LDS3);
-        return go(conv3x3_s2_planes_kernel<CIN, NTT, TH, WM, WN, 1, true>, LDS1);
-    }
-    if (precision == EG_PREC_BF16X3) return go(conv3x3_s2_planes_kernel<CIN, NTT, TH, WM, WN, 3, false>, LDS3);
-    return go(conv3x3_s2_planes_kernel<CIN, NTT, TH, WM, WN, 1, false>, LDS1);
+    auto go = [&](auto kern, size_t lds_bytes) { return launch_dyn(kern, grid, lds_bytes, "conv3x3 (stride 2, planes)", st, a, p.whi, p.wlo); };
+    // the training path's input affine has instantiations of its own, so that the inference kernels carry none of it
+    if (precision == EG_PREC_BF16X3)
+        return a.in_scale ? go(conv3x3_s2_planes_kernel<CIN, NTT, TH, WM, WN, 3, true>, RingLds<PL, NTT * 16, 3>::BYTES)
+                          : go(conv3x3_s2_planes_kernel<CIN, NTT, TH, WM, WN, 3, false>, RingLds<PL, NTT * 16, 3>::BYTES);
+    return a.in_scale ? go(conv3x3_s2_planes_kernel<CIN, NTT, TH, WM, WN, 1, true>, RingLds<PL, NTT * 16, 1>::BYTES)
+                      : go(conv3x3_s2_planes_kernel<CIN, NTT, TH, WM, WN, 1, false>, RingLds<PL, NTT * 16, 1>::BYTES);
 }
-// Which form a stage-entry convolution takes: 0 = interleaved halo (conv3x3_bf16_kernel, S = 2, 2-row tiles), else the tile height of the plane walk.
+// Which form a stage-entry convolution takes: 0 = interleaved halo (conv3x3_bf16_kernel, S = 2, the route's 2-row tiles), else the tile height of the plane walk.
+// The larger tiles belong to that form alone: its pooling partials keep the route's 2-row layout, so eg_conv3x3_gap_tiles is the same for both forms.
 // EG_CONV_S2 is an A/B switch read per call (a captured graph keeps what it was captured with): "interleaved"; "planes" (the plane walk at every
 // size); "planes4" / "planes8" (the same with the 32 -> 64 entry's tile height forced; the 64 -> 128 entry has 4-row tiles only); unset = by size.
 // Measured alone (TED shapes, bf16x3, us per launch at 1 / 8 / 16 / 32 / 64 clips; profiles/r13_stride2_planes_ab.txt):
@@ -1628,84 +1623,112 @@ bool conv32_persistent_enabled() {
     static const bool on = [] { const char* e = getenv("EG_CONV32_PERSISTENT"); return !(e && e[0] == '0'); }();
     return on;
 }
-
-template <int TERMS, int TH>
-int launch_conv32_persistent_t(const ConvArgs& a, int batch, const bf8* whi, const bf8* wlo, hipStream_t st) {
-    using G = ConvGeom<1, TH>;
-    constexpr int NIMG = (TERMS == 3) ? 2 : 1;
-    constexpr size_t LDS_BYTES = sizeof(bf8) * (size_t)(NIMG * 4 * G::PL + NIMG * 9 * 128) + (TH == 4 ? 2 * 4 * 32 * sizeof(float) : 0);   // + sums / squares scratch
-    auto kern = conv3x3_c32_persistent_kernel<TERMS, TH>;
-    if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS_BYTES, "conv3x3 (32 -> 32, persistent)")) return rc;
+int launch_conv32_persistent(const ConvArgs& a, int batch, int precision, hipStream_t st) {
+    const PackedImages p = packed_images(a.w, 32, 32);
     const int total = a.tiles * batch;
     // 512 = 2 workgroups per CU, each walking total / 512 tiles (more, shorter-lived workgroups were measured slower alone and under four lanes:
     // profiles/r05_conv32_experiments.txt).
-    const int cap = 512;
-    int grid = total < cap ? total : cap;
-    int tpw = eg_cdiv(total, grid);
-    grid = eg_cdiv(total, tpw);
+    int grid = total < 512 ? total : 512;
+    grid = eg_cdiv(total, eg_cdiv(total, grid));
     if (grid >= 8) grid = (int)eg_round_up(grid, 8);             // XCD remap needs a multiple of 8 (surplus workgroups exit at once)
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDS_BYTES, st, a, whi, wlo, total, tpw);
-    return eg_check_launch("conv3x3 (32 -> 32, persistent)");
-}
-int launch_conv32_persistent(const ConvArgs& a, int batch, int precision, int th, hipStream_t st) {
-    const size_t f32_floats = (size_t)9 * 32 * 32;
-    const bf8* whi = reinterpret_cast<const bf8*>(a.w + f32_floats);
-    const bf8* wlo = whi + (size_t)9 * 4 * 32;
-    static const bool stamp = [] { const char* e = getenv("EG_CONV32_STAMP"); return e && e[0] == '1'; }();
-    if (stamp && precision == EG_PREC_BF16X3 && th == 4) {
-        // diagnostic: per-phase cycle sums of every wave, averaged and printed after the launch (synchronises: never use while timing)
-        static unsigned int* dbg = nullptr;
-        const int nwords = 512 * 4 * 8;
-        if (!dbg && hipMalloc(&dbg, nwords * sizeof(unsigned int)) != hipSuccess) return EG_ERR_HIP;
-        (void)hipMemsetAsync(dbg, 0, nwords * sizeof(unsigned int), st);
-        ConvArgs b = a;
-        b.dbg = dbg;
-        constexpr size_t LDS_BYTES = sizeof(bf8) * (size_t)(2 * 4 * ConvGeom<1, 4>::PL + 2 * 9 * 128) + 2 * 4 * 32 * sizeof(float);   // sums + squares (a.gap2), as the production launch
-        auto kern = conv3x3_c32_persistent_kernel<3, 4, true>;
-        if (int rc = eg_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS_BYTES, "conv3x3 (stamps)")) return rc;
-        const int total = a.tiles * batch;
-        int grid = total < 512 ? total : 512;
-        grid = eg_cdiv(total, eg_cdiv(total, grid));
-        if (grid >= 8) grid = (int)eg_round_up(grid, 8);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDS_BYTES, st, b, whi, wlo, total, 0);
-        static unsigned int host[512 * 4 * 8];
-        if (hipMemcpyAsync(host, dbg, sizeof(host), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return EG_ERR_HIP;
-        double sum[6] = {0, 0, 0, 0, 0, 0};
-        int nw = 0;
-        for (int w = 0; w < grid * 4; ++w) {
-            if (host[w * 8 + 3] == 0) continue;
-            ++nw;
-            for (int i = 0; i < 6; ++i) sum[i] += host[w * 8 + i];
-        }
-        const double tiles_per_wave = (double)total / grid;
-        fprintf(stderr, "conv32 stamps (cycles per tile and wave, %d waves, %s residual): store_tile %.0f  barrier1 %.0f  issue_loads %.0f  taps %.0f  epilogue %.0f  barrier2 %.0f\n",
-                nw, a.res ? "with" : "no", sum[0] / nw / tiles_per_wave, sum[1] / nw / tiles_per_wave, sum[2] / nw / tiles_per_wave, sum[3] / nw / tiles_per_wave,
-                sum[4] / nw / tiles_per_wave, sum[5] / nw / tiles_per_wave);
-        return eg_check_launch("conv3x3 (32 -> 32, stamps)");
-    }
-    if (th == 8) {
-        if (precision == EG_PREC_BF16X3) return launch_conv32_persistent_t<3, 8>(a, batch, whi, wlo, st);
-        return launch_conv32_persistent_t<1, 8>(a, batch, whi, wlo, st);
-    }
-    if (precision == EG_PREC_BF16X3) return launch_conv32_persistent_t<3, 4>(a, batch, whi, wlo, st);
-    return launch_conv32_persistent_t<1, 4>(a, batch, whi, wlo, st);
+    const char* what = "conv3x3 (32 -> 32, persistent)";
+    if (precision == EG_PREC_BF16X3) return launch_dyn(conv3x3_c32_persistent_kernel<3>, dim3(grid), C32Lds<3>::BYTES, what, st, a, p.whi, p.wlo, total);
+    return launch_dyn(conv3x3_c32_persistent_kernel<1>, dim3(grid), C32Lds<1>::BYTES, what, st, a, p.whi, p.wlo, total);
 }
 
-int conv_tile_rows(int cin, int cout, int stride) {
-    if (stride == 2 || cout >= 256) return 2;
-    if (cin == 32 && cout == 32) {               // 4-row tiles: smaller LDS footprint, more workgroups in flight (HBM-bound layer)
-        static const int th = [] { const char* e = getenv("EG_CONV32_TH"); return (e && atoi(e) == 8) ? 8 : 4; }();      // experiment hook
-        return th;
+// the downsample shortcut conv2 of a stage-entry block contracts itself (conv3x3_bf16_kernel, SCC): block input x [B][h][w][cin], the packed 1x1 images
+// (EG_PACK_CONV1X1_BF16) and the per-clip vectors [f | q | h] of se_gate_pre_kernel
+struct ShortcutArgs { const float* x; const float* wimg; const float* vec; int h, w, cin, stride; };
+// what an entry point asks of conv3x3_dispatch: of `a` it fills the operands, H, W, cout, relu and nchw; the dispatch derives the rest
+struct ConvRequest {
+    ConvArgs a;
+    int batch, cin, stride, precision;
+    void* stream;
+    const ShortcutArgs* sc = nullptr;
+};
+
+int conv3x3_dispatch(ConvRequest q) {
+    ConvArgs& a = q.a;
+    const int batch = q.batch, h = a.H, wdt = a.W, cin = q.cin, cout = a.cout, stride = q.stride, precision = q.precision;
+    const ShortcutArgs* sc = q.sc;
+    EG_REQUIRE(a.x && a.w && a.y && batch > 0 && h > 0 && wdt > 0, EG_ERR_BAD_ARG, "eg_conv3x3: null pointer or empty shape");
+    EG_REQUIRE(!a.res_bits || (a.res && !a.gate && ((size_t)batch * h * wdt * cout) % 32 == 0), EG_ERR_BAD_ARG,
+               "eg_conv3x3_res_masked: the bit mask needs a residual, no gate and a map of a multiple of 32 elements");
+    EG_REQUIRE((a.in_scale == nullptr) == (a.in_shift == nullptr) && (!a.in_scale || (precision != EG_PREC_F32 && cin % 32 == 0 && eg_aligned16(a.in_scale) &&
+               eg_aligned16(a.in_shift))), EG_ERR_BAD_ARG, "eg_conv3x3: the input affine needs both vectors, a split-bf16 mode and cin %% 32 == 0");
+    // gate + residual: relu(v * gate + residual) (the fused SE tail); residual alone: v + residual, no ReLU (the training path's fused fan-in add:
+    // an input gradient that lands on a tensor with a second consumer, train/functional.py conv3x3(passthrough=True))
+    EG_REQUIRE(!a.gate || a.res, EG_ERR_BAD_ARG, "eg_conv3x3_se: a gate needs a residual");
+    EG_REQUIRE(!a.res || (!a.nchw && stride == 1 && cout % 4 == 0 && (!a.gate || eg_aligned16(a.gate)) && eg_aligned16(a.res) && a.res != a.y),
+               EG_ERR_BAD_ARG, "eg_conv3x3_se: the fused residual needs NHWC output, stride 1, cout %% 4 == 0 and a residual buffer distinct from y");
+    EG_REQUIRE(eg_aligned16(a.x) && eg_aligned16(a.w) && eg_aligned16(a.y), EG_ERR_ALIGN, "eg_conv3x3: pointers must be 16-byte aligned");
+    EG_REQUIRE(stride == 1 || stride == 2, EG_ERR_UNSUPPORTED, "eg_conv3x3: stride %d", stride);
+    EG_REQUIRE(precision >= 0 && precision <= 2, EG_ERR_BAD_ARG, "eg_conv3x3: precision %d", precision);
+    EG_REQUIRE(a.nchw || (cout % 4 == 0), EG_ERR_UNSUPPORTED, "eg_conv3x3: NHWC output needs cout %% 4 == 0");
+    a.relu2 = a.gate ? 1 : 0;
+    a.Ho = (h + 2 - 3) / stride + 1; a.Wo = (wdt + 2 - 3) / stride + 1;
+    a.tiles_x = eg_cdiv(a.Wo, 32);
+    a.tiles = a.tiles_x * eg_cdiv(a.Ho, conv_tile_rows(cin, cout, stride));
+    hipStream_t st = (hipStream_t)q.stream;
+    EgProfScope prof((int64_t)cin * 1000000 + (int64_t)cout * 1000 + stride * 100 + 1,
+                     2.0 * 9 * cin * cout * (double)a.Ho * a.Wo * batch, st);
+    if (sc) {
+        EG_REQUIRE(precision != EG_PREC_F32 && stride == 1 && !a.nchw && cout == cin && (cin == 64 || cin == 128) && sc->cin * 2 == cin, EG_ERR_UNSUPPORTED,
+                   "conv3x3: the fused downsample shortcut serves 32 -> 64 and 64 -> 128 block entries in the split-bf16 modes (cin=%d cout=%d shortcut cin=%d)",
+                   cin, cout, sc->cin);
+        EG_REQUIRE(sc->x && sc->wimg && sc->vec && !a.gate && !a.res && !a.bias && !a.relu && !a.gap2 && !a.in_scale && sc->stride >= 1 &&
+                   (sc->h - 1) / sc->stride + 1 == h && (sc->w - 1) / sc->stride + 1 == wdt && eg_aligned16(sc->x) && eg_aligned16(sc->wimg) &&
+                   eg_aligned16(sc->vec), EG_ERR_BAD_ARG, "conv3x3: fused downsample shortcut: null / misaligned operand or a block input that does not map onto the output");
+        a.sc_x = sc->x; a.sc_vec = sc->vec; a.sc_H = sc->h; a.sc_W = sc->w; a.sc_S = sc->stride; a.sc_B = batch;
+        a.sc_whi = reinterpret_cast<const bf8*>(sc->wimg);       // the packed 1x1 images: [ci/8][co][8], hi then lo
+        a.sc_wlo = a.sc_whi + (size_t)(sc->cin / 8) * cout;
+        a.scale = a.shift = nullptr;             // the epilogue's scale and shift are the per-clip q and h
+        a.relu2 = 1;
     }
-    return (cout >= 128 || cin >= 128) ? 4 : 8;
+    // forms that replace the route's tiled kernel, bit for bit: a small body launch's channel split; a stage entry's plane walk (not fp32, NCHW, padded channels)
+    const int split = body_channel_split(batch, a.tiles, cin, cout, stride, precision, a.nchw);
+    const int s2p = (stride == 2 && cout % 16 == 0 && precision != EG_PREC_F32 && !a.nchw && (!a.gap || eg_aligned16(a.gap)) && (!a.gap2 || eg_aligned16(a.gap2)))
+                        ? conv_s2_form(cin, batch, a.Ho, a.Wo) : 0;
+    switch (route_index(cin, cout, stride)) {
+    case R_32: {
+        // the retired 8-row tiles (tools/experiments/README.md) are refused, read per call: a stale A/B script must not measure the default under the old name
+        const char* th = getenv("EG_CONV32_TH");
+        EG_REQUIRE(!(th && th[0] && strcmp(th, "4") != 0), EG_ERR_BAD_ARG, "eg_conv3x3: EG_CONV32_TH=%s: the 8-row tiles of the 32 -> 32 kernel are retired "
+                   "(tools/experiments/README.md); unset it or set 4", th);
+        if (precision != EG_PREC_F32 && !a.nchw && conv32_persistent_enabled()) return launch_conv32_persistent(a, batch, precision, st);
+        return launch_conv<R_32>(a, batch, precision, st);
+    }
+    case R_32_64:
+        if (s2p == 8) return launch_conv_s2_planes<R_32_64, 8>(a, batch, precision, st);
+        if (s2p == 4) return launch_conv_s2_planes<R_32_64, 4>(a, batch, precision, st);
+        return launch_conv<R_32_64>(a, batch, precision, st);
+    case R_64_128:
+        if (s2p == 4) return launch_conv_s2_planes<R_64_128, 4>(a, batch, precision, st);
+        return launch_conv<R_64_128>(a, batch, precision, st);
+    case R_64:
+        if (sc) return split == 2 ? launch_conv_split<R_64, 2, 1>(a, batch, st) : launch_conv<R_64, 1>(a, batch, precision, st);
+        return split == 2 ? launch_conv_split<R_64, 2>(a, batch, st) : launch_conv<R_64>(a, batch, precision, st);
+    case R_128:
+        if (sc && split == 4) return launch_conv_split<R_128, 4, 2>(a, batch, st);
+        if (sc) return split == 2 ? launch_conv_split<R_128, 2, 2>(a, batch, st) : launch_conv<R_128, 2>(a, batch, precision, st);
+        if (split == 4) return launch_conv_split<R_128, 4>(a, batch, st);
+        return split == 2 ? launch_conv_split<R_128, 2>(a, batch, st) : launch_conv<R_128>(a, batch, precision, st);
+    case R_32_NARROW: return launch_conv<R_32_NARROW>(a, batch, precision, st);
+    case R_64_128_S1: return launch_conv<R_64_128_S1>(a, batch, precision, st);
+    case R_128_64: return launch_conv<R_128_64>(a, batch, precision, st);
+    case R_128_48: return launch_conv<R_128_48>(a, batch, precision, st);
+    case R_128_256: return launch_conv<R_128_256>(a, batch, precision, st);
+    case R_256: return launch_conv<R_256>(a, batch, precision, st);
+    }
+    eg_set_error("eg_conv3x3: unsupported channels cin=%d cout=%d stride=%d", cin, cout, stride);
+    return EG_ERR_UNSUPPORTED;
 }
 
 }  // namespace
 
 extern "C" int32_t eg_conv3x3_gap_tiles(int32_t h, int32_t wdt, int32_t cin, int32_t cout, int32_t stride) {
     const int ho = (h + 2 - 3) / stride + 1, wo = (wdt + 2 - 3) / stride + 1;
-    const int th = conv_tile_rows(cin, cout, stride);
-    return eg_cdiv(ho, th) * eg_cdiv(wo, 32);
+    return eg_cdiv(ho, conv_tile_rows(cin, cout, stride)) * eg_cdiv(wo, 32);
 }
 
 // The channel split eg_conv3x3 (and every entry point that shares its dispatch: _se, _sq, _sq_in_affine, _res_masked) takes for this launch.
@@ -1724,19 +1747,12 @@ extern "C" int eg_conv3x3(const float* x, const float* w, const float* bias, con
     return eg_conv3x3_se(x, w, bias, scale, shift, nullptr, nullptr, y, gap_partial, batch, h, wdt, cin, cout, stride, relu, nchw_out, precision, stream);
 }
 
-namespace {
-// the downsample shortcut conv2 of a stage-entry block contracts itself (conv3x3_bf16_kernel, SCC): block input x [B][h][w][cin], the packed 1x1 images
-// (EG_PACK_CONV1X1_BF16) and the per-clip vectors [f | q | h] of se_gate_pre_kernel
-struct ShortcutArgs { const float* x; const float* wimg; const float* vec; int h, w, cin, stride; };
-int conv3x3_dispatch(const float* x, const float* w, const float* bias, const float* scale, const float* shift, const float* gate, const float* residual,
-                     float* y, float* gap_partial, float* gap_sq, int32_t batch, int32_t h, int32_t wdt, int32_t cin, int32_t cout, int32_t stride,
-                     int32_t relu, int32_t nchw_out, int32_t precision, void* stream, const float* in_scale = nullptr, const float* in_shift = nullptr,
-                     const uint32_t* res_bits = nullptr, const ShortcutArgs* sc = nullptr);
-}
 extern "C" int eg_conv3x3_se(const float* x, const float* w, const float* bias, const float* scale, const float* shift, const float* gate,
                              const float* residual, float* y, float* gap_partial, int32_t batch, int32_t h, int32_t wdt, int32_t cin,
                              int32_t cout, int32_t stride, int32_t relu, int32_t nchw_out, int32_t precision, void* stream) {
-    return conv3x3_dispatch(x, w, bias, scale, shift, gate, residual, y, gap_partial, nullptr, batch, h, wdt, cin, cout, stride, relu, nchw_out, precision, stream);
+    return conv3x3_dispatch({.a = {.x = x, .w = w, .bias = bias, .scale = scale, .shift = shift, .y = y, .gap = gap_partial, .H = h, .W = wdt, .cout = cout,
+                                   .relu = relu, .nchw = nchw_out, .gate = gate, .res = residual},
+                             .batch = batch, .cin = cin, .stride = stride, .precision = precision, .stream = stream});
 }
 // y = conv(x) + (bit ? residual : 0): the input gradient of an SE block's first convolution with the identity shortcut's gradient
 // dout * (out > 0) (ResNetBlocks.py:33-36) added in the epilogue straight from dout and the tail's ReLU bits (csrc/train.hip: se_tail_fwd_kernel writes one bit
@@ -1744,8 +1760,8 @@ extern "C" int eg_conv3x3_se(const float* x, const float* w, const float* bias, 
 extern "C" int eg_conv3x3_res_masked(const float* x, const float* w, const float* residual, const uint32_t* res_bits, float* y, int32_t batch, int32_t h,
                                      int32_t wdt, int32_t cin, int32_t cout, int32_t precision, void* stream) {
     EG_REQUIRE(residual && res_bits, EG_ERR_BAD_ARG, "eg_conv3x3_res_masked: the residual and its bit mask are required");
-    return conv3x3_dispatch(x, w, nullptr, nullptr, nullptr, nullptr, residual, y, nullptr, nullptr, batch, h, wdt, cin, cout, 1, 0, 0, precision, stream, nullptr,
-                            nullptr, res_bits);
+    return conv3x3_dispatch({.a = {.x = x, .w = w, .y = y, .H = h, .W = wdt, .cout = cout, .res = residual, .res_bits = res_bits},
+                             .batch = batch, .cin = cin, .stride = 1, .precision = precision, .stream = stream});
 }
 // Training forward: y = [relu](conv(x) + bias), plus the per-(clip, tile) channel sums of y AND of y*y (both [batch][tiles][cout]): train-mode
 // BatchNorm takes its mean and variance from them (csrc/train.hip: eg_bn_train_forward_sq) without reading y again.  Split-bf16 modes only.
@@ -1753,10 +1769,8 @@ extern "C" int eg_conv3x3_sq(const float* x, const float* w, const float* bias, 
                              int32_t wdt, int32_t cin, int32_t cout, int32_t stride, int32_t relu, int32_t precision, void* stream) {
     EG_REQUIRE(gap_partial && gap_sq_partial, EG_ERR_BAD_ARG, "eg_conv3x3_sq: both partial buffers are required");
     EG_REQUIRE(precision != EG_PREC_F32, EG_ERR_UNSUPPORTED, "eg_conv3x3_sq: split-bf16 modes only (the fp32 kernel emits sums only)");
-    EG_REQUIRE(!(cin == 32 && cout == 32 && stride == 1) || conv_tile_rows(cin, cout, stride) == 4, EG_ERR_UNSUPPORTED,
-               "eg_conv3x3_sq: the 8-row experiment tiles of the 32 -> 32 kernel have no room for the squares scratch");
-    return conv3x3_dispatch(x, w, bias, nullptr, nullptr, nullptr, nullptr, y, gap_partial, gap_sq_partial, batch, h, wdt, cin, cout, stride, relu, 0, precision,
-                            stream);
+    return conv3x3_dispatch({.a = {.x = x, .w = w, .bias = bias, .y = y, .gap = gap_partial, .gap2 = gap_sq_partial, .H = h, .W = wdt, .cout = cout, .relu = relu},
+                             .batch = batch, .cin = cin, .stride = stride, .precision = precision, .stream = stream});
 }
 // eg_conv3x3_sq on x' = x * in_scale[ci] + in_shift[ci] (per INPUT channel, in-image pixels; the zero padding stays zero): the train-mode BatchNorm in
 // front of the convolution folded into its operand staging, so that the normalised map is never written (ResNetBlocks.py:26-27: bn1 -> conv2).
@@ -1765,100 +1779,10 @@ extern "C" int eg_conv3x3_sq_in_affine(const float* x, const float* in_scale, co
                                        int32_t stride, int32_t relu, int32_t precision, void* stream) {
     EG_REQUIRE(in_scale && in_shift, EG_ERR_BAD_ARG, "eg_conv3x3_sq_in_affine: both affine vectors are required");
     EG_REQUIRE(!gap_partial == !gap_sq_partial, EG_ERR_BAD_ARG, "eg_conv3x3_sq_in_affine: both partial buffers or none");
-    return conv3x3_dispatch(x, w, bias, nullptr, nullptr, nullptr, nullptr, y, gap_partial, gap_sq_partial, batch, h, wdt, cin, cout, stride, relu, 0, precision,
-                            stream, in_scale, in_shift);
+    return conv3x3_dispatch({.a = {.x = x, .w = w, .bias = bias, .y = y, .gap = gap_partial, .gap2 = gap_sq_partial, .H = h, .W = wdt, .cout = cout, .relu = relu,
+                                   .in_scale = in_scale, .in_shift = in_shift},
+                             .batch = batch, .cin = cin, .stride = stride, .precision = precision, .stream = stream});
 }
-namespace {
-int conv3x3_dispatch(const float* x, const float* w, const float* bias, const float* scale, const float* shift, const float* gate, const float* residual,
-                     float* y, float* gap_partial, float* gap_sq, int32_t batch, int32_t h, int32_t wdt, int32_t cin, int32_t cout, int32_t stride,
-                     int32_t relu, int32_t nchw_out, int32_t precision, void* stream, const float* in_scale, const float* in_shift, const uint32_t* res_bits,
-                     const ShortcutArgs* sc) {
-    EG_REQUIRE(x && w && y && batch > 0 && h > 0 && wdt > 0, EG_ERR_BAD_ARG, "eg_conv3x3: null pointer or empty shape");
-    EG_REQUIRE(!res_bits || (residual && !gate && ((size_t)batch * h * wdt * cout) % 32 == 0), EG_ERR_BAD_ARG,
-               "eg_conv3x3_res_masked: the bit mask needs a residual, no gate and a map of a multiple of 32 elements");
-    EG_REQUIRE((in_scale == nullptr) == (in_shift == nullptr) && (!in_scale || (precision != EG_PREC_F32 && cin % 32 == 0 && eg_aligned16(in_scale) &&
-               eg_aligned16(in_shift))), EG_ERR_BAD_ARG, "eg_conv3x3: the input affine needs both vectors, a split-bf16 mode and cin %% 32 == 0");
-    // gate + residual: relu(v * gate + residual) (the fused SE tail); residual alone: v + residual, no ReLU (the training path's fused fan-in add:
-    // an input gradient that lands on a tensor with a second consumer, train/functional.py conv3x3(passthrough=True))
-    EG_REQUIRE(!gate || residual, EG_ERR_BAD_ARG, "eg_conv3x3_se: a gate needs a residual");
-    EG_REQUIRE(!residual || (!nchw_out && stride == 1 && cout % 4 == 0 && (!gate || eg_aligned16(gate)) && eg_aligned16(residual) && residual != y),
-               EG_ERR_BAD_ARG, "eg_conv3x3_se: the fused residual needs NHWC output, stride 1, cout %% 4 == 0 and a residual buffer distinct from y");
-    EG_REQUIRE(eg_aligned16(x) && eg_aligned16(w) && eg_aligned16(y), EG_ERR_ALIGN, "eg_conv3x3: pointers must be 16-byte aligned");
-    EG_REQUIRE(stride == 1 || stride == 2, EG_ERR_UNSUPPORTED, "eg_conv3x3: stride %d", stride);
-    EG_REQUIRE(precision >= 0 && precision <= 2, EG_ERR_BAD_ARG, "eg_conv3x3: precision %d", precision);
-    EG_REQUIRE(nchw_out || (cout % 4 == 0), EG_ERR_UNSUPPORTED, "eg_conv3x3: NHWC output needs cout %% 4 == 0");
-    ConvArgs a;
-    a.x = x; a.w = w; a.bias = bias; a.scale = scale; a.shift = shift; a.y = y; a.gap = gap_partial; a.gap2 = gap_sq;
-    a.gate = gate; a.res = residual; a.relu2 = gate ? 1 : 0;
-    a.res_bits = res_bits;
-    a.in_scale = in_scale; a.in_shift = in_shift;
-    a.H = h; a.W = wdt; a.Ho = (h + 2 - 3) / stride + 1; a.Wo = (wdt + 2 - 3) / stride + 1;
-    a.cout = cout; a.relu = relu; a.nchw = nchw_out;
-    const int th = conv_tile_rows(cin, cout, stride);
-    a.tiles_x = eg_cdiv(a.Wo, 32);
-    a.tiles = a.tiles_x * eg_cdiv(a.Ho, th);
-    hipStream_t st = (hipStream_t)stream;
-    const int coutp = (int)eg_round_up(cout, 16);
-    EgProfScope prof((int64_t)cin * 1000000 + (int64_t)cout * 1000 + stride * 100 + 1,
-                     2.0 * 9 * cin * cout * (double)a.Ho * a.Wo * batch, st);
-    if (sc) {
-        EG_REQUIRE(precision != EG_PREC_F32 && stride == 1 && !nchw_out && cout == cin && (cin == 64 || cin == 128) && sc->cin * 2 == cin, EG_ERR_UNSUPPORTED,
-                   "conv3x3: the fused downsample shortcut serves 32 -> 64 and 64 -> 128 block entries in the split-bf16 modes (cin=%d cout=%d shortcut cin=%d)",
-                   cin, cout, sc->cin);
-        EG_REQUIRE(sc->x && sc->wimg && sc->vec && !gate && !residual && !bias && !relu && !gap_sq && !in_scale && sc->stride >= 1 &&
-                   (sc->h - 1) / sc->stride + 1 == h && (sc->w - 1) / sc->stride + 1 == wdt && eg_aligned16(sc->x) && eg_aligned16(sc->wimg) &&
-                   eg_aligned16(sc->vec), EG_ERR_BAD_ARG, "conv3x3: fused downsample shortcut: null / misaligned operand or a block input that does not map onto the output");
-        a.sc_x = sc->x; a.sc_vec = sc->vec; a.sc_H = sc->h; a.sc_W = sc->w; a.sc_S = sc->stride; a.sc_B = batch;
-        a.sc_whi = reinterpret_cast<const bf8*>(sc->wimg);
-        a.sc_wlo = a.sc_whi + (size_t)(sc->cin / 8) * cout;
-        a.scale = a.shift = nullptr;             // the epilogue's scale and shift are the per-clip q and h
-        a.relu2 = 1;
-        const int split = body_channel_split(batch, a.tiles, cin, cout, 1, precision, 0);
-        const bf8* whi = reinterpret_cast<const bf8*>(a.w + (size_t)9 * cin * cout);
-        const bf8* wlo = whi + (size_t)9 * (cin / 8) * cout;
-        if (cin == 64 && split == 2) return launch_conv_split_t<64, 2, 8, 4, 1, 3, 1>(a, batch, whi, wlo, st);
-        if (cin == 64) return launch_conv<64, 4, 1, 8, 4, 1, 1>(a, batch, precision, st);
-        if (split == 2) return launch_conv_split_t<128, 4, 4, 2, 2, 3, 2>(a, batch, whi, wlo, st);
-        if (split == 4) return launch_conv_split_t<128, 2, 4, 2, 2, 3, 2>(a, batch, whi, wlo, st);
-        return launch_conv<128, 8, 1, 4, 2, 2, 2>(a, batch, precision, st);
-    }
-    if (cin == 32 && coutp == 32 && cout == 32 && stride == 1 && precision != EG_PREC_F32 && !nchw_out && conv32_persistent_enabled())
-        return launch_conv32_persistent(a, batch, precision, th, st);
-    if (cin == 32 && coutp == 32 && stride == 1 && th == 4) return launch_conv<32, 2, 1, 4, 4, 1>(a, batch, precision, st);
-    if (cin == 32 && coutp == 32 && stride == 1) return launch_conv<32, 2, 1, 8, 4, 1>(a, batch, precision, st);
-    // the stage entries walk parity planes (conv_s2_form); the interleaved form serves fp32, NCHW output, padded channels and the A/B switch
-    const int s2p = (stride == 2 && cout == coutp && precision != EG_PREC_F32 && !nchw_out && (!gap_partial || eg_aligned16(gap_partial)) &&
-                     (!gap_sq || eg_aligned16(gap_sq))) ? conv_s2_form(cin, batch, a.Ho, a.Wo) : 0;
-    if (cin == 32 && coutp == 64 && stride == 2 && s2p == 8) return launch_conv_s2_planes<32, 4, 8, 4, 1>(a, batch, precision, st);
-    if (cin == 32 && coutp == 64 && stride == 2 && s2p == 4) return launch_conv_s2_planes<32, 4, 4, 2, 2>(a, batch, precision, st);
-    if (cin == 32 && coutp == 64 && stride == 2) return launch_conv<32, 4, 2, 2, 2, 2>(a, batch, precision, st);
-    if (const int split = body_channel_split(batch, a.tiles, cin, cout, stride, precision, nchw_out); split > 1) {
-        // few pixel tiles (small batches): spread the output channels over workgroups as well -- bitwise the unsplit kernels below
-        const size_t f32_floats = (size_t)9 * cin * cout;
-        const bf8* whi = reinterpret_cast<const bf8*>(a.w + f32_floats);
-        const bf8* wlo = whi + (size_t)9 * (cin / 8) * cout;
-        if (cin == 64 && split == 2) return launch_conv_split_t<64, 2, 8, 4, 1, 3>(a, batch, whi, wlo, st);
-        if (cin == 128 && split == 2) return launch_conv_split_t<128, 4, 4, 2, 2, 3>(a, batch, whi, wlo, st);
-        if (cin == 128 && split == 4) return launch_conv_split_t<128, 2, 4, 2, 2, 3>(a, batch, whi, wlo, st);
-    }
-    if (cin == 64 && coutp == 64 && stride == 1) return launch_conv<64, 4, 1, 8, 4, 1>(a, batch, precision, st);
-    if (cin == 64 && coutp == 128 && stride == 2 && s2p == 4) return launch_conv_s2_planes<64, 8, 4, 2, 2>(a, batch, precision, st);
-    if (cin == 64 && coutp == 128 && stride == 2) return launch_conv<64, 8, 2, 2, 2, 2>(a, batch, precision, st);
-    if (cin == 64 && coutp == 128 && stride == 1) return launch_conv<64, 8, 1, 4, 2, 2>(a, batch, precision, st);      // training: input gradient of final_conv1 (dy padded to 64 channels)
-    if (cin == 128 && coutp == 128 && stride == 1) return launch_conv<128, 8, 1, 4, 2, 2>(a, batch, precision, st);
-    // 256-channel stage of the audio emotion classifier (model/audio_emotion_classifer.py:20-22): 2-row tiles, waves split the channels
-    if (cin == 128 && coutp == 256 && stride == 2) return launch_conv<128, 16, 2, 2, 1, 4>(a, batch, precision, st);
-    if (cin == 256 && coutp == 256 && stride == 1) return launch_conv<256, 16, 1, 2, 1, 4>(a, batch, precision, st);
-    if (cin == 128 && coutp <= 64 && stride == 1) {       // final_conv1: 128 -> frames (34 -> 48, 60 -> 64)
-        if (coutp <= 48) return launch_conv<128, 3, 1, 4, 4, 1>(a, batch, precision, st);
-        return launch_conv<128, 4, 1, 4, 4, 1>(a, batch, precision, st);
-    }
-    // final_conv1 with 65..128 frames (BEAT-long, 120): the 128-wide body kernel on weights zero-padded to 128 channels
-    if (cin == 128 && coutp <= 128 && stride == 1) return launch_conv<128, 8, 1, 4, 2, 2>(a, batch, precision, st);
-    eg_set_error("eg_conv3x3: unsupported channels cin=%d cout=%d stride=%d", cin, cout, stride);
-    return EG_ERR_UNSUPPORTED;
-}
-}  // namespace
 
 // dx = F.conv2d's input gradient of nn.Conv2d(cin -> cout, k = 3, pad = 1, stride = 2) (the `_make_layer` entry convolutions, ResNetSE34V2.py:40-55):
 // dy [batch][ho][wo][cout], w_flip = the packed images of the rotated, transposed filter (cout -> cin: the image the stride-1 input gradients use),
@@ -1877,13 +1801,10 @@ extern "C" int eg_conv3x3_dgrad_s2(const float* dy, const float* w_flip, const f
     a.cout = cin; a.relu = 0; a.nchw = 0; a.tiles_x = eg_cdiv(a.W, 32); a.tiles = 0;
     a.res_q = res_q;
     hipStream_t st = (hipStream_t)stream;
-    const size_t f32_floats = (size_t)9 * cout * cin;                              // the flipped image: cout "input" channels -> cin "output" channels
-    const bf8* whi = reinterpret_cast<const bf8*>(w_flip + f32_floats);
-    const bf8* wlo = whi + (size_t)9 * (cout / 8) * cin;
     EgProfScope prof((int64_t)cin * 1000000 + (int64_t)cout * 1000 + 200 + 8, 2.0 * 9 * cin * cout * (double)a.H * a.W * batch, st);
-    if (cin == 32 && cout == 64) return launch_dgrad_s2_t<64, 2, 4, 4, 1>(a, batch, whi, wlo, st);
-    if (cin == 64 && cout == 128) return launch_dgrad_s2_t<128, 4, 2, 2, 2>(a, batch, whi, wlo, st);
-    if (cin == 128 && cout == 256) return launch_dgrad_s2_t<256, 8, 1, 1, 4>(a, batch, whi, wlo, st);
+    if (cin == 32 && cout == 64) return launch_dgrad_s2<64, 2, 4, 4, 1>(a, batch, st);
+    if (cin == 64 && cout == 128) return launch_dgrad_s2<128, 4, 2, 2, 2>(a, batch, st);
+    if (cin == 128 && cout == 256) return launch_dgrad_s2<256, 8, 1, 1, 4>(a, batch, st);
     eg_set_error("eg_conv3x3_dgrad_s2: unsupported channels %d -> %d", cin, cout);
     return EG_ERR_UNSUPPORTED;
 }
@@ -1949,8 +1870,8 @@ extern "C" int eg_se_block_fused(const float* x, const float* conv1_w, const flo
                                     ds_w ? ds_scale : nullptr, ds_w ? ds_shift : nullptr, ds_w ? sc_vec : nullptr)) return rc;
     if (!ds_w) return eg_conv3x3_se(t1, conv2_w, nullptr, scale2, shift2, gate, x, out, nullptr, batch, ho, wo, cout, cout, 1, 0, 0, precision, stream);
     const ShortcutArgs sc{x, ds_w, sc_vec, h, wdt, cin, stride};
-    return conv3x3_dispatch(t1, conv2_w, nullptr, nullptr, nullptr, nullptr, nullptr, out, nullptr, nullptr, batch, ho, wo, cout, cout, 1, 0, 0, precision, stream,
-                            nullptr, nullptr, nullptr, &sc);
+    return conv3x3_dispatch({.a = {.x = t1, .w = conv2_w, .y = out, .H = ho, .W = wo, .cout = cout},
+                             .batch = batch, .cin = cout, .stride = 1, .precision = precision, .stream = stream, .sc = &sc});
 }
 
 extern "C" int eg_se_residual_relu(const float* y, const float* gate, const float* x_in, const float* ds_w,

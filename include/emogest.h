@@ -898,7 +898,10 @@ int eg_take_distance(const float* feat, int32_t recordings, int32_t draws, int32
  *   y NHWC [B,Ho,Wo,Cout] or, if nchw_out, [B,Cout,Ho*Wo]
  *   gap_partial (optional) [B, eg_conv3x3_gap_tiles(...), Cout]: per-tile channel sums of y (for SE).
  * The stride-2 stage entries (32 -> 64, 64 -> 128, split-bf16 modes, NHWC) run on parity planes with 4- or 8-row tiles once the launch fills the
- * chip (EG_CONV_S2 = interleaved | planes | planes4 | planes8 forces a form); their partials stay one per 2 x 32 output block in either form. */
+ * chip (EG_CONV_S2 = interleaved | planes | planes4 | planes8 forces a form); their partials stay one per 2 x 32 output block in either form.
+ * Served (Cin, stride, Cout): (32, 1, 17..32) (32, 2, 49..64) (64, 1, 49..64) (64, 2, 113..128) (64, 1, 128) (128, 1, 1..128) (128, 2, 241..256)
+ * (256, 1, 256); anything else returns EG_ERR_UNSUPPORTED before a launch.  (64, 1, 113..127) and (256, 1, 241..255) launched until round 14, on a
+ * grid of 4- and 2-row tiles over partials that eg_conv3x3_gap_tiles counts in 8- and 4-row tiles: wrong results, now refused. */
 int eg_conv3x3(const float* x, const float* w, const float* bias, const float* scale, const float* shift,
                float* y, float* gap_partial, int32_t batch, int32_t h, int32_t wdt, int32_t cin, int32_t cout,
                int32_t stride, int32_t relu, int32_t nchw_out, int32_t precision, void* stream);

@@ -50,7 +50,7 @@ def test_conv3x3_epilogues(cin, cout, stride, H, W, nchw, prec):
         assert rel_l2(gap.sum(1).cpu().numpy(), ref.sum((2, 3)).numpy()) < max(TOL[prec], 1e-5)
 
 
-def test_conv3x3_rejects_bad_arguments():
+def test_conv3x3_rejects_bad_arguments(monkeypatch):
     from emotiongestures_amd import ops
     from emotiongestures_amd._lib import EgError
     x = torch.zeros(1, 8, 8, 48, device=dev())
@@ -60,6 +60,17 @@ def test_conv3x3_rejects_bad_arguments():
         ops.conv3x3(torch.zeros(1, 8, 8, 32), torch.zeros(32, 32, 3, 3))       # CPU tensor: no fallback
     with pytest.raises(EgError):
         ops.conv3x3(torch.zeros(1, 8, 8, 32, device=dev()), torch.zeros(32, 32, 3, 3), stride=3)
+    # 64 -> 128 at stride 1 has 4-row kernels, but eg_conv3x3_gap_tiles counts 113 .. 127 output channels in 8-row tiles: no route, no launch on a grid
+    # that disagrees with the caller's buffers (the same holds for 256 -> 241 .. 255)
+    with pytest.raises(EgError):
+        ops.conv3x3(torch.zeros(1, 8, 8, 64, device=dev()), torch.zeros(120, 64, 3, 3))
+    # the retired 8-row tiles of the 32 -> 32 kernel: a stale EG_CONV32_TH must not silently measure the default (read per call)
+    x32, w32 = torch.zeros(1, 8, 8, 32, device=dev()), torch.zeros(32, 32, 3, 3)
+    monkeypatch.setenv("EG_CONV32_TH", "8")
+    with pytest.raises(EgError):
+        ops.conv3x3(x32, w32, precision="bf16x3")
+    monkeypatch.setenv("EG_CONV32_TH", "4")
+    assert ops.conv3x3(x32, w32, precision="bf16x3").shape == (1, 8, 8, 32)
 
 
 def test_stem_conv():
