@@ -173,6 +173,7 @@ SIGNATURES = {
     "eg_se_gate_pre": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "eg_se_block_fused": (C.c_int, [_P] * 19 + [_I] * 7 + [_P]),
     "eg_conv3x3_gap_tiles": (_I, [_I, _I, _I, _I, _I]),
+    "eg_conv3x3_cout_pad": (_I, [_I, _I, _I]),
     "eg_conv3x3_channel_split": (_I, [_I, _I, _I, _I, _I, _I, _I]),
     "eg_stem_conv": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "eg_se_gate": (C.c_int, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P]),

@@ -1731,6 +1731,12 @@ extern "C" int32_t eg_conv3x3_gap_tiles(int32_t h, int32_t wdt, int32_t cin, int
     return eg_cdiv(ho, conv_tile_rows(cin, cout, stride)) * eg_cdiv(wo, 32);
 }
 
+// The row length of the packed images (and of bias / scale / shift) the route's kernels read: fixed by the route, not by cout.  0: no route serves the shape.
+extern "C" int32_t eg_conv3x3_cout_pad(int32_t cin, int32_t cout, int32_t stride) {
+    const int i = route_index(cin, cout, stride);
+    return i < NROUTES ? ROUTES[i].nt() * 16 : 0;
+}
+
 // The channel split eg_conv3x3 (and every entry point that shares its dispatch: _se, _sq, _sq_in_affine, _res_masked) takes for this launch.
 extern "C" int32_t eg_conv3x3_channel_split(int32_t batch, int32_t h, int32_t wdt, int32_t cin, int32_t cout, int32_t stride, int32_t precision) {
     return body_channel_split(batch, eg_conv3x3_gap_tiles(h, wdt, cin, cout, stride), cin, cout, stride, precision, 0);

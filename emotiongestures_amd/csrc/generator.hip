@@ -211,7 +211,10 @@ LinW add_linear(Layout& L, const std::string& prefix, int n, int k, bool bias, i
 }
 ConvW add_conv3(Layout& L, const std::string& key, int cin, int cout, int stride) {
     ConvW c;
-    c.cin = cin; c.cout = cout; c.coutp = (int)eg_round_up(cout, 16); c.stride = stride;
+    // the row length the route's kernels read (128 -> 1..48 on the 48-wide kernel, 128 -> 65..128 on the 128-wide one); an unserved shape keeps the
+    // 16-channel granule and is refused at its first launch
+    const int routed = eg_conv3x3_cout_pad(cin, cout, stride);
+    c.cin = cin; c.cout = cout; c.coutp = routed ? routed : (int)eg_round_up(cout, 16); c.stride = stride;
     c.w = L.add(key + ".weight", EG_PACK_CONV3X3, cout, cin, c.coutp, 0, (int64_t)9 * cin * c.coutp * 2);
     return c;
 }
@@ -800,13 +803,6 @@ extern "C" int eg_generator_create(const EgGeneratorConfig* cfg, EgGenerator** o
         }
     }
     g->final_conv = add_conv3(L, "audio_encoder.final_conv1", 128, F, 1);
-    if (g->final_conv.coutp > 64) {         // 65..128 frames run on the 128-wide kernel: pad the packed weights to 128 channels
-        g->final_conv.coutp = 128;
-        L.entries.back().dims[2] = 128;
-        L.total -= L.entries.back().numel;
-        L.entries.back().numel = (int64_t)9 * 128 * 128 * 2;
-        L.total += L.entries.back().numel;
-    }
     g->final_conv.bias = L.vec("audio_encoder.final_conv1.bias", F, g->final_conv.coutp);
     add_bn(L, "audio_encoder.bn1", F, g->final_conv.coutp, g->final_conv.scale, g->final_conv.shift);
     if (g->fold) {

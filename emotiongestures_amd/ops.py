@@ -36,9 +36,16 @@ def pack_linear_weight(w: torch.Tensor, device) -> torch.Tensor:
     return torch.from_numpy(packing._pack_linear(w.detach().cpu().float(), npad, kpad)).to(device), npad, kpad
 
 
-def pack_conv3x3_weight(w: torch.Tensor, device):
-    opad = (w.shape[0] + 15) // 16 * 16
-    if w.is_cuda and w.device == torch.device(device) and w.dtype == torch.float32 and w.shape[1] % 8 == 0:
+def conv3x3_cout_pad(cin: int, cout: int, stride: int = 1) -> int:
+    """Row length of the weight image and of bias / scale / shift that eg_conv3x3 reads at this shape (eg_conv3x3_cout_pad: the serving kernel's
+    padded width, e.g. 48 for 128 -> 20).  A shape no kernel serves keeps the 16-channel granule; its launch is refused."""
+    return int(L.load().eg_conv3x3_cout_pad(cin, cout, stride)) or (cout + 15) // 16 * 16
+
+
+def pack_conv3x3_weight(w: torch.Tensor, device, stride: int = 1):
+    opad = conv3x3_cout_pad(w.shape[1], w.shape[0], stride)
+    # the device packer builds rows of round_up(cout, 16); a wider route (128 -> 1..32, 128 -> 65..112) is packed on the host
+    if w.is_cuda and w.device == torch.device(device) and w.dtype == torch.float32 and w.shape[1] % 8 == 0 and opad == (w.shape[0] + 15) // 16 * 16:
         lib = L.load()
         wd = w.detach().contiguous()
         img = torch.empty(int(lib.eg_conv3x3_packed_floats(wd.shape[1], opad)), dtype=torch.float32, device=wd.device)
@@ -67,7 +74,7 @@ def conv3x3(x_nhwc, weight_oihw, bias=None, scale=None, shift=None, stride=1, re
     if packed is not None:
         wp, bias_p, scale_p, shift_p = packed
     else:
-        wp, bias_p, scale_p, shift_p = conv3x3_pack(weight_oihw, bias, scale, shift, dev)
+        wp, bias_p, scale_p, shift_p = conv3x3_pack(weight_oihw, bias, scale, shift, dev, stride)
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     y = torch.empty((B, Cout, Ho * Wo) if nchw_out else (B, Ho, Wo, Cout), device=dev)
     gap = None
@@ -79,9 +86,11 @@ def conv3x3(x_nhwc, weight_oihw, bias=None, scale=None, shift=None, stride=1, re
     return (y, gap) if want_gap else y
 
 
-def conv3x3_pack(weight_oihw, bias, scale, shift, device):
-    """Device-resident operands of conv3x3 (weight images + channel vectors padded to the packed channel count)."""
-    wp, opad = pack_conv3x3_weight(weight_oihw, device)
+def conv3x3_pack(weight_oihw, bias, scale, shift, device, stride=1):
+    """Device-resident operands of conv3x3 (weight images + channel vectors padded to the packed channel count of the route that serves
+    (cin, stride, cout); every stride-2 route is round_up(cout, 16) wide, which is also what the stride-1 query answers or falls back to for those channel
+    counts, so a caller that packs without naming the stride stays right)."""
+    wp, opad = pack_conv3x3_weight(weight_oihw, device, stride)
     return wp, _padvec(bias, opad, device), _padvec(scale, opad, device), _padvec(shift, opad, device)
 
 

@@ -621,7 +621,13 @@ def gap_planes(gap) -> int:
 # ---- conv3x3 forward, one helper per ConvRoute.forward: (xd, wd, b, stride, relu, planes, prec, aff) -> (y, gap) -------------------------------
 def _conv_operands(wd, b):
     """The packed filter image and the bias padded to the image's 16-channel granule."""
-    Co = wd.shape[0]
+    Co, Ci = wd.shape[:2]
+    # the device packer builds rows of round_up(Co, 16); a route that reads wider rows (eg_conv3x3_cout_pad: 128 -> 1..32 and 128 -> 65..112, i.e.
+    # final_conv1 at those frame counts) would read this image at the wrong row length, so the training path refuses it instead of launching
+    routed = int(L.load().eg_conv3x3_cout_pad(Ci, Co, 1))          # a host-side query, not a launch
+    if routed and routed != (Co + 15) // 16 * 16:
+        raise L.EgError(f"conv3x3 (training): {Ci} -> {Co} runs on a kernel that reads weight rows of {routed} channels, the training path packs rows of "
+                        f"{(Co + 15) // 16 * 16}; supported output-channel counts at {Ci} inputs are those with round_up(Co, 16) == {routed}")
     wp, bp = _pack_conv(wd), None
     if b is not None:
         bp = torch.zeros((Co + 15) // 16 * 16, dtype=torch.float32, device=wd.device)

@@ -895,6 +895,9 @@ int eg_take_distance(const float* feat, int32_t recordings, int32_t draws, int32
 /* nn.Conv2d 3x3 pad 1 (Full_model/ResNetBlocks.py:12,14; ResNetSE34V2.py:21) on NHWC fp32 with the
  * fused epilogue  v = acc + bias[c]; if relu: v = max(v,0); v = v*scale[c] + shift[c].
  *   x [B,H,W,Cin]   w EG_PACK_CONV3X3   bias/scale/shift [Cout_pad] (NULL = 0/1/0)
+ *   Cout_pad = eg_conv3x3_cout_pad(Cin, Cout, stride): the padded width of the kernel that serves the shape, NOT round_up(Cout, 16) -- 128 -> 1..48
+ *   reads rows of 48 and 128 -> 65..128 rows of 128.  The weight image is packed at that row length (zero columns past Cout) and all three vectors
+ *   have that many readable elements.
  *   y NHWC [B,Ho,Wo,Cout] or, if nchw_out, [B,Cout,Ho*Wo]
  *   gap_partial (optional) [B, eg_conv3x3_gap_tiles(...), Cout]: per-tile channel sums of y (for SE).
  * The stride-2 stage entries (32 -> 64, 64 -> 128, split-bf16 modes, NHWC) run on parity planes with 4- or 8-row tiles once the launch fills the
@@ -906,6 +909,8 @@ int eg_conv3x3(const float* x, const float* w, const float* bias, const float* s
                float* y, float* gap_partial, int32_t batch, int32_t h, int32_t wdt, int32_t cin, int32_t cout,
                int32_t stride, int32_t relu, int32_t nchw_out, int32_t precision, void* stream);
 int32_t eg_conv3x3_gap_tiles(int32_t h, int32_t wdt, int32_t cin, int32_t cout, int32_t stride);
+/* Cout_pad of eg_conv3x3 and of every entry point that shares its dispatch: a multiple of 16, >= cout; 0 where no kernel serves (cin, stride, cout). */
+int32_t eg_conv3x3_cout_pad(int32_t cin, int32_t cout, int32_t stride);
 /* The output-channel split (1, 2 or 4 workgroups per pixel tile) the NHWC convolution takes at this shape and precision: the split kernels
  * serve the bf16x3 stride-1 64 -> 64 and 128 -> 128 bodies while there are few pixel tiles (EG_CONV_SPLIT forces 1, 2 or 4). */
 int32_t eg_conv3x3_channel_split(int32_t batch, int32_t h, int32_t wdt, int32_t cin, int32_t cout, int32_t stride, int32_t precision);
@@ -1251,7 +1256,8 @@ int eg_conv3x3_wgrad_gather_mfma(const float* x, const float* dy, float* dw_mat,
 /* Device-side build of the weight image eg_conv3x3 reads (eg_conv3x3_packed_floats(cin', round_up(cout',16)) floats: fp32 image, then the
  * bf16 hi / lo images), for weights that change every step.  flip_transpose = 0: conv weight [cout][cin][3][3] as in the state_dict
  * (cin' = cin, cout' = cout).  flip_transpose = 1: the filter of the input-gradient convolution, w'[ci][co][kh][kw] = w[co][ci][2-kh][2-kw]
- * (cin' = cout, cout' = cin) -- F.conv2d's dgrad for stride 1 is eg_conv3x3 of dy with that image. */
+ * (cin' = cout, cout' = cin) -- F.conv2d's dgrad for stride 1 is eg_conv3x3 of dy with that image.  The rows are round_up(cout', 16) wide: the image
+ * serves eg_conv3x3 only where eg_conv3x3_cout_pad(cin', cout', stride) is that width (not 128 -> 1..32 and 128 -> 65..112). */
 int eg_pack_conv3x3_device(const float* w_oihw, int32_t cout, int32_t cin, int32_t flip_transpose, float* image, void* stream);
 /* Device-side build of the weight image eg_linear's split-bf16 modes read (EG_PACK_LINEAR layout; eg_linear_packed_floats(n, k) floats,
  * ldw = k rounded up to 64) from w [n][k] fp32 with row stride ld.  transpose != 0: the image of w^T (w is then [k][n]): dX = dY W. */

@@ -100,6 +100,26 @@ def test_generator_matches_oracle_same_inputs(prec):
         assert clip_rel_l2(a.cpu().numpy(), b.numpy()) < tol * (5 if name == "emotion_prediction" else 1), name
 
 
+@pytest.mark.parametrize("frames,prec", [(20, "f32"), (20, "bf16x3")])
+def test_generator_matches_oracle_at_a_frame_count_inside_a_padded_conv_width(frames, prec):
+    """final_conv1 is 128 -> frames: 20 frames run on the 48-wide kernel, so the engine packs the weights and the three channel vectors at
+    eg_conv3x3_cout_pad (48), not at round_up(frames, 16) = 32 (B = 2, same oracle and tolerances as above)."""
+    from oracle import emogest_oracle as O
+    model = build_mirror("spatial", frames, 126, 4, 4, seed=13, precision=prec)
+    sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    inp = synth_inputs(2, frames=frames, seed=13)
+    t = {k: torch.from_numpy(v) for k, v in inp.items()}
+    with torch.no_grad():
+        ref = O.generator_forward(sd, O.GenCfg(frames=frames), t["spec"], t["text"], t["pre_pose"], t["sampled"])
+    model.to(dev())
+    with torch.no_grad():
+        got = model(t["spec"].to(dev()), t["text"].to(dev()), t["pre_pose"].to(dev()), t["sampled"].to(dev()))
+    tol = POSE_TOL[prec]
+    assert tuple(got[0].shape) == (2, frames, 126)
+    for name, a, b in zip(("pose", "emotion_feature", "semantic_feature", "emotion_prediction", "text_embedding"), got, ref):
+        assert clip_rel_l2(a.cpu().numpy(), b.numpy()) < tol * (5 if name == "emotion_prediction" else 1), name
+
+
 def test_batch_invariance_and_repeatability():
     """Clips are independent in the spatial variant: clip i of a batch equals clip i alone; two runs
     of the same batch are bitwise identical (no atomics anywhere on the path)."""

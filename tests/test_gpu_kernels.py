@@ -26,6 +26,9 @@ def T(key, shape, lo=-1.0, hi=1.0, seed=0):
 CONV_CASES = [   # cin, cout, stride, H, W, nchw
     (32, 32, 1, 24, 40, False), (32, 64, 2, 24, 44, False), (64, 64, 1, 16, 62, False), (64, 128, 2, 18, 62, False),
     (128, 128, 1, 12, 31, False), (128, 34, 1, 8, 31, True), (128, 60, 1, 8, 20, True), (32, 32, 1, 128, 124, False),
+    # output-channel counts strictly inside a route's padded width, and the routes no case above launches (tests/test_gpu_conv3x3_f64.py holds them per element)
+    (128, 20, 1, 8, 31, True), (128, 100, 1, 8, 20, False), (32, 20, 1, 9, 33, False), (64, 128, 1, 9, 33, False), (128, 256, 2, 10, 66, False),
+    (256, 256, 1, 5, 33, False),
 ]
 
 
