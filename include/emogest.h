@@ -1022,13 +1022,9 @@ typedef struct EgLinearArgs {
     const float* gate_src;          /* [M, ldg] or NULL */
     const int32_t* drop_epoch;      /* device-resident step counter or NULL (eg_dropout_dev) */
     float* partial;                 /* split-K scratch or NULL */
-    const void* x_images;           /* NULL, or X as bf16 (hi, lo) tile-planar images of width k_x (eg_split_tiles layout; then x is ignored): the
-                                       pre-split product of eg_linear_presplit with this epilogue */
-    void* y_images;                 /* NULL, or a second output: Y as images of width y_k for the next product (written beside y) */
     uint64_t drop_offset;
     int32_t lda, ldw, ldr, ldc, ldg;
     int32_t m, n, k, relu, precision, splits;
-    int32_t k_x, y_k;
     uint32_t drop_seed;
     float drop_p;
 } EgLinearArgs;
@@ -1293,8 +1289,7 @@ int eg_layernorm_backward(const float* x, const float* dy, const float* gamma, f
 int64_t eg_layernorm_backward_ex_workspace_floats(int32_t rows, int32_t d);
 int eg_layernorm_backward_ex(const float* x, const float* dy, const float* gamma, float* dx, float* dx_dropped, float* dgamma, float* dbeta,
                              int32_t rows, int32_t d, float eps, float drop_p, uint32_t drop_seed, uint64_t drop_offset, const int32_t* epoch_dev,
-                             float* workspace, void* branch_images, void* stream);      /* branch_images (may be NULL): the gradient that enters the
-                             Dropout'ed branch (dx_dropped, or dx when drop_p == 0) also as bf16 (hi, lo) images for a pre-split input-gradient product */
+                             float* workspace, void* stream);
 /* Training pair on the fp32 matrix pipe (v_mfma_f32_16x16x4_f32) with nn.Dropout(p) on the probabilities (Modules.py:21) from the counter-based
  * mask of eg_dropout (counter = offset + linear index of (clip, head, query, key); epoch_dev as in eg_dropout_dev, may be NULL).  The forward stores
  * the UNMASKED probabilities in `attn` [batch, heads, lq, lk]; the backward recomputes the mask from the same (p, seed, offset, epoch).  The backward

@@ -31,6 +31,35 @@ def test_library_exports_every_header_symbol():
     assert lib.eg_version().startswith(b"emogest-hip")
 
 
+def test_linear_args_struct_matches_the_header():
+    """_lib.EgLinearArgs against `typedef struct EgLinearArgs` of include/emogest.h: the same field names in declaration order, the same width per
+    field, and ctypes' size equal to the size the header's list gives when every field sits at its natural alignment."""
+    from emotiongestures_amd import _lib
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "emogest.h")).read(), flags=re.S)
+    body = re.search(r"typedef\s+struct\s+EgLinearArgs\s*\{(.*?)\}\s*EgLinearArgs\s*;", text, flags=re.S).group(1)
+    widths = {"uint64_t": 8, "int32_t": 4, "uint32_t": 4, "float": 4}
+    header = []                                                     # (name, bytes, kind) in declaration order
+    for decl in (d.strip() for d in body.split(";")):
+        if not decl:
+            continue
+        m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\*?)\s*(.+)", decl, flags=re.S)
+        base, star, names = m.group(1), m.group(2), m.group(3)
+        for name in (n.strip() for n in names.split(",")):
+            if star or name.startswith("*"):
+                header.append((name.lstrip("* "), C.sizeof(C.c_void_p), "pointer"))
+            else:
+                header.append((name, widths[base], base))
+    assert len(header) > 20
+    kinds = {C.c_void_p: "pointer", C.c_uint64: "uint64_t", C.c_int32: "int32_t", C.c_uint32: "uint32_t", C.c_float: "float"}
+    bound = [(n, C.sizeof(t), kinds[t]) for n, t in _lib.EgLinearArgs._fields_]
+    assert bound == header
+    size = align = 0
+    for _n, w, _k in header:
+        size = (size + w - 1) // w * w + w
+        align = max(align, w)
+    assert C.sizeof(_lib.EgLinearArgs) == (size + align - 1) // align * align
+
+
 def test_manifest_covers_the_state_dict_and_packs_to_declared_sizes():
     """Every parameter that influences the eval forward appears in the manifest; packing fills exactly numel floats."""
     from emotiongestures_amd import packing

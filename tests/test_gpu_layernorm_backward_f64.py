@@ -119,7 +119,7 @@ def ex_case(rows, d, rw, cls, p):
     sbuf = torch.full((need + GUARD,), SENTINEL, dtype=torch.int32, device=dev())
     xd, dyd, gd = x.to(dev()), dy.to(dev()), g.to(dev())
     L.check(lib.eg_layernorm_backward_ex(_ptr(xd), _ptr(dyd), _ptr(gd), _ptr(dx), _ptr(dxm) if p > 0 else None, _ptr(dg), _ptr(db),
-                                         rows, d, G.LNB_EPS, p, G.LNB_SEED, G.LNB_OFFSET, None, _ptr(sbuf), None, st), what)
+                                         rows, d, G.LNB_EPS, p, G.LNB_SEED, G.LNB_OFFSET, None, _ptr(sbuf), st), what)
     torch.cuda.synchronize()
     assert bool((sbuf[need:] == SENTINEL).all()), f"{what}: a store behind the {need} workspace floats"
     assert bool(torch.isfinite(sbuf[:need].view(torch.float32)).all()), f"{what}: a partial was not written"
@@ -151,7 +151,7 @@ def test_layernorm_backward_ex_refusals_leave_the_outputs_untouched():
     ws = torch.full((4 * 1088 + GUARD,), SENTINEL, dtype=torch.int32, device=dev())
 
     def call(d=64, p=0.0, dropped=None):
-        return lib.eg_layernorm_backward_ex(_ptr(x), _ptr(x), _ptr(g), _ptr(dx), dropped, _ptr(dg), _ptr(db), rows, d, G.LNB_EPS, p, 1, 0, None, _ptr(ws), None, st)
+        return lib.eg_layernorm_backward_ex(_ptr(x), _ptr(x), _ptr(g), _ptr(dx), dropped, _ptr(dg), _ptr(db), rows, d, G.LNB_EPS, p, 1, 0, None, _ptr(ws), st)
 
     for what, rc, want in (("D = 96", call(d=96), UNSUPPORTED), ("D = 1088", call(d=1088), UNSUPPORTED), ("p > 0, dx_dropped = NULL", call(p=0.2), BAD_ARG),
                            ("p = 0 with dx_dropped", call(dropped=_ptr(dxm)), BAD_ARG)):

@@ -2291,20 +2291,6 @@ def test_linear_ex_epilogue_masks_match_the_separate_kernels(precision):
             both = F.raw_linear(x, w, b, gate=gate, drop=site, res=res, relu=True)
             assert torch.equal(both, torch.relu(torch.where(gate > 0, want_d, torch.zeros_like(plain)) + res))
             assert float((want_d == 0).float().mean()) > 0.1
-            if precision == "bf16x3" and K % 64 == 0 and N % 64 == 0:
-                # the pre-split product (X through images, both operands by LDS-DMA) with the same epilogue, and Y leaving as images for the next one
-                ximg = F.new_images(M, K, DEV)
-                L.check(L.load().eg_split_tiles(_ptr(x), K, M, K, _ptr(ximg), _stream(DEV)), "eg_split_tiles")
-                got_p, yimg = F.raw_linear(x, w, b, gate=gate, drop=site, res=res, relu=True, x_img=ximg, want_img=True)
-                # bitwise the fp32-input kernel's result unless that one took its split-K path (another summation order over K)
-                assert torch.equal(got_p, both) if K < 1024 else rel(got_p, both) < 1e-6
-                want_y = torch.zeros_like(yimg)
-                L.check(L.load().eg_split_tiles(_ptr(got_p), N, M, N, _ptr(want_y), _stream(DEV)), "eg_split_tiles")
-                mt = (M + 63) // 64
-                a16, b16 = yimg.view(torch.int16).view(2, mt, N // 8, 64, 8), want_y.view(torch.int16).view(2, mt, N // 8, 64, 8)
-                for t in range(mt):
-                    r = min(64, M - t * 64)
-                    assert torch.equal(a16[:, t, :, :r], b16[:, t, :, :r])
 
 
 @pytest.mark.parametrize("rows,D,p", [(68, 512, 0.0), (544, 512, 0.1), (4352, 512, 0.1), (130, 128, 0.2), (70, 1024, 0.0)])
@@ -2318,7 +2304,7 @@ def test_layernorm_backward_ex_matches_torch_and_the_dropout_kernel(rows, D, p):
     TF.layer_norm(xr, (D,), gr, br, 1e-6).backward(dy.double())
     gp, bp = torch.nn.Parameter(g.clone().to(DEV)), torch.nn.Parameter(torch.zeros(D, device=DEV))
     site = (p, 5, 8192, None) if p > 0 else None
-    dpre, dbr, dg, db, _img = F._ln_backward_ex(x.to(DEV), dy.to(DEV), gp.detach(), 1e-6, site, gp, bp)
+    dpre, dbr, dg, db = F._ln_backward_ex(x.to(DEV), dy.to(DEV), gp.detach(), 1e-6, site, gp, bp)
     assert rel(dpre, xr.grad) < 2e-6 and rel(dg, gr.grad) < 2e-6 and rel(db, br.grad) < 2e-6
     if p > 0:
         want = torch.empty_like(dpre)
@@ -2328,20 +2314,6 @@ def test_layernorm_backward_ex_matches_torch_and_the_dropout_kernel(rows, D, p):
         assert dbr is dpre
     again = F._ln_backward_ex(x.to(DEV), dy.to(DEV), gp.detach(), 1e-6, site, gp, bp)
     assert all(torch.equal(a, b) for a, b in zip(again[:4], (dpre, dbr, dg, db)))          # fixed-order partial sums: bitwise reproducible
-    # the branch gradient as pre-split images (for the input-gradient product that follows in large-batch steps): the split eg_split_tiles makes of it
-    with F.precision("bf16x3"):
-        old, F.PRESPLIT_ROWS = F.PRESPLIT_ROWS, 1
-        try:
-            img = F._ln_backward_ex(x.to(DEV), dy.to(DEV), gp.detach(), 1e-6, site, gp, bp, want_img=True)[4]
-        finally:
-            F.PRESPLIT_ROWS = old
-    want_img = torch.zeros_like(img)
-    L.check(L.load().eg_split_tiles(_ptr(dbr), D, rows, D, _ptr(want_img), _stream(DEV)), "eg_split_tiles")
-    mt, n_valid = (rows + 63) // 64, None
-    a16, b16 = img.view(torch.int16).view(2, mt, D // 8, 64, 8), want_img.view(torch.int16).view(2, mt, D // 8, 64, 8)
-    for t in range(mt):                 # rows past the end of the last tile are not written by the LayerNorm kernel (never read as results)
-        r = min(64, rows - t * 64)
-        assert torch.equal(a16[:, t, :, :r], b16[:, t, :, :r])
 
 
 class _ReluSites:
@@ -2388,9 +2360,8 @@ class _ReluSites:
         return out
 
 
-@pytest.mark.parametrize("precision,flat,dropout,chain", [("f32", False, False, False), ("f32", True, True, False), ("bf16x3", True, True, False),
-                                                          ("bf16x3", True, False, False), ("bf16x3", True, True, True)])
-def test_fused_blocks_step_equals_the_operator_by_operator_step(precision, flat, dropout, chain):
+@pytest.mark.parametrize("precision,flat,dropout", [("f32", False, False), ("f32", True, True), ("bf16x3", True, True), ("bf16x3", True, False)])
+def test_fused_blocks_step_equals_the_operator_by_operator_step(precision, flat, dropout):
     """The fused transformer blocks (one autograd node per MultiHeadAttention / FFN / Linear chain: Q|K|V and K|V as one product, Dropout + residual
     and the ReLU backward in GEMM epilogues, LayerNorm backward with both gradients and the affine sums) against the operator-by-operator
     composition they replace, on the whole generator + CVAE step: same loss, same gradient for every parameter.  With Dropout on, both draw the
@@ -2407,10 +2378,7 @@ def test_fused_blocks_step_equals_the_operator_by_operator_step(precision, flat,
     from emotiongestures_amd.train import functional as F
     from emotiongestures_amd.train import nets
     from emotiongestures_amd.train.optim import flatten_parameters
-    # chain: force the large-batch mode of the fused blocks at this small size -- activations handed from block to block as pre-split images (the
-    # producing LayerNorm / GEMM epilogue writes them, the consuming product reads them by LDS-DMA: functional.presplit_ok)
     B = 3
-    old_rows = F.PRESPLIT_ROWS
     target = T("tgt", (B, 34, 126), -0.5, 0.5).to(DEV)
 
     def run(seed):
@@ -2419,7 +2387,6 @@ def test_fused_blocks_step_equals_the_operator_by_operator_step(precision, flat,
         label = g["label"].argmax(1)
         eps = g["z"]
         out = []
-        F.PRESPLIT_ROWS = 64 if chain else 1 << 30
         try:
             for fused in (False, True):
                 F.FUSE_BLOCKS = fused
@@ -2452,7 +2419,6 @@ def test_fused_blocks_step_equals_the_operator_by_operator_step(precision, flat,
                     assert all(w.grad.data_ptr() == w._eg_slot.data_ptr() for w in (a.w_qs.weight, a.w_ks.weight, a.w_vs.weight)) or not fused
         finally:
             F.FUSE_BLOCKS = True
-            F.PRESPLIT_ROWS = old_rows
             F.reset_state()
         return out
 

@@ -1,4 +1,4 @@
-"""Print gradient norms / a checksum of a few parameters for the fused (chain) and the operator-by-operator training step (the A/B of
+"""Print gradient norms / a checksum of a few parameters for the fused and the operator-by-operator training step (the A/B of
 tests/test_gpu_training.py::test_fused_blocks_step_equals_the_operator_by_operator_step) -- for comparing two builds of the library."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,7 +13,6 @@ DEV = "cuda:0"
 def T(key, shape, lo=-1.0, hi=1.0, seed=0):
     n = int(np.prod(shape)); return torch.from_numpy((lo + (hi - lo) * hash_unit(key, n, seed)).astype(np.float32).reshape(shape))
 B = 3
-F.PRESPLIT_ROWS = int(os.environ.get("ROWS", "64"))
 inp = synth_inputs(B, 34, 126, 4, seed=31)
 g = {k: torch.from_numpy(v).to(DEV) for k, v in inp.items()}
 target = T("tgt", (B, 34, 126), -0.5, 0.5).to(DEV); label = g["label"].argmax(1); eps = g["z"]
@@ -49,7 +48,7 @@ for fused in (False, True):
     gr = {n: p.grad.detach().double().cpu() for n, p in both.named_parameters() if p.grad is not None}
     print("fused" if fused else "unfused", "loss %.9f" % float(loss.detach()), "pose sum %.9f" % float(pose.detach().double().sum()))
     for k in keys: print("   %-55s norm %.12e  sum %.12e" % (k, float(gr[k].norm()), float(gr[k].sum())))
-    F.unregister_weight_images(fp.images); F.reset_state(); F.PRESPLIT_ROWS = int(os.environ.get("ROWS", "64"))
+    F.unregister_weight_images(fp.images); F.reset_state()
 
 a, b = MASKS[False], MASKS[True]
 print("relu sites", len(a), len(b))

@@ -155,3 +155,51 @@ def test_presplit128_64_deep_steps_bitwise_equal(prec, M, N, K, monkeypatch):
     ref = torch.relu(x.double() @ w.double().T + bias.double() + res.double())
     assert rel_l2(outs["128"].cpu().numpy(), ref.numpy()) < {"bf16x3": 3e-5, "bf16": 2e-2}[prec]
     assert torch.equal(outs["128k64"], outs["128"])
+
+
+# ---- round 15: the training image chain (activations and gradients handed from product to product as pre-split bf16 (hi, lo) images:
+# functional.PRESPLIT_ROWS / presplit_ok / new_images / raw_linear(x_img=, want_img=) / _ln_backward_ex(want_img=), EgLinearArgs::x_images / y_images /
+# k_x / y_k, eg_layernorm_backward_ex's branch_images).  From tests/test_gpu_training.py, whose T, DEV and rel they use; they need the files of the
+# parent commit named in README.md ----
+
+def linear_ex_presplit_tail(F, L, _ptr, _stream, precision, M, K, N, x, w, b, gate, site, res, both):
+    """The end of the shape loop of test_linear_ex_epilogue_masks_match_the_separate_kernels: the pre-split product with the training epilogue
+    (gemm_presplit_kernel<3, true>, gemm_presplit128_kernel<3, true>, gemm_skinny_kernel<1..4, false, true>) against the fp32-input kernel."""
+    if precision == "bf16x3" and K % 64 == 0 and N % 64 == 0:
+        # the pre-split product (X through images, both operands by LDS-DMA) with the same epilogue, and Y leaving as images for the next one
+        ximg = F.new_images(M, K, DEV)
+        L.check(L.load().eg_split_tiles(_ptr(x), K, M, K, _ptr(ximg), _stream(DEV)), "eg_split_tiles")
+        got_p, yimg = F.raw_linear(x, w, b, gate=gate, drop=site, res=res, relu=True, x_img=ximg, want_img=True)
+        # bitwise the fp32-input kernel's result unless that one took its split-K path (another summation order over K)
+        assert torch.equal(got_p, both) if K < 1024 else rel(got_p, both) < 1e-6
+        want_y = torch.zeros_like(yimg)
+        L.check(L.load().eg_split_tiles(_ptr(got_p), N, M, N, _ptr(want_y), _stream(DEV)), "eg_split_tiles")
+        mt = (M + 63) // 64
+        a16, b16 = yimg.view(torch.int16).view(2, mt, N // 8, 64, 8), want_y.view(torch.int16).view(2, mt, N // 8, 64, 8)
+        for t in range(mt):
+            r = min(64, M - t * 64)
+            assert torch.equal(a16[:, t, :, :r], b16[:, t, :, :r])
+
+
+def layernorm_backward_ex_image_tail(F, L, _ptr, _stream, x, dy, gp, bp, site, dbr, rows, D):
+    """The end of test_layernorm_backward_ex_matches_torch_and_the_dropout_kernel: ln_bwd_ex_kernel's image store against eg_split_tiles of dbr."""
+    # the branch gradient as pre-split images (for the input-gradient product that follows in large-batch steps): the split eg_split_tiles makes of it
+    with F.precision("bf16x3"):
+        old, F.PRESPLIT_ROWS = F.PRESPLIT_ROWS, 1
+        try:
+            img = F._ln_backward_ex(x.to(DEV), dy.to(DEV), gp.detach(), 1e-6, site, gp, bp, want_img=True)[4]
+        finally:
+            F.PRESPLIT_ROWS = old
+    want_img = torch.zeros_like(img)
+    L.check(L.load().eg_split_tiles(_ptr(dbr), D, rows, D, _ptr(want_img), _stream(DEV)), "eg_split_tiles")
+    mt, n_valid = (rows + 63) // 64, None
+    a16, b16 = img.view(torch.int16).view(2, mt, D // 8, 64, 8), want_img.view(torch.int16).view(2, mt, D // 8, 64, 8)
+    for t in range(mt):                 # rows past the end of the last tile are not written by the LayerNorm kernel (never read as results)
+        r = min(64, rows - t * 64)
+        assert torch.equal(a16[:, t, :, :r], b16[:, t, :, :r])
+
+
+# test_fused_blocks_step_equals_the_operator_by_operator_step had a fifth parameter `chain` and the row ("bf16x3", True, True, True); inside run(seed):
+#         F.PRESPLIT_ROWS = 64 if chain else 1 << 30        (before the `try`)
+#             F.PRESPLIT_ROWS = old_rows                     (in the `finally`, old_rows read before run was defined)
+# i.e. the large-batch mode forced at 102 rows: activations handed from block to block as images, checked like the four rows that remain.
