@@ -65,6 +65,7 @@ EG_ARTICULATE_BASIS_ROWS, EG_ARTICULATE_BASIS_COLUMNS = 0, 1
 EG_UNWRAP_TILE_FRAMES = 64
 EG_SMOOTH_MAX_WINDOW, EG_SMOOTH_TILE_FRAMES, EG_SMOOTH_TILE_COLS = 31, 64, 64
 EG_KIN_MAX_JOINTS, EG_KIN_MAX_BINS, EG_KIN_TILE_FRAMES = 64, 256, 64
+EG_JOINTSCORE_TILE_FRAMES, EG_SRGR_MAX_JOINTS, EG_L1DIV_MAX_COLS = 32, 64, 512
 
 # name -> (restype, argtypes).  Must list every symbol include/emogest.h declares
 # (tests/test_abi.py cross-checks this table against the header).
@@ -154,6 +155,11 @@ SIGNATURES = {
     "eg_kin_edges2": (C.c_int, [_P, _I, C.c_double, _P]),
     "eg_kin_workspace_bytes": (_L, [_I, _I, _I, _I]),
     "eg_kin_stats": (C.c_int, [_P, _I, _I, _I, _P, _P, _I, _I, C.c_double, _P, _I, _P, _L, _P, _P, _P]),
+    "eg_jointscore_tile_frames": (_I, []),
+    "eg_srgr_workspace_bytes": (_L, [_I, _I, _I]),
+    "eg_srgr_tracks": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, C.c_double, C.c_double, _P, _L, _P, _P, _P, _P]),
+    "eg_l1div_workspace_bytes": (_L, [_I, _I, _I]),
+    "eg_l1div_tracks": (C.c_int, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P]),
     "eg_beat_tables": (C.c_int, [_P, _P, _P, _P]),
     "eg_beat_workspace_bytes": (_L, [_I, _I]),
     "eg_beat_align": (C.c_int, [_P, _I, _I, _P, _I, _I, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P]),

@@ -369,11 +369,17 @@ class alignment(object):
         return avg_dis_all_b2a
 
 
+def _refuse_joint_score(what):
+    raise BeatScoreUnavailable(f"model.Beat_score_v2.{what}: not part of the eval loop and not built in this module; the joint-space scores "
+                               f"of whole tracks are emotiongestures_amd.jointscore.{what} (run / avg as upstream, CUDA tensors through the "
+                               "kernel)")
+
+
 class L1div(object):
     def __init__(self, *a, **k):
-        _refuse("L1div")
+        _refuse_joint_score("L1div")
 
 
 class SRGR(object):
     def __init__(self, *a, **k):
-        _refuse("SRGR")
+        _refuse_joint_score("SRGR")

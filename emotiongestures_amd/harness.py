@@ -465,7 +465,7 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
                want_windows: bool = False, want_aux: bool = False, mel=None, lengths=None, draws: Optional[int] = None,
                beat: bool = False, diversity=None, audio_rate: Optional[int] = None, joints=None, joints_mean=None,
                joints_unit: bool = False, joints_fps=None, rotations=None, rotations_space: str = "local", smooth=None, euler=None,
-               euler_unwrap: bool = False, kinematics=None) -> Dict[str, torch.Tensor]:
+               euler_unwrap: bool = False, kinematics=None, srgr=None, l1div: bool = False) -> Dict[str, torch.Tensor]:
     """One gesture track per utterance from raw 16 kHz audio: windows -> mel -> optional CVAE sample per window -> roll-out.
 
     ``models = (generator, vae | None)``, eval mode, on the GPU.  ``audio [U, total_samples]``; ``text [U, W, 60]`` (the words of every
@@ -541,11 +541,23 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     device.  ``rate`` is the output rate: ``joints_fps[1]`` when given, else ``fps``.  With ``smooth=`` the figures describe the smoothed
     joints, because that is what ``out["joints"]`` holds; the raw figure is
     ``kinematics_of_joints(skeleton.joints_from_tracks(out["track"], skeleton, frames, joints_mean, joints_unit, joints_fps)[0], rate,
-    out["joint_frames"])``.  Works with ``lengths`` and ``draws``; without ``kinematics`` no key and no launch changes."""
+    out["joint_frames"])``.  Works with ``lengths`` and ``draws``; without ``kinematics`` no key and no launch changes.
+
+    ``srgr=SemanticTargets(joints, semantic, threshold)`` (``jointscore.SemanticTargets``; with ``joints=``, without it refused by name): the
+    target joints ``[U, T', J, 3]`` and semantic weights ``[U, T']`` of the recordings at the output rate, made from the captured tracks by
+    ``skeleton.joints_from_tracks`` / ``joints_from_rot6d`` with this call's ``joints_mean`` / ``joints_unit`` / ``joints_fps``.  Adds
+    ``"srgr"``: ``jointscore.srgr_of_joints(out["joints"], targets, semantic, out["joint_frames"], threshold)`` -- ``"srgr"``, ``"recall"``
+    ``[U, (R,)]`` float64, ``"hits"`` ``[U, (R,) J]`` int32, ``"frames"`` --, two launches; with ``draws`` the R takes of a recording share its
+    target.  Targets whose U, T' or J do not fit are refused by name before anything runs (T' once the generator's geometry is known).
+    ``l1div=True`` (with ``joints=``): adds ``"l1div"``, ``jointscore.l1div_of_tracks(out["joints"].flatten(-2), out["joint_frames"])`` --
+    ``"l1div"``, ``"l1_sum"`` ``[U, (R,)]`` and ``"mean"`` ``[U, (R,) 3J]`` float64, in metres --, four launches.  Both describe the smoothed
+    joints with ``smooth=`` and work with ``lengths`` and ``draws``; without them no key and no launch changes."""
     outputs = _track_outputs("synthesize", seed_pose, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, euler, euler_unwrap)
     kinematics = _kinematics_arg("synthesize", kinematics, outputs, joints_fps, fps)
+    srgr, l1div = _jointscore_args("synthesize", srgr, l1div, outputs, audio)
     return _synthesize("synthesize", models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate,
-                       want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=False, kinematics=kinematics)
+                       want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=False, kinematics=kinematics,
+                       srgr=srgr, l1div=l1div)
 
 
 def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch.Tensor, labels: Optional[torch.Tensor] = None, *,
@@ -554,7 +566,7 @@ def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose:
                      want_windows: bool = False, want_aux: bool = False, mel=None, beat: bool = False, diversity=None,
                      audio_rate: Optional[int] = None, joints=None, joints_mean=None, joints_unit: bool = False, joints_fps=None,
                      rotations=None, rotations_space: str = "local", smooth=None, euler=None,
-                     euler_unwrap: bool = False, kinematics=None) -> Dict[str, torch.Tensor]:
+                     euler_unwrap: bool = False, kinematics=None, srgr=None, l1div: bool = False) -> Dict[str, torch.Tensor]:
     """``draws`` = R sampled takes for each of U recordings of any and unequal length, from raw audio, in one call: ``synthesize(lengths=)`` and
     ``synthesize(draws=)`` combined (a VAE is required).  ``audio [U, max_total]`` with ``lengths[u]`` real samples in row u (``None``: every
     row at full length); recording u has ``W_u = ceil(lengths[u] / hop_samples)`` windows, N = sum W_u.  ``text`` padded ``[U, Wmax, 60]`` or
@@ -565,11 +577,14 @@ def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose:
     zero past ``track_frames[u]``) plus packed ``"spec"`` and ``"windows_per"``.  Every other option is ``synthesize``'s, applied per take with
     recording u's own samples and poses: ``beat`` -> ``"beat"`` ``[U, R]``; ``diversity`` (R >= 2) -> ``"take_distance"`` ``[U, R, R]`` and
     ``"take_diversity"`` ``[U]``; ``joints`` -> ``[U, R, T', J, 3]``; ``rotations`` -> ``[U, R, T', K, 4]``; ``audio_rate``; ``smooth`` ->
-    ``"track_smooth"`` ``[U, R, T, pose_dim]``; ``kinematics`` (with ``joints``) -> ``"kinematics"``, the figures ``[U, R, J]`` per take."""
+    ``"track_smooth"`` ``[U, R, T, pose_dim]``; ``kinematics`` (with ``joints``) -> ``"kinematics"``, the figures ``[U, R, J]`` per take; ``srgr``
+    and ``l1div`` (with ``joints``) -> ``"srgr"`` and ``"l1div"``, the figures ``[U, R]`` per take (the takes of a recording share its target)."""
     outputs = _track_outputs("synthesize_takes", seed_pose, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, euler, euler_unwrap)
     kinematics = _kinematics_arg("synthesize_takes", kinematics, outputs, joints_fps, fps)
+    srgr, l1div = _jointscore_args("synthesize_takes", srgr, l1div, outputs, audio)
     return _synthesize("synthesize_takes", models, audio, text, seed_pose, labels, hop_samples, n_samples, None, z, alpha, fps, sample_rate,
-                       want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=True, kinematics=kinematics)
+                       want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=True, kinematics=kinematics,
+                       srgr=srgr, l1div=l1div)
 
 
 def _kinematics_arg(who, kinematics, outputs, joints_fps, fps):
@@ -582,6 +597,24 @@ def _kinematics_arg(who, kinematics, outputs, joints_fps, fps):
     return KN.SpeedBins.of(kinematics, f"{who}: kinematics", fps if joints_fps is None else joints_fps[1])
 
 
+def _jointscore_args(who, srgr, l1div, outputs, audio):
+    """The ``srgr=`` and ``l1div=`` arguments of `synthesize` / `synthesize_takes`, checked before anything runs: the SemanticTargets (or None)
+    against the recordings and the body's joints, and the flag."""
+    if srgr is None and not l1div:
+        return None, False
+    for name, given in (("srgr", srgr is not None), ("l1div", bool(l1div))):
+        if given and outputs is None:
+            raise L.EgError(f"{who}: {name}= without joints= (the score is that of out[\"joints\"], in metres)")
+    if l1div is not True and l1div:
+        raise L.EgError(f"{who}: l1div= takes True, got {type(l1div).__name__}")
+    if srgr is not None:
+        from .jointscore import SemanticTargets
+        if not isinstance(srgr, SemanticTargets):
+            raise L.EgError(f"{who}: srgr= takes a jointscore.SemanticTargets, got {type(srgr).__name__}")
+        srgr.fit(who, U=int(audio.shape[0]) if audio.dim() == 2 else None, J=outputs.body.J)
+    return srgr, bool(l1div)
+
+
 def _track_outputs(who, seed_pose, *args):
     """The output stage of `synthesize` / `synthesize_takes` (skeleton.TrackOutputs, or None): their arguments, checked before anything else."""
     from . import skeleton as SK
@@ -591,7 +624,7 @@ def _track_outputs(who, seed_pose, *args):
 
 
 def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate, want_windows, want_aux,
-                mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes, kinematics=None):
+                mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes, kinematics=None, srgr=None, l1div=False):
     """The body of `synthesize` and `synthesize_takes` (`who` names the caller in errors): argument checks, resampling, the roll-out of the
     call's kind, then the per-track extras.  `outputs`: the caller's checked output stage (`_track_outputs`)."""
     gen, vae = models
@@ -628,6 +661,15 @@ def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samp
         from . import resample as RS
         if lengths is not None:
             lengths = int_list(lengths)
+    if srgr is not None:                                                                  # the targets' T' against the track this call will make
+        from .skeleton import out_frames
+        hop = int(round((c.frames - c.prior_frames) * sample_rate / fps)) if hop_samples is None else int(hop_samples)      # _front_end's
+        at_model_rate = (lambda v: RS.out_length(v, int(audio_rate), int(sample_rate))) if resampled else int
+        most = max(-(-at_model_rate(v) // hop) for v in int_list(lengths)) if lengths is not None else (
+            int(text.shape[1]) if windows is None and text.dim() == 3 else windows)
+        if most is not None and most >= 1:
+            srgr.fit(who, T=out_frames(most * (c.frames - c.prior_frames) + c.prior_frames, outputs.fps))
+    if resampled:
         with torch.no_grad():
             audio = RS.resample_audio(audio, int(audio_rate), int(sample_rate), lengths=lengths)
         if lengths is not None:
@@ -672,6 +714,14 @@ def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samp
         from . import kinematics as KN
         with torch.no_grad():
             out["kinematics"] = KN.kinematics_of_joints(out["joints"], kinematics.fps, frames=out["joint_frames"], edges=kinematics)
+    if srgr is not None or l1div:                                                         # of out["joints"] too
+        from . import jointscore as JS
+        with torch.no_grad():
+            if srgr is not None:
+                there = lambda v: None if v is None else torch.as_tensor(v).to(out["joints"].device)
+                out["srgr"] = JS.srgr_of_joints(out["joints"], there(srgr.joints), there(srgr.semantic), out["joint_frames"], srgr.threshold)
+            if l1div:
+                out["l1div"] = JS.l1div_of_tracks(out["joints"].flatten(-2), out["joint_frames"])
     return out
 
 

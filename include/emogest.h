@@ -771,6 +771,59 @@ int eg_kin_stats(const float* joints, int32_t rows, int32_t T, int32_t J, const 
                  int32_t* hist, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Joint-space scores of whole tracks: SRGR (semantic-relevant gesture recall) and L1 diversity, model/Beat_score_v2.py SRGR / L1div
+ * (csrc/jointscore.hip)
+ * ------------------------------------------------------------------------------------------ */
+/* Rows as in eg_kin_stats: row b has n = clamp(d_frames[b / draws] * frame_unit, 0, T) valid frames (d_frames NULL: T); frames t >= n may
+ * hold NaN and are never read.  A row's result depends on its own data and n only -- not on rows, on its place in the batch or on T.  A
+ * recording with n < 1 is refused by name from `frames`, the HOST copy of the counts (int32 [rows / draws]; NULL exactly when d_frames is
+ * NULL); with a device count of 0 although the host count is not, that row's outputs are zeros and every access stays in range.
+ *
+ * SRGR.  results r [rows, T, J, 3] fp32; targets g [rows / draws, T, J, 3] fp32, one per recording, shared by its `draws` takes; semantic
+ * weights w [rows / draws, T] fp32 (NULL: every weight 1); threshold and scale fp64 (the reference's normaliser is scale = 1 / 0.165, formed
+ * on the host).
+ *     d[t, j] = (|rx - gx| + |ry - gy|) + |rz - gz|    each difference one IEEE fp32 subtraction, the absolute values widened to fp64, the two
+ *                                                      fp64 additions in that order (no product: nothing to contract)
+ *     hit[t, j] = d[t, j] < threshold                  a value equal to the threshold is a miss, and so is a NaN
+ *     hits[b, j] = sum_t hit[t, j]                     int32, exact
+ *     c[t] = sum_j hit[t, j];   weighted[b] = sum_t double(w[t]) * c[t]     every product exact (24 x 7 bits); the sum in fp64: the frames of a
+ *                                                      tile of EG_JOINTSCORE_TILE_FRAMES in ascending order from 0, then the row's tiles in
+ *                                                      ascending order -- an order that depends on n and the tile size only
+ *     srgr[b] = weighted[b] * scale / (n * J);   recall[b] = (sum_j hits[b, j]) / (n * J)         fp64
+ * Error of srgr against the exact sum: the first-order bound of a fixed-order fp64 sum of n terms, (n + 8) * 2^-53 * sum_t |w[t]| c[t] *
+ * scale / (n J) (the scale, the division and the reference sum's own rounding are the 8).
+ * eg_srgr_tracks: two launches on `stream` -- the tiles, the finalise --; no allocation, no synchronisation, no memset and no atomics: a
+ * workgroup owns one tile of one row and stores its partials (one fp64 and J int32) to the workspace, and the finalise adds a row's own
+ * ceil(n / tile) tiles.  The grids depend on (rows, T, J, draws) only, so the call captures into a hipGraph; the takes of a recording are
+ * neighbours in the grid (they read one target tile).  workspace: eg_srgr_workspace_bytes (0 for refused arguments).
+ *
+ * L1 diversity.  x [rows, T, D] fp32, any column layout (joints as J*3 columns, a 126- or 282-column track, Euler channels), never written.
+ *     mean[b, c] = (sum_t double(x[t, c])) / n;   l1_sum[b] = sum_t sum_c |double(x[t, c]) - mean[b, c]|;   l1div[b] = l1_sum[b] / n
+ * Both sums in fp64 in a fixed order that depends on n, D and the kernel's tile constants only (runs of frames of a tile ascending, the runs
+ * of a tile ascending, the columns by a fixed tree, the tiles ascending).  Against the exact values (S = sum |x - m|, A = sum |x| over the
+ * row, m the exact mean): |mean - m| <= (n + 8) * 2^-53 * sum_t |x[t, c]| / n per column, and
+ *     |l1_sum - S| <= 2^-53 * ((n D + 8) * S + 2 (n + 8) * A)
+ * -- the first-order bound of any fixed summation order of n D terms plus the mean's error carried through n frames.
+ * eg_l1div_tracks: four launches on `stream` -- column sums, means, deviations, finalise --; otherwise as eg_srgr_tracks.  workspace:
+ * eg_l1div_workspace_bytes, the [rows, tiles, D] and [rows, tiles] fp64 tile sums.
+ *
+ * Both refuse by name before the first launch: null pointers (semantic may be NULL), results / targets / x / workspace not 16-byte aligned,
+ * fp64 outputs not 8-byte and int32 arrays not 4-byte aligned, rows < 1, T < 1, J outside 1..EG_SRGR_MAX_JOINTS, D outside
+ * 1..EG_L1DIV_MAX_COLS, rows not a multiple of draws, frame_unit < 1, a threshold or scale that is not finite, a host count below 1, a
+ * short workspace, grid / index range. */
+#define EG_JOINTSCORE_TILE_FRAMES 32
+#define EG_SRGR_MAX_JOINTS 64
+#define EG_L1DIV_MAX_COLS 512
+int32_t eg_jointscore_tile_frames(void);
+int64_t eg_srgr_workspace_bytes(int32_t rows, int32_t T, int32_t J);
+int eg_srgr_tracks(const float* results, const float* targets, const float* semantic, int32_t rows, int32_t T, int32_t J,
+                   const int32_t* frames, const int32_t* d_frames, int32_t draws, int32_t frame_unit, double threshold, double scale,
+                   void* workspace, int64_t workspace_bytes, double* srgr, double* recall, int32_t* hits, void* stream);
+int64_t eg_l1div_workspace_bytes(int32_t rows, int32_t T, int32_t D);
+int eg_l1div_tracks(const float* x, int32_t rows, int32_t T, int32_t D, const int32_t* frames, const int32_t* d_frames, int32_t draws,
+                    int32_t frame_unit, void* workspace, int64_t workspace_bytes, double* mean, double* l1_sum, double* l1div, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Beat-alignment score = model/Beat_score_v2.py alignment(sigma, order): load_audio + load_pose +
  * calculate_align for a batch of clips (test_emotion_gesture_diversity_iterative.py:241-248)
  * ------------------------------------------------------------------------------------------ */

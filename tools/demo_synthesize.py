@@ -30,6 +30,10 @@ With --kinematics (and --joints, TED shape) the call also returns the motion sta
 speed, acceleration and jerk per joint and a histogram of the joint speeds, one read of the joints on the device), and the script prints the
 mean speed and jerk of the two wrists -- with --smooth also those of the raw joints and the Hellinger distance between the raw and the smoothed
 speed histograms.
+With --srgr and / or --l1div (and --joints, TED shape) the call also returns the joint-space scores of the BEAT table per recording
+(jointscore.srgr_of_joints: two more launches; jointscore.l1div_of_tracks on the joints as 129 columns: four more).  There is no captured
+motion here, so the stand-in target of --srgr is the joints of the same track smoothed with a (9, 3) Savitzky-Golay filter and the semantic
+weights are 1 on every third second: the script prints the recall at 2 cm, the weighted rate and the L1 diversity in metres.
 With --beat --joints the body is a skeleton.JointTree -- the BEAT columns are one 6-D rotation per joint -- read from the HIERARCHY block of
 --bvh FILE (which must have 47 joints, or name them with --bvh-joints A,B,...), or a synthetic 47-joint upper body without --bvh: joint
 positions and, with --rotations, one local rotation per joint come from ONE more launch (skeleton.launch_articulate), and the script prints their
@@ -37,7 +41,7 @@ shapes, how far the deepest joint travels and the largest rotation angle.
 With --bvh FILE --bvh-out DIR the call also returns the Euler channels of every joint in the file's own channel orders (euler=BvhFile,
 euler_unwrap=True: one more launch and the Euler filter's three) and the script writes DIR/recording_U[_take_R].bvh -- the file's HIERARCHY,
 then the generated MOTION at the joints' frame rate -- one file per recording and take, formatted on the host (bvh.BvhFile.write).
-usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--bvh FILE [--bvh-joints A,B,...] [--bvh-out DIR]] [--joints-fps N] [--rotations]] [--smooth K P] [--kinematics] [--out tracks.npz]"""
+usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--bvh FILE [--bvh-joints A,B,...] [--bvh-out DIR]] [--joints-fps N] [--rotations]] [--smooth K P] [--kinematics] [--srgr] [--l1div] [--out tracks.npz]"""
 import os
 import sys
 import time
@@ -53,7 +57,7 @@ from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
 from emotiongestures_amd.synth import load_synth_weights, synth_audio
 
 argv, DRAWS, OUT, BEAT, DIVERSITY, RATE, JOINTS, JOINTS_FPS, ROTATIONS, SMOOTH = [], 0, None, False, False, 16000, False, None, False, None
-BVH, BVH_JOINTS, BVH_OUT, KINEMATICS = None, None, None, False
+BVH, BVH_JOINTS, BVH_OUT, KINEMATICS, SRGR, L1DIV = None, None, None, False, False, False
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--draws":
@@ -82,6 +86,10 @@ for a in it:
         SMOOTH = (int(next(it)), int(next(it)))
     elif a == "--kinematics":
         KINEMATICS = True
+    elif a == "--srgr":
+        SRGR = True
+    elif a == "--l1div":
+        L1DIV = True
     else:
         argv.append(a)
 if DIVERSITY and DRAWS < 2:
@@ -96,6 +104,10 @@ if ROTATIONS and not JOINTS:
     sys.exit("--rotations needs --joints (the rest pose belongs to the skeleton's bones)")
 if KINEMATICS and (not JOINTS or BEAT):
     sys.exit("--kinematics needs --joints without --beat (the statistics are those of the joints, in metres; the script names the TED wrists)")
+if (SRGR or L1DIV) and (not JOINTS or BEAT):
+    sys.exit("--srgr / --l1div need --joints without --beat (the scores are those of the joints, in metres)")
+if SRGR and SMOOTH:
+    sys.exit("--srgr without --smooth: the smoothed track's joints are the stand-in target the raw joints are scored against")
 U = int(argv[0]) if len(argv) > 0 else 4
 seconds = float(argv[1]) if len(argv) > 1 else 60.0
 dev = torch.device("cuda:0")
@@ -183,6 +195,12 @@ elif JOINTS:
               kinematics=True if KINEMATICS else None)
     if ROTATIONS:                                        # the rest pose: the first generated frame of recording 0 (normalised by the call)
         jk["rotations"] = track[0, PRIOR].reshape(-1, 3).cpu()
+    if SRGR:                                             # the stand-in target: the joints of the smoothed track; weights 1 on every third second
+        from emotiongestures_amd.jointscore import SemanticTargets
+        tj = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, **dict(jk, smooth=(9, 3), kinematics=None), **AR)["joints"]
+        sem = ((torch.arange(tj.shape[1], device=dev) // (JOINTS_FPS or FPS)) % 3 == 0).float()[None].expand(U, -1).contiguous()
+        jk["srgr"] = SemanticTargets(tj, sem, threshold=0.02)
+    jk["l1div"] = L1DIV
     H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, **jk, **AR)          # warm-up (uploads the bone table)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -215,6 +233,15 @@ elif JOINTS:
             print(f"--kinematics --smooth: the raw joints: mean wrist speed {wrists(raw_k, 'speed')} m/s, mean wrist jerk {wrists(raw_k, 'jerk')} m/s^3; "
                   f"Hellinger distance between the raw and the smoothed speed histograms, all joints pooled, per recording: "
                   f"{[round(float(v), 4) for v in KM.hellinger(full(raw_k), full(kin), pool=True).cpu()]}")
+    if SRGR:
+        sr = jo["srgr"]
+        print(f"--srgr: the raw joints against those of the (9, 3)-smoothed track, two more launches: recall at 2 cm per recording "
+              f"{[round(float(v), 4) for v in sr['recall'].cpu()]}, rate weighted by every third second (scale 1 / 0.165) "
+              f"{[round(float(v), 4) for v in sr['srgr'].cpu()]}; the joint hit least often: {int(sr['hits'].sum(0).argmin())}")
+    if L1DIV:
+        l1 = jo["l1div"]
+        print(f"--l1div: L1 diversity of the joints as {l1['mean'].shape[-1]} columns, four more launches: "
+              f"{[round(float(v), 4) for v in l1['l1div'].cpu()]} m summed over the columns, per frame")
     if ROTATIONS:
         rot = jo["rotations"]
         swing = lambda k: float(torch.rad2deg(2 * torch.acos(rot[:, :, k, 0].clamp(max=1.0))).max())    # bone 4 / 21: left / right forearm
