@@ -465,7 +465,8 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
                want_windows: bool = False, want_aux: bool = False, mel=None, lengths=None, draws: Optional[int] = None,
                beat: bool = False, diversity=None, audio_rate: Optional[int] = None, joints=None, joints_mean=None,
                joints_unit: bool = False, joints_fps=None, rotations=None, rotations_space: str = "local", smooth=None, euler=None,
-               euler_unwrap: bool = False, kinematics=None, srgr=None, l1div: bool = False) -> Dict[str, torch.Tensor]:
+               euler_unwrap: bool = False, kinematics=None, srgr=None, l1div: bool = False, emotion=None,
+               emotion_stride: Optional[int] = None) -> Dict[str, torch.Tensor]:
     """One gesture track per utterance from raw 16 kHz audio: windows -> mel -> optional CVAE sample per window -> roll-out.
 
     ``models = (generator, vae | None)``, eval mode, on the GPU.  ``audio [U, total_samples]``; ``text [U, W, 60]`` (the words of every
@@ -551,13 +552,23 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     target.  Targets whose U, T' or J do not fit are refused by name before anything runs (T' once the generator's geometry is known).
     ``l1div=True`` (with ``joints=``): adds ``"l1div"``, ``jointscore.l1div_of_tracks(out["joints"].flatten(-2), out["joint_frames"])`` --
     ``"l1div"``, ``"l1_sum"`` ``[U, (R,)]`` and ``"mean"`` ``[U, (R,) 3J]`` float64, in metres --, four launches.  Both describe the smoothed
-    joints with ``smooth=`` and work with ``lengths`` and ``draws``; without them no key and no launch changes."""
+    joints with ``smooth=`` and work with ``lengths`` and ``draws``; without them no key and no launch changes.
+
+    ``emotion=classifier`` (an eval-mode ``SkeletonTransformer`` whose ``pose_dim`` is the generator's; ``emotion_stride``: the stride of its
+    windows, default its ``n_position``): adds ``"emotion"``, ``emotion.emotion_of_tracks(classifier, out["track"], frames, labels,
+    emotion_stride)`` with recording u's own valid poses -- which emotion the classifier recognises in every take (``"pred"``, ``"votes"``,
+    ``"mean_logit"`` ``[U, R, ...]``, R = 1 without ``draws``) and, with a VAE and ``labels``, how often it is the one the take was asked for
+    (``"hit"``, ``"accuracy"``, ``"confusion"``, ...).  The raw track is scored, also with ``smooth=``: it measures the model.  The labels
+    are the call's own, one per take: ``[U, 8]``, or ``[U, W, 8]`` / ``[U, R, W, 8]`` / the packed forms when constant along a take's
+    windows.  Labels that change along a take are refused by name before anything runs (one label per take is what is scored; the pieces
+    can be scored with ``emotion_of_tracks``), and so are a classifier of another ``pose_dim`` or in train mode.  Works with ``lengths``,
+    ``draws`` and ``audio_rate``; without ``emotion`` no key and no launch changes."""
     outputs = _track_outputs("synthesize", seed_pose, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, euler, euler_unwrap)
     kinematics = _kinematics_arg("synthesize", kinematics, outputs, joints_fps, fps)
     srgr, l1div = _jointscore_args("synthesize", srgr, l1div, outputs, audio)
     return _synthesize("synthesize", models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate,
                        want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=False, kinematics=kinematics,
-                       srgr=srgr, l1div=l1div)
+                       srgr=srgr, l1div=l1div, emotion=emotion, emotion_stride=emotion_stride)
 
 
 def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch.Tensor, labels: Optional[torch.Tensor] = None, *,
@@ -566,7 +577,8 @@ def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose:
                      want_windows: bool = False, want_aux: bool = False, mel=None, beat: bool = False, diversity=None,
                      audio_rate: Optional[int] = None, joints=None, joints_mean=None, joints_unit: bool = False, joints_fps=None,
                      rotations=None, rotations_space: str = "local", smooth=None, euler=None,
-                     euler_unwrap: bool = False, kinematics=None, srgr=None, l1div: bool = False) -> Dict[str, torch.Tensor]:
+                     euler_unwrap: bool = False, kinematics=None, srgr=None, l1div: bool = False, emotion=None,
+                     emotion_stride: Optional[int] = None) -> Dict[str, torch.Tensor]:
     """``draws`` = R sampled takes for each of U recordings of any and unequal length, from raw audio, in one call: ``synthesize(lengths=)`` and
     ``synthesize(draws=)`` combined (a VAE is required).  ``audio [U, max_total]`` with ``lengths[u]`` real samples in row u (``None``: every
     row at full length); recording u has ``W_u = ceil(lengths[u] / hop_samples)`` windows, N = sum W_u.  ``text`` padded ``[U, Wmax, 60]`` or
@@ -578,13 +590,14 @@ def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose:
     recording u's own samples and poses: ``beat`` -> ``"beat"`` ``[U, R]``; ``diversity`` (R >= 2) -> ``"take_distance"`` ``[U, R, R]`` and
     ``"take_diversity"`` ``[U]``; ``joints`` -> ``[U, R, T', J, 3]``; ``rotations`` -> ``[U, R, T', K, 4]``; ``audio_rate``; ``smooth`` ->
     ``"track_smooth"`` ``[U, R, T, pose_dim]``; ``kinematics`` (with ``joints``) -> ``"kinematics"``, the figures ``[U, R, J]`` per take; ``srgr``
-    and ``l1div`` (with ``joints``) -> ``"srgr"`` and ``"l1div"``, the figures ``[U, R]`` per take (the takes of a recording share its target)."""
+    and ``l1div`` (with ``joints``) -> ``"srgr"`` and ``"l1div"``, the figures ``[U, R]`` per take (the takes of a recording share its target);
+    ``emotion`` -> ``"emotion"``, the recognised emotion of every take against the label it was asked for (``[U, R]`` per take)."""
     outputs = _track_outputs("synthesize_takes", seed_pose, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, euler, euler_unwrap)
     kinematics = _kinematics_arg("synthesize_takes", kinematics, outputs, joints_fps, fps)
     srgr, l1div = _jointscore_args("synthesize_takes", srgr, l1div, outputs, audio)
     return _synthesize("synthesize_takes", models, audio, text, seed_pose, labels, hop_samples, n_samples, None, z, alpha, fps, sample_rate,
                        want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=True, kinematics=kinematics,
-                       srgr=srgr, l1div=l1div)
+                       srgr=srgr, l1div=l1div, emotion=emotion, emotion_stride=emotion_stride)
 
 
 def _kinematics_arg(who, kinematics, outputs, joints_fps, fps):
@@ -615,6 +628,64 @@ def _jointscore_args(who, srgr, l1div, outputs, audio):
     return srgr, bool(l1div)
 
 
+def _emotion_arg(who, emotion, stride, gen, vae, audio, text, seed_pose, labels, hop_samples, windows, fps, sample_rate, lengths, draws,
+                 audio_rate, takes):
+    """The ``emotion=`` argument of `synthesize` / `synthesize_takes`, checked before anything runs: the classifier against the generator's
+    poses, and the call's own ``labels`` reduced to one class index per take -- int64 numpy ``[U, R]`` (R = 1 without draws), or None without
+    a VAE or labels.  Labels that change along a take's windows are refused by name: one label per take is what is scored."""
+    from . import emotion as EM
+    _F, _dm, D, _C = EM._geometry(emotion, f"{who}: emotion=")
+    if D != seed_pose.shape[-1]:
+        raise L.EgError(f"{who}: emotion=: the classifier takes pose_dim={D}, the generator's poses have {seed_pose.shape[-1]} columns")
+    if emotion.training:
+        raise L.EgError(f"{who}: emotion=: the classifier is not in eval mode (call .eval())")
+    if stride is not None and int(stride) < 1:
+        raise L.EgError(f"{who}: emotion_stride={stride} (None or >= 1)")
+    if vae is None or labels is None:
+        return None
+    if audio.dim() != 2:
+        raise L.EgError(f"audio shape {tuple(audio.shape)} != (U, total_samples)")
+    U, R = int(audio.shape[0]), 1 if draws is None else int(draws)
+    cfg = gen._origin()._cfg
+    if takes and lengths is None:
+        lengths = [int(audio.shape[1])] * U
+    if lengths is not None:                                                               # the windows of recording u, as the roll-out counts them
+        hop = int(round((cfg["frames"] - cfg["prior_frames"]) * sample_rate / fps)) if hop_samples is None else int(hop_samples)
+        at_model_rate = int
+        if audio_rate is not None and int(audio_rate) != int(sample_rate):
+            from . import resample as RS
+            at_model_rate = lambda v: RS.out_length(v, int(audio_rate), int(sample_rate))
+        wp = [max(1, -(-at_model_rate(v) // hop)) for v in int_list(lengths)]
+    else:
+        W = int(text.shape[1]) if windows is None and text.dim() == 3 else windows
+        wp = [1 if W is None else max(1, int(W))] * U
+    if len(wp) != U:
+        raise L.EgError(f"{who}: lengths has {len(wp)} entries for {U} recordings")
+    lab = np.asarray(labels.detach().cpu().numpy() if isinstance(labels, torch.Tensor) else labels)
+    Wmax, N, K = max(wp), sum(wp), lab.shape[-1] if lab.ndim else 0
+    off = np.concatenate([[0], np.cumsum(wp)[:-1]])
+    shape = tuple(lab.shape)
+    if lab.ndim == 2 and shape[0] == U:                                                   # one label per recording (U == N * R: the same rows)
+        rows = lambda u, r: lab[u][None]
+    elif lab.ndim == 3 and shape[0] == U and shape[1] >= Wmax:
+        rows = lambda u, r: lab[u, :wp[u]]
+    elif lab.ndim == 4 and shape[:2] == (U, R) and shape[2] >= Wmax:
+        rows = lambda u, r: lab[u, r, :wp[u]]
+    elif lab.ndim == 2 and shape[0] == N * R:                                             # packed: window w of take r of recording u at R*off[u] + r*W_u + w
+        rows = lambda u, r: lab[R * off[u] + r * wp[u]: R * off[u] + (r + 1) * wp[u]]
+    else:
+        raise L.EgError(f"{who}: emotion=: labels shape {shape}: need ({U},K), ({U},W,K), ({U},{R},W,K) or packed ({N * R},K) one-hot rows")
+    idx = np.zeros((U, R), np.int64)
+    for u in range(U):
+        for r in range(R):
+            w = rows(u, r)
+            if (w != w[:1]).any():
+                raise L.EgError(f"{who}: emotion=: the labels of recording {u}, take {r} change along its windows; one label per take is what "
+                                "is scored -- score the pieces with emotion.emotion_of_tracks")
+            idx[u, r] = int(np.argmax(w[0]))
+    return idx
+
+
 def _track_outputs(who, seed_pose, *args):
     """The output stage of `synthesize` / `synthesize_takes` (skeleton.TrackOutputs, or None): their arguments, checked before anything else."""
     from . import skeleton as SK
@@ -624,7 +695,8 @@ def _track_outputs(who, seed_pose, *args):
 
 
 def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate, want_windows, want_aux,
-                mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes, kinematics=None, srgr=None, l1div=False):
+                mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes, kinematics=None, srgr=None, l1div=False, emotion=None,
+                emotion_stride=None):
     """The body of `synthesize` and `synthesize_takes` (`who` names the caller in errors): argument checks, resampling, the roll-out of the
     call's kind, then the per-track extras.  `outputs`: the caller's checked output stage (`_track_outputs`)."""
     gen, vae = models
@@ -635,6 +707,9 @@ def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samp
             raise L.EgError(f"{who}: smooth=: deriv={smooth.deriv}: a velocity track is not a pose track; call smooth.smooth_tracks on "
                             "out[\"track\"] for derivatives")
     _eval_only(gen)
+    if emotion is not None:                                                               # the classifier and one label per take, before anything runs
+        emotion_labels = _emotion_arg(who, emotion, emotion_stride, gen, vae, audio, text, seed_pose, labels, hop_samples, windows, fps,
+                                      sample_rate, lengths, draws, audio_rate, takes)
     if beat and seed_pose.shape[-1] < 174:
         raise L.EgError(f"{who}: beat=True: pose_dim={seed_pose.shape[-1]}: the beat joints are columns 18:42 and 150:174 (needs >= 174)")
     if draws is not None:
@@ -703,6 +778,9 @@ def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samp
         with torch.no_grad():
             td = take_diversity(diversity, out["track"], frames=frames if takes else None, span=c.frames)
         out["take_distance"], out["take_diversity"] = td["distance"], td["diversity"]
+    if emotion is not None:                                                               # of the raw track too: it measures the model
+        from . import emotion as EM
+        out["emotion"] = EM.emotion_of_tracks(emotion, out["track"], frames, emotion_labels, emotion_stride)
     poses = out["track"]
     if smooth is not None:                                                                # beat and diversity above score the raw track
         with torch.no_grad():

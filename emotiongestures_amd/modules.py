@@ -409,14 +409,20 @@ class MultiHeadAttention(nn.Module):
         self.dropout_p = float(dropout)              # SubLayers.py:26
         self.precision = _DEFAULT_PRECISION
 
+    def packed(self, device):
+        """The four packed weight images (w_qs, w_ks, w_vs, fc) on `device`: packed once per weight version (standalone use)."""
+        ws = (self.w_qs.weight, self.w_ks.weight, self.w_vs.weight, self.fc.weight)
+        ver = (str(device),) + tuple(w._version for w in ws)
+        if getattr(self, "_pack", None) is None or self._pack[0] != ver:
+            self._pack = (ver, [ops.pack_linear_weight(w, device)[0] for w in ws])
+        return self._pack[1]
+
     def forward(self, q, k, v, mask=None):
         _eval_only(self)
         if k is not v and not torch.equal(k, v):
             raise NotImplementedError("HIP MultiHeadAttention: k is v, as on the reference path")
         ws = (self.w_qs.weight, self.w_ks.weight, self.w_vs.weight, self.fc.weight)
-        ver = (str(q.device),) + tuple(w._version for w in ws)
-        if getattr(self, "_pack", None) is None or self._pack[0] != ver:        # packed once per weight version (standalone use)
-            self._pack = (ver, [ops.pack_linear_weight(w, q.device)[0] for w in ws])
+        self.packed(q.device)
         if mask is not None:
             # the fused block (eg_multi_head_attention) has no mask argument -- the path never passes one; with a mask the same kernels run
             # operator by operator: projections, masked attention (SubLayers.py:44-47: the head axis is broadcast), output projection +

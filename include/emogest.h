@@ -939,6 +939,65 @@ int eg_take_distance(const float* feat, int32_t recordings, int32_t draws, int32
                      int32_t span /* <= 0: none */, void* workspace, int64_t workspace_bytes, double* distance, double* diversity,
                      void* stream);
 
+/* Emotion recognition of whole tracks: does a take show the emotion it was asked for?  The whole-track counterpart of the eval loop's
+ * Emotion_ACC (test_emotion_gesture_diversity_iterative.py:216-221: the skeleton emotion classifier on the generated poses), for tracks of
+ * any and unequal length with R takes each (csrc/emotion.hip).  The classifier itself (skeleton_classifer/Models.py:199-283) is eg_linear,
+ * eg_multi_head_attention and eg_positionwise_ffn; these entries are everything around it.
+ *
+ * Classifier windows.  A window is F = the classifier's n_position consecutive poses of one take: no padding, no resampling.  Recording u
+ * with frames[u] valid poses and stride S >= 1 has windows at 0, S, 2S, ... while start + F <= frames[u]; with tail != 0 one more at
+ * frames[u] - F when (frames[u] - F) % S != 0, so that every valid pose is seen.  C_u is that count; frames[u] < F is refused by name.
+ * Clip order: recording-major, then take, then window: clip R * coff[u] + r * C_u + j, coff the exclusive prefix sum of C;
+ * N = R * sum(C_u).  Poses at or beyond frames[u] are never read.
+ * Meta table (host only: no HIP call, usable without a GPU): eg_emotion_meta writes `frames | off | C | coff`, 4U int32 (the count
+ * eg_emotion_meta_ints returns; 0 for U outside 1 .. 65535), and returns N / R = sum(C_u), or 0 for refused arguments.  Refuses by name: null
+ * pointers, U outside 1 .. 65535, frames[u] < F, F < 1, S < 1, sum(frames) >= 2^31 (C_u <= frames[u], so the window counts are in range with the frames).
+ *
+ * eg_emotion_window_embed.  emb [R * sum(frames), d_model] fp32 is the classifier's per-pose embedding (prior_seq_encoder.fc1, fc2: run once
+ * per valid pose, not once per window) in the packed order of eg_track_rows_pack; pos [F, d_model] the encoder's positional table.  For
+ * the clip range [c0, c1):   x[(c - c0) * F + f, k] = emb[R*off[u] + r*frames[u] + start(u, j) + f, k] + pos[f, k]
+ * -- the gather of the windows and the encoder's first row addition in one pass, one IEEE fp32 addition per element.  One launch gridded over
+ * the chip, every output element has one owning thread, 16-byte loads and stores.  The range only bounds the caller's workspace: an element
+ * of x does not depend on it.  Refuses by name: null pointers, emb / pos / x not 16-byte aligned, d_model not a multiple of 4, draws outside
+ * 1 .. EG_TAKE_MAX_DRAWS, c0 < 0, c1 > N, an empty range, and what the meta call refuses.
+ *
+ * eg_emotion_vote on all logits [N, C] fp32, 2 <= C <= EG_EMOTION_MAX_CLASSES, from counts[u] = C_u (HOST, each >= 1) and d_counts, a device
+ * copy of `C | coff` (2U int32: the second half of the meta table).  Per window i: valid(i) = all C logits finite; window_class[i] = the
+ * lowest index among the maxima when valid, -1 otherwise.  Per take (u, r) with n = C_u windows:
+ *   votes[u, r, c]       int32   valid windows of class c
+ *   invalid[u, r]        int32   windows that are not valid
+ *   mean_logit[u, r, c]  fp64    (sum over valid windows of the widened fp32 logits) / valid count; the sum runs over ascending windows
+ *                                inside a chunk of EG_EMOTION_CHUNK_WINDOWS windows, then over ascending chunks (it may depend on that
+ *                                constant and on nothing else); NaN when no window is valid.  Against the exact mean the error is at most
+ *                                (n + 2) * 2^-53 * sum |l| / count.
+ *   pred[u, r]           int32   the class with the most votes; among tied classes the larger mean_logit; still tied, the lowest index;
+ *                                -1 when no window is valid
+ * With d_labels (int32 [U * R] on the device, may be NULL; then the seven label outputs may be NULL too and are not written):
+ *   hit[u, r] = pred == y;   window_hits[u, r] = votes[u, r, y];   accuracy = 100 * sum hit / (U R);
+ *   window_accuracy = 100 * sum window_hits / N  (fp64, in percent);   confusion [C, C] int32: row = label, column = pred, over takes with
+ *   pred >= 0;   window_confusion [C, C]: row = label, column = window_class, over valid windows.
+ * unscored (int32, always written): takes with pred == -1.
+ * The device cannot refuse a label: labels are trusted to lie in [0, C) (a host caller checks them before the upload).  A label outside
+ * the range is never used as an index: such a take has hit = window_hits = 0, enters no cell of either matrix and counts in `unscored` only.
+ * Two launches.  Stage 1: one wave per (take, chunk): the class of every window, the chunk's fp64 logit sums and int32 counts ->
+ * workspace.  Stage 2: one wave per take adds its chunks in ascending order; one further workgroup walks all takes in ascending order for
+ * the pooled figures.  No atomics, no memset, no allocation, no host round trip; grids and pointers are fixed for fixed (counts, draws, C),
+ * so the call captures into a hipGraph.  workspace >= eg_emotion_vote_workspace_bytes (0 for arguments the call would refuse).
+ * Refuses by name, before the first launch: null pointers, workspace not 16-byte aligned, fp64 outputs not 8-byte aligned, U outside
+ * 1 .. 65535, draws outside 1 .. EG_TAKE_MAX_DRAWS, C outside 2 .. EG_EMOTION_MAX_CLASSES, counts[u] < 1, N >= 2^31, a short workspace. */
+#define EG_EMOTION_CHUNK_WINDOWS 64
+#define EG_EMOTION_MAX_CLASSES 64
+int64_t eg_emotion_meta_ints(int32_t recordings);
+int64_t eg_emotion_meta(const int32_t* frames, int32_t recordings, int32_t window, int32_t stride, int32_t tail, int32_t* meta);
+int eg_emotion_window_embed(const float* emb, const float* pos, int32_t recordings, int32_t draws, int32_t window, int32_t stride,
+                            int32_t tail, int32_t d_model, const int32_t* frames, const int32_t* d_meta, int32_t c0, int32_t c1, float* x,
+                            void* stream);
+int64_t eg_emotion_vote_workspace_bytes(const int32_t* counts, int32_t recordings, int32_t draws, int32_t classes);
+int eg_emotion_vote(const float* logits, int32_t recordings, int32_t draws, int32_t classes, const int32_t* counts, const int32_t* d_counts,
+                    const int32_t* d_labels, void* workspace, int64_t workspace_bytes, int32_t* window_class, int32_t* votes,
+                    int32_t* invalid, double* mean_logit, int32_t* pred, int32_t* hit, int32_t* window_hits, double* accuracy,
+                    double* window_accuracy, int32_t* confusion, int32_t* window_confusion, int32_t* unscored, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Block-level operators (the reference's L2 blocks), used by the module-level mirrors and by the
  * per-kernel parity tests.  Weights here are passed as individual device pointers in the PACKED

@@ -34,6 +34,10 @@ With --srgr and / or --l1div (and --joints, TED shape) the call also returns the
 (jointscore.srgr_of_joints: two more launches; jointscore.l1div_of_tracks on the joints as 129 columns: four more).  There is no captured
 motion here, so the stand-in target of --srgr is the joints of the same track smoothed with a (9, 3) Savitzky-Golay filter and the semantic
 weights are 1 on every third second: the script prints the recall at 2 cm, the weighted rate and the L1 diversity in metres.
+With --emotion the call also asks a skeleton emotion classifier (a SkeletonTransformer with synthetic weights here: d_model 64, 8 heads,
+2 layers, windows of 12 poses) which emotion every returned take shows (emotion.emotion_of_tracks on the raw track: one decision per take from
+the votes of its classifier windows), and the script prints per take the asked and the recognised emotion and the pooled accuracy -- with
+--draws R every take of a recording is asked for its own emotion.
 With --beat --joints the body is a skeleton.JointTree -- the BEAT columns are one 6-D rotation per joint -- read from the HIERARCHY block of
 --bvh FILE (which must have 47 joints, or name them with --bvh-joints A,B,...), or a synthetic 47-joint upper body without --bvh: joint
 positions and, with --rotations, one local rotation per joint come from ONE more launch (skeleton.launch_articulate), and the script prints their
@@ -41,7 +45,7 @@ shapes, how far the deepest joint travels and the largest rotation angle.
 With --bvh FILE --bvh-out DIR the call also returns the Euler channels of every joint in the file's own channel orders (euler=BvhFile,
 euler_unwrap=True: one more launch and the Euler filter's three) and the script writes DIR/recording_U[_take_R].bvh -- the file's HIERARCHY,
 then the generated MOTION at the joints' frame rate -- one file per recording and take, formatted on the host (bvh.BvhFile.write).
-usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--bvh FILE [--bvh-joints A,B,...] [--bvh-out DIR]] [--joints-fps N] [--rotations]] [--smooth K P] [--kinematics] [--srgr] [--l1div] [--out tracks.npz]"""
+usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--bvh FILE [--bvh-joints A,B,...] [--bvh-out DIR]] [--joints-fps N] [--rotations]] [--smooth K P] [--kinematics] [--srgr] [--l1div] [--emotion] [--out tracks.npz]"""
 import os
 import sys
 import time
@@ -57,7 +61,7 @@ from emotiongestures_amd.CAVE.BEAT_CVAE import MLP_Reconstruct_v3
 from emotiongestures_amd.synth import load_synth_weights, synth_audio
 
 argv, DRAWS, OUT, BEAT, DIVERSITY, RATE, JOINTS, JOINTS_FPS, ROTATIONS, SMOOTH = [], 0, None, False, False, 16000, False, None, False, None
-BVH, BVH_JOINTS, BVH_OUT, KINEMATICS, SRGR, L1DIV = None, None, None, False, False, False
+BVH, BVH_JOINTS, BVH_OUT, KINEMATICS, SRGR, L1DIV, EMOTION = None, None, None, False, False, False, False
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--draws":
@@ -90,6 +94,8 @@ for a in it:
         SRGR = True
     elif a == "--l1div":
         L1DIV = True
+    elif a == "--emotion":
+        EMOTION = True
     else:
         argv.append(a)
 if DIVERSITY and DRAWS < 2:
@@ -247,6 +253,30 @@ elif JOINTS:
         swing = lambda k: float(torch.rad2deg(2 * torch.acos(rot[:, :, k, 0].clamp(max=1.0))).max())    # bone 4 / 21: left / right forearm
         print(f"--rotations: rotations {tuple(rot.shape)}, one more launch; largest elbow swing against the first generated frame: "
               f"left {swing(4):.1f} degrees, right {swing(21):.1f} degrees")
+if EMOTION:
+    from emotiongestures_amd.emotion import EmotionAccuracy
+    NAMES = ("neutral", "happiness", "anger", "sadness", "contempt", "surprise", "fear", "disgust")
+    skel = load_synth_weights(H.SkeletonTransformer(pose_dim=POSE_DIM, n_position=12, n_layers=2, d_k=64, d_v=64), 7).eval().to(dev)
+    R_E = max(DRAWS, 1)
+    asked = (torch.arange(U)[:, None] + 3 * torch.arange(R_E)[None, :]) % 8                       # [U, R]: each take its own emotion
+    ek = dict(z=torch.randn(U, R_E, W, 32), draws=R_E) if DRAWS else dict(z=z)
+    lab_e = torch.nn.functional.one_hot(asked, 8).float()[:, :, None, :].expand(U, R_E, W, 8).to(dev) if DRAWS else labels
+    H.synthesize((gen, vae), audio, text, seed_pose, labels=lab_e, emotion=skel, **ek, **AR)       # warm-up (packs the classifier's weights)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    em = H.synthesize((gen, vae), audio, text, seed_pose, labels=lab_e, emotion=skel, **ek, **AR)["emotion"]
+    torch.cuda.synchronize()
+    dt_e = time.perf_counter() - t0
+    pred, votes = em["pred"].cpu(), em["votes"].cpu()
+    print(f"--emotion: {em['logits'].shape[0]} classifier windows of 12 poses ({em['windows_per'][0]} per take), the call {1e3 * dt_e:.2f} ms against "
+          f"{1e3 * dt:.2f} ms without; per take asked -> recognised (votes of the recognised class / windows):")
+    for u in range(U):
+        print("  recording %d: " % u + ", ".join(f"{NAMES[int(asked[u, r])]} -> {NAMES[int(pred[u, r])] if pred[u, r] >= 0 else 'none'} "
+                                                   f"({int(votes[u, r].max())}/{em['windows_per'][u]})" for r in range(R_E)))
+    pool = EmotionAccuracy()
+    pool.push(em)
+    print(f"  pooled: {pool.hits} of {pool.takes} takes recognised as asked ({pool.avg():.1f} %), {pool.window_avg():.1f} % of the windows, "
+          f"{pool.unscored} takes without a valid window (synthetic weights: chance is 12.5 %)")
 if SMOOTH and not JOINTS:
     ts = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, smooth=SMOOTH, **AR)["track_smooth"]
     print(f"--smooth {SMOOTH[0]} {SMOOTH[1]}: track_smooth {tuple(ts.shape)}, one more launch; mean |pose[t+1] - pose[t]|: {float(step.mean()):.4f} raw, "
