@@ -101,6 +101,9 @@ __device__ __forceinline__ float wave_max(float v) {
 // fp32 -> (hi, lo) bf16 split: hi = rne(x), lo = rne(x - hi).  x - hi is exact in fp32.
 __device__ __forceinline__ unsigned short f32_to_bf16_rne(float x) {
     unsigned int u = __float_as_uint(x);
+    // NaN stays NaN: the rounding add below carries a full mantissa into the sign (0x7FFFFFFF -> -0) and turns a small payload into inf
+    // (0x7F800001 -> 0x7F80); keep sign and high payload, set the quiet bit.  Finite values and inf are untouched.
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (unsigned short)((u >> 16) | 0x0040u);
     u += 0x7FFFu + ((u >> 16) & 1u);
     return (unsigned short)(u >> 16);
 }

@@ -281,10 +281,14 @@ __global__ __launch_bounds__(256) void subsample_kernel(const float* __restrict_
 
 // ---- column reductions over rows: two deterministic levels ---------------------------------------------------------------
 // level 1: block (bx, by) sums rows [by*rows_per, ...) of 64 columns -> part[by][2][C]
-//   mode 0: (sum a, sum a*a)      mode 1: (sum a, sum a*b)      mode 2: (sum a, sum a*(b - mean[c]))      mode 3: (sum (a - mean[c])^2, 0)
+//   mode 0: (sum a, sum a*a)      mode 1: (sum a, sum a*b)      mode 2: (sum a, sum a*(b - mean[c]))      mode 3: (sum (a - mean[c])^2, sum (a - mean[c]))
 //   mode 4 (fast path only): mode 2 with a replaced by a * [mask > 0]  (gradient behind a ReLU whose output is `mask`)
 // The centred forms (2, 3) keep BatchNorm exact for channels whose mean is large against their spread (post-ReLU maps):
 // E[x^2] - mean^2 from fp32 partial sums loses ~eps*mean^2/var there (measured: 3e-3 in the input gradient of one block).
+// Mode 3 also returns the sum of the residuals a - mean[c]: the first-pass mean comes from fp32 chains and is off by a few ulp of the MEAN, which a
+// channel whose mean dominates its spread sees multiplied by rstd (a constant 100.3 over 3712 rows: y - beta = -7e-3 gamma instead of 0).  The
+// residuals are small, so their sum corrects the mean to its rounding and the variance to the one about the corrected mean (bn_finalize_kernel),
+// as the LayerNorm kernels' two-step mean does, with no further pass over the map.
 // (generic channel counts -- 34 / 60 / 120 frame channels behind final_conv1, the TCN's widths: the mode is a template parameter and eight rows'
 // loads are in flight per thread; with the mode a runtime branch inside a one-load-per-iteration loop a [15 872, 34] map took 21 us, round 6)
 template <int MODE>
@@ -300,7 +304,7 @@ __global__ __launch_bounds__(256) void col_partial_kernel(const float* __restric
             if (MODE == 0) { u += x; v += x * x; }
             else if (MODE == 1) { u += x; v += x * y; }
             else if (MODE == 2) { u += x; v += x * (y - mu); }
-            else { const float d = x - mu; u += d * d; }
+            else { const float d = x - mu; u += d * d; v += d; }
         };
         constexpr bool HAS_B = (MODE == 1 || MODE == 2);
         long r = r0 + w;
@@ -370,7 +374,7 @@ __global__ __launch_bounds__(256) void col_partial_fast_kernel(const float* __re
         } else if (mode == 0) { u += x; v += x * x; }
         else if (mode == 1) { u += x; v += x * y; }
         else if (mode == 2) { u += x; v += x * (y - mu); }
-        else { const f4 d = x - mu; u += d * d; }
+        else { const f4 d = x - mu; u += d * d; v += d; }
     };
     size_t f = tid;
     // four independent 16-byte loads per stream in flight per thread (the kernel is a pure stream: at one load per iteration and <= 8 waves per
@@ -404,7 +408,7 @@ __global__ __launch_bounds__(256) void col_partial_fast_kernel(const float* __re
     }
 }
 
-// level 2 for BatchNorm forward, pass 1: mean;  pass 2 (from centred squares): rstd (biased variance) and the running statistics
+// level 2 for BatchNorm forward, pass 1: mean;  pass 2 (from centred squares and residuals): the corrected mean, rstd (biased variance) and the running statistics
 // (unbiased variance, momentum) exactly as torch.nn.BatchNorm updates them
 // level 2: one wave per channel; lanes stride over the partials, the two sums are folded with a fixed-order wave reduction (double)
 __device__ __forceinline__ double wave_sum_d(double v) {
@@ -427,18 +431,23 @@ __global__ __launch_bounds__(256) void bn_mean_kernel(const float* __restrict__ 
     if ((threadIdx.x & 63) == 0) mean[c] = (float)(s / (double)rows);
 }
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ part, int nblk, int C, long rows, float eps, float momentum,
-                                                          const float* __restrict__ mean, float* __restrict__ rstd, float* __restrict__ run_mean,
+                                                          float* __restrict__ mean, float* __restrict__ rstd, float* __restrict__ run_mean,
                                                           float* __restrict__ run_var) {
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (c >= C) return;
-    double q, unused;
-    fold_partials(part, nblk, C, c, q, unused);
+    double q, s;
+    fold_partials(part, nblk, C, c, q, s);
     if ((threadIdx.x & 63) != 0) return;
-    const double var = q / (double)rows;
+    // q = sum (x - m0)^2 and s = sum (x - m0) about the first-pass mean m0: the mean is m0 + s / rows, the variance about it q / rows - (s / rows)^2
+    const double dm = s / (double)rows;
+    const float m = (float)((double)mean[c] + dm);
+    double var = q / (double)rows - dm * dm;
+    if (var < 0.0) var = 0.0;
+    mean[c] = m;
     rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
     if (run_mean) {
         const double unb = rows > 1 ? var * (double)rows / (double)(rows - 1) : var;
-        run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * mean[c];
+        run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * m;
         run_var[c] = (1.f - momentum) * run_var[c] + momentum * (float)unb;
     }
 }
@@ -470,7 +479,7 @@ __global__ __launch_bounds__(256) void col_direct_kernel(const float* __restrict
             if (mode == 0) { u += x; v += x * x; }
             else if (mode == 1) { u += x; v += x * *reinterpret_cast<const f4*>(b + (size_t)r * C + c); }
             else if (mode == 2) { u += x; v += x * (*reinterpret_cast<const f4*>(b + (size_t)r * C + c) - mu); }
-            else { const f4 d = x - mu; u += d * d; }
+            else { const f4 d = x - mu; u += d * d; v += d; }
         }
     }
     s0[tid] = u;

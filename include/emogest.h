@@ -1275,7 +1275,8 @@ int eg_conv1d_cl_backward_weight(const float* x, const float* dy, float* dw, flo
 /* [rows, k] -> [rows, k_padded] zero padded (rows of the GEMM operands are read in 16-byte pieces) */
 int eg_pad_cols(const float* x, float* y, int64_t rows, int32_t k, int32_t k_padded, void* stream);
 /* nn.BatchNorm{1,2}d in train() mode over channels-last rows [rows, C]: batch statistics (biased variance for the
- * normalisation, unbiased for running_var, momentum as torch), saved mean / rstd for the backward. */
+ * normalisation, unbiased for running_var, momentum as torch), saved mean / rstd for the backward.  The mean is taken in two steps (the centred
+ * pass also sums the residuals about the first-pass mean and corrects it): its error scales with a channel's spread, not with its magnitude. */
 int64_t eg_colreduce_workspace_floats(int32_t c);
 int eg_bn_train_forward(const float* x, const float* gamma, const float* beta, float* y, float* save_mean, float* save_rstd,
                         float* running_mean, float* running_var, int64_t rows, int32_t c, float momentum, float eps, float* workspace,
@@ -1284,7 +1285,8 @@ int eg_bn_train_forward(const float* x, const float* gamma, const float* beta, f
 int eg_bn_train_backward(const float* x, const float* dy, const float* gamma, const float* save_mean, const float* save_rstd, float* dx,
                          float* dgamma, float* dbeta, int64_t rows, int32_t c, int32_t relu_mask, float* workspace, void* stream);
 /* BatchNorm (train mode) on a map that eg_conv3x3 just wrote together with gap_partial [batch][tiles][c] (per-tile channel sums): the mean
- * and clip_sum [batch][c] (nullable) come from the partials, one centred pass over x gives the variance.  y NULL: statistics only. */
+ * and clip_sum [batch][c] (nullable) come from the partials, one centred pass over x gives the variance and corrects the mean.  y NULL:
+ * statistics only. */
 int eg_bn_train_forward_gap(const float* x, const float* gap_partial, int32_t tiles, int32_t batch, const float* gamma, const float* beta,
                             float* y, float* save_mean, float* save_rstd, float* clip_sum, float* running_mean, float* running_var,
                             int64_t rows, int32_t c, float momentum, float eps, float* workspace, void* stream);
