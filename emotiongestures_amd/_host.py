@@ -1,5 +1,5 @@
 """Host plumbing between torch tensors and the C ABI of libemogest_hip.so: pointer and stream casts, the GPU-tensor check, host integer
-vectors and the bounded "build once per key" cache.  Every wrapper module takes these from here; nothing here depends on one of them."""
+vectors, the "size a buffer or raise" call and the bounded "build once per key" cache.  Every wrapper module takes these from here; nothing here depends on one of them."""
 from __future__ import annotations
 
 import ctypes as C
@@ -35,6 +35,20 @@ def int_list(v) -> list:
     """A torch tensor (any device; a GPU tensor synchronises), an ndarray or any iterable of integer-likes -> a list of Python ints.  Nothing
     about length or range is checked here: every caller has its own check and wording.  A bare int is not iterable: TypeError."""
     return [int(a) for a in (v.tolist() if hasattr(v, "tolist") else v)]
+
+
+def sized(fn_name: str, *args) -> int:
+    """The bytes a ``*_bytes`` sizer of the library asks for; a refusal (<= 0) raises with the library's last error."""
+    lib = L.load()
+    nbytes = int(getattr(lib, fn_name)(*args))
+    if nbytes <= 0:
+        raise L.EgError(f"{fn_name}: refused ({lib.eg_last_error().decode()})")
+    return nbytes
+
+
+def device_bytes(fn_name: str, device, *args) -> torch.Tensor:
+    """A uint8 tensor of ``sized(fn_name, *args)`` bytes on ``device`` (uninitialised)."""
+    return torch.empty(sized(fn_name, *args), dtype=torch.uint8, device=device)
 
 
 class BoundedCache:

@@ -24,7 +24,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._host import BoundedCache, host_ptr, int_list, ptr as _ptr, stream as _stream
+from ._host import BoundedCache, host_ptr, ptr as _ptr, sized, stream as _stream
+from ._rows import count_list
 
 __all__ = ["beat_alignment", "beat_alignment_tracks", "alignment", "L1div", "SRGR", "BeatScoreUnavailable", "MAX_FRAMES", "SAMPLE_RATE"]
 
@@ -142,9 +143,7 @@ class _TracksPlan:
         self.T = 1 + self.lengths // HOP
         self.offsets = np.concatenate([[0], np.cumsum(self.T)[:-1]]).astype(np.int64)
         self.sum_T = int(self.T.sum())
-        self.bytes = int(lib.eg_beat_tracks_workspace_bytes(self.h_lengths, self.h_frames, U, int(draws), int(Tmax)))
-        if self.bytes <= 0:
-            raise L.EgError(f"eg_beat_tracks_workspace_bytes: refused ({lib.eg_last_error().decode()})")
+        self.bytes = sized("eg_beat_tracks_workspace_bytes", self.h_lengths, self.h_frames, U, int(draws), int(Tmax))
         self.meta = torch.from_numpy(meta).to(device)
 
 
@@ -155,13 +154,6 @@ def _tracks_plan(lib, lengths, frames, t_end, fps, draws, Tmax, device) -> _Trac
     key = (tuple(lengths), None if frames is None else tuple(frames), None if t_end is None else tuple(t_end), int(fps), int(draws),
            int(Tmax), str(device))
     return _PLANS.get(key, lambda: _TracksPlan(lib, lengths, frames, t_end, fps, draws, Tmax, device))
-
-
-def _int_list(v, n, name):
-    v = int_list(v)
-    if len(v) != n:
-        raise ValueError(f"beat_alignment_tracks: {name} has {len(v)} entries for {n} recordings")
-    return v
 
 
 def _run_tracks(audio: torch.Tensor, track: Optional[torch.Tensor], lengths, frames, fps, t_start, t_end, sigma, order, want_beats,
@@ -225,10 +217,10 @@ def beat_alignment_tracks(audio: torch.Tensor, track: torch.Tensor, lengths=None
     trk = track.to(torch.float32).contiguous()
     trk = trk if has_draws else trk[:, None]
     Tmax = trk.shape[2]
-    lengths = [audio.shape[1]] * U if lengths is None else _int_list(lengths, U, "lengths")
-    frames = [Tmax] * U if frames is None else _int_list(frames, U, "frames")
+    lengths = [audio.shape[1]] * U if lengths is None else count_list(lengths, U, "beat_alignment_tracks", "lengths")
+    frames = [Tmax] * U if frames is None else count_list(frames, U, "beat_alignment_tracks")
     if t_end is not None:
-        t_end = [int(t_end)] * U if isinstance(t_end, (int, np.integer)) else _int_list(t_end, U, "t_end")
+        t_end = [int(t_end)] * U if isinstance(t_end, (int, np.integer)) else count_list(t_end, U, "beat_alignment_tracks", "t_end")
     audio = audio.to(torch.float32)
     if t_start:
         audio = audio[:, int(t_start) * SAMPLE_RATE:]

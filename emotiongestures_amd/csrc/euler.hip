@@ -8,7 +8,7 @@
 //   scan     per row and column, over the tiles in order: the count at a tile's first frame = the totals before it + its own first k;
 //   apply    walks the tile again from that count.  It reads and writes its own tile only, so in place is safe.
 // A track of one tile needs the last launch alone.  The totals live in the caller's workspace; plain stores, one owner each, no atomics.
-#include "common.h"
+#include "rows.h"
 #include <math.h>
 
 namespace {
@@ -26,12 +26,6 @@ struct UArgs {
     float P32;
 };
 
-__device__ __forceinline__ int valid_frames(const UArgs& a, int b) {
-    if (!a.frames) return a.T;
-    const long long v = (long long)a.frames[b / a.draws] * a.frame_unit;
-    return (int)(v < 0 ? 0 : (v > a.T ? a.T : v));
-}
-
 __device__ __forceinline__ int jump(float cur, float prev, double P) { return (int)rint((double)(cur - prev) / P); }
 
 // APPLY: write the frames; else: the totals of the tile.
@@ -40,7 +34,7 @@ __global__ __launch_bounds__(THREADS) void unwrap_kernel(const UArgs a) {
     const int c = blockIdx.y * THREADS + threadIdx.x;
     if (c >= a.C) return;
     const int b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
-    const int n = valid_frames(a, b);
+    const int n = egi_valid_frames(a.frames, b / a.draws, a.frame_unit, a.T);
     const int t0 = tile * UT, t1 = min(t0 + UT, n);
     const long long slot = ((long long)b * a.tiles + tile) * a.C + c, plane = (long long)a.rows * a.tiles * a.C;
     if (t0 >= t1) {
@@ -114,8 +108,7 @@ extern "C" int eg_angle_unwrap(float* angles, int32_t rows, int32_t T, int32_t C
     EG_REQUIRE((reinterpret_cast<uintptr_t>(angles) & 3u) == 0, EG_ERR_ALIGN, "%s: angles not 4-byte aligned", who);
     const long long need = unwrap_bytes(who, rows, T, C);
     if (need <= 0) return EG_ERR_BAD_ARG;
-    EG_REQUIRE(draws >= 1 && rows % draws == 0, EG_ERR_BAD_ARG, "%s: rows=%d is not a multiple of draws=%d", who, rows, draws);
-    EG_REQUIRE(frame_unit >= 1, EG_ERR_BAD_ARG, "%s: frame_unit=%d (need >= 1)", who, frame_unit);
+    if (int rc = egi_check_rows(who, rows, T, nullptr, d_frames, false, draws, frame_unit, 0, "")) return rc;
     EG_REQUIRE(isfinite(period) && period > 0.0 && isfinite((float)period) && (float)period > 0.f, EG_ERR_BAD_ARG,
                "%s: period=%g (need finite and > 0)", who, period);
     const int tiles = (int)(((long long)T + UT - 1) / UT);

@@ -5,13 +5,13 @@
 //   L1div  mean[b, c] = (sum_t double(x[t, c])) / n;  l1_sum[b] = sum_t sum_c |double(x[t, c]) - mean[b, c]|;  l1div = l1_sum / n
 // There is no product of two rounded values anywhere (w * count is exact), so the file needs no contraction pragma.
 // A workgroup owns TF frames of one row.  The tile is one contiguous span of the row, staged into LDS with 16-byte loads on the aligned body and
-// scalar loads at its two ends (stage_span: the loop of kin_tiles_kernel); consecutive lanes then work on consecutive (frame, joint) or
+// scalar loads at its two ends (rows.h: egi_stage_exact); consecutive lanes then work on consecutive (frame, joint) or
 // (run, column) items, so LDS reads are stride-3 or stride-1 (conflict-free) and the hit flags [TF][J | 1] are read along either axis without
 // a conflict.  Every tile stores its partials -- fp64 sums and, for the hits, int32 [J] -- to the workspace with plain stores; a finalise launch
 // adds a row's own ceil(n / TF) tiles in ascending order.  No atomics, no memset, nothing to zero: a tile past n is never read.
 // SRGR with draws > 1: the takes of a recording are consecutive workgroups (draw fastest in blockIdx), so the target tile they share is fetched
 // from memory once and found in cache by the others.
-#include "common.h"
+#include "rows.h"
 #include <math.h>
 
 namespace {
@@ -24,31 +24,8 @@ constexpr int RUNS = 8;                                 // L1 diversity: runs of
 constexpr int RUN = TF / RUNS;
 static_assert(TF % RUNS == 0 && TF <= 64 && 64 + MAXJ <= THREADS && MAXD >= 282 && MAXD >= 3 * MAXJ, "tile constants");
 
-__device__ __forceinline__ int valid_frames(const int* frames, int u, int frame_unit, int T) {
-    if (!frames) return T;
-    const long long v = (long long)frames[u] * frame_unit;
-    return (int)(v < 0 ? 0 : (v > T ? T : v));          // the host refuses n < 1; a device count of 0: zeros, nothing out of range
-}
-
 // floats of a staged tile of `width` columns: TF * width elements behind a shift of up to 3, rounded up to a multiple of 4
 __host__ __device__ inline int stage_floats(int width) { return (TF * width + 6) & ~3; }
-
-// Elements [g0, g1) of p -> l, element g at l[g - (g0 & ~3)]; returns the shift g0 & 3.  p is 16-byte aligned, so every 4-element group that
-// starts at a multiple of 4 is one aligned 16-byte load.
-__device__ __forceinline__ int stage_span(float* __restrict__ l, const float* __restrict__ p, long long g0, long long g1, int tid) {
-    const long long q0 = g0 & ~3ll;
-    for (long long q = q0 + 4 * tid; q < g1; q += 4 * THREADS) {
-        float* d = l + (q - q0);
-        if (q >= g0 && q + 4 <= g1) {
-            *reinterpret_cast<f4*>(d) = *reinterpret_cast<const f4*>(p + q);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (q + e >= g0 && q + e < g1) d[e] = p[q + e];
-        }
-    }
-    return (int)(g0 - q0);
-}
 
 // ---- SRGR -------------------------------------------------------------------------------------------------------------------------------
 struct SrgrArgs {
@@ -75,13 +52,13 @@ __global__ __launch_bounds__(THREADS) void srgr_tiles_kernel(const SrgrArgs a) {
     const int tid = threadIdx.x;
     const int draw = blockIdx.x % a.draws, ut = blockIdx.x / a.draws, tile = ut % a.tiles, u = ut / a.tiles;
     const int b = u * a.draws + draw;
-    const int n = valid_frames(a.frames, u, a.frame_unit, a.T);
+    const int n = egi_valid_frames(a.frames, u, a.frame_unit, a.T);
     const int t0 = tile * TF;
     if (t0 >= n) return;                                // no frame of the row here (block-uniform): the finalise reads the row's own tiles only
     const int nt = min(TF, n - t0);                     // frames [t0, t0 + nt) of the row
     const long long rb = ((long long)b * a.T + t0) * J3, gb = ((long long)u * a.T + t0) * J3;
-    const int shift_r = stage_span(l_r, a.r, rb, rb + (long long)nt * J3, tid);
-    const int shift_g = stage_span(l_g, a.g, gb, gb + (long long)nt * J3, tid);
+    const int shift_r = egi_stage_exact(l_r, a.r, rb, rb + (long long)nt * J3, tid, THREADS);
+    const int shift_g = egi_stage_exact(l_g, a.g, gb, gb + (long long)nt * J3, tid, THREADS);
     __syncthreads();
     for (int i = tid; i < nt * J; i += THREADS) {       // i = t * J + j: consecutive lanes, consecutive joints
         const int t = i / J, j = i - t * J;
@@ -115,30 +92,6 @@ __global__ __launch_bounds__(THREADS) void srgr_tiles_kernel(const SrgrArgs a) {
     }
 }
 
-// A row's own tiles added in ascending order, sixteen loads in flight (a tile past nt adds +0.0 or 0, which changes no bit).
-__device__ __forceinline__ double sum_tiles(const double* __restrict__ src, long long stride, int nt) {
-    double acc = 0.0;
-    for (int t = 0; t < nt; t += 16) {
-        double v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = t + u < nt ? src[(long long)(t + u) * stride] : 0.0;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) acc += v[u];
-    }
-    return acc;
-}
-__device__ __forceinline__ int sum_tiles(const int* __restrict__ src, long long stride, int nt) {
-    int acc = 0;
-    for (int t = 0; t < nt; t += 16) {
-        int v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = t + u < nt ? src[(long long)(t + u) * stride] : 0;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) acc += v[u];
-    }
-    return acc;
-}
-
 // One workgroup of two waves per row: thread j < J adds joint j's hits over the row's tiles, thread 64 the weighted sums; then thread 64 adds
 // the J counts (integers: order-free) and writes the row's two figures.
 constexpr int FINAL_THREADS = 128;
@@ -146,15 +99,15 @@ static_assert(MAXJ <= 64 && FINAL_THREADS > 64, "joints in wave 0, the sums in w
 __global__ __launch_bounds__(FINAL_THREADS) void srgr_final_kernel(const SrgrArgs a) {
     __shared__ int l_c[MAXJ];
     const int J = a.J, b = blockIdx.x, tid = threadIdx.x;
-    const int n = valid_frames(a.frames, b / a.draws, a.frame_unit, a.T);
+    const int n = egi_valid_frames(a.frames, b / a.draws, a.frame_unit, a.T);
     const int nt = (n + TF - 1) / TF;
     double acc = 0.0;
     if (tid < J) {
-        const int c = sum_tiles(a.part_h + (long long)b * a.tiles * J + tid, J, nt);
+        const int c = egi_sum_tiles(a.part_h + (long long)b * a.tiles * J + tid, J, nt);
         a.hits[(long long)b * J + tid] = c;
         l_c[tid] = c;
     } else if (tid == 64) {
-        acc = sum_tiles(a.part_w + (long long)b * a.tiles, 1, nt);
+        acc = egi_sum_tiles(a.part_w + (long long)b * a.tiles, 1, nt);
     }
     __syncthreads();
     if (tid == 64) {
@@ -191,12 +144,12 @@ __global__ __launch_bounds__(THREADS) void l1_tiles_kernel(const L1Args a) {
     float* l_x = reinterpret_cast<float*>(l_run + RUNS * D);       // (THREADS + RUNS * D) doubles: a multiple of 16 bytes
     const int tid = threadIdx.x;
     const int tile = blockIdx.x % a.tiles, b = blockIdx.x / a.tiles;
-    const int n = valid_frames(a.frames, b / a.draws, a.frame_unit, a.T);
+    const int n = egi_valid_frames(a.frames, b / a.draws, a.frame_unit, a.T);
     const int t0 = tile * TF;
     if (t0 >= n) return;                                // block-uniform
     const int nt = min(TF, n - t0);
     const long long xb = ((long long)b * a.T + t0) * D;
-    const int shift = stage_span(l_x, a.x, xb, xb + (long long)nt * D, tid);
+    const int shift = egi_stage_exact(l_x, a.x, xb, xb + (long long)nt * D, tid, THREADS);
     __syncthreads();
     for (int i = tid; i < RUNS * D; i += THREADS) {     // i = run * D + c: consecutive lanes, consecutive columns
         const int run = i / D, c = i - run * D;
@@ -234,18 +187,18 @@ __global__ __launch_bounds__(THREADS) void l1_means_kernel(const L1Args a) {
     const int D = a.D;
     if (e >= (long long)a.rows * D) return;
     const int b = (int)(e / D), c = (int)(e - (long long)b * D);
-    const int n = valid_frames(a.frames, b / a.draws, a.frame_unit, a.T);
+    const int n = egi_valid_frames(a.frames, b / a.draws, a.frame_unit, a.T);
     const int nt = (n + TF - 1) / TF;
-    const double acc = sum_tiles(a.part_c + (long long)b * a.tiles * D + c, D, nt);
+    const double acc = egi_sum_tiles(a.part_c + (long long)b * a.tiles * D + c, D, nt);
     a.mean[e] = n > 0 ? acc / (double)n : 0.0;
 }
 
 __global__ __launch_bounds__(THREADS) void l1_final_kernel(const L1Args a) {
     const int b = blockIdx.x * THREADS + threadIdx.x;
     if (b >= a.rows) return;
-    const int n = valid_frames(a.frames, b / a.draws, a.frame_unit, a.T);
+    const int n = egi_valid_frames(a.frames, b / a.draws, a.frame_unit, a.T);
     const int nt = (n + TF - 1) / TF;
-    const double acc = sum_tiles(a.part_s + (long long)b * a.tiles, 1, nt);
+    const double acc = egi_sum_tiles(a.part_s + (long long)b * a.tiles, 1, nt);
     a.l1_sum[b] = acc;
     a.l1div[b] = n > 0 ? acc / (double)n : 0.0;
 }
@@ -267,21 +220,6 @@ int check_joints(const char* who, int J) {
 }
 int check_cols(const char* who, int D) {
     EG_REQUIRE(D >= 1 && D <= MAXD, EG_ERR_UNSUPPORTED, "%s: columns=%d (1..%d)", who, D, MAXD);
-    return EG_OK;
-}
-
-int check_rows(const char* who, int rows, int T, const int32_t* frames, const int32_t* d_frames, int draws, int frame_unit) {
-    EG_REQUIRE((reinterpret_cast<uintptr_t>(d_frames) & 3u) == 0, EG_ERR_ALIGN, "%s: d_frames not 4-byte aligned", who);
-    EG_REQUIRE(draws >= 1 && rows % draws == 0, EG_ERR_BAD_ARG, "%s: rows=%d is not a multiple of draws=%d", who, rows, draws);
-    EG_REQUIRE(frame_unit >= 1, EG_ERR_BAD_ARG, "%s: frame_unit=%d (need >= 1)", who, frame_unit);
-    EG_REQUIRE((d_frames == nullptr) == (frames == nullptr), EG_ERR_BAD_ARG,
-               "%s: frames (host) and d_frames (device) go together: the counts are checked on the host copy", who);
-    if (frames) {
-        for (int u = 0; u < rows / draws; ++u) {
-            const long long v = (long long)frames[u] * frame_unit, n = v < 0 ? 0 : (v > T ? T : v);
-            EG_REQUIRE(n >= 1, EG_ERR_BAD_ARG, "%s: recording %d has %lld valid frames < 1", who, u, n);
-        }
-    }
     return EG_OK;
 }
 
@@ -318,7 +256,7 @@ extern "C" int eg_srgr_tracks(const float* results, const float* targets, const 
     if (rc != EG_OK) return rc;
     rc = check_shape(who, rows, T, 3ll * J);
     if (rc != EG_OK) return rc;
-    rc = check_rows(who, rows, T, frames, d_frames, draws, frame_unit);
+    rc = egi_check_rows(who, rows, T, frames, d_frames, true, draws, frame_unit, 1, "1");
     if (rc != EG_OK) return rc;
     EG_REQUIRE(isfinite(threshold), EG_ERR_BAD_ARG, "%s: threshold=%g is not finite", who, threshold);
     EG_REQUIRE(isfinite(scale), EG_ERR_BAD_ARG, "%s: scale=%g is not finite", who, scale);
@@ -359,7 +297,7 @@ extern "C" int eg_l1div_tracks(const float* x, int32_t rows, int32_t T, int32_t 
     if (rc != EG_OK) return rc;
     rc = check_shape(who, rows, T, D);
     if (rc != EG_OK) return rc;
-    rc = check_rows(who, rows, T, frames, d_frames, draws, frame_unit);
+    rc = egi_check_rows(who, rows, T, frames, d_frames, true, draws, frame_unit, 1, "1");
     if (rc != EG_OK) return rc;
     const long long tiles = tiles_of(T), need = l1_bytes(rows, T, D);
     EG_REQUIRE(workspace_bytes >= need, EG_ERR_BAD_ARG, "%s: workspace of %lld bytes, need %lld (eg_l1div_workspace_bytes)", who,

@@ -12,7 +12,7 @@
 // joint are added in ascending order and the tile's [3, J] partials stored to the workspace; the tile's non-zero bins go to
 // `hist` (zeroed by a launch of its own ahead of this one) with integer atomics.  Stage 2: one thread per (row, k, j) adds the row's own
 // ceil((n - 1) / TF) tile partials in ascending tile order, then scales and divides.  A row's figures depend on its own n and on TF only.
-#include "common.h"
+#include "rows.h"
 #include <math.h>
 
 namespace {
@@ -37,13 +37,6 @@ struct Args {
     int rows, T, J, bins, draws, frame_unit, tiles, top;   // top: the largest power of two <= bins
 };
 
-__device__ __forceinline__ int valid_frames(const Args& a, int b) {
-    if (!a.frames) return a.T;
-    const long long v = (long long)a.frames[b / a.draws] * a.frame_unit;
-    const int n = (int)(v < 0 ? 0 : (v > a.T ? a.T : v));
-    return n < 4 ? 0 : n;                               // the host refuses n < 4; a device count that differs from it: zeros, nothing out of range
-}
-
 // LDS, in this order: edges2 [E rounded up to even] fp64 | run sums [RUNS][3][J] fp64 | staged frames [(TF + HALO) * 3J + 4 rounded up to 4]
 // fp32 | histogram [J][E] int32
 __host__ __device__ inline int lds_edges(int bins) { return (bins + 2) & ~1; }
@@ -67,22 +60,12 @@ __global__ __launch_bounds__(MAX_THREADS) void kin_tiles_kernel(const Args a) {
     int* l_hist = reinterpret_cast<int*>(l_p + lds_stage(J));
     const int tid = threadIdx.x, threads = blockDim.x;
     const int tile = blockIdx.x % a.tiles, b = blockIdx.x / a.tiles;
-    const int n = valid_frames(a, b);
+    const int n = egi_valid_frames(a.frames, b / a.draws, a.frame_unit, a.T, 4);   // the host refuses n < 4
     const int t0 = tile * TF;
     if (t0 >= n - 1) return;                            // no difference starts here (block-uniform): stage 2 reads the row's own tiles only
     const int s1 = min(t0 + TF + HALO, n);              // frames [t0, s1) of the row
-    const long long g0 = ((long long)b * a.T + t0) * J3, g1 = ((long long)b * a.T + s1) * J3, q0 = g0 & ~3ll;
-    const int shift = (int)(g0 - q0);                   // element g of the span sits at l_p[g - q0]
-    for (long long q = q0 + 4 * tid; q < g1; q += 4 * threads) {
-        float* d = l_p + (q - q0);
-        if (q >= g0 && q + 4 <= g1) {
-            *reinterpret_cast<f4*>(d) = *reinterpret_cast<const f4*>(a.p + q);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (q + e >= g0 && q + e < g1) d[e] = a.p[q + e];
-        }
-    }
+    const long long g0 = ((long long)b * a.T + t0) * J3, g1 = ((long long)b * a.T + s1) * J3;
+    const int shift = egi_stage_exact(l_p, a.p, g0, g1, tid, threads);                // element g of the span sits at l_p[g - (g0 & ~3)]
     for (int i = tid; i < E; i += threads) l_edges[i] = a.edges2[i];
     for (int i = tid; i < J * E; i += threads) l_hist[i] = 0;
     __syncthreads();
@@ -169,20 +152,11 @@ __global__ __launch_bounds__(256) void kin_means_kernel(const Args a) {
     const int J = a.J, J3 = 3 * J;
     if (e >= (long long)a.rows * J3) return;
     const int b = (int)(e / J3), i = (int)(e - (long long)b * J3), k = i / J;
-    const int n = valid_frames(a, b);
+    const int n = egi_valid_frames(a.frames, b / a.draws, a.frame_unit, a.T, 4);
     double m = 0.0;
     if (n >= 4) {
         const int nt = (n - 1 + TF - 1) / TF;
-        const double* src = a.part + (long long)b * a.tiles * J3 + i;
-        double acc = 0.0;
-        for (int t = 0; t < nt; t += 16) {              // sixteen loads in flight, added in ascending tile order (a tile past nt adds +0.0)
-            double v[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) v[u] = t + u < nt ? src[(long long)(t + u) * J3] : 0.0;
-#pragma unroll
-            for (int u = 0; u < 16; ++u) acc += v[u];
-        }
-        m = acc * a.scale[k] / (double)(n - 1 - k);
+        m = egi_sum_tiles(a.part + (long long)b * a.tiles * J3 + i, J3, nt) * a.scale[k] / (double)(n - 1 - k);
     }
     a.mean[e] = m;
 }
@@ -236,20 +210,13 @@ extern "C" int eg_kin_stats(const float* joints, int32_t rows, int32_t T, int32_
     EG_REQUIRE(eg_aligned16(joints) && eg_aligned16(workspace) && eg_aligned16(mean) && eg_aligned16(hist), EG_ERR_ALIGN,
                "%s: joints / workspace / mean / hist not 16-byte aligned", who);
     EG_REQUIRE((reinterpret_cast<uintptr_t>(d_edges2) & 7u) == 0, EG_ERR_ALIGN, "%s: d_edges2 not 8-byte aligned", who);
-    EG_REQUIRE((reinterpret_cast<uintptr_t>(d_frames) & 3u) == 0, EG_ERR_ALIGN, "%s: d_frames not 4-byte aligned", who);
     int rc = check_shape(who, rows, T, J, bins);
     if (rc != EG_OK) return rc;
-    EG_REQUIRE(draws >= 1 && rows % draws == 0, EG_ERR_BAD_ARG, "%s: rows=%d is not a multiple of draws=%d", who, rows, draws);
-    EG_REQUIRE(frame_unit >= 1, EG_ERR_BAD_ARG, "%s: frame_unit=%d (need >= 1)", who, frame_unit);
+    rc = egi_check_rows(who, rows, T, nullptr, d_frames, false, draws, frame_unit, 0, "");
+    if (rc != EG_OK) return rc;
     EG_REQUIRE(isfinite(fps) && fps > 0.0, EG_ERR_BAD_ARG, "%s: fps=%g (finite and > 0)", who, fps);
-    EG_REQUIRE((d_frames == nullptr) == (frames == nullptr), EG_ERR_BAD_ARG,
-               "%s: frames (host) and d_frames (device) go together: the counts are checked on the host copy", who);
-    if (frames) {
-        for (int u = 0; u < rows / draws; ++u) {
-            const long long v = (long long)frames[u] * frame_unit, n = v < 0 ? 0 : (v > T ? T : v);
-            EG_REQUIRE(n >= 4, EG_ERR_BAD_ARG, "%s: recording %d has %lld valid frames < 4 (the jerk reads four positions)", who, u, n);
-        }
-    }
+    rc = egi_check_rows(who, rows, T, frames, d_frames, true, draws, frame_unit, 4, "4 (the jerk reads four positions)");
+    if (rc != EG_OK) return rc;
     const long long tiles = tiles_of(T), need = 8ll * rows * tiles * 3 * J;
     EG_REQUIRE(workspace_bytes >= need, EG_ERR_BAD_ARG, "%s: workspace of %lld bytes, need %lld (eg_kin_workspace_bytes)", who,
                (long long)workspace_bytes, need);

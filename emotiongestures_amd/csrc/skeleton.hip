@@ -22,7 +22,7 @@
 //   Euler channels (eg_articulate_euler, eg_articulate_rot6d_euler): the same tracks -> the angles of every joint's BVH rotation channels, on the
 //             articulate kernel's tile walk without the level walk, and the elementwise inverse; see the section further down.  The Euler
 //             filter over the angles is csrc/euler.hip.
-#include "common.h"
+#include "rows.h"
 #include <math.h>
 
 namespace {
@@ -53,7 +53,7 @@ struct Args {
 
 // Floats [g0, g1) of base (16-byte aligned; `total` floats in all) -> lds[g - (g0 & ~3)].  Whole quads: the floats before g0 and after g1 that
 // share a quad with the span are copied too (never used); nothing past `total` is read.
-__device__ __forceinline__ void stage_span(const float* __restrict__ base, long long g0, long long g1, long long total, float* lds) {
+__device__ __forceinline__ void stage_quads(const float* __restrict__ base, long long g0, long long g1, long long total, float* lds) {
     const long long lo4 = g0 & ~3ll;
     for (long long q = lo4 + 4ll * threadIdx.x; q < g1; q += 4ll * THREADS) {
         f4 v;
@@ -88,12 +88,6 @@ __device__ __forceinline__ void store_range(float* __restrict__ base, long long 
     }
 }
 
-__device__ __forceinline__ int valid_frames(const Args& a, int b) {
-    if (!a.frames) return a.T;
-    const long long v = (long long)a.frames[b / a.draws] * a.frame_unit;
-    return (int)(v < 0 ? 0 : (v > a.T ? a.T : v));
-}
-
 __device__ __forceinline__ void load_mean(const Args& a, float* mn) {
     if (a.mean)
         for (int r = threadIdx.x; r < 3 * a.K; r += THREADS) mn[r] = a.mean[r];
@@ -124,7 +118,7 @@ __device__ __forceinline__ Tile tile_of(const Args& a, long long T_out) {
     const int b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
     const long long k0 = (long long)tile * TILE;
     const int cnt = (int)(T_out - k0 < TILE ? T_out - k0 : TILE);
-    const int n = valid_frames(a, b);
+    const int n = egi_valid_frames(a.frames, b / a.draws, a.frame_unit, a.T);
     const long long n_out = NATIVE ? n : out_frames(n, a.L, a.M);
     const long long live = n_out - k0 < 0 ? 0 : (n_out - k0 < cnt ? n_out - k0 : cnt);
     return {b, k0, cnt, n, live, (int)live};
@@ -174,7 +168,7 @@ __device__ __forceinline__ float* stage_pass(const Args& a, const Tile& t, const
     const int D = 3 * a.K;
     p = w.pass(i, t.live);
     const long long g0 = ((long long)t.b * a.T + p.s_base) * D;
-    stage_span(a.src, g0, g0 + (long long)p.nslots * D, (long long)a.B * a.T * D, xin);
+    stage_quads(a.src, g0, g0 + (long long)p.nslots * D, (long long)a.B * a.T * D, xin);
     __syncthreads();
     return xin + (int)(g0 & 3);
 }
@@ -245,7 +239,7 @@ __global__ __launch_bounds__(THREADS) void skeleton_dir_vec_kernel(const Args a)
     const Head h = load_head(a, lds);
     const bool has_mean = a.mean != nullptr;
     const long long g0 = ((long long)t.b * a.T + t.k0) * J3;
-    stage_span(a.src, g0, g0 + (long long)t.live * J3, (long long)a.B * a.T * J3, pin);
+    stage_quads(a.src, g0, g0 + (long long)t.live * J3, (long long)a.B * a.T * J3, pin);
     __syncthreads();
     const float* p = pin + (int)(g0 & 3);
     store_range(a.dst, out0, D, out0, out0 + (long long)t.live * D, [&](int fr, int r) {
@@ -716,7 +710,7 @@ int reduce_rate(const char* who, int& L, int& M) {
 }
 
 int common_checks(const char* who, const void* src, const void* dst, int B, int T, const int32_t* parents, const int32_t* children,
-                  const float* lengths, int K, const void* d_table, int draws, int frame_unit, const void* d_mean) {
+                  const float* lengths, int K, const void* d_table, const int32_t* d_frames, int draws, int frame_unit, const void* d_mean) {
     EG_REQUIRE(src, EG_ERR_BAD_ARG, "%s: null input", who);
     EG_REQUIRE(dst, EG_ERR_BAD_ARG, "%s: null output", who);
     EG_REQUIRE(d_table, EG_ERR_BAD_ARG, "%s: null d_table", who);
@@ -726,9 +720,7 @@ int common_checks(const char* who, const void* src, const void* dst, int B, int 
     EG_REQUIRE((reinterpret_cast<uintptr_t>(d_table) & 3u) == 0 && (reinterpret_cast<uintptr_t>(d_mean) & 3u) == 0, EG_ERR_ALIGN,
                "%s: d_table / d_mean not 4-byte aligned", who);
     EG_REQUIRE(B >= 1 && T >= 1, EG_ERR_BAD_ARG, "%s: rows=%d frames=%d (need >= 1)", who, B, T);
-    EG_REQUIRE(draws >= 1 && B % draws == 0, EG_ERR_BAD_ARG, "%s: rows=%d is not a multiple of draws=%d", who, B, draws);
-    EG_REQUIRE(frame_unit >= 1, EG_ERR_BAD_ARG, "%s: frame_unit=%d (need >= 1)", who, frame_unit);
-    return EG_OK;
+    return egi_check_rows(who, B, T, nullptr, d_frames, false, draws, frame_unit, 0, "");
 }
 
 // What eg_skeleton_joints and eg_skeleton_rotations check behind their own arguments, in the header's order -- the rate, out_stride, the grid
@@ -794,7 +786,7 @@ extern "C" int eg_skeleton_joints(const float* track, int32_t rows, int32_t T, c
                                   int32_t bones, const void* d_table, const int32_t* d_frames, int32_t draws, int32_t frame_unit,
                                   const float* d_mean, int32_t unit, int32_t L, int32_t M, float* joints, int64_t out_stride, void* stream) {
     const char* who = "eg_skeleton_joints";
-    int rc = common_checks(who, track, joints, rows, T, parents, children, lengths, bones, d_table, draws, frame_unit, d_mean);
+    int rc = common_checks(who, track, joints, rows, T, parents, children, lengths, bones, d_table, d_frames, draws, frame_unit, d_mean);
     if (rc != EG_OK) return rc;
     Args a = {track, static_cast<const int*>(d_table), d_frames, d_mean, joints, rows, T, bones, draws, frame_unit};
     rc = forward_args(who, a, L, M, out_stride, 3 * (bones + 1));
@@ -809,7 +801,7 @@ extern "C" int eg_skeleton_dir_vec(const float* joints, int32_t rows, int32_t T,
                                    int32_t bones, const void* d_table, const int32_t* d_frames, int32_t draws, int32_t frame_unit,
                                    const float* d_mean, float* dir_vec, void* stream) {
     const char* who = "eg_skeleton_dir_vec";
-    int rc = common_checks(who, joints, dir_vec, rows, T, parents, children, lengths, bones, d_table, draws, frame_unit, d_mean);
+    int rc = common_checks(who, joints, dir_vec, rows, T, parents, children, lengths, bones, d_table, d_frames, draws, frame_unit, d_mean);
     if (rc != EG_OK) return rc;
     Args a = {joints, static_cast<const int*>(d_table), d_frames, d_mean, dir_vec, rows, T, bones, draws, frame_unit};
     rc = inverse_args(who, a, 3 * (bones + 1), TF);
@@ -868,7 +860,7 @@ extern "C" int eg_skeleton_rotations(const float* track, int32_t rows, int32_t T
                                      int32_t draws, int32_t frame_unit, const float* d_mean, int32_t space, int32_t L, int32_t M,
                                      float* rotations, int64_t out_stride, void* stream) {
     const char* who = "eg_skeleton_rotations";
-    int rc = common_checks(who, track, rotations, rows, T, parents, children, lengths, bones, d_levels, draws, frame_unit, d_mean);
+    int rc = common_checks(who, track, rotations, rows, T, parents, children, lengths, bones, d_levels, d_frames, draws, frame_unit, d_mean);
     if (rc != EG_OK) return rc;
     rc = check_rest(who, rest, bones);
     if (rc != EG_OK) return rc;
@@ -900,13 +892,12 @@ int check_body(const char* who, const int32_t* parents, const float* offsets, in
 }
 
 // What both calls check about their rows: the counterpart of common_checks without a bone table.
-int rows_checks(const char* who, const void* src, int B, int T, int draws, int frame_unit, const void* d_mean, int basis) {
+int rows_checks(const char* who, const void* src, int B, int T, const int32_t* d_frames, int draws, int frame_unit, const void* d_mean, int basis) {
     EG_REQUIRE(src, EG_ERR_BAD_ARG, "%s: null input", who);
     EG_REQUIRE(eg_aligned16(src), EG_ERR_ALIGN, "%s: input not 16-byte aligned", who);
     EG_REQUIRE((reinterpret_cast<uintptr_t>(d_mean) & 3u) == 0, EG_ERR_ALIGN, "%s: d_mean not 4-byte aligned", who);
     EG_REQUIRE(B >= 1 && T >= 1, EG_ERR_BAD_ARG, "%s: rows=%d frames=%d (need >= 1)", who, B, T);
-    EG_REQUIRE(draws >= 1 && B % draws == 0, EG_ERR_BAD_ARG, "%s: rows=%d is not a multiple of draws=%d", who, B, draws);
-    EG_REQUIRE(frame_unit >= 1, EG_ERR_BAD_ARG, "%s: frame_unit=%d (need >= 1)", who, frame_unit);
+    if (int rc = egi_check_rows(who, B, T, nullptr, d_frames, false, draws, frame_unit, 0, "")) return rc;
     EG_REQUIRE(basis == EG_ARTICULATE_BASIS_ROWS || basis == EG_ARTICULATE_BASIS_COLUMNS, EG_ERR_BAD_ARG, "%s: basis=%d (0: rows, 1: columns)", who,
                basis);
     return EG_OK;
@@ -954,7 +945,7 @@ extern "C" int eg_articulate_forward(const float* track, int32_t rows, int32_t T
     EG_REQUIRE(d_table, EG_ERR_BAD_ARG, "%s: null d_table", who);
     int rc = check_body(who, parents, offsets, joints);
     if (rc != EG_OK) return rc;
-    rc = rows_checks(who, track, rows, T, draws, frame_unit, d_mean, basis);
+    rc = rows_checks(who, track, rows, T, d_frames, draws, frame_unit, d_mean, basis);
     if (rc != EG_OK) return rc;
     EG_REQUIRE(eg_aligned16(out_joints) && eg_aligned16(out_rotations), EG_ERR_ALIGN, "%s: out_joints / out_rotations not 16-byte aligned", who);
     EG_REQUIRE((reinterpret_cast<uintptr_t>(d_table) & 3u) == 0, EG_ERR_ALIGN, "%s: d_table not 4-byte aligned", who);
@@ -975,7 +966,7 @@ extern "C" int eg_articulate_rot6d(const float* quat, int32_t rows, int32_t T, i
     const char* who = "eg_articulate_rot6d";
     EG_REQUIRE(rot6d, EG_ERR_BAD_ARG, "%s: null output", who);
     EG_REQUIRE(joints >= 1 && joints <= MAX_J, EG_ERR_UNSUPPORTED, "%s: joints=%d (1..%d)", who, joints, MAX_J);
-    int rc = rows_checks(who, quat, rows, T, draws, frame_unit, d_mean, basis);
+    int rc = rows_checks(who, quat, rows, T, d_frames, draws, frame_unit, d_mean, basis);
     if (rc != EG_OK) return rc;
     EG_REQUIRE(eg_aligned16(rot6d), EG_ERR_ALIGN, "%s: output not 16-byte aligned", who);
     ArtArgs k = {{quat, nullptr, d_frames, d_mean, rot6d, rows, T, 2 * joints, draws, frame_unit}, nullptr, joints, basis == EG_ARTICULATE_BASIS_COLUMNS};
@@ -1005,7 +996,7 @@ extern "C" int eg_articulate_euler(const float* track, int32_t rows, int32_t T, 
     EG_REQUIRE(euler, EG_ERR_BAD_ARG, "%s: null output", who);
     int rc = check_orders(who, orders, d_orders, joints);
     if (rc != EG_OK) return rc;
-    rc = rows_checks(who, track, rows, T, draws, frame_unit, d_mean, basis);
+    rc = rows_checks(who, track, rows, T, d_frames, draws, frame_unit, d_mean, basis);
     if (rc != EG_OK) return rc;
     EG_REQUIRE(eg_aligned16(euler), EG_ERR_ALIGN, "%s: output not 16-byte aligned", who);
     EG_REQUIRE((long long)rows * T * 6 * joints < (1ll << 40), EG_ERR_UNSUPPORTED, "%s: rows=%d x frames=%d: index range", who, rows, T);
@@ -1025,7 +1016,7 @@ extern "C" int eg_articulate_rot6d_euler(const float* euler, int32_t rows, int32
     EG_REQUIRE(rot6d, EG_ERR_BAD_ARG, "%s: null output", who);
     int rc = check_orders(who, orders, d_orders, joints);
     if (rc != EG_OK) return rc;
-    rc = rows_checks(who, euler, rows, T, draws, frame_unit, d_mean, basis);
+    rc = rows_checks(who, euler, rows, T, d_frames, draws, frame_unit, d_mean, basis);
     if (rc != EG_OK) return rc;
     EG_REQUIRE(eg_aligned16(rot6d), EG_ERR_ALIGN, "%s: output not 16-byte aligned", who);
     EulArgs k = {{euler, nullptr, d_frames, d_mean, rot6d, rows, T, 2 * joints, draws, frame_unit}, static_cast<const int*>(d_orders), joints,

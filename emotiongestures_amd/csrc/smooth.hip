@@ -15,7 +15,7 @@
 // frame index) and immediate offsets; a row's first and last tiles clamp every read into the staged range.  The at most K - 1 head and tail frames of a row read their window from LDS term by term with a
 // wave-uniform table row.  Consecutive lanes hold consecutive columns: LDS and global accesses are conflict-free and coalesced.  One owning
 // thread per output element, plain vector stores, no atomics; the grid depends on (rows, T, D) only.
-#include "common.h"
+#include "rows.h"
 #include <math.h>
 
 // The arithmetic of one output element: c(j) the j-th weight, x(j) the j-th sample of the window.
@@ -46,13 +46,6 @@ struct Args {
     int B, T, D, draws, frame_unit, ftiles, ctiles;
 };
 
-__device__ __forceinline__ int valid_frames(const Args& a, int b, int K) {
-    if (!a.frames) return a.T;
-    const long long v = (long long)a.frames[b / a.draws] * a.frame_unit;
-    const int n = (int)(v < 0 ? 0 : (v > a.T ? a.T : v));
-    return n < K ? 0 : n;                               // the host refuses n < K; a device count that differs from it: zeros, nothing out of range
-}
-
 template <int K>
 __global__ __launch_bounds__(THREADS) void smooth_tracks_kernel(const Args a) {
     constexpr int HALF = K / 2;
@@ -65,7 +58,7 @@ __global__ __launch_bounds__(THREADS) void smooth_tracks_kernel(const Args a) {
     const int ft = blk % a.ftiles, b = blk / a.ftiles;
     const int c0 = ct * TC, w = min(TC, D - c0);
     const int k0 = ft * TF, cnt = min(TF, a.T - k0);
-    const int n = valid_frames(a, b, K);
+    const int n = egi_valid_frames(a.frames, b / a.draws, a.frame_unit, a.T, K);    // the host refuses n < K
     const int live = max(0, min(cnt, n - k0));
     const long long row0 = (long long)b * a.T * D;
     const int col = lane;
@@ -318,11 +311,10 @@ extern "C" int eg_smooth_tracks(const float* track, int32_t rows, int32_t T, int
     EG_REQUIRE(out, EG_ERR_BAD_ARG, "%s: null out", who);
     EG_REQUIRE(d_table, EG_ERR_BAD_ARG, "%s: null d_table", who);
     EG_REQUIRE(eg_aligned16(track) && eg_aligned16(out) && eg_aligned16(d_table), EG_ERR_ALIGN, "%s: track / out / d_table not 16-byte aligned", who);
-    EG_REQUIRE((reinterpret_cast<uintptr_t>(d_frames) & 3u) == 0, EG_ERR_ALIGN, "%s: d_frames not 4-byte aligned", who);
     EG_REQUIRE(rows >= 1 && T >= 1 && D >= 1, EG_ERR_BAD_ARG, "%s: rows=%d frames=%d columns=%d (need >= 1)", who, rows, T, D);
-    EG_REQUIRE(draws >= 1 && rows % draws == 0, EG_ERR_BAD_ARG, "%s: rows=%d is not a multiple of draws=%d", who, rows, draws);
-    EG_REQUIRE(frame_unit >= 1, EG_ERR_BAD_ARG, "%s: frame_unit=%d (need >= 1)", who, frame_unit);
-    int rc = check_window(who, K);
+    int rc = egi_check_rows(who, rows, T, nullptr, d_frames, false, draws, frame_unit, 0, "");
+    if (rc != EG_OK) return rc;
+    rc = check_window(who, K);
     if (rc != EG_OK) return rc;
     const long long elems = (long long)rows * T * D;
     const long long ftiles = ((long long)T + TF - 1) / TF, ctiles = ((long long)D + TC - 1) / TC;
@@ -332,16 +324,11 @@ extern "C" int eg_smooth_tracks(const float* track, int32_t rows, int32_t T, int
         const uintptr_t x0 = reinterpret_cast<uintptr_t>(track), y0 = reinterpret_cast<uintptr_t>(out), nb = (uintptr_t)elems * 4u;
         EG_REQUIRE(x0 + nb <= y0 || y0 + nb <= x0, EG_ERR_BAD_ARG, "%s: out overlaps track (every output reads %d input frames: not in place)", who, K);
     }
-    EG_REQUIRE((d_frames == nullptr) == (frames == nullptr), EG_ERR_BAD_ARG,
-               "%s: frames (host) and d_frames (device) go together: the counts are checked on the host copy", who);
-    if (frames) {
-        for (int u = 0; u < rows / draws; ++u) {
-            const long long v = (long long)frames[u] * frame_unit, n = v < 0 ? 0 : (v > T ? T : v);
-            EG_REQUIRE(n >= K, EG_ERR_BAD_ARG, "%s: recording %d has %lld valid frames < window=%d (there is no shrinking window)", who, u, n, K);
-        }
-    } else {
-        EG_REQUIRE(T >= K, EG_ERR_BAD_ARG, "%s: frames=%d < window=%d (there is no shrinking window)", who, T, K);
-    }
+    char why[64];
+    snprintf(why, sizeof why, "window=%d (there is no shrinking window)", K);
+    rc = egi_check_rows(who, rows, T, frames, d_frames, true, draws, frame_unit, K, why);
+    if (rc != EG_OK) return rc;
+    EG_REQUIRE(frames || T >= K, EG_ERR_BAD_ARG, "%s: frames=%d < window=%d (there is no shrinking window)", who, T, K);
     const Args a = {track, d_table, d_frames, out, rows, T, D, draws, frame_unit, (int)ftiles, (int)ctiles};
     const dim3 grid((unsigned)(ftiles * ctiles * rows));
     hipStream_t st = static_cast<hipStream_t>(stream);

@@ -37,7 +37,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from ._host import BoundedCache, host_ptr, int_list, ptr as _ptr, stream as _stream
+from ._host import BoundedCache, host_ptr, int_list, ptr as _ptr, sized, stream as _stream
 
 __all__ = ["window_plan", "window_logits", "emotion_votes", "emotion_of_tracks", "EmotionAccuracy", "vote_workspace_bytes", "CHUNK_WINDOWS",
            "MAX_CLASSES"]
@@ -277,11 +277,7 @@ def _label_index(labels, U: int, R: int, C: int, who: str):
 def vote_workspace_bytes(plan_or_counts, draws: int, classes: int) -> int:
     """Bytes of ``emotion_votes``' workspace (eg_emotion_vote_workspace_bytes; host only)."""
     _a, h, _t, _keep = _counts_of(plan_or_counts, None)
-    lib = L.load()
-    n = int(lib.eg_emotion_vote_workspace_bytes(h, len(_a), int(draws), int(classes)))
-    if n <= 0:
-        raise L.EgError(f"eg_emotion_vote_workspace_bytes: refused ({lib.eg_last_error().decode()})")
-    return n
+    return sized("eg_emotion_vote_workspace_bytes", h, len(_a), int(draws), int(classes))
 
 
 def _new_out(U, R, C, N, dev, with_labels):

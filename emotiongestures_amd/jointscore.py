@@ -27,8 +27,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._host import host_ptr, ptr as _ptr, stream as _stream
-from .skeleton import _dev32, _frames_dev, _frames_list, _is_cuda, _lead, _per_row
+from . import _rows as RW
+from ._host import device_bytes, host_ptr, ptr as _ptr, stream as _stream
 
 __all__ = ["srgr_of_joints", "l1div_of_tracks", "launch_srgr", "launch_l1div", "SemanticTargets", "SRGR", "L1div", "MAX_JOINTS", "MAX_COLS",
            "TILE_FRAMES", "SCALE"]
@@ -71,14 +71,6 @@ def _l1_host(x: np.ndarray, frames: Sequence[int]):
 
 
 # ---- the launches --------------------------------------------------------------------------------------------------------------------------
-def _workspace(fn_name: str, device, *shape) -> torch.Tensor:
-    lib = L.load()
-    nbytes = int(getattr(lib, fn_name)(*shape))
-    if nbytes <= 0:
-        raise L.EgError(f"{fn_name}: refused ({lib.eg_last_error().decode()})")
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
-
-
 def launch_srgr(joints: torch.Tensor, targets: torch.Tensor, semantic: Optional[torch.Tensor] = None, frames: Optional[Sequence[int]] = None,
                 d_frames: Optional[torch.Tensor] = None, draws: int = 1, frame_unit: int = 1, threshold: float = 0.1, scale: float = SCALE,
                 workspace: Optional[torch.Tensor] = None, out=None):
@@ -90,12 +82,12 @@ def launch_srgr(joints: torch.Tensor, targets: torch.Tensor, semantic: Optional[
     rows, T, J, _three = joints.shape
     dev = joints.device
     if workspace is None:
-        workspace = _workspace("eg_srgr_workspace_bytes", dev, rows, T, J)
+        workspace = device_bytes("eg_srgr_workspace_bytes", dev, rows, T, J)
     if out is None:
         out = (torch.empty(rows, dtype=torch.float64, device=dev), torch.empty(rows, dtype=torch.float64, device=dev),
                torch.empty(rows, J, dtype=torch.int32, device=dev))
     srgr, recall, hits = out
-    fr = None if frames is None else np.ascontiguousarray(frames, np.int32)
+    fr = RW.counts32(frames)
     L.check(L.load().eg_srgr_tracks(_ptr(joints), _ptr(targets), _ptr(semantic), rows, T, J, host_ptr(fr), _ptr(d_frames), int(draws),
                                     int(frame_unit), float(threshold), float(scale), _ptr(workspace), int(workspace.numel()), _ptr(srgr),
                                     _ptr(recall), _ptr(hits), _stream(dev)), "eg_srgr_tracks")
@@ -110,28 +102,18 @@ def launch_l1div(x: torch.Tensor, frames: Optional[Sequence[int]] = None, d_fram
     rows, T, D = x.shape
     dev = x.device
     if workspace is None:
-        workspace = _workspace("eg_l1div_workspace_bytes", dev, rows, T, D)
+        workspace = device_bytes("eg_l1div_workspace_bytes", dev, rows, T, D)
     if out is None:
         out = (torch.empty(rows, D, dtype=torch.float64, device=dev), torch.empty(rows, dtype=torch.float64, device=dev),
                torch.empty(rows, dtype=torch.float64, device=dev))
     mean, l1_sum, l1div = out
-    fr = None if frames is None else np.ascontiguousarray(frames, np.int32)
+    fr = RW.counts32(frames)
     L.check(L.load().eg_l1div_tracks(_ptr(x), rows, T, D, host_ptr(fr), _ptr(d_frames), int(draws), int(frame_unit), _ptr(workspace),
                                      int(workspace.numel()), _ptr(mean), _ptr(l1_sum), _ptr(l1div), _stream(dev)), "eg_l1div_tracks")
     return mean, l1_sum, l1div
 
 
 # ---- the front ends ------------------------------------------------------------------------------------------------------------------------
-def _valid(frames, U: int, T: int, who: str):
-    """``frames`` checked -> (the list or None, the counts per recording); a recording without a valid frame is refused by name."""
-    fr = _frames_list(frames, U, T, who)
-    per = fr if fr is not None else [T] * U
-    empty = [u for u, n in enumerate(per) if n < 1]
-    if empty:
-        raise L.EgError(f"{who}: recording {empty[0]} has {per[empty[0]]} valid frames < 1")
-    return fr, per
-
-
 def _finite(value, name: str, who: str) -> float:
     v = float(value)
     if not np.isfinite(v):
@@ -139,12 +121,8 @@ def _finite(value, name: str, who: str) -> float:
     return v
 
 
-def _host32(x) -> np.ndarray:
-    return np.asarray(x.detach().numpy() if isinstance(x, torch.Tensor) else x, np.float32)
-
-
 def _same_side(a, b, name: str, who: str):
-    if b is not None and _is_cuda(a) != _is_cuda(b):
+    if b is not None and RW.is_cuda(a) != RW.is_cuda(b):
         raise L.EgError(f"{who}: joints and {name} are not on one side (a CUDA tensor goes with CUDA tensors, host data with host data)")
 
 
@@ -165,7 +143,7 @@ def srgr_of_joints(joints, targets, semantic=None, frames=None, threshold: float
     shape = tuple(joints.shape)
     if len(shape) < 3 or shape[-1] != 3 or not 1 <= shape[-2] <= MAX_JOINTS or shape[-3] < 1:
         raise L.EgError(f"{who}: joints shape {shape}: need [..., T >= 1, J, 3] with 1 <= J <= {MAX_JOINTS}")
-    lead, U, R = _lead(shape, 3, who)
+    lead, U, R = RW.lead_axes(shape, 3, who)
     T, J = shape[-3], shape[-2]
     want = lead[:1] + (T, J, 3)
     if tuple(targets.shape) != want:
@@ -175,21 +153,19 @@ def srgr_of_joints(joints, targets, semantic=None, frames=None, threshold: float
     _same_side(joints, targets, "targets", who)
     _same_side(joints, semantic, "semantic", who)
     threshold, scale = _finite(threshold, "threshold", who), _finite(scale, "scale", who)
-    fr, per = _valid(frames, U, T, who)
-    if _is_cuda(joints):
-        x = _dev32(joints).reshape(U * R, T, J, 3)
-        dev = x.device
-        g = _dev32(targets.to(dev)).reshape(U, T, J, 3)
-        w = None if semantic is None else _dev32(semantic.to(dev)).reshape(U, T)
-        srgr, recall, hits = launch_srgr(x, g, w, fr, _frames_dev(fr, dev), R, 1, threshold, scale)
-    else:
-        w = None if semantic is None else _host32(semantic).reshape(U, T)
-        srgr, recall, hits = _srgr_host(_host32(joints).reshape(U * R, T, J, 3), _host32(targets).reshape(U, T, J, 3), w,
-                                        _per_row(fr, U, R, T), R, threshold, scale)
-        if isinstance(joints, torch.Tensor):
-            srgr, recall, hits = torch.from_numpy(srgr), torch.from_numpy(recall), torch.from_numpy(hits)
+    def on_device(x, fr, d_frames, _R):
+        g = RW.dev32(targets.to(x.device)).reshape(U, T, J, 3)
+        w = None if semantic is None else RW.dev32(semantic.to(x.device)).reshape(U, T)
+        return launch_srgr(x, g, w, fr, d_frames, R, 1, threshold, scale)
+
+    def on_host(x, per_row):
+        w = None if semantic is None else RW.host32(semantic).reshape(U, T)
+        return _srgr_host(x, RW.host32(targets).reshape(U, T, J, 3), w, per_row, R, threshold, scale)
+
+    fe = RW.front(joints, 3, frames, who, on_device, on_host, 1, "1", RW.host32)
+    srgr, recall, hits = fe.res
     return {"srgr": srgr.reshape(lead), "recall": recall.reshape(lead), "hits": hits.reshape(lead + (J,)),
-            "frames": np.asarray(_per_row(fr, U, R, T), np.int64).reshape(lead)}
+            "frames": np.asarray(fe.per_row, np.int64).reshape(lead)}
 
 
 def l1div_of_tracks(x, frames=None) -> dict:
@@ -202,18 +178,10 @@ def l1div_of_tracks(x, frames=None) -> dict:
     shape = tuple(x.shape)
     if len(shape) < 2 or not 1 <= shape[-1] <= MAX_COLS or shape[-2] < 1:
         raise L.EgError(f"{who}: shape {shape}: need [..., T >= 1, D] with 1 <= D <= {MAX_COLS}")
-    lead, U, R = _lead(shape, 2, who)
-    T, D = shape[-2], shape[-1]
-    fr, _per = _valid(frames, U, T, who)
-    if _is_cuda(x):
-        v = _dev32(x).reshape(U * R, T, D)
-        mean, l1_sum, l1div = launch_l1div(v, fr, _frames_dev(fr, v.device), R)
-    else:
-        mean, l1_sum, l1div = _l1_host(_host32(x).reshape(U * R, T, D), _per_row(fr, U, R, T))
-        if isinstance(x, torch.Tensor):
-            mean, l1_sum, l1div = torch.from_numpy(mean), torch.from_numpy(l1_sum), torch.from_numpy(l1div)
-    return {"l1div": l1div.reshape(lead), "l1_sum": l1_sum.reshape(lead), "mean": mean.reshape(lead + (D,)),
-            "frames": np.asarray(_per_row(fr, U, R, T), np.int64).reshape(lead)}
+    fe = RW.front(x, 2, frames, who, lambda v, fr, d_frames, R: launch_l1div(v, fr, d_frames, R), _l1_host, 1, "1", RW.host32)
+    (mean, l1_sum, l1div), lead = fe.res, fe.lead
+    return {"l1div": l1div.reshape(lead), "l1_sum": l1_sum.reshape(lead), "mean": mean.reshape(lead + (shape[-1],)),
+            "frames": np.asarray(fe.per_row, np.int64).reshape(lead)}
 
 
 class SemanticTargets:

@@ -29,8 +29,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._host import BoundedCache, host_ptr, ptr as _ptr, stream as _stream
-from .skeleton import _dev32, _frames_dev, _frames_list, _is_cuda, _lead, _per_row
+from . import _rows as RW
+from ._host import BoundedCache, device_bytes, host_ptr, ptr as _ptr, stream as _stream
 
 __all__ = ["SpeedBins", "kinematics_of_joints", "launch_kinematics", "hellinger", "MAX_JOINTS", "MAX_BINS", "TILE_FRAMES"]
 
@@ -102,21 +102,17 @@ def launch_kinematics(joints: torch.Tensor, bins: SpeedBins, frames: Optional[Se
     ``d_frames`` their device int32 copy, both or neither.  ``workspace``: a uint8 tensor of eg_kin_workspace_bytes; ``out``: ``(mean,
     hist)`` to write into; ``edges2``: a device float64 table ``[B + 1]`` in place of ``bins.table(device)``."""
     rows, T, J, _three = joints.shape
-    lib = L.load()
     table = bins.table(joints.device) if edges2 is None else edges2
     B = int(table.numel()) - 1
     if workspace is None:
-        nbytes = int(lib.eg_kin_workspace_bytes(rows, T, J, B))
-        if nbytes <= 0:
-            raise L.EgError(f"eg_kin_workspace_bytes: refused ({lib.eg_last_error().decode()})")
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=joints.device)
+        workspace = device_bytes("eg_kin_workspace_bytes", joints.device, rows, T, J, B)
     if out is None:
         out = (torch.empty(rows, 3, J, dtype=torch.float64, device=joints.device),
                torch.empty(rows, J, B + 1, dtype=torch.int32, device=joints.device))
     mean, hist = out
-    fr = None if frames is None else np.ascontiguousarray(frames, np.int32)
-    L.check(lib.eg_kin_stats(_ptr(joints), rows, T, J, host_ptr(fr), _ptr(d_frames), int(draws), int(frame_unit), bins.fps, _ptr(table), B,
-                             _ptr(workspace), int(workspace.numel()), _ptr(mean), _ptr(hist), _stream(joints.device)), "eg_kin_stats")
+    fr = RW.counts32(frames)
+    L.check(L.load().eg_kin_stats(_ptr(joints), rows, T, J, host_ptr(fr), _ptr(d_frames), int(draws), int(frame_unit), bins.fps, _ptr(table), B,
+                                  _ptr(workspace), int(workspace.numel()), _ptr(mean), _ptr(hist), _stream(joints.device)), "eg_kin_stats")
     return mean, hist
 
 
@@ -137,20 +133,9 @@ def kinematics_of_joints(joints, fps, frames=None, edges=None) -> dict:
     shape = tuple(joints.shape)
     if len(shape) < 3 or shape[-1] != 3 or not 1 <= shape[-2] <= MAX_JOINTS:
         raise L.EgError(f"{who}: joints shape {shape}: need [..., T, J, 3] with 1 <= J <= {MAX_JOINTS}")
-    lead, U, R = _lead(shape, 3, who)
-    T, J = shape[-3], shape[-2]
-    fr = _frames_list(frames, U, T, who)
-    short = [(u, n) for u, n in enumerate(fr if fr is not None else [T] * U) if n < 4]
-    if short:
-        raise L.EgError(f"{who}: recording {short[0][0]} has {short[0][1]} valid frames < 4 (the jerk reads four positions)")
-    if _is_cuda(joints):
-        x = _dev32(joints).reshape(U * R, T, J, 3)
-        mean, hist = launch_kinematics(x, bins, fr, _frames_dev(fr, x.device), R)
-    else:
-        x = joints.detach().numpy() if isinstance(joints, torch.Tensor) else joints
-        mean, hist = _stats_host(np.asarray(x, np.float32).reshape(U * R, T, J, 3), _per_row(fr, U, R, T), bins.edges2, bins.fps)
-        if isinstance(joints, torch.Tensor):
-            mean, hist = torch.from_numpy(mean), torch.from_numpy(hist)
+    fe = RW.front(joints, 3, frames, who, lambda x, fr, d_frames, R: launch_kinematics(x, bins, fr, d_frames, R),
+                  lambda x, per_row: _stats_host(x, per_row, bins.edges2, bins.fps), 4, "4 (the jerk reads four positions)", RW.host32)
+    (mean, hist), lead, J = fe.res, fe.lead, shape[-2]
     res = {name: mean[:, k].reshape(lead + (J,)) for k, name in enumerate(NAMES)}
     res["speed_hist"] = hist[:, :, :bins.bins].reshape(lead + (J, bins.bins))
     res["speed_over"] = hist[:, :, bins.bins].reshape(lead + (J,))

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._host import BoundedCache, host_ptr, int_list, ptr as _ptr, stream as _stream
+from ._host import BoundedCache, host_ptr, int_list, ptr as _ptr, sized, stream as _stream
 
 __all__ = ["ratio", "plan", "out_length", "stream_delay", "resample_audio", "StreamResampler", "TILE", "MAX_FACTOR"]
 
@@ -177,10 +177,7 @@ class StreamResampler:
         self.device = dev
         self._lib = L.load()
         self._bank = _Bank.get(self.rate_in, self.rate_out, dev)
-        nbytes = int(self._lib.eg_resample_stream_state_bytes(self.U, self.rate_in, self.rate_out))
-        if nbytes <= 0:
-            raise L.EgError(f"eg_resample_stream_state_bytes: refused ({self._lib.eg_last_error().decode()})")
-        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        self.state = torch.zeros(sized("eg_resample_stream_state_bytes", self.U, self.rate_in, self.rate_out), dtype=torch.uint8, device=dev)
         self.chunk = torch.zeros(self.U, self.hop_in, dtype=torch.float32, device=dev)
         self.ends = torch.full((self.U,), -1, dtype=torch.int32, device=dev)
         self.out = torch.zeros(self.U, self.hop_out, dtype=torch.float32, device=dev)

@@ -62,7 +62,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._host import BoundedCache, host_ptr, int_list, ptr as _ptr, stream as _stream
+from ._host import BoundedCache, host_ptr, ptr as _ptr, stream as _stream
+from ._rows import dev32, frames_dev, frames_list, front, host64, is_cuda, lead_axes, per_row
 
 __all__ = ["Skeleton", "RestPose", "ted_expressive", "joints_from_tracks", "dir_vec_from_joints", "rotations_from_tracks", "out_frames",
            "rate_ratio", "TILE_FRAMES", "MAX_BONES", "MAX_FACTOR", "JointTree", "joints_from_rot6d", "rotations_from_rot6d",
@@ -232,46 +233,6 @@ def out_frames(n: int, fps=None) -> int:
     return -(-int(n) * Lf // M)
 
 
-def _frames_list(frames, U: int, T: int, who: str) -> Optional[List[int]]:
-    if frames is None:
-        return None
-    fr = int_list([frames] if isinstance(frames, int) else frames)          # a bare int means one recording
-    if len(fr) != U:
-        raise L.EgError(f"{who}: frames has {len(fr)} entries for {U} recordings")
-    if any(v < 0 or v > T for v in fr):
-        raise L.EgError(f"{who}: frames {fr}: every value must be in [0, {T}]")
-    return fr
-
-
-def _frames_dev(fr: Optional[List[int]], device) -> Optional[torch.Tensor]:
-    return None if fr is None else torch.tensor(fr, dtype=torch.int32, device=device)
-
-
-def _lead(shape, n_tail: int, who: str):
-    """Leading axes ``()``, ``(U,)`` or ``(U, R)`` -> (U, R)."""
-    lead = tuple(shape[:-n_tail])
-    if len(lead) > 2:
-        raise L.EgError(f"{who}: shape {tuple(shape)}: at most two leading axes ([U, R, ...])")
-    U = lead[0] if lead else 1
-    R = lead[1] if len(lead) == 2 else 1
-    return lead, int(U), int(R)
-
-
-def _is_cuda(x) -> bool:
-    return isinstance(x, torch.Tensor) and x.is_cuda
-
-
-def _host64(x, who: str) -> np.ndarray:
-    if isinstance(x, torch.Tensor):
-        x = x.detach().cpu().numpy()
-    return np.asarray(x, np.float64)
-
-
-def _dev32(x: torch.Tensor) -> torch.Tensor:
-    x = x.detach().to(torch.float32).contiguous()
-    return x.clone() if x.data_ptr() % 16 else x                # a slice of a larger tensor may start anywhere
-
-
 def _mean_checked(m, D: int, who: str):                        # m: the flat mean, a tensor or an array; D: the body's pose_dim
     if len(m) != D:
         raise L.EgError(f"{who}: mean has {len(m)} values, the skeleton's tracks have {D}")
@@ -283,7 +244,7 @@ def _mean_dev(mean, D: int, device, who: str) -> Optional[torch.Tensor]:
 
 
 def _mean_host(mean, D: int, who: str) -> Optional[np.ndarray]:
-    return None if mean is None else _mean_checked(_host64(mean, who).reshape(-1), D, who)
+    return None if mean is None else _mean_checked(host64(mean, who).reshape(-1), D, who)
 
 
 # ---- the float64 path: the definition ------------------------------------------------------------------------------------------------------
@@ -451,10 +412,6 @@ def launch_rotations(track: torch.Tensor, sk: Skeleton, rest: RestPose, d_frames
 
 
 # ---- the public functions --------------------------------------------------------------------------------------------------------------------
-def _per_row(fr: Optional[List[int]], U: int, R: int, T: int) -> List[int]:
-    return [n for n in (fr if fr is not None else [T] * U) for _ in range(R)]
-
-
 def _body_checked(body, kind, who: str):
     if not isinstance(body, kind):
         raise L.EgError(f"{who}: {kind.noun} must be a {kind.__name__}, got {type(body).__name__}")
@@ -478,11 +435,11 @@ def _front(track, sk: Skeleton, frames, fps, who: str) -> SimpleNamespace:
     """The second half, behind a caller's own checks: the leading axes ``lead`` of the track (``()``, ``(U,)`` or ``(U, R)``), ``U``, ``R``,
     ``T``, the reduced ``ratio = (L, M)``, ``fr`` (``frames`` as a checked list, or None), ``t_out``, the valid source frames
     ``per_row [U * R]`` and the valid output frames ``n_out [U]``."""
-    lead, U, R = _lead(track.shape, 2, who)
+    lead, U, R = lead_axes(track.shape, 2, who)
     T = track.shape[-2]
     Lf, M = rate_ratio(fps, f"{who}: fps")
-    fr = _frames_list(frames, U, T, who)
-    return SimpleNamespace(lead=lead, U=U, R=R, T=T, ratio=(Lf, M), fr=fr, t_out=-(-T * Lf // M), per_row=_per_row(fr, U, R, T),
+    fr = frames_list(frames, U, T, who)
+    return SimpleNamespace(lead=lead, U=U, R=R, T=T, ratio=(Lf, M), fr=fr, t_out=-(-T * Lf // M), per_row=per_row(fr, U, R, T),
                            n_out=[-(-n * Lf // M) for n in (fr if fr is not None else [T] * U)])
 
 
@@ -499,11 +456,11 @@ def _forward(track, body, frames, mean, fps, who: str, tail: Tuple[int, int], on
     or ``on_host(v [U * R, T, D] float64, fe, mean64)`` for anything else, then ``_finish``."""
     fe = _front(track, body, frames, fps, who)
     D = body.pose_dim
-    if _is_cuda(track):
-        x = _dev32(track).reshape(fe.U * fe.R, fe.T, D)
-        res = on_device(x, fe, _frames_dev(fe.fr, x.device), _mean_dev(mean, D, x.device, who))
+    if is_cuda(track):
+        x = dev32(track).reshape(fe.U * fe.R, fe.T, D)
+        res = on_device(x, fe, frames_dev(fe.fr, x.device), _mean_dev(mean, D, x.device, who))
     else:
-        res = on_host(_host64(track, who).reshape(fe.U * fe.R, fe.T, D), fe, _mean_host(mean, D, who))
+        res = on_host(host64(track, who).reshape(fe.U * fe.R, fe.T, D), fe, _mean_host(mean, D, who))
     return _finish(res, track, fe, tail, frames, fps)
 
 
@@ -520,16 +477,8 @@ def _per_frame(x, n_tail: int, frames, who: str, tail: Tuple[int, ...], on_devic
     """The front end and the finish of the inverse and in-place functions, whose output has the input's frames: ``x [..., T, *]`` with
     ``n_tail`` axes from T on and up to two leading ones -> ``[..., T, *tail]`` from ``on_device(x [U * R, T, *] fp32, d_frames, R)`` for a
     CUDA tensor or ``on_host(x [U * R, T, *] float64, per_row)`` for anything else (tensor in: tensor out)."""
-    shape = tuple(x.shape)
-    lead, U, R = _lead(shape, n_tail, who)
-    T = shape[-n_tail]
-    fr = _frames_list(frames, U, T, who)
-    rows = (U * R,) + shape[-n_tail:]
-    if _is_cuda(x):
-        xd = _dev32(x).reshape(rows)
-        return on_device(xd, _frames_dev(fr, xd.device), R).reshape(lead + (T,) + tail)
-    res = on_host(_host64(x, who).reshape(rows), _per_row(fr, U, R, T)).reshape(lead + (T,) + tail)
-    return torch.from_numpy(res) if isinstance(x, torch.Tensor) else res
+    fe = front(x, n_tail, frames, who, lambda xd, _fr, d_frames, R: on_device(xd, d_frames, R), on_host)
+    return fe.res.reshape(fe.lead + (fe.T,) + tail)
 
 
 def joints_from_tracks(track, skeleton: Skeleton, frames=None, mean=None, unit: bool = False, fps=None):
@@ -1071,7 +1020,7 @@ def euler_from_rot6d(track, tree: JointTree, order, frames=None, mean=None, fps=
 
 def _unwrapped(euler: torch.Tensor, fe: SimpleNamespace, period: float) -> torch.Tensor:
     """The Euler filter over ``euler [U * R, T_out, J, 3]`` on the device, in place, on the valid output frames of the front end ``fe``."""
-    launch_unwrap(euler.view(fe.U * fe.R, fe.t_out, -1), _frames_dev(fe.n_out if fe.fr is not None else None, euler.device), fe.R, 1, period)
+    launch_unwrap(euler.view(fe.U * fe.R, fe.t_out, -1), frames_dev(fe.n_out if fe.fr is not None else None, euler.device), fe.R, 1, period)
     return euler
 
 
@@ -1228,8 +1177,8 @@ class TrackOutputs:
         of ``poses``, ``[U, (R,) T_out, ., .]``, and ``"joint_frames"``, the valid output frames per recording; the Euler channels
         unwrapped where the caller asked for it."""
         fe = _front(poses, self.body, frames, self.fps, f"{self.who}: joints")
-        x = _dev32(poses).reshape(fe.U * fe.R, fe.T, self.body.pose_dim)
-        out = self.to(x.device).launch(x, _frames_dev(fe.fr, x.device), fe.R)
+        x = dev32(poses).reshape(fe.U * fe.R, fe.T, self.body.pose_dim)
+        out = self.to(x.device).launch(x, frames_dev(fe.fr, x.device), fe.R)
         if self.unwrap:
             _unwrapped(out["euler"], fe, 360.0)
         return dict({n: v.reshape(fe.lead + tuple(v.shape[1:])) for n, v in out.items()}, joint_frames=fe.n_out)

@@ -26,8 +26,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._host import BoundedCache, host_ptr, ptr as _ptr, stream as _stream
-from .skeleton import _dev32, _frames_dev, _frames_list, _host64, _is_cuda, _lead, _per_row
+from . import _rows as RW
+from ._host import BoundedCache, host_ptr, ptr as _ptr, sized, stream as _stream
 
 __all__ = ["Smoother", "smooth_tracks", "launch_smooth", "StreamSmoother", "MAX_WINDOW", "TILE_FRAMES", "TILE_COLS"]
 
@@ -100,7 +100,7 @@ def launch_smooth(track: torch.Tensor, sm: Smoother, frames: Optional[Sequence[i
     B, T, D = track.shape
     if out is None:
         out = torch.empty_like(track)
-    fr = None if frames is None else np.ascontiguousarray(frames, np.int32)
+    fr = RW.counts32(frames)
     L.check(L.load().eg_smooth_tracks(_ptr(track), B, T, D, sm.window, _ptr(sm.device_table(track.device)), host_ptr(fr), _ptr(d_frames),
                                       int(draws), int(frame_unit), _ptr(out), _stream(track.device)), "eg_smooth_tracks")
     return out
@@ -121,17 +121,9 @@ def smooth_tracks(track, smoother, frames=None):
     shape = tuple(track.shape)
     if len(shape) < 2 or shape[-2] < 1 or shape[-1] < 1:
         raise L.EgError(f"{who}: track shape {shape}: need [..., T >= 1, D >= 1]")
-    lead, U, R = _lead(shape, 2, who)
-    T, D = shape[-2:]
-    fr = _frames_list(frames, U, T, who)
-    short = [(u, n) for u, n in enumerate(fr if fr is not None else [T] * U) if n < sm.window]
-    if short:
-        raise L.EgError(f"{who}: recording {short[0][0]} has {short[0][1]} valid frames < window={sm.window} (there is no shrinking window)")
-    if _is_cuda(track):
-        x = _dev32(track).reshape(U * R, T, D)
-        return launch_smooth(x, sm, fr, _frames_dev(fr, x.device), R).reshape(shape)
-    y = _smooth64(_host64(track, who).reshape(U * R, T, D), sm.table, _per_row(fr, U, R, T)).reshape(shape)
-    return torch.from_numpy(y) if isinstance(track, torch.Tensor) else y
+    return RW.front(track, 2, frames, who, lambda x, fr, d_frames, R: launch_smooth(x, sm, fr, d_frames, R),
+                    lambda v, per_row: _smooth64(v, sm.table, per_row), sm.window,
+                    f"window={sm.window} (there is no shrinking window)").res.reshape(shape)
 
 
 class StreamSmoother:
@@ -159,10 +151,7 @@ class StreamSmoother:
             raise L.EgError("StreamSmoother: device must be a CUDA device (emotiongestures_amd has no CPU fallback)")
         self.device, self.delay = dev, self.sm.half
         self._lib = L.load()
-        nbytes = int(self._lib.eg_smooth_stream_state_bytes(self.U, self.D, self.sm.window))
-        if nbytes <= 0:
-            raise L.EgError(f"eg_smooth_stream_state_bytes: refused ({self._lib.eg_last_error().decode()})")
-        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        self.state = torch.zeros(sized("eg_smooth_stream_state_bytes", self.U, self.D, self.sm.window), dtype=torch.uint8, device=dev)
         self.out = torch.zeros(self.U, self.H, self.D, dtype=torch.float32, device=dev)
         self._table = self.sm.device_table(dev)
 

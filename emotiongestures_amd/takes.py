@@ -26,7 +26,8 @@ import torch
 
 from . import _lib as L
 from . import ops
-from ._host import BoundedCache, host_ptr, int_list, ptr as _ptr, stream as _stream
+from ._host import BoundedCache, host_ptr, ptr as _ptr, sized, stream as _stream
+from ._rows import count_list
 
 __all__ = ["track_features", "take_distance", "take_diversity", "pack_rows", "workspace_bytes", "FEATURE_DIM", "MAX_DRAWS"]
 
@@ -48,9 +49,7 @@ class _TakesPlan:
         self.sum_frames = int(self.frames.astype(np.int64).sum())
         self.bytes = 0
         if draws >= 2:
-            self.bytes = int(lib.eg_take_distance_workspace_bytes(self.h_frames, U, int(draws)))
-            if self.bytes <= 0:
-                raise L.EgError(f"eg_take_distance_workspace_bytes: refused ({lib.eg_last_error().decode()})")
+            self.bytes = sized("eg_take_distance_workspace_bytes", self.h_frames, U, int(draws))
         self.meta = torch.from_numpy(meta).to(device)
 
     @classmethod
@@ -59,13 +58,6 @@ class _TakesPlan:
 
 
 _PLANS = BoundedCache(16)
-
-
-def _int_list(v, n, who):
-    v = int_list(v)
-    if len(v) != n:
-        raise ValueError(f"{who}: frames has {len(v)} entries for {n} recordings")
-    return v
 
 
 def _track4(track, who):
@@ -82,7 +74,7 @@ def pack_rows(track: torch.Tensor, frames=None):
     (eg_track_rows_pack, one launch).  Rows at or beyond ``frames[u]`` are never read.  -> (rows [N, Dpad], frames, off)."""
     trk = _track4(track, "pack_rows")
     U, R, Tmax, D = trk.shape
-    frames = [Tmax] * U if frames is None else _int_list(frames, U, "pack_rows")
+    frames = [Tmax] * U if frames is None else count_list(frames, U, "pack_rows")
     lib = L.load()
     plan = _TakesPlan.get(lib, frames, R, trk.device)
     rows = torch.empty(R * plan.sum_frames, (D + 3) // 4 * 4, dtype=torch.float32, device=trk.device)
@@ -134,7 +126,7 @@ def take_distance(feat: torch.Tensor, frames, draws: int, span: Optional[int] = 
         raise RuntimeError("take_distance: feat must be a CUDA tensor (there is no CPU fallback)")
     if feat.dim() != 2:
         raise ValueError(f"take_distance: feat must be packed [N, K], got {tuple(feat.shape)}")
-    frames = _int_list(frames, len(frames), "take_distance")
+    frames = count_list(frames, len(frames), "take_distance")
     U = len(frames)
     N, K = feat.shape
     if N != R * sum(frames):
@@ -156,10 +148,7 @@ def take_distance(feat: torch.Tensor, frames, draws: int, span: Optional[int] = 
 def workspace_bytes(frames, draws: int) -> int:
     """Bytes of ``take_distance``'s workspace for (frames, draws) (eg_take_distance_workspace_bytes; host only)."""
     fr = np.ascontiguousarray(frames, np.int32)
-    n = int(L.load().eg_take_distance_workspace_bytes(host_ptr(fr), len(fr), int(draws)))
-    if n <= 0:
-        raise L.EgError(f"eg_take_distance_workspace_bytes: refused ({L.load().eg_last_error().decode()})")
-    return n
+    return sized("eg_take_distance_workspace_bytes", host_ptr(fr), len(fr), int(draws))
 
 
 def take_diversity(fgd, track: torch.Tensor, frames=None, span: Optional[int] = None, workspace: Optional[torch.Tensor] = None,

@@ -509,6 +509,19 @@ int eg_resample_stream_push(void* state, int32_t rows, int32_t rate_in, int32_t 
                             int32_t hop_in, const int32_t* ends_in, float* out, int32_t hop_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Rows of whole tracks: what (rows, T, d_frames, draws, frame_unit [, frames]) mean in every whole-track stage below (csrc/rows.h)
+ * ------------------------------------------------------------------------------------------ */
+/* rows = U * draws tracks of T frames: recording u owns the `draws` consecutive rows from u * draws on.  d_frames: device int32 [rows / draws],
+ * 4-byte aligned, one count per recording, or NULL; frame_unit: what one count stands for, 1 for frame counts, H for a stream's 0 / 1 valid
+ * flags.  Row b has n = clamp(d_frames[b / draws] * frame_unit, 0, T) valid frames, in 64-bit (d_frames NULL: T).  Frames t >= n are never
+ * used and may hold NaN; outputs behind a row's last frame are zeros.  A stage that needs a minimum of valid frames (a window, four
+ * positions, one frame) cannot check a device count before its launch, so it also takes `frames`, the HOST copy of the counts (int32
+ * [rows / draws]; NULL exactly when d_frames is NULL), and refuses the first recording below the minimum by name.  Nothing ties the two
+ * copies together: a row whose device count is below the minimum although the host count is not comes out as zeros, and every access stays
+ * in range.  Every stage refuses by name, before its first launch: d_frames not 4-byte aligned, rows not a multiple of draws (or draws < 1),
+ * frame_unit < 1, `frames` and d_frames not given together, a host count below the minimum. */
+
+/* ------------------------------------------------------------------------------------------
  * Skeleton output: tracks of bone direction vectors <-> joint positions on the device (csrc/skeleton.hip)
  * ------------------------------------------------------------------------------------------ */
 /* A skeleton is a table of K bones in topological order, 1 <= K <= EG_SKELETON_MAX_BONES, over J = K + 1 joints: bone k = (parents[k],
@@ -526,8 +539,7 @@ int32_t eg_skeleton_tile_frames(void);
 /* Forward: track [rows, T, 3K] fp32 -> joints [rows, out_stride, J, 3] fp32, out_stride >= ceil(T * L / M); L / M = output rate / input
  * rate (reduced here).  For a source frame t: x_k = track[b, t, 3k .. 3k+2] + d_mean[3k ..] (d_mean NULL: no mean term); unit != 0:
  * x_k /= max(|x_k|, 1e-12); p[0] = 0, p[children[k]] = p[parents[k]] + lengths[k] * x_k in table order.  Row b has
- * n = clamp(d_frames[b / draws] * frame_unit, 0, T) valid frames (d_frames NULL: T; device int32 [rows / draws]: one count per recording,
- * shared by its `draws` consecutive rows; frame_unit: what one count stands for, 1 for frame counts, H for a stream's 0 / 1 valid flags)
+ * n valid frames ("Rows of whole tracks" above: d_frames, draws, frame_unit)
  * and n_out = ceil(n * L / M) output frames: frame k' is p(lo) + (p(lo + 1) - p(lo)) * f with lo = min(floor(k' M / L), n - 2),
  * f = (k' M - lo L) / L in exact integers (linear interpolation, extrapolated past the last frame; n = 1: p(0)); at L / M = 1 nothing is
  * blended and frame k' is p(k').  Frames k' >= n_out are written as zeros; source frames t >= n are never used and may hold NaN.
@@ -564,7 +576,7 @@ int eg_skeleton_dir_vec(const float* joints, int32_t rows, int32_t T, const int3
  *     G_k = P_k (x) L_k             (global rotation; its sign is the product's, never flipped)
  * so G_k o rest_k = x^_k for every bone, and forward kinematics with the offsets lengths[k] * rest_k and the locals L_k reproduces
  * eg_skeleton_joints(unit = 1).
- * Frames.  rows, d_frames, draws, frame_unit, the reduced ratio L / M, n_out = ceil(n L / M), lo and f exactly as in eg_skeleton_joints.  On
+ * Frames.  rows, d_frames, draws, frame_unit: "Rows of whole tracks"; the reduced ratio L / M, n_out = ceil(n L / M), lo and f: eg_skeleton_joints.  On
  * an interpolated frame the VECTORS are blended before anything else: x_k = fmaf(x_k(lo + 1) - x_k(lo), f, x_k(lo)), taken after the mean;
  * the chain then runs on the blended frame.  n = 1: frame 0.  At L / M = 1 nothing is blended.
  * Output.  L_k for space = EG_SKELETON_SPACE_LOCAL, G_k for EG_SKELETON_SPACE_GLOBAL.  Frames k' >= n_out are written as zeros; source
@@ -604,7 +616,7 @@ int eg_skeleton_rotations(const float* track, int32_t rows, int32_t T, const int
  *     tr:  (1 + tr, m21 - m12, m02 - m20, m10 - m01)          m00: (m21 - m12, 1 + m00 - m11 - m22, m01 + m10, m02 + m20)
  *     m11: (m02 - m20, m01 + m10, 1 - m00 + m11 - m22, m12 + m21)   m22: (m10 - m01, m02 + m20, m12 + m21, 1 - m00 - m11 + m22)
  * divided by max(|q|, 1e-12) and negated where w < 0, so w >= 0.  Either output pointer may be NULL, not both; one launch writes both.
- * Frames.  rows, d_frames, draws, frame_unit, the reduced ratio L / M, n_out = ceil(n L / M), lo and f exactly as in eg_skeleton_joints.  On
+ * Frames.  rows, d_frames, draws, frame_unit: "Rows of whole tracks"; the reduced ratio L / M, n_out = ceil(n L / M), lo and f: eg_skeleton_joints.  On
  * an interpolated frame the 6-D VECTORS of the source frames lo and lo + 1 are blended, after the mean: d = fmaf(d(lo + 1) - d(lo), f,
  * d(lo)); the whole chain then runs on the blended frame, so the joints and rotations of one call describe the same pose.  n = 1: frame 0.
  * Frames k' >= n_out are written as zeros; source frames t >= n are never read and may hold NaN.
@@ -693,11 +705,9 @@ int eg_angle_unwrap(float* angles, int32_t rows, int32_t T, int32_t C, const int
  * which is scipy.signal.savgol_filter(x, K, p, deriv=d, delta=delta, axis=0, mode="interp").  Frames i >= n of the output are zeros; source
  * frames t >= n are never read and may hold NaN; no sample outside [0, n) enters any output (no padding at the ends).  On the device every
  * output element is acc = 0, then acc = fmaf(C[.][j], x[.], acc) for j = 0 .. K - 1 in that order, in fp32.
- * eg_smooth_tracks: track [rows, T, D] fp32 -> out [rows, T, D] fp32.  Row b has n = clamp(d_frames[b / draws] * frame_unit, 0, T) valid
- * frames, exactly as in eg_skeleton_joints (d_frames NULL: T).  A row with n < K is refused by name -- there is no shrinking window -- and a
- * device count cannot be checked before the launch, so the call also takes `frames`, the HOST copy of the counts (int32 [rows / draws];
- * NULL exactly when d_frames is NULL), and checks that.  Nothing ties the two together: with a d_frames that differs from `frames` a row
- * whose device count is below K comes out as zeros, and every access stays in range.  d_table: device copy of table32.
+ * eg_smooth_tracks: track [rows, T, D] fp32 -> out [rows, T, D] fp32.  Row b has n valid frames and the call takes
+ * the host copy `frames` ("Rows of whole tracks"): a row with n < K is refused by name -- there is no shrinking window --, and a row
+ * whose device count is below K although the host count is not comes out as zeros.  d_table: device copy of table32.
  * All pointers are caller-owned; no allocation, no synchronisation, one launch on `stream`; the grid -- (tile of EG_SMOOTH_TILE_FRAMES
  * frames) x (tile of EG_SMOOTH_TILE_COLS columns) x row -- depends on (rows, T, D) only, so the call captures into a hipGraph; one owning
  * thread per output element, plain vector stores, no atomics.  A row's result does not depend on rows, on its place in the batch or on T.
@@ -735,7 +745,7 @@ int eg_smooth_stream_tail(const void* state, int32_t rows, int32_t P, int32_t D,
  * Motion statistics of whole tracks: mean speed, acceleration and jerk per joint and a histogram of the joint speeds (csrc/kinematics.hip)
  * ------------------------------------------------------------------------------------------ */
 /* Input: joint positions p [rows, T, J, 3] in fp32 metres (what eg_skeleton_joints / eg_articulate_forward write).  Row b has
- * n = clamp(d_frames[b / draws] * frame_unit, 0, T) valid frames, exactly as in eg_smooth_tracks (d_frames NULL: T); frames t >= n may hold
+ * n valid frames ("Rows of whole tracks"); frames t >= n may hold
  * NaN and no sample at or beyond n enters any output.
  * Differences, in fp32, one IEEE subtraction each, by successive differencing:
  *     d1[t] = p[t+1] - p[t] for t < n - 1;   d2[t] = d1[t+1] - d1[t] for t < n - 2;   d3[t] = d2[t+1] - d2[t] for t < n - 3
@@ -754,8 +764,7 @@ int eg_smooth_stream_tail(const void* state, int32_t rows, int32_t P, int32_t D,
  * atomics (integer atomics for the bins: order-free), plain vector stores; the grids depend on (rows, T, J, bins) only, so the call captures
  * into a hipGraph.  A row's result does not depend on rows, on its place in the batch or on T.  workspace: eg_kin_workspace_bytes (0 for
  * refused arguments), the [rows, tiles, 3, J] fp64 tile sums.  d_edges2: device copy of eg_kin_edges2's table.
- * A row with n < 4 is refused by name from `frames`, the HOST copy of the counts (int32 [rows / draws]; NULL exactly when d_frames is NULL),
- * the mechanism of eg_smooth_tracks; with a device count below 4 although the host count is not, that row's outputs are zeros and every
+ * A row with n < 4 is refused by name from `frames`, the host copy of the counts ("Rows of whole tracks"); with a device count below 4 although the host count is not, that row's outputs are zeros and every
  * access stays in range.
  * Refuses by name before the first launch: null pointers, joints / workspace / mean / hist not 16-byte aligned, rows < 1, T < 4, J outside
  * 1..EG_KIN_MAX_JOINTS, bins outside 1..EG_KIN_MAX_BINS, rows not a multiple of draws, frame_unit < 1, fps not finite or not positive, a host
@@ -774,10 +783,8 @@ int eg_kin_stats(const float* joints, int32_t rows, int32_t T, int32_t J, const 
  * Joint-space scores of whole tracks: SRGR (semantic-relevant gesture recall) and L1 diversity, model/Beat_score_v2.py SRGR / L1div
  * (csrc/jointscore.hip)
  * ------------------------------------------------------------------------------------------ */
-/* Rows as in eg_kin_stats: row b has n = clamp(d_frames[b / draws] * frame_unit, 0, T) valid frames (d_frames NULL: T); frames t >= n may
- * hold NaN and are never read.  A row's result depends on its own data and n only -- not on rows, on its place in the batch or on T.  A
- * recording with n < 1 is refused by name from `frames`, the HOST copy of the counts (int32 [rows / draws]; NULL exactly when d_frames is
- * NULL); with a device count of 0 although the host count is not, that row's outputs are zeros and every access stays in range.
+/* Rows: "Rows of whole tracks", with the host copy `frames` and a minimum of 1 valid frame.  A row's result depends on its own data and n
+ * only -- not on rows, on its place in the batch or on T.
  *
  * SRGR.  results r [rows, T, J, 3] fp32; targets g [rows / draws, T, J, 3] fp32, one per recording, shared by its `draws` takes; semantic
  * weights w [rows / draws, T] fp32 (NULL: every weight 1); threshold and scale fp64 (the reference's normaliser is scale = 1 / 0.165, formed

@@ -129,6 +129,37 @@ def test_the_same_call_twice_and_a_device_count_below_four():
         assert torch.equal(out[0][b], first[0][b]) and torch.equal(out[1][b], first[1][b])
 
 
+@pytest.mark.parametrize("unit,counts,zero", [(1, None, True), (4, 1, False), (4, 0, True)], ids=["count-3", "flags-of-4-one", "flags-of-4-none"])
+def test_device_counts_that_differ_from_the_host_copy_meet_the_floor_of_four(unit, counts, zero):
+    """The floor of the shared device count (csrc/rows.h) at its edge, with draws: U = 2 recordings of 2 draws, T = one tile + 5 frames (two
+    tiles, the second ragged), J = 3.  The host counts pass ([T, T]); the device counts give recording 1 three frames (one below the floor:
+    zeros), or in the stream's flag form (frame_unit = 4, [T / 4, 1 or 0]) four frames (the floor itself: the figures of four frames) or none
+    (zeros).  Recording 0 has the bits of the call whose two copies agree; the NaN behind every device count reaches no output."""
+    T, J, dev_ = TF + 5, 3, dev()
+    d_counts = [T, 3] if counts is None else [T // 4, counts]
+    n = [min(c * unit, T) for c in d_counts]
+    rng = np.random.default_rng(40 + unit)
+    p = (rng.standard_normal((4, T, J, 3)) * 0.02).astype(np.float32)
+    for u in range(2):
+        p[2 * u:2 * u + 2, n[u]:] = np.nan
+    x = torch.from_numpy(p).to(dev_)
+    bins = KM.SpeedBins(fps=FPS)
+    out = (torch.full((4, 3, J), 7.0, dtype=torch.float64, device=dev_), torch.full((4, J, 41), 7, dtype=torch.int32, device=dev_))
+    KM.launch_kinematics(x, bins, [T, T], torch.tensor(d_counts, dtype=torch.int32, device=dev_), 2, unit, out=out)
+    mean, hist = out
+    assert bool(torch.isfinite(mean).all())
+    # the call whose host and device copies agree: recording 1 gets the floor's four frames so that the host check passes
+    agree = [d_counts[0], max(d_counts[1], -(-4 // unit))]
+    want_mean, want_hist = KM.launch_kinematics(x, bins, agree, torch.tensor(agree, dtype=torch.int32, device=dev_), 2, unit)
+    assert torch.equal(mean[:2], want_mean[:2]) and torch.equal(hist[:2], want_hist[:2])
+    assert hist[:2].sum(-1).cpu().tolist() == [[n[0] - 1] * J] * 2
+    if zero:
+        assert not mean[2:].any() and not hist[2:].any()
+    else:
+        assert torch.equal(mean[2:], want_mean[2:]) and torch.equal(hist[2:], want_hist[2:])
+        assert hist[2:].sum(-1).cpu().tolist() == [[3] * J] * 2 and bool((mean[2:] > 0).all())
+
+
 def test_graph_replay_equals_the_eager_call():
     from emotiongestures_amd.pipeline import CAPTURE_MODE
     T, J, frames = 2 * TF + 4, 43, [2 * TF + 4, TF - 1, 4, 40, 2 * TF, TF + 2]

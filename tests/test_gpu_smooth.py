@@ -86,6 +86,31 @@ def test_a_row_does_not_depend_on_the_batch_or_on_T(K, p):
     assert torch.equal(SM.smooth_tracks(torch.from_numpy(row[None]).to(dev()), sm, frames=[n])[0], alone)
 
 
+@pytest.mark.parametrize("unit", [1, 4], ids=["count-K-1", "flags-of-4"])
+def test_device_counts_that_differ_from_the_host_copy_meet_the_floor_of_the_window(unit):
+    """The floor of the shared device count (csrc/rows.h) at its edge, with draws: U = 2 recordings of 2 draws, T = one tile + 5 frames (two
+    tiles, the second ragged), D = 5, window 5.  The host counts pass ([T, T]); the device counts give recording 1 K - 1 = 4 frames, as a
+    count or in the stream's flag form (frame_unit = 4, [T / 4, 1]): a zero track.  Recording 0 has the bits of the call whose two copies
+    agree; the NaN behind every device count reaches no output."""
+    sm = smoother(5, 2)
+    K, T, D, dev_ = sm.window, TF + 5, 5, dev()
+    d_counts = [T, K - 1] if unit == 1 else [T // 4, 1]
+    n = [min(c * unit, T) for c in d_counts]
+    assert n[1] == K - 1 and n[0] > TF
+    rng = np.random.default_rng(50 + unit)
+    v = rng.standard_normal((4, T, D)).astype(np.float32)
+    for u in range(2):
+        v[2 * u:2 * u + 2, n[u]:] = np.nan
+    x = torch.from_numpy(v).to(dev_)
+    out = torch.full_like(x, 7.0)
+    SM.launch_smooth(x, sm, [T, T], torch.tensor(d_counts, dtype=torch.int32, device=dev_), 2, unit, out=out)
+    assert not out[2:].any() and bool(torch.isfinite(out).all())
+    # the call whose host and device copies agree: recording 1 gets a whole window so that the host check passes
+    agree = [d_counts[0], -(-K // unit)]
+    want = SM.launch_smooth(x, sm, agree, torch.tensor(agree, dtype=torch.int32, device=dev_), 2, unit)
+    assert torch.equal(out[:2], want[:2]) and bool(out[:2, :n[0]].any()) and not out[:2, n[0]:].any()
+
+
 def test_graph_replay_equals_the_eager_call():
     from emotiongestures_amd.pipeline import CAPTURE_MODE
     sm = smoother(9, 3)

@@ -53,3 +53,27 @@ def test_host_ptr():
     a = np.arange(6, dtype=np.int32)
     assert H.host_ptr(None) is None
     assert H.host_ptr(a).value == a.ctypes.data
+
+
+def test_sized_returns_the_bytes_or_raises_with_the_last_error():
+    from emotiongestures_amd import _lib as L
+    assert H.sized("eg_srgr_workspace_bytes", 2, 20, 5) == (8 + 4 * 5) * 2
+    with pytest.raises(L.EgError) as e:
+        H.sized("eg_srgr_workspace_bytes", 2, 20, 65)
+    assert str(e.value) == "eg_srgr_workspace_bytes: refused (eg_srgr_workspace_bytes: joints=65 (1..64))"
+    with pytest.raises(L.EgError, match=r"^eg_kin_workspace_bytes: refused \(eg_kin_workspace_bytes: frames=3 \(need >= 4"):
+        H.sized("eg_kin_workspace_bytes", 2, 3, 5, 40)
+
+
+def test_count_list_keeps_the_callers_words():
+    from emotiongestures_amd import _rows as RW
+    assert RW.count_list(np.asarray([4, 5], np.int64), 2, "pack_rows") == [4, 5]
+    with pytest.raises(ValueError) as e:
+        RW.count_list([4, 5, 6], 2, "pack_rows")
+    assert str(e.value) == "pack_rows: frames has 3 entries for 2 recordings"
+    with pytest.raises(ValueError) as e:
+        RW.count_list(torch.tensor([7]), 2, "beat_alignment_tracks", "t_end")
+    assert str(e.value) == "beat_alignment_tracks: t_end has 1 entries for 2 recordings"
+    assert RW.counts32(None) is None
+    c = RW.counts32([3, 4])
+    assert c.dtype == np.int32 and c.flags["C_CONTIGUOUS"] and c.tolist() == [3, 4]
