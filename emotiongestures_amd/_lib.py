@@ -67,6 +67,8 @@ EG_SMOOTH_MAX_WINDOW, EG_SMOOTH_TILE_FRAMES, EG_SMOOTH_TILE_COLS = 31, 64, 64
 EG_KIN_MAX_JOINTS, EG_KIN_MAX_BINS, EG_KIN_TILE_FRAMES = 64, 256, 64
 EG_JOINTSCORE_TILE_FRAMES, EG_SRGR_MAX_JOINTS, EG_L1DIV_MAX_COLS = 32, 64, 512
 EG_EMOTION_CHUNK_WINDOWS, EG_EMOTION_MAX_CLASSES = 64, 64
+EG_TAKE_MAX_DRAWS = 64
+EG_MOTION_WINDOW, EG_MOTION_ROW_FLOATS, EG_MOTION_MAX_POSE_DIM, EG_MOTION_RUN_FRAMES = 34, 384, 128, 136
 
 # name -> (restype, argtypes).  Must list every symbol include/emogest.h declares
 # (tests/test_abi.py cross-checks this table against the header).
@@ -180,6 +182,8 @@ SIGNATURES = {
     "eg_emotion_window_embed": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
     "eg_emotion_vote_workspace_bytes": (_L, [_P, _I, _I, _I]),
     "eg_emotion_vote": (C.c_int, [_P, _I, _I, _I, _P, _P, _P, _P, _L] + [_P] * 13),
+    "eg_motion_run_windows": (_I, [_I]),
+    "eg_motion_window_rows": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P] + [_P] * 8 + [_I, _I, _P, _P]),
     "eg_conv3x3": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "eg_conv3x3_se": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "eg_se_gate_pre": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

@@ -31,6 +31,34 @@ __device__ __forceinline__ int egi_stage_exact(float* __restrict__ l, const floa
     return (int)(g0 - q0);
 }
 
+// The same span with the same loads, transposed on the way: [g0, g1) is n frames of D columns (g1 - g0 = n * D < 2^31), and column c of frame t
+// goes to l[c * pitch + t] -- channel-major, the image a convolution over frames reads with consecutive lanes on consecutive banks.  The
+// stores pay for it: the lanes of one store are 4 columns apart, 4 * pitch floats, so give an odd pitch (8 banks, 4-way) and never a
+// multiple of 8 (one or two banks).
+__device__ __forceinline__ void egi_stage_exact_t(float* __restrict__ l, int pitch, const float* __restrict__ p, long long g0, long long g1, int D,
+                                                  int tid, int threads) {
+    const long long q0 = g0 & ~3ll;
+    for (long long q = q0 + 4 * tid; q < g1; q += 4 * threads) {
+        f4 v = {0.f, 0.f, 0.f, 0.f};
+        if (q >= g0 && q + 4 <= g1) {
+            v = *reinterpret_cast<const f4*>(p + q);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (q + e >= g0 && q + e < g1) v[e] = p[q + e];
+        }
+        const int rel = (int)(q - g0);                          // -3 .. : the first group may start before the span
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int i = rel + e;
+            if (i >= 0 && q + e < g1) {
+                const int t = i / D;
+                l[(i - t * D) * pitch + t] = v[e];
+            }
+        }
+    }
+}
+
 // A row's own tiles added in ascending order, sixteen loads in flight (a tile past nt adds +0.0 or 0, which changes no bit).
 template <class V>
 __device__ __forceinline__ V egi_sum_tiles(const V* __restrict__ src, long long stride, int nt) {

@@ -466,7 +466,7 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
                beat: bool = False, diversity=None, audio_rate: Optional[int] = None, joints=None, joints_mean=None,
                joints_unit: bool = False, joints_fps=None, rotations=None, rotations_space: str = "local", smooth=None, euler=None,
                euler_unwrap: bool = False, kinematics=None, srgr=None, l1div: bool = False, emotion=None,
-               emotion_stride: Optional[int] = None) -> Dict[str, torch.Tensor]:
+               emotion_stride: Optional[int] = None, diversity_stride: int = 34) -> Dict[str, torch.Tensor]:
     """One gesture track per utterance from raw 16 kHz audio: windows -> mel -> optional CVAE sample per window -> roll-out.
 
     ``models = (generator, vae | None)``, eval mode, on the GPU.  ``audio [U, total_samples]``; ``text [U, W, 60]`` (the words of every
@@ -494,6 +494,11 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     ``diversity=fgd`` (an eval-mode ``MLP_Reconstruct``; with ``draws=R``, R >= 2): adds ``"take_distance"`` ``[U, R, R]`` and
     ``"take_diversity"`` ``[U]`` (fp64), the pairwise distances of the returned takes of every recording in FGD feature space and their mean
     (takes.take_diversity with ``span = frames``: the unit of the clip metric ``calculate_diversity`` on one generator window).
+    ``diversity=ae`` (an eval-mode ``model.motion_ae.MotionAE`` whose ``pose_dim`` is the generator's: the TED-Expressive feature space): the
+    same two keys from ``motionfeat.window_features`` -- the encoder on every 34-frame window of every take at stride ``diversity_stride``
+    (default 34), one fused launch for the convolutions -- with ``span = 1``: the RMS per-window feature distance, comparable across
+    recording lengths.  A net of another pose width, in train mode, or a generator whose shortest track has fewer than 34 poses is refused
+    by name before anything runs.
 
     ``audio_rate`` (Hz; e.g. 48000, 44100, 24000): ``audio``, and ``lengths`` when given, are at that rate.  The audio is resampled to
     ``sample_rate`` once on the device (resample.resample_audio: scipy's ``resample_poly`` design, ``max(L, M) <= 640``), then the path above
@@ -568,7 +573,7 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     srgr, l1div = _jointscore_args("synthesize", srgr, l1div, outputs, audio)
     return _synthesize("synthesize", models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate,
                        want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=False, kinematics=kinematics,
-                       srgr=srgr, l1div=l1div, emotion=emotion, emotion_stride=emotion_stride)
+                       srgr=srgr, l1div=l1div, emotion=emotion, emotion_stride=emotion_stride, diversity_stride=diversity_stride)
 
 
 def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch.Tensor, labels: Optional[torch.Tensor] = None, *,
@@ -578,7 +583,7 @@ def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose:
                      audio_rate: Optional[int] = None, joints=None, joints_mean=None, joints_unit: bool = False, joints_fps=None,
                      rotations=None, rotations_space: str = "local", smooth=None, euler=None,
                      euler_unwrap: bool = False, kinematics=None, srgr=None, l1div: bool = False, emotion=None,
-                     emotion_stride: Optional[int] = None) -> Dict[str, torch.Tensor]:
+                     emotion_stride: Optional[int] = None, diversity_stride: int = 34) -> Dict[str, torch.Tensor]:
     """``draws`` = R sampled takes for each of U recordings of any and unequal length, from raw audio, in one call: ``synthesize(lengths=)`` and
     ``synthesize(draws=)`` combined (a VAE is required).  ``audio [U, max_total]`` with ``lengths[u]`` real samples in row u (``None``: every
     row at full length); recording u has ``W_u = ceil(lengths[u] / hop_samples)`` windows, N = sum W_u.  ``text`` padded ``[U, Wmax, 60]`` or
@@ -597,7 +602,7 @@ def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose:
     srgr, l1div = _jointscore_args("synthesize_takes", srgr, l1div, outputs, audio)
     return _synthesize("synthesize_takes", models, audio, text, seed_pose, labels, hop_samples, n_samples, None, z, alpha, fps, sample_rate,
                        want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=True, kinematics=kinematics,
-                       srgr=srgr, l1div=l1div, emotion=emotion, emotion_stride=emotion_stride)
+                       srgr=srgr, l1div=l1div, emotion=emotion, emotion_stride=emotion_stride, diversity_stride=diversity_stride)
 
 
 def _kinematics_arg(who, kinematics, outputs, joints_fps, fps):
@@ -626,6 +631,31 @@ def _jointscore_args(who, srgr, l1div, outputs, audio):
             raise L.EgError(f"{who}: srgr= takes a jointscore.SemanticTargets, got {type(srgr).__name__}")
         srgr.fit(who, U=int(audio.shape[0]) if audio.dim() == 2 else None, J=outputs.body.J)
     return srgr, bool(l1div)
+
+
+def _motion_ae_arg(who, diversity, stride, gen, seed_pose) -> bool:
+    """``diversity=`` as a ``MotionAE`` (True) or anything else (False: the FGD encoder's path, unchanged).  Checked before anything runs: the
+    net's pose width against the generator's, eval mode, a latent size ``take_distance`` can read, the stride, and the shortest track the
+    generator can make (one window) against the 34 poses of a MotionAE window."""
+    from .model.motion_ae import MotionAE
+    if not isinstance(diversity, MotionAE):
+        return False
+    from . import motionfeat as MF
+    _enc, D, latent = MF._encoder(diversity, f"{who}: diversity=")
+    if D != seed_pose.shape[-1]:
+        raise L.EgError(f"{who}: diversity=: the MotionAE takes pose_dim={D}, the generator's poses have {seed_pose.shape[-1]} columns")
+    if diversity.training:
+        raise L.EgError(f"{who}: diversity=: the MotionAE is not in eval mode (call .eval())")
+    if latent < 4 or latent % 4:
+        raise L.EgError(f"{who}: diversity=: the MotionAE's latent_dim={latent}: take_distance reads features in 16-byte groups "
+                        "(a multiple of 4, >= 4)")
+    if stride is None or int(stride) < 1:
+        raise L.EgError(f"{who}: diversity_stride={stride} (need >= 1)")
+    shortest = int(gen._origin()._cfg["frames"])
+    if shortest < MF.WINDOW:
+        raise L.EgError(f"{who}: diversity=: a recording of one generator window has {shortest} poses < window={MF.WINDOW} "
+                        "(the MotionAE takes whole windows: no padding, no resampling)")
+    return True
 
 
 def _emotion_arg(who, emotion, stride, gen, vae, audio, text, seed_pose, labels, hop_samples, windows, fps, sample_rate, lengths, draws,
@@ -696,7 +726,7 @@ def _track_outputs(who, seed_pose, *args):
 
 def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate, want_windows, want_aux,
                 mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes, kinematics=None, srgr=None, l1div=False, emotion=None,
-                emotion_stride=None):
+                emotion_stride=None, diversity_stride=34):
     """The body of `synthesize` and `synthesize_takes` (`who` names the caller in errors): argument checks, resampling, the roll-out of the
     call's kind, then the per-track extras.  `outputs`: the caller's checked output stage (`_track_outputs`)."""
     gen, vae = models
@@ -724,6 +754,7 @@ def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samp
     if diversity is not None and (draws is None or int(draws) < 2):
         raise L.EgError(f"{who}: diversity= needs draws >= 2 (got draws={draws}): the take diversity is a distance between the takes of "
                         "one recording")
+    motion_ae = _motion_ae_arg(who, diversity, diversity_stride, gen, seed_pose)          # a MotionAE: checked before anything runs
     eng = gen.engine()
     c = eng.cfg
     if audio.dim() != 2:
@@ -776,7 +807,10 @@ def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samp
             out["beat"] = beat_alignment_tracks(audio, out["track"], lengths=lengths, frames=frames, fps=fps)
     if diversity is not None:
         with torch.no_grad():
-            td = take_diversity(diversity, out["track"], frames=frames if takes else None, span=c.frames)
+            if motion_ae:                                                                 # per 34-frame window of the TED feature space
+                td = take_diversity(diversity, out["track"], frames=frames if takes else None, span=1, stride=int(diversity_stride))
+            else:
+                td = take_diversity(diversity, out["track"], frames=frames if takes else None, span=c.frames)
         out["take_distance"], out["take_diversity"] = td["distance"], td["diversity"]
     if emotion is not None:                                                               # of the raw track too: it measures the model
         from . import emotion as EM

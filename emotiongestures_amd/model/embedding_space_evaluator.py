@@ -50,6 +50,23 @@ class EmbeddingSpaceEvaluator:
         self.recon_err_diff.append(l_fake - l_real)
         self.cos_err_diff.append(c_fake - c_real)
 
+    @torch.no_grad()
+    def push_tracks(self, generated_track, real_track, frames=None, stride=None, tail=True):
+        """Whole tracks instead of 34-frame clips: the encoder's features of every window of ``generated_track`` and of ``real_track``
+        (``[U, Tmax, D]`` or ``[U, R, Tmax, D]``, CUDA; ``motionfeat.window_features``) are appended to ``generated_feat_list`` and
+        ``real_feat_list``.  Both tracks share ``frames`` (valid poses per recording), ``stride`` (default 34) and ``tail``, so their windows
+        are paired row by row and ``get_scores`` / ``get_diversity_scores`` work on whole tracks.  The decoder does not run: the
+        reconstruction-error lists (``recon_err_diff``, ``cos_err_diff``) stay untouched.  -> the window plan."""
+        from .. import motionfeat as MF
+        if tuple(generated_track.shape) != tuple(real_track.shape):
+            raise ValueError(f"push_tracks: generated track {tuple(generated_track.shape)} and real track {tuple(real_track.shape)} differ in shape: "
+                             "the features are paired window by window")
+        real_feat, plan = MF.window_features(self.net, real_track, frames, stride, tail)
+        generated_feat, _plan = MF.window_features(self.net, generated_track, frames, stride, tail)
+        self.real_feat_list.append(real_feat.cpu().numpy())
+        self.generated_feat_list.append(generated_feat.cpu().numpy())
+        return plan
+
     def get_features_for_viz(self):
         import umap
         g, r = np.vstack(self.generated_feat_list), np.vstack(self.real_feat_list)

@@ -42,17 +42,23 @@ def _dense(x, lin: Linear, bn=None):
     return ops.linear(x, hit[1], hit[2], packed=hit[3])
 
 
-def _conv(x, conv, bn=None, weight=None, stride=1, padding=0, leaky=False):
-    """Conv1d (+ folded BatchNorm1d, + LeakyReLU 0.2); folded weights cached on the layer per parameter version.
-    ``weight`` overrides conv.weight (ConvTranspose1d expressed as a convolution)."""
-    ver = (str(x.device),) + _versions(conv, bn)
+def _conv_pack(conv, device, bn=None, weight=None):
+    """(weight [cout, cin, k], bias) of a Conv1d with its BatchNorm1d folded in: fp32, contiguous, on `device`; cached on the layer per
+    parameter version.  ``weight`` overrides conv.weight (ConvTranspose1d expressed as a convolution)."""
+    ver = (str(device),) + _versions(conv, bn)
     hit = getattr(conv, "_eg_pack", None)
     if hit is None or hit[0] != ver:
         w = conv.weight if weight is None else weight(conv)
         w, b = (w, conv.bias) if bn is None else _fold(w, conv.bias, bn)
-        hit = (ver, w.detach().float().contiguous().to(x.device), b.detach().float().contiguous().to(x.device))
+        hit = (ver, w.detach().float().contiguous().to(device), b.detach().float().contiguous().to(device))
         object.__setattr__(conv, "_eg_pack", hit)
-    return ops.conv1d(x, hit[1], hit[2], stride=stride, padding=padding, leaky=leaky)
+    return hit[1], hit[2]
+
+
+def _conv(x, conv, bn=None, weight=None, stride=1, padding=0, leaky=False):
+    """Conv1d (+ folded BatchNorm1d, + LeakyReLU 0.2) on the weights `_conv_pack` caches."""
+    w, b = _conv_pack(conv, x.device, bn, weight)
+    return ops.conv1d(x, w, b, stride=stride, padding=padding, leaky=leaky)
 
 
 class PoseEncoderConv(nn.Module):

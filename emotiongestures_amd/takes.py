@@ -32,7 +32,7 @@ from ._rows import count_list
 __all__ = ["track_features", "take_distance", "take_diversity", "pack_rows", "workspace_bytes", "FEATURE_DIM", "MAX_DRAWS"]
 
 FEATURE_DIM = 512
-MAX_DRAWS = 64                      # EG_TAKE_MAX_DRAWS
+MAX_DRAWS = L.EG_TAKE_MAX_DRAWS
 
 
 class _TakesPlan:
@@ -152,11 +152,28 @@ def workspace_bytes(frames, draws: int) -> int:
 
 
 def take_diversity(fgd, track: torch.Tensor, frames=None, span: Optional[int] = None, workspace: Optional[torch.Tensor] = None,
-                   out: Optional[dict] = None) -> Dict[str, torch.Tensor]:
+                   out: Optional[dict] = None, stride: Optional[int] = None, tail: bool = True) -> Dict[str, torch.Tensor]:
     """``take_distance(track_features(fgd, track, frames), frames, R, span)`` for ``track [U, R, Tmax, D]``: how far apart the R takes of
-    every recording are in FGD feature space.  -> ``{"distance": [U, R, R], "diversity": [U]}`` fp64 on the device."""
+    every recording are in FGD feature space.  -> ``{"distance": [U, R, R], "diversity": [U]}`` fp64 on the device.
+
+    With a ``model.motion_ae.MotionAE`` as the net (the TED feature space) the features are
+    ``motionfeat.window_features(net, track, frames, stride, tail)``, one row of ``latent_dim`` floats per 34-frame window, and the distance
+    runs over recording u's windows: ``frames = plan.counts``, ``K = latent_dim`` (a multiple of 4; anything else is refused by name) and
+    ``span`` counts windows -- ``span=1`` is the RMS per-window feature distance, comparable across recording lengths.  ``stride`` and
+    ``tail`` belong to this form alone."""
     if not isinstance(track, torch.Tensor) or track.dim() != 4 or track.shape[1] < 2:
         raise L.EgError(f"take_diversity: track must be [U, R, Tmax, D] with R >= 2 takes per recording, got "
                         f"{tuple(track.shape) if isinstance(track, torch.Tensor) else type(track).__name__}")
+    from .model.motion_ae import MotionAE
+    if isinstance(fgd, MotionAE):
+        from . import motionfeat as MF
+        latent = MF._encoder(fgd, "take_diversity")[2]
+        if latent < 4 or latent % 4:
+            raise L.EgError(f"take_diversity: the MotionAE's latent_dim={latent}: take_distance reads features in 16-byte groups "
+                            "(a multiple of 4, >= 4)")
+        feat, plan = MF.window_features(fgd, track, frames, stride, tail)
+        return take_distance(feat, plan.counts.tolist(), track.shape[1], span=span, workspace=workspace, out=out)
+    if stride is not None or not tail:
+        raise L.EgError("take_diversity: stride= and tail= are the window arguments of a MotionAE; the FGD encoder is per frame")
     feat, frames, _off = track_features(fgd, track, frames)
     return take_distance(feat, frames, track.shape[1], span=span, workspace=workspace, out=out)

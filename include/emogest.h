@@ -1005,6 +1005,39 @@ int eg_emotion_vote(const float* logits, int32_t recordings, int32_t draws, int3
                     int32_t* invalid, double* mean_logit, int32_t* pred, int32_t* hit, int32_t* window_hits, double* accuracy,
                     double* window_accuracy, int32_t* confusion, int32_t* window_confusion, int32_t* unscored, void* stream);
 
+/* Motion-clip features of whole tracks: the convolutional tower of MotionAE's encoder (model/motion_ae.py: PoseEncoderConv.net, the feature
+ * net behind the TED-style Frechet gesture distance) on every 34-frame window of tracks of any and unequal length with R takes each, in one
+ * launch (csrc/motionfeat.hip).  The three Linears behind it (out_net) are eg_linear products on the rows this entry writes.
+ *
+ * Windows, clip order and the `frames | off | C | coff` table are those of eg_emotion_meta with window = EG_MOTION_WINDOW: the caller uploads
+ * that table once per (frames, stride, tail) and passes the device copy as d_frames (its first U entries are the frames) beside the host vector.
+ * track [U, R, Tmax, D] fp32; poses at or beyond frames[u] are never read and may hold NaN.
+ * Weights: four (w [cout, cin, k], bias [cout]) pairs in PyTorch's Conv1d layout with the BatchNorm already folded in:
+ *   D -> 32, k 3, LeakyReLU(0.2);   32 -> 64, k 3, LeakyReLU;   64 -> 64, k 4, stride 2, LeakyReLU;   64 -> 32, k 3, plain
+ * (34 -> 32 -> 30 -> 14 -> 12 positions).  For the clip range [c0, c1):   rows[c - c0, co * 12 + l] = the last layer's output (co, l) of clip
+ * c -- [c1 - c0, EG_MOTION_ROW_FLOATS], the flatten(1) layout out_net consumes.  The range only bounds the caller's workspace: an element of
+ * rows does not depend on it.
+ * Arithmetic: every output element of every layer is bias first, then one fp32 multiply-add per term with ci ascending and k inner, then the
+ * LeakyReLU -- eg_conv1d's order, so the rows equal the chain of four eg_conv1d calls on host-cut windows bit for bit.
+ * Kernel: a workgroup owns a run of eg_motion_run_windows(stride) consecutive strided windows of one take (the tail window is a run of its
+ * own) and stages at most EG_MOTION_RUN_FRAMES poses for it, channel-major, once; the first two layers (stride 1, no padding: shift-
+ * invariant) run once per position of the run, not once per window; the last two run per window in batches or, where the windows of a run
+ * overlap enough (small strides), once per position too: output l of the window at pose s is position s + 2l of one stride-1 pass, shared
+ * by all windows of one start parity.  The weights are staged layer by layer; activations never leave the LDS.  No atomics, no memset, no allocation, no host round trip; grid and pointers are fixed for fixed
+ * (frames, draws, stride, tail, range), so the launch captures into a hipGraph.
+ * Refuses by name, before the launch: null pointers, track / rows not 16-byte aligned, U outside 1 .. 65535, draws outside
+ * 1 .. EG_TAKE_MAX_DRAWS, D outside 1 .. EG_MOTION_MAX_POSE_DIM, window != EG_MOTION_WINDOW, stride < 1, frames[u] < window or > Tmax,
+ * N >= 2^31, c0 < 0, c1 > N, an empty range, and a d_frames the rows contract refuses (not 4-byte aligned). */
+#define EG_MOTION_WINDOW 34
+#define EG_MOTION_ROW_FLOATS 384
+#define EG_MOTION_MAX_POSE_DIM 128
+#define EG_MOTION_RUN_FRAMES 136
+int32_t eg_motion_run_windows(int32_t stride);
+int eg_motion_window_rows(const float* track, int32_t recordings, int32_t draws, int32_t Tmax, int32_t pose_dim, int32_t window,
+                          int32_t stride, int32_t tail, const int32_t* frames, const int32_t* d_frames, const float* w1, const float* b1,
+                          const float* w2, const float* b2, const float* w3, const float* b3, const float* w4, const float* b4, int32_t c0,
+                          int32_t c1, float* rows, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Block-level operators (the reference's L2 blocks), used by the module-level mirrors and by the
  * per-kernel parity tests.  Weights here are passed as individual device pointers in the PACKED

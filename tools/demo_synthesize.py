@@ -14,7 +14,8 @@ With --beat the generator is BEAT-shaped (60 poses of 282 columns, 10 of them th
 call also returns the beat-alignment score of each track against its own audio (per recording, and per draw with --draws).
 With --diversity (and --draws R, R >= 2) the draws call also returns the take diversity of every recording: the mean pairwise distance of its
 R takes in FGD feature space (takes.take_diversity, fp64 on the GPU, in the unit of one generator window), and the script shows the FGD of
-whole tracks from the same features (takes.track_features -> FrechetAccumulator).
+whole tracks from the same features (takes.track_features -> FrechetAccumulator).  On the TED shape (without --beat) it shows both also in
+MotionAE's latent space: diversity=MotionAE and motionfeat.window_features (the encoder on every 34-frame window, one fused launch per range).
 With --audio-rate HZ (48000, 44100, 24000, ...) the test signal is made at that rate and every call gets audio_rate=HZ: the recordings are
 resampled to 16 kHz on the GPU (resample.resample_audio) before anything else runs; lengths are then counted in samples at HZ.
 With --joints (TED shape only) the rectangular call also returns the joint positions of every track in metres (skeleton.ted_expressive(): 43
@@ -321,6 +322,20 @@ if DRAWS > 0:
         acc_b.push(takes.track_features(fgd, tracks[:, 1].contiguous())[0])
         fgd_ab = H.calculate_frechet_distance(*acc_a.stats(), *acc_b.stats())
         print(f"--diversity: FGD of the draw-0 tracks against the draw-1 tracks ({U * tracks.shape[2]} feature rows each): {float(np.real(fgd_ab)):.4f}")
+        if not BEAT:    # the TED shape has a feature space of its own: MotionAE's encoder on every 34-frame window, one fused launch per range
+            from emotiongestures_amd import motionfeat
+            from emotiongestures_amd.model.motion_ae import MotionAE
+            ae = load_synth_weights(MotionAE(POSE_DIM, 128), 41).eval().to(dev)
+            ted = H.synthesize((gen, vae), audio, text, seed_pose, labels=labels_r, z=zr, draws=DRAWS, diversity=ae, **AR)
+            print(f"--diversity: the same in MotionAE's latent space (RMS feature distance per 34-frame window, stride 34): "
+                  f"{[round(float(v), 4) for v in ted['take_diversity'].cpu()]}")
+            acc_a, acc_b = H.FrechetAccumulator(128, dev), H.FrechetAccumulator(128, dev)
+            fa, plan = motionfeat.window_features(ae, tracks[:, 0].contiguous(), stride=17)
+            acc_a.push(fa)
+            acc_b.push(motionfeat.window_features(ae, tracks[:, 1].contiguous(), stride=17)[0])
+            fgd_ab = H.calculate_frechet_distance(*acc_a.stats(), *acc_b.stats())
+            print(f"--diversity: MotionAE FGD of the draw-0 tracks against the draw-1 tracks ({plan.total} windows each at stride 17): "
+                  f"{float(np.real(fgd_ab)):.4f}")
     spread = (tracks - tracks.mean(dim=1, keepdim=True)).norm(dim=3).mean()
     print(f"--draws {DRAWS}: tracks {tuple(tracks.shape)} in one call, {1e3 * dt_r:.2f} ms = {1e3 * dt_r / (U * DRAWS * tracks.shape[2] / FPS):.4f} ms per "
           f"second of track (one track per recording: {1e3 * dt / (U * track.shape[1] / FPS):.4f}); mean distance of a draw from its recording's mean "
