@@ -216,6 +216,10 @@ SIGNATURES = {
     "eg_profile_read_workgroups": (_I, [_P, _I]),
     "eg_time_linear": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "eg_reparameterize": (C.c_int, [_P, _P, _P, _P, _L, _P]),
+    "eg_prior_encoder": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "eg_embedding": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "eg_small_linear": (C.c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "eg_conv_transpose1d": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "eg_conv1d": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "eg_contrastive_workspace_bytes": (C.c_int64, [_I]),
     "eg_contrastive_loss": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _L, _P]),

@@ -734,6 +734,10 @@ int validate_cfg(const EgGeneratorConfig& c) {
     EG_REQUIRE(c.frames <= 128, EG_ERR_UNSUPPORTED, "config: frames=%d > 128 (final conv width)", c.frames);
     EG_REQUIRE(c.embed_dim == c.tcn_hidden && c.embed_dim % 4 == 0, EG_ERR_UNSUPPORTED, "config: TCN needs embed_dim == hidden, %%4");
     EG_REQUIRE(c.variant == 0 || c.variant == 1, EG_ERR_BAD_ARG, "config: variant=%d", c.variant);
+    // the memory variant gates and scales the first `chunk` PREDICTED frames and keeps its TM scores in a 64-entry array (tm_apply_kernel)
+    EG_REQUIRE(c.variant != 1 || (c.chunk <= 64 && c.chunk <= c.frames - c.prior_frames), EG_ERR_UNSUPPORTED,
+               "config: memory variant chunk=%d exceeds min(frames - prior_frames, 64) = %d", c.chunk,
+               c.frames - c.prior_frames < 64 ? c.frames - c.prior_frames : 64);
     EG_REQUIRE(c.precision >= 0 && c.precision <= 2, EG_ERR_BAD_ARG, "config: precision=%d", c.precision);
     EG_REQUIRE(c.n_position >= c.frames, EG_ERR_BAD_ARG, "config: n_position < frames");
     EG_REQUIRE(c.pose_dim > 0 && c.pose_dim <= 1024 && c.n_words > 0 && c.text_len > 0 && c.text_len <= 128, EG_ERR_BAD_ARG, "config: sizes");

@@ -1245,6 +1245,48 @@ int eg_add_rows(const float* a, const float* table, float* out, int64_t rows, in
  * EG_TIME_LINEAR=ref (read per call) selects the one-row-at-a-time reference kernel; any other non-empty value is EG_ERR_BAD_ARG. */
 int eg_time_linear(const float* x, const float* w, const float* bias, float* y, int32_t batch, int32_t len, int32_t c, int32_t ld, void* stream);
 
+/* The front half of Prior_MemoryEncoder on its own (the generator calls the same launcher): Full_model/Models_spatial_memory.py:366-390 and, for
+ * the memory variant, Full_model/Models_memory.py:233-251,282-293.  PL = frames - prior_frames.
+ *   prior [batch, prior_frames, d];  conv: a HOST array of eight device pointers {w1 [PL, prior_frames, 3], b1, s1, t1 [PL], w2 [PL, PL, 3], b2, s2,
+ *   t2 [PL]}: pred = BN2(ReLU(conv2(BN1(ReLU(conv1(prior)))))) with the prior frames as channels, the pose axis as the length (padding 1, the hidden
+ *   map zero padded) and each eval-mode BatchNorm folded to y * s + t.
+ *   mem: NULL or a HOST array of twelve device pointers, all NULL for variant 0 and all set for variant 1 (nn.Linear layouts):
+ *   {sp_w0 [d, chunk d], sp_b0 [d], sp_w1 [d, d], sp_b1 [d], tc_w0, tc_b0, tc_w1, tc_b1 (the same shapes), tm_w0 [chunk, chunk d], tm_b0 [chunk],
+ *   tm_w1 [chunk, chunk], tm_b1 [chunk]}.  Variant 1: m = sp1(sp0(flat(prior[:, P - chunk:]))), the first chunk frames of pred become
+ *   s pred_c + (1 - s) m with s = sigmoid(<m, pred_c>);  tm_mem = tc1(tc0(the same flat chunk)),  tm_pe = tm1(tm0(flat(the gated frames))),
+ *   tm_gram = tm_mem^T tm_pe (a sum over the BATCH: the clips of one call are coupled, as in the reference), w = softmax_c(tm_mem[b] tm_gram),
+ *   pred_c = pred_c + pred_c w_c.
+ *   cat [batch, frames, dpad] = cat(prior, pred) with the columns d .. dpad-1 written as +0;  tm_mem [batch, d], tm_pe [batch, chunk],
+ *   tm_gram [d, chunk] (variant 1 only; may be NULL for variant 0, where chunk is ignored).
+ * EG_ERR_BAD_ARG, by name: dpad < d; variant 1 with chunk outside 1 .. min(prior_frames, frames - prior_frames, 64) (the gated frames are
+ * predicted ones, the scores live in 64 slots); memory pointers partly set, or not matching the variant.  EG_ERR_UNSUPPORTED: the slice of one
+ * workgroup (variant 0: 64 pose columns; variant 1: the whole axis plus chunk d + 2 d floats) needs more than 160 KiB of LDS; the conv weights
+ * are staged in LDS when they fit beside it and read from global memory otherwise.  Nothing is launched or written on a refusal. */
+int eg_prior_encoder(const float* prior, const float* const* conv, const float* const* mem, float* cat, float* tm_mem, float* tm_pe, float* tm_gram,
+                     int32_t batch, int32_t prior_frames, int32_t frames, int32_t d, int32_t dpad, int32_t chunk, int32_t variant, void* stream);
+
+/* nn.Embedding gather into padded rows (Full_model/Models_spatial_memory.py:171): out[r, 0:dim] = table[clamp(idx[r], 0, n_words - 1)], bit for
+ * bit; idx int64 [rows], table [n_words, dim], out [rows, ld].  dim % 4 == 0, ld >= dim, ld % 4 == 0 (else EG_ERR_ALIGN).
+ * images == NULL: the columns dim .. ld-1 of out are left untouched.
+ * images != NULL (ld % 64 == 0, else EG_ERR_ALIGN): the columns dim .. ld-1 are written as +0 and `images` receives the rows as eg_split_tiles
+ * images of width ld (4 * ceil(rows/64) * 64 * ld bytes); the image slots of the last tile's rows past `rows` are left untouched.  zero_line
+ * (optional, only with images): 64 * ld bf16 slots (128 * ld bytes) that are cleared -- the zero row source of the causal products that follow. */
+int eg_embedding(const int64_t* idx, const float* table, float* out, void* images, void* zero_line, int32_t rows, int32_t dim, int32_t ld,
+                 int32_t n_words, void* stream);
+
+/* The CVAE's dense layers (CAVE/BEAT_CVAE.py: Posterior_Y_embedding, fusion_z_*): y[r, o] = bias[o] + sum_i w[o, i] x[r, i] for r < n, o < out;
+ * x rows ldx >= in floats apart, y rows ldy >= out apart (the columns out .. ldy-1 of y are untouched), w [out, in].  One wave per output: lane l
+ * sums i = l, l + 64, ... in ascending order, the 64 partials by a butterfly, the bias last.  n <= 65535. */
+int eg_small_linear(const float* x, int32_t ldx, const float* w, const float* bias, float* y, int32_t ldy, int32_t n, int32_t in, int32_t out,
+                    void* stream);
+
+/* nn.ConvTranspose1d(k 3, stride 2, padding 1, output_padding 1) -> LeakyReLU(0.2) -> y * scale[co] + shift[co] (the CVAE decoder's stages,
+ * CAVE/BEAT_CVAE.py:355-362): x [n, cin, lin] -> y [n, cout, 2 lin], w [cin, cout, 3] (PyTorch layout);
+ * y[co, lo] = bias[co] + sum_ci sum_k x[ci, (lo + 1 - k) / 2] w[ci, co, k] over the k with lo + 1 - k even and 0 <= (lo + 1 - k) / 2 < lin:
+ * a term outside that range is dropped, not multiplied by zero.  Summed bias first, ci outer, k inner.  scale and shift are required. */
+int eg_conv_transpose1d(const float* x, const float* w, const float* bias, const float* scale, const float* shift, float* y, int32_t n, int32_t cin,
+                        int32_t cout, int32_t lin, void* stream);
+
 /* VAE reparameterisation (CAVE/BEAT_CVAE.py:397-399): z = eps*exp(0.5*logvar) + mu, n elements. */
 int eg_reparameterize(const float* mu, const float* logvar, const float* eps, float* z, int64_t n, void* stream);
 

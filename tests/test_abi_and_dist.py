@@ -118,6 +118,32 @@ def test_config_validation_and_status_codes():
     assert lib.eg_se_gate(one, 4, one, one, one, one, one, 1, 200, 16, None) == -2                              # C = 200
     assert lib.eg_generator_forward(None, None, 1, None, None, None, None, None, None, None, None, None, None, 0, None) < 0
     assert lib.eg_mel_workspace_bytes(0, 64000) == 0 and lib.eg_mel_workspace_bytes(2, 64000) == 2 * 128 * 126 * 4
+    # the four entry points of kernels the generator and the CVAE launch internally (tests/misc_f64.py)
+    with pytest.raises(_lib.EgError, match="chunk=65"):
+        GeneratorEngine(variant="memory", frames=128, prior_frames=100, chunk=65)      # the TM scores live in 64 slots
+    with pytest.raises(_lib.EgError, match="chunk=10"):
+        GeneratorEngine(variant="memory", frames=34, prior_frames=30, chunk=10)        # only 4 predicted frames to gate
+    conv, mem = (C.c_void_p * 8)(*[16] * 8), (C.c_void_p * 12)(*[16] * 12)
+    none12, part = (C.c_void_p * 12)(), (C.c_void_p * 12)(*[16] * 11)
+    pe = lambda cv, mm, *a: lib.eg_prior_encoder(one, cv, mm, one, one, one, one, *a, None)
+    assert pe(conv, None, 2, 4, 34, 126, 125, 4, 0) == -1 and b"dpad=125 < d=126" in lib.eg_last_error()
+    assert pe(conv, part, 2, 4, 34, 126, 128, 4, 1) == -1 and b"partly set (11 of 12)" in lib.eg_last_error()
+    assert pe(conv, mem, 2, 4, 34, 126, 128, 4, 0) == -1 and pe(conv, none12, 2, 4, 34, 126, 128, 4, 1) == -1      # pointers against the variant
+    assert pe(conv, mem, 2, 100, 128, 126, 128, 65, 1) == -1 and b"chunk=65" in lib.eg_last_error()
+    assert pe(conv, mem, 2, 4, 34, 126, 128, 0, 1) == -1 and pe(conv, mem, 2, 4, 34, 126, 128, 5, 1) == -1           # chunk < 1, chunk > prior_frames
+    assert pe(conv, mem, 2, 30, 34, 126, 128, 5, 1) == -1 and b"= 4" in lib.eg_last_error()                          # chunk > frames - prior_frames
+    assert pe((C.c_void_p * 8)(*[16] * 7), None, 2, 4, 34, 126, 128, 4, 0) == -1 and b"conv[7]" in lib.eg_last_error()
+    assert pe(conv, mem, 1, 10, 120, 282, 320, 10, 1) == -2 and b"LDS need" in lib.eg_last_error()                   # 181 KB for one workgroup
+    assert lib.eg_embedding(one, one, one, None, None, 4, 6, 8, 10, None) == -5 and b"dim=6" in lib.eg_last_error()
+    assert lib.eg_embedding(one, one, one, None, None, 4, 8, 4, 10, None) == -5 and b"ld=4 < dim=8" in lib.eg_last_error()
+    assert lib.eg_embedding(one, one, one, one, None, 4, 8, 32, 10, None) == -5 and b"images need ld % 64 == 0" in lib.eg_last_error()
+    assert lib.eg_embedding(one, one, one, None, one, 4, 8, 64, 10, None) == -1 and b"zero_line without images" in lib.eg_last_error()
+    assert lib.eg_embedding(one, one, None, None, None, 4, 8, 64, 10, None) == -1 and lib.eg_embedding(one, one, one, None, None, 0, 8, 64, 10, None) == -1
+    assert lib.eg_small_linear(one, 8, one, one, None, 16, 2, 8, 16, None) == -1                                      # null y
+    assert lib.eg_small_linear(one, 7, one, one, one, 16, 2, 8, 16, None) == -1 and b"ldx=7" in lib.eg_last_error()   # ldx < in
+    assert lib.eg_small_linear(one, 8, one, one, one, 15, 2, 8, 16, None) == -1 and lib.eg_small_linear(one, 8, one, one, one, 16, 0, 8, 16, None) == -1
+    assert lib.eg_conv_transpose1d(one, one, one, None, None, one, 2, 4, 8, 16, None) == -1 and b"scale and shift are required" in lib.eg_last_error()
+    assert lib.eg_conv_transpose1d(one, one, one, one, one, one, 2, 4, 8, 0, None) == -1 and b"lin=0" in lib.eg_last_error()
 
 
 def test_conv_pack_layout_roundtrip():
