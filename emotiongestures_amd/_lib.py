@@ -57,6 +57,12 @@ class EgResamplePlan(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("L", "M", "half", "K", "D", "Hs", "pitch", "bank_floats")]
 
 
+class EgBvhTextArgs(C.Structure):
+    """include/emogest.h: the arguments eg_bvh_text_measure and eg_bvh_text_write share (field order = the header's)."""
+    _fields_ = [(n, _P) for n in ("euler", "root_position", "table", "d_table", "frames", "d_frames")] + \
+               [(n, _I) for n in ("rows", "T", "J3", "C", "draws", "frame_unit")]
+
+
 EG_RESAMPLE_TILE, EG_RESAMPLE_MAX_FACTOR = 1024, 640
 EG_SKELETON_MAX_BONES, EG_SKELETON_MAX_FACTOR, EG_SKELETON_TILE_FRAMES = 63, 64, 32
 EG_SKELETON_SPACE_LOCAL, EG_SKELETON_SPACE_GLOBAL = 0, 1
@@ -68,6 +74,7 @@ EG_KIN_MAX_JOINTS, EG_KIN_MAX_BINS, EG_KIN_TILE_FRAMES = 64, 256, 64
 EG_JOINTSCORE_TILE_FRAMES, EG_SRGR_MAX_JOINTS, EG_L1DIV_MAX_COLS = 32, 64, 512
 EG_EMOTION_CHUNK_WINDOWS, EG_EMOTION_MAX_CLASSES = 64, 64
 EG_TAKE_MAX_DRAWS = 64
+EG_BVH_TEXT_MAX_CHANNELS, EG_BVH_TEXT_MAX_WIDTH, EG_BVH_TEXT_TILE_FRAMES = 512, 18, 8
 EG_MOTION_WINDOW, EG_MOTION_ROW_FLOATS, EG_MOTION_MAX_POSE_DIM, EG_MOTION_RUN_FRAMES = 34, 384, 128, 136
 
 # name -> (restype, argtypes).  Must list every symbol include/emogest.h declares
@@ -146,6 +153,12 @@ SIGNATURES = {
     "eg_articulate_rot6d_euler": (C.c_int, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P, _P]),
     "eg_angle_unwrap_workspace_bytes": (_L, [_I, _I, _I]),
     "eg_angle_unwrap": (C.c_int, [_P, _I, _I, _I, _P, _I, _I, C.c_double, _P, _L, _P]),
+    "eg_bvh_text_decimal": (_I, [C.c_float, C.c_char_p]),
+    "eg_bvh_text_tile_frames": (_I, []),
+    "eg_bvh_text_table_bytes": (_L, [_I]),
+    "eg_bvh_text_workspace_bytes": (_L, [_I, _I, _I]),
+    "eg_bvh_text_measure": (C.c_int, [C.POINTER(EgBvhTextArgs), _P, _L, _P, _P, _P]),
+    "eg_bvh_text_write": (C.c_int, [C.POINTER(EgBvhTextArgs), _P, _P, _L, _P]),
     "eg_smooth_design": (C.c_int, [_I, _I, _I, C.c_double, _P, _P]),
     "eg_smooth_tile_frames": (_I, []),
     "eg_smooth_tile_cols": (_I, []),

@@ -466,7 +466,7 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
                beat: bool = False, diversity=None, audio_rate: Optional[int] = None, joints=None, joints_mean=None,
                joints_unit: bool = False, joints_fps=None, rotations=None, rotations_space: str = "local", smooth=None, euler=None,
                euler_unwrap: bool = False, kinematics=None, srgr=None, l1div: bool = False, emotion=None,
-               emotion_stride: Optional[int] = None, diversity_stride: int = 34) -> Dict[str, torch.Tensor]:
+               emotion_stride: Optional[int] = None, diversity_stride: int = 34, bvh_text: bool = False) -> Dict[str, torch.Tensor]:
     """One gesture track per utterance from raw 16 kHz audio: windows -> mel -> optional CVAE sample per window -> roll-out.
 
     ``models = (generator, vae | None)``, eval mode, on the GPU.  ``audio [U, total_samples]``; ``text [U, W, 60]`` (the words of every
@@ -534,6 +534,12 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     of ``out["euler"]`` into a ``.bvh`` text.  Made from ``"track_smooth"`` with ``smooth=``.  Refused by name: ``euler=`` without
     ``joints=``, and with a ``Skeleton`` (direction-vector bodies have no joint rotations).
 
+    ``bvh_text=True`` (with ``euler=BvhFile``): adds ``"bvh"``, a ``bvh.BvhText``: ``euler.format_tracks(out["euler"], out["joint_frames"],
+    tree.names, frame_time=1 / rate)`` at the output rate (``joints_fps[1]`` when given, else ``fps``) -- the ``MOTION`` lines of every take
+    formatted on the device, four launches and one small copy of the sizes to the host; ``out["bvh"].text(u, r)`` is ``euler.format`` of that
+    take and ``out["bvh"].write(dir)`` writes one ``.bvh`` per take from one copy of the text.  Refused by name before anything runs:
+    ``bvh_text=True`` without ``euler=`` being a ``BvhFile``.
+
     ``smooth=Smoother | (window, polyorder)`` (``smooth.Smoother``; a pair is a filter at ``fps``): adds ``"track_smooth"``, the shape of
     ``"track"``: ``smooth.smooth_tracks(out["track"], smooth, frames)``, a Savitzky-Golay filter (``scipy.signal.savgol_filter``,
     ``mode="interp"``) over recording u's own valid poses, zeros behind them, one launch.  ``"track"`` stays raw and ``beat`` / ``diversity`` keep
@@ -571,9 +577,11 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     outputs = _track_outputs("synthesize", seed_pose, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, euler, euler_unwrap)
     kinematics = _kinematics_arg("synthesize", kinematics, outputs, joints_fps, fps)
     srgr, l1div = _jointscore_args("synthesize", srgr, l1div, outputs, audio)
+    bvh_text = _bvh_text_arg("synthesize", bvh_text, euler, joints, joints_fps, fps)
     return _synthesize("synthesize", models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate,
                        want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=False, kinematics=kinematics,
-                       srgr=srgr, l1div=l1div, emotion=emotion, emotion_stride=emotion_stride, diversity_stride=diversity_stride)
+                       srgr=srgr, l1div=l1div, emotion=emotion, emotion_stride=emotion_stride, diversity_stride=diversity_stride,
+                       bvh_text=bvh_text)
 
 
 def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch.Tensor, labels: Optional[torch.Tensor] = None, *,
@@ -583,7 +591,7 @@ def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose:
                      audio_rate: Optional[int] = None, joints=None, joints_mean=None, joints_unit: bool = False, joints_fps=None,
                      rotations=None, rotations_space: str = "local", smooth=None, euler=None,
                      euler_unwrap: bool = False, kinematics=None, srgr=None, l1div: bool = False, emotion=None,
-                     emotion_stride: Optional[int] = None, diversity_stride: int = 34) -> Dict[str, torch.Tensor]:
+                     emotion_stride: Optional[int] = None, diversity_stride: int = 34, bvh_text: bool = False) -> Dict[str, torch.Tensor]:
     """``draws`` = R sampled takes for each of U recordings of any and unequal length, from raw audio, in one call: ``synthesize(lengths=)`` and
     ``synthesize(draws=)`` combined (a VAE is required).  ``audio [U, max_total]`` with ``lengths[u]`` real samples in row u (``None``: every
     row at full length); recording u has ``W_u = ceil(lengths[u] / hop_samples)`` windows, N = sum W_u.  ``text`` padded ``[U, Wmax, 60]`` or
@@ -600,9 +608,21 @@ def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose:
     outputs = _track_outputs("synthesize_takes", seed_pose, joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, euler, euler_unwrap)
     kinematics = _kinematics_arg("synthesize_takes", kinematics, outputs, joints_fps, fps)
     srgr, l1div = _jointscore_args("synthesize_takes", srgr, l1div, outputs, audio)
+    bvh_text = _bvh_text_arg("synthesize_takes", bvh_text, euler, joints, joints_fps, fps)
     return _synthesize("synthesize_takes", models, audio, text, seed_pose, labels, hop_samples, n_samples, None, z, alpha, fps, sample_rate,
                        want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=True, kinematics=kinematics,
-                       srgr=srgr, l1div=l1div, emotion=emotion, emotion_stride=emotion_stride, diversity_stride=diversity_stride)
+                       srgr=srgr, l1div=l1div, emotion=emotion, emotion_stride=emotion_stride, diversity_stride=diversity_stride,
+                       bvh_text=bvh_text)
+
+
+def _bvh_text_arg(who, bvh_text, euler, joints, joints_fps, fps):
+    """The ``bvh_text=`` argument of `synthesize` / `synthesize_takes`, checked before anything runs: (the BvhFile, seconds per output frame), or None."""
+    if not bvh_text:
+        return None
+    if not callable(getattr(euler, "format_tracks", None)):
+        raise L.EgError(f"{who}: bvh_text=True needs euler=BvhFile (the text is that file's HIERARCHY and channel layout), got euler="
+                        f"{type(euler).__name__}")
+    return euler, 1.0 / float(fps if joints_fps is None else joints_fps[1])
 
 
 def _kinematics_arg(who, kinematics, outputs, joints_fps, fps):
@@ -726,7 +746,7 @@ def _track_outputs(who, seed_pose, *args):
 
 def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate, want_windows, want_aux,
                 mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes, kinematics=None, srgr=None, l1div=False, emotion=None,
-                emotion_stride=None, diversity_stride=34):
+                emotion_stride=None, diversity_stride=34, bvh_text=None):
     """The body of `synthesize` and `synthesize_takes` (`who` names the caller in errors): argument checks, resampling, the roll-out of the
     call's kind, then the per-track extras.  `outputs`: the caller's checked output stage (`_track_outputs`)."""
     gen, vae = models
@@ -822,6 +842,9 @@ def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samp
     if outputs is not None:                                                               # joints, rotations, Euler channels: skeleton.TrackOutputs
         with torch.no_grad():
             out.update(outputs.tracks(poses, frames))
+    if bvh_text is not None:                                                              # the MOTION lines of every take, made on the device
+        bvh_file, frame_time = bvh_text
+        out["bvh"] = bvh_file.format_tracks(out["euler"], frames=out["joint_frames"], joints=outputs.body.names, frame_time=frame_time)
     if kinematics is not None:                                                            # of out["joints"]: the smoothed ones with smooth=
         from . import kinematics as KN
         with torch.no_grad():

@@ -690,6 +690,60 @@ int eg_angle_unwrap(float* angles, int32_t rows, int32_t T, int32_t C, const int
                     double period, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * BVH text of whole takes: the MOTION lines of every take, formatted on the device (csrc/bvhtext.hip, csrc/bvhtext.h)
+ * ------------------------------------------------------------------------------------------ */
+/* The text of a finite fp32 v with |v| < 2^31 is "%.6f" of it, defined in integers: q = (double)|v| * 1e6 (exact: 1e6 = 2^6 * 15625, so at
+ * most 24 + 14 significant bits, and q < 2^53); N = (uint64) rint(q), ties to even; '-' iff signbit(v) (-0.0 and -1e-9 print "-0.000000", as
+ * C does); the decimal digits of N / 10^6 without leading zeros, at least one; '.'; the six digits of N % 10^6.  8 .. EG_BVH_TEXT_MAX_WIDTH
+ * bytes.  NaN, an infinity and |v| >= 2^31 are "not writable".
+ * eg_bvh_text_decimal (host only, no HIP call, usable without a GPU): the text of v into out (0-terminated) and its length, or -1 for a value
+ * that is not writable (or a null out).  It runs the routine the kernels run (csrc/bvhtext.h: egi_decimal6).
+ * A take's text.  Row b with n valid frames is n lines; a line is C values joined by one space and ended by '\n'.  Channel c is described
+ * by the table, a blob of eg_bvh_text_table_bytes(C) = 28 C bytes: src int32 [C] | const_len int32 [C] | const_text bytes [C][20].
+ *     src[c] >= 0          element src[c] of the row's euler [J3] of that frame
+ *     src[c] = -1, -2, -3  axis X, Y, Z of root_position [rows / draws, T, 3] (per recording, shared by its draws)
+ *     src[c] = -4          the const_len[c] bytes at const_text[c]: text the caller formatted (an OFFSET that need not be an fp32 value)
+ * `table` is the blob on the HOST (checked here), d_table the caller's upload of the same bytes; nothing ties the two together: the kernels
+ * clamp what they read from d_table, so with an upload that differs the text is unspecified and every access stays in range.
+ * Rows: "Rows of whole tracks", with the host copy `frames` and a minimum of 1 valid frame.  The arguments both calls share travel in one
+ * block, EgBvhTextArgs.
+ * eg_bvh_text_measure: line_off int64 [rows * T + 1]: the byte at which line (b, t) starts, an exclusive scan of the line lengths in
+ * (row, frame) order with length 0 for t >= n -- rows are packed back to back, line_off[b * T] is where row b starts and
+ * line_off[rows * T] the total.  A value that is not writable counts as "0.000000".  summary (device, 8-byte aligned, 8 + 4 rows bytes): the
+ * total (int64), then per row the number of values in its valid frames that are not writable (int32 [rows]).  Three launches -- line
+ * lengths and tile totals (a tile is EG_BVH_TEXT_TILE_FRAMES frames of a row), the scan of the totals in one workgroup, the pass that adds
+ * a tile's start -- in integers: no atomics, no memset.  workspace: eg_bvh_text_workspace_bytes bytes (0 for refused arguments), 8-byte
+ * aligned.
+ * eg_bvh_text_write: the text [line_off[rows * T]] bytes into `text` (16-byte aligned), one launch.  A workgroup formats a tile into LDS
+ * and streams it out with 16-byte stores over the aligned interior and byte stores for its head and tail.  Values that are not writable
+ * are written as "0.000000" (the caller reads summary and refuses them first); no store goes beyond text_bytes or outside the LDS of the
+ * workgroup, whatever line_off holds.  Bytes of `text` outside [0, line_off[rows * T]) are not written.
+ * Both: caller-owned memory, no allocation, no synchronisation, capturable (grids depend on (rows, T, C) only; C > 431 needs more than 64 KB
+ * of LDS, which the first call of a process opts into: make it outside a capture).  A row's bytes do not depend on rows, on its place in
+ * the batch or on T.  Refuse by name before the first launch: a null block or null pointers, pointers not aligned as stated, rows or T
+ * < 1, C outside 1 .. EG_BVH_TEXT_MAX_CHANNELS, J3 < 1, a src entry outside -4 .. J3 - 1, -1 .. -3 without root_position, a const_len
+ * outside 8 .. EG_BVH_TEXT_MAX_WIDTH, rows not a multiple of draws, frame_unit < 1, a host count below 1, a short workspace, text_bytes
+ * < 1, grid / index range. */
+#define EG_BVH_TEXT_MAX_CHANNELS 512
+#define EG_BVH_TEXT_MAX_WIDTH 18
+#define EG_BVH_TEXT_TILE_FRAMES 8
+typedef struct EgBvhTextArgs {
+    const float* euler;          /* device [rows, T, J3] */
+    const float* root_position;  /* device [rows / draws, T, 3], or NULL */
+    const void* table;           /* host blob */
+    const void* d_table;         /* device copy of it */
+    const int32_t* frames;       /* host counts [rows / draws], or NULL */
+    const int32_t* d_frames;     /* the same on the device */
+    int32_t rows, T, J3, C, draws, frame_unit;
+} EgBvhTextArgs;
+int32_t eg_bvh_text_decimal(float v, char* out);
+int32_t eg_bvh_text_tile_frames(void);
+int64_t eg_bvh_text_table_bytes(int32_t C);
+int64_t eg_bvh_text_workspace_bytes(int32_t rows, int32_t T, int32_t C);
+int eg_bvh_text_measure(const EgBvhTextArgs* in, void* workspace, int64_t workspace_bytes, int64_t* line_off, void* summary, void* stream);
+int eg_bvh_text_write(const EgBvhTextArgs* in, const int64_t* line_off, void* text, int64_t text_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Smoothed output: a Savitzky-Golay filter along the time axis of whole tracks on the device (csrc/smooth.hip)
  * ------------------------------------------------------------------------------------------ */
 /* A filter is (window K, polyorder p, deriv d, delta): K odd, 3 <= K <= EG_SMOOTH_MAX_WINDOW; 1 <= p <= min(5, K - 1); 0 <= d <= min(2, p);

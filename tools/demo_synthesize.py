@@ -45,7 +45,7 @@ positions and, with --rotations, one local rotation per joint come from ONE more
 shapes, how far the deepest joint travels and the largest rotation angle.
 With --bvh FILE --bvh-out DIR the call also returns the Euler channels of every joint in the file's own channel orders (euler=BvhFile,
 euler_unwrap=True: one more launch and the Euler filter's three) and the script writes DIR/recording_U[_take_R].bvh -- the file's HIERARCHY,
-then the generated MOTION at the joints' frame rate -- one file per recording and take, formatted on the host (bvh.BvhFile.write).
+then the generated MOTION at the joints' frame rate -- one file per recording and take, formatted on the device in one call (bvh.BvhFile.write_tracks).
 usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--bvh FILE [--bvh-joints A,B,...] [--bvh-out DIR]] [--joints-fps N] [--rotations]] [--smooth K P] [--kinematics] [--srgr] [--l1div] [--emotion] [--out tracks.npz]"""
 import os
 import sys
@@ -188,14 +188,12 @@ if JOINTS and BEAT:
         os.makedirs(BVH_OUT, exist_ok=True)
         eul = jo["euler"]
         takes = eul if eul.dim() == 5 else eul[:, None]                  # [U, R, T', J, 3]
+        names = [os.path.join(BVH_OUT, f"recording_{u}" + (f"_take_{r}" if eul.dim() == 5 else "") + ".bvh")
+                 for u in range(takes.shape[0]) for r in range(takes.shape[1])]
         t0 = time.perf_counter()
-        for u in range(takes.shape[0]):
-            for r in range(takes.shape[1]):
-                name = f"recording_{u}" + (f"_take_{r}" if eul.dim() == 5 else "") + ".bvh"
-                bvh_file.write(os.path.join(BVH_OUT, name), takes[u, r, :jo["joint_frames"][u]], joints=tree.names,
-                               frame_time=1.0 / (JOINTS_FPS or FPS))
-        print(f"--bvh-out: euler {tuple(eul.shape)} in the orders of {BVH} (unwrapped), {takes.shape[0] * takes.shape[1]} files in {BVH_OUT} "
-              f"formatted on the host in {time.perf_counter() - t0:.2f} s")
+        bvh_file.write_tracks(names, eul, jo["joint_frames"], joints=tree.names, frame_time=1.0 / (JOINTS_FPS or FPS))
+        print(f"--bvh-out: euler {tuple(eul.shape)} in the orders of {BVH} (unwrapped), {len(names)} files in {BVH_OUT} "
+              f"formatted on the device and written in {time.perf_counter() - t0:.2f} s")
 elif JOINTS:
     from emotiongestures_amd.skeleton import ted_expressive
     jk = dict(joints=ted_expressive(), joints_unit=True, joints_fps=(FPS, JOINTS_FPS) if JOINTS_FPS else None, smooth=SMOOTH,
