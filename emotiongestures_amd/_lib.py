@@ -70,6 +70,7 @@ EG_ARTICULATE_MAX_JOINTS, EG_ARTICULATE_TILE_FRAMES = 64, 8
 EG_ARTICULATE_BASIS_ROWS, EG_ARTICULATE_BASIS_COLUMNS = 0, 1
 EG_UNWRAP_TILE_FRAMES = 64
 EG_SMOOTH_MAX_WINDOW, EG_SMOOTH_TILE_FRAMES, EG_SMOOTH_TILE_COLS = 31, 64, 64
+EG_RENDER_STREAM_MAX_DELTA = 64
 EG_KIN_MAX_JOINTS, EG_KIN_MAX_BINS, EG_KIN_TILE_FRAMES = 64, 256, 64
 EG_JOINTSCORE_TILE_FRAMES, EG_SRGR_MAX_JOINTS, EG_L1DIV_MAX_COLS = 32, 64, 512
 EG_EMOTION_CHUNK_WINDOWS, EG_EMOTION_MAX_CLASSES = 64, 64
@@ -167,6 +168,14 @@ SIGNATURES = {
     "eg_smooth_stream_reset": (C.c_int, [_P, _I, _I, _I, _P, _P]),
     "eg_smooth_stream_push": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "eg_smooth_stream_tail": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "eg_render_stream_state_bytes": (_L, [_I, _I, _I]),
+    "eg_render_stream_reset": (C.c_int, [_P, _I, _I, _I, _P, _P]),
+    "eg_render_stream_push": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "eg_render_stream_tail": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "eg_skeleton_joints_window": (C.c_int, [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _L, _P]),
+    "eg_skeleton_rotations_window": (C.c_int, [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _L, _P]),
+    "eg_articulate_forward_window": (C.c_int, [_P, _I, _I, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _L, _P]),
+    "eg_articulate_euler_window": (C.c_int, [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P]),
     "eg_kin_tile_frames": (_I, []),
     "eg_kin_edges2": (C.c_int, [_P, _I, C.c_double, _P]),
     "eg_kin_workspace_bytes": (_L, [_I, _I, _I, _I]),

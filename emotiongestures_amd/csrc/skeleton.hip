@@ -129,6 +129,18 @@ __device__ __forceinline__ void zero_tail(float* __restrict__ dst, long long out
     if (t.live < t.cnt) store_range(dst, out0, row, out0 + t.live64 * row, out0 + (long long)t.cnt * row, [](int, int) { return 0.f; });
 }
 
+// The window form of the forward kernels (eg_*_window: a stream's delayed output stage, csrc/render_stream.hip).  A row is a window of source
+// frames, and two things are new.  The output limit: a.T_out may be less than ceil(T L / M), and `cnt` above already cuts `live` there.  The
+// zeroed head: a.frames holds two ints per row, [2][B] -- the window's valid frames, which egi_valid_frames reads as ever (draws = 1), then
+// the number of leading output frames that are written as zeros.  Returns that number inside the tile, 0..live; the frames below it are
+// computed like the others (from finite source frames) and replaced by zeros where they are stored.  WINDOW = false: nothing, no code.
+template <bool WINDOW>
+__device__ __forceinline__ int zero_head(const Args& a, const Tile& t) {
+    if (!WINDOW) return 0;
+    const long long h = (long long)a.frames[a.B + t.b] - t.k0;
+    return (int)(h < 0 ? 0 : (h < t.live ? h : t.live));
+}
+
 // The source frames of a tile of the forward kernels.  A pass makes the outputs [i, i1) of the tile from the source frames
 // [s_base, s_base + nslots): as many outputs as SL source frames reach (all of them unless the rate drops, M > L).  SL: the tile height + 2.
 struct Pass { long long s_base; int i1, nslots; };
@@ -173,8 +185,8 @@ __device__ __forceinline__ float* stage_pass(const Args& a, const Tile& t, const
     return xin + (int)(g0 & 3);
 }
 
-// NATIVE: L / M = 1.
-template <bool UNIT, bool NATIVE>
+// NATIVE: L / M = 1.  WINDOW: the window form (zero_head).
+template <bool UNIT, bool NATIVE, bool WINDOW = false>
 __global__ __launch_bounds__(THREADS) void skeleton_joints_kernel(const Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int K = a.K, D = 3 * K, J3 = 3 * (K + 1), tid = threadIdx.x;
@@ -184,6 +196,7 @@ __global__ __launch_bounds__(THREADS) void skeleton_joints_kernel(const Args a) 
     const long long out0 = ((long long)t.b * a.T_out + t.k0) * J3;
     zero_tail(a.dst, out0, J3, t);
     if (t.live == 0) return;
+    const int zh = zero_head<WINDOW>(a, t);
     const Head h = load_head(a, lds);
     for (int c = tid; c < NC; c += THREADS) pj[c] = 0.f;                        // the root joint, every column
     const bool has_mean = a.mean != nullptr;
@@ -219,6 +232,7 @@ __global__ __launch_bounds__(THREADS) void skeleton_joints_kernel(const Args a) 
         store_range(a.dst, out0, J3, out0 + (long long)i * J3, out0 + (long long)ps.i1 * J3, [&](int fr, int r) {
             const int jt = r / 3, c = r - 3 * jt;
             const float* row = pj + jt * NC + c;
+            if (WINDOW && fr < zh) return 0.f;
             if (NATIVE) return row[3 * (fr - i)];
             if (t.n < 2) return row[0];
             const Blend bl = w.blend(ps, fr);
@@ -300,7 +314,7 @@ __device__ __forceinline__ Quat arc(float a0, float a1, float a2, float b0, floa
 
 // NATIVE: L / M = 1.  GLOBAL: the output holds G_k, else L_k.
 // a.table is the level table of eg_skeleton_levels; as in load_head its numbers index LDS and the output, so they are clamped.
-template <bool NATIVE, bool GLOBAL>
+template <bool NATIVE, bool GLOBAL, bool WINDOW = false>
 __global__ __launch_bounds__(THREADS) void skeleton_rotations_kernel(const Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int K = a.K, D = 3 * K, Q = 4 * K, tid = threadIdx.x;
@@ -315,6 +329,7 @@ __global__ __launch_bounds__(THREADS) void skeleton_rotations_kernel(const Args 
     float* out = a.dst + ((long long)t.b * a.T_out + t.k0) * Q;                  // 16-byte aligned: Q is a multiple of 4
     for (int q = t.live * K + tid; q < t.cnt * K; q += THREADS) *reinterpret_cast<f4*>(out + 4ll * q) = f4{0.f, 0.f, 0.f, 0.f};
     if (t.live == 0) return;
+    const int zh = zero_head<WINDOW>(a, t);
     const int nlev = min(max(a.table[0], 1), K);
     for (int l = tid; l <= nlev; l += THREADS) lv[l] = min(max(a.table[LV_FIRST + l], 0), K);
     for (int k = tid; k < K; k += THREADS) {
@@ -364,7 +379,8 @@ __global__ __launch_bounds__(THREADS) void skeleton_rotations_kernel(const Args 
                 float* gk = gt + k * 4 * TF + fr;
                 gk[0] = G.w; gk[TF] = G.x; gk[2 * TF] = G.y; gk[3 * TF] = G.z;
                 const Quat& o = GLOBAL ? G : Lq;
-                *reinterpret_cast<f4*>(out + ((long long)fr * K + k) * 4) = f4{o.w, o.x, o.y, o.z};
+                if (WINDOW && fr < zh) *reinterpret_cast<f4*>(out + ((long long)fr * K + k) * 4) = f4{0.f, 0.f, 0.f, 0.f};
+                else *reinterpret_cast<f4*>(out + ((long long)fr * K + k) * 4) = f4{o.w, o.x, o.y, o.z};
             }
             __syncthreads();                                                    // a level reads what the level before wrote
         }
@@ -443,7 +459,7 @@ __device__ __forceinline__ void rot6d_matrix(const float* x, const Walk<NATIVE, 
 }
 
 // NATIVE: L / M = 1.  GLOBAL: the rotations hold G_j, else R_j.  a.dst: the joints or null; k.rot: the rotations or null.
-template <bool NATIVE, bool GLOBAL>
+template <bool NATIVE, bool GLOBAL, bool WINDOW = false>
 __global__ __launch_bounds__(THREADS) void articulate_kernel(const ArtArgs k) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const Args& a = k.a;
@@ -462,6 +478,7 @@ __global__ __launch_bounds__(THREADS) void articulate_kernel(const ArtArgs k) {
     if (rot)
         for (int q = t.live * J + tid; q < t.cnt * J; q += THREADS) *reinterpret_cast<f4*>(rot + 4ll * q) = f4{0.f, 0.f, 0.f, 0.f};
     if (t.live == 0) return;
+    const int zh = zero_head<WINDOW>(a, t);
     const int nlev = min(max(a.table[0], 1), J);
     for (int l = tid; l <= nlev; l += THREADS) lv[l] = min(max(a.table[AL_FIRST + l], 0), J);
     for (int j = tid; j < J; j += THREADS) {
@@ -485,7 +502,10 @@ __global__ __launch_bounds__(THREADS) void articulate_kernel(const ArtArgs k) {
             float* sj = st + j * AST + fr;
 #pragma unroll
             for (int e = 0; e < 9; ++e) sj[e * TFA] = R[e];
-            if (!GLOBAL && rot) *reinterpret_cast<f4*>(rot + ((long long)fr * J + j) * 4) = quat_of(R);
+            if (!GLOBAL && rot) {
+                if (WINDOW && fr < zh) *reinterpret_cast<f4*>(rot + ((long long)fr * J + j) * 4) = f4{0.f, 0.f, 0.f, 0.f};
+                else *reinterpret_cast<f4*>(rot + ((long long)fr * J + j) * 4) = quat_of(R);
+            }
         }
         __syncthreads();                                                        // xin is free from here on; the chain reads R from the tile
         // Phase 2, the chain, only where something needs it: G_j replaces R_j in the joint's plane (its owner reads R_j and writes G_j; nobody
@@ -521,13 +541,17 @@ __global__ __launch_bounds__(THREADS) void articulate_kernel(const ArtArgs k) {
                 }
 #pragma unroll
                 for (int e = 0; e < 3; ++e) sj[(9 + e) * TFA] = pos[e];
-                if (GLOBAL && rot) *reinterpret_cast<f4*>(rot + ((long long)fr * J + j) * 4) = quat_of(G);
+                if (GLOBAL && rot) {
+                    if (WINDOW && fr < zh) *reinterpret_cast<f4*>(rot + ((long long)fr * J + j) * 4) = f4{0.f, 0.f, 0.f, 0.f};
+                    else *reinterpret_cast<f4*>(rot + ((long long)fr * J + j) * 4) = quat_of(G);
+                }
             }
             __syncthreads();                                                    // a level reads what the level before wrote
         }
         if (a.dst)                                                              // the positions of the pass, from the state tile
             store_range(a.dst, f0 * J3, J3, (f0 + i) * J3, (f0 + ps.i1) * J3, [&](int fr, int r) {
                 const int jt = r / 3;
+                if (WINDOW && fr < zh) return 0.f;
                 return st[jt * AST + (9 + r - 3 * jt) * TFA + fr];
             });
     }
@@ -596,7 +620,7 @@ __device__ __forceinline__ Axes order_axes(int code) {
     return {i, j, k, j == (i == 2 ? 0 : i + 1) ? 1.f : -1.f};
 }
 
-template <bool NATIVE>
+template <bool NATIVE, bool WINDOW = false>
 __global__ __launch_bounds__(THREADS) void articulate_euler_kernel(const EulArgs k) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const Args& a = k.a;
@@ -609,6 +633,7 @@ __global__ __launch_bounds__(THREADS) void articulate_euler_kernel(const EulArgs
     const long long f0 = (long long)t.b * a.T_out + t.k0;
     zero_tail(a.dst, f0 * J3, J3, t);
     if (t.live == 0) return;
+    const int zh = zero_head<WINDOW>(a, t);
     for (int j = tid; j < J; j += THREADS) ord[j] = min(max(k.orders[j], 0), 5);
     const bool has_mean = a.mean != nullptr;
     load_mean(a, mn);
@@ -637,7 +662,7 @@ __global__ __launch_bounds__(THREADS) void articulate_euler_kernel(const EulArgs
             e3[0] = ea * k.scale; e3[1] = eb * k.scale; e3[2] = ec * k.scale;
         }
         __syncthreads();
-        store_range(a.dst, f0 * J3, J3, (f0 + i) * J3, (f0 + ps.i1) * J3, [&](int fr, int r) { return eo[fr * J3 + r]; });
+        store_range(a.dst, f0 * J3, J3, (f0 + i) * J3, (f0 + ps.i1) * J3, [&](int fr, int r) { return WINDOW && fr < zh ? 0.f : eo[fr * J3 + r]; });
     }
 }
 
@@ -725,13 +750,20 @@ int common_checks(const char* who, const void* src, const void* dst, int B, int 
 
 // What eg_skeleton_joints and eg_skeleton_rotations check behind their own arguments, in the header's order -- the rate, out_stride, the grid
 // and the index range of an output of `per_frame` floats per frame -- and the rest of the kernel's arguments: a.L, a.M, a.tiles, a.T_out.
-// `tile`: the output frames of one workgroup.
-int forward_args(const char* who, Args& a, int L, int M, long long out_stride, int per_frame, int tile = TF) {
+// `tile`: the output frames of one workgroup.  `window`: the window form, whose out_stride is the output limit, 1 .. t_out, and whose
+// a.frames is the [2][rows] table of zero_head.
+int forward_args(const char* who, Args& a, int L, int M, long long out_stride, int per_frame, int tile = TF, bool window = false) {
     int rc = reduce_rate(who, L, M);
     if (rc != EG_OK) return rc;
     const long long t_out = out_frames(a.T, L, M);
-    EG_REQUIRE(out_stride >= t_out, EG_ERR_BAD_ARG, "%s: out_stride=%lld < %lld output frames of %d input frames at L=%d / M=%d", who, out_stride,
-               t_out, a.T, L, M);
+    if (window) {
+        EG_REQUIRE(a.frames, EG_ERR_BAD_ARG, "%s: null d_window (device int32 [2, rows]: valid frames | zeroed head)", who);
+        EG_REQUIRE(out_stride >= 1 && out_stride <= t_out, EG_ERR_BAD_ARG, "%s: out_frames=%lld outside 1 .. %lld, the output frames of %d input frames at L=%d / M=%d",
+                   who, out_stride, t_out, a.T, L, M);
+    } else {
+        EG_REQUIRE(out_stride >= t_out, EG_ERR_BAD_ARG, "%s: out_stride=%lld < %lld output frames of %d input frames at L=%d / M=%d", who, out_stride,
+                   t_out, a.T, L, M);
+    }
     const long long tiles = (out_stride + tile - 1) / tile;
     EG_REQUIRE(tiles * a.B <= 0x7fffffffll && (long long)a.B * out_stride * per_frame < (1ll << 40), EG_ERR_UNSUPPORTED,
                "%s: rows=%d x out_stride=%lld: grid / index range", who, a.B, out_stride);
@@ -782,19 +814,40 @@ extern "C" int64_t eg_skeleton_out_frames(int64_t n, int32_t L, int32_t M) {
 
 extern "C" int32_t eg_skeleton_tile_frames(void) { return TF; }
 
-extern "C" int eg_skeleton_joints(const float* track, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children, const float* lengths,
-                                  int32_t bones, const void* d_table, const int32_t* d_frames, int32_t draws, int32_t frame_unit,
-                                  const float* d_mean, int32_t unit, int32_t L, int32_t M, float* joints, int64_t out_stride, void* stream) {
-    const char* who = "eg_skeleton_joints";
+namespace {
+// Both forms of a forward call share one body: `window` picks the checks of the output limit and the WINDOW instantiation.
+int joints_call(const char* who, bool window, const float* track, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children,
+                const float* lengths, int32_t bones, const void* d_table, const int32_t* d_frames, int32_t draws, int32_t frame_unit,
+                const float* d_mean, int32_t unit, int32_t L, int32_t M, float* joints, int64_t out_stride, void* stream) {
     int rc = common_checks(who, track, joints, rows, T, parents, children, lengths, bones, d_table, d_frames, draws, frame_unit, d_mean);
     if (rc != EG_OK) return rc;
     Args a = {track, static_cast<const int*>(d_table), d_frames, d_mean, joints, rows, T, bones, draws, frame_unit};
-    rc = forward_args(who, a, L, M, out_stride, 3 * (bones + 1));
+    rc = forward_args(who, a, L, M, out_stride, 3 * (bones + 1), TF, window);
     if (rc != EG_OK) return rc;
     const bool native = a.L == 1 && a.M == 1;
-    return launch(unit ? (native ? skeleton_joints_kernel<true, true> : skeleton_joints_kernel<true, false>)
-                       : (native ? skeleton_joints_kernel<false, true> : skeleton_joints_kernel<false, false>),
-                  a, HEAD + round4(SLOTS * 3 * bones + 8) + (bones + 1) * NC, stream, "skeleton_joints");
+    void (*kernel)(Args);
+    if (window)
+        kernel = unit ? (native ? skeleton_joints_kernel<true, true, true> : skeleton_joints_kernel<true, false, true>)
+                      : (native ? skeleton_joints_kernel<false, true, true> : skeleton_joints_kernel<false, false, true>);
+    else
+        kernel = unit ? (native ? skeleton_joints_kernel<true, true> : skeleton_joints_kernel<true, false>)
+                      : (native ? skeleton_joints_kernel<false, true> : skeleton_joints_kernel<false, false>);
+    return launch(kernel, a, HEAD + round4(SLOTS * 3 * bones + 8) + (bones + 1) * NC, stream, window ? "skeleton_joints_window" : "skeleton_joints");
+}
+}  // namespace
+
+extern "C" int eg_skeleton_joints(const float* track, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children, const float* lengths,
+                                  int32_t bones, const void* d_table, const int32_t* d_frames, int32_t draws, int32_t frame_unit,
+                                  const float* d_mean, int32_t unit, int32_t L, int32_t M, float* joints, int64_t out_stride, void* stream) {
+    return joints_call("eg_skeleton_joints", false, track, rows, T, parents, children, lengths, bones, d_table, d_frames, draws, frame_unit, d_mean,
+                       unit, L, M, joints, out_stride, stream);
+}
+
+extern "C" int eg_skeleton_joints_window(const float* window, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children,
+                                         const float* lengths, int32_t bones, const void* d_table, const int32_t* d_window, const float* d_mean,
+                                         int32_t unit, int32_t L, int32_t M, float* joints, int64_t out_frames, void* stream) {
+    return joints_call("eg_skeleton_joints_window", true, window, rows, T, parents, children, lengths, bones, d_table, d_window, 1, 1, d_mean, unit, L,
+                       M, joints, out_frames, stream);
 }
 
 extern "C" int eg_skeleton_dir_vec(const float* joints, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children, const float* lengths,
@@ -855,23 +908,44 @@ extern "C" int eg_skeleton_levels(const int32_t* parents, const int32_t* childre
     return EG_OK;
 }
 
-extern "C" int eg_skeleton_rotations(const float* track, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children,
-                                     const float* lengths, int32_t bones, const double* rest, const void* d_levels, const int32_t* d_frames,
-                                     int32_t draws, int32_t frame_unit, const float* d_mean, int32_t space, int32_t L, int32_t M,
-                                     float* rotations, int64_t out_stride, void* stream) {
-    const char* who = "eg_skeleton_rotations";
+namespace {
+int rotations_call(const char* who, bool window, const float* track, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children,
+                   const float* lengths, int32_t bones, const double* rest, const void* d_levels, const int32_t* d_frames, int32_t draws,
+                   int32_t frame_unit, const float* d_mean, int32_t space, int32_t L, int32_t M, float* rotations, int64_t out_stride, void* stream) {
     int rc = common_checks(who, track, rotations, rows, T, parents, children, lengths, bones, d_levels, d_frames, draws, frame_unit, d_mean);
     if (rc != EG_OK) return rc;
     rc = check_rest(who, rest, bones);
     if (rc != EG_OK) return rc;
     EG_REQUIRE(space == EG_SKELETON_SPACE_LOCAL || space == EG_SKELETON_SPACE_GLOBAL, EG_ERR_BAD_ARG, "%s: space=%d (0: local, 1: global)", who, space);
     Args a = {track, static_cast<const int*>(d_levels), d_frames, d_mean, rotations, rows, T, bones, draws, frame_unit};
-    rc = forward_args(who, a, L, M, out_stride, 4 * bones);
+    rc = forward_args(who, a, L, M, out_stride, 4 * bones, TF, window);
     if (rc != EG_OK) return rc;
-    const bool native = a.L == 1 && a.M == 1;
-    return launch(space == EG_SKELETON_SPACE_GLOBAL ? (native ? skeleton_rotations_kernel<true, true> : skeleton_rotations_kernel<false, true>)
-                                                    : (native ? skeleton_rotations_kernel<true, false> : skeleton_rotations_kernel<false, false>),
-                  a, RHEAD + round4(SLOTS * 3 * bones + 8) + bones * 4 * TF, stream, "skeleton_rotations");
+    const bool native = a.L == 1 && a.M == 1, glob = space == EG_SKELETON_SPACE_GLOBAL;
+    void (*kernel)(Args);
+    if (window)
+        kernel = glob ? (native ? skeleton_rotations_kernel<true, true, true> : skeleton_rotations_kernel<false, true, true>)
+                      : (native ? skeleton_rotations_kernel<true, false, true> : skeleton_rotations_kernel<false, false, true>);
+    else
+        kernel = glob ? (native ? skeleton_rotations_kernel<true, true> : skeleton_rotations_kernel<false, true>)
+                      : (native ? skeleton_rotations_kernel<true, false> : skeleton_rotations_kernel<false, false>);
+    return launch(kernel, a, RHEAD + round4(SLOTS * 3 * bones + 8) + bones * 4 * TF, stream, window ? "skeleton_rotations_window" : "skeleton_rotations");
+}
+}  // namespace
+
+extern "C" int eg_skeleton_rotations(const float* track, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children,
+                                     const float* lengths, int32_t bones, const double* rest, const void* d_levels, const int32_t* d_frames,
+                                     int32_t draws, int32_t frame_unit, const float* d_mean, int32_t space, int32_t L, int32_t M,
+                                     float* rotations, int64_t out_stride, void* stream) {
+    return rotations_call("eg_skeleton_rotations", false, track, rows, T, parents, children, lengths, bones, rest, d_levels, d_frames, draws,
+                          frame_unit, d_mean, space, L, M, rotations, out_stride, stream);
+}
+
+extern "C" int eg_skeleton_rotations_window(const float* window, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children,
+                                            const float* lengths, int32_t bones, const double* rest, const void* d_levels, const int32_t* d_window,
+                                            const float* d_mean, int32_t space, int32_t L, int32_t M, float* rotations, int64_t out_frames,
+                                            void* stream) {
+    return rotations_call("eg_skeleton_rotations_window", true, window, rows, T, parents, children, lengths, bones, rest, d_levels, d_window, 1, 1,
+                          d_mean, space, L, M, rotations, out_frames, stream);
 }
 
 // ---- articulated bodies: host ---------------------------------------------------------------------------------------------------------------
@@ -936,11 +1010,10 @@ extern "C" int eg_articulate_levels(const int32_t* parents, const float* offsets
     return EG_OK;
 }
 
-extern "C" int eg_articulate_forward(const float* track, int32_t rows, int32_t T, const int32_t* parents, const float* offsets, int32_t joints,
-                                     const void* d_table, const int32_t* d_frames, int32_t draws, int32_t frame_unit, const float* d_mean,
-                                     int32_t basis, int32_t space, int32_t L, int32_t M, float* out_joints, float* out_rotations, int64_t out_stride,
-                                     void* stream) {
-    const char* who = "eg_articulate_forward";
+namespace {
+int articulate_call(const char* who, bool window, const float* track, int32_t rows, int32_t T, const int32_t* parents, const float* offsets,
+                    int32_t joints, const void* d_table, const int32_t* d_frames, int32_t draws, int32_t frame_unit, const float* d_mean,
+                    int32_t basis, int32_t space, int32_t L, int32_t M, float* out_joints, float* out_rotations, int64_t out_stride, void* stream) {
     EG_REQUIRE(out_joints || out_rotations, EG_ERR_BAD_ARG, "%s: null out_joints and out_rotations (need one of them)", who);
     EG_REQUIRE(d_table, EG_ERR_BAD_ARG, "%s: null d_table", who);
     int rc = check_body(who, parents, offsets, joints);
@@ -953,12 +1026,34 @@ extern "C" int eg_articulate_forward(const float* track, int32_t rows, int32_t T
     EG_REQUIRE((long long)rows * T * 6 * joints < (1ll << 40), EG_ERR_UNSUPPORTED, "%s: rows=%d x frames=%d: index range", who, rows, T);
     ArtArgs k = {{track, static_cast<const int*>(d_table), d_frames, d_mean, out_joints, rows, T, 2 * joints, draws, frame_unit}, out_rotations, joints,
                  basis == EG_ARTICULATE_BASIS_COLUMNS};
-    rc = forward_args(who, k.a, L, M, out_stride, 4 * joints, TFA);
+    rc = forward_args(who, k.a, L, M, out_stride, 4 * joints, TFA, window);
     if (rc != EG_OK) return rc;
-    const bool native = k.a.L == 1 && k.a.M == 1;
-    return launch(space == EG_SKELETON_SPACE_GLOBAL ? (native ? articulate_kernel<true, true> : articulate_kernel<false, true>)
-                                                    : (native ? articulate_kernel<true, false> : articulate_kernel<false, false>),
-                  k.a, k, AHEAD + round4(SLA * 6 * joints + 8) + joints * AST, stream, "articulate_forward");
+    const bool native = k.a.L == 1 && k.a.M == 1, glob = space == EG_SKELETON_SPACE_GLOBAL;
+    void (*kernel)(ArtArgs);
+    if (window)
+        kernel = glob ? (native ? articulate_kernel<true, true, true> : articulate_kernel<false, true, true>)
+                      : (native ? articulate_kernel<true, false, true> : articulate_kernel<false, false, true>);
+    else
+        kernel = glob ? (native ? articulate_kernel<true, true> : articulate_kernel<false, true>)
+                      : (native ? articulate_kernel<true, false> : articulate_kernel<false, false>);
+    return launch(kernel, k.a, k, AHEAD + round4(SLA * 6 * joints + 8) + joints * AST, stream, window ? "articulate_forward_window" : "articulate_forward");
+}
+}  // namespace
+
+extern "C" int eg_articulate_forward(const float* track, int32_t rows, int32_t T, const int32_t* parents, const float* offsets, int32_t joints,
+                                     const void* d_table, const int32_t* d_frames, int32_t draws, int32_t frame_unit, const float* d_mean,
+                                     int32_t basis, int32_t space, int32_t L, int32_t M, float* out_joints, float* out_rotations, int64_t out_stride,
+                                     void* stream) {
+    return articulate_call("eg_articulate_forward", false, track, rows, T, parents, offsets, joints, d_table, d_frames, draws, frame_unit, d_mean,
+                           basis, space, L, M, out_joints, out_rotations, out_stride, stream);
+}
+
+extern "C" int eg_articulate_forward_window(const float* window, int32_t rows, int32_t T, const int32_t* parents, const float* offsets,
+                                            int32_t joints, const void* d_table, const int32_t* d_window, const float* d_mean, int32_t basis,
+                                            int32_t space, int32_t L, int32_t M, float* out_joints, float* out_rotations, int64_t out_frames,
+                                            void* stream) {
+    return articulate_call("eg_articulate_forward_window", true, window, rows, T, parents, offsets, joints, d_table, d_window, 1, 1, d_mean, basis,
+                           space, L, M, out_joints, out_rotations, out_frames, stream);
 }
 
 extern "C" int eg_articulate_rot6d(const float* quat, int32_t rows, int32_t T, int32_t joints, const int32_t* d_frames, int32_t draws,
@@ -989,10 +1084,10 @@ int check_orders(const char* who, const int32_t* orders, const void* d_orders, i
 
 }  // namespace
 
-extern "C" int eg_articulate_euler(const float* track, int32_t rows, int32_t T, int32_t joints, const int32_t* orders, const void* d_orders,
-                                   const int32_t* d_frames, int32_t draws, int32_t frame_unit, const float* d_mean, int32_t basis,
-                                   int32_t degrees, int32_t L, int32_t M, float* euler, int64_t out_stride, void* stream) {
-    const char* who = "eg_articulate_euler";
+namespace {
+int euler_call(const char* who, bool window, const float* track, int32_t rows, int32_t T, int32_t joints, const int32_t* orders, const void* d_orders,
+               const int32_t* d_frames, int32_t draws, int32_t frame_unit, const float* d_mean, int32_t basis, int32_t degrees, int32_t L, int32_t M,
+               float* euler, int64_t out_stride, void* stream) {
     EG_REQUIRE(euler, EG_ERR_BAD_ARG, "%s: null output", who);
     int rc = check_orders(who, orders, d_orders, joints);
     if (rc != EG_OK) return rc;
@@ -1002,11 +1097,28 @@ extern "C" int eg_articulate_euler(const float* track, int32_t rows, int32_t T, 
     EG_REQUIRE((long long)rows * T * 6 * joints < (1ll << 40), EG_ERR_UNSUPPORTED, "%s: rows=%d x frames=%d: index range", who, rows, T);
     EulArgs k = {{track, nullptr, d_frames, d_mean, euler, rows, T, 2 * joints, draws, frame_unit}, static_cast<const int*>(d_orders), joints,
                  basis == EG_ARTICULATE_BASIS_COLUMNS, degrees ? (float)(180.0 / M_PI) : 1.f};
-    rc = forward_args(who, k.a, L, M, out_stride, 3 * joints, TFA);
+    rc = forward_args(who, k.a, L, M, out_stride, 3 * joints, TFA, window);
     if (rc != EG_OK) return rc;
     const bool native = k.a.L == 1 && k.a.M == 1;
-    return launch(native ? articulate_euler_kernel<true> : articulate_euler_kernel<false>, k.a, k,
-                  EHEAD + round4(SLA * 6 * joints + 8) + TFA * 3 * joints, stream, "articulate_euler");
+    void (*kernel)(EulArgs);
+    if (window) kernel = native ? articulate_euler_kernel<true, true> : articulate_euler_kernel<false, true>;
+    else kernel = native ? articulate_euler_kernel<true> : articulate_euler_kernel<false>;
+    return launch(kernel, k.a, k, EHEAD + round4(SLA * 6 * joints + 8) + TFA * 3 * joints, stream, window ? "articulate_euler_window" : "articulate_euler");
+}
+}  // namespace
+
+extern "C" int eg_articulate_euler(const float* track, int32_t rows, int32_t T, int32_t joints, const int32_t* orders, const void* d_orders,
+                                   const int32_t* d_frames, int32_t draws, int32_t frame_unit, const float* d_mean, int32_t basis,
+                                   int32_t degrees, int32_t L, int32_t M, float* euler, int64_t out_stride, void* stream) {
+    return euler_call("eg_articulate_euler", false, track, rows, T, joints, orders, d_orders, d_frames, draws, frame_unit, d_mean, basis, degrees, L,
+                      M, euler, out_stride, stream);
+}
+
+extern "C" int eg_articulate_euler_window(const float* window, int32_t rows, int32_t T, int32_t joints, const int32_t* orders, const void* d_orders,
+                                          const int32_t* d_window, const float* d_mean, int32_t basis, int32_t degrees, int32_t L, int32_t M,
+                                          float* euler, int64_t out_frames, void* stream) {
+    return euler_call("eg_articulate_euler_window", true, window, rows, T, joints, orders, d_orders, d_window, 1, 1, d_mean, basis, degrees, L, M,
+                      euler, out_frames, stream);
 }
 
 extern "C" int eg_articulate_rot6d_euler(const float* euler, int32_t rows, int32_t T, int32_t joints, const int32_t* orders, const void* d_orders,

@@ -1104,7 +1104,8 @@ class TrackOutputs:
         self._mean, self._rotations, self._device = joints_mean, rotations, None
         if streaming and joints_fps is not None:
             raise L.EgError(f"{who}: joints_fps= is not supported (a frame-rate change needs the frame after the last one emitted, which a "
-                            "stream does not have yet); resample the joints of the finished track with skeleton.joints_from_tracks(..., fps=)")
+                            "stream does not have yet); resample the joints of the finished track with skeleton.joints_from_tracks(..., fps=); in a live "
+                            "session: render=")
         if rotations is not None and joints is None:
             raise L.EgError(f"{who}: rotations= without joints=skeleton (the rest pose belongs to a skeleton's bones)")
         if pose_dim is not None:

@@ -22,6 +22,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib as L
+from . import render as RD
 from . import skeleton as SK
 from . import smooth as SM
 from ._host import int_list, need_cuda as _need_cuda
@@ -169,12 +170,21 @@ class GestureStream:
     that was not valid, None while `rows` is None.  `tail_smooth()`: the last `[U, P + half, D]` smoothed frames.  A row's `last_smooth`,
     concatenated after dropping step 0's leading `half` entries, followed by `tail_smooth()`, is smooth.smooth_tracks on its finished track bit
     for bit.  `reset(rows=)` resets the smoothing state of those rows.  Not together with `joints=`: the first `half` entries of step 0 are not
-    poses."""
+    poses.
+    `render=RenderSpec | dict` (render.RenderSpec: `joints`, `mean`, `unit`, `fps=(src, dst)`, `rotations`, `rotations_space`, `euler`, `smooth`):
+    the delayed output stage, independent of the arguments above -- what `smooth=` with `joints=` and `joints_fps=` refuse.  Every step ends
+    with the launches of a render.StreamRender (inside the graph) that leave in `last_render = {name: [U, render_frames, ., .]}` the smoothed
+    joints / rotations / Euler channels at the output rate, `render_delay` source frames behind the rows just emitted (`render_delay / fps`
+    seconds); the first `render_lead` entries of a row's first valid step are zeros, a row that was not valid has zeros, None while `rows` is
+    None.  `tail_render()`: the last output frames.  For every name a row's `last_render`, concatenated after dropping the first step's
+    leading `render_lead` entries, followed by `tail_render()`, is `harness.synthesize(smooth=, joints=, rotations=, euler=, joints_fps=)` on
+    its finished track bit for bit."""
 
     def __init__(self, models: Tuple, rows: int, seed_pose: torch.Tensor, *, hop_samples: Optional[int] = None, n_samples: Optional[int] = None,
                  fps: int = 15, sample_rate: int = 16000, alpha: Optional[torch.Tensor] = None, graph: bool = True, want_windows: bool = False,
                  draws: Optional[int] = None, audio_rate: Optional[int] = None, joints=None, joints_mean=None, joints_unit: bool = False,
-                 joints_fps=None, rotations=None, rotations_space: str = "local", smooth=None, euler=None, euler_unwrap: bool = False):
+                 joints_fps=None, rotations=None, rotations_space: str = "local", smooth=None, euler=None, euler_unwrap: bool = False,
+                 render=None):
         # the output stage: what needs no model is checked here, the rest once pose_dim is known
         outputs = SK.TrackOutputs("GestureStream", joints, joints_mean, joints_unit, joints_fps, rotations, rotations_space, euler, euler_unwrap,
                                   streaming=True)
@@ -182,8 +192,9 @@ class GestureStream:
             if joints is not None:
                 raise L.EgError("GestureStream: smooth= together with joints= is not supported (the smoothed rows run half a window behind and "
                                 "the first `half` entries of step 0 are not poses); take joints from the raw rows, or smooth the finished "
-                                "track with harness.synthesize(..., smooth=, joints=)")
+                                "track with harness.synthesize(..., smooth=, joints=); in a live session: render=")
             smooth = SM.Smoother.of(smooth, "GestureStream: smooth", fps)
+        render = None if render is None else RD.RenderSpec.of(render)          # refuses what needs no model
         if draws is not None:
             raise L.EgError("GestureStream: draws= is not supported (a stream has one track per row); for several sampled tracks of a whole "
                             "recording call the rectangular synthesize(..., draws=R), or open the stream with each speaker's row repeated")
@@ -253,6 +264,9 @@ class GestureStream:
         # the smoother's state, table and output are held here: the captured graph replays their addresses
         self._sm = None if smooth is None else SM.StreamSmoother(self.U, self.H, self.D, smooth, device=dev)
         self.smooth_delay: Optional[int] = None if self._sm is None else self._sm.delay
+        # the delayed output stage, with a smoother, a delay line and outputs of its own: static buffers, as above
+        self._rd = None if render is None else RD.StreamRender(self.U, self.H, self.P, self.D, render, device=dev, src_fps=fps)
+        self.render_delay, self.render_frames, self.render_lead = (None,) * 3 if self._rd is None else (self._rd.delay, self._rd.frames, self._rd.lead)
         self._graphs: Dict[bool, dict] = {}
         self.last_valid: List[bool] = [False] * self.U           # the host's verdict for the last step, and the window index per valid row
         self.last_windows: List[Optional[int]] = [None] * self.U
@@ -261,6 +275,7 @@ class GestureStream:
         self.last_rotations: Optional[torch.Tensor] = None       # with rotations=: their bone rotations [U, H, K, 4], under the same rules
         self.last_euler: Optional[torch.Tensor] = None           # with euler=: their Euler channels [U, H, J, 3] in degrees (principal values), likewise
         self.last_smooth: Optional[torch.Tensor] = None          # with smooth=: the smoothed frames [U, H, D], smooth_delay frames behind the rows
+        self.last_render: Optional[Dict[str, torch.Tensor]] = None       # with render=: {name: [U, render_frames, ., .]}, render_delay frames behind the rows
         eng.stream_reset(self._state, *self._geom, self.seed_pose)
 
     # ---- engines, staleness ----
@@ -319,6 +334,8 @@ class GestureStream:
                 out.update(self._outs.launch(out["rows"], out["valid"], 1, self.H))
             if self._sm is not None:                # the outputs, then the new history in a launch of its own
                 out["smooth"] = self._sm.run(out["rows"], out["valid"])
+            if self._rd is not None:                # the delayed stage: its smoother, its delay line, then the output launches
+                out["render"] = self._rd.run(out["rows"], out["valid"])
             return out
 
     def _push_only(self):
@@ -334,6 +351,7 @@ class GestureStream:
         snap = self._state.clone()
         rs_snap = self._rs.snapshot() if self._rs is not None else None      # the resampler's history advances with every run, too
         sm_snap = self._sm.snapshot() if self._sm is not None else None      # and the smoother's
+        rd_snap = self._rd.snapshot() if self._rd is not None else None      # and the render stage's
         cap = torch.cuda.Stream(dev)
         cap.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(cap):
@@ -349,6 +367,8 @@ class GestureStream:
             self._rs.restore(rs_snap)
         if self._sm is not None:
             self._sm.restore(sm_snap)
+        if self._rd is not None:
+            self._rd.restore(rd_snap)
         torch.cuda.synchronize(dev)
         # the graph replays raw pointers into the engines' arenas and workspaces: keep them alive as long as the graph (ClipPipeline._capture)
         st = self._engine_state()
@@ -449,6 +469,7 @@ class GestureStream:
         self.last_joints, self.last_rotations, self.last_euler = (out[name].clone() if out is not None and name in out else None
                                                                   for name in ("joints", "rotations", "euler"))
         self.last_smooth = out["smooth"].clone() if out is not None and self._sm is not None else None
+        self.last_render = {n: v.clone() for n, v in out["render"].items()} if out is not None and self._rd is not None else None
         if out is None:
             return None, torch.zeros(self.U, dtype=torch.int32, device=self.device)
         return out["rows"].clone(), out["valid"].clone()
@@ -500,6 +521,8 @@ class GestureStream:
             self._rs.reset(None if len(sel) == self.U else sel)
         if self._sm is not None:
             self._sm.reset(None if len(sel) == self.U else sel)
+        if self._rd is not None:
+            self._rd.reset(None if len(sel) == self.U else sel)
 
     def tail(self) -> torch.Tensor:
         """[U, P, D]: every row's current prior = the last P rows of its track."""
@@ -530,6 +553,14 @@ class GestureStream:
             raise L.EgError("tail_smooth: the session was opened without smooth=")
         with torch.no_grad():
             return self._sm.tail(self.tail())
+
+    def tail_render(self) -> Dict[str, torch.Tensor]:
+        """{name: [U, n_tail, ., .]}: the last output frames of every row's track (a session opened with render=); zeros for a row that has
+        emitted nothing."""
+        if self._rd is None:
+            raise L.EgError("tail_render: the session was opened without render=")
+        with torch.no_grad():
+            return self._rd.tail(self.tail())
 
     def finish(self, text, labels=None, z=None, sampled=None, last_chunk=None, ends=None) -> torch.Tensor:
         """End every row together and run R = text.shape[1] steps in all: `text [U, R, text_len]`, `labels [U, 8]` or `[U, R, 8]`, `z [U, R, 32]`

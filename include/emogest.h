@@ -796,6 +796,58 @@ int eg_smooth_stream_tail(const void* state, int32_t rows, int32_t P, int32_t D,
                           float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Delayed output stage of a stream: smoothed joints, rotations and Euler channels at a renderer's frame rate (csrc/render_stream.hip,
+ * csrc/skeleton.hip)
+ * ------------------------------------------------------------------------------------------ */
+/* A stream emits H pose frames per step.  The Savitzky-Golay filter needs `half` frames behind a frame, the interpolator of a frame-rate
+ * change (L / M reduced, eg_skeleton_joints) the source frame after it.  Let the output run d source frames behind the rows just emitted:
+ *     d0 = half + (L == M ? 0 : 1);   d = M ceil(d0 / M);   delta = d - half;   Hout = H L / M;   lead = d L / M
+ * (H a multiple of M, d <= H; the caller's to check).  With y the smoothed track (eg_smooth_stream_push's output, which starts at frame
+ * sH - half in a row's s-th valid step; or the raw track with half = 0), that step's outputs are the first Hout output frames of the
+ * window y[sH - d .. sH - d + W), W = H + (L != M), run as a row of its own: d L / M and H L / M are integers, so the window starts at phase 0
+ * and its output frame j is output frame (sH - d) L / M + j of the whole track -- the same lo, the same weight (k' M - lo L) / L in integers,
+ * the same arithmetic, and the clamp lo <= n - 2 is never reached: the same bits.  Frames before frame 0 do not exist: the first `lead`
+ * outputs of a row's first valid step are zeros.
+ * Delay line.  state: the last delta frames of y [rows, delta, D] fp32, then an int32 count of valid steps per row, in a caller-owned
+ * device buffer of eg_render_stream_state_bytes (0 for refused arguments), 16-byte aligned.  0 <= delta <= EG_RENDER_STREAM_MAX_DELTA.
+ * eg_render_stream_reset zeroes history and count of the rows with row_mask[u] != 0 (device int32 [rows]; NULL: every row).
+ * eg_render_stream_push: chunk [rows, H, D] and d_valid (device int32 [rows]; NULL: every row) -> window [rows, frames, D] =
+ * history | chunk[0 .. frames - delta) for the valid rows (delta < frames <= delta + H; the window of a row that is not valid is not
+ * written and never read), and d_window, device int32 [2, rows]: the valid frames of every row's window (frames, or 0) | its zeroed head
+ * (lead in a row's first valid step, else 0).  Then, in a launch of their own, the new history -- the chunk's last delta frames -- and
+ * the count, for the valid rows; the state of a row that is not valid stays.  Two launches, nothing that depends on the step index.
+ * eg_render_stream_tail: last [rows, F, D], the last F frames of y (eg_smooth_stream_tail's P + half, or eg_stream_tail's P) ->
+ * window [rows, delta + F, D] = history | last and d_window = (delta + F, or 0 for a row without a valid step) | 0: the window
+ * y[SH - d .. T) of a track of S steps, whose outputs as an ordinary row of delta + F frames are the track's last ceil((d + P) L / M)
+ * output frames, its extrapolated last frames included (the clamp falls on the same frame).  One launch; the state is read only.
+ * One owning thread per element, 16-byte stores where a quad lies inside a row, no atomics, no memset.
+ * Window form of the forward kernels.  eg_skeleton_joints_window, eg_skeleton_rotations_window, eg_articulate_forward_window and
+ * eg_articulate_euler_window are eg_skeleton_joints, eg_skeleton_rotations, eg_articulate_forward and eg_articulate_euler on
+ * window [rows, T, .] with draws = frame_unit = 1 and two differences: the output has out_frames frames per row, 1 <= out_frames <=
+ * ceil(T L / M) -- frames from there on are not made --, and d_window (device int32 [2, rows], required) gives every row's valid source
+ * frames n and, behind them, the number of its leading output frames that are written as zeros.  Every other output frame has the bits
+ * of the whole-track call on the same row.  They are separate instantiations of the same kernels; the whole-track calls are unchanged. */
+#define EG_RENDER_STREAM_MAX_DELTA 64
+int64_t eg_render_stream_state_bytes(int32_t rows, int32_t D, int32_t delta);
+int eg_render_stream_reset(void* state, int32_t rows, int32_t D, int32_t delta, const int32_t* row_mask, void* stream);
+int eg_render_stream_push(void* state, int32_t rows, int32_t H, int32_t D, int32_t delta, int32_t frames, int32_t lead, const float* chunk,
+                          const int32_t* d_valid, float* window, int32_t* d_window, void* stream);
+int eg_render_stream_tail(const void* state, int32_t rows, int32_t F, int32_t D, int32_t delta, const float* last, float* window,
+                          int32_t* d_window, void* stream);
+int eg_skeleton_joints_window(const float* window, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children,
+                              const float* lengths, int32_t bones, const void* d_table, const int32_t* d_window, const float* d_mean,
+                              int32_t unit, int32_t L, int32_t M, float* joints, int64_t out_frames, void* stream);
+int eg_skeleton_rotations_window(const float* window, int32_t rows, int32_t T, const int32_t* parents, const int32_t* children,
+                                 const float* lengths, int32_t bones, const double* rest, const void* d_levels, const int32_t* d_window,
+                                 const float* d_mean, int32_t space, int32_t L, int32_t M, float* rotations, int64_t out_frames, void* stream);
+int eg_articulate_forward_window(const float* window, int32_t rows, int32_t T, const int32_t* parents, const float* offsets, int32_t joints,
+                                 const void* d_table, const int32_t* d_window, const float* d_mean, int32_t basis, int32_t space, int32_t L,
+                                 int32_t M, float* out_joints, float* out_rotations, int64_t out_frames, void* stream);
+int eg_articulate_euler_window(const float* window, int32_t rows, int32_t T, int32_t joints, const int32_t* orders, const void* d_orders,
+                               const int32_t* d_window, const float* d_mean, int32_t basis, int32_t degrees, int32_t L, int32_t M, float* euler,
+                               int64_t out_frames, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion statistics of whole tracks: mean speed, acceleration and jerk per joint and a histogram of the joint speeds (csrc/kinematics.hip)
  * ------------------------------------------------------------------------------------------ */
 /* Input: joint positions p [rows, T, J, 3] in fp32 metres (what eg_skeleton_joints / eg_articulate_forward write).  Row b has

@@ -26,7 +26,13 @@ largest rotation angle per push.
 With --euler (and --beat --joints) the stream also gets euler= -- the channel orders of --bvh FILE, or ZXY for every joint -- and one more launch
 inside the graph leaves the BVH rotation channels of the rows just emitted in stream.last_euler [U, 50, 47, 3] (degrees, principal values: the
 Euler filter runs on a finished track, skeleton.unwrap_angles); the script prints the largest angle per push.
-usage: demo_stream.py [rows=4] [seconds=20] [--beat] [--audio-rate HZ] [--joints [--bvh FILE] [--rotations] [--euler]] [--smooth K P]"""
+With --render-fps N (TED body; optionally --smooth K P and --rotations, which then belong to the stage) the stream is opened with
+render=dict(joints=ted_expressive(), unit=True, fps=(15, N), smooth=(K, P), rotations=rest) beside the raw joints= stage: the delayed output
+stage leaves in stream.last_render the smoothed joints (and rotations) at N frames per second, stream.render_delay source frames behind the rows
+just emitted; the script prints that delay in frames and milliseconds and the wrists' frame-to-frame step in metres per second before (raw joints
+at 15 fps) and after.
+usage: demo_stream.py [rows=4] [seconds=20] [--beat] [--audio-rate HZ] [--joints [--bvh FILE] [--rotations] [--euler]] [--smooth K P]
+                      [--render-fps N [--smooth K P] [--rotations]]"""
 import os
 import sys
 import time
@@ -55,6 +61,15 @@ if "--bvh" in sys.argv:
     i = sys.argv.index("--bvh")
     BVH = sys.argv[i + 1]
     del sys.argv[i:i + 2]
+RENDER_FPS = None
+if "--render-fps" in sys.argv:
+    i = sys.argv.index("--render-fps")
+    RENDER_FPS = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
+    if BEAT:
+        sys.exit("--render-fps: this demo renders the TED body (drop --beat)")
+    if "--joints" not in sys.argv:
+        sys.argv.append("--joints")                      # the raw joints= stage stays beside it: the figure "before"
 JOINTS, JK, TREE = "--joints" in sys.argv, {}, None
 if BVH and not (BEAT and JOINTS):
     sys.exit("--bvh needs --beat --joints (a BVH hierarchy is the body of the BEAT generators' 6-D joint rotations)")
@@ -84,10 +99,11 @@ if "--smooth" in sys.argv:
     i = sys.argv.index("--smooth")
     SMOOTH = (int(sys.argv[i + 1]), int(sys.argv[i + 2]))
     del sys.argv[i:i + 3]
-    if JOINTS:
+    if JOINTS and RENDER_FPS is None:
         sys.exit("--smooth is not combined with --joints in a stream (the smoothed rows run half a window behind; smooth the finished track with "
                  "demo_synthesize.py --smooth K P --joints)")
-    JK["smooth"] = SMOOTH
+    if RENDER_FPS is None:
+        JK["smooth"] = SMOOTH
 U = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 20.0
 dev = torch.device("cuda:0")
@@ -104,7 +120,13 @@ elif ROTATIONS:                                          # the rest pose: the fi
     first = H.synthesize((gen, vae), audio[:1], torch.zeros(1, 1, 60, dtype=torch.int64, device=dev), torch.zeros(1, PRIOR, POSE_DIM, device=dev),
                          labels=torch.nn.functional.one_hot(torch.zeros(1, dtype=torch.int64), 8).float().to(dev), z=torch.zeros(1, 1, 32), **AR)
     JK["rotations"] = first["track"][0, PRIOR].reshape(-1, 3).cpu()
+if RENDER_FPS is not None:                               # the delayed stage takes the filter and the rest pose; the raw stage keeps its joints
+    JK["render"] = dict(joints=JK["joints"], unit=True, fps=(FPS, RENDER_FPS), smooth=SMOOTH, rotations=JK.get("rotations"))
+    SMOOTH = None                                        # nothing below reads last_smooth: the stream has no smooth= of its own
 stream = H.open_stream((gen, vae), U, torch.zeros(U, PRIOR, POSE_DIM, device=dev), **AR, **JK)
+if RENDER_FPS is not None:
+    print(f"render: {stream.render_frames} frames per push at {RENDER_FPS} fps, render_delay {stream.render_delay} frames = "
+          f"{1e3 * stream.render_delay / FPS:.0f} ms behind the rows just emitted (the first {stream.render_lead} entries of a row's first step are zeros)")
 hop, hop16 = stream.hop_in, stream.hop                    # samples per push at the caller's rate and at 16 kHz
 W = (to16(total) - 1) // hop16 + 1                               # windows per recording = pushes that carry its audio
 short = total // 2                                       # the leaving row's first recording; its second one has `short` samples too
@@ -170,6 +192,13 @@ for k in range(1, steps + 1):
         j = stream.last_joints
         ext = [float((j[:, :, w].amax(1) - j[:, :, w].amin(1)).norm(dim=1).max()) for w in (6, 7)]
         print(f"         last_joints {tuple(j.shape)}: wrist extent left {ext[0]:.3f} m, right {ext[1]:.3f} m")
+    if RENDER_FPS is not None and stream.last_render is not None:
+        live = valid.bool() & torch.tensor([len(tracks[u][which[u]]) > 1 for u in range(U)], device=dev)        # past the first step's leading zeros
+        if bool(live.any()):
+            speed = lambda j, rate: float((j[live][:, 1:, 6:8] - j[live][:, :-1, 6:8]).norm(dim=3).mean()) * rate
+            r = stream.last_render
+            print(f"         last_render {({n: tuple(t.shape) for n, t in r.items()})}: wrists' frame-to-frame step "
+                  f"{speed(stream.last_joints, FPS):.3f} m/s raw at {FPS} fps, {speed(r['joints'], RENDER_FPS):.3f} m/s rendered at {RENDER_FPS} fps")
     if ROTATIONS and TREE is None and stream.last_rotations is not None:
         q = stream.last_rotations[valid.bool()]             # a row that was not valid holds zeros, not rotations
         deg = [float(torch.rad2deg(2 * torch.acos(q[:, :, b, 0].clamp(max=1.0))).max()) for b in (4, 21)]      # the forearm bones
