@@ -76,6 +76,8 @@ EG_JOINTSCORE_TILE_FRAMES, EG_SRGR_MAX_JOINTS, EG_L1DIV_MAX_COLS = 32, 64, 512
 EG_EMOTION_CHUNK_WINDOWS, EG_EMOTION_MAX_CLASSES = 64, 64
 EG_TAKE_MAX_DRAWS = 64
 EG_BVH_TEXT_MAX_CHANNELS, EG_BVH_TEXT_MAX_WIDTH, EG_BVH_TEXT_TILE_FRAMES = 512, 18, 8
+EG_PREVIEW_MAX_BONES, EG_PREVIEW_MIN_SIZE, EG_PREVIEW_MAX_SIZE, EG_PREVIEW_MIN_RADIUS, EG_PREVIEW_MAX_RADIUS = 64, 8, 2048, 0.25, 16.0
+EG_PREVIEW_TABLE_WORDS, EG_PREVIEW_HWC, EG_PREVIEW_CHW = 324, 0, 1
 EG_MOTION_WINDOW, EG_MOTION_ROW_FLOATS, EG_MOTION_MAX_POSE_DIM, EG_MOTION_RUN_FRAMES = 34, 384, 128, 136
 
 # name -> (restype, argtypes).  Must list every symbol include/emogest.h declares
@@ -160,6 +162,9 @@ SIGNATURES = {
     "eg_bvh_text_workspace_bytes": (_L, [_I, _I, _I]),
     "eg_bvh_text_measure": (C.c_int, [C.POINTER(EgBvhTextArgs), _P, _L, _P, _P, _P]),
     "eg_bvh_text_write": (C.c_int, [C.POINTER(EgBvhTextArgs), _P, _P, _L, _P]),
+    "eg_preview_max_bones": (_I, []),
+    "eg_preview_check": (C.c_int, [_P, _I, _I]),
+    "eg_preview_raster": (C.c_int, [_P, _I, _I, _I, _P, _I, _P, _P, C.c_float, _I, _I, _I, _I, _I, _P, _P, _P]),
     "eg_smooth_design": (C.c_int, [_I, _I, _I, C.c_double, _P, _P]),
     "eg_smooth_tile_frames": (_I, []),
     "eg_smooth_tile_cols": (_I, []),

@@ -466,7 +466,7 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
                beat: bool = False, diversity=None, audio_rate: Optional[int] = None, joints=None, joints_mean=None,
                joints_unit: bool = False, joints_fps=None, rotations=None, rotations_space: str = "local", smooth=None, euler=None,
                euler_unwrap: bool = False, kinematics=None, srgr=None, l1div: bool = False, emotion=None,
-               emotion_stride: Optional[int] = None, diversity_stride: int = 34, bvh_text: bool = False) -> Dict[str, torch.Tensor]:
+               emotion_stride: Optional[int] = None, diversity_stride: int = 34, bvh_text: bool = False, preview=None) -> Dict[str, torch.Tensor]:
     """One gesture track per utterance from raw 16 kHz audio: windows -> mel -> optional CVAE sample per window -> roll-out.
 
     ``models = (generator, vae | None)``, eval mode, on the GPU.  ``audio [U, total_samples]``; ``text [U, W, 60]`` (the words of every
@@ -540,6 +540,13 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     take and ``out["bvh"].write(dir)`` writes one ``.bvh`` per take from one copy of the text.  Refused by name before anything runs:
     ``bvh_text=True`` without ``euler=`` being a ``BvhFile``.
 
+    ``preview=PreviewSpec | dict`` (``preview.PreviewSpec``; with ``joints=``): adds ``"preview"``, stick-figure pictures of every frame of
+    every take, ``uint8 [U, (R,) T', H, W, 3]`` (or ``[..., 3, H, W]`` with ``layout="chw"``): ``preview.render_joints(out["joints"], spec,
+    out["joint_frames"])``, one launch -- of the smoothed joints with ``smooth=`` and at the output rate with ``joints_fps=``, because that is
+    what ``out["joints"]`` holds; all-zero bytes behind a recording's frames.  ``preview.write_y4m`` turns one take into a video stream.
+    Refused by name before anything runs: ``preview=`` without ``joints=``, a spec whose body is not the ``joints=`` body, and an output
+    larger than ``spec.max_bytes``.  Without ``preview`` no key and no launch changes.
+
     ``smooth=Smoother | (window, polyorder)`` (``smooth.Smoother``; a pair is a filter at ``fps``): adds ``"track_smooth"``, the shape of
     ``"track"``: ``smooth.smooth_tracks(out["track"], smooth, frames)``, a Savitzky-Golay filter (``scipy.signal.savgol_filter``,
     ``mode="interp"``) over recording u's own valid poses, zeros behind them, one launch.  ``"track"`` stays raw and ``beat`` / ``diversity`` keep
@@ -578,10 +585,11 @@ def synthesize(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch
     kinematics = _kinematics_arg("synthesize", kinematics, outputs, joints_fps, fps)
     srgr, l1div = _jointscore_args("synthesize", srgr, l1div, outputs, audio)
     bvh_text = _bvh_text_arg("synthesize", bvh_text, euler, joints, joints_fps, fps)
+    preview = _preview_arg("synthesize", preview, outputs)
     return _synthesize("synthesize", models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate,
                        want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=False, kinematics=kinematics,
                        srgr=srgr, l1div=l1div, emotion=emotion, emotion_stride=emotion_stride, diversity_stride=diversity_stride,
-                       bvh_text=bvh_text)
+                       bvh_text=bvh_text, preview=preview)
 
 
 def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose: torch.Tensor, labels: Optional[torch.Tensor] = None, *,
@@ -591,7 +599,7 @@ def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose:
                      audio_rate: Optional[int] = None, joints=None, joints_mean=None, joints_unit: bool = False, joints_fps=None,
                      rotations=None, rotations_space: str = "local", smooth=None, euler=None,
                      euler_unwrap: bool = False, kinematics=None, srgr=None, l1div: bool = False, emotion=None,
-                     emotion_stride: Optional[int] = None, diversity_stride: int = 34, bvh_text: bool = False) -> Dict[str, torch.Tensor]:
+                     emotion_stride: Optional[int] = None, diversity_stride: int = 34, bvh_text: bool = False, preview=None) -> Dict[str, torch.Tensor]:
     """``draws`` = R sampled takes for each of U recordings of any and unequal length, from raw audio, in one call: ``synthesize(lengths=)`` and
     ``synthesize(draws=)`` combined (a VAE is required).  ``audio [U, max_total]`` with ``lengths[u]`` real samples in row u (``None``: every
     row at full length); recording u has ``W_u = ceil(lengths[u] / hop_samples)`` windows, N = sum W_u.  ``text`` padded ``[U, Wmax, 60]`` or
@@ -609,10 +617,11 @@ def synthesize_takes(models, audio: torch.Tensor, text: torch.Tensor, seed_pose:
     kinematics = _kinematics_arg("synthesize_takes", kinematics, outputs, joints_fps, fps)
     srgr, l1div = _jointscore_args("synthesize_takes", srgr, l1div, outputs, audio)
     bvh_text = _bvh_text_arg("synthesize_takes", bvh_text, euler, joints, joints_fps, fps)
+    preview = _preview_arg("synthesize_takes", preview, outputs)
     return _synthesize("synthesize_takes", models, audio, text, seed_pose, labels, hop_samples, n_samples, None, z, alpha, fps, sample_rate,
                        want_windows, want_aux, mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes=True, kinematics=kinematics,
                        srgr=srgr, l1div=l1div, emotion=emotion, emotion_stride=emotion_stride, diversity_stride=diversity_stride,
-                       bvh_text=bvh_text)
+                       bvh_text=bvh_text, preview=preview)
 
 
 def _bvh_text_arg(who, bvh_text, euler, joints, joints_fps, fps):
@@ -623,6 +632,22 @@ def _bvh_text_arg(who, bvh_text, euler, joints, joints_fps, fps):
         raise L.EgError(f"{who}: bvh_text=True needs euler=BvhFile (the text is that file's HIERARCHY and channel layout), got euler="
                         f"{type(euler).__name__}")
     return euler, 1.0 / float(fps if joints_fps is None else joints_fps[1])
+
+
+def _preview_arg(who, preview, outputs):
+    """The ``preview=`` argument of `synthesize` / `synthesize_takes`, checked before anything runs: the PreviewSpec, whose body is the
+    ``joints=`` body, or None."""
+    if preview is None:
+        return None
+    if outputs is None:
+        raise L.EgError(f"{who}: preview= without joints= (the pictures are those of out[\"joints\"], in metres)")
+    from .preview import PreviewSpec
+    spec = PreviewSpec.of(preview, f"{who}: preview")
+    if spec.body is not outputs.body and spec.body != outputs.body:
+        raise L.EgError(f"{who}: preview=: the spec draws {spec.body!r}, joints= is {outputs.body!r}: the bones must name the joints that "
+                        "out[\"joints\"] holds")
+    spec.check(outputs.body.J)
+    return spec
 
 
 def _kinematics_arg(who, kinematics, outputs, joints_fps, fps):
@@ -746,7 +771,7 @@ def _track_outputs(who, seed_pose, *args):
 
 def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samples, windows, z, alpha, fps, sample_rate, want_windows, want_aux,
                 mel, lengths, draws, beat, diversity, audio_rate, outputs, smooth, takes, kinematics=None, srgr=None, l1div=False, emotion=None,
-                emotion_stride=None, diversity_stride=34, bvh_text=None):
+                emotion_stride=None, diversity_stride=34, bvh_text=None, preview=None):
     """The body of `synthesize` and `synthesize_takes` (`who` names the caller in errors): argument checks, resampling, the roll-out of the
     call's kind, then the per-track extras.  `outputs`: the caller's checked output stage (`_track_outputs`)."""
     gen, vae = models
@@ -787,14 +812,18 @@ def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samp
         from . import resample as RS
         if lengths is not None:
             lengths = int_list(lengths)
-    if srgr is not None:                                                                  # the targets' T' against the track this call will make
+    if srgr is not None or preview is not None:                                           # T' of the track this call will make: the targets' and the pictures'
         from .skeleton import out_frames
         hop = int(round((c.frames - c.prior_frames) * sample_rate / fps)) if hop_samples is None else int(hop_samples)      # _front_end's
         at_model_rate = (lambda v: RS.out_length(v, int(audio_rate), int(sample_rate))) if resampled else int
         most = max(-(-at_model_rate(v) // hop) for v in int_list(lengths)) if lengths is not None else (
             int(text.shape[1]) if windows is None and text.dim() == 3 else windows)
-        if most is not None and most >= 1:
-            srgr.fit(who, T=out_frames(most * (c.frames - c.prior_frames) + c.prior_frames, outputs.fps))
+        if most is not None and most >= 1:                                               # otherwise the call is refused below ("windows=None"): nothing runs
+            t_out = out_frames(most * (c.frames - c.prior_frames) + c.prior_frames, outputs.fps)
+            if srgr is not None:
+                srgr.fit(who, T=t_out)
+            if preview is not None:
+                preview.fit(int(U) * (1 if draws is None else max(1, int(draws))), t_out, f"{who}: preview=")
     if resampled:
         with torch.no_grad():
             audio = RS.resample_audio(audio, int(audio_rate), int(sample_rate), lengths=lengths)
@@ -845,6 +874,10 @@ def _synthesize(who, models, audio, text, seed_pose, labels, hop_samples, n_samp
     if bvh_text is not None:                                                              # the MOTION lines of every take, made on the device
         bvh_file, frame_time = bvh_text
         out["bvh"] = bvh_file.format_tracks(out["euler"], frames=out["joint_frames"], joints=outputs.body.names, frame_time=frame_time)
+    if preview is not None:                                                               # the pictures of out["joints"], one launch
+        from .preview import render_joints
+        with torch.no_grad():
+            out["preview"] = render_joints(out["joints"], preview, out["joint_frames"])
     if kinematics is not None:                                                            # of out["joints"]: the smoothed ones with smooth=
         from . import kinematics as KN
         with torch.no_grad():

@@ -744,6 +744,56 @@ int eg_bvh_text_measure(const EgBvhTextArgs* in, void* workspace, int64_t worksp
 int eg_bvh_text_write(const EgBvhTextArgs* in, const int64_t* line_off, void* text, int64_t text_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Preview frames: stick figures of whole takes, one 8-bit picture per frame, drawn on the device (csrc/preview.hip)
+ * ------------------------------------------------------------------------------------------ */
+/* joints [rows, T, J, 3] fp32 -> out [rows, T, H, W, 3] (layout EG_PREVIEW_HWC) or [rows, T, 3, H, W] (EG_PREVIEW_CHW) uint8.  Rows: "Rows of
+ * whole tracks", no minimum: a frame t >= n is all-zero bytes and its joints are never read.
+ * Bones.  `bones`: n_bones pairs (ja, jb) of joint indices on the HOST, 1 <= n_bones <= EG_PREVIEW_MAX_BONES, every index in [0, J);
+ * eg_preview_check (host only, no HIP call, usable without a GPU) refuses anything else by name.  d_table, the device copy, is
+ * EG_PREVIEW_TABLE_WORDS 32-bit words, 16-byte aligned:
+ *     [0] n_bones | [1] n_used | [2] background (r | g << 8 | b << 16) | [3] 0 | used [128]: the distinct joints the bones name, ascending |
+ *     a [64], b [64]: the two ends of bone k as positions in `used` | colour [64] (packed as the background)
+ * Nothing ties the upload to the host list: the kernel clamps what it reads from d_table, so with an upload that differs the picture is
+ * unspecified and every access stays in range.  The three channels are bytes to the device, whatever colour space the caller means.
+ * Camera.  `camera`: 8 fp32 on the HOST, read at the call and passed by value -- M00 M01 M02 M10 M11 M12 c0 c1.
+ * One frame.  Every + - x below is one IEEE fp32 operation in the order written (no fused multiply-add); the square root and the reciprocal
+ * are correctly rounded; a comparison with a NaN is false.
+ *     u_j = ((M00 x_j + M01 y_j) + M02 z_j) + c0,   v_j = ((M10 x_j + M11 y_j) + M12 z_j) + c1         per joint the bones name
+ *     picture = background;  per bone k = (ja, jb), in the order of `bones`:
+ *         ax, ay = u_ja, v_ja;  ex = u_jb - ax;  ey = v_jb - ay;  l2 = ex ex + ey ey;  inv = l2 > 0 ? 1 / l2 : 0
+ *         per pixel (px, py), X = px + 0.5, Y = py + 0.5:
+ *             wx = X - ax;  wy = Y - ay;  s = (wx ex + wy ey) inv;  t = s < 0 ? 0 : s;  t = t > 1 ? 1 : t          (a NaN stays a NaN)
+ *             dx = wx - t ex;  dy = wy - t ey;  a = (radius + 0.5) - sqrt(dx dx + dy dy)
+ *             q = a >= 1 ? 255 : a > 0 ? (int)(a 255 + 0.5) : 0                                                     (a NaN: q = 0)
+ *             every channel:  c = (c (255 - q) + colour[k] q + 127) / 255                                          in integers
+ * Later bones paint over earlier ones; a bone of zero length is a disc; a bone with an end that is not finite draws nothing (every q is 0).
+ * eg_preview_raster: one launch on `stream`, one workgroup per (frame, band of image rows).  The frame's projected joints and bone
+ * parameters are made once per workgroup in LDS, and the workgroup keeps the list of the bones whose bounding box -- grown by radius + 1
+ * and by 2^-20 of the largest coordinate, more than the rounding of the formula can move a pixel's distance -- touches its rows; a wave
+ * composites a block of the band in LDS, walking only the boxes of the listed bones, and every thread then stores 16 consecutive pixels of
+ * a row with 16-byte stores (W not a multiple of 16: the same bytes through stores that assume no alignment, and a narrower tail).  The
+ * picture is that of the formula, not of the boxes.  No allocation, no synchronisation, no atomics, no
+ * memset; the grid depends on (rows, T, H, W) only, so the call captures into a hipGraph.  A row's pictures do not depend on rows, on its
+ * place in the batch or on T.  Refuses by name before the launch: null pointers, joints / out / d_table not 16-byte aligned, rows, T or J < 1,
+ * a bad bones list (as eg_preview_check), H or W outside EG_PREVIEW_MIN_SIZE .. EG_PREVIEW_MAX_SIZE, a radius outside
+ * EG_PREVIEW_MIN_RADIUS .. EG_PREVIEW_MAX_RADIUS (or NaN), a camera entry that is not finite, an unknown layout, rows not a multiple of draws,
+ * frame_unit < 1, d_frames not 4-byte aligned, grid / index range.
+ * eg_preview_max_bones: EG_PREVIEW_MAX_BONES. */
+#define EG_PREVIEW_MAX_BONES 64
+#define EG_PREVIEW_MIN_SIZE 8
+#define EG_PREVIEW_MAX_SIZE 2048
+#define EG_PREVIEW_MIN_RADIUS 0.25f
+#define EG_PREVIEW_MAX_RADIUS 16.0f
+#define EG_PREVIEW_TABLE_WORDS 324  /* 4 + 2 * EG_PREVIEW_MAX_BONES + 3 * EG_PREVIEW_MAX_BONES */
+#define EG_PREVIEW_HWC 0
+#define EG_PREVIEW_CHW 1
+int32_t eg_preview_max_bones(void);
+int eg_preview_check(const int32_t* bones, int32_t n_bones, int32_t J);
+int eg_preview_raster(const float* joints, int32_t rows, int32_t T, int32_t J, const int32_t* bones, int32_t n_bones, const int32_t* d_table,
+                      const float* camera, float radius, int32_t H, int32_t W, int32_t layout, int32_t draws, int32_t frame_unit,
+                      const int32_t* d_frames, uint8_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Smoothed output: a Savitzky-Golay filter along the time axis of whole tracks on the device (csrc/smooth.hip)
  * ------------------------------------------------------------------------------------------ */
 /* A filter is (window K, polyorder p, deriv d, delta): K odd, 3 <= K <= EG_SMOOTH_MAX_WINDOW; 1 <= p <= min(5, K - 1); 0 <= d <= min(2, p);

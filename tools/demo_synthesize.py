@@ -46,7 +46,10 @@ shapes, how far the deepest joint travels and the largest rotation angle.
 With --bvh FILE --bvh-out DIR the call also returns the Euler channels of every joint in the file's own channel orders (euler=BvhFile,
 euler_unwrap=True: one more launch and the Euler filter's three) and the script writes DIR/recording_U[_take_R].bvh -- the file's HIERARCHY,
 then the generated MOTION at the joints' frame rate -- one file per recording and take, formatted on the device in one call (bvh.BvhFile.write_tracks).
-usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--bvh FILE [--bvh-joints A,B,...] [--bvh-out DIR]] [--joints-fps N] [--rotations]] [--smooth K P] [--kinematics] [--srgr] [--l1div] [--emotion] [--out tracks.npz]"""
+With --joints --preview DIR [--preview-size H W] (default 240 320) the call also returns stick-figure pictures of every frame (preview=: one more
+launch; Y, Cb, Cr planes) and the script writes DIR/recording_U[_take_R].y4m, uncompressed YUV4MPEG2 that players and encoders read, and prints
+the encoder command that would mux a file with its audio (it does not run it).
+usage: demo_synthesize.py [utterances=4] [seconds=60] [--draws R] [--beat] [--diversity] [--audio-rate HZ] [--joints [--bvh FILE [--bvh-joints A,B,...] [--bvh-out DIR]] [--joints-fps N] [--rotations] [--preview DIR [--preview-size H W]]] [--smooth K P] [--kinematics] [--srgr] [--l1div] [--emotion] [--out tracks.npz]"""
 import os
 import sys
 import time
@@ -63,6 +66,7 @@ from emotiongestures_amd.synth import load_synth_weights, synth_audio
 
 argv, DRAWS, OUT, BEAT, DIVERSITY, RATE, JOINTS, JOINTS_FPS, ROTATIONS, SMOOTH = [], 0, None, False, False, 16000, False, None, False, None
 BVH, BVH_JOINTS, BVH_OUT, KINEMATICS, SRGR, L1DIV, EMOTION = None, None, None, False, False, False, False
+PREVIEW, PREVIEW_SIZE = None, (240, 320)
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--draws":
@@ -97,6 +101,10 @@ for a in it:
         L1DIV = True
     elif a == "--emotion":
         EMOTION = True
+    elif a == "--preview":
+        PREVIEW = next(it)
+    elif a == "--preview-size":
+        PREVIEW_SIZE = (int(next(it)), int(next(it)))
     else:
         argv.append(a)
 if DIVERSITY and DRAWS < 2:
@@ -107,6 +115,8 @@ if BVH_OUT and not BVH:
     sys.exit("--bvh-out needs --bvh FILE (the written files repeat that file's HIERARCHY)")
 if JOINTS_FPS and not JOINTS:
     sys.exit("--joints-fps needs --joints")
+if PREVIEW and not JOINTS:
+    sys.exit("--preview needs --joints (the pictures are those of the joints)")
 if ROTATIONS and not JOINTS:
     sys.exit("--rotations needs --joints (the rest pose belongs to the skeleton's bones)")
 if KINEMATICS and (not JOINTS or BEAT):
@@ -132,6 +142,32 @@ audio = torch.from_numpy(synth_audio(U, total_in, seed=90)).to(dev)
 text = torch.zeros(U, W, 60, dtype=torch.int64, device=dev)
 seed_pose = torch.zeros(U, PRIOR, POSE_DIM, device=dev)
 labels = torch.nn.functional.one_hot(torch.arange(U) % 8, 8).float().to(dev)     # one emotion per recording
+
+
+
+def write_previews(jo, spec, dt_with):
+    """--preview: one .y4m per recording and take from jo["preview"], and the command that would mux the first with its audio."""
+    from emotiongestures_amd import preview as PV_
+    os.makedirs(PREVIEW, exist_ok=True)
+    pics, rate = jo["preview"], JOINTS_FPS or FPS
+    takes = pics if pics.dim() == 6 else pics[:, None]                     # [U, R, T', 3, H, W]
+    t0 = time.perf_counter()
+    names, nbytes = [], 0
+    for u in range(takes.shape[0]):
+        for r in range(takes.shape[1]):
+            names.append(os.path.join(PREVIEW, f"recording_{u}" + (f"_take_{r}" if pics.dim() == 6 else "") + ".y4m"))
+            nbytes += PV_.write_y4m(names[-1], takes[u, r], rate, n=jo["joint_frames"][u], spec=spec)
+    print(f"--preview: preview {tuple(pics.shape)} uint8 (Y, Cb, Cr planes), one more launch in the call ({1e3 * dt_with:.2f} ms); {len(names)} files, "
+          f"{nbytes / 1e6:.1f} MB, written to {PREVIEW} in {time.perf_counter() - t0:.2f} s; to mux one with its audio (YOUR_AUDIO.wav: the "
+          f"recording it was made from, which this script does not write):\n"
+          f"  ffmpeg -i {names[0]} -i YOUR_AUDIO.wav -c:v libx264 -pix_fmt yuv420p -shortest {os.path.splitext(names[0])[0]}.mp4")
+
+
+def preview_spec(body):
+    from emotiongestures_amd import preview as PV_
+    return PV_.PreviewSpec(body, *PREVIEW_SIZE, camera=PV_.Camera.orbit(span=1.4, height=PREVIEW_SIZE[0], width=PREVIEW_SIZE[1]), layout="chw",
+                           colorspace="ycbcr")
+
 
 gen = build_mirror("spatial", FRAMES, POSE_DIM, PRIOR, PRIOR, seed=7, precision="bf16x3").to(dev)
 vae = load_synth_weights(MLP_Reconstruct_v3(frames=FRAMES), 7).eval().to(dev)
@@ -165,6 +201,8 @@ if JOINTS and BEAT:
         from emotiongestures_amd import bvh as BVH_
         bvh_file = BVH_.read(BVH)
         jk.update(euler=bvh_file, euler_unwrap=True)
+    if PREVIEW:
+        jk["preview"] = preview_spec(tree)
     H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, **jk, **AR)          # warm-up (uploads the level table)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -177,6 +215,8 @@ if JOINTS and BEAT:
     print(f"--joints: {tree!r}{' from ' + BVH if BVH else ' (synthetic)'}: joints {tuple(joints.shape)} (frames per recording {jo['joint_frames']}" +
           (f", {FPS} -> {JOINTS_FPS} fps" if JOINTS_FPS else "") + f"), one more launch in the call ({1e3 * dt_j:.2f} ms against {1e3 * dt:.2f} ms); "
           f"extent of joint {deep}{' ' + tree.names[deep] if tree.names else ''} ({int(tree.depth[deep])} joints from the root): {float(extent):.3f} m")
+    if PREVIEW:
+        write_previews(jo, jk["preview"], dt_j)
     if SMOOTH:
         print(f"--smooth {SMOOTH[0]} {SMOOTH[1]}: the joints come from track_smooth {tuple(jo['track_smooth'].shape)}: Gram-Schmidt re-orthonormalises "
               "the filtered 6-D rows")
@@ -206,6 +246,8 @@ elif JOINTS:
         sem = ((torch.arange(tj.shape[1], device=dev) // (JOINTS_FPS or FPS)) % 3 == 0).float()[None].expand(U, -1).contiguous()
         jk["srgr"] = SemanticTargets(tj, sem, threshold=0.02)
     jk["l1div"] = L1DIV
+    if PREVIEW:
+        jk["preview"] = preview_spec(jk["joints"])
     H.synthesize((gen, vae), audio, text, seed_pose, labels=labels, z=z, **jk, **AR)          # warm-up (uploads the bone table)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -217,6 +259,8 @@ elif JOINTS:
     print(f"--joints: joints {tuple(joints.shape)} (frames per recording {jo['joint_frames']}" +
           (f", {FPS} -> {JOINTS_FPS} fps" if JOINTS_FPS else "") + f"), one more launch in the call ({1e3 * dt_j:.2f} ms against {1e3 * dt:.2f} ms); "
           f"wrist extent: left {float(extent(6)):.3f} m, right {float(extent(7)):.3f} m")
+    if PREVIEW:
+        write_previews(jo, jk["preview"], dt_j)
     if SMOOTH:                                           # the joints above come from out["track_smooth"]; the raw track's for comparison
         from emotiongestures_amd.skeleton import joints_from_tracks
         raw = joints_from_tracks(jo["track"], jk["joints"], unit=True, fps=jk["joints_fps"])
